@@ -10,9 +10,11 @@ the masks of the V/N views it "produced" and each step all-gathers the masks ove
 one exchange step, double-buffered: the all-gather of step i+1 runs under the kernels of step i)
 and then fuses its shard.  --weak gives every rank its own --points instead.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--points P] [--filter] [--masks iid|block64] [--weak]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--points P] [--filter] [--masks iid|block64] [--weak] [--dump-outputs DIR]
 
-Prints ONE JSON line on rank 0 (see README/DESIGN.md for the fields).
+Prints ONE JSON line on rank 0 (see README/DESIGN.md for the fields); `ms_per_step` = wall milliseconds of one of the K
+timed steps.  --dump-outputs DIR writes the labels of the last timed step as .npy (the inputs are seeded: two builds run
+with the same arguments can be compared output for output).
 """
 import argparse
 import json
@@ -61,7 +63,13 @@ def parse():
     ap.add_argument('--prepared', action='store_true', help='cell-sort once outside the timed loop and keep the sorted cloud resident')
     ap.add_argument('--overlap-sort', action='store_true', help='sort the cloud of step i+1 on a second stream while step i is fused (measured: no '
                     'gain, 1.43 vs 1.39 ms -- the fused kernel holds every wave slot of the chip, the sort kernels queue behind it)')
-    return ap.parse_args()
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='after the timed steps, write the labels of the last timed step to DIR/*.npy (float32; see dump_outputs); '
+                         'bench_out/ is git-ignored')
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error('--steps must be at least 1')
+    return args
 
 
 THRESHOLD = float(os.environ.get('F3D_BENCH_THRESHOLD', '0.5'))      # (experiments only: the headline is BASELINE's 0.5)
@@ -77,6 +85,34 @@ def fuse_instance(labels_present, flt):
     if codes <= 100:
         return f'{codes} codes: packed 8-bit bins, view tables in global memory (<= 100 codes)'
     return f'{codes} codes: packed 8-bit bins, any alphabet'
+
+
+DUMP_LIMIT_BYTES = 64_000_000         # --dump-outputs: at most this many bytes in all (over every rank)
+DUMP_SAMPLE_SEED = 4321
+
+
+def dump_outputs(out_dir, labels, rank, world, lo):
+    """--dump-outputs: the per-point labels [n] int64 the timed step returned to its caller, as float32 (0..133 are exact).
+    With one rank: DIR/labels.npy.  With N ranks every rank writes its share of the cloud, DIR/labels_rank<r>.npy.  When the
+    labels exceed this rank's share of DUMP_LIMIT_BYTES, a fixed seeded sample of point indices is written instead, beside
+    DIR/labels_index[_rank<r>].npy (float64 point indices into the cloud, sorted; with --weak, into this rank's own cloud)."""
+    out_dir = Path(out_dir)
+    out_dir.mkdir(parents=True, exist_ok=True)
+    suffix = '' if world == 1 else f'_rank{rank}'
+    n = len(labels)
+    budget = DUMP_LIMIT_BYTES // world
+    files = {}
+    if n * 4 <= budget:
+        files[f'labels{suffix}'] = labels.astype(np.float32)
+    else:
+        k = budget // (4 + 8)                       # float32 label + float64 index per sampled point
+        idx = np.sort(np.random.default_rng([DUMP_SAMPLE_SEED, rank]).choice(n, k, replace=False))
+        files[f'labels{suffix}'] = labels[idx].astype(np.float32)
+        files[f'labels_index{suffix}'] = (idx + lo).astype(np.float64)
+    for name, arr in files.items():
+        np.save(out_dir / f'{name}.npy', arr)
+    return dict(dir=str(out_dir), files=sorted(f'{k}.npy' for k in files), points=n,
+                sampled=len(files) > 1, bytes=int(sum(a.nbytes for a in files.values())))
 
 
 def algorithmic_bytes(n, v, h, w, xyz_bytes):
@@ -581,6 +617,7 @@ def main():
         step()
     fence()
     elapsed = time.perf_counter() - t0
+    dumped = dump_outputs(args.dump_outputs, classes.cpu().numpy(), rank, world, lo) if args.dump_outputs else None   # before anything else writes `classes`
     if use_dist:
         tt = torch.tensor([elapsed], dtype=torch.float64, device=dev)
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
@@ -665,6 +702,8 @@ def main():
                                exchange='none' if not use_dist else (f'RCCL all_gather of {V // world} masks/rank per step, double-buffered and overlapped with the previous step' if not chunked else
                                                                      f'RCCL all_reduce(MAX) of the label-presence bytes + {args.chunks} all_gathers of {V // world // args.chunks} {"CODED " if coded_x else ""}masks/rank per step; chunk c+1 on the wire while chunk c votes (vote state carried in HBM)' + (' -- each rank codes only its own masks' if coded_x else ''))),
                    roofline=roofline)
+        if dumped is not None:
+            out['dumped_outputs'] = dumped
 
     # secondary, HBM-streaming kernels of the same path (not part of `value`)
     if rank == 0 and world == 1 and not args.no_extras:
