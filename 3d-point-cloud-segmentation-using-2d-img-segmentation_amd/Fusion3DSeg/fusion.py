@@ -8,9 +8,12 @@ frustum and projects the survivors (rows a3, a4, a2 -- here ONE launch of the si
 greedily matches depth patches to those points and down-samples what is left (``patch_downsample``).  The greedy part is
 a chain of data-dependent decisions (every match removes pixels from later candidates) and runs on the host, as in the
 reference; it draws its shuffles from NumPy's global generator at the same places, so a seeded run reproduces the
-reference's output (tests/golden/fuse.npz).
+reference's output (tests/golden/fuse.npz).  ``Fusion.fuse_device`` is the same loop with the cloud, the frames and the lookups resident on the
+GPU (opt-in; bit-identical to ``fuse``).
 """
 import pickle
+import time
+from fractions import Fraction
 from pathlib import Path
 
 import numpy as np
@@ -114,6 +117,58 @@ def _row_norms(rows):
     return np.sqrt(sq)
 
 
+def _fma(a, b, c):
+    """a * b + c rounded once (exact rational arithmetic, then one rounding to float64)."""
+    return float(Fraction(a) * Fraction(b) + Fraction(c))
+
+
+def _norm_probe_vectors(n=64, seed=20260917):
+    """Vectors on which the plain order (x*x + y*y) + z*z and the FMA chain fma(z,z, fma(y,y, x*x)) round differently."""
+    rng = np.random.default_rng(seed)
+    out = []
+    while len(out) < n:
+        x, y, z = (float(c) for c in rng.normal(size=3))
+        if (x * x + y * y) + z * z != _fma(z, z, _fma(y, y, x * x)):
+            out.append((x, y, z))
+    return np.array(out)
+
+
+def _classify_dot(values, vectors):
+    """Which order produced `values` = v.dot(v) of every probe vector: f3d.NORM_FMA, f3d.NORM_PLAIN, or f3d.NORM_HOST (neither)."""
+    values = np.asarray(values, np.float64)
+    fma = np.array([_fma(z, z, _fma(y, y, x * x)) for x, y, z in vectors])
+    plain = (vectors[:, 0] * vectors[:, 0] + vectors[:, 1] * vectors[:, 1]) + vectors[:, 2] * vectors[:, 2]
+    if np.array_equal(values, fma):
+        return f3d.NORM_FMA
+    if np.array_equal(values, plain):
+        return f3d.NORM_PLAIN
+    return f3d.NORM_HOST
+
+
+def _probe_norm_mode(dot=None):
+    """The order in which this process's NumPy takes the 1-D ``v.dot(v)`` of ``_row_norms`` (BLAS ddot: the kernel OpenBLAS picks for
+    the CPU decides it), as the mode the fusion kernels take: both that dot and ``np.vecdot`` (which ``_row_norms`` uses for long
+    inputs) must agree with one order, else NORM_HOST (the host normalises).  ``dot``: classify that function instead."""
+    vectors = _norm_probe_vectors()
+    if dot is not None:
+        return _classify_dot([dot(v) for v in vectors], vectors)
+    mode = _classify_dot([v.dot(v) for v in vectors], vectors)
+    fast = getattr(np, 'vecdot', None)
+    if fast is not None and _classify_dot(fast(vectors, vectors), vectors) != mode:
+        return f3d.NORM_HOST
+    return mode
+
+
+_NORM_MODE = []
+
+
+def _norm_mode():
+    """``_probe_norm_mode()``, probed once per process."""
+    if not _NORM_MODE:
+        _NORM_MODE.append(_probe_norm_mode())
+    return _NORM_MODE[0]
+
+
 def _mergeable(seed_pt, seed_normal, cand_pts, cand_normals, max_distance, min_cosine):
     """The reference's merge criterion (:165-170, :223-228): closer than max_distance AND normals within the angle."""
     near = np.linalg.norm(cand_pts - seed_pt[None, :], axis=-1) < max_distance
@@ -132,7 +187,10 @@ class Fusion:
     @classmethod
     def from_frames(cls, K, w, h, wxyzs, translations, frames, lookup_dir=None, lookup_sink=None):
         """The same object without the file readers: ``frames[i]`` = (name, points, normals, colours, valid).  Per-frame
-        lookups go to ``lookup_dir`` (as .npy, like the reference) and/or to ``lookup_sink(name, uv2pt)``."""
+        lookups go to ``lookup_dir`` (as .npy, like the reference) and/or to ``lookup_sink(name, uv2pt)``: a NumPy int32 [h*w] from
+        ``fuse``; from ``fuse_device`` a fresh int32 CUDA tensor [h*w], what ``f3d_vote_uv2pt_batch_dev`` consumes (complete once
+        ``fuse_device`` has returned, in the order of the caller's stream).  ``fuse_device`` also accepts frames of torch device
+        tensors."""
         self = object.__new__(cls)
         self._setup(K, w, h, wxyzs, translations, frames, lookup_dir is not None or lookup_sink is not None, lookup_dir)
         self._lookup_sink = lookup_sink
@@ -301,6 +359,45 @@ class Fusion:
                 self._save_uv2pt(uv2pt, name)
         return pts, nrm, clr, nmerges, occurences
 
+    def fuse_device(self, radius=0.05, angle=10, stride=None, max_depth=10, skip=1, verbose=False):
+        """``fuse`` with the cloud and the lookups resident on the GPU -> (points, normals, colours float64 [M,3], nmerges int64 [M],
+        occurences uint32 [M]) as torch tensors on the context's device, bit-identical to what ``fuse`` returns on the same frames
+        under the same seeded global NumPy generator (lookups and the generator's final state included).
+
+        Frames: ``self.frames[i]`` may hold NumPy arrays (uploaded once per frame through a pinned staging buffer) or torch device
+        tensors (points / normals / colours float64 [h*w,3] contiguous, valid bool or uint8 [h*w]), used in place.  The frame's
+        ``valid`` is copied into a free-pixel buffer of this call and never written; ``fuse`` instead consumes the frame's mask in
+        place.  Lookups: ``lookup_dir`` gets the same .npy bytes as ``fuse`` writes; ``lookup_sink(name, uv2pt)`` gets a fresh int32
+        device tensor [h*w] per frame (what ``f3d_vote_uv2pt_batch_dev`` consumes).
+
+        Work goes on the caller's current torch stream (a side stream ordered behind it when that is the null stream); the caller's
+        stream waits for it before this returns.  Per frame the host still sees: the shuffle (drawn on the host from the global
+        generator, h*w int64 uploaded, drawn while the GPU matches); two small readbacks (hits / valid pixels / cloud rows after the
+        projection, free pixels / sequential flag after the matching); the per-round counter of the seed resolution; the frame upload
+        for NumPy frames; the lookups when written to disk.  Nothing per seed or per pixel comes back, except on the two host paths
+        counted in ``self.fuse_device_stats``: frames patch_downsample hands to its sequential loop ('sequential_frames'), and rows
+        normalised on the host when this process's BLAS dot matches neither kernel order ('host_normalised')."""
+        ctx = f3d.default_context()
+        import torch
+        if not torch.cuda.is_available():
+            raise f3d.F3DUnavailable('Fusion.fuse_device needs a HIP device; there is no CPU fallback')
+        dev = torch.device('cuda', ctx.device)
+        caller = torch.cuda.current_stream(dev)
+        work = caller
+        if caller.cuda_stream == 0:                                           # never hand the null stream to the library
+            work = torch.cuda.Stream(dev)
+            work.wait_stream(caller)
+        try:
+            with torch.cuda.device(dev), torch.cuda.stream(work):
+                out = _DeviceFusion(self, ctx, torch, dev, work, caller).run(radius, angle, stride, max_depth, skip, verbose)
+        finally:
+            if work is not caller:
+                caller.wait_stream(work)
+        if work is not caller:
+            for t in out:
+                t.record_stream(caller)
+        return out
+
     def _save_uv2pt(self, uv2pt, frame_name):
         if self.uv2pt_dir is not None:
             np.save(Path(self.uv2pt_dir) / f'{frame_name}.npy', uv2pt)
@@ -345,3 +442,218 @@ class Fusion:
             with open(dirname / 'fusion' / 'adj.pkl', 'rb') as fp:
                 adj = pickle.load(fp)
         return [d['points'], d['normals'], d['colors'], d['nmerges'], d['occurences'], d['nframes'], d['depth_hw'], adj]
+
+
+class _DeviceFusion:
+    """One call of Fusion.fuse_device: the resident cloud (capacity doubling), the per-frame buffers and the frame loop."""
+
+    def __init__(self, fu, ctx, torch, dev, stream, caller):
+        self.fu, self.ctx, self.torch, self.dev, self.stream, self.sh = fu, ctx, torch, dev, stream, stream.cuda_stream
+        self.caller = caller
+        self.h, self.w, self.npx = fu.h, fu.w, fu.npts
+        self.mode = _norm_mode()
+        self.stats = fu.fuse_device_stats = {'frames': 0, 'sequential_frames': 0, 'host_normalised': 0, 'rounds': 0,
+                                             'shuffle_s': 0.0, 'draws_undone': 0, 'capacity_growths': 0}
+        T, n = torch, self.npx
+        self.cap = 0
+        self.count_dev = T.zeros(1, dtype=T.int64, device=dev)
+        self.free = T.zeros(n, dtype=T.uint8, device=dev)
+        self.owner = T.empty(n, dtype=T.int32, device=dev)
+        self.prio = T.empty(n, dtype=T.int32, device=dev)
+        self.order = T.empty(n, dtype=T.int64, device=dev)
+        self.px_sums = T.empty((n, 9), dtype=T.float64, device=dev)
+        self.px_counts = T.empty(n, dtype=T.int32, device=dev)
+        self.stats_dev = T.zeros(3, dtype=T.int64, device=dev)
+        self.check_dev = T.zeros(2, dtype=T.int64, device=dev)
+        self.stage = [T.empty((n, 3), dtype=T.float64).pin_memory() for _ in range(3)] + [T.empty(n, dtype=T.uint8).pin_memory()]
+        self.order_stage = T.empty(n, dtype=T.int64).pin_memory()
+        self.frame_buf = [T.empty((n, 3), dtype=T.float64, device=dev) for _ in range(3)] + [T.empty(n, dtype=T.uint8, device=dev)]
+
+    # ---------------------------------------------------------------- storage
+    def reserve(self, rows):
+        """Capacity for `rows` cloud rows (doubling, device-to-device copy of what is there)."""
+        if rows <= self.cap:
+            return
+        T, dev = self.torch, self.dev
+        cap = max(rows, 2 * self.cap, 4096)
+        new = [T.zeros((cap, 3), dtype=T.float64, device=dev) for _ in range(3)] + [T.zeros(cap, dtype=T.int64, device=dev)]
+        occ = T.zeros(cap, dtype=T.int32, device=dev)                     # uint32 bits (returned as a uint32 view)
+        if self.cap:
+            for a, b in zip(new + [occ], self.cloud + [self.occ]):
+                a[:self.cap].copy_(b)
+            self.stats['capacity_growths'] += 1
+        self.cloud, self.occ, self.cap = new, occ, cap
+        self.uv_all = T.empty((2, cap), dtype=T.int32, device=dev)
+        self.inside = T.empty(cap, dtype=T.uint8, device=dev)
+        self.ids = T.empty(cap, dtype=T.int32, device=dev)
+        self.uv = T.empty(2 * cap, dtype=T.int32, device=dev)
+        self.hit_pts = T.empty((cap, 3), dtype=T.float64, device=dev)
+        self.hit_nrm = T.empty((cap, 3), dtype=T.float64, device=dev)
+        self.sums = T.empty((cap, 9), dtype=T.float64, device=dev)
+        self.counts = T.empty(cap, dtype=T.int32, device=dev)
+
+    def cloud_ptrs(self):
+        return tuple(t.data_ptr() for t in self.cloud + [self.occ])
+
+    # ---------------------------------------------------------------- frames
+    def frame(self, j):
+        """(name, points, normals, colours, valid uint8) on the device, plus the host arrays of a NumPy frame (else None)."""
+        T = self.torch
+        name, pts, nrm, clr, valid = self.fu.frames[j]
+        if isinstance(pts, T.Tensor):
+            for t in (pts, nrm, clr):
+                if t.device != self.dev or t.dtype != T.float64 or tuple(t.shape) != (self.npx, 3) or not t.is_contiguous():
+                    raise ValueError(f'fuse_device: frame tensors must be float64 [{self.npx},3] contiguous on {self.dev}')
+            if valid.device != self.dev or valid.dtype not in (T.bool, T.uint8) or valid.numel() != self.npx or not valid.is_contiguous():
+                raise ValueError(f'fuse_device: valid must be bool or uint8 [{self.npx}] on {self.dev}')
+            return name, pts, nrm, clr, valid.reshape(-1).view(T.uint8), None
+        host = [np.asarray(pts, np.float64).reshape(self.npx, 3), np.asarray(nrm, np.float64).reshape(self.npx, 3),
+                np.asarray(clr, np.float64).reshape(self.npx, 3), np.asarray(valid).reshape(self.npx)]
+        for src, stage, buf in zip(host, self.stage, self.frame_buf):      # the previous upload has completed (a readback followed it)
+            np.copyto(stage.numpy(), src, casting='unsafe')
+            buf.copy_(stage, non_blocking=True)
+        return (name, *self.frame_buf, host)
+
+    def draw(self):
+        """np.random.shuffle(np.arange(h*w)) of the global generator, into the pinned staging buffer."""
+        t0 = time.perf_counter()
+        order = self.order_stage.numpy()
+        order[:] = np.arange(self.npx)
+        np.random.shuffle(order)
+        self.stats['shuffle_s'] += time.perf_counter() - t0
+        return order
+
+    # ---------------------------------------------------------------- steps
+    def host_normalise(self, rows):
+        """Normals of the given cloud rows (device int64 tensor) normalised with _row_norms on the host."""
+        if not len(rows):
+            return
+        nrm = self.cloud[1]
+        ns = nrm[rows].cpu().numpy()
+        nrm[rows] = self.torch.from_numpy(ns / _row_norms(ns)[:, None]).to(self.dev)
+        self.stats['host_normalised'] += len(ns)
+
+    def downsample(self, order, frame, half, radius, min_cosine, fallback, nfree, count, uv2pt):
+        """patch_downsample of the frame's `nfree` free pixels, appended to the cloud at row `count` -> the new row count (or a bound)."""
+        T, ctx, sh, h, w, npx = self.torch, self.ctx, self.sh, self.h, self.w, self.npx
+        name, dp, dn, dc, dv, host = frame
+        self.reserve(count + npx)
+        if fallback:                                                         # the reference's own order of events, on the host
+            self.stats['sequential_frames'] += 1
+            if host is None:
+                host = [dp.cpu().numpy(), dn.cpu().numpy(), dc.cpu().numpy()]
+            free = self.free.cpu().numpy().astype(bool).reshape(h, w)
+            fu = self.fu
+            with np.errstate(all='ignore'):
+                n_pts, n_nrm, n_clr, n_uv, n_mrg = Fusion._patch_downsample_sequential(
+                    order, host[0], host[1], host[2], h, w, half, radius, min_cosine, fu.pcdimg, fu.pt2u, fu.pt2v, free)
+            k = len(n_mrg)
+            if k:
+                for buf, rows in zip(self.cloud[:3], (n_pts, n_nrm, n_clr)):
+                    buf[count:count + k].copy_(T.from_numpy(np.ascontiguousarray(rows, np.float64).reshape(k, 3)))
+                self.cloud[3][count:count + k].copy_(T.from_numpy(np.asarray(n_mrg, np.int64)))
+                self.occ[count:count + k].fill_(1)
+            fresh = T.from_numpy(n_uv).to(self.dev)
+            uv2pt.copy_(T.where(fresh != -1, fresh + count, uv2pt))
+            self.free.copy_(T.from_numpy(free.reshape(-1).astype(np.uint8)))
+            self.count_dev.fill_(count + k)
+            return count + k
+        self.order.copy_(self.order_stage, non_blocking=True)                # the stage is rewritten only after a later readback
+        ctx.fusion_prio_dev(self.order.data_ptr(), npx, self.prio.data_ptr(), sh)
+        self.stats['rounds'] += ctx.patch_seeds_sums_dev(dp.data_ptr(), dn.data_ptr(), dc.data_ptr(), self.prio.data_ptr(), self.free.data_ptr(),
+                                                         h, w, half, radius, min_cosine, self.owner.data_ptr(), self.px_sums.data_ptr(),
+                                                         self.px_counts.data_ptr(), sh)
+        p, n, c, m, o = self.cloud_ptrs()
+        ctx.fusion_new_seeds_dev(self.owner.data_ptr(), self.prio.data_ptr(), self.px_sums.data_ptr(), self.px_counts.data_ptr(), npx, self.mode,
+                                 self.count_dev.data_ptr(), self.cap, p, n, c, m, o, uv2pt.data_ptr(), self.free.data_ptr(), sh)
+        if self.mode == f3d.NORM_HOST:
+            new = int(self.count_dev.item())
+            self.host_normalise(T.arange(count, new, device=self.dev))
+            return new
+        return count + nfree
+
+    def save(self, uv2pt, name):
+        fu = self.fu
+        if fu.uv2pt_dir is not None:
+            np.save(Path(fu.uv2pt_dir) / f'{name}.npy', uv2pt.cpu().numpy())
+        if fu._lookup_sink is not None:
+            if self.stream is not self.caller:
+                uv2pt.record_stream(self.caller)
+            fu._lookup_sink(name, uv2pt)
+
+    def check(self, frame, radius, min_cosine):
+        """-> (free pixels, sequential flag) of the current free buffer against the frame (one readback)."""
+        _, dp, dn, _, _, _ = frame
+        self.ctx.fusion_frame_check_dev(self.free.data_ptr(), dp.data_ptr(), dn.data_ptr(), self.npx, radius, min_cosine,
+                                        self.check_dev.data_ptr(), self.sh)
+        return self.check_dev
+
+    # ---------------------------------------------------------------- the loop of Fusion.fuse
+    def run(self, radius, angle, stride, max_depth, skip, verbose):
+        T, ctx, sh, fu, npx = self.torch, self.ctx, self.sh, self.fu, self.npx
+        fu.ds_radius, fu.ds_angle = radius, angle
+        stride = max(10, int(radius * 200)) if stride is None else stride
+        half, min_cosine = stride // 2, np.cos(np.deg2rad(angle))
+        for first in range(0, fu.nframes):                                  # first frame with any valid pixel seeds the cloud
+            valid = fu.frames[first][4]
+            if bool(valid.any()):
+                break
+        self.reserve(npx)
+        frame = self.frame(first)
+        self.free.copy_(frame[4])
+        check = self.check(frame, radius, min_cosine)
+        order = self.draw()
+        nfree, fallback = check.tolist()
+        uv2pt = T.full((npx,), -1, dtype=T.int32, device=self.dev)
+        count_bound = self.downsample(order, frame, half, radius, min_cosine, fallback, nfree, 0, uv2pt)
+        self.stats['frames'] += 1
+        if fu.save_lookups:
+            self.save(uv2pt, frame[0])
+        have_free, prev_hits = False, npx
+        for j in range(first + 1, fu.nframes, skip):
+            frame = self.frame(j)
+            name, dp, dn, dc, dv, _ = frame
+            p, n, c, m, o = self.cloud_ptrs()                               # rows < count_bound <= capacity
+            ctx.project_view_dev(p, f3d.F64, count_bound, fu._frame_view(j, max_depth), self.uv_all.data_ptr(), self.inside.data_ptr(), sh)
+            ctx.fusion_hits_dev(self.inside.data_ptr(), self.uv_all.data_ptr(), count_bound, self.count_dev.data_ptr(), p, n, dv.data_ptr(), npx,
+                                self.ids.data_ptr(), self.uv.data_ptr(), self.hit_pts.data_ptr(), self.hit_nrm.data_ptr(),
+                                self.stats_dev.data_ptr(), sh)
+            hits, nvalid, count = self.stats_dev.tolist()
+            count_bound = count
+            if verbose:
+                print(f'fusing frame: {j + 1}, total points = {count}, previous intersections = {prev_hits}')
+            if not nvalid:
+                continue
+            prev_hits = hits
+            self.stats['frames'] += 1
+            uv2pt = T.empty(npx, dtype=T.int32, device=self.dev)
+            if hits:
+                self.free.copy_(dv)                                         # the frame's mask, copied: the caller's tensors stay as they are
+                have_free = True
+                ctx.patch_match_dev(self.uv.data_ptr(), hits, self.h, self.w, half, radius, min_cosine, self.hit_pts.data_ptr(),
+                                    self.hit_nrm.data_ptr(), dp.data_ptr(), dn.data_ptr(), dc.data_ptr(), self.free.data_ptr(),
+                                    self.owner.data_ptr(), self.sums.data_ptr(), self.counts.data_ptr(), sh)
+                ctx.fusion_seed_update_dev(self.ids.data_ptr(), hits, self.sums.data_ptr(), self.counts.data_ptr(), self.mode, p, n, c, m, o, sh)
+                if self.mode == f3d.NORM_HOST:
+                    took = self.counts[:hits] > 0
+                    self.host_normalise(self.ids[:hits][took].long())
+                ctx.fusion_lookup_dev(self.owner.data_ptr(), self.ids.data_ptr(), npx, uv2pt.data_ptr(), self.free.data_ptr(), sh)
+            else:
+                uv2pt.fill_(-1)
+                if not have_free:                                          # what `fuse` meets here: its `free` was never assigned
+                    raise UnboundLocalError("local variable 'free' referenced before assignment (the first fused frame has no hits)")
+            check = self.check(frame, radius, min_cosine)
+            state = np.random.get_state()                                  # draw while the GPU matches; undone if the frame needs none
+            order = self.draw()
+            nfree, fallback = check.tolist()
+            if nfree:
+                # fuse calls patch_downsample with 2 * stride, whose half window is then (2 * stride) // 2
+                count_bound = self.downsample(order, frame, (2 * stride) // 2, radius, min_cosine, fallback, nfree, count, uv2pt)
+            else:
+                np.random.set_state(state)
+                self.stats['draws_undone'] += 1
+            if fu.save_lookups:
+                self.save(uv2pt, name)
+        total = int(self.count_dev.item())
+        pts, nrm, clr, nmerges = (t[:total] for t in self.cloud[:4])
+        return pts, nrm, clr, nmerges, self.occ[:total].view(T.uint32)

@@ -141,8 +141,18 @@ class _DeviceVotes:
             pass
 
     def add_frames(self, luts, masks, h, w):
-        """Frames of h*w lookups each, in order, as ONE batched call."""
+        """Frames of h*w lookups each, in order, as ONE batched call.  The lookups may be device tensors (the int32 [h*w] ones
+        Fusion.fuse_device hands its lookup_sink): they are stacked on the device, after the work of the caller's current stream."""
         if not luts:
+            return
+        if self.torch is not None and isinstance(luts[0], self.torch.Tensor):
+            torch = self.torch
+            self.stream.wait_stream(torch.cuda.current_stream(self.dev))
+            with torch.cuda.stream(self.stream):
+                dl = torch.stack([t.reshape(-1).to(self.dev, torch.int32) for t in luts])
+                dm = torch.stack([torch.as_tensor(mk).reshape(-1).to(self.dev, torch.uint8) for mk in masks])
+                self.ctx.vote_uv2pt_batch_dev(dl.data_ptr(), dm.data_ptr(), len(luts), h, w, self.t.data_ptr(), self.t.shape[0], self.t.shape[1],
+                                              self.stream.cuda_stream)
             return
         lut = np.ascontiguousarray(np.stack(luts), dtype=np.int32)
         m = np.ascontiguousarray(np.stack(masks), dtype=np.uint8)

@@ -24,7 +24,7 @@ namespace {
 
 enum { SLOT_XYZ = 0, SLOT_OUT0, SLOT_OUT1, SLOT_VIEWS, SLOT_MASKS, SLOT_AUX0, SLOT_AUX1, SLOT_SORT_PERM, SLOT_SORT_SCRATCH,
        SLOT_TILED_MASKS, SLOT_TODO, SLOT_GRAPH, SLOT_GRAPH_BBOX, SLOT_PATCH,
-       SLOT_GRP_ORDER, SLOT_GRP_KEYS, SLOT_GRP_STARTS, SLOT_GRP_SCRATCH, SLOT_OBB_TABLE, SLOT_OBB_FACETS, SLOT_OBB_CAND, SLOT_FUSE_TABLES, SLOT_FUSE_CARRY, SLOT_FUSE_XYZ, SLOT_COUNT };
+       SLOT_GRP_ORDER, SLOT_GRP_KEYS, SLOT_GRP_STARTS, SLOT_GRP_SCRATCH, SLOT_OBB_TABLE, SLOT_OBB_FACETS, SLOT_OBB_CAND, SLOT_FUSE_TABLES, SLOT_FUSE_CARRY, SLOT_FUSE_XYZ, SLOT_FUSION, SLOT_PATCH_STATUS, SLOT_COUNT };
 
 thread_local char g_create_err[512] = "";
 
@@ -1310,6 +1310,108 @@ int f3d_patch_seeds_sums(f3d_ctx* ctx, const double* pts, const double* nrm, con
     F3D_HIP(ctx, hipMemcpyAsync(counts, dcnt, (size_t)npx * 4, hipMemcpyDeviceToHost, s));
     F3D_HIP(ctx, hipStreamSynchronize(s));
     if (rounds) *rounds = r;
+    return F3D_OK;
+}
+
+int f3d_patch_match_dev(f3d_ctx* ctx, const int32_t* uv, int64_t m, int h, int w, int half, double radius, double min_cosine,
+                        const double* seed_pts, const double* seed_nrm, const double* q_pts, const double* q_nrm, const double* q_clr,
+                        const uint8_t* free_px, int32_t* owner, double* sums, int32_t* counts, void* stream) {
+    int rc = enter(ctx); if (rc) return rc;
+    const int64_t npx = (int64_t)h * w;
+    if (h < 0 || w < 0 || m < 0 || half < 0 || npx > 0x7fffffffLL || m > 0x7fffffffLL || (m > 0 && (!uv || !seed_pts || !seed_nrm || !sums || !counts)) ||
+        (npx > 0 && (!q_pts || !q_nrm || !free_px || !owner)))
+        return fail(ctx, F3D_ERR_INVALID, "patch_match: bad arguments");
+    if (npx == 0) return F3D_OK;
+    void* scratch;
+    if ((rc = ensure(ctx, SLOT_PATCH, f3d_patch_scratch_bytes(h, w, m), &scratch))) return rc;
+    hipStream_t s = pick(ctx, stream);
+    F3D_HIP(ctx, f3d_launch_patch_owner(uv, m, h, w, half, radius, min_cosine, seed_pts, seed_nrm, q_pts, q_nrm, free_px, owner, scratch, s));
+    F3D_HIP(ctx, f3d_launch_patch_sums(owner, uv, m, h, w, half, q_pts, q_nrm, q_clr, sums, counts, s));
+    return F3D_OK;
+}
+
+int f3d_patch_seeds_sums_dev(f3d_ctx* ctx, const double* pts, const double* nrm, const double* clr, const int32_t* prio, const uint8_t* free_px,
+                             int h, int w, int half, double radius, double min_cosine, int32_t* owner, double* sums, int32_t* counts,
+                             int32_t* rounds, void* stream) {
+    int rc = enter(ctx); if (rc) return rc;
+    const int64_t npx = (int64_t)h * w;
+    if (h < 0 || w < 0 || half < 0 || npx > 0x7fffffffLL || (npx > 0 && (!pts || !nrm || !prio || !free_px || !owner || !sums || !counts)))
+        return fail(ctx, F3D_ERR_INVALID, "patch_seeds_sums: bad arguments");
+    if (rounds) *rounds = 0;
+    if (npx == 0) return F3D_OK;
+    void* dstat;
+    if ((rc = ensure(ctx, SLOT_PATCH_STATUS, (size_t)npx * 4 + 256, &dstat))) return rc;
+    hipStream_t s = pick(ctx, stream);
+    int r = 0;
+    int32_t* counter = (int32_t*)((char*)dstat + (((size_t)npx * 4 + 63) & ~(size_t)63));
+    F3D_HIP(ctx, f3d_launch_patch_seeds(pts, nrm, prio, free_px, h, w, half, radius, min_cosine, (int32_t*)dstat, owner, counter, &r, s));
+    F3D_HIP(ctx, f3d_launch_patch_sums(owner, nullptr, npx, h, w, half, pts, nrm, clr, sums, counts, s));
+    if (rounds) *rounds = r;
+    return F3D_OK;
+}
+
+// ---------------------------------------------------------------------------------------------
+// a5 on a device-resident cloud (Fusion.fuse_device): the per-frame steps, enqueue only
+// ---------------------------------------------------------------------------------------------
+int f3d_fusion_hits_dev(f3d_ctx* ctx, const uint8_t* inside, const int32_t* uv_all, int64_t n, const int64_t* count, const double* pts,
+                        const double* nrm, const uint8_t* valid, int64_t npx, int32_t* ids, int32_t* uv, double* hit_pts, double* hit_nrm,
+                        int64_t* stats, void* stream) {
+    int rc = enter(ctx); if (rc) return rc;
+    if (n < 0 || npx < 0 || n > 0x7ffffffeLL || !count || !stats || (npx > 0 && !valid) ||
+        (n > 0 && (!inside || !uv_all || !pts || !nrm || !ids || !uv || !hit_pts || !hit_nrm)))
+        return fail(ctx, F3D_ERR_INVALID, "fusion_hits: bad arguments");
+    void* scratch;
+    if ((rc = ensure(ctx, SLOT_FUSION, f3d_fusion_scratch_bytes(n), &scratch))) return rc;
+    F3D_HIP(ctx, f3d_launch_fusion_hits(inside, uv_all, n, count, pts, nrm, valid, npx, ids, uv, hit_pts, hit_nrm, stats, scratch,
+                                        pick(ctx, stream)));
+    return F3D_OK;
+}
+
+static bool norm_mode_ok(int mode) { return mode == F3D_NORM_PLAIN || mode == F3D_NORM_FMA || mode == F3D_NORM_HOST; }
+
+int f3d_fusion_seed_update_dev(f3d_ctx* ctx, const int32_t* ids, int64_t m, const double* sums, const int32_t* counts, int norm_mode,
+                               double* pts, double* nrm, double* clr, int64_t* nmerges, uint32_t* occ, void* stream) {
+    int rc = enter(ctx); if (rc) return rc;
+    if (m < 0 || !norm_mode_ok(norm_mode) || (m > 0 && (!ids || !sums || !counts || !pts || !nrm || !clr || !nmerges || !occ)))
+        return fail(ctx, F3D_ERR_INVALID, "fusion_seed_update: bad arguments");
+    F3D_HIP(ctx, f3d_launch_fusion_seed_update(ids, m, sums, counts, norm_mode, pts, nrm, clr, nmerges, occ, pick(ctx, stream)));
+    return F3D_OK;
+}
+
+int f3d_fusion_lookup_dev(f3d_ctx* ctx, const int32_t* owner, const int32_t* ids, int64_t npx, int32_t* uv2pt, uint8_t* free_px, void* stream) {
+    int rc = enter(ctx); if (rc) return rc;
+    if (npx < 0 || (npx > 0 && (!owner || !ids || !uv2pt || !free_px))) return fail(ctx, F3D_ERR_INVALID, "fusion_lookup: bad arguments");
+    F3D_HIP(ctx, f3d_launch_fusion_lookup(owner, ids, npx, uv2pt, free_px, pick(ctx, stream)));
+    return F3D_OK;
+}
+
+int f3d_fusion_frame_check_dev(f3d_ctx* ctx, const uint8_t* free_px, const double* pts, const double* nrm, int64_t npx, double radius,
+                               double min_cosine, int64_t* stats, void* stream) {
+    int rc = enter(ctx); if (rc) return rc;
+    if (npx < 0 || !stats || (npx > 0 && (!free_px || !pts || !nrm))) return fail(ctx, F3D_ERR_INVALID, "fusion_frame_check: bad arguments");
+    F3D_HIP(ctx, f3d_launch_fusion_check(free_px, pts, nrm, npx, radius, min_cosine, stats, pick(ctx, stream)));
+    return F3D_OK;
+}
+
+int f3d_fusion_prio_dev(f3d_ctx* ctx, const int64_t* order, int64_t npx, int32_t* prio, void* stream) {
+    int rc = enter(ctx); if (rc) return rc;
+    if (npx < 0 || npx > 0x7fffffffLL || (npx > 0 && (!order || !prio))) return fail(ctx, F3D_ERR_INVALID, "fusion_prio: bad arguments");
+    F3D_HIP(ctx, f3d_launch_fusion_prio(order, npx, prio, pick(ctx, stream)));
+    return F3D_OK;
+}
+
+int f3d_fusion_new_seeds_dev(f3d_ctx* ctx, const int32_t* owner, const int32_t* prio, const double* sums, const int32_t* counts, int64_t npx,
+                             int norm_mode, int64_t* count, int64_t cap, double* pts, double* nrm, double* clr, int64_t* nmerges,
+                             uint32_t* occ, int32_t* uv2pt, uint8_t* free_px, void* stream) {
+    int rc = enter(ctx); if (rc) return rc;
+    if (npx < 0 || npx > 0x7ffffffeLL || cap < 0 || cap > 0x7fffffffLL || !norm_mode_ok(norm_mode) || !count ||
+        (npx > 0 && (!owner || !prio || !sums || !counts || !pts || !nrm || !clr || !nmerges || !occ || !uv2pt || !free_px)))
+        return fail(ctx, F3D_ERR_INVALID, "fusion_new_seeds: bad arguments");
+    if (npx == 0) return F3D_OK;
+    void* scratch;
+    if ((rc = ensure(ctx, SLOT_FUSION, f3d_fusion_scratch_bytes(npx), &scratch))) return rc;
+    F3D_HIP(ctx, f3d_launch_fusion_new_seeds(owner, prio, sums, counts, npx, norm_mode, count, cap, pts, nrm, clr, nmerges, occ, uv2pt, free_px,
+                                             scratch, pick(ctx, stream)));
     return F3D_OK;
 }
 

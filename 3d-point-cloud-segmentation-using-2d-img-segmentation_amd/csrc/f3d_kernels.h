@@ -124,6 +124,21 @@ hipError_t f3d_launch_patch_seeds(const double* pts, const double* nrm, const in
 // their projections, m of them; uv == NULL: the self-owning pixels of patch_downsample, m = h*w); sums [m, 9], counts [m]
 hipError_t f3d_launch_patch_sums(const int32_t* owner, const int32_t* uv, int64_t m, int h, int w, int half, const double* rows_a,
                                  const double* rows_b, const double* rows_c, double* sums, int32_t* counts, hipStream_t s);
+// the per-frame steps of Fusion.fuse_device on a device-resident cloud (f3d_fusion.hip); scratch: f3d_fusion_scratch_bytes(n) for a
+// compaction of n flags (hits: n = cloud rows, new seeds: n = h*w)
+size_t f3d_fusion_scratch_bytes(int64_t n);
+hipError_t f3d_launch_fusion_hits(const uint8_t* inside, const int32_t* uv_all, int64_t n, const int64_t* count, const double* pts,
+                                  const double* nrm, const uint8_t* valid, int64_t npx, int32_t* ids, int32_t* uv, double* hit_pts,
+                                  double* hit_nrm, int64_t* stats, void* scratch, hipStream_t s);
+hipError_t f3d_launch_fusion_seed_update(const int32_t* ids, int64_t m, const double* sums, const int32_t* counts, int mode, double* pts,
+                                         double* nrm, double* clr, int64_t* nmerges, uint32_t* occ, hipStream_t s);
+hipError_t f3d_launch_fusion_lookup(const int32_t* owner, const int32_t* ids, int64_t npx, int32_t* uv2pt, uint8_t* free_px, hipStream_t s);
+hipError_t f3d_launch_fusion_check(const uint8_t* free_px, const double* pts, const double* nrm, int64_t npx, double radius,
+                                   double min_cosine, int64_t* stats, hipStream_t s);
+hipError_t f3d_launch_fusion_prio(const int64_t* order, int64_t npx, int32_t* prio, hipStream_t s);
+hipError_t f3d_launch_fusion_new_seeds(const int32_t* owner, const int32_t* prio, const double* sums, const int32_t* counts, int64_t npx,
+                                       int mode, int64_t* count, int64_t cap, double* pts, double* nrm, double* clr, int64_t* nmerges,
+                                       uint32_t* occ, int32_t* uv2pt, uint8_t* free_px, void* scratch, hipStream_t s);
 // a12: remaining intersections.py primitives (f3d_geom.hip), device pointers
 hipError_t f3d_launch_ray_x_lines(const double o[3], const double d[3], const double* starts, const double* ends, int64_t n, double* pts,
                                   uint8_t* within, hipStream_t s);

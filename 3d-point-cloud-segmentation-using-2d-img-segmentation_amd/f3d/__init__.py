@@ -25,6 +25,7 @@ VIEW_DOUBLES = 88            # sizeof(f3d_view) / 8
 OBB_DOUBLES = 15             # sizeof(f3d_obb) / 8
 MAX_OBB = 4096
 OBB_OK, OBB_FEW, OBB_DEFERRED = 0, 1, 2
+NORM_PLAIN, NORM_FMA, NORM_HOST = 0, 1, 2   # how the fusion kernels take sqrt(v.dot(v)) (f3d.h F3D_NORM_*)
 
 
 class F3DError(RuntimeError):
@@ -133,6 +134,14 @@ def library():
         'f3d_patch_seeds': (i32, [vp, vp, vp, vp, vp, i32, i32, i32, dbl, dbl, vp, vp]),
         'f3d_patch_match': (i32, [vp, vp, i64, i32, i32, i32, dbl, dbl, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
         'f3d_patch_seeds_sums': (i32, [vp, vp, vp, vp, vp, vp, i32, i32, i32, dbl, dbl, vp, vp, vp, vp]),
+        'f3d_patch_match_dev': (i32, [vp, vp, i64, i32, i32, i32, dbl, dbl, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
+        'f3d_patch_seeds_sums_dev': (i32, [vp, vp, vp, vp, vp, vp, i32, i32, i32, dbl, dbl, vp, vp, vp, vp, vp]),
+        'f3d_fusion_hits_dev': (i32, [vp, vp, vp, i64, vp, vp, vp, vp, i64, vp, vp, vp, vp, vp, vp]),
+        'f3d_fusion_seed_update_dev': (i32, [vp, vp, i64, vp, vp, i32, vp, vp, vp, vp, vp, vp]),
+        'f3d_fusion_lookup_dev': (i32, [vp, vp, vp, i64, vp, vp, vp]),
+        'f3d_fusion_frame_check_dev': (i32, [vp, vp, vp, vp, i64, dbl, dbl, vp, vp]),
+        'f3d_fusion_prio_dev': (i32, [vp, vp, i64, vp, vp]),
+        'f3d_fusion_new_seeds_dev': (i32, [vp, vp, vp, vp, vp, i64, i32, vp, i64, vp, vp, vp, vp, vp, vp, vp, vp]),
         'f3d_unproject_depth': (i32, [vp, vp, i32, i32, i32, vp, dbl, vp, vp, vp]),
         'f3d_unproject_depth_dev': (i32, [vp, vp, i32, i32, i32, vp, dbl, vp, vp, vp, vp]),
         'f3d_unproject_depth_batch_dev': (i32, [vp, vp, i32, i32, i32, i32, vp, dbl, vp, vp, vp, vp]),
@@ -703,6 +712,45 @@ class Context:
 
     def relabel_dev(self, ids_ptr, n, from_id, to_id, count_ptr=None, stream=None):
         self._check(self._lib.f3d_relabel_dev(self._h, ids_ptr, n, int(from_id), int(to_id), count_ptr, stream))
+
+    # a5 on a device-resident cloud (Fusion.fuse_device): device pointers, enqueue only (f3d.h)
+    def patch_match_dev(self, uv_ptr, m, h, w, half, radius, min_cosine, seed_pts_ptr, seed_nrm_ptr, q_pts_ptr, q_nrm_ptr, q_clr_ptr,
+                        free_ptr, owner_ptr, sums_ptr, counts_ptr, stream=None):
+        self._check(self._lib.f3d_patch_match_dev(self._h, uv_ptr, int(m), int(h), int(w), int(half), float(radius), float(min_cosine),
+                                                  seed_pts_ptr, seed_nrm_ptr, q_pts_ptr, q_nrm_ptr, q_clr_ptr, free_ptr, owner_ptr, sums_ptr,
+                                                  counts_ptr, stream))
+
+    def patch_seeds_sums_dev(self, q_pts_ptr, q_nrm_ptr, q_clr_ptr, prio_ptr, free_ptr, h, w, half, radius, min_cosine, owner_ptr, sums_ptr,
+                             counts_ptr, stream=None):
+        """-> the number of seed-resolution rounds (each one a 4-byte readback)."""
+        rounds = C.c_int32(0)
+        self._check(self._lib.f3d_patch_seeds_sums_dev(self._h, q_pts_ptr, q_nrm_ptr, q_clr_ptr, prio_ptr, free_ptr, int(h), int(w), int(half),
+                                                       float(radius), float(min_cosine), owner_ptr, sums_ptr, counts_ptr, C.byref(rounds), stream))
+        return rounds.value
+
+    def fusion_hits_dev(self, inside_ptr, uv_all_ptr, n, count_ptr, pts_ptr, nrm_ptr, valid_ptr, npx, ids_ptr, uv_ptr, hit_pts_ptr,
+                        hit_nrm_ptr, stats_ptr, stream=None):
+        self._check(self._lib.f3d_fusion_hits_dev(self._h, inside_ptr, uv_all_ptr, int(n), count_ptr, pts_ptr, nrm_ptr, valid_ptr, int(npx),
+                                                  ids_ptr, uv_ptr, hit_pts_ptr, hit_nrm_ptr, stats_ptr, stream))
+
+    def fusion_seed_update_dev(self, ids_ptr, m, sums_ptr, counts_ptr, norm_mode, pts_ptr, nrm_ptr, clr_ptr, nmerges_ptr, occ_ptr, stream=None):
+        self._check(self._lib.f3d_fusion_seed_update_dev(self._h, ids_ptr, int(m), sums_ptr, counts_ptr, int(norm_mode), pts_ptr, nrm_ptr, clr_ptr,
+                                                         nmerges_ptr, occ_ptr, stream))
+
+    def fusion_lookup_dev(self, owner_ptr, ids_ptr, npx, uv2pt_ptr, free_ptr, stream=None):
+        self._check(self._lib.f3d_fusion_lookup_dev(self._h, owner_ptr, ids_ptr, int(npx), uv2pt_ptr, free_ptr, stream))
+
+    def fusion_frame_check_dev(self, free_ptr, q_pts_ptr, q_nrm_ptr, npx, radius, min_cosine, stats_ptr, stream=None):
+        self._check(self._lib.f3d_fusion_frame_check_dev(self._h, free_ptr, q_pts_ptr, q_nrm_ptr, int(npx), float(radius), float(min_cosine),
+                                                         stats_ptr, stream))
+
+    def fusion_prio_dev(self, order_ptr, npx, prio_ptr, stream=None):
+        self._check(self._lib.f3d_fusion_prio_dev(self._h, order_ptr, int(npx), prio_ptr, stream))
+
+    def fusion_new_seeds_dev(self, owner_ptr, prio_ptr, sums_ptr, counts_ptr, npx, norm_mode, count_ptr, cap, pts_ptr, nrm_ptr, clr_ptr,
+                             nmerges_ptr, occ_ptr, uv2pt_ptr, free_ptr, stream=None):
+        self._check(self._lib.f3d_fusion_new_seeds_dev(self._h, owner_ptr, prio_ptr, sums_ptr, counts_ptr, int(npx), int(norm_mode), count_ptr,
+                                                       int(cap), pts_ptr, nrm_ptr, clr_ptr, nmerges_ptr, occ_ptr, uv2pt_ptr, free_ptr, stream))
 
 
 _default = {}

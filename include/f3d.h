@@ -451,6 +451,52 @@ int f3d_patch_match(f3d_ctx* ctx, const int32_t* uv, int64_t m, int h, int w, in
 int f3d_patch_seeds_sums(f3d_ctx* ctx, const double* frame_pts, const double* frame_normals, const double* frame_colors,
                          const int32_t* prio, const uint8_t* free_px, int h, int w, int half, double radius, double min_cosine,
                          int32_t* owner, double* sums, int32_t* counts, int32_t* rounds);
+/* The same two calls on DEVICE pointers (frame, seeds, free mask, outputs), enqueued on `stream`.  f3d_patch_seeds_sums_dev still
+ * reads back one counter per round of the seed resolution (the round loop is data dependent); *rounds is a host int (may be NULL). */
+int f3d_patch_match_dev(f3d_ctx* ctx, const int32_t* uv, int64_t m, int h, int w, int half, double radius, double min_cosine,
+                        const double* seed_pts, const double* seed_normals, const double* frame_pts, const double* frame_normals,
+                        const double* frame_colors, const uint8_t* free_px, int32_t* owner, double* sums, int32_t* counts,
+                        void* stream);
+int f3d_patch_seeds_sums_dev(f3d_ctx* ctx, const double* frame_pts, const double* frame_normals, const double* frame_colors,
+                             const int32_t* prio, const uint8_t* free_px, int h, int w, int half, double radius,
+                             double min_cosine, int32_t* owner, double* sums, int32_t* counts, int32_t* rounds, void* stream);
+
+/* ---- a5 on a device-resident cloud: the per-frame steps of Fusion.fuse_device --------------------------- */
+/* The cloud is rows [0, *count) of caller-owned device arrays points / normals / colours float64 [cap,3], nmerges int64 [cap],
+ * occurences uint32 [cap]; *count is an int64 on the device that f3d_fusion_new_seeds_dev advances.  Normals are normalised as
+ * nsum / sqrt(nsum.dot(nsum)), the dot in the order `norm_mode` names: F3D_NORM_PLAIN ((x*x + y*y) + z*z), F3D_NORM_FMA
+ * (fma(z,z, fma(y,y, x*x)), what an FMA BLAS ddot gives) or F3D_NORM_HOST (left unnormalised: the caller normalises). */
+#define F3D_NORM_PLAIN 0
+#define F3D_NORM_FMA 1
+#define F3D_NORM_HOST 2
+
+/* Order-preserving compaction of project_view's inside flags over n rows (rows >= *count ignored): the hits k = 0..m-1 in ascending
+ * row, ids int32 [m], uv int32 [2,m] (row stride m; uv_all is [2,n]), hit_pts / hit_normals [m,3] (copies of the cloud rows).  Room
+ * for m = n in every output.  stats int64 [3] (device) = {m, valid pixels of the frame (valid uint8 [npx], nonzero = valid), *count}:
+ * the one small readback before the matching. */
+int f3d_fusion_hits_dev(f3d_ctx* ctx, const uint8_t* inside, const int32_t* uv_all, int64_t n, const int64_t* count,
+                        const double* points, const double* normals, const uint8_t* valid, int64_t npx, int32_t* ids,
+                        int32_t* uv, double* hit_pts, double* hit_normals, int64_t* stats, void* stream);
+/* The matches of a frame (f3d_patch_match_dev's sums / counts over the m hits) applied in place to the rows ids[k] with counts[k] > 0:
+ * (sum + row) / (n + 1) for points, colours and normals, the normal normalised, nmerges += n, occurences += 1. */
+int f3d_fusion_seed_update_dev(f3d_ctx* ctx, const int32_t* ids, int64_t m, const double* sums, const int32_t* counts, int norm_mode,
+                               double* points, double* normals, double* colors, int64_t* nmerges, uint32_t* occurences,
+                               void* stream);
+/* uv2pt int32 [npx] = ids[owner[p]] (-1 where owner[p] < 0); free_px[p] = 0 for every taken pixel. */
+int f3d_fusion_lookup_dev(f3d_ctx* ctx, const int32_t* owner, const int32_t* ids, int64_t npx, int32_t* uv2pt, uint8_t* free_px,
+                          void* stream);
+/* patch_downsample's guard on a frame: stats int64 [2] (device) = {free pixels, 1 if the frame takes the sequential path}: radius <= 0,
+ * or a free pixel whose own normal test fails (normals.normals <= min_cosine) or whose point is not finite. */
+int f3d_fusion_frame_check_dev(f3d_ctx* ctx, const uint8_t* free_px, const double* frame_pts, const double* frame_normals, int64_t npx,
+                               double radius, double min_cosine, int64_t* stats, void* stream);
+/* prio int32 [npx] = the inverse of the visiting order: prio[order[i]] = i (order int64 [npx], a permutation of 0..npx-1). */
+int f3d_fusion_prio_dev(f3d_ctx* ctx, const int64_t* order, int64_t npx, int32_t* prio, void* stream);
+/* patch_downsample's new seeds (f3d_patch_seeds_sums_dev's owner / sums / counts) appended to the cloud in visiting order: the seed of
+ * rank r goes to row *count + r (mean = sum / n, normal normalised, nmerges = n, occurences = 1), uv2pt[p] = *count + rank of
+ * owner[p] and free_px[p] = 0 for every taken pixel, then *count += seeds.  The caller guarantees cap >= *count + npx. */
+int f3d_fusion_new_seeds_dev(f3d_ctx* ctx, const int32_t* owner, const int32_t* prio, const double* sums, const int32_t* counts,
+                             int64_t npx, int norm_mode, int64_t* count, int64_t cap, double* points, double* normals, double* colors,
+                             int64_t* nmerges, uint32_t* occurences, int32_t* uv2pt, uint8_t* free_px, void* stream);
 
 /* ---- (f)#3: depth frame -> world points (RTAB_utils/ios_rtab.py) -------------------------- */
 /* RTAB2Cache.__getRGBP3d (:171-173): x = (px - cx) * (d / fx), y = (py - cy) * (d / fy), z = d with the scaled
