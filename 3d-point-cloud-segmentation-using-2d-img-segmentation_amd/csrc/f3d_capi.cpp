@@ -24,7 +24,7 @@ namespace {
 
 enum { SLOT_XYZ = 0, SLOT_OUT0, SLOT_OUT1, SLOT_VIEWS, SLOT_MASKS, SLOT_AUX0, SLOT_AUX1, SLOT_SORT_PERM, SLOT_SORT_SCRATCH,
        SLOT_TILED_MASKS, SLOT_TODO, SLOT_GRAPH, SLOT_GRAPH_BBOX, SLOT_PATCH,
-       SLOT_GRP_ORDER, SLOT_GRP_KEYS, SLOT_GRP_STARTS, SLOT_GRP_SCRATCH, SLOT_OBB_TABLE, SLOT_OBB_FACETS, SLOT_OBB_CAND, SLOT_FUSE_TABLES, SLOT_FUSE_CARRY, SLOT_FUSE_XYZ, SLOT_FUSION, SLOT_PATCH_STATUS, SLOT_COUNT };
+       SLOT_GRP_ORDER, SLOT_GRP_KEYS, SLOT_GRP_STARTS, SLOT_GRP_SCRATCH, SLOT_OBB_TABLE, SLOT_OBB_FACETS, SLOT_OBB_CAND, SLOT_FUSE_TABLES, SLOT_FUSE_CARRY, SLOT_FUSE_XYZ, SLOT_FUSION, SLOT_PATCH_STATUS, SLOT_NRM, SLOT_NRM_CAMS, SLOT_COUNT };
 
 thread_local char g_create_err[512] = "";
 
@@ -1501,6 +1501,90 @@ int f3d_radius_graph_fill(f3d_ctx* ctx, int64_t n, int32_t* nbrs) {
     if ((rc = ensure(ctx, SLOT_MASKS, (size_t)nnz * 4, &dnb))) return rc;
     if ((rc = f3d_radius_graph_fill_dev(ctx, n, doffs, (int32_t*)dnb, s))) return rc;
     F3D_HIP(ctx, hipMemcpyAsync(nbrs, dnb, (size_t)nnz * 4, hipMemcpyDeviceToHost, s));
+    F3D_HIP(ctx, hipStreamSynchronize(s));
+    return F3D_OK;
+}
+
+// ---------------------------------------------------------------------------------------------
+// surface normals of depth frames: RTAB2Cache.surface_normal_estimation (ios_rtab.py:236-248)
+// ---------------------------------------------------------------------------------------------
+int f3d_estimate_normals_batch_dev(f3d_ctx* ctx, const double* xyz, int nframes, int64_t n, const double* cam_centres, double radius,
+                                   int max_nn, int orient, double* normals, int32_t* counts, int32_t* neighbours, void* stream) {
+    int rc = enter(ctx); if (rc) return rc;
+    if (nframes < 0 || n < 0 || (int64_t)nframes * n > 0x7fffffffLL)
+        return fail(ctx, F3D_ERR_INVALID, "estimate_normals: bad arguments (F >= 0, n >= 0, F * n < 2^31)");
+    if (!(radius > 0.0) || !(radius < 1e300)) return fail(ctx, F3D_ERR_INVALID, "estimate_normals: radius must be finite and > 0");
+    if (max_nn < 1 || max_nn > F3D_NORMALS_MAX_NN)
+        return fail(ctx, F3D_ERR_INVALID, "estimate_normals: max_nn %d outside [1, %d]", max_nn, F3D_NORMALS_MAX_NN);
+    const int64_t total = (int64_t)nframes * n;
+    if (total == 0) return F3D_OK;
+    if (!xyz || !normals || (orient && !cam_centres)) return fail(ctx, F3D_ERR_INVALID, "estimate_normals: bad arguments (NULL)");
+    hipStream_t s = pick(ctx, stream);
+    void *dbox, *scratch, *dcams = nullptr;
+    if ((rc = ensure(ctx, SLOT_GRAPH_BBOX, f3d_graph_bbox_bytes(), &dbox))) return rc;
+    if ((rc = ensure(ctx, SLOT_NRM, f3d_normals_scratch_bytes(total), &scratch))) return rc;
+    if (orient) {
+        // staged before the readback below, which therefore also completes this upload from pageable memory
+        if ((rc = ensure(ctx, SLOT_NRM_CAMS, (size_t)nframes * 24, &dcams))) return rc;
+        F3D_HIP(ctx, hipMemcpyAsync(dcams, cam_centres, (size_t)nframes * 24, hipMemcpyHostToDevice, s));
+    }
+    // the one blocking readback: bounding box of the batch (grid) and the count of non-finite coordinates
+    int nb = 0;
+    F3D_HIP(ctx, f3d_launch_graph_bbox(xyz, F3D_F64, total, dbox, &nb, s));
+    std::vector<char> hbox(f3d_graph_bbox_bytes());
+    F3D_HIP(ctx, hipMemcpyAsync(hbox.data(), dbox, hbox.size(), hipMemcpyDeviceToHost, s));
+    F3D_HIP(ctx, hipStreamSynchronize(s));
+    double lo[3], hi[3], ext[3];
+    if (f3d_graph_reduce_bbox(hbox.data(), nb, lo, hi)) return fail(ctx, F3D_ERR_INVALID, "estimate_normals: the cloud contains NaN or infinity");
+    for (int c = 0; c < 3; ++c) { ext[c] = hi[c] - lo[c]; if (!(ext[c] < 1e300)) return fail(ctx, F3D_ERR_INVALID, "estimate_normals: extent overflow"); }
+    // cell edge a hair above the radius (two points within it are in adjacent cells whatever the rounding of the cell index), grown
+    // until frame + cell coordinates fit a 63-bit key.  No table over the cells: the key space may be sparse.
+    int fbits = 0; while (((int64_t)1 << fbits) < nframes) ++fbits;
+    f3d_nrmgrid g;
+    double cell = radius * 1.000001 + 1e-300;
+    for (;;) {
+        int bits = fbits; bool ok = true;
+        for (int c = 0; c < 3; ++c) {
+            const double d = floor(ext[c] / cell) + 1.0;
+            if (!(d <= 1073741824.0)) { ok = false; break; }
+            g.dim[c] = (int)d;
+            int b = 0; while (((int64_t)1 << b) < g.dim[c]) ++b;
+            g.shift[c + 1] = (c == 0 ? 0 : g.shift[c]) + b;
+            bits += b;
+        }
+        if (ok && bits <= 63) { g.key_bits = bits < 1 ? 1 : bits; break; }
+        cell *= 1.25;
+    }
+    g.shift[0] = 0;
+    for (int c = 0; c < 3; ++c) g.lo[c] = lo[c];
+    g.inv_cell = 1.0 / cell;
+    F3D_HIP(ctx, f3d_launch_normals(xyz, nframes, n, g, radius * radius, max_nn, (const double*)dcams, orient, scratch, normals, counts,
+                                    neighbours, s));
+    return F3D_OK;
+}
+
+int f3d_estimate_normals(f3d_ctx* ctx, const double* xyz, int64_t n, const double cam_centre[3], double radius, int max_nn, int orient,
+                         double* normals, int32_t* counts, int32_t* neighbours) {
+    int rc = enter(ctx); if (rc) return rc;
+    if (n < 0 || n > 0x7fffffffLL) return fail(ctx, F3D_ERR_INVALID, "estimate_normals: bad arguments (0 <= n < 2^31)");
+    if (!(radius > 0.0) || !(radius < 1e300)) return fail(ctx, F3D_ERR_INVALID, "estimate_normals: radius must be finite and > 0");
+    if (max_nn < 1 || max_nn > F3D_NORMALS_MAX_NN)
+        return fail(ctx, F3D_ERR_INVALID, "estimate_normals: max_nn %d outside [1, %d]", max_nn, F3D_NORMALS_MAX_NN);
+    if (n == 0) return F3D_OK;
+    if (!xyz || !normals || (orient && !cam_centre)) return fail(ctx, F3D_ERR_INVALID, "estimate_normals: bad arguments (NULL)");
+    void *dxyz, *dnrm, *dcnt = nullptr, *dnb = nullptr;
+    if ((rc = ensure(ctx, SLOT_XYZ, (size_t)n * 24, &dxyz))) return rc;
+    if ((rc = ensure(ctx, SLOT_OUT0, (size_t)n * 24, &dnrm))) return rc;
+    if (counts && (rc = ensure(ctx, SLOT_OUT1, (size_t)n * 4, &dcnt))) return rc;
+    if (neighbours && (rc = ensure(ctx, SLOT_MASKS, (size_t)n * max_nn * 4, &dnb))) return rc;
+    hipStream_t s = ctx->stream;
+    F3D_HIP(ctx, hipMemcpyAsync(dxyz, xyz, (size_t)n * 24, hipMemcpyHostToDevice, s));
+    if ((rc = f3d_estimate_normals_batch_dev(ctx, (const double*)dxyz, 1, n, cam_centre, radius, max_nn, orient, (double*)dnrm,
+                                             (int32_t*)dcnt, (int32_t*)dnb, s)))
+        return rc;
+    F3D_HIP(ctx, hipMemcpyAsync(normals, dnrm, (size_t)n * 24, hipMemcpyDeviceToHost, s));
+    if (counts) F3D_HIP(ctx, hipMemcpyAsync(counts, dcnt, (size_t)n * 4, hipMemcpyDeviceToHost, s));
+    if (neighbours) F3D_HIP(ctx, hipMemcpyAsync(neighbours, dnb, (size_t)n * max_nn * 4, hipMemcpyDeviceToHost, s));
     F3D_HIP(ctx, hipStreamSynchronize(s));
     return F3D_OK;
 }

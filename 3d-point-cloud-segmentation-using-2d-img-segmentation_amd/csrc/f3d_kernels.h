@@ -29,6 +29,14 @@ struct f3d_graphgrid {                     // uniform grid of the radius graph (
     int pad;
 };
 
+struct f3d_nrmgrid {                       // cell grid of the normal estimation (by-value kernel argument)
+    double lo[3];                          // bounding box corner of the whole batch
+    double inv_cell;                       // 1 / cell edge; the edge is a hair above the query radius
+    int dim[3];                            // cells per axis, dim[c] <= 1 << (shift[c + 1] - shift[c])
+    int shift[4];                          // key = frame << shift[3] | cz << shift[2] | cy << shift[1] | cx  (shift[0] = 0)
+    int key_bits;                          // bits the radix sort orders (<= 63: key + 1 never wraps)
+};
+
 struct f3d_plane_args {                    // by-value kernel argument of k_inside_polyhedra
     int m;
     int accumulate;                        // 1: AND into the existing `inside` bytes (chained launches)
@@ -112,6 +120,12 @@ hipError_t f3d_launch_graph_count(const void* xyz, int dtype, int64_t n, const f
                                   int64_t* offsets, hipStream_t s);
 hipError_t f3d_launch_graph_fill(int64_t n, const f3d_graphgrid& g, double r2, const void* scratch, const int64_t* offsets,
                                  int32_t* nbrs, hipStream_t s);
+
+// surface normals (f3d_normals.hip): F frames of n float64 points, grid chosen on the host from the f3d_launch_graph_bbox partials;
+// cams device [F, 3].  Enqueue only.  scratch: f3d_normals_scratch_bytes(F * n)
+size_t f3d_normals_scratch_bytes(int64_t total);
+hipError_t f3d_launch_normals(const double* xyz, int nframes, int64_t n, const f3d_nrmgrid& g, double r2, int max_nn, const double* cams,
+                              int orient, void* scratch, double* normals, int32_t* counts, int32_t* nbrs, hipStream_t s);
 // a5 patch matching (f3d_patch.hip): owner[p] = first seed (lowest index) whose window covers free pixel p and accepts it, -1 if none
 size_t f3d_patch_scratch_bytes(int h, int w, int64_t m);
 hipError_t f3d_launch_patch_owner(const int32_t* uv, int64_t m, int h, int w, int half, double radius, double min_cosine,

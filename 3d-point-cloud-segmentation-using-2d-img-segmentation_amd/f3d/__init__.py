@@ -26,6 +26,7 @@ OBB_DOUBLES = 15             # sizeof(f3d_obb) / 8
 MAX_OBB = 4096
 OBB_OK, OBB_FEW, OBB_DEFERRED = 0, 1, 2
 NORM_PLAIN, NORM_FMA, NORM_HOST = 0, 1, 2   # how the fusion kernels take sqrt(v.dot(v)) (f3d.h F3D_NORM_*)
+NORMALS_MAX_NN = 64          # F3D_NORMALS_MAX_NN: the largest max_nn of estimate_normals
 
 
 class F3DError(RuntimeError):
@@ -149,6 +150,8 @@ def library():
         'f3d_radius_graph_fill': (i32, [vp, i64, vp]),
         'f3d_radius_graph_count_dev': (i32, [vp, vp, i32, i64, dbl, vp, vp, vp]),
         'f3d_radius_graph_fill_dev': (i32, [vp, i64, vp, vp, vp]),
+        'f3d_estimate_normals': (i32, [vp, vp, i64, vp, dbl, i32, i32, vp, vp, vp]),
+        'f3d_estimate_normals_batch_dev': (i32, [vp, vp, i32, i64, vp, dbl, i32, i32, vp, vp, vp, vp]),
     }
     for name, (res, args) in protos.items():
         fn = getattr(lib, name)          # AttributeError here = header/library mismatch
@@ -599,6 +602,21 @@ class Context:
         self._check(self._lib.f3d_radius_graph_fill(self._h, len(p), _ptr(nb)))
         return offs, nb
 
+    def estimate_normals(self, points, cam_centre, radius=0.05, max_nn=30, orient=True, want_neighbours=False):
+        """Open3D's estimate_normals(KDTreeSearchParamHybrid(radius, max_nn)) + the flip towards ``cam_centre`` of
+        RTAB2Cache.surface_normal_estimation (ios_rtab.py:236-248), one frame: float64 [N,3] (f3d.h f3d_estimate_normals).
+        want_neighbours: also (counts int32 [N], neighbours int32 [N, max_nn], -1 padded, in (distance, index) order)."""
+        p = _f64(points)
+        if p.ndim != 2 or p.shape[1] != 3:
+            raise ValueError(f'points must be [N,3], got {p.shape}')
+        c = _f64(cam_centre, (3,)) if orient else None
+        out = np.empty_like(p)
+        counts = np.empty(len(p), np.int32) if want_neighbours else None
+        nb = np.empty((len(p), max(int(max_nn), 0)), np.int32) if want_neighbours else None
+        self._check(self._lib.f3d_estimate_normals(self._h, _ptr(p), len(p), _ptr(c), float(radius), int(max_nn), int(bool(orient)), _ptr(out),
+                                                   _ptr(counts), _ptr(nb)))
+        return (out, counts, nb) if want_neighbours else out
+
     # ---------------------------------------------------------------- device-pointer calls
     def project_vote_argmax_dev(self, xyz_ptr, dtype, n, views_ptr, nviews, masks_ptr, h, w, nclasses, threshold,
                                 filter_classes, classes_ptr, votes_ptr=None, stream=None, flags=0, perm_ptr=None):
@@ -709,6 +727,14 @@ class Context:
         K, q, t = _f64(K, (3, 3)), _f64(q_wxyz, (int(nframes), 4)), _f64(t, (int(nframes), 3))
         self._check(self._lib.f3d_unproject_depth_batch_dev(self._h, depth_ptr, int(depth_code), int(nframes), int(h), int(w), _ptr(K), float(depth_scale),
                                                             _ptr(q), _ptr(t), out_ptr, stream))
+
+    def estimate_normals_batch_dev(self, xyz_ptr, nframes, n, cam_centres, normals_ptr, radius=0.05, max_nn=30, orient=True,
+                                   counts_ptr=None, neighbours_ptr=None, stream=None):
+        """F frames of n points, float64 [F,n,3] on the device -> normals [F,n,3] (counts int32 [F*n], neighbours int32 [F*n, max_nn]
+        optional); cam_centres: host [F,3].  One blocking readback per call (f3d.h f3d_estimate_normals_batch_dev)."""
+        c = _f64(cam_centres, (int(nframes), 3)) if orient else None
+        self._check(self._lib.f3d_estimate_normals_batch_dev(self._h, xyz_ptr, int(nframes), int(n), _ptr(c), float(radius), int(max_nn),
+                                                             int(bool(orient)), normals_ptr, counts_ptr, neighbours_ptr, stream))
 
     def relabel_dev(self, ids_ptr, n, from_id, to_id, count_ptr=None, stream=None):
         self._check(self._lib.f3d_relabel_dev(self._h, ids_ptr, n, int(from_id), int(to_id), count_ptr, stream))

@@ -517,6 +517,31 @@ int f3d_unproject_depth_batch_dev(f3d_ctx* ctx, const void* depth, int depth_typ
                                   const double K[9], double depth_scale, const double* q_wxyz, const double* t,
                                   double* xyz, void* stream);
 
+
+/* ---- surface normals of depth frames: RTAB2Cache.surface_normal_estimation (RTAB_utils/ios_rtab.py:236-248) ---- */
+/* Open3D's estimate_normals(KDTreeSearchParamHybrid(radius, max_nn)) restated, then the flip towards the camera.  Per point i
+ * of a frame, in float64 (parity with Open3D itself is unpinned):
+ *   neighbours: the points j of the SAME frame (i included) with d2 = (dx*dx + dy*dy) + dz*dz < radius*radius (strict), the
+ *               max_nn smallest in (d2, j) order (ties to the lower index);
+ *   normal    : (0, 0, 1) when fewer than 3 are kept, when all kept points are bit-identical (the zero-depth cluster) or when
+ *               the covariance vanishes; else the unit eigenvector of the smallest eigenvalue of C = E[p p^T] - E[p] E[p]^T
+ *               over the kept set (deterministic: no float atomics);
+ *   orient    : flipped when dot(n, (p - c) / |p - c|) > 0, c = the frame's camera centre; a point p == c gives NaN and is not
+ *               flipped, as in the reference.  orient = 0 returns the unoriented normals.
+ * Non-finite coordinates, radius <= 0 (or not finite), max_nn outside [1, F3D_NORMALS_MAX_NN] -> F3D_ERR_INVALID, nothing written.
+ * F * n < 2^31.  F == 0 or n == 0 is a no-op. */
+#define F3D_NORMALS_MAX_NN 64
+/* One frame, host pointers: xyz [n, 3] -> normals [n, 3]; counts [n] int32 (kept neighbours) and neighbours [n, max_nn] int32
+ * (-1 padded, (d2, j) order) may be NULL; cam_centre may be NULL when orient == 0. */
+int f3d_estimate_normals(f3d_ctx* ctx, const double* xyz, int64_t n, const double cam_centre[3], double radius, int max_nn,
+                         int orient, double* normals, int32_t* counts, int32_t* neighbours);
+/* F frames at once: xyz device [F, n, 3], cam_centres HOST [F, 3] (may be NULL when orient == 0) -> normals device [F, n, 3];
+ * counts device [F*n] and neighbours device [F*n, max_nn] optional (NULL).  One blocking readback per call (the bounding box
+ * of the batch, which sizes the grid and rejects non-finite input), none per frame; the rest is enqueued on `stream`. */
+int f3d_estimate_normals_batch_dev(f3d_ctx* ctx, const double* xyz, int nframes, int64_t n, const double* cam_centres,
+                                   double radius, int max_nn, int orient, double* normals, int32_t* counts, int32_t* neighbours,
+                                   void* stream);
+
 #ifdef __cplusplus
 }
 #endif
