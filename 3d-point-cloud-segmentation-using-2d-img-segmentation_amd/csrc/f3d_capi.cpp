@@ -150,6 +150,62 @@ int take_error(f3d_ctx* ctx, hipStream_t s, int mask = F3D_DEVERR_ALL) {
     return F3D_OK;
 }
 
+// One call of an entry without "_dev" (include/f3d.h): inputs are copied into scratch slots as they are staged, on the context's
+// stream; outputs are copied back by finish(), which returns after the stream has drained.  The first failed allocation or copy
+// stays in `rc` and turns every later step into a no-op.  A NULL host pointer is not copied: a NULL output is not wanted (no slot,
+// NULL device pointer), a NULL input (an optional one) leaves its slot uninitialised.
+struct staging {
+    f3d_ctx* ctx;
+    int rc = F3D_OK;
+    struct { void* host; const void* dev; size_t bytes; } back_[4];    // the most outputs an entry copies back
+    int nback = 0;
+
+    explicit staging(f3d_ctx* c) : ctx(c) {}
+    void* slot(int s, size_t bytes) {
+        void* p = nullptr;
+        if (!rc) rc = ensure(ctx, s, bytes, &p);
+        return p;
+    }
+    void put(void* dev, const void* host, size_t bytes) { if (!rc && host && bytes) rc = h2d(dev, host, bytes); }
+    void back(void* host, const void* dev, size_t bytes) {
+        if (!host || !bytes || rc) return;
+        if (nback == 4) { rc = fail(ctx, F3D_ERR_INVALID, "staging: more than 4 outputs"); return; }
+        back_[nback++] = {host, dev, bytes};
+    }
+    template <class T> T* in(int s, const T* host, size_t bytes) {
+        void* p = slot(s, bytes);
+        put(p, host, bytes);
+        return (T*)p;
+    }
+    template <class T> T* out(int s, T* host, size_t bytes) {
+        if (!host) return nullptr;
+        T* p = (T*)slot(s, bytes);
+        back(host, p, bytes);
+        return p;
+    }
+    template <class T> T* inout(int s, T* host, size_t bytes) {
+        T* p = in(s, host, bytes);
+        back(host, p, bytes);
+        return p;
+    }
+    // Consumes the device-error bits in `mask` before the copies back (an IndexError writes nothing), or after them with
+    // `keep_partial` (what was applied before the error stays applied, as NumPy leaves it).
+    int finish(int mask = 0, bool keep_partial = false) {
+        if (rc) return rc;
+        hipStream_t s = ctx->stream;
+        if (mask && !keep_partial && (rc = take_error(ctx, s, mask))) return rc;
+        for (int k = 0; k < nback; ++k) F3D_HIP(ctx, hipMemcpyAsync(back_[k].host, back_[k].dev, back_[k].bytes, hipMemcpyDeviceToHost, s));
+        F3D_HIP(ctx, hipStreamSynchronize(s));
+        return mask && keep_partial ? take_error(ctx, s, mask) : F3D_OK;
+    }
+
+  private:
+    int h2d(void* dev, const void* host, size_t bytes) {
+        F3D_HIP(ctx, hipMemcpyAsync(dev, host, bytes, hipMemcpyHostToDevice, ctx->stream));
+        return F3D_OK;
+    }
+};
+
 // ---- host geometry, mirrored operation for operation by oracle/np_ref.py::frustum_data ------
 void inv3(const double K[9], double o[9]) {
     const double a = K[0], b = K[1], c = K[2], d = K[3], e = K[4], f = K[5], g = K[6], h = K[7], i = K[8];
@@ -383,14 +439,11 @@ int f3d_rotate_f64(f3d_ctx* ctx, const double* xyz, int64_t n, const double q[4]
     int rc = enter(ctx); if (rc) return rc;
     if (n < 0 || (n > 0 && (!xyz || !out)) || !q) return fail(ctx, F3D_ERR_INVALID, "rotate: bad arguments");
     if (n == 0) return F3D_OK;
-    void *din, *dout;
-    if ((rc = ensure(ctx, SLOT_XYZ, (size_t)n * 24, &din))) return rc;
-    if ((rc = ensure(ctx, SLOT_OUT0, (size_t)n * 24, &dout))) return rc;
-    F3D_HIP(ctx, hipMemcpyAsync(din, xyz, (size_t)n * 24, hipMemcpyHostToDevice, ctx->stream));
-    F3D_HIP(ctx, f3d_launch_rotate((const double*)din, n, q, (double*)dout, ctx->stream));
-    F3D_HIP(ctx, hipMemcpyAsync(out, dout, (size_t)n * 24, hipMemcpyDeviceToHost, ctx->stream));
-    F3D_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    return F3D_OK;
+    staging st(ctx);
+    const double* din = st.in(SLOT_XYZ, xyz, (size_t)n * 24);
+    double* dout = st.out(SLOT_OUT0, out, (size_t)n * 24);
+    if (!st.rc) st.rc = f3d_rotate_f64_dev(ctx, din, n, q, dout, ctx->stream);
+    return st.finish();
 }
 
 int f3d_rotate_f64_dev(f3d_ctx* ctx, const double* xyz, int64_t n, const double q[4], double* out, void* stream) {
@@ -435,14 +488,11 @@ int f3d_unproject_depth(f3d_ctx* ctx, const void* depth, int depth_type, int h, 
     if (depth_type != F3D_DEPTH_U16 && depth_type != F3D_DEPTH_F32 && depth_type != F3D_DEPTH_F64)
         return fail(ctx, F3D_ERR_INVALID, "unproject_depth: unknown depth type %d", depth_type);
     if (n == 0) return F3D_OK;
-    void *din, *dout;
-    if ((rc = ensure(ctx, SLOT_AUX0, depth_bytes(depth_type, n), &din))) return rc;
-    if ((rc = ensure(ctx, SLOT_OUT0, (size_t)n * 24, &dout))) return rc;
-    F3D_HIP(ctx, hipMemcpyAsync(din, depth, depth_bytes(depth_type, n), hipMemcpyHostToDevice, ctx->stream));
-    if ((rc = f3d_unproject_depth_dev(ctx, din, depth_type, h, w, K, depth_scale, q_wxyz, t, (double*)dout, ctx->stream))) return rc;
-    F3D_HIP(ctx, hipMemcpyAsync(xyz, dout, (size_t)n * 24, hipMemcpyDeviceToHost, ctx->stream));
-    F3D_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    return F3D_OK;
+    staging st(ctx);
+    const void* din = st.in(SLOT_AUX0, depth, depth_bytes(depth_type, n));
+    double* dout = st.out(SLOT_OUT0, xyz, (size_t)n * 24);
+    if (!st.rc) st.rc = f3d_unproject_depth_dev(ctx, din, depth_type, h, w, K, depth_scale, q_wxyz, t, dout, ctx->stream);
+    return st.finish();
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -460,16 +510,12 @@ int f3d_project_view_f64(f3d_ctx* ctx, const double* xyz, int64_t n, const f3d_v
     int rc = enter(ctx); if (rc) return rc;
     if (n < 0 || !view || (!uv && !inside) || (n > 0 && !xyz)) return fail(ctx, F3D_ERR_INVALID, "project_view: bad arguments");
     if (n == 0) return F3D_OK;
-    void *din, *duv = nullptr, *din_s = nullptr;
-    if ((rc = ensure(ctx, SLOT_XYZ, (size_t)n * 24, &din))) return rc;
-    if (uv && (rc = ensure(ctx, SLOT_OUT0, (size_t)n * 8, &duv))) return rc;
-    if (inside && (rc = ensure(ctx, SLOT_OUT1, (size_t)n, &din_s))) return rc;
-    F3D_HIP(ctx, hipMemcpyAsync(din, xyz, (size_t)n * 24, hipMemcpyHostToDevice, ctx->stream));
-    F3D_HIP(ctx, f3d_launch_project_view(din, F3D_F64, n, *view, (int32_t*)duv, (uint8_t*)din_s, ctx->stream));
-    if (uv) F3D_HIP(ctx, hipMemcpyAsync(uv, duv, (size_t)n * 8, hipMemcpyDeviceToHost, ctx->stream));
-    if (inside) F3D_HIP(ctx, hipMemcpyAsync(inside, din_s, (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
-    F3D_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    return F3D_OK;
+    staging st(ctx);
+    const double* din = st.in(SLOT_XYZ, xyz, (size_t)n * 24);
+    int32_t* duv = st.out(SLOT_OUT0, uv, (size_t)n * 8);
+    uint8_t* dinside = st.out(SLOT_OUT1, inside, (size_t)n);
+    if (!st.rc) st.rc = f3d_project_view_dev(ctx, din, F3D_F64, n, view, duv, dinside, ctx->stream);
+    return st.finish();
 }
 
 static int pose_view(f3d_ctx* ctx, const double K[9], const double q[4], const double t[3], f3d_view* vw) {
@@ -523,14 +569,11 @@ int f3d_inside_polyhedra_f64(f3d_ctx* ctx, const double* xyz, int64_t n, const d
     int rc = enter(ctx); if (rc) return rc;
     if (n < 0 || !inside || (n > 0 && !xyz)) return fail(ctx, F3D_ERR_INVALID, "inside_polyhedra: bad arguments");
     if (n == 0) return F3D_OK;
-    void *din, *dout;
-    if ((rc = ensure(ctx, SLOT_XYZ, (size_t)n * 24, &din))) return rc;
-    if ((rc = ensure(ctx, SLOT_OUT1, (size_t)n, &dout))) return rc;
-    F3D_HIP(ctx, hipMemcpyAsync(din, xyz, (size_t)n * 24, hipMemcpyHostToDevice, ctx->stream));
-    if ((rc = f3d_inside_polyhedra_dev(ctx, din, F3D_F64, n, plane_pts, normals, m, (uint8_t*)dout, ctx->stream))) return rc;
-    F3D_HIP(ctx, hipMemcpyAsync(inside, dout, (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
-    F3D_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    return F3D_OK;
+    staging st(ctx);
+    const double* din = st.in(SLOT_XYZ, xyz, (size_t)n * 24);
+    uint8_t* dout = st.out(SLOT_OUT1, inside, (size_t)n);
+    if (!st.rc) st.rc = f3d_inside_polyhedra_dev(ctx, din, F3D_F64, n, plane_pts, normals, m, dout, ctx->stream);
+    return st.finish();
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -717,22 +760,19 @@ int f3d_debug_fastpath_audit(f3d_ctx* ctx, const void* xyz, f3d_dtype dtype, int
     int rc = enter(ctx); if (rc) return rc;
     if (n < 0 || n > 0x7fffffffLL || nviews < 0 || w <= 0 || h <= 0 || !stats || (n > 0 && !xyz) || (nviews > 0 && !views))
         return fail(ctx, F3D_ERR_INVALID, "fastpath_audit: bad arguments");
-    void *dxyz, *dsorted, *dperm, *dviews, *dstats, *scratch;
-    if ((rc = ensure(ctx, SLOT_XYZ, xyz_bytes(dtype, n), &dxyz))) return rc;
-    if ((rc = ensure(ctx, SLOT_OUT0, xyz_bytes(dtype, n), &dsorted))) return rc;
-    if ((rc = ensure(ctx, SLOT_SORT_PERM, (size_t)n * 4, &dperm))) return rc;
-    if ((rc = ensure(ctx, SLOT_SORT_SCRATCH, f3d_sort_scratch_bytes(n), &scratch))) return rc;
-    if ((rc = ensure(ctx, SLOT_VIEWS, sizeof(f3d_view) * (size_t)nviews, &dviews))) return rc;
-    if ((rc = ensure(ctx, SLOT_AUX0, 64, &dstats))) return rc;
-    hipStream_t s = ctx->stream;
-    if (n) F3D_HIP(ctx, hipMemcpyAsync(dxyz, xyz, xyz_bytes(dtype, n), hipMemcpyHostToDevice, s));
-    if (nviews) F3D_HIP(ctx, hipMemcpyAsync(dviews, views, sizeof(f3d_view) * (size_t)nviews, hipMemcpyHostToDevice, s));
+    staging st(ctx);
+    const void* dxyz = st.in(SLOT_XYZ, xyz, xyz_bytes(dtype, n));
+    void* dsorted = st.slot(SLOT_OUT0, xyz_bytes(dtype, n));
+    int32_t* dperm = (int32_t*)st.slot(SLOT_SORT_PERM, (size_t)n * 4);
+    void* scratch = st.slot(SLOT_SORT_SCRATCH, f3d_sort_scratch_bytes(n));
+    const f3d_view* dviews = st.in(SLOT_VIEWS, views, sizeof(f3d_view) * (size_t)nviews);
+    void* dstats = st.slot(SLOT_AUX0, 64);
+    st.back(stats, dstats, 32);
+    if (st.rc) return st.rc;
     // waves of 64 consecutive points must be spatial neighbours, as in the fused call: audit the cell-sorted copy
-    if (n) F3D_HIP(ctx, f3d_launch_cell_sort(dxyz, dtype, n, dsorted, (int32_t*)dperm, scratch, s));
-    F3D_HIP(ctx, f3d_launch_fastpath_audit(dsorted, dtype, n, (const f3d_view*)dviews, nviews, w, h, (unsigned long long*)dstats, s));
-    F3D_HIP(ctx, hipMemcpyAsync(stats, dstats, 32, hipMemcpyDeviceToHost, s));
-    F3D_HIP(ctx, hipStreamSynchronize(s));
-    return F3D_OK;
+    if (n) F3D_HIP(ctx, f3d_launch_cell_sort(dxyz, dtype, n, dsorted, dperm, scratch, ctx->stream));
+    F3D_HIP(ctx, f3d_launch_fastpath_audit(dsorted, dtype, n, dviews, nviews, w, h, (unsigned long long*)dstats, ctx->stream));
+    return st.finish();
 }
 
 int f3d_debug_fuse_deferred(f3d_ctx* ctx, void* stream, uint32_t counts[2]) {
@@ -756,30 +796,17 @@ int f3d_project_vote_argmax(f3d_ctx* ctx, const void* xyz, f3d_dtype dtype, int6
     if (n < 0 || nviews < 0 || h <= 0 || w <= 0 || nclasses < 0 || !classes || (n > 0 && !xyz) || (nviews > 0 && (!views || !masks)))
         return fail(ctx, F3D_ERR_INVALID, "project_vote_argmax: bad arguments");
     if (n == 0) return F3D_OK;
-    const size_t mbytes = (size_t)nviews * h * w, ncols = (size_t)nclasses + 1;
-    void *dxyz, *dviews, *dmasks, *dcls, *dvotes = nullptr;
-    if ((rc = ensure(ctx, SLOT_XYZ, xyz_bytes(dtype, n), &dxyz))) return rc;
-    if ((rc = ensure(ctx, SLOT_VIEWS, sizeof(f3d_view) * (size_t)nviews, &dviews))) return rc;
-    if ((rc = ensure(ctx, SLOT_MASKS, mbytes, &dmasks))) return rc;
-    if ((rc = ensure(ctx, SLOT_OUT0, (size_t)n * 8, &dcls))) return rc;
-    if (votes_u16 && (rc = ensure(ctx, SLOT_OUT1, (size_t)n * ncols * 2, &dvotes))) return rc;
-    hipStream_t s = ctx->stream;
-    F3D_HIP(ctx, hipMemcpyAsync(dxyz, xyz, xyz_bytes(dtype, n), hipMemcpyHostToDevice, s));
-    if (nviews) {
-        F3D_HIP(ctx, hipMemcpyAsync(dviews, views, sizeof(f3d_view) * (size_t)nviews, hipMemcpyHostToDevice, s));
-        F3D_HIP(ctx, hipMemcpyAsync(dmasks, masks, mbytes, hipMemcpyHostToDevice, s));
-    }
+    staging st(ctx);
+    const void* dxyz = st.in(SLOT_XYZ, xyz, xyz_bytes(dtype, n));
+    const f3d_view* dviews = st.in(SLOT_VIEWS, views, sizeof(f3d_view) * (size_t)nviews);
+    const uint8_t* dmasks = st.in(SLOT_MASKS, masks, (size_t)nviews * h * w);
+    int64_t* dcls = st.out(SLOT_OUT0, classes, (size_t)n * 8);
+    uint16_t* dvotes = st.out(SLOT_OUT1, votes_u16, (size_t)n * ((size_t)nclasses + 1) * 2);
     // NumPy callers hand over clouds in arbitrary order: cell-sort large ones (results are order-independent)
     const unsigned flags = n >= 65536 ? F3D_FUSE_SORT : 0u;
-    if ((rc = f3d_project_vote_argmax_dev(ctx, dxyz, dtype, n, (const f3d_view*)dviews, nviews, (const uint8_t*)dmasks, h, w,
-                                          nclasses, filter, nfilter, threshold, (int64_t*)dcls, (uint16_t*)dvotes, flags,
-                                          nullptr, s)))
-        return rc;
-    if ((rc = take_error(ctx, s, F3D_DEVERR_FUSE))) return rc;
-    F3D_HIP(ctx, hipMemcpyAsync(classes, dcls, (size_t)n * 8, hipMemcpyDeviceToHost, s));
-    if (votes_u16) F3D_HIP(ctx, hipMemcpyAsync(votes_u16, dvotes, (size_t)n * ncols * 2, hipMemcpyDeviceToHost, s));
-    F3D_HIP(ctx, hipStreamSynchronize(s));
-    return F3D_OK;
+    if (!st.rc) st.rc = f3d_project_vote_argmax_dev(ctx, dxyz, dtype, n, dviews, nviews, dmasks, h, w, nclasses, filter, nfilter, threshold,
+                                                    dcls, dvotes, flags, nullptr, ctx->stream);
+    return st.finish(F3D_DEVERR_FUSE);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -851,17 +878,12 @@ int f3d_vote_uv2pt_batch(f3d_ctx* ctx, const int32_t* luts, const uint8_t* masks
     if (nframes < 0 || h < 0 || w < 0 || npts < 0 || ncols <= 0 || (nframes > 0 && hw > 0 && (!luts || !masks || !votes)))
         return fail(ctx, F3D_ERR_INVALID, "vote_uv2pt_batch: bad arguments");
     if (nframes == 0 || hw == 0) return F3D_OK;
-    const size_t vbytes = (size_t)npts * ncols * 8, lb = (size_t)nframes * hw * 4, mb = (size_t)nframes * hw;
-    void *dlut, *dmask, *dvotes;
-    if ((rc = ensure(ctx, SLOT_AUX0, lb, &dlut)) || (rc = ensure(ctx, SLOT_AUX1, mb, &dmask)) || (rc = ensure(ctx, SLOT_OUT1, vbytes, &dvotes))) return rc;
-    hipStream_t s = ctx->stream;
-    F3D_HIP(ctx, hipMemcpyAsync(dlut, luts, lb, hipMemcpyHostToDevice, s));                    // every frame's lookup in ONE copy
-    F3D_HIP(ctx, hipMemcpyAsync(dmask, masks, mb, hipMemcpyHostToDevice, s));
-    F3D_HIP(ctx, hipMemcpyAsync(dvotes, votes, vbytes, hipMemcpyHostToDevice, s));             // the matrix travels once per BATCH, not per frame
-    if ((rc = f3d_vote_uv2pt_batch_dev(ctx, (const int32_t*)dlut, (const uint8_t*)dmask, nframes, h, w, (double*)dvotes, npts, ncols, s))) return rc;
-    F3D_HIP(ctx, hipMemcpyAsync(votes, dvotes, vbytes, hipMemcpyDeviceToHost, s));             // frames before a bad one stay applied, like NumPy
-    F3D_HIP(ctx, hipStreamSynchronize(s));
-    return take_error(ctx, s, F3D_DEVERR_VOTE);
+    staging st(ctx);                                          // every frame's lookup in ONE copy, the matrix once per BATCH
+    const int32_t* dlut = st.in(SLOT_AUX0, luts, (size_t)nframes * hw * 4);
+    const uint8_t* dmask = st.in(SLOT_AUX1, masks, (size_t)nframes * hw);
+    double* dvotes = st.inout(SLOT_OUT1, votes, (size_t)npts * ncols * 8);
+    if (!st.rc) st.rc = f3d_vote_uv2pt_batch_dev(ctx, dlut, dmask, nframes, h, w, dvotes, npts, ncols, ctx->stream);
+    return st.finish(F3D_DEVERR_VOTE, true);                  // frames before a bad one stay applied, like NumPy
 }
 
 int f3d_vote_uv2pt(f3d_ctx* ctx, const int32_t* uv2pt, const uint8_t* mask, int64_t hw, double* votes, int64_t npts, int ncols) {
@@ -869,20 +891,12 @@ int f3d_vote_uv2pt(f3d_ctx* ctx, const int32_t* uv2pt, const uint8_t* mask, int6
     if (hw < 0 || npts < 0 || ncols <= 0 || (hw > 0 && (!uv2pt || !mask || !votes)))
         return fail(ctx, F3D_ERR_INVALID, "vote_uv2pt: bad arguments");
     if (hw == 0) return F3D_OK;
-    const size_t vbytes = (size_t)npts * ncols * 8;
-    void *dlut, *dmask, *dvotes;
-    if ((rc = ensure(ctx, SLOT_AUX0, (size_t)hw * 4, &dlut))) return rc;
-    if ((rc = ensure(ctx, SLOT_AUX1, (size_t)hw, &dmask))) return rc;
-    if ((rc = ensure(ctx, SLOT_OUT1, vbytes, &dvotes))) return rc;
-    hipStream_t s = ctx->stream;
-    F3D_HIP(ctx, hipMemcpyAsync(dlut, uv2pt, (size_t)hw * 4, hipMemcpyHostToDevice, s));
-    F3D_HIP(ctx, hipMemcpyAsync(dmask, mask, (size_t)hw, hipMemcpyHostToDevice, s));
-    F3D_HIP(ctx, hipMemcpyAsync(dvotes, votes, vbytes, hipMemcpyHostToDevice, s));
-    if ((rc = f3d_vote_uv2pt_dev(ctx, (const int32_t*)dlut, (const uint8_t*)dmask, hw, (double*)dvotes, npts, ncols, s))) return rc;
-    if ((rc = take_error(ctx, s, F3D_DEVERR_VOTE))) return rc;   // nothing was written in that case
-    F3D_HIP(ctx, hipMemcpyAsync(votes, dvotes, vbytes, hipMemcpyDeviceToHost, s));
-    F3D_HIP(ctx, hipStreamSynchronize(s));
-    return F3D_OK;
+    staging st(ctx);
+    const int32_t* dlut = st.in(SLOT_AUX0, uv2pt, (size_t)hw * 4);
+    const uint8_t* dmask = st.in(SLOT_AUX1, mask, (size_t)hw);
+    double* dvotes = st.inout(SLOT_OUT1, votes, (size_t)npts * ncols * 8);
+    if (!st.rc) st.rc = f3d_vote_uv2pt_dev(ctx, dlut, dmask, hw, dvotes, npts, ncols, ctx->stream);
+    return st.finish(F3D_DEVERR_VOTE);                        // nothing is written back on an IndexError
 }
 
 int f3d_segment_votes_dev(f3d_ctx* ctx, const double* votes, int64_t npts, int ncols, int nclasses, double threshold,
@@ -901,17 +915,11 @@ int f3d_segment_votes(f3d_ctx* ctx, const double* votes, int64_t npts, int ncols
     int rc = enter(ctx); if (rc) return rc;
     if (npts < 0 || ncols <= 0 || (npts > 0 && (!votes || !classes))) return fail(ctx, F3D_ERR_INVALID, "segment_votes: bad arguments");
     if (npts == 0) return F3D_OK;
-    const size_t vbytes = (size_t)npts * ncols * 8;
-    void *dvotes, *dcls;
-    if ((rc = ensure(ctx, SLOT_OUT1, vbytes, &dvotes))) return rc;
-    if ((rc = ensure(ctx, SLOT_OUT0, (size_t)npts * 8, &dcls))) return rc;
-    hipStream_t s = ctx->stream;
-    F3D_HIP(ctx, hipMemcpyAsync(dvotes, votes, vbytes, hipMemcpyHostToDevice, s));
-    if ((rc = f3d_segment_votes_dev(ctx, (const double*)dvotes, npts, ncols, nclasses, threshold, filter, nfilter, (int64_t*)dcls, s)))
-        return rc;
-    F3D_HIP(ctx, hipMemcpyAsync(classes, dcls, (size_t)npts * 8, hipMemcpyDeviceToHost, s));
-    F3D_HIP(ctx, hipStreamSynchronize(s));
-    return F3D_OK;
+    staging st(ctx);
+    const double* dvotes = st.in(SLOT_OUT1, votes, (size_t)npts * ncols * 8);
+    int64_t* dcls = st.out(SLOT_OUT0, classes, (size_t)npts * 8);
+    if (!st.rc) st.rc = f3d_segment_votes_dev(ctx, dvotes, npts, ncols, nclasses, threshold, filter, nfilter, dcls, ctx->stream);
+    return st.finish();
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -939,15 +947,11 @@ int f3d_sem_logits_to_mask(f3d_ctx* ctx, const float* sem, int c, int64_t hw, fl
     int rc = enter(ctx); if (rc) return rc;
     if (c <= 0 || hw < 0 || (hw > 0 && (!sem || !mask))) return fail(ctx, F3D_ERR_INVALID, "sem_logits_to_mask: bad arguments");
     if (hw == 0) return F3D_OK;
-    void *dsem, *dmask;
-    if ((rc = ensure(ctx, SLOT_MASKS, (size_t)c * hw * 4, &dsem))) return rc;
-    if ((rc = ensure(ctx, SLOT_AUX1, (size_t)hw, &dmask))) return rc;
-    hipStream_t s = ctx->stream;
-    F3D_HIP(ctx, hipMemcpyAsync(dsem, sem, (size_t)c * hw * 4, hipMemcpyHostToDevice, s));
-    if ((rc = f3d_sem_logits_to_mask_dev(ctx, (const float*)dsem, c, hw, conf, low_label, (uint8_t*)dmask, s))) return rc;
-    F3D_HIP(ctx, hipMemcpyAsync(mask, dmask, (size_t)hw, hipMemcpyDeviceToHost, s));
-    F3D_HIP(ctx, hipStreamSynchronize(s));
-    return F3D_OK;
+    staging st(ctx);
+    const float* dsem = st.in(SLOT_MASKS, sem, (size_t)c * hw * 4);
+    uint8_t* dmask = st.out(SLOT_AUX1, mask, (size_t)hw);
+    if (!st.rc) st.rc = f3d_sem_logits_to_mask_dev(ctx, dsem, c, hw, conf, low_label, dmask, ctx->stream);
+    return st.finish();
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -974,19 +978,14 @@ int f3d_points_in_obb(f3d_ctx* ctx, const void* xyz, f3d_dtype dtype, int64_t n,
     int rc = enter(ctx); if (rc) return rc;
     if (n < 0 || b < 0 || (n > 0 && !xyz) || (!inside_bits && !cooc)) return fail(ctx, F3D_ERR_INVALID, "points_in_obb: bad arguments");
     if (b == 0) return F3D_OK;
-    const size_t words = (size_t)(b + 31) / 32;
-    void *dxyz, *dbits = nullptr, *dcooc = nullptr;
-    if ((rc = ensure(ctx, SLOT_XYZ, xyz_bytes(dtype, n), &dxyz))) return rc;
-    if (inside_bits && (rc = ensure(ctx, SLOT_OUT1, (size_t)n * words * 4, &dbits))) return rc;
-    if (cooc && (rc = ensure(ctx, SLOT_AUX0, (size_t)b * b, &dcooc))) return rc;
-    hipStream_t s = ctx->stream;
-    if (n) F3D_HIP(ctx, hipMemcpyAsync(dxyz, xyz, xyz_bytes(dtype, n), hipMemcpyHostToDevice, s));
-    if (cooc && n == 0) F3D_HIP(ctx, hipMemsetAsync(dcooc, 0, (size_t)b * b, s));
-    if ((rc = f3d_points_in_obb_dev(ctx, dxyz, dtype, n, boxes, b, (uint32_t*)dbits, (uint8_t*)dcooc, s))) return rc;
-    if (inside_bits && n) F3D_HIP(ctx, hipMemcpyAsync(inside_bits, dbits, (size_t)n * words * 4, hipMemcpyDeviceToHost, s));
-    if (cooc) F3D_HIP(ctx, hipMemcpyAsync(cooc, dcooc, (size_t)b * b, hipMemcpyDeviceToHost, s));
-    F3D_HIP(ctx, hipStreamSynchronize(s));
-    return F3D_OK;
+    staging st(ctx);
+    const void* dxyz = st.in(SLOT_XYZ, xyz, xyz_bytes(dtype, n));
+    uint32_t* dbits = st.out(SLOT_OUT1, inside_bits, (size_t)n * (((size_t)b + 31) / 32) * 4);
+    uint8_t* dcooc = st.out(SLOT_AUX0, cooc, (size_t)b * b);
+    if (st.rc) return st.rc;
+    if (dcooc && n == 0) F3D_HIP(ctx, hipMemsetAsync(dcooc, 0, (size_t)b * b, ctx->stream));
+    st.rc = f3d_points_in_obb_dev(ctx, dxyz, dtype, n, boxes, b, dbits, dcooc, ctx->stream);
+    return st.finish();
 }
 
 int f3d_relabel_dev(f3d_ctx* ctx, int64_t* ids, int64_t n, int64_t from, int64_t to, int64_t* count_dev, void* stream) {
@@ -1003,45 +1002,29 @@ int f3d_relabel(f3d_ctx* ctx, int64_t* ids, int64_t n, int64_t from, int64_t to,
     if (n < 0 || (n > 0 && !ids)) return fail(ctx, F3D_ERR_INVALID, "relabel: bad arguments");
     if (count) *count = 0;
     if (n == 0) return F3D_OK;
-    void* dids;
-    if ((rc = ensure(ctx, SLOT_OUT0, (size_t)n * 8, &dids))) return rc;
-    hipStream_t s = ctx->stream;
-    F3D_HIP(ctx, hipMemcpyAsync(dids, ids, (size_t)n * 8, hipMemcpyHostToDevice, s));
-    if ((rc = f3d_relabel_dev(ctx, (int64_t*)dids, n, from, to, (int64_t*)ctx->count_dev, s))) return rc;
-    F3D_HIP(ctx, hipMemcpyAsync(ids, dids, (size_t)n * 8, hipMemcpyDeviceToHost, s));
-    if (count) F3D_HIP(ctx, hipMemcpyAsync(count, ctx->count_dev, 8, hipMemcpyDeviceToHost, s));
-    F3D_HIP(ctx, hipStreamSynchronize(s));
-    return F3D_OK;
+    staging st(ctx);
+    int64_t* dids = st.inout(SLOT_OUT0, ids, (size_t)n * 8);
+    st.back(count, ctx->count_dev, 8);
+    if (!st.rc) st.rc = f3d_relabel_dev(ctx, dids, n, from, to, (int64_t*)ctx->count_dev, ctx->stream);
+    return st.finish();
 }
 
 // ---------------------------------------------------------------------------------------------
 // a12 remaining intersections.py primitives (host pointers)
 // ---------------------------------------------------------------------------------------------
-namespace {
-struct dbuf { void* p; };
-int up(f3d_ctx* ctx, int slot, const void* src, size_t bytes, void** dst) {
-    int rc = ensure(ctx, slot, bytes, dst); if (rc) return rc;
-    if (bytes) F3D_HIP(ctx, hipMemcpyAsync(*dst, src, bytes, hipMemcpyHostToDevice, ctx->stream));
-    return F3D_OK;
-}
-int down(f3d_ctx* ctx, void* dst, const void* src, size_t bytes) {
-    if (bytes) F3D_HIP(ctx, hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, ctx->stream));
-    return F3D_OK;
-}
-}  // namespace
-
 int f3d_ray_x_lines(f3d_ctx* ctx, const double origin[3], const double direction[3], const double* starts, const double* ends, int64_t n,
                     double* points, uint8_t* within) {
     int rc = enter(ctx); if (rc) return rc;
     if (n < 0 || !origin || !direction || (n > 0 && (!starts || !ends || !points || !within))) return fail(ctx, F3D_ERR_INVALID, "ray_x_lines: bad arguments");
     if (n == 0) return F3D_OK;
-    void *ds, *de, *dp, *dw;
-    if ((rc = up(ctx, SLOT_XYZ, starts, (size_t)n * 24, &ds)) || (rc = up(ctx, SLOT_OUT1, ends, (size_t)n * 24, &de))) return rc;
-    if ((rc = ensure(ctx, SLOT_OUT0, (size_t)n * 24, &dp)) || (rc = ensure(ctx, SLOT_AUX1, (size_t)n, &dw))) return rc;
-    F3D_HIP(ctx, f3d_launch_ray_x_lines(origin, direction, (const double*)ds, (const double*)de, n, (double*)dp, (uint8_t*)dw, ctx->stream));
-    if ((rc = down(ctx, points, dp, (size_t)n * 24)) || (rc = down(ctx, within, dw, (size_t)n))) return rc;
-    F3D_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    return F3D_OK;
+    staging st(ctx);
+    const double* ds = st.in(SLOT_XYZ, starts, (size_t)n * 24);
+    const double* de = st.in(SLOT_OUT1, ends, (size_t)n * 24);
+    double* dp = st.out(SLOT_OUT0, points, (size_t)n * 24);
+    uint8_t* dw = st.out(SLOT_AUX1, within, (size_t)n);
+    if (st.rc) return st.rc;
+    F3D_HIP(ctx, f3d_launch_ray_x_lines(origin, direction, ds, de, n, dp, dw, ctx->stream));
+    return st.finish();
 }
 
 int f3d_rays_x_plane(f3d_ctx* ctx, const double pp[3], const double pn[3], const double* origins, const double* dirs, int64_t n, double* points,
@@ -1049,13 +1032,14 @@ int f3d_rays_x_plane(f3d_ctx* ctx, const double pp[3], const double pn[3], const
     int rc = enter(ctx); if (rc) return rc;
     if (n < 0 || !pp || !pn || (n > 0 && (!origins || !dirs || !points || !valid))) return fail(ctx, F3D_ERR_INVALID, "rays_x_plane: bad arguments");
     if (n == 0) return F3D_OK;
-    void *d_o, *dd, *dp, *dv;
-    if ((rc = up(ctx, SLOT_XYZ, origins, (size_t)n * 24, &d_o)) || (rc = up(ctx, SLOT_OUT1, dirs, (size_t)n * 24, &dd))) return rc;
-    if ((rc = ensure(ctx, SLOT_OUT0, (size_t)n * 24, &dp)) || (rc = ensure(ctx, SLOT_AUX1, (size_t)n, &dv))) return rc;
-    F3D_HIP(ctx, f3d_launch_rays_x_plane(pp, pn, (const double*)d_o, (const double*)dd, n, (double*)dp, (uint8_t*)dv, ctx->stream));
-    if ((rc = down(ctx, points, dp, (size_t)n * 24)) || (rc = down(ctx, valid, dv, (size_t)n))) return rc;
-    F3D_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    return F3D_OK;
+    staging st(ctx);
+    const double* d_o = st.in(SLOT_XYZ, origins, (size_t)n * 24);
+    const double* dd = st.in(SLOT_OUT1, dirs, (size_t)n * 24);
+    double* dp = st.out(SLOT_OUT0, points, (size_t)n * 24);
+    uint8_t* dv = st.out(SLOT_AUX1, valid, (size_t)n);
+    if (st.rc) return st.rc;
+    F3D_HIP(ctx, f3d_launch_rays_x_plane(pp, pn, d_o, dd, n, dp, dv, ctx->stream));
+    return st.finish();
 }
 
 int f3d_lines_x_planes(f3d_ctx* ctx, const double* lo, const double* le, int64_t n, const double* pps, const double* pns, int m, double* points,
@@ -1065,40 +1049,42 @@ int f3d_lines_x_planes(f3d_ctx* ctx, const double* lo, const double* le, int64_t
         return fail(ctx, F3D_ERR_INVALID, "lines_x_planes: bad arguments");
     if (n != 1 && n != m) return fail(ctx, F3D_ERR_INVALID, "operands could not be broadcast together with shapes (%lld,%d,3) (%lld,3)", (long long)n, m, (long long)n);
     if (n == 0 || m == 0) return F3D_OK;
-    void *d_o, *de, *dpp, *dpn, *dp, *dv;
-    if ((rc = up(ctx, SLOT_XYZ, lo, (size_t)n * 24, &d_o)) || (rc = up(ctx, SLOT_OUT1, le, (size_t)n * 24, &de))) return rc;
-    if ((rc = up(ctx, SLOT_VIEWS, pps, (size_t)m * 24, &dpp)) || (rc = up(ctx, SLOT_AUX0, pns, (size_t)m * 24, &dpn))) return rc;
-    if ((rc = ensure(ctx, SLOT_OUT0, (size_t)n * m * 24, &dp)) || (rc = ensure(ctx, SLOT_AUX1, (size_t)n * m, &dv))) return rc;
-    F3D_HIP(ctx, f3d_launch_lines_x_planes((const double*)d_o, (const double*)de, n, (const double*)dpp, (const double*)dpn, m, n == 1 ? 0 : 1,
-                                           (double*)dp, (uint8_t*)dv, ctx->stream));
-    if ((rc = down(ctx, points, dp, (size_t)n * m * 24)) || (rc = down(ctx, valid, dv, (size_t)n * m))) return rc;
-    F3D_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    return F3D_OK;
+    staging st(ctx);
+    const double* d_o = st.in(SLOT_XYZ, lo, (size_t)n * 24);
+    const double* de = st.in(SLOT_OUT1, le, (size_t)n * 24);
+    const double* dpp = st.in(SLOT_VIEWS, pps, (size_t)m * 24);
+    const double* dpn = st.in(SLOT_AUX0, pns, (size_t)m * 24);
+    double* dp = st.out(SLOT_OUT0, points, (size_t)n * m * 24);
+    uint8_t* dv = st.out(SLOT_AUX1, valid, (size_t)n * m);
+    if (st.rc) return st.rc;
+    F3D_HIP(ctx, f3d_launch_lines_x_planes(d_o, de, n, dpp, dpn, m, n == 1 ? 0 : 1, dp, dv, ctx->stream));
+    return st.finish();
 }
 
 int f3d_point_inside_polygon(f3d_ctx* ctx, const double* points, int64_t n, const double* verts, int m, uint8_t* inside, uint8_t* within) {
     int rc = enter(ctx); if (rc) return rc;
     if (n < 0 || m < 1 || !verts || (n > 0 && (!points || !inside || !within))) return fail(ctx, F3D_ERR_INVALID, "point_inside_polygon: bad arguments");
     if (n == 0) return F3D_OK;
-    void *dp, *dv, *di, *dw;
-    if ((rc = up(ctx, SLOT_XYZ, points, (size_t)n * 24, &dp)) || (rc = up(ctx, SLOT_VIEWS, verts, (size_t)m * 24, &dv))) return rc;
-    if ((rc = ensure(ctx, SLOT_AUX1, (size_t)n, &di)) || (rc = ensure(ctx, SLOT_OUT0, (size_t)n * m, &dw))) return rc;
-    F3D_HIP(ctx, f3d_launch_point_inside_polygon((const double*)dp, n, (const double*)dv, m, (uint8_t*)di, (uint8_t*)dw, ctx->stream));
-    if ((rc = down(ctx, inside, di, (size_t)n)) || (rc = down(ctx, within, dw, (size_t)n * m))) return rc;
-    F3D_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    return F3D_OK;
+    staging st(ctx);
+    const double* dp = st.in(SLOT_XYZ, points, (size_t)n * 24);
+    const double* dv = st.in(SLOT_VIEWS, verts, (size_t)m * 24);
+    uint8_t* di = st.out(SLOT_AUX1, inside, (size_t)n);
+    uint8_t* dw = st.out(SLOT_OUT0, within, (size_t)n * m);
+    if (st.rc) return st.rc;
+    F3D_HIP(ctx, f3d_launch_point_inside_polygon(dp, n, dv, m, di, dw, ctx->stream));
+    return st.finish();
 }
 
 int f3d_points_plane_projection(f3d_ctx* ctx, const double* points, int64_t n, const double pp[3], const double nr[3], double* out) {
     int rc = enter(ctx); if (rc) return rc;
     if (n < 0 || !pp || !nr || (n > 0 && (!points || !out))) return fail(ctx, F3D_ERR_INVALID, "points_plane_projection: bad arguments");
     if (n == 0) return F3D_OK;
-    void *dp, *d_o;
-    if ((rc = up(ctx, SLOT_XYZ, points, (size_t)n * 24, &dp)) || (rc = ensure(ctx, SLOT_OUT0, (size_t)n * 24, &d_o))) return rc;
-    F3D_HIP(ctx, f3d_launch_points_plane_projection((const double*)dp, n, pp, nr, (double*)d_o, ctx->stream));
-    if ((rc = down(ctx, out, d_o, (size_t)n * 24))) return rc;
-    F3D_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    return F3D_OK;
+    staging st(ctx);
+    const double* dp = st.in(SLOT_XYZ, points, (size_t)n * 24);
+    double* d_o = st.out(SLOT_OUT0, out, (size_t)n * 24);
+    if (st.rc) return st.rc;
+    F3D_HIP(ctx, f3d_launch_points_plane_projection(dp, n, pp, nr, d_o, ctx->stream));
+    return st.finish();
 }
 
 int f3d_lines_plane_projection(f3d_ctx* ctx, const double* starts, const double* ends, int64_t n, const double pp[3], const double nr[3],
@@ -1106,16 +1092,17 @@ int f3d_lines_plane_projection(f3d_ctx* ctx, const double* starts, const double*
     int rc = enter(ctx); if (rc) return rc;
     if (n < 0 || !pp || !nr || (n > 0 && (!starts || !ends || !sp || !ep || !dirs))) return fail(ctx, F3D_ERR_INVALID, "lines_plane_projection: bad arguments");
     if (n == 0) return F3D_OK;
-    void *ds, *de, *dsp, *dep, *dd;
-    if ((rc = up(ctx, SLOT_XYZ, starts, (size_t)n * 24, &ds)) || (rc = up(ctx, SLOT_OUT1, ends, (size_t)n * 24, &de))) return rc;
-    if ((rc = ensure(ctx, SLOT_OUT0, (size_t)n * 24, &dsp)) || (rc = ensure(ctx, SLOT_MASKS, (size_t)n * 24, &dep)) ||
-        (rc = ensure(ctx, SLOT_AUX0, (size_t)n * 24, &dd))) return rc;
-    F3D_HIP(ctx, f3d_launch_points_plane_projection((const double*)ds, n, pp, nr, (double*)dsp, ctx->stream));
-    F3D_HIP(ctx, f3d_launch_points_plane_projection((const double*)de, n, pp, nr, (double*)dep, ctx->stream));
-    F3D_HIP(ctx, f3d_launch_unit_difference((const double*)dsp, (const double*)dep, n, (double*)dd, ctx->stream));
-    if ((rc = down(ctx, sp, dsp, (size_t)n * 24)) || (rc = down(ctx, ep, dep, (size_t)n * 24)) || (rc = down(ctx, dirs, dd, (size_t)n * 24))) return rc;
-    F3D_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    return F3D_OK;
+    staging st(ctx);
+    const double* ds = st.in(SLOT_XYZ, starts, (size_t)n * 24);
+    const double* de = st.in(SLOT_OUT1, ends, (size_t)n * 24);
+    double* dsp = st.out(SLOT_OUT0, sp, (size_t)n * 24);
+    double* dep = st.out(SLOT_MASKS, ep, (size_t)n * 24);
+    double* dd = st.out(SLOT_AUX0, dirs, (size_t)n * 24);
+    if (st.rc) return st.rc;
+    F3D_HIP(ctx, f3d_launch_points_plane_projection(ds, n, pp, nr, dsp, ctx->stream));
+    F3D_HIP(ctx, f3d_launch_points_plane_projection(de, n, pp, nr, dep, ctx->stream));
+    F3D_HIP(ctx, f3d_launch_unit_difference(dsp, dep, n, dd, ctx->stream));
+    return st.finish();
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1137,22 +1124,14 @@ int f3d_components_same_class(f3d_ctx* ctx, const int64_t* classes, int64_t n, c
     if (n == 0) return F3D_OK;
     const int64_t e = offsets[n];
     if (e < 0 || (e > 0 && !nbrs)) return fail(ctx, F3D_ERR_INVALID, "components_same_class: bad adjacency");
-    void *dcls, *doffs, *dnb, *dpar, *droot;
-    if ((rc = ensure(ctx, SLOT_XYZ, (size_t)n * 8, &dcls))) return rc;
-    if ((rc = ensure(ctx, SLOT_OUT1, (size_t)(n + 1) * 8, &doffs))) return rc;
-    if ((rc = ensure(ctx, SLOT_MASKS, (size_t)e * 4, &dnb))) return rc;
-    if ((rc = ensure(ctx, SLOT_AUX0, (size_t)n * 4, &dpar))) return rc;
-    if ((rc = ensure(ctx, SLOT_OUT0, (size_t)n * 8, &droot))) return rc;
-    hipStream_t s = ctx->stream;
-    F3D_HIP(ctx, hipMemcpyAsync(dcls, classes, (size_t)n * 8, hipMemcpyHostToDevice, s));
-    F3D_HIP(ctx, hipMemcpyAsync(doffs, offsets, (size_t)(n + 1) * 8, hipMemcpyHostToDevice, s));
-    if (e) F3D_HIP(ctx, hipMemcpyAsync(dnb, nbrs, (size_t)e * 4, hipMemcpyHostToDevice, s));
-    if ((rc = f3d_components_same_class_dev(ctx, (const int64_t*)dcls, n, (const int64_t*)doffs, (const int32_t*)dnb, (int32_t*)dpar,
-                                            (int64_t*)droot, s))) return rc;
-    if ((rc = take_error(ctx, s, F3D_DEVERR_CC))) return rc;
-    F3D_HIP(ctx, hipMemcpyAsync(root, droot, (size_t)n * 8, hipMemcpyDeviceToHost, s));
-    F3D_HIP(ctx, hipStreamSynchronize(s));
-    return F3D_OK;
+    staging st(ctx);
+    const int64_t* dcls = st.in(SLOT_XYZ, classes, (size_t)n * 8);
+    const int64_t* doffs = st.in(SLOT_OUT1, offsets, (size_t)(n + 1) * 8);
+    const int32_t* dnb = st.in(SLOT_MASKS, nbrs, (size_t)e * 4);
+    int32_t* dpar = (int32_t*)st.slot(SLOT_AUX0, (size_t)n * 4);
+    int64_t* droot = st.out(SLOT_OUT0, root, (size_t)n * 8);
+    if (!st.rc) st.rc = f3d_components_same_class_dev(ctx, dcls, n, doffs, dnb, dpar, droot, ctx->stream);
+    return st.finish(F3D_DEVERR_CC);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1182,54 +1161,16 @@ int f3d_patch_owner(f3d_ctx* ctx, const int32_t* uv, int64_t m, int h, int w, in
     if (h < 0 || w < 0 || m < 0 || (m > 0 && (!uv || !seed_pts || !seed_nrm)) || (npx > 0 && (!q_pts || !q_nrm || !free_px || !owner)))
         return fail(ctx, F3D_ERR_INVALID, "patch_owner: bad arguments");
     if (npx == 0) return F3D_OK;
-    void *duv, *dsp, *dsn, *dqp, *dqn, *dfree, *down;
-    if ((rc = ensure(ctx, SLOT_AUX0, (size_t)m * 8 + 8, &duv)) || (rc = ensure(ctx, SLOT_XYZ, (size_t)m * 24 + 8, &dsp)) ||
-        (rc = ensure(ctx, SLOT_OUT1, (size_t)m * 24 + 8, &dsn)) || (rc = ensure(ctx, SLOT_MASKS, (size_t)npx * 24, &dqp)) ||
-        (rc = ensure(ctx, SLOT_VIEWS, (size_t)npx * 24, &dqn)) || (rc = ensure(ctx, SLOT_AUX1, (size_t)npx, &dfree)) ||
-        (rc = ensure(ctx, SLOT_OUT0, (size_t)npx * 4, &down)))
-        return rc;
-    hipStream_t s = ctx->stream;
-    if (m) {
-        F3D_HIP(ctx, hipMemcpyAsync(duv, uv, (size_t)m * 8, hipMemcpyHostToDevice, s));
-        F3D_HIP(ctx, hipMemcpyAsync(dsp, seed_pts, (size_t)m * 24, hipMemcpyHostToDevice, s));
-        F3D_HIP(ctx, hipMemcpyAsync(dsn, seed_nrm, (size_t)m * 24, hipMemcpyHostToDevice, s));
-    }
-    F3D_HIP(ctx, hipMemcpyAsync(dqp, q_pts, (size_t)npx * 24, hipMemcpyHostToDevice, s));
-    F3D_HIP(ctx, hipMemcpyAsync(dqn, q_nrm, (size_t)npx * 24, hipMemcpyHostToDevice, s));
-    F3D_HIP(ctx, hipMemcpyAsync(dfree, free_px, (size_t)npx, hipMemcpyHostToDevice, s));
-    if ((rc = f3d_patch_owner_dev(ctx, (const int32_t*)duv, m, h, w, half, radius, min_cosine, (const double*)dsp, (const double*)dsn,
-                                  (const double*)dqp, (const double*)dqn, (const uint8_t*)dfree, (int32_t*)down, s))) return rc;
-    F3D_HIP(ctx, hipMemcpyAsync(owner, down, (size_t)npx * 4, hipMemcpyDeviceToHost, s));
-    F3D_HIP(ctx, hipStreamSynchronize(s));
-    return F3D_OK;
-}
-
-int f3d_patch_seeds(f3d_ctx* ctx, const double* pts, const double* nrm, const int32_t* prio, const uint8_t* free_px, int h, int w,
-                    int half, double radius, double min_cosine, int32_t* owner, int32_t* rounds) {
-    int rc = enter(ctx); if (rc) return rc;
-    const int64_t npx = (int64_t)h * w;
-    if (h < 0 || w < 0 || half < 0 || npx > 0x7fffffffLL || (npx > 0 && (!pts || !nrm || !prio || !free_px || !owner)))
-        return fail(ctx, F3D_ERR_INVALID, "patch_seeds: bad arguments");
-    if (rounds) *rounds = 0;
-    if (npx == 0) return F3D_OK;
-    void *dp, *dn, *dprio, *dfree, *dstat, *down;
-    if ((rc = ensure(ctx, SLOT_MASKS, (size_t)npx * 24, &dp)) || (rc = ensure(ctx, SLOT_VIEWS, (size_t)npx * 24, &dn)) ||
-        (rc = ensure(ctx, SLOT_AUX0, (size_t)npx * 4, &dprio)) || (rc = ensure(ctx, SLOT_AUX1, (size_t)npx, &dfree)) ||
-        (rc = ensure(ctx, SLOT_PATCH, (size_t)npx * 4 + 256, &dstat)) || (rc = ensure(ctx, SLOT_OUT0, (size_t)npx * 4, &down)))
-        return rc;
-    hipStream_t s = ctx->stream;
-    F3D_HIP(ctx, hipMemcpyAsync(dp, pts, (size_t)npx * 24, hipMemcpyHostToDevice, s));
-    F3D_HIP(ctx, hipMemcpyAsync(dn, nrm, (size_t)npx * 24, hipMemcpyHostToDevice, s));
-    F3D_HIP(ctx, hipMemcpyAsync(dprio, prio, (size_t)npx * 4, hipMemcpyHostToDevice, s));
-    F3D_HIP(ctx, hipMemcpyAsync(dfree, free_px, (size_t)npx, hipMemcpyHostToDevice, s));
-    int r = 0;
-    int32_t* counter = (int32_t*)((char*)dstat + (((size_t)npx * 4 + 63) & ~(size_t)63));
-    F3D_HIP(ctx, f3d_launch_patch_seeds((const double*)dp, (const double*)dn, (const int32_t*)dprio, (const uint8_t*)dfree, h, w, half, radius,
-                                        min_cosine, (int32_t*)dstat, (int32_t*)down, counter, &r, s));
-    F3D_HIP(ctx, hipMemcpyAsync(owner, down, (size_t)npx * 4, hipMemcpyDeviceToHost, s));
-    F3D_HIP(ctx, hipStreamSynchronize(s));
-    if (rounds) *rounds = r;
-    return F3D_OK;
+    staging st(ctx);
+    const int32_t* duv = st.in(SLOT_AUX0, uv, (size_t)m * 8);
+    const double* dsp = st.in(SLOT_XYZ, seed_pts, (size_t)m * 24);
+    const double* dsn = st.in(SLOT_OUT1, seed_nrm, (size_t)m * 24);
+    const double* dqp = st.in(SLOT_MASKS, q_pts, (size_t)npx * 24);
+    const double* dqn = st.in(SLOT_VIEWS, q_nrm, (size_t)npx * 24);
+    const uint8_t* dfree = st.in(SLOT_AUX1, free_px, (size_t)npx);
+    int32_t* down = st.out(SLOT_OUT0, owner, (size_t)npx * 4);
+    if (!st.rc) st.rc = f3d_patch_owner_dev(ctx, duv, m, h, w, half, radius, min_cosine, dsp, dsn, dqp, dqn, dfree, down, ctx->stream);
+    return st.finish();
 }
 
 // The matching of one frame of Fusion.fuse with the ordered sums of what every seed takes: the frame is uploaded once, the owner and
@@ -1243,36 +1184,23 @@ int f3d_patch_match(f3d_ctx* ctx, const int32_t* uv, int64_t m, int h, int w, in
         (npx > 0 && (!q_pts || !q_nrm || !free_px || !owner)))
         return fail(ctx, F3D_ERR_INVALID, "patch_match: bad arguments");
     if (npx == 0) return F3D_OK;
-    void *duv, *dsp, *dsn, *dqp, *dqn, *dqc, *dfree, *down, *dsum, *scratch;
-    if ((rc = ensure(ctx, SLOT_AUX0, (size_t)m * 8 + 8, &duv)) || (rc = ensure(ctx, SLOT_XYZ, (size_t)m * 24 + 8, &dsp)) ||
-        (rc = ensure(ctx, SLOT_OUT1, (size_t)m * 24 + 8, &dsn)) || (rc = ensure(ctx, SLOT_MASKS, (size_t)npx * 24, &dqp)) ||
-        (rc = ensure(ctx, SLOT_VIEWS, (size_t)npx * 24, &dqn)) || (rc = ensure(ctx, SLOT_TILED_MASKS, (size_t)npx * 24, &dqc)) ||
-        (rc = ensure(ctx, SLOT_AUX1, (size_t)npx, &dfree)) || (rc = ensure(ctx, SLOT_OUT0, (size_t)npx * 4, &down)) ||
-        (rc = ensure(ctx, SLOT_GRAPH, (size_t)m * 76 + 16, &dsum)) || (rc = ensure(ctx, SLOT_PATCH, f3d_patch_scratch_bytes(h, w, m), &scratch)))
-        return rc;
-    hipStream_t s = ctx->stream;
-    if (m) {
-        F3D_HIP(ctx, hipMemcpyAsync(duv, uv, (size_t)m * 8, hipMemcpyHostToDevice, s));
-        F3D_HIP(ctx, hipMemcpyAsync(dsp, seed_pts, (size_t)m * 24, hipMemcpyHostToDevice, s));
-        F3D_HIP(ctx, hipMemcpyAsync(dsn, seed_nrm, (size_t)m * 24, hipMemcpyHostToDevice, s));
-    }
-    F3D_HIP(ctx, hipMemcpyAsync(dqp, q_pts, (size_t)npx * 24, hipMemcpyHostToDevice, s));
-    F3D_HIP(ctx, hipMemcpyAsync(dqn, q_nrm, (size_t)npx * 24, hipMemcpyHostToDevice, s));
-    if (q_clr) F3D_HIP(ctx, hipMemcpyAsync(dqc, q_clr, (size_t)npx * 24, hipMemcpyHostToDevice, s));
-    F3D_HIP(ctx, hipMemcpyAsync(dfree, free_px, (size_t)npx, hipMemcpyHostToDevice, s));
-    F3D_HIP(ctx, f3d_launch_patch_owner((const int32_t*)duv, m, h, w, half, radius, min_cosine, (const double*)dsp, (const double*)dsn, (const double*)dqp,
-                                        (const double*)dqn, (const uint8_t*)dfree, (int32_t*)down, scratch, s));
-    double* dsums = (double*)dsum;
-    int32_t* dcnt = (int32_t*)((char*)dsum + (((size_t)m * 72 + 15) & ~(size_t)15));
-    F3D_HIP(ctx, f3d_launch_patch_sums((const int32_t*)down, (const int32_t*)duv, m, h, w, half, (const double*)dqp, (const double*)dqn,
-                                       q_clr ? (const double*)dqc : nullptr, dsums, dcnt, s));
-    F3D_HIP(ctx, hipMemcpyAsync(owner, down, (size_t)npx * 4, hipMemcpyDeviceToHost, s));
-    if (m) {
-        F3D_HIP(ctx, hipMemcpyAsync(sums, dsums, (size_t)m * 72, hipMemcpyDeviceToHost, s));
-        F3D_HIP(ctx, hipMemcpyAsync(counts, dcnt, (size_t)m * 4, hipMemcpyDeviceToHost, s));
-    }
-    F3D_HIP(ctx, hipStreamSynchronize(s));
-    return F3D_OK;
+    staging st(ctx);
+    const int32_t* duv = st.in(SLOT_AUX0, uv, (size_t)m * 8);
+    const double* dsp = st.in(SLOT_XYZ, seed_pts, (size_t)m * 24);
+    const double* dsn = st.in(SLOT_OUT1, seed_nrm, (size_t)m * 24);
+    const double* dqp = st.in(SLOT_MASKS, q_pts, (size_t)npx * 24);
+    const double* dqn = st.in(SLOT_VIEWS, q_nrm, (size_t)npx * 24);
+    const double* dqc = st.in(SLOT_TILED_MASKS, q_clr, (size_t)npx * 24);
+    const uint8_t* dfree = st.in(SLOT_AUX1, free_px, (size_t)npx);
+    int32_t* down = st.out(SLOT_OUT0, owner, (size_t)npx * 4);
+    char* dsums = (char*)st.slot(SLOT_GRAPH, (size_t)m * 76 + 16);              // sums [m, 9], then the counts (16-byte aligned)
+    if (st.rc) return st.rc;
+    int32_t* dcnt = (int32_t*)(dsums + (((size_t)m * 72 + 15) & ~(size_t)15));
+    st.back(sums, dsums, (size_t)m * 72);
+    st.back(counts, dcnt, (size_t)m * 4);
+    st.rc = f3d_patch_match_dev(ctx, duv, m, h, w, half, radius, min_cosine, dsp, dsn, dqp, dqn, q_clr ? dqc : nullptr, dfree, down,
+                                (double*)dsums, dcnt, ctx->stream);
+    return st.finish();
 }
 
 // patch_downsample with the ordered sums of every seed's members (sums [h*w, 9], counts [h*w]; only the self-owning pixels carry values)
@@ -1285,32 +1213,21 @@ int f3d_patch_seeds_sums(f3d_ctx* ctx, const double* pts, const double* nrm, con
         return fail(ctx, F3D_ERR_INVALID, "patch_seeds_sums: bad arguments");
     if (rounds) *rounds = 0;
     if (npx == 0) return F3D_OK;
-    void *dp, *dn, *dc, *dprio, *dfree, *dstat, *down, *dsum;
-    if ((rc = ensure(ctx, SLOT_MASKS, (size_t)npx * 24, &dp)) || (rc = ensure(ctx, SLOT_VIEWS, (size_t)npx * 24, &dn)) ||
-        (rc = ensure(ctx, SLOT_TILED_MASKS, (size_t)npx * 24, &dc)) || (rc = ensure(ctx, SLOT_AUX0, (size_t)npx * 4, &dprio)) ||
-        (rc = ensure(ctx, SLOT_AUX1, (size_t)npx, &dfree)) || (rc = ensure(ctx, SLOT_PATCH, (size_t)npx * 4 + 256, &dstat)) ||
-        (rc = ensure(ctx, SLOT_OUT0, (size_t)npx * 4, &down)) || (rc = ensure(ctx, SLOT_GRAPH, (size_t)npx * 76 + 16, &dsum)))
-        return rc;
-    hipStream_t s = ctx->stream;
-    F3D_HIP(ctx, hipMemcpyAsync(dp, pts, (size_t)npx * 24, hipMemcpyHostToDevice, s));
-    F3D_HIP(ctx, hipMemcpyAsync(dn, nrm, (size_t)npx * 24, hipMemcpyHostToDevice, s));
-    if (clr) F3D_HIP(ctx, hipMemcpyAsync(dc, clr, (size_t)npx * 24, hipMemcpyHostToDevice, s));
-    F3D_HIP(ctx, hipMemcpyAsync(dprio, prio, (size_t)npx * 4, hipMemcpyHostToDevice, s));
-    F3D_HIP(ctx, hipMemcpyAsync(dfree, free_px, (size_t)npx, hipMemcpyHostToDevice, s));
-    int r = 0;
-    int32_t* counter = (int32_t*)((char*)dstat + (((size_t)npx * 4 + 63) & ~(size_t)63));
-    F3D_HIP(ctx, f3d_launch_patch_seeds((const double*)dp, (const double*)dn, (const int32_t*)dprio, (const uint8_t*)dfree, h, w, half, radius,
-                                        min_cosine, (int32_t*)dstat, (int32_t*)down, counter, &r, s));
-    double* dsums = (double*)dsum;
-    int32_t* dcnt = (int32_t*)((char*)dsum + (((size_t)npx * 72 + 15) & ~(size_t)15));
-    F3D_HIP(ctx, f3d_launch_patch_sums((const int32_t*)down, nullptr, npx, h, w, half, (const double*)dp, (const double*)dn, clr ? (const double*)dc : nullptr,
-                                       dsums, dcnt, s));
-    F3D_HIP(ctx, hipMemcpyAsync(owner, down, (size_t)npx * 4, hipMemcpyDeviceToHost, s));
-    F3D_HIP(ctx, hipMemcpyAsync(sums, dsums, (size_t)npx * 72, hipMemcpyDeviceToHost, s));
-    F3D_HIP(ctx, hipMemcpyAsync(counts, dcnt, (size_t)npx * 4, hipMemcpyDeviceToHost, s));
-    F3D_HIP(ctx, hipStreamSynchronize(s));
-    if (rounds) *rounds = r;
-    return F3D_OK;
+    staging st(ctx);
+    const double* dp = st.in(SLOT_MASKS, pts, (size_t)npx * 24);
+    const double* dn = st.in(SLOT_VIEWS, nrm, (size_t)npx * 24);
+    const double* dc = st.in(SLOT_TILED_MASKS, clr, (size_t)npx * 24);
+    const int32_t* dprio = st.in(SLOT_AUX0, prio, (size_t)npx * 4);
+    const uint8_t* dfree = st.in(SLOT_AUX1, free_px, (size_t)npx);
+    int32_t* down = st.out(SLOT_OUT0, owner, (size_t)npx * 4);
+    char* dsums = (char*)st.slot(SLOT_GRAPH, (size_t)npx * 76 + 16);            // sums [h*w, 9], then the counts (16-byte aligned)
+    if (st.rc) return st.rc;
+    int32_t* dcnt = (int32_t*)(dsums + (((size_t)npx * 72 + 15) & ~(size_t)15));
+    st.back(sums, dsums, (size_t)npx * 72);
+    st.back(counts, dcnt, (size_t)npx * 4);
+    st.rc = f3d_patch_seeds_sums_dev(ctx, dp, dn, clr ? dc : nullptr, dprio, dfree, h, w, half, radius, min_cosine, down, (double*)dsums, dcnt,
+                                     rounds, ctx->stream);
+    return st.finish();
 }
 
 int f3d_patch_match_dev(f3d_ctx* ctx, const int32_t* uv, int64_t m, int h, int w, int half, double radius, double min_cosine,
@@ -1418,6 +1335,22 @@ int f3d_fusion_new_seeds_dev(f3d_ctx* ctx, const int32_t* owner, const int32_t* 
 // ---------------------------------------------------------------------------------------------
 // (f)#1 adjacency: KDTree(points).query_radius(points, r) (fusion.py:374-375) as CSR
 // ---------------------------------------------------------------------------------------------
+// The one blocking readback of the grid builders: the bounding box of the cloud, as lo and ext = hi - lo.  NaN or infinity in the
+// cloud, or an extent beyond 1e300, is F3D_ERR_INVALID (`op` names the operation).
+static int cloud_bbox(f3d_ctx* ctx, const void* xyz, f3d_dtype dtype, int64_t n, hipStream_t s, const char* op, double lo[3], double ext[3]) {
+    void* dbox;
+    int rc = ensure(ctx, SLOT_GRAPH_BBOX, f3d_graph_bbox_bytes(), &dbox); if (rc) return rc;
+    int nb = 0;
+    F3D_HIP(ctx, f3d_launch_graph_bbox(xyz, dtype, n, dbox, &nb, s));
+    std::vector<char> hbox(f3d_graph_bbox_bytes());
+    F3D_HIP(ctx, hipMemcpyAsync(hbox.data(), dbox, hbox.size(), hipMemcpyDeviceToHost, s));
+    F3D_HIP(ctx, hipStreamSynchronize(s));
+    double hi[3];
+    if (f3d_graph_reduce_bbox(hbox.data(), nb, lo, hi)) return fail(ctx, F3D_ERR_INVALID, "%s: the cloud contains NaN or infinity", op);
+    for (int c = 0; c < 3; ++c) { ext[c] = hi[c] - lo[c]; if (!(ext[c] < 1e300)) return fail(ctx, F3D_ERR_INVALID, "%s: extent overflow", op); }
+    return F3D_OK;
+}
+
 int f3d_radius_graph_count_dev(f3d_ctx* ctx, const void* xyz, f3d_dtype dtype, int64_t n, double radius, int64_t* offsets,
                                int64_t* nnz, void* stream) {
     int rc = enter(ctx); if (rc) return rc;
@@ -1426,22 +1359,12 @@ int f3d_radius_graph_count_dev(f3d_ctx* ctx, const void* xyz, f3d_dtype dtype, i
     *nnz = 0; ctx->graph_n = -1;
     if (n == 0) return F3D_OK;
     hipStream_t s = pick(ctx, stream);
-    void* dbox;
-    if ((rc = ensure(ctx, SLOT_GRAPH_BBOX, f3d_graph_bbox_bytes(), &dbox))) return rc;
-    int nb = 0;
-    F3D_HIP(ctx, f3d_launch_graph_bbox(xyz, dtype, n, dbox, &nb, s));
-    std::vector<char> hbox(f3d_graph_bbox_bytes());
-    F3D_HIP(ctx, hipMemcpyAsync(hbox.data(), dbox, hbox.size(), hipMemcpyDeviceToHost, s));
-    F3D_HIP(ctx, hipStreamSynchronize(s));
-    double lo[3], hi[3];
-    if (f3d_graph_reduce_bbox(hbox.data(), nb, lo, hi))
-        return fail(ctx, F3D_ERR_INVALID, "radius_graph: the cloud contains NaN or infinity (sklearn's KDTree raises ValueError)");
+    double lo[3], ext[3];
+    if ((rc = cloud_bbox(ctx, xyz, dtype, n, s, "radius_graph", lo, ext))) return rc;     // NaN: sklearn's KDTree raises ValueError
     // cell edge: a hair above the radius (two points within r are then provably in adjacent cells whatever the rounding of
     // the cell index), grown until every axis has <= 1024 cells and the table <= 2^24 cells
     f3d_graphgrid g;
     double cell = radius * 1.000001 + 1e-300;
-    double ext[3];
-    for (int c = 0; c < 3; ++c) { ext[c] = hi[c] - lo[c]; if (!(ext[c] < 1e300)) return fail(ctx, F3D_ERR_INVALID, "radius_graph: extent overflow"); }
     for (;;) {
         double cells = 1.0; bool ok = true;
         for (int c = 0; c < 3; ++c) { const double d = floor(ext[c] / cell) + 1.0; if (!(d <= 1024.0)) ok = false; cells *= d; }
@@ -1475,15 +1398,11 @@ int f3d_radius_graph_count(f3d_ctx* ctx, const void* xyz, f3d_dtype dtype, int64
     if (n < 0 || !nnz || (n > 0 && (!xyz || !offsets))) return fail(ctx, F3D_ERR_INVALID, "radius_graph: bad arguments");
     *nnz = 0;
     if (n == 0) { ctx->graph_n = 0; return F3D_OK; }
-    void *dxyz, *doffs;
-    if ((rc = ensure(ctx, SLOT_XYZ, xyz_bytes(dtype, n), &dxyz))) return rc;
-    if ((rc = ensure(ctx, SLOT_OUT1, (size_t)(n + 1) * 8, &doffs))) return rc;
-    hipStream_t s = ctx->stream;
-    F3D_HIP(ctx, hipMemcpyAsync(dxyz, xyz, xyz_bytes(dtype, n), hipMemcpyHostToDevice, s));
-    if ((rc = f3d_radius_graph_count_dev(ctx, dxyz, dtype, n, radius, (int64_t*)doffs, nnz, s))) return rc;
-    F3D_HIP(ctx, hipMemcpyAsync(offsets, doffs, (size_t)(n + 1) * 8, hipMemcpyDeviceToHost, s));
-    F3D_HIP(ctx, hipStreamSynchronize(s));
-    return F3D_OK;
+    staging st(ctx);
+    const void* dxyz = st.in(SLOT_XYZ, xyz, xyz_bytes(dtype, n));
+    int64_t* doffs = st.out(SLOT_OUT1, offsets, (size_t)(n + 1) * 8);   // f3d_radius_graph_fill reads them there
+    if (!st.rc) st.rc = f3d_radius_graph_count_dev(ctx, dxyz, dtype, n, radius, doffs, nnz, ctx->stream);
+    return st.finish();
 }
 
 int f3d_radius_graph_fill(f3d_ctx* ctx, int64_t n, int32_t* nbrs) {
@@ -1497,12 +1416,10 @@ int f3d_radius_graph_fill(f3d_ctx* ctx, int64_t n, int32_t* nbrs) {
     F3D_HIP(ctx, hipStreamSynchronize(s));
     if (nnz == 0) return F3D_OK;
     if (!nbrs) return fail(ctx, F3D_ERR_INVALID, "radius_graph_fill: nbrs is NULL");
-    void* dnb;
-    if ((rc = ensure(ctx, SLOT_MASKS, (size_t)nnz * 4, &dnb))) return rc;
-    if ((rc = f3d_radius_graph_fill_dev(ctx, n, doffs, (int32_t*)dnb, s))) return rc;
-    F3D_HIP(ctx, hipMemcpyAsync(nbrs, dnb, (size_t)nnz * 4, hipMemcpyDeviceToHost, s));
-    F3D_HIP(ctx, hipStreamSynchronize(s));
-    return F3D_OK;
+    staging st(ctx);
+    int32_t* dnb = st.out(SLOT_MASKS, nbrs, (size_t)nnz * 4);
+    if (!st.rc) st.rc = f3d_radius_graph_fill_dev(ctx, n, doffs, dnb, s);
+    return st.finish();
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1520,23 +1437,15 @@ int f3d_estimate_normals_batch_dev(f3d_ctx* ctx, const double* xyz, int nframes,
     if (total == 0) return F3D_OK;
     if (!xyz || !normals || (orient && !cam_centres)) return fail(ctx, F3D_ERR_INVALID, "estimate_normals: bad arguments (NULL)");
     hipStream_t s = pick(ctx, stream);
-    void *dbox, *scratch, *dcams = nullptr;
-    if ((rc = ensure(ctx, SLOT_GRAPH_BBOX, f3d_graph_bbox_bytes(), &dbox))) return rc;
+    void *scratch, *dcams = nullptr;
     if ((rc = ensure(ctx, SLOT_NRM, f3d_normals_scratch_bytes(total), &scratch))) return rc;
     if (orient) {
         // staged before the readback below, which therefore also completes this upload from pageable memory
         if ((rc = ensure(ctx, SLOT_NRM_CAMS, (size_t)nframes * 24, &dcams))) return rc;
         F3D_HIP(ctx, hipMemcpyAsync(dcams, cam_centres, (size_t)nframes * 24, hipMemcpyHostToDevice, s));
     }
-    // the one blocking readback: bounding box of the batch (grid) and the count of non-finite coordinates
-    int nb = 0;
-    F3D_HIP(ctx, f3d_launch_graph_bbox(xyz, F3D_F64, total, dbox, &nb, s));
-    std::vector<char> hbox(f3d_graph_bbox_bytes());
-    F3D_HIP(ctx, hipMemcpyAsync(hbox.data(), dbox, hbox.size(), hipMemcpyDeviceToHost, s));
-    F3D_HIP(ctx, hipStreamSynchronize(s));
-    double lo[3], hi[3], ext[3];
-    if (f3d_graph_reduce_bbox(hbox.data(), nb, lo, hi)) return fail(ctx, F3D_ERR_INVALID, "estimate_normals: the cloud contains NaN or infinity");
-    for (int c = 0; c < 3; ++c) { ext[c] = hi[c] - lo[c]; if (!(ext[c] < 1e300)) return fail(ctx, F3D_ERR_INVALID, "estimate_normals: extent overflow"); }
+    double lo[3], ext[3];
+    if ((rc = cloud_bbox(ctx, xyz, F3D_F64, total, s, "estimate_normals", lo, ext))) return rc;
     // cell edge a hair above the radius (two points within it are in adjacent cells whatever the rounding of the cell index), grown
     // until frame + cell coordinates fit a 63-bit key.  No table over the cells: the key space may be sparse.
     int fbits = 0; while (((int64_t)1 << fbits) < nframes) ++fbits;
@@ -1572,21 +1481,13 @@ int f3d_estimate_normals(f3d_ctx* ctx, const double* xyz, int64_t n, const doubl
         return fail(ctx, F3D_ERR_INVALID, "estimate_normals: max_nn %d outside [1, %d]", max_nn, F3D_NORMALS_MAX_NN);
     if (n == 0) return F3D_OK;
     if (!xyz || !normals || (orient && !cam_centre)) return fail(ctx, F3D_ERR_INVALID, "estimate_normals: bad arguments (NULL)");
-    void *dxyz, *dnrm, *dcnt = nullptr, *dnb = nullptr;
-    if ((rc = ensure(ctx, SLOT_XYZ, (size_t)n * 24, &dxyz))) return rc;
-    if ((rc = ensure(ctx, SLOT_OUT0, (size_t)n * 24, &dnrm))) return rc;
-    if (counts && (rc = ensure(ctx, SLOT_OUT1, (size_t)n * 4, &dcnt))) return rc;
-    if (neighbours && (rc = ensure(ctx, SLOT_MASKS, (size_t)n * max_nn * 4, &dnb))) return rc;
-    hipStream_t s = ctx->stream;
-    F3D_HIP(ctx, hipMemcpyAsync(dxyz, xyz, (size_t)n * 24, hipMemcpyHostToDevice, s));
-    if ((rc = f3d_estimate_normals_batch_dev(ctx, (const double*)dxyz, 1, n, cam_centre, radius, max_nn, orient, (double*)dnrm,
-                                             (int32_t*)dcnt, (int32_t*)dnb, s)))
-        return rc;
-    F3D_HIP(ctx, hipMemcpyAsync(normals, dnrm, (size_t)n * 24, hipMemcpyDeviceToHost, s));
-    if (counts) F3D_HIP(ctx, hipMemcpyAsync(counts, dcnt, (size_t)n * 4, hipMemcpyDeviceToHost, s));
-    if (neighbours) F3D_HIP(ctx, hipMemcpyAsync(neighbours, dnb, (size_t)n * max_nn * 4, hipMemcpyDeviceToHost, s));
-    F3D_HIP(ctx, hipStreamSynchronize(s));
-    return F3D_OK;
+    staging st(ctx);
+    const double* dxyz = st.in(SLOT_XYZ, xyz, (size_t)n * 24);
+    double* dnrm = st.out(SLOT_OUT0, normals, (size_t)n * 24);
+    int32_t* dcnt = st.out(SLOT_OUT1, counts, (size_t)n * 4);
+    int32_t* dnb = st.out(SLOT_MASKS, neighbours, (size_t)n * max_nn * 4);
+    if (!st.rc) st.rc = f3d_estimate_normals_batch_dev(ctx, dxyz, 1, n, cam_centre, radius, max_nn, orient, dnrm, dcnt, dnb, ctx->stream);
+    return st.finish();
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1663,22 +1564,18 @@ int f3d_obb_fit(f3d_ctx* ctx, const double* pts, const int64_t* start, int nfit,
     const int64_t total = start[nfit];
     if (total < 0 || start[0] != 0 || (total > 0 && !pts)) return fail(ctx, F3D_ERR_INVALID, "obb_fit: start must run from 0 to the number of points");
     for (int k = 0; k < nfit; ++k) if (start[k + 1] < start[k]) return fail(ctx, F3D_ERR_INVALID, "obb_fit: start must be non-decreasing");
-    void *dpts, *dstart, *dboxes, *dstatus, *dvert, *dnv;
-    if ((rc = ensure(ctx, SLOT_XYZ, (size_t)total * 24, &dpts)) || (rc = ensure(ctx, SLOT_AUX0, (size_t)(nfit + 1) * 8, &dstart)) ||
-        (rc = ensure(ctx, SLOT_OUT0, (size_t)nfit * sizeof(f3d_obb), &dboxes)) || (rc = ensure(ctx, SLOT_AUX1, (size_t)nfit * 8, &dstatus)) ||
-        (rc = ensure(ctx, SLOT_OUT1, (size_t)total, &dvert)))
-        return rc;
-    dnv = (char*)dstatus + (size_t)nfit * 4;
-    hipStream_t s = ctx->stream;
-    if (total) F3D_HIP(ctx, hipMemcpyAsync(dpts, pts, (size_t)total * 24, hipMemcpyHostToDevice, s));
-    F3D_HIP(ctx, hipMemcpyAsync(dstart, start, (size_t)(nfit + 1) * 8, hipMemcpyHostToDevice, s));
-    if ((rc = f3d_obb_fit_dev(ctx, (const double*)dpts, (const int64_t*)dstart, nfit, total, (double*)dboxes, (int32_t*)dstatus, (uint8_t*)dvert, (int32_t*)dnv, s))) return rc;
-    F3D_HIP(ctx, hipMemcpyAsync(boxes, dboxes, (size_t)nfit * sizeof(f3d_obb), hipMemcpyDeviceToHost, s));
-    F3D_HIP(ctx, hipMemcpyAsync(status, dstatus, (size_t)nfit * 4, hipMemcpyDeviceToHost, s));
-    if (isvert && total) F3D_HIP(ctx, hipMemcpyAsync(isvert, dvert, (size_t)total, hipMemcpyDeviceToHost, s));
-    if (nvert) F3D_HIP(ctx, hipMemcpyAsync(nvert, dnv, (size_t)nfit * 4, hipMemcpyDeviceToHost, s));
-    F3D_HIP(ctx, hipStreamSynchronize(s));
-    return F3D_OK;
+    staging st(ctx);
+    const double* dpts = st.in(SLOT_XYZ, pts, (size_t)total * 24);
+    const int64_t* dstart = st.in(SLOT_AUX0, start, (size_t)(nfit + 1) * 8);
+    double* dboxes = st.out(SLOT_OUT0, boxes, (size_t)nfit * sizeof(f3d_obb));
+    int32_t* dstatus = (int32_t*)st.slot(SLOT_AUX1, (size_t)nfit * 8);            // status, then the vertex counts
+    uint8_t* dvert = (uint8_t*)st.slot(SLOT_OUT1, (size_t)total);                 // written whether or not the caller wants it
+    if (st.rc) return st.rc;
+    st.back(status, dstatus, (size_t)nfit * 4);
+    st.back(isvert, dvert, (size_t)total);
+    st.back(nvert, dstatus + nfit, (size_t)nfit * 4);
+    st.rc = f3d_obb_fit_dev(ctx, dpts, dstart, nfit, total, dboxes, dstatus, dvert, dstatus + nfit, ctx->stream);
+    return st.finish();
 }
 
 // host-pointer sequence; the grouping (and, from the extremes call on, the cloud) stays in the context between the calls
@@ -1686,16 +1583,14 @@ int f3d_group_by_id(f3d_ctx* ctx, const int64_t* ids, int64_t n, int64_t nids, i
     int rc = enter(ctx); if (rc) return rc;
     if (n < 0 || nids < 0 || !starts || (n > 0 && (!ids || !order))) return fail(ctx, F3D_ERR_INVALID, "group_by_id: bad arguments");
     ctx->grp_n = -1;
-    void *dids, *dorder, *dkeys, *dstarts;
-    if ((rc = ensure(ctx, SLOT_OUT0, (size_t)n * 8, &dids)) || (rc = ensure(ctx, SLOT_GRP_ORDER, (size_t)n * 4, &dorder)) ||
-        (rc = ensure(ctx, SLOT_GRP_KEYS, (size_t)n * 4, &dkeys)) || (rc = ensure(ctx, SLOT_GRP_STARTS, (size_t)(nids + 2) * 8, &dstarts)))
-        return rc;
-    hipStream_t s = ctx->stream;
-    if (n) F3D_HIP(ctx, hipMemcpyAsync(dids, ids, (size_t)n * 8, hipMemcpyHostToDevice, s));
-    if ((rc = f3d_group_by_id_dev(ctx, (const int64_t*)dids, n, nids, (int32_t*)dorder, (uint32_t*)dkeys, (int64_t*)dstarts, s))) return rc;
-    if (n) F3D_HIP(ctx, hipMemcpyAsync(order, dorder, (size_t)n * 4, hipMemcpyDeviceToHost, s));
-    F3D_HIP(ctx, hipMemcpyAsync(starts, dstarts, (size_t)(nids + 2) * 8, hipMemcpyDeviceToHost, s));
-    F3D_HIP(ctx, hipStreamSynchronize(s));
+    staging st(ctx);
+    const int64_t* dids = st.in(SLOT_OUT0, ids, (size_t)n * 8);
+    int32_t* dorder = (int32_t*)st.slot(SLOT_GRP_ORDER, (size_t)n * 4);
+    st.back(order, dorder, (size_t)n * 4);
+    uint32_t* dkeys = (uint32_t*)st.slot(SLOT_GRP_KEYS, (size_t)n * 4);
+    int64_t* dstarts = st.out(SLOT_GRP_STARTS, starts, (size_t)(nids + 2) * 8);
+    if (!st.rc) st.rc = f3d_group_by_id_dev(ctx, dids, n, nids, dorder, dkeys, dstarts, ctx->stream);
+    if ((rc = st.finish())) return rc;
     ctx->grp_n = n; ctx->grp_nids = nids;
     return F3D_OK;
 }
@@ -1705,15 +1600,13 @@ int f3d_obb_extremes(f3d_ctx* ctx, const void* xyz, f3d_dtype dtype, int64_t n, 
     if (n != ctx->grp_n || n < 0) return fail(ctx, F3D_ERR_INVALID, "obb_extremes: call f3d_group_by_id for this cloud first");
     const int64_t nids = ctx->grp_nids;
     if ((n > 0 && !xyz) || (nids > 0 && !extremes)) return fail(ctx, F3D_ERR_INVALID, "obb_extremes: bad arguments");
-    void *dxyz, *dext;
-    if ((rc = ensure(ctx, SLOT_XYZ, xyz_bytes(dtype, n), &dxyz)) || (rc = ensure(ctx, SLOT_OBB_CAND, (size_t)(n > nids * F3D_OBB_NDIR ? n : nids * F3D_OBB_NDIR) * 4 + (size_t)nids * 4, &dext)))
-        return rc;
-    hipStream_t s = ctx->stream;
-    if (n) F3D_HIP(ctx, hipMemcpyAsync(dxyz, xyz, xyz_bytes(dtype, n), hipMemcpyHostToDevice, s));
-    if ((rc = f3d_obb_extremes_dev(ctx, dxyz, dtype, n, (const int32_t*)ctx->slot[SLOT_GRP_ORDER], (const uint32_t*)ctx->slot[SLOT_GRP_KEYS], nids,
-                                   (int32_t*)dext, s))) return rc;
-    if (nids) F3D_HIP(ctx, hipMemcpyAsync(extremes, dext, (size_t)nids * F3D_OBB_NDIR * 4, hipMemcpyDeviceToHost, s));
-    F3D_HIP(ctx, hipStreamSynchronize(s));
+    staging st(ctx);
+    const void* dxyz = st.in(SLOT_XYZ, xyz, xyz_bytes(dtype, n));                  // stays there for f3d_obb_hull_filter
+    int32_t* dext = (int32_t*)st.slot(SLOT_OBB_CAND, (size_t)(n > nids * F3D_OBB_NDIR ? n : nids * F3D_OBB_NDIR) * 4 + (size_t)nids * 4);
+    st.back(extremes, dext, (size_t)nids * F3D_OBB_NDIR * 4);
+    if (!st.rc) st.rc = f3d_obb_extremes_dev(ctx, dxyz, dtype, n, (const int32_t*)ctx->slot[SLOT_GRP_ORDER], (const uint32_t*)ctx->slot[SLOT_GRP_KEYS],
+                                             nids, dext, ctx->stream);
+    if ((rc = st.finish())) return rc;
     ctx->grp_dtype = dtype;
     return F3D_OK;
 }
@@ -1727,27 +1620,23 @@ int f3d_obb_hull_filter(f3d_ctx* ctx, int64_t n, const int32_t* facet_start, con
     if (nids == 0) return F3D_OK;
     const int64_t nf = facet_start[nids];
     if (nf < 0 || (nf > 0 && !facets) || (n > 0 && !cand)) return fail(ctx, F3D_ERR_INVALID, "obb_hull_filter: bad facet table");
-    void *dfac, *dcand;
-    const size_t fbytes = (size_t)(nids + 1) * 4, ebytes = (size_t)nf * 32, mbytes = (size_t)nids * 8;
-    if ((rc = ensure(ctx, SLOT_OBB_FACETS, ((fbytes + 7) & ~(size_t)7) + ebytes + mbytes + 64, &dfac)) ||
-        (rc = ensure(ctx, SLOT_OBB_CAND, (size_t)(n > nids * F3D_OBB_NDIR ? n : nids * F3D_OBB_NDIR) * 4 + (size_t)nids * 4, &dcand)))
-        return rc;
-    char* base = (char*)dfac;
-    int32_t* dfs = (int32_t*)base;
-    double* deq = (double*)(base + ((fbytes + 7) & ~(size_t)7));
+    const size_t fbytes = (size_t)(nids + 1) * 4, foff = (fbytes + 7) & ~(size_t)7, ebytes = (size_t)nf * 32, mbytes = (size_t)nids * 8;
+    const size_t ncand = (size_t)(n > nids * F3D_OBB_NDIR ? n : nids * F3D_OBB_NDIR);
+    staging st(ctx);
+    char* dfac = (char*)st.slot(SLOT_OBB_FACETS, foff + ebytes + mbytes + 64);          // facet starts, facet planes, margins
+    int32_t* dcand = (int32_t*)st.slot(SLOT_OBB_CAND, ncand * 4 + (size_t)nids * 4);    // candidates, then the count per instance
+    if (st.rc) return st.rc;
+    double* deq = (double*)(dfac + foff);
     double* dmg = deq + 4 * (size_t)nf;
-    int32_t* dcnt = (int32_t*)((char*)dcand + (size_t)(n > nids * F3D_OBB_NDIR ? n : nids * F3D_OBB_NDIR) * 4);
-    hipStream_t s = ctx->stream;
-    F3D_HIP(ctx, hipMemcpyAsync(dfs, facet_start, fbytes, hipMemcpyHostToDevice, s));
-    if (nf) F3D_HIP(ctx, hipMemcpyAsync(deq, facets, ebytes, hipMemcpyHostToDevice, s));
-    F3D_HIP(ctx, hipMemcpyAsync(dmg, margin, mbytes, hipMemcpyHostToDevice, s));
-    if ((rc = f3d_obb_hull_filter_dev(ctx, ctx->slot[SLOT_XYZ], (f3d_dtype)ctx->grp_dtype, n, (const int32_t*)ctx->slot[SLOT_GRP_ORDER],
-                                      (const uint32_t*)ctx->slot[SLOT_GRP_KEYS], (const int64_t*)ctx->slot[SLOT_GRP_STARTS], nids, dfs, deq, dmg,
-                                      (int32_t*)dcand, dcnt, s))) return rc;
-    if (n) F3D_HIP(ctx, hipMemcpyAsync(cand, dcand, (size_t)n * 4, hipMemcpyDeviceToHost, s));
-    F3D_HIP(ctx, hipMemcpyAsync(cand_count, dcnt, (size_t)nids * 4, hipMemcpyDeviceToHost, s));
-    F3D_HIP(ctx, hipStreamSynchronize(s));
-    return F3D_OK;
+    st.put(dfac, facet_start, fbytes);
+    st.put(deq, facets, ebytes);
+    st.put(dmg, margin, mbytes);
+    st.back(cand, dcand, (size_t)n * 4);
+    st.back(cand_count, dcand + ncand, (size_t)nids * 4);
+    if (!st.rc) st.rc = f3d_obb_hull_filter_dev(ctx, ctx->slot[SLOT_XYZ], (f3d_dtype)ctx->grp_dtype, n, (const int32_t*)ctx->slot[SLOT_GRP_ORDER],
+                                                (const uint32_t*)ctx->slot[SLOT_GRP_KEYS], (const int64_t*)ctx->slot[SLOT_GRP_STARTS], nids,
+                                                (const int32_t*)dfac, deq, dmg, dcand, dcand + ncand, ctx->stream);
+    return st.finish();
 }
 
 }  // extern "C"

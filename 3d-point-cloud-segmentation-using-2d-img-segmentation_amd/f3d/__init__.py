@@ -132,7 +132,6 @@ def library():
         'f3d_components_same_class_dev': (i32, [vp, vp, i64, vp, vp, vp, vp, vp]),
         'f3d_patch_owner': (i32, [vp, vp, i64, i32, i32, i32, dbl, dbl, vp, vp, vp, vp, vp, vp]),
         'f3d_patch_owner_dev': (i32, [vp, vp, i64, i32, i32, i32, dbl, dbl, vp, vp, vp, vp, vp, vp, vp]),
-        'f3d_patch_seeds': (i32, [vp, vp, vp, vp, vp, i32, i32, i32, dbl, dbl, vp, vp]),
         'f3d_patch_match': (i32, [vp, vp, i64, i32, i32, i32, dbl, dbl, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
         'f3d_patch_seeds_sums': (i32, [vp, vp, vp, vp, vp, vp, i32, i32, i32, dbl, dbl, vp, vp, vp, vp]),
         'f3d_patch_match_dev': (i32, [vp, vp, i64, i32, i32, i32, dbl, dbl, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
@@ -533,19 +532,6 @@ class Context:
                                               _ptr(qp), _ptr(qn), _ptr(fr), _ptr(owner)))
         return owner
 
-    def patch_seeds(self, frame_pts, frame_normals, prio, free, h, w, half, radius, min_cosine):
-        """Fusion.patch_downsample's seeds and what they take: owner int32 [h*w] (seed pixel index, -1 = nobody), rounds."""
-        qp, qn = _f64(frame_pts, (h * w, 3)), _f64(frame_normals, (h * w, 3))
-        pr = np.ascontiguousarray(prio, dtype=np.int32).reshape(-1)
-        fr = np.ascontiguousarray(free, dtype=np.uint8).reshape(-1)
-        if len(pr) != h * w or len(fr) != h * w:
-            raise ValueError('patch_seeds: prio and free must have h*w entries')
-        owner = np.empty(h * w, np.int32)
-        rounds = C.c_int32(0)
-        self._check(self._lib.f3d_patch_seeds(self._h, _ptr(qp), _ptr(qn), _ptr(pr), _ptr(fr), h, w, int(half), float(radius), float(min_cosine),
-                                              _ptr(owner), C.byref(rounds)))
-        return owner, rounds.value
-
     def patch_match(self, uv, seed_pts, seed_normals, frame_pts, frame_normals, frame_colors, free, h, w, half, radius, min_cosine):
         """patch_owner plus, per seed, the ordered sums of the frame rows it takes: (owner int32 [h*w], sums float64 [m, 9] =
         points | normals | colours, counts int32 [m])."""
@@ -563,7 +549,8 @@ class Context:
         return owner, sums, counts
 
     def patch_seeds_sums(self, frame_pts, frame_normals, frame_colors, prio, free, h, w, half, radius, min_cosine):
-        """patch_seeds plus the ordered sums per seed pixel: (owner int32 [h*w], sums float64 [h*w, 9], counts int32 [h*w], rounds)."""
+        """Fusion.patch_downsample's seeds, what they take and the ordered sums per seed pixel: (owner int32 [h*w] (seed pixel index,
+        -1 = nobody), sums float64 [h*w, 9], counts int32 [h*w], rounds)."""
         qp, qn = _f64(frame_pts, (h * w, 3)), _f64(frame_normals, (h * w, 3))
         qc = None if frame_colors is None else _f64(frame_colors, (h * w, 3))
         pr = np.ascontiguousarray(prio, dtype=np.int32).reshape(-1)
