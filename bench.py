@@ -10,11 +10,17 @@ the masks of the V/N views it "produced" and each step all-gathers the masks ove
 one exchange step, double-buffered: the all-gather of step i+1 runs under the kernels of step i)
 and then fuses its shard.  --weak gives every rank its own --points instead.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--points P] [--filter] [--masks iid|block64] [--weak] [--dump-outputs DIR]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--points P] [--filter] [--masks iid|block64] [--weak] [--dump-outputs DIR] [--full]
 
 Prints ONE JSON line on rank 0 (see README/DESIGN.md for the fields); `ms_per_step` = wall milliseconds of one of the K
 timed steps.  --dump-outputs DIR writes the labels of the last timed step as .npy (the inputs are seeded: two builds run
 with the same arguments can be compared output for output).
+
+A plain run does only what the headline needs: set up, warm up, time the K steps, dump, print.  --full adds everything
+else to the same line: the roofline object (the fused call and the sort timed on their own), the chunked step checked
+against one call, and at N=1 the streaming kernels, the mask / view variants, the C3 end-to-end and C5 merge legs, the
+CPU baselines and the parity of the HIP path with the oracle on the CPU slice (--no-extras, --no-merge and
+--no-cpu-baseline trim it).
 """
 import argparse
 import json
@@ -48,15 +54,16 @@ def parse():
                          'one step, the all-gather split into --chunks view chunks, chunk c+1 on the wire while chunk c votes; coded = chunked with the '
                          'mask coding sharded as well: every rank codes its own V/N masks, CODED planes are all-gathered')
     ap.add_argument('--chunks', type=int, default=2, help='view chunks per rank of --exchange chunked')
-    ap.add_argument('--no-merge', action='store_true', help='skip the C5 bbox-merge leg (50M points, 4096 instances)')
+    ap.add_argument('--full', action='store_true', help='after the headline, also run every other measurement and check (see the module docstring)')
+    ap.add_argument('--no-merge', action='store_true', help='--full: skip the C5 bbox-merge leg (50M points, 4096 instances)')
     ap.add_argument('--views', type=int, default=64)
     ap.add_argument('--size', type=int, default=1024, help='mask width = height')
     ap.add_argument('--masks', default='block64', choices=['block64', 'block64x40', 'block64x96', 'block64x100', 'iid'])
     ap.add_argument('--filter', action='store_true', help='segment with the reference default filter_classes=[86,114,115]')
     ap.add_argument('--f32', action='store_true', help='store xyz as float32 (12 B/point) instead of float64')
-    ap.add_argument('--no-cpu-baseline', action='store_true')
-    ap.add_argument('--no-extras', action='store_true', help='skip the streaming-kernel measurements')
-    ap.add_argument('--cpu-sample', type=int, default=5_000_000, help='points of the CPU-baseline slice (all views)')
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='--full: skip the CPU baselines and the parity check on the CPU slice')
+    ap.add_argument('--no-extras', action='store_true', help='--full: skip the streaming-kernel, variant, end-to-end and merge measurements')
+    ap.add_argument('--cpu-sample', type=int, default=5_000_000, help='--full: points of the CPU-baseline slice (all views)')
     ap.add_argument('--sorted', action='store_true', help='experiment: hand the cloud over already in grid-cell order (host sort)')
     ap.add_argument('--sorted-morton', type=int, default=0, metavar='BITS', help='experiment: hand the cloud over in Morton order with BITS bits per axis (host sort), no sort in the step')
     ap.add_argument('--no-sort', action='store_true', help='do not cell-sort the cloud inside the step')
@@ -625,7 +632,7 @@ def main():
     ctx.take_device_error(stream.cuda_stream)
     deferred = ctx.fuse_deferred(stream.cuda_stream)        # (to the float64 tier, to the exact kernel) in the last step
     chunk_check = None
-    if chunked:                                             # the chunked step against one call over all views, same inputs
+    if chunked and args.full:                               # the chunked step against one call over all views, same inputs
         stepped = classes.clone()
         if coded_x:                                         # (the raw planes of the other ranks, for this check only, in the buffer's order)
             for c in range(args.chunks):
@@ -636,51 +643,53 @@ def main():
         stream.synchronize()
         chunk_check = bool(torch.equal(stepped, classes))
 
-    # dominant kernel alone (k_fuse), HIP events on its launch stream, same resident inputs: with the in-step
-    # sort the step is [sort kernels][k_fuse reading xyz through perm]; both parts are timed on their own.
-    k_iters = max(3, min(args.steps, 10))
-    t_sort = 0.0
-    if flags & f3d.FUSE_SORT:
-        perm_t = torch.empty(n, dtype=torch.int32, device=dev)
-        t_sort = time_kernel(torch, lambda: ctx.cloud_sort_cells_dev(xyz.data_ptr(), dtype, n, None, perm_t.data_ptr(),
-                                                                     stream.cuda_stream), k_iters, stream)
-        t_kernel = time_kernel(torch, lambda: ctx.project_vote_argmax_dev(
-            xyz.data_ptr(), dtype, n, views.data_ptr(), V, masks_full.data_ptr(), S, S, 133, 0.5, flt, classes.data_ptr(), None,
-            stream.cuda_stream, flags=f3d.FUSE_GATHER, perm_ptr=perm_t.data_ptr()), k_iters, stream)
-    else:
-        t_kernel = time_kernel(torch, fuse, k_iters, stream)
     xyz_b = 12 if args.f32 else 24
-    abytes = algorithmic_bytes(n, V, S, S, xyz_b)
-    achieved = abytes / t_kernel / 1e9
-    # HBM traffic of the dominant kernel from the PMC passes of THIS build (scripts/pmc_custom.sh; separate rocprofv3 --pmc runs):
-    # the CSV names the library it was taken with, a different build gets null
-    traffic, traffic_src = None, 'no PMC pass of this build under profiles/ (the CSV names another libf3d_hip.so)'
-    import hashlib
-    lib_sha = hashlib.sha256(f3d.library_path().read_bytes()).hexdigest()[:16]
-    pmc = ROOT / 'profiles' / 'r03_pmc_by_kernel.csv'
-    if (pmc.is_file() and n == 10_000_000 and V == 64 and S == 1024 and not args.f32 and world == 1 and args.masks == 'block64' and
-            not (args.prepared or args.sorted or args.no_sort or args.filter)):      # the counters were taken on the default workload only
-        lines = pmc.read_text().splitlines()
-        if lines and lines[0].strip() == f'# lib_sha16={lib_sha}':
-            vals = {}
-            for line in lines[1:]:
-                parts = line.split(',')
-                if len(parts) >= 3 and parts[0] == 'k_fuse':
-                    vals[parts[1]] = float(parts[2])
-            if 'FETCH_SIZE' in vals and 'WRITE_SIZE' in vals:
-                traffic = int((vals['FETCH_SIZE'] + vals['WRITE_SIZE']) * 1024)
-                traffic_src = (f'profiles/r03_pmc_by_kernel.csv (lib {lib_sha}): (FETCH_SIZE + WRITE_SIZE) KB per k_fuse launch, raw (the x2 '
-                               'FETCH_SIZE correction is calibrated for wide streams, not for 1-byte gathers; L2 misses incl. Infinity-Cache hits)')
-    roofline = dict(bound='hbm', achieved=round(achieved, 2), peak=HBM_PEAK_GBS, unit='GB/s',
-                    frac=round(achieved / HBM_PEAK_GBS, 5), traffic=traffic, traffic_source=traffic_src,
-                    kernel='k_fuse', kernel_ms=round(t_kernel * 1e3, 4), sort_ms=round(t_sort * 1e3, 4),
-                    algorithmic_bytes=abytes,
-                    reference_flop_frac=round(FLOP_PER_POINT_VIEW * n * V / t_kernel / (FP64_VALU_PEAK_TFLOPS * 1e12), 4),
-                    note='kernel_ms = the whole fused call (label presence + mask coding + k_fuse + float64 middle tier + exact '
-                         'kernel), HIP events on its stream.  The fused V-view path is instruction-issue / gather bound, not HBM '
-                         'bound (SURVEY 8(d): HBM-fraction ceiling ~7% at V=64).  reference_flop_frac = 82 flop of the REFERENCE '
-                         'formulation x N x V / t / 78.6 TF fp64 -- NOT a utilisation: ~55% of the (wave, view) pairs are culled and '
-                         'never executed, and the executed arithmetic is float32 (profiles/ has the executed-instruction counters)')
+    roofline = None
+    if args.full:
+        # dominant kernel alone (k_fuse), HIP events on its launch stream, same resident inputs: with the in-step
+        # sort the step is [sort kernels][k_fuse reading xyz through perm]; both parts are timed on their own.
+        k_iters = max(3, min(args.steps, 10))
+        t_sort = 0.0
+        if flags & f3d.FUSE_SORT:
+            perm_t = torch.empty(n, dtype=torch.int32, device=dev)
+            t_sort = time_kernel(torch, lambda: ctx.cloud_sort_cells_dev(xyz.data_ptr(), dtype, n, None, perm_t.data_ptr(),
+                                                                         stream.cuda_stream), k_iters, stream)
+            t_kernel = time_kernel(torch, lambda: ctx.project_vote_argmax_dev(
+                xyz.data_ptr(), dtype, n, views.data_ptr(), V, masks_full.data_ptr(), S, S, 133, 0.5, flt, classes.data_ptr(), None,
+                stream.cuda_stream, flags=f3d.FUSE_GATHER, perm_ptr=perm_t.data_ptr()), k_iters, stream)
+        else:
+            t_kernel = time_kernel(torch, fuse, k_iters, stream)
+        abytes = algorithmic_bytes(n, V, S, S, xyz_b)
+        achieved = abytes / t_kernel / 1e9
+        # HBM traffic of the dominant kernel from the PMC passes of THIS build (scripts/pmc_custom.sh; separate rocprofv3 --pmc runs):
+        # the CSV names the library it was taken with, a different build gets null
+        traffic, traffic_src = None, 'no PMC pass of this build under profiles/ (the CSV names another libf3d_hip.so)'
+        import hashlib
+        lib_sha = hashlib.sha256(f3d.library_path().read_bytes()).hexdigest()[:16]
+        pmc = ROOT / 'profiles' / 'r03_pmc_by_kernel.csv'
+        if (pmc.is_file() and n == 10_000_000 and V == 64 and S == 1024 and not args.f32 and world == 1 and args.masks == 'block64' and
+                not (args.prepared or args.sorted or args.no_sort or args.filter)):      # the counters were taken on the default workload only
+            lines = pmc.read_text().splitlines()
+            if lines and lines[0].strip() == f'# lib_sha16={lib_sha}':
+                vals = {}
+                for line in lines[1:]:
+                    parts = line.split(',')
+                    if len(parts) >= 3 and parts[0] == 'k_fuse':
+                        vals[parts[1]] = float(parts[2])
+                if 'FETCH_SIZE' in vals and 'WRITE_SIZE' in vals:
+                    traffic = int((vals['FETCH_SIZE'] + vals['WRITE_SIZE']) * 1024)
+                    traffic_src = (f'profiles/r03_pmc_by_kernel.csv (lib {lib_sha}): (FETCH_SIZE + WRITE_SIZE) KB per k_fuse launch, raw (the x2 '
+                                   'FETCH_SIZE correction is calibrated for wide streams, not for 1-byte gathers; L2 misses incl. Infinity-Cache hits)')
+        roofline = dict(bound='hbm', achieved=round(achieved, 2), peak=HBM_PEAK_GBS, unit='GB/s',
+                        frac=round(achieved / HBM_PEAK_GBS, 5), traffic=traffic, traffic_source=traffic_src,
+                        kernel='k_fuse', kernel_ms=round(t_kernel * 1e3, 4), sort_ms=round(t_sort * 1e3, 4),
+                        algorithmic_bytes=abytes,
+                        reference_flop_frac=round(FLOP_PER_POINT_VIEW * n * V / t_kernel / (FP64_VALU_PEAK_TFLOPS * 1e12), 4),
+                        note='kernel_ms = the whole fused call (label presence + mask coding + k_fuse + float64 middle tier + exact '
+                             'kernel), HIP events on its stream.  The fused V-view path is instruction-issue / gather bound, not HBM '
+                             'bound (SURVEY 8(d): HBM-fraction ceiling ~7% at V=64).  reference_flop_frac = 82 flop of the REFERENCE '
+                             'formulation x N x V / t / 78.6 TF fp64 -- NOT a utilisation: ~55% of the (wave, view) pairs are culled and '
+                             'never executed, and the executed arithmetic is float32 (profiles/ has the executed-instruction counters)')
 
     out = None
     if rank == 0:
@@ -706,7 +715,7 @@ def main():
             out['dumped_outputs'] = dumped
 
     # secondary, HBM-streaming kernels of the same path (not part of `value`)
-    if rank == 0 and world == 1 and not args.no_extras:
+    if args.full and rank == 0 and world == 1 and not args.no_extras:
         extras = {}
         # the per-point streaming kernels run on a 50M-point cloud (1.2 GB of xyz, 1.65 GB per pass): far beyond the 256 MiB
         # Infinity Cache, so that GB/s is HBM traffic and not cache hits across the timed repeats
@@ -814,16 +823,16 @@ def main():
         del ins, cooc
         out['streaming_kernels'] = extras
 
-    if rank == 0 and world == 1 and not args.no_extras and not (args.prepared or args.sorted or overlap):
+    if args.full and rank == 0 and world == 1 and not args.no_extras and not (args.prepared or args.sorted or overlap):
         out['variants'] = variants_leg(torch, ctx, dev, stream, xyz, dtype, n, views, V, S, flags, perm_ptr)
         if 'share_of_the_cloud_no_exchange' in out['variants']:
             out['share_of_the_cloud_no_exchange'] = out['variants'].pop('share_of_the_cloud_no_exchange')
         out['c3_end_to_end'] = end_to_end_leg(torch, ctx, dev, stream, xyz, dtype, n, views, views_np, V, S, flt, flags, perm_ptr)
 
-    if rank == 0 and world == 1 and not args.no_merge and not args.no_extras:
+    if args.full and rank == 0 and world == 1 and not args.no_merge and not args.no_extras:
         out['merge_bb'] = merge_leg(local)
 
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:          # reported at N=1 only
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:          # reported at N=1 only
         from oracle import np_ref as O
         cb, cls_cpu, pts_cpu, masks_cpu, (K, q, t), want0, wvotes = cpu_baseline(args.cpu_sample, V, S, args.masks, flt)
         out['cpu_baseline'] = cb

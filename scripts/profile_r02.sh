@@ -1,6 +1,6 @@
 #!/bin/bash
 # usage (GPU box): scripts/profile_r02.sh   -- the evidence behind bench.py's roofline object for the library as built:
-#   1. rocprofv3 --kernel-trace --stats of the default `python3 bench.py`            -> gpurun_out/prof_r02/stats/
+#   1. rocprofv3 --kernel-trace --stats of `python3 bench.py --full`                  -> $out/stats/
 #   2. counter passes of the same workload (3 steps), one rocprofv3 run per list      -> gpurun_out/pmc_r02/pN/
 # Counter lists respect the per-block register counts (TCC 4 raw events per pass -- FETCH_SIZE alone is 3 on gfx950, TA / TCP 2):
 # a list that needs more does not fail, the profiled process stalls (profiles/r02_summary.md).  Each run has its own timeout.
@@ -9,7 +9,7 @@ root=$GRAFT_REPO_ROOT
 out=$root/gpurun_out/prof_r02
 mkdir -p $out
 cd /tmp
-timeout -k 10 560 rocprofv3 --kernel-trace --stats --output-format csv -d $out/stats -o r02 -- python3 $root/bench.py > $out/bench_line.json 2> $out/bench_stderr.log || { echo "kernel-trace run failed"; exit 1; }
+timeout -k 10 560 rocprofv3 --kernel-trace --stats --output-format csv -d $out/stats -o r02 -- python3 $root/bench.py --full > $out/bench_line.json 2> $out/bench_stderr.log || { echo "kernel-trace run failed"; exit 1; }
 tail -c 600 $out/bench_line.json; echo
 bash $root/scripts/pmc_custom.sh r02 "" \
   "FETCH_SIZE TCC_HIT_sum" \
