@@ -258,6 +258,19 @@ int quat_inverse(const double q[4], double o[4]) {
     return F3D_OK;
 }
 
+// cell edge of a neighbour grid over a box of extent `ext`: a hair above the radius (two points within it are then provably in adjacent
+// cells whatever the rounding of the cell index), grown by 1.25 until fits(cells per axis) holds; dim receives the cells per axis
+template <typename Fits>
+double neighbour_cell(double radius, const double ext[3], int dim[3], Fits fits) {
+    for (double cell = radius * 1.000001 + 1e-300;; cell *= 1.25) {
+        double d[3];
+        for (int c = 0; c < 3; ++c) d[c] = floor(ext[c] / cell) + 1.0;
+        if (fits(d)) { for (int c = 0; c < 3; ++c) dim[c] = (int)d[c]; return cell; }
+    }
+}
+
+int bits_for(int64_t v) { int b = 0; while (((int64_t)1 << b) < v) ++b; return b; }     // smallest b with 2^b >= v
+
 }  // namespace
 
 static int ensure_table(f3d_ctx* ctx, int64_t hw);
@@ -1361,17 +1374,12 @@ int f3d_radius_graph_count_dev(f3d_ctx* ctx, const void* xyz, f3d_dtype dtype, i
     hipStream_t s = pick(ctx, stream);
     double lo[3], ext[3];
     if ((rc = cloud_bbox(ctx, xyz, dtype, n, s, "radius_graph", lo, ext))) return rc;     // NaN: sklearn's KDTree raises ValueError
-    // cell edge: a hair above the radius (two points within r are then provably in adjacent cells whatever the rounding of
-    // the cell index), grown until every axis has <= 1024 cells and the table <= 2^24 cells
+    // the grid fits when every axis has <= 1024 cells and the table <= 2^24 cells
     f3d_graphgrid g;
-    double cell = radius * 1.000001 + 1e-300;
-    for (;;) {
-        double cells = 1.0; bool ok = true;
-        for (int c = 0; c < 3; ++c) { const double d = floor(ext[c] / cell) + 1.0; if (!(d <= 1024.0)) ok = false; cells *= d; }
-        if (ok && cells <= 16777216.0) break;
-        cell *= 1.25;
-    }
-    for (int c = 0; c < 3; ++c) { g.lo[c] = lo[c]; g.dim[c] = (int)(floor(ext[c] / cell) + 1.0); }
+    const double cell = neighbour_cell(radius, ext, g.dim, [](const double d[3]) {
+        return d[0] <= 1024.0 && d[1] <= 1024.0 && d[2] <= 1024.0 && d[0] * d[1] * d[2] <= 16777216.0;
+    });
+    for (int c = 0; c < 3; ++c) g.lo[c] = lo[c];
     g.inv_cell = 1.0 / cell; g.pad = 0;
     const int64_t ncells = (int64_t)g.dim[0] * g.dim[1] * g.dim[2];
     void* scratch;
@@ -1446,26 +1454,17 @@ int f3d_estimate_normals_batch_dev(f3d_ctx* ctx, const double* xyz, int nframes,
     }
     double lo[3], ext[3];
     if ((rc = cloud_bbox(ctx, xyz, F3D_F64, total, s, "estimate_normals", lo, ext))) return rc;
-    // cell edge a hair above the radius (two points within it are in adjacent cells whatever the rounding of the cell index), grown
-    // until frame + cell coordinates fit a 63-bit key.  No table over the cells: the key space may be sparse.
-    int fbits = 0; while (((int64_t)1 << fbits) < nframes) ++fbits;
+    // the grid fits when frame + cell coordinates fit a 63-bit key.  No table over the cells: the key space may be sparse.
+    const int fbits = bits_for(nframes);
     f3d_nrmgrid g;
-    double cell = radius * 1.000001 + 1e-300;
-    for (;;) {
-        int bits = fbits; bool ok = true;
-        for (int c = 0; c < 3; ++c) {
-            const double d = floor(ext[c] / cell) + 1.0;
-            if (!(d <= 1073741824.0)) { ok = false; break; }
-            g.dim[c] = (int)d;
-            int b = 0; while (((int64_t)1 << b) < g.dim[c]) ++b;
-            g.shift[c + 1] = (c == 0 ? 0 : g.shift[c]) + b;
-            bits += b;
-        }
-        if (ok && bits <= 63) { g.key_bits = bits < 1 ? 1 : bits; break; }
-        cell *= 1.25;
-    }
+    const double cell = neighbour_cell(radius, ext, g.dim, [&](const double d[3]) {
+        return d[0] <= 1073741824.0 && d[1] <= 1073741824.0 && d[2] <= 1073741824.0 &&
+               fbits + bits_for((int64_t)d[0]) + bits_for((int64_t)d[1]) + bits_for((int64_t)d[2]) <= 63;
+    });
     g.shift[0] = 0;
-    for (int c = 0; c < 3; ++c) g.lo[c] = lo[c];
+    for (int c = 0; c < 3; ++c) { g.lo[c] = lo[c]; g.shift[c + 1] = g.shift[c] + bits_for(g.dim[c]); }
+    const int bits = fbits + g.shift[3];
+    g.key_bits = bits < 1 ? 1 : bits;
     g.inv_cell = 1.0 / cell;
     F3D_HIP(ctx, f3d_launch_normals(xyz, nframes, n, g, radius * radius, max_nn, (const double*)dcams, orient, scratch, normals, counts,
                                     neighbours, s));

@@ -25,7 +25,6 @@
 
 #pragma clang fp contract(off)
 
-#define F3D_BLOCK 256
 #define F3D_NO_PREFILL ((int64_t)0x7fffffffffffffffLL)   // "the label vector was not pre-filled": every label is stored
 #define F3D_PART_MAX_GROUPS 16            // view groups whose open-view masks a parked point carries (more: the point is redone from nothing)
 #ifndef F3D_MID_DENSE
@@ -48,19 +47,7 @@
 
 namespace {
 
-template <typename T>
-__device__ __forceinline__ f3d_p3 load_point(const T* __restrict__ xyz, int64_t i) {
-    const T* p = xyz + 3 * i;
-    f3d_p3 r;
-    r.x = (double)p[0]; r.y = (double)p[1]; r.z = (double)p[2];
-    return r;
-}
 enum { MODE_HIST8 = 0, MODE_HIST16 = 1 };
-
-// k-th entry of filter_classes: short lists travel in the kernarg, long ones in device memory
-__device__ __forceinline__ int filter_at(const f3d_filter_args& flt, int k) {
-    return (flt.nfilter <= 8) ? flt.cls[k & 7] : flt.cls_dev[k];
-}
 
 template <int MODE>
 struct hist_traits;
@@ -241,7 +228,7 @@ __device__ __forceinline__ void code_lut_block(f3d_codebook* __restrict__ cb, in
     __syncthreads();
     if (book == 2) {
         if (l == 0)
-            for (int k = flt.nfilter - 1; k >= 0; --k) { const int f = filter_at(flt, k); if (f >= 0 && f < 256) first_of[f] = k; }
+            for (int k = flt.nfilter - 1; k >= 0; --k) { const int f = f3d_filter_at(flt, k); if (f >= 0 && f < 256) first_of[f] = k; }
         __syncthreads();
         const bool listed = first_of[l] >= 0 && (int)l <= nclasses;
         int rank = 0;                                              // distinct listed labels below l
@@ -499,7 +486,7 @@ __device__ __forceinline__ void finish_point(const vote_state<MODE>& st, const u
     if (flt.nfilter > 0) {                                                       // votes[:, filter_classes]: first maximum wins
         win_c = -1; win_i = 0;
         for (int k = 0; k < flt.nfilter; ++k) {
-            const int l = filter_at(flt, k);
+            const int l = f3d_filter_at(flt, k);
             int c = 0;
             if (l >= 0 && l < ncols) c = (int)((hist[(l >> HT::shift) * F3D_BLOCK + tid] >> ((l & (HT::per_word - 1)) * HT::bits)) & HT::mask);
             if (c > win_c) { win_c = c; win_i = k; }
@@ -507,7 +494,7 @@ __device__ __forceinline__ void finish_point(const vote_state<MODE>& st, const u
     } else {
         win_c = (int)(st.best >> 16); win_i = (int)(0xFFFFu - (st.best & 0xFFFFu));
     }
-    const int64_t cls = segment_point(win_c, win_i, st.total, flt.nfilter, [&](int k) { return filter_at(flt, k); }, nclasses, threshold);
+    const int64_t cls = segment_point(win_c, win_i, st.total, flt.nfilter, [&](int k) { return f3d_filter_at(flt, k); }, nclasses, threshold);
     if (store) F3D_STORE_CLASS(&classes[orig], cls);
     if (WRITE_VOTES && store) {
         for (int l = 0; l < ncols; ++l)
@@ -841,7 +828,7 @@ __global__ __launch_bounds__(F3D_BLOCK, F3D_FUSE_WAVES) void k_fuse(const T* __r
                 live[q] = (q < PPL) & (i < npts);
                 orig[q] = live[q] ? (perm ? perm[i] : i) : i;                      // caller-order index of this point
                 p[q].x = p[q].y = p[q].z = 0.0;
-                if (live[q]) p[q] = load_point(xyz, (int64_t)(gather_xyz ? orig[q] : i));
+                if (live[q]) p[q] = f3d_load_p3(xyz, (int64_t)(gather_xyz ? orig[q] : i));
                 // first of several view chunks of a gathered cloud: leave the points behind in cell order, the later chunks stream them
                 if (CARRY && xyz_keep && live[q]) { xyz_keep[3 * (size_t)i] = (T)p[q].x; xyz_keep[3 * (size_t)i + 1] = (T)p[q].y; xyz_keep[3 * (size_t)i + 2] = (T)p[q].z; }
                 const double pscale = (fabs(p[q].x) + fabs(p[q].y)) + fabs(p[q].z);
@@ -1263,7 +1250,7 @@ __global__ __launch_bounds__(F3D_BLOCK) void k_fuse_mid(const T* __restrict__ xy
         const bool full = (entry < 0) | (k >= park_slots) | (umask == nullptr);
         {
             f3d_p3 p = {0.0, 0.0, 0.0};
-            if (live) p = load_point(xyz, (int64_t)src);
+            if (live) p = f3d_load_p3(xyz, (int64_t)src);
             spt[tid] = p.x; spt[F3D_BLOCK + tid] = p.y; spt[2 * F3D_BLOCK + tid] = p.z;
             sdefer[tid] = 0u;
             unsigned nv0 = 0;
@@ -1402,7 +1389,7 @@ __global__ __launch_bounds__(F3D_BLOCK) void k_fuse_exact(const T* __restrict__ 
         const int64_t src = live ? (todo ? (int64_t)todo[k] : k) : 0;             // index into xyz as k_fuse saw it
         const int64_t orig = (live && perm && !gather_xyz) ? (int64_t)perm[src] : src;
         f3d_p3 p = {0.0, 0.0, 0.0};
-        if (live) p = load_point(xyz, src);
+        if (live) p = f3d_load_p3(xyz, src);
         for (int wd = 0; wd < words; ++wd) hist[wd * F3D_BLOCK + tid] = 0u;
         vote_state<MODE> st;
         for (int v = 0; v < nviews; ++v) {
@@ -1440,7 +1427,7 @@ __global__ __launch_bounds__(F3D_BLOCK) void k_fastpath_audit(const T* __restric
         const int64_t i = tile * F3D_BLOCK + threadIdx.x;
         const bool live = i < n;
         f3d_p3 p = {0.0, 0.0, 0.0};
-        if (live) p = load_point(xyz, i);
+        if (live) p = f3d_load_p3(xyz, i);
         const double pscale = (fabs(p.x) + fabs(p.y)) + fabs(p.z);
         const bool small = pscale < 1.0e30;
         const float px32 = (float)p.x, py32 = (float)p.y, pz32 = (float)p.z;
@@ -1502,19 +1489,11 @@ __global__ __launch_bounds__(F3D_BLOCK) void k_fastpath_audit(const T* __restric
     atomicAdd(&stats[0], pairs); atomicAdd(&stats[1], fallback); atomicAdd(&stats[2], wrong); atomicAdd(&stats[3], cullwrong);
 }
 
-inline int grid_for(int64_t n, int per_block, int cap) {
-    int64_t g = (n + per_block - 1) / per_block;
-    if (g < 1) g = 1;
-    if (g > cap) g = cap;
-    return (int)g;
-}
-
 }  // namespace
 
 // =============================================================================================
 // launchers (called from f3d_capi.cpp)
 // =============================================================================================
-#define F3D_GRID_CAP (256 * 8 * 4)      // 256 CUs x 8 blocks, x4 so that tails stay short
 #ifndef F3D_FUSE_GRID
 #define F3D_FUSE_GRID (256 * 4 * 8)     // k_fuse: blocks per launch (multiple of 8; several rounds so that the tail stays short)
 #endif
@@ -1562,7 +1541,7 @@ static int pick_book(const f3d_filter_args& flt, bool want_votes) {
 hipError_t f3d_launch_mask_presence(const uint8_t* src, int64_t nbytes, f3d_codebook* cb, hipStream_t s) {
     if (nbytes <= 0) return hipSuccess;
     const bool vec = !((uintptr_t)src & 7);
-    const dim3 g(grid_for(nbytes >> 3, F3D_BLOCK, 256 * 8)), b(F3D_BLOCK);
+    const dim3 g(f3d_grid_for(nbytes >> 3, F3D_BLOCK, 256 * 8)), b(F3D_BLOCK);
     if (vec) hipLaunchKernelGGL(k_mask_presence<true>, g, b, 0, s, src, nbytes, cb);
     else hipLaunchKernelGGL(k_mask_presence<false>, g, b, 0, s, src, nbytes, cb);
     return hipGetLastError();
@@ -1586,7 +1565,7 @@ hipError_t f3d_launch_code_planes(const uint8_t* src, uint8_t* dst, int nviews, 
     if (nviews <= 0) return hipSuccess;
     if ((uintptr_t)dst & 7) return hipErrorInvalidValue;
     const int64_t total = (int64_t)nviews * (int64_t)(f3d_coded_plane(h, w) / 8);
-    const dim3 g(grid_for(total, F3D_BLOCK, F3D_GRID_CAP)), b(F3D_BLOCK);
+    const dim3 g(f3d_grid_for(total, F3D_BLOCK, F3D_GRID_CAP)), b(F3D_BLOCK);
     if (!(w & 7) && !((uintptr_t)src & 7)) hipLaunchKernelGGL(k_code_masks<true>, g, b, 0, s, src, dst, nviews, h, w, cb);
     else hipLaunchKernelGGL(k_code_masks<false>, g, b, 0, s, src, dst, nviews, h, w, cb);
     return hipGetLastError();
@@ -1684,7 +1663,7 @@ static hipError_t launch_fuse_t(const void* xyz, int64_t n, const f3d_view* view
     if (fast && !(chunk_flags & 2)) {                        // (a chunk that parks its bins writes no labels)
         prefilled = unlabelled_after_remap(nclasses, flt);
         if (prefilled != F3D_NO_PREFILL)
-            hipLaunchKernelGGL(k_fill_labels, dim3(grid_for(n, F3D_BLOCK, 2048)), dim3(F3D_BLOCK), 0, s, classes, n, prefilled);
+            hipLaunchKernelGGL(k_fill_labels, dim3(f3d_grid_for(n, F3D_BLOCK, 2048)), dim3(F3D_BLOCK), 0, s, classes, n, prefilled);
     }
     if (fast) {
         // the guarded vote: an 8-bit bin of a real code can wrap (more than 255 views), or the "no sample" byte could (a point casts up to
@@ -1804,7 +1783,7 @@ hipError_t f3d_launch_fastpath_audit(const void* xyz, int dtype, int64_t n, cons
                                      unsigned long long* stats_dev, hipStream_t s) {
     hipError_t e = hipMemsetAsync(stats_dev, 0, 4 * sizeof(unsigned long long), s);
     if (e != hipSuccess || n <= 0) return e;
-    const dim3 g(grid_for(n, F3D_BLOCK, F3D_GRID_CAP)), b(F3D_BLOCK);
+    const dim3 g(f3d_grid_for(n, F3D_BLOCK, F3D_GRID_CAP)), b(F3D_BLOCK);
     if (dtype == F3D_F64) hipLaunchKernelGGL(k_fastpath_audit<double>, g, b, 0, s, (const double*)xyz, n, views_dev, nviews, w, h, stats_dev);
     else hipLaunchKernelGGL(k_fastpath_audit<float>, g, b, 0, s, (const float*)xyz, n, views_dev, nviews, w, h, stats_dev);
     return hipGetLastError();

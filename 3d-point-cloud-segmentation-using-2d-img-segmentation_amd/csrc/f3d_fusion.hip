@@ -24,8 +24,6 @@ namespace {
 
 constexpr int FB = 256;
 
-inline int blocks_for(int64_t n) { int64_t b = (n + FB - 1) / FB; return (int)(b < 1 ? 1 : (b > 8192 ? 8192 : b)); }
-
 // nsum / np.linalg.norm(nsum) of a 1-D vector: sqrt(v.dot(v)), the dot in `mode`'s order
 __device__ __forceinline__ void normalise(double v[3], int mode) {
     if (mode == F3D_NORM_HOST) return;
@@ -197,40 +195,49 @@ size_t scan_temp(int64_t n) {
     return b + 256;
 }
 
-size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
+// compaction of n + 1 flags: the flags, their exclusive scan, the scan's temporary storage
+struct compact_layout { size_t flags, scan, temp, temp_bytes, total; };
+
+compact_layout layout_for(int64_t n) {
+    compact_layout L;
+    f3d_carve c;
+    L.flags = c.take((size_t)(n + 1) * 4); L.scan = c.take((size_t)(n + 1) * 4);
+    L.temp_bytes = scan_temp(n); L.temp = c.take(L.temp_bytes);
+    L.total = c.off;
+    return L;
+}
 
 }  // namespace
 
-size_t f3d_fusion_scratch_bytes(int64_t n) { return 2 * align256((size_t)(n + 1) * 4) + align256(scan_temp(n)); }
+size_t f3d_fusion_scratch_bytes(int64_t n) { return layout_for(n).total; }
 
 hipError_t f3d_launch_fusion_hits(const uint8_t* inside, const int32_t* uv_all, int64_t n, const int64_t* count, const double* pts,
                                   const double* nrm, const uint8_t* valid, int64_t npx, int32_t* ids, int32_t* uv, double* hit_pts,
                                   double* hit_nrm, int64_t* stats, void* scratch, hipStream_t s) {
+    const compact_layout L = layout_for(n);
     char* base = (char*)scratch;
-    int32_t* flags = (int32_t*)base;
-    int32_t* offs = (int32_t*)(base + align256((size_t)(n + 1) * 4));
-    void* temp = base + 2 * align256((size_t)(n + 1) * 4);
+    int32_t *flags = (int32_t*)(base + L.flags), *offs = (int32_t*)(base + L.scan);
     hipError_t e = hipMemsetAsync(stats, 0, 3 * sizeof(int64_t), s);
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(k_fu_hit_flags, dim3(blocks_for(n + 1)), dim3(FB), 0, s, inside, n, count, flags);
-    size_t t = scan_temp(n);
-    e = rocprim::exclusive_scan(temp, t, flags, offs, (int32_t)0, (size_t)n + 1, rocprim::plus<int32_t>(), s);
+    hipLaunchKernelGGL(k_fu_hit_flags, dim3(f3d_grid_for(n + 1, FB, 8192)), dim3(FB), 0, s, inside, n, count, flags);
+    size_t t = L.temp_bytes;
+    e = rocprim::exclusive_scan(base + L.temp, t, flags, offs, (int32_t)0, (size_t)n + 1, rocprim::plus<int32_t>(), s);
     if (e != hipSuccess) return e;
-    if (n > 0) hipLaunchKernelGGL(k_fu_hits, dim3(blocks_for(n)), dim3(FB), 0, s, flags, offs, n, uv_all, pts, nrm, ids, uv, hit_pts, hit_nrm);
-    hipLaunchKernelGGL(k_fu_hit_stats, dim3(blocks_for(npx)), dim3(FB), 0, s, offs, n, count, valid, npx, stats);
+    if (n > 0) hipLaunchKernelGGL(k_fu_hits, dim3(f3d_grid_for(n, FB, 8192)), dim3(FB), 0, s, flags, offs, n, uv_all, pts, nrm, ids, uv, hit_pts, hit_nrm);
+    hipLaunchKernelGGL(k_fu_hit_stats, dim3(f3d_grid_for(npx, FB, 8192)), dim3(FB), 0, s, offs, n, count, valid, npx, stats);
     return hipGetLastError();
 }
 
 hipError_t f3d_launch_fusion_seed_update(const int32_t* ids, int64_t m, const double* sums, const int32_t* counts, int mode, double* pts,
                                          double* nrm, double* clr, int64_t* nmerges, uint32_t* occ, hipStream_t s) {
     if (m <= 0) return hipSuccess;
-    hipLaunchKernelGGL(k_fu_seed_update, dim3(blocks_for(m)), dim3(FB), 0, s, ids, m, sums, counts, mode, pts, nrm, clr, nmerges, occ);
+    hipLaunchKernelGGL(k_fu_seed_update, dim3(f3d_grid_for(m, FB, 8192)), dim3(FB), 0, s, ids, m, sums, counts, mode, pts, nrm, clr, nmerges, occ);
     return hipGetLastError();
 }
 
 hipError_t f3d_launch_fusion_lookup(const int32_t* owner, const int32_t* ids, int64_t npx, int32_t* uv2pt, uint8_t* free_px, hipStream_t s) {
     if (npx <= 0) return hipSuccess;
-    hipLaunchKernelGGL(k_fu_lookup, dim3(blocks_for(npx)), dim3(FB), 0, s, owner, ids, npx, uv2pt, free_px);
+    hipLaunchKernelGGL(k_fu_lookup, dim3(f3d_grid_for(npx, FB, 8192)), dim3(FB), 0, s, owner, ids, npx, uv2pt, free_px);
     return hipGetLastError();
 }
 
@@ -238,13 +245,13 @@ hipError_t f3d_launch_fusion_check(const uint8_t* free_px, const double* pts, co
                                    double min_cosine, int64_t* stats, hipStream_t s) {
     hipError_t e = hipMemsetAsync(stats, 0, 2 * sizeof(int64_t), s);
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(k_fu_check, dim3(blocks_for(npx)), dim3(FB), 0, s, free_px, pts, nrm, npx, radius, min_cosine, stats);
+    hipLaunchKernelGGL(k_fu_check, dim3(f3d_grid_for(npx, FB, 8192)), dim3(FB), 0, s, free_px, pts, nrm, npx, radius, min_cosine, stats);
     return hipGetLastError();
 }
 
 hipError_t f3d_launch_fusion_prio(const int64_t* order, int64_t npx, int32_t* prio, hipStream_t s) {
     if (npx <= 0) return hipSuccess;
-    hipLaunchKernelGGL(k_fu_prio, dim3(blocks_for(npx)), dim3(FB), 0, s, order, npx, prio);
+    hipLaunchKernelGGL(k_fu_prio, dim3(f3d_grid_for(npx, FB, 8192)), dim3(FB), 0, s, order, npx, prio);
     return hipGetLastError();
 }
 
@@ -252,14 +259,13 @@ hipError_t f3d_launch_fusion_new_seeds(const int32_t* owner, const int32_t* prio
                                        int mode, int64_t* count, int64_t cap, double* pts, double* nrm, double* clr, int64_t* nmerges,
                                        uint32_t* occ, int32_t* uv2pt, uint8_t* free_px, void* scratch, hipStream_t s) {
     if (npx <= 0) return hipSuccess;
+    const compact_layout L = layout_for(npx);
     char* base = (char*)scratch;
-    int32_t* flags = (int32_t*)base;
-    int32_t* rank = (int32_t*)(base + align256((size_t)(npx + 1) * 4));
-    void* temp = base + 2 * align256((size_t)(npx + 1) * 4);
-    const dim3 g(blocks_for(npx)), b(FB);
-    hipLaunchKernelGGL(k_fu_seed_flags, dim3(blocks_for(npx + 1)), b, 0, s, owner, prio, npx, flags);
-    size_t t = scan_temp(npx);
-    hipError_t e = rocprim::exclusive_scan(temp, t, flags, rank, (int32_t)0, (size_t)npx + 1, rocprim::plus<int32_t>(), s);
+    int32_t *flags = (int32_t*)(base + L.flags), *rank = (int32_t*)(base + L.scan);
+    const dim3 g(f3d_grid_for(npx, FB, 8192)), b(FB);
+    hipLaunchKernelGGL(k_fu_seed_flags, dim3(f3d_grid_for(npx + 1, FB, 8192)), b, 0, s, owner, prio, npx, flags);
+    size_t t = L.temp_bytes;
+    hipError_t e = rocprim::exclusive_scan(base + L.temp, t, flags, rank, (int32_t)0, (size_t)npx + 1, rocprim::plus<int32_t>(), s);
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL(k_fu_seed_rows, g, b, 0, s, owner, prio, rank, sums, counts, npx, mode, (const int64_t*)count, cap, pts, nrm, clr,
                        nmerges, occ);

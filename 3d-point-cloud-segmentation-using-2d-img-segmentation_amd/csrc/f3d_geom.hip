@@ -6,6 +6,7 @@
 #include <math.h>
 #include <stdint.h>
 #include "f3d.h"
+#include "f3d_math.h"
 #include "f3d_kernels.h"
 
 #pragma clang fp contract(off)
@@ -13,13 +14,13 @@
 namespace {
 
 constexpr int GB = 256;
-struct v3 { double x, y, z; };
-__device__ __forceinline__ v3 ldv(const double* p) { v3 r; r.x = p[0]; r.y = p[1]; r.z = p[2]; return r; }
-__device__ __forceinline__ v3 sub(v3 a, v3 b) { v3 r; r.x = a.x - b.x; r.y = a.y - b.y; r.z = a.z - b.z; return r; }
-__device__ __forceinline__ double dot(v3 a, v3 b) { return (a.x * b.x + a.y * b.y) + a.z * b.z; }
-__device__ __forceinline__ v3 cross(v3 a, v3 b) { v3 r; r.x = a.y * b.z - a.z * b.y; r.y = a.z * b.x - a.x * b.z; r.z = a.x * b.y - a.y * b.x; return r; }
-__device__ __forceinline__ double norm(v3 a) { return sqrt((a.x * a.x + a.y * a.y) + a.z * a.z); }
-__device__ __forceinline__ v3 axpy(v3 o, v3 d, double t) { v3 r; r.x = o.x + t * d.x; r.y = o.y + t * d.y; r.z = o.z + t * d.z; return r; }
+// ldv(p + 3 * i) rather than f3d_load_p3(p, i): indexing inside the helper reorders this file's address arithmetic
+__device__ __forceinline__ f3d_p3 ldv(const double* p) { f3d_p3 r; r.x = p[0]; r.y = p[1]; r.z = p[2]; return r; }
+__device__ __forceinline__ f3d_p3 sub(f3d_p3 a, f3d_p3 b) { f3d_p3 r; r.x = a.x - b.x; r.y = a.y - b.y; r.z = a.z - b.z; return r; }
+__device__ __forceinline__ double dot(f3d_p3 a, f3d_p3 b) { return (a.x * b.x + a.y * b.y) + a.z * b.z; }
+__device__ __forceinline__ f3d_p3 cross(f3d_p3 a, f3d_p3 b) { f3d_p3 r; r.x = a.y * b.z - a.z * b.y; r.y = a.z * b.x - a.x * b.z; r.z = a.x * b.y - a.y * b.x; return r; }
+__device__ __forceinline__ double norm(f3d_p3 a) { return sqrt((a.x * a.x + a.y * a.y) + a.z * a.z); }
+__device__ __forceinline__ f3d_p3 axpy(f3d_p3 o, f3d_p3 d, double t) { f3d_p3 r; r.x = o.x + t * d.x; r.y = o.y + t * d.y; r.z = o.z + t * d.z; return r; }
 
 struct vec3_arg { double v[3]; };
 
@@ -27,13 +28,13 @@ struct vec3_arg { double v[3]; };
 __global__ __launch_bounds__(GB) void k_ray_x_lines(vec3_arg origin, vec3_arg direction, const double* __restrict__ starts,
                                                     const double* __restrict__ ends, int64_t n, double* __restrict__ pts,
                                                     uint8_t* __restrict__ within) {
-    const v3 o = ldv(origin.v), d = ldv(direction.v);
+    const f3d_p3 o = ldv(origin.v), d = ldv(direction.v);
     for (int64_t i = (int64_t)blockIdx.x * GB + threadIdx.x; i < n; i += (int64_t)gridDim.x * GB) {
-        const v3 s = ldv(starts + 3 * i), e = ldv(ends + 3 * i);
-        const v3 ld_ = sub(e, s), rl = sub(s, o);
-        const v3 perp = cross(d, ld_), rlxl = cross(rl, ld_);
+        const f3d_p3 s = ldv(starts + 3 * i), e = ldv(ends + 3 * i);
+        const f3d_p3 ld_ = sub(e, s), rl = sub(s, o);
+        const f3d_p3 perp = cross(d, ld_), rlxl = cross(rl, ld_);
         const double t = dot(rlxl, perp) / dot(perp, perp);
-        const v3 x = axpy(o, d, t);                                  // origin + t*direction (:32)
+        const f3d_p3 x = axpy(o, d, t);                              // origin + t*direction (:32)
         pts[3 * i] = x.x; pts[3 * i + 1] = x.y; pts[3 * i + 2] = x.z;
         const double both = norm(sub(x, s)) + norm(sub(x, e));
         const double len = norm(sub(e, s)) + 1e-6;
@@ -45,13 +46,13 @@ __global__ __launch_bounds__(GB) void k_ray_x_lines(vec3_arg origin, vec3_arg di
 __global__ __launch_bounds__(GB) void k_rays_x_plane(vec3_arg pp_, vec3_arg pn_, const double* __restrict__ origins,
                                                      const double* __restrict__ dirs, int64_t n, double* __restrict__ pts,
                                                      uint8_t* __restrict__ valid) {
-    const v3 pp = ldv(pp_.v), pn = ldv(pn_.v);
+    const f3d_p3 pp = ldv(pp_.v), pn = ldv(pn_.v);
     for (int64_t i = (int64_t)blockIdx.x * GB + threadIdx.x; i < n; i += (int64_t)gridDim.x * GB) {
-        const v3 o = ldv(origins + 3 * i), d = ldv(dirs + 3 * i);
+        const f3d_p3 o = ldv(origins + 3 * i), d = ldv(dirs + 3 * i);
         const double denom = dot(pn, d);
         const bool ok = denom < -1e-6;
         const double t = ok ? dot(sub(pp, o), pn) / denom : 0.0;
-        v3 x; x.x = o.x + d.x * t; x.y = o.y + d.y * t; x.z = o.z + d.z * t;
+        f3d_p3 x; x.x = o.x + d.x * t; x.y = o.y + d.y * t; x.z = o.z + d.z * t;
         pts[3 * i] = x.x; pts[3 * i + 1] = x.y; pts[3 * i + 2] = x.z;
         valid[i] = ok;
     }
@@ -65,15 +66,15 @@ __global__ __launch_bounds__(GB) void k_lines_x_planes(const double* __restrict_
     const int64_t total = n * m;
     for (int64_t k = (int64_t)blockIdx.x * GB + threadIdx.x; k < total; k += (int64_t)gridDim.x * GB) {
         const int64_t i = k / m; const int j = (int)(k - i * m);
-        const v3 o = ldv(lo + 3 * i), e = ldv(le + 3 * i);
-        v3 d = sub(e, o);
+        const f3d_p3 o = ldv(lo + 3 * i), e = ldv(le + 3 * i);
+        f3d_p3 d = sub(e, o);
         const double dn = norm(d);
         d.x /= dn; d.y /= dn; d.z /= dn;
-        const v3 pp = ldv(pps + 3 * j), pn = ldv(pns + 3 * j);
+        const f3d_p3 pp = ldv(pps + 3 * j), pn = ldv(pns + 3 * j);
         const double denom = dot(d, pn);
         const bool ok = (denom < -1e-6) | (denom > 1e-6);
         const double t = ok ? dot(sub(pp, o), pn) / denom : 0.0;
-        v3 x; x.x = o.x + d.x * t; x.y = o.y + d.y * t; x.z = o.z + d.z * t;
+        f3d_p3 x; x.x = o.x + d.x * t; x.y = o.y + d.y * t; x.z = o.z + d.z * t;
         pts[3 * k] = x.x; pts[3 * k + 1] = x.y; pts[3 * k + 2] = x.z;
         const int64_t b = bmode ? j : 0;
         const double both = norm(sub(x, ldv(lo + 3 * b))) + norm(sub(x, ldv(le + 3 * b)));
@@ -87,11 +88,11 @@ __global__ __launch_bounds__(GB) void k_point_inside_polygon(const double* __res
                                                              const double* __restrict__ verts, int m, uint8_t* __restrict__ inside,
                                                              uint8_t* __restrict__ within) {
     for (int64_t i = (int64_t)blockIdx.x * GB + threadIdx.x; i < n; i += (int64_t)gridDim.x * GB) {
-        const v3 p = ldv(points + 3 * i);
+        const f3d_p3 p = ldv(points + 3 * i);
         int count = 0;
         for (int j = 0; j < m; ++j) {
-            const v3 v = ldv(verts + 3 * j), w = ldv(verts + 3 * ((j + 1 == m) ? 0 : j + 1));
-            const v3 e = sub(w, v), d = sub(p, v);
+            const f3d_p3 v = ldv(verts + 3 * j), w = ldv(verts + 3 * ((j + 1 == m) ? 0 : j + 1));
+            const f3d_p3 e = sub(w, v), d = sub(p, v);
             const double dp = (d.x * e.x + d.z * e.z) + d.y * e.y;
             const bool in = dp >= 0.0;
             within[(size_t)j * n + i] = in;
@@ -104,10 +105,10 @@ __global__ __launch_bounds__(GB) void k_point_inside_polygon(const double* __res
 // points_plane_projection, intersections.py:167-180 (also the first half of lines_plane_projection :183-204)
 __global__ __launch_bounds__(GB) void k_points_plane_projection(const double* __restrict__ points, int64_t n, vec3_arg pp_, vec3_arg nr_,
                                                                 double* __restrict__ out) {
-    const v3 pp = ldv(pp_.v), nr = ldv(nr_.v);
+    const f3d_p3 pp = ldv(pp_.v), nr = ldv(nr_.v);
     const double c = dot(pp, nr);
     for (int64_t i = (int64_t)blockIdx.x * GB + threadIdx.x; i < n; i += (int64_t)gridDim.x * GB) {
-        const v3 p = ldv(points + 3 * i);
+        const f3d_p3 p = ldv(points + 3 * i);
         const double t = c - dot(nr, p);
         out[3 * i] = p.x + t * nr.x; out[3 * i + 1] = p.y + t * nr.y; out[3 * i + 2] = p.z + t * nr.z;
     }
@@ -117,42 +118,41 @@ __global__ __launch_bounds__(GB) void k_points_plane_projection(const double* __
 __global__ __launch_bounds__(GB) void k_unit_difference(const double* __restrict__ a, const double* __restrict__ b, int64_t n,
                                                         double* __restrict__ out) {
     for (int64_t i = (int64_t)blockIdx.x * GB + threadIdx.x; i < n; i += (int64_t)gridDim.x * GB) {
-        v3 d = sub(ldv(b + 3 * i), ldv(a + 3 * i));
+        f3d_p3 d = sub(ldv(b + 3 * i), ldv(a + 3 * i));
         const double dn = norm(d);
         out[3 * i] = d.x / dn; out[3 * i + 1] = d.y / dn; out[3 * i + 2] = d.z / dn;
     }
 }
 
-inline dim3 grid(int64_t n) { int64_t g = (n + GB - 1) / GB; if (g < 1) g = 1; if (g > 8192) g = 8192; return dim3((unsigned)g); }
 inline vec3_arg va(const double* p) { vec3_arg r; r.v[0] = p[0]; r.v[1] = p[1]; r.v[2] = p[2]; return r; }
 
 }  // namespace
 
 hipError_t f3d_launch_ray_x_lines(const double o[3], const double d[3], const double* starts, const double* ends, int64_t n, double* pts,
                                   uint8_t* within, hipStream_t s) {
-    if (n > 0) hipLaunchKernelGGL(k_ray_x_lines, grid(n), dim3(GB), 0, s, va(o), va(d), starts, ends, n, pts, within);
+    if (n > 0) hipLaunchKernelGGL(k_ray_x_lines, dim3(f3d_grid_for(n, GB, 8192)), dim3(GB), 0, s, va(o), va(d), starts, ends, n, pts, within);
     return hipGetLastError();
 }
 hipError_t f3d_launch_rays_x_plane(const double pp[3], const double pn[3], const double* origins, const double* dirs, int64_t n, double* pts,
                                    uint8_t* valid, hipStream_t s) {
-    if (n > 0) hipLaunchKernelGGL(k_rays_x_plane, grid(n), dim3(GB), 0, s, va(pp), va(pn), origins, dirs, n, pts, valid);
+    if (n > 0) hipLaunchKernelGGL(k_rays_x_plane, dim3(f3d_grid_for(n, GB, 8192)), dim3(GB), 0, s, va(pp), va(pn), origins, dirs, n, pts, valid);
     return hipGetLastError();
 }
 hipError_t f3d_launch_lines_x_planes(const double* lo, const double* le, int64_t n, const double* pps, const double* pns, int m, int bmode,
                                      double* pts, uint8_t* valid, hipStream_t s) {
-    if (n > 0 && m > 0) hipLaunchKernelGGL(k_lines_x_planes, grid(n * m), dim3(GB), 0, s, lo, le, n, pps, pns, m, bmode, pts, valid);
+    if (n > 0 && m > 0) hipLaunchKernelGGL(k_lines_x_planes, dim3(f3d_grid_for(n * m, GB, 8192)), dim3(GB), 0, s, lo, le, n, pps, pns, m, bmode, pts, valid);
     return hipGetLastError();
 }
 hipError_t f3d_launch_point_inside_polygon(const double* points, int64_t n, const double* verts, int m, uint8_t* inside, uint8_t* within,
                                            hipStream_t s) {
-    if (n > 0) hipLaunchKernelGGL(k_point_inside_polygon, grid(n), dim3(GB), 0, s, points, n, verts, m, inside, within);
+    if (n > 0) hipLaunchKernelGGL(k_point_inside_polygon, dim3(f3d_grid_for(n, GB, 8192)), dim3(GB), 0, s, points, n, verts, m, inside, within);
     return hipGetLastError();
 }
 hipError_t f3d_launch_points_plane_projection(const double* points, int64_t n, const double pp[3], const double nr[3], double* out, hipStream_t s) {
-    if (n > 0) hipLaunchKernelGGL(k_points_plane_projection, grid(n), dim3(GB), 0, s, points, n, va(pp), va(nr), out);
+    if (n > 0) hipLaunchKernelGGL(k_points_plane_projection, dim3(f3d_grid_for(n, GB, 8192)), dim3(GB), 0, s, points, n, va(pp), va(nr), out);
     return hipGetLastError();
 }
 hipError_t f3d_launch_unit_difference(const double* a, const double* b, int64_t n, double* out, hipStream_t s) {
-    if (n > 0) hipLaunchKernelGGL(k_unit_difference, grid(n), dim3(GB), 0, s, a, b, n, out);
+    if (n > 0) hipLaunchKernelGGL(k_unit_difference, dim3(f3d_grid_for(n, GB, 8192)), dim3(GB), 0, s, a, b, n, out);
     return hipGetLastError();
 }

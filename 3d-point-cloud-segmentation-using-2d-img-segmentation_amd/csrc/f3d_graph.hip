@@ -56,19 +56,12 @@ __global__ __launch_bounds__(GB) void k_graph_bbox(const T* __restrict__ xyz, in
     }
 }
 
-__device__ __forceinline__ void cell_of(const f3d_graphgrid& g, double x, double y, double z, int& cx, int& cy, int& cz) {
-    // clamped: rounding at the upper faces of the box must not leave the grid
-    cx = min(g.dim[0] - 1, max(0, (int)floor((x - g.lo[0]) * g.inv_cell)));
-    cy = min(g.dim[1] - 1, max(0, (int)floor((y - g.lo[1]) * g.inv_cell)));
-    cz = min(g.dim[2] - 1, max(0, (int)floor((z - g.lo[2]) * g.inv_cell)));
-}
-
 template <typename T>
 __global__ __launch_bounds__(GB) void k_graph_keys(const T* __restrict__ xyz, int64_t n, f3d_graphgrid g, uint32_t* __restrict__ keys,
                                                     uint32_t* __restrict__ idx) {
     for (int64_t i = (int64_t)blockIdx.x * GB + threadIdx.x; i < n; i += (int64_t)gridDim.x * GB) {
         int cx, cy, cz;
-        cell_of(g, (double)xyz[3 * i], (double)xyz[3 * i + 1], (double)xyz[3 * i + 2], cx, cy, cz);
+        f3d_cell_of(g, (double)xyz[3 * i], (double)xyz[3 * i + 1], (double)xyz[3 * i + 2], cx, cy, cz);
         keys[i] = (uint32_t)((cz * g.dim[1] + cy) * g.dim[0] + cx);
         idx[i] = (uint32_t)i;
     }
@@ -99,7 +92,7 @@ __global__ __launch_bounds__(GB) void k_graph_scan(const double* __restrict__ so
     for (int64_t j = (int64_t)blockIdx.x * GB + threadIdx.x; j < n; j += (int64_t)gridDim.x * GB) {
         const double px = sorted[3 * j], py = sorted[3 * j + 1], pz = sorted[3 * j + 2];
         int cx, cy, cz;
-        cell_of(g, px, py, pz, cx, cy, cz);
+        f3d_cell_of(g, px, py, pz, cx, cy, cz);
         const int64_t orig = perm[j];
         int64_t out = FILL ? offsets[orig] : 0;
         for (int dz = -1; dz <= 1; ++dz) {
@@ -127,17 +120,14 @@ __global__ __launch_bounds__(GB) void k_graph_scan(const double* __restrict__ so
     }
 }
 
-inline int grid_blocks(int64_t n) { int64_t b = (n + GB - 1) / GB; return (int)(b < 1 ? 1 : (b > 8192 ? 8192 : b)); }
-
 struct graph_layout { size_t keys_a, keys_b, idx_a, perm, sorted, cells, bbox, temp, total; };
 
 graph_layout layout_for(int64_t n, int64_t ncells, size_t temp_bytes) {
     graph_layout L;
-    size_t o = 0;
-    auto take = [&](size_t bytes) { const size_t at = o; o += (bytes + 255) & ~(size_t)255; return at; };
-    L.keys_a = take((size_t)n * 4); L.keys_b = take((size_t)n * 4); L.idx_a = take((size_t)n * 4); L.perm = take((size_t)n * 4);
-    L.sorted = take((size_t)n * 24); L.cells = take((size_t)ncells * 8); L.bbox = take(sizeof(gbox) * 1024); L.temp = take(temp_bytes);
-    L.total = o;
+    f3d_carve c;
+    L.keys_a = c.take((size_t)n * 4); L.keys_b = c.take((size_t)n * 4); L.idx_a = c.take((size_t)n * 4); L.perm = c.take((size_t)n * 4);
+    L.sorted = c.take((size_t)n * 24); L.cells = c.take((size_t)ncells * 8); L.bbox = c.take(sizeof(gbox) * 1024); L.temp = c.take(temp_bytes);
+    L.total = c.off;
     return L;
 }
 
@@ -154,7 +144,7 @@ size_t f3d_graph_bbox_bytes(void) { return sizeof(gbox) * 1024; }
 
 // stage 1 of the count pass: bounding box partials (the host reduces <= 1024 of them and chooses the grid)
 hipError_t f3d_launch_graph_bbox(const void* xyz, int dtype, int64_t n, void* partial, int* nblocks, hipStream_t s) {
-    int b = grid_blocks(n); if (b > 1024) b = 1024;
+    const int b = f3d_grid_for(n, GB, 1024);
     *nblocks = b;
     if (dtype == F3D_F64) hipLaunchKernelGGL(k_graph_bbox<double>, dim3(b), dim3(GB), 0, s, (const double*)xyz, n, (gbox*)partial);
     else hipLaunchKernelGGL(k_graph_bbox<float>, dim3(b), dim3(GB), 0, s, (const float*)xyz, n, (gbox*)partial);
@@ -184,7 +174,7 @@ hipError_t f3d_launch_graph_count(const void* xyz, int dtype, int64_t n, const f
     uint32_t *ka = (uint32_t*)(base + L.keys_a), *kb = (uint32_t*)(base + L.keys_b), *ia = (uint32_t*)(base + L.idx_a), *perm = (uint32_t*)(base + L.perm);
     double* sorted = (double*)(base + L.sorted);
     int2* cells = (int2*)(base + L.cells);
-    const dim3 gr(grid_blocks(n)), b(GB);
+    const dim3 gr(f3d_grid_for(n, GB, 8192)), b(GB);
     if (dtype == F3D_F64) hipLaunchKernelGGL(k_graph_keys<double>, gr, b, 0, s, (const double*)xyz, n, g, ka, ia);
     else hipLaunchKernelGGL(k_graph_keys<float>, gr, b, 0, s, (const float*)xyz, n, g, ka, ia);
     unsigned bits = 1; while (bits < 32 && ((int64_t)1 << bits) < ncells) ++bits;
@@ -211,7 +201,7 @@ hipError_t f3d_launch_graph_fill(int64_t n, const f3d_graphgrid& g, double r2, c
     const int64_t ncells = (int64_t)g.dim[0] * g.dim[1] * g.dim[2];
     const graph_layout L = layout_for(n, ncells, temp_bytes_for(n));
     const char* base = (const char*)scratch;
-    hipLaunchKernelGGL(k_graph_scan<true>, dim3(grid_blocks(n)), dim3(GB), 0, s, (const double*)(base + L.sorted), n,
+    hipLaunchKernelGGL(k_graph_scan<true>, dim3(f3d_grid_for(n, GB, 8192)), dim3(GB), 0, s, (const double*)(base + L.sorted), n,
                        (const uint32_t*)(base + L.perm), g, (const int2*)(base + L.cells), r2, const_cast<int64_t*>(offsets), nbrs);
     return hipGetLastError();
 }

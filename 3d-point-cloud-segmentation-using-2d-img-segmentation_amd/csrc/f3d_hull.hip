@@ -25,6 +25,7 @@
 #include <stdint.h>
 #include <math.h>
 #include "f3d.h"
+#include "f3d_math.h"
 #include "f3d_kernels.h"
 #include "f3d_eigen.h"
 
@@ -36,13 +37,9 @@ constexpr int HW = 64;                        // one wave per instance
 constexpr int FRONT_CAP = 1024;               // frontier edges kept in LDS per instance (a hull of ~150 vertices peaks near 60)
 constexpr double O3D_ERR_A = (7.0 + 56.0 * 1.1102230246251565e-16) * 1.1102230246251565e-16;   // Shewchuk, orient3d stage A
 
-struct p3 { double x, y, z; };
-
-__device__ __forceinline__ p3 ldp(const double* __restrict__ pts, int64_t i) { return p3{pts[3 * i], pts[3 * i + 1], pts[3 * i + 2]}; }
-
 // S(a, b, c, d) = ((b - a) x (c - a)) . (d - a): > 0 when d is on the side of plane (a, b, c) its counter-clockwise normal points to.
 // Returns +1 / -1 when the sign is certain, 0 when |S| is within the rounding bound (the caller defers the instance).
-__device__ __forceinline__ int side(const p3& a, const p3& b, const p3& c, const p3& d) {
+__device__ __forceinline__ int side(const f3d_p3& a, const f3d_p3& b, const f3d_p3& c, const f3d_p3& d) {
     const double adx = a.x - d.x, ady = a.y - d.y, adz = a.z - d.z;
     const double bdx = b.x - d.x, bdy = b.y - d.y, bdz = b.z - d.z;
     const double cdx = c.x - d.x, cdy = c.y - d.y, cdz = c.z - d.z;
@@ -60,14 +57,14 @@ __device__ __forceinline__ int side(const p3& a, const p3& b, const p3& c, const
 // wave-wide: the index (into the instance's points) that wins the tournament around the directed edge v -> u, starting from `start`
 // (a point every other point beats: the third vertex of the known facet, or a virtual point given by coordinates).
 // `unsure` is raised when a comparison that decided something was not certified.
-__device__ __forceinline__ int wrap_edge(const double* __restrict__ pts, int m, const p3& pv, const p3& pu, int iv, int iu, int istart, const p3& pstart,
+__device__ __forceinline__ int wrap_edge(const double* __restrict__ pts, int m, const f3d_p3& pv, const f3d_p3& pu, int iv, int iu, int istart, const f3d_p3& pstart,
                                          bool& unsure) {
     const int lane = threadIdx.x & (HW - 1);
     int best = istart;
-    p3 pb = pstart;
+    f3d_p3 pb = pstart;
     for (int j = lane; j < m; j += HW) {
         if (j == iv || j == iu || j == best) continue;
-        const p3 q = ldp(pts, j);
+        const f3d_p3 q = f3d_load_p3(pts, j);
         const int s = side(pv, pu, pb, q);
         if (s == 0) unsure = true;
         if (s > 0) { best = j; pb = q; }
@@ -75,7 +72,7 @@ __device__ __forceinline__ int wrap_edge(const double* __restrict__ pts, int m, 
 #pragma unroll
     for (int off = 1; off < HW; off <<= 1) {
         const int ob = __shfl_xor(best, off, HW);
-        p3 q;
+        f3d_p3 q;
         q.x = __shfl_xor(pb.x, off, HW); q.y = __shfl_xor(pb.y, off, HW); q.z = __shfl_xor(pb.z, off, HW);
         if (ob != best && ob != istart) {
             if (best == istart) { best = ob; pb = q; }
@@ -115,7 +112,7 @@ __device__ int wave_hull(const double* __restrict__ pts, int m, uint8_t* __restr
     {
         double bx = INFINITY, by = INFINITY, bz = INFINITY; int bi = 0x7fffffff;
         for (int j = lane; j < m; j += HW) {
-            const p3 q = ldp(pts, j);
+            const f3d_p3 q = f3d_load_p3(pts, j);
             if (!(fabs(q.x) < 1e300 && fabs(q.y) < 1e300 && fabs(q.z) < 1e300)) unsure = true;      // non-finite coordinates: the host decides (Qhull raises)
             const bool less = q.x < bx || (q.x == bx && (q.y < by || (q.y == by && (q.z < bz || (q.z == bz && j < bi)))));
             if (less) { bx = q.x; by = q.y; bz = q.z; bi = j; }
@@ -130,22 +127,22 @@ __device__ int wave_hull(const double* __restrict__ pts, int m, uint8_t* __restr
         ia = __builtin_amdgcn_readfirstlane(bi);
         if (__any(unsure) || ia == 0x7fffffff) return F3D_OBB_DEFERRED;
     }
-    const p3 pa = ldp(pts, ia);
+    const f3d_p3 pa = f3d_load_p3(pts, ia);
     // ---- first edge a - b: the supporting plane x = a.x contains the virtual points a' = a + (0, L, 0) and a'' = a + (0, 0, -L);
     // (a, a', a'') is counter-clockwise seen from -x, i.e. every point is behind it, so a'' is a valid start around the axis a -> a'
     double ext = 1.0;
     {
         double mx = 0.0;
-        for (int j = lane; j < m; j += HW) { const p3 q = ldp(pts, j); mx = fmax(mx, fmax(fabs(q.x - pa.x), fmax(fabs(q.y - pa.y), fabs(q.z - pa.z)))); }
+        for (int j = lane; j < m; j += HW) { const f3d_p3 q = f3d_load_p3(pts, j); mx = fmax(mx, fmax(fabs(q.x - pa.x), fmax(fabs(q.y - pa.y), fabs(q.z - pa.z)))); }
 #pragma unroll
         for (int off = 1; off < HW; off <<= 1) mx = fmax(mx, __shfl_xor(mx, off, HW));
         ext = mx > 0.0 ? mx : 1.0;
     }
-    const p3 pa1 = p3{pa.x, pa.y + ext, pa.z}, pa2 = p3{pa.x, pa.y, pa.z - ext};
+    const f3d_p3 pa1 = {pa.x, pa.y + ext, pa.z}, pa2 = {pa.x, pa.y, pa.z - ext};
     // around the directed axis a1 -> a (so that the known "facet" is (a, a1, a2) = u -> v with u = a, v = a1, w = a2)
     const int ib = wrap_edge(pts, m, pa1, pa, -1, ia, -2, pa2, unsure);
     if (unsure || ib < 0) return F3D_OBB_DEFERRED;
-    const p3 pb = ldp(pts, ib);
+    const f3d_p3 pb = f3d_load_p3(pts, ib);
     // the plane (a1, a, b) supports the hull and contains a, b: facet "(a1, a, b)" plays the known facet of edge a -> b (u = a, v = b?)
     // Known facet orientation: (v', u', p) = (a1, a, b) is outward, its directed edges are a1 -> a, a -> b, b -> a1.  The hull facet
     // across the directed edge a -> b contains b -> a: wrap around v = b, u = a starting from w = a1.
@@ -157,7 +154,7 @@ __device__ int wave_hull(const double* __restrict__ pts, int m, uint8_t* __restr
     auto emit_facet = [&](int i0, int i1, int i2) {                   // outward facet (i0, i1, i2)
         if (MODE == MODE_FACETS) {
             if (nf < facet_cap && lane == 0) {
-                const p3 A = ldp(pts, i0), B = ldp(pts, i1), C = ldp(pts, i2);
+                const f3d_p3 A = f3d_load_p3(pts, i0), B = f3d_load_p3(pts, i1), C = f3d_load_p3(pts, i2);
                 const double ux = B.x - A.x, uy = B.y - A.y, uz = B.z - A.z, vx = C.x - A.x, vy = C.y - A.y, vz = C.z - A.z;
                 double nx = uy * vz - uz * vy, ny = uz * vx - ux * vz, nz = ux * vy - uy * vx;
                 const double nn = sqrt((nx * nx + ny * ny) + nz * nz);
@@ -197,7 +194,7 @@ __device__ int wave_hull(const double* __restrict__ pts, int m, uint8_t* __restr
         --nfront;
         const int u = L.fu[nfront], v = L.fv[nfront], w = L.fw[nfront];       // known facet (u, v, w); wanted: the facet with edge v -> u
         __builtin_amdgcn_wave_barrier();
-        const p3 pu = ldp(pts, u), pv = ldp(pts, v), pw = ldp(pts, w);
+        const f3d_p3 pu = f3d_load_p3(pts, u), pv = f3d_load_p3(pts, v), pw = f3d_load_p3(pts, w);
         const int p = wrap_edge(pts, m, pv, pu, v, u, w, pw, unsure);
         if (unsure || p == w) return F3D_OBB_DEFERRED;                // p == w: every other point is coplanar with the known facet (flat input)
         emit_facet(v, u, p);
@@ -248,13 +245,13 @@ __global__ __launch_bounds__(HW) void k_obb_fit(const double* __restrict__ pts_a
             __builtin_amdgcn_wave_barrier();
             // mean and covariance of the vertices: lane-strided partial sums over the list, fixed tree
             double sx = 0, sy = 0, sz = 0;
-            for (int r = lane; r < nv; r += HW) { const p3 q = ldp(pts, vlist[r]); sx += q.x; sy += q.y; sz += q.z; }
+            for (int r = lane; r < nv; r += HW) { const f3d_p3 q = f3d_load_p3(pts, vlist[r]); sx += q.x; sy += q.y; sz += q.z; }
 #pragma unroll
             for (int off = 1; off < HW; off <<= 1) { sx += __shfl_xor(sx, off, HW); sy += __shfl_xor(sy, off, HW); sz += __shfl_xor(sz, off, HW); }
             const double mx = sx / nv, my = sy / nv, mz = sz / nv;
             double c00 = 0, c01 = 0, c02 = 0, c11 = 0, c12 = 0, c22 = 0;
             for (int r = lane; r < nv; r += HW) {
-                const p3 q = ldp(pts, vlist[r]);
+                const f3d_p3 q = f3d_load_p3(pts, vlist[r]);
                 const double dx = q.x - mx, dy = q.y - my, dz = q.z - mz;
                 c00 += dx * dx; c01 += dx * dy; c02 += dx * dz; c11 += dy * dy; c12 += dy * dz; c22 += dz * dz;
             }
@@ -286,7 +283,7 @@ __global__ __launch_bounds__(HW) void k_obb_fit(const double* __restrict__ pts_a
             // extents of the vertices in the frame
             double lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
             for (int r = lane; r < nv; r += HW) {
-                const p3 q = ldp(pts, vlist[r]);
+                const f3d_p3 q = f3d_load_p3(pts, vlist[r]);
                 const double dx = q.x - mx, dy = q.y - my, dz = q.z - mz;
 #pragma unroll
                 for (int a = 0; a < 3; ++a) {

@@ -1,4 +1,4 @@
-// Internal interface between the C-ABI layer (f3d_capi.cpp) and the kernels (f3d_kernels.hip).
+// Internal interface between the C-ABI layer (f3d_capi.cpp) and the kernel sources (f3d_*.hip), and the launch helpers they share.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -13,6 +13,22 @@
 #define F3D_PLANES_PER_LAUNCH 16
 #define F3D_OBB_MAX_BOXES 4096
 #define F3D_SORT_MAX_CELLS 32767            // + 1 overflow cell = 2^15 keys -> 16 key bits sorted
+#define F3D_BLOCK 256                       // threads per block of the f3d_kernels.hip / f3d_fuse.hip kernels
+#define F3D_GRID_CAP (256 * 8 * 4)          // their usual grid cap: 256 CUs x 8 blocks, x4 so that tails stay short
+
+// blocks of a grid-stride launch over n items, per_block items per block: ceil(n / per_block) clamped to [1, cap]
+inline int f3d_grid_for(int64_t n, int per_block, int cap) {
+    int64_t g = (n + per_block - 1) / per_block;
+    if (g < 1) g = 1;
+    if (g > cap) g = cap;
+    return (int)g;
+}
+
+// offsets of the pieces of a scratch buffer: each piece starts on a 256-byte boundary; `off` ends as the total size
+struct f3d_carve {
+    size_t off = 0;
+    size_t take(size_t bytes) { const size_t at = off; off += (bytes + 255) & ~(size_t)255; return at; }
+};
 
 struct f3d_cellgrid {                      // device-resident description of the cell-sort grid
     double lo[3];
@@ -37,6 +53,15 @@ struct f3d_nrmgrid {                       // cell grid of the normal estimation
     int key_bits;                          // bits the radix sort orders (<= 63: key + 1 never wraps)
 };
 
+// cell of a point in a neighbour grid (f3d_graphgrid, f3d_nrmgrid)
+template <typename G>
+__device__ __forceinline__ void f3d_cell_of(const G& g, double x, double y, double z, int& cx, int& cy, int& cz) {
+    // clamped: rounding at the upper faces of the box must not leave the grid
+    cx = min(g.dim[0] - 1, max(0, (int)floor((x - g.lo[0]) * g.inv_cell)));
+    cy = min(g.dim[1] - 1, max(0, (int)floor((y - g.lo[1]) * g.inv_cell)));
+    cz = min(g.dim[2] - 1, max(0, (int)floor((z - g.lo[2]) * g.inv_cell)));
+}
+
 struct f3d_plane_args {                    // by-value kernel argument of k_inside_polyhedra
     int m;
     int accumulate;                        // 1: AND into the existing `inside` bytes (chained launches)
@@ -50,6 +75,11 @@ struct f3d_filter_args {                   // filter_classes of VotingSegmentati
     const int* cls_dev;                    // device copy of the list when nfilter > 8
     const int* cls_host;                   // host copy of the whole list (the context's staging array; NULL when nfilter == 0)
 };
+
+// k-th entry of filter_classes: short lists travel in the kernarg, long ones in device memory
+__device__ __forceinline__ int f3d_filter_at(const f3d_filter_args& flt, int k) {
+    return (flt.nfilter <= 8) ? flt.cls[k & 7] : flt.cls_dev[k];
+}
 
 // device-resident code book of the fused path's vote bins (built per call by k_mask_presence + k_code_lut, f3d_fuse.hip)
 struct f3d_codebook {

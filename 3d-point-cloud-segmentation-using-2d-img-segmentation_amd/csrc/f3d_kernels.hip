@@ -13,17 +13,7 @@
 
 #pragma clang fp contract(off)
 
-#define F3D_BLOCK 256
-
 namespace {
-
-template <typename T>
-__device__ __forceinline__ f3d_p3 load_point(const T* __restrict__ xyz, int64_t i) {
-    const T* p = xyz + 3 * i;
-    f3d_p3 r;
-    r.x = (double)p[0]; r.y = (double)p[1]; r.z = (double)p[2];
-    return r;
-}
 
 // ------------------------------------------------------------------------------------------
 // a1: rotate
@@ -33,7 +23,7 @@ struct quat_arg { double q[4]; };
 __global__ __launch_bounds__(F3D_BLOCK) void k_rotate(const double* __restrict__ xyz, int64_t n,
                                                        quat_arg qa, double* __restrict__ out) {
     for (int64_t i = (int64_t)blockIdx.x * F3D_BLOCK + threadIdx.x; i < n; i += (int64_t)gridDim.x * F3D_BLOCK) {
-        const f3d_p3 o = f3d_rotate(qa.q, load_point(xyz, i));
+        const f3d_p3 o = f3d_rotate(qa.q, f3d_load_p3(xyz, i));
         out[3 * i] = o.x; out[3 * i + 1] = o.y; out[3 * i + 2] = o.z;
     }
 }
@@ -93,7 +83,7 @@ template <typename T, bool WRITE_UV, bool WRITE_INSIDE>
 __global__ __launch_bounds__(F3D_BLOCK) void k_project_view(const T* __restrict__ xyz, int64_t n, f3d_view vw,
                                                              int32_t* __restrict__ uv, uint8_t* __restrict__ inside) {
     for (int64_t i = (int64_t)blockIdx.x * F3D_BLOCK + threadIdx.x; i < n; i += (int64_t)gridDim.x * F3D_BLOCK) {
-        const f3d_p3 p = load_point(xyz, i);
+        const f3d_p3 p = f3d_load_p3(xyz, i);
         if (WRITE_UV) {
             const f3d_p3 h = f3d_project_h(vw.K, vw.qinv, vw.t, p);
             uv[i] = f3d_floor_to_i32(h.x / h.z);                       // camera_utils.py:24-25
@@ -108,7 +98,7 @@ template <typename T>
 __global__ __launch_bounds__(F3D_BLOCK) void k_inside_polyhedra(const T* __restrict__ xyz, int64_t n, f3d_plane_args pa,
                                                                  uint8_t* __restrict__ inside) {
     for (int64_t i = (int64_t)blockIdx.x * F3D_BLOCK + threadIdx.x; i < n; i += (int64_t)gridDim.x * F3D_BLOCK) {
-        const f3d_p3 p = load_point(xyz, i);
+        const f3d_p3 p = f3d_load_p3(xyz, i);
         bool in = pa.accumulate ? (inside[i] != 0) : true;
         for (int m = 0; m < pa.m; ++m) in = in & (f3d_plane_dp(pa.pt[m], pa.n[m], p) >= 0.0);
         inside[i] = in ? 1 : 0;
@@ -116,11 +106,6 @@ __global__ __launch_bounds__(F3D_BLOCK) void k_inside_polyhedra(const T* __restr
 }
 
 // (the fused multi-view path -- mask coding, k_fuse, k_fuse_exact, the accelerator audit -- lives in f3d_fuse.hip)
-
-// k-th entry of filter_classes: short lists travel in the kernarg, long ones in device memory
-__device__ __forceinline__ int filter_at(const f3d_filter_args& flt, int k) {
-    return (flt.nfilter <= 8) ? flt.cls[k & 7] : flt.cls_dev[k];
-}
 
 // ------------------------------------------------------------------------------------------
 // a8: segment over a dense float64 votes matrix (HBM streaming: ncols*8 B in, 8 B out per point).
@@ -156,7 +141,7 @@ __global__ __launch_bounds__(F3D_BLOCK) void k_segment_votes(const double* __res
         if (flt.nfilter > 0) {                       // votes[:, filter_classes]: position in the list is the index
             best = -INFINITY; besti = 0x7fffffff;
             for (int k = lane16; k < flt.nfilter; k += 16) {
-                const int l = filter_at(flt, k);
+                const int l = f3d_filter_at(flt, k);
                 const double x = r[l];
                 if (x > best) { best = x; besti = k; }
             }
@@ -176,7 +161,7 @@ __global__ __launch_bounds__(F3D_BLOCK) void k_segment_votes(const double* __res
             if (flt.nfilter > 0) {
                 int64_t q = cls;
                 for (int k = 0; k < flt.nfilter; ++k) {
-                    if (q == k) q = filter_at(flt, k);
+                    if (q == k) q = f3d_filter_at(flt, k);
                 }
                 cls = q;
             }
@@ -516,7 +501,7 @@ __global__ __launch_bounds__(F3D_BLOCK) void k_points_in_obb_cells(const T* __re
         const int64_t i = tile * F3D_BLOCK + tid;
         const bool live = i < n;
         f3d_p3 p = {0, 0, 0};
-        if (live) p = load_point(xyz, i);
+        if (live) p = f3d_load_p3(xyz, i);
         auto cell1 = [](double x, double lo, double inv, int dim) {
             const double t = (x - lo) * inv;
             return t >= (double)dim ? dim - 1 : (t > 0.0 ? (int)t : 0);          // NaN: 0
@@ -563,7 +548,7 @@ __global__ __launch_bounds__(F3D_BLOCK) void k_points_in_obb(const T* __restrict
         const int64_t i = tile * F3D_BLOCK + tid;
         const bool live = i < n;
         f3d_p3 p = {0, 0, 0};
-        if (live) p = load_point(xyz, i);
+        if (live) p = f3d_load_p3(xyz, i);
         uint32_t any = 0;
         // the boxes are wave-uniform: scalar loads straight from global memory (SGPR operands).  Staging them in LDS made the
         // kernel LDS-bound (15 broadcast 8-B reads per point-box test against ~25 VALU instructions).
@@ -624,19 +609,11 @@ __global__ void k_vote_batch_flag(const int* __restrict__ first_bad, int* __rest
     if (*first_bad != 0x7f7f7f7f) atomicOr(err, F3D_DEVERR_VOTE);
 }
 
-inline int grid_for(int64_t n, int per_block, int cap) {
-    int64_t g = (n + per_block - 1) / per_block;
-    if (g < 1) g = 1;
-    if (g > cap) g = cap;
-    return (int)g;
-}
-
 }  // namespace
 
 // =============================================================================================
 // launchers (called from f3d_capi.cpp)
 // =============================================================================================
-#define F3D_GRID_CAP (256 * 8 * 4)      // 256 CUs x 8 blocks, x4 so that tails stay short
 
 hipError_t f3d_launch_clear_error_bits(int* err, int bits, hipStream_t s) {
     hipLaunchKernelGGL(k_clear_error_bits, dim3(1), dim3(1), 0, s, err, bits);
@@ -646,7 +623,7 @@ hipError_t f3d_launch_clear_error_bits(int* err, int bits, hipStream_t s) {
 hipError_t f3d_launch_rotate(const double* xyz, int64_t n, const double q[4], double* out, hipStream_t s) {
     if (n <= 0) return hipSuccess;
     quat_arg qa; for (int k = 0; k < 4; ++k) qa.q[k] = q[k];
-    hipLaunchKernelGGL(k_rotate, dim3(grid_for(n, F3D_BLOCK, F3D_GRID_CAP)), dim3(F3D_BLOCK), 0, s, xyz, n, qa, out);
+    hipLaunchKernelGGL(k_rotate, dim3(f3d_grid_for(n, F3D_BLOCK, F3D_GRID_CAP)), dim3(F3D_BLOCK), 0, s, xyz, n, qa, out);
     return hipGetLastError();
 }
 
@@ -658,7 +635,7 @@ hipError_t f3d_launch_unproject_depth(const void* depth, int depth_type, int h, 
     a.fx = K[0]; a.fy = K[4]; a.cx = K[2]; a.cy = K[5]; a.scale = scale;
     for (int k = 0; k < 4; ++k) a.q[k] = q[k];
     for (int k = 0; k < 3; ++k) a.t[k] = t[k];
-    const dim3 g(grid_for(n, F3D_BLOCK, F3D_GRID_CAP)), b(F3D_BLOCK);
+    const dim3 g(f3d_grid_for(n, F3D_BLOCK, F3D_GRID_CAP)), b(F3D_BLOCK);
     if (depth_type == F3D_DEPTH_U16) hipLaunchKernelGGL(k_unproject_depth<uint16_t>, g, b, 0, s, (const uint16_t*)depth, h, w, a, out);
     else if (depth_type == F3D_DEPTH_F32) hipLaunchKernelGGL(k_unproject_depth<float>, g, b, 0, s, (const float*)depth, h, w, a, out);
     else if (depth_type == F3D_DEPTH_F64) hipLaunchKernelGGL(k_unproject_depth<double>, g, b, 0, s, (const double*)depth, h, w, a, out);
@@ -683,7 +660,7 @@ hipError_t f3d_launch_unproject_depth_batch(const void* depth, int depth_type, i
             for (int k = 0; k < 3; ++k) pb.p[f][4 + k] = t_host[3 * (size_t)(f0 + f) + k];
         }
         const int cap = (F3D_GRID_CAP + nf - 1) / nf;
-        const dim3 g(grid_for(n, F3D_BLOCK, cap < 64 ? 64 : cap), nf), b(F3D_BLOCK);
+        const dim3 g(f3d_grid_for(n, F3D_BLOCK, cap < 64 ? 64 : cap), nf), b(F3D_BLOCK);
         const char* din = reinterpret_cast<const char*>(depth) + (size_t)f0 * n * esz;
         double* dout = out + 3 * (size_t)f0 * n;
         if (depth_type == F3D_DEPTH_U16) hipLaunchKernelGGL(k_unproject_depth_batch<uint16_t>, g, b, 0, s, (const uint16_t*)din, h, w, a, pb, dout);
@@ -697,7 +674,7 @@ hipError_t f3d_launch_unproject_depth_batch(const void* depth, int depth_type, i
 hipError_t f3d_launch_project_view(const void* xyz, int dtype, int64_t n, const f3d_view& vw, int32_t* uv, uint8_t* inside,
                                    hipStream_t s) {
     if (n <= 0) return hipSuccess;
-    const dim3 g(grid_for(n, F3D_BLOCK, F3D_GRID_CAP)), b(F3D_BLOCK);
+    const dim3 g(f3d_grid_for(n, F3D_BLOCK, F3D_GRID_CAP)), b(F3D_BLOCK);
 #define F3D_PV(T, U, I) hipLaunchKernelGGL((k_project_view<T, U, I>), g, b, 0, s, (const T*)xyz, n, vw, uv, inside)
     if (dtype == F3D_F64) {
         if (uv && inside) F3D_PV(double, true, true); else if (uv) F3D_PV(double, true, false); else F3D_PV(double, false, true);
@@ -711,7 +688,7 @@ hipError_t f3d_launch_project_view(const void* xyz, int dtype, int64_t n, const 
 hipError_t f3d_launch_inside_polyhedra(const void* xyz, int dtype, int64_t n, const f3d_plane_args& pa, uint8_t* inside,
                                        hipStream_t s) {
     if (n <= 0) return hipSuccess;
-    const dim3 g(grid_for(n, F3D_BLOCK, F3D_GRID_CAP)), b(F3D_BLOCK);
+    const dim3 g(f3d_grid_for(n, F3D_BLOCK, F3D_GRID_CAP)), b(F3D_BLOCK);
     if (dtype == F3D_F64) hipLaunchKernelGGL(k_inside_polyhedra<double>, g, b, 0, s, (const double*)xyz, n, pa, inside);
     else hipLaunchKernelGGL(k_inside_polyhedra<float>, g, b, 0, s, (const float*)xyz, n, pa, inside);
     return hipGetLastError();
@@ -720,7 +697,7 @@ hipError_t f3d_launch_inside_polyhedra(const void* xyz, int dtype, int64_t n, co
 hipError_t f3d_launch_segment_votes(const double* votes, int64_t npts, int ncols, int nclasses, double threshold,
                                     const f3d_filter_args& flt, int64_t* classes, hipStream_t s) {
     if (npts <= 0) return hipSuccess;
-    const dim3 g(grid_for(npts, F3D_BLOCK / 16, F3D_GRID_CAP)), b(F3D_BLOCK);
+    const dim3 g(f3d_grid_for(npts, F3D_BLOCK / 16, F3D_GRID_CAP)), b(F3D_BLOCK);
     const bool vec2 = (ncols % 2 == 0) && ((reinterpret_cast<uintptr_t>(votes) & 15) == 0);
     if (vec2) hipLaunchKernelGGL(k_segment_votes<true>, g, b, 0, s, votes, npts, ncols, nclasses, threshold, flt, classes);
     else hipLaunchKernelGGL(k_segment_votes<false>, g, b, 0, s, votes, npts, ncols, nclasses, threshold, flt, classes);
@@ -732,7 +709,7 @@ hipError_t f3d_launch_vote_uv2pt(const int32_t* uv2pt, const uint8_t* mask, int6
     if (hw <= 0) return hipSuccess;
     hipError_t e = hipMemsetAsync(table, 0xFF, table_slots * sizeof(unsigned long long), s);
     if (e != hipSuccess) return e;
-    const dim3 g(grid_for(hw, F3D_BLOCK, F3D_GRID_CAP)), b(F3D_BLOCK);
+    const dim3 g(f3d_grid_for(hw, F3D_BLOCK, F3D_GRID_CAP)), b(F3D_BLOCK);
     hipLaunchKernelGGL(k_vote_validate, g, b, 0, s, uv2pt, mask, hw, npts, ncols, err);
     hipLaunchKernelGGL(k_vote_uv2pt, g, b, 0, s, uv2pt, mask, hw, votes, npts, ncols, table, (uint64_t)(table_slots - 1), err);
     return hipGetLastError();
@@ -743,7 +720,7 @@ hipError_t f3d_launch_vote_uv2pt_batch(const int32_t* luts, const uint8_t* masks
                                        int* err, hipStream_t s) {
     if (nframes <= 0 || h <= 0 || w <= 0) return hipSuccess;
     const int64_t hw = (int64_t)h * w;
-    hipLaunchKernelGGL(k_vote_validate_batch, dim3(grid_for(hw * nframes, F3D_BLOCK, F3D_GRID_CAP)), dim3(F3D_BLOCK), 0, s, luts, masks, (int64_t)nframes, hw,
+    hipLaunchKernelGGL(k_vote_validate_batch, dim3(f3d_grid_for(hw * nframes, F3D_BLOCK, F3D_GRID_CAP)), dim3(F3D_BLOCK), 0, s, luts, masks, (int64_t)nframes, hw,
                        npts, ncols, frame0, first_bad);
     const int tx = (w + F3D_VOTE_TILE - 1) / F3D_VOTE_TILE, ty = (h + F3D_VOTE_TILE - 1) / F3D_VOTE_TILE;
     const int64_t blocks = (int64_t)nframes * tx * ty;
@@ -759,8 +736,8 @@ hipError_t f3d_launch_sem_to_mask(const float* sem, int nimg, int c, int64_t hw,
     const bool vec4 = (hw % 4 == 0) && ((reinterpret_cast<uintptr_t>(sem) & 15) == 0) && ((reinterpret_cast<uintptr_t>(mask) & 3) == 0);
     const dim3 b(F3D_BLOCK);
     const int cap = nimg > 1 ? (F3D_GRID_CAP + nimg - 1) / nimg : F3D_GRID_CAP;
-    if (vec4) hipLaunchKernelGGL(k_sem_to_mask<true>, dim3(grid_for(hw / 4, F3D_BLOCK, cap), nimg), b, 0, s, sem, c, hw, conf, low_label, mask);
-    else hipLaunchKernelGGL(k_sem_to_mask<false>, dim3(grid_for(hw, F3D_BLOCK, cap), nimg), b, 0, s, sem, c, hw, conf, low_label, mask);
+    if (vec4) hipLaunchKernelGGL(k_sem_to_mask<true>, dim3(f3d_grid_for(hw / 4, F3D_BLOCK, cap), nimg), b, 0, s, sem, c, hw, conf, low_label, mask);
+    else hipLaunchKernelGGL(k_sem_to_mask<false>, dim3(f3d_grid_for(hw, F3D_BLOCK, cap), nimg), b, 0, s, sem, c, hw, conf, low_label, mask);
     return hipGetLastError();
 }
 
@@ -775,7 +752,7 @@ hipError_t f3d_launch_points_in_obb(const void* xyz, int dtype, int64_t n, const
         hipError_t e = hipMemsetAsync(cooc, 0, (size_t)b * b, s);
         if (e != hipSuccess) return e;
     }
-    const dim3 g(grid_for(n, F3D_BLOCK, F3D_GRID_CAP)), blk(F3D_BLOCK);
+    const dim3 g(f3d_grid_for(n, F3D_BLOCK, F3D_GRID_CAP)), blk(F3D_BLOCK);
     if (b >= F3D_OBB_CELL_MIN_BOXES && b <= 64 && cells) {     // a point visits the boxes of its cell only
         obb_grid* grid = reinterpret_cast<obb_grid*>(cells);
         unsigned long long* table = reinterpret_cast<unsigned long long*>(grid + 1);
@@ -804,6 +781,6 @@ hipError_t f3d_launch_points_in_obb(const void* xyz, int dtype, int64_t n, const
 
 hipError_t f3d_launch_relabel(int64_t* ids, int64_t n, int64_t from, int64_t to, unsigned long long* count, hipStream_t s) {
     if (n <= 0) return hipSuccess;
-    hipLaunchKernelGGL(k_relabel, dim3(grid_for(n, F3D_BLOCK, F3D_GRID_CAP)), dim3(F3D_BLOCK), 0, s, ids, n, from, to, count);
+    hipLaunchKernelGGL(k_relabel, dim3(f3d_grid_for(n, F3D_BLOCK, F3D_GRID_CAP)), dim3(F3D_BLOCK), 0, s, ids, n, from, to, count);
     return hipGetLastError();
 }

@@ -18,6 +18,15 @@
 
 struct f3d_p3 { double x, y, z; };
 
+// point i of an [n, 3] float or double cloud
+template <typename T>
+F3D_HD f3d_p3 f3d_load_p3(const T* __restrict__ xyz, int64_t i) {
+    const T* p = xyz + 3 * i;
+    f3d_p3 r;
+    r.x = (double)p[0]; r.y = (double)p[1]; r.z = (double)p[2];
+    return r;
+}
+
 // (a0*b0 + a1*b1) + a2*b2  -- the left-to-right order of the oracle
 F3D_HD double f3d_dot3(double a0, double a1, double a2, double b0, double b1, double b2) {
     return (a0 * b0 + a1 * b1) + a2 * b2;

@@ -31,18 +31,11 @@ __device__ __forceinline__ uint64_t pack_key(const f3d_nrmgrid& g, uint64_t f, i
     return (f << g.shift[3]) | ((uint64_t)cz << g.shift[2]) | ((uint64_t)cy << g.shift[1]) | (uint64_t)cx;
 }
 
-__device__ __forceinline__ void cell_of(const f3d_nrmgrid& g, double x, double y, double z, int& cx, int& cy, int& cz) {
-    // clamped: rounding at the upper faces of the box must not leave the grid
-    cx = min(g.dim[0] - 1, max(0, (int)floor((x - g.lo[0]) * g.inv_cell)));
-    cy = min(g.dim[1] - 1, max(0, (int)floor((y - g.lo[1]) * g.inv_cell)));
-    cz = min(g.dim[2] - 1, max(0, (int)floor((z - g.lo[2]) * g.inv_cell)));
-}
-
 __global__ __launch_bounds__(256) void k_nrm_keys(const double* __restrict__ xyz, int64_t n, int64_t total, f3d_nrmgrid g,
                                                    uint64_t* __restrict__ keys, uint32_t* __restrict__ idx) {
     for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
         int cx, cy, cz;
-        cell_of(g, xyz[3 * i], xyz[3 * i + 1], xyz[3 * i + 2], cx, cy, cz);
+        f3d_cell_of(g, xyz[3 * i], xyz[3 * i + 1], xyz[3 * i + 2], cx, cy, cz);
         keys[i] = pack_key(g, (uint64_t)(i / n), cx, cy, cz);
         idx[i] = (uint32_t)i;
     }
@@ -100,7 +93,7 @@ __global__ __launch_bounds__(NB) void k_nrm_query(const double* __restrict__ xyz
         const int64_t gi = perm[j];
         const int64_t f = gi / n, base = f * n;
         int cx, cy, cz;
-        cell_of(g, px, py, pz, cx, cy, cz);
+        f3d_cell_of(g, px, py, pz, cx, cy, cz);
         const uint64_t own = pack_key(g, (uint64_t)f, cx, cy, cz);
         const int64_t flo = base, fhi = base + n;                  // frame f's sorted positions
         topk<K> top;
@@ -191,17 +184,14 @@ __global__ __launch_bounds__(NB) void k_nrm_query(const double* __restrict__ xyz
     }
 }
 
-inline int grid_blocks(int64_t total, int block) { int64_t b = (total + block - 1) / block; return (int)(b < 1 ? 1 : (b > 65536 ? 65536 : b)); }
-
 struct nrm_layout { size_t keys_a, keys_b, idx_a, perm, sorted, temp, total; };
 
 nrm_layout layout_for(int64_t total, size_t temp_bytes) {
     nrm_layout L;
-    size_t o = 0;
-    auto take = [&](size_t bytes) { const size_t at = o; o += (bytes + 255) & ~(size_t)255; return at; };
-    L.keys_a = take((size_t)total * 8); L.keys_b = take((size_t)total * 8); L.idx_a = take((size_t)total * 4); L.perm = take((size_t)total * 4);
-    L.sorted = take((size_t)total * 24); L.temp = take(temp_bytes);
-    L.total = o;
+    f3d_carve c;
+    L.keys_a = c.take((size_t)total * 8); L.keys_b = c.take((size_t)total * 8); L.idx_a = c.take((size_t)total * 4); L.perm = c.take((size_t)total * 4);
+    L.sorted = c.take((size_t)total * 24); L.temp = c.take(temp_bytes);
+    L.total = c.off;
     return L;
 }
 
@@ -225,12 +215,12 @@ hipError_t f3d_launch_normals(const double* xyz, int nframes, int64_t n, const f
     uint64_t *ka = (uint64_t*)(base + L.keys_a), *kb = (uint64_t*)(base + L.keys_b);
     uint32_t *ia = (uint32_t*)(base + L.idx_a), *perm = (uint32_t*)(base + L.perm);
     double* sorted = (double*)(base + L.sorted);
-    hipLaunchKernelGGL(k_nrm_keys, dim3(grid_blocks(total, 256)), dim3(256), 0, s, xyz, n, total, g, ka, ia);
+    hipLaunchKernelGGL(k_nrm_keys, dim3(f3d_grid_for(total, 256, 65536)), dim3(256), 0, s, xyz, n, total, g, ka, ia);
     size_t t = tb;
     hipError_t e = rocprim::radix_sort_pairs(base + L.temp, t, ka, kb, ia, perm, (size_t)total, 0u, (unsigned)g.key_bits, s);
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(k_nrm_gather, dim3(grid_blocks(total, 256)), dim3(256), 0, s, xyz, total, perm, sorted);
-    const dim3 gr(grid_blocks(total, NB)), b(NB);
+    hipLaunchKernelGGL(k_nrm_gather, dim3(f3d_grid_for(total, 256, 65536)), dim3(256), 0, s, xyz, total, perm, sorted);
+    const dim3 gr(f3d_grid_for(total, NB, 65536)), b(NB);
     if (max_nn <= 8)
         hipLaunchKernelGGL(k_nrm_query<8>, gr, b, 0, s, xyz, sorted, kb, perm, n, total, g, r2, max_nn, cams, orient, normals, counts, nbrs);
     else if (max_nn <= 32)

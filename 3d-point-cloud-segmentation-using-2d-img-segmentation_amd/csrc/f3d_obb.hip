@@ -15,16 +15,12 @@
 #include <stdint.h>
 #include <rocprim/device/device_radix_sort.hpp>
 #include "f3d.h"
+#include "f3d_math.h"
 #include "f3d_kernels.h"
 
 namespace {
 
 constexpr int OB = 256;
-
-template <typename T>
-__device__ __forceinline__ void load3(const T* __restrict__ xyz, int64_t i, double& x, double& y, double& z) {
-    x = (double)xyz[3 * i]; y = (double)xyz[3 * i + 1]; z = (double)xyz[3 * i + 2];
-}
 
 __global__ __launch_bounds__(OB) void k_id_keys(const int64_t* __restrict__ ids, int64_t n, int64_t nids, uint32_t* __restrict__ keys,
                                                  uint32_t* __restrict__ idx) {
@@ -72,9 +68,8 @@ __global__ __launch_bounds__(OB) void k_obb_extremes(const T* __restrict__ xyz, 
         const uint32_t seg = live ? keys[i] : 0xFFFFFFFFu;
         float d[13];
         if (live) {
-            double x, y, z;
-            load3(xyz, (int64_t)order[i], x, y, z);
-            dir_dots((float)x, (float)y, (float)z, d);
+            const f3d_p3 p = f3d_load_p3(xyz, (int64_t)order[i]);
+            dir_dots((float)p.x, (float)p.y, (float)p.z, d);
         } else {
             for (int k = 0; k < 13; ++k) d[k] = 0.f;
         }
@@ -130,12 +125,11 @@ __global__ __launch_bounds__(OB) void k_obb_hull_filter(const T* __restrict__ xy
         const int f0 = fstart[seg], f1 = fstart[seg + 1];
         bool inside = f1 > f0;
         if (inside) {
-            double x, y, z;
-            load3(xyz, (int64_t)o, x, y, z);
+            const f3d_p3 p = f3d_load_p3(xyz, (int64_t)o);
             const double mg = -margin[seg];
             for (int f = f0; f < f1 && inside; ++f) {
                 const double* e = facets + 4 * (size_t)f;
-                inside = (__builtin_fma(e[0], x, __builtin_fma(e[1], y, __builtin_fma(e[2], z, e[3]))) < mg);
+                inside = (__builtin_fma(e[0], p.x, __builtin_fma(e[1], p.y, __builtin_fma(e[2], p.z, e[3]))) < mg);
             }
         }
         if (!inside) cand[starts[seg] + atomicAdd(&cand_count[seg], 1)] = o;
@@ -159,12 +153,11 @@ __global__ __launch_bounds__(OB) void k_obb_filter_mask(const T* __restrict__ xy
                 const int nf = nfacets[seg];
                 bool inside = nf > 0;
                 if (inside) {
-                    double x, y, z;
-                    load3(xyz, (int64_t)order[i], x, y, z);
+                    const f3d_p3 p = f3d_load_p3(xyz, (int64_t)order[i]);
                     const double mg = -margin[seg];
                     const double* e = facets + (size_t)seg * F3D_OBB_SMALL_FACETS * 4;
                     for (int f = 0; f < nf && inside; ++f, e += 4)
-                        inside = (__builtin_fma(e[0], x, __builtin_fma(e[1], y, __builtin_fma(e[2], z, e[3]))) < mg);
+                        inside = (__builtin_fma(e[0], p.x, __builtin_fma(e[1], p.y, __builtin_fma(e[2], p.z, e[3]))) < mg);
                 }
                 keep = !inside;
             }
@@ -249,26 +242,18 @@ __global__ __launch_bounds__(OB) void k_gather_points(const T* __restrict__ xyz,
     }
 }
 
-inline int grid_for(int64_t n, int cap) {
-    int64_t g = (n + OB - 1) / OB;
-    if (g < 1) g = 1;
-    if (g > cap) g = cap;
-    return (int)g;
-}
-
 struct group_layout { size_t keys_in, idx_in, temp, temp_bytes, total; };
 group_layout group_layout_for(int64_t n, unsigned bits) {
     group_layout L;
-    size_t off = 0;
-    auto take = [&](size_t bytes) { size_t o = off; off = (off + bytes + 255) & ~(size_t)255; return o; };
-    L.keys_in = take((size_t)n * 4);
-    L.idx_in = take((size_t)n * 4);
+    f3d_carve c;
+    L.keys_in = c.take((size_t)n * 4);
+    L.idx_in = c.take((size_t)n * 4);
     size_t tb = 0;
     (void)rocprim::radix_sort_pairs(nullptr, tb, (uint32_t*)nullptr, (uint32_t*)nullptr, (uint32_t*)nullptr, (uint32_t*)nullptr, (size_t)n, 0u, bits,
                                     (hipStream_t)0);
     L.temp_bytes = tb;
-    L.temp = take(tb);
-    L.total = off;
+    L.temp = c.take(tb);
+    L.total = c.off;
     return L;
 }
 
@@ -285,7 +270,7 @@ size_t f3d_group_scratch_bytes(int64_t n, int64_t nids) { return group_layout_fo
 hipError_t f3d_launch_group_by_id(const int64_t* ids, int64_t n, int64_t nids, int32_t* order, uint32_t* sorted_keys, int64_t* starts,
                                   void* scratch, hipStream_t s) {
     if (n <= 0) {
-        hipLaunchKernelGGL(k_seg_starts, dim3(grid_for(nids + 2, 65536)), dim3(OB), 0, s, sorted_keys, (int64_t)0, nids, starts);
+        hipLaunchKernelGGL(k_seg_starts, dim3(f3d_grid_for(nids + 2, OB, 65536)), dim3(OB), 0, s, sorted_keys, (int64_t)0, nids, starts);
         return hipGetLastError();
     }
     if (n > 0x7fffffffLL || nids < 0 || nids >= 0x7fffffffLL) return hipErrorInvalidValue;
@@ -294,13 +279,13 @@ hipError_t f3d_launch_group_by_id(const int64_t* ids, int64_t n, int64_t nids, i
     char* base = reinterpret_cast<char*>(scratch);
     uint32_t* keys_in = reinterpret_cast<uint32_t*>(base + L.keys_in);
     uint32_t* idx_in = reinterpret_cast<uint32_t*>(base + L.idx_in);
-    hipLaunchKernelGGL(k_id_keys, dim3(grid_for(n, 8192)), dim3(OB), 0, s, ids, n, nids, keys_in, idx_in);
+    hipLaunchKernelGGL(k_id_keys, dim3(f3d_grid_for(n, OB, 8192)), dim3(OB), 0, s, ids, n, nids, keys_in, idx_in);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
     size_t tb = L.temp_bytes;
     e = rocprim::radix_sort_pairs(base + L.temp, tb, keys_in, sorted_keys, idx_in, reinterpret_cast<uint32_t*>(order), (size_t)n, 0u, bits, s);
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(k_seg_starts, dim3(grid_for(nids + 2, 65536)), dim3(OB), 0, s, sorted_keys, n, nids, starts);
+    hipLaunchKernelGGL(k_seg_starts, dim3(f3d_grid_for(nids + 2, OB, 65536)), dim3(OB), 0, s, sorted_keys, n, nids, starts);
     return hipGetLastError();
 }
 
@@ -310,11 +295,11 @@ hipError_t f3d_launch_obb_extremes(const void* xyz, int dtype, int64_t n, const 
     hipError_t e = hipMemsetAsync(table, 0, (size_t)nseg * F3D_OBB_NDIR * sizeof(unsigned long long), s);
     if (e != hipSuccess) return e;
     if (n > 0) {
-        const dim3 g(grid_for(n, 8192)), b(OB);
+        const dim3 g(f3d_grid_for(n, OB, 8192)), b(OB);
         if (dtype == F3D_F64) hipLaunchKernelGGL(k_obb_extremes<double>, g, b, 0, s, (const double*)xyz, n, order, sorted_keys, nseg, table);
         else hipLaunchKernelGGL(k_obb_extremes<float>, g, b, 0, s, (const float*)xyz, n, order, sorted_keys, nseg, table);
     }
-    hipLaunchKernelGGL(k_obb_extremes_out, dim3(grid_for(nseg * F3D_OBB_NDIR, 65536)), dim3(OB), 0, s, table, order, nseg * F3D_OBB_NDIR, extremes);
+    hipLaunchKernelGGL(k_obb_extremes_out, dim3(f3d_grid_for(nseg * F3D_OBB_NDIR, OB, 65536)), dim3(OB), 0, s, table, order, nseg * F3D_OBB_NDIR, extremes);
     return hipGetLastError();
 }
 
@@ -324,7 +309,7 @@ hipError_t f3d_launch_obb_hull_filter(const void* xyz, int dtype, int64_t n, con
     if (nseg <= 0) return hipSuccess;
     hipError_t e = hipMemsetAsync(cand_count, 0, (size_t)nseg * sizeof(int32_t), s);
     if (e != hipSuccess || n <= 0) return e;
-    const dim3 g(grid_for(n, 8192)), b(OB);
+    const dim3 g(f3d_grid_for(n, OB, 8192)), b(OB);
     if (dtype == F3D_F64)
         hipLaunchKernelGGL(k_obb_hull_filter<double>, g, b, 0, s, (const double*)xyz, n, order, sorted_keys, starts, nseg, fstart, facets, margin, cand, cand_count);
     else
@@ -337,21 +322,20 @@ namespace {
 struct cand_layout { size_t extremes, gathered, isvert, facets, nfacets, margin, maskw, wordoff, blocksum, total, bytes; int64_t nwords; int nblocks; };
 cand_layout cand_layout_for(int64_t n, int64_t nids) {
     cand_layout L;
-    size_t off = 0;
-    auto take = [&](size_t bytes) { size_t o = off; off = (off + bytes + 255) & ~(size_t)255; return o; };
+    f3d_carve c;
     L.nwords = (n + 63) / 64;
     L.nblocks = (int)((L.nwords + SCAN_WORDS - 1) / SCAN_WORDS);
-    L.extremes = take((size_t)nids * F3D_OBB_NDIR * 4);
-    L.gathered = take((size_t)nids * F3D_OBB_NDIR * 24);
-    L.isvert = take((size_t)nids * F3D_OBB_NDIR);
-    L.facets = take((size_t)nids * F3D_OBB_SMALL_FACETS * 32);
-    L.nfacets = take((size_t)nids * 4);
-    L.margin = take((size_t)nids * 8);
-    L.maskw = take((size_t)L.nwords * 8);
-    L.wordoff = take((size_t)L.nwords * 4);
-    L.blocksum = take((size_t)(L.nblocks + 1) * 4);
-    L.total = take(8);
-    L.bytes = off;
+    L.extremes = c.take((size_t)nids * F3D_OBB_NDIR * 4);
+    L.gathered = c.take((size_t)nids * F3D_OBB_NDIR * 24);
+    L.isvert = c.take((size_t)nids * F3D_OBB_NDIR);
+    L.facets = c.take((size_t)nids * F3D_OBB_SMALL_FACETS * 32);
+    L.nfacets = c.take((size_t)nids * 4);
+    L.margin = c.take((size_t)nids * 8);
+    L.maskw = c.take((size_t)L.nwords * 8);
+    L.wordoff = c.take((size_t)L.nwords * 4);
+    L.blocksum = c.take((size_t)(L.nblocks + 1) * 4);
+    L.total = c.take(8);
+    L.bytes = c.off;
     return L;
 }
 }  // namespace
@@ -378,19 +362,19 @@ hipError_t f3d_launch_obb_candidates(const void* xyz, int dtype, int64_t n, cons
     hipError_t e = f3d_launch_obb_extremes(xyz, dtype, n, order, sorted_keys, nids, table, extremes, s);
     if (e != hipSuccess) return e;
     if ((e = f3d_launch_obb_small_hulls(xyz, dtype, extremes, starts, nids, min_members, gathered, isvert, facets, nfacets, margin, s)) != hipSuccess) return e;
-    const dim3 g(grid_for(n, 8192)), b(OB);
+    const dim3 g(f3d_grid_for(n, OB, 8192)), b(OB);
     if (dtype == F3D_F64) hipLaunchKernelGGL(k_obb_filter_mask<double>, g, b, 0, s, (const double*)xyz, n, order, sorted_keys, nids, nfacets, facets, margin, maskw);
     else hipLaunchKernelGGL(k_obb_filter_mask<float>, g, b, 0, s, (const float*)xyz, n, order, sorted_keys, nids, nfacets, facets, margin, maskw);
     hipLaunchKernelGGL(k_mask_scan_local, dim3(L.nblocks), b, 0, s, maskw, L.nwords, wordoff, blocksum);
     hipLaunchKernelGGL(k_mask_scan_blocks, dim3(1), b, 0, s, blocksum, L.nblocks, total);
     hipLaunchKernelGGL(k_obb_compact, g, b, 0, s, n, order, maskw, wordoff, blocksum, cand);
-    hipLaunchKernelGGL(k_obb_cand_starts, dim3(grid_for(nids + 1, 65536)), b, 0, s, n, starts, nids, maskw, wordoff, blocksum, total, cand_start);
+    hipLaunchKernelGGL(k_obb_cand_starts, dim3(f3d_grid_for(nids + 1, OB, 65536)), b, 0, s, n, starts, nids, maskw, wordoff, blocksum, total, cand_start);
     return hipGetLastError();
 }
 
 hipError_t f3d_launch_gather_points(const void* xyz, int dtype, const int32_t* idx, int64_t count, double* out, hipStream_t s) {
     if (count <= 0) return hipSuccess;
-    const dim3 g(grid_for(count, 8192)), b(OB);
+    const dim3 g(f3d_grid_for(count, OB, 8192)), b(OB);
     if (dtype == F3D_F64) hipLaunchKernelGGL(k_gather_points<double>, g, b, 0, s, (const double*)xyz, idx, count, out);
     else hipLaunchKernelGGL(k_gather_points<float>, g, b, 0, s, (const float*)xyz, idx, count, out);
     return hipGetLastError();

@@ -205,8 +205,6 @@ __global__ __launch_bounds__(PB) void k_patch_sums(const int32_t* __restrict__ o
     }
 }
 
-inline int blocks_for(int64_t n) { int64_t b = (n + PB - 1) / PB; return (int)(b < 1 ? 1 : (b > 8192 ? 8192 : b)); }
-
 struct patch_layout { size_t count, start, cursor, bucket, odd, nodd, temp, total; };
 
 size_t scan_temp(int64_t npx) {
@@ -217,11 +215,10 @@ size_t scan_temp(int64_t npx) {
 
 patch_layout layout_for(int64_t npx, int64_t m) {
     patch_layout L;
-    size_t o = 0;
-    auto take = [&](size_t bytes) { const size_t at = o; o += (bytes + 255) & ~(size_t)255; return at; };
-    L.count = take((size_t)(npx + 1) * 4); L.start = take((size_t)(npx + 1) * 4); L.cursor = take((size_t)(npx + 1) * 4);
-    L.bucket = take((size_t)m * 4 + 4); L.odd = take((size_t)m * 4 + 4); L.nodd = take(256); L.temp = take(scan_temp(npx));
-    L.total = o;
+    f3d_carve c;
+    L.count = c.take((size_t)(npx + 1) * 4); L.start = c.take((size_t)(npx + 1) * 4); L.cursor = c.take((size_t)(npx + 1) * 4);
+    L.bucket = c.take((size_t)m * 4 + 4); L.odd = c.take((size_t)m * 4 + 4); L.nodd = c.take(256); L.temp = c.take(scan_temp(npx));
+    L.total = c.off;
     return L;
 }
 
@@ -243,12 +240,12 @@ hipError_t f3d_launch_patch_owner(const int32_t* uv, int64_t m, int h, int w, in
     if (e != hipSuccess) return e;
     if ((e = hipMemsetAsync(base + L.cursor, 0, (size_t)(npx + 1) * 4, s)) != hipSuccess) return e;
     if ((e = hipMemsetAsync(nodd, 0, 4, s)) != hipSuccess) return e;
-    if (m > 0) hipLaunchKernelGGL(k_patch_count, dim3(blocks_for(m)), dim3(PB), 0, s, uv, m, a, count, odd, nodd);
+    if (m > 0) hipLaunchKernelGGL(k_patch_count, dim3(f3d_grid_for(m, PB, 8192)), dim3(PB), 0, s, uv, m, a, count, odd, nodd);
     size_t t = scan_temp(npx);
     e = rocprim::exclusive_scan(base + L.temp, t, count, start, (int32_t)0, (size_t)npx + 1, rocprim::plus<int32_t>(), s);
     if (e != hipSuccess) return e;
-    if (m > 0) hipLaunchKernelGGL(k_patch_fill, dim3(blocks_for(m)), dim3(PB), 0, s, uv, m, a, start, cursor, bucket);
-    hipLaunchKernelGGL(k_patch_owner, dim3(blocks_for(npx)), dim3(PB), 0, s, uv, m, a, start, bucket, odd, nodd, seed_pts, seed_nrm, q_pts,
+    if (m > 0) hipLaunchKernelGGL(k_patch_fill, dim3(f3d_grid_for(m, PB, 8192)), dim3(PB), 0, s, uv, m, a, start, cursor, bucket);
+    hipLaunchKernelGGL(k_patch_owner, dim3(f3d_grid_for(npx, PB, 8192)), dim3(PB), 0, s, uv, m, a, start, bucket, odd, nodd, seed_pts, seed_nrm, q_pts,
                        q_nrm, free_px, owner);
     return hipGetLastError();
 }
@@ -262,7 +259,7 @@ hipError_t f3d_launch_patch_seeds(const double* pts, const double* nrm, const in
     *rounds = 0;
     if (npx <= 0) return hipSuccess;
     patch_args a; a.h = h; a.w = w; a.half = half; a.radius = radius; a.min_cosine = min_cosine;
-    const dim3 g(blocks_for(npx)), b(PB);
+    const dim3 g(f3d_grid_for(npx, PB, 8192)), b(PB);
     hipLaunchKernelGGL(k_pd_init, g, b, 0, s, free_px, npx, status);
     for (int r = 0; r < (int)(npx < 1000000 ? npx + 2 : 1000002); ++r) {        // every pass resolves at least the earliest undecided pixel
         hipError_t e = hipMemsetAsync(counter, 0, 4, s);
@@ -282,7 +279,7 @@ hipError_t f3d_launch_patch_sums(const int32_t* owner, const int32_t* uv, int64_
                                  const double* rows_b, const double* rows_c, double* sums, int32_t* counts, hipStream_t s) {
     if (m <= 0) return hipSuccess;
     patch_args a; a.h = h; a.w = w; a.half = half; a.radius = 0; a.min_cosine = 0;
-    if (uv) hipLaunchKernelGGL(k_patch_sums<true>, dim3(blocks_for(m)), dim3(PB), 0, s, owner, uv, m, a, rows_a, rows_b, rows_c, sums, counts);
-    else hipLaunchKernelGGL(k_patch_sums<false>, dim3(blocks_for(m)), dim3(PB), 0, s, owner, uv, m, a, rows_a, rows_b, rows_c, sums, counts);
+    if (uv) hipLaunchKernelGGL(k_patch_sums<true>, dim3(f3d_grid_for(m, PB, 8192)), dim3(PB), 0, s, owner, uv, m, a, rows_a, rows_b, rows_c, sums, counts);
+    else hipLaunchKernelGGL(k_patch_sums<false>, dim3(f3d_grid_for(m, PB, 8192)), dim3(PB), 0, s, owner, uv, m, a, rows_a, rows_b, rows_c, sums, counts);
     return hipGetLastError();
 }

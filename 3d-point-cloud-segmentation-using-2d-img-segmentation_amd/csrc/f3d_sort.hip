@@ -383,16 +383,15 @@ struct sort_layout {
 
 sort_layout layout_for(int64_t n) {
     sort_layout L;
-    size_t off = 0;
-    auto take = [&](size_t bytes) { size_t o = off; off = (off + bytes + 255) & ~(size_t)255; return o; };
+    f3d_carve c;
     L.ntiles = (int)((n + RS_TILE - 1) / RS_TILE);
     L.wide = n > (1 << 24);
-    L.partial = take(64 * sizeof(bbox6));
-    L.keys = take((size_t)n * sizeof(sort_key_t));
-    L.recs = take((size_t)n * (L.wide ? 8 : 4));
-    L.hist = take((size_t)256 * L.ntiles * 4);
-    L.tot = take(256 * 4);
-    L.total = off;
+    L.partial = c.take(64 * sizeof(bbox6));
+    L.keys = c.take((size_t)n * sizeof(sort_key_t));
+    L.recs = c.take((size_t)n * (L.wide ? 8 : 4));
+    L.hist = c.take((size_t)256 * L.ntiles * 4);
+    L.tot = c.take(256 * 4);
+    L.total = c.off;
     return L;
 }
 
@@ -429,11 +428,10 @@ hipError_t f3d_launch_cell_sort(const void* xyz, int dtype, int64_t n, void* sor
     bbox6* partial = reinterpret_cast<bbox6*>(base + L.partial);
     sort_key_t* keys = reinterpret_cast<sort_key_t*>(base + L.keys);
     uint32_t* hist = reinterpret_cast<uint32_t*>(base + L.hist);
-    const int64_t gb = (n + SB - 1) / SB;
     const int64_t stride = n > (1 << 16) ? n >> 16 : 1;          // inspect <= ~65k points for the bounding box (4 strided loads per thread of 64 blocks)
     const int64_t sb = ((n + stride - 1) / stride + SB - 1) / SB;
     const int nparts = (int)(sb < 64 ? sb : 64);                 // (one lane of k_rs_keys' first wave per partial box)
-    const int gstream = (int)(gb < 8192 ? gb : 8192);
+    const int gstream = f3d_grid_for(n, SB, 8192);
     const dim3 gt(L.ntiles);
     const bool small = L.ntiles < 512;                          // fewer tiles than two per CU
     if (dtype == F3D_F64) {
