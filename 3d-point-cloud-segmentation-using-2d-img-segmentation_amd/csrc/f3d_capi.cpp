@@ -24,7 +24,8 @@ namespace {
 
 enum { SLOT_XYZ = 0, SLOT_OUT0, SLOT_OUT1, SLOT_VIEWS, SLOT_MASKS, SLOT_AUX0, SLOT_AUX1, SLOT_SORT_PERM, SLOT_SORT_SCRATCH,
        SLOT_TILED_MASKS, SLOT_TODO, SLOT_GRAPH, SLOT_GRAPH_BBOX, SLOT_PATCH,
-       SLOT_GRP_ORDER, SLOT_GRP_KEYS, SLOT_GRP_STARTS, SLOT_GRP_SCRATCH, SLOT_OBB_TABLE, SLOT_OBB_FACETS, SLOT_OBB_CAND, SLOT_FUSE_TABLES, SLOT_FUSE_CARRY, SLOT_FUSE_XYZ, SLOT_FUSION, SLOT_PATCH_STATUS, SLOT_NRM, SLOT_NRM_CAMS, SLOT_COUNT };
+       SLOT_GRP_ORDER, SLOT_GRP_KEYS, SLOT_GRP_STARTS, SLOT_GRP_SCRATCH, SLOT_OBB_TABLE, SLOT_OBB_FACETS, SLOT_OBB_CAND, SLOT_FUSE_TABLES, SLOT_FUSE_CARRY, SLOT_FUSE_XYZ, SLOT_FUSION, SLOT_PATCH_STATUS, SLOT_NRM, SLOT_NRM_CAMS,
+       SLOT_QRY, SLOT_QRY_IN, SLOT_QRY_OFFS, SLOT_COUNT };
 
 thread_local char g_create_err[512] = "";
 
@@ -53,6 +54,13 @@ struct f3d_ctx {
     int64_t graph_n;
     double graph_r2;
     const void* graph_xyz;
+    // radius query: the data's grid of the last count pass, in slots of its own (SLOT_QRY*), for the fill pass of the same queries
+    f3d_graphgrid qry_grid;
+    double qry_lo[3], qry_hi[3];
+    double qry_r2;
+    int64_t qry_m, qry_n;
+    int qry_qdtype;
+    const void* qry_queries;
     // instance grouping of the last f3d_group_by_id call (host-pointer sequence group -> extremes -> hull filter)
     int64_t grp_n, grp_nids;
     int grp_dtype;
@@ -290,7 +298,7 @@ f3d_ctx* f3d_ctx_create(int device) {
     }
     if (device < 0 || device >= count) { fail(nullptr, F3D_ERR_INVALID, "device %d out of range [0,%d)", device, count); return nullptr; }
     f3d_ctx* ctx = (f3d_ctx*)calloc(1, sizeof(f3d_ctx));
-    if (ctx) { ctx->graph_n = -1; ctx->grp_n = -1; }
+    if (ctx) { ctx->graph_n = -1; ctx->grp_n = -1; ctx->qry_n = -1; }
     if (!ctx) { fail(nullptr, F3D_ERR_NOMEM, "out of host memory"); return nullptr; }
     ctx->device = device;
     bool ok = hipSetDevice(device) == hipSuccess && hipStreamCreateWithFlags(&ctx->stream, hipStreamNonBlocking) == hipSuccess &&
@@ -1427,6 +1435,91 @@ int f3d_radius_graph_fill(f3d_ctx* ctx, int64_t n, int32_t* nbrs) {
     staging st(ctx);
     int32_t* dnb = st.out(SLOT_MASKS, nbrs, (size_t)nnz * 4);
     if (!st.rc) st.rc = f3d_radius_graph_fill_dev(ctx, n, doffs, dnb, s);
+    return st.finish();
+}
+
+// ---------------------------------------------------------------------------------------------
+// radius query: KDTree(data).query_radius(queries, r) inverted per query (correspondance.py:234-242) as CSR
+// ---------------------------------------------------------------------------------------------
+int f3d_radius_query_count_dev(f3d_ctx* ctx, const void* data, f3d_dtype ddtype, int64_t m, const void* queries, f3d_dtype qdtype, int64_t n,
+                               double radius, int64_t* offsets, int64_t* nnz, void* stream) {
+    int rc = enter(ctx); if (rc) return rc;
+    ctx->qry_n = -1;
+    if (!nnz || m < 0 || m > 0x7fffffffLL || n < 0 || n > 0x7fffffffLL || (m > 0 && !data) || (n > 0 && (!queries || !offsets)) ||
+        (ddtype != F3D_F64 && ddtype != F3D_F32) || (qdtype != F3D_F64 && qdtype != F3D_F32) || radius >= 1e300)
+        return fail(ctx, F3D_ERR_INVALID, "radius_query: bad arguments (m, n < 2^31, radius < 1e300)");
+    if (m == 0) return fail(ctx, F3D_ERR_INVALID, "radius_query: the data set is empty (sklearn's KDTree raises ValueError)");
+    *nnz = 0;
+    if (n == 0) { ctx->qry_n = 0; return F3D_OK; }
+    hipStream_t s = pick(ctx, stream);
+    double lo[3], ext[3];
+    if ((rc = cloud_bbox(ctx, data, ddtype, m, s, "radius_query", lo, ext))) return rc;
+    // radius < 0 or NaN: every row is empty (sklearn); the grid is built for radius 0 and no distance passes r2 = -1
+    const bool none = !(radius >= 0.0);
+    f3d_graphgrid g;
+    const double cell = neighbour_cell(none ? 0.0 : radius, ext, g.dim, [](const double d[3]) {
+        return d[0] <= 1024.0 && d[1] <= 1024.0 && d[2] <= 1024.0 && d[0] * d[1] * d[2] <= 16777216.0;
+    });
+    for (int c = 0; c < 3; ++c) g.lo[c] = lo[c];
+    g.inv_cell = 1.0 / cell; g.pad = 0;
+    double blo[3], bhi[3];                                                  // a query outside this box is more than one cell (> r) away
+    for (int c = 0; c < 3; ++c) { blo[c] = lo[c] - cell; bhi[c] = (lo[c] + ext[c]) + cell; }
+    const int64_t ncells = (int64_t)g.dim[0] * g.dim[1] * g.dim[2];
+    void* scratch;
+    if ((rc = ensure(ctx, SLOT_QRY, f3d_query_scratch_bytes(m, n, ncells), &scratch))) return rc;
+    const double r2 = none ? -1.0 : radius * radius;                       // sklearn: reduced radius = r ** 2, inclusive
+    int64_t words[2] = {0, 0};
+    F3D_HIP(ctx, f3d_launch_query_count(data, ddtype, m, queries, qdtype, n, g, blo, bhi, r2, scratch, offsets, words, s));
+    F3D_HIP(ctx, hipStreamSynchronize(s));
+    if (words[1]) return fail(ctx, F3D_ERR_INVALID, "radius_query: the queries contain NaN or infinity");
+    *nnz = words[0];
+    ctx->qry_grid = g; ctx->qry_r2 = r2; ctx->qry_m = m; ctx->qry_n = n; ctx->qry_qdtype = qdtype; ctx->qry_queries = queries;
+    for (int c = 0; c < 3; ++c) { ctx->qry_lo[c] = blo[c]; ctx->qry_hi[c] = bhi[c]; }
+    return F3D_OK;
+}
+
+int f3d_radius_query_fill_dev(f3d_ctx* ctx, const void* queries, f3d_dtype qdtype, int64_t n, const int64_t* offsets, int32_t* nbrs,
+                              void* stream) {
+    int rc = enter(ctx); if (rc) return rc;
+    if (n < 0 || n != ctx->qry_n || (n > 0 && (queries != ctx->qry_queries || qdtype != ctx->qry_qdtype)))
+        return fail(ctx, F3D_ERR_INVALID, "radius_query_fill: call f3d_radius_query_count for these queries first");
+    if (n == 0) return F3D_OK;
+    if (!offsets || !nbrs) return fail(ctx, F3D_ERR_INVALID, "radius_query_fill: bad arguments");
+    F3D_HIP(ctx, f3d_launch_query_fill(queries, qdtype, ctx->qry_m, n, ctx->qry_grid, ctx->qry_lo, ctx->qry_hi, ctx->qry_r2, ctx->slot[SLOT_QRY],
+                                       offsets, nbrs, pick(ctx, stream)));
+    return F3D_OK;
+}
+
+int f3d_radius_query_count(f3d_ctx* ctx, const void* data, f3d_dtype ddtype, int64_t m, const void* queries, f3d_dtype qdtype, int64_t n,
+                           double radius, int64_t* offsets, int64_t* nnz) {
+    int rc = enter(ctx); if (rc) return rc;
+    ctx->qry_n = -1;
+    if (!nnz || m < 0 || n < 0 || (m > 0 && !data) || (n > 0 && (!queries || !offsets)) ||
+        (ddtype != F3D_F64 && ddtype != F3D_F32) || (qdtype != F3D_F64 && qdtype != F3D_F32))
+        return fail(ctx, F3D_ERR_INVALID, "radius_query: bad arguments");
+    staging st(ctx);
+    const void* ddata = st.in(SLOT_XYZ, data, xyz_bytes(ddtype, m));
+    const void* dq = st.in(SLOT_QRY_IN, queries, xyz_bytes(qdtype, n));        // f3d_radius_query_fill reads them there
+    int64_t* doffs = st.out(SLOT_QRY_OFFS, offsets, (size_t)(n + 1) * 8);      // and these
+    if (!st.rc) st.rc = f3d_radius_query_count_dev(ctx, ddata, ddtype, m, dq, qdtype, n, radius, doffs, nnz, ctx->stream);
+    return st.finish();
+}
+
+int f3d_radius_query_fill(f3d_ctx* ctx, int64_t n, int32_t* nbrs) {
+    int rc = enter(ctx); if (rc) return rc;
+    if (n < 0 || n != ctx->qry_n || (n > 0 && ctx->qry_queries != ctx->slot[SLOT_QRY_IN]))
+        return fail(ctx, F3D_ERR_INVALID, "radius_query_fill: call f3d_radius_query_count for these queries first");
+    if (n == 0) return F3D_OK;
+    hipStream_t s = ctx->stream;
+    int64_t nnz = 0;
+    const int64_t* doffs = (const int64_t*)ctx->slot[SLOT_QRY_OFFS];         // left there by f3d_radius_query_count
+    F3D_HIP(ctx, hipMemcpyAsync(&nnz, doffs + n, 8, hipMemcpyDeviceToHost, s));
+    F3D_HIP(ctx, hipStreamSynchronize(s));
+    if (nnz == 0) return F3D_OK;
+    if (!nbrs) return fail(ctx, F3D_ERR_INVALID, "radius_query_fill: nbrs is NULL");
+    staging st(ctx);
+    int32_t* dnb = st.out(SLOT_MASKS, nbrs, (size_t)nnz * 4);
+    if (!st.rc) st.rc = f3d_radius_query_fill_dev(ctx, ctx->qry_queries, (f3d_dtype)ctx->qry_qdtype, n, doffs, dnb, s);
     return st.finish();
 }
 

@@ -164,13 +164,10 @@ int f3d_graph_reduce_bbox(const void* partial_host, int nblocks, double lo[3], d
 
 size_t f3d_graph_scratch_bytes(int64_t n, int64_t ncells) { return layout_for(n, ncells, temp_bytes_for(n)).total; }
 
-// count pass after the grid is known: sort by cell, cell table, sorted copy, neighbour counts, exclusive scan into offsets[n + 1]
-hipError_t f3d_launch_graph_count(const void* xyz, int dtype, int64_t n, const f3d_graphgrid& g, double r2, void* scratch,
-                                  int64_t* offsets, hipStream_t s) {
+// the grid itself, shared by the radius graph and the radius query: cell keys, stable sort by cell, cell table, sorted float64 copy
+static hipError_t build_grid(const void* xyz, int dtype, int64_t n, const f3d_graphgrid& g, const graph_layout& L, size_t tb, char* base,
+                             hipStream_t s) {
     const int64_t ncells = (int64_t)g.dim[0] * g.dim[1] * g.dim[2];
-    const size_t tb = temp_bytes_for(n);
-    const graph_layout L = layout_for(n, ncells, tb);
-    char* base = (char*)scratch;
     uint32_t *ka = (uint32_t*)(base + L.keys_a), *kb = (uint32_t*)(base + L.keys_b), *ia = (uint32_t*)(base + L.idx_a), *perm = (uint32_t*)(base + L.perm);
     double* sorted = (double*)(base + L.sorted);
     int2* cells = (int2*)(base + L.cells);
@@ -186,10 +183,24 @@ hipError_t f3d_launch_graph_count(const void* xyz, int dtype, int64_t n, const f
     hipLaunchKernelGGL(k_graph_cells, gr, b, 0, s, kb, n, cells);
     if (dtype == F3D_F64) hipLaunchKernelGGL(k_graph_gather<double>, gr, b, 0, s, (const double*)xyz, n, perm, sorted);
     else hipLaunchKernelGGL(k_graph_gather<float>, gr, b, 0, s, (const float*)xyz, n, perm, sorted);
-    hipLaunchKernelGGL(k_graph_scan<false>, gr, b, 0, s, sorted, n, perm, g, cells, r2, offsets, (int32_t*)nullptr);
+    return hipGetLastError();
+}
+
+// count pass after the grid is known: sort by cell, cell table, sorted copy, neighbour counts, exclusive scan into offsets[n + 1]
+hipError_t f3d_launch_graph_count(const void* xyz, int dtype, int64_t n, const f3d_graphgrid& g, double r2, void* scratch,
+                                  int64_t* offsets, hipStream_t s) {
+    const int64_t ncells = (int64_t)g.dim[0] * g.dim[1] * g.dim[2];
+    const size_t tb = temp_bytes_for(n);
+    const graph_layout L = layout_for(n, ncells, tb);
+    char* base = (char*)scratch;
+    hipError_t e = build_grid(xyz, dtype, n, g, L, tb, base, s);
+    if (e != hipSuccess) return e;
+    const dim3 gr(f3d_grid_for(n, GB, 8192)), b(GB);
+    hipLaunchKernelGGL(k_graph_scan<false>, gr, b, 0, s, (const double*)(base + L.sorted), n, (const uint32_t*)(base + L.perm), g,
+                       (const int2*)(base + L.cells), r2, offsets, (int32_t*)nullptr);
     e = hipMemsetAsync(offsets + n, 0, 8, s);
     if (e != hipSuccess) return e;
-    t = tb;
+    size_t t = tb;
     e = rocprim::exclusive_scan(base + L.temp, t, offsets, offsets, (int64_t)0, (size_t)n + 1, rocprim::plus<int64_t>(), s);
     if (e != hipSuccess) return e;
     return hipGetLastError();
@@ -203,5 +214,202 @@ hipError_t f3d_launch_graph_fill(int64_t n, const f3d_graphgrid& g, double r2, c
     const char* base = (const char*)scratch;
     hipLaunchKernelGGL(k_graph_scan<true>, dim3(f3d_grid_for(n, GB, 8192)), dim3(GB), 0, s, (const double*)(base + L.sorted), n,
                        (const uint32_t*)(base + L.perm), g, (const int2*)(base + L.cells), r2, const_cast<int64_t*>(offsets), nbrs);
+    return hipGetLastError();
+}
+
+// ---------------------------------------------------------------------------------------------
+// Bipartite form: KDTree(data).query_radius(queries, r) inverted to one row per query, rows in ascending data index.
+//   the data's grid is built as above (build_grid); one thread per query point, in the caller's order
+//   k_query_scan<0>   : matches per query -> offsets[q]; non-finite queries raise a flag (sklearn rejects them)
+//   rocprim exclusive scan -> offsets[n + 1]
+//   k_query_scan<1>   : same loops, writes the matches' caller-order data indices; the cell walk leaves <= 27 ascending runs, which
+//                       the thread sorts in place when the row is short, else it lists the row for k_query_sort_long
+//   k_query_sort_long : one block per listed row, a bitonic network in LDS (or in place in global memory past the LDS capacity)
+// A query more than one cell outside the data's box cannot match anything (cell > r) and skips the walk.  Inside that margin
+// the clamped cell of f3d_cell_of is safe: clamping never moves two points more than one cell apart, and every candidate still
+// gets the exact test.
+namespace {
+
+constexpr int QRY_SHORT = 32;           // rows up to this length are sorted by their own thread (insertion sort)
+constexpr int QRY_LDS = 8192;           // longest row k_query_sort_long sorts in LDS (32 KiB)
+
+struct qbox { double lo[3], hi[3]; };   // the data's box grown by one cell
+
+struct query_layout { graph_layout grid; size_t words, longrows, total; };
+
+// words: [0] nnz (copied from offsets[n]), [1] bit 0 = a query is NaN / infinite, [2] number of rows listed for k_query_sort_long
+query_layout query_layout_for(int64_t m, int64_t n, int64_t ncells, size_t temp_bytes) {
+    query_layout Q;
+    Q.grid = layout_for(m, ncells, temp_bytes);
+    f3d_carve c;
+    c.off = Q.grid.total;
+    Q.words = c.take(64); Q.longrows = c.take((size_t)n * 4);
+    Q.total = c.off;
+    return Q;
+}
+
+size_t query_temp_bytes(int64_t m, int64_t n) {
+    size_t a = 0, b = 0;
+    (void)rocprim::radix_sort_pairs(nullptr, a, (uint32_t*)nullptr, (uint32_t*)nullptr, (uint32_t*)nullptr, (uint32_t*)nullptr, (size_t)m, 0u, 32u);
+    (void)rocprim::exclusive_scan(nullptr, b, (int64_t*)nullptr, (int64_t*)nullptr, (int64_t)0, (size_t)n + 1, rocprim::plus<int64_t>());
+    return (a > b ? a : b) + 256;
+}
+
+template <typename T, bool FILL>
+__global__ __launch_bounds__(GB) void k_query_scan(const T* __restrict__ q, int64_t n, const double* __restrict__ sorted,
+                                                    const uint32_t* __restrict__ perm, f3d_graphgrid g, qbox box, const int2* __restrict__ cells,
+                                                    double r2, int64_t* __restrict__ offsets, int32_t* __restrict__ nbrs,
+                                                    unsigned long long* __restrict__ words, int32_t* __restrict__ longrows) {
+    for (int64_t i = (int64_t)blockIdx.x * GB + threadIdx.x; i < n; i += (int64_t)gridDim.x * GB) {
+        const double px = (double)q[3 * i], py = (double)q[3 * i + 1], pz = (double)q[3 * i + 2];
+        const int64_t start = FILL ? offsets[i] : 0, end = FILL ? offsets[i + 1] : 0;
+        int64_t out = start;
+        if (!FILL && !(fabs(px) <= 1.7976931348623157e308 && fabs(py) <= 1.7976931348623157e308 && fabs(pz) <= 1.7976931348623157e308))
+            atomicOr(&words[1], 1ull);
+        // (false for NaN as well)
+        if (px >= box.lo[0] && px <= box.hi[0] && py >= box.lo[1] && py <= box.hi[1] && pz >= box.lo[2] && pz <= box.hi[2]) {
+            int cx, cy, cz;
+            f3d_cell_of(g, px, py, pz, cx, cy, cz);
+            for (int dz = -1; dz <= 1; ++dz) {
+                const int z = cz + dz;
+                if (z < 0 || z >= g.dim[2]) continue;
+                for (int dy = -1; dy <= 1; ++dy) {
+                    const int y = cy + dy;
+                    if (y < 0 || y >= g.dim[1]) continue;
+                    for (int dx = -1; dx <= 1; ++dx) {
+                        const int x = cx + dx;
+                        if (x < 0 || x >= g.dim[0]) continue;
+                        const int2 range = cells[(z * g.dim[1] + y) * g.dim[0] + x];
+                        for (int k = range.x; k < range.y; ++k) {
+                            const double t0 = px - sorted[3 * (int64_t)k], t1 = py - sorted[3 * (int64_t)k + 1], t2 = pz - sorted[3 * (int64_t)k + 2];
+                            const double d = (t0 * t0 + t1 * t1) + t2 * t2;            // euclidean_rdist, left to right
+                            if (d <= r2) {
+                                if (FILL && out < end) nbrs[out] = (int32_t)perm[k];   // (queries changed since the count: never past the row)
+                                ++out;
+                            }
+                        }
+                    }
+                }
+            }
+        }
+        if (FILL) out = min(out, end);
+        if (!FILL) {
+            offsets[i] = out;
+        } else if (out - start > QRY_SHORT) {
+            longrows[atomicAdd((unsigned long long*)&words[2], 1ull)] = (int32_t)i;
+        } else {
+            for (int64_t a = start + 1; a < out; ++a) {                             // the row was just written: it is in this CU's cache
+                const int32_t v = nbrs[a];
+                int64_t b = a;
+                for (; b > start && nbrs[b - 1] > v; --b) nbrs[b] = nbrs[b - 1];
+                nbrs[b] = v;
+            }
+        }
+    }
+}
+
+// Ascending bitonic network on a[0, len) padded to p (a power of two) with virtual +inf: every comparator puts the smaller value at the
+// lower position (the first stage of each merge compares mirrored positions), so a comparator whose upper element lies past len is a no-op.
+// I: int in LDS, int64_t for rows sorted in place in global memory (their padded length may pass 2^30).
+template <typename I>
+__device__ void bitonic_sort(int32_t* a, I len, I p) {
+    for (I k = 2; k <= p; k <<= 1) {
+        for (I j = k >> 1; j >= 1; j >>= 1) {
+            for (I t = threadIdx.x; t < (p >> 1); t += GB) {
+                const I lo = ((t & ~(j - 1)) << 1) | (t & (j - 1));
+                const I hi = (j == (k >> 1)) ? (lo ^ (k - 1)) : lo + j;
+                if (hi < len) {
+                    const int32_t x = a[lo], y = a[hi];
+                    if (y < x) { a[lo] = y; a[hi] = x; }
+                }
+            }
+            __syncthreads();
+        }
+    }
+}
+
+__global__ __launch_bounds__(GB) void k_query_sort_long(const int64_t* __restrict__ offsets, int32_t* __restrict__ nbrs,
+                                                         const unsigned long long* __restrict__ words, const int32_t* __restrict__ longrows) {
+    __shared__ int32_t sh[QRY_LDS];
+    const int64_t count = (int64_t)words[2];
+    for (int64_t r = blockIdx.x; r < count; r += gridDim.x) {
+        const int64_t row = longrows[r];
+        const int64_t start = offsets[row];
+        const int64_t len = offsets[row + 1] - start;
+        int64_t p = 1;
+        while (p < len) p <<= 1;
+        int32_t* a = nbrs + start;
+        if (p <= QRY_LDS) {
+            for (int t = threadIdx.x; t < (int)len; t += GB) sh[t] = a[t];
+            __syncthreads();
+            bitonic_sort<int>(sh, (int)len, (int)p);
+            for (int t = threadIdx.x; t < (int)len; t += GB) a[t] = sh[t];
+        } else {
+            bitonic_sort<int64_t>(a, len, p);                                      // one block: its barriers order the global accesses
+        }
+        __syncthreads();
+    }
+}
+
+}  // namespace
+
+size_t f3d_query_scratch_bytes(int64_t m, int64_t n, int64_t ncells) {
+    return query_layout_for(m, n, ncells, query_temp_bytes(m, n)).total;
+}
+
+hipError_t f3d_launch_query_count(const void* data, int ddtype, int64_t m, const void* queries, int qdtype, int64_t n, const f3d_graphgrid& g,
+                                  const double box_lo[3], const double box_hi[3], double r2, void* scratch, int64_t* offsets,
+                                  int64_t* words_host, hipStream_t s) {
+    const int64_t ncells = (int64_t)g.dim[0] * g.dim[1] * g.dim[2];
+    const size_t tb = query_temp_bytes(m, n);
+    const query_layout Q = query_layout_for(m, n, ncells, tb);
+    char* base = (char*)scratch;
+    unsigned long long* words = (unsigned long long*)(base + Q.words);
+    hipError_t e = hipMemsetAsync(words, 0, 64, s);
+    if (e != hipSuccess) return e;
+    if ((e = build_grid(data, ddtype, m, g, Q.grid, tb, base, s)) != hipSuccess) return e;
+    qbox box;
+    for (int c = 0; c < 3; ++c) { box.lo[c] = box_lo[c]; box.hi[c] = box_hi[c]; }
+    const double* sorted = (const double*)(base + Q.grid.sorted);
+    const uint32_t* perm = (const uint32_t*)(base + Q.grid.perm);
+    const int2* cells = (const int2*)(base + Q.grid.cells);
+    const dim3 gr(f3d_grid_for(n, GB, 8192)), b(GB);
+    if (qdtype == F3D_F64)
+        hipLaunchKernelGGL((k_query_scan<double, false>), gr, b, 0, s, (const double*)queries, n, sorted, perm, g, box, cells, r2, offsets,
+                           (int32_t*)nullptr, words, (int32_t*)nullptr);
+    else
+        hipLaunchKernelGGL((k_query_scan<float, false>), gr, b, 0, s, (const float*)queries, n, sorted, perm, g, box, cells, r2, offsets,
+                           (int32_t*)nullptr, words, (int32_t*)nullptr);
+    if ((e = hipMemsetAsync(offsets + n, 0, 8, s)) != hipSuccess) return e;
+    size_t t = tb;
+    e = rocprim::exclusive_scan(base + Q.grid.temp, t, offsets, offsets, (int64_t)0, (size_t)n + 1, rocprim::plus<int64_t>(), s);
+    if (e != hipSuccess) return e;
+    if ((e = hipMemcpyAsync(words, offsets + n, 8, hipMemcpyDeviceToDevice, s)) != hipSuccess) return e;
+    return hipMemcpyAsync(words_host, words, 16, hipMemcpyDeviceToHost, s);     // the caller synchronises
+}
+
+hipError_t f3d_launch_query_fill(const void* queries, int qdtype, int64_t m, int64_t n, const f3d_graphgrid& g, const double box_lo[3],
+                                 const double box_hi[3], double r2, void* scratch, const int64_t* offsets, int32_t* nbrs, hipStream_t s) {
+    const int64_t ncells = (int64_t)g.dim[0] * g.dim[1] * g.dim[2];
+    const query_layout Q = query_layout_for(m, n, ncells, query_temp_bytes(m, n));
+    char* base = (char*)scratch;
+    unsigned long long* words = (unsigned long long*)(base + Q.words);
+    int32_t* longrows = (int32_t*)(base + Q.longrows);
+    hipError_t e = hipMemsetAsync(words + 2, 0, 8, s);
+    if (e != hipSuccess) return e;
+    qbox box;
+    for (int c = 0; c < 3; ++c) { box.lo[c] = box_lo[c]; box.hi[c] = box_hi[c]; }
+    const double* sorted = (const double*)(base + Q.grid.sorted);
+    const uint32_t* perm = (const uint32_t*)(base + Q.grid.perm);
+    const int2* cells = (const int2*)(base + Q.grid.cells);
+    int64_t* offs = const_cast<int64_t*>(offsets);                              // (read only in the fill pass)
+    const dim3 gr(f3d_grid_for(n, GB, 8192)), b(GB);
+    if (qdtype == F3D_F64)
+        hipLaunchKernelGGL((k_query_scan<double, true>), gr, b, 0, s, (const double*)queries, n, sorted, perm, g, box, cells, r2, offs, nbrs,
+                           words, longrows);
+    else
+        hipLaunchKernelGGL((k_query_scan<float, true>), gr, b, 0, s, (const float*)queries, n, sorted, perm, g, box, cells, r2, offs, nbrs,
+                           words, longrows);
+    hipLaunchKernelGGL(k_query_sort_long, dim3(2048), b, 0, s, offsets, nbrs, words, longrows);
     return hipGetLastError();
 }

@@ -150,6 +150,16 @@ hipError_t f3d_launch_graph_count(const void* xyz, int dtype, int64_t n, const f
                                   int64_t* offsets, hipStream_t s);
 hipError_t f3d_launch_graph_fill(int64_t n, const f3d_graphgrid& g, double r2, const void* scratch, const int64_t* offsets,
                                  int32_t* nbrs, hipStream_t s);
+// radius query (f3d_graph.hip): KDTree(data).query_radius(queries, r) inverted, one row per query in ascending data index.  Grid over
+// the m data points (from the f3d_launch_graph_bbox partials), box_lo / box_hi = the data's box grown by one cell.  The count pass
+// enqueues the readback of words_host[0] = nnz and words_host[1] = 1 if a query is NaN / infinite (the caller synchronises); the fill
+// pass needs the same queries and the scratch (f3d_query_scratch_bytes) of the count pass
+size_t f3d_query_scratch_bytes(int64_t m, int64_t n, int64_t ncells);
+hipError_t f3d_launch_query_count(const void* data, int ddtype, int64_t m, const void* queries, int qdtype, int64_t n, const f3d_graphgrid& g,
+                                  const double box_lo[3], const double box_hi[3], double r2, void* scratch, int64_t* offsets,
+                                  int64_t* words_host, hipStream_t s);
+hipError_t f3d_launch_query_fill(const void* queries, int qdtype, int64_t m, int64_t n, const f3d_graphgrid& g, const double box_lo[3],
+                                 const double box_hi[3], double r2, void* scratch, const int64_t* offsets, int32_t* nbrs, hipStream_t s);
 
 // surface normals (f3d_normals.hip): F frames of n float64 points, grid chosen on the host from the f3d_launch_graph_bbox partials;
 // cams device [F, 3].  Enqueue only.  scratch: f3d_normals_scratch_bytes(F * n)

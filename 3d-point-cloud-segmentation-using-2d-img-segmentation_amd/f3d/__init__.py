@@ -149,6 +149,10 @@ def library():
         'f3d_radius_graph_fill': (i32, [vp, i64, vp]),
         'f3d_radius_graph_count_dev': (i32, [vp, vp, i32, i64, dbl, vp, vp, vp]),
         'f3d_radius_graph_fill_dev': (i32, [vp, i64, vp, vp, vp]),
+        'f3d_radius_query_count': (i32, [vp, vp, i32, i64, vp, i32, i64, dbl, vp, vp]),
+        'f3d_radius_query_fill': (i32, [vp, i64, vp]),
+        'f3d_radius_query_count_dev': (i32, [vp, vp, i32, i64, vp, i32, i64, dbl, vp, vp, vp]),
+        'f3d_radius_query_fill_dev': (i32, [vp, vp, i32, i64, vp, vp, vp]),
         'f3d_estimate_normals': (i32, [vp, vp, i64, vp, dbl, i32, i32, vp, vp, vp]),
         'f3d_estimate_normals_batch_dev': (i32, [vp, vp, i32, i64, vp, dbl, i32, i32, vp, vp, vp, vp]),
     }
@@ -589,6 +593,19 @@ class Context:
         self._check(self._lib.f3d_radius_graph_fill(self._h, len(p), _ptr(nb)))
         return offs, nb
 
+    def radius_query(self, data, queries, radius):
+        """KDTree(data).query_radius(queries, r=radius) inverted per query (correspondance.py:234-242) as CSR: (offsets int64 [n+1],
+        neighbours int32); row q lists the data indices within radius of query q (inclusive) in ascending order."""
+        d, ddt = _xyz(data)
+        q, qdt = _xyz(queries)
+        offs = np.zeros(len(q) + 1, np.int64)
+        nnz = C.c_int64(0)
+        self._check(self._lib.f3d_radius_query_count(self._h, _ptr(d), ddt, len(d), _ptr(q), qdt, len(q), float(radius), _ptr(offs),
+                                                     C.byref(nnz)))
+        nb = np.empty(nnz.value, np.int32)
+        self._check(self._lib.f3d_radius_query_fill(self._h, len(q), _ptr(nb)))
+        return offs, nb
+
     def estimate_normals(self, points, cam_centre, radius=0.05, max_nn=30, orient=True, want_neighbours=False):
         """Open3D's estimate_normals(KDTreeSearchParamHybrid(radius, max_nn)) + the flip towards ``cam_centre`` of
         RTAB2Cache.surface_normal_estimation (ios_rtab.py:236-248), one frame: float64 [N,3] (f3d.h f3d_estimate_normals).
@@ -637,6 +654,17 @@ class Context:
         f, nf = _filter(filter_classes)
         self._check(self._lib.f3d_fuse_chunk_coded_dev(self._h, xyz_ptr, dtype, n, views_ptr, nviews, int(v_begin), int(v_end), coded_ptr, h, w,
                                                        int(nclasses), _ptr(f), nf, float(threshold), classes_ptr, int(flags), perm_ptr, stream))
+
+    def radius_query_dev(self, data_ptr, data_dtype, m, queries_ptr, query_dtype, n, radius, offsets_ptr, stream=None):
+        """Count pass of radius_query on device pointers: offsets int64 [n+1] on the device; -> nnz (one blocking readback)."""
+        nnz = C.c_int64(0)
+        self._check(self._lib.f3d_radius_query_count_dev(self._h, data_ptr, int(data_dtype), int(m), queries_ptr, int(query_dtype), int(n),
+                                                         float(radius), offsets_ptr, C.byref(nnz), stream))
+        return nnz.value
+
+    def radius_query_fill_dev(self, queries_ptr, query_dtype, n, offsets_ptr, neighbours_ptr, stream=None):
+        """Fill pass after radius_query_dev of the same queries: neighbours int32 [nnz] on the device (enqueue only)."""
+        self._check(self._lib.f3d_radius_query_fill_dev(self._h, queries_ptr, int(query_dtype), int(n), offsets_ptr, neighbours_ptr, stream))
 
     def rotate_dev(self, xyz_ptr, n, q_wxyz, out_ptr, stream=None):
         q = _f64(q_wxyz, (4,))

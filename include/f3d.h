@@ -417,6 +417,27 @@ int f3d_radius_graph_count_dev(f3d_ctx* ctx, const void* xyz, f3d_dtype dtype, i
 int f3d_radius_graph_fill_dev(f3d_ctx* ctx, int64_t n, const int64_t* offsets /*device*/,
                               int32_t* neighbours /*device [nnz]*/, void* stream);
 
+/* ---- the bipartite form: PointCorrespondance.get_merge_maps (segUtils/correspondance.py:234-242) ------ */
+/* tree = KDTree(dense, leaf_size=2); nb = tree.query_radius(sparse, r) inverted: row q (one per QUERY point, the dense pixels)
+ * lists every DATA index i (the sparse cloud) with float64 squared distance ((dx*dx + dy*dy) + dz*dz, sklearn's euclidean_rdist
+ * order) <= r*r, INCLUSIVE, in ASCENDING i (the order the reference's inversion loop appends them in).  float32 inputs are widened
+ * exactly; data and queries have a dtype each.  CSR in two passes, like f3d_radius_graph_*:
+ *   count: offsets int64 [n+1] (exclusive scan, offsets[n] = *nnz); the data's grid stays in the context, in state of its own
+ *          (other entries may run between the two passes),
+ *   fill : neighbours int32 [*nnz], row q = offsets[q] .. offsets[q+1]; must follow the count pass of the same queries (the _dev
+ *          fill takes the same query pointer and dtype again, and the queries must hold the same values).
+ * Errors (sklearn raises ValueError, here F3D_ERR_INVALID): m == 0, NaN / infinity in the data or in the queries, radius = +inf
+ * (sklearn would return every pair; so does any radius >= 1e300 here).  radius < 0 or NaN: every row is empty, no error.  n == 0:
+ * nothing to do.  One blocking readback per count pass (nnz and the non-finite flag together). */
+int f3d_radius_query_count(f3d_ctx* ctx, const void* data, f3d_dtype data_dtype, int64_t m, const void* queries,
+                           f3d_dtype query_dtype, int64_t n, double radius, int64_t* offsets /*[n+1]*/, int64_t* nnz);
+int f3d_radius_query_fill(f3d_ctx* ctx, int64_t n, int32_t* neighbours /*[nnz]*/);
+int f3d_radius_query_count_dev(f3d_ctx* ctx, const void* data, f3d_dtype data_dtype, int64_t m, const void* queries,
+                               f3d_dtype query_dtype, int64_t n, double radius, int64_t* offsets /*device [n+1]*/,
+                               int64_t* nnz /*host*/, void* stream);
+int f3d_radius_query_fill_dev(f3d_ctx* ctx, const void* queries /*device, as counted*/, f3d_dtype query_dtype, int64_t n,
+                              const int64_t* offsets /*device*/, int32_t* neighbours /*device [nnz]*/, void* stream);
+
 /* ---- a5: patch matching of Fusion.fuse (Fusion3DSeg/fusion.py:269-298) ------------------- */
 /* The loop over the in-frustum points ("seeds", in index order) of one frame: seed k takes the still-free depth pixels of
  * the (2*half+1)^2 window around its projection uv[:,k] that lie within `radius` of it and whose normals satisfy
