@@ -455,6 +455,96 @@ def fuse_match_frame(uv, x_pts, x_nrm, x_clr, x_mrg, x_occ, ids, q_pts, q_nrm, q
     return uv2pt
 
 
+def patch_downsample(points, normals, colors, h, w, stride, radius, min_cosine, pcdimg, pt2u, pt2v, free=None):
+    """Fusion.patch_downsample (fusion.py:134-210), literally: the pixels are visited in an order shuffled by the GLOBAL NumPy
+    generator; a pixel still free when visited is a seed that takes the free pixels of its row-major window passing the criterion
+    (itself included when it accepts itself), stops at ``count == 0``, and appends the np.mean of what it took (an empty set gives
+    a NaN row and a zero count).  ``free`` [h, w] is consumed in place.  Returns (points, normals, colours, uv2pt int32 [h*w], nmerges)."""
+    order = np.arange(len(points))
+    np.random.shuffle(order)
+    free = np.ones((h, w), dtype=bool) if free is None else free
+    uv2pt = np.full(h * w, -1, np.int32)
+    count, half = h * w, stride // 2
+    out_p, out_n, out_c, out_m = [], [], [], []
+    for pt in order:
+        u_, v_ = pt2u[pt], pt2v[pt]
+        if not free[v_, u_]:
+            continue
+        if not count:
+            break
+        starti, endi = max(0, v_ - half), v_ + half + 1
+        startj, endj = max(0, u_ - half), u_ + half + 1
+        patch = pcdimg[starti:endi, startj:endj].reshape(-1)
+        patch = patch[free[starti:endi, startj:endj].reshape(-1)]
+        p_pts, p_nrm, p_clr = points[patch], normals[patch], colors[patch]
+        dist = np.linalg.norm(p_pts - points[pt][None, :], axis=-1)
+        mask = (dist < radius) & (np.einsum('ij, j -> i', p_nrm, normals[pt]) > min_cosine)
+        taken = mask.sum()
+        merged = patch[mask]
+        count -= taken
+        out_p.append(np.mean(p_pts[mask], axis=0))
+        out_c.append(np.mean(p_clr[mask], axis=0))
+        n = np.mean(p_nrm[mask], axis=0)
+        out_n.append(n / np.linalg.norm(n))
+        out_m.append(taken)
+        uv2pt[merged] = len(out_m) - 1
+        free[pt2v[merged], pt2u[merged]] = False
+    return np.array(out_p), np.array(out_n), np.array(out_c), uv2pt, np.array(out_m)
+
+
+def fuse(K, w, h, wxyzs, translations, frames, radius=0.05, angle=10, stride=None, max_depth=10, skip=1):
+    """Fusion.fuse (fusion.py:212-324), literally, on ``frames[i]`` = (name, points [h*w,3], normals, colours, valid [h*w]) ->
+    (points, normals, colours, nmerges, occurences, lookups); ``lookups`` lists (name, uv2pt) in the order the reference saves them.
+
+    Quirks kept: the first frame with any valid pixel is down-sampled with ``stride``, later frames with ``2 * stride``; frames
+    ``first + 1, first + 1 + skip, ...`` are fused and all-invalid ones skipped; the frames' valid masks are consumed in place; a frame
+    whose frustum holds none of the cloud down-samples its points on the PREVIOUS fused frame's (consumed) mask -- UnboundLocalError
+    if there is none; new rows' lookups are offset by the cloud size; ``occurences`` is uint32; the default stride is
+    max(10, int(radius * 200)).  The frustum planes, cull and projection are this module's (a3, a4, a2).  Pinned, with
+    patch_downsample, by tests/test_fusion_oracle_cpu.py against tests/golden/fuse.npz and fuse_curved.npz."""
+    stride = max(10, int(radius * 200)) if stride is None else stride
+    half, min_cosine = stride // 2, np.cos(np.deg2rad(angle))
+    npts = h * w
+    pcdimg = np.arange(npts).reshape(h, w)
+    pt2u, pt2v = (np.arange(npts) % w).astype(np.int32), (np.arange(npts) // w).astype(np.int32)
+    plane_pts, plane_nrm = frustum_planes(K, w, h, wxyzs, translations, max_depth)
+    lookups = []
+    for first in range(len(frames)):
+        name, pts, nrm, clr, valid = frames[first]
+        if valid.any():
+            break
+    pts, nrm, clr, uv2pt, nmerges = patch_downsample(pts, nrm, clr, h, w, stride, radius, min_cosine, pcdimg, pt2u, pt2v,
+                                                     valid.reshape(h, w))
+    lookups.append((name, uv2pt))
+    occurences = np.ones(len(pts), np.uint32)
+    free = None
+    for j in range(first + 1, len(frames), skip):
+        name, q_pts, q_nrm, q_clr, q_valid = frames[j]
+        if not q_valid.any():
+            continue
+        uv2pt = np.full(npts, -1, np.int32)
+        hits = point_inside_polyhedra(pts, plane_pts[j], plane_nrm[j])
+        if hits.any():
+            ids = np.where(hits)[0]
+            x_pts, x_nrm, x_clr, x_mrg, x_occ = pts[hits], nrm[hits], clr[hits], nmerges[hits], occurences[hits]
+            uv = points2pixel(x_pts, K, wxyzs[j], translations[j])
+            free = q_valid.reshape(h, w)
+            uv2pt = fuse_match_frame(uv, x_pts, x_nrm, x_clr, x_mrg, x_occ, ids, q_pts, q_nrm, q_clr, free, h, w, half, radius, min_cosine)
+            pts[hits], nrm[hits], clr[hits], nmerges[hits], occurences[hits] = x_pts, x_nrm, x_clr, x_mrg, x_occ
+        if free is None:
+            raise UnboundLocalError("the first fused frame has no hits: the reference has no free mask to down-sample on")
+        if free.any():
+            n_pts, n_nrm, n_clr, n_uv2pt, n_mrg = patch_downsample(q_pts, q_nrm, q_clr, h, w, 2 * stride, radius, min_cosine,
+                                                                   pcdimg, pt2u, pt2v, free)
+            fresh = n_uv2pt != -1
+            uv2pt[fresh] = n_uv2pt[fresh] + len(pts)
+            pts, nrm, clr = np.vstack([pts, n_pts]), np.vstack([nrm, n_nrm]), np.vstack([clr, n_clr])
+            nmerges = np.hstack([nmerges, n_mrg])
+            occurences = np.hstack([occurences, np.ones(len(n_pts), np.uint32)])
+        lookups.append((name, uv2pt))
+    return pts, nrm, clr, nmerges, occurences, lookups
+
+
 def radius_adjacency(points, r):
     """fusion.py:374-375: KDTree(points).query_radius(points, r) -- brute force over all pairs with the tree's leaf test:
     sklearn's euclidean_rdist accumulates (x1[j] - x2[j])**2 for j = 0, 1, 2 in that order and query_radius keeps
