@@ -6,11 +6,12 @@ the north star names (last row); it runs as ONE fused HIP kernel.
 ``Fusion`` is the reference's class (fusion.py:80-407): per frame, ``fuse`` culls the fused cloud against the frame's
 frustum and projects the survivors (rows a3, a4, a2 -- here ONE launch of the single-view HIP kernel per frame), then
 greedily matches depth patches to those points and down-samples what is left (``patch_downsample``).  The greedy part is
-a chain of data-dependent decisions (every match removes pixels from later candidates) and runs on the host, as in the
-reference; it draws its shuffles from NumPy's global generator at the same places, so a seeded run reproduces the
-reference's output (tests/golden/fuse.npz).  ``Fusion.fuse_device`` is the same loop with the cloud, the frames and the lookups resident on the
-GPU (opt-in; bit-identical to ``fuse``).
+a chain of data-dependent decisions (every match removes pixels from later candidates); HIP kernels settle it in data-parallel
+rounds with the reference's outcome.  The shuffles are drawn from NumPy's global generator at the same places, so a seeded run
+reproduces the reference's output (tests/golden/fuse.npz).  There is one frame loop, ``_DeviceFusion.run``, with the cloud
+resident on the GPU: ``fuse_device`` returns its tensors, ``fuse`` is the drop-in with NumPy in and out.
 """
+import contextlib
 import pickle
 import time
 from fractions import Fraction
@@ -175,6 +176,13 @@ def _mergeable(seed_pt, seed_normal, cand_pts, cand_normals, max_distance, min_c
     return near & (np.einsum('ij, j -> i', cand_normals, seed_normal) > min_cosine)
 
 
+def _unusable(points, normals, min_cosine):
+    """Pixels that would not accept themselves as a seed (zero / NaN normal: np.einsum's dot, the order of _mergeable) or hold a
+    non-finite point; the reference then averages an empty set and leaves the pixel to later seeds."""
+    own_cos = np.einsum('ij,ij->i', normals, normals)
+    return ~((own_cos > min_cosine) & np.isfinite(points).all(axis=1))
+
+
 class Fusion:
     def __init__(self, tof, rts, point_range=None, decimation=1, save_lookups=True):
         K, w, h, wxyzs, translations = parse_rts(rts)
@@ -225,43 +233,32 @@ class Fusion:
         is replaced by their mean.  Returns (points, normals, colours, uv2pt int32 [h*w] with -1 = none, merge counts).
 
         "Still free when visited" is the only sequential coupling, and it is local: pixel p is a seed iff no EARLIER seed whose
-        window covers it accepts it.  The HIP kernels settle that in a few data-parallel rounds and return, per pixel, the seed
-        that takes it; the host then only adds the members of every seed in the reference's order."""
+        window covers it accepts it.  The frame goes through the down-sampling step of ``fuse`` (``_DeviceFusion.downsample``) into an
+        empty resident cloud: HIP kernels settle the seeds in a few data-parallel rounds, add the members of every seed in the
+        reference's order and write the new rows in visiting order."""
         order = np.arange(len(points))
         np.random.shuffle(order)                                              # the global generator, as the reference (:172)
         free = np.ones((height, width), dtype=bool) if non_merged is None else non_merged   # updated in place, like the reference
         half = stride // 2
         points, normals = np.asarray(points, np.float64), np.asarray(normals, np.float64)
         flat_free = free.reshape(-1)
-        own_cos = np.einsum('ij,ij->i', normals, normals)
-        usable = (own_cos > min_cosine) & np.isfinite(points).all(axis=1)
-        if len(points) != height * width or not (max_distance > 0) or (flat_free & ~usable).any():
-            # a free pixel that would not accept itself (zero / NaN normal): the reference then averages an empty set and leaves the
-            # pixel to later seeds -- keep its literal order of events for such frames
+        if len(points) != height * width or not (max_distance > 0) or (flat_free & _unusable(points, normals, min_cosine)).any():
+            # a free pixel that would not accept itself: keep the reference's literal order of events for such frames
             return cls._patch_downsample_sequential(order, points, normals, colors, height, width, half, max_distance, min_cosine,
                                                     pcdimg, pt2u, pt2v, free)
-        prio = np.empty(len(points), np.int32)
-        prio[order] = np.arange(len(points), dtype=np.int32)
-        # seeds, what each of them takes, and the ordered sums of those rows (a thread per seed adds its members in ascending pixel
-        # index = the reference's window order, so the means are bit-identical): one call, the frame uploaded once
-        colors = np.asarray(colors, np.float64)
-        owner, sums, counts, _ = f3d.default_context().patch_seeds_sums(points, normals, colors, prio, flat_free, height, width, half,
-                                                                        max_distance, min_cosine)
-        uv2pt = np.full(height * width, -1, np.int32)
-        seeds = np.nonzero(owner == np.arange(height * width, dtype=np.int32))[0]
-        if not len(seeds):
+        with _DeviceFusion.on_stream('Fusion.patch_downsample', height, width, pcdimg, pt2u, pt2v) as df:
+            frame = df.frame((None, points, normals, colors, flat_free))
+            df.free.copy_(frame[4])
+            df.order_stage.numpy()[:] = order
+            uv2pt = df.torch.full((height * width,), -1, dtype=df.torch.int32, device=df.dev)
+            df.downsample(order, frame, half, max_distance, min_cosine, False, height * width, 0, uv2pt)
+            k = int(df.count_dev.item())
+            out_p, out_n, out_c, n_take = (t[:k].cpu().numpy() for t in df.cloud[:4])
+            df.consume(free)
+            uv2pt = uv2pt.cpu().numpy()
+        if not k:
             return np.array([]), np.array([]), np.array([]), uv2pt, np.array([])
-        seeds = seeds[np.argsort(prio[seeds], kind='stable')]                # seeds in visiting order = output order
-        n_take = counts[seeds].astype(np.int64)
-        mean = sums[seeds] / n_take[:, None]                                 # np.mean: the ordered sum, then one division
-        out_p, nsum, out_c = mean[:, 0:3], mean[:, 3:6], mean[:, 6:9]
-        out_n = nsum / _row_norms(nsum)[:, None]
-        rank = np.empty(height * width, np.int32)
-        rank[seeds] = np.arange(len(seeds), dtype=np.int32)
-        taken = owner >= 0
-        uv2pt[taken] = rank[owner[taken]]
-        free.reshape(-1)[taken] = False
-        return np.ascontiguousarray(out_p), out_n, np.ascontiguousarray(out_c), uv2pt, n_take
+        return out_p, out_n, out_c, uv2pt, n_take
 
     @staticmethod
     def _patch_downsample_sequential(order, points, normals, colors, height, width, half, max_distance, min_cosine, pcdimg, pt2u, pt2v, free):
@@ -293,116 +290,42 @@ class Fusion:
         return f3d.views_build(self.K, self.w, self.h, self.xyzws[j:j + 1], self.translations[j:j + 1], max_depth)[0]
 
     def fuse(self, radius=0.05, angle=10, stride=None, max_depth=10, skip=1, verbose=False):
-        """Fuse + down-sample the frames into one sparse cloud (reference :212-324) ->
-        (points, normals, colours, nmerges, occurences); per-frame ``uv2pt`` lookups are saved when requested."""
-        self.ds_radius, self.ds_angle = radius, angle
-        stride = max(10, int(radius * 200)) if stride is None else stride
-        half, min_cosine = stride // 2, np.cos(np.deg2rad(angle))
-        ctx = f3d.default_context()
-        for first in range(0, self.nframes):                                 # first frame with any valid pixel seeds the cloud
-            name, pts, nrm, clr, valid = self.frames[first]
-            if valid.any():
-                break
-        pts, nrm, clr, uv2pt, nmerges = self.patch_downsample(pts, nrm, clr, self.h, self.w, stride, radius, min_cosine,
-                                                               self.pcdimg, self.pt2u, self.pt2v, valid.reshape(self.h, self.w))
-        if self.save_lookups:
-            self._save_uv2pt(uv2pt, name)
-        occurences = np.ones(len(pts), np.uint32)
-        hits = np.ones(self.npts, dtype=bool)
-        for j in range(first + 1, self.nframes, skip):
-            if verbose:
-                print(f'fusing frame: {j + 1}, total points = {len(pts)}, previous intersections = {hits.sum()}')
-            name, q_pts, q_nrm, q_clr, q_valid = self.frames[j]
-            if not q_valid.any():
-                continue
-            uv2pt = np.full(self.npts, -1, np.int32)
-            # a3 + a4 + a2 of the reference (:254-266) in one launch: frustum (4 sides + far plane at max_depth) membership of
-            # every fused point and the pixel it projects to
-            uv_all, hits = ctx.project_view(pts, self._frame_view(j, max_depth))
-            if hits.any():
-                ids = np.where(hits)[0]
-                x_pts, x_nrm, x_clr = pts[hits], nrm[hits], clr[hits]
-                x_mrg, x_occ = nmerges[hits], occurences[hits]
-                uv = uv_all[:, hits]
-                free = q_valid.reshape(self.h, self.w)                      # a view: the frame's mask is consumed, as in the reference
-                # The reference visits the seeds in index order and lets each take the free pixels of its window that pass the
-                # criterion (:269-298).  A seed's criterion uses its own position / normal from BEFORE this frame, so the result
-                # is: a free pixel belongs to the first seed whose window covers it and accepts it -- one HIP launch.
-                # ... followed, on the resident frame, by one thread per seed that adds the rows of the pixels it took in ascending
-                # pixel index (((r0 + r1) + r2) + ..., the order np.mean adds the reference's vstack in)
-                owner, sums, counts = ctx.patch_match(uv, x_pts, x_nrm, q_pts, q_nrm, q_clr, free.reshape(-1), self.h, self.w, half, radius,
-                                                      min_cosine)
-                seeds = np.nonzero(counts)[0]
-                if len(seeds):
-                    n_take = counts[seeds].astype(np.int64)
-                    denom = (n_take + 1)[:, None]                           # the seed itself is the last row of the reference's vstack
-                    x_pts[seeds] = (sums[seeds, 0:3] + x_pts[seeds]) / denom
-                    x_clr[seeds] = (sums[seeds, 6:9] + x_clr[seeds]) / denom
-                    nsum = (sums[seeds, 3:6] + x_nrm[seeds]) / denom
-                    x_nrm[seeds] = nsum / _row_norms(nsum)[:, None]
-                    x_mrg[seeds] += n_take
-                    x_occ[seeds] += 1
-                    taken = owner >= 0
-                    uv2pt[taken] = ids[owner[taken]]
-                    free.reshape(-1)[taken] = False
-                pts[hits], nrm[hits], clr[hits] = x_pts, x_nrm, x_clr
-                nmerges[hits], occurences[hits] = x_mrg, x_occ
-            if free.any():                                                    # (as in the reference, `free` of an earlier frame if none hit)
-                n_pts, n_nrm, n_clr, n_uv2pt, n_mrg = self.patch_downsample(q_pts, q_nrm, q_clr, self.h, self.w, 2 * stride, radius,
-                                                                             min_cosine, self.pcdimg, self.pt2u, self.pt2v, free)
-                fresh = n_uv2pt != -1
-                uv2pt[fresh] = n_uv2pt[fresh] + len(pts)
-                pts, nrm, clr = np.vstack([pts, n_pts]), np.vstack([nrm, n_nrm]), np.vstack([clr, n_clr])
-                nmerges = np.hstack([nmerges, n_mrg])
-                occurences = np.hstack([occurences, np.ones(len(n_pts), np.uint32)])
-            if self.save_lookups:
-                self._save_uv2pt(uv2pt, name)
-        return pts, nrm, clr, nmerges, occurences
+        """Fuse + down-sample the frames into one sparse cloud (reference :212-324) -> (points, normals, colours float64 [M,3],
+        nmerges int64 [M], occurences uint32 [M]) as NumPy arrays; per-frame ``uv2pt`` lookups (NumPy int32 [h*w]) are saved when
+        requested.  The loop of ``fuse_device`` with NumPy in and out: like the reference, it consumes the ``valid`` masks of NumPy
+        frames in place (written through ``valid.reshape(h, w)`` after every fused frame)."""
+        with _DeviceFusion.on_stream('Fusion.fuse', self.h, self.w, self.pcdimg, self.pt2u, self.pt2v) as df:
+            out = tuple(t.cpu().numpy() for t in df.run(self, radius, angle, stride, max_depth, skip, verbose, host_io=True))
+        if not len(out[0]):                                                   # no valid pixel anywhere: patch_downsample's empty arrays
+            return np.array([]), np.array([]), np.array([]), np.array([]), np.ones(0, np.uint32)
+        return out
 
     def fuse_device(self, radius=0.05, angle=10, stride=None, max_depth=10, skip=1, verbose=False):
-        """``fuse`` with the cloud and the lookups resident on the GPU -> (points, normals, colours float64 [M,3], nmerges int64 [M],
-        occurences uint32 [M]) as torch tensors on the context's device, bit-identical to what ``fuse`` returns on the same frames
-        under the same seeded global NumPy generator (lookups and the generator's final state included).
+        """``fuse`` with the cloud and the lookups left on the GPU -> (points, normals, colours float64 [M,3], nmerges int64 [M],
+        occurences uint32 [M]) as torch tensors on the context's device, the bits ``fuse`` returns on the same frames under the same
+        seeded global NumPy generator (lookups and the generator's final state included).
 
         Frames: ``self.frames[i]`` may hold NumPy arrays (uploaded once per frame through a pinned staging buffer) or torch device
         tensors (points / normals / colours float64 [h*w,3] contiguous, valid bool or uint8 [h*w]), used in place.  The frame's
-        ``valid`` is copied into a free-pixel buffer of this call and never written; ``fuse`` instead consumes the frame's mask in
-        place.  Lookups: ``lookup_dir`` gets the same .npy bytes as ``fuse`` writes; ``lookup_sink(name, uv2pt)`` gets a fresh int32
-        device tensor [h*w] per frame (what ``f3d_vote_uv2pt_batch_dev`` consumes).
+        ``valid`` is copied into a free-pixel buffer of this call and never written; ``fuse`` instead consumes the masks of NumPy
+        frames in place.  Lookups: ``lookup_dir`` gets the same .npy bytes as ``fuse`` writes; ``lookup_sink(name, uv2pt)`` gets a
+        fresh int32 device tensor [h*w] per frame (what ``f3d_vote_uv2pt_batch_dev`` consumes).
 
         Work goes on the caller's current torch stream (a side stream ordered behind it when that is the null stream); the caller's
         stream waits for it before this returns.  Per frame the host still sees: the shuffle (drawn on the host from the global
         generator, h*w int64 uploaded, drawn while the GPU matches); two small readbacks (hits / valid pixels / cloud rows after the
-        projection, free pixels / sequential flag after the matching); the per-round counter of the seed resolution; the frame upload
-        for NumPy frames; the lookups when written to disk.  Nothing per seed or per pixel comes back, except on the two host paths
-        counted in ``self.fuse_device_stats``: frames patch_downsample hands to its sequential loop ('sequential_frames'), and rows
-        normalised on the host when this process's BLAS dot matches neither kernel order ('host_normalised')."""
-        ctx = f3d.default_context()
-        import torch
-        if not torch.cuda.is_available():
-            raise f3d.F3DUnavailable('Fusion.fuse_device needs a HIP device; there is no CPU fallback')
-        dev = torch.device('cuda', ctx.device)
-        caller = torch.cuda.current_stream(dev)
-        work = caller
-        if caller.cuda_stream == 0:                                           # never hand the null stream to the library
-            work = torch.cuda.Stream(dev)
-            work.wait_stream(caller)
-        try:
-            with torch.cuda.device(dev), torch.cuda.stream(work):
-                out = _DeviceFusion(self, ctx, torch, dev, work, caller).run(radius, angle, stride, max_depth, skip, verbose)
-        finally:
-            if work is not caller:
-                caller.wait_stream(work)
-        if work is not caller:
-            for t in out:
-                t.record_stream(caller)
+        projection, free pixels / sequential flag after the matching); for NumPy frames the frame upload and the free mask, on which
+        the host takes patch_downsample's own test for the sequential loop; the per-round counter of the seed resolution; the
+        lookups when written to disk.  Nothing per seed comes back, except on the two host paths counted in
+        ``self.fuse_device_stats`` (``fuse`` fills it too): frames patch_downsample hands to its sequential loop
+        ('sequential_frames'), and rows normalised on the host when this process's BLAS dot matches neither kernel order
+        ('host_normalised')."""
+        with _DeviceFusion.on_stream('Fusion.fuse_device', self.h, self.w, self.pcdimg, self.pt2u, self.pt2v) as df:
+            out = df.run(self, radius, angle, stride, max_depth, skip, verbose)
+            if df.stream is not df.caller:
+                for t in out:
+                    t.record_stream(df.caller)
         return out
-
-    def _save_uv2pt(self, uv2pt, frame_name):
-        if self.uv2pt_dir is not None:
-            np.save(Path(self.uv2pt_dir) / f'{frame_name}.npy', uv2pt)
-        if self._lookup_sink is not None:
-            self._lookup_sink(frame_name, uv2pt)
 
     @staticmethod
     def filter(values, threshold, data=None, less_than=False):
@@ -445,15 +368,16 @@ class Fusion:
 
 
 class _DeviceFusion:
-    """One call of Fusion.fuse_device: the resident cloud (capacity doubling), the per-frame buffers and the frame loop."""
+    """The frame loop of Fusion.fuse / fuse_device and the down-sampling step of Fusion.patch_downsample: the resident cloud
+    (capacity doubling), the per-frame buffers and the steps, for frames of h x w pixels."""
 
-    def __init__(self, fu, ctx, torch, dev, stream, caller):
-        self.fu, self.ctx, self.torch, self.dev, self.stream, self.sh = fu, ctx, torch, dev, stream, stream.cuda_stream
-        self.caller = caller
-        self.h, self.w, self.npx = fu.h, fu.w, fu.npts
+    def __init__(self, h, w, pcdimg, pt2u, pt2v, ctx, torch, dev, stream, caller):
+        self.ctx, self.torch, self.dev, self.stream, self.sh, self.caller = ctx, torch, dev, stream, stream.cuda_stream, caller
+        self.h, self.w, self.npx = h, w, h * w
+        self.pcdimg, self.pt2u, self.pt2v = pcdimg, pt2u, pt2v
         self.mode = _norm_mode()
-        self.stats = fu.fuse_device_stats = {'frames': 0, 'sequential_frames': 0, 'host_normalised': 0, 'rounds': 0,
-                                             'shuffle_s': 0.0, 'draws_undone': 0, 'capacity_growths': 0}
+        self.stats = {'frames': 0, 'sequential_frames': 0, 'host_normalised': 0, 'rounds': 0, 'shuffle_s': 0.0, 'draws_undone': 0,
+                      'capacity_growths': 0}
         T, n = torch, self.npx
         self.cap = 0
         self.count_dev = T.zeros(1, dtype=T.int64, device=dev)
@@ -465,9 +389,31 @@ class _DeviceFusion:
         self.px_counts = T.empty(n, dtype=T.int32, device=dev)
         self.stats_dev = T.zeros(3, dtype=T.int64, device=dev)
         self.check_dev = T.zeros(2, dtype=T.int64, device=dev)
-        self.stage = [T.empty((n, 3), dtype=T.float64).pin_memory() for _ in range(3)] + [T.empty(n, dtype=T.uint8).pin_memory()]
-        self.order_stage = T.empty(n, dtype=T.int64).pin_memory()
+        self.stage = [T.empty((n, 3), dtype=T.float64, pin_memory=True) for _ in range(3)] + [T.empty(n, dtype=T.uint8, pin_memory=True)]
+        self.order_stage = T.empty(n, dtype=T.int64, pin_memory=True)
         self.frame_buf = [T.empty((n, 3), dtype=T.float64, device=dev) for _ in range(3)] + [T.empty(n, dtype=T.uint8, device=dev)]
+
+    @classmethod
+    @contextlib.contextmanager
+    def on_stream(cls, what, h, w, pcdimg, pt2u, pt2v):
+        """An instance working on the caller's current torch stream, or on a side stream ordered behind it when that is the null
+        stream (never handed to the library); the caller's stream waits for the work when the block ends."""
+        ctx = f3d.default_context()
+        import torch
+        if not torch.cuda.is_available():
+            raise f3d.F3DUnavailable(f'{what} needs a HIP device; there is no CPU fallback')
+        dev = torch.device('cuda', ctx.device)
+        caller = torch.cuda.current_stream(dev)
+        work = caller
+        if caller.cuda_stream == 0:
+            work = torch.cuda.Stream(dev)
+            work.wait_stream(caller)
+        try:
+            with torch.cuda.device(dev), torch.cuda.stream(work):
+                yield cls(h, w, pcdimg, pt2u, pt2v, ctx, torch, dev, work, caller)
+        finally:
+            if work is not caller:
+                caller.wait_stream(work)
 
     # ---------------------------------------------------------------- storage
     def reserve(self, rows):
@@ -496,10 +442,11 @@ class _DeviceFusion:
         return tuple(t.data_ptr() for t in self.cloud + [self.occ])
 
     # ---------------------------------------------------------------- frames
-    def frame(self, j):
-        """(name, points, normals, colours, valid uint8) on the device, plus the host arrays of a NumPy frame (else None)."""
+    def frame(self, fetched):
+        """A fetched frame (name, points, normals, colours, valid) -> (name, points, normals, colours, valid uint8) on the device, plus
+        the host arrays of a NumPy frame (else None)."""
         T = self.torch
-        name, pts, nrm, clr, valid = self.fu.frames[j]
+        name, pts, nrm, clr, valid = fetched
         if isinstance(pts, T.Tensor):
             for t in (pts, nrm, clr):
                 if t.device != self.dev or t.dtype != T.float64 or tuple(t.shape) != (self.npx, 3) or not t.is_contiguous():
@@ -523,6 +470,12 @@ class _DeviceFusion:
         self.stats['shuffle_s'] += time.perf_counter() - t0
         return order
 
+    def consume(self, mask):
+        """Pixels of the NumPy `mask` that the free buffer no longer holds are set to False, written through mask.reshape(h, w):
+        how the reference consumes a frame's mask in place."""
+        mask = mask.reshape(self.h, self.w)
+        mask[(mask != 0) & (self.free.cpu().numpy() == 0).reshape(self.h, self.w)] = False
+
     # ---------------------------------------------------------------- steps
     def host_normalise(self, rows):
         """Normals of the given cloud rows (device int64 tensor) normalised with _row_norms on the host."""
@@ -543,10 +496,9 @@ class _DeviceFusion:
             if host is None:
                 host = [dp.cpu().numpy(), dn.cpu().numpy(), dc.cpu().numpy()]
             free = self.free.cpu().numpy().astype(bool).reshape(h, w)
-            fu = self.fu
             with np.errstate(all='ignore'):
                 n_pts, n_nrm, n_clr, n_uv, n_mrg = Fusion._patch_downsample_sequential(
-                    order, host[0], host[1], host[2], h, w, half, radius, min_cosine, fu.pcdimg, fu.pt2u, fu.pt2v, free)
+                    order, host[0], host[1], host[2], h, w, half, radius, min_cosine, self.pcdimg, self.pt2u, self.pt2v, free)
             k = len(n_mrg)
             if k:
                 for buf, rows in zip(self.cloud[:3], (n_pts, n_nrm, n_clr)):
@@ -572,46 +524,70 @@ class _DeviceFusion:
             return new
         return count + nfree
 
-    def save(self, uv2pt, name):
-        fu = self.fu
+    def finish(self, fu, name, uv2pt, mask, host_io):
+        """A fused frame's end: ``fuse`` consumes the NumPy mask the free buffer stands for, then the lookup goes to fu's lookup_dir /
+        lookup_sink (a NumPy array for ``fuse``, the device tensor for ``fuse_device``)."""
+        self.stats['frames'] += 1
+        if mask is not None:
+            self.consume(mask)
+        if not fu.save_lookups:
+            return
+        host = uv2pt.cpu().numpy() if host_io or fu.uv2pt_dir is not None else None
         if fu.uv2pt_dir is not None:
-            np.save(Path(fu.uv2pt_dir) / f'{name}.npy', uv2pt.cpu().numpy())
+            np.save(Path(fu.uv2pt_dir) / f'{name}.npy', host)
         if fu._lookup_sink is not None:
-            if self.stream is not self.caller:
+            if not host_io and self.stream is not self.caller:
                 uv2pt.record_stream(self.caller)
-            fu._lookup_sink(name, uv2pt)
+            fu._lookup_sink(name, host if host_io else uv2pt)
 
     def check(self, frame, radius, min_cosine):
-        """-> (free pixels, sequential flag) of the current free buffer against the frame (one readback)."""
-        _, dp, dn, _, _, _ = frame
+        """-> (free pixels, sequential flag) of the current free buffer against the frame (one readback).  A NumPy frame's flag is
+        patch_downsample's own test, taken on the host: k_fu_check adds the normal's squared length in another order than np.einsum,
+        and a normal whose squared length lies within an ulp of min_cosine can fall on the other side."""
+        _, dp, dn, _, _, host = frame
         self.ctx.fusion_frame_check_dev(self.free.data_ptr(), dp.data_ptr(), dn.data_ptr(), self.npx, radius, min_cosine,
                                         self.check_dev.data_ptr(), self.sh)
-        return self.check_dev
+        nfree, fallback = self.check_dev.tolist()
+        if host is not None and nfree:
+            free = np.flatnonzero(self.free.cpu().numpy())
+            fallback = not (radius > 0) or _unusable(host[0][free], host[1][free], min_cosine).any()
+        return nfree, fallback
+
+    def add_free(self, frame, half, radius, min_cosine, count, uv2pt, undo):
+        """The frame's free pixels down-sampled onto the cloud at row `count` -> the new row count (or a bound).  The shuffle is drawn
+        while the GPU matches; with `undo` it is taken back when no pixel is free (the reference then calls no patch_downsample)."""
+        state = np.random.get_state()
+        order = self.draw()
+        nfree, fallback = self.check(frame, radius, min_cosine)
+        if nfree or not undo:
+            return self.downsample(order, frame, half, radius, min_cosine, fallback, nfree, count, uv2pt)
+        np.random.set_state(state)
+        self.stats['draws_undone'] += 1
+        return count
 
     # ---------------------------------------------------------------- the loop of Fusion.fuse
-    def run(self, radius, angle, stride, max_depth, skip, verbose):
-        T, ctx, sh, fu, npx = self.torch, self.ctx, self.sh, self.fu, self.npx
-        fu.ds_radius, fu.ds_angle = radius, angle
+    def run(self, fu, radius, angle, stride, max_depth, skip, verbose, host_io=False):
+        """The frames of `fu` fused into the resident cloud -> (points, normals, colours, nmerges, occurences) device tensors.
+        ``host_io``: lookups go out as NumPy arrays and the masks of NumPy frames are consumed in place, as ``fuse`` does."""
+        T, ctx, sh, npx = self.torch, self.ctx, self.sh, self.npx
+        fu.ds_radius, fu.ds_angle, fu.fuse_device_stats = radius, angle, self.stats
         stride = max(10, int(radius * 200)) if stride is None else stride
         half, min_cosine = stride // 2, np.cos(np.deg2rad(angle))
         for first in range(0, fu.nframes):                                  # first frame with any valid pixel seeds the cloud
-            valid = fu.frames[first][4]
-            if bool(valid.any()):
+            fetched = fu.frames[first]
+            if bool(fetched[4].any()):
                 break
         self.reserve(npx)
-        frame = self.frame(first)
+        frame = self.frame(fetched)
+        mask = fetched[4] if host_io and frame[5] is not None else None   # the NumPy mask the free buffer stands for
         self.free.copy_(frame[4])
-        check = self.check(frame, radius, min_cosine)
-        order = self.draw()
-        nfree, fallback = check.tolist()
         uv2pt = T.full((npx,), -1, dtype=T.int32, device=self.dev)
-        count_bound = self.downsample(order, frame, half, radius, min_cosine, fallback, nfree, 0, uv2pt)
-        self.stats['frames'] += 1
-        if fu.save_lookups:
-            self.save(uv2pt, frame[0])
+        count_bound = self.add_free(frame, half, radius, min_cosine, 0, uv2pt, undo=False)
+        self.finish(fu, frame[0], uv2pt, mask, host_io)
         have_free, prev_hits = False, npx
         for j in range(first + 1, fu.nframes, skip):
-            frame = self.frame(j)
+            fetched = fu.frames[j]
+            frame = self.frame(fetched)
             name, dp, dn, dc, dv, _ = frame
             p, n, c, m, o = self.cloud_ptrs()                               # rows < count_bound <= capacity
             ctx.project_view_dev(p, f3d.F64, count_bound, fu._frame_view(j, max_depth), self.uv_all.data_ptr(), self.inside.data_ptr(), sh)
@@ -619,17 +595,17 @@ class _DeviceFusion:
                                 self.ids.data_ptr(), self.uv.data_ptr(), self.hit_pts.data_ptr(), self.hit_nrm.data_ptr(),
                                 self.stats_dev.data_ptr(), sh)
             hits, nvalid, count = self.stats_dev.tolist()
-            count_bound = count
             if verbose:
                 print(f'fusing frame: {j + 1}, total points = {count}, previous intersections = {prev_hits}')
+            count_bound = count
             if not nvalid:
                 continue
             prev_hits = hits
-            self.stats['frames'] += 1
             uv2pt = T.empty(npx, dtype=T.int32, device=self.dev)
             if hits:
                 self.free.copy_(dv)                                         # the frame's mask, copied: the caller's tensors stay as they are
                 have_free = True
+                mask = fetched[4] if host_io and frame[5] is not None else None
                 ctx.patch_match_dev(self.uv.data_ptr(), hits, self.h, self.w, half, radius, min_cosine, self.hit_pts.data_ptr(),
                                     self.hit_nrm.data_ptr(), dp.data_ptr(), dn.data_ptr(), dc.data_ptr(), self.free.data_ptr(),
                                     self.owner.data_ptr(), self.sums.data_ptr(), self.counts.data_ptr(), sh)
@@ -640,20 +616,11 @@ class _DeviceFusion:
                 ctx.fusion_lookup_dev(self.owner.data_ptr(), self.ids.data_ptr(), npx, uv2pt.data_ptr(), self.free.data_ptr(), sh)
             else:
                 uv2pt.fill_(-1)
-                if not have_free:                                          # what `fuse` meets here: its `free` was never assigned
+                if not have_free:                                          # the reference's `free` was never assigned
                     raise UnboundLocalError("local variable 'free' referenced before assignment (the first fused frame has no hits)")
-            check = self.check(frame, radius, min_cosine)
-            state = np.random.get_state()                                  # draw while the GPU matches; undone if the frame needs none
-            order = self.draw()
-            nfree, fallback = check.tolist()
-            if nfree:
-                # fuse calls patch_downsample with 2 * stride, whose half window is then (2 * stride) // 2
-                count_bound = self.downsample(order, frame, (2 * stride) // 2, radius, min_cosine, fallback, nfree, count, uv2pt)
-            else:
-                np.random.set_state(state)
-                self.stats['draws_undone'] += 1
-            if fu.save_lookups:
-                self.save(uv2pt, name)
+            # the reference calls patch_downsample with 2 * stride, whose half window is then (2 * stride) // 2
+            count_bound = self.add_free(frame, (2 * stride) // 2, radius, min_cosine, count, uv2pt, undo=True)
+            self.finish(fu, name, uv2pt, mask, host_io)
         total = int(self.count_dev.item())
         pts, nrm, clr, nmerges = (t[:total] for t in self.cloud[:4])
         return pts, nrm, clr, nmerges, self.occ[:total].view(T.uint32)

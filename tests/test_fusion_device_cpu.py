@@ -1,4 +1,4 @@
-"""CPU-side checks of Fusion.fuse_device: the probe of the host's dot order, and no CPU fallback without a device."""
+"""CPU-side checks of Fusion.fuse / fuse_device: the probe of the host's dot order, and no CPU fallback without a device."""
 import numpy as np
 import pytest
 
@@ -47,3 +47,14 @@ def test_fuse_device_has_no_cpu_fallback():
     fu = fusion.Fusion.from_frames(K, 8, 8, q, t, frames)
     with pytest.raises(f3d.F3DUnavailable):
         fu.fuse_device()
+
+
+def test_fuse_has_no_cpu_fallback():
+    import torch
+    if torch.cuda.is_available():
+        pytest.skip('a HIP device is present')
+    from f3d import synth
+    K, q, t, frames = synth.depth_sequence(8, 8, 2)
+    fu = fusion.Fusion.from_frames(K, 8, 8, q, t, frames)
+    with pytest.raises(f3d.F3DUnavailable):
+        fu.fuse()

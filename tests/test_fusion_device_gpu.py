@@ -1,5 +1,10 @@
-"""Fusion.fuse_device: the device-resident fusion equals the host drop-in Fusion.fuse bit for bit -- cloud, lookups and the state
-of the global NumPy generator -- on the reference golden and on synthetic sequences that walk every quirk of the host path."""
+"""Fusion.fuse and Fusion.fuse_device (one frame loop: NumPy in and out, or the cloud left on the device) against the literal oracle
+O.fuse bit for bit -- cloud, lookups in order, the state of the global NumPy generator and, for fuse, the consumed masks -- on the
+reference golden and on synthetic sequences that walk every quirk of the reference's loop.  The oracle is pinned to the reference's
+own runs by tests/test_fusion_oracle_cpu.py."""
+import contextlib
+import warnings
+
 import numpy as np
 import pytest
 
@@ -7,6 +12,7 @@ import f3d
 from f3d import synth
 from Fusion3DSeg import fusion
 from Fusion3DSeg.fusion import Fusion
+from oracle import np_ref as O
 
 pytestmark = pytest.mark.gpu
 
@@ -24,34 +30,53 @@ def _copy(frames):
     return [(n, p.copy(), q.copy(), c.copy(), v.copy()) for n, p, q, c, v in frames]
 
 
-def _run(K, w, h, q, t, frames, params, seed, device, lookup_dir=None):
-    """-> (five outputs as NumPy, {name: lookup}, the generator's next draw, the Fusion object)."""
-    lookups = {}
+@contextlib.contextmanager
+def _quiet():
+    with warnings.catch_warnings(), np.errstate(all='ignore'):
+        warnings.simplefilter('ignore', RuntimeWarning)              # means of empty sets (zero normal / NaN point), as the reference
+        yield
+
+
+def _run(K, w, h, q, t, frames, params, seed, how, lookup_dir=None):
+    """`frames` through O.fuse ('oracle'), fuse ('host') or fuse_device ('device'), used as given (fuse and the oracle consume
+    their masks) -> (five outputs as NumPy, [(name, lookup)] in the order they were handed out, the generator's next draw, the
+    Fusion object)."""
+    lookups = []
+    if how == 'oracle':
+        np.random.seed(seed)
+        with _quiet():
+            *out, lookups = O.fuse(K, w, h, q, t, frames, *params)
+        return out, lookups, np.random.random(), None
 
     def sink(name, lut):
-        if device:
+        if how == 'device':
             assert lut.is_cuda and lut.dtype.is_signed and lut.element_size() == 4 and tuple(lut.shape) == (h * w,)
-            lookups[name] = lut
         else:
-            lookups[name] = np.array(lut, copy=True)
+            assert isinstance(lut, np.ndarray) and lut.dtype == np.int32 and lut.shape == (h * w,)
+        lookups.append((name, lut.clone() if how == 'device' else lut.copy()))
     fu = Fusion.from_frames(K, w, h, q, t, frames, lookup_dir=lookup_dir, lookup_sink=sink)
     np.random.seed(seed)
-    out = fu.fuse_device(*params) if device else fu.fuse(*params)
+    out = fu.fuse_device(*params) if how == 'device' else fu.fuse(*params)
     after = np.random.random()
-    if device:
+    if how == 'device':
         out = [o.cpu().numpy() for o in out]
-        lookups = {k: v.cpu().numpy() for k, v in lookups.items()}
-    return out, lookups, after, fu
+        lookups = [(n, lut.cpu().numpy()) for n, lut in lookups]
+    return list(out), lookups, after, fu
 
 
 def _assert_same(got, want):
     (go, gl, ga, _), (wo, wl, wa, _) = got, want
     for k, (a, b) in enumerate(zip(go, wo)):
         assert _same(a, b), (k, a.dtype, b.dtype, a.shape, b.shape)
-    assert sorted(gl) == sorted(wl)
-    for name in wl:
-        assert _same(gl[name], wl[name]), name
+    assert [n for n, _ in gl] == [n for n, _ in wl]
+    for (name, a), (_, b) in zip(gl, wl):
+        assert _same(a, b), name
     assert ga == wa
+
+
+def _assert_masks(got, want):
+    for (name, *_, a), (_, *_, b) in zip(got, want):
+        assert a.dtype == b.dtype and np.array_equal(a, b), name
 
 
 def test_fuse_device_matches_the_golden(golden, tmp_path):
@@ -62,21 +87,26 @@ def test_fuse_device_matches_the_golden(golden, tmp_path):
     for ci in range(int(g['ncases'])):
         radius, angle, stride, max_depth, skip, seed = g[f'c{ci}_params']
         params = (float(radius), float(angle), None if stride < 0 else int(stride), float(max_depth), int(skip))
-        (pts, nrm, clr, nmerges, occ), lookups, after, _ = _run(g['K'], w, h, g['wxyz'], g['t'], _copy(frames), params, int(seed), True,
-                                                                  tmp_path if ci == 0 else None)
-        assert pts.dtype == nrm.dtype == clr.dtype == np.float64 and nmerges.dtype == np.int64 and occ.dtype == np.uint32
-        assert np.array_equal(nmerges, g[f'c{ci}_nmerges']) and np.array_equal(occ, g[f'c{ci}_occurences']), ci
-        for got, key in ((pts, 'ds_pts'), (nrm, 'ds_norms'), (clr, 'ds_clrs')):
-            assert np.array_equal(got, g[f'c{ci}_{key}']), (ci, key)
-        assert sorted(int(k) for k in lookups) == g[f'c{ci}_uv2pt_names'].tolist()
-        for name, want in zip(g[f'c{ci}_uv2pt_names'], g[f'c{ci}_uv2pt']):
-            assert np.array_equal(lookups[str(name)], want), (ci, name)
-        _, _, host_after, _ = _run(g['K'], w, h, g['wxyz'], g['t'], _copy(frames), params, int(seed), False)
-        assert after == host_after, ci
         if ci == 0:
-            for name, want in zip(g['c0_uv2pt_names'], g['c0_uv2pt']):
-                got = np.load(tmp_path / f'{int(name)}.npy')
-                assert got.dtype == np.int32 and np.array_equal(got, want)
+            for how in ('host', 'device'):
+                (tmp_path / how).mkdir()
+        _, _, oracle_after, _ = _run(g['K'], w, h, g['wxyz'], g['t'], _copy(frames), params, int(seed), 'oracle')
+        for how in ('host', 'device'):
+            (pts, nrm, clr, nmerges, occ), lookups, after, _ = _run(g['K'], w, h, g['wxyz'], g['t'], _copy(frames), params, int(seed), how,
+                                                                    tmp_path / how if ci == 0 else None)
+            assert pts.dtype == nrm.dtype == clr.dtype == np.float64 and nmerges.dtype == np.int64 and occ.dtype == np.uint32
+            assert np.array_equal(nmerges, g[f'c{ci}_nmerges']) and np.array_equal(occ, g[f'c{ci}_occurences']), (ci, how)
+            for got, key in ((pts, 'ds_pts'), (nrm, 'ds_norms'), (clr, 'ds_clrs')):
+                assert np.array_equal(got, g[f'c{ci}_{key}']), (ci, how, key)
+            assert sorted(int(k) for k, _ in lookups) == g[f'c{ci}_uv2pt_names'].tolist()
+            lookups = dict(lookups)
+            for name, want in zip(g[f'c{ci}_uv2pt_names'], g[f'c{ci}_uv2pt']):
+                assert np.array_equal(lookups[str(name)], want), (ci, how, name)
+            assert after == oracle_after, (ci, how)
+            if ci == 0:
+                for name, want in zip(g['c0_uv2pt_names'], g['c0_uv2pt']):
+                    got = np.load(tmp_path / how / f'{int(name)}.npy')
+                    assert got.dtype == np.int32 and np.array_equal(got, want)
 
 
 def _sequence(h=96, w=128, F=24):
@@ -104,15 +134,50 @@ PARAMS = [(0.05, 10, None, 10, 1), (0.05, 10, 6, 10, 2), (0.03, 15, 4, 2.8, 1), 
 def test_fuse_device_equals_fuse_on_a_synthetic_sequence(params):
     K, q, t, frames = _sequence()
     h, w = 96, 128
-    got = _run(K, w, h, q, t, _copy(frames), params, 5, True)
-    want = _run(K, w, h, q, t, _copy(frames), params, 5, False)
+    oracle_frames, host_frames, device_frames = _copy(frames), _copy(frames), _copy(frames)
+    want = _run(K, w, h, q, t, oracle_frames, params, 5, 'oracle')
+    _assert_same(_run(K, w, h, q, t, host_frames, params, 5, 'host'), want)
+    _assert_masks(host_frames, oracle_frames)       # fuse consumes the masks as the reference does
+    assert any(not np.array_equal(a[4], b[4]) for a, b in zip(host_frames, frames))
+    got = _run(K, w, h, q, t, device_frames, params, 5, 'device')
     _assert_same(got, want)
+    _assert_masks(device_frames, frames)            # fuse_device leaves them as they are
     stats = got[3].fuse_device_stats
     if params[2] == 2:                              # a dense cloud: the resident storage doubles on the way
         assert stats['capacity_growths'] >= 1
     if params[4] == 1:                              # frames 10 and 15 are fused: both go down the sequential path
         assert stats['sequential_frames'] >= 2
         assert stats['draws_undone'] >= 1          # a no-hit frame after a fully consumed free mask draws nothing
+
+
+def _split_normal(min_cosine, seed=7):
+    """A normal whose squared length lies above min_cosine added as (x*x + y*y) + z*z and not above it in np.einsum's order."""
+    rng = np.random.default_rng(seed)
+    for _ in range(100000):
+        u = rng.normal(size=3)
+        n = u / np.linalg.norm(u) * np.sqrt(min_cosine) * (1 + rng.integers(-4, 5) * np.finfo(float).eps)
+        if (n[0] * n[0] + n[1] * n[1]) + n[2] * n[2] > min_cosine >= np.einsum('ij,ij->i', n[None], n[None])[0]:
+            return n
+    raise AssertionError('np.einsum adds a squared length as (x*x + y*y) + z*z here')
+
+
+def test_numpy_frames_take_the_sequential_path_on_the_host_test():
+    """The sequential fallback of a NumPy frame is decided as patch_downsample decides it, with np.einsum's dot: a free pixel whose
+    normal accepts itself in one summation order and not in the other sends the frame down the reference's own order of events."""
+    h, w, p = 48, 64, 20 * 64 + 30
+    params = (0.05, 10, None, 10, 1)
+    K, q, t, frames = synth.depth_sequence(h, w, 4, step=0.02, seed=5)
+    plain = _run(K, w, h, q, t, _copy(frames), params, 3, 'device')
+    assert plain[3].fuse_device_stats['sequential_frames'] == 0
+    frames = _copy(frames)
+    frames[0][4].reshape(h, w)[20 - 8:20 + 9, 30 - 8:30 + 9] = False     # alone in its window: the pixel seeds
+    frames[0][4][p] = True
+    frames[0][2][p] = _split_normal(np.cos(np.deg2rad(params[1])))
+    want = _run(K, w, h, q, t, _copy(frames), params, 3, 'oracle')
+    for how in ('host', 'device'):
+        got = _run(K, w, h, q, t, _copy(frames), params, 3, how)
+        _assert_same(got, want)
+        assert got[3].fuse_device_stats['sequential_frames'] == 1, how
 
 
 def test_fuse_device_with_device_tensor_frames():
@@ -122,11 +187,11 @@ def test_fuse_device_with_device_tensor_frames():
     K, q, t, frames = _sequence()
     h, w = 96, 128
     params = PARAMS[0]
-    want = _run(K, w, h, q, t, _copy(frames), params, 9, False)
+    want = _run(K, w, h, q, t, _copy(frames), params, 9, 'oracle')
     as_tensors = [(n, torch.from_numpy(p).to(dev), torch.from_numpy(nn).to(dev), torch.from_numpy(c).to(dev), torch.from_numpy(v).to(dev))
                   for n, p, nn, c, v in _copy(frames)]
-    _assert_same(_run(K, w, h, q, t, as_tensors, params, 9, True), want)
-    assert all(bool(v.any()) == bool(f[4].any()) for (_, _, _, _, v), f in zip(as_tensors, frames))    # masks not consumed
+    _assert_same(_run(K, w, h, q, t, as_tensors, params, 9, 'device'), want)
+    assert all(np.array_equal(v.cpu().numpy(), f[4]) for (_, _, _, _, v), f in zip(as_tensors, frames))    # masks not consumed
     # points unprojected on the device from depth frames (uint16 millimetres), valid as uint8
     F = 10
     rng = np.random.default_rng(4)
@@ -146,9 +211,9 @@ def test_fuse_device_with_device_tensor_frames():
     dev_frames = [(str(j), pts[j], nrm, clr[j], valid[j]) for j in range(F)]
     host_frames = [(str(j), pts[j].cpu().numpy(), nrm.cpu().numpy(), clr[j].cpu().numpy(), valid[j].cpu().numpy().astype(bool))
                    for j in range(F)]
-    want = _run(K, w, h, qd, td, _copy(host_frames), params, 2, False)
-    _assert_same(_run(K, w, h, qd, td, dev_frames, params, 2, True), want)
-    _assert_same(_run(K, w, h, qd, td, _copy(host_frames), params, 2, True), want)
+    want = _run(K, w, h, qd, td, _copy(host_frames), params, 2, 'oracle')
+    _assert_same(_run(K, w, h, qd, td, dev_frames, params, 2, 'device'), want)
+    _assert_same(_run(K, w, h, qd, td, _copy(host_frames), params, 2, 'device'), want)
 
 
 def test_fused_cloud_to_votes_on_the_device():
@@ -158,7 +223,8 @@ def test_fused_cloud_to_votes_on_the_device():
     ctx = f3d.default_context()
     K, q, t, frames = _sequence()
     h, w = 96, 128
-    host_out, host_luts, _, _ = _run(K, w, h, q, t, _copy(frames), PARAMS[0], 13, False)
+    host_out, host_luts, _, _ = _run(K, w, h, q, t, _copy(frames), PARAMS[0], 13, 'host')
+    host_luts = dict(host_luts)
     dev_luts = {}
     fu = Fusion.from_frames(K, w, h, q, t, _copy(frames), lookup_sink=lambda name, lut: dev_luts.__setitem__(name, lut))
     np.random.seed(13)
@@ -211,20 +277,24 @@ def test_fuse_device_without_a_matching_dot_order_normalises_on_the_host(golden,
     radius, angle, stride, max_depth, skip, seed = g['c0_params']
     params = (float(radius), float(angle), None if stride < 0 else int(stride), float(max_depth), int(skip))
     monkeypatch.setattr(fusion, '_norm_mode', lambda: f3d.NORM_HOST)
-    (pts, nrm, clr, nmerges, occ), _, _, fu = _run(g['K'], w, h, g['wxyz'], g['t'], _copy(frames), params, int(seed), True)
-    assert np.array_equal(pts, g['c0_ds_pts']) and np.array_equal(nrm, g['c0_ds_norms']) and np.array_equal(clr, g['c0_ds_clrs'])
-    assert np.array_equal(nmerges, g['c0_nmerges']) and np.array_equal(occ, g['c0_occurences'])
-    assert fu.fuse_device_stats['host_normalised'] > 0
+    for how in ('host', 'device'):
+        (pts, nrm, clr, nmerges, occ), _, _, fu = _run(g['K'], w, h, g['wxyz'], g['t'], _copy(frames), params, int(seed), how)
+        assert np.array_equal(pts, g['c0_ds_pts']) and np.array_equal(nrm, g['c0_ds_norms']) and np.array_equal(clr, g['c0_ds_clrs'])
+        assert np.array_equal(nmerges, g['c0_nmerges']) and np.array_equal(occ, g['c0_occurences'])
+        assert fu.fuse_device_stats['host_normalised'] > 0, how
 
 
 def test_first_fused_frame_without_hits_raises_like_fuse():
     K, q, t, frames = synth.depth_sequence(48, 64, 4, step=0.02)
     params = (0.05, 10, None, 1.0, 1)                      # the far plane before the wall: no frame sees the cloud
-    with pytest.raises(Exception) as host:
-        _run(K, 64, 48, q, t, _copy(frames), params, 1, False)
-    with pytest.raises(Exception) as device:
-        _run(K, 64, 48, q, t, _copy(frames), params, 1, True)
-    assert type(device.value) is type(host.value)
+    oracle_frames, host_frames = _copy(frames), _copy(frames)
+    with pytest.raises(UnboundLocalError):
+        _run(K, 64, 48, q, t, oracle_frames, params, 1, 'oracle')
+    for how, used in (('host', host_frames), ('device', _copy(frames))):
+        with pytest.raises(UnboundLocalError):
+            _run(K, 64, 48, q, t, used, params, 1, how)
+    _assert_masks(host_frames, oracle_frames)             # the first frame's mask is consumed before the error
+    assert not np.array_equal(host_frames[0][4], frames[0][4])
 
 
 def test_fuse_device_on_the_default_and_on_a_side_stream():
@@ -232,10 +302,11 @@ def test_fuse_device_on_the_default_and_on_a_side_stream():
     dev = torch.device('cuda', 0)
     K, q, t, frames = _sequence()
     params = PARAMS[0]
-    want = _run(K, 128, 96, q, t, _copy(frames), params, 21, False)
+    want = _run(K, 128, 96, q, t, _copy(frames), params, 21, 'oracle')
     assert torch.cuda.current_stream(dev).cuda_stream == 0
-    _assert_same(_run(K, 128, 96, q, t, _copy(frames), params, 21, True), want)
+    _assert_same(_run(K, 128, 96, q, t, _copy(frames), params, 21, 'device'), want)
     side = torch.cuda.Stream(dev)
     with torch.cuda.stream(side):
-        got = _run(K, 128, 96, q, t, _copy(frames), params, 21, True)
-    _assert_same(got, want)
+        got = [_run(K, 128, 96, q, t, _copy(frames), params, 21, how) for how in ('device', 'host')]
+    for g in got:
+        _assert_same(g, want)
