@@ -25,7 +25,8 @@ namespace {
 enum { SLOT_XYZ = 0, SLOT_OUT0, SLOT_OUT1, SLOT_VIEWS, SLOT_MASKS, SLOT_AUX0, SLOT_AUX1, SLOT_SORT_PERM, SLOT_SORT_SCRATCH,
        SLOT_TILED_MASKS, SLOT_TODO, SLOT_GRAPH, SLOT_GRAPH_BBOX, SLOT_PATCH,
        SLOT_GRP_ORDER, SLOT_GRP_KEYS, SLOT_GRP_STARTS, SLOT_GRP_SCRATCH, SLOT_OBB_TABLE, SLOT_OBB_FACETS, SLOT_OBB_CAND, SLOT_FUSE_TABLES, SLOT_FUSE_CARRY, SLOT_FUSE_XYZ, SLOT_FUSION, SLOT_PATCH_STATUS, SLOT_NRM, SLOT_NRM_CAMS,
-       SLOT_QRY, SLOT_QRY_IN, SLOT_QRY_OFFS, SLOT_COUNT };
+       SLOT_QRY, SLOT_QRY_IN, SLOT_QRY_OFFS,
+       SLOT_FLOOD, SLOT_COLOR, SLOT_CVS_INST, SLOT_CVS_ORDER, SLOT_CVS_COFFS, SLOT_CVS_FLAGS, SLOT_CVS_SEEDS, SLOT_CVS_STATS, SLOT_COUNT };
 
 thread_local char g_create_err[512] = "";
 
@@ -154,6 +155,10 @@ int take_error(f3d_ctx* ctx, hipStream_t s, int mask = F3D_DEVERR_ALL) {
             return fail(ctx, F3D_ERR_INDEX, "vote_uv2pt: point index or mask label out of bounds (the reference raises IndexError at voting.py:98)");
         if (e & F3D_DEVERR_CC)
             return fail(ctx, F3D_ERR_INDEX, "components_same_class: neighbour index out of bounds");
+        if (e & F3D_DEVERR_FLOOD)
+            return fail(ctx, F3D_ERR_INDEX, "flood_order: neighbour index out of bounds");
+        if (e & F3D_DEVERR_COLOR)
+            return fail(ctx, F3D_ERR_INDEX, "color_segment: seed or neighbour index out of bounds");
     }
     return F3D_OK;
 }
@@ -1153,6 +1158,127 @@ int f3d_components_same_class(f3d_ctx* ctx, const int64_t* classes, int64_t n, c
     int64_t* droot = st.out(SLOT_OUT0, root, (size_t)n * 8);
     if (!st.rc) st.rc = f3d_components_same_class_dev(ctx, dcls, n, doffs, dnb, dpar, droot, ctx->stream);
     return st.finish(F3D_DEVERR_CC);
+}
+
+// ---------------------------------------------------------------------------------------------
+// CVSegmentation: ordered same-class flood and colour growing
+// ---------------------------------------------------------------------------------------------
+#define F3D_CVSEG_RESERVED_LIST 4096         // instance classes / seeds that f3d_ctx_reserve_cvseg makes room for
+
+int f3d_ctx_reserve_cvseg(f3d_ctx* ctx, int64_t n) {
+    int rc = enter(ctx); if (rc) return rc;
+    if (n < 0 || n > 0x7fffffffLL) return fail(ctx, F3D_ERR_INVALID, "ctx_reserve_cvseg: bad arguments");
+    const int strict = ctx->strict;
+    ctx->strict = 0;
+    void* p;
+    rc = ensure(ctx, SLOT_FLOOD, f3d_flood_scratch_bytes(n), &p);
+    if (!rc) rc = ensure(ctx, SLOT_COLOR, f3d_color_scratch_bytes(n), &p);
+    if (!rc) rc = ensure(ctx, SLOT_CVS_INST, F3D_CVSEG_RESERVED_LIST * 8, &p);
+    if (!rc) rc = ensure(ctx, SLOT_CVS_STATS, 16, &p);
+    ctx->strict = strict;
+    return rc;
+}
+
+int f3d_flood_order_dev(f3d_ctx* ctx, const int64_t* classes, int64_t n, const int64_t* offsets, const int32_t* nbrs,
+                        const int64_t* inst, int ninst, int64_t* root, int64_t* order, int64_t* coffs, uint8_t* flags,
+                        int64_t stats[4], void* stream) {
+    int rc = enter(ctx); if (rc) return rc;
+    if (!stats || n < 0 || n > 0x7fffffffLL || ninst < 0 || (ninst > 0 && !inst) ||
+        (n > 0 && (!classes || !offsets || !root || !order || !coffs || !flags)))
+        return fail(ctx, F3D_ERR_INVALID, "flood_order: bad arguments (n < 2^31)");
+    for (int q = 0; q < 4; ++q) stats[q] = 0;
+    if (n == 0) return F3D_OK;
+    hipStream_t s = pick(ctx, stream);
+    void *scratch, *dinst;
+    if ((rc = ensure(ctx, SLOT_FLOOD, f3d_flood_scratch_bytes(n), &scratch))) return rc;
+    if ((rc = ensure(ctx, SLOT_CVS_INST, (size_t)(ninst > 0 ? ninst : 1) * 8, &dinst))) return rc;
+    if (ninst > 0) F3D_HIP(ctx, hipMemcpyAsync(dinst, inst, (size_t)ninst * 8, hipMemcpyHostToDevice, s));   // the launch synchronises
+    F3D_HIP(ctx, f3d_launch_flood_order(classes, n, offsets, nbrs, (const int64_t*)dinst, ninst, root, order, coffs, flags, scratch,
+                                        ctx->dev_err, stats, s));
+    return take_error(ctx, s, F3D_DEVERR_FLOOD);
+}
+
+int f3d_flood_order(f3d_ctx* ctx, const int64_t* classes, int64_t n, const int64_t* offsets, const int32_t* nbrs,
+                    const int64_t* inst, int ninst, int64_t* root, int64_t* order, int64_t* coffs, uint8_t* flags, int64_t stats[4]) {
+    int rc = enter(ctx); if (rc) return rc;
+    if (!stats || n < 0 || (n > 0 && (!classes || !offsets || !root || !order || !coffs || !flags)))
+        return fail(ctx, F3D_ERR_INVALID, "flood_order: bad arguments");
+    for (int q = 0; q < 4; ++q) stats[q] = 0;
+    if (n == 0) { coffs[0] = 0; return F3D_OK; }
+    const int64_t e = offsets[n];
+    if (e < 0 || (e > 0 && !nbrs)) return fail(ctx, F3D_ERR_INVALID, "flood_order: bad adjacency");
+    staging st(ctx);
+    const int64_t* dcls = st.in(SLOT_XYZ, classes, (size_t)n * 8);
+    const int64_t* doffs = st.in(SLOT_OUT1, offsets, (size_t)(n + 1) * 8);
+    const int32_t* dnb = st.in(SLOT_MASKS, nbrs, (size_t)e * 4);
+    int64_t* droot = st.out(SLOT_OUT0, root, (size_t)n * 8);
+    int64_t* dorder = st.out(SLOT_CVS_ORDER, order, (size_t)n * 8);
+    int64_t* dcoffs = st.out(SLOT_CVS_COFFS, coffs, (size_t)(n + 1) * 8);
+    uint8_t* dflags = st.out(SLOT_CVS_FLAGS, flags, (size_t)n);
+    if (!st.rc) st.rc = f3d_flood_order_dev(ctx, dcls, n, doffs, dnb, inst, ninst, droot, dorder, dcoffs, dflags, stats, ctx->stream);
+    return st.finish();
+}
+
+static int color_args(f3d_ctx* ctx, const double threshold[3], const int64_t* neutral_ids, int nneutral, int max_level, f3d_color_args* a) {
+    if (!threshold || nneutral < 0 || nneutral > F3D_COLOR_MAX_NEUTRAL || (nneutral > 0 && !neutral_ids))
+        return fail(ctx, F3D_ERR_INVALID, "color_segment: bad threshold or neutral ids (at most %d)", F3D_COLOR_MAX_NEUTRAL);
+    for (int c = 0; c < 3; ++c) a->thr[c] = threshold[c];
+    a->max_level = max_level;
+    a->nneutral = nneutral;
+    for (int k = 0; k < F3D_COLOR_MAX_NEUTRAL; ++k) a->neutral[k] = k < nneutral ? neutral_ids[k] : 0;
+    return F3D_OK;
+}
+
+int f3d_color_segment_dev(f3d_ctx* ctx, const void* colors, f3d_dtype dtype, int64_t n, const int64_t* offsets, const int32_t* nbrs,
+                          int64_t* ids, const int64_t* seeds, int64_t nseeds, const double threshold[3], const int64_t* neutral_ids,
+                          int nneutral, int max_level, int64_t* accepted_dev, void* stream) {
+    int rc = enter(ctx); if (rc) return rc;
+    if (n < 0 || n > 0x7fffffffLL || nseeds < 0 || (dtype != F3D_F64 && dtype != F3D_F32) ||
+        (n > 0 && nseeds > 0 && (!colors || !offsets || !ids || !seeds)))
+        return fail(ctx, F3D_ERR_INVALID, "color_segment: bad arguments (n < 2^31, float64 or float32 colours)");
+    f3d_color_args a;
+    if ((rc = color_args(ctx, threshold, neutral_ids, nneutral, max_level, &a))) return rc;
+    if (nseeds > 0 && n == 0) return fail(ctx, F3D_ERR_INDEX, "color_segment: seed index out of bounds");
+    if (n == 0 || nseeds == 0) return F3D_OK;
+    hipStream_t s = pick(ctx, stream);
+    void* scratch;
+    if ((rc = ensure(ctx, SLOT_COLOR, f3d_color_scratch_bytes(n), &scratch))) return rc;
+    if (!accepted_dev) {
+        void* p;
+        if ((rc = ensure(ctx, SLOT_CVS_STATS, 16, &p))) return rc;
+        accepted_dev = (int64_t*)p;
+    }
+    F3D_HIP(ctx, f3d_launch_color_segment(colors, dtype, n, offsets, nbrs, ids, seeds, nseeds, a, scratch, accepted_dev, ctx->dev_err, s));
+    return F3D_OK;
+}
+
+int f3d_color_segment(f3d_ctx* ctx, const void* colors, f3d_dtype dtype, int64_t n, const int64_t* offsets, const int32_t* nbrs,
+                      int64_t* ids, const int64_t* seeds, int64_t nseeds, const double threshold[3], const int64_t* neutral_ids,
+                      int nneutral, int max_level, int64_t* accepted) {
+    int rc = enter(ctx); if (rc) return rc;
+    if (accepted) *accepted = 0;
+    if (n < 0 || nseeds < 0 || (dtype != F3D_F64 && dtype != F3D_F32) || (n > 0 && nseeds > 0 && (!colors || !offsets || !ids || !seeds)))
+        return fail(ctx, F3D_ERR_INVALID, "color_segment: bad arguments (float64 or float32 colours)");
+    f3d_color_args a;
+    if ((rc = color_args(ctx, threshold, neutral_ids, nneutral, max_level, &a))) return rc;
+    if (nseeds > 0 && n == 0) return fail(ctx, F3D_ERR_INDEX, "color_segment: seed index out of bounds");
+    if (n == 0 || nseeds == 0) return F3D_OK;
+    for (int64_t k = 0; k < nseeds; ++k)
+        if (seeds[k] < 0 || seeds[k] >= n) return fail(ctx, F3D_ERR_INDEX, "color_segment: seed index %lld out of bounds", (long long)seeds[k]);
+    const int64_t e = offsets[n];
+    if (e < 0 || (e > 0 && !nbrs)) return fail(ctx, F3D_ERR_INVALID, "color_segment: bad adjacency");
+    staging st(ctx);
+    const void* dclr = st.in(SLOT_XYZ, (const char*)colors, xyz_bytes(dtype, n));
+    const int64_t* doffs = st.in(SLOT_OUT1, offsets, (size_t)(n + 1) * 8);
+    const int32_t* dnb = st.in(SLOT_MASKS, nbrs, (size_t)e * 4);
+    const int64_t* dseeds = st.in(SLOT_CVS_SEEDS, seeds, (size_t)nseeds * 8);
+    int64_t* dids = st.inout(SLOT_OUT0, ids, (size_t)n * 8);
+    int64_t* dacc = (int64_t*)st.slot(SLOT_CVS_STATS, 16);
+    if (!st.rc) st.rc = hipMemsetAsync(dacc, 0, 8, ctx->stream) == hipSuccess ? F3D_OK : fail(ctx, F3D_ERR_HIP, "color_segment: memset");
+    st.back(accepted, dacc, accepted ? 8 : 0);
+    if (!st.rc) st.rc = f3d_color_segment_dev(ctx, dclr, dtype, n, doffs, dnb, dids, dseeds, nseeds, threshold, neutral_ids, nneutral,
+                                              max_level, dacc, ctx->stream);
+    return st.finish(F3D_DEVERR_COLOR);
 }
 
 // ---------------------------------------------------------------------------------------------

@@ -9,7 +9,9 @@
 #define F3D_DEVERR_FUSE 1                  // project_vote_argmax: a sampled label > nclasses (voting.py:98)
 #define F3D_DEVERR_VOTE 2                  // vote_uv2pt: point index or label out of bounds (voting.py:98)
 #define F3D_DEVERR_CC 4                    // components_same_class: neighbour index out of bounds
-#define F3D_DEVERR_ALL 7
+#define F3D_DEVERR_FLOOD 8                 // flood_order: neighbour index out of bounds
+#define F3D_DEVERR_COLOR 16                // color_segment: neighbour or seed index out of bounds
+#define F3D_DEVERR_ALL 31
 #define F3D_PLANES_PER_LAUNCH 16
 #define F3D_OBB_MAX_BOXES 4096
 #define F3D_SORT_MAX_CELLS 32767            // + 1 overflow cell = 2^15 keys -> 16 key bits sorted
@@ -139,7 +141,27 @@ size_t f3d_sort_scratch_bytes(int64_t n);
 hipError_t f3d_launch_cell_sort(const void* xyz, int dtype, int64_t n, void* sorted_xyz, int32_t* perm, void* scratch, hipStream_t s);
 // same-class connected components (f3d_cc.hip): root[i] = smallest index of i's component; parent = int32 [n] scratch
 hipError_t f3d_launch_components(const int64_t* classes, int64_t n, const int64_t* offs, const int32_t* nbrs, int32_t* parent,
-                                 int64_t* root, int* err, hipStream_t s);
+                                 int64_t* root, int* err, hipStream_t s, int errbit = F3D_DEVERR_CC);
+// ordered same-class flood of CVSegmentation.instance_seperate (f3d_cc.hip): the clusters of the classes inst[0..k) (processing order)
+// concatenated in the reference's pop order.  root [n]; order [n] (first stats[1] used, the rest -1); coffs [n + 1] (first stats[0] + 1
+// used); flags [n] boundary points.  Synchronises the stream (the frontier length is read back every few levels); stats (host) =
+// {clusters, points in clusters, levels, readbacks}.  scratch: f3d_flood_scratch_bytes(n)
+size_t f3d_flood_scratch_bytes(int64_t n);
+hipError_t f3d_launch_flood_order(const int64_t* classes, int64_t n, const int64_t* offs, const int32_t* nbrs, const int64_t* inst, int k,
+                                  int64_t* root, int64_t* order, int64_t* coffs, uint8_t* flags, void* scratch, int* err, int64_t stats[4],
+                                  hipStream_t s);
+// running-mean colour growing of CVSegmentation.color_segment (f3d_color.hip): one workgroup for the whole seed list; ids [n] in/out;
+// seeds device [nseeds]; colors [n, 3] of `dtype`; stats_dev (device int64) += accepted points.  scratch: f3d_color_scratch_bytes(n)
+struct f3d_color_args {
+    double thr[3];
+    int max_level;                         // <= 0: no level limit (the reference's `level == max_level` never holds)
+    int nneutral;
+    int64_t neutral[F3D_COLOR_MAX_NEUTRAL];
+};
+size_t f3d_color_scratch_bytes(int64_t n);
+hipError_t f3d_launch_color_segment(const void* colors, int dtype, int64_t n, const int64_t* offs, const int32_t* nbrs, int64_t* ids,
+                                    const int64_t* seeds, int64_t nseeds, const f3d_color_args& a, void* scratch, int64_t* stats_dev, int* err,
+                                    hipStream_t s);
 // radius graph (f3d_graph.hip): KDTree.query_radius(points, r) as CSR.  bbox partials -> host picks the grid -> count pass
 // (offsets[n + 1], exclusive scan) -> fill pass; `scratch` (f3d_graph_scratch_bytes) carries the grid between the passes
 size_t f3d_graph_bbox_bytes(void);

@@ -130,6 +130,11 @@ def library():
         'f3d_lines_plane_projection': (i32, [vp, vp, vp, i64, vp, vp, vp, vp, vp]),
         'f3d_components_same_class': (i32, [vp, vp, i64, vp, vp, vp]),
         'f3d_components_same_class_dev': (i32, [vp, vp, i64, vp, vp, vp, vp, vp]),
+        'f3d_flood_order': (i32, [vp, vp, i64, vp, vp, vp, i32, vp, vp, vp, vp, vp]),
+        'f3d_flood_order_dev': (i32, [vp, vp, i64, vp, vp, vp, i32, vp, vp, vp, vp, vp, vp]),
+        'f3d_color_segment': (i32, [vp, vp, i32, i64, vp, vp, vp, vp, i64, vp, vp, i32, i32, vp]),
+        'f3d_color_segment_dev': (i32, [vp, vp, i32, i64, vp, vp, vp, vp, i64, vp, vp, i32, i32, vp, vp]),
+        'f3d_ctx_reserve_cvseg': (i32, [vp, i64]),
         'f3d_patch_owner': (i32, [vp, vp, i64, i32, i32, i32, dbl, dbl, vp, vp, vp, vp, vp, vp]),
         'f3d_patch_owner_dev': (i32, [vp, vp, i64, i32, i32, i32, dbl, dbl, vp, vp, vp, vp, vp, vp, vp]),
         'f3d_patch_match': (i32, [vp, vp, i64, i32, i32, i32, dbl, dbl, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
@@ -253,6 +258,16 @@ def _filter(filter_classes):
     return f, len(f)
 
 
+def _flood_stats(stats):
+    return {'clusters': int(stats[0]), 'points': int(stats[1]), 'levels': int(stats[2]), 'readbacks': int(stats[3])}
+
+
+def _threshold3(threshold):
+    """color_segment's threshold as float64 [3]: a scalar is repeated (cv.py:387); comparisons with it happen in float64."""
+    t = np.asarray(threshold, dtype=np.float64)
+    return np.ascontiguousarray(np.broadcast_to(t, (3,)) if t.ndim == 0 else t.reshape(3))
+
+
 class Context:
     """One f3d_ctx (device ordinal, stream, scratch arena).  Not thread-safe."""
 
@@ -288,6 +303,10 @@ class Context:
     def reserve(self, n=0, nviews=0, h=0, w=0):
         """Size the scratch of the fused path / cell sort / uv2pt vote beforehand: later _dev calls do not allocate."""
         self._check(self._lib.f3d_ctx_reserve(self._h, int(n), int(nviews), int(h), int(w)))
+
+    def reserve_cvseg(self, n):
+        """Size the scratch of flood_order / color_segment for clouds of up to n points (strict contexts then do not allocate)."""
+        self._check(self._lib.f3d_ctx_reserve_cvseg(self._h, int(n)))
 
     def set_strict(self, strict=True):
         self._check(self._lib.f3d_ctx_set_strict(self._h, int(bool(strict))))
@@ -521,6 +540,48 @@ class Context:
         self._check(self._lib.f3d_components_same_class(self._h, _ptr(cls), len(cls), _ptr(offs), _ptr(nb), _ptr(root)))
         return root
 
+    def flood_order(self, classes, offsets, neighbours, instance_classes):
+        """Ordered same-class flood of CVSegmentation.instance_seperate (include/f3d.h f3d_flood_order): the clusters of
+        `instance_classes` (processing order), numbered by class rank then ascending seed.  -> (root int64 [n], order int64 [L]
+        (the clusters concatenated in the reference's pop order), coffs int64 [M + 1], boundary flags bool [n], stats dict)."""
+        cls = np.ascontiguousarray(classes, dtype=np.int64)
+        offs = np.ascontiguousarray(offsets, dtype=np.int64)
+        nb = np.ascontiguousarray(neighbours, dtype=np.int32)
+        inst = np.ascontiguousarray(np.asarray(instance_classes).reshape(-1), dtype=np.int64)
+        n = len(cls)
+        if len(offs) != n + 1 or (n and offs[-1] != len(nb)):
+            raise ValueError('offsets must have n+1 entries ending at len(neighbours)')
+        root, order, coffs = np.empty(n, np.int64), np.empty(n, np.int64), np.zeros(n + 1, np.int64)
+        flags, stats = np.zeros(n, np.uint8), np.zeros(4, np.int64)
+        self._check(self._lib.f3d_flood_order(self._h, _ptr(cls), n, _ptr(offs), _ptr(nb), _ptr(inst), len(inst), _ptr(root),
+                                              _ptr(order), _ptr(coffs), _ptr(flags), _ptr(stats)))
+        m, L = int(stats[0]), int(stats[1])
+        return root, order[:L], coffs[:m + 1], flags.view(bool), _flood_stats(stats)
+
+    def color_segment(self, colors, offsets, neighbours, ids, seeds, threshold, neutral_ids=(0,), max_level=10):
+        """Running-mean colour growing of CVSegmentation.color_segment (include/f3d.h f3d_color_segment); `ids` (int64, C-contiguous)
+        is updated in place and returned with the number of accepted points."""
+        clr = np.asarray(colors)
+        if clr.dtype not in (np.float64, np.float32):
+            raise TypeError(f'color_segment: colours must be float64 or float32, got {clr.dtype}')
+        clr = np.ascontiguousarray(clr)
+        n = len(ids)
+        if clr.shape != (n, 3):
+            raise ValueError(f'color_segment: colours must be [{n}, 3], got {clr.shape}')
+        if not (isinstance(ids, np.ndarray) and ids.dtype == np.int64 and ids.flags.c_contiguous):
+            raise TypeError('color_segment: ids must be a C-contiguous int64 array (it is updated in place)')
+        offs = np.ascontiguousarray(offsets, dtype=np.int64)
+        nb = np.ascontiguousarray(neighbours, dtype=np.int32)
+        if len(offs) != n + 1 or (n and offs[-1] != len(nb)):
+            raise ValueError('offsets must have n+1 entries ending at len(neighbours)')
+        sd = np.ascontiguousarray(np.asarray(seeds).reshape(-1), dtype=np.int64)
+        thr = _threshold3(threshold)
+        neu = np.ascontiguousarray(np.asarray(list(neutral_ids)).reshape(-1), dtype=np.int64)
+        acc = np.zeros(1, np.int64)
+        self._check(self._lib.f3d_color_segment(self._h, _ptr(clr), F32 if clr.dtype == np.float32 else F64, n, _ptr(offs), _ptr(nb),
+                                                _ptr(ids), _ptr(sd), len(sd), _ptr(thr), _ptr(neu), len(neu), int(max_level), _ptr(acc)))
+        return ids, int(acc[0])
+
     def patch_owner(self, uv, seed_pts, seed_normals, frame_pts, frame_normals, free, h, w, half, radius, min_cosine):
         """owner int32 [h*w]: for every free depth pixel the first seed of Fusion.fuse's matching loop (fusion.py:269-298)
         that would take it, -1 if none."""
@@ -686,6 +747,24 @@ class Context:
         c = np.zeros(2, np.uint32)
         self._check(self._lib.f3d_debug_fuse_deferred(self._h, stream, _ptr(c)))
         return int(c[0]), int(c[1])
+
+    def flood_order_dev(self, classes_ptr, n, offsets_ptr, neighbours_ptr, instance_classes, root_ptr, order_ptr, coffs_ptr, flags_ptr,
+                        stream=None):
+        """f3d_flood_order_dev: device buffers root/order int64 [n], coffs int64 [n + 1], flags uint8 [n]; synchronises `stream`
+        (the frontier length is read back every few levels).  -> stats dict (clusters, points, levels, readbacks)."""
+        inst = np.ascontiguousarray(np.asarray(instance_classes).reshape(-1), dtype=np.int64)
+        stats = np.zeros(4, np.int64)
+        self._check(self._lib.f3d_flood_order_dev(self._h, classes_ptr, int(n), offsets_ptr, neighbours_ptr, _ptr(inst), len(inst), root_ptr,
+                                                  order_ptr, coffs_ptr, flags_ptr, _ptr(stats), stream))
+        return _flood_stats(stats)
+
+    def color_segment_dev(self, colors_ptr, dtype, n, offsets_ptr, neighbours_ptr, ids_ptr, seeds_ptr, nseeds, threshold, neutral_ids=(0,),
+                          max_level=10, accepted_ptr=None, stream=None):
+        """f3d_color_segment_dev: enqueue only; an index error is recorded for take_device_error."""
+        thr = _threshold3(threshold)
+        neu = np.ascontiguousarray(np.asarray(list(neutral_ids)).reshape(-1), dtype=np.int64)
+        self._check(self._lib.f3d_color_segment_dev(self._h, colors_ptr, int(dtype), int(n), offsets_ptr, neighbours_ptr, ids_ptr, seeds_ptr,
+                                                    int(nseeds), _ptr(thr), _ptr(neu), len(neu), int(max_level), accepted_ptr, stream))
 
     def take_device_error(self, stream=None):
         self._check(self._lib.f3d_take_device_error(self._h, stream))

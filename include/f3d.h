@@ -400,6 +400,47 @@ int f3d_components_same_class_dev(f3d_ctx* ctx, const int64_t* classes, int64_t 
                                   const int32_t* neighbours, int32_t* parent_scratch /*int32 [n]*/, int64_t* root,
                                   void* stream);
 
+/* ---- CVSegmentation.instance_seperate: ordered same-class flood (Fusion3DSeg/segUtils/cv.py:52-89, 309-365) ---- */
+/* The clusters (same-class connected components) of the classes inst[0..ninst) (HOST array, processing order; a repeated
+ * class counts at its first position), numbered by the rank of their class in that list, then by ascending seed (= smallest
+ * index), are concatenated in the reference's FIFO pop order:
+ *   root    int64 [n]    : smallest index of the point's component (as f3d_components_same_class)
+ *   order   int64 [n]    : order[coffs[c] .. coffs[c+1]) = cluster c in pop order; entries past stats[1] are -1
+ *   coffs   int64 [n+1]  : cluster offsets, stats[0] + 1 of them used
+ *   flags   uint8 [n]    : 1 = boundary point of its cluster (the reference's boundary[parents[q]] for a popped
+ *                          different-class neighbour q); a cluster's boundary is flags restricted to its points
+ *   stats   int64 [4]    : HOST, {clusters, points in clusters, BFS levels, frontier readbacks}
+ * Preconditions: symmetric rows without duplicate entries, which is what KDTree.query_radius and f3d_radius_graph produce
+ * (the reference follows rows as directed edges and enqueues a duplicate twice).  A neighbour index outside [0, n) ->
+ * F3D_ERR_INDEX.  n < 2^31.  The _dev twin takes device pointers (inst stays on the host), enqueues on `stream` and
+ * synchronises it: the frontier length is read back every few levels.  Scratch: f3d_ctx_reserve_cvseg(). */
+int f3d_flood_order(f3d_ctx* ctx, const int64_t* classes, int64_t n, const int64_t* offsets, const int32_t* neighbours,
+                    const int64_t* inst, int ninst, int64_t* root, int64_t* order, int64_t* coffs, uint8_t* flags, int64_t stats[4]);
+int f3d_flood_order_dev(f3d_ctx* ctx, const int64_t* classes, int64_t n, const int64_t* offsets, const int32_t* neighbours,
+                        const int64_t* inst, int ninst, int64_t* root, int64_t* order, int64_t* coffs, uint8_t* flags,
+                        int64_t stats[4], void* stream);
+
+/* ---- CVSegmentation.color_segment: running-mean colour growing (cv.py:92-142, 367-399) ---------------------------- */
+/* For every seed in order: FIFO flood from the seed (level 1) through neighbours whose id is neutral (ids in
+ * neutral_ids at the start, minus points taken by earlier seeds); a popped point at level == max_level, or with
+ * |sma - colour| > threshold in any channel, is skipped; otherwise npts += 1, sma = sma + (colour - sma) / npts in the
+ * colours' dtype (F3D_F64 or F3D_F32), ids[point] = the seed's id (read when the seed starts) and its neighbours are
+ * enqueued.  ids int64 [n] is updated in place.  threshold: HOST double [3]; neutral_ids: HOST, at most
+ * F3D_COLOR_MAX_NEUTRAL; max_level <= 0 = no limit.  One workgroup runs the whole seed list.  Same adjacency
+ * preconditions as f3d_flood_order.  A seed or neighbour index outside [0, n) -> F3D_ERR_INDEX (the host entry
+ * then leaves ids as they were).
+ * accepted (HOST, may be NULL): points accepted over all seeds.  The _dev twin: colors, offsets, neighbours, ids and seeds
+ * on the device; enqueues on `stream`; accepted_dev (device int64, may be NULL) is incremented. */
+#define F3D_COLOR_MAX_NEUTRAL 64
+int f3d_color_segment(f3d_ctx* ctx, const void* colors, f3d_dtype dtype, int64_t n, const int64_t* offsets, const int32_t* neighbours,
+                      int64_t* ids, const int64_t* seeds, int64_t nseeds, const double threshold[3], const int64_t* neutral_ids,
+                      int nneutral, int max_level, int64_t* accepted);
+int f3d_color_segment_dev(f3d_ctx* ctx, const void* colors, f3d_dtype dtype, int64_t n, const int64_t* offsets,
+                          const int32_t* neighbours, int64_t* ids, const int64_t* seeds, int64_t nseeds, const double threshold[3],
+                          const int64_t* neutral_ids, int nneutral, int max_level, int64_t* accepted_dev, void* stream);
+/* Sizes the scratch of both for clouds of up to n points: later _dev calls of a strict context do not allocate. */
+int f3d_ctx_reserve_cvseg(f3d_ctx* ctx, int64_t n);
+
 /* ---- (f)#1: the adjacency itself, Fusion.save_data (Fusion3DSeg/fusion.py:374-375) -------- */
 /* tree = KDTree(points); adj = tree.query_radius(points, r=2*ds_radius): for every point the indices of all points
  * (itself included) whose float64 squared distance ((dx*dx + dy*dy) + dz*dz, sklearn's euclidean_rdist order) is
