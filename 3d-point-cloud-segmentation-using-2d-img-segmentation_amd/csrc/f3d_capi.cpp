@@ -26,7 +26,8 @@ enum { SLOT_XYZ = 0, SLOT_OUT0, SLOT_OUT1, SLOT_VIEWS, SLOT_MASKS, SLOT_AUX0, SL
        SLOT_TILED_MASKS, SLOT_TODO, SLOT_GRAPH, SLOT_GRAPH_BBOX, SLOT_PATCH,
        SLOT_GRP_ORDER, SLOT_GRP_KEYS, SLOT_GRP_STARTS, SLOT_GRP_SCRATCH, SLOT_OBB_TABLE, SLOT_OBB_FACETS, SLOT_OBB_CAND, SLOT_FUSE_TABLES, SLOT_FUSE_CARRY, SLOT_FUSE_XYZ, SLOT_FUSION, SLOT_PATCH_STATUS, SLOT_NRM, SLOT_NRM_CAMS,
        SLOT_QRY, SLOT_QRY_IN, SLOT_QRY_OFFS,
-       SLOT_FLOOD, SLOT_COLOR, SLOT_CVS_INST, SLOT_CVS_ORDER, SLOT_CVS_COFFS, SLOT_CVS_FLAGS, SLOT_CVS_SEEDS, SLOT_CVS_STATS, SLOT_COUNT };
+       SLOT_FLOOD, SLOT_COLOR, SLOT_CVS_INST, SLOT_CVS_ORDER, SLOT_CVS_COFFS, SLOT_CVS_FLAGS, SLOT_CVS_SEEDS, SLOT_CVS_STATS,
+       SLOT_QUADS, SLOT_QUADS_OUT, SLOT_COUNT };
 
 thread_local char g_create_err[512] = "";
 
@@ -159,6 +160,8 @@ int take_error(f3d_ctx* ctx, hipStream_t s, int mask = F3D_DEVERR_ALL) {
             return fail(ctx, F3D_ERR_INDEX, "flood_order: neighbour index out of bounds");
         if (e & F3D_DEVERR_COLOR)
             return fail(ctx, F3D_ERR_INDEX, "color_segment: seed or neighbour index out of bounds");
+        if (e & F3D_DEVERR_QUADS)
+            return fail(ctx, F3D_ERR_INDEX, "door_window_quads: a triangle's vertex index is out of bounds");
     }
     return F3D_OK;
 }
@@ -1279,6 +1282,67 @@ int f3d_color_segment(f3d_ctx* ctx, const void* colors, f3d_dtype dtype, int64_t
     if (!st.rc) st.rc = f3d_color_segment_dev(ctx, dclr, dtype, n, doffs, dnb, dids, dseeds, nseeds, threshold, neutral_ids, nneutral,
                                               max_level, dacc, ctx->stream);
     return st.finish(F3D_DEVERR_COLOR);
+}
+
+// ---------------------------------------------------------------------------------------------
+// door_window_bbox.generate_mesh: door / window quads on the mesh
+// ---------------------------------------------------------------------------------------------
+static bool quads_args_ok(int64_t n, int k, int64_t nv, int64_t nt) {
+    return n >= 0 && n <= 0x7fffffffLL && k >= 0 && k <= F3D_QUADS_MAX_INST && nv >= 0 && nt >= 0 && nt <= 0x7fffffffLL;
+}
+
+int f3d_ctx_reserve_quads(f3d_ctx* ctx, int64_t n, int k, int64_t nt) {
+    int rc = enter(ctx); if (rc) return rc;
+    if (!quads_args_ok(n, k, 0, nt)) return fail(ctx, F3D_ERR_INVALID, "ctx_reserve_quads: bad arguments");
+    const int strict = ctx->strict;
+    ctx->strict = 0;
+    void* p;
+    rc = ensure(ctx, SLOT_QUADS, f3d_quads_scratch_bytes(n, k, nt), &p);
+    ctx->strict = strict;
+    return rc;
+}
+
+int f3d_door_window_quads_dev(f3d_ctx* ctx, const double* points, int64_t n, const int64_t* ids, const int64_t* inst, int k,
+                              const double* verts, int64_t nv, const int64_t* tris, int64_t nt, double* quads, int32_t* status,
+                              int32_t* tri, double* normals, void* stream) {
+    int rc = enter(ctx); if (rc) return rc;
+    if (!quads_args_ok(n, k, nv, nt) || (n > 0 && (!points || !ids)) || (k > 0 && (!inst || !quads || !status || !tri)) ||
+        (nv > 0 && !verts) || (nt > 0 && !tris))
+        return fail(ctx, F3D_ERR_INVALID, "door_window_quads: bad arguments (n, nt < 2^31, k <= %d)", F3D_QUADS_MAX_INST);
+    void* scratch;
+    if ((rc = ensure(ctx, SLOT_QUADS, f3d_quads_scratch_bytes(n, k, nt), &scratch))) return rc;
+    F3D_HIP(ctx, f3d_launch_door_window_quads(points, n, ids, inst, k, verts, nv, tris, nt, quads, status, tri, normals, scratch,
+                                              ctx->dev_err, pick(ctx, stream)));
+    return F3D_OK;
+}
+
+int f3d_door_window_quads(f3d_ctx* ctx, const double* points, int64_t n, const int64_t* ids, const int64_t* inst, int k,
+                          const double* verts, int64_t nv, const int64_t* tris, int64_t nt, double* quads, int32_t* status,
+                          int32_t* tri, double* normals) {
+    int rc = enter(ctx); if (rc) return rc;
+    if (!quads_args_ok(n, k, nv, nt) || (n > 0 && (!points || !ids)) || (k > 0 && (!inst || !quads || !status || !tri)) ||
+        (nv > 0 && !verts) || (nt > 0 && !tris))
+        return fail(ctx, F3D_ERR_INVALID, "door_window_quads: bad arguments (n, nt < 2^31, k <= %d)", F3D_QUADS_MAX_INST);
+    const size_t qbytes = (size_t)k * 96, sbytes = ((size_t)k * 4 + 7) & ~(size_t)7;
+    staging st(ctx);
+    const double* dpts = st.in(SLOT_XYZ, points, (size_t)n * 24);
+    const int64_t* dids = st.in(SLOT_AUX0, ids, (size_t)n * 8);
+    const double* dverts = st.in(SLOT_AUX1, verts, (size_t)nv * 24);
+    const int64_t* dtris = st.in(SLOT_MASKS, tris, (size_t)nt * 24);
+    double* dnrm = st.out(SLOT_OUT1, normals, (size_t)nt * 24);
+    char* dout = (char*)st.slot(SLOT_QUADS_OUT, qbytes + 2 * sbytes + (size_t)k * 8);     // quads, status, tri, then the ids wanted
+    if (st.rc) return st.rc;
+    double* dquads = (double*)dout;
+    int32_t* dstatus = (int32_t*)(dout + qbytes);
+    int32_t* dtri = (int32_t*)(dout + qbytes + sbytes);
+    int64_t* dinst = (int64_t*)(dout + qbytes + 2 * sbytes);
+    st.put(dinst, inst, (size_t)k * 8);
+    st.back(quads, dquads, qbytes);
+    st.back(status, dstatus, (size_t)k * 4);
+    st.back(tri, dtri, (size_t)k * 4);
+    if (!st.rc) st.rc = f3d_door_window_quads_dev(ctx, dpts, n, dids, dinst, k, dverts, nv, dtris, nt, dquads, dstatus, dtri, dnrm,
+                                                  ctx->stream);
+    return st.finish(F3D_DEVERR_QUADS);
 }
 
 // ---------------------------------------------------------------------------------------------

@@ -11,7 +11,8 @@
 #define F3D_DEVERR_CC 4                    // components_same_class: neighbour index out of bounds
 #define F3D_DEVERR_FLOOD 8                 // flood_order: neighbour index out of bounds
 #define F3D_DEVERR_COLOR 16                // color_segment: neighbour or seed index out of bounds
-#define F3D_DEVERR_ALL 31
+#define F3D_DEVERR_QUADS 32                // door_window_quads: triangle vertex index out of bounds
+#define F3D_DEVERR_ALL 63
 #define F3D_PLANES_PER_LAUNCH 16
 #define F3D_OBB_MAX_BOXES 4096
 #define F3D_SORT_MAX_CELLS 32767            // + 1 overflow cell = 2^15 keys -> 16 key bits sorted
@@ -265,3 +266,10 @@ hipError_t f3d_launch_obb_candidates(const void* xyz, int dtype, int64_t n, cons
                                      int64_t nids, int min_members, unsigned long long* table, void* scratch, int32_t* cand, int64_t* cand_start,
                                      hipStream_t s);
 hipError_t f3d_launch_gather_points(const void* xyz, int dtype, const int32_t* idx, int64_t count, double* out, hipStream_t s);
+// door / window quads of door_window_bbox.generate_mesh (f3d_quads.hip): pts float64 [n, 3], ids int64 [n], inst int64 [k] (device),
+// verts float64 [nv, 3], tris int64 [nt, 3]; quads float64 [k, 4, 3], status / tri int32 [k], normals float64 [nt, 3] (may be NULL).
+// Enqueue only.  scratch: f3d_quads_scratch_bytes(n, k, nt)
+size_t f3d_quads_scratch_bytes(int64_t n, int k, int64_t nt);
+hipError_t f3d_launch_door_window_quads(const double* pts, int64_t n, const int64_t* ids, const int64_t* inst, int k, const double* verts,
+                                        int64_t nv, const int64_t* tris, int64_t nt, double* quads, int32_t* status, int32_t* tri,
+                                        double* normals, void* scratch, int* err, hipStream_t s);

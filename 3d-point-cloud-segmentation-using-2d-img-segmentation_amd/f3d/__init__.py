@@ -27,6 +27,8 @@ MAX_OBB = 4096
 OBB_OK, OBB_FEW, OBB_DEFERRED = 0, 1, 2
 NORM_PLAIN, NORM_FMA, NORM_HOST = 0, 1, 2   # how the fusion kernels take sqrt(v.dot(v)) (f3d.h F3D_NORM_*)
 NORMALS_MAX_NN = 64          # F3D_NORMALS_MAX_NN: the largest max_nn of estimate_normals
+QUAD_OK, QUAD_HORIZONTAL, QUAD_NO_CANDIDATE = 0, 1, 2   # per-instance status of door_window_quads (f3d.h F3D_QUAD_*)
+QUADS_MAX_INST = 65535       # F3D_QUADS_MAX_INST
 
 
 class F3DError(RuntimeError):
@@ -135,6 +137,9 @@ def library():
         'f3d_color_segment': (i32, [vp, vp, i32, i64, vp, vp, vp, vp, i64, vp, vp, i32, i32, vp]),
         'f3d_color_segment_dev': (i32, [vp, vp, i32, i64, vp, vp, vp, vp, i64, vp, vp, i32, i32, vp, vp]),
         'f3d_ctx_reserve_cvseg': (i32, [vp, i64]),
+        'f3d_door_window_quads': (i32, [vp, vp, i64, vp, vp, i32, vp, i64, vp, i64, vp, vp, vp, vp]),
+        'f3d_door_window_quads_dev': (i32, [vp, vp, i64, vp, vp, i32, vp, i64, vp, i64, vp, vp, vp, vp, vp]),
+        'f3d_ctx_reserve_quads': (i32, [vp, i64, i32, i64]),
         'f3d_patch_owner': (i32, [vp, vp, i64, i32, i32, i32, dbl, dbl, vp, vp, vp, vp, vp, vp]),
         'f3d_patch_owner_dev': (i32, [vp, vp, i64, i32, i32, i32, dbl, dbl, vp, vp, vp, vp, vp, vp, vp]),
         'f3d_patch_match': (i32, [vp, vp, i64, i32, i32, i32, dbl, dbl, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
@@ -307,6 +312,10 @@ class Context:
     def reserve_cvseg(self, n):
         """Size the scratch of flood_order / color_segment for clouds of up to n points (strict contexts then do not allocate)."""
         self._check(self._lib.f3d_ctx_reserve_cvseg(self._h, int(n)))
+
+    def reserve_quads(self, n, k, ntriangles):
+        """Size the scratch of door_window_quads for n points, k instances and that many triangles."""
+        self._check(self._lib.f3d_ctx_reserve_quads(self._h, int(n), int(k), int(ntriangles)))
 
     def set_strict(self, strict=True):
         self._check(self._lib.f3d_ctx_set_strict(self._h, int(bool(strict))))
@@ -582,6 +591,26 @@ class Context:
                                                 _ptr(ids), _ptr(sd), len(sd), _ptr(thr), _ptr(neu), len(neu), int(max_level), _ptr(acc)))
         return ids, int(acc[0])
 
+    def door_window_quads(self, points, ids, instance_ids, vertices, triangles):
+        """Door / window quads of door_window_bbox.generate_mesh (include/f3d.h f3d_door_window_quads) for the distinct ids
+        `instance_ids`.  -> (quads float64 [k, 4, 3], status int32 [k] (QUAD_*), chosen triangle int32 [k], triangle normals
+        float64 [T, 3])."""
+        pts = _f64(points)
+        if pts.ndim != 2 or pts.shape[1] != 3:
+            raise ValueError(f'door_window_quads: points must be [N, 3], got {pts.shape}')
+        ids_ = np.ascontiguousarray(ids, dtype=np.int64).reshape(-1)
+        if len(ids_) != len(pts):
+            raise ValueError(f'door_window_quads: {len(ids_)} ids for {len(pts)} points')
+        inst = np.ascontiguousarray(np.asarray(instance_ids).reshape(-1), dtype=np.int64)
+        verts = _f64(vertices).reshape(-1, 3)
+        tris = np.ascontiguousarray(triangles, dtype=np.int64).reshape(-1, 3)
+        k, nt = len(inst), len(tris)
+        quads, status, tri = np.empty((k, 4, 3)), np.empty(k, np.int32), np.empty(k, np.int32)
+        normals = np.empty((nt, 3))
+        self._check(self._lib.f3d_door_window_quads(self._h, _ptr(pts), len(pts), _ptr(ids_), _ptr(inst), k, _ptr(verts), len(verts),
+                                                    _ptr(tris), nt, _ptr(quads), _ptr(status), _ptr(tri), _ptr(normals)))
+        return quads, status, tri, normals
+
     def patch_owner(self, uv, seed_pts, seed_normals, frame_pts, frame_normals, free, h, w, half, radius, min_cosine):
         """owner int32 [h*w]: for every free depth pixel the first seed of Fusion.fuse's matching loop (fusion.py:269-298)
         that would take it, -1 if none."""
@@ -765,6 +794,14 @@ class Context:
         neu = np.ascontiguousarray(np.asarray(list(neutral_ids)).reshape(-1), dtype=np.int64)
         self._check(self._lib.f3d_color_segment_dev(self._h, colors_ptr, int(dtype), int(n), offsets_ptr, neighbours_ptr, ids_ptr, seeds_ptr,
                                                     int(nseeds), _ptr(thr), _ptr(neu), len(neu), int(max_level), accepted_ptr, stream))
+
+    def door_window_quads_dev(self, points_ptr, n, ids_ptr, instance_ids_ptr, k, vertices_ptr, nvertices, triangles_ptr, ntriangles, quads_ptr,
+                              status_ptr, tri_ptr, normals_ptr=None, stream=None):
+        """f3d_door_window_quads_dev: float64 points / vertices, int64 ids / instance ids / triangles, all on the device; enqueue only
+        (a bad vertex index is recorded for take_device_error)."""
+        self._check(self._lib.f3d_door_window_quads_dev(self._h, points_ptr, int(n), ids_ptr, instance_ids_ptr, int(k), vertices_ptr,
+                                                        int(nvertices), triangles_ptr, int(ntriangles), quads_ptr, status_ptr, tri_ptr,
+                                                        normals_ptr, stream))
 
     def take_device_error(self, stream=None):
         self._check(self._lib.f3d_take_device_error(self._h, stream))

@@ -54,6 +54,66 @@ def write_ply(path, pcd):
         fp.write(rec.tobytes())
 
 
+class TriangleMesh:
+    """Minimal stand-in for the o3d.geometry.TriangleMesh that door_window_bbox.generate_mesh returns (.vertices float64 [V, 3],
+    .triangles int32 [T, 3], .vertex_colors float64 [V, 3] or None)."""
+
+    def __init__(self, vertices, triangles, vertex_colors=None):
+        self.vertices = np.asarray(vertices, np.float64).reshape(-1, 3)
+        self.triangles = np.asarray(triangles, np.int32).reshape(-1, 3)
+        self.vertex_colors = None if vertex_colors is None else np.asarray(vertex_colors, np.float64).reshape(-1, 3)
+
+
+def write_triangle_mesh(path, mesh):
+    """Binary little-endian PLY of a triangle mesh: x,y,z (double), optional red,green,blue (uchar, round(clip(c, 0, 1) * 255)),
+    faces as `list uchar int vertex_indices`."""
+    pts = np.asarray(mesh.vertices, np.float64).reshape(-1, 3)
+    tris = np.asarray(mesh.triangles).reshape(-1, 3)
+    fields = [('x', '<f8'), ('y', '<f8'), ('z', '<f8')]
+    cols = [pts[:, 0], pts[:, 1], pts[:, 2]]
+    if mesh.vertex_colors is not None:
+        c8 = np.round(np.clip(np.asarray(mesh.vertex_colors, np.float64), 0.0, 1.0) * 255.0).astype(np.uint8)
+        fields += [('red', 'u1'), ('green', 'u1'), ('blue', 'u1')]
+        cols += [c8[:, 0], c8[:, 1], c8[:, 2]]
+    rec = np.empty(len(pts), dtype=fields)
+    for (name, _), col in zip(fields, cols):
+        rec[name] = col
+    face = np.empty(len(tris), dtype=[('n', 'u1'), ('v', '<i4', (3,))])
+    face['n'], face['v'] = 3, tris
+    names = {'<f8': 'double', 'u1': 'uchar'}
+    header = 'ply\nformat binary_little_endian 1.0\n' + f'element vertex {len(pts)}\n' + \
+        ''.join(f'property {names[t]} {n}\n' for n, t in fields) + \
+        f'element face {len(tris)}\nproperty list uchar int vertex_indices\nend_header\n'
+    with open(path, 'wb') as fp:
+        fp.write(header.encode('ascii'))
+        fp.write(rec.tobytes())
+        fp.write(face.tobytes())
+
+
+def read_triangle_mesh_ply(path):
+    """The TriangleMesh of a PLY written by write_triangle_mesh."""
+    with open(path, 'rb') as fp:
+        props, nv, nf = [], 0, 0
+        while True:
+            line = fp.readline().decode('ascii').strip()
+            if line.startswith('element vertex'):
+                nv = int(line.split()[-1])
+            elif line.startswith('element face'):
+                nf = int(line.split()[-1])
+            elif line.startswith('property') and 'list' not in line:
+                props.append(line.split()[1:3])
+            elif line == 'end_header':
+                break
+        np_t = {'double': '<f8', 'uchar': 'u1'}
+        dt = np.dtype([(nm, np_t[t]) for t, nm in props])
+        rec = np.frombuffer(fp.read(nv * dt.itemsize), dtype=dt, count=nv)
+        face = np.frombuffer(fp.read(), dtype=[('n', 'u1'), ('v', '<i4', (3,))], count=nf)
+    if nf and not (face['n'] == 3).all():
+        raise ValueError(f'{path}: not a triangle mesh')
+    clr = np.stack([rec['red'], rec['green'], rec['blue']], axis=1) / 255.0 if 'red' in dt.names else None
+    return TriangleMesh(np.stack([rec['x'], rec['y'], rec['z']], axis=1), face['v'], clr)
+
+
 def read_ply_points(path):
     """xyz of a PLY written by write_ply (or any binary-LE / ascii PLY whose first three properties are x,y,z)."""
     with open(path, 'rb') as fp:

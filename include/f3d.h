@@ -441,6 +441,36 @@ int f3d_color_segment_dev(f3d_ctx* ctx, const void* colors, f3d_dtype dtype, int
 /* Sizes the scratch of both for clouds of up to n points: later _dev calls of a strict context do not allocate. */
 int f3d_ctx_reserve_cvseg(f3d_ctx* ctx, int64_t n);
 
+/* ---- door_window_bbox.generate_mesh: door / window quads on the mesh (segUtils/door_window_bbox.py:65-150) ---------- */
+/* For every wanted instance id inst[s], box_pts = points[ids == inst[s]] in ascending point index, and against the triangles
+ * tris int64 [nt, 3] of verts float64 [nv, 3] (a negative vertex index counts from the end, as in NumPy):
+ *   normal[t]  = cross(v1 - v0, v2 - v0) / sqrt((x*x + y*y) + z*z), left as it is when that squared norm is 0, and (0, 0, 1)
+ *                when its x is NaN (Open3D compute_triangle_normals, restated);
+ *   perp[m, t] = ((p - v0)_x n_x + (p - v0)_z n_z) + (p - v0)_y n_y;  tri_dist[t] = sum over m of |perp[m, t]|, in point order;
+ *   candidates = the t with tri_dist[t] < min + 0.05 * min, in triangle order (none when the minimum is 0, infinite or NaN);
+ *   per candidate the members projected onto its plane (p - n * perp) that pass _point_in_triangle (:26-47); the first
+ *   candidate with the most of them is chosen;
+ *   the instance is skipped when cos(10 deg) < n_z; else its quad [4, 3] is built from _get_perpendicular_vectors(n) and the
+ *   extents of the projected members around the first one (:119-131).
+ * np.dot / np.linalg.norm are the fma chains fma(x2, y2, fma(x1, y1, x0 * y0)); every other product and sum is rounded alone.
+ * Outputs: quads float64 [k, 4, 3] (NaN unless the status is F3D_QUAD_OK), status int32 [k], tri int32 [k] (the chosen
+ * triangle, -1 without candidates), normals float64 [nt, 3] (may be NULL).  inst holds distinct ids (a repeated id owns no
+ * points: F3D_QUAD_NO_CANDIDATE); k <= F3D_QUADS_MAX_INST.  A vertex index outside [-nv, nv) -> F3D_ERR_INDEX.  Scratch
+ * grows with n + k * nt (f3d_ctx_reserve_quads).
+ * The _dev twin takes device pointers (inst too), enqueues on `stream` and records an index error for f3d_take_device_error;
+ * the host entry reads everything back once at the end. */
+#define F3D_QUAD_OK 0
+#define F3D_QUAD_HORIZONTAL 1              /* skipped: the chosen triangle faces up (:117) */
+#define F3D_QUAD_NO_CANDIDATE 2            /* the reference raises ValueError (argmax of an empty sequence) */
+#define F3D_QUADS_MAX_INST 65535
+int f3d_door_window_quads(f3d_ctx* ctx, const double* points, int64_t n, const int64_t* ids, const int64_t* inst, int k,
+                          const double* verts, int64_t nv, const int64_t* tris, int64_t nt, double* quads, int32_t* status,
+                          int32_t* tri, double* normals);
+int f3d_door_window_quads_dev(f3d_ctx* ctx, const double* points, int64_t n, const int64_t* ids, const int64_t* inst, int k,
+                              const double* verts, int64_t nv, const int64_t* tris, int64_t nt, double* quads, int32_t* status,
+                              int32_t* tri, double* normals, void* stream);
+int f3d_ctx_reserve_quads(f3d_ctx* ctx, int64_t n, int k, int64_t nt);
+
 /* ---- (f)#1: the adjacency itself, Fusion.save_data (Fusion3DSeg/fusion.py:374-375) -------- */
 /* tree = KDTree(points); adj = tree.query_radius(points, r=2*ds_radius): for every point the indices of all points
  * (itself included) whose float64 squared distance ((dx*dx + dy*dy) + dz*dz, sklearn's euclidean_rdist order) is
