@@ -27,7 +27,7 @@ enum { SLOT_XYZ = 0, SLOT_OUT0, SLOT_OUT1, SLOT_VIEWS, SLOT_MASKS, SLOT_AUX0, SL
        SLOT_GRP_ORDER, SLOT_GRP_KEYS, SLOT_GRP_STARTS, SLOT_GRP_SCRATCH, SLOT_OBB_TABLE, SLOT_OBB_FACETS, SLOT_OBB_CAND, SLOT_FUSE_TABLES, SLOT_FUSE_CARRY, SLOT_FUSE_XYZ, SLOT_FUSION, SLOT_PATCH_STATUS, SLOT_NRM, SLOT_NRM_CAMS,
        SLOT_QRY, SLOT_QRY_IN, SLOT_QRY_OFFS,
        SLOT_FLOOD, SLOT_COLOR, SLOT_CVS_INST, SLOT_CVS_ORDER, SLOT_CVS_COFFS, SLOT_CVS_FLAGS, SLOT_CVS_SEEDS, SLOT_CVS_STATS,
-       SLOT_QUADS, SLOT_QUADS_OUT, SLOT_COUNT };
+       SLOT_QUADS, SLOT_QUADS_OUT, SLOT_GROW, SLOT_COUNT };
 
 thread_local char g_create_err[512] = "";
 
@@ -160,6 +160,8 @@ int take_error(f3d_ctx* ctx, hipStream_t s, int mask = F3D_DEVERR_ALL) {
             return fail(ctx, F3D_ERR_INDEX, "flood_order: neighbour index out of bounds");
         if (e & F3D_DEVERR_COLOR)
             return fail(ctx, F3D_ERR_INDEX, "color_segment: seed or neighbour index out of bounds");
+        if (e & F3D_DEVERR_GROW)
+            return fail(ctx, F3D_ERR_INDEX, "region_grow: seed or neighbour index out of bounds, or a seed listed twice");
         if (e & F3D_DEVERR_QUADS)
             return fail(ctx, F3D_ERR_INDEX, "door_window_quads: a triangle's vertex index is out of bounds");
     }
@@ -1282,6 +1284,94 @@ int f3d_color_segment(f3d_ctx* ctx, const void* colors, f3d_dtype dtype, int64_t
     if (!st.rc) st.rc = f3d_color_segment_dev(ctx, dclr, dtype, n, doffs, dnb, dids, dseeds, nseeds, threshold, neutral_ids, nneutral,
                                               max_level, dacc, ctx->stream);
     return st.finish(F3D_DEVERR_COLOR);
+}
+
+// ---------------------------------------------------------------------------------------------
+// refinement: region growing of a picked instance, distance to the wall plane
+// ---------------------------------------------------------------------------------------------
+int f3d_ctx_reserve_refine(f3d_ctx* ctx, int64_t n) {
+    int rc = enter(ctx); if (rc) return rc;
+    if (n < 0 || n > F3D_GROW_MAX_POINTS) return fail(ctx, F3D_ERR_INVALID, "ctx_reserve_refine: bad arguments (n <= 2^31 - 2049)");
+    const int strict = ctx->strict;
+    ctx->strict = 0;
+    void* p;
+    rc = ensure(ctx, SLOT_GROW, f3d_grow_scratch_bytes(n), &p);
+    ctx->strict = strict;
+    return rc;
+}
+
+static int grow_args(f3d_ctx* ctx, f3d_dtype dtype, int nchan, int64_t n, int64_t nseeds, const double* sma0, int64_t npts0, int seeds_given,
+                     const double* threshold, int max_level, f3d_grow_args* a) {
+    if (n < 0 || n > F3D_GROW_MAX_POINTS || nseeds < 0 || npts0 < 0 || !sma0 || !threshold ||
+        !((nchan == 1 && dtype == F3D_F64) || (nchan == 3 && (dtype == F3D_F64 || dtype == F3D_F32))))
+        return fail(ctx, F3D_ERR_INVALID, "region_grow: bad arguments (n <= 2^31 - 2049; float64 [n, 1], or float64 / float32 [n, 3] values)");
+    for (int c = 0; c < 3; ++c) { a->thr[c] = c < nchan ? threshold[c] : 0; a->sma0[c] = c < nchan ? sma0[c] : 0; }
+    a->npts0 = npts0;
+    a->max_level = max_level;
+    a->seeds_given = seeds_given != 0;
+    if (nseeds > n) return fail(ctx, F3D_ERR_INDEX, "region_grow: more seeds than points (a seed is out of bounds or listed twice)");
+    return F3D_OK;
+}
+
+int f3d_region_grow_dev(f3d_ctx* ctx, const void* values, f3d_dtype dtype, int nchan, int64_t n, const int64_t* offsets, const int32_t* nbrs,
+                        const int64_t* seeds, int64_t nseeds, const double* sma0, int64_t npts0, int seeds_given, const double* threshold,
+                        int max_level, int64_t* cluster, int64_t* count_dev, void* stream) {
+    int rc = enter(ctx); if (rc) return rc;
+    f3d_grow_args a;
+    if ((rc = grow_args(ctx, dtype, nchan, n, nseeds, sma0, npts0, seeds_given, threshold, max_level, &a))) return rc;
+    if (!count_dev || (n > 0 && (!values || !offsets || !cluster)) || (nseeds > 0 && !seeds))
+        return fail(ctx, F3D_ERR_INVALID, "region_grow: NULL argument");
+    hipStream_t s = pick(ctx, stream);
+    if (n == 0) {
+        F3D_HIP(ctx, hipMemsetAsync(count_dev, 0, 8, s));
+        return F3D_OK;
+    }
+    void* scratch;
+    if ((rc = ensure(ctx, SLOT_GROW, f3d_grow_scratch_bytes(n), &scratch))) return rc;
+    F3D_HIP(ctx, f3d_launch_region_grow(values, dtype, nchan, n, offsets, nbrs, seeds, nseeds, a, scratch, cluster, count_dev, ctx->dev_err, s));
+    return F3D_OK;
+}
+
+int f3d_region_grow(f3d_ctx* ctx, const void* values, f3d_dtype dtype, int nchan, int64_t n, const int64_t* offsets, const int32_t* nbrs,
+                    const int64_t* seeds, int64_t nseeds, const double* sma0, int64_t npts0, int seeds_given, const double* threshold,
+                    int max_level, int64_t* cluster, int64_t* count) {
+    int rc = enter(ctx); if (rc) return rc;
+    if (count) *count = 0;
+    f3d_grow_args a;
+    if ((rc = grow_args(ctx, dtype, nchan, n, nseeds, sma0, npts0, seeds_given, threshold, max_level, &a))) return rc;
+    if (!count || (n > 0 && (!values || !offsets || !cluster)) || (nseeds > 0 && !seeds)) return fail(ctx, F3D_ERR_INVALID, "region_grow: NULL argument");
+    if (n == 0 || nseeds == 0) return F3D_OK;
+    const int64_t e = offsets[n];
+    if (e < 0 || (e > 0 && !nbrs)) return fail(ctx, F3D_ERR_INVALID, "region_grow: bad adjacency");
+    staging st(ctx);
+    const void* dval = st.in(SLOT_XYZ, (const char*)values, (size_t)n * nchan * (dtype == F3D_F64 ? 8 : 4));
+    const int64_t* doffs = st.in(SLOT_OUT1, offsets, (size_t)(n + 1) * 8);
+    const int32_t* dnb = st.in(SLOT_MASKS, nbrs, (size_t)e * 4);
+    const int64_t* dseeds = st.in(SLOT_CVS_SEEDS, seeds, (size_t)nseeds * 8);
+    int64_t* dcl = st.out(SLOT_OUT0, cluster, (size_t)n * 8);
+    int64_t* dcount = st.out(SLOT_CVS_STATS, count, 8);
+    if (!st.rc) st.rc = f3d_region_grow_dev(ctx, dval, dtype, nchan, n, doffs, dnb, dseeds, nseeds, sma0, npts0, seeds_given, threshold,
+                                            max_level, dcl, dcount, ctx->stream);
+    return st.finish(F3D_DEVERR_GROW);
+}
+
+int f3d_plane_distance_dev(f3d_ctx* ctx, const double* points, int64_t n, const double plane_point[3], const double normal[3], double* out,
+                           void* stream) {
+    int rc = enter(ctx); if (rc) return rc;
+    if (n < 0 || !plane_point || !normal || (n > 0 && (!points || !out))) return fail(ctx, F3D_ERR_INVALID, "plane_distance: bad arguments");
+    F3D_HIP(ctx, f3d_launch_plane_distance(points, n, plane_point, normal, out, pick(ctx, stream)));
+    return F3D_OK;
+}
+
+int f3d_plane_distance(f3d_ctx* ctx, const double* points, int64_t n, const double plane_point[3], const double normal[3], double* out) {
+    int rc = enter(ctx); if (rc) return rc;
+    if (n < 0 || !plane_point || !normal || (n > 0 && (!points || !out))) return fail(ctx, F3D_ERR_INVALID, "plane_distance: bad arguments");
+    if (n == 0) return F3D_OK;
+    staging st(ctx);
+    const double* dpts = st.in(SLOT_XYZ, points, (size_t)n * 24);
+    double* dout = st.out(SLOT_OUT0, out, (size_t)n * 8);
+    if (!st.rc) st.rc = f3d_plane_distance_dev(ctx, dpts, n, plane_point, normal, dout, ctx->stream);
+    return st.finish();
 }
 
 // ---------------------------------------------------------------------------------------------

@@ -25,21 +25,6 @@ constexpr int CT = 1024;                 // threads of the one workgroup
 constexpr int CHUNK = CT;                // queue entries staged in LDS per step of the serial lane
 constexpr int IB = 256;
 
-__device__ __forceinline__ void block_scan(int v, int* lds, int& ex, int& tot) {
-    const int t = threadIdx.x;
-    lds[t] = v;
-    __syncthreads();
-    for (int d = 1; d < CT; d <<= 1) {
-        const int x = t >= d ? lds[t - d] : 0;
-        __syncthreads();
-        lds[t] += x;
-        __syncthreads();
-    }
-    ex = lds[t] - v;
-    tot = lds[CT - 1];
-    __syncthreads();
-}
-
 __global__ __launch_bounds__(IB) void k_color_init(const int64_t* __restrict__ ids, int64_t n, f3d_color_args a, uint8_t* __restrict__ neutral,
                                                    int32_t* __restrict__ inq, unsigned long long* __restrict__ best) {
     for (int64_t i = (int64_t)blockIdx.x * IB + threadIdx.x; i < n; i += (int64_t)gridDim.x * IB) {
@@ -122,47 +107,11 @@ __global__ __launch_bounds__(CT) void k_color_grow(const T* __restrict__ colors,
             if (t == 0) accepted += na;
             if (level + 1 == a.max_level) { __syncthreads(); break; }      // children would be skipped unseen
             // expand: minimum (accepted position, row position) per unvisited neutral neighbour
-            for (int i = t; i < na; i += CT) {
-                const int64_t v = acc[i];
-                const int64_t e0 = offs[v], e1 = offs[v + 1];
-                for (int64_t e = e0; e < e1; ++e) {
-                    const int64_t j = nbrs[e];
-                    if (j < 0 || j >= n) { atomicOr(err, F3D_DEVERR_COLOR); continue; }
-                    if (inq[j] == epoch || !neutral[j]) continue;
-                    atomicMin(best + j, (unsigned long long)i << 32 | (unsigned long long)(e - e0));
-                }
-            }
+            f3d_flood_expand<CT>(acc, na, offs, nbrs, n, best, err, F3D_DEVERR_COLOR,
+                                 [&](int64_t j) { return inq[j] != epoch && neutral[j]; });
             __syncthreads();
             // place the children in (accepted position, row position) order
-            int carry = 0;
-            for (int b = 0; b < na; b += CT) {
-                const int i = b + t;
-                int cnt = 0;
-                int64_t e0 = 0, e1 = 0;
-                if (i < na) {
-                    const int64_t v = acc[i];
-                    e0 = offs[v]; e1 = offs[v + 1];
-                    for (int64_t e = e0; e < e1; ++e) {
-                        const int64_t j = nbrs[e];
-                        if (j < 0 || j >= n) continue;
-                        if (best[j] == ((unsigned long long)i << 32 | (unsigned long long)(e - e0))) ++cnt;
-                    }
-                }
-                int ex, tot;
-                block_scan(cnt, lds, ex, tot);
-                if (i < na) {
-                    int pos = carry + ex;
-                    for (int64_t e = e0; e < e1; ++e) {
-                        const int64_t j = nbrs[e];
-                        if (j < 0 || j >= n) continue;
-                        if (best[j] != ((unsigned long long)i << 32 | (unsigned long long)(e - e0))) continue;
-                        qn[pos++] = (int32_t)j;
-                        inq[j] = epoch;
-                        best[j] = ~0ull;
-                    }
-                }
-                carry += tot;
-            }
+            const int carry = f3d_flood_place<CT>(acc, na, offs, nbrs, n, best, qn, lds, [&](int64_t j) { inq[j] = epoch; });
             if (t == 0) s_nq = carry;
             int32_t* tmp = q; q = qn; qn = tmp;
             __syncthreads();

@@ -12,7 +12,8 @@
 #define F3D_DEVERR_FLOOD 8                 // flood_order: neighbour index out of bounds
 #define F3D_DEVERR_COLOR 16                // color_segment: neighbour or seed index out of bounds
 #define F3D_DEVERR_QUADS 32                // door_window_quads: triangle vertex index out of bounds
-#define F3D_DEVERR_ALL 63
+#define F3D_DEVERR_GROW 64                 // region_grow: seed or neighbour index out of bounds, or a repeated seed
+#define F3D_DEVERR_ALL 127
 #define F3D_PLANES_PER_LAUNCH 16
 #define F3D_OBB_MAX_BOXES 4096
 #define F3D_SORT_MAX_CELLS 32767            // + 1 overflow cell = 2^15 keys -> 16 key bits sorted
@@ -32,6 +33,88 @@ struct f3d_carve {
     size_t off = 0;
     size_t take(size_t bytes) { const size_t at = off; off += (bytes + 255) & ~(size_t)255; return at; }
 };
+
+// inclusive-to-exclusive scan of one int per thread over a workgroup of NT threads (lds: NT ints): ex = sum of the values of
+// the threads before this one, tot = the workgroup's sum.  Every thread of the workgroup must call it.
+template <int NT>
+__device__ __forceinline__ void f3d_block_scan(int v, int* lds, int& ex, int& tot) {
+    const int t = threadIdx.x;
+    lds[t] = v;
+    __syncthreads();
+    for (int d = 1; d < NT; d <<= 1) {
+        const int x = t >= d ? lds[t - d] : 0;
+        __syncthreads();
+        lds[t] += x;
+        __syncthreads();
+    }
+    ex = lds[t] - v;
+    tot = lds[NT - 1];
+    __syncthreads();
+}
+
+// One level of an ordered FIFO flood run by one workgroup of NT threads (f3d_color.hip, f3d_refine.hip).  `list[0..cnt)` are the
+// level's expanding points in queue order.  A child's key is (position of its discoverer in `list` << 32 | position in the
+// discoverer's row); the smallest key over all discoverers is the reference's FIFO position.  best[j] = ~0 between levels.
+__device__ __forceinline__ unsigned long long f3d_child_key(int expander, int64_t row_pos) {
+    return (unsigned long long)expander << 32 | (unsigned long long)row_pos;
+}
+
+// expand: every neighbour j with open(j) keeps its smallest key; a neighbour outside [0, n) sets `errbit`.  The caller
+// synchronises the workgroup before f3d_flood_place.
+template <int NT, typename Open>
+__device__ __forceinline__ void f3d_flood_expand(const int32_t* list, int cnt, const int64_t* __restrict__ offs,
+                                                 const int32_t* __restrict__ nbrs, int64_t n, unsigned long long* best, int* err, int errbit,
+                                                 Open open) {
+    for (int i = threadIdx.x; i < cnt; i += NT) {
+        const int64_t v = list[i];
+        const int64_t e0 = offs[v], e1 = offs[v + 1];
+        for (int64_t e = e0; e < e1; ++e) {
+            const int64_t j = nbrs[e];
+            if (j < 0 || j >= n) { atomicOr(err, errbit); continue; }
+            if (!open(j)) continue;
+            atomicMin(best + j, f3d_child_key(i, e - e0));
+        }
+    }
+}
+
+// place: the children in key order into qn (a block scan of the per-expander counts, NT expanders at a time); mark(j) records
+// that j is enqueued, best[j] is reset.  Every thread of the workgroup must call it.  -> the number of children
+template <int NT, typename Mark>
+__device__ __forceinline__ int f3d_flood_place(const int32_t* list, int cnt, const int64_t* __restrict__ offs,
+                                               const int32_t* __restrict__ nbrs, int64_t n, unsigned long long* best, int32_t* qn, int* lds,
+                                               Mark mark) {
+    const int t = threadIdx.x;
+    int carry = 0;
+    for (int b = 0; b < cnt; b += NT) {
+        const int i = b + t;
+        int c = 0;
+        int64_t e0 = 0, e1 = 0;
+        if (i < cnt) {
+            const int64_t v = list[i];
+            e0 = offs[v]; e1 = offs[v + 1];
+            for (int64_t e = e0; e < e1; ++e) {
+                const int64_t j = nbrs[e];
+                if (j < 0 || j >= n) continue;
+                if (best[j] == f3d_child_key(i, e - e0)) ++c;
+            }
+        }
+        int ex, tot;
+        f3d_block_scan<NT>(c, lds, ex, tot);
+        if (i < cnt) {
+            int pos = carry + ex;
+            for (int64_t e = e0; e < e1; ++e) {
+                const int64_t j = nbrs[e];
+                if (j < 0 || j >= n) continue;
+                if (best[j] != f3d_child_key(i, e - e0)) continue;
+                qn[pos++] = (int32_t)j;
+                mark(j);
+                best[j] = ~0ull;
+            }
+        }
+        carry += tot;
+    }
+    return carry;
+}
 
 struct f3d_cellgrid {                      // device-resident description of the cell-sort grid
     double lo[3];
@@ -163,6 +246,23 @@ size_t f3d_color_scratch_bytes(int64_t n);
 hipError_t f3d_launch_color_segment(const void* colors, int dtype, int64_t n, const int64_t* offs, const int32_t* nbrs, int64_t* ids,
                                     const int64_t* seeds, int64_t nseeds, const f3d_color_args& a, void* scratch, int64_t* stats_dev, int* err,
                                     hipStream_t s);
+// region growing of segUtils/refinement.py (f3d_refine.hip): one workgroup, one flood.  values [n, nchan] of `dtype`; seeds device
+// [nseeds] = the first queue; cluster device int64 [n] receives the accepted points in acceptance order, *count_dev their number.
+// scratch: f3d_grow_scratch_bytes(n)
+struct f3d_grow_args {
+    double thr[3];
+    double sma0[3];                        // running mean at the start (exactly representable in the values' dtype)
+    int64_t npts0;                         // points the mean counts at the start
+    int max_level;                         // <= 0: no level limit
+    int seeds_given;                       // 1: the seeds are tested and expanded but neither accepted nor averaged in
+};
+#define F3D_GROW_MAX_POINTS (0x7fffffffLL - 2048)   // the kernel's int chunk counters step by 1024 past a level's length
+size_t f3d_grow_scratch_bytes(int64_t n);
+hipError_t f3d_launch_region_grow(const void* values, int dtype, int nchan, int64_t n, const int64_t* offs, const int32_t* nbrs,
+                                  const int64_t* seeds, int64_t nseeds, const f3d_grow_args& a, void* scratch, int64_t* cluster,
+                                  int64_t* count_dev, int* err, hipStream_t s);
+// out[i] = |((x - px) * nx + (y - py) * ny) + (z - pz) * nz| (f3d_refine.hip), float64 points [n, 3]
+hipError_t f3d_launch_plane_distance(const double* pts, int64_t n, const double pp[3], const double nr[3], double* out, hipStream_t s);
 // radius graph (f3d_graph.hip): KDTree.query_radius(points, r) as CSR.  bbox partials -> host picks the grid -> count pass
 // (offsets[n + 1], exclusive scan) -> fill pass; `scratch` (f3d_graph_scratch_bytes) carries the grid between the passes
 size_t f3d_graph_bbox_bytes(void);

@@ -137,6 +137,11 @@ def library():
         'f3d_color_segment': (i32, [vp, vp, i32, i64, vp, vp, vp, vp, i64, vp, vp, i32, i32, vp]),
         'f3d_color_segment_dev': (i32, [vp, vp, i32, i64, vp, vp, vp, vp, i64, vp, vp, i32, i32, vp, vp]),
         'f3d_ctx_reserve_cvseg': (i32, [vp, i64]),
+        'f3d_region_grow': (i32, [vp, vp, i32, i32, i64, vp, vp, vp, i64, vp, i64, i32, vp, i32, vp, vp]),
+        'f3d_region_grow_dev': (i32, [vp, vp, i32, i32, i64, vp, vp, vp, i64, vp, i64, i32, vp, i32, vp, vp, vp]),
+        'f3d_plane_distance': (i32, [vp, vp, i64, vp, vp, vp]),
+        'f3d_plane_distance_dev': (i32, [vp, vp, i64, vp, vp, vp, vp]),
+        'f3d_ctx_reserve_refine': (i32, [vp, i64]),
         'f3d_door_window_quads': (i32, [vp, vp, i64, vp, vp, i32, vp, i64, vp, i64, vp, vp, vp, vp]),
         'f3d_door_window_quads_dev': (i32, [vp, vp, i64, vp, vp, i32, vp, i64, vp, i64, vp, vp, vp, vp, vp]),
         'f3d_ctx_reserve_quads': (i32, [vp, i64, i32, i64]),
@@ -273,6 +278,16 @@ def _threshold3(threshold):
     return np.ascontiguousarray(np.broadcast_to(t, (3,)) if t.ndim == 0 else t.reshape(3))
 
 
+def _grow_params(nchan, sma0, threshold):
+    """region_grow's running mean at the start and its threshold as float64 [nchan] (a scalar threshold is repeated)."""
+    sma = np.ascontiguousarray(np.asarray(sma0, dtype=np.float64).reshape(-1))
+    thr = np.asarray(threshold, dtype=np.float64)
+    thr = np.ascontiguousarray(np.broadcast_to(thr, (nchan,)) if thr.ndim == 0 else thr.reshape(-1))
+    if len(sma) != nchan or len(thr) != nchan:
+        raise ValueError(f'region_grow: sma0 and threshold must have {nchan} entries')
+    return sma, thr
+
+
 class Context:
     """One f3d_ctx (device ordinal, stream, scratch arena).  Not thread-safe."""
 
@@ -316,6 +331,10 @@ class Context:
     def reserve_quads(self, n, k, ntriangles):
         """Size the scratch of door_window_quads for n points, k instances and that many triangles."""
         self._check(self._lib.f3d_ctx_reserve_quads(self._h, int(n), int(k), int(ntriangles)))
+
+    def reserve_refine(self, n):
+        """Size the scratch of region_grow_dev for clouds of up to n points."""
+        self._check(self._lib.f3d_ctx_reserve_refine(self._h, int(n)))
 
     def set_strict(self, strict=True):
         self._check(self._lib.f3d_ctx_set_strict(self._h, int(bool(strict))))
@@ -591,6 +610,39 @@ class Context:
                                                 _ptr(ids), _ptr(sd), len(sd), _ptr(thr), _ptr(neu), len(neu), int(max_level), _ptr(acc)))
         return ids, int(acc[0])
 
+    def region_grow(self, values, offsets, neighbours, seeds, sma0, npts0, threshold, max_level, seeds_given=False):
+        """Region growing of segUtils/refinement.py (include/f3d.h f3d_region_grow): values float64 [n] / [n, 1], or float64 / float32
+        [n, 3]; seeds = the first queue, distinct.  -> the accepted points int64 [count], in acceptance order."""
+        val = np.asarray(values)
+        if val.dtype not in (np.float64, np.float32):
+            raise TypeError(f'region_grow: values must be float64 or float32, got {val.dtype}')
+        val = np.ascontiguousarray(val)
+        n = len(val)
+        nchan = 1 if val.ndim == 1 else val.shape[1] if val.ndim == 2 else 0
+        if nchan not in (1, 3) or (nchan == 1 and val.dtype != np.float64):
+            raise ValueError(f'region_grow: values must be float64 [n] or float64 / float32 [n, 3], got {val.dtype} {val.shape}')
+        offs = np.ascontiguousarray(offsets, dtype=np.int64)
+        nb = np.ascontiguousarray(neighbours, dtype=np.int32)
+        if len(offs) != n + 1 or (n and offs[-1] != len(nb)):
+            raise ValueError('offsets must have n+1 entries ending at len(neighbours)')
+        sd = np.ascontiguousarray(np.asarray(seeds).reshape(-1), dtype=np.int64)
+        sma, thr = _grow_params(nchan, sma0, threshold)
+        cluster, count = np.empty(n, np.int64), np.zeros(1, np.int64)
+        self._check(self._lib.f3d_region_grow(self._h, _ptr(val), F32 if val.dtype == np.float32 else F64, nchan, n, _ptr(offs), _ptr(nb),
+                                              _ptr(sd), len(sd), _ptr(sma), int(npts0), int(bool(seeds_given)), _ptr(thr), int(max_level),
+                                              _ptr(cluster), _ptr(count)))
+        return cluster[:int(count[0])].copy()
+
+    def plane_distance(self, points, plane_point, normal):
+        """|((x - px) nx + (y - py) ny) + (z - pz) nz| of float64 points [n, 3] -> float64 [n]."""
+        pts = _f64(points)
+        if pts.ndim != 2 or pts.shape[1] != 3:
+            raise ValueError(f'plane_distance: points must be [N, 3], got {pts.shape}')
+        pp, nr = _f64(np.asarray(plane_point).reshape(-1), (3,)), _f64(np.asarray(normal).reshape(-1), (3,))
+        out = np.empty(len(pts))
+        self._check(self._lib.f3d_plane_distance(self._h, _ptr(pts), len(pts), _ptr(pp), _ptr(nr), _ptr(out)))
+        return out
+
     def door_window_quads(self, points, ids, instance_ids, vertices, triangles):
         """Door / window quads of door_window_bbox.generate_mesh (include/f3d.h f3d_door_window_quads) for the distinct ids
         `instance_ids`.  -> (quads float64 [k, 4, 3], status int32 [k] (QUAD_*), chosen triangle int32 [k], triangle normals
@@ -794,6 +846,20 @@ class Context:
         neu = np.ascontiguousarray(np.asarray(list(neutral_ids)).reshape(-1), dtype=np.int64)
         self._check(self._lib.f3d_color_segment_dev(self._h, colors_ptr, int(dtype), int(n), offsets_ptr, neighbours_ptr, ids_ptr, seeds_ptr,
                                                     int(nseeds), _ptr(thr), _ptr(neu), len(neu), int(max_level), accepted_ptr, stream))
+
+    def region_grow_dev(self, values_ptr, dtype, nchan, n, offsets_ptr, neighbours_ptr, seeds_ptr, nseeds, sma0, npts0, threshold, max_level,
+                        cluster_ptr, count_ptr, seeds_given=False, stream=None):
+        """f3d_region_grow_dev: cluster int64 [n] and count int64 [1] on the device; enqueue only; an index error is recorded for
+        take_device_error."""
+        sma, thr = _grow_params(int(nchan), sma0, threshold)
+        self._check(self._lib.f3d_region_grow_dev(self._h, values_ptr, int(dtype), int(nchan), int(n), offsets_ptr, neighbours_ptr, seeds_ptr,
+                                                  int(nseeds), _ptr(sma), int(npts0), int(bool(seeds_given)), _ptr(thr), int(max_level),
+                                                  cluster_ptr, count_ptr, stream))
+
+    def plane_distance_dev(self, points_ptr, n, plane_point, normal, out_ptr, stream=None):
+        """f3d_plane_distance_dev: float64 points [n, 3] and out [n] on the device; enqueue only."""
+        pp, nr = _f64(np.asarray(plane_point).reshape(-1), (3,)), _f64(np.asarray(normal).reshape(-1), (3,))
+        self._check(self._lib.f3d_plane_distance_dev(self._h, points_ptr, int(n), _ptr(pp), _ptr(nr), out_ptr, stream))
 
     def door_window_quads_dev(self, points_ptr, n, ids_ptr, instance_ids_ptr, k, vertices_ptr, nvertices, triangles_ptr, ntriangles, quads_ptr,
                               status_ptr, tri_ptr, normals_ptr=None, stream=None):

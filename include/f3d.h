@@ -441,6 +441,39 @@ int f3d_color_segment_dev(f3d_ctx* ctx, const void* colors, f3d_dtype dtype, int
 /* Sizes the scratch of both for clouds of up to n points: later _dev calls of a strict context do not allocate. */
 int f3d_ctx_reserve_cvseg(f3d_ctx* ctx, int64_t n);
 
+/* ---- segUtils/refinement.py: region growing of a picked instance (refinement.py:70-400) ------------------------------ */
+/* One FIFO flood over the adjacency with a running mean `sma` carried over the whole flood.  The first queue is
+ * seeds[0..nseeds) in the given order (level 1), distinct.  A popped entry at level == max_level (max_level <= 0 = no
+ * limit), or with |sma - value| > threshold in any channel (compared in float64), is skipped.  Any other entry expands:
+ * its neighbours that were never enqueued are enqueued in row order at level + 1.  It is also accepted, unless
+ * seeds_given != 0 and it is one of the seeds: npts += 1, sma = sma + (value - sma) / npts in the values' dtype, and the
+ * point is appended to `cluster`.  sma starts as sma0 (HOST double [nchan], exactly representable in the values' dtype)
+ * and npts as npts0.  This covers the reference's four floods:
+ *   floodfill_depth_points / floodfill_color_points : seeds = the instance, sma0 = their average, npts0 = nseeds, given
+ *   floodfill_depth_point                           : seeds = the picked list, sma0 = their average, npts0 = nseeds
+ *   floodfill_color_point                           : one seed, sma0 = its colour, npts0 = 0
+ * values: [n, nchan], nchan = 1 (F3D_F64) or 3 (F3D_F64 or F3D_F32); threshold: HOST double [nchan]; adjacency as for
+ * f3d_flood_order (rows without duplicate entries).  cluster: int64 [n], the accepted points in acceptance order;
+ * *count their number.  A seed or neighbour index outside [0, n), or a seed listed twice -> F3D_ERR_INDEX (count = 0).
+ * n <= 2^31 - 2049.  The _dev twin: values, offsets, neighbours, seeds, cluster and count_dev (device int64) on the device;
+ * enqueues on `stream`; an error is recorded for f3d_take_device_error.  Scratch: f3d_ctx_reserve_refine(). */
+int f3d_region_grow(f3d_ctx* ctx, const void* values, f3d_dtype dtype, int nchan, int64_t n, const int64_t* offsets,
+                    const int32_t* neighbours, const int64_t* seeds, int64_t nseeds, const double* sma0, int64_t npts0,
+                    int seeds_given, const double* threshold, int max_level, int64_t* cluster, int64_t* count);
+int f3d_region_grow_dev(f3d_ctx* ctx, const void* values, f3d_dtype dtype, int nchan, int64_t n, const int64_t* offsets,
+                        const int32_t* neighbours, const int64_t* seeds, int64_t nseeds, const double* sma0, int64_t npts0,
+                        int seeds_given, const double* threshold, int max_level, int64_t* cluster, int64_t* count_dev,
+                        void* stream);
+/* out[i] = |((x - px) * nx + (y - py) * ny) + (z - pz) * nz|: distance of float64 points [n, 3] to the plane through
+ * plane_point with unit normal `normal` (both HOST double [3]); no contraction.  The reference's einsum
+ * (refinement.py:155-157) sums in another order, so the two agree to rounding, not bit for bit. */
+int f3d_plane_distance(f3d_ctx* ctx, const double* points, int64_t n, const double plane_point[3], const double normal[3],
+                       double* out);
+int f3d_plane_distance_dev(f3d_ctx* ctx, const double* points, int64_t n, const double plane_point[3], const double normal[3],
+                           double* out, void* stream);
+/* Sizes the scratch of f3d_region_grow_dev for clouds of up to n points: later calls of a strict context do not allocate. */
+int f3d_ctx_reserve_refine(f3d_ctx* ctx, int64_t n);
+
 /* ---- door_window_bbox.generate_mesh: door / window quads on the mesh (segUtils/door_window_bbox.py:65-150) ---------- */
 /* For every wanted instance id inst[s], box_pts = points[ids == inst[s]] in ascending point index, and against the triangles
  * tris int64 [nt, 3] of verts float64 [nv, 3] (a negative vertex index counts from the end, as in NumPy):
