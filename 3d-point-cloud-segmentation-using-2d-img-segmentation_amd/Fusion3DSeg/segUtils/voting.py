@@ -1,11 +1,13 @@
-"""Drop-in for the reference's Fusion3DSeg/segUtils/voting.py (class VotingSegmentation).
+"""Drop-in for the reference's Fusion3DSeg/segUtils/voting.py (classes VotingSegmentation and PointVotingSegmentation).
 
 Same constructor, attributes, methods, return types and quirks (reference file:line in each
-method); the scatter vote and the segmentation run as HIP kernels (f3d_vote_uv2pt*, f3d_segment_votes*).
+method); the scatter vote and the segmentation run as HIP kernels (f3d_vote_uv2pt*, f3d_segment_votes*), and so does
+the radius search fused with the frame vote of PointVotingSegmentation (f3d_point_vote_frames*).
 The vote matrix stays on the GPU for the whole ``vote()`` loop and is downloaded once.
 OpenCV is optional: masks are read with cv2 when it is importable, else with Pillow, and the
 nearest-neighbour resize is done here (same index rule as cv2.INTER_NEAREST).
 """
+import os
 from pathlib import Path
 
 import numpy as np
@@ -202,3 +204,204 @@ class _DeviceVotes:
         if check:
             self.ctx.take_device_error(self.stream.cuda_stream)     # IndexError for the first bad frame, if any
         return self.t.cpu().numpy()
+
+
+class PointVotingSegmentation:
+    """Framewise voting of ANY [M, 3] cloud from the frames' world-space depth points and masks (reference voting.py:140-299,
+    marked deprecated there for the host cost of one KDTree.query_radius of h*w points per frame).
+
+    Per frame every pixel pairs with every cloud point within ``radius`` of its depth point (float64 squared distance
+    ``(dx*dx + dy*dy) + dz*dz <= radius*radius``, inclusive), then ``votes[i, mask[q]] += 1`` and ``votes[i, -1] += 1`` over
+    all pairs with NumPy's buffered rule: each distinct cell gets +1 per frame however many pairs hit it.  So a point can
+    receive several labels from one frame, and the last column counts the frames that saw the point.
+
+    Column collision: ``votes`` has ``nclasses + 1`` columns and the last one is that total, so a mask label equal to
+    ``nclasses`` (the 2-D stage's "low confidence" label 133 when nclasses = 133) is a legal index that lands on the total
+    column: a point a frame sees with that label gets +2 there from that frame.  A label > nclasses raises IndexError, but
+    only when its pixel has at least one neighbour; non-finite depth points raise ValueError (sklearn's); both leave the
+    earlier frames applied.  No pixel is skipped: a dropout pixel sits at its camera centre and votes like any other.
+    """
+
+    def __init__(self, tofcameradata, sparse_points, depth_hw, maskdir, nclasses, prefix='', extension='png', zfill=2,
+                 votes_file=None):
+        self._dev_votes = None
+        self._cloud_dev = None
+        if votes_file is None:
+            self.nclasses = nclasses
+            self.depth_hw = depth_hw
+            self.tofcameradata = tofcameradata
+            cloud = np.asarray(sparse_points)
+            if cloud.ndim != 2 or cloud.shape[0] == 0:
+                raise ValueError(f'sparse_points must be a non-empty [M, 3] array, got {cloud.shape}')    # sklearn's KDTree raises too
+            self._cloud = np.ascontiguousarray(cloud if cloud.dtype == np.float32 else cloud.astype(np.float64))
+            if not np.isfinite(self._cloud).all():
+                raise ValueError('sparse_points contains NaN or infinity')                               # (reference :173, sklearn)
+            if len(self._cloud) >= 1 << 31:
+                raise ValueError('sparse_points must hold fewer than 2^31 points')
+            self._ctx = f3d.default_context()                   # F3DUnavailable without a library or a device: no CPU fallback
+            self.votes = np.zeros((len(self._cloud), nclasses + 1))
+            self.maskdir = maskdir
+            self.prefix = prefix
+            self.ext = extension
+            self.zfill = zfill
+        else:                                                   # (reference :181-182; the column count minus the total)
+            self.votes = np.load(votes_file)
+            self.nclasses = self.votes.shape[1] - 1
+
+    # the vote matrix lives where it was last written: vote_frames leaves it on the device, reading ``votes`` brings it back
+    @property
+    def votes(self):
+        if self._dev_votes is not None:
+            self._host_votes = self._dev_votes.cpu().numpy()    # (synchronises with the stream the votes were enqueued on)
+            self._dev_votes = None
+        return self._host_votes
+
+    @votes.setter
+    def votes(self, value):
+        self._host_votes, self._dev_votes = value, None
+
+    def zero(self):
+        self.votes = np.zeros_like(self.votes)
+
+    @classmethod
+    def read_mask(cls, name, dirname='./', prefix='', extension='png', zfill=0):
+        """dirname/prefix + name.zfill(zfill) + '.' + extension as a grey image, None when the file is absent (reference :190-206)."""
+        filename = os.path.join(dirname, prefix + str(name).zfill(zfill) + '.' + extension)
+        return _imread_gray(filename) if os.path.isfile(filename) else None
+
+    def get_nns(self, query_points, radius=0.01):
+        """(int32 cloud indices of all queries, flattened; per-query counts) (reference :208-222).  A query's indices ascend
+        (sklearn's order inside a row is its tree traversal's, which it does not specify)."""
+        offs, nbrs = self._ctx.radius_query(self._cloud, query_points, radius)
+        return nbrs, np.diff(offs)
+
+    def _torch(self):
+        try:
+            import torch
+        except ImportError:
+            return None
+        return torch if torch.cuda.is_available() else None
+
+    def _device_state(self, torch):
+        """The cloud and the vote matrix as device tensors (uploaded when the host copy is the current one)."""
+        dev = torch.device('cuda', self._ctx.device)
+        if self._cloud_dev is None:
+            self._cloud_dev = torch.from_numpy(self._cloud).to(dev)
+        if self._dev_votes is None:
+            self._dev_votes = torch.from_numpy(np.ascontiguousarray(self._host_votes, dtype=np.float64)).to(dev)
+        return dev, self._cloud_dev, self._dev_votes
+
+    def vote_frames(self, points, masks, radius=0.01, check=True):
+        """The vote of F frames that are already on the device: ``points`` [F, hw, 3] float64 / float32 (what
+        RTAB_utils.ios_rtab.frames_world_dev returns), ``masks`` uint8 [F, hw] or [F, h, w] at the depth resolution (what
+        get2DSeg.masks_to_device returns).  No host copy, no file; the vote matrix stays on the device (returned as a float64
+        tensor [M, nclasses + 1]; ``self.votes`` downloads it).  Runs on a side stream ordered both ways with torch's current
+        stream.  ``check`` (synchronises): raise the IndexError of a label > nclasses now instead of leaving it to
+        ``f3d.Context.take_device_error``; the ValueError of non-finite points is always raised here."""
+        torch = self._torch()
+        if torch is None:
+            raise f3d.F3DUnavailable('vote_frames needs a HIP device (there is no CPU fallback)')
+        dev, cloud, votes = self._device_state(torch)
+        if not (isinstance(points, torch.Tensor) and isinstance(masks, torch.Tensor) and points.is_cuda and masks.is_cuda):
+            raise ValueError('vote_frames takes device tensors (vote() reads frames from the host)')
+        if points.dim() != 3 or points.shape[2] != 3 or points.dtype not in (torch.float64, torch.float32):
+            raise ValueError(f'points must be float64 / float32 [F, hw, 3], got {points.dtype} {tuple(points.shape)}')
+        F, hw = int(points.shape[0]), int(points.shape[1])
+        if masks.dtype != torch.uint8 or masks.shape[0] != F or masks.numel() != F * hw:
+            raise ValueError(f'masks must be uint8 [F, hw], got {masks.dtype} {tuple(masks.shape)} for {F} frames of {hw} pixels')
+        points, masks = points.to(dev).contiguous(), masks.to(dev).contiguous()
+        side = torch.cuda.Stream(dev)
+        side.wait_stream(torch.cuda.current_stream(dev))
+        try:
+            self._ctx.point_vote_frames_dev(cloud.data_ptr(), f3d.F32 if cloud.dtype == torch.float32 else f3d.F64, cloud.shape[0],
+                                            points.data_ptr(), f3d.F32 if points.dtype == torch.float32 else f3d.F64, masks.data_ptr(), F, hw,
+                                            radius, votes.data_ptr(), votes.shape[1], side.cuda_stream)
+        finally:
+            torch.cuda.current_stream(dev).wait_stream(side)
+            for x in (cloud, points, masks, votes):
+                x.record_stream(side)
+        if check:
+            self._ctx.take_device_error(side.cuda_stream)
+        return votes
+
+    def vote(self, frame_numbers=None, skip=1, radius=0.01, resize=True, filename=None, verbose=False):
+        """Accumulate the votes of ``frame_numbers[::skip]`` (reference :224-265); returns float64 [M, nclasses + 1].
+
+        A frame whose mask file is absent is skipped silently.  Frames are read on the host and handed to the GPU in bounded
+        batches (one upload and one fused search + vote per batch); the vote matrix stays on the device across the loop.
+        """
+        h, w = self.depth_hw
+        frame_numbers = np.arange(len(self.tofcameradata)) if frame_numbers is None else frame_numbers
+        total = len(frame_numbers) // skip
+        torch = self._torch()
+        if verbose:
+            print('Framewise voting ... ')
+        batch_q, batch_m, error = [], [], None
+
+        def flush():
+            nonlocal batch_q, batch_m
+            if not batch_q:
+                return
+            q, m = np.stack(batch_q), np.stack(batch_m)
+            batch_q, batch_m = [], []
+            if torch is None:
+                host = np.ascontiguousarray(self._host_votes, dtype=np.float64)
+                self._host_votes = host
+                self._ctx.point_vote_frames(host, self._cloud, q, m, radius)     # (the votes are copied back on an error as well)
+                return
+            dev = torch.device('cuda', self._ctx.device)
+            self.vote_frames(torch.from_numpy(q).to(dev), torch.from_numpy(m).to(dev), radius, check=False)
+
+        for i, idx in enumerate(frame_numbers[::skip]):
+            data = self.tofcameradata[idx]
+            if verbose:
+                print(f'frame/total = {i + 1}/{total}, progress = {((i + 1) * 100 / total):.3}%')
+            query = np.asarray(data['modPoints'])
+            fnum = int(data['frameNumber'])
+            mask = self.read_mask(fnum, self.maskdir, self.prefix, self.ext, self.zfill)
+            if mask is None:
+                continue
+            mask = resize_nearest(mask, w, h) if resize else mask
+            mask = np.ascontiguousarray(mask, dtype=np.uint8).reshape(-1)
+            query = np.ascontiguousarray(query if query.dtype == np.float32 else query.astype(np.float64)).reshape(-1, 3)
+            try:
+                if len(query) != len(mask):                       # np.repeat(mask, frequency) raises at this frame (reference :257)
+                    flush()
+                    raise ValueError(f'operands could not be broadcast together: {len(mask)} mask pixels, {len(query)} query points')
+                if batch_q and (batch_q[0].shape != query.shape or batch_q[0].dtype != query.dtype):
+                    flush()                                       # a frame of another size or type starts a batch of its own
+                batch_q.append(query); batch_m.append(mask)
+                if len(batch_q) * len(query) >= 1 << 22:          # ~100 MB of float64 points: bound the host staging memory
+                    flush()
+            except (ValueError, IndexError) as exc:               # earlier frames stay applied, later ones never run
+                error = exc
+                break
+        try:
+            if error is None:
+                flush()
+        except (ValueError, IndexError) as exc:
+            error = exc
+        votes = self.votes                                        # (the download waits for every batch)
+        if torch is not None:
+            try:                                                  # an IndexError recorded on the device precedes a later ValueError
+                self._ctx.take_device_error(None)
+            except IndexError as exc:
+                error = exc
+        if error is not None:
+            raise error
+        if filename is not None:
+            if verbose:
+                print('writing file ... ')
+            os.makedirs(os.path.dirname(filename), exist_ok=True)
+            np.save(filename, votes)
+        return votes
+
+    def segment(self, threshold, filter_classes=None, votes=None):
+        """Per-point class from the votes (reference :267-299) -> int64 [M].
+
+        As VotingSegmentation.segment (first-maximum argmax, ``nclasses`` for no votes, for max/total < threshold and for a
+        zero maximum, the sequential index->class remap with its aliasing, quirk Q3), except that the total is the LAST
+        COLUMN, not the row sum, and the unfiltered candidates are ``votes[:, :-1]``.
+        """
+        votes = self.votes if votes is None else votes
+        return f3d.default_context().segment_votes_lastcol(votes, self.nclasses, threshold, filter_classes)

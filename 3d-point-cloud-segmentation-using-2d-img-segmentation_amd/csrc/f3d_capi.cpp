@@ -27,7 +27,7 @@ enum { SLOT_XYZ = 0, SLOT_OUT0, SLOT_OUT1, SLOT_VIEWS, SLOT_MASKS, SLOT_AUX0, SL
        SLOT_GRP_ORDER, SLOT_GRP_KEYS, SLOT_GRP_STARTS, SLOT_GRP_SCRATCH, SLOT_OBB_TABLE, SLOT_OBB_FACETS, SLOT_OBB_CAND, SLOT_FUSE_TABLES, SLOT_FUSE_CARRY, SLOT_FUSE_XYZ, SLOT_FUSION, SLOT_PATCH_STATUS, SLOT_NRM, SLOT_NRM_CAMS,
        SLOT_QRY, SLOT_QRY_IN, SLOT_QRY_OFFS,
        SLOT_FLOOD, SLOT_COLOR, SLOT_CVS_INST, SLOT_CVS_ORDER, SLOT_CVS_COFFS, SLOT_CVS_FLAGS, SLOT_CVS_SEEDS, SLOT_CVS_STATS,
-       SLOT_QUADS, SLOT_QUADS_OUT, SLOT_GROW, SLOT_COUNT };
+       SLOT_QUADS, SLOT_QUADS_OUT, SLOT_GROW, SLOT_PVOTE, SLOT_PVOTE_BITS, SLOT_COUNT };
 
 thread_local char g_create_err[512] = "";
 
@@ -63,6 +63,10 @@ struct f3d_ctx {
     int64_t qry_m, qry_n;
     int qry_qdtype;
     const void* qry_queries;
+    // point vote: device int[4] of the call being enqueued (f3d_kernels.h); pv_partial: the last call stopped at a frame with
+    // non-finite queries after applying the frames before it (the host-pointer entry still copies the votes back)
+    int* pv_words;
+    int pv_partial;
     // instance grouping of the last f3d_group_by_id call (host-pointer sequence group -> extremes -> hull filter)
     int64_t grp_n, grp_nids;
     int grp_dtype;
@@ -164,6 +168,8 @@ int take_error(f3d_ctx* ctx, hipStream_t s, int mask = F3D_DEVERR_ALL) {
             return fail(ctx, F3D_ERR_INDEX, "region_grow: seed or neighbour index out of bounds, or a seed listed twice");
         if (e & F3D_DEVERR_QUADS)
             return fail(ctx, F3D_ERR_INDEX, "door_window_quads: a triangle's vertex index is out of bounds");
+        if (e & F3D_DEVERR_PVOTE)
+            return fail(ctx, F3D_ERR_INDEX, "point_vote_frames: a mask label exceeds nclasses on a pixel that has a neighbour (the reference raises IndexError at voting.py:257)");
     }
     return F3D_OK;
 }
@@ -317,6 +323,7 @@ f3d_ctx* f3d_ctx_create(int device) {
               hipMalloc((void**)&ctx->count_dev, sizeof(unsigned long long)) == hipSuccess &&
               hipMalloc((void**)&ctx->codebook, sizeof(f3d_codebook)) == hipSuccess &&
               hipMalloc((void**)&ctx->first_bad, sizeof(int)) == hipSuccess &&
+              hipMalloc((void**)&ctx->pv_words, 4 * sizeof(int)) == hipSuccess &&
               hipMemset(ctx->dev_err, 0, sizeof(int)) == hipSuccess &&
               hipMemset(ctx->codebook, 0, sizeof(f3d_codebook)) == hipSuccess;       // (the presence set is kept zero between calls)
     if (!ok) {
@@ -338,6 +345,7 @@ void f3d_ctx_destroy(f3d_ctx* ctx) {
     if (ctx->count_dev) (void)hipFree(ctx->count_dev);
     if (ctx->codebook) (void)hipFree(ctx->codebook);
     if (ctx->first_bad) (void)hipFree(ctx->first_bad);
+    if (ctx->pv_words) (void)hipFree(ctx->pv_words);
     if (ctx->stream) (void)hipStreamDestroy(ctx->stream);
     free(ctx);
 }
@@ -950,6 +958,33 @@ int f3d_segment_votes(f3d_ctx* ctx, const double* votes, int64_t npts, int ncols
     const double* dvotes = st.in(SLOT_OUT1, votes, (size_t)npts * ncols * 8);
     int64_t* dcls = st.out(SLOT_OUT0, classes, (size_t)npts * 8);
     if (!st.rc) st.rc = f3d_segment_votes_dev(ctx, dvotes, npts, ncols, nclasses, threshold, filter, nfilter, dcls, ctx->stream);
+    return st.finish();
+}
+
+int f3d_segment_votes_lastcol_dev(f3d_ctx* ctx, const double* votes, int64_t npts, int ncols, int nclasses, double threshold,
+                                  const int32_t* filter, int nfilter, int64_t* classes, void* stream) {
+    int rc = enter(ctx); if (rc) return rc;
+    if (npts < 0 || ncols <= 0 || (npts > 0 && (!votes || !classes))) return fail(ctx, F3D_ERR_INVALID, "segment_votes_lastcol: bad arguments");
+    if (ncols < 2 && nfilter == 0 && npts > 0)                 // votes[:, :-1] has no column: NumPy's argmax raises ValueError
+        return fail(ctx, F3D_ERR_INVALID, "segment_votes_lastcol: attempt to get argmax of an empty sequence");
+    hipStream_t s = pick(ctx, stream);
+    f3d_filter_args fa;
+    if ((rc = make_filter(ctx, filter, nfilter, ncols, true, s, &fa))) return rc;
+    f3d_negmask neg = {};
+    for (int k = 0; k < fa.nfilter; ++k) if (filter[k] < 0) neg.w[k >> 5] |= 1u << (k & 31);
+    F3D_HIP(ctx, f3d_launch_segment_votes_lastcol(votes, npts, ncols, nclasses, threshold, fa, neg, classes, s));
+    return F3D_OK;
+}
+
+int f3d_segment_votes_lastcol(f3d_ctx* ctx, const double* votes, int64_t npts, int ncols, int nclasses, double threshold,
+                              const int32_t* filter, int nfilter, int64_t* classes) {
+    int rc = enter(ctx); if (rc) return rc;
+    if (npts < 0 || ncols <= 0 || (npts > 0 && (!votes || !classes))) return fail(ctx, F3D_ERR_INVALID, "segment_votes_lastcol: bad arguments");
+    if (npts == 0) return F3D_OK;
+    staging st(ctx);
+    const double* dvotes = st.in(SLOT_OUT1, votes, (size_t)npts * ncols * 8);
+    int64_t* dcls = st.out(SLOT_OUT0, classes, (size_t)npts * 8);
+    if (!st.rc) st.rc = f3d_segment_votes_lastcol_dev(ctx, dvotes, npts, ncols, nclasses, threshold, filter, nfilter, dcls, ctx->stream);
     return st.finish();
 }
 
@@ -1801,6 +1836,106 @@ int f3d_radius_query_fill(f3d_ctx* ctx, int64_t n, int32_t* nbrs) {
     int32_t* dnb = st.out(SLOT_MASKS, nbrs, (size_t)nnz * 4);
     if (!st.rc) st.rc = f3d_radius_query_fill_dev(ctx, ctx->qry_queries, (f3d_dtype)ctx->qry_qdtype, n, doffs, dnb, s);
     return st.finish();
+}
+
+// ---------------------------------------------------------------------------------------------
+// PointVotingSegmentation.vote: radius search of the frame pixels in a cloud fused with the frame vote (voting.py:224-265)
+// ---------------------------------------------------------------------------------------------
+static bool pvote_grid_fits(const double d[3]) {
+    return d[0] <= 1024.0 && d[1] <= 1024.0 && d[2] <= 1024.0 && d[0] * d[1] * d[2] <= 16777216.0;
+}
+
+int f3d_ctx_reserve_point_vote(f3d_ctx* ctx, int64_t m, int ncols) {
+    int rc = enter(ctx); if (rc) return rc;
+    if (m < 0 || m > 0x7fffffffLL || ncols <= 0) return fail(ctx, F3D_ERR_INVALID, "ctx_reserve_point_vote: bad arguments");
+    const int strict = ctx->strict;
+    ctx->strict = 0;
+    void* p;
+    rc = ensure(ctx, SLOT_GRAPH_BBOX, f3d_graph_bbox_bytes(), &p);
+    if (!rc) rc = ensure(ctx, SLOT_PVOTE, f3d_graph_scratch_bytes(m, 16777216), &p);          // (any grid the radius allows)
+    if (!rc) rc = ensure(ctx, SLOT_PVOTE_BITS, f3d_pvote_bits_bytes(m, ncols, f3d_pvote_group(m, ncols)), &p);
+    ctx->strict = strict;
+    return rc;
+}
+
+int f3d_point_vote_frames_dev(f3d_ctx* ctx, const void* cloud, f3d_dtype cdtype, int64_t m, const void* queries, f3d_dtype qdtype,
+                              const uint8_t* masks, int64_t nframes, int64_t hw, double radius, double* votes, int ncols, void* stream) {
+    int rc = enter(ctx); if (rc) return rc;
+    ctx->pv_partial = 0;
+    if (m < 0 || m > 0x7fffffffLL || nframes < 0 || nframes > 0x3fffffffLL || hw < 0 || ncols <= 0 || (m > 0 && (!cloud || !votes)) ||
+        (nframes > 0 && hw > 0 && (!queries || !masks)) || (cdtype != F3D_F64 && cdtype != F3D_F32) || (qdtype != F3D_F64 && qdtype != F3D_F32) ||
+        radius >= 1e300)
+        return fail(ctx, F3D_ERR_INVALID, "point_vote_frames: bad arguments (m < 2^31, F < 2^30, radius < 1e300)");
+    if (m == 0) return fail(ctx, F3D_ERR_INVALID, "point_vote_frames: the cloud is empty (sklearn's KDTree raises ValueError)");
+    hipStream_t s = pick(ctx, stream);
+    void* dbox;
+    if ((rc = ensure(ctx, SLOT_GRAPH_BBOX, f3d_graph_bbox_bytes(), &dbox))) return rc;
+    // one readback for the whole call: the cloud's box, and what the pre-pass saw in the masks and the queries
+    int words[4] = {0, F3D_PVOTE_NONE, F3D_PVOTE_NONE, F3D_PVOTE_NONE};
+    const bool work = nframes > 0 && hw > 0;
+    if (work) {
+        F3D_HIP(ctx, f3d_launch_pvote_prepass(queries, qdtype, masks, nframes, hw, ncols, ctx->pv_words, s));
+        F3D_HIP(ctx, hipMemcpyAsync(words, ctx->pv_words, sizeof words, hipMemcpyDeviceToHost, s));
+    }
+    double lo[3], ext[3];
+    if ((rc = cloud_bbox(ctx, cloud, cdtype, m, s, "point_vote_frames", lo, ext))) return rc;      // (synchronises)
+    if (!work) return F3D_OK;
+    const int64_t bad_query = words[1] == F3D_PVOTE_NONE ? nframes : words[1];                     // frames from here on never ran
+    // radius < 0 or NaN: no pair at all (sklearn); the grid is built for radius 0 and no distance passes r2 = -1
+    const bool none = !(radius >= 0.0);
+    f3d_graphgrid g;
+    const double cell = neighbour_cell(none ? 0.0 : radius, ext, g.dim, pvote_grid_fits);
+    for (int c = 0; c < 3; ++c) g.lo[c] = lo[c];
+    g.inv_cell = 1.0 / cell; g.pad = 0;
+    f3d_pvote_box box;                                                       // a pixel outside this box is more than one cell (> r) away
+    for (int c = 0; c < 3; ++c) { box.lo[c] = lo[c] - cell; box.hi[c] = (lo[c] + ext[c]) + cell; }
+    const double r2 = none ? -1.0 : radius * radius;
+    if (bad_query > 0) {
+        const int64_t ncells = (int64_t)g.dim[0] * g.dim[1] * g.dim[2];
+        const int group = (int)(bad_query < f3d_pvote_group(m, ncols) ? bad_query : f3d_pvote_group(m, ncols));
+        void *scratch, *bits;
+        if ((rc = ensure(ctx, SLOT_PVOTE, f3d_graph_scratch_bytes(m, ncells), &scratch))) return rc;
+        if ((rc = ensure(ctx, SLOT_PVOTE_BITS, f3d_pvote_bits_bytes(m, ncols, group), &bits))) return rc;
+        f3d_gridview gv;
+        F3D_HIP(ctx, f3d_launch_graph_grid(cloud, cdtype, m, g, scratch, &gv, s));
+        if (words[0])                                                        // the second search: only when a label > nclasses exists
+            F3D_HIP(ctx, f3d_launch_pvote_validate(queries, qdtype, masks, bad_query, hw, ncols, gv, g, box, r2, ctx->pv_words, s));
+        F3D_HIP(ctx, f3d_launch_pvote_frames(queries, qdtype, masks, bad_query, hw, m, ncols, gv, g, box, r2, votes, (uint32_t*)bits, group,
+                                             ctx->pv_words, ctx->dev_err, s));
+        if (words[0]) F3D_HIP(ctx, f3d_launch_pvote_flag(ctx->pv_words, (int)bad_query, ctx->dev_err, s));
+    }
+    if (bad_query < nframes) {
+        if (words[0] && bad_query > 0) {                                     // both offences in one call: the first offending frame decides
+            F3D_HIP(ctx, hipMemcpyAsync(words, ctx->pv_words, sizeof words, hipMemcpyDeviceToHost, s));
+            F3D_HIP(ctx, hipStreamSynchronize(s));
+            if (words[2] < bad_query) return F3D_OK;                         // the IndexError, recorded for f3d_take_device_error
+        }
+        ctx->pv_partial = 1;
+        return fail(ctx, F3D_ERR_INVALID, "point_vote_frames: the queries of frame %lld contain NaN or infinity (the frames before it are applied)",
+                    (long long)bad_query);
+    }
+    return F3D_OK;
+}
+
+int f3d_point_vote_frames(f3d_ctx* ctx, const void* cloud, f3d_dtype cdtype, int64_t m, const void* queries, f3d_dtype qdtype,
+                          const uint8_t* masks, int64_t nframes, int64_t hw, double radius, double* votes, int ncols) {
+    int rc = enter(ctx); if (rc) return rc;
+    if (m < 0 || nframes < 0 || hw < 0 || ncols <= 0 || (m > 0 && (!cloud || !votes)) || (nframes > 0 && hw > 0 && (!queries || !masks)) ||
+        (cdtype != F3D_F64 && cdtype != F3D_F32) || (qdtype != F3D_F64 && qdtype != F3D_F32))
+        return fail(ctx, F3D_ERR_INVALID, "point_vote_frames: bad arguments");
+    staging st(ctx);
+    const void* dcloud = st.in(SLOT_XYZ, cloud, xyz_bytes(cdtype, m));
+    const void* dq = st.in(SLOT_AUX0, queries, xyz_bytes(qdtype, nframes * hw));
+    const uint8_t* dmask = st.in(SLOT_AUX1, masks, (size_t)(nframes * hw));
+    double* dvotes = st.inout(SLOT_OUT1, votes, (size_t)m * ncols * 8);
+    if (st.rc) return st.rc;
+    rc = f3d_point_vote_frames_dev(ctx, dcloud, cdtype, m, dq, qdtype, dmask, nframes, hw, radius, dvotes, ncols, ctx->stream);
+    if (rc && !ctx->pv_partial) return rc;
+    char msg[512];
+    memcpy(msg, ctx->err, sizeof msg);
+    const int rc2 = st.finish(F3D_DEVERR_PVOTE, true);                       // frames before an offending one stay applied, like NumPy
+    if (rc && !rc2) memcpy(ctx->err, msg, sizeof msg);
+    return rc2 ? rc2 : rc;
 }
 
 // ---------------------------------------------------------------------------------------------

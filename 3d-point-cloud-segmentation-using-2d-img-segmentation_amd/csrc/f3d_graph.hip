@@ -186,6 +186,17 @@ static hipError_t build_grid(const void* xyz, int dtype, int64_t n, const f3d_gr
     return hipGetLastError();
 }
 
+// the grid alone, for searches that keep no CSR (f3d_pointvote.hip): scratch holds f3d_graph_scratch_bytes(n, ncells)
+hipError_t f3d_launch_graph_grid(const void* xyz, int dtype, int64_t n, const f3d_graphgrid& g, void* scratch, f3d_gridview* view,
+                                 hipStream_t s) {
+    const int64_t ncells = (int64_t)g.dim[0] * g.dim[1] * g.dim[2];
+    const size_t tb = temp_bytes_for(n);
+    const graph_layout L = layout_for(n, ncells, tb);
+    char* base = (char*)scratch;
+    view->sorted = (const double*)(base + L.sorted); view->perm = (const uint32_t*)(base + L.perm); view->cells = (const int2*)(base + L.cells);
+    return build_grid(xyz, dtype, n, g, L, tb, base, s);
+}
+
 // count pass after the grid is known: sort by cell, cell table, sorted copy, neighbour counts, exclusive scan into offsets[n + 1]
 hipError_t f3d_launch_graph_count(const void* xyz, int dtype, int64_t n, const f3d_graphgrid& g, double r2, void* scratch,
                                   int64_t* offsets, hipStream_t s) {

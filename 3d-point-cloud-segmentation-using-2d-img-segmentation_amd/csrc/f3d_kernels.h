@@ -13,7 +13,8 @@
 #define F3D_DEVERR_COLOR 16                // color_segment: neighbour or seed index out of bounds
 #define F3D_DEVERR_QUADS 32                // door_window_quads: triangle vertex index out of bounds
 #define F3D_DEVERR_GROW 64                 // region_grow: seed or neighbour index out of bounds, or a repeated seed
-#define F3D_DEVERR_ALL 127
+#define F3D_DEVERR_PVOTE 128               // point_vote_frames: a pixel with a neighbour carries a label > nclasses (voting.py:257)
+#define F3D_DEVERR_ALL 255
 #define F3D_PLANES_PER_LAUNCH 16
 #define F3D_OBB_MAX_BOXES 4096
 #define F3D_SORT_MAX_CELLS 32767            // + 1 overflow cell = 2^15 keys -> 16 key bits sorted
@@ -273,6 +274,10 @@ hipError_t f3d_launch_graph_count(const void* xyz, int dtype, int64_t n, const f
                                   int64_t* offsets, hipStream_t s);
 hipError_t f3d_launch_graph_fill(int64_t n, const f3d_graphgrid& g, double r2, const void* scratch, const int64_t* offsets,
                                  int32_t* nbrs, hipStream_t s);
+// the grid of the radius graph on its own: cell-sorted float64 copy, caller-order index of every sorted point, [first, last) of every cell
+struct f3d_gridview { const double* sorted; const uint32_t* perm; const int2* cells; };
+hipError_t f3d_launch_graph_grid(const void* xyz, int dtype, int64_t n, const f3d_graphgrid& g, void* scratch, f3d_gridview* view,
+                                 hipStream_t s);
 // radius query (f3d_graph.hip): KDTree(data).query_radius(queries, r) inverted, one row per query in ascending data index.  Grid over
 // the m data points (from the f3d_launch_graph_bbox partials), box_lo / box_hi = the data's box grown by one cell.  The count pass
 // enqueues the readback of words_host[0] = nnz and words_host[1] = 1 if a query is NaN / infinite (the caller synchronises); the fill
@@ -329,6 +334,12 @@ hipError_t f3d_launch_points_plane_projection(const double* points, int64_t n, c
 hipError_t f3d_launch_unit_difference(const double* a, const double* b, int64_t n, double* out, hipStream_t s);
 hipError_t f3d_launch_segment_votes(const double* votes, int64_t npts, int ncols, int nclasses, double threshold,
                                     const f3d_filter_args& flt, int64_t* classes, hipStream_t s);
+// PointVotingSegmentation.segment: the total is the last column, the unfiltered candidates are the columns before it.  neg: bit k =
+// filter_classes[k] was given as a negative index; the remap then writes the class as given (NumPy stores cls_ itself), flt holds
+// the column it reads
+struct f3d_negmask { uint32_t w[F3D_MAX_FILTER / 32]; };
+hipError_t f3d_launch_segment_votes_lastcol(const double* votes, int64_t npts, int ncols, int nclasses, double threshold,
+                                            const f3d_filter_args& flt, const f3d_negmask& neg, int64_t* classes, hipStream_t s);
 hipError_t f3d_launch_vote_uv2pt(const int32_t* uv2pt, const uint8_t* mask, int64_t hw, double* votes, int64_t npts, int ncols,
                                  unsigned long long* table, uint64_t table_slots, int* err, hipStream_t s);
 // batched vote: frames [frame0, frame0 + nframes) of a call; table slots carry `gen` (< 16383), first_bad = device int (INT_MAX = none)
@@ -373,3 +384,23 @@ size_t f3d_quads_scratch_bytes(int64_t n, int k, int64_t nt);
 hipError_t f3d_launch_door_window_quads(const double* pts, int64_t n, const int64_t* ids, const int64_t* inst, int k, const double* verts,
                                         int64_t nv, const int64_t* tris, int64_t nt, double* quads, int32_t* status, int32_t* tri,
                                         double* normals, void* scratch, int* err, hipStream_t s);
+
+// fused radius search + frame vote of PointVotingSegmentation.vote (f3d_pointvote.hip).  words: device int[4] = {a label >= ncols
+// exists, first frame with a non-finite query coordinate, first frame whose pixel with such a label has a neighbour, spare};
+// "none" = F3D_PVOTE_NONE.  bits: the per-frame (point, label) sets, f3d_pvote_bits_bytes(m, ncols, group) bytes.
+#define F3D_PVOTE_NONE 0x7f7f7f7f
+#define F3D_PVOTE_MAX_GROUP 64               // frames one vote launch covers at most
+#define F3D_PVOTE_BITS_BUDGET ((size_t)256 << 20)
+struct f3d_pvote_box { double lo[3], hi[3]; };   // the cloud's box grown by one cell
+int f3d_pvote_words_per_point(int ncols);
+int f3d_pvote_group(int64_t m, int ncols);   // frames per vote launch: the bitsets of a group fit the budget (at least 1 frame)
+size_t f3d_pvote_bits_bytes(int64_t m, int ncols, int group);
+hipError_t f3d_launch_pvote_prepass(const void* queries, int qdtype, const uint8_t* masks, int64_t nframes, int64_t hw, int ncols, int* words,
+                                    hipStream_t s);
+hipError_t f3d_launch_pvote_validate(const void* queries, int qdtype, const uint8_t* masks, int64_t nframes, int64_t hw, int ncols,
+                                     const f3d_gridview& gv, const f3d_graphgrid& g, const f3d_pvote_box& box, double r2, int* words,
+                                     hipStream_t s);
+hipError_t f3d_launch_pvote_frames(const void* queries, int qdtype, const uint8_t* masks, int64_t nframes, int64_t hw, int64_t m, int ncols,
+                                   const f3d_gridview& gv, const f3d_graphgrid& g, const f3d_pvote_box& box, double r2, double* votes,
+                                   uint32_t* bits, int group, const int* words, const int* err, hipStream_t s);
+hipError_t f3d_launch_pvote_flag(const int* words, int limit, int* err, hipStream_t s);

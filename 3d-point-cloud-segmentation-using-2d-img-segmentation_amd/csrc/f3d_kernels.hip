@@ -110,10 +110,12 @@ __global__ __launch_bounds__(F3D_BLOCK) void k_inside_polyhedra(const T* __restr
 // ------------------------------------------------------------------------------------------
 // a8: segment over a dense float64 votes matrix (HBM streaming: ncols*8 B in, 8 B out per point).
 // 16 lanes per row, 4 rows per wave; each lane streams 16-B (ncols even) or 8-B pieces of its row.
+// LASTCOL (PointVotingSegmentation.segment, voting.py:267-299): the total is the row's last column instead of its sum, and
+// the unfiltered candidates are the columns before it.
 // ------------------------------------------------------------------------------------------
-template <bool VEC2>
+template <bool VEC2, bool LASTCOL>
 __global__ __launch_bounds__(F3D_BLOCK) void k_segment_votes(const double* __restrict__ votes, int64_t npts, int ncols,
-                                                              int nclasses, double threshold, f3d_filter_args flt,
+                                                              int nclasses, double threshold, f3d_filter_args flt, f3d_negmask neg,
                                                               int64_t* __restrict__ classes) {
     const int lane16 = threadIdx.x & 15;
     const int64_t group = ((int64_t)blockIdx.x * F3D_BLOCK + threadIdx.x) >> 4;
@@ -129,13 +131,13 @@ __global__ __launch_bounds__(F3D_BLOCK) void k_segment_votes(const double* __res
                 const double2 x = r2[c];
                 total += x.x; total += x.y;
                 if (x.x > best) { best = x.x; besti = 2 * c; }
-                if (x.y > best) { best = x.y; besti = 2 * c + 1; }
+                if (x.y > best && !(LASTCOL && 2 * c + 1 == ncols - 1)) { best = x.y; besti = 2 * c + 1; }
             }
         } else {
             for (int c = lane16; c < ncols; c += 16) {
                 const double x = r[c];
                 total += x;
-                if (x > best) { best = x; besti = c; }
+                if (x > best && !(LASTCOL && c == ncols - 1)) { best = x; besti = c; }
             }
         }
         if (flt.nfilter > 0) {                       // votes[:, filter_classes]: position in the list is the index
@@ -153,6 +155,7 @@ __global__ __launch_bounds__(F3D_BLOCK) void k_segment_votes(const double* __res
             const int oi = __shfl_xor(besti, off, 16);
             if (ob > best || (ob == best && oi < besti)) { best = ob; besti = oi; }
         }
+        if (LASTCOL) total = r[ncols - 1];
         if (lane16 == 0) {
             int64_t cls = besti;
             if (!(total > 0.0)) cls = nclasses;
@@ -161,7 +164,10 @@ __global__ __launch_bounds__(F3D_BLOCK) void k_segment_votes(const double* __res
             if (flt.nfilter > 0) {
                 int64_t q = cls;
                 for (int k = 0; k < flt.nfilter; ++k) {
-                    if (q == k) q = f3d_filter_at(flt, k);
+                    if (q == k) {
+                        q = f3d_filter_at(flt, k);
+                        if (LASTCOL && (neg.w[k >> 5] >> (k & 31) & 1u)) q -= ncols;      // a negative class stays as given (and never aliases)
+                    }
                 }
                 cls = q;
             }
@@ -699,8 +705,19 @@ hipError_t f3d_launch_segment_votes(const double* votes, int64_t npts, int ncols
     if (npts <= 0) return hipSuccess;
     const dim3 g(f3d_grid_for(npts, F3D_BLOCK / 16, F3D_GRID_CAP)), b(F3D_BLOCK);
     const bool vec2 = (ncols % 2 == 0) && ((reinterpret_cast<uintptr_t>(votes) & 15) == 0);
-    if (vec2) hipLaunchKernelGGL(k_segment_votes<true>, g, b, 0, s, votes, npts, ncols, nclasses, threshold, flt, classes);
-    else hipLaunchKernelGGL(k_segment_votes<false>, g, b, 0, s, votes, npts, ncols, nclasses, threshold, flt, classes);
+    const f3d_negmask neg = {};
+    if (vec2) hipLaunchKernelGGL((k_segment_votes<true, false>), g, b, 0, s, votes, npts, ncols, nclasses, threshold, flt, neg, classes);
+    else hipLaunchKernelGGL((k_segment_votes<false, false>), g, b, 0, s, votes, npts, ncols, nclasses, threshold, flt, neg, classes);
+    return hipGetLastError();
+}
+
+hipError_t f3d_launch_segment_votes_lastcol(const double* votes, int64_t npts, int ncols, int nclasses, double threshold,
+                                            const f3d_filter_args& flt, const f3d_negmask& neg, int64_t* classes, hipStream_t s) {
+    if (npts <= 0) return hipSuccess;
+    const dim3 g(f3d_grid_for(npts, F3D_BLOCK / 16, F3D_GRID_CAP)), b(F3D_BLOCK);
+    const bool vec2 = (ncols % 2 == 0) && ((reinterpret_cast<uintptr_t>(votes) & 15) == 0);
+    if (vec2) hipLaunchKernelGGL((k_segment_votes<true, true>), g, b, 0, s, votes, npts, ncols, nclasses, threshold, flt, neg, classes);
+    else hipLaunchKernelGGL((k_segment_votes<false, true>), g, b, 0, s, votes, npts, ncols, nclasses, threshold, flt, neg, classes);
     return hipGetLastError();
 }
 

@@ -107,6 +107,11 @@ def library():
         'f3d_vote_uv2pt_batch_dev': (i32, [vp, vp, vp, i64, i32, i32, vp, i64, i32, vp]),
         'f3d_segment_votes': (i32, [vp, vp, i64, i32, i32, dbl, vp, i32, vp]),
         'f3d_segment_votes_dev': (i32, [vp, vp, i64, i32, i32, dbl, vp, i32, vp, vp]),
+        'f3d_segment_votes_lastcol': (i32, [vp, vp, i64, i32, i32, dbl, vp, i32, vp]),
+        'f3d_segment_votes_lastcol_dev': (i32, [vp, vp, i64, i32, i32, dbl, vp, i32, vp, vp]),
+        'f3d_point_vote_frames': (i32, [vp, vp, i32, i64, vp, i32, vp, i64, i64, dbl, vp, i32]),
+        'f3d_point_vote_frames_dev': (i32, [vp, vp, i32, i64, vp, i32, vp, i64, i64, dbl, vp, i32, vp]),
+        'f3d_ctx_reserve_point_vote': (i32, [vp, i64, i32]),
         'f3d_sem_logits_to_mask': (i32, [vp, vp, i32, i64, flt, i32, vp]),
         'f3d_sem_logits_to_mask_dev': (i32, [vp, vp, i32, i64, flt, i32, vp, vp]),
         'f3d_sem_logits_to_masks_dev': (i32, [vp, vp, i32, i32, i64, flt, i32, vp, vp]),
@@ -336,6 +341,10 @@ class Context:
         """Size the scratch of region_grow_dev for clouds of up to n points."""
         self._check(self._lib.f3d_ctx_reserve_refine(self._h, int(n)))
 
+    def reserve_point_vote(self, m, ncols):
+        """Size the scratch of point_vote_frames_dev for clouds of up to m points and ncols vote columns, at any radius."""
+        self._check(self._lib.f3d_ctx_reserve_point_vote(self._h, int(m), int(ncols)))
+
     def set_strict(self, strict=True):
         self._check(self._lib.f3d_ctx_set_strict(self._h, int(bool(strict))))
 
@@ -430,6 +439,39 @@ class Context:
         self._check(self._lib.f3d_segment_votes(self._h, _ptr(v), v.shape[0], v.shape[1], int(nclasses), float(threshold),
                                                 _ptr(f), nf, _ptr(cls)))
         return cls
+
+    def segment_votes_lastcol(self, votes, nclasses, threshold, filter_classes=None):
+        """PointVotingSegmentation.segment (voting.py:267-299): segment_votes with the last column as the total and, without a
+        filter, the columns before it as the candidates."""
+        v = _f64(votes)
+        if v.ndim != 2:
+            raise ValueError('votes must be [npts, ncols]')
+        f, nf = _filter(filter_classes)
+        cls = np.empty(len(v), np.int64)
+        if v.shape[1] == 0:
+            raise IndexError('index -1 is out of bounds for axis 1 with size 0')
+        self._check(self._lib.f3d_segment_votes_lastcol(self._h, _ptr(v), v.shape[0], v.shape[1], int(nclasses), float(threshold),
+                                                        _ptr(f), nf, _ptr(cls)))
+        return cls
+
+    def point_vote_frames(self, votes, cloud, queries, masks, radius):
+        """The frames of PointVotingSegmentation.vote in one call (f3d.h f3d_point_vote_frames), in place on `votes` (float64
+        [M, ncols], C-contiguous): cloud [M, 3], queries [F, hw, 3] (float32 or float64 each), masks uint8 [F, hw]."""
+        if votes.dtype != np.float64 or not votes.flags.c_contiguous or votes.ndim != 2:
+            raise ValueError('votes must be a C-contiguous float64 [npts, ncols] array')
+        c, cdt = _xyz(cloud)
+        q = np.asarray(queries)
+        if q.ndim != 3 or q.shape[2] != 3:
+            raise ValueError(f'queries must be [F, hw, 3], got {q.shape}')
+        qq, qdt = _xyz(q.reshape(-1, 3))
+        m = np.ascontiguousarray(masks, dtype=np.uint8).reshape(q.shape[0], -1 if q.shape[0] else q.shape[1])
+        if m.shape != q.shape[:2]:
+            raise ValueError(f'shape mismatch: queries {q.shape[:2]}, masks {m.shape}')
+        if len(c) != votes.shape[0]:
+            raise ValueError(f'votes has {votes.shape[0]} rows, the cloud {len(c)} points')
+        self._check(self._lib.f3d_point_vote_frames(self._h, _ptr(c), cdt, len(c), _ptr(qq), qdt, _ptr(m), q.shape[0], q.shape[1],
+                                                    float(radius), _ptr(votes), votes.shape[1]))
+        return votes
 
     def sem_logits_to_mask(self, sem, conf_threshold=0.017, low_label=133):
         s = np.ascontiguousarray(sem, dtype=np.float32)
@@ -880,6 +922,18 @@ class Context:
         f, nf = _filter(filter_classes)
         self._check(self._lib.f3d_segment_votes_dev(self._h, votes_ptr, npts, ncols, int(nclasses), float(threshold),
                                                     _ptr(f), nf, classes_ptr, stream))
+
+    def segment_votes_lastcol_dev(self, votes_ptr, npts, ncols, nclasses, threshold, filter_classes, classes_ptr, stream=None):
+        f, nf = _filter(filter_classes)
+        self._check(self._lib.f3d_segment_votes_lastcol_dev(self._h, votes_ptr, npts, ncols, int(nclasses), float(threshold),
+                                                            _ptr(f), nf, classes_ptr, stream))
+
+    def point_vote_frames_dev(self, cloud_ptr, cloud_dtype, m, queries_ptr, query_dtype, masks_ptr, nframes, hw, radius, votes_ptr, ncols,
+                              stream=None):
+        """Enqueues on `stream` after one readback (f3d.h); a label > nclasses on a pixel with a neighbour is recorded for
+        take_device_error, non-finite queries raise ValueError here after the frames before them are enqueued."""
+        self._check(self._lib.f3d_point_vote_frames_dev(self._h, cloud_ptr, int(cloud_dtype), int(m), queries_ptr, int(query_dtype), masks_ptr,
+                                                        int(nframes), int(hw), float(radius), votes_ptr, int(ncols), stream))
 
     def vote_uv2pt_dev(self, uv2pt_ptr, mask_ptr, hw, votes_ptr, npts, ncols, stream=None):
         self._check(self._lib.f3d_vote_uv2pt_dev(self._h, uv2pt_ptr, mask_ptr, hw, votes_ptr, npts, ncols, stream))

@@ -282,6 +282,18 @@ int f3d_segment_votes_dev(f3d_ctx* ctx, const double* votes, int64_t npts, int n
                           double threshold, const int32_t* filter /*host*/, int nfilter,
                           int64_t* classes, void* stream);
 
+/* ---- PointVotingSegmentation.segment (voting.py:267-299) ---------------------------------- */
+/* As f3d_segment_votes (first-maximum argmax, `nclasses` for no votes / max/total < threshold / a zero maximum, the sequential
+ * index -> class remap with its aliasing), with the two differences of that class: the total of a row is its LAST COLUMN, not
+ * its sum, and without a filter the candidates are the columns before the last one.  A negative filter entry reads the column
+ * NumPy's index wraps to and is written to `classes` as given (the reference stores the list's value).  ncols == 1 without a filter ->
+ * F3D_ERR_INVALID (NumPy: argmax of an empty sequence). */
+int f3d_segment_votes_lastcol(f3d_ctx* ctx, const double* votes, int64_t npts, int ncols, int nclasses,
+                              double threshold, const int32_t* filter, int nfilter, int64_t* classes);
+int f3d_segment_votes_lastcol_dev(f3d_ctx* ctx, const double* votes, int64_t npts, int ncols, int nclasses,
+                                  double threshold, const int32_t* filter /*host*/, int nfilter,
+                                  int64_t* classes, void* stream);
+
 /* ---- a9: mask post-processing of SegmentImage (get2DSeg.py:110-118) ----------------------- */
 /* sem: float32 [c, hw] logits -> uint8 mask[hw]: argmax over c; softmax max < conf -> `low`. */
 int f3d_sem_logits_to_mask(f3d_ctx* ctx, const float* sem, int c, int64_t hw, float conf_threshold,
@@ -541,6 +553,41 @@ int f3d_radius_query_count_dev(f3d_ctx* ctx, const void* data, f3d_dtype data_dt
                                int64_t* nnz /*host*/, void* stream);
 int f3d_radius_query_fill_dev(f3d_ctx* ctx, const void* queries /*device, as counted*/, f3d_dtype query_dtype, int64_t n,
                               const int64_t* offsets /*device*/, int32_t* neighbours /*device [nnz]*/, void* stream);
+
+/* ---- PointVotingSegmentation.vote: radius search fused with the frame vote (segUtils/voting.py:224-265) ------ */
+/* The loop body of the reference for F frames in one call.  cloud [m, 3] (`cloud_dtype`), queries [F, hw, 3] (`query_dtype`: the
+ * frames' world-space depth points), masks uint8 [F, hw] (already at the depth resolution), votes float64 [m, ncols] updated IN
+ * PLACE, ncols = nclasses + 1.  Per frame, in frame order:
+ *     nns = KDTree(cloud).query_radius(queries[f], radius)     pixel q pairs with every cloud index i whose float64 squared distance
+ *                                                              ((dx*dx + dy*dy) + dz*dz) is <= radius*radius, INCLUSIVE (the
+ *                                                              predicate of f3d_radius_query_*; float32 inputs are widened exactly)
+ *     votes[i, masks[f, q]] += 1 ; votes[i, ncols - 1] += 1    over all pairs, with NumPy's buffered fancy-index rule: every DISTINCT
+ *                                                              cell gets +1 per frame however many pairs hit it
+ * so a point may receive several labels from one frame, and the last column counts the FRAMES that saw the point.  A label equal to
+ * ncols - 1 is a legal index that lands on the last column: that cell then gets +2 from the frame.  No pixel is skipped (a dropout
+ * pixel sits at its camera centre and votes like any other).  The result is bit-reproducible (integer counts, exact float64 adds).
+ * Errors, as the reference raises them:
+ *   - a label >= ncols on a pixel that HAS a neighbour is an IndexError at that frame (a pixel without one drops its label);
+ *   - NaN / infinity in the queries is sklearn's ValueError at that frame (F3D_ERR_INVALID);
+ *   the frames before the first offending frame are applied, it and the later ones are not; if one frame has both, the ValueError
+ *   wins (the search precedes the vote).  The host variant returns F3D_ERR_INDEX / F3D_ERR_INVALID after copying the votes back.
+ *   The _dev variant returns F3D_ERR_INVALID at once for the ValueError, and records the IndexError in a bit of its own of the
+ *   device error word, for f3d_take_device_error; while that bit is pending, further calls write nothing.
+ *   - m == 0, NaN / infinity in the cloud, radius >= 1e300: F3D_ERR_INVALID, nothing applied.  radius < 0 or NaN: no pair, no error.
+ * One blocking readback per call (the cloud's box and a streaming pre-pass over masks and queries together); the search that looks
+ * for an offending label's neighbours runs only when the pre-pass saw such a label.  The cloud's grid is built once per call, in
+ * context state of its own (other entries may run between calls).
+ * Scratch, independent of the number of pairs: the grid, 40*m + 8*cells bytes + the sort's temporary storage (cells <= 2^24), and
+ * the per-frame key sets, G * m * W * 4 bytes with W = ceil((min(ncols, 256) + 1) / 32) words per point and
+ * G = clamp(256 MiB / (m * W * 4), 1, 64) frames per launch.  f3d_ctx_reserve_point_vote sizes both for any radius, so that a strict
+ * context does not allocate. */
+int f3d_point_vote_frames(f3d_ctx* ctx, const void* cloud, f3d_dtype cloud_dtype, int64_t m, const void* queries,
+                          f3d_dtype query_dtype, const uint8_t* masks, int64_t nframes, int64_t hw, double radius,
+                          double* votes /*[m, ncols], in place*/, int ncols);
+int f3d_point_vote_frames_dev(f3d_ctx* ctx, const void* cloud, f3d_dtype cloud_dtype, int64_t m, const void* queries,
+                              f3d_dtype query_dtype, const uint8_t* masks, int64_t nframes, int64_t hw, double radius,
+                              double* votes /*device [m, ncols], in place*/, int ncols, void* stream);
+int f3d_ctx_reserve_point_vote(f3d_ctx* ctx, int64_t m, int ncols);
 
 /* ---- a5: patch matching of Fusion.fuse (Fusion3DSeg/fusion.py:269-298) ------------------- */
 /* The loop over the in-frustum points ("seeds", in index order) of one frame: seed k takes the still-free depth pixels of
