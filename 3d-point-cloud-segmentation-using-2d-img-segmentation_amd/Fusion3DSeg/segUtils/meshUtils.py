@@ -1,0 +1,314 @@
+"""The mesh-topology part of the reference's Fusion3DSeg/segUtils/meshUtils.py on the GPU, plus ``clean_mesh``.
+
+Same names and positional signatures as the reference (file:line in each docstring).  NumPy arrays in give NumPy arrays out
+(host-pointer entries of libf3d_hip); device tensors in give device tensors out, on a side stream ordered both ways with
+torch's current stream.  The kernel-backed functions have no CPU fallback.
+
+Limits: V < 2^31 vertices, 3 M < 2^31; triangles are int32 or int64 [M, 3].  A vertex index outside [0, V) raises IndexError
+and writes nothing -- a stated deviation: the reference's list and NumPy indexing wrap a negative index.
+
+The Open3D / cv2 converters and viewers of the reference file (to_pcd, to_mesh, to_lines, to_uvmesh, to_image, pick_points,
+get_roi, read_images, load_o3d_camera_data), generate_texture, uv2rgb and classwise_triangle_colors are not provided.
+"""
+import numpy as np
+
+import f3d
+from Fusion3DSeg.segUtils.cv import _on_device, _work_stream
+
+__all__ = ['vertex_triangle_mapping', 'remove_faces_by_vertices', 'keep_faces_by_vertices', 'get_triangle_clusters', 'clean_mesh',
+           'bbox_axes', 'one_to_all_angles', 'VertexTriangleMap']
+
+
+# ------------------------------------------------------------------------------------------------ argument checks
+def _triangles(triangles):
+    """int32 / int64 [M, 3], C-contiguous, as given (NumPy array or device tensor)."""
+    if _on_device(triangles):
+        import torch
+        if triangles.dtype not in (torch.int32, torch.int64):
+            raise TypeError(f'triangles must be int32 or int64, got {triangles.dtype}')
+        if triangles.dim() != 2 or triangles.shape[1] != 3:
+            raise ValueError(f'triangles must be [M, 3], got {tuple(triangles.shape)}')
+        tris = triangles.contiguous()
+    else:
+        tris = np.asarray(triangles)
+        if tris.dtype not in (np.int32, np.int64):
+            raise TypeError(f'triangles must be int32 or int64, got {tris.dtype}')
+        if tris.ndim != 2 or tris.shape[1] != 3:
+            raise ValueError(f'triangles must be [M, 3], got {tris.shape}')
+        tris = np.ascontiguousarray(tris)
+    if 3 * tris.shape[0] >= 1 << 31:
+        raise ValueError('3 * M must be below 2^31')
+    return tris
+
+
+def _nvertices(nvertices):
+    nv = int(nvertices)
+    if nv < 0 or nv >= 1 << 31:
+        raise ValueError(f'nvertices must be in [0, 2^31), got {nv}')
+    return nv
+
+
+def _vertices(vertices, like):
+    """float64 / float32 [V, 3] where `like` (the triangles) lives; other dtypes are widened to float64."""
+    if _on_device(like):
+        import torch
+        verts = torch.as_tensor(vertices, device=like.device)
+        if verts.dtype not in (torch.float64, torch.float32):
+            verts = verts.to(torch.float64)
+        shape = tuple(verts.shape)
+        verts = verts.contiguous()
+    else:
+        verts = np.asarray(vertices.cpu() if _on_device(vertices) else vertices)
+        if verts.dtype not in (np.float64, np.float32):
+            verts = verts.astype(np.float64)
+        shape = verts.shape
+        verts = np.ascontiguousarray(verts)
+    if len(shape) != 2 or shape[1] != 3:
+        raise ValueError(f'vertices must be [V, 3], got {shape}')
+    _nvertices(shape[0])
+    return verts
+
+
+def _mask(mask, nv, like, name='mask'):
+    """bool [V] where `like` lives."""
+    if _on_device(like):
+        import torch
+        m = torch.as_tensor(mask, device=like.device)
+        shape = tuple(m.shape)
+        m = m.to(torch.bool).contiguous()
+    else:
+        m = np.asarray(mask.cpu() if _on_device(mask) else mask)
+        shape = m.shape
+        m = np.ascontiguousarray(m, dtype=bool)
+    if shape != (nv,):
+        raise ValueError(f'{name} must have one entry per vertex ({nv}), got shape {shape}')
+    return m
+
+
+def _ctx(like):
+    return f3d.default_context(like.device.index if _on_device(like) else None)
+
+
+def _itype(t):
+    return f3d.I32 if t.element_size() == 4 else f3d.I64
+
+
+def _vdtype(t):
+    return f3d.F32 if t.element_size() == 4 else f3d.F64
+
+
+def _counts(ctx, counts, work):
+    """The one blocking readback of a device call: its output sizes; the IndexError of a bad vertex index is raised here."""
+    host = counts.cpu()
+    if int(host[2]):
+        ctx.take_device_error(work.cuda_stream)
+        raise IndexError('mesh: a triangle vertex index is outside [0, nvertices)')
+    return int(host[0]), int(host[1])
+
+
+# ------------------------------------------------------------------------------------------------ 1. vertex -> triangle map
+class VertexTriangleMap:
+    """What vertex_triangle_mapping returns: ``.csr`` = (offsets int64 [V + 1], tri int32 [3M], pos int8 [3M]), row v =
+    ``offsets[v]:offsets[v + 1]``.  It unpacks as the reference's pair ``triangles_of_vertices, position_of_vertices`` (two lists
+    of V lists of ints), which are built when first read."""
+
+    def __init__(self, offsets, tri, pos):
+        self.csr = (offsets, tri, pos)
+        self._lists = None
+
+    def _build(self):
+        if self._lists is None:
+            offsets, tri, pos = (a.cpu().numpy() if _on_device(a) else a for a in self.csr)
+            cuts = offsets[1:-1]
+            self._lists = ([r.tolist() for r in np.split(tri, cuts)] if len(offsets) > 1 else [],
+                           [r.tolist() for r in np.split(pos, cuts)] if len(offsets) > 1 else [])
+        return self._lists
+
+    @property
+    def triangles_of_vertices(self):
+        return self._build()[0]
+
+    @property
+    def position_of_vertices(self):
+        return self._build()[1]
+
+    def __len__(self):
+        return 2
+
+    def __getitem__(self, i):
+        return self._build()[i]
+
+    def __iter__(self):
+        return iter(self._build())
+
+
+def vertex_triangle_mapping(triangles, nvertices):
+    """For every vertex the triangles that hold it and the corner they hold it at (reference :235-259), as a VertexTriangleMap.
+
+    One stable radix sort of (vertex, slot) pairs, slot = 3 f + j: rows are in ascending slot order, the reference's append
+    order; a face (v, v, w) lists f twice in row v, with positions 0 and 1."""
+    tris, nv = _triangles(triangles), _nvertices(nvertices)
+    ctx = _ctx(tris)
+    if not _on_device(tris):
+        return VertexTriangleMap(*ctx.mesh_vertex_map(tris, nv))
+    import torch
+    dev, nt = tris.device, tris.shape[0]
+    offsets = torch.empty(nv + 1, dtype=torch.int64, device=dev)
+    tri = torch.empty(3 * nt, dtype=torch.int32, device=dev)
+    pos = torch.empty(3 * nt, dtype=torch.int8, device=dev)
+    counts = torch.empty(4, dtype=torch.int64, device=dev)
+    with _work_stream(dev) as work:
+        ctx.mesh_vertex_map_dev(tris.data_ptr(), _itype(tris), nt, nv, offsets.data_ptr(), tri.data_ptr(), pos.data_ptr(), counts.data_ptr(),
+                                work.cuda_stream)
+        _counts(ctx, counts, work)
+    return VertexTriangleMap(offsets, tri, pos)
+
+
+# ------------------------------------------------------------------------------------------------ 2. remove faces
+def remove_faces_by_vertices(nvertices, triangles, mask):
+    """Drop every face that touches a masked vertex (reference :262-301) -> (not_removed bool [M], remaining_triangles [Q, 3] in
+    the dtype of ``triangles``, oldids2newids int64 [V]).
+
+    oldids2newids is the exclusive scan of ``~mask`` at the kept vertices and 0 at the removed ones; remaining_triangles =
+    oldids2newids[triangles[not_removed]], face order kept."""
+    tris, nv = _triangles(triangles), _nvertices(nvertices)
+    m = _mask(mask, nv, tris)
+    ctx = _ctx(tris)
+    if not _on_device(tris):
+        return ctx.mesh_remove_faces(tris, nv, m)
+    import torch
+    dev, nt = tris.device, tris.shape[0]
+    nr = torch.empty(nt, dtype=torch.bool, device=dev)
+    rem = torch.empty((nt, 3), dtype=tris.dtype, device=dev)
+    o2n = torch.empty(nv, dtype=torch.int64, device=dev)
+    counts = torch.empty(4, dtype=torch.int64, device=dev)
+    with _work_stream(dev) as work:
+        ctx.mesh_remove_faces_dev(tris.data_ptr(), _itype(tris), nt, nv, m.data_ptr(), nr.data_ptr(), rem.data_ptr(), o2n.data_ptr(),
+                                  counts.data_ptr(), work.cuda_stream)
+        q, _ = _counts(ctx, counts, work)
+    return nr, rem[:q], o2n
+
+
+# ------------------------------------------------------------------------------------------------ 3. keep faces
+def keep_faces_by_vertices(vertices, triangles, mask):
+    """Keep the faces with at least one masked corner and the vertices they use (reference :304-333) -> (remaining_vertices
+    [P, 3], remaining_triangles [Q, 3]).
+
+    The vertices are renumbered in order of first appearance over the kept faces (faces in order, corners 0, 1, 2), computed
+    data-parallel from per-vertex slot minima, so the result does not depend on thread timing.
+
+    Deviations from the reference: it returns arrays ([P, 3] in the dtype of ``vertices``, [Q, 3] in the dtype of ``triangles``;
+    shape (0, 3) when empty) where the reference returns Python lists of rows; and it leaves the caller's ``triangles``
+    untouched, where the reference renumbers the caller's array in place (its ``face`` is a view)."""
+    tris = _triangles(triangles)
+    verts = _vertices(vertices, tris)
+    nv, nt = verts.shape[0], tris.shape[0]
+    m = _mask(mask, nv, tris)
+    ctx = _ctx(tris)
+    if not _on_device(tris):
+        return ctx.mesh_keep_faces(verts, tris, m)
+    import torch
+    dev = tris.device
+    ov = torch.empty((min(3 * nt, nv), 3), dtype=verts.dtype, device=dev)
+    ot = torch.empty((nt, 3), dtype=tris.dtype, device=dev)
+    counts = torch.empty(4, dtype=torch.int64, device=dev)
+    with _work_stream(dev) as work:
+        ctx.mesh_keep_faces_dev(verts.data_ptr(), _vdtype(verts), nv, tris.data_ptr(), _itype(tris), nt, m.data_ptr(), ov.data_ptr(),
+                                ot.data_ptr(), counts.data_ptr(), work.cuda_stream)
+        p, q = _counts(ctx, counts, work)
+    return ov[:p], ot[:q]
+
+
+# ------------------------------------------------------------------------------------------------ 4. triangle clusters
+def _mesh_parts(mesh):
+    if hasattr(mesh, 'vertices') and hasattr(mesh, 'triangles'):
+        return mesh.vertices, mesh.triangles
+    vertices, triangles = mesh
+    return vertices, triangles
+
+
+def get_triangle_clusters(mesh, return_triangle_areas=False):
+    """Connected triangle clusters (reference :360-375, Open3D's cluster_connected_triangles restated; parity with Open3D is
+    unpinned) -> (triangle_clusters int32 [M], cluster_n_triangles int64 [P], cluster_area float64 [P]).
+
+    ``mesh`` has ``.vertices`` and ``.triangles`` (get3DSeg.TriangleMesh) or is a ``(vertices, triangles)`` pair.  Two triangles
+    are adjacent iff they share an ordered edge (min(a, b), max(a, b)) among their edges (0,1), (0,2), (1,2); sharing only a
+    vertex does not connect them, a non-manifold edge connects all its triangles.  Clusters are numbered in ascending order of
+    their lowest triangle.  A triangle's area is 0.5 * sqrt((cx*cx + cy*cy) + cz*cz), c = cross(p0 - p1, p0 - p2); a cluster's
+    area is a fixed-shape float64 sum (two calls return identical bits).  ``return_triangle_areas`` appends the areas [M]."""
+    vertices, triangles = _mesh_parts(mesh)
+    tris = _triangles(triangles)
+    verts = _vertices(vertices, tris)
+    nv, nt = verts.shape[0], tris.shape[0]
+    ctx = _ctx(tris)
+    if not _on_device(tris):
+        return ctx.mesh_triangle_clusters(verts, tris, return_triangle_areas)
+    import torch
+    dev = tris.device
+    cl = torch.empty(nt, dtype=torch.int32, device=dev)
+    cn = torch.empty(nt, dtype=torch.int64, device=dev)
+    ca = torch.empty(nt, dtype=torch.float64, device=dev)
+    ta = torch.empty(nt, dtype=torch.float64, device=dev) if return_triangle_areas else None
+    counts = torch.empty(4, dtype=torch.int64, device=dev)
+    with _work_stream(dev) as work:
+        ctx.mesh_triangle_clusters_dev(verts.data_ptr(), _vdtype(verts), nv, tris.data_ptr(), _itype(tris), nt, cl.data_ptr(), cn.data_ptr(),
+                                       ca.data_ptr(), None if ta is None else ta.data_ptr(), counts.data_ptr(), work.cuda_stream)
+        p, _ = _counts(ctx, counts, work)
+    out = (cl, cn[:p], ca[:p])
+    return out + (ta,) if return_triangle_areas else out
+
+
+# ------------------------------------------------------------------------------------------------ 5. clean_mesh
+def clean_mesh(vertices, triangles, remove_mask=None, min_triangles=1, min_area=0.0):
+    """Remove masked vertices and small fragments from a mesh, on the device from end to end (no reference counterpart) ->
+    (new_vertices, new_triangles, kept_vertex_mask bool [V], kept_triangle_mask bool [M]).
+
+    1. with ``remove_mask`` (bool [V]): drop every face that touches a masked vertex (remove_faces_by_vertices);
+    2. cluster the surviving faces (get_triangle_clusters);
+    3. drop the clusters with fewer than ``min_triangles`` triangles or with an area below ``min_area``;
+    4. drop the vertices no face references, keeping vertex order, and renumber the faces.
+
+    It is the composition of the functions above and equals it bit for bit; one blocking readback (the output sizes)."""
+    tris = _triangles(triangles)
+    verts = _vertices(vertices, tris)
+    nv, nt = verts.shape[0], tris.shape[0]
+    m = None if remove_mask is None else _mask(remove_mask, nv, tris, 'remove_mask')
+    ctx = _ctx(tris)
+    if not _on_device(tris):
+        return ctx.mesh_clean(verts, tris, m, min_triangles, min_area)
+    import torch
+    dev = tris.device
+    nvs = torch.empty((nv, 3), dtype=verts.dtype, device=dev)
+    nts = torch.empty((nt, 3), dtype=tris.dtype, device=dev)
+    kv = torch.zeros(nv, dtype=torch.bool, device=dev)
+    kt = torch.zeros(nt, dtype=torch.bool, device=dev)
+    counts = torch.empty(4, dtype=torch.int64, device=dev)
+    with _work_stream(dev) as work:
+        ctx.mesh_clean_dev(verts.data_ptr(), _vdtype(verts), nv, tris.data_ptr(), _itype(tris), nt, None if m is None else m.data_ptr(),
+                           min_triangles, min_area, nvs.data_ptr(), nts.data_ptr(), kv.data_ptr(), kt.data_ptr(), counts.data_ptr(),
+                           work.cuda_stream)
+        q, p = _counts(ctx, counts, work)
+    return nvs[:p], nts[:q], kv, kt
+
+
+# ------------------------------------------------------------------------------------------------ 6. host helpers
+def bbox_axes(corners):
+    """Origin, unit x and y axes and their lengths of an oriented box from its 8 corners in Open3D's order (reference :336-357):
+    the x axis is the longest of the three edges at corner 0, the y axis the middle one; the origin is the midpoint of corners
+    0 and 3.  NumPy on the host (a handful of vectors)."""
+    edges = corners[1:4] - corners[0][None, :]
+    lengths = np.linalg.norm(edges, axis=-1)
+    by_length = np.argsort(lengths)
+    i, li = edges[by_length[2]], lengths[by_length[2]]
+    j, lj = edges[by_length[1]], lengths[by_length[1]]
+    origin = (corners[0] + corners[3]) / 2
+    return origin, i / li, j / lj, li, lj
+
+
+def one_to_all_angles(vec1, vec2):
+    """Angles in degrees between every vector of vec2 [M, 3] and every vector of vec1 [N, 3] -> [M, N] (reference :455-467).
+    Both arguments are normalised IN PLACE, as in the reference.  NumPy on the host."""
+    vec1 /= np.linalg.norm(vec1, axis=1)[:, None]
+    vec2 /= np.linalg.norm(vec2, axis=1)[:, None]
+    cos = np.sum(vec1[None, :, :] * vec2[:, None, :], axis=2)
+    return np.rad2deg(np.arccos(cos))

@@ -27,7 +27,7 @@ enum { SLOT_XYZ = 0, SLOT_OUT0, SLOT_OUT1, SLOT_VIEWS, SLOT_MASKS, SLOT_AUX0, SL
        SLOT_GRP_ORDER, SLOT_GRP_KEYS, SLOT_GRP_STARTS, SLOT_GRP_SCRATCH, SLOT_OBB_TABLE, SLOT_OBB_FACETS, SLOT_OBB_CAND, SLOT_FUSE_TABLES, SLOT_FUSE_CARRY, SLOT_FUSE_XYZ, SLOT_FUSION, SLOT_PATCH_STATUS, SLOT_NRM, SLOT_NRM_CAMS,
        SLOT_QRY, SLOT_QRY_IN, SLOT_QRY_OFFS,
        SLOT_FLOOD, SLOT_COLOR, SLOT_CVS_INST, SLOT_CVS_ORDER, SLOT_CVS_COFFS, SLOT_CVS_FLAGS, SLOT_CVS_SEEDS, SLOT_CVS_STATS,
-       SLOT_QUADS, SLOT_QUADS_OUT, SLOT_GROW, SLOT_PVOTE, SLOT_PVOTE_BITS, SLOT_COUNT };
+       SLOT_QUADS, SLOT_QUADS_OUT, SLOT_GROW, SLOT_PVOTE, SLOT_PVOTE_BITS, SLOT_MESH, SLOT_MESH_IO, SLOT_COUNT };
 
 thread_local char g_create_err[512] = "";
 
@@ -170,6 +170,8 @@ int take_error(f3d_ctx* ctx, hipStream_t s, int mask = F3D_DEVERR_ALL) {
             return fail(ctx, F3D_ERR_INDEX, "door_window_quads: a triangle's vertex index is out of bounds");
         if (e & F3D_DEVERR_PVOTE)
             return fail(ctx, F3D_ERR_INDEX, "point_vote_frames: a mask label exceeds nclasses on a pixel that has a neighbour (the reference raises IndexError at voting.py:257)");
+        if (e & F3D_DEVERR_MESH)
+            return fail(ctx, F3D_ERR_INDEX, "mesh: a triangle's vertex index is outside [0, nv)");
     }
     return F3D_OK;
 }
@@ -181,7 +183,7 @@ int take_error(f3d_ctx* ctx, hipStream_t s, int mask = F3D_DEVERR_ALL) {
 struct staging {
     f3d_ctx* ctx;
     int rc = F3D_OK;
-    struct { void* host; const void* dev; size_t bytes; } back_[4];    // the most outputs an entry copies back
+    struct { void* host; const void* dev; size_t bytes; } back_[6];    // the most outputs an entry copies back
     int nback = 0;
 
     explicit staging(f3d_ctx* c) : ctx(c) {}
@@ -193,7 +195,7 @@ struct staging {
     void put(void* dev, const void* host, size_t bytes) { if (!rc && host && bytes) rc = h2d(dev, host, bytes); }
     void back(void* host, const void* dev, size_t bytes) {
         if (!host || !bytes || rc) return;
-        if (nback == 4) { rc = fail(ctx, F3D_ERR_INVALID, "staging: more than 4 outputs"); return; }
+        if (nback == 6) { rc = fail(ctx, F3D_ERR_INVALID, "staging: more than 6 outputs"); return; }
         back_[nback++] = {host, dev, bytes};
     }
     template <class T> T* in(int s, const T* host, size_t bytes) {
@@ -1468,6 +1470,209 @@ int f3d_door_window_quads(f3d_ctx* ctx, const double* points, int64_t n, const i
     if (!st.rc) st.rc = f3d_door_window_quads_dev(ctx, dpts, n, dids, dinst, k, dverts, nv, dtris, nt, dquads, dstatus, dtri, dnrm,
                                                   ctx->stream);
     return st.finish(F3D_DEVERR_QUADS);
+}
+
+// ---------------------------------------------------------------------------------------------
+// segUtils/meshUtils.py: face filtering, vertex maps, triangle clusters
+// ---------------------------------------------------------------------------------------------
+static bool mesh_args_ok(int64_t nv, int64_t nt, int itype, int vdtype) {
+    return nv >= 0 && nv <= 0x7fffffffLL && nt >= 0 && 3 * nt <= 0x7fffffffLL && (itype == F3D_I64 || itype == F3D_I32) &&
+           (vdtype == F3D_F64 || vdtype == F3D_F32);
+}
+#define F3D_MESH_BAD "bad arguments (nv < 2^31, 3 * nt < 2^31, int64 / int32 triangles, float64 / float32 vertices)"
+
+static size_t tri_bytes(int itype, int64_t nt) { return (size_t)nt * 3 * (itype == F3D_I64 ? 8 : 4); }
+
+int f3d_ctx_reserve_mesh(f3d_ctx* ctx, int64_t nv, int64_t nt) {
+    int rc = enter(ctx); if (rc) return rc;
+    if (!mesh_args_ok(nv, nt, F3D_I64, F3D_F64)) return fail(ctx, F3D_ERR_INVALID, "ctx_reserve_mesh: " F3D_MESH_BAD);
+    const int strict = ctx->strict;
+    ctx->strict = 0;
+    void* p;
+    rc = ensure(ctx, SLOT_MESH, f3d_mesh_scratch_bytes(nv, nt), &p);
+    ctx->strict = strict;
+    return rc;
+}
+
+int f3d_mesh_vertex_map_dev(f3d_ctx* ctx, const void* tris, int itype, int64_t nt, int64_t nv, int64_t* offsets, int32_t* tri,
+                            int8_t* pos, int64_t* counts, void* stream) {
+    int rc = enter(ctx); if (rc) return rc;
+    if (!mesh_args_ok(nv, nt, itype, F3D_F64) || !offsets || !counts || (nt > 0 && (!tris || !tri || !pos)))
+        return fail(ctx, F3D_ERR_INVALID, "mesh_vertex_map: " F3D_MESH_BAD);
+    void* scratch;
+    if ((rc = ensure(ctx, SLOT_MESH, f3d_mesh_scratch_bytes(nv, nt), &scratch))) return rc;
+    F3D_HIP(ctx, f3d_launch_mesh_vertex_map(tris, itype, nt, nv, offsets, tri, pos, scratch, counts, ctx->dev_err, pick(ctx, stream)));
+    return F3D_OK;
+}
+
+int f3d_mesh_vertex_map(f3d_ctx* ctx, const void* tris, int itype, int64_t nt, int64_t nv, int64_t* offsets, int32_t* tri,
+                        int8_t* pos, int64_t* counts) {
+    int rc = enter(ctx); if (rc) return rc;
+    if (!mesh_args_ok(nv, nt, itype, F3D_F64) || !offsets || !counts || (nt > 0 && (!tris || !tri || !pos)))
+        return fail(ctx, F3D_ERR_INVALID, "mesh_vertex_map: " F3D_MESH_BAD);
+    f3d_carve c;
+    const size_t o_tris = c.take(tri_bytes(itype, nt)), o_offs = c.take((size_t)(nv + 1) * 8), o_tri = c.take((size_t)nt * 12),
+                 o_pos = c.take((size_t)nt * 3), o_cnt = c.take(32);
+    staging st(ctx);
+    char* io = (char*)st.slot(SLOT_MESH_IO, c.off);
+    if (st.rc) return st.rc;
+    st.put(io + o_tris, tris, tri_bytes(itype, nt));
+    st.back(offsets, io + o_offs, (size_t)(nv + 1) * 8);
+    st.back(tri, io + o_tri, (size_t)nt * 12);
+    st.back(pos, io + o_pos, (size_t)nt * 3);
+    st.back(counts, io + o_cnt, 32);
+    if (!st.rc) st.rc = f3d_mesh_vertex_map_dev(ctx, io + o_tris, itype, nt, nv, (int64_t*)(io + o_offs), (int32_t*)(io + o_tri),
+                                                (int8_t*)(io + o_pos), (int64_t*)(io + o_cnt), ctx->stream);
+    return st.finish(F3D_DEVERR_MESH);
+}
+
+int f3d_mesh_remove_faces_dev(f3d_ctx* ctx, const void* tris, int itype, int64_t nt, int64_t nv, const uint8_t* mask,
+                              uint8_t* not_removed, void* remaining, int64_t* old2new, int64_t* counts, void* stream) {
+    int rc = enter(ctx); if (rc) return rc;
+    if (!mesh_args_ok(nv, nt, itype, F3D_F64) || !counts || (nv > 0 && (!mask || !old2new)) || (nt > 0 && (!tris || !not_removed || !remaining)))
+        return fail(ctx, F3D_ERR_INVALID, "mesh_remove_faces: " F3D_MESH_BAD);
+    void* scratch;
+    if ((rc = ensure(ctx, SLOT_MESH, f3d_mesh_scratch_bytes(nv, nt), &scratch))) return rc;
+    F3D_HIP(ctx, f3d_launch_mesh_remove_faces(tris, itype, nt, nv, mask, not_removed, remaining, old2new, scratch, counts, ctx->dev_err,
+                                              pick(ctx, stream)));
+    return F3D_OK;
+}
+
+int f3d_mesh_remove_faces(f3d_ctx* ctx, const void* tris, int itype, int64_t nt, int64_t nv, const uint8_t* mask,
+                          uint8_t* not_removed, void* remaining, int64_t* old2new, int64_t* counts) {
+    int rc = enter(ctx); if (rc) return rc;
+    if (!mesh_args_ok(nv, nt, itype, F3D_F64) || !counts || (nv > 0 && (!mask || !old2new)) || (nt > 0 && (!tris || !not_removed || !remaining)))
+        return fail(ctx, F3D_ERR_INVALID, "mesh_remove_faces: " F3D_MESH_BAD);
+    f3d_carve c;
+    const size_t tb = tri_bytes(itype, nt);
+    const size_t o_tris = c.take(tb), o_mask = c.take((size_t)nv), o_nr = c.take((size_t)nt), o_rem = c.take(tb), o_o2n = c.take((size_t)nv * 8),
+                 o_cnt = c.take(32);
+    staging st(ctx);
+    char* io = (char*)st.slot(SLOT_MESH_IO, c.off);
+    if (st.rc) return st.rc;
+    st.put(io + o_tris, tris, tb);
+    st.put(io + o_mask, mask, (size_t)nv);
+    st.back(not_removed, io + o_nr, (size_t)nt);
+    st.back(remaining, io + o_rem, tb);
+    st.back(old2new, io + o_o2n, (size_t)nv * 8);
+    st.back(counts, io + o_cnt, 32);
+    if (!st.rc) st.rc = f3d_mesh_remove_faces_dev(ctx, io + o_tris, itype, nt, nv, (const uint8_t*)(io + o_mask), (uint8_t*)(io + o_nr), io + o_rem,
+                                                  (int64_t*)(io + o_o2n), (int64_t*)(io + o_cnt), ctx->stream);
+    return st.finish(F3D_DEVERR_MESH);
+}
+
+int f3d_mesh_keep_faces_dev(f3d_ctx* ctx, const void* verts, int vdtype, int64_t nv, const void* tris, int itype, int64_t nt,
+                            const uint8_t* mask, void* out_verts, void* out_tris, int64_t* counts, void* stream) {
+    int rc = enter(ctx); if (rc) return rc;
+    if (!mesh_args_ok(nv, nt, itype, vdtype) || !counts || (nv > 0 && (!verts || !mask)) || (nt > 0 && (!tris || !out_tris)) ||
+        (nt > 0 && nv > 0 && !out_verts))
+        return fail(ctx, F3D_ERR_INVALID, "mesh_keep_faces: " F3D_MESH_BAD);
+    void* scratch;
+    if ((rc = ensure(ctx, SLOT_MESH, f3d_mesh_scratch_bytes(nv, nt), &scratch))) return rc;
+    F3D_HIP(ctx, f3d_launch_mesh_keep_faces(verts, vdtype, nv, tris, itype, nt, mask, out_verts, out_tris, scratch, counts, ctx->dev_err,
+                                            pick(ctx, stream)));
+    return F3D_OK;
+}
+
+int f3d_mesh_keep_faces(f3d_ctx* ctx, const void* verts, int vdtype, int64_t nv, const void* tris, int itype, int64_t nt,
+                        const uint8_t* mask, void* out_verts, void* out_tris, int64_t* counts) {
+    int rc = enter(ctx); if (rc) return rc;
+    if (!mesh_args_ok(nv, nt, itype, vdtype) || !counts || (nv > 0 && (!verts || !mask)) || (nt > 0 && (!tris || !out_tris)) ||
+        (nt > 0 && nv > 0 && !out_verts))
+        return fail(ctx, F3D_ERR_INVALID, "mesh_keep_faces: " F3D_MESH_BAD);
+    f3d_carve c;
+    const size_t tb = tri_bytes(itype, nt), vb = xyz_bytes((f3d_dtype)vdtype, nv), ob = xyz_bytes((f3d_dtype)vdtype, 3 * nt < nv ? 3 * nt : nv);
+    const size_t o_verts = c.take(vb), o_tris = c.take(tb), o_mask = c.take((size_t)nv), o_ov = c.take(ob), o_ot = c.take(tb), o_cnt = c.take(32);
+    staging st(ctx);
+    char* io = (char*)st.slot(SLOT_MESH_IO, c.off);
+    if (st.rc) return st.rc;
+    st.put(io + o_verts, verts, vb);
+    st.put(io + o_tris, tris, tb);
+    st.put(io + o_mask, mask, (size_t)nv);
+    st.back(out_verts, io + o_ov, ob);
+    st.back(out_tris, io + o_ot, tb);
+    st.back(counts, io + o_cnt, 32);
+    if (!st.rc) st.rc = f3d_mesh_keep_faces_dev(ctx, io + o_verts, vdtype, nv, io + o_tris, itype, nt, (const uint8_t*)(io + o_mask), io + o_ov,
+                                                io + o_ot, (int64_t*)(io + o_cnt), ctx->stream);
+    return st.finish(F3D_DEVERR_MESH);
+}
+
+int f3d_mesh_triangle_clusters_dev(f3d_ctx* ctx, const void* verts, int vdtype, int64_t nv, const void* tris, int itype,
+                                   int64_t nt, int32_t* clusters, int64_t* cluster_n, double* cluster_area, double* tri_area,
+                                   int64_t* counts, void* stream) {
+    int rc = enter(ctx); if (rc) return rc;
+    if (!mesh_args_ok(nv, nt, itype, vdtype) || !counts || (nv > 0 && !verts) || (nt > 0 && (!tris || !clusters || !cluster_n || !cluster_area)))
+        return fail(ctx, F3D_ERR_INVALID, "mesh_triangle_clusters: " F3D_MESH_BAD);
+    void* scratch;
+    if ((rc = ensure(ctx, SLOT_MESH, f3d_mesh_scratch_bytes(nv, nt), &scratch))) return rc;
+    F3D_HIP(ctx, f3d_launch_mesh_clusters(verts, vdtype, nv, tris, itype, nt, clusters, cluster_n, cluster_area, tri_area, scratch, counts,
+                                          ctx->dev_err, pick(ctx, stream)));
+    return F3D_OK;
+}
+
+int f3d_mesh_triangle_clusters(f3d_ctx* ctx, const void* verts, int vdtype, int64_t nv, const void* tris, int itype, int64_t nt,
+                               int32_t* clusters, int64_t* cluster_n, double* cluster_area, double* tri_area, int64_t* counts) {
+    int rc = enter(ctx); if (rc) return rc;
+    if (!mesh_args_ok(nv, nt, itype, vdtype) || !counts || (nv > 0 && !verts) || (nt > 0 && (!tris || !clusters || !cluster_n || !cluster_area)))
+        return fail(ctx, F3D_ERR_INVALID, "mesh_triangle_clusters: " F3D_MESH_BAD);
+    f3d_carve c;
+    const size_t tb = tri_bytes(itype, nt), vb = xyz_bytes((f3d_dtype)vdtype, nv);
+    const size_t o_verts = c.take(vb), o_tris = c.take(tb), o_cl = c.take((size_t)nt * 4), o_n = c.take((size_t)nt * 8), o_a = c.take((size_t)nt * 8),
+                 o_ta = c.take((size_t)nt * 8), o_cnt = c.take(32);
+    staging st(ctx);
+    char* io = (char*)st.slot(SLOT_MESH_IO, c.off);
+    if (st.rc) return st.rc;
+    st.put(io + o_verts, verts, vb);
+    st.put(io + o_tris, tris, tb);
+    st.back(clusters, io + o_cl, (size_t)nt * 4);
+    st.back(cluster_n, io + o_n, (size_t)nt * 8);
+    st.back(cluster_area, io + o_a, (size_t)nt * 8);
+    st.back(tri_area, io + o_ta, (size_t)nt * 8);
+    st.back(counts, io + o_cnt, 32);
+    if (!st.rc) st.rc = f3d_mesh_triangle_clusters_dev(ctx, io + o_verts, vdtype, nv, io + o_tris, itype, nt, (int32_t*)(io + o_cl),
+                                                       (int64_t*)(io + o_n), (double*)(io + o_a), tri_area ? (double*)(io + o_ta) : nullptr,
+                                                       (int64_t*)(io + o_cnt), ctx->stream);
+    return st.finish(F3D_DEVERR_MESH);
+}
+
+int f3d_mesh_clean_dev(f3d_ctx* ctx, const void* verts, int vdtype, int64_t nv, const void* tris, int itype, int64_t nt,
+                       const uint8_t* remove_mask, int64_t min_triangles, double min_area, void* new_verts, void* new_tris,
+                       uint8_t* kept_v, uint8_t* kept_t, int64_t* counts, void* stream) {
+    int rc = enter(ctx); if (rc) return rc;
+    if (!mesh_args_ok(nv, nt, itype, vdtype) || !counts || (nv > 0 && (!verts || !new_verts || !kept_v)) || (nt > 0 && (!tris || !new_tris || !kept_t)))
+        return fail(ctx, F3D_ERR_INVALID, "mesh_clean: " F3D_MESH_BAD);
+    void* scratch;
+    if ((rc = ensure(ctx, SLOT_MESH, f3d_mesh_scratch_bytes(nv, nt), &scratch))) return rc;
+    F3D_HIP(ctx, f3d_launch_mesh_clean(verts, vdtype, nv, tris, itype, nt, remove_mask, min_triangles, min_area, new_verts, new_tris, kept_v,
+                                       kept_t, scratch, counts, ctx->dev_err, pick(ctx, stream)));
+    return F3D_OK;
+}
+
+int f3d_mesh_clean(f3d_ctx* ctx, const void* verts, int vdtype, int64_t nv, const void* tris, int itype, int64_t nt,
+                   const uint8_t* remove_mask, int64_t min_triangles, double min_area, void* new_verts, void* new_tris,
+                   uint8_t* kept_v, uint8_t* kept_t, int64_t* counts) {
+    int rc = enter(ctx); if (rc) return rc;
+    if (!mesh_args_ok(nv, nt, itype, vdtype) || !counts || (nv > 0 && (!verts || !new_verts || !kept_v)) || (nt > 0 && (!tris || !new_tris || !kept_t)))
+        return fail(ctx, F3D_ERR_INVALID, "mesh_clean: " F3D_MESH_BAD);
+    f3d_carve c;
+    const size_t tb = tri_bytes(itype, nt), vb = xyz_bytes((f3d_dtype)vdtype, nv);
+    const size_t o_verts = c.take(vb), o_tris = c.take(tb), o_mask = c.take((size_t)nv), o_nv = c.take(vb), o_nt = c.take(tb),
+                 o_kv = c.take((size_t)nv), o_kt = c.take((size_t)nt), o_cnt = c.take(32);
+    staging st(ctx);
+    char* io = (char*)st.slot(SLOT_MESH_IO, c.off);
+    if (st.rc) return st.rc;
+    st.put(io + o_verts, verts, vb);
+    st.put(io + o_tris, tris, tb);
+    st.put(io + o_mask, remove_mask, (size_t)nv);
+    st.back(new_verts, io + o_nv, vb);
+    st.back(new_tris, io + o_nt, tb);
+    st.back(kept_v, io + o_kv, (size_t)nv);
+    st.back(kept_t, io + o_kt, (size_t)nt);
+    st.back(counts, io + o_cnt, 32);
+    if (!st.rc) st.rc = f3d_mesh_clean_dev(ctx, io + o_verts, vdtype, nv, io + o_tris, itype, nt, remove_mask ? (const uint8_t*)(io + o_mask) : nullptr,
+                                           min_triangles, min_area, io + o_nv, io + o_nt, (uint8_t*)(io + o_kv), (uint8_t*)(io + o_kt),
+                                           (int64_t*)(io + o_cnt), ctx->stream);
+    return st.finish(F3D_DEVERR_MESH);
 }
 
 // ---------------------------------------------------------------------------------------------

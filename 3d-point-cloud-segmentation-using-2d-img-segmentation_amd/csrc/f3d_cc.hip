@@ -5,8 +5,7 @@
 // seed is its connected component in the graph restricted to same-class edges, and "lowest remaining index" is the
 // component's minimum index.  That is what this file computes: a lock-free union-find where the larger root is
 // always linked under the smaller one (so every component ends rooted at its minimum index), one pass over the
-// CSR edges, then a compression pass.  Parent reads are agent-scope relaxed atomic loads (served by L2): a CU's L1 is
-// not coherent with other CUs' atomics, and the CAS return value -- always current -- drives the retry.
+// CSR edges, then a compression pass.  The union-find itself (f3d_find_root, f3d_uf_link) lives in f3d_kernels.h.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <rocprim/device/device_radix_sort.hpp>
@@ -17,18 +16,6 @@
 namespace {
 
 constexpr int CB = 256;
-
-__device__ __forceinline__ int32_t ld(const int32_t* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-
-__device__ __forceinline__ int32_t find_root(int32_t* parent, int32_t x) {
-    for (;;) {
-        const int32_t p = ld(parent + x);
-        if (p == x) return x;
-        const int32_t gp = ld(parent + p);
-        if (gp != p) __hip_atomic_store(parent + x, gp, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // path halving (any ancestor is valid)
-        x = p;
-    }
-}
 
 __global__ __launch_bounds__(CB) void k_cc_init(int32_t* __restrict__ parent, int64_t n) {
     for (int64_t i = (int64_t)blockIdx.x * CB + threadIdx.x; i < n; i += (int64_t)gridDim.x * CB) parent[i] = (int32_t)i;
@@ -42,15 +29,7 @@ __global__ __launch_bounds__(CB) void k_cc_hook(const int64_t* __restrict__ clas
             const int64_t j = nbrs[e];
             if (j < 0 || j >= n) { atomicOr(err, errbit); continue; }
             if (j == i || classes[j] != ci) continue;
-            int32_t a = (int32_t)i, b = (int32_t)j;
-            for (;;) {
-                a = find_root(parent, a); b = find_root(parent, b);
-                if (a == b) break;
-                if (a < b) { const int32_t t = a; a = b; b = t; }            // a = larger root, goes under b
-                const int32_t old = atomicCAS(parent + a, a, b);
-                if (old == a) break;
-                a = old;                                                     // someone else linked a first: continue from there
-            }
+            f3d_uf_link(parent, (int32_t)i, (int32_t)j);
         }
     }
 }
@@ -58,7 +37,7 @@ __global__ __launch_bounds__(CB) void k_cc_hook(const int64_t* __restrict__ clas
 __global__ __launch_bounds__(CB) void k_cc_compress(int32_t* parent, int64_t n, int64_t* __restrict__ root) {
     for (int64_t i = (int64_t)blockIdx.x * CB + threadIdx.x; i < n; i += (int64_t)gridDim.x * CB) {
         int32_t x = (int32_t)i;
-        for (;;) { const int32_t p = ld(parent + x); if (p == x) break; x = p; }
+        for (;;) { const int32_t p = f3d_uf_load(parent + x); if (p == x) break; x = p; }
         root[i] = x;
     }
 }

@@ -14,7 +14,8 @@
 #define F3D_DEVERR_QUADS 32                // door_window_quads: triangle vertex index out of bounds
 #define F3D_DEVERR_GROW 64                 // region_grow: seed or neighbour index out of bounds, or a repeated seed
 #define F3D_DEVERR_PVOTE 128               // point_vote_frames: a pixel with a neighbour carries a label > nclasses (voting.py:257)
-#define F3D_DEVERR_ALL 255
+#define F3D_DEVERR_MESH 256                // meshUtils: triangle vertex index outside [0, nv)
+#define F3D_DEVERR_ALL 511
 #define F3D_PLANES_PER_LAUNCH 16
 #define F3D_OBB_MAX_BOXES 4096
 #define F3D_SORT_MAX_CELLS 32767            // + 1 overflow cell = 2^15 keys -> 16 key bits sorted
@@ -51,6 +52,33 @@ __device__ __forceinline__ void f3d_block_scan(int v, int* lds, int& ex, int& to
     ex = lds[t] - v;
     tot = lds[NT - 1];
     __syncthreads();
+}
+
+// Lock-free union-find over int32 parents (f3d_cc.hip, f3d_mesh.hip): the larger root is always linked under the smaller one, so
+// every component ends rooted at its minimum index.  Parent reads are agent-scope relaxed atomic loads (served by L2): a CU's L1
+// is not coherent with other CUs' atomics, and the CAS return value -- always current -- drives the retry.
+__device__ __forceinline__ int32_t f3d_uf_load(const int32_t* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+
+__device__ __forceinline__ int32_t f3d_find_root(int32_t* parent, int32_t x) {
+    for (;;) {
+        const int32_t p = f3d_uf_load(parent + x);
+        if (p == x) return x;
+        const int32_t gp = f3d_uf_load(parent + p);
+        if (gp != p) __hip_atomic_store(parent + x, gp, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // path halving (any ancestor is valid)
+        x = p;
+    }
+}
+
+// joins the components of a and b
+__device__ __forceinline__ void f3d_uf_link(int32_t* parent, int32_t a, int32_t b) {
+    for (;;) {
+        a = f3d_find_root(parent, a); b = f3d_find_root(parent, b);
+        if (a == b) break;
+        if (a < b) { const int32_t t = a; a = b; b = t; }            // a = larger root, goes under b
+        const int32_t old = atomicCAS(parent + a, a, b);
+        if (old == a) break;
+        a = old;                                                     // someone else linked a first: continue from there
+    }
 }
 
 // One level of an ordered FIFO flood run by one workgroup of NT threads (f3d_color.hip, f3d_refine.hip).  `list[0..cnt)` are the
@@ -404,3 +432,20 @@ hipError_t f3d_launch_pvote_frames(const void* queries, int qdtype, const uint8_
                                    const f3d_gridview& gv, const f3d_graphgrid& g, const f3d_pvote_box& box, double r2, double* votes,
                                    uint32_t* bits, int group, const int* words, const int* err, hipStream_t s);
 hipError_t f3d_launch_pvote_flag(const int* words, int limit, int* err, hipStream_t s);
+
+// meshUtils (f3d_mesh.hip): triangles [nt, 3] of `itype` (F3D_I64 / F3D_I32), vertices [nv, 3] of `vdtype`.  counts: device int64[4] =
+// {first size, second size, 1 when a vertex index is outside [0, nv) (then nothing else is written and `errbit` is set), spare}.
+// Enqueue only.  scratch: f3d_mesh_scratch_bytes(nv, nt) for every entry
+size_t f3d_mesh_scratch_bytes(int64_t nv, int64_t nt);
+hipError_t f3d_launch_mesh_vertex_map(const void* tris, int itype, int64_t nt, int64_t nv, int64_t* offsets, int32_t* tri, int8_t* pos,
+                                      void* scratch, int64_t* counts, int* err, hipStream_t s);
+hipError_t f3d_launch_mesh_remove_faces(const void* tris, int itype, int64_t nt, int64_t nv, const uint8_t* mask, uint8_t* not_removed,
+                                        void* remaining, int64_t* old2new, void* scratch, int64_t* counts, int* err, hipStream_t s);
+hipError_t f3d_launch_mesh_keep_faces(const void* verts, int vdtype, int64_t nv, const void* tris, int itype, int64_t nt, const uint8_t* mask,
+                                      void* out_verts, void* out_tris, void* scratch, int64_t* counts, int* err, hipStream_t s);
+hipError_t f3d_launch_mesh_clusters(const void* verts, int vdtype, int64_t nv, const void* tris, int itype, int64_t nt, int32_t* clusters,
+                                    int64_t* cluster_n, double* cluster_area, double* tri_area, void* scratch, int64_t* counts, int* err,
+                                    hipStream_t s);
+hipError_t f3d_launch_mesh_clean(const void* verts, int vdtype, int64_t nv, const void* tris, int itype, int64_t nt, const uint8_t* remove_mask,
+                                 int64_t min_triangles, double min_area, void* new_verts, void* new_tris, uint8_t* kept_v, uint8_t* kept_t,
+                                 void* scratch, int64_t* counts, int* err, hipStream_t s);

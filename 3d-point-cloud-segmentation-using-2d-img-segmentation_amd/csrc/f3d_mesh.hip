@@ -1,0 +1,530 @@
+// Mesh topology of segUtils/meshUtils.py (reference :235-333, :360-375) on gfx950, plus clean_mesh, their composition.
+//
+// The slot of a triangle corner is s = 3 * f + j.  Three building blocks serve every entry:
+//   group   : a stable rocPRIM radix sort of (key, position) pairs and a lower-bound kernel -> a CSR whose rows list their members
+//             in ascending position (vertex -> slots for vertex_triangle_mapping, cluster -> triangles for the area sums);
+//   compact : 0 / 1 flags of the vertices and of the faces in ONE array, one exclusive scan, one kernel that writes the
+//             renumbered faces (face order kept), the old -> new vertex ids and, when wanted, the surviving vertex rows;
+//   cluster : 3 edge keys (min << b | max, b = bits of nv) per triangle, radix sort limited to 2b (+1) bits, union of the triangles
+//             of equal neighbouring keys (f3d_uf_link: a root is its component's lowest triangle), compression, roots flagged
+//             and scanned -> clusters numbered by their lowest triangle.
+// keep_faces_by_vertices' first-appearance numbering: first[v] = atomicMin of the slots of kept faces that hold v; slot s is a
+// first occurrence iff first[tri[s]] == s; the scan of those flags over the slots is the new id.  Minima, not timing, decide.
+// Areas: 0.5 * sqrt((cx*cx + cy*cy) + cz*cz), c = cross(p0 - p1, p0 - p2) by plain multiply and subtract (no contraction).  A
+// cluster's members, in ascending triangle index, are cut into chunks of 4096; a chunk is summed by one wave (lane l adds the items
+// l, l + 64, l + 128, ... left to right, then the 64 lane sums meet in an xor butterfly, offsets 32, 16, .., 1) and the chunk sums
+// are summed the same way.  The shape depends on the member count alone; no float atomics.
+// Every kernel after k_mesh_check returns at once when counts[2] is set (an index outside [0, nv)): nothing is written.
+#include <hip/hip_runtime.h>
+#include <math.h>
+#include <stdint.h>
+#include <rocprim/device/device_radix_sort.hpp>
+#include <rocprim/device/device_scan.hpp>
+#include "f3d.h"
+#include "f3d_kernels.h"
+
+#pragma clang fp contract(off)
+
+namespace {
+
+constexpr int MB = 256;
+constexpr int MGRID = 8192;
+constexpr int AREA_CHUNK = 4096;          // members per chunk of a cluster's area sum
+
+#define MESH_LOOP(i, n) for (int64_t i = (int64_t)blockIdx.x * MB + threadIdx.x; i < (n); i += (int64_t)gridDim.x * MB)
+
+__device__ __forceinline__ int64_t tri_at(const void* __restrict__ tris, int itype, int64_t s) {
+    return itype == F3D_I32 ? (int64_t)reinterpret_cast<const int32_t*>(tris)[s] : reinterpret_cast<const int64_t*>(tris)[s];
+}
+
+__device__ __forceinline__ void tri_put(void* __restrict__ tris, int itype, int64_t s, int64_t v) {
+    if (itype == F3D_I32) reinterpret_cast<int32_t*>(tris)[s] = (int32_t)v; else reinterpret_cast<int64_t*>(tris)[s] = v;
+}
+
+// row `from` of src -> row `to` of dst, [*, 3] of float64 or float32, bit for bit
+__device__ __forceinline__ void row_copy(const void* __restrict__ src, void* __restrict__ dst, int vdtype, int64_t from, int64_t to) {
+    if (vdtype == F3D_F64) {
+        const uint64_t* a = reinterpret_cast<const uint64_t*>(src) + 3 * from;
+        uint64_t* b = reinterpret_cast<uint64_t*>(dst) + 3 * to;
+        b[0] = a[0]; b[1] = a[1]; b[2] = a[2];
+    } else {
+        const uint32_t* a = reinterpret_cast<const uint32_t*>(src) + 3 * from;
+        uint32_t* b = reinterpret_cast<uint32_t*>(dst) + 3 * to;
+        b[0] = a[0]; b[1] = a[1]; b[2] = a[2];
+    }
+}
+
+__device__ __forceinline__ double coord(const void* __restrict__ verts, int vdtype, int64_t i) {
+    return vdtype == F3D_F64 ? reinterpret_cast<const double*>(verts)[i] : (double)reinterpret_cast<const float*>(verts)[i];
+}
+
+// counts[2] = 1 and the error bit when a corner is outside [0, nv)
+__global__ __launch_bounds__(MB) void k_mesh_check(const void* __restrict__ tris, int itype, int64_t n3, int64_t nv, int64_t* counts,
+                                                   int* err, int errbit) {
+    bool bad = false;
+    MESH_LOOP(s, n3) {
+        const int64_t v = tri_at(tris, itype, s);
+        bad |= (v < 0) | (v >= nv);
+    }
+    if (bad) { counts[2] = 1; atomicOr(err, errbit); }
+}
+
+// ---- group ------------------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(MB) void k_mesh_corner_keys(const void* __restrict__ tris, int itype, int64_t n3, const int64_t* counts,
+                                                         uint32_t* __restrict__ keys, uint32_t* __restrict__ vals) {
+    if (counts[2]) return;
+    MESH_LOOP(s, n3) { keys[s] = (uint32_t)tri_at(tris, itype, s); vals[s] = (uint32_t)s; }
+}
+
+// offsets[k] = first position of key k in the sorted keys, k = 0 .. nkeys (nkeys_dev, when given, holds nkeys)
+__global__ __launch_bounds__(MB) void k_mesh_lower_bound(const uint32_t* __restrict__ keys, int64_t n, int64_t nkeys,
+                                                         const uint32_t* __restrict__ nkeys_dev, const int64_t* counts,
+                                                         int64_t* __restrict__ offsets) {
+    if (counts[2]) return;
+    if (nkeys_dev) nkeys = (int64_t)*nkeys_dev;
+    MESH_LOOP(k, nkeys + 1) {
+        int64_t lo = 0, hi = n;
+        while (lo < hi) {
+            const int64_t mid = (lo + hi) >> 1;
+            if ((int64_t)keys[mid] < k) lo = mid + 1; else hi = mid;
+        }
+        offsets[k] = lo;
+    }
+}
+
+__global__ __launch_bounds__(MB) void k_mesh_vmap_out(const uint32_t* __restrict__ slots, int64_t n3, const int64_t* counts,
+                                                      int32_t* __restrict__ tri, int8_t* __restrict__ pos) {
+    if (counts[2]) return;
+    MESH_LOOP(i, n3) {
+        const uint32_t s = slots[i];
+        tri[i] = (int32_t)(s / 3u);
+        pos[i] = (int8_t)(s % 3u);
+    }
+}
+
+// ---- compact ----------------------------------------------------------------------------------------------------------
+// face_off[f] = 1 when a corner of f has vmask set (else 0), or the reverse with `invert`
+__global__ __launch_bounds__(MB) void k_mesh_face_touch(const void* __restrict__ tris, int itype, int64_t nt, const uint8_t* __restrict__ vmask,
+                                                        int invert, const int64_t* counts, uint8_t* __restrict__ out) {
+    if (counts[2]) return;
+    MESH_LOOP(f, nt) {
+        const bool touch = vmask[tri_at(tris, itype, 3 * f)] | vmask[tri_at(tris, itype, 3 * f + 1)] | vmask[tri_at(tris, itype, 3 * f + 2)];
+        out[f] = (uint8_t)(touch != (invert != 0));
+    }
+}
+
+// flags[0 .. nv) = vertex kept (vmask != 0, reversed with `invert`), flags[nv .. nv + nt) = fkeep, flags[nv + nt] = 0
+__global__ __launch_bounds__(MB) void k_mesh_flags(int64_t nv, int64_t nt, const uint8_t* __restrict__ vmask, int invert,
+                                                   const uint8_t* __restrict__ fkeep, const int64_t* counts, uint32_t* __restrict__ flags) {
+    if (counts[2]) return;
+    MESH_LOOP(i, nv + nt + 1) {
+        uint32_t v = 0;
+        if (i < nv) v = (vmask[i] != 0) != (invert != 0);
+        else if (i < nv + nt) v = fkeep[i - nv] != 0;
+        flags[i] = v;
+    }
+}
+
+// scan = the exclusive scan of k_mesh_flags' array.  old2new (may be NULL): the new id of a kept vertex, 0 for a dropped one;
+// out_verts (may be NULL): the kept rows; out_tris: the kept faces renumbered, in face order; counts = {faces, vertices}
+__global__ __launch_bounds__(MB) void k_mesh_compact(const void* __restrict__ tris, int itype, int64_t nt, int64_t nv,
+                                                     const uint32_t* __restrict__ scan, const void* __restrict__ verts, int vdtype,
+                                                     void* __restrict__ out_tris, int64_t* __restrict__ old2new, void* __restrict__ out_verts,
+                                                     int64_t* counts) {
+    if (counts[2]) return;
+    const uint32_t fbase = scan[nv];
+    MESH_LOOP(i, nv + nt) {
+        const uint32_t at = scan[i];
+        const bool kept = scan[i + 1] != at;
+        if (i < nv) {
+            if (old2new) old2new[i] = kept ? (int64_t)at : 0;
+            if (out_verts && kept) row_copy(verts, out_verts, vdtype, i, at);
+        } else if (kept) {
+            const int64_t f = i - nv, to = (int64_t)(at - fbase);
+            for (int j = 0; j < 3; ++j) tri_put(out_tris, itype, 3 * to + j, (int64_t)scan[tri_at(tris, itype, 3 * f + j)]);
+        }
+        if (i == 0) { counts[0] = (int64_t)(scan[nv + nt] - fbase); counts[1] = (int64_t)fbase; }
+    }
+}
+
+// ---- keep_faces_by_vertices -------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(MB) void k_mesh_keep_first(const void* __restrict__ tris, int itype, int64_t nt, const uint8_t* __restrict__ mask,
+                                                        const int64_t* counts, uint32_t* first, uint8_t* __restrict__ fkeep) {
+    if (counts[2]) return;
+    MESH_LOOP(f, nt) {
+        const int64_t a = tri_at(tris, itype, 3 * f), b = tri_at(tris, itype, 3 * f + 1), c = tri_at(tris, itype, 3 * f + 2);
+        const bool k = mask[a] | mask[b] | mask[c];
+        fkeep[f] = k;
+        if (k) {
+            atomicMin(first + a, (uint32_t)(3 * f));
+            atomicMin(first + b, (uint32_t)(3 * f + 1));
+            atomicMin(first + c, (uint32_t)(3 * f + 2));
+        }
+    }
+}
+
+// flags[0 .. 3nt) = the slot is its vertex's first occurrence over the kept faces, flags[3nt .. 4nt) = fkeep, flags[4nt] = 0
+__global__ __launch_bounds__(MB) void k_mesh_keep_flags(const void* __restrict__ tris, int itype, int64_t nt, const uint32_t* __restrict__ first,
+                                                        const uint8_t* __restrict__ fkeep, const int64_t* counts, uint32_t* __restrict__ flags) {
+    if (counts[2]) return;
+    const int64_t n3 = 3 * nt;
+    MESH_LOOP(i, n3 + nt + 1) {
+        uint32_t v = 0;
+        if (i < n3) v = fkeep[i / 3] && first[tri_at(tris, itype, i)] == (uint32_t)i;
+        else if (i < n3 + nt) v = fkeep[i - n3] != 0;
+        flags[i] = v;
+    }
+}
+
+__global__ __launch_bounds__(MB) void k_mesh_keep_out(const void* __restrict__ verts, int vdtype, const void* __restrict__ tris, int itype,
+                                                      int64_t nt, const uint32_t* __restrict__ first, const uint32_t* __restrict__ scan,
+                                                      void* __restrict__ out_verts, void* __restrict__ out_tris, int64_t* counts) {
+    if (counts[2]) return;
+    const int64_t n3 = 3 * nt;
+    const uint32_t fbase = scan[n3];
+    MESH_LOOP(i, n3 + nt) {
+        const uint32_t at = scan[i];
+        if (scan[i + 1] != at) {
+            if (i < n3) row_copy(verts, out_verts, vdtype, tri_at(tris, itype, i), at);
+            else {
+                const int64_t f = i - n3, to = (int64_t)(at - fbase);
+                for (int j = 0; j < 3; ++j) tri_put(out_tris, itype, 3 * to + j, (int64_t)scan[first[tri_at(tris, itype, 3 * f + j)]]);
+            }
+        }
+        if (i == 0) { counts[0] = (int64_t)fbase; counts[1] = (int64_t)(scan[n3 + nt] - fbase); }
+    }
+}
+
+// ---- cluster ----------------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(MB) void k_mesh_area(const void* __restrict__ verts, int vdtype, const void* __restrict__ tris, int itype,
+                                                  int64_t nt, const int64_t* counts, double* __restrict__ area) {
+    if (counts[2]) return;
+    MESH_LOOP(f, nt) {
+        double p[3][3];
+        for (int j = 0; j < 3; ++j) {
+            const int64_t v = tri_at(tris, itype, 3 * f + j);
+            for (int c = 0; c < 3; ++c) p[j][c] = coord(verts, vdtype, 3 * v + c);
+        }
+        const double a0 = p[0][0] - p[1][0], a1 = p[0][1] - p[1][1], a2 = p[0][2] - p[1][2];
+        const double b0 = p[0][0] - p[2][0], b1 = p[0][1] - p[2][1], b2 = p[0][2] - p[2][2];
+        const double cx = a1 * b2 - a2 * b1, cy = a2 * b0 - a0 * b2, cz = a0 * b1 - a1 * b0;
+        area[f] = 0.5 * sqrt((cx * cx + cy * cy) + cz * cz);
+    }
+}
+
+__device__ __forceinline__ uint64_t edge_key(uint64_t u, uint64_t v, int b) { return u < v ? (u << b | v) : (v << b | u); }
+
+// the edges (0,1), (0,2), (1,2) of every triangle as min << b | max; a face that is not active carries bit 2b instead
+__global__ __launch_bounds__(MB) void k_mesh_edge_keys(const void* __restrict__ tris, int itype, int64_t nt, const uint8_t* __restrict__ active,
+                                                       int b, const int64_t* counts, uint64_t* __restrict__ keys, uint32_t* __restrict__ vals,
+                                                       int32_t* __restrict__ parent) {
+    if (counts[2]) return;
+    MESH_LOOP(f, nt) {
+        parent[f] = (int32_t)f;
+        const uint64_t v0 = (uint64_t)tri_at(tris, itype, 3 * f), v1 = (uint64_t)tri_at(tris, itype, 3 * f + 1),
+                       v2 = (uint64_t)tri_at(tris, itype, 3 * f + 2);
+        const bool on = !active || active[f];
+        const uint64_t off = (uint64_t)1 << (2 * b);
+        keys[3 * f] = on ? edge_key(v0, v1, b) : off;
+        keys[3 * f + 1] = on ? edge_key(v0, v2, b) : off;
+        keys[3 * f + 2] = on ? edge_key(v1, v2, b) : off;
+        vals[3 * f] = vals[3 * f + 1] = vals[3 * f + 2] = (uint32_t)f;
+    }
+}
+
+__global__ __launch_bounds__(MB) void k_mesh_union(const uint64_t* __restrict__ keys, const uint32_t* __restrict__ vals, int64_t n3, int b,
+                                                   const int64_t* counts, int32_t* parent) {
+    if (counts[2]) return;
+    MESH_LOOP(i, n3) {
+        if (i == 0) continue;
+        const uint64_t k = keys[i];
+        if (k != keys[i - 1] || (k >> (2 * b))) continue;
+        f3d_uf_link(parent, (int32_t)vals[i - 1], (int32_t)vals[i]);
+    }
+}
+
+// root[f] = lowest triangle of f's component; flags[f] = f is the root of an active component; flags[nt] = 0
+__global__ __launch_bounds__(MB) void k_mesh_roots(const int32_t* parent, int64_t nt, const uint8_t* __restrict__ active, const int64_t* counts,
+                                                   int32_t* __restrict__ root, uint32_t* __restrict__ flags) {
+    if (counts[2]) return;
+    MESH_LOOP(f, nt + 1) {
+        if (f == nt) { flags[f] = 0; continue; }
+        int32_t x = (int32_t)f;
+        for (;;) { const int32_t p = f3d_uf_load(parent + x); if (p == x) break; x = p; }
+        root[f] = x;
+        flags[f] = x == (int32_t)f && (!active || active[f]);
+    }
+}
+
+// clusters[f] = number of f's cluster (-1 for a face that is not active); the grouping keys of the area sums; counts[0] = clusters
+__global__ __launch_bounds__(MB) void k_mesh_labels(const int32_t* __restrict__ root, const uint32_t* __restrict__ scan, int64_t nt,
+                                                    const uint8_t* __restrict__ active, int32_t* __restrict__ clusters,
+                                                    uint32_t* __restrict__ gkeys, uint32_t* __restrict__ gvals, int64_t* counts) {
+    if (counts[2]) return;
+    MESH_LOOP(f, nt) {
+        const bool on = !active || active[f];
+        const uint32_t c = scan[root[f]];
+        clusters[f] = on ? (int32_t)c : -1;
+        gkeys[f] = on ? c : (uint32_t)nt;
+        gvals[f] = (uint32_t)f;
+        if (f == 0) counts[0] = (int64_t)scan[nt];
+    }
+}
+
+// wave_sum: lane l adds the items l, l + 64, l + 128, ... of [0, count) left to right, then the 64 lane sums meet in an xor butterfly
+template <typename At>
+__device__ __forceinline__ double wave_sum(int64_t count, int lane, At at) {
+    double acc = 0.0;
+    for (int64_t i = lane; i < count; i += 64) acc = acc + at(i);
+    for (int off = 32; off > 0; off >>= 1) acc = acc + __shfl_xor(acc, off);
+    return acc;
+}
+
+// partial[q] = wave_sum of the chunk of AREA_CHUNK consecutive members that starts at grouped position q.  A wave looks at 64
+// positions, finds the chunk starts among them (position - start of its cluster is a multiple of AREA_CHUNK) and sums each.
+__global__ __launch_bounds__(MB) void k_mesh_chunk_sums(const double* __restrict__ tri_area, const uint32_t* __restrict__ order,
+                                                        const uint32_t* __restrict__ skeys, const int64_t* __restrict__ starts,
+                                                        const uint32_t* __restrict__ nclusters, int64_t nt, const int64_t* counts,
+                                                        double* __restrict__ partial) {
+    if (counts[2]) return;
+    const int64_t P = (int64_t)*nclusters;
+    const int lane = threadIdx.x & 63;
+    for (int64_t w0 = (int64_t)blockIdx.x * MB + threadIdx.x - lane; w0 < nt; w0 += (int64_t)gridDim.x * MB) {
+        const int64_t p = w0 + lane;
+        bool head = false;
+        long long e = 0;
+        if (p < nt) {
+            const int64_t c = (int64_t)skeys[p];
+            if (c < P) { e = starts[c + 1]; head = ((p - starts[c]) % AREA_CHUNK) == 0; }
+        }
+        unsigned long long todo = __ballot(head);
+        while (todo) {
+            const int src = __ffsll((long long)todo) - 1;
+            todo &= todo - 1;
+            const int64_t q = w0 + src, ce = (int64_t)__shfl(e, src);
+            const int64_t len = ce - q < AREA_CHUNK ? ce - q : AREA_CHUNK;
+            const double sum = wave_sum(len, lane, [&](int64_t i) { return tri_area[order[q + i]]; });
+            if (lane == 0) partial[q] = sum;
+        }
+    }
+}
+
+// one wave per cluster: the member count, and the area = wave_sum of the cluster's chunk sums
+__global__ __launch_bounds__(MB) void k_mesh_cluster_sums(const double* __restrict__ partial, const int64_t* __restrict__ starts,
+                                                          const uint32_t* __restrict__ nclusters, const int64_t* counts,
+                                                          int64_t* __restrict__ cluster_n, double* __restrict__ cluster_area) {
+    if (counts[2]) return;
+    const int64_t P = (int64_t)*nclusters;
+    const int lane = threadIdx.x & 63;
+    for (int64_t c = ((int64_t)blockIdx.x * MB + threadIdx.x) >> 6; c < P; c += ((int64_t)gridDim.x * MB) >> 6) {
+        const int64_t b = starts[c], e = starts[c + 1];
+        const double sum = wave_sum((e - b + AREA_CHUNK - 1) / AREA_CHUNK, lane, [&](int64_t j) { return partial[b + j * AREA_CHUNK]; });
+        if (lane == 0) { cluster_n[c] = e - b; cluster_area[c] = sum; }
+    }
+}
+
+// ---- clean_mesh -------------------------------------------------------------------------------------------------------
+// kept_t[f] = f's cluster has at least min_triangles members and its area is not below min_area; kept_v (zeroed before) = 1 at
+// the corners of the kept faces
+__global__ __launch_bounds__(MB) void k_mesh_clean_keep(const void* __restrict__ tris, int itype, int64_t nt, const int32_t* __restrict__ clusters,
+                                                        const int64_t* __restrict__ cluster_n, const double* __restrict__ cluster_area,
+                                                        int64_t min_triangles, double min_area, const int64_t* counts,
+                                                        uint8_t* __restrict__ kept_t, uint8_t* kept_v) {
+    if (counts[2]) return;
+    MESH_LOOP(f, nt) {
+        const int32_t c = clusters[f];
+        const bool k = c >= 0 && cluster_n[c] >= min_triangles && !(cluster_area[c] < min_area);
+        kept_t[f] = k;
+        if (k) for (int j = 0; j < 3; ++j) kept_v[tri_at(tris, itype, 3 * f + j)] = 1;
+    }
+}
+
+int bits_for(int64_t v) { int b = 1; while (((int64_t)1 << b) < v) ++b; return b; }     // smallest b >= 1 with 2^b >= v
+
+struct mesh_layout {
+    size_t keys_a, keys_b, vals_a, vals_b, flags, parent, root, first, fkeep, active, clusters, cluster_n, cluster_area, tri_area, partial, starts, temp,
+        total;
+    size_t temp_bytes;
+};
+
+mesh_layout mesh_layout_for(int64_t nv, int64_t nt) {
+    if (nv < 1) nv = 1;
+    if (nt < 1) nt = 1;
+    mesh_layout L;
+    const size_t n3 = (size_t)nt * 3, nflags = (size_t)(nv + nt > 4 * nt ? nv + nt : 4 * nt) + 1;
+    size_t a = 0, b = 0, c = 0;
+    (void)rocprim::radix_sort_pairs(nullptr, a, (uint64_t*)nullptr, (uint64_t*)nullptr, (uint32_t*)nullptr, (uint32_t*)nullptr, n3, 0u, 64u);
+    (void)rocprim::radix_sort_pairs(nullptr, b, (uint32_t*)nullptr, (uint32_t*)nullptr, (uint32_t*)nullptr, (uint32_t*)nullptr, n3, 0u, 32u);
+    (void)rocprim::exclusive_scan(nullptr, c, (uint32_t*)nullptr, (uint32_t*)nullptr, (uint32_t)0, nflags, rocprim::plus<uint32_t>());
+    L.temp_bytes = (a > b ? (a > c ? a : c) : (b > c ? b : c)) + 256;
+    f3d_carve k;
+    L.keys_a = k.take(n3 * 8); L.keys_b = k.take(n3 * 8); L.vals_a = k.take(n3 * 4); L.vals_b = k.take(n3 * 4);
+    L.flags = k.take(nflags * 4);
+    L.parent = k.take((size_t)nt * 4); L.root = k.take((size_t)nt * 4); L.first = k.take((size_t)nv * 4);
+    L.fkeep = k.take((size_t)nt); L.active = k.take((size_t)nt);
+    L.clusters = k.take((size_t)nt * 4); L.cluster_n = k.take((size_t)nt * 8); L.cluster_area = k.take((size_t)nt * 8);
+    L.tri_area = k.take((size_t)nt * 8); L.partial = k.take((size_t)nt * 8); L.starts = k.take((size_t)(nt + 2) * 8);
+    L.temp = k.take(L.temp_bytes);
+    L.total = k.off;
+    return L;
+}
+
+#define MESH_TRY(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) return e_; } while (0)
+
+bool mesh_sizes_ok(int64_t nv, int64_t nt) { return nv >= 0 && nv <= 0x7fffffffLL && nt >= 0 && 3 * nt <= 0x7fffffffLL; }
+
+dim3 grid_of(int64_t n) { return dim3(f3d_grid_for(n, MB, MGRID)); }
+
+// counts = 0, then the index check
+hipError_t mesh_begin(const void* tris, int itype, int64_t nt, int64_t nv, int64_t* counts, int* err, hipStream_t s) {
+    MESH_TRY(hipMemsetAsync(counts, 0, 4 * sizeof(int64_t), s));
+    if (nt > 0) hipLaunchKernelGGL(k_mesh_check, grid_of(3 * nt), dim3(MB), 0, s, tris, itype, 3 * nt, nv, counts, err, F3D_DEVERR_MESH);
+    return hipGetLastError();
+}
+
+hipError_t mesh_scan(const mesh_layout& L, char* base, size_t n, hipStream_t s) {
+    size_t tb = L.temp_bytes;
+    uint32_t* flags = reinterpret_cast<uint32_t*>(base + L.flags);
+    return rocprim::exclusive_scan(base + L.temp, tb, flags, flags, (uint32_t)0, n, rocprim::plus<uint32_t>(), s);
+}
+
+// stable sort of the n (key, value) pairs in keys_a / vals_a by the low `bits` of the key -> keys_b / vals_b
+hipError_t mesh_sort32(const mesh_layout& L, char* base, size_t n, int bits, hipStream_t s) {
+    size_t tb = L.temp_bytes;
+    return rocprim::radix_sort_pairs(base + L.temp, tb, reinterpret_cast<uint32_t*>(base + L.keys_a), reinterpret_cast<uint32_t*>(base + L.keys_b),
+                                     reinterpret_cast<uint32_t*>(base + L.vals_a), reinterpret_cast<uint32_t*>(base + L.vals_b), n, 0u,
+                                     (unsigned)bits, s);
+}
+
+// the compaction: flags from vmask / fkeep, their scan, the outputs (k_mesh_compact)
+hipError_t mesh_compact(const mesh_layout& L, char* base, const void* verts, int vdtype, int64_t nv, const void* tris, int itype, int64_t nt,
+                        const uint8_t* vmask, int invert, const uint8_t* fkeep, void* out_tris, int64_t* old2new, void* out_verts,
+                        int64_t* counts, hipStream_t s) {
+    uint32_t* flags = reinterpret_cast<uint32_t*>(base + L.flags);
+    hipLaunchKernelGGL(k_mesh_flags, grid_of(nv + nt + 1), dim3(MB), 0, s, nv, nt, vmask, invert, fkeep, counts, flags);
+    MESH_TRY(hipGetLastError());
+    MESH_TRY(mesh_scan(L, base, (size_t)(nv + nt + 1), s));
+    hipLaunchKernelGGL(k_mesh_compact, grid_of(nv + nt), dim3(MB), 0, s, tris, itype, nt, nv, flags, verts, vdtype, out_tris, old2new, out_verts,
+                       counts);
+    return hipGetLastError();
+}
+
+// clusters of the active faces (all when active == NULL); cluster_n / cluster_area / tri_area hold nt entries
+hipError_t mesh_clusters(const mesh_layout& L, char* base, const void* verts, int vdtype, int64_t nv, const void* tris, int itype, int64_t nt,
+                         const uint8_t* active, int32_t* clusters, int64_t* cluster_n, double* cluster_area, double* tri_area, int64_t* counts,
+                         hipStream_t s) {
+    uint64_t *ka = reinterpret_cast<uint64_t*>(base + L.keys_a), *kb = reinterpret_cast<uint64_t*>(base + L.keys_b);
+    uint32_t *va = reinterpret_cast<uint32_t*>(base + L.vals_a), *vb = reinterpret_cast<uint32_t*>(base + L.vals_b);
+    uint32_t* flags = reinterpret_cast<uint32_t*>(base + L.flags);
+    int32_t *parent = reinterpret_cast<int32_t*>(base + L.parent), *root = reinterpret_cast<int32_t*>(base + L.root);
+    int64_t* starts = reinterpret_cast<int64_t*>(base + L.starts);
+    const dim3 g(grid_of(nt + 1)), g3(grid_of(3 * nt)), b(MB);
+    const int vb_bits = bits_for(nv);
+    hipLaunchKernelGGL(k_mesh_area, g, b, 0, s, verts, vdtype, tris, itype, nt, counts, tri_area);
+    hipLaunchKernelGGL(k_mesh_edge_keys, g, b, 0, s, tris, itype, nt, active, vb_bits, counts, ka, va, parent);
+    MESH_TRY(hipGetLastError());
+    size_t tb = L.temp_bytes;
+    MESH_TRY(rocprim::radix_sort_pairs(base + L.temp, tb, ka, kb, va, vb, (size_t)(3 * nt), 0u, (unsigned)(2 * vb_bits + (active ? 1 : 0)), s));
+    hipLaunchKernelGGL(k_mesh_union, g3, b, 0, s, kb, vb, 3 * nt, vb_bits, counts, parent);
+    hipLaunchKernelGGL(k_mesh_roots, g, b, 0, s, parent, nt, active, counts, root, flags);
+    MESH_TRY(hipGetLastError());
+    MESH_TRY(mesh_scan(L, base, (size_t)(nt + 1), s));
+    hipLaunchKernelGGL(k_mesh_labels, g, b, 0, s, root, flags, nt, active, clusters, reinterpret_cast<uint32_t*>(ka), va, counts);
+    MESH_TRY(hipGetLastError());
+    MESH_TRY(mesh_sort32(L, base, (size_t)nt, bits_for(nt + 1), s));
+    hipLaunchKernelGGL(k_mesh_lower_bound, g, b, 0, s, reinterpret_cast<const uint32_t*>(kb), nt, nt, flags + nt, counts, starts);
+    double* partial = reinterpret_cast<double*>(base + L.partial);
+    hipLaunchKernelGGL(k_mesh_chunk_sums, g, b, 0, s, tri_area, vb, reinterpret_cast<const uint32_t*>(kb), starts, flags + nt, nt, counts, partial);
+    hipLaunchKernelGGL(k_mesh_cluster_sums, dim3(f3d_grid_for(nt, MB / 64, MGRID)), b, 0, s, partial, starts, flags + nt, counts, cluster_n,
+                       cluster_area);
+    return hipGetLastError();
+}
+
+}  // namespace
+
+size_t f3d_mesh_scratch_bytes(int64_t nv, int64_t nt) { return mesh_layout_for(nv, nt).total; }
+
+hipError_t f3d_launch_mesh_vertex_map(const void* tris, int itype, int64_t nt, int64_t nv, int64_t* offsets, int32_t* tri, int8_t* pos,
+                                      void* scratch, int64_t* counts, int* err, hipStream_t s) {
+    if (!mesh_sizes_ok(nv, nt)) return hipErrorInvalidValue;
+    MESH_TRY(mesh_begin(tris, itype, nt, nv, counts, err, s));
+    if (nt == 0) return hipMemsetAsync(offsets, 0, (size_t)(nv + 1) * 8, s);
+    const mesh_layout L = mesh_layout_for(nv, nt);
+    char* base = reinterpret_cast<char*>(scratch);
+    const int64_t n3 = 3 * nt;
+    hipLaunchKernelGGL(k_mesh_corner_keys, grid_of(n3), dim3(MB), 0, s, tris, itype, n3, counts, reinterpret_cast<uint32_t*>(base + L.keys_a),
+                       reinterpret_cast<uint32_t*>(base + L.vals_a));
+    MESH_TRY(hipGetLastError());
+    MESH_TRY(mesh_sort32(L, base, (size_t)n3, bits_for(nv), s));
+    hipLaunchKernelGGL(k_mesh_lower_bound, grid_of(nv + 1), dim3(MB), 0, s, reinterpret_cast<const uint32_t*>(base + L.keys_b), n3, nv,
+                       (const uint32_t*)nullptr, counts, offsets);
+    hipLaunchKernelGGL(k_mesh_vmap_out, grid_of(n3), dim3(MB), 0, s, reinterpret_cast<const uint32_t*>(base + L.vals_b), n3, counts, tri, pos);
+    return hipGetLastError();
+}
+
+hipError_t f3d_launch_mesh_remove_faces(const void* tris, int itype, int64_t nt, int64_t nv, const uint8_t* mask, uint8_t* not_removed,
+                                        void* remaining, int64_t* old2new, void* scratch, int64_t* counts, int* err, hipStream_t s) {
+    if (!mesh_sizes_ok(nv, nt)) return hipErrorInvalidValue;
+    MESH_TRY(mesh_begin(tris, itype, nt, nv, counts, err, s));
+    const mesh_layout L = mesh_layout_for(nv, nt);
+    char* base = reinterpret_cast<char*>(scratch);
+    if (nt > 0) hipLaunchKernelGGL(k_mesh_face_touch, grid_of(nt), dim3(MB), 0, s, tris, itype, nt, mask, 1, counts, not_removed);
+    MESH_TRY(hipGetLastError());
+    return mesh_compact(L, base, nullptr, F3D_F64, nv, tris, itype, nt, mask, 1, not_removed, remaining, old2new, nullptr, counts, s);
+}
+
+hipError_t f3d_launch_mesh_keep_faces(const void* verts, int vdtype, int64_t nv, const void* tris, int itype, int64_t nt, const uint8_t* mask,
+                                      void* out_verts, void* out_tris, void* scratch, int64_t* counts, int* err, hipStream_t s) {
+    if (!mesh_sizes_ok(nv, nt)) return hipErrorInvalidValue;
+    MESH_TRY(mesh_begin(tris, itype, nt, nv, counts, err, s));
+    if (nt == 0) return hipSuccess;
+    const mesh_layout L = mesh_layout_for(nv, nt);
+    char* base = reinterpret_cast<char*>(scratch);
+    uint32_t *first = reinterpret_cast<uint32_t*>(base + L.first), *flags = reinterpret_cast<uint32_t*>(base + L.flags);
+    uint8_t* fkeep = reinterpret_cast<uint8_t*>(base + L.fkeep);
+    MESH_TRY(hipMemsetAsync(first, 0xff, (size_t)nv * 4, s));
+    hipLaunchKernelGGL(k_mesh_keep_first, grid_of(nt), dim3(MB), 0, s, tris, itype, nt, mask, counts, first, fkeep);
+    hipLaunchKernelGGL(k_mesh_keep_flags, grid_of(4 * nt + 1), dim3(MB), 0, s, tris, itype, nt, first, fkeep, counts, flags);
+    MESH_TRY(hipGetLastError());
+    MESH_TRY(mesh_scan(L, base, (size_t)(4 * nt + 1), s));
+    hipLaunchKernelGGL(k_mesh_keep_out, grid_of(4 * nt), dim3(MB), 0, s, verts, vdtype, tris, itype, nt, first, flags, out_verts, out_tris, counts);
+    return hipGetLastError();
+}
+
+hipError_t f3d_launch_mesh_clusters(const void* verts, int vdtype, int64_t nv, const void* tris, int itype, int64_t nt, int32_t* clusters,
+                                    int64_t* cluster_n, double* cluster_area, double* tri_area, void* scratch, int64_t* counts, int* err,
+                                    hipStream_t s) {
+    if (!mesh_sizes_ok(nv, nt)) return hipErrorInvalidValue;
+    MESH_TRY(mesh_begin(tris, itype, nt, nv, counts, err, s));
+    if (nt == 0) return hipSuccess;
+    const mesh_layout L = mesh_layout_for(nv, nt);
+    char* base = reinterpret_cast<char*>(scratch);
+    if (!tri_area) tri_area = reinterpret_cast<double*>(base + L.tri_area);
+    return mesh_clusters(L, base, verts, vdtype, nv, tris, itype, nt, nullptr, clusters, cluster_n, cluster_area, tri_area, counts, s);
+}
+
+hipError_t f3d_launch_mesh_clean(const void* verts, int vdtype, int64_t nv, const void* tris, int itype, int64_t nt, const uint8_t* remove_mask,
+                                 int64_t min_triangles, double min_area, void* new_verts, void* new_tris, uint8_t* kept_v, uint8_t* kept_t,
+                                 void* scratch, int64_t* counts, int* err, hipStream_t s) {
+    if (!mesh_sizes_ok(nv, nt)) return hipErrorInvalidValue;
+    MESH_TRY(mesh_begin(tris, itype, nt, nv, counts, err, s));
+    if (nv > 0) MESH_TRY(hipMemsetAsync(kept_v, 0, (size_t)nv, s));
+    if (nt == 0) return hipSuccess;
+    const mesh_layout L = mesh_layout_for(nv, nt);
+    char* base = reinterpret_cast<char*>(scratch);
+    uint8_t* active = nullptr;
+    if (remove_mask) {
+        active = reinterpret_cast<uint8_t*>(base + L.active);
+        hipLaunchKernelGGL(k_mesh_face_touch, grid_of(nt), dim3(MB), 0, s, tris, itype, nt, remove_mask, 1, counts, active);
+        MESH_TRY(hipGetLastError());
+    }
+    int32_t* clusters = reinterpret_cast<int32_t*>(base + L.clusters);
+    int64_t* cluster_n = reinterpret_cast<int64_t*>(base + L.cluster_n);
+    double* cluster_area = reinterpret_cast<double*>(base + L.cluster_area);
+    MESH_TRY(mesh_clusters(L, base, verts, vdtype, nv, tris, itype, nt, active, clusters, cluster_n, cluster_area,
+                           reinterpret_cast<double*>(base + L.tri_area), counts, s));
+    hipLaunchKernelGGL(k_mesh_clean_keep, grid_of(nt), dim3(MB), 0, s, tris, itype, nt, clusters, cluster_n, cluster_area, min_triangles, min_area,
+                       counts, kept_t, kept_v);
+    MESH_TRY(hipGetLastError());
+    return mesh_compact(L, base, verts, vdtype, nv, tris, itype, nt, kept_v, 0, kept_t, new_tris, nullptr, new_verts, counts, s);
+}

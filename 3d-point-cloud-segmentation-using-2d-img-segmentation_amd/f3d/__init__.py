@@ -29,6 +29,7 @@ NORM_PLAIN, NORM_FMA, NORM_HOST = 0, 1, 2   # how the fusion kernels take sqrt(v
 NORMALS_MAX_NN = 64          # F3D_NORMALS_MAX_NN: the largest max_nn of estimate_normals
 QUAD_OK, QUAD_HORIZONTAL, QUAD_NO_CANDIDATE = 0, 1, 2   # per-instance status of door_window_quads (f3d.h F3D_QUAD_*)
 QUADS_MAX_INST = 65535       # F3D_QUADS_MAX_INST
+I64, I32 = 0, 1              # f3d_itype: the index type of mesh triangles
 
 
 class F3DError(RuntimeError):
@@ -150,6 +151,17 @@ def library():
         'f3d_door_window_quads': (i32, [vp, vp, i64, vp, vp, i32, vp, i64, vp, i64, vp, vp, vp, vp]),
         'f3d_door_window_quads_dev': (i32, [vp, vp, i64, vp, vp, i32, vp, i64, vp, i64, vp, vp, vp, vp, vp]),
         'f3d_ctx_reserve_quads': (i32, [vp, i64, i32, i64]),
+        'f3d_mesh_vertex_map': (i32, [vp, vp, i32, i64, i64, vp, vp, vp, vp]),
+        'f3d_mesh_vertex_map_dev': (i32, [vp, vp, i32, i64, i64, vp, vp, vp, vp, vp]),
+        'f3d_mesh_remove_faces': (i32, [vp, vp, i32, i64, i64, vp, vp, vp, vp, vp]),
+        'f3d_mesh_remove_faces_dev': (i32, [vp, vp, i32, i64, i64, vp, vp, vp, vp, vp, vp]),
+        'f3d_mesh_keep_faces': (i32, [vp, vp, i32, i64, vp, i32, i64, vp, vp, vp, vp]),
+        'f3d_mesh_keep_faces_dev': (i32, [vp, vp, i32, i64, vp, i32, i64, vp, vp, vp, vp, vp]),
+        'f3d_mesh_triangle_clusters': (i32, [vp, vp, i32, i64, vp, i32, i64, vp, vp, vp, vp, vp]),
+        'f3d_mesh_triangle_clusters_dev': (i32, [vp, vp, i32, i64, vp, i32, i64, vp, vp, vp, vp, vp, vp]),
+        'f3d_mesh_clean': (i32, [vp, vp, i32, i64, vp, i32, i64, vp, i64, dbl, vp, vp, vp, vp, vp]),
+        'f3d_mesh_clean_dev': (i32, [vp, vp, i32, i64, vp, i32, i64, vp, i64, dbl, vp, vp, vp, vp, vp, vp]),
+        'f3d_ctx_reserve_mesh': (i32, [vp, i64, i64]),
         'f3d_patch_owner': (i32, [vp, vp, i64, i32, i32, i32, dbl, dbl, vp, vp, vp, vp, vp, vp]),
         'f3d_patch_owner_dev': (i32, [vp, vp, i64, i32, i32, i32, dbl, dbl, vp, vp, vp, vp, vp, vp, vp]),
         'f3d_patch_match': (i32, [vp, vp, i64, i32, i32, i32, dbl, dbl, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
@@ -193,6 +205,14 @@ def _f64(a, shape=None):
     if shape is not None and a.shape != tuple(shape):
         raise ValueError(f'expected shape {tuple(shape)}, got {a.shape}')
     return a
+
+
+def _itype(tris):
+    return I32 if tris.dtype == np.int32 else I64
+
+
+def _vdtype(verts):
+    return F32 if verts.dtype == np.float32 else F64
 
 
 def _raise(code, msg):
@@ -336,6 +356,10 @@ class Context:
     def reserve_quads(self, n, k, ntriangles):
         """Size the scratch of door_window_quads for n points, k instances and that many triangles."""
         self._check(self._lib.f3d_ctx_reserve_quads(self._h, int(n), int(k), int(ntriangles)))
+
+    def reserve_mesh(self, nvertices, ntriangles):
+        """Size the scratch of the mesh_*_dev calls for meshes of up to that many vertices and triangles."""
+        self._check(self._lib.f3d_ctx_reserve_mesh(self._h, int(nvertices), int(ntriangles)))
 
     def reserve_refine(self, n):
         """Size the scratch of region_grow_dev for clouds of up to n points."""
@@ -685,6 +709,50 @@ class Context:
         self._check(self._lib.f3d_plane_distance(self._h, _ptr(pts), len(pts), _ptr(pp), _ptr(nr), _ptr(out)))
         return out
 
+    # meshUtils (include/f3d.h f3d_mesh_*): verts float64 / float32 [V, 3], tris int64 / int32 [M, 3], masks bool [V], all C-contiguous
+    # NumPy arrays (Fusion3DSeg.segUtils.meshUtils checks them).  An index outside [0, V) raises IndexError.
+    def mesh_vertex_map(self, tris, nvertices):
+        """-> the CSR of vertex_triangle_mapping: (offsets int64 [V + 1], tri int32 [3M], pos int8 [3M])."""
+        nt, nv = len(tris), int(nvertices)
+        offsets, tri, pos, counts = np.empty(nv + 1, np.int64), np.empty(3 * nt, np.int32), np.empty(3 * nt, np.int8), np.zeros(4, np.int64)
+        self._check(self._lib.f3d_mesh_vertex_map(self._h, _ptr(tris), _itype(tris), nt, nv, _ptr(offsets), _ptr(tri), _ptr(pos), _ptr(counts)))
+        return offsets, tri, pos
+
+    def mesh_remove_faces(self, tris, nvertices, mask):
+        """-> (not_removed bool [M], remaining [Q, 3] of tris' dtype, oldids2newids int64 [V])."""
+        nt, nv = len(tris), int(nvertices)
+        nr, rem, o2n, counts = np.empty(nt, bool), np.empty((nt, 3), tris.dtype), np.empty(nv, np.int64), np.zeros(4, np.int64)
+        self._check(self._lib.f3d_mesh_remove_faces(self._h, _ptr(tris), _itype(tris), nt, nv, _ptr(mask), _ptr(nr), _ptr(rem), _ptr(o2n),
+                                                    _ptr(counts)))
+        return nr, rem[:counts[0]], o2n
+
+    def mesh_keep_faces(self, verts, tris, mask):
+        """-> (remaining vertices [P, 3] of verts' dtype, remaining triangles [Q, 3] of tris' dtype)."""
+        nt, nv = len(tris), len(verts)
+        ov, ot, counts = np.empty((min(3 * nt, nv), 3), verts.dtype), np.empty((nt, 3), tris.dtype), np.zeros(4, np.int64)
+        self._check(self._lib.f3d_mesh_keep_faces(self._h, _ptr(verts), _vdtype(verts), nv, _ptr(tris), _itype(tris), nt, _ptr(mask), _ptr(ov),
+                                                  _ptr(ot), _ptr(counts)))
+        return ov[:counts[0]], ot[:counts[1]]
+
+    def mesh_triangle_clusters(self, verts, tris, want_tri_area=False):
+        """-> (triangle_clusters int32 [M], cluster_n_triangles int64 [P], cluster_area float64 [P]) (+ the triangle areas [M])."""
+        nt, nv = len(tris), len(verts)
+        cl, cn, ca, counts = np.empty(nt, np.int32), np.empty(nt, np.int64), np.empty(nt, np.float64), np.zeros(4, np.int64)
+        ta = np.empty(nt, np.float64) if want_tri_area else None
+        self._check(self._lib.f3d_mesh_triangle_clusters(self._h, _ptr(verts), _vdtype(verts), nv, _ptr(tris), _itype(tris), nt, _ptr(cl), _ptr(cn),
+                                                         _ptr(ca), _ptr(ta), _ptr(counts)))
+        out = (cl, cn[:counts[0]].copy(), ca[:counts[0]].copy())
+        return out + (ta,) if want_tri_area else out
+
+    def mesh_clean(self, verts, tris, remove_mask, min_triangles, min_area):
+        """-> (new vertices, new triangles, kept_vertex_mask bool [V], kept_triangle_mask bool [M])."""
+        nt, nv = len(tris), len(verts)
+        nvs, nts, counts = np.empty((nv, 3), verts.dtype), np.empty((nt, 3), tris.dtype), np.zeros(4, np.int64)
+        kv, kt = np.zeros(nv, bool), np.zeros(nt, bool)
+        self._check(self._lib.f3d_mesh_clean(self._h, _ptr(verts), _vdtype(verts), nv, _ptr(tris), _itype(tris), nt, _ptr(remove_mask),
+                                             int(min_triangles), float(min_area), _ptr(nvs), _ptr(nts), _ptr(kv), _ptr(kt), _ptr(counts)))
+        return nvs[:counts[1]].copy(), nts[:counts[0]].copy(), kv, kt
+
     def door_window_quads(self, points, ids, instance_ids, vertices, triangles):
         """Door / window quads of door_window_bbox.generate_mesh (include/f3d.h f3d_door_window_quads) for the distinct ids
         `instance_ids`.  -> (quads float64 [k, 4, 3], status int32 [k] (QUAD_*), chosen triangle int32 [k], triangle normals
@@ -910,6 +978,29 @@ class Context:
         self._check(self._lib.f3d_door_window_quads_dev(self._h, points_ptr, int(n), ids_ptr, instance_ids_ptr, int(k), vertices_ptr,
                                                         int(nvertices), triangles_ptr, int(ntriangles), quads_ptr, status_ptr, tri_ptr,
                                                         normals_ptr, stream))
+
+    # f3d_mesh_*_dev: device pointers throughout (counts int64 [4] too); itype I64 / I32, vdtype F64 / F32; enqueue only.  An index
+    # outside [0, V) sets counts[2], writes nothing else and is recorded for take_device_error
+    def mesh_vertex_map_dev(self, tris_ptr, itype, nt, nv, offsets_ptr, tri_ptr, pos_ptr, counts_ptr, stream=None):
+        self._check(self._lib.f3d_mesh_vertex_map_dev(self._h, tris_ptr, itype, int(nt), int(nv), offsets_ptr, tri_ptr, pos_ptr, counts_ptr, stream))
+
+    def mesh_remove_faces_dev(self, tris_ptr, itype, nt, nv, mask_ptr, not_removed_ptr, remaining_ptr, old2new_ptr, counts_ptr, stream=None):
+        self._check(self._lib.f3d_mesh_remove_faces_dev(self._h, tris_ptr, itype, int(nt), int(nv), mask_ptr, not_removed_ptr, remaining_ptr,
+                                                        old2new_ptr, counts_ptr, stream))
+
+    def mesh_keep_faces_dev(self, verts_ptr, vdtype, nv, tris_ptr, itype, nt, mask_ptr, out_verts_ptr, out_tris_ptr, counts_ptr, stream=None):
+        self._check(self._lib.f3d_mesh_keep_faces_dev(self._h, verts_ptr, vdtype, int(nv), tris_ptr, itype, int(nt), mask_ptr, out_verts_ptr,
+                                                      out_tris_ptr, counts_ptr, stream))
+
+    def mesh_triangle_clusters_dev(self, verts_ptr, vdtype, nv, tris_ptr, itype, nt, clusters_ptr, cluster_n_ptr, cluster_area_ptr, tri_area_ptr,
+                                   counts_ptr, stream=None):
+        self._check(self._lib.f3d_mesh_triangle_clusters_dev(self._h, verts_ptr, vdtype, int(nv), tris_ptr, itype, int(nt), clusters_ptr,
+                                                             cluster_n_ptr, cluster_area_ptr, tri_area_ptr, counts_ptr, stream))
+
+    def mesh_clean_dev(self, verts_ptr, vdtype, nv, tris_ptr, itype, nt, remove_mask_ptr, min_triangles, min_area, new_verts_ptr, new_tris_ptr,
+                       kept_v_ptr, kept_t_ptr, counts_ptr, stream=None):
+        self._check(self._lib.f3d_mesh_clean_dev(self._h, verts_ptr, vdtype, int(nv), tris_ptr, itype, int(nt), remove_mask_ptr, int(min_triangles),
+                                                 float(min_area), new_verts_ptr, new_tris_ptr, kept_v_ptr, kept_t_ptr, counts_ptr, stream))
 
     def take_device_error(self, stream=None):
         self._check(self._lib.f3d_take_device_error(self._h, stream))

@@ -516,6 +516,73 @@ int f3d_door_window_quads_dev(f3d_ctx* ctx, const double* points, int64_t n, con
                               int32_t* tri, double* normals, void* stream);
 int f3d_ctx_reserve_quads(f3d_ctx* ctx, int64_t n, int k, int64_t nt);
 
+/* ---- segUtils/meshUtils.py: face filtering, vertex maps, triangle clusters (reference :235-333, :360-375) ------------ */
+/* Common to the five entries below.  tris: [nt, 3] vertex indices, C-contiguous, int64 (F3D_I64) or int32 (F3D_I32); face
+ * outputs have the same type.  verts: [nv, 3] of F3D_F64 or F3D_F32; vertex outputs have the same type.  Masks and flags are
+ * bytes (0 / not 0 in, 0 / 1 out).  nv < 2^31 and 3 * nt < 2^31.  The slot of a triangle corner is s = 3 * f + j.
+ * Outputs whose length depends on the data are sized by the caller for the largest case given below; counts (int64 [4])
+ * receives {first length, second length, 1 when a vertex index is outside [0, nv), 0}.
+ * A vertex index outside [0, nv) -> F3D_ERR_INDEX and no output is written (the reference's NumPy / list indexing wraps a
+ * negative index instead: a stated deviation).  The host entries return it; the _dev twins take device pointers (counts
+ * too), enqueue on `stream`, write counts = {0, 0, 1, 0} alone and record the error in a bit of its own for
+ * f3d_take_device_error.
+ * Scratch grows with nv + nt (f3d_ctx_reserve_mesh). */
+typedef enum f3d_itype {
+    F3D_I64 = 0,
+    F3D_I32 = 1
+} f3d_itype;
+
+/* vertex_triangle_mapping (:235-259) as a CSR: one stable radix sort of (vertex, slot) pairs.  offsets int64 [nv + 1];
+ * tri int32 [3 nt] and pos int8 [3 nt]: row v = offsets[v] .. offsets[v + 1] lists the faces that hold v and the corner
+ * they hold it at, in ascending slot order (the reference's append order; a face (v, v, w) is listed twice in row v). */
+int f3d_mesh_vertex_map(f3d_ctx* ctx, const void* tris, int itype, int64_t nt, int64_t nv, int64_t* offsets, int32_t* tri,
+                        int8_t* pos, int64_t* counts);
+int f3d_mesh_vertex_map_dev(f3d_ctx* ctx, const void* tris, int itype, int64_t nt, int64_t nv, int64_t* offsets, int32_t* tri,
+                            int8_t* pos, int64_t* counts, void* stream);
+
+/* remove_faces_by_vertices (:262-301).  mask [nv]: the vertices to remove.  not_removed [nt] = no corner of the face is
+ * masked; old2new int64 [nv] = the exclusive scan of !mask at the kept vertices, 0 at the removed ones; remaining
+ * [counts[0], 3] (room for nt rows) = old2new[tris[not_removed]], face order kept. */
+int f3d_mesh_remove_faces(f3d_ctx* ctx, const void* tris, int itype, int64_t nt, int64_t nv, const uint8_t* mask,
+                          uint8_t* not_removed, void* remaining, int64_t* old2new, int64_t* counts);
+int f3d_mesh_remove_faces_dev(f3d_ctx* ctx, const void* tris, int itype, int64_t nt, int64_t nv, const uint8_t* mask,
+                              uint8_t* not_removed, void* remaining, int64_t* old2new, int64_t* counts, void* stream);
+
+/* keep_faces_by_vertices (:304-333).  mask [nv]: a face is kept when any corner is masked.  The vertices of the kept faces
+ * are renumbered in order of first appearance (faces in order, corners 0, 1, 2): out_verts [counts[0], 3] (room for
+ * min(3 nt, nv) rows), out_tris [counts[1], 3] (room for nt rows).  The result does not depend on thread timing. */
+int f3d_mesh_keep_faces(f3d_ctx* ctx, const void* verts, int vdtype, int64_t nv, const void* tris, int itype, int64_t nt,
+                        const uint8_t* mask, void* out_verts, void* out_tris, int64_t* counts);
+int f3d_mesh_keep_faces_dev(f3d_ctx* ctx, const void* verts, int vdtype, int64_t nv, const void* tris, int itype, int64_t nt,
+                            const uint8_t* mask, void* out_verts, void* out_tris, int64_t* counts, void* stream);
+
+/* get_triangle_clusters (:360-375; Open3D's cluster_connected_triangles restated, parity with Open3D unpinned).  Two
+ * triangles are adjacent iff they share an ordered edge (min(a, b), max(a, b)) among (0,1), (0,2), (1,2); clusters are
+ * numbered in ascending order of their lowest triangle.  clusters int32 [nt]; cluster_n int64 and cluster_area float64
+ * [counts[0]] (room for nt entries); tri_area float64 [nt] (may be NULL) = 0.5 * sqrt((cx*cx + cy*cy) + cz*cz) with
+ * c = cross(p0 - p1, p0 - p2), every product and difference rounded alone.  A cluster's area is a fixed-shape float64 sum
+ * of its members in ascending triangle index (chunks of 4096 members; in a chunk item i goes to lane i mod 64, a lane adds
+ * left to right, the lanes meet in an xor butterfly 32, 16, .., 1; the chunk sums are summed the same way): the same bits
+ * on every call. */
+int f3d_mesh_triangle_clusters(f3d_ctx* ctx, const void* verts, int vdtype, int64_t nv, const void* tris, int itype, int64_t nt,
+                               int32_t* clusters, int64_t* cluster_n, double* cluster_area, double* tri_area, int64_t* counts);
+int f3d_mesh_triangle_clusters_dev(f3d_ctx* ctx, const void* verts, int vdtype, int64_t nv, const void* tris, int itype,
+                                   int64_t nt, int32_t* clusters, int64_t* cluster_n, double* cluster_area, double* tri_area,
+                                   int64_t* counts, void* stream);
+
+/* clean_mesh (no reference counterpart): drop the faces that touch a vertex of remove_mask [nv] (may be NULL), cluster the
+ * survivors, drop the clusters with fewer than min_triangles faces or an area below min_area, drop the vertices no face
+ * references (vertex order kept) and renumber.  kept_v [nv], kept_t [nt]; new_verts [counts[1], 3] (room for nv rows),
+ * new_tris [counts[0], 3] (room for nt rows).  Equal, bit for bit, to the composition of the entries above. */
+int f3d_mesh_clean(f3d_ctx* ctx, const void* verts, int vdtype, int64_t nv, const void* tris, int itype, int64_t nt,
+                   const uint8_t* remove_mask, int64_t min_triangles, double min_area, void* new_verts, void* new_tris,
+                   uint8_t* kept_v, uint8_t* kept_t, int64_t* counts);
+int f3d_mesh_clean_dev(f3d_ctx* ctx, const void* verts, int vdtype, int64_t nv, const void* tris, int itype, int64_t nt,
+                       const uint8_t* remove_mask, int64_t min_triangles, double min_area, void* new_verts, void* new_tris,
+                       uint8_t* kept_v, uint8_t* kept_t, int64_t* counts, void* stream);
+/* Sizes the scratch of the f3d_mesh_*_dev entries for meshes of up to nv vertices and nt triangles. */
+int f3d_ctx_reserve_mesh(f3d_ctx* ctx, int64_t nv, int64_t nt);
+
 /* ---- (f)#1: the adjacency itself, Fusion.save_data (Fusion3DSeg/fusion.py:374-375) -------- */
 /* tree = KDTree(points); adj = tree.query_radius(points, r=2*ds_radius): for every point the indices of all points
  * (itself included) whose float64 squared distance ((dx*dx + dy*dy) + dz*dz, sklearn's euclidean_rdist order) is
