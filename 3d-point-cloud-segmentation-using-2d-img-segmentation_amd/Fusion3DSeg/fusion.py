@@ -20,6 +20,7 @@ from pathlib import Path
 import numpy as np
 
 import f3d
+from f3d.tensors import torch_device, work_stream
 
 
 def parse_rts(rts):
@@ -322,7 +323,7 @@ class Fusion:
         ('host_normalised')."""
         with _DeviceFusion.on_stream('Fusion.fuse_device', self.h, self.w, self.pcdimg, self.pt2u, self.pt2v) as df:
             out = df.run(self, radius, angle, stride, max_depth, skip, verbose)
-            if df.stream is not df.caller:
+            if df.stream != df.caller:
                 for t in out:
                     t.record_stream(df.caller)
         return out
@@ -396,24 +397,12 @@ class _DeviceFusion:
     @classmethod
     @contextlib.contextmanager
     def on_stream(cls, what, h, w, pcdimg, pt2u, pt2v):
-        """An instance working on the caller's current torch stream, or on a side stream ordered behind it when that is the null
-        stream (never handed to the library); the caller's stream waits for the work when the block ends."""
+        """An instance working on the stream ``f3d.tensors.work_stream`` gives for the caller's current torch stream."""
         ctx = f3d.default_context()
-        import torch
-        if not torch.cuda.is_available():
-            raise f3d.F3DUnavailable(f'{what} needs a HIP device; there is no CPU fallback')
-        dev = torch.device('cuda', ctx.device)
+        torch, dev = torch_device(ctx, what)
         caller = torch.cuda.current_stream(dev)
-        work = caller
-        if caller.cuda_stream == 0:
-            work = torch.cuda.Stream(dev)
-            work.wait_stream(caller)
-        try:
-            with torch.cuda.device(dev), torch.cuda.stream(work):
-                yield cls(h, w, pcdimg, pt2u, pt2v, ctx, torch, dev, work, caller)
-        finally:
-            if work is not caller:
-                caller.wait_stream(work)
+        with torch.cuda.device(dev), work_stream(dev) as work:
+            yield cls(h, w, pcdimg, pt2u, pt2v, ctx, torch, dev, work, caller)
 
     # ---------------------------------------------------------------- storage
     def reserve(self, rows):
@@ -536,7 +525,7 @@ class _DeviceFusion:
         if fu.uv2pt_dir is not None:
             np.save(Path(fu.uv2pt_dir) / f'{name}.npy', host)
         if fu._lookup_sink is not None:
-            if not host_io and self.stream is not self.caller:
+            if not host_io and self.stream != self.caller:
                 uv2pt.record_stream(self.caller)
             fu._lookup_sink(name, host if host_io else uv2pt)
 

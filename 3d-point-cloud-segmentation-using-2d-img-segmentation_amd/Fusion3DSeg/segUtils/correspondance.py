@@ -23,16 +23,13 @@ from typing import NamedTuple
 import numpy as np
 
 import f3d
+from f3d.tensors import dtype_code, on_device, torch_device, work_stream
 
 
 class CSR(NamedTuple):
     """Rows of a merge map: row p = ``indices[offsets[p]:offsets[p + 1]]`` (NumPy arrays or torch tensors)."""
     offsets: object
     indices: object
-
-
-def _is_tensor(a):
-    return type(a).__module__.split('.')[0] == 'torch'
 
 
 def _csr_of(merge_maps):
@@ -53,7 +50,7 @@ def _csr_of(merge_maps):
 def _objects(csr):
     """CSR -> the reference's ``np.array(merge_maps, dtype=object)`` (lists of Python ints)."""
     offs, idx = csr
-    if _is_tensor(offs):
+    if on_device(offs):
         offs, idx = offs.cpu().numpy(), idx.cpu().numpy()
     flat = idx.tolist()
     o = offs.tolist()
@@ -116,7 +113,7 @@ class PointCorrespondance:
                 args = pickle.load(fp)
             self.pcdimgs, self.pcd2xy, self.imgids, self.merge_maps, self.nframes = args
             return
-        if _is_tensor(sparse_points) or _is_tensor(dense_points):
+        if hasattr(sparse_points, 'is_cuda') or hasattr(dense_points, 'is_cuda'):        # torch tensors; CPU ones are uploaded
             self._init_device(sparse_points, dense_points, radius, nframes, depth_hw)
             return
         pcd2xy, imgids, pcdimgs = self.get_lookups(nframes, depth_hw)
@@ -127,11 +124,8 @@ class PointCorrespondance:
         self.nframes = nframes
 
     def _init_device(self, sparse_points, dense_points, radius, nframes, depth_hw):
-        import torch
         ctx = f3d.default_context()
-        if not torch.cuda.is_available():
-            raise f3d.F3DUnavailable('PointCorrespondance on tensors needs a HIP device (there is no CPU fallback)')
-        dev = torch.device('cuda', ctx.device)
+        torch, dev = torch_device(ctx, 'PointCorrespondance on tensors')
         h, w = (int(x) for x in depth_hw)
         hw, F = h * w, int(nframes)
         i64 = dict(dtype=torch.int64, device=dev)
@@ -154,15 +148,17 @@ class PointCorrespondance:
                 raise ValueError(f'{name}: found an array with 0 sample(s) (sklearn raises ValueError)')
             if t.dtype != torch.float32:
                 t = t.to(torch.float64)
-            return t.contiguous(), (f3d.F32 if t.dtype == torch.float32 else f3d.F64)
-        s, sdt = prep(sparse_points, 'sparse_points')
-        d, ddt = prep(dense_points, 'dense_points')
-        stream = torch.cuda.current_stream(dev)
+            return t.contiguous()
+        s = prep(sparse_points, 'sparse_points')
+        d = prep(dense_points, 'dense_points')
         offs = torch.empty(len(d) + 1, dtype=torch.int64, device=dev)
-        nnz = ctx.radius_query_dev(s.data_ptr(), sdt, len(s), d.data_ptr(), ddt, len(d), r, offs.data_ptr(), stream.cuda_stream)
-        nb = torch.empty(nnz, dtype=torch.int32, device=dev)
+        with work_stream(dev) as work:                                      # the count is read back: complete when this returns
+            nnz = ctx.radius_query_dev(s.data_ptr(), dtype_code(s), len(s), d.data_ptr(), dtype_code(d), len(d), r, offs.data_ptr(),
+                                       work.cuda_stream)
+        nb = torch.empty(nnz, dtype=torch.int32, device=dev)                # between the blocks: memory of the caller's stream
         if nnz:
-            ctx.radius_query_fill_dev(d.data_ptr(), ddt, len(d), offs.data_ptr(), nb.data_ptr(), stream.cuda_stream)
+            with work_stream(dev) as work:
+                ctx.radius_query_fill_dev(d.data_ptr(), dtype_code(d), len(d), offs.data_ptr(), nb.data_ptr(), work.cuda_stream)
         return CSR(offs, nb)
 
     @classmethod
@@ -216,7 +212,7 @@ class PointCorrespondance:
 
     def save(self, filename):
         """Pickle (pcdimgs, pcd2xy, imgids, merge_maps, nframes) as the reference does (device tables are saved as NumPy)."""
-        host = [t.cpu().numpy() if _is_tensor(t) else t for t in (self.pcdimgs, self.pcd2xy, self.imgids)]
+        host = [t.cpu().numpy() if on_device(t) else t for t in (self.pcdimgs, self.pcd2xy, self.imgids)]
         with open(filename, 'wb') as fp:
             pickle.dump((host[0], host[1], host[2], self.merge_maps, self.nframes), fp)
 
@@ -224,7 +220,7 @@ class PointCorrespondance:
         """images [k] frame ids, coords [k, 2] (x, y) -> (indices int32 [p], frequency int64 [k]): the cloud points of every
         queried pixel, concatenated, and how many each pixel has (reference :253-271; NumPy indexing: negative coordinates
         wrap, out-of-range ones raise IndexError)."""
-        if _is_tensor(self._csr.offsets):
+        if on_device(self._csr.offsets):
             return self._get_point_device(images, coords)
         x, y = np.asarray(coords).T
         indices = self.pcdimgs[images, y, x]

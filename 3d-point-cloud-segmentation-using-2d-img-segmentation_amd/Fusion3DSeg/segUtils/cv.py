@@ -19,11 +19,11 @@ directed edges; the two coincide for symmetric lists, which is what ``KDTree.que
 fusion.py:369-377) returns.
 """
 from collections.abc import Sequence
-from contextlib import contextmanager
 
 import numpy as np
 
 import f3d
+from f3d.tensors import CSR_ADJACENCY, device_csr, dtype_code, host_csr, on_device, work_stream
 
 
 def adjacency_to_csr(adj, n):
@@ -111,35 +111,12 @@ def split_into_instances(classes, adj, nclasses=133, instance_classes=None, mini
 
 
 # ------------------------------------------------------------------------------------------------ CVSegmentation
-def _on_device(a):
-    return getattr(a, 'is_cuda', False)
-
-
-@contextmanager
-def _work_stream(device):
-    """The stream the library is handed: the caller's own, or -- when that is the legacy default stream, whose handle (0)
-    the library reads as "the context's stream" -- a side stream ordered after the caller's work; the caller's stream waits
-    for the side stream when the block ends.  No host stall."""
-    import torch
-    caller = torch.cuda.current_stream(device)
-    work = caller
-    if caller.cuda_stream == 0:
-        work = torch.cuda.Stream(device)
-        work.wait_stream(caller)
-    try:
-        with torch.cuda.stream(work):
-            yield work
-    finally:
-        if work is not caller:
-            caller.wait_stream(work)
-
-
 class _Flood:
     """One f3d_flood_order pass: the compact form (order, offsets, flags, root) plus, on the host, each cluster's class."""
 
     def __init__(self, ctx, classes, adj, inst):
         n = len(classes)
-        if _on_device(classes):
+        if on_device(classes):
             import torch
             offs, nbrs = adj
             dev = classes.device
@@ -147,7 +124,7 @@ class _Flood:
             order = torch.empty(n, dtype=torch.int64, device=dev)
             coffs = torch.zeros(n + 1, dtype=torch.int64, device=dev)
             flags = torch.zeros(n, dtype=torch.uint8, device=dev)
-            with _work_stream(dev) as work:                     # the call itself drains `work` (frontier readbacks)
+            with work_stream(dev) as work:                     # the call itself drains `work` (frontier readbacks)
                 self.stats = ctx.flood_order_dev(classes.data_ptr(), n, offs.data_ptr(), nbrs.data_ptr(), inst, self.root.data_ptr(),
                                                  order.data_ptr(), coffs.data_ptr(), flags.data_ptr(), work.cuda_stream)
             m, L = self.stats['clusters'], self.stats['points']
@@ -171,7 +148,7 @@ class _Flood:
     def boundary(self, k, n):
         """length-n bool boundary of cluster k"""
         pts = self.order[self.coffs[k]:self.coffs[k + 1]]
-        if _on_device(self.order):
+        if on_device(self.order):
             import torch
             out = torch.zeros(n, dtype=torch.bool, device=self.order.device)
         else:
@@ -194,10 +171,10 @@ class Boundaries(Sequence):
         if isinstance(i, slice):
             return [self[k] for k in range(*i.indices(len(self)))]
         parts = [None if p is None else p[0].boundary(p[1], self._n) for p in self._groups[i]]
-        if any(_on_device(p) for p in parts) and all(p is not None for p in parts):
+        if any(on_device(p) for p in parts) and all(p is not None for p in parts):
             import torch
             return torch.cat(parts)
-        return np.hstack([p if p is None or not _on_device(p) else p.cpu().numpy() for p in parts])
+        return np.hstack([p if p is None or not on_device(p) else p.cpu().numpy() for p in parts])
 
 
 def _merge_plan(ids, idinfo, classes):
@@ -224,10 +201,10 @@ def _merge_plan(ids, idinfo, classes):
 def _remap(ids, new_of):
     """outids[ids == old] = new for every (old, new), on the original ids (ids without a record keep theirs)"""
     if not new_of:
-        return ids.clone() if _on_device(ids) else ids.copy()
+        return ids.clone() if on_device(ids) else ids.copy()
     old = np.fromiter(new_of.keys(), np.int64, len(new_of))
     new = np.fromiter(new_of.values(), np.int64, len(new_of))
-    if _on_device(ids):
+    if on_device(ids):
         import torch
         o = torch.as_tensor(old, device=ids.device)
         srt, perm = torch.sort(o)
@@ -252,18 +229,9 @@ class CVSegmentation:
 
     def _csr(self, n):
         """(offsets int64 [n + 1], neighbours int32 [offsets[n]]), checked: the kernels read every row the offsets name."""
-        if _on_device(self.classes):
-            import torch
-            if not (isinstance(self.adj, tuple) and len(self.adj) == 2 and all(_on_device(a) for a in self.adj)):
-                raise TypeError('CVSegmentation: device classes need a device CSR adjacency (offsets, neighbours)')
-            offs, nbrs = self.adj[0].to(torch.int64).contiguous(), self.adj[1].to(torch.int32).contiguous()
-            if offs.dim() != 1 or len(offs) != n + 1 or int(offs[-1]) != len(nbrs):   # one scalar readback per call
-                raise ValueError('CSR adjacency: offsets must have n + 1 entries ending at len(neighbours)')
-            return offs, nbrs
-        offs, nbrs = adjacency_to_csr(self.adj, n)
-        if len(offs) != n + 1 or offs[-1] != len(nbrs):
-            raise ValueError('CSR adjacency: offsets must have n + 1 entries ending at len(neighbours)')
-        return offs, nbrs
+        if on_device(self.classes):
+            return device_csr(self.adj, n, self.classes.device, 'CVSegmentation: device classes')
+        return host_csr(*adjacency_to_csr(self.adj, n), n, CSR_ADJACENCY)
 
     @staticmethod
     def merge_classes(classes, source, destination):
@@ -279,14 +247,14 @@ class CVSegmentation:
 
     @staticmethod
     def get_objects(ids, objectids):
-        if _on_device(ids):
+        if on_device(ids):
             import torch
             return torch.isin(ids, torch.as_tensor(list(objectids), dtype=ids.dtype, device=ids.device))
         return np.isin(ids, np.asarray(list(objectids), dtype=ids.dtype if len(objectids) else None))
 
     @staticmethod
     def get_classes(ids, idinfo):
-        classes = ids.clone().zero_() if _on_device(ids) else np.zeros_like(ids)
+        classes = ids.clone().zero_() if on_device(ids) else np.zeros_like(ids)
         for info in idinfo:                                      # the last matching record wins
             classes[ids == info['id']] = info['category_id']
         return classes
@@ -313,7 +281,7 @@ class CVSegmentation:
         self.classes is rewritten in place (small clusters become class 0), as in the reference.  The fifth value is a
         read-only sequence (``Boundaries``) rather than a list: entry i is built when it is read (indexing, slicing,
         iteration and len() work as on the reference's list; use list(...) for a mutable copy)."""
-        dev = _on_device(self.classes)
+        dev = on_device(self.classes)
         classes = self.classes
         n = len(classes)
         adj = self._csr(n)
@@ -399,21 +367,21 @@ class CVSegmentation:
     def color_segment(self, colors, ids, seeds, threshold, neutral_ids=(0, ), max_level=10):
         """-> ids, updated in place; see the reference docstring (:367-386).  Colours float64 or float32."""
         n = len(ids)
-        if _on_device(ids):
+        if on_device(ids):
             import torch
             if colors.dtype not in (torch.float64, torch.float32):
                 raise TypeError(f'color_segment: colours must be float64 or float32, got {colors.dtype}')
             if ids.dtype != torch.int64 or not ids.is_contiguous():
                 raise TypeError('color_segment: device ids must be a contiguous int64 tensor (updated in place)')
-            if not _on_device(colors) or colors.device != ids.device or tuple(colors.shape) != (n, 3):
+            if not on_device(colors) or colors.device != ids.device or tuple(colors.shape) != (n, 3):
                 raise ValueError(f'color_segment: colours must be a [{n}, 3] tensor on {ids.device}')
             offs, nbrs = self._csr(n)
             sd = torch.as_tensor(seeds, dtype=torch.int64, device=ids.device).reshape(-1)
             sd = torch.where(sd < 0, sd + n, sd).contiguous()  # NumPy's negative indices; the kernel rejects the rest (IndexError)
             clr = colors.contiguous()
             ctx = f3d.default_context(ids.device.index)
-            with _work_stream(ids.device) as work:
-                ctx.color_segment_dev(clr.data_ptr(), f3d.F32 if clr.dtype == torch.float32 else f3d.F64, n, offs.data_ptr(),
+            with work_stream(ids.device) as work:
+                ctx.color_segment_dev(clr.data_ptr(), dtype_code(clr), n, offs.data_ptr(),
                                       nbrs.data_ptr(), ids.data_ptr(), sd.data_ptr(), len(sd), threshold, neutral_ids, max_level, None,
                                       work.cuda_stream)
                 ctx.take_device_error(work.cuda_stream)

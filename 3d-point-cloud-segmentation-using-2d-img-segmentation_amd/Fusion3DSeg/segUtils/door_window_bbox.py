@@ -20,7 +20,7 @@ from pathlib import Path
 import numpy as np
 
 import f3d
-from Fusion3DSeg.segUtils.cv import _work_stream
+from f3d.tensors import on_device, work_stream
 
 DOOR_WINDOW = (86, 115, 116)                   # :72
 
@@ -67,7 +67,7 @@ def _door_window_entries(info):
 
 def _run(ctx, points, ids, uniq, vertices, triangles):
     """(quads [k, 4, 3], status [k], chosen triangle [k]) as NumPy arrays, for the distinct instance ids `uniq`."""
-    if getattr(points, 'is_cuda', False):
+    if on_device(points):
         import torch
         dev = points.device
         pts = points.to(torch.float64).contiguous()
@@ -83,7 +83,7 @@ def _run(ctx, points, ids, uniq, vertices, triangles):
         quads = torch.empty((k, 4, 3), dtype=torch.float64, device=dev)
         status = torch.empty(k, dtype=torch.int32, device=dev)
         tri = torch.empty(k, dtype=torch.int32, device=dev)
-        with _work_stream(dev) as work:
+        with work_stream(dev) as work:
             ctx.door_window_quads_dev(pts.data_ptr(), len(pts), ids_d.data_ptr(), inst.data_ptr(), k, verts.data_ptr(), len(verts),
                                       tris.data_ptr(), len(tris), quads.data_ptr(), status.data_ptr(), tri.data_ptr(), None,
                                       work.cuda_stream)
@@ -117,7 +117,7 @@ def door_window_quads(points, ids, info, vertices, triangles, ctx=None):
     if not entries:
         raise ValueError('need at least one array to concatenate')               # np.vstack([]) (:140)
     wanted = np.array([int(d['id']) for d in entries], np.int64)
-    ctx = ctx or f3d.default_context(points.device.index if getattr(points, 'is_cuda', False) else None)
+    ctx = ctx or f3d.default_context(points.device.index if on_device(points) else None)
     uniq, slot = np.unique(wanted, return_inverse=True)
     quads, status, _ = _run(ctx, points, ids, uniq, vertices, triangles)
     status, quads = status[slot], quads[slot]

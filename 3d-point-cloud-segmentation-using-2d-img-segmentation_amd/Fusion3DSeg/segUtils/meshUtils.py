@@ -1,8 +1,8 @@
 """The mesh-topology part of the reference's Fusion3DSeg/segUtils/meshUtils.py on the GPU, plus ``clean_mesh``.
 
 Same names and positional signatures as the reference (file:line in each docstring).  NumPy arrays in give NumPy arrays out
-(host-pointer entries of libf3d_hip); device tensors in give device tensors out, on a side stream ordered both ways with
-torch's current stream.  The kernel-backed functions have no CPU fallback.
+(host-pointer entries of libf3d_hip); device tensors in give device tensors out, ordered with torch's current stream
+(``f3d.tensors.work_stream``).  The kernel-backed functions have no CPU fallback.
 
 Limits: V < 2^31 vertices, 3 M < 2^31; triangles are int32 or int64 [M, 3].  A vertex index outside [0, V) raises IndexError
 and writes nothing -- a stated deviation: the reference's list and NumPy indexing wrap a negative index.
@@ -13,7 +13,7 @@ get_roi, read_images, load_o3d_camera_data), generate_texture, uv2rgb and classw
 import numpy as np
 
 import f3d
-from Fusion3DSeg.segUtils.cv import _on_device, _work_stream
+from f3d.tensors import dtype_code, index_code, on_device, work_stream
 
 __all__ = ['vertex_triangle_mapping', 'remove_faces_by_vertices', 'keep_faces_by_vertices', 'get_triangle_clusters', 'clean_mesh',
            'bbox_axes', 'one_to_all_angles', 'VertexTriangleMap']
@@ -22,7 +22,7 @@ __all__ = ['vertex_triangle_mapping', 'remove_faces_by_vertices', 'keep_faces_by
 # ------------------------------------------------------------------------------------------------ argument checks
 def _triangles(triangles):
     """int32 / int64 [M, 3], C-contiguous, as given (NumPy array or device tensor)."""
-    if _on_device(triangles):
+    if on_device(triangles):
         import torch
         if triangles.dtype not in (torch.int32, torch.int64):
             raise TypeError(f'triangles must be int32 or int64, got {triangles.dtype}')
@@ -50,7 +50,7 @@ def _nvertices(nvertices):
 
 def _vertices(vertices, like):
     """float64 / float32 [V, 3] where `like` (the triangles) lives; other dtypes are widened to float64."""
-    if _on_device(like):
+    if on_device(like):
         import torch
         verts = torch.as_tensor(vertices, device=like.device)
         if verts.dtype not in (torch.float64, torch.float32):
@@ -58,7 +58,7 @@ def _vertices(vertices, like):
         shape = tuple(verts.shape)
         verts = verts.contiguous()
     else:
-        verts = np.asarray(vertices.cpu() if _on_device(vertices) else vertices)
+        verts = np.asarray(vertices.cpu() if on_device(vertices) else vertices)
         if verts.dtype not in (np.float64, np.float32):
             verts = verts.astype(np.float64)
         shape = verts.shape
@@ -71,13 +71,13 @@ def _vertices(vertices, like):
 
 def _mask(mask, nv, like, name='mask'):
     """bool [V] where `like` lives."""
-    if _on_device(like):
+    if on_device(like):
         import torch
         m = torch.as_tensor(mask, device=like.device)
         shape = tuple(m.shape)
         m = m.to(torch.bool).contiguous()
     else:
-        m = np.asarray(mask.cpu() if _on_device(mask) else mask)
+        m = np.asarray(mask.cpu() if on_device(mask) else mask)
         shape = m.shape
         m = np.ascontiguousarray(m, dtype=bool)
     if shape != (nv,):
@@ -86,15 +86,7 @@ def _mask(mask, nv, like, name='mask'):
 
 
 def _ctx(like):
-    return f3d.default_context(like.device.index if _on_device(like) else None)
-
-
-def _itype(t):
-    return f3d.I32 if t.element_size() == 4 else f3d.I64
-
-
-def _vdtype(t):
-    return f3d.F32 if t.element_size() == 4 else f3d.F64
+    return f3d.default_context(like.device.index if on_device(like) else None)
 
 
 def _counts(ctx, counts, work):
@@ -118,7 +110,7 @@ class VertexTriangleMap:
 
     def _build(self):
         if self._lists is None:
-            offsets, tri, pos = (a.cpu().numpy() if _on_device(a) else a for a in self.csr)
+            offsets, tri, pos = (a.cpu().numpy() if on_device(a) else a for a in self.csr)
             cuts = offsets[1:-1]
             self._lists = ([r.tolist() for r in np.split(tri, cuts)] if len(offsets) > 1 else [],
                            [r.tolist() for r in np.split(pos, cuts)] if len(offsets) > 1 else [])
@@ -149,7 +141,7 @@ def vertex_triangle_mapping(triangles, nvertices):
     order; a face (v, v, w) lists f twice in row v, with positions 0 and 1."""
     tris, nv = _triangles(triangles), _nvertices(nvertices)
     ctx = _ctx(tris)
-    if not _on_device(tris):
+    if not on_device(tris):
         return VertexTriangleMap(*ctx.mesh_vertex_map(tris, nv))
     import torch
     dev, nt = tris.device, tris.shape[0]
@@ -157,8 +149,8 @@ def vertex_triangle_mapping(triangles, nvertices):
     tri = torch.empty(3 * nt, dtype=torch.int32, device=dev)
     pos = torch.empty(3 * nt, dtype=torch.int8, device=dev)
     counts = torch.empty(4, dtype=torch.int64, device=dev)
-    with _work_stream(dev) as work:
-        ctx.mesh_vertex_map_dev(tris.data_ptr(), _itype(tris), nt, nv, offsets.data_ptr(), tri.data_ptr(), pos.data_ptr(), counts.data_ptr(),
+    with work_stream(dev) as work:
+        ctx.mesh_vertex_map_dev(tris.data_ptr(), index_code(tris), nt, nv, offsets.data_ptr(), tri.data_ptr(), pos.data_ptr(), counts.data_ptr(),
                                 work.cuda_stream)
         _counts(ctx, counts, work)
     return VertexTriangleMap(offsets, tri, pos)
@@ -174,7 +166,7 @@ def remove_faces_by_vertices(nvertices, triangles, mask):
     tris, nv = _triangles(triangles), _nvertices(nvertices)
     m = _mask(mask, nv, tris)
     ctx = _ctx(tris)
-    if not _on_device(tris):
+    if not on_device(tris):
         return ctx.mesh_remove_faces(tris, nv, m)
     import torch
     dev, nt = tris.device, tris.shape[0]
@@ -182,8 +174,8 @@ def remove_faces_by_vertices(nvertices, triangles, mask):
     rem = torch.empty((nt, 3), dtype=tris.dtype, device=dev)
     o2n = torch.empty(nv, dtype=torch.int64, device=dev)
     counts = torch.empty(4, dtype=torch.int64, device=dev)
-    with _work_stream(dev) as work:
-        ctx.mesh_remove_faces_dev(tris.data_ptr(), _itype(tris), nt, nv, m.data_ptr(), nr.data_ptr(), rem.data_ptr(), o2n.data_ptr(),
+    with work_stream(dev) as work:
+        ctx.mesh_remove_faces_dev(tris.data_ptr(), index_code(tris), nt, nv, m.data_ptr(), nr.data_ptr(), rem.data_ptr(), o2n.data_ptr(),
                                   counts.data_ptr(), work.cuda_stream)
         q, _ = _counts(ctx, counts, work)
     return nr, rem[:q], o2n
@@ -205,15 +197,15 @@ def keep_faces_by_vertices(vertices, triangles, mask):
     nv, nt = verts.shape[0], tris.shape[0]
     m = _mask(mask, nv, tris)
     ctx = _ctx(tris)
-    if not _on_device(tris):
+    if not on_device(tris):
         return ctx.mesh_keep_faces(verts, tris, m)
     import torch
     dev = tris.device
     ov = torch.empty((min(3 * nt, nv), 3), dtype=verts.dtype, device=dev)
     ot = torch.empty((nt, 3), dtype=tris.dtype, device=dev)
     counts = torch.empty(4, dtype=torch.int64, device=dev)
-    with _work_stream(dev) as work:
-        ctx.mesh_keep_faces_dev(verts.data_ptr(), _vdtype(verts), nv, tris.data_ptr(), _itype(tris), nt, m.data_ptr(), ov.data_ptr(),
+    with work_stream(dev) as work:
+        ctx.mesh_keep_faces_dev(verts.data_ptr(), dtype_code(verts), nv, tris.data_ptr(), index_code(tris), nt, m.data_ptr(), ov.data_ptr(),
                                 ot.data_ptr(), counts.data_ptr(), work.cuda_stream)
         p, q = _counts(ctx, counts, work)
     return ov[:p], ot[:q]
@@ -241,7 +233,7 @@ def get_triangle_clusters(mesh, return_triangle_areas=False):
     verts = _vertices(vertices, tris)
     nv, nt = verts.shape[0], tris.shape[0]
     ctx = _ctx(tris)
-    if not _on_device(tris):
+    if not on_device(tris):
         return ctx.mesh_triangle_clusters(verts, tris, return_triangle_areas)
     import torch
     dev = tris.device
@@ -250,8 +242,8 @@ def get_triangle_clusters(mesh, return_triangle_areas=False):
     ca = torch.empty(nt, dtype=torch.float64, device=dev)
     ta = torch.empty(nt, dtype=torch.float64, device=dev) if return_triangle_areas else None
     counts = torch.empty(4, dtype=torch.int64, device=dev)
-    with _work_stream(dev) as work:
-        ctx.mesh_triangle_clusters_dev(verts.data_ptr(), _vdtype(verts), nv, tris.data_ptr(), _itype(tris), nt, cl.data_ptr(), cn.data_ptr(),
+    with work_stream(dev) as work:
+        ctx.mesh_triangle_clusters_dev(verts.data_ptr(), dtype_code(verts), nv, tris.data_ptr(), index_code(tris), nt, cl.data_ptr(), cn.data_ptr(),
                                        ca.data_ptr(), None if ta is None else ta.data_ptr(), counts.data_ptr(), work.cuda_stream)
         p, _ = _counts(ctx, counts, work)
     out = (cl, cn[:p], ca[:p])
@@ -274,7 +266,7 @@ def clean_mesh(vertices, triangles, remove_mask=None, min_triangles=1, min_area=
     nv, nt = verts.shape[0], tris.shape[0]
     m = None if remove_mask is None else _mask(remove_mask, nv, tris, 'remove_mask')
     ctx = _ctx(tris)
-    if not _on_device(tris):
+    if not on_device(tris):
         return ctx.mesh_clean(verts, tris, m, min_triangles, min_area)
     import torch
     dev = tris.device
@@ -283,8 +275,8 @@ def clean_mesh(vertices, triangles, remove_mask=None, min_triangles=1, min_area=
     kv = torch.zeros(nv, dtype=torch.bool, device=dev)
     kt = torch.zeros(nt, dtype=torch.bool, device=dev)
     counts = torch.empty(4, dtype=torch.int64, device=dev)
-    with _work_stream(dev) as work:
-        ctx.mesh_clean_dev(verts.data_ptr(), _vdtype(verts), nv, tris.data_ptr(), _itype(tris), nt, None if m is None else m.data_ptr(),
+    with work_stream(dev) as work:
+        ctx.mesh_clean_dev(verts.data_ptr(), dtype_code(verts), nv, tris.data_ptr(), index_code(tris), nt, None if m is None else m.data_ptr(),
                            min_triangles, min_area, nvs.data_ptr(), nts.data_ptr(), kv.data_ptr(), kt.data_ptr(), counts.data_ptr(),
                            work.cuda_stream)
         q, p = _counts(ctx, counts, work)

@@ -21,7 +21,8 @@ import os
 import numpy as np
 
 import f3d
-from Fusion3DSeg.segUtils.cv import _on_device, _work_stream, adjacency_to_csr
+from f3d.tensors import CSR_ADJACENCY, device_csr, dtype_code, host_csr, on_device, work_stream
+from Fusion3DSeg.segUtils.cv import adjacency_to_csr
 from RTAB_utils.spatQuad import SpatQuadranion as Quat
 
 _COL = {'Shapeinfo': 0, 'indicies': 1, 'BBoxids': 2, 'BBoxpoints': 3}          # columns of the plane table (planeUtils.Headers)
@@ -40,18 +41,6 @@ def _seeds_host(seeds, n, what):
     return sd
 
 
-def _device_csr(adj, n, dev):
-    import torch
-    if not (isinstance(adj, tuple) and len(adj) == 2 and all(_on_device(a) for a in adj)):
-        raise TypeError('device values need a device CSR adjacency (offsets, neighbours)')
-    offs, nbrs = adj[0].to(torch.int64).contiguous(), adj[1].to(torch.int32).contiguous()
-    if offs.device != dev or nbrs.device != dev:
-        raise ValueError(f'CSR adjacency must be on {dev}')
-    if offs.dim() != 1 or len(offs) != n + 1 or int(offs[-1]) != len(nbrs):       # one scalar readback per call
-        raise ValueError('CSR adjacency: offsets must have n + 1 entries ending at len(neighbours)')
-    return offs, nbrs
-
-
 def _grow(values, nchan, adj, seeds, threshold, max_level, given, single, what):
     """The flood over `values` ([n] for nchan 1, [n, 3] for nchan 3).  `single`: the reference's one-point colour rule (the mean
     starts as the seed's value and counts no point); otherwise it starts as the seeds' average and counts them."""
@@ -62,13 +51,13 @@ def _grow(values, nchan, adj, seeds, threshold, max_level, given, single, what):
     thr = np.asarray(threshold, dtype=np.float64)
     if thr.ndim and thr.size != nchan:
         raise ValueError(f'{what}: threshold must be a scalar or have {nchan} entries')
-    if _on_device(values):
+    if on_device(values):
         import torch
         dev = values.device
         ok = (torch.float64,) if nchan == 1 else (torch.float64, torch.float32)
         if values.dtype not in ok:
             raise TypeError(f'{what}: values must be {" or ".join(str(t) for t in ok)}, got {values.dtype}')
-        offs, nbrs = _device_csr(adj, n, dev)
+        offs, nbrs = device_csr(adj, n, dev, 'device values')
         sd = torch.as_tensor(seeds, device=dev)
         if (sd.dtype.is_floating_point or sd.dtype == torch.bool) and sd.numel():
             raise TypeError(f'{what}: seeds must be integer indices, got {sd.dtype}')
@@ -83,8 +72,8 @@ def _grow(values, nchan, adj, seeds, threshold, max_level, given, single, what):
         cluster = torch.empty(n, dtype=torch.int64, device=dev)
         count = torch.zeros(1, dtype=torch.int64, device=dev)
         ctx = f3d.default_context(dev.index)
-        with _work_stream(dev) as work:
-            ctx.region_grow_dev(val.data_ptr(), f3d.F32 if val.dtype == torch.float32 else f3d.F64, nchan, n, offs.data_ptr(),
+        with work_stream(dev) as work:
+            ctx.region_grow_dev(val.data_ptr(), dtype_code(val), nchan, n, offs.data_ptr(),
                                 nbrs.data_ptr(), sd.data_ptr(), len(sd), sma0, npts0, thr, max_level, cluster.data_ptr(),
                                 count.data_ptr(), given, work.cuda_stream)
             try:
@@ -102,9 +91,7 @@ def _grow(values, nchan, adj, seeds, threshold, max_level, given, single, what):
         raise TypeError(f'{what}: values must be {" or ".join(np.dtype(t).name for t in ok)}, got {val.dtype}')
     if not isinstance(adj, tuple) and n and isinstance(adj[0], (set, frozenset)):
         adj = [list(a) for a in adj]                                      # the reference's list[set]: rows in the sets' iteration order
-    offs, nbrs = adjacency_to_csr(adj, n)
-    if len(offs) != n + 1 or offs[-1] != len(nbrs):
-        raise ValueError('CSR adjacency: offsets must have n + 1 entries ending at len(neighbours)')
+    offs, nbrs = host_csr(*adjacency_to_csr(adj, n), n, CSR_ADJACENCY)
     sd = _seeds_host(seeds, n, what)
     if not len(sd):
         return np.zeros(0, np.int64)
@@ -133,13 +120,13 @@ def plane_distance(points, plane_point, normal):
     """|(points - plane_point) . normal| on the GPU (f3d_plane_distance), float64 [N]: NumPy array or device tensor.  The sum is
     ((dx nx + dy ny) + dz nz); the reference's einsum adds in another order, so a point whose distance lies within rounding of the
     threshold may fall on the other side of it than in the reference."""
-    if _on_device(points):
+    if on_device(points):
         import torch
         if points.dtype != torch.float64 or points.dim() != 2 or points.shape[1] != 3:
             raise TypeError(f'plane_distance: points must be a float64 [N, 3] tensor, got {points.dtype} {tuple(points.shape)}')
         pts = points.contiguous()
         out = torch.empty(len(pts), dtype=torch.float64, device=pts.device)
-        with _work_stream(pts.device) as work:
+        with work_stream(pts.device) as work:
             f3d.default_context(pts.device.index).plane_distance_dev(pts.data_ptr(), len(pts), plane_point, normal, out.data_ptr(),
                                                                      work.cuda_stream)
         return out

@@ -13,6 +13,7 @@ from pathlib import Path
 import numpy as np
 
 import f3d
+from f3d.tensors import dtype_code, torch_device, work_stream
 
 
 def _imread_gray(path):
@@ -275,33 +276,23 @@ class PointVotingSegmentation:
         offs, nbrs = self._ctx.radius_query(self._cloud, query_points, radius)
         return nbrs, np.diff(offs)
 
-    def _torch(self):
-        try:
-            import torch
-        except ImportError:
-            return None
-        return torch if torch.cuda.is_available() else None
-
-    def _device_state(self, torch):
-        """The cloud and the vote matrix as device tensors (uploaded when the host copy is the current one)."""
-        dev = torch.device('cuda', self._ctx.device)
+    def _device_state(self):
+        """torch, the device, and the cloud and the vote matrix as device tensors (uploaded when the host copy is the current one)."""
+        torch, dev = torch_device(self._ctx, 'vote_frames')
         if self._cloud_dev is None:
             self._cloud_dev = torch.from_numpy(self._cloud).to(dev)
         if self._dev_votes is None:
             self._dev_votes = torch.from_numpy(np.ascontiguousarray(self._host_votes, dtype=np.float64)).to(dev)
-        return dev, self._cloud_dev, self._dev_votes
+        return torch, dev, self._cloud_dev, self._dev_votes
 
     def vote_frames(self, points, masks, radius=0.01, check=True):
         """The vote of F frames that are already on the device: ``points`` [F, hw, 3] float64 / float32 (what
         RTAB_utils.ios_rtab.frames_world_dev returns), ``masks`` uint8 [F, hw] or [F, h, w] at the depth resolution (what
         get2DSeg.masks_to_device returns).  No host copy, no file; the vote matrix stays on the device (returned as a float64
-        tensor [M, nclasses + 1]; ``self.votes`` downloads it).  Runs on a side stream ordered both ways with torch's current
-        stream.  ``check`` (synchronises): raise the IndexError of a label > nclasses now instead of leaving it to
-        ``f3d.Context.take_device_error``; the ValueError of non-finite points is always raised here."""
-        torch = self._torch()
-        if torch is None:
-            raise f3d.F3DUnavailable('vote_frames needs a HIP device (there is no CPU fallback)')
-        dev, cloud, votes = self._device_state(torch)
+        tensor [M, nclasses + 1]; ``self.votes`` downloads it).  Ordered with torch's current stream
+        (``f3d.tensors.work_stream``).  ``check`` (synchronises): raise the IndexError of a label > nclasses now instead of
+        leaving it to ``f3d.Context.take_device_error``; the ValueError of non-finite points is always raised here."""
+        torch, dev, cloud, votes = self._device_state()
         if not (isinstance(points, torch.Tensor) and isinstance(masks, torch.Tensor) and points.is_cuda and masks.is_cuda):
             raise ValueError('vote_frames takes device tensors (vote() reads frames from the host)')
         if points.dim() != 3 or points.shape[2] != 3 or points.dtype not in (torch.float64, torch.float32):
@@ -310,18 +301,11 @@ class PointVotingSegmentation:
         if masks.dtype != torch.uint8 or masks.shape[0] != F or masks.numel() != F * hw:
             raise ValueError(f'masks must be uint8 [F, hw], got {masks.dtype} {tuple(masks.shape)} for {F} frames of {hw} pixels')
         points, masks = points.to(dev).contiguous(), masks.to(dev).contiguous()
-        side = torch.cuda.Stream(dev)
-        side.wait_stream(torch.cuda.current_stream(dev))
-        try:
-            self._ctx.point_vote_frames_dev(cloud.data_ptr(), f3d.F32 if cloud.dtype == torch.float32 else f3d.F64, cloud.shape[0],
-                                            points.data_ptr(), f3d.F32 if points.dtype == torch.float32 else f3d.F64, masks.data_ptr(), F, hw,
-                                            radius, votes.data_ptr(), votes.shape[1], side.cuda_stream)
-        finally:
-            torch.cuda.current_stream(dev).wait_stream(side)
-            for x in (cloud, points, masks, votes):
-                x.record_stream(side)
-        if check:
-            self._ctx.take_device_error(side.cuda_stream)
+        with work_stream(dev) as work:
+            self._ctx.point_vote_frames_dev(cloud.data_ptr(), dtype_code(cloud), cloud.shape[0], points.data_ptr(), dtype_code(points),
+                                            masks.data_ptr(), F, hw, radius, votes.data_ptr(), votes.shape[1], work.cuda_stream)
+            if check:
+                self._ctx.take_device_error(work.cuda_stream)
         return votes
 
     def vote(self, frame_numbers=None, skip=1, radius=0.01, resize=True, filename=None, verbose=False):
@@ -333,7 +317,10 @@ class PointVotingSegmentation:
         h, w = self.depth_hw
         frame_numbers = np.arange(len(self.tofcameradata)) if frame_numbers is None else frame_numbers
         total = len(frame_numbers) // skip
-        torch = self._torch()
+        try:
+            torch, dev = torch_device(self._ctx, 'vote')
+        except f3d.F3DUnavailable:                                # no torch: the frames go through the host-pointer entry
+            torch = None
         if verbose:
             print('Framewise voting ... ')
         batch_q, batch_m, error = [], [], None
@@ -349,7 +336,6 @@ class PointVotingSegmentation:
                 self._host_votes = host
                 self._ctx.point_vote_frames(host, self._cloud, q, m, radius)     # (the votes are copied back on an error as well)
                 return
-            dev = torch.device('cuda', self._ctx.device)
             self.vote_frames(torch.from_numpy(q).to(dev), torch.from_numpy(m).to(dev), radius, check=False)
 
         for i, idx in enumerate(frame_numbers[::skip]):

@@ -7,6 +7,7 @@ around the methods restated here, ``__getRGBP3d`` (:155-177), ``__getModP3d`` (:
 import numpy as np
 
 import f3d
+from f3d.tensors import torch_device, work_stream
 
 
 def resize_camera_matrix(intrinsic, scale_x, scale_y):
@@ -41,11 +42,8 @@ def frames_world_dev(depths, intrinsics_scaled, odo_xyzw, odo_xyz, depth_scale=1
     torch tensor; uint16, float32 or float64) -> (points, normals), float64 torch tensors [F, H*W, 3] on the context's device.
     ``points[j]`` / ``normals[j]`` are what Fusion.from_frames(...).fuse_device takes.  The camera centre of frame j is
     ``odo_xyz[j]``, as the reference passes it (:280-283).  Raises F3DUnavailable without a device."""
-    import torch
     ctx = f3d.default_context()
-    if not torch.cuda.is_available():
-        raise f3d.F3DUnavailable('frames_world_dev needs a HIP device (there is no CPU fallback)')
-    dev = torch.device('cuda', ctx.device)
+    torch, dev = torch_device(ctx, 'frames_world_dev')
     q = np.asarray(odo_xyzw, np.float64).reshape(-1, 4)[:, [3, 0, 1, 2]]
     t = np.asarray(odo_xyz, np.float64).reshape(-1, 3)
     if isinstance(depths, torch.Tensor):
@@ -64,12 +62,7 @@ def frames_world_dev(depths, intrinsics_scaled, odo_xyzw, odo_xyz, depth_scale=1
     F, H, W = (int(x) for x in d.shape)
     pts = torch.empty((F, H * W, 3), dtype=torch.float64, device=dev)
     nrm = torch.empty((F, H * W, 3), dtype=torch.float64, device=dev)
-    # a side stream ordered after torch's current one both ways (a null-stream handle would select the context's own stream)
-    side = torch.cuda.Stream(dev)
-    side.wait_stream(torch.cuda.current_stream(dev))
-    ctx.unproject_depth_batch_dev(d.data_ptr(), code, F, H, W, intrinsics_scaled, q, t, pts.data_ptr(), float(depth_scale), side.cuda_stream)
-    ctx.estimate_normals_batch_dev(pts.data_ptr(), F, H * W, t, nrm.data_ptr(), radius, max_nn, True, stream=side.cuda_stream)
-    torch.cuda.current_stream(dev).wait_stream(side)
-    for x in (d, pts, nrm):
-        x.record_stream(side)
+    with work_stream(dev) as work:
+        ctx.unproject_depth_batch_dev(d.data_ptr(), code, F, H, W, intrinsics_scaled, q, t, pts.data_ptr(), float(depth_scale), work.cuda_stream)
+        ctx.estimate_normals_batch_dev(pts.data_ptr(), F, H * W, t, nrm.data_ptr(), radius, max_nn, True, stream=work.cuda_stream)
     return pts, nrm

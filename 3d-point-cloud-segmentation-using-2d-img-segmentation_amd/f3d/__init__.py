@@ -15,6 +15,8 @@ from pathlib import Path
 
 import numpy as np
 
+from f3d.tensors import dtype_code, host_csr, index_code
+
 __all__ = ['F3DError', 'F3DUnavailable', 'Context', 'default_context', 'library', 'library_path',
            'views_build', 'frustum_data', 'quat_inverse', 'VIEW_DOUBLES', 'F64', 'F32', 'FUSE_SORT', 'FUSE_GATHER']
 
@@ -207,12 +209,11 @@ def _f64(a, shape=None):
     return a
 
 
-def _itype(tris):
-    return I32 if tris.dtype == np.int32 else I64
-
-
-def _vdtype(verts):
-    return F32 if verts.dtype == np.float32 else F64
+def _n3(a, message='expected [N,3], got {}'):
+    a = _f64(a)
+    if a.ndim != 2 or a.shape[1] != 3:
+        raise ValueError(message.format(a.shape))
+    return a
 
 
 def _raise(code, msg):
@@ -378,27 +379,21 @@ class Context:
 
     # ---------------------------------------------------------------- NumPy (host pointer) calls
     def rotate(self, points, q_wxyz):
-        p = _f64(points)
-        if p.ndim != 2 or p.shape[1] != 3:
-            raise ValueError('points must be [N,3]')
+        p = _n3(points, 'points must be [N,3]')
         q = _f64(q_wxyz, (4,))
         out = np.empty_like(p)
         self._check(self._lib.f3d_rotate_f64(self._h, _ptr(p), len(p), _ptr(q), _ptr(out)))
         return out
 
     def points2pixel(self, points, intrinsic, quat, translation):
-        p = _f64(points)
-        if p.ndim != 2 or p.shape[1] != 3:
-            raise ValueError('points must be [N,3]')
+        p = _n3(points, 'points must be [N,3]')
         K, q, t = _f64(intrinsic, (3, 3)), _f64(quat, (4,)), _f64(translation, (3,))
         uv = np.empty((2, len(p)), np.int32)
         self._check(self._lib.f3d_points2pixel_f64(self._h, _ptr(p), len(p), _ptr(K), _ptr(q), _ptr(t), _ptr(uv)))
         return uv
 
     def inside_polyhedra(self, points, plane_points, normals):
-        p = _f64(points)
-        if p.ndim != 2 or p.shape[1] != 3:
-            raise ValueError('points must be [N,3]')
+        p = _n3(points, 'points must be [N,3]')
         pp, nr = _f64(plane_points), _f64(normals)
         if pp.shape != nr.shape or pp.ndim != 2 or pp.shape[1] != 3:
             raise ValueError('plane_points and normals must both be [M,3]')
@@ -580,45 +575,38 @@ class Context:
         return int(cnt[0])
 
     # ---- the other intersections.py primitives (a12)
-    @staticmethod
-    def _n3(a):
-        a = _f64(a)
-        if a.ndim != 2 or a.shape[1] != 3:
-            raise ValueError(f'expected [N,3], got {a.shape}')
-        return a
-
     def ray_x_lines(self, origin, direction, starts, ends):
-        o, d, s, e = _f64(origin, (3,)), _f64(direction, (3,)), self._n3(starts), self._n3(ends)
+        o, d, s, e = _f64(origin, (3,)), _f64(direction, (3,)), _n3(starts), _n3(ends)
         pts, within = np.empty_like(s), np.empty(len(s), np.uint8)
         self._check(self._lib.f3d_ray_x_lines(self._h, _ptr(o), _ptr(d), _ptr(s), _ptr(e), len(s), _ptr(pts), _ptr(within)))
         return pts, within.view(np.bool_)
 
     def rays_x_plane(self, plane_point, plane_normal, origins, directions):
-        pp, pn, o, d = _f64(plane_point, (3,)), _f64(plane_normal, (3,)), self._n3(origins), self._n3(directions)
+        pp, pn, o, d = _f64(plane_point, (3,)), _f64(plane_normal, (3,)), _n3(origins), _n3(directions)
         pts, valid = np.empty_like(o), np.empty(len(o), np.uint8)
         self._check(self._lib.f3d_rays_x_plane(self._h, _ptr(pp), _ptr(pn), _ptr(o), _ptr(d), len(o), _ptr(pts), _ptr(valid)))
         return pts, valid.view(np.bool_)
 
     def lines_x_planes(self, line_origins, line_ends, plane_points, plane_normals):
-        lo, le, pp, pn = self._n3(line_origins), self._n3(line_ends), self._n3(plane_points), self._n3(plane_normals)
+        lo, le, pp, pn = _n3(line_origins), _n3(line_ends), _n3(plane_points), _n3(plane_normals)
         pts, valid = np.empty((len(lo), len(pp), 3)), np.empty((len(lo), len(pp)), np.uint8)
         self._check(self._lib.f3d_lines_x_planes(self._h, _ptr(lo), _ptr(le), len(lo), _ptr(pp), _ptr(pn), len(pp), _ptr(pts), _ptr(valid)))
         return pts, valid.view(np.bool_)
 
     def point_inside_polygon(self, points, vertices):
-        p, v = self._n3(points), self._n3(vertices)
+        p, v = _n3(points), _n3(vertices)
         inside, within = np.empty(len(p), np.uint8), np.empty((len(v), len(p)), np.uint8)
         self._check(self._lib.f3d_point_inside_polygon(self._h, _ptr(p), len(p), _ptr(v), len(v), _ptr(inside), _ptr(within)))
         return inside.view(np.bool_), within.view(np.bool_)
 
     def points_plane_projection(self, points, plane_point, normal):
-        p, pp, nr = self._n3(points), _f64(plane_point, (3,)), _f64(normal, (3,))
+        p, pp, nr = _n3(points), _f64(plane_point, (3,)), _f64(normal, (3,))
         out = np.empty_like(p)
         self._check(self._lib.f3d_points_plane_projection(self._h, _ptr(p), len(p), _ptr(pp), _ptr(nr), _ptr(out)))
         return out
 
     def lines_plane_projection(self, starts, ends, plane_point, normal):
-        s, e, pp, nr = self._n3(starts), self._n3(ends), _f64(plane_point, (3,)), _f64(normal, (3,))
+        s, e, pp, nr = _n3(starts), _n3(ends), _f64(plane_point, (3,)), _f64(normal, (3,))
         sp, ep, dr = np.empty_like(s), np.empty_like(s), np.empty_like(s)
         self._check(self._lib.f3d_lines_plane_projection(self._h, _ptr(s), _ptr(e), len(s), _ptr(pp), _ptr(nr), _ptr(sp), _ptr(ep), _ptr(dr)))
         return sp, ep, dr
@@ -626,10 +614,7 @@ class Context:
     def components_same_class(self, classes, offsets, neighbours):
         """root[i] = smallest index of point i's same-class connected component (CSR adjacency, symmetric)."""
         cls = np.ascontiguousarray(classes, dtype=np.int64)
-        offs = np.ascontiguousarray(offsets, dtype=np.int64)
-        nb = np.ascontiguousarray(neighbours, dtype=np.int32)
-        if len(offs) != len(cls) + 1 or (len(cls) and offs[-1] != len(nb)):
-            raise ValueError('offsets must have n+1 entries ending at len(neighbours)')
+        offs, nb = host_csr(offsets, neighbours, len(cls))
         root = np.empty(len(cls), np.int64)
         self._check(self._lib.f3d_components_same_class(self._h, _ptr(cls), len(cls), _ptr(offs), _ptr(nb), _ptr(root)))
         return root
@@ -639,12 +624,9 @@ class Context:
         `instance_classes` (processing order), numbered by class rank then ascending seed.  -> (root int64 [n], order int64 [L]
         (the clusters concatenated in the reference's pop order), coffs int64 [M + 1], boundary flags bool [n], stats dict)."""
         cls = np.ascontiguousarray(classes, dtype=np.int64)
-        offs = np.ascontiguousarray(offsets, dtype=np.int64)
-        nb = np.ascontiguousarray(neighbours, dtype=np.int32)
         inst = np.ascontiguousarray(np.asarray(instance_classes).reshape(-1), dtype=np.int64)
         n = len(cls)
-        if len(offs) != n + 1 or (n and offs[-1] != len(nb)):
-            raise ValueError('offsets must have n+1 entries ending at len(neighbours)')
+        offs, nb = host_csr(offsets, neighbours, n)
         root, order, coffs = np.empty(n, np.int64), np.empty(n, np.int64), np.zeros(n + 1, np.int64)
         flags, stats = np.zeros(n, np.uint8), np.zeros(4, np.int64)
         self._check(self._lib.f3d_flood_order(self._h, _ptr(cls), n, _ptr(offs), _ptr(nb), _ptr(inst), len(inst), _ptr(root),
@@ -664,15 +646,12 @@ class Context:
             raise ValueError(f'color_segment: colours must be [{n}, 3], got {clr.shape}')
         if not (isinstance(ids, np.ndarray) and ids.dtype == np.int64 and ids.flags.c_contiguous):
             raise TypeError('color_segment: ids must be a C-contiguous int64 array (it is updated in place)')
-        offs = np.ascontiguousarray(offsets, dtype=np.int64)
-        nb = np.ascontiguousarray(neighbours, dtype=np.int32)
-        if len(offs) != n + 1 or (n and offs[-1] != len(nb)):
-            raise ValueError('offsets must have n+1 entries ending at len(neighbours)')
+        offs, nb = host_csr(offsets, neighbours, n)
         sd = np.ascontiguousarray(np.asarray(seeds).reshape(-1), dtype=np.int64)
         thr = _threshold3(threshold)
         neu = np.ascontiguousarray(np.asarray(list(neutral_ids)).reshape(-1), dtype=np.int64)
         acc = np.zeros(1, np.int64)
-        self._check(self._lib.f3d_color_segment(self._h, _ptr(clr), F32 if clr.dtype == np.float32 else F64, n, _ptr(offs), _ptr(nb),
+        self._check(self._lib.f3d_color_segment(self._h, _ptr(clr), dtype_code(clr), n, _ptr(offs), _ptr(nb),
                                                 _ptr(ids), _ptr(sd), len(sd), _ptr(thr), _ptr(neu), len(neu), int(max_level), _ptr(acc)))
         return ids, int(acc[0])
 
@@ -687,23 +666,18 @@ class Context:
         nchan = 1 if val.ndim == 1 else val.shape[1] if val.ndim == 2 else 0
         if nchan not in (1, 3) or (nchan == 1 and val.dtype != np.float64):
             raise ValueError(f'region_grow: values must be float64 [n] or float64 / float32 [n, 3], got {val.dtype} {val.shape}')
-        offs = np.ascontiguousarray(offsets, dtype=np.int64)
-        nb = np.ascontiguousarray(neighbours, dtype=np.int32)
-        if len(offs) != n + 1 or (n and offs[-1] != len(nb)):
-            raise ValueError('offsets must have n+1 entries ending at len(neighbours)')
+        offs, nb = host_csr(offsets, neighbours, n)
         sd = np.ascontiguousarray(np.asarray(seeds).reshape(-1), dtype=np.int64)
         sma, thr = _grow_params(nchan, sma0, threshold)
         cluster, count = np.empty(n, np.int64), np.zeros(1, np.int64)
-        self._check(self._lib.f3d_region_grow(self._h, _ptr(val), F32 if val.dtype == np.float32 else F64, nchan, n, _ptr(offs), _ptr(nb),
+        self._check(self._lib.f3d_region_grow(self._h, _ptr(val), dtype_code(val), nchan, n, _ptr(offs), _ptr(nb),
                                               _ptr(sd), len(sd), _ptr(sma), int(npts0), int(bool(seeds_given)), _ptr(thr), int(max_level),
                                               _ptr(cluster), _ptr(count)))
         return cluster[:int(count[0])].copy()
 
     def plane_distance(self, points, plane_point, normal):
         """|((x - px) nx + (y - py) ny) + (z - pz) nz| of float64 points [n, 3] -> float64 [n]."""
-        pts = _f64(points)
-        if pts.ndim != 2 or pts.shape[1] != 3:
-            raise ValueError(f'plane_distance: points must be [N, 3], got {pts.shape}')
+        pts = _n3(points, 'plane_distance: points must be [N, 3], got {}')
         pp, nr = _f64(np.asarray(plane_point).reshape(-1), (3,)), _f64(np.asarray(normal).reshape(-1), (3,))
         out = np.empty(len(pts))
         self._check(self._lib.f3d_plane_distance(self._h, _ptr(pts), len(pts), _ptr(pp), _ptr(nr), _ptr(out)))
@@ -715,14 +689,14 @@ class Context:
         """-> the CSR of vertex_triangle_mapping: (offsets int64 [V + 1], tri int32 [3M], pos int8 [3M])."""
         nt, nv = len(tris), int(nvertices)
         offsets, tri, pos, counts = np.empty(nv + 1, np.int64), np.empty(3 * nt, np.int32), np.empty(3 * nt, np.int8), np.zeros(4, np.int64)
-        self._check(self._lib.f3d_mesh_vertex_map(self._h, _ptr(tris), _itype(tris), nt, nv, _ptr(offsets), _ptr(tri), _ptr(pos), _ptr(counts)))
+        self._check(self._lib.f3d_mesh_vertex_map(self._h, _ptr(tris), index_code(tris), nt, nv, _ptr(offsets), _ptr(tri), _ptr(pos), _ptr(counts)))
         return offsets, tri, pos
 
     def mesh_remove_faces(self, tris, nvertices, mask):
         """-> (not_removed bool [M], remaining [Q, 3] of tris' dtype, oldids2newids int64 [V])."""
         nt, nv = len(tris), int(nvertices)
         nr, rem, o2n, counts = np.empty(nt, bool), np.empty((nt, 3), tris.dtype), np.empty(nv, np.int64), np.zeros(4, np.int64)
-        self._check(self._lib.f3d_mesh_remove_faces(self._h, _ptr(tris), _itype(tris), nt, nv, _ptr(mask), _ptr(nr), _ptr(rem), _ptr(o2n),
+        self._check(self._lib.f3d_mesh_remove_faces(self._h, _ptr(tris), index_code(tris), nt, nv, _ptr(mask), _ptr(nr), _ptr(rem), _ptr(o2n),
                                                     _ptr(counts)))
         return nr, rem[:counts[0]], o2n
 
@@ -730,7 +704,7 @@ class Context:
         """-> (remaining vertices [P, 3] of verts' dtype, remaining triangles [Q, 3] of tris' dtype)."""
         nt, nv = len(tris), len(verts)
         ov, ot, counts = np.empty((min(3 * nt, nv), 3), verts.dtype), np.empty((nt, 3), tris.dtype), np.zeros(4, np.int64)
-        self._check(self._lib.f3d_mesh_keep_faces(self._h, _ptr(verts), _vdtype(verts), nv, _ptr(tris), _itype(tris), nt, _ptr(mask), _ptr(ov),
+        self._check(self._lib.f3d_mesh_keep_faces(self._h, _ptr(verts), dtype_code(verts), nv, _ptr(tris), index_code(tris), nt, _ptr(mask), _ptr(ov),
                                                   _ptr(ot), _ptr(counts)))
         return ov[:counts[0]], ot[:counts[1]]
 
@@ -739,7 +713,7 @@ class Context:
         nt, nv = len(tris), len(verts)
         cl, cn, ca, counts = np.empty(nt, np.int32), np.empty(nt, np.int64), np.empty(nt, np.float64), np.zeros(4, np.int64)
         ta = np.empty(nt, np.float64) if want_tri_area else None
-        self._check(self._lib.f3d_mesh_triangle_clusters(self._h, _ptr(verts), _vdtype(verts), nv, _ptr(tris), _itype(tris), nt, _ptr(cl), _ptr(cn),
+        self._check(self._lib.f3d_mesh_triangle_clusters(self._h, _ptr(verts), dtype_code(verts), nv, _ptr(tris), index_code(tris), nt, _ptr(cl), _ptr(cn),
                                                          _ptr(ca), _ptr(ta), _ptr(counts)))
         out = (cl, cn[:counts[0]].copy(), ca[:counts[0]].copy())
         return out + (ta,) if want_tri_area else out
@@ -749,7 +723,7 @@ class Context:
         nt, nv = len(tris), len(verts)
         nvs, nts, counts = np.empty((nv, 3), verts.dtype), np.empty((nt, 3), tris.dtype), np.zeros(4, np.int64)
         kv, kt = np.zeros(nv, bool), np.zeros(nt, bool)
-        self._check(self._lib.f3d_mesh_clean(self._h, _ptr(verts), _vdtype(verts), nv, _ptr(tris), _itype(tris), nt, _ptr(remove_mask),
+        self._check(self._lib.f3d_mesh_clean(self._h, _ptr(verts), dtype_code(verts), nv, _ptr(tris), index_code(tris), nt, _ptr(remove_mask),
                                              int(min_triangles), float(min_area), _ptr(nvs), _ptr(nts), _ptr(kv), _ptr(kt), _ptr(counts)))
         return nvs[:counts[1]].copy(), nts[:counts[0]].copy(), kv, kt
 
@@ -757,9 +731,7 @@ class Context:
         """Door / window quads of door_window_bbox.generate_mesh (include/f3d.h f3d_door_window_quads) for the distinct ids
         `instance_ids`.  -> (quads float64 [k, 4, 3], status int32 [k] (QUAD_*), chosen triangle int32 [k], triangle normals
         float64 [T, 3])."""
-        pts = _f64(points)
-        if pts.ndim != 2 or pts.shape[1] != 3:
-            raise ValueError(f'door_window_quads: points must be [N, 3], got {pts.shape}')
+        pts = _n3(points, 'door_window_quads: points must be [N, 3], got {}')
         ids_ = np.ascontiguousarray(ids, dtype=np.int64).reshape(-1)
         if len(ids_) != len(pts):
             raise ValueError(f'door_window_quads: {len(ids_)} ids for {len(pts)} points')
@@ -862,9 +834,7 @@ class Context:
         """Open3D's estimate_normals(KDTreeSearchParamHybrid(radius, max_nn)) + the flip towards ``cam_centre`` of
         RTAB2Cache.surface_normal_estimation (ios_rtab.py:236-248), one frame: float64 [N,3] (f3d.h f3d_estimate_normals).
         want_neighbours: also (counts int32 [N], neighbours int32 [N, max_nn], -1 padded, in (distance, index) order)."""
-        p = _f64(points)
-        if p.ndim != 2 or p.shape[1] != 3:
-            raise ValueError(f'points must be [N,3], got {p.shape}')
+        p = _n3(points, 'points must be [N,3], got {}')
         c = _f64(cam_centre, (3,)) if orient else None
         out = np.empty_like(p)
         counts = np.empty(len(p), np.int32) if want_neighbours else None

@@ -22,6 +22,7 @@ from pathlib import Path
 import numpy as np
 
 import f3d
+from f3d.tensors import work_stream
 
 # the reference makes its un-vendored ./OneFormer checkout importable (`demo.defaults`, `oneformer`) this way (get2DSeg.py:12)
 sys.path.insert(1, os.path.join(sys.path[0], 'OneFormer'))
@@ -68,17 +69,6 @@ def _logits_of(outputs):
     return outputs
 
 
-def _launch_stream(torch, device):
-    """The producer's stream; the library needs a real stream handle, so the legacy null stream is replaced by a side stream
-    ordered behind it (and the null stream made to wait for the side stream afterwards by the caller)."""
-    cur = torch.cuda.current_stream(device)
-    if cur.cuda_stream != 0:
-        return cur, None
-    side = torch.cuda.Stream(device)
-    side.wait_stream(cur)
-    return side, cur
-
-
 def sem_to_mask(sem, conf_threshold=0.017, low_label=133):
     """[C,H,W] float32 logits (torch CUDA tensor or array) -> uint8 [H,W] class mask on the HOST (reference :110-120)."""
     ctx = f3d.default_context()
@@ -112,11 +102,8 @@ def sem_to_mask_device(sem, out, conf_threshold=0.017, low_label=133):
     c, h, w = sem.shape[-3:]
     if out.dtype != torch.uint8 or not out.is_contiguous() or out.numel() != b * h * w:
         raise ValueError(f'sem_to_mask_device: out must be a contiguous uint8 tensor of {b} x {h} x {w} elements')
-    stream, null = _launch_stream(torch, sem.device)
-    ctx.sem_logits_to_masks_dev(sem.data_ptr(), b, c, h * w, conf_threshold, low_label, out.data_ptr(), stream.cuda_stream)
-    sem.record_stream(stream)
-    if null is not None:
-        null.wait_stream(stream)
+    with work_stream(sem.device) as work:
+        ctx.sem_logits_to_masks_dev(sem.data_ptr(), b, c, h * w, conf_threshold, low_label, out.data_ptr(), work.cuda_stream)
     return out
 
 
