@@ -20,7 +20,7 @@ from pathlib import Path
 import numpy as np
 
 import f3d
-from f3d.tensors import torch_device, work_stream
+from f3d.tensors import dtype_code, on_device, torch_device, work_stream
 
 
 def parse_rts(rts):
@@ -46,6 +46,92 @@ def project_vote_argmax(points, K, wxyzs, translations, masks, max_depth=10, ncl
     V, H, W = masks.shape
     views = f3d.views_build(K, W, H, wxyzs, translations, max_depth)
     return f3d.default_context().project_vote_argmax(points, views, masks, nclasses, threshold, filter_classes, return_votes)
+
+
+def _device_cloud(torch, dev, points):
+    """points as a contiguous float64 / float32 [N,3] tensor on `dev` (float32 stays float32, everything else is widened)."""
+    pts = points.to(dev)
+    if pts.dim() != 2 or pts.shape[1] != 3:
+        raise ValueError(f'points must be [N,3], got {tuple(pts.shape)}')
+    return (pts if pts.dtype == torch.float32 else pts.to(torch.float64)).contiguous()
+
+
+def render_lookups(points, K, wxyzs, translations, hw, max_depth=10, splat=0):
+    """Per-view depth buffers and ``uv2pt`` lookups of a posed cloud, rendered on the GPU as a point-splat z-buffer.
+
+    For clouds that come without depth frames (an RTAB-Map export, a LiDAR scan, mesh vertices, a reloaded fused cloud) this
+    gives what ``Fusion.fuse`` writes per frame (reference fusion.py:105-111, :326-327): pixel -> the point a camera sees there,
+    -1 for none.  The lookups feed ``VotingSegmentation`` / ``f3d.Context.vote_uv2pt_batch`` as they are.
+
+    Per view the samples are those of ``project_vote_argmax`` (5 frustum planes, ``points2pixel``, inside the image) with a
+    normal positive float32 depth; a point covers the (2 splat + 1)^2 pixels around its pixel; per pixel the nearest point by
+    float32 depth wins, ties go to the lowest index (f3d.h, f3d_render_lookups).  ``hw`` = (H, W) of the images.
+
+    Returns depth float32 [V,H,W] (+inf = empty) and uv2pt int32 [V,H*W].  NumPy in, NumPy out; a torch device tensor for
+    ``points`` gives device tensors, ordered with torch's current stream, with no host round trip of the cloud."""
+    H, W = (int(x) for x in hw)
+    views = f3d.views_build(K, W, H, wxyzs, translations, max_depth)
+    ctx = f3d.default_context()
+    if not on_device(points):
+        return ctx.render_lookups(points, views, H, W, splat)
+    torch, dev = torch_device(ctx, 'render_lookups')
+    pts = _device_cloud(torch, dev, points)
+    with torch.cuda.device(dev), work_stream(dev) as work:
+        dviews = torch.from_numpy(views).to(dev)
+        depth = torch.empty((len(views), H, W), dtype=torch.float32, device=dev)
+        uv2pt = torch.empty((len(views), H * W), dtype=torch.int32, device=dev)
+        ctx.render_lookups_dev(pts.data_ptr(), dtype_code(pts), len(pts), dviews.data_ptr(), len(views), H, W, splat, depth.data_ptr(),
+                               uv2pt.data_ptr(), work.cuda_stream)
+    for t in (depth, uv2pt):                                                  # allocated on the work stream, handed to the caller's
+        t.record_stream(torch.cuda.current_stream(dev))
+    return depth, uv2pt
+
+
+def project_vote_argmax_visible(points, K, wxyzs, translations, masks, max_depth=10, nclasses=133, threshold=0.5,
+                                filter_classes=None, return_votes=False, splat=1, depth_tol=0.05):
+    """``project_vote_argmax`` with an occlusion test: a point votes in a view only when that view sees it.
+
+    The cloud is rendered into every view as for ``render_lookups`` (``splat``); a sample votes iff its float32 depth is within
+    ``depth_tol`` of the nearest depth rendered into its pixel (f3d.h, f3d_vote_visible), so a point behind a wall no longer
+    collects the wall's label from the cameras in front of it.  ``depth_tol`` defaults to the project's fusion radius
+    (``Fusion.fuse``); with ``depth_tol=inf`` the votes are those of ``project_vote_argmax``.  A label > nclasses on a visible
+    sample raises IndexError.
+
+    Returns int64 [N] (and float64 [N, nclasses+1] votes, the layout of ``VotingSegmentation``).  NumPy in, NumPy out; torch device
+    tensors for ``points`` and ``masks`` give device tensors, ordered with torch's current stream, with no host round trip."""
+    ctx = f3d.default_context()
+    device = on_device(points) or on_device(masks)
+    if not device:
+        masks = np.ascontiguousarray(masks, dtype=np.uint8)
+    if masks.ndim != 3:
+        raise ValueError('masks must be uint8 [V,H,W]')
+    V, H, W = (int(x) for x in masks.shape)
+    views = f3d.views_build(K, W, H, wxyzs, translations, max_depth)
+    if len(views) != V:
+        raise ValueError(f'{len(views)} poses for {V} masks')
+    if not device:
+        votes = np.zeros((len(points), nclasses + 1))
+        ctx.vote_visible(votes, points, views, masks, splat, depth_tol)
+        cls = ctx.segment_votes(votes, nclasses, threshold, filter_classes)
+        return (cls, votes) if return_votes else cls
+    torch, dev = torch_device(ctx, 'project_vote_argmax_visible')
+    to_t = lambda a: a if isinstance(a, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(a))   # noqa: E731
+    pts = _device_cloud(torch, dev, to_t(points))
+    dmasks = to_t(masks).to(dev)
+    if dmasks.dtype != torch.uint8:
+        raise ValueError(f'masks must be uint8, got {dmasks.dtype}')
+    dmasks = dmasks.contiguous()
+    with torch.cuda.device(dev), work_stream(dev) as work:
+        dviews = torch.from_numpy(views).to(dev)
+        votes = torch.zeros((len(pts), nclasses + 1), dtype=torch.float64, device=dev)
+        cls = torch.empty(len(pts), dtype=torch.int64, device=dev)
+        ctx.vote_visible_dev(pts.data_ptr(), dtype_code(pts), len(pts), dviews.data_ptr(), V, dmasks.data_ptr(), H, W, splat, depth_tol,
+                             votes.data_ptr(), nclasses + 1, 0, work.cuda_stream)
+        ctx.segment_votes_dev(votes.data_ptr(), len(pts), nclasses + 1, nclasses, threshold, filter_classes, cls.data_ptr(), work.cuda_stream)
+        ctx.take_device_error(work.cuda_stream)                               # the IndexError of a label > nclasses (synchronises)
+    for t in (votes, cls):
+        t.record_stream(torch.cuda.current_stream(dev))
+    return (cls, votes) if return_votes else cls
 
 
 def radius_adjacency(points, ds_radius, as_csr=False):

@@ -27,7 +27,7 @@ enum { SLOT_XYZ = 0, SLOT_OUT0, SLOT_OUT1, SLOT_VIEWS, SLOT_MASKS, SLOT_AUX0, SL
        SLOT_GRP_ORDER, SLOT_GRP_KEYS, SLOT_GRP_STARTS, SLOT_GRP_SCRATCH, SLOT_OBB_TABLE, SLOT_OBB_FACETS, SLOT_OBB_CAND, SLOT_FUSE_TABLES, SLOT_FUSE_CARRY, SLOT_FUSE_XYZ, SLOT_FUSION, SLOT_PATCH_STATUS, SLOT_NRM, SLOT_NRM_CAMS,
        SLOT_QRY, SLOT_QRY_IN, SLOT_QRY_OFFS,
        SLOT_FLOOD, SLOT_COLOR, SLOT_CVS_INST, SLOT_CVS_ORDER, SLOT_CVS_COFFS, SLOT_CVS_FLAGS, SLOT_CVS_SEEDS, SLOT_CVS_STATS,
-       SLOT_QUADS, SLOT_QUADS_OUT, SLOT_GROW, SLOT_PVOTE, SLOT_PVOTE_BITS, SLOT_MESH, SLOT_MESH_IO, SLOT_COUNT };
+       SLOT_QUADS, SLOT_QUADS_OUT, SLOT_GROW, SLOT_PVOTE, SLOT_PVOTE_BITS, SLOT_MESH, SLOT_MESH_IO, SLOT_ZKEY, SLOT_ZCOUNTS, SLOT_COUNT };
 
 thread_local char g_create_err[512] = "";
 
@@ -172,6 +172,8 @@ int take_error(f3d_ctx* ctx, hipStream_t s, int mask = F3D_DEVERR_ALL) {
             return fail(ctx, F3D_ERR_INDEX, "point_vote_frames: a mask label exceeds nclasses on a pixel that has a neighbour (the reference raises IndexError at voting.py:257)");
         if (e & F3D_DEVERR_MESH)
             return fail(ctx, F3D_ERR_INDEX, "mesh: a triangle's vertex index is outside [0, nv)");
+        if (e & F3D_DEVERR_ZVOTE)
+            return fail(ctx, F3D_ERR_INDEX, "vote_visible: the mask label of a visible sample exceeds nclasses (the reference raises IndexError at voting.py:98)");
     }
     return F3D_OK;
 }
@@ -2349,6 +2351,146 @@ int f3d_obb_hull_filter(f3d_ctx* ctx, int64_t n, const int32_t* facet_start, con
                                                 (const uint32_t*)ctx->slot[SLOT_GRP_KEYS], (const int64_t*)ctx->slot[SLOT_GRP_STARTS], nids,
                                                 (const int32_t*)dfac, deq, dmg, dcand, dcand + ncand, ctx->stream);
     return st.finish();
+}
+
+// ---------------------------------------------------------------------------------------------
+// occlusion-aware forward voting: point-splat z-buffer renders of the cloud (f3d_render.hip)
+// ---------------------------------------------------------------------------------------------
+#define F3D_ZKEY_BUDGET ((size_t)256 << 20)          // keys of an automatic pass
+#define F3D_RENDER_BAD "bad arguments (n < 2^31, float64 / float32 cloud, h, w > 0, splat in [0, 8])"
+
+static bool render_args_ok(const void* xyz, f3d_dtype dtype, int64_t n, const void* views, int nviews, int h, int w, int splat) {
+    return n >= 0 && n <= 0x7fffffffLL && (dtype == F3D_F64 || dtype == F3D_F32) && nviews >= 0 && h > 0 && w > 0 && splat >= 0 && splat <= 8 &&
+           (n == 0 || xyz) && (nviews == 0 || views);
+}
+
+// views of one pass: views_per_pass, or with 0 as many as fit the budget; at least 1, at most nviews
+static int render_pass_views(int nviews, int h, int w, int views_per_pass) {
+    int64_t per = views_per_pass > 0 ? (int64_t)views_per_pass : (int64_t)(F3D_ZKEY_BUDGET / ((size_t)h * w * 8));
+    if (per < 1) per = 1;
+    return (int)(per < nviews ? per : nviews);
+}
+
+int f3d_ctx_reserve_render(f3d_ctx* ctx, int64_t n, int nviews, int h, int w) {
+    int rc = enter(ctx); if (rc) return rc;
+    if (n < 0 || n > 0x7fffffffLL || nviews < 0 || h <= 0 || w <= 0) return fail(ctx, F3D_ERR_INVALID, "ctx_reserve_render: bad arguments");
+    const int strict = ctx->strict;
+    ctx->strict = 0;
+    void* p;
+    rc = ensure(ctx, SLOT_ZKEY, (size_t)render_pass_views(nviews, h, w, 0) * h * w * 8, &p);
+    ctx->strict = strict;
+    return rc;
+}
+
+int f3d_render_lookups_dev(f3d_ctx* ctx, const void* xyz, f3d_dtype dtype, int64_t n, const f3d_view* views_dev, int nviews, int h, int w,
+                           int splat, float* depth, int32_t* uv2pt, void* stream) {
+    int rc = enter(ctx); if (rc) return rc;
+    if (!render_args_ok(xyz, dtype, n, views_dev, nviews, h, w, splat)) return fail(ctx, F3D_ERR_INVALID, "render_lookups: " F3D_RENDER_BAD);
+    if (nviews == 0 || (!depth && !uv2pt)) return F3D_OK;
+    hipStream_t s = pick(ctx, stream);
+    const size_t hw = (size_t)h * w;
+    const int per = render_pass_views(nviews, h, w, 0);
+    void* zk;
+    if ((rc = ensure(ctx, SLOT_ZKEY, (size_t)per * hw * 8, &zk))) return rc;
+    unsigned long long* zkey = (unsigned long long*)zk;
+    for (int v0 = 0; v0 < nviews; v0 += per) {
+        const int nv = nviews - v0 < per ? nviews - v0 : per;
+        F3D_HIP(ctx, f3d_launch_zkey_fill(zkey, (size_t)nv * hw, s));
+        F3D_HIP(ctx, f3d_launch_zsplat(xyz, dtype, n, views_dev + v0, nv, h, w, splat, zkey, nullptr, s));
+        F3D_HIP(ctx, f3d_launch_zkey_unpack(zkey, (size_t)nv * hw, depth ? depth + (size_t)v0 * hw : nullptr,
+                                            uv2pt ? uv2pt + (size_t)v0 * hw : nullptr, s));
+    }
+    return F3D_OK;
+}
+
+int f3d_render_lookups(f3d_ctx* ctx, const void* xyz, f3d_dtype dtype, int64_t n, const f3d_view* views, int nviews, int h, int w, int splat,
+                       float* depth, int32_t* uv2pt) {
+    int rc = enter(ctx); if (rc) return rc;
+    if (!render_args_ok(xyz, dtype, n, views, nviews, h, w, splat)) return fail(ctx, F3D_ERR_INVALID, "render_lookups: " F3D_RENDER_BAD);
+    if (nviews == 0) return F3D_OK;
+    const size_t cells = (size_t)nviews * h * w;
+    staging st(ctx);
+    const void* dxyz = st.in(SLOT_XYZ, xyz, xyz_bytes(dtype, n));
+    const f3d_view* dviews = st.in(SLOT_VIEWS, views, sizeof(f3d_view) * (size_t)nviews);
+    float* ddepth = st.out(SLOT_OUT0, depth, cells * 4);
+    int32_t* dlut = st.out(SLOT_AUX0, uv2pt, cells * 4);
+    if (!st.rc) st.rc = f3d_render_lookups_dev(ctx, dxyz, dtype, n, dviews, nviews, h, w, splat, ddepth, dlut, ctx->stream);
+    return st.finish();
+}
+
+int f3d_vote_visible_dev(f3d_ctx* ctx, const void* xyz, f3d_dtype dtype, int64_t n, const f3d_view* views_dev, int nviews, const uint8_t* masks,
+                         int h, int w, int splat, double depth_tol, double* votes, int ncols, int views_per_pass, void* stream) {
+    int rc = enter(ctx); if (rc) return rc;
+    if (!render_args_ok(xyz, dtype, n, views_dev, nviews, h, w, splat) || !(depth_tol >= 0.0) || ncols <= 0 || views_per_pass < 0 ||
+        (n > 0 && !votes) || (nviews > 0 && !masks))
+        return fail(ctx, F3D_ERR_INVALID, "vote_visible: " F3D_RENDER_BAD ", depth_tol >= 0, views_per_pass >= 0");
+    if (n == 0 || nviews == 0) return F3D_OK;
+    hipStream_t s = pick(ctx, stream);
+    const size_t hw = (size_t)h * w;
+    const int per = render_pass_views(nviews, h, w, views_per_pass);
+    void* zk;
+    if ((rc = ensure(ctx, SLOT_ZKEY, (size_t)per * hw * 8, &zk))) return rc;
+    unsigned long long* zkey = (unsigned long long*)zk;
+    for (int v0 = 0; v0 < nviews; v0 += per) {                               // a pass: render, then vote (votes are sums over views)
+        const int nv = nviews - v0 < per ? nviews - v0 : per;
+        F3D_HIP(ctx, f3d_launch_zkey_fill(zkey, (size_t)nv * hw, s));
+        F3D_HIP(ctx, f3d_launch_zsplat(xyz, dtype, n, views_dev + v0, nv, h, w, splat, zkey, nullptr, s));
+        F3D_HIP(ctx, f3d_launch_vote_visible(xyz, dtype, n, views_dev + v0, nv, masks + (size_t)v0 * hw, h, w, zkey, depth_tol, votes, ncols,
+                                             ctx->dev_err, s));
+    }
+    return F3D_OK;
+}
+
+int f3d_vote_visible(f3d_ctx* ctx, const void* xyz, f3d_dtype dtype, int64_t n, const f3d_view* views, int nviews, const uint8_t* masks,
+                     int h, int w, int splat, double depth_tol, double* votes, int ncols, int views_per_pass) {
+    int rc = enter(ctx); if (rc) return rc;
+    if (!render_args_ok(xyz, dtype, n, views, nviews, h, w, splat) || !(depth_tol >= 0.0) || ncols <= 0 || views_per_pass < 0 ||
+        (n > 0 && !votes) || (nviews > 0 && !masks))
+        return fail(ctx, F3D_ERR_INVALID, "vote_visible: " F3D_RENDER_BAD ", depth_tol >= 0, views_per_pass >= 0");
+    if (n == 0 || nviews == 0) return F3D_OK;
+    staging st(ctx);
+    const void* dxyz = st.in(SLOT_XYZ, xyz, xyz_bytes(dtype, n));
+    const f3d_view* dviews = st.in(SLOT_VIEWS, views, sizeof(f3d_view) * (size_t)nviews);
+    const uint8_t* dmasks = st.in(SLOT_MASKS, masks, (size_t)nviews * h * w);
+    double* dvotes = st.inout(SLOT_OUT1, votes, (size_t)n * ncols * 8);
+    if (!st.rc) st.rc = f3d_vote_visible_dev(ctx, dxyz, dtype, n, dviews, nviews, dmasks, h, w, splat, depth_tol, dvotes, ncols, views_per_pass,
+                                             ctx->stream);
+    return st.finish(F3D_DEVERR_ZVOTE);                                      // nothing is written back on an IndexError
+}
+
+int f3d_debug_render_counts(f3d_ctx* ctx, const void* xyz, f3d_dtype dtype, int64_t n, const f3d_view* views_dev, int nviews, int h, int w,
+                            int splat, uint64_t counts[3], double ms[2], void* stream) {
+    int rc = enter(ctx); if (rc) return rc;
+    if (!render_args_ok(xyz, dtype, n, views_dev, nviews, h, w, splat) || !counts) return fail(ctx, F3D_ERR_INVALID, "debug_render_counts: " F3D_RENDER_BAD);
+    hipStream_t s = pick(ctx, stream);
+    const size_t hw = (size_t)h * w;
+    const int per = render_pass_views(nviews, h, w, 0);
+    void *zk, *cnt;
+    if ((rc = ensure(ctx, SLOT_ZKEY, (size_t)per * hw * 8, &zk))) return rc;
+    if ((rc = ensure(ctx, SLOT_ZCOUNTS, 3 * sizeof(unsigned long long), &cnt))) return rc;
+    F3D_HIP(ctx, hipMemsetAsync(cnt, 0, 3 * sizeof(unsigned long long), s));
+    hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
+    for (int k = 0; k < 3; ++k) F3D_HIP(ctx, hipEventCreate(&ev[k]));
+    double fill_ms = 0.0, splat_ms = 0.0;
+    hipError_t e = hipSuccess;
+    for (int v0 = 0; v0 < nviews && e == hipSuccess; v0 += per) {            // one synchronisation per pass: the events are read back
+        const int nv = nviews - v0 < per ? nviews - v0 : per;
+        float a = 0.f, b = 0.f;
+        if ((e = hipEventRecord(ev[0], s)) != hipSuccess) break;
+        if ((e = f3d_launch_zkey_fill((unsigned long long*)zk, (size_t)nv * hw, s)) != hipSuccess) break;
+        if ((e = hipEventRecord(ev[1], s)) != hipSuccess) break;
+        if ((e = f3d_launch_zsplat(xyz, dtype, n, views_dev + v0, nv, h, w, splat, (unsigned long long*)zk, (unsigned long long*)cnt, s)) != hipSuccess) break;
+        if ((e = hipEventRecord(ev[2], s)) != hipSuccess) break;
+        if ((e = hipEventSynchronize(ev[2])) != hipSuccess) break;
+        if ((e = hipEventElapsedTime(&a, ev[0], ev[1])) != hipSuccess || (e = hipEventElapsedTime(&b, ev[1], ev[2])) != hipSuccess) break;
+        fill_ms += a; splat_ms += b;
+    }
+    for (int k = 0; k < 3; ++k) (void)hipEventDestroy(ev[k]);
+    F3D_HIP(ctx, e);
+    F3D_HIP(ctx, hipMemcpyAsync(counts, cnt, 3 * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
+    F3D_HIP(ctx, hipStreamSynchronize(s));
+    if (ms) { ms[0] = fill_ms; ms[1] = splat_ms; }
+    return F3D_OK;
 }
 
 }  // extern "C"

@@ -15,7 +15,8 @@
 #define F3D_DEVERR_GROW 64                 // region_grow: seed or neighbour index out of bounds, or a repeated seed
 #define F3D_DEVERR_PVOTE 128               // point_vote_frames: a pixel with a neighbour carries a label > nclasses (voting.py:257)
 #define F3D_DEVERR_MESH 256                // meshUtils: triangle vertex index outside [0, nv)
-#define F3D_DEVERR_ALL 511
+#define F3D_DEVERR_ZVOTE 512               // vote_visible: a visible sample's label >= ncols (voting.py:98)
+#define F3D_DEVERR_ALL 1023
 #define F3D_PLANES_PER_LAUNCH 16
 #define F3D_OBB_MAX_BOXES 4096
 #define F3D_SORT_MAX_CELLS 32767            // + 1 overflow cell = 2^15 keys -> 16 key bits sorted
@@ -449,3 +450,13 @@ hipError_t f3d_launch_mesh_clusters(const void* verts, int vdtype, int64_t nv, c
 hipError_t f3d_launch_mesh_clean(const void* verts, int vdtype, int64_t nv, const void* tris, int itype, int64_t nt, const uint8_t* remove_mask,
                                  int64_t min_triangles, double min_area, void* new_verts, void* new_tris, uint8_t* kept_v, uint8_t* kept_t,
                                  void* scratch, int64_t* counts, int* err, hipStream_t s);
+
+// point-splat z-buffer and the visibility-tested forward vote (f3d_render.hip).  zkey: uint64 [nv, h, w] depth keys of the nv views of
+// a pass (views_dev / masks point at the pass's first view); counts (device uint64 [3], may be NULL) += {samples, cells covered,
+// atomics issued}.  Enqueue only.
+hipError_t f3d_launch_zkey_fill(unsigned long long* zkey, size_t cells, hipStream_t s);
+hipError_t f3d_launch_zsplat(const void* xyz, int dtype, int64_t n, const f3d_view* views_dev, int nv, int h, int w, int splat,
+                             unsigned long long* zkey, unsigned long long* counts, hipStream_t s);
+hipError_t f3d_launch_zkey_unpack(const unsigned long long* zkey, size_t cells, float* depth, int32_t* uv2pt, hipStream_t s);
+hipError_t f3d_launch_vote_visible(const void* xyz, int dtype, int64_t n, const f3d_view* views_dev, int nv, const uint8_t* masks, int h, int w,
+                                   const unsigned long long* zkey, double depth_tol, double* votes, int ncols, int* err, hipStream_t s);

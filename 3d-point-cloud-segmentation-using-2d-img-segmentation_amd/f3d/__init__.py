@@ -115,6 +115,12 @@ def library():
         'f3d_point_vote_frames': (i32, [vp, vp, i32, i64, vp, i32, vp, i64, i64, dbl, vp, i32]),
         'f3d_point_vote_frames_dev': (i32, [vp, vp, i32, i64, vp, i32, vp, i64, i64, dbl, vp, i32, vp]),
         'f3d_ctx_reserve_point_vote': (i32, [vp, i64, i32]),
+        'f3d_render_lookups': (i32, [vp, vp, i32, i64, vp, i32, i32, i32, i32, vp, vp]),
+        'f3d_render_lookups_dev': (i32, [vp, vp, i32, i64, vp, i32, i32, i32, i32, vp, vp, vp]),
+        'f3d_vote_visible': (i32, [vp, vp, i32, i64, vp, i32, vp, i32, i32, i32, dbl, vp, i32, i32]),
+        'f3d_vote_visible_dev': (i32, [vp, vp, i32, i64, vp, i32, vp, i32, i32, i32, dbl, vp, i32, i32, vp]),
+        'f3d_ctx_reserve_render': (i32, [vp, i64, i32, i32, i32]),
+        'f3d_debug_render_counts': (i32, [vp, vp, i32, i64, vp, i32, i32, i32, i32, vp, vp, vp]),
         'f3d_sem_logits_to_mask': (i32, [vp, vp, i32, i64, flt, i32, vp]),
         'f3d_sem_logits_to_mask_dev': (i32, [vp, vp, i32, i64, flt, i32, vp, vp]),
         'f3d_sem_logits_to_masks_dev': (i32, [vp, vp, i32, i32, i64, flt, i32, vp, vp]),
@@ -370,6 +376,10 @@ class Context:
         """Size the scratch of point_vote_frames_dev for clouds of up to m points and ncols vote columns, at any radius."""
         self._check(self._lib.f3d_ctx_reserve_point_vote(self._h, int(m), int(ncols)))
 
+    def reserve_render(self, n, nviews, h, w):
+        """Size the depth keys of render_lookups_dev / vote_visible_dev (automatic pass size) for nviews views of h x w pixels."""
+        self._check(self._lib.f3d_ctx_reserve_render(self._h, int(n), int(nviews), int(h), int(w)))
+
     def set_strict(self, strict=True):
         self._check(self._lib.f3d_ctx_set_strict(self._h, int(bool(strict))))
 
@@ -490,6 +500,36 @@ class Context:
             raise ValueError(f'votes has {votes.shape[0]} rows, the cloud {len(c)} points')
         self._check(self._lib.f3d_point_vote_frames(self._h, _ptr(c), cdt, len(c), _ptr(qq), qdt, _ptr(m), q.shape[0], q.shape[1],
                                                     float(radius), _ptr(votes), votes.shape[1]))
+        return votes
+
+    def render_lookups(self, points, views, h, w, splat=0, want_depth=True, want_uv2pt=True):
+        """Point-splat z-buffer of the cloud in every view (f3d.h f3d_render_lookups) -> depth float32 [V, h, w] (+inf = empty),
+        uv2pt int32 [V, h*w] (-1 = empty): the nearest point by float32 depth per pixel, ties to the lowest index."""
+        p, dt = _xyz(points)
+        views = _f64(views)
+        if views.ndim != 2 or views.shape[1] != VIEW_DOUBLES:
+            raise ValueError(f'views must be [V,{VIEW_DOUBLES}]')
+        V, h, w = len(views), int(h), int(w)
+        depth = np.empty((V, h, w), np.float32) if want_depth else None
+        uv2pt = np.empty((V, h * w), np.int32) if want_uv2pt else None
+        self._check(self._lib.f3d_render_lookups(self._h, _ptr(p), dt, len(p), _ptr(views), V, h, w, int(splat), _ptr(depth), _ptr(uv2pt)))
+        return depth, uv2pt
+
+    def vote_visible(self, votes, points, views, masks, splat=1, depth_tol=0.05, views_per_pass=0):
+        """The forward vote with the visibility test of f3d.h f3d_vote_visible, in place on `votes` (float64 [N, ncols],
+        C-contiguous): only samples within depth_tol of the front surface of their pixel vote.  views_per_pass = 0: automatic."""
+        if votes.dtype != np.float64 or not votes.flags.c_contiguous or votes.ndim != 2:
+            raise ValueError('votes must be a C-contiguous float64 [npts, ncols] array')
+        p, dt = _xyz(points)
+        views = _f64(views)
+        masks = np.ascontiguousarray(masks, dtype=np.uint8)
+        if masks.ndim != 3 or views.ndim != 2 or views.shape[1] != VIEW_DOUBLES or len(views) != len(masks):
+            raise ValueError(f'views must be [V,{VIEW_DOUBLES}] and masks uint8 [V,H,W]')
+        if len(p) != votes.shape[0]:
+            raise ValueError(f'votes has {votes.shape[0]} rows, the cloud {len(p)} points')
+        V, H, W = masks.shape
+        self._check(self._lib.f3d_vote_visible(self._h, _ptr(p), dt, len(p), _ptr(views), V, _ptr(masks), H, W, int(splat), float(depth_tol),
+                                               _ptr(votes), votes.shape[1], int(views_per_pass)))
         return votes
 
     def sem_logits_to_mask(self, sem, conf_threshold=0.017, low_label=133):
@@ -995,6 +1035,25 @@ class Context:
         take_device_error, non-finite queries raise ValueError here after the frames before them are enqueued."""
         self._check(self._lib.f3d_point_vote_frames_dev(self._h, cloud_ptr, int(cloud_dtype), int(m), queries_ptr, int(query_dtype), masks_ptr,
                                                         int(nframes), int(hw), float(radius), votes_ptr, int(ncols), stream))
+
+    def render_lookups_dev(self, xyz_ptr, dtype, n, views_ptr, nviews, h, w, splat, depth_ptr, uv2pt_ptr, stream=None):
+        """depth_ptr float32 [V, h, w] and uv2pt_ptr int32 [V, h*w] on the device, either may be None; enqueue only."""
+        self._check(self._lib.f3d_render_lookups_dev(self._h, xyz_ptr, int(dtype), int(n), views_ptr, int(nviews), int(h), int(w), int(splat),
+                                                     depth_ptr, uv2pt_ptr, stream))
+
+    def vote_visible_dev(self, xyz_ptr, dtype, n, views_ptr, nviews, masks_ptr, h, w, splat, depth_tol, votes_ptr, ncols, views_per_pass=0,
+                         stream=None):
+        """Enqueue only; a label >= ncols on a visible sample is recorded for take_device_error."""
+        self._check(self._lib.f3d_vote_visible_dev(self._h, xyz_ptr, int(dtype), int(n), views_ptr, int(nviews), masks_ptr, int(h), int(w),
+                                                   int(splat), float(depth_tol), votes_ptr, int(ncols), int(views_per_pass), stream))
+
+    def render_counts_dev(self, xyz_ptr, dtype, n, views_ptr, nviews, h, w, splat, stream=None):
+        """Diagnostic (synchronises): samples, covered cells and issued atomics of a render of these views, and the device-event times
+        of the key fill and of the (counting) splat kernel (f3d.h f3d_debug_render_counts)."""
+        counts, ms = np.zeros(3, np.uint64), np.zeros(2)
+        self._check(self._lib.f3d_debug_render_counts(self._h, xyz_ptr, int(dtype), int(n), views_ptr, int(nviews), int(h), int(w), int(splat),
+                                                      _ptr(counts), _ptr(ms), stream))
+        return {'samples': int(counts[0]), 'cells': int(counts[1]), 'atomics': int(counts[2]), 'fill_ms': float(ms[0]), 'splat_ms': float(ms[1])}
 
     def vote_uv2pt_dev(self, uv2pt_ptr, mask_ptr, hw, votes_ptr, npts, ncols, stream=None):
         self._check(self._lib.f3d_vote_uv2pt_dev(self._h, uv2pt_ptr, mask_ptr, hw, votes_ptr, npts, ncols, stream))

@@ -656,6 +656,53 @@ int f3d_point_vote_frames_dev(f3d_ctx* ctx, const void* cloud, f3d_dtype cloud_d
                               double* votes /*device [m, ncols], in place*/, int ncols, void* stream);
 int f3d_ctx_reserve_point_vote(f3d_ctx* ctx, int64_t m, int ncols);
 
+/* ---- occlusion-aware forward voting: point-splat z-buffer renders of the cloud (no reference counterpart) ------------------ */
+/* The forward path (f3d_project_vote_argmax) lets a point vote in every view whose frustum holds it, also through a wall; the
+ * reference's votes go through uv2pt, the pixel -> point table Fusion.fuse builds from depth frames (fusion.py:105-111, :326-327),
+ * so only the surface a camera saw gets its label.  These entries render the cloud itself into per-view depth buffers and give
+ * (1) uv2pt-style lookups for any posed cloud, which feed f3d_vote_uv2pt_batch, and (2) the forward vote with a visibility test.
+ * View j is views[j] from f3d_views_build; point i is the caller-order index, n < 2^31; float32 clouds are widened exactly.
+ *   sample   (h0, h1, h2) = f3d_project_h(p), u = floor(h0 / h2), v = floor(h1 / h2), z32 = (float)h2 rounded to nearest even: the
+ *            arithmetic of f3d_project_view.  Point i has a sample in view j iff it is inside the view's 5 planes (a4),
+ *            0 <= u < w, 0 <= v < h and FLT_MIN <= z32 < +inf (the bits of z32 are then a monotone unsigned key; NaN, zero,
+ *            negative and subnormal depths have no sample).
+ *   key      key(i, j) = (uint64)bits(z32) << 32 | (uint32)i.  Cell (j, r, c) of zkey [V, h, w] is the minimum key over all samples
+ *            (i, j) and offsets |du|, |dv| <= splat with r = v + dv, c = u + du inside the image; all ones when there is none.  The
+ *            nearest point by float32 depth wins, ties go to the lowest index; the result does not depend on thread timing, launch
+ *            shape or the pass size.  splat is an integer in [0, 8]: a point owns the (2 splat + 1)^2 pixel patch around its pixel.
+ *   lookups  depth float32 [V, h, w] = the winning z32, +inf for an empty cell; uv2pt int32 [V, h * w] = the winning index, -1 for
+ *            an empty cell (pixel index v * w + u).  Either may be NULL.
+ *   visible  sample (i, j) is visible iff (double)z32 <= (double)zmin32 + depth_tol, zmin32 = the depth of cell (j, v, u) (never
+ *            empty: the sample covers it).  depth_tol >= 0, +inf allowed (every sample is visible: the votes of
+ *            f3d_project_vote_argmax).
+ *   vote     votes[i, masks[j, v, u]] += 1 for every visible sample; votes float64 [n, ncols], IN PLACE (the layout of
+ *            VotingSegmentation: f3d_segment_votes finishes the job).  A label >= ncols on a visible sample is the reference's
+ *            IndexError: F3D_ERR_INDEX from the host variant, a bit of its own for f3d_take_device_error from the _dev variant;
+ *            the outputs are then unspecified.  Labels of invisible samples are never read.
+ * The keys live in context scratch and the views are processed in passes (render, then unpack or vote) of views_per_pass views;
+ * 0 = as many as fit 256 MiB of keys, at least 1.  Votes are sums over views, so the pass size never changes a result.
+ * F3D_ERR_INVALID: n >= 2^31, splat outside [0, 8], depth_tol negative or NaN, views_per_pass < 0.
+ * f3d_ctx_reserve_render sizes the keys of an automatic pass over nviews views of h x w pixels, the only scratch of the _dev entries:
+ * a strict context then allocates nothing in them with views_per_pass = 0 (or any smaller pass).  The keys do not grow with n, which
+ * is only checked against the limit above. */
+int f3d_render_lookups(f3d_ctx* ctx, const void* xyz, f3d_dtype dtype, int64_t n, const f3d_view* views, int nviews, int h, int w,
+                       int splat, float* depth, int32_t* uv2pt);
+int f3d_render_lookups_dev(f3d_ctx* ctx, const void* xyz, f3d_dtype dtype, int64_t n, const f3d_view* views_dev /*device [V]*/,
+                           int nviews, int h, int w, int splat, float* depth, int32_t* uv2pt, void* stream);
+int f3d_vote_visible(f3d_ctx* ctx, const void* xyz, f3d_dtype dtype, int64_t n, const f3d_view* views, int nviews,
+                     const uint8_t* masks /*[V,H,W]*/, int h, int w, int splat, double depth_tol, double* votes /*[n, ncols], in place*/,
+                     int ncols, int views_per_pass);
+int f3d_vote_visible_dev(f3d_ctx* ctx, const void* xyz, f3d_dtype dtype, int64_t n, const f3d_view* views_dev /*device [V]*/,
+                         int nviews, const uint8_t* masks, int h, int w, int splat, double depth_tol, double* votes, int ncols,
+                         int views_per_pass, void* stream);
+int f3d_ctx_reserve_render(f3d_ctx* ctx, int64_t n, int nviews, int h, int w);
+/* Diagnostic: renders the views like f3d_render_lookups_dev with a counting build of the splat kernel.  counts[0] = samples,
+ * counts[1] = cells they cover, counts[2] = atomics issued (a cell that already held a smaller key is skipped; this count depends on
+ * thread timing, the rendered keys do not).  ms (may be NULL): device-event times of the key fill and of the splat, summed over the
+ * passes.  Device pointers; synchronises `stream` once per pass. */
+int f3d_debug_render_counts(f3d_ctx* ctx, const void* xyz, f3d_dtype dtype, int64_t n, const f3d_view* views_dev, int nviews,
+                            int h, int w, int splat, uint64_t counts[3], double ms[2], void* stream);
+
 /* ---- a5: patch matching of Fusion.fuse (Fusion3DSeg/fusion.py:269-298) ------------------- */
 /* The loop over the in-frustum points ("seeds", in index order) of one frame: seed k takes the still-free depth pixels of
  * the (2*half+1)^2 window around its projection uv[:,k] that lie within `radius` of it and whose normals satisfy
