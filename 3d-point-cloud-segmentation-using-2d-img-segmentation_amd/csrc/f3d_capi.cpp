@@ -51,15 +51,12 @@ struct f3d_ctx {
     int32_t filter_host[F3D_MAX_FILTER];  // its staging copy: must outlive the asynchronous upload
     unsigned long long* count_dev;
     f3d_codebook* codebook;             // vote-bin code book of the fused path (device)
-    // radius graph: the grid of the last count pass (the fill pass must follow it for the same cloud)
-    f3d_graphgrid graph_grid;
+    // radius graph: the search of the last count pass (the fill pass must follow it for the same cloud)
+    f3d_gridsearch graph;
     int64_t graph_n;
-    double graph_r2;
     const void* graph_xyz;
-    // radius query: the data's grid of the last count pass, in slots of its own (SLOT_QRY*), for the fill pass of the same queries
-    f3d_graphgrid qry_grid;
-    double qry_lo[3], qry_hi[3];
-    double qry_r2;
+    // radius query: the search of the last count pass, in slots of its own (SLOT_QRY*), for the fill pass of the same queries
+    f3d_gridsearch qry;
     int64_t qry_m, qry_n;
     int qry_qdtype;
     const void* qry_queries;
@@ -1894,6 +1891,27 @@ static int cloud_bbox(f3d_ctx* ctx, const void* xyz, f3d_dtype dtype, int64_t n,
     return F3D_OK;
 }
 
+// a search grid fits when every axis has <= 1024 cells and the cell table <= 2^24 cells
+constexpr int64_t GRID_MAX_CELLS = 16777216;
+static bool search_grid_fits(const double d[3]) {
+    return d[0] <= 1024.0 && d[1] <= 1024.0 && d[2] <= 1024.0 && d[0] * d[1] * d[2] <= (double)GRID_MAX_CELLS;
+}
+
+// What a radius search in a cloud needs (f3d_gridsearch), from the cloud's bounding box (cloud_bbox: synchronises): the grid with a
+// cell edge a hair above the radius, the box grown by one cell and sklearn's reduced radius r ** 2.  radius < 0 or NaN: no pair at
+// all (sklearn); the grid is built for radius 0 and no distance passes r2 = -1.
+static int cloud_search(f3d_ctx* ctx, const void* xyz, f3d_dtype dtype, int64_t n, double radius, hipStream_t s, const char* op,
+                        f3d_gridsearch* gs) {
+    double lo[3], ext[3];
+    int rc = cloud_bbox(ctx, xyz, dtype, n, s, op, lo, ext); if (rc) return rc;
+    const bool none = !(radius >= 0.0);
+    const double cell = neighbour_cell(none ? 0.0 : radius, ext, gs->g.dim, search_grid_fits);
+    for (int c = 0; c < 3; ++c) { gs->g.lo[c] = lo[c]; gs->reach.lo[c] = lo[c] - cell; gs->reach.hi[c] = (lo[c] + ext[c]) + cell; }
+    gs->g.inv_cell = 1.0 / cell; gs->g.pad = 0;
+    gs->r2 = none ? -1.0 : radius * radius;
+    return F3D_OK;
+}
+
 int f3d_radius_graph_count_dev(f3d_ctx* ctx, const void* xyz, f3d_dtype dtype, int64_t n, double radius, int64_t* offsets,
                                int64_t* nnz, void* stream) {
     int rc = enter(ctx); if (rc) return rc;
@@ -1902,23 +1920,14 @@ int f3d_radius_graph_count_dev(f3d_ctx* ctx, const void* xyz, f3d_dtype dtype, i
     *nnz = 0; ctx->graph_n = -1;
     if (n == 0) return F3D_OK;
     hipStream_t s = pick(ctx, stream);
-    double lo[3], ext[3];
-    if ((rc = cloud_bbox(ctx, xyz, dtype, n, s, "radius_graph", lo, ext))) return rc;     // NaN: sklearn's KDTree raises ValueError
-    // the grid fits when every axis has <= 1024 cells and the table <= 2^24 cells
-    f3d_graphgrid g;
-    const double cell = neighbour_cell(radius, ext, g.dim, [](const double d[3]) {
-        return d[0] <= 1024.0 && d[1] <= 1024.0 && d[2] <= 1024.0 && d[0] * d[1] * d[2] <= 16777216.0;
-    });
-    for (int c = 0; c < 3; ++c) g.lo[c] = lo[c];
-    g.inv_cell = 1.0 / cell; g.pad = 0;
-    const int64_t ncells = (int64_t)g.dim[0] * g.dim[1] * g.dim[2];
+    f3d_gridsearch gs;
+    if ((rc = cloud_search(ctx, xyz, dtype, n, radius, s, "radius_graph", &gs))) return rc;   // NaN: sklearn's KDTree raises ValueError
     void* scratch;
-    if ((rc = ensure(ctx, SLOT_GRAPH, f3d_graph_scratch_bytes(n, ncells), &scratch))) return rc;
-    const double r2 = radius * radius;                                     // sklearn: reduced radius = r ** 2
-    F3D_HIP(ctx, f3d_launch_graph_count(xyz, dtype, n, g, r2, scratch, offsets, s));
+    if ((rc = ensure(ctx, SLOT_GRAPH, f3d_graph_scratch_bytes(n, f3d_ncells(gs.g)), &scratch))) return rc;
+    F3D_HIP(ctx, f3d_launch_graph_count(xyz, dtype, n, gs, scratch, offsets, s));
     F3D_HIP(ctx, hipMemcpyAsync(nnz, offsets + n, 8, hipMemcpyDeviceToHost, s));
     F3D_HIP(ctx, hipStreamSynchronize(s));
-    ctx->graph_grid = g; ctx->graph_n = n; ctx->graph_r2 = r2; ctx->graph_xyz = xyz;
+    ctx->graph = gs; ctx->graph_n = n; ctx->graph_xyz = xyz;
     return F3D_OK;
 }
 
@@ -1927,7 +1936,7 @@ int f3d_radius_graph_fill_dev(f3d_ctx* ctx, int64_t n, const int64_t* offsets, i
     if (n != ctx->graph_n || n < 0) return fail(ctx, F3D_ERR_INVALID, "radius_graph_fill: call f3d_radius_graph_count for this cloud first");
     if (n == 0) return F3D_OK;
     if (!offsets || !nbrs) return fail(ctx, F3D_ERR_INVALID, "radius_graph_fill: bad arguments");
-    F3D_HIP(ctx, f3d_launch_graph_fill(n, ctx->graph_grid, ctx->graph_r2, ctx->slot[SLOT_GRAPH], offsets, nbrs, pick(ctx, stream)));
+    F3D_HIP(ctx, f3d_launch_graph_fill(n, ctx->graph, ctx->slot[SLOT_GRAPH], offsets, nbrs, pick(ctx, stream)));
     return F3D_OK;
 }
 
@@ -1974,29 +1983,16 @@ int f3d_radius_query_count_dev(f3d_ctx* ctx, const void* data, f3d_dtype ddtype,
     *nnz = 0;
     if (n == 0) { ctx->qry_n = 0; return F3D_OK; }
     hipStream_t s = pick(ctx, stream);
-    double lo[3], ext[3];
-    if ((rc = cloud_bbox(ctx, data, ddtype, m, s, "radius_query", lo, ext))) return rc;
-    // radius < 0 or NaN: every row is empty (sklearn); the grid is built for radius 0 and no distance passes r2 = -1
-    const bool none = !(radius >= 0.0);
-    f3d_graphgrid g;
-    const double cell = neighbour_cell(none ? 0.0 : radius, ext, g.dim, [](const double d[3]) {
-        return d[0] <= 1024.0 && d[1] <= 1024.0 && d[2] <= 1024.0 && d[0] * d[1] * d[2] <= 16777216.0;
-    });
-    for (int c = 0; c < 3; ++c) g.lo[c] = lo[c];
-    g.inv_cell = 1.0 / cell; g.pad = 0;
-    double blo[3], bhi[3];                                                  // a query outside this box is more than one cell (> r) away
-    for (int c = 0; c < 3; ++c) { blo[c] = lo[c] - cell; bhi[c] = (lo[c] + ext[c]) + cell; }
-    const int64_t ncells = (int64_t)g.dim[0] * g.dim[1] * g.dim[2];
+    f3d_gridsearch gs;
+    if ((rc = cloud_search(ctx, data, ddtype, m, radius, s, "radius_query", &gs))) return rc;
     void* scratch;
-    if ((rc = ensure(ctx, SLOT_QRY, f3d_query_scratch_bytes(m, n, ncells), &scratch))) return rc;
-    const double r2 = none ? -1.0 : radius * radius;                       // sklearn: reduced radius = r ** 2, inclusive
+    if ((rc = ensure(ctx, SLOT_QRY, f3d_query_scratch_bytes(m, n, f3d_ncells(gs.g)), &scratch))) return rc;
     int64_t words[2] = {0, 0};
-    F3D_HIP(ctx, f3d_launch_query_count(data, ddtype, m, queries, qdtype, n, g, blo, bhi, r2, scratch, offsets, words, s));
+    F3D_HIP(ctx, f3d_launch_query_count(data, ddtype, m, queries, qdtype, n, gs, scratch, offsets, words, s));
     F3D_HIP(ctx, hipStreamSynchronize(s));
     if (words[1]) return fail(ctx, F3D_ERR_INVALID, "radius_query: the queries contain NaN or infinity");
     *nnz = words[0];
-    ctx->qry_grid = g; ctx->qry_r2 = r2; ctx->qry_m = m; ctx->qry_n = n; ctx->qry_qdtype = qdtype; ctx->qry_queries = queries;
-    for (int c = 0; c < 3; ++c) { ctx->qry_lo[c] = blo[c]; ctx->qry_hi[c] = bhi[c]; }
+    ctx->qry = gs; ctx->qry_m = m; ctx->qry_n = n; ctx->qry_qdtype = qdtype; ctx->qry_queries = queries;
     return F3D_OK;
 }
 
@@ -2007,8 +2003,7 @@ int f3d_radius_query_fill_dev(f3d_ctx* ctx, const void* queries, f3d_dtype qdtyp
         return fail(ctx, F3D_ERR_INVALID, "radius_query_fill: call f3d_radius_query_count for these queries first");
     if (n == 0) return F3D_OK;
     if (!offsets || !nbrs) return fail(ctx, F3D_ERR_INVALID, "radius_query_fill: bad arguments");
-    F3D_HIP(ctx, f3d_launch_query_fill(queries, qdtype, ctx->qry_m, n, ctx->qry_grid, ctx->qry_lo, ctx->qry_hi, ctx->qry_r2, ctx->slot[SLOT_QRY],
-                                       offsets, nbrs, pick(ctx, stream)));
+    F3D_HIP(ctx, f3d_launch_query_fill(queries, qdtype, ctx->qry_m, n, ctx->qry, ctx->slot[SLOT_QRY], offsets, nbrs, pick(ctx, stream)));
     return F3D_OK;
 }
 
@@ -2048,10 +2043,6 @@ int f3d_radius_query_fill(f3d_ctx* ctx, int64_t n, int32_t* nbrs) {
 // ---------------------------------------------------------------------------------------------
 // PointVotingSegmentation.vote: radius search of the frame pixels in a cloud fused with the frame vote (voting.py:224-265)
 // ---------------------------------------------------------------------------------------------
-static bool pvote_grid_fits(const double d[3]) {
-    return d[0] <= 1024.0 && d[1] <= 1024.0 && d[2] <= 1024.0 && d[0] * d[1] * d[2] <= 16777216.0;
-}
-
 int f3d_ctx_reserve_point_vote(f3d_ctx* ctx, int64_t m, int ncols) {
     int rc = enter(ctx); if (rc) return rc;
     if (m < 0 || m > 0x7fffffffLL || ncols <= 0) return fail(ctx, F3D_ERR_INVALID, "ctx_reserve_point_vote: bad arguments");
@@ -2059,7 +2050,7 @@ int f3d_ctx_reserve_point_vote(f3d_ctx* ctx, int64_t m, int ncols) {
     ctx->strict = 0;
     void* p;
     rc = ensure(ctx, SLOT_GRAPH_BBOX, f3d_graph_bbox_bytes(), &p);
-    if (!rc) rc = ensure(ctx, SLOT_PVOTE, f3d_graph_scratch_bytes(m, 16777216), &p);          // (any grid the radius allows)
+    if (!rc) rc = ensure(ctx, SLOT_PVOTE, f3d_graph_scratch_bytes(m, GRID_MAX_CELLS), &p);          // (any grid the radius allows)
     if (!rc) rc = ensure(ctx, SLOT_PVOTE_BITS, f3d_pvote_bits_bytes(m, ncols, f3d_pvote_group(m, ncols)), &p);
     ctx->strict = strict;
     return rc;
@@ -2084,30 +2075,20 @@ int f3d_point_vote_frames_dev(f3d_ctx* ctx, const void* cloud, f3d_dtype cdtype,
         F3D_HIP(ctx, f3d_launch_pvote_prepass(queries, qdtype, masks, nframes, hw, ncols, ctx->pv_words, s));
         F3D_HIP(ctx, hipMemcpyAsync(words, ctx->pv_words, sizeof words, hipMemcpyDeviceToHost, s));
     }
-    double lo[3], ext[3];
-    if ((rc = cloud_bbox(ctx, cloud, cdtype, m, s, "point_vote_frames", lo, ext))) return rc;      // (synchronises)
+    f3d_gridsearch gs;
+    if ((rc = cloud_search(ctx, cloud, cdtype, m, radius, s, "point_vote_frames", &gs))) return rc;   // (synchronises)
     if (!work) return F3D_OK;
     const int64_t bad_query = words[1] == F3D_PVOTE_NONE ? nframes : words[1];                     // frames from here on never ran
-    // radius < 0 or NaN: no pair at all (sklearn); the grid is built for radius 0 and no distance passes r2 = -1
-    const bool none = !(radius >= 0.0);
-    f3d_graphgrid g;
-    const double cell = neighbour_cell(none ? 0.0 : radius, ext, g.dim, pvote_grid_fits);
-    for (int c = 0; c < 3; ++c) g.lo[c] = lo[c];
-    g.inv_cell = 1.0 / cell; g.pad = 0;
-    f3d_pvote_box box;                                                       // a pixel outside this box is more than one cell (> r) away
-    for (int c = 0; c < 3; ++c) { box.lo[c] = lo[c] - cell; box.hi[c] = (lo[c] + ext[c]) + cell; }
-    const double r2 = none ? -1.0 : radius * radius;
     if (bad_query > 0) {
-        const int64_t ncells = (int64_t)g.dim[0] * g.dim[1] * g.dim[2];
         const int group = (int)(bad_query < f3d_pvote_group(m, ncols) ? bad_query : f3d_pvote_group(m, ncols));
         void *scratch, *bits;
-        if ((rc = ensure(ctx, SLOT_PVOTE, f3d_graph_scratch_bytes(m, ncells), &scratch))) return rc;
+        if ((rc = ensure(ctx, SLOT_PVOTE, f3d_graph_scratch_bytes(m, f3d_ncells(gs.g)), &scratch))) return rc;
         if ((rc = ensure(ctx, SLOT_PVOTE_BITS, f3d_pvote_bits_bytes(m, ncols, group), &bits))) return rc;
         f3d_gridview gv;
-        F3D_HIP(ctx, f3d_launch_graph_grid(cloud, cdtype, m, g, scratch, &gv, s));
+        F3D_HIP(ctx, f3d_launch_graph_grid(cloud, cdtype, m, gs.g, scratch, &gv, s));
         if (words[0])                                                        // the second search: only when a label > nclasses exists
-            F3D_HIP(ctx, f3d_launch_pvote_validate(queries, qdtype, masks, bad_query, hw, ncols, gv, g, box, r2, ctx->pv_words, s));
-        F3D_HIP(ctx, f3d_launch_pvote_frames(queries, qdtype, masks, bad_query, hw, m, ncols, gv, g, box, r2, votes, (uint32_t*)bits, group,
+            F3D_HIP(ctx, f3d_launch_pvote_validate(queries, qdtype, masks, bad_query, hw, ncols, gv, gs, ctx->pv_words, s));
+        F3D_HIP(ctx, f3d_launch_pvote_frames(queries, qdtype, masks, bad_query, hw, m, ncols, gv, gs, votes, (uint32_t*)bits, group,
                                              ctx->pv_words, ctx->dev_err, s));
         if (words[0]) F3D_HIP(ctx, f3d_launch_pvote_flag(ctx->pv_words, (int)bad_query, ctx->dev_err, s));
     }

@@ -7,10 +7,9 @@
 //   k_graph_cells     : [first, last) position of every non-empty cell in the sorted order
 //   k_graph_gather    : sorted float64 copy of the cloud (candidate loops read it contiguously)
 //   k_graph_scan<0>   : neighbours per point -> counts[orig] ; rocprim exclusive scan -> offsets[n + 1]
-//   k_graph_scan<1>   : same loops, writes the neighbours' caller-order indices at offsets[orig]
-// The distance test is the tree's leaf test, operation for operation (sklearn/metrics/_dist_metrics: euclidean_rdist
-// accumulates tmp * tmp over the 3 coordinates left to right; query_radius compares it with r * r, inclusive).  The
-// order inside a row is (cell, index) instead of the tree's traversal order, which sklearn does not specify either.
+//   k_graph_scan<1>   : same walk, writes the neighbours' caller-order indices at offsets[orig]
+// The walk and its distance test are f3d_grid_walk (f3d_kernels.h).  The order inside a row is (cell, index) instead of the tree's
+// traversal order, which sklearn does not specify either.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <cstring>
@@ -33,7 +32,7 @@ __global__ __launch_bounds__(GB) void k_graph_bbox(const T* __restrict__ xyz, in
 #pragma unroll
         for (int c = 0; c < 3; ++c) {
             const double x = (double)xyz[3 * i + c];
-            if (fabs(x) <= 1.7976931348623157e308) { lo[c] = fmin(lo[c], x); hi[c] = fmax(hi[c], x); } else ++bad;
+            if (f3d_finite(x)) { lo[c] = fmin(lo[c], x); hi[c] = fmax(hi[c], x); } else ++bad;
         }
     }
     __shared__ gbox sh[GB / 64];
@@ -87,35 +86,17 @@ __global__ __launch_bounds__(GB) void k_graph_gather(const T* __restrict__ xyz, 
 // one thread per point, in cell order (a wave's threads walk nearly the same candidate ranges)
 template <bool FILL>
 __global__ __launch_bounds__(GB) void k_graph_scan(const double* __restrict__ sorted, int64_t n, const uint32_t* __restrict__ perm,
-                                                    f3d_graphgrid g, const int2* __restrict__ cells, double r2,
-                                                    int64_t* __restrict__ offsets, int32_t* __restrict__ nbrs) {
+                                                    const int2* __restrict__ cells, f3d_gridsearch gs, int64_t* __restrict__ offsets,
+                                                    int32_t* __restrict__ nbrs) {
+    const f3d_gridview gv = {sorted, perm, cells};
     for (int64_t j = (int64_t)blockIdx.x * GB + threadIdx.x; j < n; j += (int64_t)gridDim.x * GB) {
-        const double px = sorted[3 * j], py = sorted[3 * j + 1], pz = sorted[3 * j + 2];
-        int cx, cy, cz;
-        f3d_cell_of(g, px, py, pz, cx, cy, cz);
         const int64_t orig = perm[j];
         int64_t out = FILL ? offsets[orig] : 0;
-        for (int dz = -1; dz <= 1; ++dz) {
-            const int z = cz + dz;
-            if (z < 0 || z >= g.dim[2]) continue;
-            for (int dy = -1; dy <= 1; ++dy) {
-                const int y = cy + dy;
-                if (y < 0 || y >= g.dim[1]) continue;
-                for (int dx = -1; dx <= 1; ++dx) {
-                    const int x = cx + dx;
-                    if (x < 0 || x >= g.dim[0]) continue;
-                    const int2 range = cells[(z * g.dim[1] + y) * g.dim[0] + x];
-                    for (int k = range.x; k < range.y; ++k) {
-                        const double t0 = px - sorted[3 * (int64_t)k], t1 = py - sorted[3 * (int64_t)k + 1], t2 = pz - sorted[3 * (int64_t)k + 2];
-                        const double d = (t0 * t0 + t1 * t1) + t2 * t2;            // euclidean_rdist, left to right
-                        if (d <= r2) {
-                            if (FILL) nbrs[out] = (int32_t)perm[k];
-                            ++out;
-                        }
-                    }
-                }
-            }
-        }
+        f3d_grid_walk(gv, gs.g, sorted[3 * j], sorted[3 * j + 1], sorted[3 * j + 2], gs.r2, [&](int k) {
+            if (FILL) nbrs[out] = (int32_t)perm[k];
+            ++out;
+            return false;
+        });
         if (!FILL) offsets[orig] = out;
     }
 }
@@ -131,11 +112,17 @@ graph_layout layout_for(int64_t n, int64_t ncells, size_t temp_bytes) {
     return L;
 }
 
-size_t temp_bytes_for(int64_t n) {
+// rocprim's temporary storage: the cell sort of `nsort` points and the scan of `nscan` + 1 offsets share it
+size_t temp_bytes_for(int64_t nsort, int64_t nscan) {
     size_t a = 0, b = 0;
-    (void)rocprim::radix_sort_pairs(nullptr, a, (uint32_t*)nullptr, (uint32_t*)nullptr, (uint32_t*)nullptr, (uint32_t*)nullptr, (size_t)n, 0u, 32u);
-    (void)rocprim::exclusive_scan(nullptr, b, (int64_t*)nullptr, (int64_t*)nullptr, (int64_t)0, (size_t)n + 1, rocprim::plus<int64_t>());
+    (void)rocprim::radix_sort_pairs(nullptr, a, (uint32_t*)nullptr, (uint32_t*)nullptr, (uint32_t*)nullptr, (uint32_t*)nullptr, (size_t)nsort, 0u, 32u);
+    (void)rocprim::exclusive_scan(nullptr, b, (int64_t*)nullptr, (int64_t*)nullptr, (int64_t)0, (size_t)nscan + 1, rocprim::plus<int64_t>());
     return (a > b ? a : b) + 256;
+}
+
+f3d_gridview view_of(const void* scratch, const graph_layout& L) {
+    const char* base = (const char*)scratch;
+    return {(const double*)(base + L.sorted), (const uint32_t*)(base + L.perm), (const int2*)(base + L.cells)};
 }
 
 }  // namespace
@@ -162,12 +149,12 @@ int f3d_graph_reduce_bbox(const void* partial_host, int nblocks, double lo[3], d
     return bad ? 1 : 0;
 }
 
-size_t f3d_graph_scratch_bytes(int64_t n, int64_t ncells) { return layout_for(n, ncells, temp_bytes_for(n)).total; }
+size_t f3d_graph_scratch_bytes(int64_t n, int64_t ncells) { return layout_for(n, ncells, temp_bytes_for(n, n)).total; }
 
 // the grid itself, shared by the radius graph and the radius query: cell keys, stable sort by cell, cell table, sorted float64 copy
 static hipError_t build_grid(const void* xyz, int dtype, int64_t n, const f3d_graphgrid& g, const graph_layout& L, size_t tb, char* base,
                              hipStream_t s) {
-    const int64_t ncells = (int64_t)g.dim[0] * g.dim[1] * g.dim[2];
+    const int64_t ncells = f3d_ncells(g);
     uint32_t *ka = (uint32_t*)(base + L.keys_a), *kb = (uint32_t*)(base + L.keys_b), *ia = (uint32_t*)(base + L.idx_a), *perm = (uint32_t*)(base + L.perm);
     double* sorted = (double*)(base + L.sorted);
     int2* cells = (int2*)(base + L.cells);
@@ -189,26 +176,23 @@ static hipError_t build_grid(const void* xyz, int dtype, int64_t n, const f3d_gr
 // the grid alone, for searches that keep no CSR (f3d_pointvote.hip): scratch holds f3d_graph_scratch_bytes(n, ncells)
 hipError_t f3d_launch_graph_grid(const void* xyz, int dtype, int64_t n, const f3d_graphgrid& g, void* scratch, f3d_gridview* view,
                                  hipStream_t s) {
-    const int64_t ncells = (int64_t)g.dim[0] * g.dim[1] * g.dim[2];
-    const size_t tb = temp_bytes_for(n);
-    const graph_layout L = layout_for(n, ncells, tb);
-    char* base = (char*)scratch;
-    view->sorted = (const double*)(base + L.sorted); view->perm = (const uint32_t*)(base + L.perm); view->cells = (const int2*)(base + L.cells);
-    return build_grid(xyz, dtype, n, g, L, tb, base, s);
+    const size_t tb = temp_bytes_for(n, n);
+    const graph_layout L = layout_for(n, f3d_ncells(g), tb);
+    *view = view_of(scratch, L);
+    return build_grid(xyz, dtype, n, g, L, tb, (char*)scratch, s);
 }
 
 // count pass after the grid is known: sort by cell, cell table, sorted copy, neighbour counts, exclusive scan into offsets[n + 1]
-hipError_t f3d_launch_graph_count(const void* xyz, int dtype, int64_t n, const f3d_graphgrid& g, double r2, void* scratch,
-                                  int64_t* offsets, hipStream_t s) {
-    const int64_t ncells = (int64_t)g.dim[0] * g.dim[1] * g.dim[2];
-    const size_t tb = temp_bytes_for(n);
-    const graph_layout L = layout_for(n, ncells, tb);
+hipError_t f3d_launch_graph_count(const void* xyz, int dtype, int64_t n, const f3d_gridsearch& gs, void* scratch, int64_t* offsets,
+                                  hipStream_t s) {
+    const size_t tb = temp_bytes_for(n, n);
+    const graph_layout L = layout_for(n, f3d_ncells(gs.g), tb);
     char* base = (char*)scratch;
-    hipError_t e = build_grid(xyz, dtype, n, g, L, tb, base, s);
+    hipError_t e = build_grid(xyz, dtype, n, gs.g, L, tb, base, s);
     if (e != hipSuccess) return e;
-    const dim3 gr(f3d_grid_for(n, GB, 8192)), b(GB);
-    hipLaunchKernelGGL(k_graph_scan<false>, gr, b, 0, s, (const double*)(base + L.sorted), n, (const uint32_t*)(base + L.perm), g,
-                       (const int2*)(base + L.cells), r2, offsets, (int32_t*)nullptr);
+    const f3d_gridview gv = view_of(scratch, L);
+    hipLaunchKernelGGL(k_graph_scan<false>, dim3(f3d_grid_for(n, GB, 8192)), dim3(GB), 0, s, gv.sorted, n, gv.perm, gv.cells, gs, offsets,
+                       (int32_t*)nullptr);
     e = hipMemsetAsync(offsets + n, 0, 8, s);
     if (e != hipSuccess) return e;
     size_t t = tb;
@@ -218,13 +202,11 @@ hipError_t f3d_launch_graph_count(const void* xyz, int dtype, int64_t n, const f
 }
 
 // fill pass: the scratch still holds the grid of the count pass
-hipError_t f3d_launch_graph_fill(int64_t n, const f3d_graphgrid& g, double r2, const void* scratch, const int64_t* offsets,
-                                 int32_t* nbrs, hipStream_t s) {
-    const int64_t ncells = (int64_t)g.dim[0] * g.dim[1] * g.dim[2];
-    const graph_layout L = layout_for(n, ncells, temp_bytes_for(n));
-    const char* base = (const char*)scratch;
-    hipLaunchKernelGGL(k_graph_scan<true>, dim3(f3d_grid_for(n, GB, 8192)), dim3(GB), 0, s, (const double*)(base + L.sorted), n,
-                       (const uint32_t*)(base + L.perm), g, (const int2*)(base + L.cells), r2, const_cast<int64_t*>(offsets), nbrs);
+hipError_t f3d_launch_graph_fill(int64_t n, const f3d_gridsearch& gs, const void* scratch, const int64_t* offsets, int32_t* nbrs,
+                                 hipStream_t s) {
+    const f3d_gridview gv = view_of(scratch, layout_for(n, f3d_ncells(gs.g), temp_bytes_for(n, n)));
+    hipLaunchKernelGGL(k_graph_scan<true>, dim3(f3d_grid_for(n, GB, 8192)), dim3(GB), 0, s, gv.sorted, n, gv.perm, gv.cells, gs,
+                       const_cast<int64_t*>(offsets), nbrs);
     return hipGetLastError();
 }
 
@@ -233,18 +215,14 @@ hipError_t f3d_launch_graph_fill(int64_t n, const f3d_graphgrid& g, double r2, c
 //   the data's grid is built as above (build_grid); one thread per query point, in the caller's order
 //   k_query_scan<0>   : matches per query -> offsets[q]; non-finite queries raise a flag (sklearn rejects them)
 //   rocprim exclusive scan -> offsets[n + 1]
-//   k_query_scan<1>   : same loops, writes the matches' caller-order data indices; the cell walk leaves <= 27 ascending runs, which
+//   k_query_scan<1>   : same walk, writes the matches' caller-order data indices; the cell walk leaves <= 27 ascending runs, which
 //                       the thread sorts in place when the row is short, else it lists the row for k_query_sort_long
 //   k_query_sort_long : one block per listed row, a bitonic network in LDS (or in place in global memory past the LDS capacity)
-// A query more than one cell outside the data's box cannot match anything (cell > r) and skips the walk.  Inside that margin
-// the clamped cell of f3d_cell_of is safe: clamping never moves two points more than one cell apart, and every candidate still
-// gets the exact test.
+// A query outside the reach box (f3d_gridsearch) cannot match anything and skips the walk.
 namespace {
 
 constexpr int QRY_SHORT = 32;           // rows up to this length are sorted by their own thread (insertion sort)
 constexpr int QRY_LDS = 8192;           // longest row k_query_sort_long sorts in LDS (32 KiB)
-
-struct qbox { double lo[3], hi[3]; };   // the data's box grown by one cell
 
 struct query_layout { graph_layout grid; size_t words, longrows, total; };
 
@@ -259,50 +237,23 @@ query_layout query_layout_for(int64_t m, int64_t n, int64_t ncells, size_t temp_
     return Q;
 }
 
-size_t query_temp_bytes(int64_t m, int64_t n) {
-    size_t a = 0, b = 0;
-    (void)rocprim::radix_sort_pairs(nullptr, a, (uint32_t*)nullptr, (uint32_t*)nullptr, (uint32_t*)nullptr, (uint32_t*)nullptr, (size_t)m, 0u, 32u);
-    (void)rocprim::exclusive_scan(nullptr, b, (int64_t*)nullptr, (int64_t*)nullptr, (int64_t)0, (size_t)n + 1, rocprim::plus<int64_t>());
-    return (a > b ? a : b) + 256;
-}
-
 template <typename T, bool FILL>
 __global__ __launch_bounds__(GB) void k_query_scan(const T* __restrict__ q, int64_t n, const double* __restrict__ sorted,
-                                                    const uint32_t* __restrict__ perm, f3d_graphgrid g, qbox box, const int2* __restrict__ cells,
-                                                    double r2, int64_t* __restrict__ offsets, int32_t* __restrict__ nbrs,
+                                                    const uint32_t* __restrict__ perm, const int2* __restrict__ cells, f3d_gridsearch gs,
+                                                    int64_t* __restrict__ offsets, int32_t* __restrict__ nbrs,
                                                     unsigned long long* __restrict__ words, int32_t* __restrict__ longrows) {
+    const f3d_gridview gv = {sorted, perm, cells};
     for (int64_t i = (int64_t)blockIdx.x * GB + threadIdx.x; i < n; i += (int64_t)gridDim.x * GB) {
         const double px = (double)q[3 * i], py = (double)q[3 * i + 1], pz = (double)q[3 * i + 2];
         const int64_t start = FILL ? offsets[i] : 0, end = FILL ? offsets[i + 1] : 0;
         int64_t out = start;
-        if (!FILL && !(fabs(px) <= 1.7976931348623157e308 && fabs(py) <= 1.7976931348623157e308 && fabs(pz) <= 1.7976931348623157e308))
-            atomicOr(&words[1], 1ull);
-        // (false for NaN as well)
-        if (px >= box.lo[0] && px <= box.hi[0] && py >= box.lo[1] && py <= box.hi[1] && pz >= box.lo[2] && pz <= box.hi[2]) {
-            int cx, cy, cz;
-            f3d_cell_of(g, px, py, pz, cx, cy, cz);
-            for (int dz = -1; dz <= 1; ++dz) {
-                const int z = cz + dz;
-                if (z < 0 || z >= g.dim[2]) continue;
-                for (int dy = -1; dy <= 1; ++dy) {
-                    const int y = cy + dy;
-                    if (y < 0 || y >= g.dim[1]) continue;
-                    for (int dx = -1; dx <= 1; ++dx) {
-                        const int x = cx + dx;
-                        if (x < 0 || x >= g.dim[0]) continue;
-                        const int2 range = cells[(z * g.dim[1] + y) * g.dim[0] + x];
-                        for (int k = range.x; k < range.y; ++k) {
-                            const double t0 = px - sorted[3 * (int64_t)k], t1 = py - sorted[3 * (int64_t)k + 1], t2 = pz - sorted[3 * (int64_t)k + 2];
-                            const double d = (t0 * t0 + t1 * t1) + t2 * t2;            // euclidean_rdist, left to right
-                            if (d <= r2) {
-                                if (FILL && out < end) nbrs[out] = (int32_t)perm[k];   // (queries changed since the count: never past the row)
-                                ++out;
-                            }
-                        }
-                    }
-                }
-            }
-        }
+        if (!FILL && !f3d_finite(px, py, pz)) atomicOr(&words[1], 1ull);
+        if (f3d_in_box(gs.reach, px, py, pz))
+            f3d_grid_walk(gv, gs.g, px, py, pz, gs.r2, [&](int k) {
+                if (FILL && out < end) nbrs[out] = (int32_t)perm[k];               // (queries changed since the count: never past the row)
+                ++out;
+                return false;
+            });
         if (FILL) out = min(out, end);
         if (!FILL) {
             offsets[i] = out;
@@ -365,31 +316,25 @@ __global__ __launch_bounds__(GB) void k_query_sort_long(const int64_t* __restric
 }  // namespace
 
 size_t f3d_query_scratch_bytes(int64_t m, int64_t n, int64_t ncells) {
-    return query_layout_for(m, n, ncells, query_temp_bytes(m, n)).total;
+    return query_layout_for(m, n, ncells, temp_bytes_for(m, n)).total;
 }
 
-hipError_t f3d_launch_query_count(const void* data, int ddtype, int64_t m, const void* queries, int qdtype, int64_t n, const f3d_graphgrid& g,
-                                  const double box_lo[3], const double box_hi[3], double r2, void* scratch, int64_t* offsets,
-                                  int64_t* words_host, hipStream_t s) {
-    const int64_t ncells = (int64_t)g.dim[0] * g.dim[1] * g.dim[2];
-    const size_t tb = query_temp_bytes(m, n);
-    const query_layout Q = query_layout_for(m, n, ncells, tb);
+hipError_t f3d_launch_query_count(const void* data, int ddtype, int64_t m, const void* queries, int qdtype, int64_t n, const f3d_gridsearch& gs,
+                                  void* scratch, int64_t* offsets, int64_t* words_host, hipStream_t s) {
+    const size_t tb = temp_bytes_for(m, n);
+    const query_layout Q = query_layout_for(m, n, f3d_ncells(gs.g), tb);
     char* base = (char*)scratch;
     unsigned long long* words = (unsigned long long*)(base + Q.words);
     hipError_t e = hipMemsetAsync(words, 0, 64, s);
     if (e != hipSuccess) return e;
-    if ((e = build_grid(data, ddtype, m, g, Q.grid, tb, base, s)) != hipSuccess) return e;
-    qbox box;
-    for (int c = 0; c < 3; ++c) { box.lo[c] = box_lo[c]; box.hi[c] = box_hi[c]; }
-    const double* sorted = (const double*)(base + Q.grid.sorted);
-    const uint32_t* perm = (const uint32_t*)(base + Q.grid.perm);
-    const int2* cells = (const int2*)(base + Q.grid.cells);
+    if ((e = build_grid(data, ddtype, m, gs.g, Q.grid, tb, base, s)) != hipSuccess) return e;
+    const f3d_gridview gv = view_of(scratch, Q.grid);
     const dim3 gr(f3d_grid_for(n, GB, 8192)), b(GB);
     if (qdtype == F3D_F64)
-        hipLaunchKernelGGL((k_query_scan<double, false>), gr, b, 0, s, (const double*)queries, n, sorted, perm, g, box, cells, r2, offsets,
+        hipLaunchKernelGGL((k_query_scan<double, false>), gr, b, 0, s, (const double*)queries, n, gv.sorted, gv.perm, gv.cells, gs, offsets,
                            (int32_t*)nullptr, words, (int32_t*)nullptr);
     else
-        hipLaunchKernelGGL((k_query_scan<float, false>), gr, b, 0, s, (const float*)queries, n, sorted, perm, g, box, cells, r2, offsets,
+        hipLaunchKernelGGL((k_query_scan<float, false>), gr, b, 0, s, (const float*)queries, n, gv.sorted, gv.perm, gv.cells, gs, offsets,
                            (int32_t*)nullptr, words, (int32_t*)nullptr);
     if ((e = hipMemsetAsync(offsets + n, 0, 8, s)) != hipSuccess) return e;
     size_t t = tb;
@@ -399,27 +344,22 @@ hipError_t f3d_launch_query_count(const void* data, int ddtype, int64_t m, const
     return hipMemcpyAsync(words_host, words, 16, hipMemcpyDeviceToHost, s);     // the caller synchronises
 }
 
-hipError_t f3d_launch_query_fill(const void* queries, int qdtype, int64_t m, int64_t n, const f3d_graphgrid& g, const double box_lo[3],
-                                 const double box_hi[3], double r2, void* scratch, const int64_t* offsets, int32_t* nbrs, hipStream_t s) {
-    const int64_t ncells = (int64_t)g.dim[0] * g.dim[1] * g.dim[2];
-    const query_layout Q = query_layout_for(m, n, ncells, query_temp_bytes(m, n));
+hipError_t f3d_launch_query_fill(const void* queries, int qdtype, int64_t m, int64_t n, const f3d_gridsearch& gs, void* scratch,
+                                 const int64_t* offsets, int32_t* nbrs, hipStream_t s) {
+    const query_layout Q = query_layout_for(m, n, f3d_ncells(gs.g), temp_bytes_for(m, n));
     char* base = (char*)scratch;
     unsigned long long* words = (unsigned long long*)(base + Q.words);
     int32_t* longrows = (int32_t*)(base + Q.longrows);
     hipError_t e = hipMemsetAsync(words + 2, 0, 8, s);
     if (e != hipSuccess) return e;
-    qbox box;
-    for (int c = 0; c < 3; ++c) { box.lo[c] = box_lo[c]; box.hi[c] = box_hi[c]; }
-    const double* sorted = (const double*)(base + Q.grid.sorted);
-    const uint32_t* perm = (const uint32_t*)(base + Q.grid.perm);
-    const int2* cells = (const int2*)(base + Q.grid.cells);
+    const f3d_gridview gv = view_of(scratch, Q.grid);
     int64_t* offs = const_cast<int64_t*>(offsets);                              // (read only in the fill pass)
     const dim3 gr(f3d_grid_for(n, GB, 8192)), b(GB);
     if (qdtype == F3D_F64)
-        hipLaunchKernelGGL((k_query_scan<double, true>), gr, b, 0, s, (const double*)queries, n, sorted, perm, g, box, cells, r2, offs, nbrs,
+        hipLaunchKernelGGL((k_query_scan<double, true>), gr, b, 0, s, (const double*)queries, n, gv.sorted, gv.perm, gv.cells, gs, offs, nbrs,
                            words, longrows);
     else
-        hipLaunchKernelGGL((k_query_scan<float, true>), gr, b, 0, s, (const float*)queries, n, sorted, perm, g, box, cells, r2, offs, nbrs,
+        hipLaunchKernelGGL((k_query_scan<float, true>), gr, b, 0, s, (const float*)queries, n, gv.sorted, gv.perm, gv.cells, gs, offs, nbrs,
                            words, longrows);
     hipLaunchKernelGGL(k_query_sort_long, dim3(2048), b, 0, s, offsets, nbrs, words, longrows);
     return hipGetLastError();

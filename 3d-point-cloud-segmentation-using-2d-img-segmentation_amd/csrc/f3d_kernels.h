@@ -178,6 +178,55 @@ __device__ __forceinline__ void f3d_cell_of(const G& g, double x, double y, doub
     cz = min(g.dim[2] - 1, max(0, (int)floor((z - g.lo[2]) * g.inv_cell)));
 }
 
+// a built f3d_graphgrid (f3d_launch_graph_grid): cell-sorted float64 copy, caller-order index of every sorted point, [first, last) of every cell
+struct f3d_gridview { const double* sorted; const uint32_t* perm; const int2* cells; };
+struct f3d_box { double lo[3], hi[3]; };
+// what a radius search over a built grid needs besides the view: the grid, the cloud's box grown by one cell (a point outside it is
+// more than one cell, hence more than r, from every cloud point) and the reduced radius r * r (-1: nothing matches)
+struct f3d_gridsearch { f3d_graphgrid g; f3d_box reach; double r2; };
+inline int64_t f3d_ncells(const f3d_graphgrid& g) { return (int64_t)g.dim[0] * g.dim[1] * g.dim[2]; }
+
+// (false for NaN as well)
+__device__ __forceinline__ bool f3d_in_box(const f3d_box& b, double x, double y, double z) {
+    return x >= b.lo[0] && x <= b.hi[0] && y >= b.lo[1] && y <= b.hi[1] && z >= b.lo[2] && z <= b.hi[2];
+}
+// neither NaN nor infinite (sklearn rejects such coordinates)
+__device__ __forceinline__ bool f3d_finite(double x) { return fabs(x) <= 1.7976931348623157e308; }
+__device__ __forceinline__ bool f3d_finite(double x, double y, double z) { return f3d_finite(x) && f3d_finite(y) && f3d_finite(z); }
+
+// The radius search of the radius graph, the radius query and the point vote: hit(k) for every sorted point k of the grid with
+// |p - sorted[k]|^2 <= r2, until hit returns true (-> true: it did).  The cell edge is above r, so every match lies in the <= 27 cells around p's own;
+// they are visited dz outer, dy, dx inner, each cell's points in ascending k.  p may lie up to one cell outside the grid (f3d_in_box
+// of the reach box): f3d_cell_of clamps its cell, which never moves two points more than one cell apart, and every candidate still
+// gets the exact test.  That test is the leaf test of sklearn's KDTree, operation for operation (sklearn/metrics/_dist_metrics:
+// euclidean_rdist accumulates tmp * tmp over the 3 coordinates left to right; query_radius compares it with r * r, inclusive).
+template <typename Hit>
+__device__ __forceinline__ bool f3d_grid_walk(const f3d_gridview& gv, const f3d_graphgrid& g, double px, double py, double pz, double r2,
+                                              Hit hit) {
+    int cx, cy, cz;
+    f3d_cell_of(g, px, py, pz, cx, cy, cz);
+    bool stop = false;                                                             // (a flag, not a return: it folds away when hit is constant)
+    for (int dz = -1; dz <= 1 && !stop; ++dz) {
+        const int z = cz + dz;
+        if (z < 0 || z >= g.dim[2]) continue;
+        for (int dy = -1; dy <= 1 && !stop; ++dy) {
+            const int y = cy + dy;
+            if (y < 0 || y >= g.dim[1]) continue;
+            for (int dx = -1; dx <= 1 && !stop; ++dx) {
+                const int x = cx + dx;
+                if (x < 0 || x >= g.dim[0]) continue;
+                const int2 range = gv.cells[(z * g.dim[1] + y) * g.dim[0] + x];
+                for (int k = range.x; k < range.y; ++k) {
+                    const double t0 = px - gv.sorted[3 * (int64_t)k], t1 = py - gv.sorted[3 * (int64_t)k + 1], t2 = pz - gv.sorted[3 * (int64_t)k + 2];
+                    const double d = (t0 * t0 + t1 * t1) + t2 * t2;                // euclidean_rdist, left to right
+                    if (d <= r2 && hit(k)) { stop = true; break; }
+                }
+            }
+        }
+    }
+    return stop;
+}
+
 struct f3d_plane_args {                    // by-value kernel argument of k_inside_polyhedra
     int m;
     int accumulate;                        // 1: AND into the existing `inside` bytes (chained launches)
@@ -299,24 +348,22 @@ size_t f3d_graph_bbox_bytes(void);
 hipError_t f3d_launch_graph_bbox(const void* xyz, int dtype, int64_t n, void* partial, int* nblocks, hipStream_t s);
 int f3d_graph_reduce_bbox(const void* partial_host, int nblocks, double lo[3], double hi[3]);      // 1: non-finite coordinates seen
 size_t f3d_graph_scratch_bytes(int64_t n, int64_t ncells);
-hipError_t f3d_launch_graph_count(const void* xyz, int dtype, int64_t n, const f3d_graphgrid& g, double r2, void* scratch,
-                                  int64_t* offsets, hipStream_t s);
-hipError_t f3d_launch_graph_fill(int64_t n, const f3d_graphgrid& g, double r2, const void* scratch, const int64_t* offsets,
-                                 int32_t* nbrs, hipStream_t s);
-// the grid of the radius graph on its own: cell-sorted float64 copy, caller-order index of every sorted point, [first, last) of every cell
-struct f3d_gridview { const double* sorted; const uint32_t* perm; const int2* cells; };
+hipError_t f3d_launch_graph_count(const void* xyz, int dtype, int64_t n, const f3d_gridsearch& gs, void* scratch, int64_t* offsets,
+                                  hipStream_t s);
+hipError_t f3d_launch_graph_fill(int64_t n, const f3d_gridsearch& gs, const void* scratch, const int64_t* offsets, int32_t* nbrs,
+                                 hipStream_t s);
+// the grid of the radius graph on its own, for searches that keep no CSR
 hipError_t f3d_launch_graph_grid(const void* xyz, int dtype, int64_t n, const f3d_graphgrid& g, void* scratch, f3d_gridview* view,
                                  hipStream_t s);
 // radius query (f3d_graph.hip): KDTree(data).query_radius(queries, r) inverted, one row per query in ascending data index.  Grid over
-// the m data points (from the f3d_launch_graph_bbox partials), box_lo / box_hi = the data's box grown by one cell.  The count pass
-// enqueues the readback of words_host[0] = nnz and words_host[1] = 1 if a query is NaN / infinite (the caller synchronises); the fill
-// pass needs the same queries and the scratch (f3d_query_scratch_bytes) of the count pass
+// the m data points (from the f3d_launch_graph_bbox partials).  The count pass enqueues the readback of words_host[0] = nnz and
+// words_host[1] = 1 if a query is NaN / infinite (the caller synchronises); the fill pass needs the same queries and the scratch
+// (f3d_query_scratch_bytes) of the count pass
 size_t f3d_query_scratch_bytes(int64_t m, int64_t n, int64_t ncells);
-hipError_t f3d_launch_query_count(const void* data, int ddtype, int64_t m, const void* queries, int qdtype, int64_t n, const f3d_graphgrid& g,
-                                  const double box_lo[3], const double box_hi[3], double r2, void* scratch, int64_t* offsets,
-                                  int64_t* words_host, hipStream_t s);
-hipError_t f3d_launch_query_fill(const void* queries, int qdtype, int64_t m, int64_t n, const f3d_graphgrid& g, const double box_lo[3],
-                                 const double box_hi[3], double r2, void* scratch, const int64_t* offsets, int32_t* nbrs, hipStream_t s);
+hipError_t f3d_launch_query_count(const void* data, int ddtype, int64_t m, const void* queries, int qdtype, int64_t n, const f3d_gridsearch& gs,
+                                  void* scratch, int64_t* offsets, int64_t* words_host, hipStream_t s);
+hipError_t f3d_launch_query_fill(const void* queries, int qdtype, int64_t m, int64_t n, const f3d_gridsearch& gs, void* scratch,
+                                 const int64_t* offsets, int32_t* nbrs, hipStream_t s);
 
 // surface normals (f3d_normals.hip): F frames of n float64 points, grid chosen on the host from the f3d_launch_graph_bbox partials;
 // cams device [F, 3].  Enqueue only.  scratch: f3d_normals_scratch_bytes(F * n)
@@ -420,18 +467,16 @@ hipError_t f3d_launch_door_window_quads(const double* pts, int64_t n, const int6
 #define F3D_PVOTE_NONE 0x7f7f7f7f
 #define F3D_PVOTE_MAX_GROUP 64               // frames one vote launch covers at most
 #define F3D_PVOTE_BITS_BUDGET ((size_t)256 << 20)
-struct f3d_pvote_box { double lo[3], hi[3]; };   // the cloud's box grown by one cell
 int f3d_pvote_words_per_point(int ncols);
 int f3d_pvote_group(int64_t m, int ncols);   // frames per vote launch: the bitsets of a group fit the budget (at least 1 frame)
 size_t f3d_pvote_bits_bytes(int64_t m, int ncols, int group);
 hipError_t f3d_launch_pvote_prepass(const void* queries, int qdtype, const uint8_t* masks, int64_t nframes, int64_t hw, int ncols, int* words,
                                     hipStream_t s);
 hipError_t f3d_launch_pvote_validate(const void* queries, int qdtype, const uint8_t* masks, int64_t nframes, int64_t hw, int ncols,
-                                     const f3d_gridview& gv, const f3d_graphgrid& g, const f3d_pvote_box& box, double r2, int* words,
-                                     hipStream_t s);
+                                     const f3d_gridview& gv, const f3d_gridsearch& gs, int* words, hipStream_t s);
 hipError_t f3d_launch_pvote_frames(const void* queries, int qdtype, const uint8_t* masks, int64_t nframes, int64_t hw, int64_t m, int ncols,
-                                   const f3d_gridview& gv, const f3d_graphgrid& g, const f3d_pvote_box& box, double r2, double* votes,
-                                   uint32_t* bits, int group, const int* words, const int* err, hipStream_t s);
+                                   const f3d_gridview& gv, const f3d_gridsearch& gs, double* votes, uint32_t* bits, int group,
+                                   const int* words, const int* err, hipStream_t s);
 hipError_t f3d_launch_pvote_flag(const int* words, int limit, int* err, hipStream_t s);
 
 // meshUtils (f3d_mesh.hip): triangles [nt, 3] of `itype` (F3D_I64 / F3D_I32), vertices [nv, 3] of `vdtype`.  counts: device int64[4] =

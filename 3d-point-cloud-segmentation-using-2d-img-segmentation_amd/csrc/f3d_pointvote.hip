@@ -11,8 +11,7 @@
 //                      coordinate (sklearn raises ValueError there)
 //   k_pvote<.., true>: only when such a label exists: the first frame in which a pixel carrying one HAS a neighbour (NumPy raises
 //                      IndexError there; np.repeat drops the labels of pixels that found nothing)
-//   k_pvote<.., false>: the vote.  One thread per pixel walks the <= 27 cells around it in the cloud's grid (build_grid of
-//                      f3d_graph.hip; the walk, the box early-exit and the exact float64 test are those of k_query_scan) and feeds
+//   k_pvote<.., false>: the vote.  One thread per pixel searches the cloud's grid (f3d_launch_graph_grid, f3d_grid_walk) and feeds
 //                      every hit into the frame's set of (point, label) keys.
 // The set is a bitset per (frame of the group, point): bit 0 = "a pixel of the frame saw the point", bit 1 + l = label l.  A hit
 // first reads its word (an L2 load; most hits are duplicates and end here), else one atomicOr sets the missing bits and its return
@@ -27,7 +26,6 @@
 namespace {
 
 constexpr int PB = 256;
-constexpr double DBL_MAX_ = 1.7976931348623157e308;
 
 template <typename T>
 __global__ __launch_bounds__(PB) void k_pvote_prepass(const T* __restrict__ q, const uint8_t* __restrict__ masks, int64_t total, int64_t hw,
@@ -36,8 +34,7 @@ __global__ __launch_bounds__(PB) void k_pvote_prepass(const T* __restrict__ q, c
     int bad = F3D_PVOTE_NONE;
     for (int64_t i = (int64_t)blockIdx.x * PB + threadIdx.x; i < total; i += (int64_t)gridDim.x * PB) {
         label |= (int)masks[i] >= ncols;
-        const double x = (double)q[3 * i], y = (double)q[3 * i + 1], z = (double)q[3 * i + 2];
-        if (!(fabs(x) <= DBL_MAX_ && fabs(y) <= DBL_MAX_ && fabs(z) <= DBL_MAX_)) { const int f = (int)(i / hw); bad = f < bad ? f : bad; }
+        if (!f3d_finite((double)q[3 * i], (double)q[3 * i + 1], (double)q[3 * i + 2])) { const int f = (int)(i / hw); bad = f < bad ? f : bad; }
     }
     if (label) atomicOr(&words[0], 1);
     if (bad != F3D_PVOTE_NONE) atomicMin(&words[1], bad);
@@ -49,13 +46,14 @@ __global__ __launch_bounds__(PB) void k_pvote_prepass(const T* __restrict__ q, c
 template <typename T, bool VALIDATE>
 __global__ __launch_bounds__(PB) void k_pvote(const T* __restrict__ q, const uint8_t* __restrict__ masks, int64_t total, int64_t hw, int frame0,
                                                int64_t m, int ncols, int wpp, const double* __restrict__ sorted,
-                                               const uint32_t* __restrict__ perm, f3d_graphgrid g, f3d_pvote_box box,
-                                               const int2* __restrict__ cells, double r2, double* __restrict__ votes,
-                                               uint32_t* __restrict__ bits, int* __restrict__ words, const int* __restrict__ err) {
+                                               const uint32_t* __restrict__ perm, const int2* __restrict__ cells, f3d_gridsearch gs,
+                                               double* __restrict__ votes, uint32_t* __restrict__ bits, int* __restrict__ words,
+                                               const int* __restrict__ err) {
     // an earlier, untaken IndexError of this operation: nothing is written any more.  (The bit is set between launches only, by
     // k_pvote_flag: see the note in k_vote_uv2pt_batch.)
     if (!VALIDATE && (*err & F3D_DEVERR_PVOTE)) return;
     const int fb = VALIDATE ? F3D_PVOTE_NONE : words[2];
+    const f3d_gridview gv = {sorted, perm, cells};
     for (int64_t i = (int64_t)blockIdx.x * PB + threadIdx.x; i < total; i += (int64_t)gridDim.x * PB) {
         const int f = (int)(i / hw);
         const int label = masks[i];
@@ -67,49 +65,30 @@ __global__ __launch_bounds__(PB) void k_pvote(const T* __restrict__ q, const uin
             if (label >= ncols) continue;                                      // (validated: such a pixel has no neighbour)
         }
         const double px = (double)q[3 * i], py = (double)q[3 * i + 1], pz = (double)q[3 * i + 2];
-        // (false for NaN as well)
-        if (!(px >= box.lo[0] && px <= box.hi[0] && py >= box.lo[1] && py <= box.hi[1] && pz >= box.lo[2] && pz <= box.hi[2])) continue;
+        if (!f3d_in_box(gs.reach, px, py, pz)) continue;
         uint32_t* fbits = VALIDATE ? nullptr : bits + (size_t)f * (size_t)m * wpp;
         const int lbit = label + 1;                                            // bit 0 of a point's first word: seen by this frame
         const uint32_t first = 1u | (lbit < 32 ? 1u << lbit : 0u);
-        int cx, cy, cz;
-        f3d_cell_of(g, px, py, pz, cx, cy, cz);
-        bool found = false;
-        for (int dz = -1; dz <= 1 && !found; ++dz) {
-            const int z = cz + dz;
-            if (z < 0 || z >= g.dim[2]) continue;
-            for (int dy = -1; dy <= 1 && !found; ++dy) {
-                const int y = cy + dy;
-                if (y < 0 || y >= g.dim[1]) continue;
-                for (int dx = -1; dx <= 1 && !found; ++dx) {
-                    const int x = cx + dx;
-                    if (x < 0 || x >= g.dim[0]) continue;
-                    const int2 range = cells[(z * g.dim[1] + y) * g.dim[0] + x];
-                    for (int k = range.x; k < range.y; ++k) {
-                        const double t0 = px - sorted[3 * (int64_t)k], t1 = py - sorted[3 * (int64_t)k + 1], t2 = pz - sorted[3 * (int64_t)k + 2];
-                        const double d = (t0 * t0 + t1 * t1) + t2 * t2;            // euclidean_rdist, left to right
-                        if (!(d <= r2)) continue;
-                        if (VALIDATE) { found = true; break; }
-                        const size_t j = perm[k];
-                        uint32_t* pw = fbits + j * wpp;
-                        double* row = votes + j * (size_t)ncols;
-                        const uint32_t have = __hip_atomic_load(pw, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                        const uint32_t want = first & ~have;
-                        if (want) {
-                            const uint32_t made = want & ~atomicOr(pw, want);
-                            if (made & 1u) atomicAdd(row + (ncols - 1), 1.0);          // votes[nns, -1] += 1
-                            if (made & ~1u) atomicAdd(row + label, 1.0);               // votes[nns, label] += 1
-                        }
-                        if (lbit >= 32) {
-                            uint32_t* lw = pw + (lbit >> 5);
-                            const uint32_t b = 1u << (lbit & 31);
-                            if (!(__hip_atomic_load(lw, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) & b) && !(atomicOr(lw, b) & b))
-                                atomicAdd(row + label, 1.0);
-                        }
-                    }
-                }
+        const bool found = f3d_grid_walk(gv, gs.g, px, py, pz, gs.r2, [&](int k) {
+            if (VALIDATE) return true;
+            const size_t j = perm[k];
+            uint32_t* pw = fbits + j * wpp;
+            double* row = votes + j * (size_t)ncols;
+            const uint32_t have = __hip_atomic_load(pw, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            const uint32_t want = first & ~have;
+            if (want) {
+                const uint32_t made = want & ~atomicOr(pw, want);
+                if (made & 1u) atomicAdd(row + (ncols - 1), 1.0);                  // votes[nns, -1] += 1
+                if (made & ~1u) atomicAdd(row + label, 1.0);                       // votes[nns, label] += 1
             }
-        }
+            if (lbit >= 32) {
+                uint32_t* lw = pw + (lbit >> 5);
+                const uint32_t b = 1u << (lbit & 31);
+                if (!(__hip_atomic_load(lw, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) & b) && !(atomicOr(lw, b) & b))
+                    atomicAdd(row + label, 1.0);
+            }
+            return false;
+        });
         if (VALIDATE && found) atomicMin(&words[2], frame0 + f);
     }
 }
@@ -146,23 +125,22 @@ hipError_t f3d_launch_pvote_prepass(const void* queries, int qdtype, const uint8
 }
 
 hipError_t f3d_launch_pvote_validate(const void* queries, int qdtype, const uint8_t* masks, int64_t nframes, int64_t hw, int ncols,
-                                     const f3d_gridview& gv, const f3d_graphgrid& g, const f3d_pvote_box& box, double r2, int* words,
-                                     hipStream_t s) {
+                                     const f3d_gridview& gv, const f3d_gridsearch& gs, int* words, hipStream_t s) {
     const int64_t total = nframes * hw;
     if (total <= 0) return hipSuccess;
     const dim3 gr(f3d_grid_for(total, PB, 1 << 20)), b(PB);
     if (qdtype == F3D_F64)
         hipLaunchKernelGGL((k_pvote<double, true>), gr, b, 0, s, (const double*)queries, masks, total, hw, 0, (int64_t)0, ncols, 0, gv.sorted, gv.perm,
-                           g, box, gv.cells, r2, (double*)nullptr, (uint32_t*)nullptr, words, (const int*)nullptr);
+                           gv.cells, gs, (double*)nullptr, (uint32_t*)nullptr, words, (const int*)nullptr);
     else
         hipLaunchKernelGGL((k_pvote<float, true>), gr, b, 0, s, (const float*)queries, masks, total, hw, 0, (int64_t)0, ncols, 0, gv.sorted, gv.perm,
-                           g, box, gv.cells, r2, (double*)nullptr, (uint32_t*)nullptr, words, (const int*)nullptr);
+                           gv.cells, gs, (double*)nullptr, (uint32_t*)nullptr, words, (const int*)nullptr);
     return hipGetLastError();
 }
 
 hipError_t f3d_launch_pvote_frames(const void* queries, int qdtype, const uint8_t* masks, int64_t nframes, int64_t hw, int64_t m, int ncols,
-                                   const f3d_gridview& gv, const f3d_graphgrid& g, const f3d_pvote_box& box, double r2, double* votes,
-                                   uint32_t* bits, int group, const int* words, const int* err, hipStream_t s) {
+                                   const f3d_gridview& gv, const f3d_gridsearch& gs, double* votes, uint32_t* bits, int group,
+                                   const int* words, const int* err, hipStream_t s) {
     const int wpp = f3d_pvote_words_per_point(ncols);
     const size_t qstride = (size_t)hw * 3 * (qdtype == F3D_F64 ? 8 : 4);
     for (int64_t f0 = 0; f0 < nframes; f0 += group) {
@@ -174,11 +152,11 @@ hipError_t f3d_launch_pvote_frames(const void* queries, int qdtype, const uint8_
         const char* qp = (const char*)queries + (size_t)f0 * qstride;
         const uint8_t* mp = masks + (size_t)f0 * hw;
         if (qdtype == F3D_F64)
-            hipLaunchKernelGGL((k_pvote<double, false>), gr, b, 0, s, (const double*)qp, mp, total, hw, (int)f0, m, ncols, wpp, gv.sorted, gv.perm, g, box,
-                               gv.cells, r2, votes, bits, const_cast<int*>(words), err);
+            hipLaunchKernelGGL((k_pvote<double, false>), gr, b, 0, s, (const double*)qp, mp, total, hw, (int)f0, m, ncols, wpp, gv.sorted, gv.perm, gv.cells,
+                               gs, votes, bits, const_cast<int*>(words), err);
         else
-            hipLaunchKernelGGL((k_pvote<float, false>), gr, b, 0, s, (const float*)qp, mp, total, hw, (int)f0, m, ncols, wpp, gv.sorted, gv.perm, g, box,
-                               gv.cells, r2, votes, bits, const_cast<int*>(words), err);
+            hipLaunchKernelGGL((k_pvote<float, false>), gr, b, 0, s, (const float*)qp, mp, total, hw, (int)f0, m, ncols, wpp, gv.sorted, gv.perm, gv.cells,
+                               gs, votes, bits, const_cast<int*>(words), err);
     }
     return hipGetLastError();
 }

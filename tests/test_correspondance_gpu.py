@@ -1,6 +1,7 @@
 """segUtils.correspondance on the GPU: the radius query (f3d_radius_query_*) against the reference's golden and against sklearn's
 KDTree inverted by a stable sort, rows compared in order; host entries against _dev entries; the count -> other call -> fill
-interleaving; the device-resident path from depth frames to PointCorrespondance on tensors."""
+interleaving; the device-resident path from depth frames to PointCorrespondance on tensors; degenerate clouds through all three
+callers of the shared grid walk (radius graph, radius query, point vote)."""
 import ctypes as C
 
 import numpy as np
@@ -121,6 +122,39 @@ def test_queries_far_outside_the_cloud_and_radius_edges():
         ctx.radius_query(np.zeros((0, 3)), dense, 0.1)
     offs, nb = ctx.radius_query(sparse, np.zeros((0, 3)), 0.1)
     assert list(offs) == [0] and len(nb) == 0
+
+
+def _degenerate_clouds():
+    rng = np.random.default_rng(14)
+    flat = np.concatenate([rng.uniform(0, 100, (4000, 2)), np.zeros((4000, 1))], axis=1)
+    lattice = np.stack(np.meshgrid(np.arange(9.0), np.arange(7.0), np.arange(5.0), indexing='ij'), -1).reshape(-1, 3)
+    return {'one_point': (np.array([[0.25, -1.5, 3.0]]), 0.1),
+            'identical_points': (np.tile([[0.5, -0.25, 2.0]], (70, 1)), 0.05),                # a 1 x 1 x 1 grid
+            'flat': (flat, 2.5),                                                               # one axis has dim 1
+            'lattice_r1': (lattice, 1.0),                                                      # ties exactly on r * r, points on
+            'lattice_sqrt2': (lattice, float(np.sqrt(2.0))),                                   # the upper faces of the box
+            'offset': (rng.uniform(0, 1, (3000, 3)) + [1e6, -2e6, 3e5], 0.08)}
+
+
+@pytest.mark.parametrize('name', list(_degenerate_clouds()))
+def test_degenerate_clouds_through_graph_query_and_vote(name):
+    P, r = _degenerate_clouds()[name]
+    n, ncols = len(P), 6
+    ctx = f3d.default_context()
+    want = [np.sort(row) for row in KDTree(P).query_radius(P, r)]
+    want_offs = np.concatenate([[0], np.cumsum([len(row) for row in want])])
+    goffs, gnb = ctx.radius_graph(P, r)
+    qoffs, qnb = ctx.radius_query(P, P, r)
+    assert np.array_equal(goffs, qoffs) and np.array_equal(qoffs, want_offs)
+    graph_rows = np.concatenate([np.sort(gnb[goffs[i]:goffs[i + 1]]) for i in range(n)])
+    assert np.array_equal(graph_rows, qnb) and np.array_equal(qnb, np.concatenate(want))
+    labels = (np.arange(n) % 5).astype(np.uint8)
+    expect = np.zeros((n, ncols))
+    for j, row in enumerate(want):                                      # row j: the pixels within r of point j (the relation is symmetric)
+        expect[j, labels[row]] = 1
+    expect[:, -1] = 1                                                   # every point is its own neighbour
+    votes = ctx.point_vote_frames(np.zeros((n, ncols)), P, P[None], labels[None], r)
+    assert np.array_equal(votes, expect)
 
 
 def test_host_entries_equal_dev_entries():
