@@ -27,7 +27,8 @@ enum { SLOT_XYZ = 0, SLOT_OUT0, SLOT_OUT1, SLOT_VIEWS, SLOT_MASKS, SLOT_AUX0, SL
        SLOT_GRP_ORDER, SLOT_GRP_KEYS, SLOT_GRP_STARTS, SLOT_GRP_SCRATCH, SLOT_OBB_TABLE, SLOT_OBB_FACETS, SLOT_OBB_CAND, SLOT_FUSE_TABLES, SLOT_FUSE_CARRY, SLOT_FUSE_XYZ, SLOT_FUSION, SLOT_PATCH_STATUS, SLOT_NRM, SLOT_NRM_CAMS,
        SLOT_QRY, SLOT_QRY_IN, SLOT_QRY_OFFS,
        SLOT_FLOOD, SLOT_COLOR, SLOT_CVS_INST, SLOT_CVS_ORDER, SLOT_CVS_COFFS, SLOT_CVS_FLAGS, SLOT_CVS_SEEDS, SLOT_CVS_STATS,
-       SLOT_QUADS, SLOT_QUADS_OUT, SLOT_GROW, SLOT_PVOTE, SLOT_PVOTE_BITS, SLOT_MESH, SLOT_MESH_IO, SLOT_ZKEY, SLOT_ZCOUNTS, SLOT_COUNT };
+       SLOT_QUADS, SLOT_QUADS_OUT, SLOT_GROW, SLOT_PVOTE, SLOT_PVOTE_BITS, SLOT_MESH, SLOT_MESH_IO, SLOT_ZKEY, SLOT_ZCOUNTS,
+       SLOT_KNN, SLOT_KNN_FLAG, SLOT_COUNT };
 
 thread_local char g_create_err[512] = "";
 
@@ -2037,6 +2038,109 @@ int f3d_radius_query_fill(f3d_ctx* ctx, int64_t n, int32_t* nbrs) {
     staging st(ctx);
     int32_t* dnb = st.out(SLOT_MASKS, nbrs, (size_t)nnz * 4);
     if (!st.rc) st.rc = f3d_radius_query_fill_dev(ctx, ctx->qry_queries, (f3d_dtype)ctx->qry_qdtype, n, doffs, dnb, s);
+    return st.finish();
+}
+
+// ---------------------------------------------------------------------------------------------
+// hybrid k-nearest search and label transfer (no reference counterpart; contract in f3d.h)
+// ---------------------------------------------------------------------------------------------
+int f3d_ctx_reserve_knn(f3d_ctx* ctx, int64_t m) {
+    int rc = enter(ctx); if (rc) return rc;
+    if (m < 0 || m > 0x7fffffffLL) return fail(ctx, F3D_ERR_INVALID, "ctx_reserve_knn: bad arguments");
+    const int strict = ctx->strict;
+    ctx->strict = 0;
+    void* p;
+    rc = ensure(ctx, SLOT_GRAPH_BBOX, f3d_graph_bbox_bytes(), &p);
+    if (!rc) rc = ensure(ctx, SLOT_KNN_FLAG, 64, &p);
+    if (!rc) rc = ensure(ctx, SLOT_KNN, f3d_graph_scratch_bytes(m, GRID_MAX_CELLS), &p);            // (any grid the radius allows)
+    ctx->strict = strict;
+    return rc;
+}
+
+// What f3d_knn_query_dev and f3d_transfer_labels_dev share: the argument checks, the one readback (the cloud's box and the queries'
+// non-finite flag together) and the data's grid, built in SLOT_KNN.  *run = false: nothing to launch (n == 0).
+static int knn_prepare(f3d_ctx* ctx, const char* op, const void* data, f3d_dtype ddtype, int64_t m, const void* queries, f3d_dtype qdtype,
+                       int64_t n, int k, double radius, hipStream_t s, f3d_gridsearch* gs, f3d_gridview* gv, bool* run) {
+    *run = false;
+    if (k < 1 || k > F3D_KNN_MAX_K) return fail(ctx, F3D_ERR_INVALID, "%s: k %d outside [1, %d]", op, k, F3D_KNN_MAX_K);
+    if (m < 0 || m > 0x7fffffffLL || n < 0 || n > 0x7fffffffLL || (m > 0 && !data) || (n > 0 && !queries) ||
+        (ddtype != F3D_F64 && ddtype != F3D_F32) || (qdtype != F3D_F64 && qdtype != F3D_F32) || radius >= 1e300)
+        return fail(ctx, F3D_ERR_INVALID, "%s: bad arguments (m, n < 2^31, radius < 1e300)", op);
+    if (m == 0) return fail(ctx, F3D_ERR_INVALID, "%s: the data set is empty", op);
+    if (n == 0) return F3D_OK;
+    void *dbox, *dflag;
+    int rc = ensure(ctx, SLOT_GRAPH_BBOX, f3d_graph_bbox_bytes(), &dbox); if (rc) return rc;
+    if ((rc = ensure(ctx, SLOT_KNN_FLAG, 64, &dflag))) return rc;
+    unsigned flag = 0;
+    F3D_HIP(ctx, hipMemsetAsync(dflag, 0, 4, s));
+    F3D_HIP(ctx, f3d_launch_knn_flag(queries, qdtype, n, (unsigned*)dflag, s));
+    F3D_HIP(ctx, hipMemcpyAsync(&flag, dflag, 4, hipMemcpyDeviceToHost, s));
+    if ((rc = cloud_search(ctx, data, ddtype, m, radius, s, op, gs))) return rc;                    // (synchronises)
+    if (flag) return fail(ctx, F3D_ERR_INVALID, "%s: the queries contain NaN or infinity", op);
+    void* scratch;
+    if ((rc = ensure(ctx, SLOT_KNN, f3d_graph_scratch_bytes(m, f3d_ncells(gs->g)), &scratch))) return rc;
+    F3D_HIP(ctx, f3d_launch_graph_grid(data, ddtype, m, gs->g, scratch, gv, s));
+    *run = true;
+    return F3D_OK;
+}
+
+int f3d_knn_query_dev(f3d_ctx* ctx, const void* data, f3d_dtype ddtype, int64_t m, const void* queries, f3d_dtype qdtype, int64_t n, int k,
+                      double radius, int32_t* idx, double* dist2, int32_t* counts, void* stream) {
+    int rc = enter(ctx); if (rc) return rc;
+    if (n > 0 && !idx) return fail(ctx, F3D_ERR_INVALID, "knn_query: idx is NULL");
+    hipStream_t s = pick(ctx, stream);
+    f3d_gridsearch gs;
+    f3d_gridview gv;
+    bool run;
+    if ((rc = knn_prepare(ctx, "knn_query", data, ddtype, m, queries, qdtype, n, k, radius, s, &gs, &gv, &run)) || !run) return rc;
+    F3D_HIP(ctx, f3d_launch_knn_query(queries, qdtype, n, k, gv, gs, idx, dist2, counts, s));
+    return F3D_OK;
+}
+
+int f3d_transfer_labels_dev(f3d_ctx* ctx, const void* data, f3d_dtype ddtype, int64_t m, const int64_t* labels, const void* queries,
+                            f3d_dtype qdtype, int64_t n, int k, double radius, int64_t fill, int64_t* out, int32_t* support, void* stream) {
+    int rc = enter(ctx); if (rc) return rc;
+    if ((n > 0 && !out) || (m > 0 && !labels)) return fail(ctx, F3D_ERR_INVALID, "transfer_labels: labels or out is NULL");
+    hipStream_t s = pick(ctx, stream);
+    f3d_gridsearch gs;
+    f3d_gridview gv;
+    bool run;
+    if ((rc = knn_prepare(ctx, "transfer_labels", data, ddtype, m, queries, qdtype, n, k, radius, s, &gs, &gv, &run)) || !run) return rc;
+    F3D_HIP(ctx, f3d_launch_knn_labels(queries, qdtype, n, k, gv, gs, labels, fill, out, support, s));
+    return F3D_OK;
+}
+
+int f3d_knn_query(f3d_ctx* ctx, const void* data, f3d_dtype ddtype, int64_t m, const void* queries, f3d_dtype qdtype, int64_t n, int k,
+                  double radius, int32_t* idx, double* dist2, int32_t* counts) {
+    int rc = enter(ctx); if (rc) return rc;
+    if (k < 1 || k > F3D_KNN_MAX_K) return fail(ctx, F3D_ERR_INVALID, "knn_query: k %d outside [1, %d]", k, F3D_KNN_MAX_K);
+    if (m < 0 || n < 0 || (m > 0 && !data) || (n > 0 && (!queries || !idx)) || (ddtype != F3D_F64 && ddtype != F3D_F32) ||
+        (qdtype != F3D_F64 && qdtype != F3D_F32))
+        return fail(ctx, F3D_ERR_INVALID, "knn_query: bad arguments");
+    staging st(ctx);
+    const void* ddata = st.in(SLOT_XYZ, data, xyz_bytes(ddtype, m));
+    const void* dq = st.in(SLOT_AUX0, queries, xyz_bytes(qdtype, n));
+    int32_t* didx = st.out(SLOT_OUT0, idx, (size_t)n * k * 4);
+    double* dd2 = st.out(SLOT_MASKS, dist2, (size_t)n * k * 8);       // (not SLOT_OUT1: f3d_radius_graph_count leaves its offsets there)
+    int32_t* dcnt = st.out(SLOT_AUX1, counts, (size_t)n * 4);
+    if (!st.rc) st.rc = f3d_knn_query_dev(ctx, ddata, ddtype, m, dq, qdtype, n, k, radius, didx, dd2, dcnt, ctx->stream);
+    return st.finish();
+}
+
+int f3d_transfer_labels(f3d_ctx* ctx, const void* data, f3d_dtype ddtype, int64_t m, const int64_t* labels, const void* queries,
+                        f3d_dtype qdtype, int64_t n, int k, double radius, int64_t fill, int64_t* out, int32_t* support) {
+    int rc = enter(ctx); if (rc) return rc;
+    if (k < 1 || k > F3D_KNN_MAX_K) return fail(ctx, F3D_ERR_INVALID, "transfer_labels: k %d outside [1, %d]", k, F3D_KNN_MAX_K);
+    if (m < 0 || n < 0 || (m > 0 && (!data || !labels)) || (n > 0 && (!queries || !out)) || (ddtype != F3D_F64 && ddtype != F3D_F32) ||
+        (qdtype != F3D_F64 && qdtype != F3D_F32))
+        return fail(ctx, F3D_ERR_INVALID, "transfer_labels: bad arguments");
+    staging st(ctx);
+    const void* ddata = st.in(SLOT_XYZ, data, xyz_bytes(ddtype, m));
+    const void* dq = st.in(SLOT_AUX0, queries, xyz_bytes(qdtype, n));
+    const int64_t* dlab = st.in(SLOT_AUX1, labels, (size_t)m * 8);
+    int64_t* dout = st.out(SLOT_OUT0, out, (size_t)n * 8);
+    int32_t* dsup = st.out(SLOT_MASKS, support, (size_t)n * 4);
+    if (!st.rc) st.rc = f3d_transfer_labels_dev(ctx, ddata, ddtype, m, dlab, dq, qdtype, n, k, radius, fill, dout, dsup, ctx->stream);
     return st.finish();
 }
 

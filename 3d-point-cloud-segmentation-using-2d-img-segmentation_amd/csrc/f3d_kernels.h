@@ -194,15 +194,15 @@ __device__ __forceinline__ bool f3d_in_box(const f3d_box& b, double x, double y,
 __device__ __forceinline__ bool f3d_finite(double x) { return fabs(x) <= 1.7976931348623157e308; }
 __device__ __forceinline__ bool f3d_finite(double x, double y, double z) { return f3d_finite(x) && f3d_finite(y) && f3d_finite(z); }
 
-// The radius search of the radius graph, the radius query and the point vote: hit(k) for every sorted point k of the grid with
-// |p - sorted[k]|^2 <= r2, until hit returns true (-> true: it did).  The cell edge is above r, so every match lies in the <= 27 cells around p's own;
+// The radius search of the radius graph, the radius query, the point vote and the k-nearest search: hit(k, d) for every sorted point k
+// of the grid with d = |p - sorted[k]|^2 <= r2, until hit returns true (-> true: it did).  The cell edge is above r, so every match lies in the <= 27 cells around p's own;
 // they are visited dz outer, dy, dx inner, each cell's points in ascending k.  p may lie up to one cell outside the grid (f3d_in_box
 // of the reach box): f3d_cell_of clamps its cell, which never moves two points more than one cell apart, and every candidate still
 // gets the exact test.  That test is the leaf test of sklearn's KDTree, operation for operation (sklearn/metrics/_dist_metrics:
 // euclidean_rdist accumulates tmp * tmp over the 3 coordinates left to right; query_radius compares it with r * r, inclusive).
 template <typename Hit>
-__device__ __forceinline__ bool f3d_grid_walk(const f3d_gridview& gv, const f3d_graphgrid& g, double px, double py, double pz, double r2,
-                                              Hit hit) {
+__device__ __forceinline__ bool f3d_grid_walk_d2(const f3d_gridview& gv, const f3d_graphgrid& g, double px, double py, double pz, double r2,
+                                                 Hit hit) {
     int cx, cy, cz;
     f3d_cell_of(g, px, py, pz, cx, cy, cz);
     bool stop = false;                                                             // (a flag, not a return: it folds away when hit is constant)
@@ -219,13 +219,44 @@ __device__ __forceinline__ bool f3d_grid_walk(const f3d_gridview& gv, const f3d_
                 for (int k = range.x; k < range.y; ++k) {
                     const double t0 = px - gv.sorted[3 * (int64_t)k], t1 = py - gv.sorted[3 * (int64_t)k + 1], t2 = pz - gv.sorted[3 * (int64_t)k + 2];
                     const double d = (t0 * t0 + t1 * t1) + t2 * t2;                // euclidean_rdist, left to right
-                    if (d <= r2 && hit(k)) { stop = true; break; }
+                    if (d <= r2 && hit(k, d)) { stop = true; break; }
                 }
             }
         }
     }
     return stop;
 }
+
+// the same search for callers that need the position only: hit(k)
+template <typename Hit>
+__device__ __forceinline__ bool f3d_grid_walk(const f3d_gridview& gv, const f3d_graphgrid& g, double px, double py, double pz, double r2,
+                                              Hit hit) {
+    return f3d_grid_walk_d2(gv, g, px, py, pz, r2, [&](int k, double) { return hit(k); });
+}
+
+// the K smallest (d2, j) seen so far, ascending; empty slots are (+inf, INT_MAX)
+template <int K>
+struct topk {
+    double d[K];
+    int j[K];
+    __device__ __forceinline__ void init() {
+#pragma unroll
+        for (int s = 0; s < K; ++s) { d[s] = INFINITY; j[s] = 0x7fffffff; }
+    }
+    __device__ __forceinline__ static bool less(double da, int ja, double db, int jb) { return da < db || (da == db && ja < jb); }
+    __device__ __forceinline__ void insert(double dn, int jn) {
+        if (!less(dn, jn, d[K - 1], j[K - 1])) return;
+        d[K - 1] = dn; j[K - 1] = jn;                        // replaces the worst, then sinks to its place
+#pragma unroll
+        for (int s = K - 1; s >= 1; --s) {
+            const bool sw = less(d[s], j[s], d[s - 1], j[s - 1]);
+            const double da = d[s - 1], db = d[s];
+            const int ja = j[s - 1], jb = j[s];
+            d[s - 1] = sw ? db : da; d[s] = sw ? da : db;
+            j[s - 1] = sw ? jb : ja; j[s] = sw ? ja : jb;
+        }
+    }
+};
 
 struct f3d_plane_args {                    // by-value kernel argument of k_inside_polyhedra
     int m;
@@ -364,6 +395,15 @@ hipError_t f3d_launch_query_count(const void* data, int ddtype, int64_t m, const
                                   void* scratch, int64_t* offsets, int64_t* words_host, hipStream_t s);
 hipError_t f3d_launch_query_fill(const void* queries, int qdtype, int64_t m, int64_t n, const f3d_gridsearch& gs, void* scratch,
                                  const int64_t* offsets, int32_t* nbrs, hipStream_t s);
+// hybrid k-nearest search and label transfer (f3d_knn.hip): per query the <= k data points within the radius that are smallest under
+// (d2, caller-order data index), over a grid built by f3d_launch_graph_grid.  K_MAX bounds k; flag: device word, bit 0 raised by
+// f3d_launch_knn_flag when a query is NaN / infinite (cleared by the caller).  Enqueue only; every offset is 64-bit.
+#define F3D_KNN_MAX_K 32
+hipError_t f3d_launch_knn_flag(const void* queries, int qdtype, int64_t n, unsigned* flag, hipStream_t s);
+hipError_t f3d_launch_knn_query(const void* queries, int qdtype, int64_t n, int k, const f3d_gridview& gv, const f3d_gridsearch& gs,
+                                int32_t* idx, double* dist2 /* may be NULL */, int32_t* counts /* may be NULL */, hipStream_t s);
+hipError_t f3d_launch_knn_labels(const void* queries, int qdtype, int64_t n, int k, const f3d_gridview& gv, const f3d_gridsearch& gs,
+                                 const int64_t* labels, int64_t fill, int64_t* out, int32_t* support /* may be NULL */, hipStream_t s);
 
 // surface normals (f3d_normals.hip): F frames of n float64 points, grid chosen on the host from the f3d_launch_graph_bbox partials;
 // cams device [F, 3].  Enqueue only.  scratch: f3d_normals_scratch_bytes(F * n)

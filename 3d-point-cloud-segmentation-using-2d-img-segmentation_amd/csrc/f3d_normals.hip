@@ -58,30 +58,7 @@ __device__ __forceinline__ int64_t lower_bound(const uint64_t* __restrict__ keys
     return a;
 }
 
-// the K smallest (d2, j) seen so far, ascending; empty slots are (+inf, INT_MAX)
-template <int K>
-struct topk {
-    double d[K];
-    int j[K];
-    __device__ __forceinline__ void init() {
-#pragma unroll
-        for (int s = 0; s < K; ++s) { d[s] = INFINITY; j[s] = 0x7fffffff; }
-    }
-    __device__ __forceinline__ static bool less(double da, int ja, double db, int jb) { return da < db || (da == db && ja < jb); }
-    __device__ __forceinline__ void insert(double dn, int jn) {
-        if (!less(dn, jn, d[K - 1], j[K - 1])) return;
-        d[K - 1] = dn; j[K - 1] = jn;                        // replaces the worst, then sinks to its place
-#pragma unroll
-        for (int s = K - 1; s >= 1; --s) {
-            const bool sw = less(d[s], j[s], d[s - 1], j[s - 1]);
-            const double da = d[s - 1], db = d[s];
-            const int ja = j[s - 1], jb = j[s];
-            d[s - 1] = sw ? db : da; d[s] = sw ? da : db;
-            j[s - 1] = sw ? jb : ja; j[s] = sw ? ja : jb;
-        }
-    }
-};
-
+// selection: topk<K> (f3d_kernels.h)
 template <int K>
 __global__ __launch_bounds__(NB) void k_nrm_query(const double* __restrict__ xyz, const double* __restrict__ sorted,
                                                    const uint64_t* __restrict__ skeys, const uint32_t* __restrict__ perm, int64_t n,

@@ -32,6 +32,7 @@ NORMALS_MAX_NN = 64          # F3D_NORMALS_MAX_NN: the largest max_nn of estimat
 QUAD_OK, QUAD_HORIZONTAL, QUAD_NO_CANDIDATE = 0, 1, 2   # per-instance status of door_window_quads (f3d.h F3D_QUAD_*)
 QUADS_MAX_INST = 65535       # F3D_QUADS_MAX_INST
 I64, I32 = 0, 1              # f3d_itype: the index type of mesh triangles
+KNN_MAX_K = 32               # F3D_KNN_MAX_K: the largest k of knn_query / transfer_labels
 
 
 class F3DError(RuntimeError):
@@ -193,6 +194,11 @@ def library():
         'f3d_radius_query_fill': (i32, [vp, i64, vp]),
         'f3d_radius_query_count_dev': (i32, [vp, vp, i32, i64, vp, i32, i64, dbl, vp, vp, vp]),
         'f3d_radius_query_fill_dev': (i32, [vp, vp, i32, i64, vp, vp, vp]),
+        'f3d_knn_query': (i32, [vp, vp, i32, i64, vp, i32, i64, i32, dbl, vp, vp, vp]),
+        'f3d_knn_query_dev': (i32, [vp, vp, i32, i64, vp, i32, i64, i32, dbl, vp, vp, vp, vp]),
+        'f3d_transfer_labels': (i32, [vp, vp, i32, i64, vp, vp, i32, i64, i32, dbl, i64, vp, vp]),
+        'f3d_transfer_labels_dev': (i32, [vp, vp, i32, i64, vp, vp, i32, i64, i32, dbl, i64, vp, vp, vp]),
+        'f3d_ctx_reserve_knn': (i32, [vp, i64]),
         'f3d_estimate_normals': (i32, [vp, vp, i64, vp, dbl, i32, i32, vp, vp, vp]),
         'f3d_estimate_normals_batch_dev': (i32, [vp, vp, i32, i64, vp, dbl, i32, i32, vp, vp, vp, vp]),
     }
@@ -293,6 +299,14 @@ def _xyz(points):
     return np.ascontiguousarray(p, dtype=np.float64), F64
 
 
+def _knn_k(k):
+    """k of knn_query / transfer_labels, checked before anything is launched."""
+    k = int(k)
+    if k < 1 or k > KNN_MAX_K:
+        raise ValueError(f'k must be in [1, {KNN_MAX_K}], got {k}')
+    return k
+
+
 def _filter(filter_classes):
     if filter_classes is None:
         return None, 0
@@ -375,6 +389,10 @@ class Context:
     def reserve_point_vote(self, m, ncols):
         """Size the scratch of point_vote_frames_dev for clouds of up to m points and ncols vote columns, at any radius."""
         self._check(self._lib.f3d_ctx_reserve_point_vote(self._h, int(m), int(ncols)))
+
+    def reserve_knn(self, m):
+        """Size the scratch of knn_query_dev / transfer_labels_dev for data clouds of up to m points, at any radius."""
+        self._check(self._lib.f3d_ctx_reserve_knn(self._h, int(m)))
 
     def reserve_render(self, n, nviews, h, w):
         """Size the depth keys of render_lookups_dev / vote_visible_dev (automatic pass size) for nviews views of h x w pixels."""
@@ -870,6 +888,34 @@ class Context:
         self._check(self._lib.f3d_radius_query_fill(self._h, len(q), _ptr(nb)))
         return offs, nb
 
+    def knn_query(self, data, queries, k, radius):
+        """At most k nearest data points within radius of every query (f3d.h f3d_knn_query) -> (idx int32 [n, k], dist2 float64
+        [n, k], counts int32 [n]); a row is in (distance, index) order, padded with -1 / +inf."""
+        k = _knn_k(k)
+        d, ddt = _xyz(data)
+        q, qdt = _xyz(queries)
+        idx = np.empty((len(q), k), np.int32)
+        dist2 = np.empty((len(q), k), np.float64)
+        counts = np.empty(len(q), np.int32)
+        self._check(self._lib.f3d_knn_query(self._h, _ptr(d), ddt, len(d), _ptr(q), qdt, len(q), k, float(radius), _ptr(idx), _ptr(dist2),
+                                            _ptr(counts)))
+        return idx, dist2, counts
+
+    def transfer_labels(self, data, labels, queries, k, radius, fill=-1):
+        """The plurality label of every query's knn_query row (f3d.h f3d_transfer_labels) -> (out int64 [n], support int32 [n]);
+        a query without a neighbour gets (fill, 0).  labels: one integer per data point."""
+        k = _knn_k(k)
+        d, ddt = _xyz(data)
+        q, qdt = _xyz(queries)
+        lab = np.ascontiguousarray(labels, dtype=np.int64)
+        if lab.shape != (len(d),):
+            raise ValueError(f'labels must have one entry per data point ({len(d)}), got shape {lab.shape}')
+        out = np.empty(len(q), np.int64)
+        support = np.empty(len(q), np.int32)
+        self._check(self._lib.f3d_transfer_labels(self._h, _ptr(d), ddt, len(d), _ptr(lab), _ptr(q), qdt, len(q), k, float(radius), int(fill),
+                                                  _ptr(out), _ptr(support)))
+        return out, support
+
     def estimate_normals(self, points, cam_centre, radius=0.05, max_nn=30, orient=True, want_neighbours=False):
         """Open3D's estimate_normals(KDTreeSearchParamHybrid(radius, max_nn)) + the flip towards ``cam_centre`` of
         RTAB2Cache.surface_normal_estimation (ios_rtab.py:236-248), one frame: float64 [N,3] (f3d.h f3d_estimate_normals).
@@ -927,6 +973,22 @@ class Context:
     def radius_query_fill_dev(self, queries_ptr, query_dtype, n, offsets_ptr, neighbours_ptr, stream=None):
         """Fill pass after radius_query_dev of the same queries: neighbours int32 [nnz] on the device (enqueue only)."""
         self._check(self._lib.f3d_radius_query_fill_dev(self._h, queries_ptr, int(query_dtype), int(n), offsets_ptr, neighbours_ptr, stream))
+
+    def knn_query_dev(self, data_ptr, data_dtype, m, queries_ptr, query_dtype, n, k, radius, idx_ptr, dist2_ptr=None, counts_ptr=None,
+                      stream=None):
+        """knn_query on device pointers: idx int32 [n, k], dist2 float64 [n, k] and counts int32 [n] on the device (the last two
+        may be None); enqueues after one blocking readback."""
+        k = _knn_k(k)
+        self._check(self._lib.f3d_knn_query_dev(self._h, data_ptr, int(data_dtype), int(m), queries_ptr, int(query_dtype), int(n), k,
+                                                float(radius), idx_ptr, dist2_ptr, counts_ptr, stream))
+
+    def transfer_labels_dev(self, data_ptr, data_dtype, m, labels_ptr, queries_ptr, query_dtype, n, k, radius, fill, out_ptr,
+                            support_ptr=None, stream=None):
+        """transfer_labels on device pointers: labels int64 [m], out int64 [n], support int32 [n] (may be None) on the device;
+        enqueues after one blocking readback."""
+        k = _knn_k(k)
+        self._check(self._lib.f3d_transfer_labels_dev(self._h, data_ptr, int(data_dtype), int(m), labels_ptr, queries_ptr, int(query_dtype),
+                                                      int(n), k, float(radius), int(fill), out_ptr, support_ptr, stream))
 
     def rotate_dev(self, xyz_ptr, n, q_wxyz, out_ptr, stream=None):
         q = _f64(q_wxyz, (4,))

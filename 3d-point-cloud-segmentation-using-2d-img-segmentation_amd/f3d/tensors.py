@@ -84,3 +84,14 @@ def device_csr(adj, n, dev, what):
     if offs.dim() != 1 or len(offs) != n + 1 or int(offs[-1]) != len(nbrs):
         raise ValueError(CSR_ADJACENCY)
     return offs, nbrs
+
+
+def device_points(a, dev, name):
+    """`a` as a contiguous float32 / float64 [N, 3] tensor on `dev` (other dtypes are widened to float64)."""
+    import torch
+    t = torch.as_tensor(a).to(dev)
+    if t.dim() != 2 or t.shape[1] != 3:
+        raise ValueError(f'{name} must be [N, 3], got {tuple(t.shape)}')
+    if t.dtype != torch.float32:
+        t = t.to(torch.float64)
+    return t.contiguous()

@@ -621,6 +621,46 @@ int f3d_radius_query_count_dev(f3d_ctx* ctx, const void* data, f3d_dtype data_dt
 int f3d_radius_query_fill_dev(f3d_ctx* ctx, const void* queries /*device, as counted*/, f3d_dtype query_dtype, int64_t n,
                               const int64_t* offsets /*device*/, int32_t* neighbours /*device [nnz]*/, void* stream);
 
+/* ---- hybrid k-nearest search and label transfer between point sets (no reference counterpart) ------ */
+/* "At most k nearest within the radius" (Open3D's KDTreeSearchParamHybrid; sklearn's KDTree.query cut at a radius), from n QUERY
+ * points into m DATA points, and a label transfer built on it that carries one int64 per data point (class ids, panoptic ids, 0/1
+ * bits, negative values, values above 2^32) to every query point.  data [m, 3] and queries [n, 3] have a dtype each; float32 inputs
+ * are widened exactly.
+ *
+ * f3d_knn_query.  Let C_q be the data indices i with float64 d2(q, i) = (dx*dx + dy*dy) + dz*dz <= radius*radius, INCLUSIVE: the
+ * predicate of f3d_radius_query_*, so C_q is that entry's row q.  Row q of the result holds the c = min(k, |C_q|) members of C_q that
+ * are smallest under the lexicographic order (d2, i), in that order: ties in distance go to the lower index, and the result depends
+ * on neither thread timing, launch shape nor cell order.  idx int32 [n, k], dist2 float64 [n, k] (the d2 above, bit for bit), counts
+ * int32 [n] = c; the slots c .. k-1 hold idx = -1 and dist2 = +inf.  dist2 and counts may be NULL.
+ *
+ * f3d_transfer_labels.  The kept set of query q is the row above.  out[q] is the label with the most occurrences in it; among labels
+ * with the same count the one whose first occurrence comes earliest in the row wins (so k = 1 gives the nearest point's label, and
+ * an all-distinct row gives it too).  support[q] int32 = the winner's count (may be NULL).  An empty row gives out = fill,
+ * support = 0.  labels int64 [m] are read only at the kept indices: never for a query without a neighbour.  Nothing of size [n, k]
+ * is kept in memory.
+ *
+ * Ranges and errors, as for f3d_radius_query_*: 1 <= k <= 32, else F3D_ERR_INVALID; m == 0, NaN / infinity in the data or in the
+ * queries, radius >= 1e300: F3D_ERR_INVALID, nothing written.  radius < 0 or NaN: every row is empty, no error.  n == 0: nothing to
+ * do.  The search is radius-bounded by construction -- the grid's cell edge is the radius -- so an unbounded k-NN is not offered,
+ * and a radius far above the point spacing degrades towards brute force (every query then visits most of the cloud).
+ * Cost: one blocking readback per call (the cloud's box and the queries' non-finite flag together); the rest is enqueued.  The data's
+ * grid is built per call in context state of its own: a call between the count and fill passes of f3d_radius_query_* or
+ * f3d_radius_graph_* disturbs neither.  Scratch, independent of n and k: the grid, 40*m + 8*cells bytes + the sort's temporary
+ * storage (cells <= 2^24), and a 64-byte flag word.  f3d_ctx_reserve_knn(m) sizes it for any radius (cells = 2^24), so that a strict
+ * context does not allocate. */
+int f3d_knn_query(f3d_ctx* ctx, const void* data, f3d_dtype data_dtype, int64_t m, const void* queries, f3d_dtype query_dtype,
+                  int64_t n, int k, double radius, int32_t* idx /*[n,k]*/, double* dist2 /*[n,k]*/, int32_t* counts /*[n]*/);
+int f3d_knn_query_dev(f3d_ctx* ctx, const void* data, f3d_dtype data_dtype, int64_t m, const void* queries, f3d_dtype query_dtype,
+                      int64_t n, int k, double radius, int32_t* idx /*device [n,k]*/, double* dist2 /*device [n,k]*/,
+                      int32_t* counts /*device [n]*/, void* stream);
+int f3d_transfer_labels(f3d_ctx* ctx, const void* data, f3d_dtype data_dtype, int64_t m, const int64_t* labels /*[m]*/,
+                        const void* queries, f3d_dtype query_dtype, int64_t n, int k, double radius, int64_t fill,
+                        int64_t* out /*[n]*/, int32_t* support /*[n]*/);
+int f3d_transfer_labels_dev(f3d_ctx* ctx, const void* data, f3d_dtype data_dtype, int64_t m, const int64_t* labels /*device [m]*/,
+                            const void* queries, f3d_dtype query_dtype, int64_t n, int k, double radius, int64_t fill,
+                            int64_t* out /*device [n]*/, int32_t* support /*device [n]*/, void* stream);
+int f3d_ctx_reserve_knn(f3d_ctx* ctx, int64_t m);
+
 /* ---- PointVotingSegmentation.vote: radius search fused with the frame vote (segUtils/voting.py:224-265) ------ */
 /* The loop body of the reference for F frames in one call.  cloud [m, 3] (`cloud_dtype`), queries [F, hw, 3] (`query_dtype`: the
  * frames' world-space depth points), masks uint8 [F, hw] (already at the depth resolution), votes float64 [m, ncols] updated IN
