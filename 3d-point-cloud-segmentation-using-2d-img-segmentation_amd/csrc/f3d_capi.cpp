@@ -2,6 +2,7 @@
 // wrappers, and the tiny per-view host geometry.  No CPU fallback: every compute entry point
 // needs a HIP device.
 #include <hip/hip_runtime.h>
+#include <initializer_list>
 #include <vector>
 #include <cstddef>
 #include <math.h>
@@ -22,13 +23,29 @@ static_assert(offsetof(f3d_view, img_h) == offsetof(f3d_view, cull_n32) + 23 * 4
 
 namespace {
 
-enum { SLOT_XYZ = 0, SLOT_OUT0, SLOT_OUT1, SLOT_VIEWS, SLOT_MASKS, SLOT_AUX0, SLOT_AUX1, SLOT_SORT_PERM, SLOT_SORT_SCRATCH,
-       SLOT_TILED_MASKS, SLOT_TODO, SLOT_GRAPH, SLOT_GRAPH_BBOX, SLOT_PATCH,
-       SLOT_GRP_ORDER, SLOT_GRP_KEYS, SLOT_GRP_STARTS, SLOT_GRP_SCRATCH, SLOT_OBB_TABLE, SLOT_OBB_FACETS, SLOT_OBB_CAND, SLOT_FUSE_TABLES, SLOT_FUSE_CARRY, SLOT_FUSE_XYZ, SLOT_FUSION, SLOT_PATCH_STATUS, SLOT_NRM, SLOT_NRM_CAMS,
-       SLOT_QRY, SLOT_QRY_IN, SLOT_QRY_OFFS,
-       SLOT_FLOOD, SLOT_COLOR, SLOT_CVS_INST, SLOT_CVS_ORDER, SLOT_CVS_COFFS, SLOT_CVS_FLAGS, SLOT_CVS_SEEDS, SLOT_CVS_STATS,
-       SLOT_QUADS, SLOT_QUADS_OUT, SLOT_GROW, SLOT_PVOTE, SLOT_PVOTE_BITS, SLOT_MESH, SLOT_MESH_IO, SLOT_ZKEY, SLOT_ZCOUNTS,
-       SLOT_KNN, SLOT_KNN_FLAG, SLOT_COUNT };
+// Device memory of a context, three kinds of buffer with a type each, so that a name of one kind does not compile where another
+// is expected.  All grow on first use of a larger problem (grow()) and are refused growth by a strict context.
+//   scratch_slot: the work area of a _dev entry (grids, sort buffers, coded masks, ...), one name per area; only _dev entries
+//                 ensure() them, and f3d_ctx_reserve* sizes them.  Some hold state between two _dev calls (the grid between a count
+//                 and its fill pass, the coded masks and the todo list of a view-chunked fused call).
+//   staging:      the device copies of a host-pointer entry's arguments.  They have no names: the k-th buffer a call asks for
+//                 is ctx->stage[k] (struct staging), and nothing in them outlives the call.
+//   kept_slot:    what a host-pointer SEQUENCE leaves on the device for its next call, owned by that sequence alone
+//                 (f3d_ctx::graph_kept, qry_kept, grp_cloud say whether they hold it).
+enum scratch_slot { SLOT_OBB_BOXES = 0, SLOT_SORT_PERM, SLOT_SORT_SCRATCH, SLOT_TILED_MASKS, SLOT_TODO, SLOT_GRAPH, SLOT_GRAPH_BBOX,
+                    SLOT_PATCH, SLOT_GRP_SCRATCH, SLOT_OBB_TABLE, SLOT_OBB_FACETS, SLOT_OBB_CAND, SLOT_FUSE_TABLES, SLOT_FUSE_CARRY,
+                    SLOT_FUSE_XYZ, SLOT_FUSION, SLOT_PATCH_STATUS, SLOT_NRM, SLOT_NRM_CAMS, SLOT_QRY, SLOT_FLOOD, SLOT_COLOR,
+                    SLOT_CVS_INST, SLOT_CVS_STATS, SLOT_QUADS, SLOT_GROW, SLOT_PVOTE, SLOT_PVOTE_BITS, SLOT_MESH, SLOT_ZKEY,
+                    SLOT_ZCOUNTS, SLOT_KNN, SLOT_KNN_FLAG, SLOT_COUNT };
+enum kept_slot { KEPT_GRAPH_OFFS = 0,                                      // f3d_radius_graph_count -> _fill: the offsets
+                 KEPT_QRY_IN, KEPT_QRY_OFFS,                               // f3d_radius_query_count -> _fill: the queries, the offsets
+                 KEPT_GRP_ORDER, KEPT_GRP_KEYS, KEPT_GRP_STARTS,           // f3d_group_by_id -> f3d_obb_extremes -> f3d_obb_hull_filter
+                 KEPT_GRP_XYZ,                                             //   ... and, from the extremes call on, the cloud
+                 KEPT_COUNT };
+enum { STAGE_MAX = 9,                                                      // staging buffers of one call: f3d_patch_match and f3d_door_window_quads take 9
+       BACK_MAX = 5 };                                                     // outputs one call copies back: f3d_mesh_clean has 5
+
+struct devbuf { void* p; size_t cap; };
 
 thread_local char g_create_err[512] = "";
 
@@ -38,8 +55,9 @@ struct f3d_ctx {
     int device;
     hipStream_t stream;
     char err[512];
-    void* slot[SLOT_COUNT];
-    size_t cap[SLOT_COUNT];
+    devbuf scratch[SLOT_COUNT];
+    devbuf stage[STAGE_MAX];
+    devbuf kept[KEPT_COUNT];
     int* dev_err;                       // sticky device error word: one bit per operation (F3D_DEVERR_*)
     int strict;                         // 1: a scratch buffer that would have to grow is F3D_ERR_NOMEM (allocation-free _dev calls)
     long long allocs;                   // device allocations made by this context so far (f3d_ctx_alloc_count)
@@ -52,22 +70,27 @@ struct f3d_ctx {
     int32_t filter_host[F3D_MAX_FILTER];  // its staging copy: must outlive the asynchronous upload
     unsigned long long* count_dev;
     f3d_codebook* codebook;             // vote-bin code book of the fused path (device)
-    // radius graph: the search of the last count pass (the fill pass must follow it for the same cloud)
+    // radius graph: the search of the last count pass (the fill pass must follow it for the same cloud); graph_kept: that pass was
+    // f3d_radius_graph_count, whose offsets KEPT_GRAPH_OFFS holds
     f3d_gridsearch graph;
     int64_t graph_n;
-    const void* graph_xyz;
-    // radius query: the search of the last count pass, in slots of its own (SLOT_QRY*), for the fill pass of the same queries
+    bool graph_kept;
+    // radius query: the search of the last count pass, its grid in SLOT_QRY, for the fill pass of the same queries; qry_kept: that
+    // pass was f3d_radius_query_count, whose queries and offsets KEPT_QRY_IN / KEPT_QRY_OFFS hold
     f3d_gridsearch qry;
     int64_t qry_m, qry_n;
     int qry_qdtype;
     const void* qry_queries;
+    bool qry_kept;
     // point vote: device int[4] of the call being enqueued (f3d_kernels.h); pv_partial: the last call stopped at a frame with
     // non-finite queries after applying the frames before it (the host-pointer entry still copies the votes back)
     int* pv_words;
     int pv_partial;
-    // instance grouping of the last f3d_group_by_id call (host-pointer sequence group -> extremes -> hull filter)
+    // instance grouping of the last f3d_group_by_id call (host-pointer sequence group -> extremes -> hull filter), in KEPT_GRP_*;
+    // grp_cloud: f3d_obb_extremes has run for this grouping and left its cloud (of grp_dtype) in KEPT_GRP_XYZ
     int64_t grp_n, grp_nids;
     int grp_dtype;
+    bool grp_cloud;
     // view-chunked fused call in progress (f3d_fuse_chunked_begin_dev .. the chunk with v_end == nviews)
     struct { int active, next, nviews, h, w, nclasses, gather; int64_t n; const int32_t* perm; const void* xyz; } chunk;
 };
@@ -90,20 +113,25 @@ int fail(f3d_ctx* ctx, int code, const char* fmt, ...) {
                                           "%s: %s", #call, hipGetErrorString(e_));                       \
     } while (0)
 
-int ensure(f3d_ctx* ctx, int s, size_t bytes, void** out) {
+// One buffer of the context with room for `bytes`: it grows (with 1/8 of headroom) when it is too small, which a strict context refuses.
+int grow(f3d_ctx* ctx, devbuf* b, size_t bytes, const char* kind, int index, void** out) {
     if (bytes == 0) bytes = 16;
-    if (ctx->cap[s] < bytes) {
+    if (b->cap < bytes) {
         if (ctx->strict)
-            return fail(ctx, F3D_ERR_NOMEM, "strict context: scratch slot %d holds %zu bytes, %zu needed (f3d_ctx_reserve first)", s, ctx->cap[s], bytes);
-        if (ctx->slot[s]) { F3D_HIP(ctx, hipFree(ctx->slot[s])); ctx->slot[s] = nullptr; ctx->cap[s] = 0; }
+            return fail(ctx, F3D_ERR_NOMEM, "strict context: %s buffer %d holds %zu bytes, %zu needed (f3d_ctx_reserve first)", kind, index, b->cap, bytes);
+        if (b->p) { F3D_HIP(ctx, hipFree(b->p)); b->p = nullptr; b->cap = 0; }
         size_t want = bytes + bytes / 8;
-        F3D_HIP(ctx, hipMalloc(&ctx->slot[s], want));
-        ctx->cap[s] = want;
+        F3D_HIP(ctx, hipMalloc(&b->p, want));
+        b->cap = want;
         ++ctx->allocs;
     }
-    *out = ctx->slot[s];
+    *out = b->p;
     return F3D_OK;
 }
+
+int ensure(f3d_ctx* ctx, scratch_slot s, size_t bytes, void** out) { return grow(ctx, &ctx->scratch[s], bytes, "scratch", s, out); }
+
+bool dtype_ok(int dt) { return dt == F3D_F64 || dt == F3D_F32; }
 
 hipStream_t pick(f3d_ctx* ctx, void* stream) { return stream ? (hipStream_t)stream : ctx->stream; }
 
@@ -176,41 +204,49 @@ int take_error(f3d_ctx* ctx, hipStream_t s, int mask = F3D_DEVERR_ALL) {
     return F3D_OK;
 }
 
-// One call of an entry without "_dev" (include/f3d.h): inputs are copied into scratch slots as they are staged, on the context's
-// stream; outputs are copied back by finish(), which returns after the stream has drained.  The first failed allocation or copy
-// stays in `rc` and turns every later step into a no-op.  A NULL host pointer is not copied: a NULL output is not wanted (no slot,
-// NULL device pointer), a NULL input (an optional one) leaves its slot uninitialised.
+// One call of an entry without "_dev" (include/f3d.h): inputs are copied into the context's staging buffers as they are staged, on
+// the context's stream; outputs are copied back by finish(), which returns after the stream has drained, so no two calls' staging
+// is alive at once and the k-th buffer a call asks for is simply ctx->stage[k].  The first failed allocation or copy stays in `rc`
+// and turns every later step into a no-op.  A NULL host pointer is not copied: a NULL output is not wanted (its buffer is passed
+// over, NULL device pointer), a NULL input (an optional one) leaves its buffer uninitialised.
 struct staging {
     f3d_ctx* ctx;
     int rc = F3D_OK;
-    struct { void* host; const void* dev; size_t bytes; } back_[6];    // the most outputs an entry copies back
-    int nback = 0;
+    struct { void* host; const void* dev; size_t bytes; } back_[BACK_MAX];
+    int nback = 0, next = 0;
 
     explicit staging(f3d_ctx* c) : ctx(c) {}
-    void* slot(int s, size_t bytes) {
+    void* slot(size_t bytes) {
         void* p = nullptr;
-        if (!rc) rc = ensure(ctx, s, bytes, &p);
+        if (!rc && next >= STAGE_MAX) rc = fail(ctx, F3D_ERR_INVALID, "staging: more than %d buffers", STAGE_MAX);
+        if (!rc) { rc = grow(ctx, &ctx->stage[next], bytes, "staging", next, &p); ++next; }
+        return p;
+    }
+    // what a host-pointer sequence leaves for its next call: a buffer of the sequence's own instead of a staging buffer
+    void* keep(kept_slot k, size_t bytes) {
+        void* p = nullptr;
+        if (!rc) rc = grow(ctx, &ctx->kept[k], bytes, "kept", k, &p);
         return p;
     }
     void put(void* dev, const void* host, size_t bytes) { if (!rc && host && bytes) rc = h2d(dev, host, bytes); }
     void back(void* host, const void* dev, size_t bytes) {
         if (!host || !bytes || rc) return;
-        if (nback == 6) { rc = fail(ctx, F3D_ERR_INVALID, "staging: more than 6 outputs"); return; }
+        if (nback == BACK_MAX) { rc = fail(ctx, F3D_ERR_INVALID, "staging: more than %d outputs", BACK_MAX); return; }
         back_[nback++] = {host, dev, bytes};
     }
-    template <class T> T* in(int s, const T* host, size_t bytes) {
-        void* p = slot(s, bytes);
+    template <class T> T* in(const T* host, size_t bytes) {
+        void* p = slot(bytes);
         put(p, host, bytes);
         return (T*)p;
     }
-    template <class T> T* out(int s, T* host, size_t bytes) {
-        if (!host) return nullptr;
-        T* p = (T*)slot(s, bytes);
+    template <class T> T* out(T* host, size_t bytes) {
+        if (!host) { ++next; return nullptr; }                 // (a call's buffers keep their positions whatever it leaves out)
+        T* p = (T*)slot(bytes);
         back(host, p, bytes);
         return p;
     }
-    template <class T> T* inout(int s, T* host, size_t bytes) {
-        T* p = in(s, host, bytes);
+    template <class T> T* inout(T* host, size_t bytes) {
+        T* p = in(host, bytes);
         back(host, p, bytes);
         return p;
     }
@@ -301,6 +337,22 @@ int bits_for(int64_t v) { int b = 0; while (((int64_t)1 << b) < v) ++b; return b
 
 static int ensure_table(f3d_ctx* ctx, int64_t hw);
 
+// What every f3d_ctx_reserve* does after its argument check: sizes the listed scratch buffers (an entry with wanted == false is
+// passed over) and, with table_hw > 0, the vote table for frames of that many pixels.  Reserving is the one thing a strict context
+// may allocate for: strict is lifted here and back in place on every path.
+struct reservation { scratch_slot s; size_t bytes; bool wanted = true; };
+
+static int reserve(f3d_ctx* ctx, std::initializer_list<reservation> list, int64_t table_hw = 0) {
+    const int strict = ctx->strict;
+    ctx->strict = 0;
+    int rc = F3D_OK;
+    void* p;
+    for (const reservation& r : list) if (!rc && r.wanted) rc = ensure(ctx, r.s, r.bytes, &p);
+    if (!rc && table_hw > 0) rc = ensure_table(ctx, table_hw);
+    ctx->strict = strict;
+    return rc;
+}
+
 extern "C" {
 
 int f3d_version(void) { return F3D_VERSION; }
@@ -340,7 +392,9 @@ void f3d_ctx_destroy(f3d_ctx* ctx) {
     if (!ctx) return;
     (void)hipSetDevice(ctx->device);
     if (ctx->stream) (void)hipStreamSynchronize(ctx->stream);
-    for (int s = 0; s < SLOT_COUNT; ++s) if (ctx->slot[s]) (void)hipFree(ctx->slot[s]);
+    for (devbuf& b : ctx->scratch) if (b.p) (void)hipFree(b.p);
+    for (devbuf& b : ctx->stage) if (b.p) (void)hipFree(b.p);
+    for (devbuf& b : ctx->kept) if (b.p) (void)hipFree(b.p);
     if (ctx->dev_err) (void)hipFree(ctx->dev_err);
     if (ctx->table) (void)hipFree(ctx->table);
     if (ctx->filter_dev) (void)hipFree(ctx->filter_dev);
@@ -365,17 +419,13 @@ void* f3d_ctx_stream(f3d_ctx* ctx) { return ctx ? (void*)ctx->stream : nullptr; 
 int f3d_ctx_reserve(f3d_ctx* ctx, int64_t n, int nviews, int h, int w) {
     int rc = enter(ctx); if (rc) return rc;
     if (n < 0 || n > 0x7fffffffLL || nviews < 0 || h < 0 || w < 0) return fail(ctx, F3D_ERR_INVALID, "ctx_reserve: bad arguments");
-    const int strict = ctx->strict;
-    ctx->strict = 0;
-    void* p;
-    rc = ensure(ctx, SLOT_TODO, f3d_fuse_todo_bytes(n, nviews, F3D_CODE_MAX_NCLASSES), &p);   // (any number of classes)
-    if (!rc && n > 0) rc = ensure(ctx, SLOT_SORT_PERM, (size_t)n * 4, &p);
-    if (!rc && n > 0) rc = ensure(ctx, SLOT_SORT_SCRATCH, f3d_sort_scratch_bytes(n), &p);
-    if (!rc && nviews > 0 && h > 0 && w > 0) rc = ensure(ctx, SLOT_TILED_MASKS, f3d_coded_masks_bytes(nviews, h, w), &p);
-    if (!rc && h > 0 && w > 0) rc = ensure_table(ctx, (int64_t)h * w);
-    if (!rc) rc = ensure(ctx, SLOT_FUSE_TABLES, f3d_fuse_tables_bytes(nviews > 0 ? nviews : 1), &p);
-    ctx->strict = strict;
-    return rc;
+    const bool frames = h > 0 && w > 0;
+    return reserve(ctx, {{SLOT_TODO, f3d_fuse_todo_bytes(n, nviews, F3D_CODE_MAX_NCLASSES)},                  // (any number of classes)
+                         {SLOT_SORT_PERM, (size_t)n * 4, n > 0},
+                         {SLOT_SORT_SCRATCH, f3d_sort_scratch_bytes(n), n > 0},
+                         {SLOT_TILED_MASKS, frames && nviews > 0 ? f3d_coded_masks_bytes(nviews, h, w) : 0, frames && nviews > 0},
+                         {SLOT_FUSE_TABLES, f3d_fuse_tables_bytes(nviews > 0 ? nviews : 1)}},
+                   frames ? (int64_t)h * w : 0);
 }
 
 int f3d_ctx_set_strict(f3d_ctx* ctx, int strict) {
@@ -481,8 +531,8 @@ int f3d_rotate_f64(f3d_ctx* ctx, const double* xyz, int64_t n, const double q[4]
     if (n < 0 || (n > 0 && (!xyz || !out)) || !q) return fail(ctx, F3D_ERR_INVALID, "rotate: bad arguments");
     if (n == 0) return F3D_OK;
     staging st(ctx);
-    const double* din = st.in(SLOT_XYZ, xyz, (size_t)n * 24);
-    double* dout = st.out(SLOT_OUT0, out, (size_t)n * 24);
+    const double* din = st.in(xyz, (size_t)n * 24);
+    double* dout = st.out(out, (size_t)n * 24);
     if (!st.rc) st.rc = f3d_rotate_f64_dev(ctx, din, n, q, dout, ctx->stream);
     return st.finish();
 }
@@ -530,8 +580,8 @@ int f3d_unproject_depth(f3d_ctx* ctx, const void* depth, int depth_type, int h, 
         return fail(ctx, F3D_ERR_INVALID, "unproject_depth: unknown depth type %d", depth_type);
     if (n == 0) return F3D_OK;
     staging st(ctx);
-    const void* din = st.in(SLOT_AUX0, depth, depth_bytes(depth_type, n));
-    double* dout = st.out(SLOT_OUT0, xyz, (size_t)n * 24);
+    const void* din = st.in(depth, depth_bytes(depth_type, n));
+    double* dout = st.out(xyz, (size_t)n * 24);
     if (!st.rc) st.rc = f3d_unproject_depth_dev(ctx, din, depth_type, h, w, K, depth_scale, q_wxyz, t, dout, ctx->stream);
     return st.finish();
 }
@@ -552,9 +602,9 @@ int f3d_project_view_f64(f3d_ctx* ctx, const double* xyz, int64_t n, const f3d_v
     if (n < 0 || !view || (!uv && !inside) || (n > 0 && !xyz)) return fail(ctx, F3D_ERR_INVALID, "project_view: bad arguments");
     if (n == 0) return F3D_OK;
     staging st(ctx);
-    const double* din = st.in(SLOT_XYZ, xyz, (size_t)n * 24);
-    int32_t* duv = st.out(SLOT_OUT0, uv, (size_t)n * 8);
-    uint8_t* dinside = st.out(SLOT_OUT1, inside, (size_t)n);
+    const double* din = st.in(xyz, (size_t)n * 24);
+    int32_t* duv = st.out(uv, (size_t)n * 8);
+    uint8_t* dinside = st.out(inside, (size_t)n);
     if (!st.rc) st.rc = f3d_project_view_dev(ctx, din, F3D_F64, n, view, duv, dinside, ctx->stream);
     return st.finish();
 }
@@ -611,8 +661,8 @@ int f3d_inside_polyhedra_f64(f3d_ctx* ctx, const double* xyz, int64_t n, const d
     if (n < 0 || !inside || (n > 0 && !xyz)) return fail(ctx, F3D_ERR_INVALID, "inside_polyhedra: bad arguments");
     if (n == 0) return F3D_OK;
     staging st(ctx);
-    const double* din = st.in(SLOT_XYZ, xyz, (size_t)n * 24);
-    uint8_t* dout = st.out(SLOT_OUT1, inside, (size_t)n);
+    const double* din = st.in(xyz, (size_t)n * 24);
+    uint8_t* dout = st.out(inside, (size_t)n);
     if (!st.rc) st.rc = f3d_inside_polyhedra_dev(ctx, din, F3D_F64, n, plane_pts, normals, m, dout, ctx->stream);
     return st.finish();
 }
@@ -802,25 +852,24 @@ int f3d_debug_fastpath_audit(f3d_ctx* ctx, const void* xyz, f3d_dtype dtype, int
     if (n < 0 || n > 0x7fffffffLL || nviews < 0 || w <= 0 || h <= 0 || !stats || (n > 0 && !xyz) || (nviews > 0 && !views))
         return fail(ctx, F3D_ERR_INVALID, "fastpath_audit: bad arguments");
     staging st(ctx);
-    const void* dxyz = st.in(SLOT_XYZ, xyz, xyz_bytes(dtype, n));
-    void* dsorted = st.slot(SLOT_OUT0, xyz_bytes(dtype, n));
-    int32_t* dperm = (int32_t*)st.slot(SLOT_SORT_PERM, (size_t)n * 4);
-    void* scratch = st.slot(SLOT_SORT_SCRATCH, f3d_sort_scratch_bytes(n));
-    const f3d_view* dviews = st.in(SLOT_VIEWS, views, sizeof(f3d_view) * (size_t)nviews);
-    void* dstats = st.slot(SLOT_AUX0, 64);
+    const void* dxyz = st.in(xyz, xyz_bytes(dtype, n));
+    void* dsorted = st.slot(xyz_bytes(dtype, n));
+    int32_t* dperm = (int32_t*)st.slot((size_t)n * 4);
+    const f3d_view* dviews = st.in(views, sizeof(f3d_view) * (size_t)nviews);
+    void* dstats = st.slot(64);
     st.back(stats, dstats, 32);
     if (st.rc) return st.rc;
     // waves of 64 consecutive points must be spatial neighbours, as in the fused call: audit the cell-sorted copy
-    if (n) F3D_HIP(ctx, f3d_launch_cell_sort(dxyz, dtype, n, dsorted, dperm, scratch, ctx->stream));
+    if ((rc = f3d_cloud_sort_cells_dev(ctx, dxyz, dtype, n, dsorted, dperm, ctx->stream))) return rc;
     F3D_HIP(ctx, f3d_launch_fastpath_audit(dsorted, dtype, n, dviews, nviews, w, h, (unsigned long long*)dstats, ctx->stream));
     return st.finish();
 }
 
 int f3d_debug_fuse_deferred(f3d_ctx* ctx, void* stream, uint32_t counts[2]) {
     int rc = enter(ctx); if (rc) return rc;
-    if (!counts || !ctx->slot[SLOT_TODO]) return fail(ctx, F3D_ERR_INVALID, "fuse_deferred: no fused call has run in this context");
+    if (!counts || !ctx->scratch[SLOT_TODO].p) return fail(ctx, F3D_ERR_INVALID, "fuse_deferred: no fused call has run in this context");
     hipStream_t s = pick(ctx, stream);
-    F3D_HIP(ctx, hipMemcpyAsync(counts, ctx->slot[SLOT_TODO], 8, hipMemcpyDeviceToHost, s));
+    F3D_HIP(ctx, hipMemcpyAsync(counts, ctx->scratch[SLOT_TODO].p, 8, hipMemcpyDeviceToHost, s));
     F3D_HIP(ctx, hipStreamSynchronize(s));
     return F3D_OK;
 }
@@ -838,11 +887,11 @@ int f3d_project_vote_argmax(f3d_ctx* ctx, const void* xyz, f3d_dtype dtype, int6
         return fail(ctx, F3D_ERR_INVALID, "project_vote_argmax: bad arguments");
     if (n == 0) return F3D_OK;
     staging st(ctx);
-    const void* dxyz = st.in(SLOT_XYZ, xyz, xyz_bytes(dtype, n));
-    const f3d_view* dviews = st.in(SLOT_VIEWS, views, sizeof(f3d_view) * (size_t)nviews);
-    const uint8_t* dmasks = st.in(SLOT_MASKS, masks, (size_t)nviews * h * w);
-    int64_t* dcls = st.out(SLOT_OUT0, classes, (size_t)n * 8);
-    uint16_t* dvotes = st.out(SLOT_OUT1, votes_u16, (size_t)n * ((size_t)nclasses + 1) * 2);
+    const void* dxyz = st.in(xyz, xyz_bytes(dtype, n));
+    const f3d_view* dviews = st.in(views, sizeof(f3d_view) * (size_t)nviews);
+    const uint8_t* dmasks = st.in(masks, (size_t)nviews * h * w);
+    int64_t* dcls = st.out(classes, (size_t)n * 8);
+    uint16_t* dvotes = st.out(votes_u16, (size_t)n * ((size_t)nclasses + 1) * 2);
     // NumPy callers hand over clouds in arbitrary order: cell-sort large ones (results are order-independent)
     const unsigned flags = n >= 65536 ? F3D_FUSE_SORT : 0u;
     if (!st.rc) st.rc = f3d_project_vote_argmax_dev(ctx, dxyz, dtype, n, dviews, nviews, dmasks, h, w, nclasses, filter, nfilter, threshold,
@@ -920,9 +969,9 @@ int f3d_vote_uv2pt_batch(f3d_ctx* ctx, const int32_t* luts, const uint8_t* masks
         return fail(ctx, F3D_ERR_INVALID, "vote_uv2pt_batch: bad arguments");
     if (nframes == 0 || hw == 0) return F3D_OK;
     staging st(ctx);                                          // every frame's lookup in ONE copy, the matrix once per BATCH
-    const int32_t* dlut = st.in(SLOT_AUX0, luts, (size_t)nframes * hw * 4);
-    const uint8_t* dmask = st.in(SLOT_AUX1, masks, (size_t)nframes * hw);
-    double* dvotes = st.inout(SLOT_OUT1, votes, (size_t)npts * ncols * 8);
+    const int32_t* dlut = st.in(luts, (size_t)nframes * hw * 4);
+    const uint8_t* dmask = st.in(masks, (size_t)nframes * hw);
+    double* dvotes = st.inout(votes, (size_t)npts * ncols * 8);
     if (!st.rc) st.rc = f3d_vote_uv2pt_batch_dev(ctx, dlut, dmask, nframes, h, w, dvotes, npts, ncols, ctx->stream);
     return st.finish(F3D_DEVERR_VOTE, true);                  // frames before a bad one stay applied, like NumPy
 }
@@ -933,9 +982,9 @@ int f3d_vote_uv2pt(f3d_ctx* ctx, const int32_t* uv2pt, const uint8_t* mask, int6
         return fail(ctx, F3D_ERR_INVALID, "vote_uv2pt: bad arguments");
     if (hw == 0) return F3D_OK;
     staging st(ctx);
-    const int32_t* dlut = st.in(SLOT_AUX0, uv2pt, (size_t)hw * 4);
-    const uint8_t* dmask = st.in(SLOT_AUX1, mask, (size_t)hw);
-    double* dvotes = st.inout(SLOT_OUT1, votes, (size_t)npts * ncols * 8);
+    const int32_t* dlut = st.in(uv2pt, (size_t)hw * 4);
+    const uint8_t* dmask = st.in(mask, (size_t)hw);
+    double* dvotes = st.inout(votes, (size_t)npts * ncols * 8);
     if (!st.rc) st.rc = f3d_vote_uv2pt_dev(ctx, dlut, dmask, hw, dvotes, npts, ncols, ctx->stream);
     return st.finish(F3D_DEVERR_VOTE);                        // nothing is written back on an IndexError
 }
@@ -957,8 +1006,8 @@ int f3d_segment_votes(f3d_ctx* ctx, const double* votes, int64_t npts, int ncols
     if (npts < 0 || ncols <= 0 || (npts > 0 && (!votes || !classes))) return fail(ctx, F3D_ERR_INVALID, "segment_votes: bad arguments");
     if (npts == 0) return F3D_OK;
     staging st(ctx);
-    const double* dvotes = st.in(SLOT_OUT1, votes, (size_t)npts * ncols * 8);
-    int64_t* dcls = st.out(SLOT_OUT0, classes, (size_t)npts * 8);
+    const double* dvotes = st.in(votes, (size_t)npts * ncols * 8);
+    int64_t* dcls = st.out(classes, (size_t)npts * 8);
     if (!st.rc) st.rc = f3d_segment_votes_dev(ctx, dvotes, npts, ncols, nclasses, threshold, filter, nfilter, dcls, ctx->stream);
     return st.finish();
 }
@@ -984,8 +1033,8 @@ int f3d_segment_votes_lastcol(f3d_ctx* ctx, const double* votes, int64_t npts, i
     if (npts < 0 || ncols <= 0 || (npts > 0 && (!votes || !classes))) return fail(ctx, F3D_ERR_INVALID, "segment_votes_lastcol: bad arguments");
     if (npts == 0) return F3D_OK;
     staging st(ctx);
-    const double* dvotes = st.in(SLOT_OUT1, votes, (size_t)npts * ncols * 8);
-    int64_t* dcls = st.out(SLOT_OUT0, classes, (size_t)npts * 8);
+    const double* dvotes = st.in(votes, (size_t)npts * ncols * 8);
+    int64_t* dcls = st.out(classes, (size_t)npts * 8);
     if (!st.rc) st.rc = f3d_segment_votes_lastcol_dev(ctx, dvotes, npts, ncols, nclasses, threshold, filter, nfilter, dcls, ctx->stream);
     return st.finish();
 }
@@ -1016,8 +1065,8 @@ int f3d_sem_logits_to_mask(f3d_ctx* ctx, const float* sem, int c, int64_t hw, fl
     if (c <= 0 || hw < 0 || (hw > 0 && (!sem || !mask))) return fail(ctx, F3D_ERR_INVALID, "sem_logits_to_mask: bad arguments");
     if (hw == 0) return F3D_OK;
     staging st(ctx);
-    const float* dsem = st.in(SLOT_MASKS, sem, (size_t)c * hw * 4);
-    uint8_t* dmask = st.out(SLOT_AUX1, mask, (size_t)hw);
+    const float* dsem = st.in(sem, (size_t)c * hw * 4);
+    uint8_t* dmask = st.out(mask, (size_t)hw);
     if (!st.rc) st.rc = f3d_sem_logits_to_mask_dev(ctx, dsem, c, hw, conf, low_label, dmask, ctx->stream);
     return st.finish();
 }
@@ -1034,7 +1083,7 @@ int f3d_points_in_obb_dev(f3d_ctx* ctx, const void* xyz, f3d_dtype dtype, int64_
     hipStream_t s = pick(ctx, stream);
     void* dboxes;                                              // the cell table (8-byte aligned), the boxes, then their float32 bounds
     const size_t cells = f3d_obb_cells_bytes();
-    if ((rc = ensure(ctx, SLOT_VIEWS, cells + (sizeof(f3d_obb) + 6 * sizeof(float)) * (size_t)b, &dboxes))) return rc;
+    if ((rc = ensure(ctx, SLOT_OBB_BOXES, cells + (sizeof(f3d_obb) + 6 * sizeof(float)) * (size_t)b, &dboxes))) return rc;
     char* base = (char*)dboxes + cells;
     F3D_HIP(ctx, hipMemcpyAsync(base, boxes, sizeof(f3d_obb) * (size_t)b, hipMemcpyHostToDevice, s));
     F3D_HIP(ctx, f3d_launch_points_in_obb(xyz, dtype, n, (const f3d_obb*)base, b, (float*)(base + sizeof(f3d_obb) * (size_t)b), dboxes, inside_bits, cooc, s));
@@ -1047,9 +1096,9 @@ int f3d_points_in_obb(f3d_ctx* ctx, const void* xyz, f3d_dtype dtype, int64_t n,
     if (n < 0 || b < 0 || (n > 0 && !xyz) || (!inside_bits && !cooc)) return fail(ctx, F3D_ERR_INVALID, "points_in_obb: bad arguments");
     if (b == 0) return F3D_OK;
     staging st(ctx);
-    const void* dxyz = st.in(SLOT_XYZ, xyz, xyz_bytes(dtype, n));
-    uint32_t* dbits = st.out(SLOT_OUT1, inside_bits, (size_t)n * (((size_t)b + 31) / 32) * 4);
-    uint8_t* dcooc = st.out(SLOT_AUX0, cooc, (size_t)b * b);
+    const void* dxyz = st.in(xyz, xyz_bytes(dtype, n));
+    uint32_t* dbits = st.out(inside_bits, (size_t)n * (((size_t)b + 31) / 32) * 4);
+    uint8_t* dcooc = st.out(cooc, (size_t)b * b);
     if (st.rc) return st.rc;
     if (dcooc && n == 0) F3D_HIP(ctx, hipMemsetAsync(dcooc, 0, (size_t)b * b, ctx->stream));
     st.rc = f3d_points_in_obb_dev(ctx, dxyz, dtype, n, boxes, b, dbits, dcooc, ctx->stream);
@@ -1071,7 +1120,7 @@ int f3d_relabel(f3d_ctx* ctx, int64_t* ids, int64_t n, int64_t from, int64_t to,
     if (count) *count = 0;
     if (n == 0) return F3D_OK;
     staging st(ctx);
-    int64_t* dids = st.inout(SLOT_OUT0, ids, (size_t)n * 8);
+    int64_t* dids = st.inout(ids, (size_t)n * 8);
     st.back(count, ctx->count_dev, 8);
     if (!st.rc) st.rc = f3d_relabel_dev(ctx, dids, n, from, to, (int64_t*)ctx->count_dev, ctx->stream);
     return st.finish();
@@ -1086,10 +1135,10 @@ int f3d_ray_x_lines(f3d_ctx* ctx, const double origin[3], const double direction
     if (n < 0 || !origin || !direction || (n > 0 && (!starts || !ends || !points || !within))) return fail(ctx, F3D_ERR_INVALID, "ray_x_lines: bad arguments");
     if (n == 0) return F3D_OK;
     staging st(ctx);
-    const double* ds = st.in(SLOT_XYZ, starts, (size_t)n * 24);
-    const double* de = st.in(SLOT_OUT1, ends, (size_t)n * 24);
-    double* dp = st.out(SLOT_OUT0, points, (size_t)n * 24);
-    uint8_t* dw = st.out(SLOT_AUX1, within, (size_t)n);
+    const double* ds = st.in(starts, (size_t)n * 24);
+    const double* de = st.in(ends, (size_t)n * 24);
+    double* dp = st.out(points, (size_t)n * 24);
+    uint8_t* dw = st.out(within, (size_t)n);
     if (st.rc) return st.rc;
     F3D_HIP(ctx, f3d_launch_ray_x_lines(origin, direction, ds, de, n, dp, dw, ctx->stream));
     return st.finish();
@@ -1101,10 +1150,10 @@ int f3d_rays_x_plane(f3d_ctx* ctx, const double pp[3], const double pn[3], const
     if (n < 0 || !pp || !pn || (n > 0 && (!origins || !dirs || !points || !valid))) return fail(ctx, F3D_ERR_INVALID, "rays_x_plane: bad arguments");
     if (n == 0) return F3D_OK;
     staging st(ctx);
-    const double* d_o = st.in(SLOT_XYZ, origins, (size_t)n * 24);
-    const double* dd = st.in(SLOT_OUT1, dirs, (size_t)n * 24);
-    double* dp = st.out(SLOT_OUT0, points, (size_t)n * 24);
-    uint8_t* dv = st.out(SLOT_AUX1, valid, (size_t)n);
+    const double* d_o = st.in(origins, (size_t)n * 24);
+    const double* dd = st.in(dirs, (size_t)n * 24);
+    double* dp = st.out(points, (size_t)n * 24);
+    uint8_t* dv = st.out(valid, (size_t)n);
     if (st.rc) return st.rc;
     F3D_HIP(ctx, f3d_launch_rays_x_plane(pp, pn, d_o, dd, n, dp, dv, ctx->stream));
     return st.finish();
@@ -1118,12 +1167,12 @@ int f3d_lines_x_planes(f3d_ctx* ctx, const double* lo, const double* le, int64_t
     if (n != 1 && n != m) return fail(ctx, F3D_ERR_INVALID, "operands could not be broadcast together with shapes (%lld,%d,3) (%lld,3)", (long long)n, m, (long long)n);
     if (n == 0 || m == 0) return F3D_OK;
     staging st(ctx);
-    const double* d_o = st.in(SLOT_XYZ, lo, (size_t)n * 24);
-    const double* de = st.in(SLOT_OUT1, le, (size_t)n * 24);
-    const double* dpp = st.in(SLOT_VIEWS, pps, (size_t)m * 24);
-    const double* dpn = st.in(SLOT_AUX0, pns, (size_t)m * 24);
-    double* dp = st.out(SLOT_OUT0, points, (size_t)n * m * 24);
-    uint8_t* dv = st.out(SLOT_AUX1, valid, (size_t)n * m);
+    const double* d_o = st.in(lo, (size_t)n * 24);
+    const double* de = st.in(le, (size_t)n * 24);
+    const double* dpp = st.in(pps, (size_t)m * 24);
+    const double* dpn = st.in(pns, (size_t)m * 24);
+    double* dp = st.out(points, (size_t)n * m * 24);
+    uint8_t* dv = st.out(valid, (size_t)n * m);
     if (st.rc) return st.rc;
     F3D_HIP(ctx, f3d_launch_lines_x_planes(d_o, de, n, dpp, dpn, m, n == 1 ? 0 : 1, dp, dv, ctx->stream));
     return st.finish();
@@ -1134,10 +1183,10 @@ int f3d_point_inside_polygon(f3d_ctx* ctx, const double* points, int64_t n, cons
     if (n < 0 || m < 1 || !verts || (n > 0 && (!points || !inside || !within))) return fail(ctx, F3D_ERR_INVALID, "point_inside_polygon: bad arguments");
     if (n == 0) return F3D_OK;
     staging st(ctx);
-    const double* dp = st.in(SLOT_XYZ, points, (size_t)n * 24);
-    const double* dv = st.in(SLOT_VIEWS, verts, (size_t)m * 24);
-    uint8_t* di = st.out(SLOT_AUX1, inside, (size_t)n);
-    uint8_t* dw = st.out(SLOT_OUT0, within, (size_t)n * m);
+    const double* dp = st.in(points, (size_t)n * 24);
+    const double* dv = st.in(verts, (size_t)m * 24);
+    uint8_t* di = st.out(inside, (size_t)n);
+    uint8_t* dw = st.out(within, (size_t)n * m);
     if (st.rc) return st.rc;
     F3D_HIP(ctx, f3d_launch_point_inside_polygon(dp, n, dv, m, di, dw, ctx->stream));
     return st.finish();
@@ -1148,8 +1197,8 @@ int f3d_points_plane_projection(f3d_ctx* ctx, const double* points, int64_t n, c
     if (n < 0 || !pp || !nr || (n > 0 && (!points || !out))) return fail(ctx, F3D_ERR_INVALID, "points_plane_projection: bad arguments");
     if (n == 0) return F3D_OK;
     staging st(ctx);
-    const double* dp = st.in(SLOT_XYZ, points, (size_t)n * 24);
-    double* d_o = st.out(SLOT_OUT0, out, (size_t)n * 24);
+    const double* dp = st.in(points, (size_t)n * 24);
+    double* d_o = st.out(out, (size_t)n * 24);
     if (st.rc) return st.rc;
     F3D_HIP(ctx, f3d_launch_points_plane_projection(dp, n, pp, nr, d_o, ctx->stream));
     return st.finish();
@@ -1161,11 +1210,11 @@ int f3d_lines_plane_projection(f3d_ctx* ctx, const double* starts, const double*
     if (n < 0 || !pp || !nr || (n > 0 && (!starts || !ends || !sp || !ep || !dirs))) return fail(ctx, F3D_ERR_INVALID, "lines_plane_projection: bad arguments");
     if (n == 0) return F3D_OK;
     staging st(ctx);
-    const double* ds = st.in(SLOT_XYZ, starts, (size_t)n * 24);
-    const double* de = st.in(SLOT_OUT1, ends, (size_t)n * 24);
-    double* dsp = st.out(SLOT_OUT0, sp, (size_t)n * 24);
-    double* dep = st.out(SLOT_MASKS, ep, (size_t)n * 24);
-    double* dd = st.out(SLOT_AUX0, dirs, (size_t)n * 24);
+    const double* ds = st.in(starts, (size_t)n * 24);
+    const double* de = st.in(ends, (size_t)n * 24);
+    double* dsp = st.out(sp, (size_t)n * 24);
+    double* dep = st.out(ep, (size_t)n * 24);
+    double* dd = st.out(dirs, (size_t)n * 24);
     if (st.rc) return st.rc;
     F3D_HIP(ctx, f3d_launch_points_plane_projection(ds, n, pp, nr, dsp, ctx->stream));
     F3D_HIP(ctx, f3d_launch_points_plane_projection(de, n, pp, nr, dep, ctx->stream));
@@ -1193,11 +1242,11 @@ int f3d_components_same_class(f3d_ctx* ctx, const int64_t* classes, int64_t n, c
     const int64_t e = offsets[n];
     if (e < 0 || (e > 0 && !nbrs)) return fail(ctx, F3D_ERR_INVALID, "components_same_class: bad adjacency");
     staging st(ctx);
-    const int64_t* dcls = st.in(SLOT_XYZ, classes, (size_t)n * 8);
-    const int64_t* doffs = st.in(SLOT_OUT1, offsets, (size_t)(n + 1) * 8);
-    const int32_t* dnb = st.in(SLOT_MASKS, nbrs, (size_t)e * 4);
-    int32_t* dpar = (int32_t*)st.slot(SLOT_AUX0, (size_t)n * 4);
-    int64_t* droot = st.out(SLOT_OUT0, root, (size_t)n * 8);
+    const int64_t* dcls = st.in(classes, (size_t)n * 8);
+    const int64_t* doffs = st.in(offsets, (size_t)(n + 1) * 8);
+    const int32_t* dnb = st.in(nbrs, (size_t)e * 4);
+    int32_t* dpar = (int32_t*)st.slot((size_t)n * 4);
+    int64_t* droot = st.out(root, (size_t)n * 8);
     if (!st.rc) st.rc = f3d_components_same_class_dev(ctx, dcls, n, doffs, dnb, dpar, droot, ctx->stream);
     return st.finish(F3D_DEVERR_CC);
 }
@@ -1210,15 +1259,8 @@ int f3d_components_same_class(f3d_ctx* ctx, const int64_t* classes, int64_t n, c
 int f3d_ctx_reserve_cvseg(f3d_ctx* ctx, int64_t n) {
     int rc = enter(ctx); if (rc) return rc;
     if (n < 0 || n > 0x7fffffffLL) return fail(ctx, F3D_ERR_INVALID, "ctx_reserve_cvseg: bad arguments");
-    const int strict = ctx->strict;
-    ctx->strict = 0;
-    void* p;
-    rc = ensure(ctx, SLOT_FLOOD, f3d_flood_scratch_bytes(n), &p);
-    if (!rc) rc = ensure(ctx, SLOT_COLOR, f3d_color_scratch_bytes(n), &p);
-    if (!rc) rc = ensure(ctx, SLOT_CVS_INST, F3D_CVSEG_RESERVED_LIST * 8, &p);
-    if (!rc) rc = ensure(ctx, SLOT_CVS_STATS, 16, &p);
-    ctx->strict = strict;
-    return rc;
+    return reserve(ctx, {{SLOT_FLOOD, f3d_flood_scratch_bytes(n)}, {SLOT_COLOR, f3d_color_scratch_bytes(n)},
+                         {SLOT_CVS_INST, F3D_CVSEG_RESERVED_LIST * 8}, {SLOT_CVS_STATS, 16}});
 }
 
 int f3d_flood_order_dev(f3d_ctx* ctx, const int64_t* classes, int64_t n, const int64_t* offsets, const int32_t* nbrs,
@@ -1250,13 +1292,13 @@ int f3d_flood_order(f3d_ctx* ctx, const int64_t* classes, int64_t n, const int64
     const int64_t e = offsets[n];
     if (e < 0 || (e > 0 && !nbrs)) return fail(ctx, F3D_ERR_INVALID, "flood_order: bad adjacency");
     staging st(ctx);
-    const int64_t* dcls = st.in(SLOT_XYZ, classes, (size_t)n * 8);
-    const int64_t* doffs = st.in(SLOT_OUT1, offsets, (size_t)(n + 1) * 8);
-    const int32_t* dnb = st.in(SLOT_MASKS, nbrs, (size_t)e * 4);
-    int64_t* droot = st.out(SLOT_OUT0, root, (size_t)n * 8);
-    int64_t* dorder = st.out(SLOT_CVS_ORDER, order, (size_t)n * 8);
-    int64_t* dcoffs = st.out(SLOT_CVS_COFFS, coffs, (size_t)(n + 1) * 8);
-    uint8_t* dflags = st.out(SLOT_CVS_FLAGS, flags, (size_t)n);
+    const int64_t* dcls = st.in(classes, (size_t)n * 8);
+    const int64_t* doffs = st.in(offsets, (size_t)(n + 1) * 8);
+    const int32_t* dnb = st.in(nbrs, (size_t)e * 4);
+    int64_t* droot = st.out(root, (size_t)n * 8);
+    int64_t* dorder = st.out(order, (size_t)n * 8);
+    int64_t* dcoffs = st.out(coffs, (size_t)(n + 1) * 8);
+    uint8_t* dflags = st.out(flags, (size_t)n);
     if (!st.rc) st.rc = f3d_flood_order_dev(ctx, dcls, n, doffs, dnb, inst, ninst, droot, dorder, dcoffs, dflags, stats, ctx->stream);
     return st.finish();
 }
@@ -1275,7 +1317,7 @@ int f3d_color_segment_dev(f3d_ctx* ctx, const void* colors, f3d_dtype dtype, int
                           int64_t* ids, const int64_t* seeds, int64_t nseeds, const double threshold[3], const int64_t* neutral_ids,
                           int nneutral, int max_level, int64_t* accepted_dev, void* stream) {
     int rc = enter(ctx); if (rc) return rc;
-    if (n < 0 || n > 0x7fffffffLL || nseeds < 0 || (dtype != F3D_F64 && dtype != F3D_F32) ||
+    if (n < 0 || n > 0x7fffffffLL || nseeds < 0 || !dtype_ok(dtype) ||
         (n > 0 && nseeds > 0 && (!colors || !offsets || !ids || !seeds)))
         return fail(ctx, F3D_ERR_INVALID, "color_segment: bad arguments (n < 2^31, float64 or float32 colours)");
     f3d_color_args a;
@@ -1299,7 +1341,7 @@ int f3d_color_segment(f3d_ctx* ctx, const void* colors, f3d_dtype dtype, int64_t
                       int nneutral, int max_level, int64_t* accepted) {
     int rc = enter(ctx); if (rc) return rc;
     if (accepted) *accepted = 0;
-    if (n < 0 || nseeds < 0 || (dtype != F3D_F64 && dtype != F3D_F32) || (n > 0 && nseeds > 0 && (!colors || !offsets || !ids || !seeds)))
+    if (n < 0 || nseeds < 0 || !dtype_ok(dtype) || (n > 0 && nseeds > 0 && (!colors || !offsets || !ids || !seeds)))
         return fail(ctx, F3D_ERR_INVALID, "color_segment: bad arguments (float64 or float32 colours)");
     f3d_color_args a;
     if ((rc = color_args(ctx, threshold, neutral_ids, nneutral, max_level, &a))) return rc;
@@ -1310,12 +1352,12 @@ int f3d_color_segment(f3d_ctx* ctx, const void* colors, f3d_dtype dtype, int64_t
     const int64_t e = offsets[n];
     if (e < 0 || (e > 0 && !nbrs)) return fail(ctx, F3D_ERR_INVALID, "color_segment: bad adjacency");
     staging st(ctx);
-    const void* dclr = st.in(SLOT_XYZ, (const char*)colors, xyz_bytes(dtype, n));
-    const int64_t* doffs = st.in(SLOT_OUT1, offsets, (size_t)(n + 1) * 8);
-    const int32_t* dnb = st.in(SLOT_MASKS, nbrs, (size_t)e * 4);
-    const int64_t* dseeds = st.in(SLOT_CVS_SEEDS, seeds, (size_t)nseeds * 8);
-    int64_t* dids = st.inout(SLOT_OUT0, ids, (size_t)n * 8);
-    int64_t* dacc = (int64_t*)st.slot(SLOT_CVS_STATS, 16);
+    const void* dclr = st.in((const char*)colors, xyz_bytes(dtype, n));
+    const int64_t* doffs = st.in(offsets, (size_t)(n + 1) * 8);
+    const int32_t* dnb = st.in(nbrs, (size_t)e * 4);
+    const int64_t* dseeds = st.in(seeds, (size_t)nseeds * 8);
+    int64_t* dids = st.inout(ids, (size_t)n * 8);
+    int64_t* dacc = (int64_t*)st.slot(16);
     if (!st.rc) st.rc = hipMemsetAsync(dacc, 0, 8, ctx->stream) == hipSuccess ? F3D_OK : fail(ctx, F3D_ERR_HIP, "color_segment: memset");
     st.back(accepted, dacc, accepted ? 8 : 0);
     if (!st.rc) st.rc = f3d_color_segment_dev(ctx, dclr, dtype, n, doffs, dnb, dids, dseeds, nseeds, threshold, neutral_ids, nneutral,
@@ -1329,18 +1371,13 @@ int f3d_color_segment(f3d_ctx* ctx, const void* colors, f3d_dtype dtype, int64_t
 int f3d_ctx_reserve_refine(f3d_ctx* ctx, int64_t n) {
     int rc = enter(ctx); if (rc) return rc;
     if (n < 0 || n > F3D_GROW_MAX_POINTS) return fail(ctx, F3D_ERR_INVALID, "ctx_reserve_refine: bad arguments (n <= 2^31 - 2049)");
-    const int strict = ctx->strict;
-    ctx->strict = 0;
-    void* p;
-    rc = ensure(ctx, SLOT_GROW, f3d_grow_scratch_bytes(n), &p);
-    ctx->strict = strict;
-    return rc;
+    return reserve(ctx, {{SLOT_GROW, f3d_grow_scratch_bytes(n)}});
 }
 
 static int grow_args(f3d_ctx* ctx, f3d_dtype dtype, int nchan, int64_t n, int64_t nseeds, const double* sma0, int64_t npts0, int seeds_given,
                      const double* threshold, int max_level, f3d_grow_args* a) {
     if (n < 0 || n > F3D_GROW_MAX_POINTS || nseeds < 0 || npts0 < 0 || !sma0 || !threshold ||
-        !((nchan == 1 && dtype == F3D_F64) || (nchan == 3 && (dtype == F3D_F64 || dtype == F3D_F32))))
+        !((nchan == 1 && dtype == F3D_F64) || (nchan == 3 && dtype_ok(dtype))))
         return fail(ctx, F3D_ERR_INVALID, "region_grow: bad arguments (n <= 2^31 - 2049; float64 [n, 1], or float64 / float32 [n, 3] values)");
     for (int c = 0; c < 3; ++c) { a->thr[c] = c < nchan ? threshold[c] : 0; a->sma0[c] = c < nchan ? sma0[c] : 0; }
     a->npts0 = npts0;
@@ -1381,12 +1418,12 @@ int f3d_region_grow(f3d_ctx* ctx, const void* values, f3d_dtype dtype, int nchan
     const int64_t e = offsets[n];
     if (e < 0 || (e > 0 && !nbrs)) return fail(ctx, F3D_ERR_INVALID, "region_grow: bad adjacency");
     staging st(ctx);
-    const void* dval = st.in(SLOT_XYZ, (const char*)values, (size_t)n * nchan * (dtype == F3D_F64 ? 8 : 4));
-    const int64_t* doffs = st.in(SLOT_OUT1, offsets, (size_t)(n + 1) * 8);
-    const int32_t* dnb = st.in(SLOT_MASKS, nbrs, (size_t)e * 4);
-    const int64_t* dseeds = st.in(SLOT_CVS_SEEDS, seeds, (size_t)nseeds * 8);
-    int64_t* dcl = st.out(SLOT_OUT0, cluster, (size_t)n * 8);
-    int64_t* dcount = st.out(SLOT_CVS_STATS, count, 8);
+    const void* dval = st.in((const char*)values, (size_t)n * nchan * (dtype == F3D_F64 ? 8 : 4));
+    const int64_t* doffs = st.in(offsets, (size_t)(n + 1) * 8);
+    const int32_t* dnb = st.in(nbrs, (size_t)e * 4);
+    const int64_t* dseeds = st.in(seeds, (size_t)nseeds * 8);
+    int64_t* dcl = st.out(cluster, (size_t)n * 8);
+    int64_t* dcount = st.out(count, 8);
     if (!st.rc) st.rc = f3d_region_grow_dev(ctx, dval, dtype, nchan, n, doffs, dnb, dseeds, nseeds, sma0, npts0, seeds_given, threshold,
                                             max_level, dcl, dcount, ctx->stream);
     return st.finish(F3D_DEVERR_GROW);
@@ -1405,8 +1442,8 @@ int f3d_plane_distance(f3d_ctx* ctx, const double* points, int64_t n, const doub
     if (n < 0 || !plane_point || !normal || (n > 0 && (!points || !out))) return fail(ctx, F3D_ERR_INVALID, "plane_distance: bad arguments");
     if (n == 0) return F3D_OK;
     staging st(ctx);
-    const double* dpts = st.in(SLOT_XYZ, points, (size_t)n * 24);
-    double* dout = st.out(SLOT_OUT0, out, (size_t)n * 8);
+    const double* dpts = st.in(points, (size_t)n * 24);
+    double* dout = st.out(out, (size_t)n * 8);
     if (!st.rc) st.rc = f3d_plane_distance_dev(ctx, dpts, n, plane_point, normal, dout, ctx->stream);
     return st.finish();
 }
@@ -1421,21 +1458,23 @@ static bool quads_args_ok(int64_t n, int k, int64_t nv, int64_t nt) {
 int f3d_ctx_reserve_quads(f3d_ctx* ctx, int64_t n, int k, int64_t nt) {
     int rc = enter(ctx); if (rc) return rc;
     if (!quads_args_ok(n, k, 0, nt)) return fail(ctx, F3D_ERR_INVALID, "ctx_reserve_quads: bad arguments");
-    const int strict = ctx->strict;
-    ctx->strict = 0;
-    void* p;
-    rc = ensure(ctx, SLOT_QUADS, f3d_quads_scratch_bytes(n, k, nt), &p);
-    ctx->strict = strict;
-    return rc;
+    return reserve(ctx, {{SLOT_QUADS, f3d_quads_scratch_bytes(n, k, nt)}});
+}
+
+// the argument test of f3d_door_window_quads and of its _dev twin
+static int quads_check(f3d_ctx* ctx, const double* points, int64_t n, const int64_t* ids, const int64_t* inst, int k, const double* verts,
+                       int64_t nv, const int64_t* tris, int64_t nt, const double* quads, const int32_t* status, const int32_t* tri) {
+    if (!quads_args_ok(n, k, nv, nt) || (n > 0 && (!points || !ids)) || (k > 0 && (!inst || !quads || !status || !tri)) ||
+        (nv > 0 && !verts) || (nt > 0 && !tris))
+        return fail(ctx, F3D_ERR_INVALID, "door_window_quads: bad arguments (n, nt < 2^31, k <= %d)", F3D_QUADS_MAX_INST);
+    return F3D_OK;
 }
 
 int f3d_door_window_quads_dev(f3d_ctx* ctx, const double* points, int64_t n, const int64_t* ids, const int64_t* inst, int k,
                               const double* verts, int64_t nv, const int64_t* tris, int64_t nt, double* quads, int32_t* status,
                               int32_t* tri, double* normals, void* stream) {
     int rc = enter(ctx); if (rc) return rc;
-    if (!quads_args_ok(n, k, nv, nt) || (n > 0 && (!points || !ids)) || (k > 0 && (!inst || !quads || !status || !tri)) ||
-        (nv > 0 && !verts) || (nt > 0 && !tris))
-        return fail(ctx, F3D_ERR_INVALID, "door_window_quads: bad arguments (n, nt < 2^31, k <= %d)", F3D_QUADS_MAX_INST);
+    if ((rc = quads_check(ctx, points, n, ids, inst, k, verts, nv, tris, nt, quads, status, tri))) return rc;
     void* scratch;
     if ((rc = ensure(ctx, SLOT_QUADS, f3d_quads_scratch_bytes(n, k, nt), &scratch))) return rc;
     F3D_HIP(ctx, f3d_launch_door_window_quads(points, n, ids, inst, k, verts, nv, tris, nt, quads, status, tri, normals, scratch,
@@ -1447,26 +1486,17 @@ int f3d_door_window_quads(f3d_ctx* ctx, const double* points, int64_t n, const i
                           const double* verts, int64_t nv, const int64_t* tris, int64_t nt, double* quads, int32_t* status,
                           int32_t* tri, double* normals) {
     int rc = enter(ctx); if (rc) return rc;
-    if (!quads_args_ok(n, k, nv, nt) || (n > 0 && (!points || !ids)) || (k > 0 && (!inst || !quads || !status || !tri)) ||
-        (nv > 0 && !verts) || (nt > 0 && !tris))
-        return fail(ctx, F3D_ERR_INVALID, "door_window_quads: bad arguments (n, nt < 2^31, k <= %d)", F3D_QUADS_MAX_INST);
-    const size_t qbytes = (size_t)k * 96, sbytes = ((size_t)k * 4 + 7) & ~(size_t)7;
+    if ((rc = quads_check(ctx, points, n, ids, inst, k, verts, nv, tris, nt, quads, status, tri))) return rc;
     staging st(ctx);
-    const double* dpts = st.in(SLOT_XYZ, points, (size_t)n * 24);
-    const int64_t* dids = st.in(SLOT_AUX0, ids, (size_t)n * 8);
-    const double* dverts = st.in(SLOT_AUX1, verts, (size_t)nv * 24);
-    const int64_t* dtris = st.in(SLOT_MASKS, tris, (size_t)nt * 24);
-    double* dnrm = st.out(SLOT_OUT1, normals, (size_t)nt * 24);
-    char* dout = (char*)st.slot(SLOT_QUADS_OUT, qbytes + 2 * sbytes + (size_t)k * 8);     // quads, status, tri, then the ids wanted
-    if (st.rc) return st.rc;
-    double* dquads = (double*)dout;
-    int32_t* dstatus = (int32_t*)(dout + qbytes);
-    int32_t* dtri = (int32_t*)(dout + qbytes + sbytes);
-    int64_t* dinst = (int64_t*)(dout + qbytes + 2 * sbytes);
-    st.put(dinst, inst, (size_t)k * 8);
-    st.back(quads, dquads, qbytes);
-    st.back(status, dstatus, (size_t)k * 4);
-    st.back(tri, dtri, (size_t)k * 4);
+    const double* dpts = st.in(points, (size_t)n * 24);
+    const int64_t* dids = st.in(ids, (size_t)n * 8);
+    const int64_t* dinst = st.in(inst, (size_t)k * 8);
+    const double* dverts = st.in(verts, (size_t)nv * 24);
+    const int64_t* dtris = st.in(tris, (size_t)nt * 24);
+    double* dquads = st.out(quads, (size_t)k * 96);
+    int32_t* dstatus = st.out(status, (size_t)k * 4);
+    int32_t* dtri = st.out(tri, (size_t)k * 4);
+    double* dnrm = st.out(normals, (size_t)nt * 24);
     if (!st.rc) st.rc = f3d_door_window_quads_dev(ctx, dpts, n, dids, dinst, k, dverts, nv, dtris, nt, dquads, dstatus, dtri, dnrm,
                                                   ctx->stream);
     return st.finish(F3D_DEVERR_QUADS);
@@ -1477,7 +1507,7 @@ int f3d_door_window_quads(f3d_ctx* ctx, const double* points, int64_t n, const i
 // ---------------------------------------------------------------------------------------------
 static bool mesh_args_ok(int64_t nv, int64_t nt, int itype, int vdtype) {
     return nv >= 0 && nv <= 0x7fffffffLL && nt >= 0 && 3 * nt <= 0x7fffffffLL && (itype == F3D_I64 || itype == F3D_I32) &&
-           (vdtype == F3D_F64 || vdtype == F3D_F32);
+           dtype_ok(vdtype);
 }
 #define F3D_MESH_BAD "bad arguments (nv < 2^31, 3 * nt < 2^31, int64 / int32 triangles, float64 / float32 vertices)"
 
@@ -1486,18 +1516,17 @@ static size_t tri_bytes(int itype, int64_t nt) { return (size_t)nt * 3 * (itype 
 int f3d_ctx_reserve_mesh(f3d_ctx* ctx, int64_t nv, int64_t nt) {
     int rc = enter(ctx); if (rc) return rc;
     if (!mesh_args_ok(nv, nt, F3D_I64, F3D_F64)) return fail(ctx, F3D_ERR_INVALID, "ctx_reserve_mesh: " F3D_MESH_BAD);
-    const int strict = ctx->strict;
-    ctx->strict = 0;
-    void* p;
-    rc = ensure(ctx, SLOT_MESH, f3d_mesh_scratch_bytes(nv, nt), &p);
-    ctx->strict = strict;
-    return rc;
+    return reserve(ctx, {{SLOT_MESH, f3d_mesh_scratch_bytes(nv, nt)}});
+}
+
+static bool mesh_vertex_map_bad(int64_t nv, int64_t nt, int itype, const void* tris, const void* offsets, const void* tri, const void* pos, const void* counts) {
+    return !mesh_args_ok(nv, nt, itype, F3D_F64) || !offsets || !counts || (nt > 0 && (!tris || !tri || !pos));
 }
 
 int f3d_mesh_vertex_map_dev(f3d_ctx* ctx, const void* tris, int itype, int64_t nt, int64_t nv, int64_t* offsets, int32_t* tri,
                             int8_t* pos, int64_t* counts, void* stream) {
     int rc = enter(ctx); if (rc) return rc;
-    if (!mesh_args_ok(nv, nt, itype, F3D_F64) || !offsets || !counts || (nt > 0 && (!tris || !tri || !pos)))
+    if (mesh_vertex_map_bad(nv, nt, itype, tris, offsets, tri, pos, counts))
         return fail(ctx, F3D_ERR_INVALID, "mesh_vertex_map: " F3D_MESH_BAD);
     void* scratch;
     if ((rc = ensure(ctx, SLOT_MESH, f3d_mesh_scratch_bytes(nv, nt), &scratch))) return rc;
@@ -1508,13 +1537,13 @@ int f3d_mesh_vertex_map_dev(f3d_ctx* ctx, const void* tris, int itype, int64_t n
 int f3d_mesh_vertex_map(f3d_ctx* ctx, const void* tris, int itype, int64_t nt, int64_t nv, int64_t* offsets, int32_t* tri,
                         int8_t* pos, int64_t* counts) {
     int rc = enter(ctx); if (rc) return rc;
-    if (!mesh_args_ok(nv, nt, itype, F3D_F64) || !offsets || !counts || (nt > 0 && (!tris || !tri || !pos)))
+    if (mesh_vertex_map_bad(nv, nt, itype, tris, offsets, tri, pos, counts))
         return fail(ctx, F3D_ERR_INVALID, "mesh_vertex_map: " F3D_MESH_BAD);
     f3d_carve c;
     const size_t o_tris = c.take(tri_bytes(itype, nt)), o_offs = c.take((size_t)(nv + 1) * 8), o_tri = c.take((size_t)nt * 12),
                  o_pos = c.take((size_t)nt * 3), o_cnt = c.take(32);
     staging st(ctx);
-    char* io = (char*)st.slot(SLOT_MESH_IO, c.off);
+    char* io = (char*)st.slot(c.off);
     if (st.rc) return st.rc;
     st.put(io + o_tris, tris, tri_bytes(itype, nt));
     st.back(offsets, io + o_offs, (size_t)(nv + 1) * 8);
@@ -1526,10 +1555,15 @@ int f3d_mesh_vertex_map(f3d_ctx* ctx, const void* tris, int itype, int64_t nt, i
     return st.finish(F3D_DEVERR_MESH);
 }
 
+static bool mesh_remove_faces_bad(int64_t nv, int64_t nt, int itype, const void* tris, const void* mask, const void* not_removed, const void* remaining, const void* old2new,
+                                  const void* counts) {
+    return !mesh_args_ok(nv, nt, itype, F3D_F64) || !counts || (nv > 0 && (!mask || !old2new)) || (nt > 0 && (!tris || !not_removed || !remaining));
+}
+
 int f3d_mesh_remove_faces_dev(f3d_ctx* ctx, const void* tris, int itype, int64_t nt, int64_t nv, const uint8_t* mask,
                               uint8_t* not_removed, void* remaining, int64_t* old2new, int64_t* counts, void* stream) {
     int rc = enter(ctx); if (rc) return rc;
-    if (!mesh_args_ok(nv, nt, itype, F3D_F64) || !counts || (nv > 0 && (!mask || !old2new)) || (nt > 0 && (!tris || !not_removed || !remaining)))
+    if (mesh_remove_faces_bad(nv, nt, itype, tris, mask, not_removed, remaining, old2new, counts))
         return fail(ctx, F3D_ERR_INVALID, "mesh_remove_faces: " F3D_MESH_BAD);
     void* scratch;
     if ((rc = ensure(ctx, SLOT_MESH, f3d_mesh_scratch_bytes(nv, nt), &scratch))) return rc;
@@ -1541,14 +1575,14 @@ int f3d_mesh_remove_faces_dev(f3d_ctx* ctx, const void* tris, int itype, int64_t
 int f3d_mesh_remove_faces(f3d_ctx* ctx, const void* tris, int itype, int64_t nt, int64_t nv, const uint8_t* mask,
                           uint8_t* not_removed, void* remaining, int64_t* old2new, int64_t* counts) {
     int rc = enter(ctx); if (rc) return rc;
-    if (!mesh_args_ok(nv, nt, itype, F3D_F64) || !counts || (nv > 0 && (!mask || !old2new)) || (nt > 0 && (!tris || !not_removed || !remaining)))
+    if (mesh_remove_faces_bad(nv, nt, itype, tris, mask, not_removed, remaining, old2new, counts))
         return fail(ctx, F3D_ERR_INVALID, "mesh_remove_faces: " F3D_MESH_BAD);
     f3d_carve c;
     const size_t tb = tri_bytes(itype, nt);
     const size_t o_tris = c.take(tb), o_mask = c.take((size_t)nv), o_nr = c.take((size_t)nt), o_rem = c.take(tb), o_o2n = c.take((size_t)nv * 8),
                  o_cnt = c.take(32);
     staging st(ctx);
-    char* io = (char*)st.slot(SLOT_MESH_IO, c.off);
+    char* io = (char*)st.slot(c.off);
     if (st.rc) return st.rc;
     st.put(io + o_tris, tris, tb);
     st.put(io + o_mask, mask, (size_t)nv);
@@ -1561,11 +1595,16 @@ int f3d_mesh_remove_faces(f3d_ctx* ctx, const void* tris, int itype, int64_t nt,
     return st.finish(F3D_DEVERR_MESH);
 }
 
+static bool mesh_keep_faces_bad(int64_t nv, int64_t nt, int itype, int vdtype, const void* verts, const void* tris, const void* mask, const void* out_verts,
+                                const void* out_tris, const void* counts) {
+    return !mesh_args_ok(nv, nt, itype, vdtype) || !counts || (nv > 0 && (!verts || !mask)) || (nt > 0 && (!tris || !out_tris)) ||
+           (nt > 0 && nv > 0 && !out_verts);
+}
+
 int f3d_mesh_keep_faces_dev(f3d_ctx* ctx, const void* verts, int vdtype, int64_t nv, const void* tris, int itype, int64_t nt,
                             const uint8_t* mask, void* out_verts, void* out_tris, int64_t* counts, void* stream) {
     int rc = enter(ctx); if (rc) return rc;
-    if (!mesh_args_ok(nv, nt, itype, vdtype) || !counts || (nv > 0 && (!verts || !mask)) || (nt > 0 && (!tris || !out_tris)) ||
-        (nt > 0 && nv > 0 && !out_verts))
+    if (mesh_keep_faces_bad(nv, nt, itype, vdtype, verts, tris, mask, out_verts, out_tris, counts))
         return fail(ctx, F3D_ERR_INVALID, "mesh_keep_faces: " F3D_MESH_BAD);
     void* scratch;
     if ((rc = ensure(ctx, SLOT_MESH, f3d_mesh_scratch_bytes(nv, nt), &scratch))) return rc;
@@ -1577,14 +1616,13 @@ int f3d_mesh_keep_faces_dev(f3d_ctx* ctx, const void* verts, int vdtype, int64_t
 int f3d_mesh_keep_faces(f3d_ctx* ctx, const void* verts, int vdtype, int64_t nv, const void* tris, int itype, int64_t nt,
                         const uint8_t* mask, void* out_verts, void* out_tris, int64_t* counts) {
     int rc = enter(ctx); if (rc) return rc;
-    if (!mesh_args_ok(nv, nt, itype, vdtype) || !counts || (nv > 0 && (!verts || !mask)) || (nt > 0 && (!tris || !out_tris)) ||
-        (nt > 0 && nv > 0 && !out_verts))
+    if (mesh_keep_faces_bad(nv, nt, itype, vdtype, verts, tris, mask, out_verts, out_tris, counts))
         return fail(ctx, F3D_ERR_INVALID, "mesh_keep_faces: " F3D_MESH_BAD);
     f3d_carve c;
     const size_t tb = tri_bytes(itype, nt), vb = xyz_bytes((f3d_dtype)vdtype, nv), ob = xyz_bytes((f3d_dtype)vdtype, 3 * nt < nv ? 3 * nt : nv);
     const size_t o_verts = c.take(vb), o_tris = c.take(tb), o_mask = c.take((size_t)nv), o_ov = c.take(ob), o_ot = c.take(tb), o_cnt = c.take(32);
     staging st(ctx);
-    char* io = (char*)st.slot(SLOT_MESH_IO, c.off);
+    char* io = (char*)st.slot(c.off);
     if (st.rc) return st.rc;
     st.put(io + o_verts, verts, vb);
     st.put(io + o_tris, tris, tb);
@@ -1597,11 +1635,16 @@ int f3d_mesh_keep_faces(f3d_ctx* ctx, const void* verts, int vdtype, int64_t nv,
     return st.finish(F3D_DEVERR_MESH);
 }
 
+static bool mesh_triangle_clusters_bad(int64_t nv, int64_t nt, int itype, int vdtype, const void* verts, const void* tris, const void* clusters, const void* cluster_n,
+                                       const void* cluster_area, const void* counts) {
+    return !mesh_args_ok(nv, nt, itype, vdtype) || !counts || (nv > 0 && !verts) || (nt > 0 && (!tris || !clusters || !cluster_n || !cluster_area));
+}
+
 int f3d_mesh_triangle_clusters_dev(f3d_ctx* ctx, const void* verts, int vdtype, int64_t nv, const void* tris, int itype,
                                    int64_t nt, int32_t* clusters, int64_t* cluster_n, double* cluster_area, double* tri_area,
                                    int64_t* counts, void* stream) {
     int rc = enter(ctx); if (rc) return rc;
-    if (!mesh_args_ok(nv, nt, itype, vdtype) || !counts || (nv > 0 && !verts) || (nt > 0 && (!tris || !clusters || !cluster_n || !cluster_area)))
+    if (mesh_triangle_clusters_bad(nv, nt, itype, vdtype, verts, tris, clusters, cluster_n, cluster_area, counts))
         return fail(ctx, F3D_ERR_INVALID, "mesh_triangle_clusters: " F3D_MESH_BAD);
     void* scratch;
     if ((rc = ensure(ctx, SLOT_MESH, f3d_mesh_scratch_bytes(nv, nt), &scratch))) return rc;
@@ -1613,14 +1656,14 @@ int f3d_mesh_triangle_clusters_dev(f3d_ctx* ctx, const void* verts, int vdtype, 
 int f3d_mesh_triangle_clusters(f3d_ctx* ctx, const void* verts, int vdtype, int64_t nv, const void* tris, int itype, int64_t nt,
                                int32_t* clusters, int64_t* cluster_n, double* cluster_area, double* tri_area, int64_t* counts) {
     int rc = enter(ctx); if (rc) return rc;
-    if (!mesh_args_ok(nv, nt, itype, vdtype) || !counts || (nv > 0 && !verts) || (nt > 0 && (!tris || !clusters || !cluster_n || !cluster_area)))
+    if (mesh_triangle_clusters_bad(nv, nt, itype, vdtype, verts, tris, clusters, cluster_n, cluster_area, counts))
         return fail(ctx, F3D_ERR_INVALID, "mesh_triangle_clusters: " F3D_MESH_BAD);
     f3d_carve c;
     const size_t tb = tri_bytes(itype, nt), vb = xyz_bytes((f3d_dtype)vdtype, nv);
     const size_t o_verts = c.take(vb), o_tris = c.take(tb), o_cl = c.take((size_t)nt * 4), o_n = c.take((size_t)nt * 8), o_a = c.take((size_t)nt * 8),
                  o_ta = c.take((size_t)nt * 8), o_cnt = c.take(32);
     staging st(ctx);
-    char* io = (char*)st.slot(SLOT_MESH_IO, c.off);
+    char* io = (char*)st.slot(c.off);
     if (st.rc) return st.rc;
     st.put(io + o_verts, verts, vb);
     st.put(io + o_tris, tris, tb);
@@ -1635,11 +1678,16 @@ int f3d_mesh_triangle_clusters(f3d_ctx* ctx, const void* verts, int vdtype, int6
     return st.finish(F3D_DEVERR_MESH);
 }
 
+static bool mesh_clean_bad(int64_t nv, int64_t nt, int itype, int vdtype, const void* verts, const void* tris, const void* new_verts, const void* new_tris,
+                           const void* kept_v, const void* kept_t, const void* counts) {
+    return !mesh_args_ok(nv, nt, itype, vdtype) || !counts || (nv > 0 && (!verts || !new_verts || !kept_v)) || (nt > 0 && (!tris || !new_tris || !kept_t));
+}
+
 int f3d_mesh_clean_dev(f3d_ctx* ctx, const void* verts, int vdtype, int64_t nv, const void* tris, int itype, int64_t nt,
                        const uint8_t* remove_mask, int64_t min_triangles, double min_area, void* new_verts, void* new_tris,
                        uint8_t* kept_v, uint8_t* kept_t, int64_t* counts, void* stream) {
     int rc = enter(ctx); if (rc) return rc;
-    if (!mesh_args_ok(nv, nt, itype, vdtype) || !counts || (nv > 0 && (!verts || !new_verts || !kept_v)) || (nt > 0 && (!tris || !new_tris || !kept_t)))
+    if (mesh_clean_bad(nv, nt, itype, vdtype, verts, tris, new_verts, new_tris, kept_v, kept_t, counts))
         return fail(ctx, F3D_ERR_INVALID, "mesh_clean: " F3D_MESH_BAD);
     void* scratch;
     if ((rc = ensure(ctx, SLOT_MESH, f3d_mesh_scratch_bytes(nv, nt), &scratch))) return rc;
@@ -1652,14 +1700,14 @@ int f3d_mesh_clean(f3d_ctx* ctx, const void* verts, int vdtype, int64_t nv, cons
                    const uint8_t* remove_mask, int64_t min_triangles, double min_area, void* new_verts, void* new_tris,
                    uint8_t* kept_v, uint8_t* kept_t, int64_t* counts) {
     int rc = enter(ctx); if (rc) return rc;
-    if (!mesh_args_ok(nv, nt, itype, vdtype) || !counts || (nv > 0 && (!verts || !new_verts || !kept_v)) || (nt > 0 && (!tris || !new_tris || !kept_t)))
+    if (mesh_clean_bad(nv, nt, itype, vdtype, verts, tris, new_verts, new_tris, kept_v, kept_t, counts))
         return fail(ctx, F3D_ERR_INVALID, "mesh_clean: " F3D_MESH_BAD);
     f3d_carve c;
     const size_t tb = tri_bytes(itype, nt), vb = xyz_bytes((f3d_dtype)vdtype, nv);
     const size_t o_verts = c.take(vb), o_tris = c.take(tb), o_mask = c.take((size_t)nv), o_nv = c.take(vb), o_nt = c.take(tb),
                  o_kv = c.take((size_t)nv), o_kt = c.take((size_t)nt), o_cnt = c.take(32);
     staging st(ctx);
-    char* io = (char*)st.slot(SLOT_MESH_IO, c.off);
+    char* io = (char*)st.slot(c.off);
     if (st.rc) return st.rc;
     st.put(io + o_verts, verts, vb);
     st.put(io + o_tris, tris, tb);
@@ -1703,13 +1751,13 @@ int f3d_patch_owner(f3d_ctx* ctx, const int32_t* uv, int64_t m, int h, int w, in
         return fail(ctx, F3D_ERR_INVALID, "patch_owner: bad arguments");
     if (npx == 0) return F3D_OK;
     staging st(ctx);
-    const int32_t* duv = st.in(SLOT_AUX0, uv, (size_t)m * 8);
-    const double* dsp = st.in(SLOT_XYZ, seed_pts, (size_t)m * 24);
-    const double* dsn = st.in(SLOT_OUT1, seed_nrm, (size_t)m * 24);
-    const double* dqp = st.in(SLOT_MASKS, q_pts, (size_t)npx * 24);
-    const double* dqn = st.in(SLOT_VIEWS, q_nrm, (size_t)npx * 24);
-    const uint8_t* dfree = st.in(SLOT_AUX1, free_px, (size_t)npx);
-    int32_t* down = st.out(SLOT_OUT0, owner, (size_t)npx * 4);
+    const int32_t* duv = st.in(uv, (size_t)m * 8);
+    const double* dsp = st.in(seed_pts, (size_t)m * 24);
+    const double* dsn = st.in(seed_nrm, (size_t)m * 24);
+    const double* dqp = st.in(q_pts, (size_t)npx * 24);
+    const double* dqn = st.in(q_nrm, (size_t)npx * 24);
+    const uint8_t* dfree = st.in(free_px, (size_t)npx);
+    int32_t* down = st.out(owner, (size_t)npx * 4);
     if (!st.rc) st.rc = f3d_patch_owner_dev(ctx, duv, m, h, w, half, radius, min_cosine, dsp, dsn, dqp, dqn, dfree, down, ctx->stream);
     return st.finish();
 }
@@ -1726,15 +1774,15 @@ int f3d_patch_match(f3d_ctx* ctx, const int32_t* uv, int64_t m, int h, int w, in
         return fail(ctx, F3D_ERR_INVALID, "patch_match: bad arguments");
     if (npx == 0) return F3D_OK;
     staging st(ctx);
-    const int32_t* duv = st.in(SLOT_AUX0, uv, (size_t)m * 8);
-    const double* dsp = st.in(SLOT_XYZ, seed_pts, (size_t)m * 24);
-    const double* dsn = st.in(SLOT_OUT1, seed_nrm, (size_t)m * 24);
-    const double* dqp = st.in(SLOT_MASKS, q_pts, (size_t)npx * 24);
-    const double* dqn = st.in(SLOT_VIEWS, q_nrm, (size_t)npx * 24);
-    const double* dqc = st.in(SLOT_TILED_MASKS, q_clr, (size_t)npx * 24);
-    const uint8_t* dfree = st.in(SLOT_AUX1, free_px, (size_t)npx);
-    int32_t* down = st.out(SLOT_OUT0, owner, (size_t)npx * 4);
-    char* dsums = (char*)st.slot(SLOT_GRAPH, (size_t)m * 76 + 16);              // sums [m, 9], then the counts (16-byte aligned)
+    const int32_t* duv = st.in(uv, (size_t)m * 8);
+    const double* dsp = st.in(seed_pts, (size_t)m * 24);
+    const double* dsn = st.in(seed_nrm, (size_t)m * 24);
+    const double* dqp = st.in(q_pts, (size_t)npx * 24);
+    const double* dqn = st.in(q_nrm, (size_t)npx * 24);
+    const double* dqc = st.in(q_clr, (size_t)npx * 24);
+    const uint8_t* dfree = st.in(free_px, (size_t)npx);
+    int32_t* down = st.out(owner, (size_t)npx * 4);
+    char* dsums = (char*)st.slot((size_t)m * 76 + 16);              // sums [m, 9], then the counts (16-byte aligned)
     if (st.rc) return st.rc;
     int32_t* dcnt = (int32_t*)(dsums + (((size_t)m * 72 + 15) & ~(size_t)15));
     st.back(sums, dsums, (size_t)m * 72);
@@ -1755,13 +1803,13 @@ int f3d_patch_seeds_sums(f3d_ctx* ctx, const double* pts, const double* nrm, con
     if (rounds) *rounds = 0;
     if (npx == 0) return F3D_OK;
     staging st(ctx);
-    const double* dp = st.in(SLOT_MASKS, pts, (size_t)npx * 24);
-    const double* dn = st.in(SLOT_VIEWS, nrm, (size_t)npx * 24);
-    const double* dc = st.in(SLOT_TILED_MASKS, clr, (size_t)npx * 24);
-    const int32_t* dprio = st.in(SLOT_AUX0, prio, (size_t)npx * 4);
-    const uint8_t* dfree = st.in(SLOT_AUX1, free_px, (size_t)npx);
-    int32_t* down = st.out(SLOT_OUT0, owner, (size_t)npx * 4);
-    char* dsums = (char*)st.slot(SLOT_GRAPH, (size_t)npx * 76 + 16);            // sums [h*w, 9], then the counts (16-byte aligned)
+    const double* dp = st.in(pts, (size_t)npx * 24);
+    const double* dn = st.in(nrm, (size_t)npx * 24);
+    const double* dc = st.in(clr, (size_t)npx * 24);
+    const int32_t* dprio = st.in(prio, (size_t)npx * 4);
+    const uint8_t* dfree = st.in(free_px, (size_t)npx);
+    int32_t* down = st.out(owner, (size_t)npx * 4);
+    char* dsums = (char*)st.slot((size_t)npx * 76 + 16);            // sums [h*w, 9], then the counts (16-byte aligned)
     if (st.rc) return st.rc;
     int32_t* dcnt = (int32_t*)(dsums + (((size_t)npx * 72 + 15) & ~(size_t)15));
     st.back(sums, dsums, (size_t)npx * 72);
@@ -1918,7 +1966,7 @@ int f3d_radius_graph_count_dev(f3d_ctx* ctx, const void* xyz, f3d_dtype dtype, i
     int rc = enter(ctx); if (rc) return rc;
     if (n < 0 || n > 0x7fffffffLL || !nnz || (n > 0 && (!xyz || !offsets)) || !(radius >= 0.0) || !(radius < 1e300))
         return fail(ctx, F3D_ERR_INVALID, "radius_graph: bad arguments (n < 2^31, finite radius >= 0)");
-    *nnz = 0; ctx->graph_n = -1;
+    *nnz = 0; ctx->graph_n = -1; ctx->graph_kept = false;
     if (n == 0) return F3D_OK;
     hipStream_t s = pick(ctx, stream);
     f3d_gridsearch gs;
@@ -1928,7 +1976,7 @@ int f3d_radius_graph_count_dev(f3d_ctx* ctx, const void* xyz, f3d_dtype dtype, i
     F3D_HIP(ctx, f3d_launch_graph_count(xyz, dtype, n, gs, scratch, offsets, s));
     F3D_HIP(ctx, hipMemcpyAsync(nnz, offsets + n, 8, hipMemcpyDeviceToHost, s));
     F3D_HIP(ctx, hipStreamSynchronize(s));
-    ctx->graph = gs; ctx->graph_n = n; ctx->graph_xyz = xyz;
+    ctx->graph = gs; ctx->graph_n = n;
     return F3D_OK;
 }
 
@@ -1937,7 +1985,7 @@ int f3d_radius_graph_fill_dev(f3d_ctx* ctx, int64_t n, const int64_t* offsets, i
     if (n != ctx->graph_n || n < 0) return fail(ctx, F3D_ERR_INVALID, "radius_graph_fill: call f3d_radius_graph_count for this cloud first");
     if (n == 0) return F3D_OK;
     if (!offsets || !nbrs) return fail(ctx, F3D_ERR_INVALID, "radius_graph_fill: bad arguments");
-    F3D_HIP(ctx, f3d_launch_graph_fill(n, ctx->graph, ctx->slot[SLOT_GRAPH], offsets, nbrs, pick(ctx, stream)));
+    F3D_HIP(ctx, f3d_launch_graph_fill(n, ctx->graph, ctx->scratch[SLOT_GRAPH].p, offsets, nbrs, pick(ctx, stream)));
     return F3D_OK;
 }
 
@@ -1947,25 +1995,29 @@ int f3d_radius_graph_count(f3d_ctx* ctx, const void* xyz, f3d_dtype dtype, int64
     *nnz = 0;
     if (n == 0) { ctx->graph_n = 0; return F3D_OK; }
     staging st(ctx);
-    const void* dxyz = st.in(SLOT_XYZ, xyz, xyz_bytes(dtype, n));
-    int64_t* doffs = st.out(SLOT_OUT1, offsets, (size_t)(n + 1) * 8);   // f3d_radius_graph_fill reads them there
+    const void* dxyz = st.in(xyz, xyz_bytes(dtype, n));
+    int64_t* doffs = (int64_t*)st.keep(KEPT_GRAPH_OFFS, (size_t)(n + 1) * 8);   // f3d_radius_graph_fill reads them there
+    st.back(offsets, doffs, (size_t)(n + 1) * 8);
     if (!st.rc) st.rc = f3d_radius_graph_count_dev(ctx, dxyz, dtype, n, radius, doffs, nnz, ctx->stream);
-    return st.finish();
+    if ((rc = st.finish())) { ctx->graph_n = -1; return rc; }
+    ctx->graph_kept = true;
+    return F3D_OK;
 }
 
 int f3d_radius_graph_fill(f3d_ctx* ctx, int64_t n, int32_t* nbrs) {
     int rc = enter(ctx); if (rc) return rc;
-    if (n != ctx->graph_n || n < 0) return fail(ctx, F3D_ERR_INVALID, "radius_graph_fill: call f3d_radius_graph_count for this cloud first");
+    if (n != ctx->graph_n || n < 0 || (n > 0 && !ctx->graph_kept))
+        return fail(ctx, F3D_ERR_INVALID, "radius_graph_fill: call f3d_radius_graph_count for this cloud first");
     if (n == 0) return F3D_OK;
     hipStream_t s = ctx->stream;
     int64_t nnz = 0;
-    const int64_t* doffs = (const int64_t*)ctx->slot[SLOT_OUT1];           // left there by f3d_radius_graph_count
+    const int64_t* doffs = (const int64_t*)ctx->kept[KEPT_GRAPH_OFFS].p;   // left there by f3d_radius_graph_count
     F3D_HIP(ctx, hipMemcpyAsync(&nnz, doffs + n, 8, hipMemcpyDeviceToHost, s));
     F3D_HIP(ctx, hipStreamSynchronize(s));
     if (nnz == 0) return F3D_OK;
     if (!nbrs) return fail(ctx, F3D_ERR_INVALID, "radius_graph_fill: nbrs is NULL");
     staging st(ctx);
-    int32_t* dnb = st.out(SLOT_MASKS, nbrs, (size_t)nnz * 4);
+    int32_t* dnb = st.out(nbrs, (size_t)nnz * 4);
     if (!st.rc) st.rc = f3d_radius_graph_fill_dev(ctx, n, doffs, dnb, s);
     return st.finish();
 }
@@ -1976,9 +2028,9 @@ int f3d_radius_graph_fill(f3d_ctx* ctx, int64_t n, int32_t* nbrs) {
 int f3d_radius_query_count_dev(f3d_ctx* ctx, const void* data, f3d_dtype ddtype, int64_t m, const void* queries, f3d_dtype qdtype, int64_t n,
                                double radius, int64_t* offsets, int64_t* nnz, void* stream) {
     int rc = enter(ctx); if (rc) return rc;
-    ctx->qry_n = -1;
+    ctx->qry_n = -1; ctx->qry_kept = false;
     if (!nnz || m < 0 || m > 0x7fffffffLL || n < 0 || n > 0x7fffffffLL || (m > 0 && !data) || (n > 0 && (!queries || !offsets)) ||
-        (ddtype != F3D_F64 && ddtype != F3D_F32) || (qdtype != F3D_F64 && qdtype != F3D_F32) || radius >= 1e300)
+        !dtype_ok(ddtype) || !dtype_ok(qdtype) || radius >= 1e300)
         return fail(ctx, F3D_ERR_INVALID, "radius_query: bad arguments (m, n < 2^31, radius < 1e300)");
     if (m == 0) return fail(ctx, F3D_ERR_INVALID, "radius_query: the data set is empty (sklearn's KDTree raises ValueError)");
     *nnz = 0;
@@ -2004,7 +2056,7 @@ int f3d_radius_query_fill_dev(f3d_ctx* ctx, const void* queries, f3d_dtype qdtyp
         return fail(ctx, F3D_ERR_INVALID, "radius_query_fill: call f3d_radius_query_count for these queries first");
     if (n == 0) return F3D_OK;
     if (!offsets || !nbrs) return fail(ctx, F3D_ERR_INVALID, "radius_query_fill: bad arguments");
-    F3D_HIP(ctx, f3d_launch_query_fill(queries, qdtype, ctx->qry_m, n, ctx->qry, ctx->slot[SLOT_QRY], offsets, nbrs, pick(ctx, stream)));
+    F3D_HIP(ctx, f3d_launch_query_fill(queries, qdtype, ctx->qry_m, n, ctx->qry, ctx->scratch[SLOT_QRY].p, offsets, nbrs, pick(ctx, stream)));
     return F3D_OK;
 }
 
@@ -2013,30 +2065,34 @@ int f3d_radius_query_count(f3d_ctx* ctx, const void* data, f3d_dtype ddtype, int
     int rc = enter(ctx); if (rc) return rc;
     ctx->qry_n = -1;
     if (!nnz || m < 0 || n < 0 || (m > 0 && !data) || (n > 0 && (!queries || !offsets)) ||
-        (ddtype != F3D_F64 && ddtype != F3D_F32) || (qdtype != F3D_F64 && qdtype != F3D_F32))
+        !dtype_ok(ddtype) || !dtype_ok(qdtype))
         return fail(ctx, F3D_ERR_INVALID, "radius_query: bad arguments");
     staging st(ctx);
-    const void* ddata = st.in(SLOT_XYZ, data, xyz_bytes(ddtype, m));
-    const void* dq = st.in(SLOT_QRY_IN, queries, xyz_bytes(qdtype, n));        // f3d_radius_query_fill reads them there
-    int64_t* doffs = st.out(SLOT_QRY_OFFS, offsets, (size_t)(n + 1) * 8);      // and these
+    const void* ddata = st.in(data, xyz_bytes(ddtype, m));
+    void* dq = st.keep(KEPT_QRY_IN, xyz_bytes(qdtype, n));                         // f3d_radius_query_fill reads them there
+    st.put(dq, queries, xyz_bytes(qdtype, n));
+    int64_t* doffs = (int64_t*)st.keep(KEPT_QRY_OFFS, (size_t)(n + 1) * 8);        // and these
+    st.back(offsets, doffs, (size_t)(n + 1) * 8);
     if (!st.rc) st.rc = f3d_radius_query_count_dev(ctx, ddata, ddtype, m, dq, qdtype, n, radius, doffs, nnz, ctx->stream);
-    return st.finish();
+    if ((rc = st.finish())) { ctx->qry_n = -1; return rc; }
+    ctx->qry_kept = true;
+    return F3D_OK;
 }
 
 int f3d_radius_query_fill(f3d_ctx* ctx, int64_t n, int32_t* nbrs) {
     int rc = enter(ctx); if (rc) return rc;
-    if (n < 0 || n != ctx->qry_n || (n > 0 && ctx->qry_queries != ctx->slot[SLOT_QRY_IN]))
+    if (n < 0 || n != ctx->qry_n || (n > 0 && !ctx->qry_kept))
         return fail(ctx, F3D_ERR_INVALID, "radius_query_fill: call f3d_radius_query_count for these queries first");
     if (n == 0) return F3D_OK;
     hipStream_t s = ctx->stream;
     int64_t nnz = 0;
-    const int64_t* doffs = (const int64_t*)ctx->slot[SLOT_QRY_OFFS];         // left there by f3d_radius_query_count
+    const int64_t* doffs = (const int64_t*)ctx->kept[KEPT_QRY_OFFS].p;       // left there by f3d_radius_query_count
     F3D_HIP(ctx, hipMemcpyAsync(&nnz, doffs + n, 8, hipMemcpyDeviceToHost, s));
     F3D_HIP(ctx, hipStreamSynchronize(s));
     if (nnz == 0) return F3D_OK;
     if (!nbrs) return fail(ctx, F3D_ERR_INVALID, "radius_query_fill: nbrs is NULL");
     staging st(ctx);
-    int32_t* dnb = st.out(SLOT_MASKS, nbrs, (size_t)nnz * 4);
+    int32_t* dnb = st.out(nbrs, (size_t)nnz * 4);
     if (!st.rc) st.rc = f3d_radius_query_fill_dev(ctx, ctx->qry_queries, (f3d_dtype)ctx->qry_qdtype, n, doffs, dnb, s);
     return st.finish();
 }
@@ -2047,14 +2103,8 @@ int f3d_radius_query_fill(f3d_ctx* ctx, int64_t n, int32_t* nbrs) {
 int f3d_ctx_reserve_knn(f3d_ctx* ctx, int64_t m) {
     int rc = enter(ctx); if (rc) return rc;
     if (m < 0 || m > 0x7fffffffLL) return fail(ctx, F3D_ERR_INVALID, "ctx_reserve_knn: bad arguments");
-    const int strict = ctx->strict;
-    ctx->strict = 0;
-    void* p;
-    rc = ensure(ctx, SLOT_GRAPH_BBOX, f3d_graph_bbox_bytes(), &p);
-    if (!rc) rc = ensure(ctx, SLOT_KNN_FLAG, 64, &p);
-    if (!rc) rc = ensure(ctx, SLOT_KNN, f3d_graph_scratch_bytes(m, GRID_MAX_CELLS), &p);            // (any grid the radius allows)
-    ctx->strict = strict;
-    return rc;
+    return reserve(ctx, {{SLOT_GRAPH_BBOX, f3d_graph_bbox_bytes()}, {SLOT_KNN_FLAG, 64},
+                         {SLOT_KNN, f3d_graph_scratch_bytes(m, GRID_MAX_CELLS)}});                     // (any grid the radius allows)
 }
 
 // What f3d_knn_query_dev and f3d_transfer_labels_dev share: the argument checks, the one readback (the cloud's box and the queries'
@@ -2064,7 +2114,7 @@ static int knn_prepare(f3d_ctx* ctx, const char* op, const void* data, f3d_dtype
     *run = false;
     if (k < 1 || k > F3D_KNN_MAX_K) return fail(ctx, F3D_ERR_INVALID, "%s: k %d outside [1, %d]", op, k, F3D_KNN_MAX_K);
     if (m < 0 || m > 0x7fffffffLL || n < 0 || n > 0x7fffffffLL || (m > 0 && !data) || (n > 0 && !queries) ||
-        (ddtype != F3D_F64 && ddtype != F3D_F32) || (qdtype != F3D_F64 && qdtype != F3D_F32) || radius >= 1e300)
+        !dtype_ok(ddtype) || !dtype_ok(qdtype) || radius >= 1e300)
         return fail(ctx, F3D_ERR_INVALID, "%s: bad arguments (m, n < 2^31, radius < 1e300)", op);
     if (m == 0) return fail(ctx, F3D_ERR_INVALID, "%s: the data set is empty", op);
     if (n == 0) return F3D_OK;
@@ -2114,15 +2164,15 @@ int f3d_knn_query(f3d_ctx* ctx, const void* data, f3d_dtype ddtype, int64_t m, c
                   double radius, int32_t* idx, double* dist2, int32_t* counts) {
     int rc = enter(ctx); if (rc) return rc;
     if (k < 1 || k > F3D_KNN_MAX_K) return fail(ctx, F3D_ERR_INVALID, "knn_query: k %d outside [1, %d]", k, F3D_KNN_MAX_K);
-    if (m < 0 || n < 0 || (m > 0 && !data) || (n > 0 && (!queries || !idx)) || (ddtype != F3D_F64 && ddtype != F3D_F32) ||
-        (qdtype != F3D_F64 && qdtype != F3D_F32))
+    if (m < 0 || n < 0 || (m > 0 && !data) || (n > 0 && (!queries || !idx)) || !dtype_ok(ddtype) ||
+        !dtype_ok(qdtype))
         return fail(ctx, F3D_ERR_INVALID, "knn_query: bad arguments");
     staging st(ctx);
-    const void* ddata = st.in(SLOT_XYZ, data, xyz_bytes(ddtype, m));
-    const void* dq = st.in(SLOT_AUX0, queries, xyz_bytes(qdtype, n));
-    int32_t* didx = st.out(SLOT_OUT0, idx, (size_t)n * k * 4);
-    double* dd2 = st.out(SLOT_MASKS, dist2, (size_t)n * k * 8);       // (not SLOT_OUT1: f3d_radius_graph_count leaves its offsets there)
-    int32_t* dcnt = st.out(SLOT_AUX1, counts, (size_t)n * 4);
+    const void* ddata = st.in(data, xyz_bytes(ddtype, m));
+    const void* dq = st.in(queries, xyz_bytes(qdtype, n));
+    int32_t* didx = st.out(idx, (size_t)n * k * 4);
+    double* dd2 = st.out(dist2, (size_t)n * k * 8);
+    int32_t* dcnt = st.out(counts, (size_t)n * 4);
     if (!st.rc) st.rc = f3d_knn_query_dev(ctx, ddata, ddtype, m, dq, qdtype, n, k, radius, didx, dd2, dcnt, ctx->stream);
     return st.finish();
 }
@@ -2131,15 +2181,15 @@ int f3d_transfer_labels(f3d_ctx* ctx, const void* data, f3d_dtype ddtype, int64_
                         f3d_dtype qdtype, int64_t n, int k, double radius, int64_t fill, int64_t* out, int32_t* support) {
     int rc = enter(ctx); if (rc) return rc;
     if (k < 1 || k > F3D_KNN_MAX_K) return fail(ctx, F3D_ERR_INVALID, "transfer_labels: k %d outside [1, %d]", k, F3D_KNN_MAX_K);
-    if (m < 0 || n < 0 || (m > 0 && (!data || !labels)) || (n > 0 && (!queries || !out)) || (ddtype != F3D_F64 && ddtype != F3D_F32) ||
-        (qdtype != F3D_F64 && qdtype != F3D_F32))
+    if (m < 0 || n < 0 || (m > 0 && (!data || !labels)) || (n > 0 && (!queries || !out)) || !dtype_ok(ddtype) ||
+        !dtype_ok(qdtype))
         return fail(ctx, F3D_ERR_INVALID, "transfer_labels: bad arguments");
     staging st(ctx);
-    const void* ddata = st.in(SLOT_XYZ, data, xyz_bytes(ddtype, m));
-    const void* dq = st.in(SLOT_AUX0, queries, xyz_bytes(qdtype, n));
-    const int64_t* dlab = st.in(SLOT_AUX1, labels, (size_t)m * 8);
-    int64_t* dout = st.out(SLOT_OUT0, out, (size_t)n * 8);
-    int32_t* dsup = st.out(SLOT_MASKS, support, (size_t)n * 4);
+    const void* ddata = st.in(data, xyz_bytes(ddtype, m));
+    const void* dq = st.in(queries, xyz_bytes(qdtype, n));
+    const int64_t* dlab = st.in(labels, (size_t)m * 8);
+    int64_t* dout = st.out(out, (size_t)n * 8);
+    int32_t* dsup = st.out(support, (size_t)n * 4);
     if (!st.rc) st.rc = f3d_transfer_labels_dev(ctx, ddata, ddtype, m, dlab, dq, qdtype, n, k, radius, fill, dout, dsup, ctx->stream);
     return st.finish();
 }
@@ -2150,14 +2200,9 @@ int f3d_transfer_labels(f3d_ctx* ctx, const void* data, f3d_dtype ddtype, int64_
 int f3d_ctx_reserve_point_vote(f3d_ctx* ctx, int64_t m, int ncols) {
     int rc = enter(ctx); if (rc) return rc;
     if (m < 0 || m > 0x7fffffffLL || ncols <= 0) return fail(ctx, F3D_ERR_INVALID, "ctx_reserve_point_vote: bad arguments");
-    const int strict = ctx->strict;
-    ctx->strict = 0;
-    void* p;
-    rc = ensure(ctx, SLOT_GRAPH_BBOX, f3d_graph_bbox_bytes(), &p);
-    if (!rc) rc = ensure(ctx, SLOT_PVOTE, f3d_graph_scratch_bytes(m, GRID_MAX_CELLS), &p);          // (any grid the radius allows)
-    if (!rc) rc = ensure(ctx, SLOT_PVOTE_BITS, f3d_pvote_bits_bytes(m, ncols, f3d_pvote_group(m, ncols)), &p);
-    ctx->strict = strict;
-    return rc;
+    return reserve(ctx, {{SLOT_GRAPH_BBOX, f3d_graph_bbox_bytes()},
+                         {SLOT_PVOTE, f3d_graph_scratch_bytes(m, GRID_MAX_CELLS)},                     // (any grid the radius allows)
+                         {SLOT_PVOTE_BITS, f3d_pvote_bits_bytes(m, ncols, f3d_pvote_group(m, ncols))}});
 }
 
 int f3d_point_vote_frames_dev(f3d_ctx* ctx, const void* cloud, f3d_dtype cdtype, int64_t m, const void* queries, f3d_dtype qdtype,
@@ -2165,7 +2210,7 @@ int f3d_point_vote_frames_dev(f3d_ctx* ctx, const void* cloud, f3d_dtype cdtype,
     int rc = enter(ctx); if (rc) return rc;
     ctx->pv_partial = 0;
     if (m < 0 || m > 0x7fffffffLL || nframes < 0 || nframes > 0x3fffffffLL || hw < 0 || ncols <= 0 || (m > 0 && (!cloud || !votes)) ||
-        (nframes > 0 && hw > 0 && (!queries || !masks)) || (cdtype != F3D_F64 && cdtype != F3D_F32) || (qdtype != F3D_F64 && qdtype != F3D_F32) ||
+        (nframes > 0 && hw > 0 && (!queries || !masks)) || !dtype_ok(cdtype) || !dtype_ok(qdtype) ||
         radius >= 1e300)
         return fail(ctx, F3D_ERR_INVALID, "point_vote_frames: bad arguments (m < 2^31, F < 2^30, radius < 1e300)");
     if (m == 0) return fail(ctx, F3D_ERR_INVALID, "point_vote_frames: the cloud is empty (sklearn's KDTree raises ValueError)");
@@ -2213,13 +2258,13 @@ int f3d_point_vote_frames(f3d_ctx* ctx, const void* cloud, f3d_dtype cdtype, int
                           const uint8_t* masks, int64_t nframes, int64_t hw, double radius, double* votes, int ncols) {
     int rc = enter(ctx); if (rc) return rc;
     if (m < 0 || nframes < 0 || hw < 0 || ncols <= 0 || (m > 0 && (!cloud || !votes)) || (nframes > 0 && hw > 0 && (!queries || !masks)) ||
-        (cdtype != F3D_F64 && cdtype != F3D_F32) || (qdtype != F3D_F64 && qdtype != F3D_F32))
+        !dtype_ok(cdtype) || !dtype_ok(qdtype))
         return fail(ctx, F3D_ERR_INVALID, "point_vote_frames: bad arguments");
     staging st(ctx);
-    const void* dcloud = st.in(SLOT_XYZ, cloud, xyz_bytes(cdtype, m));
-    const void* dq = st.in(SLOT_AUX0, queries, xyz_bytes(qdtype, nframes * hw));
-    const uint8_t* dmask = st.in(SLOT_AUX1, masks, (size_t)(nframes * hw));
-    double* dvotes = st.inout(SLOT_OUT1, votes, (size_t)m * ncols * 8);
+    const void* dcloud = st.in(cloud, xyz_bytes(cdtype, m));
+    const void* dq = st.in(queries, xyz_bytes(qdtype, nframes * hw));
+    const uint8_t* dmask = st.in(masks, (size_t)(nframes * hw));
+    double* dvotes = st.inout(votes, (size_t)m * ncols * 8);
     if (st.rc) return st.rc;
     rc = f3d_point_vote_frames_dev(ctx, dcloud, cdtype, m, dq, qdtype, dmask, nframes, hw, radius, dvotes, ncols, ctx->stream);
     if (rc && !ctx->pv_partial) return rc;
@@ -2281,10 +2326,10 @@ int f3d_estimate_normals(f3d_ctx* ctx, const double* xyz, int64_t n, const doubl
     if (n == 0) return F3D_OK;
     if (!xyz || !normals || (orient && !cam_centre)) return fail(ctx, F3D_ERR_INVALID, "estimate_normals: bad arguments (NULL)");
     staging st(ctx);
-    const double* dxyz = st.in(SLOT_XYZ, xyz, (size_t)n * 24);
-    double* dnrm = st.out(SLOT_OUT0, normals, (size_t)n * 24);
-    int32_t* dcnt = st.out(SLOT_OUT1, counts, (size_t)n * 4);
-    int32_t* dnb = st.out(SLOT_MASKS, neighbours, (size_t)n * max_nn * 4);
+    const double* dxyz = st.in(xyz, (size_t)n * 24);
+    double* dnrm = st.out(normals, (size_t)n * 24);
+    int32_t* dcnt = st.out(counts, (size_t)n * 4);
+    int32_t* dnb = st.out(neighbours, (size_t)n * max_nn * 4);
     if (!st.rc) st.rc = f3d_estimate_normals_batch_dev(ctx, dxyz, 1, n, cam_centre, radius, max_nn, orient, dnrm, dcnt, dnb, ctx->stream);
     return st.finish();
 }
@@ -2364,11 +2409,11 @@ int f3d_obb_fit(f3d_ctx* ctx, const double* pts, const int64_t* start, int nfit,
     if (total < 0 || start[0] != 0 || (total > 0 && !pts)) return fail(ctx, F3D_ERR_INVALID, "obb_fit: start must run from 0 to the number of points");
     for (int k = 0; k < nfit; ++k) if (start[k + 1] < start[k]) return fail(ctx, F3D_ERR_INVALID, "obb_fit: start must be non-decreasing");
     staging st(ctx);
-    const double* dpts = st.in(SLOT_XYZ, pts, (size_t)total * 24);
-    const int64_t* dstart = st.in(SLOT_AUX0, start, (size_t)(nfit + 1) * 8);
-    double* dboxes = st.out(SLOT_OUT0, boxes, (size_t)nfit * sizeof(f3d_obb));
-    int32_t* dstatus = (int32_t*)st.slot(SLOT_AUX1, (size_t)nfit * 8);            // status, then the vertex counts
-    uint8_t* dvert = (uint8_t*)st.slot(SLOT_OUT1, (size_t)total);                 // written whether or not the caller wants it
+    const double* dpts = st.in(pts, (size_t)total * 24);
+    const int64_t* dstart = st.in(start, (size_t)(nfit + 1) * 8);
+    double* dboxes = st.out(boxes, (size_t)nfit * sizeof(f3d_obb));
+    int32_t* dstatus = (int32_t*)st.slot((size_t)nfit * 8);            // status, then the vertex counts
+    uint8_t* dvert = (uint8_t*)st.slot((size_t)total);                 // written whether or not the caller wants it
     if (st.rc) return st.rc;
     st.back(status, dstatus, (size_t)nfit * 4);
     st.back(isvert, dvert, (size_t)total);
@@ -2381,13 +2426,14 @@ int f3d_obb_fit(f3d_ctx* ctx, const double* pts, const int64_t* start, int nfit,
 int f3d_group_by_id(f3d_ctx* ctx, const int64_t* ids, int64_t n, int64_t nids, int32_t* order, int64_t* starts) {
     int rc = enter(ctx); if (rc) return rc;
     if (n < 0 || nids < 0 || !starts || (n > 0 && (!ids || !order))) return fail(ctx, F3D_ERR_INVALID, "group_by_id: bad arguments");
-    ctx->grp_n = -1;
+    ctx->grp_n = -1; ctx->grp_cloud = false;
     staging st(ctx);
-    const int64_t* dids = st.in(SLOT_OUT0, ids, (size_t)n * 8);
-    int32_t* dorder = (int32_t*)st.slot(SLOT_GRP_ORDER, (size_t)n * 4);
+    const int64_t* dids = st.in(ids, (size_t)n * 8);
+    int32_t* dorder = (int32_t*)st.keep(KEPT_GRP_ORDER, (size_t)n * 4);
     st.back(order, dorder, (size_t)n * 4);
-    uint32_t* dkeys = (uint32_t*)st.slot(SLOT_GRP_KEYS, (size_t)n * 4);
-    int64_t* dstarts = st.out(SLOT_GRP_STARTS, starts, (size_t)(nids + 2) * 8);
+    uint32_t* dkeys = (uint32_t*)st.keep(KEPT_GRP_KEYS, (size_t)n * 4);
+    int64_t* dstarts = (int64_t*)st.keep(KEPT_GRP_STARTS, (size_t)(nids + 2) * 8);
+    st.back(starts, dstarts, (size_t)(nids + 2) * 8);
     if (!st.rc) st.rc = f3d_group_by_id_dev(ctx, dids, n, nids, dorder, dkeys, dstarts, ctx->stream);
     if ((rc = st.finish())) return rc;
     ctx->grp_n = n; ctx->grp_nids = nids;
@@ -2399,42 +2445,37 @@ int f3d_obb_extremes(f3d_ctx* ctx, const void* xyz, f3d_dtype dtype, int64_t n, 
     if (n != ctx->grp_n || n < 0) return fail(ctx, F3D_ERR_INVALID, "obb_extremes: call f3d_group_by_id for this cloud first");
     const int64_t nids = ctx->grp_nids;
     if ((n > 0 && !xyz) || (nids > 0 && !extremes)) return fail(ctx, F3D_ERR_INVALID, "obb_extremes: bad arguments");
+    ctx->grp_cloud = false;
     staging st(ctx);
-    const void* dxyz = st.in(SLOT_XYZ, xyz, xyz_bytes(dtype, n));                  // stays there for f3d_obb_hull_filter
-    int32_t* dext = (int32_t*)st.slot(SLOT_OBB_CAND, (size_t)(n > nids * F3D_OBB_NDIR ? n : nids * F3D_OBB_NDIR) * 4 + (size_t)nids * 4);
-    st.back(extremes, dext, (size_t)nids * F3D_OBB_NDIR * 4);
-    if (!st.rc) st.rc = f3d_obb_extremes_dev(ctx, dxyz, dtype, n, (const int32_t*)ctx->slot[SLOT_GRP_ORDER], (const uint32_t*)ctx->slot[SLOT_GRP_KEYS],
-                                             nids, dext, ctx->stream);
+    void* dxyz = st.keep(KEPT_GRP_XYZ, xyz_bytes(dtype, n));                       // stays there for f3d_obb_hull_filter
+    st.put(dxyz, xyz, xyz_bytes(dtype, n));
+    int32_t* dext = st.out(extremes, (size_t)nids * F3D_OBB_NDIR * 4);
+    if (!st.rc) st.rc = f3d_obb_extremes_dev(ctx, dxyz, dtype, n, (const int32_t*)ctx->kept[KEPT_GRP_ORDER].p,
+                                             (const uint32_t*)ctx->kept[KEPT_GRP_KEYS].p, nids, dext, ctx->stream);
     if ((rc = st.finish())) return rc;
-    ctx->grp_dtype = dtype;
+    ctx->grp_dtype = dtype; ctx->grp_cloud = true;
     return F3D_OK;
 }
 
 int f3d_obb_hull_filter(f3d_ctx* ctx, int64_t n, const int32_t* facet_start, const double* facets, const double* margin, int32_t* cand,
                         int32_t* cand_count) {
     int rc = enter(ctx); if (rc) return rc;
-    if (n != ctx->grp_n || n < 0) return fail(ctx, F3D_ERR_INVALID, "obb_hull_filter: call f3d_group_by_id and f3d_obb_extremes for this cloud first");
+    if (n != ctx->grp_n || n < 0 || !ctx->grp_cloud)
+        return fail(ctx, F3D_ERR_INVALID, "obb_hull_filter: call f3d_group_by_id and f3d_obb_extremes for this cloud first");
     const int64_t nids = ctx->grp_nids;
     if (nids > 0 && (!facet_start || !margin || !cand_count)) return fail(ctx, F3D_ERR_INVALID, "obb_hull_filter: bad arguments");
     if (nids == 0) return F3D_OK;
     const int64_t nf = facet_start[nids];
     if (nf < 0 || (nf > 0 && !facets) || (n > 0 && !cand)) return fail(ctx, F3D_ERR_INVALID, "obb_hull_filter: bad facet table");
-    const size_t fbytes = (size_t)(nids + 1) * 4, foff = (fbytes + 7) & ~(size_t)7, ebytes = (size_t)nf * 32, mbytes = (size_t)nids * 8;
-    const size_t ncand = (size_t)(n > nids * F3D_OBB_NDIR ? n : nids * F3D_OBB_NDIR);
     staging st(ctx);
-    char* dfac = (char*)st.slot(SLOT_OBB_FACETS, foff + ebytes + mbytes + 64);          // facet starts, facet planes, margins
-    int32_t* dcand = (int32_t*)st.slot(SLOT_OBB_CAND, ncand * 4 + (size_t)nids * 4);    // candidates, then the count per instance
-    if (st.rc) return st.rc;
-    double* deq = (double*)(dfac + foff);
-    double* dmg = deq + 4 * (size_t)nf;
-    st.put(dfac, facet_start, fbytes);
-    st.put(deq, facets, ebytes);
-    st.put(dmg, margin, mbytes);
-    st.back(cand, dcand, (size_t)n * 4);
-    st.back(cand_count, dcand + ncand, (size_t)nids * 4);
-    if (!st.rc) st.rc = f3d_obb_hull_filter_dev(ctx, ctx->slot[SLOT_XYZ], (f3d_dtype)ctx->grp_dtype, n, (const int32_t*)ctx->slot[SLOT_GRP_ORDER],
-                                                (const uint32_t*)ctx->slot[SLOT_GRP_KEYS], (const int64_t*)ctx->slot[SLOT_GRP_STARTS], nids,
-                                                (const int32_t*)dfac, deq, dmg, dcand, dcand + ncand, ctx->stream);
+    const int32_t* dfs = st.in(facet_start, (size_t)(nids + 1) * 4);
+    const double* deq = st.in(facets, (size_t)nf * 32);
+    const double* dmg = st.in(margin, (size_t)nids * 8);
+    int32_t* dcand = st.out(cand, (size_t)n * 4);
+    int32_t* dcnt = st.out(cand_count, (size_t)nids * 4);
+    if (!st.rc) st.rc = f3d_obb_hull_filter_dev(ctx, ctx->kept[KEPT_GRP_XYZ].p, (f3d_dtype)ctx->grp_dtype, n, (const int32_t*)ctx->kept[KEPT_GRP_ORDER].p,
+                                                (const uint32_t*)ctx->kept[KEPT_GRP_KEYS].p, (const int64_t*)ctx->kept[KEPT_GRP_STARTS].p, nids,
+                                                dfs, deq, dmg, dcand, dcnt, ctx->stream);
     return st.finish();
 }
 
@@ -2445,7 +2486,7 @@ int f3d_obb_hull_filter(f3d_ctx* ctx, int64_t n, const int32_t* facet_start, con
 #define F3D_RENDER_BAD "bad arguments (n < 2^31, float64 / float32 cloud, h, w > 0, splat in [0, 8])"
 
 static bool render_args_ok(const void* xyz, f3d_dtype dtype, int64_t n, const void* views, int nviews, int h, int w, int splat) {
-    return n >= 0 && n <= 0x7fffffffLL && (dtype == F3D_F64 || dtype == F3D_F32) && nviews >= 0 && h > 0 && w > 0 && splat >= 0 && splat <= 8 &&
+    return n >= 0 && n <= 0x7fffffffLL && dtype_ok(dtype) && nviews >= 0 && h > 0 && w > 0 && splat >= 0 && splat <= 8 &&
            (n == 0 || xyz) && (nviews == 0 || views);
 }
 
@@ -2459,12 +2500,7 @@ static int render_pass_views(int nviews, int h, int w, int views_per_pass) {
 int f3d_ctx_reserve_render(f3d_ctx* ctx, int64_t n, int nviews, int h, int w) {
     int rc = enter(ctx); if (rc) return rc;
     if (n < 0 || n > 0x7fffffffLL || nviews < 0 || h <= 0 || w <= 0) return fail(ctx, F3D_ERR_INVALID, "ctx_reserve_render: bad arguments");
-    const int strict = ctx->strict;
-    ctx->strict = 0;
-    void* p;
-    rc = ensure(ctx, SLOT_ZKEY, (size_t)render_pass_views(nviews, h, w, 0) * h * w * 8, &p);
-    ctx->strict = strict;
-    return rc;
+    return reserve(ctx, {{SLOT_ZKEY, (size_t)render_pass_views(nviews, h, w, 0) * h * w * 8}});
 }
 
 int f3d_render_lookups_dev(f3d_ctx* ctx, const void* xyz, f3d_dtype dtype, int64_t n, const f3d_view* views_dev, int nviews, int h, int w,
@@ -2495,10 +2531,10 @@ int f3d_render_lookups(f3d_ctx* ctx, const void* xyz, f3d_dtype dtype, int64_t n
     if (nviews == 0) return F3D_OK;
     const size_t cells = (size_t)nviews * h * w;
     staging st(ctx);
-    const void* dxyz = st.in(SLOT_XYZ, xyz, xyz_bytes(dtype, n));
-    const f3d_view* dviews = st.in(SLOT_VIEWS, views, sizeof(f3d_view) * (size_t)nviews);
-    float* ddepth = st.out(SLOT_OUT0, depth, cells * 4);
-    int32_t* dlut = st.out(SLOT_AUX0, uv2pt, cells * 4);
+    const void* dxyz = st.in(xyz, xyz_bytes(dtype, n));
+    const f3d_view* dviews = st.in(views, sizeof(f3d_view) * (size_t)nviews);
+    float* ddepth = st.out(depth, cells * 4);
+    int32_t* dlut = st.out(uv2pt, cells * 4);
     if (!st.rc) st.rc = f3d_render_lookups_dev(ctx, dxyz, dtype, n, dviews, nviews, h, w, splat, ddepth, dlut, ctx->stream);
     return st.finish();
 }
@@ -2534,10 +2570,10 @@ int f3d_vote_visible(f3d_ctx* ctx, const void* xyz, f3d_dtype dtype, int64_t n, 
         return fail(ctx, F3D_ERR_INVALID, "vote_visible: " F3D_RENDER_BAD ", depth_tol >= 0, views_per_pass >= 0");
     if (n == 0 || nviews == 0) return F3D_OK;
     staging st(ctx);
-    const void* dxyz = st.in(SLOT_XYZ, xyz, xyz_bytes(dtype, n));
-    const f3d_view* dviews = st.in(SLOT_VIEWS, views, sizeof(f3d_view) * (size_t)nviews);
-    const uint8_t* dmasks = st.in(SLOT_MASKS, masks, (size_t)nviews * h * w);
-    double* dvotes = st.inout(SLOT_OUT1, votes, (size_t)n * ncols * 8);
+    const void* dxyz = st.in(xyz, xyz_bytes(dtype, n));
+    const f3d_view* dviews = st.in(views, sizeof(f3d_view) * (size_t)nviews);
+    const uint8_t* dmasks = st.in(masks, (size_t)nviews * h * w);
+    double* dvotes = st.inout(votes, (size_t)n * ncols * 8);
     if (!st.rc) st.rc = f3d_vote_visible_dev(ctx, dxyz, dtype, n, dviews, nviews, dmasks, h, w, splat, depth_tol, dvotes, ncols, views_per_pass,
                                              ctx->stream);
     return st.finish(F3D_DEVERR_ZVOTE);                                      // nothing is written back on an IndexError

@@ -13,12 +13,19 @@
  *   - every function returns F3D_OK (0) or a negative f3d_status; the text of the last error
  *     of a context is available from f3d_last_error().
  *   - functions without a "_dev" suffix take HOST pointers: inputs are copied to the device
- *     through the context's scratch arena, the kernels run on the context's stream, outputs are
- *     copied back, and the call returns after the stream has drained (NumPy drop-in).
+ *     through the context's staging buffers, the kernels run on the context's stream, outputs are
+ *     copied back, and the call returns after the stream has drained (NumPy drop-in).  Staging is
+ *     separate from the scratch of the _dev functions and holds nothing once a call has returned.
+ *     Three host-pointer sequences keep data on the device between their calls, in buffers of their
+ *     own: f3d_radius_graph_count -> _fill, f3d_radius_query_count -> _fill and f3d_group_by_id ->
+ *     f3d_obb_extremes -> f3d_obb_hull_filter.  Any other call on the context may come in between;
+ *     a sequence ends where its first call is made again.  Staging and these buffers grow on first
+ *     use like scratch (and a strict context refuses that); f3d_ctx_reserve*() does not size them.
  *   - "_dev" functions take DEVICE pointers and a hipStream_t (as void*; NULL = the context's
  *     own stream).  They only enqueue work and never synchronise.  Scratch (sort keys, coded masks,
  *     the deferred-point list, the vote table) lives in the context and GROWS ON FIRST USE of a larger
- *     problem (hipMalloc, not capturable); size it beforehand with f3d_ctx_reserve() and a _dev call
+ *     problem (hipMalloc, not capturable); size it beforehand with f3d_ctx_reserve() (and its
+ *     f3d_ctx_reserve_*() kin: they cover the scratch of _dev calls only) and a _dev call
  *     of that or a smaller size performs no allocation at all (hipGraph-safe).  With
  *     f3d_ctx_set_strict(ctx, 1) a call that would have to grow scratch fails with F3D_ERR_NOMEM instead.
  *   - the caller owns every buffer; the library keeps no caller pointer after a call returns

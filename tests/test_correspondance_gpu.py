@@ -191,7 +191,7 @@ def test_count_then_other_calls_then_fill():
                                               0.08, offs.ctypes.data, C.byref(nnz)))
         return offs, np.empty(nnz.value, np.int32)
     offs, nb = count()
-    # entries that use the shared input / output slots, the radius graph's scratch and the patch entries' slot (SLOT_GRAPH)
+    # entries that use the staging buffers and the radius graph's scratch, and the patch entries (nine staging buffers)
     other = rng.uniform(-1, 1, (50000, 3))
     ctx.radius_graph(other, 0.05)
     ctx.rotate(other, [1.0, 0.0, 0.0, 0.0])

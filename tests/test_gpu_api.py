@@ -379,3 +379,135 @@ def test_two_ranks_sharded_merge_bb_on_the_hip_path(tmp_path):
             d = np.abs(np.array(g['bbox'])[:, None, :] - np.array(w['bbox'])[None, :, :]).max(-1)
             assert (d.min(1) < 1e-8).all() and (d.min(0) < 1e-8).all()
     assert np.array_equal(np.load(tmp_path / 'panoptic_segmentation' / 'ids.npy'), single_ids)
+
+
+# ---- what a host-pointer sequence keeps on the device is its own: other calls on the context in between do not disturb it
+def _cloud300(seed=31):
+    return np.random.default_rng(seed).uniform(0, 1, (300, 3))
+
+
+def _c_api(ctx):
+    import ctypes as C
+    return ctx._lib, ctx._h, (lambda a: C.c_void_p(a.ctypes.data)), C
+
+
+def test_radius_graph_fill_after_another_call_staged_offsets():
+    """f3d_radius_graph_count, then f3d_components_same_class with offsets of its own (the complete graph: offsets[n] = n * n, so
+    `nbrs` has room whichever offsets the fill pass reads), then f3d_radius_graph_fill: the graph of the uninterrupted call."""
+    pts, r = _cloud300(), 0.15
+    n = len(pts)
+    want_offs, want_nb = f3d.default_context().radius_graph(pts, r)
+    ctx = f3d.Context(0)
+    lib, h, ptr, C = _c_api(ctx)
+    offs, nnz = np.zeros(n + 1, np.int64), C.c_int64(0)
+    assert lib.f3d_radius_graph_count(h, ptr(pts), f3d.F64, n, r, ptr(offs), C.byref(nnz)) == 0
+    full_offs = np.arange(n + 1, dtype=np.int64) * n
+    full_nb = np.tile(np.arange(n, dtype=np.int32), n)
+    root = ctx.components_same_class(np.zeros(n, np.int64), full_offs, full_nb)
+    assert (root == 0).all()
+    nb = np.full(n * n, -1, np.int32)
+    assert lib.f3d_radius_graph_fill(h, n, ptr(nb)) == 0
+    assert nnz.value == want_offs[n] and np.array_equal(offs, want_offs) and np.array_equal(nb[:nnz.value], want_nb)
+    assert (nb[nnz.value:] == -1).all()
+    ctx.close()
+
+
+def test_radius_query_fill_after_other_calls():
+    pts, r = _cloud300(), 0.15
+    queries = np.random.default_rng(32).uniform(0, 1, (200, 3))
+    want_offs, want_nb = f3d.default_context().radius_query(pts, queries, r)
+    ctx = f3d.Context(0)
+    lib, h, ptr, C = _c_api(ctx)
+    offs, nnz = np.zeros(len(queries) + 1, np.int64), C.c_int64(0)
+    assert lib.f3d_radius_query_count(h, ptr(pts), f3d.F64, len(pts), ptr(queries), f3d.F64, len(queries), r, ptr(offs), C.byref(nnz)) == 0
+    ctx.rotate(_cloud300(33), [0.5, 0.5, 0.5, 0.5])
+    ctx.knn_query(_cloud300(34), queries, 4, 0.2)
+    nb = np.full(max(nnz.value, 1), -1, np.int32)
+    assert lib.f3d_radius_query_fill(h, len(queries), ptr(nb)) == 0
+    assert nnz.value == len(want_nb) > 0 and np.array_equal(offs, want_offs) and np.array_equal(nb[:nnz.value], want_nb)
+    ctx.close()
+
+
+def _hull_facets(pts, ext, nids):
+    """Facet planes of the hull of every id's extremes, laid out as merge_intersecting_bb.py hands them to the hull filter."""
+    from scipy.spatial import ConvexHull
+    fstart, margin, eqs = np.zeros(nids + 1, np.int32), np.zeros(nids), []
+    for k in range(nids):
+        p = pts[np.unique(ext[k][ext[k] >= 0])]
+        eq = ConvexHull(p).equations
+        eqs.append(eq)
+        fstart[k + 1] = fstart[k] + len(eq)
+        margin[k] = 1e-9 * (np.abs(p).max() + 1.0)
+    return fstart, np.ascontiguousarray(np.concatenate(eqs)), margin
+
+
+def test_hull_filter_after_another_call_staged_a_cloud():
+    pts, nids = _cloud300(), 8
+    n = len(pts)
+    ids = np.random.default_rng(35).integers(0, nids, n).astype(np.int64)
+    ref = f3d.default_context()
+    want_order, want_starts = ref.group_by_id(ids, nids)
+    want_ext = ref.obb_extremes(pts)
+    fstart, facets, margin = _hull_facets(pts, want_ext, nids)
+    want_cand, want_cnt = ref.obb_hull_filter(fstart, facets, margin)
+    assert 0 < want_cnt.sum() < n                                        # the filter drops some members and keeps some
+    ctx = f3d.Context(0)
+    lib, h, ptr, C = _c_api(ctx)
+    order, starts, ext = np.empty(n, np.int32), np.empty(nids + 2, np.int64), np.empty((nids, 26), np.int32)
+    assert lib.f3d_group_by_id(h, ptr(ids), n, nids, ptr(order), ptr(starts)) == 0
+    assert lib.f3d_obb_extremes(h, ptr(pts), f3d.F64, n, ptr(ext)) == 0
+    ctx.rotate(_cloud300(36) * 50.0 - 25.0, [0.5, 0.5, 0.5, 0.5])        # another cloud of n float64 points
+    cand, cnt = np.full(n, -1, np.int32), np.empty(nids, np.int32)
+    assert lib.f3d_obb_hull_filter(h, n, ptr(fstart), ptr(facets), ptr(margin), ptr(cand), ptr(cnt)) == 0
+    assert np.array_equal(order, want_order) and np.array_equal(starts, want_starts) and np.array_equal(ext, want_ext)
+    assert np.array_equal(cnt, want_cnt)
+    for k in range(nids):
+        lo, hi = starts[k], starts[k] + cnt[k]                            # (survivors of an id come in no fixed order)
+        assert np.array_equal(np.sort(cand[lo:hi]), np.sort(want_cand[lo:hi])), k
+    ctx.close()
+
+
+def test_hull_filter_refuses_a_grouping_without_extremes():
+    pts, nids = _cloud300(), 8
+    n = len(pts)
+    ids = np.random.default_rng(35).integers(0, nids, n).astype(np.int64)
+    ctx = f3d.Context(0)
+    lib, h, ptr, C = _c_api(ctx)
+    ctx.rotate(pts, [1.0, 0.0, 0.0, 0.0])                                # (n float64 points have been staged, whatever a call reads)
+    order, starts = np.empty(n, np.int32), np.empty(nids + 2, np.int64)
+    assert lib.f3d_group_by_id(h, ptr(ids), n, nids, ptr(order), ptr(starts)) == 0
+    fstart, facets, margin = np.zeros(nids + 1, np.int32), np.zeros((1, 4)), np.zeros(nids)
+    cand, cnt = np.full(n, -1, np.int32), np.full(nids, -1, np.int32)
+    rc = lib.f3d_obb_hull_filter(h, n, ptr(fstart), ptr(facets), ptr(margin), ptr(cand), ptr(cnt))
+    msg = lib.f3d_last_error(h).decode()
+    assert rc == f3d.ERR_INVALID
+    assert 'call f3d_group_by_id and f3d_obb_extremes' in msg and msg.endswith('first')
+    assert (cand == -1).all() and (cnt == -1).all()
+    ctx.close()
+
+
+def test_host_staging_reaches_a_steady_state():
+    """The staging buffers of a host-pointer call grow on its first use and then stay: an identical second call allocates nothing."""
+    rng = np.random.default_rng(37)
+    hh = ww = 16
+    m = 8
+    uv = rng.integers(0, 16, (2, m)).astype(np.int32)
+    unit = lambda a: a / np.linalg.norm(a, axis=1, keepdims=True)
+    sp, sn = rng.uniform(0, 1, (m, 3)), unit(rng.normal(size=(m, 3)))
+    qp, qn, qc = rng.uniform(0, 1, (hh * ww, 3)), unit(rng.normal(size=(hh * ww, 3))), rng.uniform(0, 1, (hh * ww, 3))
+    free = np.ones(hh * ww, np.uint8)
+    pts = _cloud300()
+    offs, nb = f3d.default_context().radius_graph(pts, 0.15)
+    cls = rng.integers(0, 3, len(pts)).astype(np.int64)
+    lazy = f3d.Context(0)
+    first = lazy.patch_match(uv, sp, sn, qp, qn, qc, free, hh, ww, 2, 0.3, 0.5)
+    grown = lazy.alloc_count
+    again = lazy.patch_match(uv, sp, sn, qp, qn, qc, free, hh, ww, 2, 0.3, 0.5)
+    assert lazy.alloc_count == grown
+    assert all(np.array_equal(a, b) for a, b in zip(first, again))
+    first = lazy.flood_order(cls, offs, nb, [0, 2])
+    grown = lazy.alloc_count
+    again = lazy.flood_order(cls, offs, nb, [0, 2])
+    assert lazy.alloc_count == grown
+    assert all(np.array_equal(a, b) for a, b in zip(first[:4], again[:4]))
+    lazy.close()
