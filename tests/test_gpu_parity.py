@@ -1,6 +1,8 @@
 """Parity of the HIP path (through the C-ABI, via ctypes) against the oracle and the golden vectors.
 Needs a real MI355X: run with `-m gpu`.  Integer outputs (labels, uv, inside, votes) are compared
 bit for bit with the oracle on the same seeded inputs."""
+import functools
+
 import numpy as np
 import pytest
 
@@ -286,9 +288,24 @@ def test_vote_uv2pt_batch_index_error_keeps_the_earlier_frames(ctx):
         assert np.array_equal(got, want), (it, fbad)
 
 
-def _dev_fuse(ctx, pts, views, masks, flt, thr, flags, presort=False, f32=False, nclasses=133, mask_shift=0, votes_at=None):
+def _dev_perm(ctx, x, dt, perm, permuted_copy, s):
+    """(xyz to hand over, int32 permutation on the device) for a caller's `perm`: an int array, or 'sort' for f3d_cloud_sort_cells_dev's."""
+    import torch
+    n = len(x)
+    if isinstance(perm, str):
+        permd = torch.full((n,), -1, dtype=torch.int32, device=x.device)
+        ctx.cloud_sort_cells_dev(x.data_ptr(), dt, n, None, permd.data_ptr(), s.cuda_stream)
+    else:
+        assert np.array_equal(np.sort(perm), np.arange(n))
+        permd = torch.from_numpy(np.ascontiguousarray(perm, dtype=np.int32)).to(x.device)
+    return (x[permd.long()] if permuted_copy else x), permd
+
+
+def _dev_fuse(ctx, pts, views, masks, flt, thr, flags, presort=False, f32=False, nclasses=133, mask_shift=0, votes_at=None,
+              perm=None, permuted_copy=False):
     """One call of f3d_project_vote_argmax_dev on device-resident inputs.  votes_at: caller-order indices whose uint16 vote
-    rows are returned as well (the full [n, nclasses + 1] matrix stays on the device)."""
+    rows are returned as well (the full [n, nclasses + 1] matrix stays on the device).  perm: the caller's permutation, an int array or
+    'sort' for the cell sort's; xyz stays in caller order (for F3D_FUSE_GATHER) unless permuted_copy hands over x[perm]."""
     import torch
     dev = torch.device('cuda', 0)
     x = torch.from_numpy(pts.astype(np.float32) if f32 else pts).to(dev)
@@ -309,10 +326,15 @@ def _dev_fuse(ctx, pts, views, masks, flt, thr, flags, presort=False, f32=False,
             perm = torch.empty(n, dtype=torch.int32, device=dev)
             ctx.cloud_sort_cells_dev(x.data_ptr(), dt, n, xs.data_ptr(), perm.data_ptr(), s.cuda_stream)
             s.synchronize()
-            if n <= 20_000_000:
-                assert np.array_equal(np.sort(perm.cpu().numpy()), np.arange(n))          # a permutation
-                assert np.array_equal(xs.cpu().numpy(), x.cpu().numpy()[perm.cpu().numpy()])
+            seen = torch.zeros(n, dtype=torch.bool, device=dev)
+            seen[perm.long()] = True
+            assert bool(seen.all())                                                       # a permutation (checked on the device: any n)
+            assert torch.equal(xs, x[perm.long()])
+            del seen
             x, perm_ptr = xs, perm.data_ptr()
+        elif perm is not None:
+            x, permd = _dev_perm(ctx, x, dt, perm, permuted_copy, s)
+            perm_ptr = permd.data_ptr()
         V, H, W = masks.shape
         ctx.project_vote_argmax_dev(x.data_ptr(), dt, n, vd.data_ptr(), V, md.data_ptr(), H, W, nclasses, thr, flt,
                                     cls.data_ptr(), None if votes is None else votes.data_ptr(), s.cuda_stream, flags=flags, perm_ptr=perm_ptr)
@@ -584,9 +606,12 @@ def test_nclasses_edge_values(ctx):
 
 
 # ---- the view-chunked call (f3d_fuse_chunked_begin_dev / f3d_fuse_chunk_dev): same labels as the one-shot call ----------------
-def _dev_fuse_chunked(ctx, pts, views, masks, flt, thr, flags, bounds, f32=False, nclasses=133, order=None, presence='own', coded=False):
+def _dev_fuse_chunked(ctx, pts, views, masks, flt, thr, flags, bounds, f32=False, nclasses=133, order=None, presence='own', coded=False,
+                      perm=None, permuted_copy=False):
     """bounds: chunk boundaries [0, ..., V].  order: views (and masks) handed over in this order (a permutation of range(V)).
-    coded: the planes are coded up front with f3d_code_planes_dev (as another rank would) and handed over coded."""
+    coded: the planes are coded up front with f3d_code_planes_dev (as another rank would) and handed over coded.
+    perm, permuted_copy: as in _dev_fuse; the first chunk alone receives the permutation ("flags and perm are taken from the first
+    chunk"), the later ones a pointer to another array that must not be read."""
     import torch
     dev = torch.device('cuda', 0)
     if order is not None:
@@ -610,13 +635,18 @@ def _dev_fuse_chunked(ctx, pts, views, masks, flt, thr, flags, bounds, f32=False
                 ctx.code_planes_dev(md[a:b].data_ptr(), b - a, H, W, cd[a:b].data_ptr(), s.cuda_stream)
             md.fill_(0xEE)                                                              # the raw masks are gone: nothing may read them
             s.wait_stream(torch.cuda.current_stream(dev))
+        permd = decoy = None
+        if perm is not None:
+            x, permd = _dev_perm(ctx, x, dt, perm, permuted_copy, s)
+            decoy = torch.zeros(n, dtype=torch.int32, device=dev)                       # in bounds, and wrong for every point but one
         for a, b in zip(bounds[:-1], bounds[1:]):
+            pp = None if permd is None else (permd if a == 0 else decoy).data_ptr()
             if coded:
                 ctx.fuse_chunk_coded_dev(x.data_ptr(), dt, n, vd.data_ptr(), V, a, b, cd.data_ptr(), H, W, nclasses, thr, flt, cls.data_ptr(),
-                                         s.cuda_stream, flags=flags)
+                                         s.cuda_stream, flags=flags, perm_ptr=pp)
             else:
                 ctx.fuse_chunk_dev(x.data_ptr(), dt, n, vd.data_ptr(), V, a, b, md.data_ptr(), H, W, nclasses, thr, flt, cls.data_ptr(),
-                                   s.cuda_stream, flags=flags)
+                                   s.cuda_stream, flags=flags, perm_ptr=pp)
         ctx.take_device_error(s.cuda_stream)
         s.synchronize()
     if presence == 'own' and not coded:
@@ -702,6 +732,95 @@ def test_view_chunked_call_deferred_points_errors_and_sequence(ctx):
         ctx.fuse_chunked_begin_dev(None, len(pts), 256, H, W, 133, None, None)
     ctx.synchronize()
     assert np.array_equal(cls.cpu().numpy(), _dev_fuse(ctx, sc['points'], views, sc['masks'], None, 0.0, 0))
+
+
+# ---- the caller's perm and F3D_FUSE_GATHER, one-shot and chunked: every point labelled by the oracle ------------------------------------
+PERM_V = 12                                              # views of the chunked cases (C1's own 4 cannot be split as [0, 1, 9, V])
+
+
+@functools.lru_cache(maxsize=None)
+def _perm_scene(n, V=None):
+    """C1 at n points (with V ring views in place of its own 4): (points, views, masks, oracle labels, oracle vote rows) at threshold 0."""
+    sc = synth.scene('C1', n=n)
+    q, t, masks = sc['wxyzs'], sc['translations'], sc['masks']
+    if V is not None:
+        q, t = synth.ring_views(V)
+        masks = synth.masks(V, sc['h'], sc['w'])
+    views = f3d.views_build(sc['K'], sc['w'], sc['h'], q, t, sc['max_depth'])
+    want, votes = O.project_vote_argmax(sc['points'], sc['K'], q, t, masks, sc['max_depth'], 133, 0.0, None, return_votes=True)
+    return sc['points'], views, masks, want, votes
+
+
+def _a_perm(kind, n):
+    return {'sort': lambda: 'sort', 'identity': lambda: np.arange(n), 'reversal': lambda: np.arange(n)[::-1],
+            'random': lambda: np.random.default_rng(41).permutation(n)}[kind]()
+
+
+@pytest.mark.parametrize('f32', [False, True], ids=['f64', 'f32'])
+@pytest.mark.parametrize('kind', ['sort', 'identity', 'reversal', 'random'])
+def test_fuse_gather_reads_the_cloud_through_any_perm(ctx, kind, f32):
+    """F3D_FUSE_GATHER: xyz in caller order, the kernel reads point perm[i] and writes label and votes back to perm[i] -- the labels and
+    vote rows of flags = 0 (and of the oracle) whatever the permutation."""
+    pts, views, masks, want, want_votes = _perm_scene(20_001)
+    rows = np.arange(len(pts))
+    assert (want != 133).mean() > 0.3
+    plain, plain_votes = _dev_fuse(ctx, pts, views, masks, None, 0.0, 0, f32=f32, votes_at=rows)
+    assert np.array_equal(plain, want) and np.array_equal(plain_votes.astype(np.float64), want_votes)
+    got, votes = _dev_fuse(ctx, pts, views, masks, None, 0.0, f3d.FUSE_GATHER, f32=f32, votes_at=rows, perm=_a_perm(kind, len(pts)))
+    assert np.array_equal(got, want) and np.array_equal(votes.astype(np.float64), want_votes)
+
+
+@pytest.mark.parametrize('f32', [False, True], ids=['f64', 'f32'])
+def test_fuse_gather_without_perm_and_a_permuted_copy_with_any_perm(ctx, f32):
+    pts, views, masks, want, want_votes = _perm_scene(20_001)
+    rows = np.arange(len(pts))
+    got, votes = _dev_fuse(ctx, pts, views, masks, None, 0.0, f3d.FUSE_GATHER, f32=f32, votes_at=rows)      # the flag alone: flags = 0
+    assert np.array_equal(got, want) and np.array_equal(votes.astype(np.float64), want_votes)
+    # xyz = x[p], perm = p without the flag, p not the sort's: results still land at the caller's indices
+    got, votes = _dev_fuse(ctx, pts, views, masks, None, 0.0, 0, f32=f32, votes_at=rows, perm=_a_perm('random', len(pts)), permuted_copy=True)
+    assert np.array_equal(got, want) and np.array_equal(votes.astype(np.float64), want_votes)
+
+
+@pytest.mark.parametrize('n', [1, 127, 129, 512, 513])
+def test_fuse_sort_and_gather_at_small_n(ctx, n):
+    """Across a wave tile (128 points) and the n > 512 rule below which F3D_FUSE_SORT skips the in-call sort."""
+    pts, views, masks, want, want_votes = _perm_scene(n)
+    rows = np.arange(n)
+    for flags, perm in [(f3d.FUSE_SORT, None), (f3d.FUSE_GATHER, 'sort'), (f3d.FUSE_GATHER, 'random'), (f3d.FUSE_GATHER, 'reversal')]:
+        got, votes = _dev_fuse(ctx, pts, views, masks, None, 0.0, flags, votes_at=rows, perm=None if perm is None else _a_perm(perm, n))
+        assert np.array_equal(got, want) and np.array_equal(votes.astype(np.float64), want_votes), (flags, perm)
+        got = _dev_fuse(ctx, pts, views, masks, None, 0.0, flags, f32=True, perm=None if perm is None else _a_perm(perm, n))
+        assert np.array_equal(got, want), (flags, perm, 'f32')
+
+
+@pytest.mark.parametrize('coded', [False, True], ids=['raw', 'coded'])
+@pytest.mark.parametrize('bounds', [[0, PERM_V], [0, 1, 9, PERM_V]], ids=['one-chunk', 'keep-copy'])
+def test_view_chunked_call_with_the_callers_perm(ctx, bounds, coded):
+    """The first chunk fixes the point order from the CALLER's perm: gathered through it (one chunk: no copy; several: the first chunk leaves
+    the cloud behind in perm order and the later ones stream that copy), or a permuted copy handed over with its perm."""
+    pts, views, masks, want, _ = _perm_scene(20_001, PERM_V)
+    assert (want != 133).mean() > 0.3
+    assert np.array_equal(_dev_fuse(ctx, pts, views, masks, None, 0.0, 0), want)
+    for f32 in (False, True):
+        for flags, kind, copy in [(f3d.FUSE_GATHER, 'sort', False), (f3d.FUSE_GATHER, 'random', False), (0, 'sort', True), (0, 'random', True)]:
+            got = _dev_fuse_chunked(ctx, pts, views, masks, None, 0.0, flags, bounds, f32=f32, coded=coded,
+                                    perm=_a_perm(kind, len(pts)), permuted_copy=copy)
+            assert np.array_equal(got, want), (f32, flags, kind, copy)
+
+
+def test_fuse_sort_and_a_perm_are_exclusive(ctx):
+    pts, views, masks, want, _ = _perm_scene(20_001, PERM_V)
+    ident = np.arange(len(pts))
+    with pytest.raises(ValueError, match='exclusive'):
+        _dev_fuse(ctx, pts, views, masks, None, 0.0, f3d.FUSE_SORT, perm=ident)
+    with pytest.raises(ValueError, match='exclusive'):
+        _dev_fuse(ctx, pts, views, masks, None, 0.0, f3d.FUSE_SORT | f3d.FUSE_GATHER, perm=ident)
+    assert np.array_equal(_dev_fuse(ctx, pts, views, masks, None, 0.0, f3d.FUSE_SORT), want)
+    for coded in (False, True):
+        with pytest.raises(ValueError, match='exclusive'):
+            _dev_fuse_chunked(ctx, pts, views, masks, None, 0.0, f3d.FUSE_SORT, [0, 1, 9, PERM_V], coded=coded, perm=ident)
+        assert np.array_equal(_dev_fuse_chunked(ctx, pts, views, masks, None, 0.0, f3d.FUSE_SORT, [0, 1, 9, PERM_V], coded=coded), want)
+        assert np.array_equal(_dev_fuse_chunked(ctx, pts, views, masks, None, 0.0, f3d.FUSE_GATHER, [0, 1, 9, PERM_V], coded=coded, perm=ident), want)
 
 
 def test_fused_randomised_configurations(ctx):
