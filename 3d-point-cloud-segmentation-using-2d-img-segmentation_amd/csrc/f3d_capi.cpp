@@ -92,7 +92,7 @@ struct f3d_ctx {
     int grp_dtype;
     bool grp_cloud;
     // view-chunked fused call in progress (f3d_fuse_chunked_begin_dev .. the chunk with v_end == nviews)
-    struct { int active, next, nviews, h, w, nclasses, gather; int64_t n; const int32_t* perm; const void* xyz; } chunk;
+    struct { int active, next, nviews, h, w, nclasses, gather; int64_t n; const int32_t* perm; const void* xyz; f3d_fuse_todo lay; } chunk;
 };
 
 namespace {
@@ -420,7 +420,7 @@ int f3d_ctx_reserve(f3d_ctx* ctx, int64_t n, int nviews, int h, int w) {
     int rc = enter(ctx); if (rc) return rc;
     if (n < 0 || n > 0x7fffffffLL || nviews < 0 || h < 0 || w < 0) return fail(ctx, F3D_ERR_INVALID, "ctx_reserve: bad arguments");
     const bool frames = h > 0 && w > 0;
-    return reserve(ctx, {{SLOT_TODO, f3d_fuse_todo_bytes(n, nviews, F3D_CODE_MAX_NCLASSES)},                  // (any number of classes)
+    return reserve(ctx, {{SLOT_TODO, f3d_fuse_todo_layout(n, nviews, F3D_CODE_MAX_NCLASSES).bytes},           // (any number of classes)
                          {SLOT_SORT_PERM, (size_t)n * 4, n > 0},
                          {SLOT_SORT_SCRATCH, f3d_sort_scratch_bytes(n), n > 0},
                          {SLOT_TILED_MASKS, frames && nviews > 0 ? f3d_coded_masks_bytes(nviews, h, w) : 0, frames && nviews > 0},
@@ -682,6 +682,32 @@ int f3d_cloud_sort_cells_dev(f3d_ctx* ctx, const void* xyz, f3d_dtype dtype, int
     return F3D_OK;
 }
 
+// The context scratch of a fused call, ensured in one place: the todo block (laid out by `lay`) and the view tables always; the coded
+// masks, the carried bins of a view-chunked call, the cell sort's permutation + scratch and `keep_bytes` of cell-ordered cloud as asked.
+enum { FUSE_CODED = 1, FUSE_CARRY = 2, FUSE_SORT = 4 };
+struct fuse_scratch { void *todo, *tables, *tm, *carry, *perm, *sort, *keep; };
+
+static int ensure_fuse_scratch(f3d_ctx* ctx, const f3d_fuse_todo& lay, int64_t n, int nviews, int h, int w, int nclasses, unsigned which,
+                               size_t keep_bytes, fuse_scratch* o) {
+    int rc;
+    *o = fuse_scratch{};
+    if ((which & FUSE_SORT) && ((rc = ensure(ctx, SLOT_SORT_PERM, (size_t)n * 4, &o->perm)) ||
+                                (rc = ensure(ctx, SLOT_SORT_SCRATCH, f3d_sort_scratch_bytes(n), &o->sort)))) return rc;
+    if (keep_bytes && (rc = ensure(ctx, SLOT_FUSE_XYZ, keep_bytes, &o->keep))) return rc;
+    if ((which & FUSE_CODED) && (rc = ensure(ctx, SLOT_TILED_MASKS, f3d_coded_masks_bytes(nviews, h, w), &o->tm))) return rc;
+    if ((rc = ensure(ctx, SLOT_TODO, lay.bytes, &o->todo))) return rc;
+    if ((rc = ensure(ctx, SLOT_FUSE_TABLES, f3d_fuse_tables_bytes(nviews > 0 ? nviews : 1), &o->tables))) return rc;
+    if ((which & FUSE_CARRY) && (rc = ensure(ctx, SLOT_FUSE_CARRY, f3d_fuse_carry_bytes(n, nclasses), &o->carry))) return rc;
+    return F3D_OK;
+}
+
+// F3D_FUSE_SORT: the cloud's cell order into the context's permutation (FUSE_SORT scratch); the kernel then reads xyz[perm[i]]
+static int sort_into_perm(f3d_ctx* ctx, const void* xyz, f3d_dtype dtype, int64_t n, const fuse_scratch& sc, hipStream_t s, const int32_t** perm) {
+    F3D_HIP(ctx, f3d_launch_cell_sort(xyz, dtype, n, nullptr, (int32_t*)sc.perm, sc.sort, s));
+    *perm = (const int32_t*)sc.perm;
+    return F3D_OK;
+}
+
 int f3d_project_vote_argmax_dev(f3d_ctx* ctx, const void* xyz, f3d_dtype dtype, int64_t n, const f3d_view* views_dev, int nviews,
                                 const uint8_t* masks, int h, int w, int nclasses, const int32_t* filter, int nfilter,
                                 double threshold, int64_t* classes, uint16_t* votes_u16, unsigned flags, const int32_t* perm,
@@ -693,36 +719,30 @@ int f3d_project_vote_argmax_dev(f3d_ctx* ctx, const void* xyz, f3d_dtype dtype, 
     if (nviews > 65535) return fail(ctx, F3D_ERR_INVALID, "project_vote_argmax: at most 65535 views");
     if ((int64_t)h * (int64_t)w >= (int64_t)1 << 31) return fail(ctx, F3D_ERR_INVALID, "project_vote_argmax: mask of %d x %d pixels is too large", h, w);
     if ((flags & F3D_FUSE_SORT) && perm) return fail(ctx, F3D_ERR_INVALID, "project_vote_argmax: F3D_FUSE_SORT and perm are exclusive");
-    hipStream_t s = pick(ctx, stream);
-    f3d_filter_args fa;
-    if ((rc = make_filter(ctx, filter, nfilter, nclasses + 1, true, s, &fa))) return rc;
-    bool gather = (flags & F3D_FUSE_GATHER) && perm;
+    f3d_fuse_job job{};
+    job.stream = pick(ctx, stream);
+    if ((rc = make_filter(ctx, filter, nfilter, nclasses + 1, true, job.stream, &job.flt))) return rc;
     const bool sort = (flags & F3D_FUSE_SORT) && n > 512 && n <= 0x7fffffffLL;
     // the accelerated kernels address the coded masks with 32-bit offsets; beyond 4 GiB of them the exact kernel labels every point
     const bool coded = nviews > 0 && nclasses <= F3D_CODE_MAX_NCLASSES && f3d_coded_masks_bytes(nviews, h, w) < ((size_t)1 << 32);
+    job.lay = f3d_fuse_todo_layout(n, nviews, nclasses);
+    fuse_scratch sc;                                                                            // grows on first use only
+    if ((rc = ensure_fuse_scratch(ctx, job.lay, n, nviews, h, w, nclasses, (coded ? FUSE_CODED : 0) | (sort ? FUSE_SORT : 0), 0, &sc))) return rc;
     // (Measured and dropped: coding the masks on a second stream, forked from and joined into `stream` with events, while the cloud is
     // sorted -- the two event dependencies cost more than the ~50 us of overlap they buy: 1.32 ms per C3 step instead of 1.26.)
+    job.xyz = xyz; job.dtype = dtype; job.n = n; job.perm = perm; job.gather = (flags & F3D_FUSE_GATHER) && perm;
     if (sort) {
-        void *sperm, *scratch;                                                                  // grow on first use only
-        if ((rc = ensure(ctx, SLOT_SORT_PERM, (size_t)n * 4, &sperm))) return rc;
-        if ((rc = ensure(ctx, SLOT_SORT_SCRATCH, f3d_sort_scratch_bytes(n), &scratch))) return rc;
-        F3D_HIP(ctx, f3d_launch_cell_sort(xyz, dtype, n, nullptr, (int32_t*)sperm, scratch, s));
-        perm = (const int32_t*)sperm; gather = true;                                            // the kernel reads xyz[perm[i]]
+        if ((rc = sort_into_perm(ctx, xyz, dtype, n, sc, job.stream, &job.perm))) return rc;
+        job.gather = true;
     }
-    const uint8_t* cmasks = nullptr;                                                            // coded, tiled copy for the fast kernel
-    void *todo, *tables;                                                                        // grow on first use only
-    if ((rc = ensure(ctx, SLOT_TODO, f3d_fuse_todo_bytes(n, nviews, nclasses), &todo))) return rc;
-    if ((rc = ensure(ctx, SLOT_FUSE_TABLES, f3d_fuse_tables_bytes(nviews > 0 ? nviews : 1), &tables))) return rc;
-    if (coded) {
-        void* tm;                                                                               // grows on first use only
-        if ((rc = ensure(ctx, SLOT_TILED_MASKS, f3d_coded_masks_bytes(nviews, h, w), &tm))) return rc;
-        F3D_HIP(ctx, f3d_launch_code_masks_with_setup(masks, (uint8_t*)tm, nviews, h, w, nclasses, fa, votes_u16 != nullptr, ctx->codebook, views_dev, tables,
-                                                      threshold, (unsigned int*)todo, s));
-        cmasks = (const uint8_t*)tm;
+    job.views_dev = views_dev; job.nviews = nviews; job.v0 = 0; job.v1 = nviews; job.masks = masks; job.h = h; job.w = w;
+    job.nclasses = nclasses; job.threshold = threshold; job.classes = classes; job.votes = votes_u16; job.err = ctx->dev_err;
+    job.todo = sc.todo; job.cb = ctx->codebook; job.tables = sc.tables;
+    if (coded) {                                                                                // coded, tiled copy for the fast kernel
+        F3D_HIP(ctx, f3d_launch_code_masks_with_setup(job, (uint8_t*)sc.tm, ctx->codebook));
+        job.cmasks = (const uint8_t*)sc.tm;
     }
-    F3D_HIP(ctx, f3d_launch_fuse(xyz, dtype, n, views_dev, nviews, masks, cmasks, h, w, nclasses, fa, threshold, classes, votes_u16,
-                                 ctx->dev_err, perm, gather, (unsigned int*)todo, (int32_t*)((char*)todo + 16), ctx->codebook, tables,
-                                 0, nviews, nullptr, nullptr, s));
+    F3D_HIP(ctx, f3d_launch_fuse(job));
     return F3D_OK;
 }
 
@@ -747,16 +767,12 @@ int f3d_fuse_chunked_begin_dev(f3d_ctx* ctx, const uint8_t* present256, int64_t 
     hipStream_t s = pick(ctx, stream);
     f3d_filter_args fa;
     if ((rc = make_filter(ctx, filter, nfilter, nclasses + 1, true, s, &fa))) return rc;
-    void* p;                                                   // every scratch buffer of the chunk calls: they allocate nothing
-    if ((rc = ensure(ctx, SLOT_TILED_MASKS, f3d_coded_masks_bytes(nviews, h, w), &p))) return rc;
-    if ((rc = ensure(ctx, SLOT_TODO, f3d_fuse_todo_bytes(n, nviews, nclasses), &p))) return rc;
-    if ((rc = ensure(ctx, SLOT_FUSE_TABLES, f3d_fuse_tables_bytes(nviews), &p))) return rc;
-    if ((rc = ensure(ctx, SLOT_FUSE_CARRY, f3d_fuse_carry_bytes(n, nclasses), &p))) return rc;
-    if (n > 0) {                                               // F3D_FUSE_SORT / a gathered cloud: permutation, sort scratch, cell-order copy
-        if ((rc = ensure(ctx, SLOT_SORT_PERM, (size_t)n * 4, &p))) return rc;
-        if ((rc = ensure(ctx, SLOT_SORT_SCRATCH, f3d_sort_scratch_bytes(n), &p))) return rc;
-        if ((rc = ensure(ctx, SLOT_FUSE_XYZ, (size_t)n * 24, &p))) return rc;
-    }
+    // every scratch buffer of the chunk calls, so that they allocate nothing: with n > 0 also what F3D_FUSE_SORT / a gathered cloud
+    // needs (permutation, sort scratch, cell-order copy)
+    ctx->chunk.lay = f3d_fuse_todo_layout(n, nviews, nclasses);
+    fuse_scratch sc;
+    if ((rc = ensure_fuse_scratch(ctx, ctx->chunk.lay, n, nviews, h, w, nclasses, FUSE_CODED | FUSE_CARRY | (n > 0 ? FUSE_SORT : 0),
+                                  (size_t)n * 24, &sc))) return rc;
     if (present256) F3D_HIP(ctx, f3d_launch_presence_bytes(ctx->codebook, const_cast<uint8_t*>(present256), false, s));
     else F3D_HIP(ctx, hipMemsetAsync(ctx->codebook->presence, 0xFF, sizeof ctx->codebook->presence, s));     // every label gets a bin
     F3D_HIP(ctx, f3d_launch_code_book(ctx->codebook, nclasses, fa, false, s));
@@ -774,16 +790,59 @@ int f3d_code_planes_dev(f3d_ctx* ctx, const uint8_t* masks, int nplanes, int h, 
     return F3D_OK;
 }
 
-static int fuse_chunk_impl(f3d_ctx* ctx, const void* xyz, f3d_dtype dtype, int64_t n, const f3d_view* views_dev, int nviews, int v_begin, int v_end,
-                           const uint8_t* masks, const uint8_t* coded, int h, int w, int nclasses, const int32_t* filter, int nfilter, double threshold,
-                           int64_t* classes, unsigned flags, const int32_t* perm, void* stream);
+// The views [v_begin, v_end) of a view-chunked call, in the job record's terms: `j` arrives with the caller's cloud, views, masks, vote
+// rule and labels.  masks: raw planes [nviews, H, W], coded here into context scratch -- or coded: planes some rank coded already
+// (f3d_code_planes_dev with the same book), [nviews] x f3d_coded_plane_bytes, used where they lie
+static int fuse_chunk_impl(f3d_ctx* ctx, f3d_fuse_job& j, const uint8_t* coded, const int32_t* filter, int nfilter, unsigned flags, void* stream) {
+    int rc;
+    const int64_t n = j.n;
+    const int nviews = j.nviews, v_begin = j.v0, v_end = j.v1, h = j.h, w = j.w, nclasses = j.nclasses;
+    if (!ctx->chunk.active || ctx->chunk.next != v_begin || ctx->chunk.nviews != nviews || ctx->chunk.h != h || ctx->chunk.w != w ||
+        ctx->chunk.nclasses != nclasses || ctx->chunk.n != n || v_end <= v_begin || v_end > nviews)
+        return fail(ctx, F3D_ERR_INVALID, "fuse_chunk: views [%d, %d) do not continue the call begun with f3d_fuse_chunked_begin_dev "
+                    "(next view %d of %d, same n / h / w / nclasses required)", v_begin, v_end, ctx->chunk.active ? ctx->chunk.next : -1, ctx->chunk.nviews);
+    if (!j.classes || (n > 0 && !j.xyz) || !j.views_dev) return fail(ctx, F3D_ERR_INVALID, "fuse_chunk: bad arguments");
+    if ((flags & F3D_FUSE_SORT) && j.perm) return fail(ctx, F3D_ERR_INVALID, "fuse_chunk: F3D_FUSE_SORT and perm are exclusive");
+    hipStream_t s = j.stream = pick(ctx, stream);
+    if ((rc = make_filter(ctx, filter, nfilter, nclasses + 1, true, s, &j.flt))) return rc;
+    const bool first = v_begin == 0, sort = first && (flags & F3D_FUSE_SORT) && n > 512;
+    // a cloud read through a permutation and more chunks to come: the first chunk leaves it behind in cell order (context scratch),
+    // the later chunks stream that copy instead of gathering 24-byte points again
+    const bool keep = first && v_end < nviews && n > 0 && (sort || ((flags & F3D_FUSE_GATHER) && j.perm));
+    fuse_scratch sc;
+    if ((rc = ensure_fuse_scratch(ctx, ctx->chunk.lay, n, nviews, h, w, nclasses, FUSE_CODED | FUSE_CARRY | (sort ? FUSE_SORT : 0),
+                                  keep ? xyz_bytes((f3d_dtype)j.dtype, n) : 0, &sc))) return rc;
+    if (first) {                                               // the point order is fixed by the first chunk
+        ctx->chunk.perm = j.perm; ctx->chunk.gather = ((flags & F3D_FUSE_GATHER) && j.perm) ? 1 : 0;
+        if (sort) {
+            if ((rc = sort_into_perm(ctx, j.xyz, (f3d_dtype)j.dtype, n, sc, s, &ctx->chunk.perm))) return rc;
+            ctx->chunk.gather = 1;
+        }
+        ctx->chunk.xyz = j.xyz;
+    }
+    j.xyz = ctx->chunk.xyz; j.perm = ctx->chunk.perm; j.gather = ctx->chunk.gather != 0;
+    const size_t plane = f3d_coded_masks_bytes(1, h, w);
+    j.cmasks = coded ? coded : (const uint8_t*)sc.tm;          // the exchange delivered coded planes: no coding, no raw masks, the exact tier reads codes
+    if (!coded) F3D_HIP(ctx, f3d_launch_code_planes(j.masks + (size_t)v_begin * h * w, (uint8_t*)sc.tm + (size_t)v_begin * plane, v_end - v_begin, h, w, ctx->codebook, s));
+    j.err = ctx->dev_err; j.todo = sc.todo; j.lay = ctx->chunk.lay; j.cb = ctx->codebook; j.tables = sc.tables; j.carry = (uint32_t*)sc.carry; j.xyz_keep = sc.keep;
+    F3D_HIP(ctx, f3d_launch_fuse_setup(j, ctx->codebook, false));
+    F3D_HIP(ctx, f3d_launch_fuse(j));
+    if (sc.keep) { ctx->chunk.xyz = sc.keep; ctx->chunk.gather = 0; }
+    ctx->chunk.next = v_end;
+    if (v_end == nviews) ctx->chunk.active = 0;
+    return F3D_OK;
+}
 
 int f3d_fuse_chunk_dev(f3d_ctx* ctx, const void* xyz, f3d_dtype dtype, int64_t n, const f3d_view* views_dev, int nviews, int v_begin, int v_end,
                        const uint8_t* masks, int h, int w, int nclasses, const int32_t* filter, int nfilter, double threshold,
                        int64_t* classes, unsigned flags, const int32_t* perm, void* stream) {
     int rc = enter(ctx); if (rc) return rc;
     if (!masks) return fail(ctx, F3D_ERR_INVALID, "fuse_chunk: bad arguments");
-    return fuse_chunk_impl(ctx, xyz, dtype, n, views_dev, nviews, v_begin, v_end, masks, nullptr, h, w, nclasses, filter, nfilter, threshold, classes, flags, perm, stream);
+    f3d_fuse_job j{};
+    j.xyz = xyz; j.dtype = dtype; j.n = n; j.perm = perm; j.views_dev = views_dev; j.nviews = nviews; j.v0 = v_begin; j.v1 = v_end;
+    j.h = h; j.w = w; j.nclasses = nclasses; j.threshold = threshold; j.classes = classes;
+    j.masks = masks;
+    return fuse_chunk_impl(ctx, j, nullptr, filter, nfilter, flags, stream);
 }
 
 int f3d_fuse_chunk_coded_dev(f3d_ctx* ctx, const void* xyz, f3d_dtype dtype, int64_t n, const f3d_view* views_dev, int nviews, int v_begin, int v_end,
@@ -791,59 +850,10 @@ int f3d_fuse_chunk_coded_dev(f3d_ctx* ctx, const void* xyz, f3d_dtype dtype, int
                              int64_t* classes, unsigned flags, const int32_t* perm, void* stream) {
     int rc = enter(ctx); if (rc) return rc;
     if (!coded || ((uintptr_t)coded & 7)) return fail(ctx, F3D_ERR_INVALID, "fuse_chunk_coded: bad arguments (coded: 8-byte aligned)");
-    return fuse_chunk_impl(ctx, xyz, dtype, n, views_dev, nviews, v_begin, v_end, nullptr, coded, h, w, nclasses, filter, nfilter, threshold, classes, flags, perm, stream);
-}
-
-// masks: raw planes [nviews, H, W], coded here into context scratch -- or coded: planes some rank coded already (f3d_code_planes_dev with the
-// same book), [nviews] x f3d_coded_plane_bytes, used where they lie
-static int fuse_chunk_impl(f3d_ctx* ctx, const void* xyz, f3d_dtype dtype, int64_t n, const f3d_view* views_dev, int nviews, int v_begin, int v_end,
-                           const uint8_t* masks, const uint8_t* coded, int h, int w, int nclasses, const int32_t* filter, int nfilter, double threshold,
-                           int64_t* classes, unsigned flags, const int32_t* perm, void* stream) {
-    int rc;
-    if (!ctx->chunk.active || ctx->chunk.next != v_begin || ctx->chunk.nviews != nviews || ctx->chunk.h != h || ctx->chunk.w != w ||
-        ctx->chunk.nclasses != nclasses || ctx->chunk.n != n || v_end <= v_begin || v_end > nviews)
-        return fail(ctx, F3D_ERR_INVALID, "fuse_chunk: views [%d, %d) do not continue the call begun with f3d_fuse_chunked_begin_dev "
-                    "(next view %d of %d, same n / h / w / nclasses required)", v_begin, v_end, ctx->chunk.active ? ctx->chunk.next : -1, ctx->chunk.nviews);
-    if (!classes || (n > 0 && !xyz) || !views_dev) return fail(ctx, F3D_ERR_INVALID, "fuse_chunk: bad arguments");
-    if ((flags & F3D_FUSE_SORT) && perm) return fail(ctx, F3D_ERR_INVALID, "fuse_chunk: F3D_FUSE_SORT and perm are exclusive");
-    hipStream_t s = pick(ctx, stream);
-    f3d_filter_args fa;
-    if ((rc = make_filter(ctx, filter, nfilter, nclasses + 1, true, s, &fa))) return rc;
-    if (v_begin == 0) {                                        // the point order is fixed by the first chunk
-        ctx->chunk.perm = perm; ctx->chunk.gather = ((flags & F3D_FUSE_GATHER) && perm) ? 1 : 0;
-        if ((flags & F3D_FUSE_SORT) && n > 512) {
-            void *sperm, *scratch;
-            if ((rc = ensure(ctx, SLOT_SORT_PERM, (size_t)n * 4, &sperm))) return rc;
-            if ((rc = ensure(ctx, SLOT_SORT_SCRATCH, f3d_sort_scratch_bytes(n), &scratch))) return rc;
-            F3D_HIP(ctx, f3d_launch_cell_sort(xyz, dtype, n, nullptr, (int32_t*)sperm, scratch, s));
-            ctx->chunk.perm = (const int32_t*)sperm; ctx->chunk.gather = 1;
-        }
-        ctx->chunk.xyz = xyz;
-    }
-    // a cloud read through a permutation and more chunks to come: the first chunk leaves it behind in cell order (context scratch),
-    // the later chunks stream that copy instead of gathering 24-byte points again
-    void* keep = nullptr;
-    if (v_begin == 0 && v_end < nviews && ctx->chunk.gather && n > 0) {
-        if ((rc = ensure(ctx, SLOT_FUSE_XYZ, (size_t)n * 3 * (dtype == F3D_F64 ? 8 : 4), &keep))) return rc;
-    }
-    const void* cxyz = ctx->chunk.xyz;
-    const bool cgather = ctx->chunk.gather != 0;
-    void *tm, *todo, *tables, *carry;
-    if ((rc = ensure(ctx, SLOT_TILED_MASKS, f3d_coded_masks_bytes(nviews, h, w), &tm))) return rc;
-    if ((rc = ensure(ctx, SLOT_TODO, f3d_fuse_todo_bytes(n, nviews, nclasses), &todo))) return rc;
-    if ((rc = ensure(ctx, SLOT_FUSE_TABLES, f3d_fuse_tables_bytes(nviews), &tables))) return rc;
-    if ((rc = ensure(ctx, SLOT_FUSE_CARRY, f3d_fuse_carry_bytes(n, nclasses), &carry))) return rc;
-    const size_t plane = f3d_coded_masks_bytes(1, h, w);
-    if (coded) tm = const_cast<uint8_t*>(coded);                // the exchange delivered coded planes: no coding, no raw masks, the exact tier reads codes
-    else F3D_HIP(ctx, f3d_launch_code_planes(masks + (size_t)v_begin * h * w, (uint8_t*)tm + (size_t)v_begin * plane, v_end - v_begin, h, w, ctx->codebook, s));
-    F3D_HIP(ctx, f3d_launch_fuse_setup(views_dev, v_begin, v_end, tables, ctx->codebook, threshold, v_begin == 0 ? (unsigned int*)todo : nullptr, s));
-    F3D_HIP(ctx, f3d_launch_fuse(cxyz, dtype, n, views_dev, nviews, masks, (const uint8_t*)tm, h, w, nclasses, fa, threshold, classes, nullptr,
-                                 ctx->dev_err, ctx->chunk.perm, cgather, (unsigned int*)todo, (int32_t*)((char*)todo + 16),
-                                 ctx->codebook, tables, v_begin, v_end, (uint32_t*)carry, keep, s));
-    if (keep) { ctx->chunk.xyz = keep; ctx->chunk.gather = 0; }
-    ctx->chunk.next = v_end;
-    if (v_end == nviews) ctx->chunk.active = 0;
-    return F3D_OK;
+    f3d_fuse_job j{};
+    j.xyz = xyz; j.dtype = dtype; j.n = n; j.perm = perm; j.views_dev = views_dev; j.nviews = nviews; j.v0 = v_begin; j.v1 = v_end;
+    j.h = h; j.w = w; j.nclasses = nclasses; j.threshold = threshold; j.classes = classes;
+    return fuse_chunk_impl(ctx, j, coded, filter, nfilter, flags, stream);
 }
 
 int f3d_debug_fastpath_audit(f3d_ctx* ctx, const void* xyz, f3d_dtype dtype, int64_t n, const f3d_view* views, int nviews, int w, int h,
@@ -869,7 +879,7 @@ int f3d_debug_fuse_deferred(f3d_ctx* ctx, void* stream, uint32_t counts[2]) {
     int rc = enter(ctx); if (rc) return rc;
     if (!counts || !ctx->scratch[SLOT_TODO].p) return fail(ctx, F3D_ERR_INVALID, "fuse_deferred: no fused call has run in this context");
     hipStream_t s = pick(ctx, stream);
-    F3D_HIP(ctx, hipMemcpyAsync(counts, ctx->scratch[SLOT_TODO].p, 8, hipMemcpyDeviceToHost, s));
+    F3D_HIP(ctx, hipMemcpyAsync(counts, f3d_fuse_todo::counters(ctx->scratch[SLOT_TODO].p), 8, hipMemcpyDeviceToHost, s));
     F3D_HIP(ctx, hipStreamSynchronize(s));
     return F3D_OK;
 }

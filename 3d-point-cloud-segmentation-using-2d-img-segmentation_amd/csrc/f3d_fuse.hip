@@ -1506,16 +1506,17 @@ size_t f3d_fuse_carry_bytes(int64_t n, int nclasses) {     // packed bins of eve
     return (size_t)((n + 2 * F3D_BLOCK - 1) / (2 * F3D_BLOCK)) * 2 * F3D_BLOCK * words_max * sizeof(uint32_t);
 }
 size_t f3d_fuse_tables_bytes(int nviews) { return (size_t)((nviews + 63) / 64) * 64 * (24 * sizeof(float) + F3D_VHEAD * sizeof(double)); }
+// the two tables of that block for `nviews` views: 24 floats per view (k_fuse's culls), then F3D_VHEAD doubles per view
+struct fuse_tables { float* ctabT; double* vtabT; };
+static fuse_tables fuse_tables_split(void* tables, int nviews) {
+    return {reinterpret_cast<float*>(tables),
+            reinterpret_cast<double*>(reinterpret_cast<char*>(tables) + (size_t)((nviews + 63) / 64) * 64 * 24 * sizeof(float))};
+}
 
-size_t f3d_fuse_lds_bytes(int mode, int nclasses) {                 // LDS of k_fuse_exact
+static size_t exact_lds_bytes(int mode, int nclasses) {               // LDS of k_fuse_exact
     const int ncols = nclasses + 1;
     const int per_word = (mode == MODE_HIST8) ? 4 : 2;
     return (size_t)((ncols + 1 + per_word - 1) / per_word) * F3D_BLOCK * sizeof(uint32_t);
-}
-
-int f3d_fuse_pick_mode(int nviews, int nfilter, bool want_votes) {
-    (void)nfilter; (void)want_votes;
-    return nviews <= 255 ? MODE_HIST8 : MODE_HIST16;
 }
 
 size_t f3d_coded_masks_bytes(int nviews, int h, int w) { return (size_t)nviews * f3d_coded_plane(h, w); }
@@ -1572,25 +1573,14 @@ hipError_t f3d_launch_code_planes(const uint8_t* src, uint8_t* dst, int nviews, 
 }
 
 // the one-shot call: presence -> [setup + book in one launch] -> coded planes
-hipError_t f3d_launch_code_masks_with_setup(const uint8_t* src, uint8_t* dst, int nviews, int h, int w, int nclasses, const f3d_filter_args& flt,
-                                            bool want_votes, f3d_codebook* cb, const f3d_view* views_dev, void* tables, double threshold,
-                                            unsigned int* todo_count, hipStream_t s) {
-    if (nviews <= 0) return hipSuccess;
-    if (nclasses < 0 || nclasses > F3D_CODE_MAX_NCLASSES || ((uintptr_t)dst & 7)) return hipErrorInvalidValue;
+hipError_t f3d_launch_code_masks_with_setup(const f3d_fuse_job& j, uint8_t* coded, f3d_codebook* cb) {
+    if (j.nviews <= 0) return hipSuccess;
+    if (j.nclasses < 0 || j.nclasses > F3D_CODE_MAX_NCLASSES || ((uintptr_t)coded & 7)) return hipErrorInvalidValue;
     hipError_t e;
-    if (pick_book(flt, want_votes) == 1 && (e = f3d_launch_mask_presence(src, (int64_t)nviews * h * w, cb, s)) != hipSuccess) return e;
-    if ((e = f3d_launch_fuse_setup(views_dev, 0, nviews, tables, cb, threshold, todo_count, s, nclasses, &flt, want_votes)) != hipSuccess) return e;
-    return f3d_launch_code_planes(src, dst, nviews, h, w, cb, s);
-}
-
-hipError_t f3d_launch_code_masks(const uint8_t* src, uint8_t* dst, int nviews, int h, int w, int nclasses, const f3d_filter_args& flt,
-                                 bool want_votes, f3d_codebook* cb, hipStream_t s) {
-    if (nviews <= 0) return hipSuccess;
-    if (nclasses < 0 || nclasses > F3D_CODE_MAX_NCLASSES || ((uintptr_t)dst & 7)) return hipErrorInvalidValue;
-    hipError_t e;
-    if (pick_book(flt, want_votes) == 1 && (e = f3d_launch_mask_presence(src, (int64_t)nviews * h * w, cb, s)) != hipSuccess) return e;
-    if ((e = f3d_launch_code_book(cb, nclasses, flt, want_votes, s)) != hipSuccess) return e;
-    return f3d_launch_code_planes(src, dst, nviews, h, w, cb, s);
+    if (pick_book(j.flt, j.votes != nullptr) == 1 &&
+        (e = f3d_launch_mask_presence(j.masks, (int64_t)j.nviews * j.h * j.w, cb, j.stream)) != hipSuccess) return e;
+    if ((e = f3d_launch_fuse_setup(j, cb, true)) != hipSuccess) return e;
+    return f3d_launch_code_planes(j.masks, coded, j.nviews, j.h, j.w, cb, j.stream);
 }
 
 // k_fuse_mid: code book, prefix / vote count / flag per point, open-view masks, the points, the bins
@@ -1598,17 +1588,24 @@ static size_t mid_lds_bytes(int words_max) {
     return (size_t)(128 + (F3D_BLOCK + 4) + 2 * F3D_BLOCK) * 4 + (size_t)F3D_BLOCK * 8 + (size_t)3 * F3D_BLOCK * 8 + (size_t)words_max * F3D_BLOCK * 4;
 }
 
-// slots of the first deferred list whose points can be parked (bins + view masks); deferred points beyond them are redone from nothing
-static int64_t fuse_park_slots(int64_t n, int nviews) {
-    if (nviews > 64 * F3D_PART_MAX_GROUPS || nviews <= 0) return 0;
-    int64_t k = n / 16 + 4096;
-    if (const char* e = getenv("F3D_DEBUG_PARK_SLOTS")) k = atoll(e);   // tests: force the overflow path (deferred points beyond the parked slots)
-    return k < n ? (k < 0 ? 0 : k) : n;
-}
-// 4 counters, two index lists of n entries (fast -> float64 tier -> exact), the view masks and the parked bins of the first list's slots
-size_t f3d_fuse_todo_bytes(int64_t n, int nviews, int nclasses) {
-    const size_t k = (size_t)fuse_park_slots(n, nviews);
-    return 16 + (size_t)n * 8 + k * ((size_t)((nviews + 63) / 64) * 8 + (size_t)((nclasses + 1 + 2 + 3) >> 2) * 4);
+// The layout of the todo block (f3d_fuse_todo, f3d_kernels.h).  The slots of the first list whose points can be parked (bins + view
+// masks) are n / 16 + 4096; deferred points beyond them are redone from nothing.
+f3d_fuse_todo f3d_fuse_todo_layout(int64_t n, int nviews, int nclasses) {
+    int64_t k = 0;
+    if (nviews > 0 && nviews <= 64 * F3D_PART_MAX_GROUPS) {
+        k = n / 16 + 4096;
+        if (const char* e = getenv("F3D_DEBUG_PARK_SLOTS")) k = atoll(e);   // tests: force the overflow path (deferred points beyond the parked slots)
+        k = k < n ? (k < 0 ? 0 : k) : n;
+    }
+    f3d_fuse_todo t;
+    t.park_slots = (int)k;
+    t.park_stride = (nclasses + 1 + 2 + 3) >> 2;              // every label 0..nclasses present, plus the codes "no sample" and "rejected"
+    t.ngroups = (nviews + 63) / 64;
+    t.list2_off = 4 * sizeof(unsigned int) + (size_t)n * sizeof(int32_t);
+    t.umask_off = t.list2_off + (size_t)n * sizeof(int32_t);
+    t.park_off = t.umask_off + (size_t)k * t.ngroups * sizeof(unsigned long long);
+    t.bytes = t.park_off + (size_t)k * t.park_stride * sizeof(uint32_t);
+    return t;
 }
 
 // The label vector is filled with the label of a point nobody votes for ("unlabelled": nclasses, through the filter remap) by
@@ -1635,35 +1632,40 @@ static hipError_t raise_lds(KernelT kernel, size_t lds) {
 }
 
 template <typename T, bool V, bool CARRY>
-static hipError_t launch_fuse_t(const void* xyz, int64_t n, const f3d_view* views_dev, int nviews, const uint8_t* masks, const uint8_t* cmasks,
-                                int h, int w, int nclasses, const f3d_filter_args& flt, double threshold, int64_t* classes, uint16_t* votes,
-                                int* err, const int32_t* perm, bool gather_xyz, unsigned int* todo_count, int32_t* todo,
-                                unsigned int* todo2_count, int32_t* todo2, const f3d_codebook* cb, void* tables, int mode, int grid,
-                                int v0, int v1, uint32_t* carry, void* xyz_keep, unsigned long long* umask, uint32_t* park, int park_slots,
-                                int park_stride, hipStream_t s) {
+static hipError_t launch_fuse_t(const f3d_fuse_job& j, int mode, int grid) {
     // CARRY: the fast kernel runs over the views [v0, v1) only and parks / resumes the vote bins in `carry`; the float64 tier and
     // the exact kernel follow the last chunk (v1 == nviews) and see every view.  Otherwise v0 = 0, v1 = nviews.
-    const bool fast = cmasks != nullptr;                     // no coded masks (nclasses > F3D_CODE_MAX_NCLASSES): exact kernel only
-    if (CARRY && (!fast || nviews > 255 || !carry || v0 < 0 || v1 <= v0 || v1 > nviews)) return hipErrorInvalidValue;
+    const int64_t n = j.n;
+    const int nviews = j.nviews, h = j.h, w = j.w, nclasses = j.nclasses, v0 = CARRY ? j.v0 : 0, v1 = CARRY ? j.v1 : j.nviews;
+    const f3d_filter_args& flt = j.flt;
+    const T* xyz = (const T*)j.xyz;
+    const int gather = j.gather ? 1 : 0;
+    hipStream_t s = j.stream;
+    // the todo block: (with coded masks its counters were zeroed by f3d_launch_fuse_setup, which must precede this call)
+    unsigned int *todo_count = f3d_fuse_todo::counters(j.todo), *todo2_count = todo_count + 1;
+    int32_t *todo = f3d_fuse_todo::list(j.todo), *todo2 = j.lay.list2(j.todo);
+    unsigned long long* umask = j.lay.umask(j.todo);
+    uint32_t* park = j.lay.park(j.todo);
+    const bool fast = j.cmasks != nullptr;                   // no coded masks (nclasses > F3D_CODE_MAX_NCLASSES): exact kernel only
+    if (CARRY && (!fast || nviews > 255 || !j.carry || v0 < 0 || v1 <= v0 || v1 > nviews)) return hipErrorInvalidValue;
     const int chunk_flags = CARRY ? ((v0 > 0 ? 1 : 0) | (v1 < nviews ? 2 : 0)) : 0;
-    const f3d_view* cviews = views_dev + v0;
-    const uint8_t* ccm = fast ? cmasks + (size_t)v0 * f3d_coded_plane(h, w) : nullptr;
+    const f3d_view* cviews = j.views_dev + v0;
+    const uint8_t* ccm = fast ? j.cmasks + (size_t)v0 * f3d_coded_plane(h, w) : nullptr;
     const int cnv = v1 - v0;
     if (fast && (n > 0x7ffff000LL || (flt.nfilter > 0 && !flt.cls_dev) || (uint64_t)nviews * f3d_coded_plane(h, w) >= (1ull << 32)))
         return hipErrorInvalidValue;                         // 32-bit point indices and mask offsets; filter list in device memory
     const dim3 g(grid), b(F3D_BLOCK), ge(fast ? 512 : grid);
-    const int words_max = (nclasses + 1 + 2 + 3) >> 2;      // every label 0..nclasses present, plus the codes "no sample" and "rejected"
+    const int words_max = j.lay.park_stride;                 // bin words of a point with every code in use
     const size_t lds_small = fuse_lds_bytes(F3D_BIN32_MAX_CODES, 2, cnv <= 64), lds_full = fuse_lds_bytes(words_max, 2, false);
-    float* ctabT = reinterpret_cast<float*>(tables);
-    double* vtabT = reinterpret_cast<double*>(reinterpret_cast<char*>(tables) + (size_t)((cnv + 63) / 64) * 64 * 24 * sizeof(float));
-    const size_t lds_exact = f3d_fuse_lds_bytes(mode, nclasses);
+    const fuse_tables tab = fuse_tables_split(j.tables, cnv);
+    const size_t lds_exact = exact_lds_bytes(mode, nclasses);
     if (lds_exact > 160 * 1024 || lds_full > 160 * 1024) return hipErrorInvalidValue;
     hipError_t e;
     int64_t prefilled = F3D_NO_PREFILL;
     if (fast && !(chunk_flags & 2)) {                        // (a chunk that parks its bins writes no labels)
         prefilled = unlabelled_after_remap(nclasses, flt);
         if (prefilled != F3D_NO_PREFILL)
-            hipLaunchKernelGGL(k_fill_labels, dim3(f3d_grid_for(n, F3D_BLOCK, 2048)), dim3(F3D_BLOCK), 0, s, classes, n, prefilled);
+            hipLaunchKernelGGL(k_fill_labels, dim3(f3d_grid_for(n, F3D_BLOCK, 2048)), dim3(F3D_BLOCK), 0, s, j.classes, n, prefilled);
     }
     if (fast) {
         // the guarded vote: an 8-bit bin of a real code can wrap (more than 255 views), or the "no sample" byte could (a point casts up to
@@ -1686,97 +1688,60 @@ static hipError_t launch_fuse_t(const void* xyz, int64_t n, const f3d_view* view
         // of codes): LDS per block decides how many blocks a CU holds, and only the device
         // knows how many labels the masks contain -- the code book says which instance runs, the others return at once
         const size_t lds_mid = fuse_lds_bytes(F3D_PACKED_SMALL_WORDS, 2, one_group);
-        hipLaunchKernelGGL(ks, g, b, lds_small, s, (const T*)xyz, n, cviews, cnv, ccm, h, w, nclasses, flt.nfilter, flt.cls_dev, threshold,
-                           classes, votes, err, perm, gather_xyz ? 1 : 0, todo_count, todo, cb, 0, F3D_BIN32_MAX_CODES, ctabT, vtabT, carry, chunk_flags, (T*)xyz_keep, umask, park, park_slots, park_stride, prefilled);
-        if (nclasses + 3 > F3D_BIN32_MAX_CODES)
-            hipLaunchKernelGGL(km2, g, b, lds_mid, s, (const T*)xyz, n, cviews, cnv, ccm, h, w, nclasses, flt.nfilter, flt.cls_dev, threshold,
-                               classes, votes, err, perm, gather_xyz ? 1 : 0, todo_count, todo, cb, F3D_BIN32_MAX_CODES + 1, 4 * F3D_PACKED_SMALL_WORDS,
-                               ctabT, vtabT, carry, chunk_flags, (T*)xyz_keep, umask, park, park_slots, park_stride, prefilled);
-        if (nclasses + 3 > 4 * F3D_PACKED_SMALL_WORDS)
-            hipLaunchKernelGGL(km3, g, b, lds_large, s, (const T*)xyz, n, cviews, cnv, ccm, h, w, nclasses, flt.nfilter, flt.cls_dev, threshold,
-                               classes, votes, err, perm, gather_xyz ? 1 : 0, todo_count, todo, cb, 4 * F3D_PACKED_SMALL_WORDS + 1, 4 * F3D_PACKED_LARGE_WORDS,
-                               ctabT, vtabT, carry, chunk_flags, (T*)xyz_keep, umask, park, park_slots, park_stride, prefilled);
-        if (nclasses + 3 > 4 * F3D_PACKED_LARGE_WORDS) {
-            hipLaunchKernelGGL(kf, g, b, lds_full, s, (const T*)xyz, n, cviews, cnv, ccm, h, w, nclasses, flt.nfilter, flt.cls_dev,
-                               threshold, classes, votes, err, perm, gather_xyz ? 1 : 0, todo_count, todo, cb, 4 * F3D_PACKED_LARGE_WORDS + 1, 256,
-                               ctabT, vtabT, carry, chunk_flags, (T*)xyz_keep, umask, park, park_slots, park_stride, prefilled);
-        }
+        auto fuse = [&](decltype(ks) kernel, size_t lds, int cmin, int cmax) {   // the instance for the books of cmin..cmax codes
+            hipLaunchKernelGGL(kernel, g, b, lds, s, xyz, n, cviews, cnv, ccm, h, w, nclasses, flt.nfilter, flt.cls_dev, j.threshold,
+                               j.classes, j.votes, j.err, j.perm, gather, todo_count, todo, j.cb, cmin, cmax, tab.ctabT, tab.vtabT,
+                               j.carry, chunk_flags, (T*)j.xyz_keep, umask, park, j.lay.park_slots, j.lay.park_stride, prefilled);
+        };
+        fuse(ks, lds_small, 0, F3D_BIN32_MAX_CODES);
+        if (nclasses + 3 > F3D_BIN32_MAX_CODES) fuse(km2, lds_mid, F3D_BIN32_MAX_CODES + 1, 4 * F3D_PACKED_SMALL_WORDS);
+        if (nclasses + 3 > 4 * F3D_PACKED_SMALL_WORDS) fuse(km3, lds_large, 4 * F3D_PACKED_SMALL_WORDS + 1, 4 * F3D_PACKED_LARGE_WORDS);
+        if (nclasses + 3 > 4 * F3D_PACKED_LARGE_WORDS) fuse(kf, lds_full, 4 * F3D_PACKED_LARGE_WORDS + 1, 256);
         if (chunk_flags & 2) return hipGetLastError();       // more view chunks to come
         // float64 tier on the deferred points' open views, the reference's arithmetic for what it cannot prove either.  Beyond 255 views a
         // point whose 8-bit bin wrapped goes on to k_fuse_exact (16-bit bins, raw masks) through a list in the second list's storage.
         const bool wide = nviews > 255;
-        if (wide && !masks) return hipErrorInvalidValue;     // (only coded planes: f3d_fuse_chunk_coded_dev, at most 255 views)
+        if (wide && !j.masks) return hipErrorInvalidValue;   // (only coded planes: f3d_fuse_chunk_coded_dev, at most 255 views)
         auto km = k_fuse_mid<T, V>;
         const size_t lds_tier2 = mid_lds_bytes(words_max);
         if ((e = raise_lds(km, lds_tier2)) != hipSuccess) return e;
-        hipLaunchKernelGGL(km, dim3(1024), b, lds_tier2, s, (const T*)xyz, todo_count, todo, views_dev, nviews, cmasks, h, w, nclasses, flt.nfilter,
-                           flt.cls_dev, threshold, classes, votes, err, perm, gather_xyz ? 1 : 0, wide ? todo_count + 2 : (unsigned int*)nullptr,
-                           wide ? todo2 : (int32_t*)nullptr, todo2_count, cb,
-                           (const unsigned long long*)umask, (const uint32_t*)park, park_slots, park_stride);
+        hipLaunchKernelGGL(km, dim3(1024), b, lds_tier2, s, xyz, todo_count, todo, j.views_dev, nviews, j.cmasks, h, w, nclasses, flt.nfilter,
+                           flt.cls_dev, j.threshold, j.classes, j.votes, j.err, j.perm, gather, wide ? todo_count + 2 : (unsigned int*)nullptr,
+                           wide ? todo2 : (int32_t*)nullptr, todo2_count, j.cb,
+                           (const unsigned long long*)umask, (const uint32_t*)park, j.lay.park_slots, j.lay.park_stride);
         if (!wide) return hipGetLastError();
     }
     const unsigned int* exact_count = fast ? todo_count + 2 : todo2_count;   // the list k_fuse_exact works on (NULL list: every point)
     const int32_t* exact_list = fast ? todo2 : nullptr;
-    if (mode == MODE_HIST8) {
-        auto ke = k_fuse_exact<T, MODE_HIST8, V>;
-        if ((e = raise_lds(ke, lds_exact)) != hipSuccess) return e;
-        hipLaunchKernelGGL(ke, ge, b, lds_exact, s, (const T*)xyz, n, exact_count, exact_list, views_dev, nviews, masks, h, w, nclasses,
-                           flt, threshold, classes, votes, err, perm, gather_xyz ? 1 : 0);
-    } else {
-        auto ke = k_fuse_exact<T, MODE_HIST16, V>;
-        if ((e = raise_lds(ke, lds_exact)) != hipSuccess) return e;
-        hipLaunchKernelGGL(ke, ge, b, lds_exact, s, (const T*)xyz, n, exact_count, exact_list, views_dev, nviews, masks, h, w, nclasses,
-                           flt, threshold, classes, votes, err, perm, gather_xyz ? 1 : 0);
-    }
+    auto ke = mode == MODE_HIST8 ? k_fuse_exact<T, MODE_HIST8, V> : k_fuse_exact<T, MODE_HIST16, V>;
+    if ((e = raise_lds(ke, lds_exact)) != hipSuccess) return e;
+    hipLaunchKernelGGL(ke, ge, b, lds_exact, s, xyz, n, exact_count, exact_list, j.views_dev, nviews, j.masks, h, w, nclasses,
+                       flt, j.threshold, j.classes, j.votes, j.err, j.perm, gather);
     return hipGetLastError();
 }
 
-// Before f3d_launch_fuse, on any stream that is joined into its stream: the threshold table of the code book (segment_point) and the
-// transposed per-view tables of the views [v0, v1) the large-alphabet instances read (tables: f3d_fuse_tables_bytes(nviews) of scratch).
-// todo_count (the 4 counters of the deferred lists; NULL for a later chunk of a view-chunked call) is zeroed here.
-hipError_t f3d_launch_fuse_setup(const f3d_view* views_dev, int v0, int v1, void* tables, f3d_codebook* cb, double threshold,
-                                 unsigned int* todo_count, hipStream_t s, int book_nclasses, const f3d_filter_args* book_flt, bool book_want_votes) {
-    // book_flt != NULL: the code book (f3d_launch_code_book's work) is built by an extra block of the same launch
-    const int cnv = v1 - v0;
+hipError_t f3d_launch_fuse_setup(const f3d_fuse_job& j, f3d_codebook* cb, bool with_book) {
+    const int v0 = j.carry ? j.v0 : 0, cnv = (j.carry ? j.v1 : j.nviews) - v0;
     if (cnv <= 0) return hipSuccess;
-    float* ctabT = reinterpret_cast<float*>(tables);
-    double* vtabT = reinterpret_cast<double*>(reinterpret_cast<char*>(tables) + (size_t)((cnv + 63) / 64) * 64 * 24 * sizeof(float));
+    const fuse_tables tab = fuse_tables_split(j.tables, cnv);
     f3d_filter_args none; none.nfilter = 0; none.cls_dev = nullptr; none.cls_host = nullptr; for (int k = 0; k < 8; ++k) none.cls[k] = -1;
-    if (book_flt && (book_nclasses < 0 || book_nclasses > F3D_CODE_MAX_NCLASSES)) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(k_fuse_setup, dim3(book_flt ? 9 : 8), dim3(F3D_BLOCK), 0, s, views_dev + v0, cnv, ctabT, vtabT, cb, threshold, todo_count,
-                       book_nclasses, book_flt ? pick_book(*book_flt, book_want_votes) : -1, book_flt ? *book_flt : none);
+    if (with_book && (j.nclasses < 0 || j.nclasses > F3D_CODE_MAX_NCLASSES)) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_fuse_setup, dim3(with_book ? 9 : 8), dim3(F3D_BLOCK), 0, j.stream, j.views_dev + v0, cnv, tab.ctabT, tab.vtabT, cb,
+                       j.threshold, v0 == 0 ? f3d_fuse_todo::counters(j.todo) : (unsigned int*)nullptr, with_book ? j.nclasses : 0,
+                       with_book ? pick_book(j.flt, j.votes != nullptr) : -1, with_book ? j.flt : none);
     return hipGetLastError();
 }
 
-hipError_t f3d_launch_fuse(const void* xyz, int dtype, int64_t n, const f3d_view* views_dev, int nviews,
-                           const uint8_t* masks, const uint8_t* cmasks, int h, int w, int nclasses, const f3d_filter_args& flt,
-                           double threshold, int64_t* classes, uint16_t* votes, int* err, const int32_t* perm, bool gather_xyz,
-                           unsigned int* todo_count, int32_t* todo, const f3d_codebook* cb, void* tables, int v0, int v1, uint32_t* carry,
-                           void* xyz_keep, hipStream_t s) {
-    // carry == NULL: one launch over all views (v0, v1 ignored).  Otherwise the views [v0, v1) of a view-chunked call: `carry` holds
-    // f3d_fuse_carry_bytes(n, nclasses) of device scratch that must survive from the chunk with v0 == 0 to the one with v1 == nviews;
-    // chunks in ascending order without gaps; no vote output.  xyz_keep (may be NULL; first chunk with gather_xyz only): n points of
-    // xyz's type, receives the cloud in perm order -- the caller passes it as xyz (gather_xyz = false, same perm) from then on.
-    // tables: f3d_fuse_tables_bytes(nviews) of device scratch.  todo_count points at 4 counters (first list, second list, 2 spare) followed by the two index lists of n entries each
-    if (n <= 0) return hipSuccess;
-    unsigned int* todo2_count = todo_count + 1;
-    int32_t* todo2 = todo + n;
-    // behind the two lists (f3d_fuse_todo_bytes): per slot of the first list the masks of the views still to be decided, then the parked bins
-    const int park_slots = (int)fuse_park_slots(n, nviews), park_stride = (nclasses + 1 + 2 + 3) >> 2, ngroups = (nviews + 63) / 64;
-    unsigned long long* umask = reinterpret_cast<unsigned long long*>(todo + 2 * n);
-    uint32_t* park = reinterpret_cast<uint32_t*>(umask + (size_t)park_slots * ngroups);
-    const int mode = f3d_fuse_pick_mode(nviews, flt.nfilter, votes != nullptr);      // bins of the exact kernel; the fast one uses 8 bits
-    const int64_t ntiles = (n + F3D_BLOCK * 2 - 1) / (F3D_BLOCK * 2);          // k_fuse: 2 points per lane
+hipError_t f3d_launch_fuse(const f3d_fuse_job& j) {
+    if (j.n <= 0) return hipSuccess;
+    const int mode = j.nviews <= 255 ? MODE_HIST8 : MODE_HIST16;               // bins of the exact kernel; the fast one uses 8 bits
+    const int64_t ntiles = (j.n + F3D_BLOCK * 2 - 1) / (F3D_BLOCK * 2);        // k_fuse: 2 points per lane
     int grid = (int)(ntiles < F3D_FUSE_GRID ? ntiles : F3D_FUSE_GRID);
     grid = (grid + 7) & ~7;                                  // the XCD-aware tile mapping needs a multiple of 8 blocks
-    if (carry && votes) return hipErrorInvalidValue;
-    if (!carry) { v0 = 0; v1 = nviews; }
-    // (with coded masks the counters of the deferred lists were zeroed by f3d_launch_fuse_setup, which must precede this call)
-#define F3D_ARGS xyz, n, views_dev, nviews, masks, cmasks, h, w, nclasses, flt, threshold, classes, votes, err, perm, gather_xyz, todo_count, todo, todo2_count, todo2, cb, tables, mode, grid, v0, v1, carry, xyz_keep, umask, park, park_slots, park_stride, s
-    if (carry) return dtype == F3D_F64 ? launch_fuse_t<double, false, true>(F3D_ARGS) : launch_fuse_t<float, false, true>(F3D_ARGS);
-    if (dtype == F3D_F64) return votes ? launch_fuse_t<double, true, false>(F3D_ARGS) : launch_fuse_t<double, false, false>(F3D_ARGS);
-    return votes ? launch_fuse_t<float, true, false>(F3D_ARGS) : launch_fuse_t<float, false, false>(F3D_ARGS);
-#undef F3D_ARGS
+    if (j.carry && j.votes) return hipErrorInvalidValue;
+    if (j.carry) return j.dtype == F3D_F64 ? launch_fuse_t<double, false, true>(j, mode, grid) : launch_fuse_t<float, false, true>(j, mode, grid);
+    if (j.dtype == F3D_F64) return j.votes ? launch_fuse_t<double, true, false>(j, mode, grid) : launch_fuse_t<double, false, false>(j, mode, grid);
+    return j.votes ? launch_fuse_t<float, true, false>(j, mode, grid) : launch_fuse_t<float, false, false>(j, mode, grid);
 }
 
 hipError_t f3d_launch_fastpath_audit(const void* xyz, int dtype, int64_t n, const f3d_view* views_dev, int nviews, int w, int h,

@@ -294,37 +294,50 @@ hipError_t f3d_launch_project_view(const void* xyz, int dtype, int64_t n, const 
                                    hipStream_t s);
 hipError_t f3d_launch_inside_polyhedra(const void* xyz, int dtype, int64_t n, const f3d_plane_args& pa, uint8_t* inside,
                                        hipStream_t s);
-size_t f3d_fuse_lds_bytes(int mode, int nclasses);
-int f3d_fuse_pick_mode(int nviews, int nfilter, bool want_votes);
-// perm (device, may be NULL): caller-order index of sorted point i.  gather_xyz = false: xyz is already the sorted copy;
-// gather_xyz = true: xyz is the caller's cloud and the kernel reads point perm[i].  todo_count / todo: device scratch
-// (1 counter + n int32) for the points the fast kernel hands to the exact kernel.  masks: the caller's [V,H,W] labels
-// (read by the exact kernel); cmasks: their coded, tiled copy made by f3d_launch_code_masks (read by the fast kernel),
-// or NULL when nclasses > F3D_CODE_MAX_NCLASSES -- the exact kernel then labels every point.
 #define F3D_CODE_MAX_NCLASSES 253            // labels 0..nclasses + "rejected" + "no sample" must fit the 256 byte codes
-size_t f3d_fuse_todo_bytes(int64_t n, int nviews, int nclasses);   // the todo_count / todo scratch of f3d_launch_fuse (counters, lists, parked bins)
-hipError_t f3d_launch_fuse(const void* xyz, int dtype, int64_t n, const f3d_view* views_dev, int nviews,
-                           const uint8_t* masks, const uint8_t* cmasks, int h, int w, int nclasses, const f3d_filter_args& flt,
-                           double threshold, int64_t* classes, uint16_t* votes, int* err, const int32_t* perm, bool gather_xyz,
-                           unsigned int* todo_count, int32_t* todo, const f3d_codebook* cb, void* tables /* f3d_fuse_tables_bytes(nviews) */,
-                           int v0, int v1, uint32_t* carry /* NULL: all views in one launch */, void* xyz_keep, hipStream_t s);
+// The SLOT_TODO scratch of a fused call: 4 counters (first list, second list, the exact kernel's list of a call
+// with more than 255 views, 1 spare); two index lists of n entries (fast kernel -> float64 tier -> exact kernel); then per parked slot of
+// the first list the open-view masks (ngroups words of 64 views) and, behind all of those, the parked bins (park_stride dwords each).
+struct f3d_fuse_todo {
+    size_t bytes, list2_off, umask_off, park_off;      // of the whole block; byte offsets (the counters and the first list have fixed ones)
+    int park_slots, park_stride, ngroups;
+    static unsigned int* counters(void* base) { return reinterpret_cast<unsigned int*>(base); }
+    static int32_t* list(void* base) { return reinterpret_cast<int32_t*>(reinterpret_cast<char*>(base) + 4 * sizeof(unsigned int)); }
+    int32_t* list2(void* base) const { return reinterpret_cast<int32_t*>(reinterpret_cast<char*>(base) + list2_off); }
+    unsigned long long* umask(void* base) const { return reinterpret_cast<unsigned long long*>(reinterpret_cast<char*>(base) + umask_off); }
+    uint32_t* park(void* base) const { return reinterpret_cast<uint32_t*>(reinterpret_cast<char*>(base) + park_off); }
+};
+f3d_fuse_todo f3d_fuse_todo_layout(int64_t n, int nviews, int nclasses);   // (reads F3D_DEBUG_PARK_SLOTS: once per C-ABI call, handed down)
 size_t f3d_fuse_tables_bytes(int nviews);
-hipError_t f3d_launch_fuse_setup(const f3d_view* views_dev, int v0, int v1, void* tables, f3d_codebook* cb, double threshold,
-                                 unsigned int* todo_count, hipStream_t s, int book_nclasses = 0, const f3d_filter_args* book_flt = nullptr,
-                                 bool book_want_votes = false);
-hipError_t f3d_launch_code_masks_with_setup(const uint8_t* src, uint8_t* dst, int nviews, int h, int w, int nclasses, const f3d_filter_args& flt,
-                                            bool want_votes, f3d_codebook* cb, const f3d_view* views_dev, void* tables, double threshold,
-                                            unsigned int* todo_count /* NULL: leave the deferred lists' counters */, hipStream_t s);
 size_t f3d_fuse_carry_bytes(int64_t n, int nclasses);
+// One fused launch.  perm (device, may be NULL): caller-order index of sorted point i.  gather = false: xyz is already the sorted copy;
+// gather = true: xyz is the caller's cloud and the kernel reads point perm[i].  cmasks: the coded, tiled copy of masks (read by the fast
+// kernel), or NULL when nclasses > F3D_CODE_MAX_NCLASSES -- the exact kernel then labels every point from the raw masks.  carry == NULL:
+// one launch over all views (v0, v1 ignored).  Otherwise the views [v0, v1) of a view-chunked call: `carry` holds f3d_fuse_carry_bytes
+// of scratch that survives from the chunk with v0 == 0 to the one with v1 == nviews; chunks ascending without gaps; no vote output.
+// xyz_keep (may be NULL; first chunk with gather only): receives the cloud in perm order -- the caller passes it as xyz from then on.
+struct f3d_fuse_job {
+    const void* xyz; int dtype; int64_t n; const int32_t* perm; bool gather;        // the cloud
+    const f3d_view* views_dev; int nviews, v0, v1;                                  // the views
+    const uint8_t *masks, *cmasks; int h, w;                                        // their masks
+    int nclasses; f3d_filter_args flt; double threshold;                            // the vote rule
+    int64_t* classes; uint16_t* votes; int* err;                                    // outputs (votes may be NULL)
+    void* todo; f3d_fuse_todo lay;                                                  // scratch: the todo block and its layout,
+    const f3d_codebook* cb; void* tables; uint32_t* carry; void* xyz_keep;          //   the code book, f3d_fuse_tables_bytes(nviews), ...
+    hipStream_t stream;
+};
+hipError_t f3d_launch_fuse(const f3d_fuse_job& job);
+// Before f3d_launch_fuse, on any stream that is joined into its stream: the threshold table of the code book (segment_point) and the
+// transposed tables of the job's views [v0, v1); v0 == 0 zeroes the deferred lists' counters.  with_book: an extra block builds the code book
+hipError_t f3d_launch_fuse_setup(const f3d_fuse_job& job, f3d_codebook* cb, bool with_book);
+// the one-shot call: presence -> [setup + book in one launch] -> job.masks coded into `coded` (f3d_coded_masks_bytes)
+hipError_t f3d_launch_code_masks_with_setup(const f3d_fuse_job& job, uint8_t* coded, f3d_codebook* cb);
 hipError_t f3d_launch_mask_presence(const uint8_t* src, int64_t nbytes, f3d_codebook* cb, hipStream_t s);
 hipError_t f3d_launch_presence_bytes(f3d_codebook* cb, uint8_t* bytes256, bool to_bytes, hipStream_t s);
 hipError_t f3d_launch_code_book(f3d_codebook* cb, int nclasses, const f3d_filter_args& flt, bool want_votes, hipStream_t s);
+// masks [V,H,W] row-major labels -> 8x8-pixel tiles of vote-bin codes (any H, W) with the book as it stands; dst holds f3d_coded_masks_bytes()
 hipError_t f3d_launch_code_planes(const uint8_t* src, uint8_t* dst, int nviews, int h, int w, const f3d_codebook* cb, hipStream_t s);
-// masks [V,H,W] row-major labels -> 8x8-pixel tiles of vote-bin codes (any H, W); dst holds f3d_coded_masks_bytes()
 size_t f3d_coded_masks_bytes(int nviews, int h, int w);
-// (builds the code book `cb` first: from filter_classes when it is short and no vote rows are wanted, else from the labels present)
-hipError_t f3d_launch_code_masks(const uint8_t* src, uint8_t* dst, int nviews, int h, int w, int nclasses, const f3d_filter_args& flt,
-                                 bool want_votes, f3d_codebook* cb, hipStream_t s);
 // audit of the fast projection (tests only): for every (point, view) pair inside the frustum counts
 // stats[0] pairs, stats[1] pairs sent to the exact fallback, stats[2] accepted pairs whose floor differs from the
 // canonical path (must stay 0), stats[3] pairs rejected/accepted by the f32 cull that the exact test contradicts (0)

@@ -688,6 +688,53 @@ def test_view_chunked_call_equals_the_one_shot_call(ctx, mask_kind):
             assert np.array_equal(got, one), ('coded', mask_kind, thr, flt, f32, bounds)
 
 
+# ---- the launcher's dispatch: which k_fuse instance a call runs is decided by the code count of its book -------------------------
+DISPATCH_N, DISPATCH_H, DISPATCH_W = 1301, 40, 56     # three 512-point tiles, the last partial and ending inside a wave; bordered planes
+# labels in the masks -> codes in the book (k_code_lut: the labels + "no sample" + "rejected").  Inside each instance's range and on both
+# sides of every boundary: dword bins <= 12 | packed small <= 48 | packed large <= 100 | any alphabet
+DISPATCH_LABELS = {5: 7, 10: 12, 11: 13, 28: 30, 46: 48, 47: 49, 73: 75, 98: 100, 99: 101, 118: 120}
+
+
+@functools.lru_cache(maxsize=None)
+def _dispatch_case(L, V):
+    """(points, view records, masks, oracle vote matrix [n, 134]) of one cell of the matrix; computed once, never written to."""
+    rng = np.random.default_rng([L, V])
+    h, w = DISPATCH_H, DISPATCH_W
+    K = np.array([[w * 0.8, 0, w / 2], [0, w * 0.8, h / 2], [0, 0, 1]])
+    q, t = synth.ring_views(V)
+    pts = synth.cloud(DISPATCH_N)                                  # float32-representable: one oracle run serves both cloud types
+    masks = rng.integers(0, L, (V, h, w), dtype=np.uint8)
+    assert len(np.unique(masks)) == L
+    votes = O.forward_votes(pts, K, q, t, masks, 10.0, ncols=134)
+    votes.setflags(write=False)
+    return pts, f3d.views_build(K, w, h, q, t, 10.0), masks, votes
+
+
+@pytest.mark.parametrize('V', [5, 65], ids=['one-group', 'two-groups'])
+@pytest.mark.parametrize('L', sorted(DISPATCH_LABELS))
+def test_fused_launcher_dispatch_matrix(ctx, L, V):
+    """Every instance of k_fuse the launcher can pick (dword bins, packed small, packed large, any alphabet), strictly inside its range
+    of code counts and on both sides of each boundary (12|13, 48|49, 100|101), with the view tables in LDS (5 views) and in global memory
+    (65 views: two groups), float64 and float32 clouds, as labels only, labels + vote rows, and view-chunked with bounds [0, 2, V].
+    nclasses = L - 1 makes nclasses + 3 the code count, so the instance that must run is the last one the launcher enqueues; the
+    labels-only call is repeated with nclasses = 133, where all four are enqueued and the book alone picks.  All equal to the oracle."""
+    assert DISPATCH_LABELS[L] == L + 2
+    pts, views, masks, votes = _dispatch_case(L, V)
+    everyone = np.arange(DISPATCH_N)
+    want = O.segment(votes[:, :L], L - 1, 0.0, None)
+    want133 = O.segment(votes, 133, 0.0, None)
+    assert (want != L - 1).mean() > 0.5 and (want133 != 133).mean() > 0.5          # real labels, not the 'unclassified' default
+    for f32 in (False, True):
+        key = (L, V, f32)
+        assert np.array_equal(_dev_fuse(ctx, pts, views, masks, None, 0.0, 0, f32=f32, nclasses=L - 1), want), key
+        assert np.array_equal(_dev_fuse(ctx, pts, views, masks, None, 0.0, 0, f32=f32), want133), key
+        cls, rows = _dev_fuse(ctx, pts, views, masks, None, 0.0, f3d.FUSE_SORT, f32=f32, nclasses=L - 1, votes_at=everyone)
+        assert np.array_equal(cls, want), key
+        assert np.array_equal(rows.astype(np.float64), votes[:, :L]), key
+        got = _dev_fuse_chunked(ctx, pts, views, masks, None, 0.0, f3d.FUSE_SORT, [0, 2, V], f32=f32, nclasses=L - 1)
+        assert np.array_equal(got, want), key
+
+
 def test_view_chunked_call_deferred_points_errors_and_sequence(ctx):
     import torch
     dev = torch.device('cuda', 0)
