@@ -36,7 +36,7 @@ enum scratch_slot { SLOT_OBB_BOXES = 0, SLOT_SORT_PERM, SLOT_SORT_SCRATCH, SLOT_
                     SLOT_PATCH, SLOT_GRP_SCRATCH, SLOT_OBB_TABLE, SLOT_OBB_FACETS, SLOT_OBB_CAND, SLOT_FUSE_TABLES, SLOT_FUSE_CARRY,
                     SLOT_FUSE_XYZ, SLOT_FUSION, SLOT_PATCH_STATUS, SLOT_NRM, SLOT_NRM_CAMS, SLOT_QRY, SLOT_FLOOD, SLOT_COLOR,
                     SLOT_CVS_INST, SLOT_CVS_STATS, SLOT_QUADS, SLOT_GROW, SLOT_PVOTE, SLOT_PVOTE_BITS, SLOT_MESH, SLOT_ZKEY,
-                    SLOT_ZCOUNTS, SLOT_KNN, SLOT_KNN_FLAG, SLOT_COUNT };
+                    SLOT_ZCOUNTS, SLOT_KNN, SLOT_KNN_FLAG, SLOT_PLANES, SLOT_COUNT };
 enum kept_slot { KEPT_GRAPH_OFFS = 0,                                      // f3d_radius_graph_count -> _fill: the offsets
                  KEPT_QRY_IN, KEPT_QRY_OFFS,                               // f3d_radius_query_count -> _fill: the queries, the offsets
                  KEPT_GRP_ORDER, KEPT_GRP_KEYS, KEPT_GRP_STARTS,           // f3d_group_by_id -> f3d_obb_extremes -> f3d_obb_hull_filter
@@ -198,6 +198,8 @@ int take_error(f3d_ctx* ctx, hipStream_t s, int mask = F3D_DEVERR_ALL) {
             return fail(ctx, F3D_ERR_INDEX, "point_vote_frames: a mask label exceeds nclasses on a pixel that has a neighbour (the reference raises IndexError at voting.py:257)");
         if (e & F3D_DEVERR_MESH)
             return fail(ctx, F3D_ERR_INDEX, "mesh: a triangle's vertex index is outside [0, nv)");
+        if (e & F3D_DEVERR_PLANES)
+            return fail(ctx, F3D_ERR_INDEX, "extract_planes: neighbour index outside [0, n)");
         if (e & F3D_DEVERR_ZVOTE)
             return fail(ctx, F3D_ERR_INDEX, "vote_visible: the mask label of a visible sample exceeds nclasses (the reference raises IndexError at voting.py:98)");
     }
@@ -1510,6 +1512,78 @@ int f3d_door_window_quads(f3d_ctx* ctx, const double* points, int64_t n, const i
     if (!st.rc) st.rc = f3d_door_window_quads_dev(ctx, dpts, n, dids, dinst, k, dverts, nv, dtris, nt, dquads, dstatus, dtri, dnrm,
                                                   ctx->stream);
     return st.finish(F3D_DEVERR_QUADS);
+}
+
+// ---------------------------------------------------------------------------------------------
+// extract_planes: the plane table of a cloud over its adjacency
+// ---------------------------------------------------------------------------------------------
+int f3d_ctx_reserve_planes(f3d_ctx* ctx, int64_t n) {
+    int rc = enter(ctx); if (rc) return rc;
+    if (n < 0 || n > 0x7fffffffLL) return fail(ctx, F3D_ERR_INVALID, "ctx_reserve_planes: bad arguments (n < 2^31)");
+    return reserve(ctx, {{SLOT_PLANES, f3d_planes_scratch_bytes(n)}});
+}
+
+static bool planes_args_bad(f3d_dtype dtype, int64_t n, const void* xyz, const void* offsets, int64_t min_points, int64_t max_rounds,
+                            int64_t max_planes, const void* labels, const void* planes, const void* corners, const void* counts) {
+    return !dtype_ok(dtype) || n < 0 || n > 0x7fffffffLL || min_points < 3 || max_rounds < 0 || max_planes < 0 || !counts ||
+           (n > 0 && (!xyz || !offsets || !labels)) || (max_planes > 0 && (!planes || !corners));
+}
+#define F3D_PLANES_BAD "extract_planes: bad arguments (n < 2^31, min_points >= 3, max_rounds >= 0, max_planes >= 0)"
+
+int f3d_extract_planes_dev(f3d_ctx* ctx, const void* xyz, f3d_dtype dtype, int64_t n, const int64_t* offsets, const int32_t* neighbours,
+                           const double* normals, double cos_angle, double offset, double dist, double max_variation, int64_t min_points,
+                           int64_t max_rounds, int64_t max_planes, int32_t* labels, double* planes, double* corners, int64_t* counts,
+                           double* normals_out, void* stream) {
+    int rc = enter(ctx); if (rc) return rc;
+    if (planes_args_bad(dtype, n, xyz, offsets, min_points, max_rounds, max_planes, labels, planes, corners, counts))
+        return fail(ctx, F3D_ERR_INVALID, F3D_PLANES_BAD);
+    hipStream_t s = pick(ctx, stream);
+    if (n == 0) {
+        F3D_HIP(ctx, hipMemsetAsync(counts, 0, 4 * sizeof(int64_t), s));
+        if (max_planes > 0) {
+            F3D_HIP(ctx, hipMemsetAsync(planes, 0, (size_t)max_planes * 8 * sizeof(double), s));
+            F3D_HIP(ctx, hipMemsetAsync(corners, 0, (size_t)max_planes * 12 * sizeof(double), s));
+        }
+        return F3D_OK;
+    }
+    void* scratch;
+    if ((rc = ensure(ctx, SLOT_PLANES, f3d_planes_scratch_bytes(n), &scratch))) return rc;
+    const f3d_planes_args a = {cos_angle, offset, dist, max_variation, min_points, max_rounds, max_planes};
+    F3D_HIP(ctx, f3d_launch_extract_planes(xyz, dtype, n, offsets, neighbours, normals, a, labels, planes, corners, counts, normals_out,
+                                           scratch, ctx->dev_err, s));
+    return F3D_OK;
+}
+
+int f3d_extract_planes(f3d_ctx* ctx, const void* xyz, f3d_dtype dtype, int64_t n, const int64_t* offsets, const int32_t* neighbours,
+                       const double* normals, double cos_angle, double offset, double dist, double max_variation, int64_t min_points,
+                       int64_t max_rounds, int64_t max_planes, int32_t* labels, double* planes, double* corners, int64_t* counts,
+                       double* normals_out) {
+    int rc = enter(ctx); if (rc) return rc;
+    if (planes_args_bad(dtype, n, xyz, offsets, min_points, max_rounds, max_planes, labels, planes, corners, counts))
+        return fail(ctx, F3D_ERR_INVALID, F3D_PLANES_BAD);
+    const int64_t e = n > 0 ? offsets[n] : 0;
+    if (e < 0 || (e > 0 && !neighbours)) return fail(ctx, F3D_ERR_INVALID, "extract_planes: bad adjacency");
+    f3d_carve c;
+    const size_t nb = (size_t)n * 24, pb = (size_t)max_planes * 64, cb = (size_t)max_planes * 96;
+    const size_t o_xyz = c.take(xyz_bytes(dtype, n)), o_offs = c.take((size_t)(n + 1) * 8), o_nbrs = c.take((size_t)e * 4), o_nin = c.take(nb),
+                 o_lab = c.take((size_t)n * 4), o_pl = c.take(pb), o_cr = c.take(cb), o_cnt = c.take(32), o_nout = c.take(nb);
+    staging st(ctx);
+    char* io = (char*)st.slot(c.off);
+    if (st.rc) return st.rc;
+    st.put(io + o_xyz, xyz, xyz_bytes(dtype, n));
+    st.put(io + o_offs, offsets, (size_t)(n + 1) * 8);
+    st.put(io + o_nbrs, neighbours, (size_t)e * 4);
+    st.put(io + o_nin, normals, nb);
+    st.back(labels, io + o_lab, (size_t)n * 4);
+    st.back(planes, io + o_pl, pb);
+    st.back(corners, io + o_cr, cb);
+    st.back(counts, io + o_cnt, 32);
+    if (!normals) st.back(normals_out, io + o_nout, nb);
+    if (!st.rc) st.rc = f3d_extract_planes_dev(ctx, io + o_xyz, dtype, n, (const int64_t*)(io + o_offs), (const int32_t*)(io + o_nbrs),
+                                               normals ? (const double*)(io + o_nin) : nullptr, cos_angle, offset, dist, max_variation, min_points,
+                                               max_rounds, max_planes, (int32_t*)(io + o_lab), (double*)(io + o_pl), (double*)(io + o_cr),
+                                               (int64_t*)(io + o_cnt), normals_out && !normals ? (double*)(io + o_nout) : nullptr, ctx->stream);
+    return st.finish(F3D_DEVERR_PLANES);
 }
 
 // ---------------------------------------------------------------------------------------------

@@ -16,7 +16,8 @@
 #define F3D_DEVERR_PVOTE 128               // point_vote_frames: a pixel with a neighbour carries a label > nclasses (voting.py:257)
 #define F3D_DEVERR_MESH 256                // meshUtils: triangle vertex index outside [0, nv)
 #define F3D_DEVERR_ZVOTE 512               // vote_visible: a visible sample's label >= ncols (voting.py:98)
-#define F3D_DEVERR_ALL 1023
+#define F3D_DEVERR_PLANES 1024             // extract_planes: neighbour index outside [0, n)
+#define F3D_DEVERR_ALL 2047
 #define F3D_PLANES_PER_LAUNCH 16
 #define F3D_OBB_MAX_BOXES 4096
 #define F3D_SORT_MAX_CELLS 32767            // + 1 overflow cell = 2^15 keys -> 16 key bits sorted
@@ -558,3 +559,12 @@ hipError_t f3d_launch_zsplat(const void* xyz, int dtype, int64_t n, const f3d_vi
 hipError_t f3d_launch_zkey_unpack(const unsigned long long* zkey, size_t cells, float* depth, int32_t* uv2pt, hipStream_t s);
 hipError_t f3d_launch_vote_visible(const void* xyz, int dtype, int64_t n, const f3d_view* views_dev, int nv, const uint8_t* masks, int h, int w,
                                    const unsigned long long* zkey, double depth_tol, double* votes, int ncols, int* err, hipStream_t s);
+
+// plane table of a cloud over its adjacency (f3d_planes.hip).  Device pointers (counts int64 [4] too); normals (may be NULL: PCA of the
+// rows) and normals_out (may be NULL; written in PCA mode only) float64 [n, 3].  n >= 1.  Enqueues on `s` and synchronises it every few
+// attach rounds.  A neighbour outside [0, n) sets F3D_DEVERR_PLANES and nothing is written.  scratch: f3d_planes_scratch_bytes(n)
+struct f3d_planes_args { double cos_angle, offset, dist, max_variation; int64_t min_points, max_rounds, max_planes; };
+size_t f3d_planes_scratch_bytes(int64_t n);
+hipError_t f3d_launch_extract_planes(const void* xyz, int dtype, int64_t n, const int64_t* offs, const int32_t* nbrs,
+                                     const double* normals, const f3d_planes_args& a, int32_t* labels, double* planes, double* corners,
+                                     int64_t* counts, double* normals_out, void* scratch, int* err, hipStream_t s);

@@ -171,6 +171,9 @@ def library():
         'f3d_mesh_clean': (i32, [vp, vp, i32, i64, vp, i32, i64, vp, i64, dbl, vp, vp, vp, vp, vp]),
         'f3d_mesh_clean_dev': (i32, [vp, vp, i32, i64, vp, i32, i64, vp, i64, dbl, vp, vp, vp, vp, vp, vp]),
         'f3d_ctx_reserve_mesh': (i32, [vp, i64, i64]),
+        'f3d_extract_planes': (i32, [vp, vp, i32, i64, vp, vp, vp, dbl, dbl, dbl, dbl, i64, i64, i64, vp, vp, vp, vp, vp]),
+        'f3d_extract_planes_dev': (i32, [vp, vp, i32, i64, vp, vp, vp, dbl, dbl, dbl, dbl, i64, i64, i64, vp, vp, vp, vp, vp, vp]),
+        'f3d_ctx_reserve_planes': (i32, [vp, i64]),
         'f3d_patch_owner': (i32, [vp, vp, i64, i32, i32, i32, dbl, dbl, vp, vp, vp, vp, vp, vp]),
         'f3d_patch_owner_dev': (i32, [vp, vp, i64, i32, i32, i32, dbl, dbl, vp, vp, vp, vp, vp, vp, vp]),
         'f3d_patch_match': (i32, [vp, vp, i64, i32, i32, i32, dbl, dbl, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
@@ -381,6 +384,10 @@ class Context:
     def reserve_mesh(self, nvertices, ntriangles):
         """Size the scratch of the mesh_*_dev calls for meshes of up to that many vertices and triangles."""
         self._check(self._lib.f3d_ctx_reserve_mesh(self._h, int(nvertices), int(ntriangles)))
+
+    def reserve_planes(self, n):
+        """Size the scratch of extract_planes_dev for clouds of up to n points, for any max_planes."""
+        self._check(self._lib.f3d_ctx_reserve_planes(self._h, int(n)))
 
     def reserve_refine(self, n):
         """Size the scratch of region_grow_dev for clouds of up to n points."""
@@ -785,6 +792,21 @@ class Context:
                                              int(min_triangles), float(min_area), _ptr(nvs), _ptr(nts), _ptr(kv), _ptr(kt), _ptr(counts)))
         return nvs[:counts[1]].copy(), nts[:counts[0]].copy(), kv, kt
 
+    def extract_planes(self, points, offsets, neighbours, normals, cos_angle, offset, dist, max_variation, min_points, max_rounds,
+                       max_planes, want_normals=False):
+        """Plane table of a cloud over its adjacency (include/f3d.h f3d_extract_planes).  points float64 / float32 [n, 3]; offsets /
+        neighbours a checked host CSR; normals float64 [n, 3] or None (PCA of the rows).  -> (labels int32 [n], planes float64
+        [P, 8], corners float64 [P, 4, 3], counts int64 [4]) (+ the computed normals [n, 3] with want_normals and normals None)."""
+        n, mp = len(points), int(max_planes)
+        rows = max(mp, 0)                                           # (a negative max_planes is the library's ValueError)
+        labels, planes, corners, counts = np.empty(n, np.int32), np.zeros((rows, 8)), np.zeros((rows, 4, 3)), np.zeros(4, np.int64)
+        nout = np.zeros((n, 3)) if want_normals and normals is None else None
+        self._check(self._lib.f3d_extract_planes(self._h, _ptr(points), dtype_code(points), n, _ptr(offsets), _ptr(neighbours), _ptr(normals),
+                                                 float(cos_angle), float(offset), float(dist), float(max_variation), int(min_points),
+                                                 int(max_rounds), mp, _ptr(labels), _ptr(planes), _ptr(corners), _ptr(counts), _ptr(nout)))
+        out = (labels, planes[:counts[0]].copy(), corners[:counts[0]].copy(), counts)
+        return out + (nout,) if want_normals else out
+
     def door_window_quads(self, points, ids, instance_ids, vertices, triangles):
         """Door / window quads of door_window_bbox.generate_mesh (include/f3d.h f3d_door_window_quads) for the distinct ids
         `instance_ids`.  -> (quads float64 [k, 4, 3], status int32 [k] (QUAD_*), chosen triangle int32 [k], triangle normals
@@ -1073,6 +1095,17 @@ class Context:
                        kept_v_ptr, kept_t_ptr, counts_ptr, stream=None):
         self._check(self._lib.f3d_mesh_clean_dev(self._h, verts_ptr, vdtype, int(nv), tris_ptr, itype, int(nt), remove_mask_ptr, int(min_triangles),
                                                  float(min_area), new_verts_ptr, new_tris_ptr, kept_v_ptr, kept_t_ptr, counts_ptr, stream))
+
+    def extract_planes_dev(self, xyz_ptr, dtype, n, offsets_ptr, neighbours_ptr, normals_ptr, cos_angle, offset, dist, max_variation,
+                           min_points, max_rounds, max_planes, labels_ptr, planes_ptr, corners_ptr, counts_ptr, normals_out_ptr=None,
+                           stream=None):
+        """f3d_extract_planes_dev: device pointers throughout (counts int64 [4] too; normals_ptr / normals_out_ptr may be None).
+        Enqueues on `stream` and synchronises it every few attach rounds; a neighbour index outside [0, n) is recorded for
+        take_device_error."""
+        self._check(self._lib.f3d_extract_planes_dev(self._h, xyz_ptr, int(dtype), int(n), offsets_ptr, neighbours_ptr, normals_ptr,
+                                                     float(cos_angle), float(offset), float(dist), float(max_variation), int(min_points),
+                                                     int(max_rounds), int(max_planes), labels_ptr, planes_ptr, corners_ptr, counts_ptr,
+                                                     normals_out_ptr, stream))
 
     def take_device_error(self, stream=None):
         self._check(self._lib.f3d_take_device_error(self._h, stream))

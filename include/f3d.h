@@ -590,6 +590,64 @@ int f3d_mesh_clean_dev(f3d_ctx* ctx, const void* verts, int vdtype, int64_t nv, 
 /* Sizes the scratch of the f3d_mesh_*_dev entries for meshes of up to nv vertices and nt triangles. */
 int f3d_ctx_reserve_mesh(f3d_ctx* ctx, int64_t nv, int64_t nt);
 
+/* ---- extract_planes: the plane table of a cloud over its adjacency (no reference counterpart) ------------------------------ */
+/* refinement.py's depth_floodfill_dl / depth_floodfill_point / door_floor_align take a plane table (PlaneswithPoints, BoundingPoints)
+ * that the reference got from a binary it does not ship (planeUtils.run_connected_executable).  This entry produces it: a
+ * deterministic plane segmentation of a cloud over its adjacency.  tests/planes_ref.py restates the contract in NumPy.
+ *
+ * Inputs.  xyz [n, 3] of `dtype` (float32 is widened exactly); offsets int64 [n + 1] / neighbours int32: a symmetric CSR adjacency
+ * without duplicate entries, as f3d_radius_graph_* produces it (the preconditions of f3d_flood_order; a row may or may not list its
+ * own point).  normals float64 [n, 3], optional: unit vectors, used as given.  dot(a, b) below is (a0*b0 + a1*b1) + a2*b2; every
+ * product, sum and difference is rounded alone.  jacobi3 is the cyclic Jacobi solver of csrc/f3d_eigen.h; of its eigenvalues w[0..3)
+ * lambda0 is the smallest (ties: the lowest index), lambda2 the largest of the other two (ties: the lowest index), lambda1 the third.
+ *   1 core     The others of point i are the entries of its row that differ from i, in row order.
+ *              normals given: i is core iff n_i's three components are finite and i has at least 2 others.
+ *              normals NULL : with at least 2 others, over the sequence i, others (m points): mean = (sum added in that order) / m;
+ *              the 6 centred second moments xx xy xz yy yz zz, each the sum of the products of (p - mean) added in that order;
+ *              jacobi3; tr = (lambda0 + lambda1) + lambda2; i is core iff tr > 0 and lambda0 / tr <= max_variation; n_i = lambda0's
+ *              eigenvector as jacobi3 returns it.  normals_out (optional, this mode only) receives n_i, 0 for a point with fewer
+ *              than 2 others.
+ *   2 edges    For adjacent core points i and j, d = p_j - p_i: the edge holds iff |dot(n_i, n_j)| >= cos_angle and
+ *              max(|dot(d, n_i)|, |dot(d, n_j)|) <= offset.  Both tests give the same bits from either end, so the relation is
+ *              symmetric on a symmetric adjacency.  Its components are found by union-find; a component's root is its lowest index.
+ *   3 planes   A component with at least min_points (>= 3) core members is a plane; planes are numbered by ascending root.
+ *              centroid c_P = S(p) / count and then the centred moments S((p - c_P)(p - c_P)^T), where S is a fixed-shape sum over
+ *              the members in ascending index: chunks of 4096 members; in a chunk item i goes to lane i mod 64, a lane adds left to
+ *              right from 0.0, the lanes meet in an xor butterfly 32, 16, .., 1; the chunk sums are summed the same way.  No float
+ *              atomics.  jacobi3 of the moment sums: n_P = lambda0's vector, u_P = lambda2's vector, v_P = n_P x u_P.  Signs: with
+ *              normals given n_P is negated when dot(n_P, n_root) < 0; without, when its component of largest magnitude (ties: the
+ *              lowest axis) is negative.  u_P follows the largest-component rule in both modes.
+ *   4 inliers  A member with |dot(p - c_P, n_P)| > dist becomes -1.  The plane is not refitted.
+ *   5 attach   Synchronous rounds.  In round t every point that held -1 at the end of round t - 1 (points that are not core and
+ *              dropped members included) looks along its row at the planes its neighbours held at the end of round t - 1 and takes
+ *              the lowest P with |dot(p - c_P, n_P)| <= dist.  The rounds end with the first round that changes nothing (it
+ *              counts), or after max_rounds; max_rounds = 0: no attaching.  The result depends on the rounds, not on thread timing.
+ *   6 quads    a = dot(p - c_P, u_P), b = dot(p - c_P, v_P) over the final members; their extents through order-preserving 64-bit
+ *              integer atomicMin / atomicMax.  Corner = (c_P + a u_P) + b v_P for (a, b) = (min, min), (max, min), (max, max),
+ *              (min, max).  The quad's area is the product of the two extents.
+ * Outputs.  labels int32 [n] (-1: no plane); planes float64 [max_planes, 8] = n_P, -dot(n_P, c_P), c_P, the rms residual
+ * sqrt(S(dot(p - c_P, n_P)^2) / count) over the final members; corners float64 [max_planes, 4, 3]; counts int64 [4] = {planes
+ * written, qualifying components, attach rounds run, labelled points}.  When more than max_planes components qualify the first
+ * max_planes by root are written and the members of the others stay -1 (counts[1] tells); rows past the planes written are zero.  A
+ * plane whose members were all dropped in step 4 and that attaches nothing keeps its number; its rms and corners are NaN.
+ * Errors.  A neighbour index outside [0, n) -> F3D_ERR_INDEX and no output is written: the host entry returns it; the _dev twin
+ * records it in a bit of its own for f3d_take_device_error, and every later kernel of the call returns at once.  n >= 2^31,
+ * min_points < 3, max_rounds < 0, max_planes < 0 -> F3D_ERR_INVALID.  n == 0: counts = 0.
+ * Two calls return identical bits.  Limits: two parallel layers closer than `offset` are one plane; with normals == NULL two layers
+ * closer than the graph's radius share their rows, so they are one plane while their spread passes max_variation and hold no core
+ * point otherwise; pass a finer graph, or normals.
+ * The _dev twin takes device pointers (counts too), enqueues on `stream` and synchronises it every few attach rounds (the changed
+ * flag stays on the device; {done, rounds} are read back).  Scratch: f3d_ctx_reserve_planes(n), for any max_planes. */
+int f3d_extract_planes(f3d_ctx* ctx, const void* xyz, f3d_dtype dtype, int64_t n, const int64_t* offsets, const int32_t* neighbours,
+                       const double* normals, double cos_angle, double offset, double dist, double max_variation, int64_t min_points,
+                       int64_t max_rounds, int64_t max_planes, int32_t* labels, double* planes, double* corners, int64_t* counts,
+                       double* normals_out);
+int f3d_extract_planes_dev(f3d_ctx* ctx, const void* xyz, f3d_dtype dtype, int64_t n, const int64_t* offsets, const int32_t* neighbours,
+                           const double* normals, double cos_angle, double offset, double dist, double max_variation, int64_t min_points,
+                           int64_t max_rounds, int64_t max_planes, int32_t* labels, double* planes, double* corners, int64_t* counts,
+                           double* normals_out, void* stream);
+int f3d_ctx_reserve_planes(f3d_ctx* ctx, int64_t n);
+
 /* ---- (f)#1: the adjacency itself, Fusion.save_data (Fusion3DSeg/fusion.py:374-375) -------- */
 /* tree = KDTree(points); adj = tree.query_radius(points, r=2*ds_radius): for every point the indices of all points
  * (itself included) whose float64 squared distance ((dx*dx + dy*dy) + dz*dz, sklearn's euclidean_rdist order) is
