@@ -20,7 +20,7 @@ from pathlib import Path
 import numpy as np
 
 import f3d
-from f3d.tensors import dtype_code, on_device, torch_device, work_stream
+from f3d.tensors import dtype_code, index_code, on_device, torch_device, work_stream
 
 
 def parse_rts(rts):
@@ -129,6 +129,97 @@ def project_vote_argmax_visible(points, K, wxyzs, translations, masks, max_depth
                              votes.data_ptr(), nclasses + 1, 0, work.cuda_stream)
         ctx.segment_votes_dev(votes.data_ptr(), len(pts), nclasses + 1, nclasses, threshold, filter_classes, cls.data_ptr(), work.cuda_stream)
         ctx.take_device_error(work.cuda_stream)                               # the IndexError of a label > nclasses (synchronises)
+    for t in (votes, cls):
+        t.record_stream(torch.cuda.current_stream(dev))
+    return (cls, votes) if return_votes else cls
+
+
+def _device_mesh(torch, dev, vertices, triangles):
+    """(vertices float64 / float32 [V,3], triangles int64 / int32 [M,3]) as contiguous tensors on `dev`."""
+    to_t = lambda a: a if isinstance(a, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(a))   # noqa: E731
+    verts = _device_cloud(torch, dev, to_t(vertices))
+    tris = to_t(triangles).to(dev)
+    if tris.dtype not in (torch.int32, torch.int64):
+        raise TypeError(f'triangles must be int32 or int64, got {tris.dtype}')
+    if tris.dim() != 2 or tris.shape[1] != 3:
+        raise ValueError(f'triangles must be [M,3], got {tuple(tris.shape)}')
+    return verts, tris.contiguous()
+
+
+def render_mesh_lookups(vertices, triangles, K, wxyzs, translations, hw, max_depth=10):
+    """Per-view depth buffers and pixel -> triangle lookups of a posed triangle mesh, rasterised on the GPU.
+
+    What ``render_lookups`` gives for a cloud, from a watertight surface: no splat size to choose, no gaps for the surface behind to
+    show through.  A pixel is covered when its centre lies inside a triangle's projection (edges inclusive, evaluated so that the two
+    triangles sharing an edge never both miss it); the depth is perspective-correct; per pixel the nearest float32 depth wins, ties
+    go to the lowest triangle index; fragments beyond ``max_depth`` are dropped (f3d.h, f3d_render_mesh_lookups).  There is no
+    near-plane clipping: a triangle that crosses the camera plane is skipped and counted in ``straddling`` -- subdivide coarse meshes.
+
+    Returns depth float32 [V,H,W] (+inf = empty), uv2tri int32 [V,H*W] (-1 = empty), straddling int64 [V].  NumPy in, NumPy out;
+    torch device tensors for the mesh give device tensors, ordered with torch's current stream."""
+    H, W = (int(x) for x in hw)
+    views = f3d.views_build(K, W, H, wxyzs, translations, max_depth)
+    ctx = f3d.default_context()
+    if not (on_device(vertices) or on_device(triangles)):
+        return ctx.render_mesh_lookups(vertices, triangles, views, H, W, max_depth)
+    torch, dev = torch_device(ctx, 'render_mesh_lookups')
+    verts, tris = _device_mesh(torch, dev, vertices, triangles)
+    with torch.cuda.device(dev), work_stream(dev) as work:
+        dviews = torch.from_numpy(views).to(dev)
+        depth = torch.empty((len(views), H, W), dtype=torch.float32, device=dev)
+        uv2tri = torch.empty((len(views), H * W), dtype=torch.int32, device=dev)
+        straddling = torch.empty(len(views), dtype=torch.int64, device=dev)
+        ctx.render_mesh_lookups_dev(verts.data_ptr(), dtype_code(verts), len(verts), tris.data_ptr(), index_code(tris), len(tris), dviews.data_ptr(),
+                                    len(views), H, W, max_depth, depth.data_ptr(), uv2tri.data_ptr(), straddling.data_ptr(), work.cuda_stream)
+        ctx.take_device_error(work.cuda_stream)                               # the IndexError of a bad vertex index (synchronises)
+    for t in (depth, uv2tri, straddling):
+        t.record_stream(torch.cuda.current_stream(dev))
+    return depth, uv2tri, straddling
+
+
+def project_vote_argmax_occluded(points, vertices, triangles, K, wxyzs, translations, masks, max_depth=10, nclasses=133, threshold=0.5,
+                                 filter_classes=None, return_votes=False, depth_tol=0.05):
+    """``project_vote_argmax_visible`` with a triangle mesh of the scene as the occluder instead of a splat of the cloud itself.
+
+    The mesh is rasterised into every view as for ``render_mesh_lookups``; a point's sample votes iff its float32 depth is within
+    ``depth_tol`` of the mesh depth of its pixel, and a pixel no triangle covers hides nothing (f3d.h, f3d_vote_visible_mesh).  A mesh
+    neither leaks between the cloud's points nor fattens silhouettes.  With ``depth_tol=inf`` the votes are those of
+    ``project_vote_argmax``.  A label > nclasses on a visible sample, or a vertex index outside the mesh, raises IndexError.
+
+    Returns int64 [N] (and float64 [N, nclasses+1] votes).  NumPy in, NumPy out; torch device tensors for ``points``, ``masks`` or the
+    mesh give device tensors, ordered with torch's current stream, with no host round trip."""
+    ctx = f3d.default_context()
+    device = on_device(points) or on_device(masks) or on_device(vertices) or on_device(triangles)
+    if not device:
+        masks = np.ascontiguousarray(masks, dtype=np.uint8)
+    if masks.ndim != 3:
+        raise ValueError('masks must be uint8 [V,H,W]')
+    V, H, W = (int(x) for x in masks.shape)
+    views = f3d.views_build(K, W, H, wxyzs, translations, max_depth)
+    if len(views) != V:
+        raise ValueError(f'{len(views)} poses for {V} masks')
+    if not device:
+        votes = np.zeros((len(points), nclasses + 1))
+        ctx.vote_visible_mesh(votes, points, vertices, triangles, views, masks, max_depth, depth_tol)
+        cls = ctx.segment_votes(votes, nclasses, threshold, filter_classes)
+        return (cls, votes) if return_votes else cls
+    torch, dev = torch_device(ctx, 'project_vote_argmax_occluded')
+    to_t = lambda a: a if isinstance(a, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(a))   # noqa: E731
+    pts = _device_cloud(torch, dev, to_t(points))
+    verts, tris = _device_mesh(torch, dev, vertices, triangles)
+    dmasks = to_t(masks).to(dev)
+    if dmasks.dtype != torch.uint8:
+        raise ValueError(f'masks must be uint8, got {dmasks.dtype}')
+    dmasks = dmasks.contiguous()
+    with torch.cuda.device(dev), work_stream(dev) as work:
+        dviews = torch.from_numpy(views).to(dev)
+        votes = torch.zeros((len(pts), nclasses + 1), dtype=torch.float64, device=dev)
+        cls = torch.empty(len(pts), dtype=torch.int64, device=dev)
+        ctx.vote_visible_mesh_dev(pts.data_ptr(), dtype_code(pts), len(pts), verts.data_ptr(), dtype_code(verts), len(verts), tris.data_ptr(),
+                                  index_code(tris), len(tris), dviews.data_ptr(), V, dmasks.data_ptr(), H, W, max_depth, depth_tol,
+                                  votes.data_ptr(), nclasses + 1, 0, work.cuda_stream)
+        ctx.segment_votes_dev(votes.data_ptr(), len(pts), nclasses + 1, nclasses, threshold, filter_classes, cls.data_ptr(), work.cuda_stream)
+        ctx.take_device_error(work.cuda_stream)                               # the IndexErrors (synchronises)
     for t in (votes, cls):
         t.record_stream(torch.cuda.current_stream(dev))
     return (cls, votes) if return_votes else cls

@@ -15,7 +15,7 @@ import numpy as np
 import f3d
 from f3d.tensors import dtype_code, index_code, on_device, work_stream
 
-__all__ = ['vertex_triangle_mapping', 'remove_faces_by_vertices', 'keep_faces_by_vertices', 'get_triangle_clusters', 'clean_mesh',
+__all__ = ['vertex_triangle_mapping', 'remove_faces_by_vertices', 'keep_faces_by_vertices', 'get_triangle_clusters', 'clean_mesh', 'label_faces',
            'bbox_axes', 'one_to_all_angles', 'VertexTriangleMap']
 
 
@@ -283,7 +283,66 @@ def clean_mesh(vertices, triangles, remove_mask=None, min_triangles=1, min_area=
     return nvs[:p], nts[:q], kv, kt
 
 
-# ------------------------------------------------------------------------------------------------ 6. host helpers
+# ------------------------------------------------------------------------------------------------ 6. face labels
+def label_faces(vertices, *args, **kwargs):
+    """label_faces(vertices, triangles, K, wxyzs, translations, masks, max_depth=10, nclasses=133, threshold=0.5,
+    filter_classes=None, return_votes=False), or with a mesh (``.vertices`` / ``.triangles`` as get3DSeg.TriangleMesh has them, or a
+    ``(vertices, triangles)`` pair) in place of the first two arguments.
+
+    Label the faces of a posed mesh from V masks (no reference counterpart): the mesh is rasterised into every view, every covered
+    pixel votes for the triangle it sees with its mask label (f3d.h, f3d_vote_faces: the reference's voting direction, one row per
+    triangle, a (triangle, label) pair counting once per view), and ``VotingSegmentation.segment`` picks the classes.  masks uint8
+    [V,H,W].  Fragments beyond ``max_depth`` are dropped; triangles crossing the camera plane are skipped (no near-plane clipping).
+
+    Returns int64 [M] classes (and float64 [M, nclasses+1] votes).  NumPy in, NumPy out; device tensors in (the triangles decide)
+    give device tensors.  A label > nclasses on a covered pixel, or a vertex index outside [0, V), raises IndexError."""
+    if isinstance(vertices, tuple) or (hasattr(vertices, 'vertices') and hasattr(vertices, 'triangles')):
+        return _label_faces(*_mesh_parts(vertices), *args, **kwargs)
+    return _label_faces(vertices, *args, **kwargs)
+
+
+def _label_faces(vertices, triangles, K, wxyzs, translations, masks, max_depth=10, nclasses=133, threshold=0.5, filter_classes=None,
+                 return_votes=False):
+    tris = _triangles(triangles)
+    if tris.shape[0] >= 1 << 31:
+        raise ValueError('M must be below 2^31')
+    verts = _vertices(vertices, tris)
+    ctx = _ctx(tris)
+    device = on_device(tris)
+    if not device:
+        masks = np.ascontiguousarray(masks.cpu() if on_device(masks) else masks, dtype=np.uint8)
+    if masks.ndim != 3:
+        raise ValueError('masks must be uint8 [V,H,W]')
+    V, H, W = (int(x) for x in masks.shape)
+    views = f3d.views_build(K, W, H, wxyzs, translations, max_depth)
+    if len(views) != V:
+        raise ValueError(f'{len(views)} poses for {V} masks')
+    nt, ncols = tris.shape[0], nclasses + 1
+    if not device:
+        votes = np.zeros((nt, ncols))
+        ctx.vote_faces(votes, verts, tris, views, masks, max_depth)
+        cls = ctx.segment_votes(votes, nclasses, threshold, filter_classes)
+        return (cls, votes) if return_votes else cls
+    import torch
+    dev = tris.device
+    dmasks = torch.as_tensor(masks, device=dev)
+    if dmasks.dtype != torch.uint8:
+        raise ValueError(f'masks must be uint8, got {dmasks.dtype}')
+    dmasks = dmasks.contiguous()
+    with torch.cuda.device(dev), work_stream(dev) as work:
+        dviews = torch.from_numpy(views).to(dev)
+        votes = torch.zeros((nt, ncols), dtype=torch.float64, device=dev)
+        cls = torch.empty(nt, dtype=torch.int64, device=dev)
+        ctx.vote_faces_dev(verts.data_ptr(), dtype_code(verts), verts.shape[0], tris.data_ptr(), index_code(tris), nt, dviews.data_ptr(), V,
+                           dmasks.data_ptr(), H, W, max_depth, votes.data_ptr(), ncols, 0, work.cuda_stream)
+        ctx.segment_votes_dev(votes.data_ptr(), nt, ncols, nclasses, threshold, filter_classes, cls.data_ptr(), work.cuda_stream)
+        ctx.take_device_error(work.cuda_stream)                               # the IndexErrors (synchronises)
+    for t in (votes, cls):
+        t.record_stream(torch.cuda.current_stream(dev))
+    return (cls, votes) if return_votes else cls
+
+
+# ------------------------------------------------------------------------------------------------ 7. host helpers
 def bbox_axes(corners):
     """Origin, unit x and y axes and their lengths of an oriented box from its 8 corners in Open3D's order (reference :336-357):
     the x axis is the longest of the three edges at corner 0, the y axis the middle one; the origin is the midpoint of corners

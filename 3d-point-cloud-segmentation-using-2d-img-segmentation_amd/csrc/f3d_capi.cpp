@@ -36,7 +36,7 @@ enum scratch_slot { SLOT_OBB_BOXES = 0, SLOT_SORT_PERM, SLOT_SORT_SCRATCH, SLOT_
                     SLOT_PATCH, SLOT_GRP_SCRATCH, SLOT_OBB_TABLE, SLOT_OBB_FACETS, SLOT_OBB_CAND, SLOT_FUSE_TABLES, SLOT_FUSE_CARRY,
                     SLOT_FUSE_XYZ, SLOT_FUSION, SLOT_PATCH_STATUS, SLOT_NRM, SLOT_NRM_CAMS, SLOT_QRY, SLOT_FLOOD, SLOT_COLOR,
                     SLOT_CVS_INST, SLOT_CVS_STATS, SLOT_QUADS, SLOT_GROW, SLOT_PVOTE, SLOT_PVOTE_BITS, SLOT_MESH, SLOT_ZKEY,
-                    SLOT_ZCOUNTS, SLOT_KNN, SLOT_KNN_FLAG, SLOT_PLANES, SLOT_COUNT };
+                    SLOT_ZCOUNTS, SLOT_KNN, SLOT_KNN_FLAG, SLOT_PLANES, SLOT_RASTER, SLOT_ZLUT, SLOT_COUNT };
 enum kept_slot { KEPT_GRAPH_OFFS = 0,                                      // f3d_radius_graph_count -> _fill: the offsets
                  KEPT_QRY_IN, KEPT_QRY_OFFS,                               // f3d_radius_query_count -> _fill: the queries, the offsets
                  KEPT_GRP_ORDER, KEPT_GRP_KEYS, KEPT_GRP_STARTS,           // f3d_group_by_id -> f3d_obb_extremes -> f3d_obb_hull_filter
@@ -200,6 +200,8 @@ int take_error(f3d_ctx* ctx, hipStream_t s, int mask = F3D_DEVERR_ALL) {
             return fail(ctx, F3D_ERR_INDEX, "mesh: a triangle's vertex index is outside [0, nv)");
         if (e & F3D_DEVERR_PLANES)
             return fail(ctx, F3D_ERR_INDEX, "extract_planes: neighbour index outside [0, n)");
+        if (e & F3D_DEVERR_RASTER)
+            return fail(ctx, F3D_ERR_INDEX, "mesh render: a triangle's vertex index is outside [0, nv)");
         if (e & F3D_DEVERR_ZVOTE)
             return fail(ctx, F3D_ERR_INDEX, "vote_visible: the mask label of a visible sample exceeds nclasses (the reference raises IndexError at voting.py:98)");
     }
@@ -942,19 +944,19 @@ int f3d_vote_uv2pt_dev(f3d_ctx* ctx, const int32_t* uv2pt, const uint8_t* mask, 
     return F3D_OK;
 }
 
-int f3d_vote_uv2pt_batch_dev(f3d_ctx* ctx, const int32_t* luts, const uint8_t* masks, int64_t nframes, int h, int w, double* votes,
-                             int64_t npts, int ncols, void* stream) {
-    int rc = enter(ctx); if (rc) return rc;
-    const int64_t hw = (int64_t)h * w;
-    if (nframes < 0 || h < 0 || w < 0 || npts < 0 || npts >= ((int64_t)1 << 31) || ncols <= 0 || ncols > 256 ||
-        (nframes > 0 && hw > 0 && (!luts || !masks || !votes)))
-        return fail(ctx, F3D_ERR_INVALID, "vote_uv2pt_batch: bad arguments (npts < 2^31, ncols <= 256)");
-    if (nframes == 0 || hw == 0) return F3D_OK;
-    hipStream_t s = pick(ctx, stream);
-    // frames per launch: at most 1023 (10 bits of the key) and at most 2^25 lookups (a 512 MiB set at load <= 1/2)
+// frames per launch of the batched vote: at most 1023 (10 bits of the key) and at most 2^25 lookups (a 512 MiB set at load <= 1/2)
+static int64_t vote_batch_frames(int64_t hw) {
     int64_t per = ((int64_t)1 << 25) / hw;
     if (per < 1) per = 1;
-    if (per > 1023) per = 1023;
+    return per > 1023 ? 1023 : per;
+}
+
+// The launches of f3d_vote_uv2pt_batch_dev, arguments checked (nframes, hw > 0): also the vote of f3d_vote_faces_dev's passes.
+static int vote_batch_enqueue(f3d_ctx* ctx, const int32_t* luts, const uint8_t* masks, int64_t nframes, int h, int w, double* votes,
+                              int64_t npts, int ncols, hipStream_t s) {
+    int rc;
+    const int64_t hw = (int64_t)h * w;
+    const int64_t per = vote_batch_frames(hw);
     const int64_t first = nframes < per ? nframes : per;
     if ((rc = ensure_table(ctx, first * hw))) return rc;
     F3D_HIP(ctx, hipMemsetAsync(ctx->first_bad, 0x7f, sizeof(int), s));                        // 0x7f7f7f7f: no bad frame
@@ -971,6 +973,17 @@ int f3d_vote_uv2pt_batch_dev(f3d_ctx* ctx, const int32_t* luts, const uint8_t* m
                                                  ctx->first_bad, ctx->dev_err, s));
     }
     return F3D_OK;
+}
+
+int f3d_vote_uv2pt_batch_dev(f3d_ctx* ctx, const int32_t* luts, const uint8_t* masks, int64_t nframes, int h, int w, double* votes,
+                             int64_t npts, int ncols, void* stream) {
+    int rc = enter(ctx); if (rc) return rc;
+    const int64_t hw = (int64_t)h * w;
+    if (nframes < 0 || h < 0 || w < 0 || npts < 0 || npts >= ((int64_t)1 << 31) || ncols <= 0 || ncols > 256 ||
+        (nframes > 0 && hw > 0 && (!luts || !masks || !votes)))
+        return fail(ctx, F3D_ERR_INVALID, "vote_uv2pt_batch: bad arguments (npts < 2^31, ncols <= 256)");
+    if (nframes == 0 || hw == 0) return F3D_OK;
+    return vote_batch_enqueue(ctx, luts, masks, nframes, h, w, votes, npts, ncols, pick(ctx, stream));
 }
 
 int f3d_vote_uv2pt_batch(f3d_ctx* ctx, const int32_t* luts, const uint8_t* masks, int64_t nframes, int h, int w, double* votes,
@@ -2603,7 +2616,7 @@ int f3d_render_lookups_dev(f3d_ctx* ctx, const void* xyz, f3d_dtype dtype, int64
         F3D_HIP(ctx, f3d_launch_zkey_fill(zkey, (size_t)nv * hw, s));
         F3D_HIP(ctx, f3d_launch_zsplat(xyz, dtype, n, views_dev + v0, nv, h, w, splat, zkey, nullptr, s));
         F3D_HIP(ctx, f3d_launch_zkey_unpack(zkey, (size_t)nv * hw, depth ? depth + (size_t)v0 * hw : nullptr,
-                                            uv2pt ? uv2pt + (size_t)v0 * hw : nullptr, s));
+                                            uv2pt ? uv2pt + (size_t)v0 * hw : nullptr, nullptr, s));
     }
     return F3D_OK;
 }
@@ -2641,7 +2654,7 @@ int f3d_vote_visible_dev(f3d_ctx* ctx, const void* xyz, f3d_dtype dtype, int64_t
         F3D_HIP(ctx, f3d_launch_zkey_fill(zkey, (size_t)nv * hw, s));
         F3D_HIP(ctx, f3d_launch_zsplat(xyz, dtype, n, views_dev + v0, nv, h, w, splat, zkey, nullptr, s));
         F3D_HIP(ctx, f3d_launch_vote_visible(xyz, dtype, n, views_dev + v0, nv, masks + (size_t)v0 * hw, h, w, zkey, depth_tol, votes, ncols,
-                                             ctx->dev_err, s));
+                                             nullptr, ctx->dev_err, s));
     }
     return F3D_OK;
 }
@@ -2695,6 +2708,226 @@ int f3d_debug_render_counts(f3d_ctx* ctx, const void* xyz, f3d_dtype dtype, int6
     F3D_HIP(ctx, hipMemcpyAsync(counts, cnt, 3 * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
     F3D_HIP(ctx, hipStreamSynchronize(s));
     if (ms) { ms[0] = fill_ms; ms[1] = splat_ms; }
+    return F3D_OK;
+}
+
+// ---------------------------------------------------------------------------------------------
+// triangle-mesh z-buffer renders: face voting and mesh occlusion (f3d_raster.hip)
+// ---------------------------------------------------------------------------------------------
+#define F3D_RASTER_BAD "bad arguments (nv < 2^31, nt < 2^31, float64 / float32 vertices, int64 / int32 triangles, h, w > 0, h * w <= 2^30, z_far not NaN)"
+
+struct raster_mesh { const void* verts; f3d_dtype vdtype; int64_t nv; const void* tris; int itype; int64_t nt; };
+
+static bool raster_args_ok(const raster_mesh& m, const void* views, int nviews, int h, int w, double z_far) {
+    return m.nv >= 0 && m.nv <= 0x7fffffffLL && m.nt >= 0 && m.nt <= 0x7fffffffLL && dtype_ok(m.vdtype) && (m.itype == F3D_I64 || m.itype == F3D_I32) &&
+           nviews >= 0 && h > 0 && w > 0 && (int64_t)h * w <= ((int64_t)1 << 30) && z_far == z_far &&
+           (m.nv == 0 || m.verts) && (m.nt == 0 || m.tris) && (nviews == 0 || views);
+}
+
+// views of a face-vote pass: a pass is also one launch of the batched vote
+static int raster_vote_pass_views(int nviews, int h, int w, int views_per_pass) {
+    const int per = render_pass_views(nviews, h, w, views_per_pass);
+    const int64_t frames = vote_batch_frames((int64_t)h * w);
+    return per < frames ? per : (int)frames;
+}
+
+int f3d_ctx_reserve_mesh_render(f3d_ctx* ctx, int nviews, int h, int w) {
+    int rc = enter(ctx); if (rc) return rc;
+    if (nviews < 0 || h <= 0 || w <= 0 || (int64_t)h * w > ((int64_t)1 << 30)) return fail(ctx, F3D_ERR_INVALID, "ctx_reserve_mesh_render: bad arguments");
+    const size_t hw = (size_t)h * w;
+    const int vper = raster_vote_pass_views(nviews, h, w, 0);
+    return reserve(ctx, {{SLOT_ZKEY, (size_t)render_pass_views(nviews, h, w, 0) * hw * 8}, {SLOT_RASTER, f3d_raster_scratch_bytes(F3D_RASTER_LIST_CAP)},
+                         {SLOT_ZLUT, (size_t)vper * hw * 4}}, (int64_t)vper * (int64_t)hw);
+}
+
+// the scratch every mesh render starts with: keys of `per` views, the rasteriser's block (cleared, the index pre-pass enqueued)
+static int raster_begin(f3d_ctx* ctx, const raster_mesh& m, int nviews, int per, size_t hw, int64_t* straddling, hipStream_t s,
+                        unsigned long long** zkey, void** rs) {
+    int rc;
+    void* zk;
+    if ((rc = ensure(ctx, SLOT_ZKEY, (size_t)per * hw * 8, &zk))) return rc;
+    if ((rc = ensure(ctx, SLOT_RASTER, f3d_raster_scratch_bytes(F3D_RASTER_LIST_CAP), rs))) return rc;
+    *zkey = (unsigned long long*)zk;
+    F3D_HIP(ctx, f3d_launch_raster_check(m.tris, m.itype, m.nt, m.nv, *rs, nviews, (long long*)straddling, ctx->dev_err, s));
+    return F3D_OK;
+}
+
+static int raster_pass(f3d_ctx* ctx, const raster_mesh& m, const f3d_view* views_dev, int v0, int nv, int h, int w, double z_far,
+                       unsigned long long* zkey, int64_t* straddling, void* rs, unsigned list_cap, bool stats, hipStream_t s) {
+    F3D_HIP(ctx, f3d_launch_zkey_fill(zkey, (size_t)nv * h * w, s));       // (also under a bad index: the keys then stay empty)
+    F3D_HIP(ctx, f3d_launch_raster(m.verts, m.vdtype, m.tris, m.itype, m.nt, views_dev, v0, nv, h, w, z_far, zkey, (long long*)straddling, rs, list_cap,
+                                   stats, s));
+    return F3D_OK;
+}
+
+static const int* raster_flag(const void* rs) { return (const int*)((const char*)rs + f3d_raster_scratch_layout(0).flag); }
+
+int f3d_render_mesh_lookups_dev(f3d_ctx* ctx, const void* verts, f3d_dtype vdtype, int64_t nv, const void* tris, int itype, int64_t nt,
+                                const f3d_view* views_dev, int nviews, int h, int w, double z_far, float* depth, int32_t* uv2tri,
+                                int64_t* straddling, void* stream) {
+    int rc = enter(ctx); if (rc) return rc;
+    const raster_mesh m{verts, vdtype, nv, tris, itype, nt};
+    if (!raster_args_ok(m, views_dev, nviews, h, w, z_far)) return fail(ctx, F3D_ERR_INVALID, "render_mesh_lookups: " F3D_RASTER_BAD);
+    if (nviews == 0 || (!depth && !uv2tri && !straddling)) return F3D_OK;
+    hipStream_t s = pick(ctx, stream);
+    const size_t hw = (size_t)h * w;
+    const int per = render_pass_views(nviews, h, w, 0);
+    unsigned long long* zkey; void* rs;
+    if ((rc = raster_begin(ctx, m, nviews, per, hw, straddling, s, &zkey, &rs))) return rc;
+    for (int v0 = 0; v0 < nviews; v0 += per) {
+        const int nvp = nviews - v0 < per ? nviews - v0 : per;
+        if ((rc = raster_pass(ctx, m, views_dev, v0, nvp, h, w, z_far, zkey, straddling, rs, F3D_RASTER_LIST_CAP, false, s))) return rc;
+        F3D_HIP(ctx, f3d_launch_zkey_unpack(zkey, (size_t)nvp * hw, depth ? depth + (size_t)v0 * hw : nullptr,
+                                            uv2tri ? uv2tri + (size_t)v0 * hw : nullptr, raster_flag(rs), s));
+    }
+    return F3D_OK;
+}
+
+int f3d_render_mesh_lookups(f3d_ctx* ctx, const void* verts, f3d_dtype vdtype, int64_t nv, const void* tris, int itype, int64_t nt,
+                            const f3d_view* views, int nviews, int h, int w, double z_far, float* depth, int32_t* uv2tri, int64_t* straddling) {
+    int rc = enter(ctx); if (rc) return rc;
+    const raster_mesh m{verts, vdtype, nv, tris, itype, nt};
+    if (!raster_args_ok(m, views, nviews, h, w, z_far)) return fail(ctx, F3D_ERR_INVALID, "render_mesh_lookups: " F3D_RASTER_BAD);
+    if (nviews == 0) return F3D_OK;
+    const size_t cells = (size_t)nviews * h * w;
+    staging st(ctx);
+    const void* dverts = st.in(verts, xyz_bytes(vdtype, nv));
+    const void* dtris = st.in(tris, tri_bytes(itype, nt));
+    const f3d_view* dviews = st.in(views, sizeof(f3d_view) * (size_t)nviews);
+    float* ddepth = st.out(depth, cells * 4);
+    int32_t* dlut = st.out(uv2tri, cells * 4);
+    int64_t* dstr = st.out(straddling, (size_t)nviews * 8);
+    if (!st.rc) st.rc = f3d_render_mesh_lookups_dev(ctx, dverts, vdtype, nv, dtris, itype, nt, dviews, nviews, h, w, z_far, ddepth, dlut, dstr, ctx->stream);
+    return st.finish(F3D_DEVERR_RASTER);                                     // nothing is written back on a bad index
+}
+
+int f3d_vote_faces_dev(f3d_ctx* ctx, const void* verts, f3d_dtype vdtype, int64_t nv, const void* tris, int itype, int64_t nt,
+                       const f3d_view* views_dev, int nviews, const uint8_t* masks, int h, int w, double z_far, double* votes, int ncols,
+                       int views_per_pass, void* stream) {
+    int rc = enter(ctx); if (rc) return rc;
+    const raster_mesh m{verts, vdtype, nv, tris, itype, nt};
+    if (!raster_args_ok(m, views_dev, nviews, h, w, z_far) || ncols <= 0 || ncols > 256 || views_per_pass < 0 || (nt > 0 && !votes) || (nviews > 0 && !masks))
+        return fail(ctx, F3D_ERR_INVALID, "vote_faces: " F3D_RASTER_BAD ", 0 < ncols <= 256, views_per_pass >= 0");
+    if (nt == 0 || nviews == 0) return F3D_OK;
+    hipStream_t s = pick(ctx, stream);
+    const size_t hw = (size_t)h * w;
+    const int per = raster_vote_pass_views(nviews, h, w, views_per_pass);
+    unsigned long long* zkey; void *rs, *lut;
+    if ((rc = raster_begin(ctx, m, nviews, per, hw, nullptr, s, &zkey, &rs))) return rc;
+    if ((rc = ensure(ctx, SLOT_ZLUT, (size_t)per * hw * 4, &lut))) return rc;
+    for (int v0 = 0; v0 < nviews; v0 += per) {                               // a pass: raster, unpack, the batched uv2pt vote over its lookups
+        const int nvp = nviews - v0 < per ? nviews - v0 : per;
+        if ((rc = raster_pass(ctx, m, views_dev, v0, nvp, h, w, z_far, zkey, nullptr, rs, F3D_RASTER_LIST_CAP, false, s))) return rc;
+        // (under a bad index the keys stay empty, the lookups are all -1 and nothing votes)
+        F3D_HIP(ctx, f3d_launch_zkey_unpack(zkey, (size_t)nvp * hw, nullptr, (int32_t*)lut, nullptr, s));
+        if ((rc = vote_batch_enqueue(ctx, (const int32_t*)lut, masks + (size_t)v0 * hw, nvp, h, w, votes, nt, ncols, s))) return rc;
+    }
+    return F3D_OK;
+}
+
+int f3d_vote_faces(f3d_ctx* ctx, const void* verts, f3d_dtype vdtype, int64_t nv, const void* tris, int itype, int64_t nt,
+                   const f3d_view* views, int nviews, const uint8_t* masks, int h, int w, double z_far, double* votes, int ncols,
+                   int views_per_pass) {
+    int rc = enter(ctx); if (rc) return rc;
+    const raster_mesh m{verts, vdtype, nv, tris, itype, nt};
+    if (!raster_args_ok(m, views, nviews, h, w, z_far) || ncols <= 0 || ncols > 256 || views_per_pass < 0 || (nt > 0 && !votes) || (nviews > 0 && !masks))
+        return fail(ctx, F3D_ERR_INVALID, "vote_faces: " F3D_RASTER_BAD ", 0 < ncols <= 256, views_per_pass >= 0");
+    if (nt == 0 || nviews == 0) return F3D_OK;
+    staging st(ctx);
+    const void* dverts = st.in(verts, xyz_bytes(vdtype, nv));
+    const void* dtris = st.in(tris, tri_bytes(itype, nt));
+    const f3d_view* dviews = st.in(views, sizeof(f3d_view) * (size_t)nviews);
+    const uint8_t* dmasks = st.in(masks, (size_t)nviews * h * w);
+    double* dvotes = st.inout(votes, (size_t)nt * ncols * 8);
+    if (!st.rc) st.rc = f3d_vote_faces_dev(ctx, dverts, vdtype, nv, dtris, itype, nt, dviews, nviews, dmasks, h, w, z_far, dvotes, ncols, views_per_pass,
+                                           ctx->stream);
+    return st.finish(F3D_DEVERR_RASTER | F3D_DEVERR_VOTE);                   // nothing is written back on an IndexError
+}
+
+static bool visible_mesh_args_ok(const void* xyz, f3d_dtype dtype, int64_t n, const raster_mesh& m, const void* views, int nviews, const void* masks,
+                                 int h, int w, double z_far, double depth_tol, const void* votes, int ncols, int views_per_pass) {
+    return render_args_ok(xyz, dtype, n, views, nviews, h, w, 0) && raster_args_ok(m, views, nviews, h, w, z_far) && depth_tol >= 0.0 && ncols > 0 &&
+           views_per_pass >= 0 && (n == 0 || votes) && (nviews == 0 || masks);
+}
+
+int f3d_vote_visible_mesh_dev(f3d_ctx* ctx, const void* xyz, f3d_dtype dtype, int64_t n, const void* verts, f3d_dtype vdtype, int64_t nv,
+                              const void* tris, int itype, int64_t nt, const f3d_view* views_dev, int nviews, const uint8_t* masks, int h, int w,
+                              double z_far, double depth_tol, double* votes, int ncols, int views_per_pass, void* stream) {
+    int rc = enter(ctx); if (rc) return rc;
+    const raster_mesh m{verts, vdtype, nv, tris, itype, nt};
+    if (!visible_mesh_args_ok(xyz, dtype, n, m, views_dev, nviews, masks, h, w, z_far, depth_tol, votes, ncols, views_per_pass))
+        return fail(ctx, F3D_ERR_INVALID, "vote_visible_mesh: " F3D_RASTER_BAD ", n < 2^31, depth_tol >= 0, views_per_pass >= 0");
+    if (n == 0 || nviews == 0) return F3D_OK;
+    hipStream_t s = pick(ctx, stream);
+    const size_t hw = (size_t)h * w;
+    const int per = render_pass_views(nviews, h, w, views_per_pass);
+    unsigned long long* zkey; void* rs;
+    if ((rc = raster_begin(ctx, m, nviews, per, hw, nullptr, s, &zkey, &rs))) return rc;
+    for (int v0 = 0; v0 < nviews; v0 += per) {
+        const int nvp = nviews - v0 < per ? nviews - v0 : per;
+        if ((rc = raster_pass(ctx, m, views_dev, v0, nvp, h, w, z_far, zkey, nullptr, rs, F3D_RASTER_LIST_CAP, false, s))) return rc;
+        F3D_HIP(ctx, f3d_launch_vote_visible(xyz, dtype, n, views_dev + v0, nvp, masks + (size_t)v0 * hw, h, w, zkey, depth_tol, votes, ncols,
+                                             raster_flag(rs), ctx->dev_err, s));
+    }
+    return F3D_OK;
+}
+
+int f3d_vote_visible_mesh(f3d_ctx* ctx, const void* xyz, f3d_dtype dtype, int64_t n, const void* verts, f3d_dtype vdtype, int64_t nv,
+                          const void* tris, int itype, int64_t nt, const f3d_view* views, int nviews, const uint8_t* masks, int h, int w,
+                          double z_far, double depth_tol, double* votes, int ncols, int views_per_pass) {
+    int rc = enter(ctx); if (rc) return rc;
+    const raster_mesh m{verts, vdtype, nv, tris, itype, nt};
+    if (!visible_mesh_args_ok(xyz, dtype, n, m, views, nviews, masks, h, w, z_far, depth_tol, votes, ncols, views_per_pass))
+        return fail(ctx, F3D_ERR_INVALID, "vote_visible_mesh: " F3D_RASTER_BAD ", n < 2^31, depth_tol >= 0, views_per_pass >= 0");
+    if (n == 0 || nviews == 0) return F3D_OK;
+    staging st(ctx);
+    const void* dxyz = st.in(xyz, xyz_bytes(dtype, n));
+    const void* dverts = st.in(verts, xyz_bytes(vdtype, nv));
+    const void* dtris = st.in(tris, tri_bytes(itype, nt));
+    const f3d_view* dviews = st.in(views, sizeof(f3d_view) * (size_t)nviews);
+    const uint8_t* dmasks = st.in(masks, (size_t)nviews * h * w);
+    double* dvotes = st.inout(votes, (size_t)n * ncols * 8);
+    if (!st.rc) st.rc = f3d_vote_visible_mesh_dev(ctx, dxyz, dtype, n, dverts, vdtype, nv, dtris, itype, nt, dviews, nviews, dmasks, h, w, z_far, depth_tol,
+                                                  dvotes, ncols, views_per_pass, ctx->stream);
+    return st.finish(F3D_DEVERR_RASTER | F3D_DEVERR_ZVOTE);
+}
+
+int f3d_debug_raster_counts(f3d_ctx* ctx, const void* verts, f3d_dtype vdtype, int64_t nv, const void* tris, int itype, int64_t nt,
+                            const f3d_view* views_dev, int nviews, int h, int w, double z_far, int64_t list_capacity, float* depth, int32_t* uv2tri,
+                            uint64_t counts[4], double ms[2], void* stream) {
+    int rc = enter(ctx); if (rc) return rc;
+    const raster_mesh m{verts, vdtype, nv, tris, itype, nt};
+    if (!raster_args_ok(m, views_dev, nviews, h, w, z_far) || !counts || list_capacity < 0 || list_capacity > (int64_t)F3D_RASTER_LIST_CAP)
+        return fail(ctx, F3D_ERR_INVALID, "debug_raster_counts: " F3D_RASTER_BAD ", list_capacity in [0, %u]", F3D_RASTER_LIST_CAP);
+    hipStream_t s = pick(ctx, stream);
+    const size_t hw = (size_t)h * w;
+    const unsigned cap = list_capacity ? (unsigned)list_capacity : F3D_RASTER_LIST_CAP;
+    const int per = render_pass_views(nviews, h, w, 0);
+    unsigned long long* zkey; void* rs;
+    if ((rc = raster_begin(ctx, m, nviews, per, hw, nullptr, s, &zkey, &rs))) return rc;
+    hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
+    for (int k = 0; k < 3; ++k) F3D_HIP(ctx, hipEventCreate(&ev[k]));
+    double fill_ms = 0.0, raster_ms = 0.0;
+    hipError_t e = hipSuccess;
+    for (int v0 = 0; v0 < nviews && e == hipSuccess; v0 += per) {            // one synchronisation per pass: the events are read back
+        const int nvp = nviews - v0 < per ? nviews - v0 : per;
+        float a = 0.f, b = 0.f;
+        if ((e = hipEventRecord(ev[0], s)) != hipSuccess) break;
+        if ((e = f3d_launch_zkey_fill(zkey, (size_t)nvp * hw, s)) != hipSuccess) break;
+        if ((e = hipEventRecord(ev[1], s)) != hipSuccess) break;
+        if ((e = f3d_launch_raster(verts, vdtype, tris, itype, nt, views_dev, v0, nvp, h, w, z_far, zkey, nullptr, rs, cap, true, s)) != hipSuccess) break;
+        if ((e = hipEventRecord(ev[2], s)) != hipSuccess) break;
+        if ((e = f3d_launch_zkey_unpack(zkey, (size_t)nvp * hw, depth ? depth + (size_t)v0 * hw : nullptr, uv2tri ? uv2tri + (size_t)v0 * hw : nullptr,
+                                        raster_flag(rs), s)) != hipSuccess) break;
+        if ((e = hipEventSynchronize(ev[2])) != hipSuccess) break;
+        if ((e = hipEventElapsedTime(&a, ev[0], ev[1])) != hipSuccess || (e = hipEventElapsedTime(&b, ev[1], ev[2])) != hipSuccess) break;
+        fill_ms += a; raster_ms += b;
+    }
+    for (int k = 0; k < 3; ++k) (void)hipEventDestroy(ev[k]);
+    F3D_HIP(ctx, e);
+    F3D_HIP(ctx, hipMemcpyAsync(counts, (const char*)rs + f3d_raster_scratch_layout(0).stats, 4 * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
+    F3D_HIP(ctx, hipStreamSynchronize(s));
+    if (ms) { ms[0] = fill_ms; ms[1] = raster_ms; }
     return F3D_OK;
 }
 

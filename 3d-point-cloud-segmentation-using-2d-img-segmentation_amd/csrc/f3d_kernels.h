@@ -17,7 +17,8 @@
 #define F3D_DEVERR_MESH 256                // meshUtils: triangle vertex index outside [0, nv)
 #define F3D_DEVERR_ZVOTE 512               // vote_visible: a visible sample's label >= ncols (voting.py:98)
 #define F3D_DEVERR_PLANES 1024             // extract_planes: neighbour index outside [0, n)
-#define F3D_DEVERR_ALL 2047
+#define F3D_DEVERR_RASTER 2048             // mesh z-buffer: triangle vertex index outside [0, nv)
+#define F3D_DEVERR_ALL 4095
 #define F3D_PLANES_PER_LAUNCH 16
 #define F3D_OBB_MAX_BOXES 4096
 #define F3D_SORT_MAX_CELLS 32767            // + 1 overflow cell = 2^15 keys -> 16 key bits sorted
@@ -556,9 +557,36 @@ hipError_t f3d_launch_mesh_clean(const void* verts, int vdtype, int64_t nv, cons
 hipError_t f3d_launch_zkey_fill(unsigned long long* zkey, size_t cells, hipStream_t s);
 hipError_t f3d_launch_zsplat(const void* xyz, int dtype, int64_t n, const f3d_view* views_dev, int nv, int h, int w, int splat,
                              unsigned long long* zkey, unsigned long long* counts, hipStream_t s);
-hipError_t f3d_launch_zkey_unpack(const unsigned long long* zkey, size_t cells, float* depth, int32_t* uv2pt, hipStream_t s);
+// skip (device int, may be NULL): nothing is written when it is set (the mesh entries' bad-index flag).
+hipError_t f3d_launch_zkey_unpack(const unsigned long long* zkey, size_t cells, float* depth, int32_t* uv2pt, const int* skip, hipStream_t s);
+// mesh_flag == NULL: the keys are a splat of this very cloud (a sample's cell is never empty).  Otherwise they are a mesh's: an empty
+// cell counts as +inf, and nothing is written when *mesh_flag is set.
 hipError_t f3d_launch_vote_visible(const void* xyz, int dtype, int64_t n, const f3d_view* views_dev, int nv, const uint8_t* masks, int h, int w,
-                                   const unsigned long long* zkey, double depth_tol, double* votes, int ncols, int* err, hipStream_t s);
+                                   const unsigned long long* zkey, double depth_tol, double* votes, int ncols, const int* mesh_flag, int* err,
+                                   hipStream_t s);
+
+// triangle rasteriser into the same keys (f3d_raster.hip).  scratch: f3d_raster_scratch_bytes(capacity of the deferral list), laid out
+// by f3d_raster_scratch_layout: a bad-index flag, the list's counter, 4 tier counters, the list.  f3d_launch_raster_check clears the
+// first three, flags a corner outside [0, nv) (F3D_DEVERR_RASTER) and zeroes straddling (may be NULL); every later launch returns at
+// once under the flag.  f3d_launch_raster rasterises the pass's nv views [view0, view0 + nv) of views_dev into zkey [nv, h, w] (filled
+// by f3d_launch_zkey_fill) and adds to straddling[view0 ..]; list_cap <= the capacity the scratch was sized for; stats: count the pairs.
+struct f3d_raster_entry { int32_t view, tri, u0, v0, u1, v1; };
+struct f3d_raster_scratch { size_t flag, count, stats, entries, bytes; };
+#define F3D_RASTER_LIST_CAP (1u << 16)
+inline f3d_raster_scratch f3d_raster_scratch_layout(unsigned list_cap) {
+    f3d_carve c;
+    f3d_raster_scratch l;
+    l.flag = c.take(sizeof(int)); l.count = c.take(sizeof(unsigned)); l.stats = c.take(4 * sizeof(unsigned long long));
+    l.entries = c.take((size_t)list_cap * sizeof(f3d_raster_entry));
+    l.bytes = c.off;
+    return l;
+}
+size_t f3d_raster_scratch_bytes(unsigned list_cap);
+hipError_t f3d_launch_raster_check(const void* tris, int itype, int64_t nt, int64_t nv, void* scratch, int nviews, long long* straddling, int* err,
+                                   hipStream_t s);
+hipError_t f3d_launch_raster(const void* verts, int vdtype, const void* tris, int itype, int64_t nt, const f3d_view* views_dev, int view0, int nv,
+                             int h, int w, double z_far, unsigned long long* zkey, long long* straddling, void* scratch, unsigned list_cap,
+                             bool stats, hipStream_t s);
 
 // plane table of a cloud over its adjacency (f3d_planes.hip).  Device pointers (counts int64 [4] too); normals (may be NULL: PCA of the
 // rows) and normals_out (may be NULL; written in PCA mode only) float64 [n, 3].  n >= 1.  Enqueues on `s` and synchronises it every few

@@ -67,7 +67,8 @@ __global__ __launch_bounds__(F3D_BLOCK) void k_zsplat(const T* __restrict__ xyz,
 
 // keys -> the lookups: depth = the winning z32 (+inf for an empty cell), uv2pt = the winning index (-1)
 __global__ __launch_bounds__(F3D_BLOCK) void k_zkey_unpack(const unsigned long long* __restrict__ zkey, size_t cells, float* __restrict__ depth,
-                                                            int32_t* __restrict__ uv2pt) {
+                                                            int32_t* __restrict__ uv2pt, const int* __restrict__ skip) {
+    if (skip && *skip) return;
     for (size_t i = (size_t)blockIdx.x * F3D_BLOCK + threadIdx.x; i < cells; i += (size_t)gridDim.x * F3D_BLOCK) {
         const unsigned long long key = zkey[i];
         const bool empty = key == F3D_ZKEY_EMPTY;
@@ -77,12 +78,15 @@ __global__ __launch_bounds__(F3D_BLOCK) void k_zkey_unpack(const unsigned long l
 }
 
 // One thread per point, looping over the views of the pass (uniform index: scalar loads of the record).  The thread owns its vote
-// row: plain float64 read-modify-writes, exact counts.  masks = the plane of the pass's first view.
-template <typename T>
+// row: plain float64 read-modify-writes, exact counts.  masks = the plane of the pass's first view.  MESH: the keys are a mesh's
+// (f3d_raster.hip), so the sample's own cell may be empty -- nothing in front of it, +inf -- and *mesh_flag set means a bad mesh.
+template <typename T, bool MESH>
 __global__ __launch_bounds__(F3D_BLOCK) void k_vote_visible(const T* __restrict__ xyz, int64_t n, const f3d_view* __restrict__ views, int nv,
                                                              const uint8_t* __restrict__ masks, int h, int w,
                                                              const unsigned long long* __restrict__ zkey, double depth_tol,
-                                                             double* __restrict__ votes, int ncols, int* __restrict__ err) {
+                                                             double* __restrict__ votes, int ncols, const int* __restrict__ mesh_flag,
+                                                             int* __restrict__ err) {
+    if (MESH && *mesh_flag) return;
     const size_t hw = (size_t)h * w;
     for (int64_t i = (int64_t)blockIdx.x * F3D_BLOCK + threadIdx.x; i < n; i += (int64_t)gridDim.x * F3D_BLOCK) {
         const f3d_p3 p = f3d_load_p3(xyz, i);
@@ -92,7 +96,8 @@ __global__ __launch_bounds__(F3D_BLOCK) void k_vote_visible(const T* __restrict_
             float z32;
             if (!f3d_sample(views[j], p, h, w, u, v, z32)) continue;
             const size_t cell = (size_t)j * hw + (size_t)v * w + u;
-            const float zmin32 = __uint_as_float((uint32_t)(zkey[cell] >> 32));     // never empty: this sample covers the cell
+            const unsigned long long key = zkey[cell];
+            const float zmin32 = MESH && key == F3D_ZKEY_EMPTY ? INFINITY : __uint_as_float((uint32_t)(key >> 32));   // !MESH: never empty, this sample covers the cell
             if (!((double)z32 <= (double)zmin32 + depth_tol)) continue;
             const int label = masks[cell];
             if (label >= ncols) { atomicOr(err, F3D_DEVERR_ZVOTE); continue; }      // the reference's IndexError (voting.py:98)
@@ -121,19 +126,20 @@ hipError_t f3d_launch_zsplat(const void* xyz, int dtype, int64_t n, const f3d_vi
     return hipGetLastError();
 }
 
-hipError_t f3d_launch_zkey_unpack(const unsigned long long* zkey, size_t cells, float* depth, int32_t* uv2pt, hipStream_t s) {
+hipError_t f3d_launch_zkey_unpack(const unsigned long long* zkey, size_t cells, float* depth, int32_t* uv2pt, const int* skip, hipStream_t s) {
     if (!cells || (!depth && !uv2pt)) return hipSuccess;
-    hipLaunchKernelGGL(k_zkey_unpack, dim3(f3d_grid_for((int64_t)cells, F3D_BLOCK, F3D_GRID_CAP)), dim3(F3D_BLOCK), 0, s, zkey, cells, depth, uv2pt);
+    hipLaunchKernelGGL(k_zkey_unpack, dim3(f3d_grid_for((int64_t)cells, F3D_BLOCK, F3D_GRID_CAP)), dim3(F3D_BLOCK), 0, s, zkey, cells, depth, uv2pt, skip);
     return hipGetLastError();
 }
 
 hipError_t f3d_launch_vote_visible(const void* xyz, int dtype, int64_t n, const f3d_view* views_dev, int nv, const uint8_t* masks, int h, int w,
-                                   const unsigned long long* zkey, double depth_tol, double* votes, int ncols, int* err, hipStream_t s) {
+                                   const unsigned long long* zkey, double depth_tol, double* votes, int ncols, const int* mesh_flag, int* err,
+                                   hipStream_t s) {
     if (n <= 0 || nv <= 0) return hipSuccess;
     const dim3 g(f3d_grid_for(n, F3D_BLOCK, F3D_GRID_CAP)), b(F3D_BLOCK);
-    if (dtype == F3D_F64)
-        hipLaunchKernelGGL(k_vote_visible<double>, g, b, 0, s, (const double*)xyz, n, views_dev, nv, masks, h, w, zkey, depth_tol, votes, ncols, err);
-    else
-        hipLaunchKernelGGL(k_vote_visible<float>, g, b, 0, s, (const float*)xyz, n, views_dev, nv, masks, h, w, zkey, depth_tol, votes, ncols, err);
+#define F3D_VV(T, M) hipLaunchKernelGGL((k_vote_visible<T, M>), g, b, 0, s, (const T*)xyz, n, views_dev, nv, masks, h, w, zkey, depth_tol, votes, ncols, mesh_flag, err)
+    if (dtype == F3D_F64) { if (mesh_flag) F3D_VV(double, true); else F3D_VV(double, false); }
+    else { if (mesh_flag) F3D_VV(float, true); else F3D_VV(float, false); }
+#undef F3D_VV
     return hipGetLastError();
 }

@@ -122,6 +122,14 @@ def library():
         'f3d_vote_visible_dev': (i32, [vp, vp, i32, i64, vp, i32, vp, i32, i32, i32, dbl, vp, i32, i32, vp]),
         'f3d_ctx_reserve_render': (i32, [vp, i64, i32, i32, i32]),
         'f3d_debug_render_counts': (i32, [vp, vp, i32, i64, vp, i32, i32, i32, i32, vp, vp, vp]),
+        'f3d_render_mesh_lookups': (i32, [vp, vp, i32, i64, vp, i32, i64, vp, i32, i32, i32, dbl, vp, vp, vp]),
+        'f3d_render_mesh_lookups_dev': (i32, [vp, vp, i32, i64, vp, i32, i64, vp, i32, i32, i32, dbl, vp, vp, vp, vp]),
+        'f3d_vote_faces': (i32, [vp, vp, i32, i64, vp, i32, i64, vp, i32, vp, i32, i32, dbl, vp, i32, i32]),
+        'f3d_vote_faces_dev': (i32, [vp, vp, i32, i64, vp, i32, i64, vp, i32, vp, i32, i32, dbl, vp, i32, i32, vp]),
+        'f3d_vote_visible_mesh': (i32, [vp, vp, i32, i64, vp, i32, i64, vp, i32, i64, vp, i32, vp, i32, i32, dbl, dbl, vp, i32, i32]),
+        'f3d_vote_visible_mesh_dev': (i32, [vp, vp, i32, i64, vp, i32, i64, vp, i32, i64, vp, i32, vp, i32, i32, dbl, dbl, vp, i32, i32, vp]),
+        'f3d_ctx_reserve_mesh_render': (i32, [vp, i32, i32, i32]),
+        'f3d_debug_raster_counts': (i32, [vp, vp, i32, i64, vp, i32, i64, vp, i32, i32, i32, dbl, i64, vp, vp, vp, vp, vp]),
         'f3d_sem_logits_to_mask': (i32, [vp, vp, i32, i64, flt, i32, vp]),
         'f3d_sem_logits_to_mask_dev': (i32, [vp, vp, i32, i64, flt, i32, vp, vp]),
         'f3d_sem_logits_to_masks_dev': (i32, [vp, vp, i32, i32, i64, flt, i32, vp, vp]),
@@ -291,6 +299,24 @@ def view_fields(views):
     return {'M': v[:, 0:9].reshape(-1, 3, 3), 't': v[:, 9:12], 'mnorm': v[:, 12:15],
             'K': v[:, 40:49].reshape(-1, 3, 3), 'qinv': v[:, 49:53],
             'plane_pt': v[:, 53:68].reshape(-1, 5, 3), 'plane_n': v[:, 68:83].reshape(-1, 5, 3), 'plane_off': v[:, 83:88]}
+
+
+def _views(views):
+    views = _f64(views)
+    if views.ndim != 2 or views.shape[1] != VIEW_DOUBLES:
+        raise ValueError(f'views must be [V,{VIEW_DOUBLES}]')
+    return views
+
+
+def _mesh(vertices, triangles):
+    """(vertices float64 / float32 [V,3], F64 / F32, triangles int64 / int32 [M,3], I64 / I32), C-contiguous."""
+    vx, vdt = _xyz(vertices)
+    tr = np.asarray(triangles)
+    if tr.dtype not in (np.int32, np.int64):
+        raise TypeError(f'triangles must be int32 or int64, got {tr.dtype}')
+    if tr.ndim != 2 or tr.shape[1] != 3:
+        raise ValueError(f'triangles must be [M,3], got {tr.shape}')
+    return vx, vdt, np.ascontiguousarray(tr), I32 if tr.dtype == np.int32 else I64
 
 
 def _xyz(points):
@@ -527,6 +553,10 @@ class Context:
                                                     float(radius), _ptr(votes), votes.shape[1]))
         return votes
 
+    def reserve_mesh_render(self, nviews, h, w):
+        """Size all scratch of render_mesh_lookups_dev / vote_faces_dev / vote_visible_mesh_dev (automatic pass size)."""
+        self._check(self._lib.f3d_ctx_reserve_mesh_render(self._h, int(nviews), int(h), int(w)))
+
     def render_lookups(self, points, views, h, w, splat=0, want_depth=True, want_uv2pt=True):
         """Point-splat z-buffer of the cloud in every view (f3d.h f3d_render_lookups) -> depth float32 [V, h, w] (+inf = empty),
         uv2pt int32 [V, h*w] (-1 = empty): the nearest point by float32 depth per pixel, ties to the lowest index."""
@@ -555,6 +585,54 @@ class Context:
         V, H, W = masks.shape
         self._check(self._lib.f3d_vote_visible(self._h, _ptr(p), dt, len(p), _ptr(views), V, _ptr(masks), H, W, int(splat), float(depth_tol),
                                                _ptr(votes), votes.shape[1], int(views_per_pass)))
+        return votes
+
+    def render_mesh_lookups(self, vertices, triangles, views, h, w, z_far=np.inf, want_depth=True, want_uv2tri=True, want_straddling=True):
+        """Triangle z-buffer of the mesh in every view (f3d.h f3d_render_mesh_lookups) -> depth float32 [V, h, w] (+inf = empty),
+        uv2tri int32 [V, h*w] (-1 = empty), straddling int64 [V] (triangles skipped because they cross the camera plane)."""
+        vx, vdt, tr, it = _mesh(vertices, triangles)
+        views = _views(views)
+        V, h, w = len(views), int(h), int(w)
+        depth = np.empty((V, h, w), np.float32) if want_depth else None
+        uv2tri = np.empty((V, h * w), np.int32) if want_uv2tri else None
+        straddling = np.empty(V, np.int64) if want_straddling else None
+        self._check(self._lib.f3d_render_mesh_lookups(self._h, _ptr(vx), vdt, len(vx), _ptr(tr), it, len(tr), _ptr(views), V, h, w, float(z_far),
+                                                      _ptr(depth), _ptr(uv2tri), _ptr(straddling)))
+        return depth, uv2tri, straddling
+
+    def vote_faces(self, votes, vertices, triangles, views, masks, z_far=np.inf, views_per_pass=0):
+        """Every pixel votes for the triangle it sees (f3d.h f3d_vote_faces), in place on `votes` (float64 [nt, ncols], C-contiguous)."""
+        if votes.dtype != np.float64 or not votes.flags.c_contiguous or votes.ndim != 2:
+            raise ValueError('votes must be a C-contiguous float64 [nt, ncols] array')
+        vx, vdt, tr, it = _mesh(vertices, triangles)
+        views = _views(views)
+        masks = np.ascontiguousarray(masks, dtype=np.uint8)
+        if masks.ndim != 3 or len(views) != len(masks):
+            raise ValueError(f'views must be [V,{VIEW_DOUBLES}] and masks uint8 [V,H,W]')
+        if len(tr) != votes.shape[0]:
+            raise ValueError(f'votes has {votes.shape[0]} rows, the mesh {len(tr)} triangles')
+        V, H, W = masks.shape
+        self._check(self._lib.f3d_vote_faces(self._h, _ptr(vx), vdt, len(vx), _ptr(tr), it, len(tr), _ptr(views), V, _ptr(masks), H, W, float(z_far),
+                                             _ptr(votes), votes.shape[1], int(views_per_pass)))
+        return votes
+
+    def vote_visible_mesh(self, votes, points, vertices, triangles, views, masks, z_far=np.inf, depth_tol=0.05, views_per_pass=0):
+        """The forward vote of the cloud with the mesh as the occluder (f3d.h f3d_vote_visible_mesh), in place on `votes`
+        (float64 [N, ncols], C-contiguous)."""
+        if votes.dtype != np.float64 or not votes.flags.c_contiguous or votes.ndim != 2:
+            raise ValueError('votes must be a C-contiguous float64 [npts, ncols] array')
+        p, dt = _xyz(points)
+        vx, vdt, tr, it = _mesh(vertices, triangles)
+        views = _views(views)
+        masks = np.ascontiguousarray(masks, dtype=np.uint8)
+        if masks.ndim != 3 or len(views) != len(masks):
+            raise ValueError(f'views must be [V,{VIEW_DOUBLES}] and masks uint8 [V,H,W]')
+        if len(p) != votes.shape[0]:
+            raise ValueError(f'votes has {votes.shape[0]} rows, the cloud {len(p)} points')
+        V, H, W = masks.shape
+        self._check(self._lib.f3d_vote_visible_mesh(self._h, _ptr(p), dt, len(p), _ptr(vx), vdt, len(vx), _ptr(tr), it, len(tr), _ptr(views), V,
+                                                    _ptr(masks), H, W, float(z_far), float(depth_tol), _ptr(votes), votes.shape[1],
+                                                    int(views_per_pass)))
         return votes
 
     def sem_logits_to_mask(self, sem, conf_threshold=0.017, low_label=133):
@@ -1149,6 +1227,38 @@ class Context:
         self._check(self._lib.f3d_debug_render_counts(self._h, xyz_ptr, int(dtype), int(n), views_ptr, int(nviews), int(h), int(w), int(splat),
                                                       _ptr(counts), _ptr(ms), stream))
         return {'samples': int(counts[0]), 'cells': int(counts[1]), 'atomics': int(counts[2]), 'fill_ms': float(ms[0]), 'splat_ms': float(ms[1])}
+
+    # mesh z-buffer (f3d.h "triangle-mesh z-buffer renders"): verts / tris as for the mesh entries (vdtype F64 / F32, itype I64 / I32)
+    def render_mesh_lookups_dev(self, verts_ptr, vdtype, nv, tris_ptr, itype, nt, views_ptr, nviews, h, w, z_far, depth_ptr, uv2tri_ptr,
+                                straddling_ptr, stream=None):
+        """depth float32 [V, h, w], uv2tri int32 [V, h*w], straddling int64 [V] on the device, any may be None; enqueue only.  A vertex
+        index outside [0, nv) writes nothing and is recorded for take_device_error."""
+        self._check(self._lib.f3d_render_mesh_lookups_dev(self._h, verts_ptr, int(vdtype), int(nv), tris_ptr, int(itype), int(nt), views_ptr,
+                                                          int(nviews), int(h), int(w), float(z_far), depth_ptr, uv2tri_ptr, straddling_ptr, stream))
+
+    def vote_faces_dev(self, verts_ptr, vdtype, nv, tris_ptr, itype, nt, views_ptr, nviews, masks_ptr, h, w, z_far, votes_ptr, ncols,
+                       views_per_pass=0, stream=None):
+        """Enqueue only; a bad vertex index or a label >= ncols on a non-empty cell is recorded for take_device_error."""
+        self._check(self._lib.f3d_vote_faces_dev(self._h, verts_ptr, int(vdtype), int(nv), tris_ptr, int(itype), int(nt), views_ptr, int(nviews),
+                                                 masks_ptr, int(h), int(w), float(z_far), votes_ptr, int(ncols), int(views_per_pass), stream))
+
+    def vote_visible_mesh_dev(self, xyz_ptr, dtype, n, verts_ptr, vdtype, nv, tris_ptr, itype, nt, views_ptr, nviews, masks_ptr, h, w, z_far,
+                              depth_tol, votes_ptr, ncols, views_per_pass=0, stream=None):
+        """Enqueue only; a bad vertex index or a label >= ncols on a visible sample is recorded for take_device_error."""
+        self._check(self._lib.f3d_vote_visible_mesh_dev(self._h, xyz_ptr, int(dtype), int(n), verts_ptr, int(vdtype), int(nv), tris_ptr, int(itype),
+                                                        int(nt), views_ptr, int(nviews), masks_ptr, int(h), int(w), float(z_far), float(depth_tol),
+                                                        votes_ptr, int(ncols), int(views_per_pass), stream))
+
+    def raster_counts_dev(self, verts_ptr, vdtype, nv, tris_ptr, itype, nt, views_ptr, nviews, h, w, z_far=np.inf, list_capacity=0,
+                          depth_ptr=None, uv2tri_ptr=None, stream=None):
+        """Diagnostic (synchronises): the (triangle, view) pairs each work tier of the rasteriser handled and the device-event times
+        of the key fill and of the raster (f3d.h f3d_debug_raster_counts); list_capacity > 0 shrinks the deferral list for this call."""
+        counts, ms = np.zeros(4, np.uint64), np.zeros(2)
+        self._check(self._lib.f3d_debug_raster_counts(self._h, verts_ptr, int(vdtype), int(nv), tris_ptr, int(itype), int(nt), views_ptr,
+                                                      int(nviews), int(h), int(w), float(z_far), int(list_capacity), depth_ptr, uv2tri_ptr,
+                                                      _ptr(counts), _ptr(ms), stream))
+        return {'small': int(counts[0]), 'medium': int(counts[1]), 'huge': int(counts[2]), 'overflow': int(counts[3]),
+                'fill_ms': float(ms[0]), 'raster_ms': float(ms[1])}
 
     def vote_uv2pt_dev(self, uv2pt_ptr, mask_ptr, hw, votes_ptr, npts, ncols, stream=None):
         self._check(self._lib.f3d_vote_uv2pt_dev(self._h, uv2pt_ptr, mask_ptr, hw, votes_ptr, npts, ncols, stream))

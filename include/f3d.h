@@ -778,7 +778,7 @@ int f3d_ctx_reserve_point_vote(f3d_ctx* ctx, int64_t m, int ncols);
  *   lookups  depth float32 [V, h, w] = the winning z32, +inf for an empty cell; uv2pt int32 [V, h * w] = the winning index, -1 for
  *            an empty cell (pixel index v * w + u).  Either may be NULL.
  *   visible  sample (i, j) is visible iff (double)z32 <= (double)zmin32 + depth_tol, zmin32 = the depth of cell (j, v, u) (never
- *            empty: the sample covers it).  depth_tol >= 0, +inf allowed (every sample is visible: the votes of
+ *            empty: the sample covers it; f3d_vote_visible_mesh tests against a mesh instead).  depth_tol >= 0, +inf allowed (every sample is visible: the votes of
  *            f3d_project_vote_argmax).
  *   vote     votes[i, masks[j, v, u]] += 1 for every visible sample; votes float64 [n, ncols], IN PLACE (the layout of
  *            VotingSegmentation: f3d_segment_votes finishes the job).  A label >= ncols on a visible sample is the reference's
@@ -807,6 +807,80 @@ int f3d_ctx_reserve_render(f3d_ctx* ctx, int64_t n, int nviews, int h, int w);
  * passes.  Device pointers; synchronises `stream` once per pass. */
 int f3d_debug_render_counts(f3d_ctx* ctx, const void* xyz, f3d_dtype dtype, int64_t n, const f3d_view* views_dev, int nviews,
                             int h, int w, int splat, uint64_t counts[3], double ms[2], void* stream);
+
+/* ---- triangle-mesh z-buffer renders: face voting and mesh occlusion (no reference counterpart) ---------------------------- */
+/* The same depth keys, filled from a triangle mesh instead of a point splat: a watertight occluder for the forward vote, and the
+ * pixel -> triangle lookups that let the masks vote for faces directly.  All arithmetic is float64 without contraction, every product
+ * and sum as written.  View j is views[j] from f3d_views_build; triangle t is the caller-order index, nt < 2^31; tris [nt, 3] int64
+ * (F3D_I64) or int32 (F3D_I32), verts [nv, 3] float64 or float32 (widened exactly), as the meshUtils entries take them; h * w <= 2^30.
+ *   vertex    (h0, h1, h2) = f3d_project_h(K, qinv, t, p), x = h0 / h2, y = h1 / h2, iz = 1.0 / h2, z32 = (float)h2.  Eligible in the view
+ *             iff FLT_MIN <= z32 < +inf, |x| <= 2^30 and |y| <= 2^30 (NaN fails).  The 5 frustum planes play no part.
+ *   pixel     (u, v) covers [u, u+1) x [v, v+1), the floor of the point path; its sample is (sx, sy) = (u + 0.5, v + 0.5).
+ *   triangle  (a, b, c) is rasterised in a view iff its three vertices are eligible, its three indices are distinct and
+ *             A = (x_b - x_a)*(y_c - y_a) - (y_b - y_a)*(x_c - x_a) is finite and non-zero.  Both windings are drawn (no culling).
+ *             There is NO near-plane clipping: a triangle with both an eligible and an ineligible vertex is skipped and counted in
+ *             straddling[j].  What is lost that way lies nearer to the camera plane than the triangle's longest edge: nothing a
+ *             camera sees of a scan mesh (centimetre edges); a coarse mesh (a wall of two triangles) must be subdivided by the caller.
+ *   edges     per edge between vertex indices i and j, lo = min(i, j), hi = max(i, j):
+ *                 e = (x_hi - x_lo)*(sy - y_lo) - (y_hi - y_lo)*(sx - x_lo)
+ *             the value of the directed edge i -> j is e if i < j, else -e.  E01, E12, E20 = the directed values of a->b, b->c, c->a,
+ *             each negated when A < 0.  The sample is covered iff E01 >= 0 && E12 >= 0 && E20 >= 0.  Two triangles sharing an edge
+ *             evaluate bit-identical e with opposite sign requirements, so a sample inside a closed fan is never dropped; a sample
+ *             exactly on a shared edge belongs to both, and the key decides.
+ *   depth     s = (E12 + E20) + E01, z = s / ((E12*iz_a + E20*iz_b) + E01*iz_c), z32 = (float)z (perspective-correct).  The fragment
+ *             exists iff the sample is covered, s > 0, FLT_MIN <= z32 < +inf and z <= z_far (+inf allowed).
+ *   pixels    the candidates of a triangle are u in [floor(min x) - 1, floor(max x) + 1], v likewise, clamped to the image; only the
+ *             coverage test decides among them.  (Every covered sample lies inside that box but for rounding on slivers thinner than
+ *             2^-20 px; fixing the box makes the result exact there too.)
+ *   key       key = (uint64)bits(z32) << 32 | (uint32)t; cell (j, r, c) of zkey [V, h, w] holds the minimum key over the fragments of
+ *             view j at that pixel, all ones when there is none: the layout and sentinel of f3d_render_lookups.  The nearest float32
+ *             depth wins, ties go to the lowest triangle index; the result does not depend on thread timing, launch shape, work
+ *             distribution or pass size.
+ * f3d_render_mesh_lookups: depth float32 [V, h, w] (+inf = empty), uv2tri int32 [V, h * w] (-1 = empty), straddling int64 [V]; any of
+ *   the three may be NULL.
+ * f3d_vote_faces: the reference's voting direction (the pixel votes for what it sees) with one row per triangle: per view,
+ *   votes[uv2tri[j], masks[j]] += 1 over the non-empty cells, float64 [nt, ncols] IN PLACE, the layout of VotingSegmentation
+ *   (f3d_segment_votes finishes the job).  Per pass this IS raster -> unpack -> the launches of f3d_vote_uv2pt_batch, so its rules hold:
+ *   ncols <= 256, and the reference's fancy-index "+=" (voting.py:98) gives a (triangle, label) pair ONE vote per view however many of
+ *   the view's pixels carry it.  A label >= ncols on a non-empty cell is the reference's IndexError.
+ * f3d_vote_visible_mesh: the forward vote of a POINT CLOUD xyz [n, 3] with the mesh as the occluder.  The points' samples are exactly
+ *   those of f3d_vote_visible; a sample is visible iff (double)z32 <= (double)zmin32 + depth_tol, zmin32 = the mesh depth of its pixel,
+ *   an EMPTY cell counting as +inf (nothing is in front of it).  depth_tol = +inf: the votes of f3d_project_vote_argmax.
+ * Views go in passes of views_per_pass (0 = as many as fit 256 MiB of keys, and for f3d_vote_faces one launch of the batched vote);
+ * the keys live in the scratch of f3d_render_lookups.  f3d_ctx_reserve_mesh_render sizes all scratch of the _dev entries (keys, the
+ * rasteriser's list, the lookups and the vote table of f3d_vote_faces) for automatic passes: a strict context then allocates nothing.
+ * Errors: a vertex index outside [0, nv) -> F3D_ERR_INDEX and nothing is written (a pre-pass; in the _dev twins a device-error bit of
+ * its own for f3d_take_device_error); the IndexErrors above likewise (host: nothing written back; _dev: outputs unspecified).
+ * nt >= 2^31, depth_tol negative or NaN, z_far NaN, views_per_pass < 0 -> F3D_ERR_INVALID.  Non-finite vertices are no error: their
+ * triangles are ineligible.  nt == 0: empty buffers, no votes. */
+int f3d_render_mesh_lookups(f3d_ctx* ctx, const void* verts, f3d_dtype vdtype, int64_t nv, const void* tris, int itype, int64_t nt,
+                            const f3d_view* views, int nviews, int h, int w, double z_far, float* depth, int32_t* uv2tri,
+                            int64_t* straddling);
+int f3d_render_mesh_lookups_dev(f3d_ctx* ctx, const void* verts, f3d_dtype vdtype, int64_t nv, const void* tris, int itype, int64_t nt,
+                                const f3d_view* views_dev /*device [V]*/, int nviews, int h, int w, double z_far, float* depth,
+                                int32_t* uv2tri, int64_t* straddling, void* stream);
+int f3d_vote_faces(f3d_ctx* ctx, const void* verts, f3d_dtype vdtype, int64_t nv, const void* tris, int itype, int64_t nt,
+                   const f3d_view* views, int nviews, const uint8_t* masks /*[V,H,W]*/, int h, int w, double z_far,
+                   double* votes /*[nt, ncols], in place*/, int ncols, int views_per_pass);
+int f3d_vote_faces_dev(f3d_ctx* ctx, const void* verts, f3d_dtype vdtype, int64_t nv, const void* tris, int itype, int64_t nt,
+                       const f3d_view* views_dev, int nviews, const uint8_t* masks, int h, int w, double z_far, double* votes, int ncols,
+                       int views_per_pass, void* stream);
+int f3d_vote_visible_mesh(f3d_ctx* ctx, const void* xyz, f3d_dtype dtype, int64_t n, const void* verts, f3d_dtype vdtype, int64_t nv,
+                          const void* tris, int itype, int64_t nt, const f3d_view* views, int nviews, const uint8_t* masks, int h, int w,
+                          double z_far, double depth_tol, double* votes /*[n, ncols], in place*/, int ncols, int views_per_pass);
+int f3d_vote_visible_mesh_dev(f3d_ctx* ctx, const void* xyz, f3d_dtype dtype, int64_t n, const void* verts, f3d_dtype vdtype, int64_t nv,
+                              const void* tris, int itype, int64_t nt, const f3d_view* views_dev, int nviews, const uint8_t* masks,
+                              int h, int w, double z_far, double depth_tol, double* votes, int ncols, int views_per_pass, void* stream);
+int f3d_ctx_reserve_mesh_render(f3d_ctx* ctx, int nviews, int h, int w);
+/* Diagnostic: renders the views like f3d_render_mesh_lookups_dev (depth, uv2tri: device, may be NULL) with a counting build of the
+ * rasteriser.  The work is split over three tiers by the size of a triangle's candidate box, which no result depends on:
+ * counts[0..3] = (triangle, view) pairs walked by one lane (small), by their wave (medium), deferred to the list of the tile kernel
+ * (huge), and huge pairs that found the list full and were walked by their wave instead (overflow).  list_capacity: 0 = the
+ * library's, else a smaller capacity for this call (a test forces the overflow path with a handful of triangles).  ms (may be NULL):
+ * device-event times of the key fill and of the raster (both kernels), summed over the passes.  Synchronises `stream` once per pass. */
+int f3d_debug_raster_counts(f3d_ctx* ctx, const void* verts, f3d_dtype vdtype, int64_t nv, const void* tris, int itype, int64_t nt,
+                            const f3d_view* views_dev, int nviews, int h, int w, double z_far, int64_t list_capacity, float* depth,
+                            int32_t* uv2tri, uint64_t counts[4], double ms[2], void* stream);
 
 /* ---- a5: patch matching of Fusion.fuse (Fusion3DSeg/fusion.py:269-298) ------------------- */
 /* The loop over the in-frustum points ("seeds", in index order) of one frame: seed k takes the still-free depth pixels of
