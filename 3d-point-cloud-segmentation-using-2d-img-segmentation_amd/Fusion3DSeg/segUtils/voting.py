@@ -3,17 +3,21 @@
 Same constructor, attributes, methods, return types and quirks (reference file:line in each
 method); the scatter vote and the segmentation run as HIP kernels (f3d_vote_uv2pt*, f3d_segment_votes*), and so does
 the radius search fused with the frame vote of PointVotingSegmentation (f3d_point_vote_frames*).
+``smooth_votes`` / ``smooth_segment`` (no reference counterpart) put a spatial prior between a vote and the instance split: every
+row becomes the sum of itself and its neighbours' rows over an adjacency (f3d_smooth_votes / f3d_smooth_segment, include/f3d.h).
 The vote matrix stays on the GPU for the whole ``vote()`` loop and is downloaded once.
 OpenCV is optional: masks are read with cv2 when it is importable, else with Pillow, and the
 nearest-neighbour resize is done here (same index rule as cv2.INTER_NEAREST).
 """
+import math
 import os
 from pathlib import Path
 
 import numpy as np
 
 import f3d
-from f3d.tensors import dtype_code, torch_device, work_stream
+from f3d.tensors import CSR_ADJACENCY, device_csr, dtype_code, host_csr, on_device, torch_device, work_stream
+from Fusion3DSeg.segUtils.cv import adjacency_to_csr
 
 
 def _imread_gray(path):
@@ -391,3 +395,154 @@ class PointVotingSegmentation:
         """
         votes = self.votes if votes is None else votes
         return f3d.default_context().segment_votes_lastcol(votes, self.nclasses, threshold, filter_classes)
+
+
+# ------------------------------------------------------------------------------------------------ neighbour-summed votes
+def _shape(a):
+    return tuple(a.shape) if hasattr(a, 'shape') else np.shape(a)
+
+
+def _smooth_scalars(what, votes, normals, angle, colors, max_color_dist, self_weight, iterations):
+    """The shapes and scalars of smooth_votes / smooth_segment, checked -> (n, ncols, cos_angle, max_color_dist, self_weight, iterations)."""
+    shape = _shape(votes)
+    if len(shape) != 2:
+        raise ValueError(f'{what}: votes must be [N, ncols], got {shape}')
+    n, ncols = shape
+    if not 1 <= ncols <= f3d.SMOOTH_MAX_COLS:
+        raise ValueError(f'{what}: votes must have 1 to {f3d.SMOOTH_MAX_COLS} columns, got {ncols}')
+    iterations = int(iterations)
+    if iterations < 1:
+        raise ValueError(f'{what}: iterations must be at least 1, got {iterations}')
+    self_weight = float(self_weight)
+    if not math.isfinite(self_weight) or self_weight < 0:
+        raise ValueError(f'{what}: self_weight must be finite and not negative, got {self_weight}')
+    if (normals is None) != (angle is None):
+        raise ValueError(f'{what}: normals and angle go together (the gate needs both)')
+    if (colors is None) != (max_color_dist is None):
+        raise ValueError(f'{what}: colors and max_color_dist go together (the gate needs both)')
+    cos_angle = 0.0
+    if normals is not None:
+        cos_angle = math.cos(math.radians(float(angle)))
+        if math.isnan(cos_angle):
+            raise ValueError(f'{what}: angle must be a number of degrees, got {angle}')
+        if _shape(normals) != (n, 3):
+            raise ValueError(f'{what}: normals must be [{n}, 3], got {_shape(normals)}')
+    limit = 0.0
+    if colors is not None:
+        limit = float(max_color_dist)
+        if not limit >= 0:
+            raise ValueError(f'{what}: max_color_dist must not be negative, got {max_color_dist}')
+        if _shape(colors) != (n, 3):
+            raise ValueError(f'{what}: colors must be [{n}, 3], got {_shape(colors)}')
+    return n, ncols, cos_angle, limit, self_weight, iterations
+
+
+def _smooth_device_inputs(what, votes, adj, n, normals, colors):
+    import torch
+    dev = votes.device
+    u16 = (torch.int16,) + ((torch.uint16,) if hasattr(torch, 'uint16') else ())           # uint16 counts may travel as int16 bits
+    if votes.dtype != torch.float64 and votes.dtype not in u16:
+        raise TypeError(f'{what}: votes must be float64 or uint16 (int16 bits as a tensor), got {votes.dtype}')
+    if normals is not None and (not on_device(normals) or normals.dtype != torch.float64):
+        raise TypeError(f'{what}: normals must be a float64 device tensor for device votes')
+    if colors is not None and (not on_device(colors) or colors.dtype not in (torch.float64, torch.float32)):
+        raise TypeError(f'{what}: colors must be a float64 or float32 device tensor for device votes')
+    offs, nbrs = device_csr(adj, n, dev, 'device votes')
+    return (dev, votes.contiguous(), offs, nbrs, None if normals is None else normals.to(dev).contiguous(),
+            None if colors is None else colors.to(dev).contiguous())
+
+
+def _smooth_host_inputs(what, votes, adj, n, normals, colors):
+    v = np.asarray(votes)
+    if v.dtype not in (np.float64, np.uint16):
+        raise TypeError(f'{what}: votes must be float64 or uint16, got {v.dtype}')
+    if normals is not None:
+        if on_device(normals) or np.asarray(normals).dtype != np.float64:
+            raise TypeError(f'{what}: normals must be a float64 array for host votes')
+        normals = np.ascontiguousarray(normals)
+    if colors is not None:
+        if on_device(colors) or np.asarray(colors).dtype not in (np.float64, np.float32):
+            raise TypeError(f'{what}: colors must be a float64 or float32 array for host votes')
+        colors = np.ascontiguousarray(colors)
+    if isinstance(adj, tuple) and any(on_device(a) for a in adj):
+        raise TypeError(f'{what}: host votes need a host adjacency (a device CSR pair goes with device tensors)')
+    offs, nbrs = host_csr(*adjacency_to_csr(adj, n), n, CSR_ADJACENCY)
+    return np.ascontiguousarray(v), offs, nbrs, normals, colors
+
+
+def _dptr(t):
+    return None if t is None else t.data_ptr()
+
+
+def _overlaps(a, b):
+    """Two device tensors share memory."""
+    a0, b0 = a.data_ptr(), b.data_ptr()
+    return a0 < b0 + b.numel() * b.element_size() and b0 < a0 + a.numel() * a.element_size()
+
+
+def smooth_votes(votes, adj, normals=None, angle=None, colors=None, max_color_dist=None, self_weight=1.0, iterations=1, out=None):
+    """Every vote row becomes ``self_weight`` times itself plus the rows of its neighbours, `iterations` times (include/f3d.h
+    f3d_smooth_votes).  votes float64 or uint16 [N, ncols] (a uint16 tensor may come as int16 bits), ncols <= 256; adj a list of rows or a CSR pair, any CSR: rows need not be
+    symmetric, the point itself is skipped, a duplicate entry counts twice.  With normals (float64 [N, 3]) and `angle` in degrees only
+    neighbours whose normal lies within `angle` of the point's (either sign) contribute; with colors (float64 / float32 [N, 3]) and
+    max_color_dist only neighbours within that colour distance.  Neighbour weights are 1.  The sums have one fixed order, so equal input
+    gives equal bits.  -> float64 [N, ncols] (`out` when given: C-contiguous float64, not sharing memory with votes).  Device tensors
+    with a device CSR pair stay on the device.  Every argument is checked before anything is launched."""
+    what = 'smooth_votes'
+    n, ncols, cos_angle, limit, self_weight, iterations = _smooth_scalars(what, votes, normals, angle, colors, max_color_dist, self_weight,
+                                                                          iterations)
+    if out is not None and _shape(out) != (n, ncols):
+        raise ValueError(f'{what}: out must be [{n}, {ncols}], got {_shape(out)}')
+    if on_device(votes):
+        import torch
+        dev, v, offs, nbrs, nrm, col = _smooth_device_inputs(what, votes, adj, n, normals, colors)
+        if out is None:
+            out = torch.empty((n, ncols), dtype=torch.float64, device=dev)
+        elif not on_device(out) or out.dtype != torch.float64 or out.device != dev or not out.is_contiguous():
+            raise TypeError(f'{what}: out must be a contiguous float64 tensor on {dev}')
+        elif _overlaps(out, v):
+            raise ValueError(f'{what}: out must not share memory with votes')
+        ctx = f3d.default_context(dev.index)
+        with work_stream(dev) as work:
+            ctx.smooth_votes_dev(v.data_ptr(), f3d._vtype(v), n, ncols, offs.data_ptr(), nbrs.data_ptr(), _dptr(nrm), cos_angle, _dptr(col),
+                                 f3d.F64 if col is None else dtype_code(col), limit, self_weight, iterations, out.data_ptr(), work.cuda_stream)
+            ctx.take_device_error(work.cuda_stream)                       # synchronises the stream: the result is complete
+        return out
+    v, offs, nbrs, nrm, col = _smooth_host_inputs(what, votes, adj, n, normals, colors)
+    if out is not None:
+        if not isinstance(out, np.ndarray) or out.dtype != np.float64 or not out.flags.c_contiguous:
+            raise TypeError(f'{what}: out must be a C-contiguous float64 array')
+        if np.shares_memory(out, v):
+            raise ValueError(f'{what}: out must not share memory with votes')
+    return f3d.default_context().smooth_votes(v, offs, nbrs, nrm, cos_angle, col, limit, self_weight, iterations, out=out)
+
+
+def smooth_segment(votes, adj, nclasses, threshold=0.5, filter_classes=None, lastcol=False, normals=None, angle=None, colors=None,
+                   max_color_dist=None, self_weight=1.0, iterations=1):
+    """``segment`` of the matrix ``smooth_votes`` would return, without writing its last iteration: VotingSegmentation.segment's rules
+    (lastcol: PointVotingSegmentation.segment's, the last column being the total) on the smoothed rows.  For integer votes and an
+    integer self_weight (every voter here) the classes equal segmenting ``smooth_votes``' result bit for bit.  Arguments as for
+    smooth_votes.  -> classes int64 [N] (a device tensor for device votes)."""
+    what = 'smooth_segment'
+    n, ncols, cos_angle, limit, self_weight, iterations = _smooth_scalars(what, votes, normals, angle, colors, max_color_dist, self_weight,
+                                                                          iterations)
+    nclasses, threshold = int(nclasses), float(threshold)
+    flt = None if filter_classes is None else [int(c) for c in filter_classes]
+    if flt is not None and any(c >= ncols or c < -ncols for c in flt):
+        raise IndexError(f'{what}: a filter class is out of bounds for {ncols} vote columns')
+    if lastcol and ncols < 2 and not flt:
+        raise ValueError(f'{what}: attempt to get argmax of an empty sequence')
+    if on_device(votes):
+        import torch
+        dev, v, offs, nbrs, nrm, col = _smooth_device_inputs(what, votes, adj, n, normals, colors)
+        cls = torch.empty(n, dtype=torch.int64, device=dev)
+        ctx = f3d.default_context(dev.index)
+        with work_stream(dev) as work:
+            ctx.smooth_segment_dev(v.data_ptr(), f3d._vtype(v), n, ncols, offs.data_ptr(), nbrs.data_ptr(), _dptr(nrm), cos_angle, _dptr(col),
+                                   f3d.F64 if col is None else dtype_code(col), limit, self_weight, iterations, nclasses, threshold, flt,
+                                   lastcol, cls.data_ptr(), work.cuda_stream)
+            ctx.take_device_error(work.cuda_stream)
+        return cls
+    v, offs, nbrs, nrm, col = _smooth_host_inputs(what, votes, adj, n, normals, colors)
+    return f3d.default_context().smooth_segment(v, offs, nbrs, nclasses, threshold, flt, lastcol, nrm, cos_angle, col, limit, self_weight,
+                                                iterations)

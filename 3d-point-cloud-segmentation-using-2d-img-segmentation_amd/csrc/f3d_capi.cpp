@@ -36,7 +36,7 @@ enum scratch_slot { SLOT_OBB_BOXES = 0, SLOT_SORT_PERM, SLOT_SORT_SCRATCH, SLOT_
                     SLOT_PATCH, SLOT_GRP_SCRATCH, SLOT_OBB_TABLE, SLOT_OBB_FACETS, SLOT_OBB_CAND, SLOT_FUSE_TABLES, SLOT_FUSE_CARRY,
                     SLOT_FUSE_XYZ, SLOT_FUSION, SLOT_PATCH_STATUS, SLOT_NRM, SLOT_NRM_CAMS, SLOT_QRY, SLOT_FLOOD, SLOT_COLOR,
                     SLOT_CVS_INST, SLOT_CVS_STATS, SLOT_QUADS, SLOT_GROW, SLOT_PVOTE, SLOT_PVOTE_BITS, SLOT_MESH, SLOT_ZKEY,
-                    SLOT_ZCOUNTS, SLOT_KNN, SLOT_KNN_FLAG, SLOT_PLANES, SLOT_RASTER, SLOT_ZLUT, SLOT_COUNT };
+                    SLOT_ZCOUNTS, SLOT_KNN, SLOT_KNN_FLAG, SLOT_PLANES, SLOT_RASTER, SLOT_ZLUT, SLOT_SMOOTH, SLOT_COUNT };
 enum kept_slot { KEPT_GRAPH_OFFS = 0,                                      // f3d_radius_graph_count -> _fill: the offsets
                  KEPT_QRY_IN, KEPT_QRY_OFFS,                               // f3d_radius_query_count -> _fill: the queries, the offsets
                  KEPT_GRP_ORDER, KEPT_GRP_KEYS, KEPT_GRP_STARTS,           // f3d_group_by_id -> f3d_obb_extremes -> f3d_obb_hull_filter
@@ -200,6 +200,8 @@ int take_error(f3d_ctx* ctx, hipStream_t s, int mask = F3D_DEVERR_ALL) {
             return fail(ctx, F3D_ERR_INDEX, "mesh: a triangle's vertex index is outside [0, nv)");
         if (e & F3D_DEVERR_PLANES)
             return fail(ctx, F3D_ERR_INDEX, "extract_planes: neighbour index outside [0, n)");
+        if (e & F3D_DEVERR_SMOOTH)
+            return fail(ctx, F3D_ERR_INDEX, "smooth_votes: neighbour index outside [0, n), or offsets that do not ascend");
         if (e & F3D_DEVERR_RASTER)
             return fail(ctx, F3D_ERR_INDEX, "mesh render: a triangle's vertex index is outside [0, nv)");
         if (e & F3D_DEVERR_ZVOTE)
@@ -1597,6 +1599,158 @@ int f3d_extract_planes(f3d_ctx* ctx, const void* xyz, f3d_dtype dtype, int64_t n
                                                max_rounds, max_planes, (int32_t*)(io + o_lab), (double*)(io + o_pl), (double*)(io + o_cr),
                                                (int64_t*)(io + o_cnt), normals_out && !normals ? (double*)(io + o_nout) : nullptr, ctx->stream);
     return st.finish(F3D_DEVERR_PLANES);
+}
+
+// ---------------------------------------------------------------------------------------------
+// smooth_votes / smooth_segment: neighbour-summed vote rows over an adjacency
+// ---------------------------------------------------------------------------------------------
+namespace {
+
+struct smooth_in {                          // what the four entries share
+    const void* votes; int vtype; int64_t n; int ncols; const int64_t* offsets; const int32_t* neighbours;
+    const double* normals; double cos_angle; const void* colors; int cdtype; double max_color_dist; double self_weight; int iterations;
+};
+#define F3D_SMOOTH_BAD "smooth_votes: bad arguments (n < 2^31, 1 <= ncols <= 256, iterations >= 1, self_weight finite and >= 0, " \
+                       "cos_angle not NaN with normals, max_color_dist >= 0 with colors)"
+
+bool smooth_args_bad(const smooth_in& a, const void* out) {
+    return (a.vtype != F3D_VOTES_F64 && a.vtype != F3D_VOTES_U16) || a.n < 0 || a.n > 0x7fffffffLL || a.ncols < 1 || a.ncols > 256 ||
+           a.iterations < 1 || !(a.self_weight >= 0.0) || !isfinite(a.self_weight) || (a.normals && a.cos_angle != a.cos_angle) ||
+           (a.colors && (!dtype_ok(a.cdtype) || !(a.max_color_dist >= 0.0))) || (a.n > 0 && (!a.votes || !a.offsets || !out));
+}
+
+size_t smooth_vote_bytes(const smooth_in& a) { return (size_t)a.n * a.ncols * (a.vtype == F3D_VOTES_U16 ? 2 : 8); }
+
+bool ranges_overlap(const void* p, size_t pb, const void* q, size_t qb) {
+    const uintptr_t a = (uintptr_t)p, b = (uintptr_t)q;
+    return a < b + qb && b < a + pb;
+}
+
+// scratch matrices of a call: smooth_votes alternates between votes_out and one matrix; smooth_segment writes iterations - 1
+// matrices, alternating between two
+int smooth_matrices(int iterations, bool segment) { return segment ? (iterations > 2 ? 2 : iterations - 1) : (iterations > 1 ? 1 : 0); }
+
+// the iterations of one call, enqueued on s.  seg NULL: the last one lands in out; else it produces classes
+int smooth_enqueue(f3d_ctx* ctx, const smooth_in& a, double* out, const f3d_smooth_seg* seg, int64_t* classes, hipStream_t s) {
+    const size_t mat = (size_t)a.n * a.ncols * 8;
+    const int nmat = smooth_matrices(a.iterations, seg != nullptr);
+    void* scratch = nullptr;
+    int rc;
+    if (nmat > 0 && (rc = ensure(ctx, SLOT_SMOOTH, mat * nmat, &scratch))) return rc;
+    double* m[2] = {(double*)scratch, (double*)((char*)scratch + (nmat > 1 ? mat : 0))};
+    const f3d_smooth_gates g = {a.normals, a.cos_angle, a.colors, a.cdtype, a.max_color_dist * a.max_color_dist};
+    F3D_HIP(ctx, f3d_launch_smooth_check(a.n, a.offsets, a.neighbours, ctx->dev_err, s));
+    const void* src = a.votes;
+    int vtype = a.vtype;
+    const int T = a.iterations;
+    for (int t = 1; t <= T; ++t) {
+        const bool last = t == T;
+        double* dst = seg ? m[(t - 1) & 1] : (((T - t) & 1) ? m[0] : out);
+        F3D_HIP(ctx, f3d_launch_smooth(src, vtype, a.n, a.ncols, a.offsets, a.neighbours, g, a.self_weight, last && seg ? nullptr : dst,
+                                       last ? seg : nullptr, last ? classes : nullptr, ctx->dev_err, s));
+        src = dst;
+        vtype = F3D_VOTES_F64;
+    }
+    return F3D_OK;
+}
+
+// the epilogue's record: make_filter's list (device copy in flt.cls_dev) and, for lastcol, which entries were given negative
+int smooth_seg_make(f3d_ctx* ctx, int ncols, int nclasses, double threshold, const int32_t* filter, int nfilter, int lastcol, hipStream_t s,
+                    f3d_smooth_seg* sg) {
+    *sg = f3d_smooth_seg{};
+    sg->nclasses = nclasses; sg->threshold = threshold; sg->lastcol = lastcol ? 1 : 0;
+    int rc;
+    if ((rc = make_filter(ctx, filter, nfilter, ncols, true, s, &sg->flt))) return rc;
+    if (lastcol) for (int k = 0; k < sg->flt.nfilter; ++k) if (filter[k] < 0) sg->neg.w[k >> 5] |= 1u << (k & 31);
+    return F3D_OK;
+}
+
+// device copies of a host call's inputs (a NULL gate array stays NULL)
+int smooth_stage(f3d_ctx* ctx, staging& st, const smooth_in& h, smooth_in* d) {
+    const int64_t e = h.n > 0 ? h.offsets[h.n] : 0;
+    if (e < 0 || (e > 0 && !h.neighbours)) return fail(ctx, F3D_ERR_INVALID, "smooth_votes: bad adjacency");
+    *d = h;
+    d->votes = st.in((const char*)h.votes, smooth_vote_bytes(h));
+    d->offsets = st.in(h.offsets, (size_t)(h.n + 1) * 8);
+    d->neighbours = st.in(h.neighbours, (size_t)e * 4);
+    d->normals = h.normals ? st.in(h.normals, (size_t)h.n * 24) : nullptr;
+    d->colors = h.colors ? st.in((const char*)h.colors, xyz_bytes((f3d_dtype)h.cdtype, h.n)) : nullptr;
+    return st.rc;
+}
+
+}  // namespace
+
+int f3d_ctx_reserve_smooth(f3d_ctx* ctx, int64_t n, int ncols, int iterations) {
+    int rc = enter(ctx); if (rc) return rc;
+    if (n < 0 || n > 0x7fffffffLL || ncols < 1 || ncols > 256 || iterations < 1)
+        return fail(ctx, F3D_ERR_INVALID, "ctx_reserve_smooth: bad arguments (n < 2^31, 1 <= ncols <= 256, iterations >= 1)");
+    const int nmat = smooth_matrices(iterations, true) > smooth_matrices(iterations, false) ? smooth_matrices(iterations, true)
+                                                                                            : smooth_matrices(iterations, false);
+    return reserve(ctx, {{SLOT_SMOOTH, (size_t)n * ncols * 8 * nmat, nmat > 0}});
+}
+
+int f3d_smooth_votes_dev(f3d_ctx* ctx, const void* votes, int vtype, int64_t n, int ncols, const int64_t* offsets,
+                         const int32_t* neighbours, const double* normals, double cos_angle, const void* colors, f3d_dtype cdtype,
+                         double max_color_dist, double self_weight, int iterations, double* votes_out, void* stream) {
+    int rc = enter(ctx); if (rc) return rc;
+    const smooth_in a = {votes, vtype, n, ncols, offsets, neighbours, normals, cos_angle, colors, cdtype, max_color_dist, self_weight, iterations};
+    if (smooth_args_bad(a, votes_out)) return fail(ctx, F3D_ERR_INVALID, F3D_SMOOTH_BAD);
+    if (n == 0) return F3D_OK;
+    if (ranges_overlap(votes, smooth_vote_bytes(a), votes_out, (size_t)n * ncols * 8))
+        return fail(ctx, F3D_ERR_INVALID, "smooth_votes: votes_out overlaps votes");
+    return smooth_enqueue(ctx, a, votes_out, nullptr, nullptr, pick(ctx, stream));
+}
+
+int f3d_smooth_votes(f3d_ctx* ctx, const void* votes, int vtype, int64_t n, int ncols, const int64_t* offsets, const int32_t* neighbours,
+                     const double* normals, double cos_angle, const void* colors, f3d_dtype cdtype, double max_color_dist,
+                     double self_weight, int iterations, double* votes_out) {
+    int rc = enter(ctx); if (rc) return rc;
+    const smooth_in h = {votes, vtype, n, ncols, offsets, neighbours, normals, cos_angle, colors, cdtype, max_color_dist, self_weight, iterations};
+    if (smooth_args_bad(h, votes_out)) return fail(ctx, F3D_ERR_INVALID, F3D_SMOOTH_BAD);
+    if (n == 0) return F3D_OK;
+    if (ranges_overlap(votes, smooth_vote_bytes(h), votes_out, (size_t)n * ncols * 8))
+        return fail(ctx, F3D_ERR_INVALID, "smooth_votes: votes_out overlaps votes");
+    staging st(ctx);
+    smooth_in d;
+    if ((rc = smooth_stage(ctx, st, h, &d))) return rc;
+    double* dout = st.out(votes_out, (size_t)n * ncols * 8);
+    if (!st.rc) st.rc = f3d_smooth_votes_dev(ctx, d.votes, vtype, n, ncols, d.offsets, d.neighbours, d.normals, cos_angle, d.colors, cdtype,
+                                             max_color_dist, self_weight, iterations, dout, ctx->stream);
+    return st.finish(F3D_DEVERR_SMOOTH);
+}
+
+int f3d_smooth_segment_dev(f3d_ctx* ctx, const void* votes, int vtype, int64_t n, int ncols, const int64_t* offsets,
+                           const int32_t* neighbours, const double* normals, double cos_angle, const void* colors, f3d_dtype cdtype,
+                           double max_color_dist, double self_weight, int iterations, int nclasses, double threshold,
+                           const int32_t* filter, int nfilter, int lastcol, int64_t* classes, void* stream) {
+    int rc = enter(ctx); if (rc) return rc;
+    const smooth_in a = {votes, vtype, n, ncols, offsets, neighbours, normals, cos_angle, colors, cdtype, max_color_dist, self_weight, iterations};
+    if (smooth_args_bad(a, classes)) return fail(ctx, F3D_ERR_INVALID, F3D_SMOOTH_BAD);
+    if (lastcol && ncols < 2 && nfilter == 0 && n > 0)          // votes[:, :-1] has no column, as in f3d_segment_votes_lastcol
+        return fail(ctx, F3D_ERR_INVALID, "smooth_segment: attempt to get argmax of an empty sequence");
+    hipStream_t s = pick(ctx, stream);
+    f3d_smooth_seg sg;
+    if ((rc = smooth_seg_make(ctx, ncols, nclasses, threshold, filter, nfilter, lastcol, s, &sg))) return rc;
+    if (n == 0) return F3D_OK;
+    return smooth_enqueue(ctx, a, nullptr, &sg, classes, s);
+}
+
+int f3d_smooth_segment(f3d_ctx* ctx, const void* votes, int vtype, int64_t n, int ncols, const int64_t* offsets,
+                       const int32_t* neighbours, const double* normals, double cos_angle, const void* colors, f3d_dtype cdtype,
+                       double max_color_dist, double self_weight, int iterations, int nclasses, double threshold,
+                       const int32_t* filter, int nfilter, int lastcol, int64_t* classes) {
+    int rc = enter(ctx); if (rc) return rc;
+    const smooth_in h = {votes, vtype, n, ncols, offsets, neighbours, normals, cos_angle, colors, cdtype, max_color_dist, self_weight, iterations};
+    if (smooth_args_bad(h, classes)) return fail(ctx, F3D_ERR_INVALID, F3D_SMOOTH_BAD);
+    if (n == 0) return F3D_OK;
+    staging st(ctx);
+    smooth_in d;
+    if ((rc = smooth_stage(ctx, st, h, &d))) return rc;
+    int64_t* dcls = st.out(classes, (size_t)n * 8);
+    if (!st.rc) st.rc = f3d_smooth_segment_dev(ctx, d.votes, vtype, n, ncols, d.offsets, d.neighbours, d.normals, cos_angle, d.colors, cdtype,
+                                               max_color_dist, self_weight, iterations, nclasses, threshold, filter, nfilter, lastcol, dcls,
+                                               ctx->stream);
+    return st.finish(F3D_DEVERR_SMOOTH);
 }
 
 // ---------------------------------------------------------------------------------------------

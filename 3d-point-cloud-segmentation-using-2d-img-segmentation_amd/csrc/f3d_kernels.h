@@ -18,7 +18,8 @@
 #define F3D_DEVERR_ZVOTE 512               // vote_visible: a visible sample's label >= ncols (voting.py:98)
 #define F3D_DEVERR_PLANES 1024             // extract_planes: neighbour index outside [0, n)
 #define F3D_DEVERR_RASTER 2048             // mesh z-buffer: triangle vertex index outside [0, nv)
-#define F3D_DEVERR_ALL 4095
+#define F3D_DEVERR_SMOOTH 4096             // smooth_votes / smooth_segment: neighbour index outside [0, n), or offsets not ascending
+#define F3D_DEVERR_ALL 8191
 #define F3D_PLANES_PER_LAUNCH 16
 #define F3D_OBB_MAX_BOXES 4096
 #define F3D_SORT_MAX_CELLS 32767            // + 1 overflow cell = 2^15 keys -> 16 key bits sorted
@@ -596,3 +597,15 @@ size_t f3d_planes_scratch_bytes(int64_t n);
 hipError_t f3d_launch_extract_planes(const void* xyz, int dtype, int64_t n, const int64_t* offs, const int32_t* nbrs,
                                      const double* normals, const f3d_planes_args& a, int32_t* labels, double* planes, double* corners,
                                      int64_t* counts, double* normals_out, void* scratch, int* err, hipStream_t s);
+
+// neighbour-summed vote rows over a CSR adjacency (f3d_smooth.hip; the contract is in include/f3d.h).  Device pointers.  A gate
+// exists iff its array is not NULL; lim2 = max_color_dist * max_color_dist.  f3d_launch_smooth_check goes first: a neighbour outside
+// [0, n) or offsets that do not ascend from >= 0 set F3D_DEVERR_SMOOTH, under which every f3d_launch_smooth returns at once.
+// f3d_launch_smooth is ONE iteration: votes (F3D_VOTES_F64 / F3D_VOTES_U16) -> out float64 [n, ncols] (seg NULL), or -> classes with the
+// rules of f3d_launch_segment_votes(_lastcol) applied to the smoothed row, which is not written (seg given; flt.cls_dev holds the list).
+struct f3d_smooth_gates { const double* normals; double cos_angle; const void* colors; int cdtype; double lim2; };
+struct f3d_smooth_seg { int nclasses; double threshold; f3d_filter_args flt; f3d_negmask neg; int lastcol; };
+hipError_t f3d_launch_smooth_check(int64_t n, const int64_t* offs, const int32_t* nbrs, int* err, hipStream_t s);
+hipError_t f3d_launch_smooth(const void* votes, int vtype, int64_t n, int ncols, const int64_t* offs, const int32_t* nbrs,
+                             const f3d_smooth_gates& g, double self_weight, double* out, const f3d_smooth_seg* seg, int64_t* classes,
+                             const int* err, hipStream_t s);

@@ -32,6 +32,8 @@ NORMALS_MAX_NN = 64          # F3D_NORMALS_MAX_NN: the largest max_nn of estimat
 QUAD_OK, QUAD_HORIZONTAL, QUAD_NO_CANDIDATE = 0, 1, 2   # per-instance status of door_window_quads (f3d.h F3D_QUAD_*)
 QUADS_MAX_INST = 65535       # F3D_QUADS_MAX_INST
 I64, I32 = 0, 1              # f3d_itype: the index type of mesh triangles
+VOTES_F64, VOTES_U16 = 0, 1  # f3d_vtype: the element type of a vote matrix handed to smooth_votes / smooth_segment
+SMOOTH_MAX_COLS = 256        # the widest vote matrix smooth_votes / smooth_segment take
 KNN_MAX_K = 32               # F3D_KNN_MAX_K: the largest k of knn_query / transfer_labels
 
 
@@ -182,6 +184,11 @@ def library():
         'f3d_extract_planes': (i32, [vp, vp, i32, i64, vp, vp, vp, dbl, dbl, dbl, dbl, i64, i64, i64, vp, vp, vp, vp, vp]),
         'f3d_extract_planes_dev': (i32, [vp, vp, i32, i64, vp, vp, vp, dbl, dbl, dbl, dbl, i64, i64, i64, vp, vp, vp, vp, vp, vp]),
         'f3d_ctx_reserve_planes': (i32, [vp, i64]),
+        'f3d_smooth_votes': (i32, [vp, vp, i32, i64, i32, vp, vp, vp, dbl, vp, i32, dbl, dbl, i32, vp]),
+        'f3d_smooth_votes_dev': (i32, [vp, vp, i32, i64, i32, vp, vp, vp, dbl, vp, i32, dbl, dbl, i32, vp, vp]),
+        'f3d_smooth_segment': (i32, [vp, vp, i32, i64, i32, vp, vp, vp, dbl, vp, i32, dbl, dbl, i32, i32, dbl, vp, i32, i32, vp]),
+        'f3d_smooth_segment_dev': (i32, [vp, vp, i32, i64, i32, vp, vp, vp, dbl, vp, i32, dbl, dbl, i32, i32, dbl, vp, i32, i32, vp, vp]),
+        'f3d_ctx_reserve_smooth': (i32, [vp, i64, i32, i32]),
         'f3d_patch_owner': (i32, [vp, vp, i64, i32, i32, i32, dbl, dbl, vp, vp, vp, vp, vp, vp]),
         'f3d_patch_owner_dev': (i32, [vp, vp, i64, i32, i32, i32, dbl, dbl, vp, vp, vp, vp, vp, vp, vp]),
         'f3d_patch_match': (i32, [vp, vp, i64, i32, i32, i32, dbl, dbl, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
@@ -343,6 +350,26 @@ def _filter(filter_classes):
     return f, len(f)
 
 
+def _vtype(votes):
+    """VOTES_F64 / VOTES_U16 of a float64 / uint16 vote matrix (array or tensor)."""
+    return VOTES_U16 if votes.dtype.itemsize == 2 else VOTES_F64
+
+
+def _smooth_arrays(votes, offsets, neighbours, normals, colors):
+    """The host arrays of smooth_votes / smooth_segment as the C entry reads them: (offsets, neighbours, normals, colors)."""
+    if not isinstance(votes, np.ndarray) or votes.ndim != 2 or votes.dtype not in (np.float64, np.uint16) or not votes.flags.c_contiguous:
+        raise ValueError('votes must be a C-contiguous float64 or uint16 [n, ncols] array')
+    n = len(votes)
+    offsets, neighbours = host_csr(offsets, neighbours, n)
+    if normals is not None:
+        normals = _f64(normals, (n, 3))
+    if colors is not None:
+        colors = np.ascontiguousarray(colors, dtype=np.float32 if np.asarray(colors).dtype == np.float32 else np.float64)
+        if colors.shape != (n, 3):
+            raise ValueError(f'expected shape {(n, 3)}, got {colors.shape}')
+    return offsets, neighbours, normals, colors
+
+
 def _flood_stats(stats):
     return {'clusters': int(stats[0]), 'points': int(stats[1]), 'levels': int(stats[2]), 'readbacks': int(stats[3])}
 
@@ -414,6 +441,11 @@ class Context:
     def reserve_planes(self, n):
         """Size the scratch of extract_planes_dev for clouds of up to n points, for any max_planes."""
         self._check(self._lib.f3d_ctx_reserve_planes(self._h, int(n)))
+
+    def reserve_smooth(self, n, ncols, iterations):
+        """Size the scratch of smooth_votes_dev / smooth_segment_dev for [n, ncols] vote matrices and that many iterations (one
+        iteration needs none)."""
+        self._check(self._lib.f3d_ctx_reserve_smooth(self._h, int(n), int(ncols), int(iterations)))
 
     def reserve_refine(self, n):
         """Size the scratch of region_grow_dev for clouds of up to n points."""
@@ -885,6 +917,36 @@ class Context:
         out = (labels, planes[:counts[0]].copy(), corners[:counts[0]].copy(), counts)
         return out + (nout,) if want_normals else out
 
+    def smooth_votes(self, votes, offsets, neighbours, normals=None, cos_angle=0.0, colors=None, max_color_dist=0.0, self_weight=1.0,
+                     iterations=1, out=None):
+        """Neighbour-summed vote rows (include/f3d.h f3d_smooth_votes).  votes float64 / uint16 [n, ncols], C-contiguous; offsets /
+        neighbours a checked host CSR; normals float64 [n, 3] or None; colors float64 / float32 [n, 3] or None.  -> float64 [n, ncols]
+        (`out` when given: C-contiguous float64 of that shape, not overlapping votes)."""
+        offsets, neighbours, normals, colors = _smooth_arrays(votes, offsets, neighbours, normals, colors)
+        if out is None:
+            out = np.empty(votes.shape, np.float64)
+        elif out.dtype != np.float64 or out.shape != votes.shape or not out.flags.c_contiguous:
+            raise ValueError('out must be a C-contiguous float64 array of the shape of votes')
+        self._check(self._lib.f3d_smooth_votes(self._h, _ptr(votes), _vtype(votes), votes.shape[0], votes.shape[1], _ptr(offsets),
+                                               _ptr(neighbours), _ptr(normals), float(cos_angle), _ptr(colors),
+                                               F64 if colors is None else dtype_code(colors), float(max_color_dist), float(self_weight),
+                                               int(iterations), _ptr(out)))
+        return out
+
+    def smooth_segment(self, votes, offsets, neighbours, nclasses, threshold=0.5, filter_classes=None, lastcol=False, normals=None,
+                       cos_angle=0.0, colors=None, max_color_dist=0.0, self_weight=1.0, iterations=1):
+        """segment_votes (lastcol: segment_votes_lastcol) of the smoothed matrix, whose last iteration is never written
+        (include/f3d.h f3d_smooth_segment).  Arrays as for smooth_votes.  -> classes int64 [n]."""
+        offsets, neighbours, normals, colors = _smooth_arrays(votes, offsets, neighbours, normals, colors)
+        f, nf = _filter(filter_classes)
+        cls = np.empty(votes.shape[0], np.int64)
+        self._check(self._lib.f3d_smooth_segment(self._h, _ptr(votes), _vtype(votes), votes.shape[0], votes.shape[1], _ptr(offsets),
+                                                 _ptr(neighbours), _ptr(normals), float(cos_angle), _ptr(colors),
+                                                 F64 if colors is None else dtype_code(colors), float(max_color_dist), float(self_weight),
+                                                 int(iterations), int(nclasses), float(threshold), _ptr(f), nf, int(bool(lastcol)),
+                                                 _ptr(cls)))
+        return cls
+
     def door_window_quads(self, points, ids, instance_ids, vertices, triangles):
         """Door / window quads of door_window_bbox.generate_mesh (include/f3d.h f3d_door_window_quads) for the distinct ids
         `instance_ids`.  -> (quads float64 [k, 4, 3], status int32 [k] (QUAD_*), chosen triangle int32 [k], triangle normals
@@ -1184,6 +1246,23 @@ class Context:
                                                      float(cos_angle), float(offset), float(dist), float(max_variation), int(min_points),
                                                      int(max_rounds), int(max_planes), labels_ptr, planes_ptr, corners_ptr, counts_ptr,
                                                      normals_out_ptr, stream))
+
+    def smooth_votes_dev(self, votes_ptr, vtype, n, ncols, offsets_ptr, neighbours_ptr, normals_ptr, cos_angle, colors_ptr, cdtype,
+                         max_color_dist, self_weight, iterations, votes_out_ptr, stream=None):
+        """f3d_smooth_votes_dev: device pointers throughout (normals_ptr / colors_ptr may be None: no gate); votes_out float64
+        [n, ncols] must not overlap votes.  A bad neighbour index is recorded for take_device_error and nothing is written."""
+        self._check(self._lib.f3d_smooth_votes_dev(self._h, votes_ptr, int(vtype), int(n), int(ncols), offsets_ptr, neighbours_ptr,
+                                                   normals_ptr, float(cos_angle), colors_ptr, int(cdtype), float(max_color_dist),
+                                                   float(self_weight), int(iterations), votes_out_ptr, stream))
+
+    def smooth_segment_dev(self, votes_ptr, vtype, n, ncols, offsets_ptr, neighbours_ptr, normals_ptr, cos_angle, colors_ptr, cdtype,
+                           max_color_dist, self_weight, iterations, nclasses, threshold, filter_classes, lastcol, classes_ptr, stream=None):
+        """f3d_smooth_segment_dev: device pointers (filter_classes stays a host list); classes int64 [n]."""
+        f, nf = _filter(filter_classes)
+        self._check(self._lib.f3d_smooth_segment_dev(self._h, votes_ptr, int(vtype), int(n), int(ncols), offsets_ptr, neighbours_ptr,
+                                                     normals_ptr, float(cos_angle), colors_ptr, int(cdtype), float(max_color_dist),
+                                                     float(self_weight), int(iterations), int(nclasses), float(threshold), _ptr(f), nf,
+                                                     int(bool(lastcol)), classes_ptr, stream))
 
     def take_device_error(self, stream=None):
         self._check(self._lib.f3d_take_device_error(self._h, stream))

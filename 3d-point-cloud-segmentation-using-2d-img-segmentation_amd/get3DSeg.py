@@ -15,7 +15,7 @@ import numpy as np
 from Fusion3DSeg.fusion import Fusion
 from Fusion3DSeg.merge_intersecting_bb import merge_bb, obb_from_points, obb_corners
 from Fusion3DSeg.segUtils.cv import split_into_instances
-from Fusion3DSeg.segUtils.voting import VotingSegmentation
+from Fusion3DSeg.segUtils.voting import VotingSegmentation, smooth_segment
 
 _HERE = Path(os.path.dirname(os.path.abspath(__file__)))
 _COCO_META = _HERE.parent / 'deeplearning' / 'segmentation' / 'mask2former' / 'coco_meta.json'      # reference :68
@@ -196,14 +196,23 @@ def panoptic_viz(points, ids, idinfo, outdir, coco_data=None, colors=None, alpha
     return colors, pcd, palette, idinfo
 
 
-def segment(dirname, mask_dir, threshold=0.5, nclasses=133, filter_classes=[86, 114, 115], min_pts_per_inst=100, verbose=True):
-    """Semantic + panoptic segmentation of a fused cloud from 2D masks (reference :18-116)."""
+def segment(dirname, mask_dir, threshold=0.5, nclasses=133, filter_classes=[86, 114, 115], min_pts_per_inst=100, verbose=True,
+            smooth_iterations=0, smooth_angle=None):
+    """Semantic + panoptic segmentation of a fused cloud from 2D masks (reference :18-116).
+
+    smooth_iterations > 0 (not in the reference; needs the adjacency): the classes come from the votes summed over every point's
+    neighbours that many times (voting.smooth_segment) instead of from each point's own row, which closes one-point islands and
+    unseen points before the instance split; smooth_angle (degrees) keeps the sums on one surface by the loaded normals."""
     dirname = Path(dirname)
     points, norms, colors, nmerges, occurences, nframes, depth_hw, adj = Fusion.load_data(dirname)
     t0 = time.perf_counter()
     voter = VotingSegmentation(len(points), depth_hw, mask_dir, dirname / 'fusion' / 'uv2pt', nclasses, votes_file=None)
     votes = voter.vote(resize=True, filename=dirname / 'segmentation' / 'votes.npy', verbose=verbose)
-    classes = voter.segment(threshold, filter_classes)
+    if smooth_iterations > 0 and adj is not None:
+        gate = {} if smooth_angle is None else {'normals': np.ascontiguousarray(norms, np.float64), 'angle': smooth_angle}
+        classes = smooth_segment(votes, adj, nclasses, threshold, filter_classes, iterations=smooth_iterations, **gate)
+    else:
+        classes = voter.segment(threshold, filter_classes)
     if verbose:
         print(f'Time taken for segmentation = {time.perf_counter() - t0} seconds')
     if adj is not None:

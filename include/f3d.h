@@ -648,6 +648,63 @@ int f3d_extract_planes_dev(f3d_ctx* ctx, const void* xyz, f3d_dtype dtype, int64
                            double* normals_out, void* stream);
 int f3d_ctx_reserve_planes(f3d_ctx* ctx, int64_t n);
 
+/* ---- smooth_votes / smooth_segment: neighbour-summed vote rows over an adjacency (no reference counterpart) ---------------- */
+/* Every voter labels a point from its own vote row alone; these entries put a spatial prior between the vote and
+ * split_into_instances: a point's row becomes the sum of its own row and of its neighbours' rows, optionally only of the neighbours
+ * on the same surface (normals gate) or of similar colour (colour gate).  tests/smooth_ref.py restates the contract in NumPy.
+ *
+ * Inputs.  votes [n, ncols]: float64 (F3D_VOTES_F64) or the uint16 matrix f3d_project_vote_argmax writes (F3D_VOTES_U16, widened
+ * exactly); 1 <= ncols <= 256.  offsets int64 [n + 1] / neighbours int32: ANY CSR -- rows need not be symmetric, may or may not list
+ * their own point, and a duplicate entry counts twice.  normals float64 [n, 3] with cos_angle: optional (NULL = no gate).  colors
+ * [n, 3] of `cdtype` (float32 is widened exactly) with max_color_dist >= 0: optional (NULL = no gate).  self_weight: finite, >= 0.
+ * iterations >= 1.
+ * One iteration.  The others of point i are the entries j != i of its row, in row order.  Such a j contributes iff every gate that
+ * was given holds:
+ *   normals  |dot(n_i, n_j)| >= cos_angle, dot(a, b) = (a0*b0 + a1*b1) + a2*b2   (the rule of f3d_extract_planes);
+ *   colours  (dr*dr + dg*dg) + db*db <= max_color_dist*max_color_dist, d = c_j - c_i.
+ * Every product, sum and difference is rounded alone; a NaN makes a comparison false.  Then per column c
+ *   out[i, c] = (..((self_weight * v[i, c]) + v[j1, c]) + v[j2, c] ..)   over the contributing others in row order.
+ * A column's sum has one fixed order, so the result is bit-reproducible for any input, not only for integer counts.  Iteration
+ * t + 1 reads the complete output of iteration t (synchronous, two buffers); nothing is atomic.
+ * f3d_smooth_votes writes votes_out float64 [n, ncols] (for odd and for even `iterations` the last one lands there); votes_out
+ * overlapping votes -> F3D_ERR_INVALID.
+ * f3d_smooth_segment produces classes int64 [n] and never writes the last iteration's matrix: its epilogue applies the rules of
+ * f3d_segment_votes (lastcol != 0: of f3d_segment_votes_lastcol) to the smoothed row held by the wave -- nclasses, threshold, the
+ * filter list with its sequential remap.  When all vote values and self_weight are integers and the row totals stay below 2^53 it
+ * equals f3d_segment_votes(_lastcol) on the matrix f3d_smooth_votes would have written, bit for bit (every voter of this library
+ * meets that condition).  Outside it, its own order defines it: the row total is summed lane-wise -- lane l adds columns l, l + 64,
+ * l + 128, l + 192 to 0.0 in ascending order, the 64 lanes meet in an xor butterfly 32, 16, .., 1 -- where f3d_segment_votes uses
+ * 16 lanes; the argmax (first maximum) and the comparisons do not depend on an order.
+ * Errors.  A neighbour index outside [0, n), or offsets that do not ascend from a value >= 0 -> F3D_ERR_INDEX and no output is
+ * written: a check kernel runs first, and under its flag every later kernel of the call returns at once, so nothing is read out of
+ * bounds.  The host entry returns it; the _dev twin records it in a bit of its own for f3d_take_device_error.  ncols > 256 (never
+ * truncated), n >= 2^31, iterations < 1, self_weight negative or not finite, a NaN cos_angle with normals, a negative or NaN
+ * max_color_dist with colors, lastcol with one column and no filter -> F3D_ERR_INVALID; a filter column outside the matrix ->
+ * F3D_ERR_INDEX.  n == 0: nothing to do.
+ * Limits.  Unit neighbour weights only: no distance or confidence weights.
+ * The host entries wrap the _dev twins, which take device pointers (the filter list stays on the host) and enqueue on `stream`.
+ * Scratch: one iteration needs none; more ping-pong through one n * ncols * 8 byte matrix of the context (two for
+ * f3d_smooth_segment from 3 iterations on): f3d_ctx_reserve_smooth(n, ncols, iterations) sizes it for both entries. */
+typedef enum f3d_vtype {
+    F3D_VOTES_F64 = 0,
+    F3D_VOTES_U16 = 1
+} f3d_vtype;
+int f3d_smooth_votes(f3d_ctx* ctx, const void* votes, int vtype, int64_t n, int ncols, const int64_t* offsets, const int32_t* neighbours,
+                     const double* normals, double cos_angle, const void* colors, f3d_dtype cdtype, double max_color_dist,
+                     double self_weight, int iterations, double* votes_out);
+int f3d_smooth_votes_dev(f3d_ctx* ctx, const void* votes, int vtype, int64_t n, int ncols, const int64_t* offsets,
+                         const int32_t* neighbours, const double* normals, double cos_angle, const void* colors, f3d_dtype cdtype,
+                         double max_color_dist, double self_weight, int iterations, double* votes_out, void* stream);
+int f3d_smooth_segment(f3d_ctx* ctx, const void* votes, int vtype, int64_t n, int ncols, const int64_t* offsets,
+                       const int32_t* neighbours, const double* normals, double cos_angle, const void* colors, f3d_dtype cdtype,
+                       double max_color_dist, double self_weight, int iterations, int nclasses, double threshold,
+                       const int32_t* filter, int nfilter, int lastcol, int64_t* classes);
+int f3d_smooth_segment_dev(f3d_ctx* ctx, const void* votes, int vtype, int64_t n, int ncols, const int64_t* offsets,
+                           const int32_t* neighbours, const double* normals, double cos_angle, const void* colors, f3d_dtype cdtype,
+                           double max_color_dist, double self_weight, int iterations, int nclasses, double threshold,
+                           const int32_t* filter, int nfilter, int lastcol, int64_t* classes, void* stream);
+int f3d_ctx_reserve_smooth(f3d_ctx* ctx, int64_t n, int ncols, int iterations);
+
 /* ---- (f)#1: the adjacency itself, Fusion.save_data (Fusion3DSeg/fusion.py:374-375) -------- */
 /* tree = KDTree(points); adj = tree.query_radius(points, r=2*ds_radius): for every point the indices of all points
  * (itself included) whose float64 squared distance ((dx*dx + dy*dy) + dz*dz, sklearn's euclidean_rdist order) is
