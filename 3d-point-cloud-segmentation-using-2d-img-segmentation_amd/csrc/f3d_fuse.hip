@@ -777,22 +777,21 @@ __global__ __launch_bounds__(F3D_BLOCK, F3D_FUSE_WAVES) void k_fuse(const T* __r
 #else
     auto gather = [&](unsigned off) -> unsigned { return (unsigned)__builtin_amdgcn_raw_buffer_load_b8(cm_rsrc, (int)off, 0, 0); };
 #endif
-    lutw[tid] = reinterpret_cast<const uint32_t*>(cb->lut)[tid];          // lut, inv and cmin are adjacent in the book (256 dwords)
     auto stage_group = [&](int g) {                                       // whole block; caller brackets with barriers
-        const int nv = min(64, nviews - 64 * g);
-        for (int k = tid; k < nv * 24; k += F3D_BLOCK) {
-            const int vi = k / 24, f = k - vi * 24;
-            ctab[vi * F3D_CULL_ROW + f] = reinterpret_cast<const float*>(&views[64 * g + vi].cull_n32[0][0])[f];
+        // from the transposed tables k_fuse_setup left for this launch ([field][view]: a wave reads 64 consecutive words): the ten loads of
+        // a thread are independent and travel together -- one round trip per block instead of one per strided pass over the view records
+        float cv[6]; double vv[4];
+#pragma unroll
+        for (int r = 0; r < 6; ++r) cv[r] = ctabT[((size_t)g * 24 + (tid >> 6) + 4 * r) * 64 + lane];
+#pragma unroll
+        for (int r = 0; r < 4; ++r) vv[r] = (tid >> 6) + 4 * r < F3D_VHEAD ? vtabT[((size_t)g * F3D_VHEAD + (tid >> 6) + 4 * r) * 64 + lane] : 0.0;
+#pragma unroll
+        for (int r = 0; r < 6; ++r) ctab[lane * F3D_CULL_ROW + (tid >> 6) + 4 * r] = cv[r];
+        if (!F3D_VTAB_GLOBAL) {
+#pragma unroll
+            for (int r = 0; r < 4; ++r) if ((tid >> 6) + 4 * r < F3D_VHEAD) vtab[((tid >> 6) + 4 * r) * 64 + lane] = vv[r];
         }
-        if (!F3D_VTAB_GLOBAL)
-            for (int k = tid; k < nv * F3D_VHEAD; k += F3D_BLOCK) {
-                const int vi = k / F3D_VHEAD, f = k - vi * F3D_VHEAD;
-                vtab[f * 64 + vi] = reinterpret_cast<const double*>(&views[64 * g + vi])[f];
-            }
     };
-    if (TLDS && ngroups > 1) return;                                      // (never launched: LDS-staged tables serve one 64-view group, see launch_fuse_t)
-    if (TLDS) stage_group(0);
-    __syncthreads();
 
     // XCD-aware tile mapping: blocks b, b+8, b+16, ... share an XCD (round-robin dispatch).  The XCDs take CHUNKS of
     // 64 consecutive tiles in turn (chunk c -> XCD c mod 8): with a cell-sorted cloud a chunk is a compact region of
@@ -810,12 +809,61 @@ __global__ __launch_bounds__(F3D_BLOCK, F3D_FUSE_WAVES) void k_fuse(const T* __r
     const int xcd = blockIdx.x & 7, bx = blockIdx.x >> 3, gx = gridDim.x >> 3;
     uint32_t* const hcol0 = hist + tid;
     uint32_t* const hcol1 = PPL == 2 ? hist + hdw * F3D_BLOCK + tid : hcol0;
-    for (int j = bx; j < tiles_per_xcd; j += gx) {
-        const int tile = ((j >> xlog) << (xlog + 3)) + (xcd << xlog) + (j & ((1 << xlog) - 1));
-        if (tile >= ntiles) continue;
+    // The tile loop is ROTATED: a tile's points are REQUESTED one tile ahead (the coordinates as stored: loads, no arithmetic) and
+    // CONSUMED at the turn of the loop; the perm words they are found through are requested two tiles ahead.  Vector-memory results
+    // return in issue order, so the one place where these loads cost the current tile nothing is behind its last mask gather: they
+    // go out right behind the final vote drain, in front of the epilogue.  The coordinates of tile k+1 and the perm words
+    // of tile k+2 then travel while tile k scans its bins and stores its labels, and the turn of the loop is the only wait for either.
+    // Only a position the block will consume is ever requested, and nothing beyond n.
+    const auto tile_at = [&](int jj) { return ((jj >> xlog) << (xlog + 3)) + (xcd << xlog) + (jj & ((1 << xlog) - 1)); };
+    const auto next_pos = [&](int jj) { while (jj < tiles_per_xcd && tile_at(jj) >= ntiles) jj += gx; return jj; };   // >= tiles_per_xcd: none left
+    const auto req_perm = [&](int t, int ln, int (&o)[2]) {               // caller-order indices of the lane's two points of tile t
+#pragma unroll
+        for (int q = 0; q < 2; ++q) {
+            const int i = t * TILE + (tid >> 6) * (64 * PPL) + ln + 64 * q;
+            o[q] = ((q < PPL) & (i < npts)) ? (perm ? perm[i] : i) : i;
+        }
+    };
+    // the coordinates of those points.  No branch around a load: a lane without a point reads point 0 (n > 0 here) and drops it when the
+    // tile is consumed
+    const auto req_xyz = [&](int t, const int (&o)[2], T (&r)[2][3], bool pinned) {
+        int idx[2];
+#pragma unroll
+        for (int q = 0; q < 2; ++q) {
+            const int i = t * TILE + (tid >> 6) * (64 * PPL) + lane + 64 * q;
+            idx[q] = ((q < PPL) & (i < npts)) ? (gather_xyz ? o[q] : i) : 0;
+        }
+        // (an empty dependency, as for the votes: the addresses exist only from here on, so the scheduler cannot hoist the loads
+        // above the view loops' gathers and the drain; the scheduling barrier keeps them from sinking into the epilogue)
+        if (pinned) asm volatile("" : "+v"(idx[0]), "+v"(idx[1]));
+#pragma unroll
+        for (int q = 0; q < 2; ++q) { const T* s = xyz + 3 * (int64_t)idx[q]; r[q][0] = s[0]; r[q][1] = s[1]; r[q][2] = s[2]; }
+        if (pinned) __builtin_amdgcn_sched_barrier(0);
+    };
+    int j = next_pos(bx);
+    if (j >= tiles_per_xcd) return;                                       // (no barrier follows)
+    int jn = next_pos(j + gx);                                            // the block's next valid position
+    int orig[2], orig_n[2], orig_nn[2] = {0, 0};
+    T raw[2][3], raw_n[2][3];
+    req_perm(tile_at(j), lane, orig_n);
+    if (jn < tiles_per_xcd) req_perm(tile_at(jn), lane, orig_nn);
+    // the block's tables are staged behind the first perm request, and the first tile's coordinates travel across the barrier
+    lutw[tid] = reinterpret_cast<const uint32_t*>(cb->lut)[tid];          // lut, inv and cmin are adjacent in the book (256 dwords)
+    if (TLDS && ngroups > 1) return;                                      // (never launched: LDS-staged tables serve one 64-view group, see launch_fuse_t)
+    if (TLDS) stage_group(0);
+    req_xyz(tile_at(j), orig_n, raw_n, false);
+    __syncthreads();
+    for (;;) {
+        // the loop turns: the requested tile becomes the current one (everything asked for so far is waited for here)
+#pragma unroll
+        for (int q = 0; q < 2; ++q) {
+            orig[q] = orig_n[q]; raw[q][0] = raw_n[q][0]; raw[q][1] = raw_n[q][1]; raw[q][2] = raw_n[q][2];
+            orig_n[q] = orig_nn[q];
+        }
+        const int jnn = jn < tiles_per_xcd ? next_pos(jn + gx) : tiles_per_xcd;   // ... and the one after it
+        const int tile = tile_at(j);
         const int i0 = tile * TILE + (tid >> 6) * (64 * PPL) + lane;      // this lane's first point; its second is i0 + 64
         bool live[2], act[2], defer[2];
-        int orig[2];
         f32x2 DX, DY, DZ;                                                  // offsets of the lane's two points from the box centre
         float c0, c1, c2, e0, e1, e2, ps_box;
         bool wave_any;
@@ -826,9 +874,7 @@ __global__ __launch_bounds__(F3D_BLOCK, F3D_FUSE_WAVES) void k_fuse(const T* __r
             for (int q = 0; q < 2; ++q) {
                 const int i = i0 + 64 * q;
                 live[q] = (q < PPL) & (i < npts);
-                orig[q] = live[q] ? (perm ? perm[i] : i) : i;                      // caller-order index of this point
-                p[q].x = p[q].y = p[q].z = 0.0;
-                if (live[q]) p[q] = f3d_load_p3(xyz, (int64_t)(gather_xyz ? orig[q] : i));
+                p[q].x = live[q] ? (double)raw[q][0] : 0.0; p[q].y = live[q] ? (double)raw[q][1] : 0.0; p[q].z = live[q] ? (double)raw[q][2] : 0.0;
                 // first of several view chunks of a gathered cloud: leave the points behind in cell order, the later chunks stream them
                 if (CARRY && xyz_keep && live[q]) { xyz_keep[3 * (size_t)i] = (T)p[q].x; xyz_keep[3 * (size_t)i + 1] = (T)p[q].y; xyz_keep[3 * (size_t)i + 2] = (T)p[q].z; }
                 const double pscale = (fabs(p[q].x) + fabs(p[q].y)) + fabs(p[q].z);
@@ -1105,9 +1151,18 @@ __global__ __launch_bounds__(F3D_BLOCK, F3D_FUSE_WAVES) void k_fuse(const T* __r
                 }
             }
         }
+        // the last votes are drained (the tile's last wait for a gather), then the next tile's coordinates and the perm words of the one
+        // after it go out.  (Requested in front of the drain they measured no faster: a wait count behind loads that only some paths
+        // issue is derived for the path without them, so the drain then waits for the coordinates too unless it is written once per path.)
+        vote(0, pend[0]); vote(1, pend[1]);
+        if (jn < tiles_per_xcd) req_xyz(tile_at(jn), orig_n, raw_n, true);
+        if (jnn < tiles_per_xcd) {
+            int ln = lane;
+            asm volatile("" : "+v"(ln));
+            req_perm(tile_at(jnn), ln, orig_nn);
+        }
 #pragma unroll
         for (int q = 0; q < PPL; ++q) {
-            vote(q, pend[q]);
             const bool part = act[q] & ((PART && slot[q] >= 0) | (unsure[q] != 0u));   // unproven views: the float64 tier adds their votes to the parked bins
             bool full = defer[q] | (part & !part_rt);          // ... or redoes the point from nothing
             defer[q] = defer[q] | part;
@@ -1155,6 +1210,8 @@ __global__ __launch_bounds__(F3D_BLOCK, F3D_FUSE_WAVES) void k_fuse(const T* __r
             }
             if (bad & !d) atomicOr(err, F3D_DEVERR_FUSE);
         }
+        if (jn >= tiles_per_xcd) break;
+        j = jn; jn = jnn;
     }
 }
 
