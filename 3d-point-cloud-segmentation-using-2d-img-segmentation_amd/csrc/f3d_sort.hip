@@ -18,8 +18,11 @@
 //   k_rs_scatter<2>: LSD pass 2 (high byte, stable): perm
 //   k_gather_xyz   : sorted[j] = xyz[perm[j]]     (only for the "prepared layout" entry point; the
 //                    in-step sort lets the fused kernel read xyz through perm instead)
-// A tile's ranks come from per-wave digit counts in LDS and 8 ballots per 64 keys (match on the digit's bits): no global atomic,
-// no look-back chain, the same perm in every run (equal keys keep their index order: both passes are stable).
+// A tile's ranks come from per-wave digit counts in LDS and, per round of 64 keys, one 64-bit lane mask per digit value in LDS (every lane
+// ORs its bit into its digit's mask, reads the mask back and counts the lanes below it: k_rs_scatter): no global atomic, no look-back
+// chain, the same perm in every run (equal keys keep their index order: both passes are stable).  (Until the lane masks a round matched
+// the digit's bits with 8 ballots on a per-lane 64-bit mask and read its counts through a volatile generic pointer: 96 vector
+// instructions and two flat round trips per round, 50 / 48 us per pass at 10M points against 42 / 38 now, profiles/sort_rank.md.)
 // History: a first version used one returning global atomic per point (counting sort): ~0.5 ms per kernel at 10M points.  r1/r2
 // used rocprim::radix_sort_pairs on (uint16 key, uint32 index): 0.27 ms for the whole sort at 10M points, of which 2 x 81 us in
 // its onesweep passes (decoupled look-back); the passes here move fewer bytes (the index is implicit in pass 1, the key is
@@ -287,12 +290,33 @@ __device__ __forceinline__ uint32_t rs_excl_scan256(uint32_t v, uint32_t* wsum /
     return before + inc - v;
 }
 
+// One point of order in a ranking round (see k_rs_scatter): an acquire-release fence over LDS at workgroup scope -- the compiler may
+// move no LDS access across it, and it compiles to `s_waitcnt lgkmcnt(0)`, so every LDS instruction the wave issued above has
+// completed -- and a wave barrier, which keeps the scheduler from moving anything else across.  (A wavefront-scope fence emits no wait.)
+__device__ __forceinline__ void rs_round_order() {
+    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup", "local");
+    __builtin_amdgcn_wave_barrier();
+}
+
 // One LSD pass over a tile.  PASS 1: digit = low byte of keys[i]; writes the record (high byte, i) to the key's place in low-byte
 // order.  PASS 2: digit = the record's high byte (pass-1 order, stable); writes the record's index to perm.  offs = the scanned
 // blkhist, tot = the digit totals.
-// The tile is first ordered in LDS (per-wave digit counts -> positions; ranks inside a round from 8 ballots), then written out by
-// consecutive threads: the keys of one digit value leave as one contiguous run (~128 B of records at 8192 keys / 256 values)
+// The tile is first ordered in LDS (per-wave digit counts -> positions; ranks inside a round from the wave's lane masks), then written
+// out by consecutive threads: the keys of one digit value leave as one contiguous run (~128 B of records at 8192 keys / 256 values)
 // instead of 64 scattered stores per instruction (measured at 10M keys: pass 1 144 -> 95 us with the run-wise output).
+//
+// Ranking a round (64 consecutive keys of a wave).  The wave owns wmask[wave][256], one 64-bit lane mask per digit value, all zero
+// between rounds, and wcount[wave][256], the tile position of the wave's next key of each digit value.
+//   (1) every live lane ORs its lane bit into wmask[wave][digit]                     (ds_or_b64, no return; an OR has no order)
+//   (2) every live lane reads wmask[wave][digit] and wcount[wave][digit]             (ds_read_b64, ds_read_b32)
+//       rank = popc(mask & lanes below me): equal digits keep lane = index order; position = count + rank
+//   (3) the lane of rank 0 stores count + popc(mask) and a zero mask                  (ds_write_b32, ds_write_b64)
+// rs_round_order() stands between (1) and (2), between (2) and (3), and between (3) and the next round's (1): each time the wave
+// waits until its own LDS instructions have completed (lgkmcnt(0)) before it issues the next group, and the compiler keeps the groups
+// apart.  No other wave touches these words, so nothing else needs an order; the OR, the loads and the stores are relaxed atomics so that the
+// compiler neither keeps a word in a register across a fence nor drops the store of the zero.  A lane without a key takes no part.
+// The mask tables lie on the first RS_WAVES x 2 KB of `srec` (a table of their own would cost a CU its third block), so the rounds
+// only compute positions -- kept with the digit in dig[r], no further register -- and the records are placed after a block barrier.
 template <int PASS, typename R>
 __global__ __launch_bounds__(RS_THREADS) void k_rs_scatter(const sort_key_t* __restrict__ keys, const R* __restrict__ recs_in, int64_t n,
                                                             const uint32_t* __restrict__ offs, const uint32_t* __restrict__ tot, int ntiles,
@@ -303,16 +327,18 @@ __global__ __launch_bounds__(RS_THREADS) void k_rs_scatter(const sort_key_t* __r
     extern __shared__ unsigned long long rs_dyn[];                   // the tile in digit order: RS_TILE records (+ pass 1: their low bytes)
     R* srec = reinterpret_cast<R*>(rs_dyn);
     uint8_t* sdig = reinterpret_cast<uint8_t*>(srec + RS_TILE);      // pass 1 only: the record carries the HIGH byte, the run is found by the low one
+    static_assert((size_t)RS_WAVES * 256 * sizeof(unsigned long long) <= (size_t)RS_TILE * sizeof(uint32_t), "the lane masks must fit under the records");
+    static_assert(RS_TILE <= (1 << 16), "a tile position is packed into 16 bits of dig[r]");
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    volatile uint32_t* mine = wcount[wave];
+    unsigned long long* const wmask = rs_dyn + wave * 256;           // this wave's lane masks (until the records are placed)
     // requested first: the two table entries of this thread's digit value (latency hidden behind the key loads and the counting)
     const int d_own = threadIdx.x & 255;
     const bool own = threadIdx.x < 256;
     const uint32_t t_d = own ? tot[d_own] : 0u;
     const uint32_t o_d = own ? offs[(size_t)d_own * ntiles + blockIdx.x] : 0u;
-    for (int k = threadIdx.x; k < RS_WAVES * 256; k += RS_THREADS) (&wcount[0][0])[k] = 0u;
+    for (int k = threadIdx.x; k < RS_WAVES * 256; k += RS_THREADS) { (&wcount[0][0])[k] = 0u; rs_dyn[k] = 0ull; }
     __syncthreads();
-    uint32_t dig[RS_ROUNDS];
+    uint32_t dig[RS_ROUNDS];                                         // the digit; after the ranking rounds (digit << 16) | tile position
     R val[RS_ROUNDS];                                                // the record that leaves (pass 1: built here; pass 2: the one that came in)
 #pragma unroll
     for (int r = 0; r < RS_ROUNDS; ++r) {
@@ -321,7 +347,7 @@ __global__ __launch_bounds__(RS_THREADS) void k_rs_scatter(const sort_key_t* __r
         if (i < n) {
             if (PASS == 1) { const uint32_t k = keys[i]; dig[r] = k & 0xFFu; val[r] = ((R)(k >> 8) << rs_rec<R>::shift) | (R)i; }
             else { val[r] = recs_in[i]; dig[r] = (uint32_t)(val[r] >> rs_rec<R>::shift) & 0xFFu; }
-            atomicAdd(const_cast<uint32_t*>(&mine[dig[r]]), 1u);
+            atomicAdd(&wcount[wave][dig[r]], 1u);
         }
     }
     __syncthreads();
@@ -337,22 +363,35 @@ __global__ __launch_bounds__(RS_THREADS) void k_rs_scatter(const sort_key_t* __r
         }
     }
     __syncthreads();
+    const unsigned long long below = (1ull << lane) - 1ull;
 #pragma unroll
     for (int r = 0; r < RS_ROUNDS; ++r) {
-        const bool live = dig[r] != 0xFFFFFFFFu;
-        unsigned long long same = __ballot(live);                    // lanes of this round with my digit value: 8 ballots, one per bit
-#pragma unroll
-        for (int b = 0; b < 8; ++b) {
-            const bool bit = (dig[r] >> b) & 1u;
-            const unsigned long long m = __ballot(bit);
-            same &= bit ? m : ~m;
+        const uint32_t d = dig[r];
+        const bool live = d != 0xFFFFFFFFu;
+        if (live) __hip_atomic_fetch_or(&wmask[d], 1ull << lane, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+        rs_round_order();                                            // (1) -> (2): the wave's ORs have landed
+        unsigned long long m = 0ull;
+        uint32_t base = 0u;
+        if (live) {
+            m = __hip_atomic_load(&wmask[d], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+            base = __hip_atomic_load(&wcount[wave][d], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
         }
-        if (live) {                                                  // (the wave's lanes run in lockstep: every read below precedes the leader's write)
-            const unsigned rank = __popcll(same & ((1ull << lane) - 1ull));
-            const uint32_t base = mine[dig[r]];
-            if (rank == 0u) mine[dig[r]] = base + (uint32_t)__popcll(same);
-            srec[base + rank] = val[r];
-            if (PASS == 1) sdig[base + rank] = (uint8_t)dig[r];
+        rs_round_order();                                            // (2) -> (3): every lane has its mask and count
+        const uint32_t rank = (uint32_t)__popcll(m & below);
+        if (live && rank == 0u) {
+            __hip_atomic_store(&wcount[wave][d], base + (uint32_t)__popcll(m), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+            __hip_atomic_store(&wmask[d], 0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+        }
+        rs_round_order();                                            // (3) -> the next round's (1): count advanced, mask zero again
+        if (live) dig[r] = (d << 16) | (base + rank);
+    }
+    __syncthreads();                                                 // every wave is done with its masks: the records may overwrite them
+#pragma unroll
+    for (int r = 0; r < RS_ROUNDS; ++r) {
+        if (dig[r] != 0xFFFFFFFFu) {
+            const uint32_t pos = dig[r] & 0xFFFFu;
+            srec[pos] = val[r];
+            if (PASS == 1) sdig[pos] = (uint8_t)(dig[r] >> 16);
         }
     }
     __syncthreads();
