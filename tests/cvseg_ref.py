@@ -107,8 +107,8 @@ def instance_seperate(classes, adj, instance_classes=None, minimum_points=1):
     return np.arange(m), ids, info, clusters, boundaries
 
 
-def color_segment(classes_unused, adj, colors, ids, seeds, threshold, neutral_ids=(0,), max_level=10):
-    """ids updated in place and returned."""
+def color_segment(classes_unused, adj, colors, ids, seeds, threshold, neutral_ids=(0,), max_level=10, counts=None):
+    """ids updated in place and returned; `counts` (a list) receives every seed's number of accepted points."""
     rows = _rows(adj)
     n = len(ids)
     thr = np.broadcast_to(np.asarray(threshold, dtype=np.float64), (3,))
@@ -136,6 +136,8 @@ def color_segment(classes_unused, adj, colors, ids, seeds, threshold, neutral_id
                     seen[q] = True
                     todo.append((q, lv + 1))
         neutral[ids == sid] = False
+        if counts is not None:
+            counts.append(count)
     return ids
 
 
