@@ -337,8 +337,6 @@ double neighbour_cell(double radius, const double ext[3], int dim[3], Fits fits)
     }
 }
 
-int bits_for(int64_t v) { int b = 0; while (((int64_t)1 << b) < v) ++b; return b; }     // smallest b with 2^b >= v
-
 }  // namespace
 
 static int ensure_table(f3d_ctx* ctx, int64_t hw);
@@ -2551,14 +2549,14 @@ int f3d_estimate_normals_batch_dev(f3d_ctx* ctx, const double* xyz, int nframes,
     double lo[3], ext[3];
     if ((rc = cloud_bbox(ctx, xyz, F3D_F64, total, s, "estimate_normals", lo, ext))) return rc;
     // the grid fits when frame + cell coordinates fit a 63-bit key.  No table over the cells: the key space may be sparse.
-    const int fbits = bits_for(nframes);
+    const int fbits = f3d_bits_for(nframes, 0);
     f3d_nrmgrid g;
     const double cell = neighbour_cell(radius, ext, g.dim, [&](const double d[3]) {
         return d[0] <= 1073741824.0 && d[1] <= 1073741824.0 && d[2] <= 1073741824.0 &&
-               fbits + bits_for((int64_t)d[0]) + bits_for((int64_t)d[1]) + bits_for((int64_t)d[2]) <= 63;
+               fbits + f3d_bits_for((int64_t)d[0], 0) + f3d_bits_for((int64_t)d[1], 0) + f3d_bits_for((int64_t)d[2], 0) <= 63;
     });
     g.shift[0] = 0;
-    for (int c = 0; c < 3; ++c) { g.lo[c] = lo[c]; g.shift[c + 1] = g.shift[c] + bits_for(g.dim[c]); }
+    for (int c = 0; c < 3; ++c) { g.lo[c] = lo[c]; g.shift[c + 1] = g.shift[c] + f3d_bits_for(g.dim[c], 0); }
     const int bits = fbits + g.shift[3];
     g.key_bits = bits < 1 ? 1 : bits;
     g.inv_cell = 1.0 / cell;

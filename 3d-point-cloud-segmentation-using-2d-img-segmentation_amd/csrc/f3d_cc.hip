@@ -34,11 +34,9 @@ __global__ __launch_bounds__(CB) void k_cc_hook(const int64_t* __restrict__ clas
     }
 }
 
-__global__ __launch_bounds__(CB) void k_cc_compress(int32_t* parent, int64_t n, int64_t* __restrict__ root) {
+__global__ __launch_bounds__(CB) void k_cc_compress(const int32_t* parent, int64_t n, int64_t* __restrict__ root) {
     for (int64_t i = (int64_t)blockIdx.x * CB + threadIdx.x; i < n; i += (int64_t)gridDim.x * CB) {
-        int32_t x = (int32_t)i;
-        for (;;) { const int32_t p = f3d_uf_load(parent + x); if (p == x) break; x = p; }
-        root[i] = x;
+        root[i] = f3d_uf_root(parent, (int32_t)i);
     }
 }
 
@@ -85,23 +83,6 @@ struct fo_words { int32_t nf[2]; int32_t levels; int32_t pad; };
 __device__ __forceinline__ int fo_rank(int64_t c, const int64_t* __restrict__ inst, int k) {
     for (int r = 0; r < k; ++r) if (inst[r] == c) return r;
     return -1;
-}
-
-// exclusive scan of one int per thread over a block of CB threads; *total receives the block's sum
-__device__ __forceinline__ int fo_block_scan(int v, int* lds, int* total) {
-    const int t = threadIdx.x;
-    lds[t] = v;
-    __syncthreads();
-    for (int d = 1; d < CB; d <<= 1) {
-        const int x = t >= d ? lds[t - d] : 0;
-        __syncthreads();
-        lds[t] += x;
-        __syncthreads();
-    }
-    const int incl = lds[t];
-    *total = lds[CB - 1];
-    __syncthreads();
-    return incl - v;
 }
 
 __global__ __launch_bounds__(CB) void k_fo_keys(const int64_t* __restrict__ classes, int64_t n, const int64_t* __restrict__ root,
@@ -193,8 +174,8 @@ __global__ __launch_bounds__(CB) void k_fo_count(int64_t n, const int64_t* __res
         if (i == 0 || FC[i - 1] != C) i0[C] = i;
         if (i == nf - 1 || FC[i + 1] != C) i1[C] = i;
     }
-    int tot;
-    fo_block_scan(sum, lds, &tot);
+    int ex, tot;
+    f3d_block_scan<CB>(sum, lds, ex, tot);
     if (threadIdx.x == 0) part[blockIdx.x] = tot;
 }
 
@@ -205,8 +186,8 @@ __global__ __launch_bounds__(CB) void k_fo_top(int32_t* __restrict__ part, fo_wo
     constexpr int PER = FO_GRID / CB;
     int v[PER], sum = 0;
     for (int k = 0; k < PER; ++k) { v[k] = part[threadIdx.x * PER + k]; sum += v[k]; }
-    int tot;
-    int run = fo_block_scan(sum, lds, &tot);
+    int run, tot;
+    f3d_block_scan<CB>(sum, lds, run, tot);
     for (int k = 0; k < PER; ++k) { part[threadIdx.x * PER + k] = run; run += v[k]; }
     if (threadIdx.x == 0) { w->nf[cur ^ 1] = tot; w->levels += 1; }
 }
@@ -222,8 +203,8 @@ __global__ __launch_bounds__(CB) void k_fo_apply(const int32_t* __restrict__ cnt
     for (int b = lo; b < hi; b += CB) {
         const int i = b + (int)threadIdx.x;
         const int v = i < hi ? cnt[i] : 0;
-        int tot;
-        const int ex = fo_block_scan(v, lds, &tot);
+        int ex, tot;
+        f3d_block_scan<CB>(v, lds, ex, tot);
         if (i < hi) gx[i] = carry + ex;
         carry += tot;
     }
@@ -299,8 +280,6 @@ fo_layout fo_layout_for(int64_t n) {
 
 size_t f3d_flood_scratch_bytes(int64_t n) { return fo_layout_for(n < 1 ? 1 : n).total; }
 
-#define FO_TRY(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) return e_; } while (0)
-
 hipError_t f3d_launch_flood_order(const int64_t* classes, int64_t n, const int64_t* offs, const int32_t* nbrs, const int64_t* inst, int k,
                                   int64_t* root, int64_t* order, int64_t* coffs, uint8_t* flags, void* scratch, int* err, int64_t stats[4],
                                   hipStream_t s) {
@@ -320,20 +299,20 @@ hipError_t f3d_launch_flood_order(const int64_t* classes, int64_t n, const int64
     unsigned long long* best = (unsigned long long*)ka;     // the unsorted keys are dead once the sort has run
     const dim3 g((unsigned)f3d_grid_for(n + 1, CB, 16384)), b(CB), gl(FO_GRID);
 
-    FO_TRY(f3d_launch_components(classes, n, offs, nbrs, parent, root, err, s, F3D_DEVERR_FLOOD));
+    F3D_TRY(f3d_launch_components(classes, n, offs, nbrs, parent, root, err, s, F3D_DEVERR_FLOOD));
     hipLaunchKernelGGL(k_fo_keys, g, b, 0, s, classes, n, root, inst, k, ka);
-    unsigned bits = 32; while (bits < 64 && ((uint64_t)1 << (bits - 32)) < (uint64_t)k + 1) ++bits;
+    const unsigned bits = 32 + (unsigned)f3d_bits_for((int64_t)k + 1, 0);          // k + 1 ranks above the 32 root bits
     size_t tb = L.temp_bytes;
-    FO_TRY(rocprim::radix_sort_keys(base + L.temp, tb, ka, kb, (size_t)n, 0u, bits, s));
+    F3D_TRY(rocprim::radix_sort_keys(base + L.temp, tb, ka, kb, (size_t)n, 0u, bits, s));
     hipLaunchKernelGGL(k_fo_heads, g, b, 0, s, kb, n, cid);
     tb = L.temp_bytes;
-    FO_TRY(rocprim::exclusive_scan(base + L.temp, tb, cid, cid, (int32_t)0, (size_t)n + 1, rocprim::plus<int32_t>(), s));
-    FO_TRY(hipMemsetAsync(w, 0, sizeof(fo_words), s));
-    FO_TRY(hipMemsetAsync(slot, 0xff, (size_t)n * 4, s));
-    FO_TRY(hipMemsetAsync(order, 0xff, (size_t)n * 8, s));
-    FO_TRY(hipMemsetAsync(coffs, 0, 8, s));
+    F3D_TRY(rocprim::exclusive_scan(base + L.temp, tb, cid, cid, (int32_t)0, (size_t)n + 1, rocprim::plus<int32_t>(), s));
+    F3D_TRY(hipMemsetAsync(w, 0, sizeof(fo_words), s));
+    F3D_TRY(hipMemsetAsync(slot, 0xff, (size_t)n * 4, s));
+    F3D_TRY(hipMemsetAsync(order, 0xff, (size_t)n * 8, s));
+    F3D_TRY(hipMemsetAsync(coffs, 0, 8, s));
     hipLaunchKernelGGL(k_fo_seeds, g, b, 0, s, kb, n, cid, coffs, order, slot, F[0], FC[0], w);
-    FO_TRY(hipMemsetAsync(best, 0xff, (size_t)n * 8, s));
+    F3D_TRY(hipMemsetAsync(best, 0xff, (size_t)n * 8, s));
 
     fo_words hw;
     int cur = 0;
@@ -346,9 +325,9 @@ hipError_t f3d_launch_flood_order(const int64_t* classes, int64_t n, const int64
             hipLaunchKernelGGL(k_fo_place, gl, b, 0, s, n, offs, nbrs, order, slot, F[cur], FC[cur], w, cur, best, gx, i0, i1, F[cur ^ 1],
                                FC[cur ^ 1]);
         }
-        FO_TRY(hipGetLastError());
-        FO_TRY(hipMemcpyAsync(&hw, w, sizeof(hw), hipMemcpyDeviceToHost, s));
-        FO_TRY(hipStreamSynchronize(s));
+        F3D_TRY(hipGetLastError());
+        F3D_TRY(hipMemcpyAsync(&hw, w, sizeof(hw), hipMemcpyDeviceToHost, s));
+        F3D_TRY(hipStreamSynchronize(s));
         ++stats[3];
         if (hw.nf[cur] == 0) break;
         if (stats[3] * FO_CHUNK > n + 2 * FO_CHUNK) return hipErrorUnknown;   // every level places a point: cannot happen
@@ -356,10 +335,10 @@ hipError_t f3d_launch_flood_order(const int64_t* classes, int64_t n, const int64
     hipLaunchKernelGGL(k_fo_boundary, g, b, 0, s, classes, n, offs, nbrs, root, slot, flags);
     int32_t mh = 0;
     int64_t lh = 0;
-    FO_TRY(hipMemcpyAsync(&mh, cid + n, 4, hipMemcpyDeviceToHost, s));
-    FO_TRY(hipStreamSynchronize(s));
-    if (mh > 0) FO_TRY(hipMemcpyAsync(&lh, coffs + mh, 8, hipMemcpyDeviceToHost, s));
-    FO_TRY(hipStreamSynchronize(s));
+    F3D_TRY(hipMemcpyAsync(&mh, cid + n, 4, hipMemcpyDeviceToHost, s));
+    F3D_TRY(hipStreamSynchronize(s));
+    if (mh > 0) F3D_TRY(hipMemcpyAsync(&lh, coffs + mh, 8, hipMemcpyDeviceToHost, s));
+    F3D_TRY(hipStreamSynchronize(s));
     stats[0] = mh; stats[1] = lh; stats[2] = hw.levels;
     return hipGetLastError();
 }

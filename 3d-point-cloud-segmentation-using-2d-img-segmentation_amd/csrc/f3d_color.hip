@@ -129,29 +129,28 @@ __global__ __launch_bounds__(CT) void k_color_grow(const T* __restrict__ colors,
     if (t == 0) *stats += accepted;
 }
 
+struct color_layout { size_t neutral, inq, best, qa, qb, acc, total; };
+
+color_layout color_layout_for(int64_t n) {
+    const size_t n4 = (size_t)(n < 1 ? 1 : n) * 4;
+    f3d_carve c;                                                         // (a braced list is evaluated left to right)
+    return {c.take(n4 / 4), c.take(n4), c.take(n4 * 2), c.take(n4), c.take(n4), c.take(n4), c.off};
+}
+
 }  // namespace
 
-size_t f3d_color_scratch_bytes(int64_t n) {
-    f3d_carve c;
-    const size_t n4 = (size_t)(n < 1 ? 1 : n) * 4;
-    c.take(n4 / 4); c.take(n4); c.take(n4 * 2); c.take(n4); c.take(n4); c.take(n4);
-    return c.off;
-}
+size_t f3d_color_scratch_bytes(int64_t n) { return color_layout_for(n).total; }
 
 hipError_t f3d_launch_color_segment(const void* colors, int dtype, int64_t n, const int64_t* offs, const int32_t* nbrs, int64_t* ids,
                                     const int64_t* seeds, int64_t nseeds, const f3d_color_args& a, void* scratch, int64_t* stats_dev, int* err,
                                     hipStream_t s) {
     if (n <= 0 || nseeds <= 0) return hipSuccess;
     if (n > 0x7fffffffLL || nseeds > 0x7ffffffeLL) return hipErrorInvalidValue;
-    f3d_carve c;
+    const color_layout L = color_layout_for(n);
     char* base = (char*)scratch;
-    const size_t n4 = (size_t)n * 4;
-    uint8_t* neutral = (uint8_t*)(base + c.take((size_t)n));
-    int32_t* inq = (int32_t*)(base + c.take(n4));
-    unsigned long long* best = (unsigned long long*)(base + c.take(n4 * 2));
-    int32_t* qa = (int32_t*)(base + c.take(n4));
-    int32_t* qb = (int32_t*)(base + c.take(n4));
-    int32_t* acc = (int32_t*)(base + c.take(n4));
+    uint8_t* neutral = (uint8_t*)(base + L.neutral);
+    int32_t *inq = (int32_t*)(base + L.inq), *qa = (int32_t*)(base + L.qa), *qb = (int32_t*)(base + L.qb), *acc = (int32_t*)(base + L.acc);
+    unsigned long long* best = (unsigned long long*)(base + L.best);
     hipLaunchKernelGGL(k_color_init, dim3(f3d_grid_for(n, IB, 16384)), dim3(IB), 0, s, ids, n, a, neutral, inq, best);
     if (dtype == F3D_F64)
         hipLaunchKernelGGL(k_color_grow<double>, dim3(1), dim3(CT), 0, s, (const double*)colors, n, offs, nbrs, ids, seeds, nseeds, a, neutral,

@@ -34,21 +34,28 @@ inline int f3d_grid_for(int64_t n, int per_block, int cap) {
     return (int)g;
 }
 
+// returns a failed HIP call's error from the enclosing function
+#define F3D_TRY(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) return e_; } while (0)
+
+// bits of a radix key: the smallest b >= min_bits with 2^b >= v, i.e. rounded up, 2^b itself needs b bits (v = number of key
+// values, so keys 0 .. m take f3d_bits_for(m + 1, ..)); min_bits = 1 where a sort must order at least one bit
+inline int f3d_bits_for(int64_t v, int min_bits) { int b = min_bits; while (((int64_t)1 << b) < v) ++b; return b; }
+
 // offsets of the pieces of a scratch buffer: each piece starts on a 256-byte boundary; `off` ends as the total size
 struct f3d_carve {
     size_t off = 0;
     size_t take(size_t bytes) { const size_t at = off; off += (bytes + 255) & ~(size_t)255; return at; }
 };
 
-// inclusive-to-exclusive scan of one int per thread over a workgroup of NT threads (lds: NT ints): ex = sum of the values of
-// the threads before this one, tot = the workgroup's sum.  Every thread of the workgroup must call it.
-template <int NT>
-__device__ __forceinline__ void f3d_block_scan(int v, int* lds, int& ex, int& tot) {
+// inclusive-to-exclusive scan of one int / uint32 per thread over a workgroup of NT threads (lds: NT of them): ex = sum of the values
+// of the threads before this one, tot = the workgroup's sum.  Every thread of the workgroup must call it.
+template <int NT, typename T>
+__device__ __forceinline__ void f3d_block_scan(T v, T* lds, T& ex, T& tot) {
     const int t = threadIdx.x;
     lds[t] = v;
     __syncthreads();
     for (int d = 1; d < NT; d <<= 1) {
-        const int x = t >= d ? lds[t - d] : 0;
+        const T x = t >= d ? lds[t - d] : 0;
         __syncthreads();
         lds[t] += x;
         __syncthreads();
@@ -58,7 +65,7 @@ __device__ __forceinline__ void f3d_block_scan(int v, int* lds, int& ex, int& to
     __syncthreads();
 }
 
-// Lock-free union-find over int32 parents (f3d_cc.hip, f3d_mesh.hip): the larger root is always linked under the smaller one, so
+// Lock-free union-find over int32 parents (f3d_cc.hip, f3d_mesh.hip, f3d_planes.hip): the larger root is always linked under the smaller one, so
 // every component ends rooted at its minimum index.  Parent reads are agent-scope relaxed atomic loads (served by L2): a CU's L1
 // is not coherent with other CUs' atomics, and the CAS return value -- always current -- drives the retry.
 __device__ __forceinline__ int32_t f3d_uf_load(const int32_t* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
@@ -73,6 +80,11 @@ __device__ __forceinline__ int32_t f3d_find_root(int32_t* parent, int32_t x) {
     }
 }
 
+// the root of x by a read-only walk (after the links: compression passes, nothing is written)
+__device__ __forceinline__ int32_t f3d_uf_root(const int32_t* parent, int32_t x) {
+    for (;;) { const int32_t p = f3d_uf_load(parent + x); if (p == x) return x; x = p; }
+}
+
 // joins the components of a and b
 __device__ __forceinline__ void f3d_uf_link(int32_t* parent, int32_t a, int32_t b) {
     for (;;) {
@@ -83,6 +95,15 @@ __device__ __forceinline__ void f3d_uf_link(int32_t* parent, int32_t a, int32_t 
         if (old == a) break;
         a = old;                                                     // someone else linked a first: continue from there
     }
+}
+
+// doubles -> unsigned integers of the same order (min / max by integer atomics; exact in any order)
+__device__ __forceinline__ unsigned long long f3d_ord_enc(double x) {
+    const unsigned long long b = (unsigned long long)__double_as_longlong(x);
+    return (b >> 63) ? ~b : (b | 0x8000000000000000ull);
+}
+__device__ __forceinline__ double f3d_ord_dec(unsigned long long u) {
+    return __longlong_as_double((long long)((u >> 63) ? (u & 0x7fffffffffffffffull) : ~u));
 }
 
 // One level of an ordered FIFO flood run by one workgroup of NT threads (f3d_color.hip, f3d_refine.hip).  `list[0..cnt)` are the

@@ -1,8 +1,8 @@
 // Mesh topology of segUtils/meshUtils.py (reference :235-333, :360-375) on gfx950, plus clean_mesh, their composition.
 //
 // The slot of a triangle corner is s = 3 * f + j.  Three building blocks serve every entry:
-//   group   : a stable rocPRIM radix sort of (key, position) pairs and a lower-bound kernel -> a CSR whose rows list their members
-//             in ascending position (vertex -> slots for vertex_triangle_mapping, cluster -> triangles for the area sums);
+//   group   : f3d_group_pairs (f3d_groups.h) of (key, position) pairs -> a CSR whose rows list their members in ascending position
+//             (vertex -> slots for vertex_triangle_mapping, cluster -> triangles for the area sums);
 //   compact : 0 / 1 flags of the vertices and of the faces in ONE array, one exclusive scan, one kernel that writes the
 //             renumbered faces (face order kept), the old -> new vertex ids and, when wanted, the surviving vertex rows;
 //   cluster : 3 edge keys (min << b | max, b = bits of nv) per triangle, radix sort limited to 2b (+1) bits, union of the triangles
@@ -11,9 +11,8 @@
 // keep_faces_by_vertices' first-appearance numbering: first[v] = atomicMin of the slots of kept faces that hold v; slot s is a
 // first occurrence iff first[tri[s]] == s; the scan of those flags over the slots is the new id.  Minima, not timing, decide.
 // Areas: 0.5 * sqrt((cx*cx + cy*cy) + cz*cz), c = cross(p0 - p1, p0 - p2) by plain multiply and subtract (no contraction).  A
-// cluster's members, in ascending triangle index, are cut into chunks of 4096; a chunk is summed by one wave (lane l adds the items
-// l, l + 64, l + 128, ... left to right, then the 64 lane sums meet in an xor butterfly, offsets 32, 16, .., 1) and the chunk sums
-// are summed the same way.  The shape depends on the member count alone; no float atomics.
+// cluster's members, in ascending triangle index, are cut into chunks of 4096; a chunk is summed by one wave (f3d_wave_sum) and the
+// chunk sums are summed the same way (f3d_groups.h).  The shape depends on the member count alone; no float atomics.
 // Every kernel after k_mesh_check returns at once when counts[2] is set (an index outside [0, nv)): nothing is written.
 #include <hip/hip_runtime.h>
 #include <math.h>
@@ -22,6 +21,7 @@
 #include <rocprim/device/device_scan.hpp>
 #include "f3d.h"
 #include "f3d_kernels.h"
+#include "f3d_groups.h"
 
 #pragma clang fp contract(off)
 
@@ -74,22 +74,6 @@ __global__ __launch_bounds__(MB) void k_mesh_corner_keys(const void* __restrict_
                                                          uint32_t* __restrict__ keys, uint32_t* __restrict__ vals) {
     if (counts[2]) return;
     MESH_LOOP(s, n3) { keys[s] = (uint32_t)tri_at(tris, itype, s); vals[s] = (uint32_t)s; }
-}
-
-// offsets[k] = first position of key k in the sorted keys, k = 0 .. nkeys (nkeys_dev, when given, holds nkeys)
-__global__ __launch_bounds__(MB) void k_mesh_lower_bound(const uint32_t* __restrict__ keys, int64_t n, int64_t nkeys,
-                                                         const uint32_t* __restrict__ nkeys_dev, const int64_t* counts,
-                                                         int64_t* __restrict__ offsets) {
-    if (counts[2]) return;
-    if (nkeys_dev) nkeys = (int64_t)*nkeys_dev;
-    MESH_LOOP(k, nkeys + 1) {
-        int64_t lo = 0, hi = n;
-        while (lo < hi) {
-            const int64_t mid = (lo + hi) >> 1;
-            if ((int64_t)keys[mid] < k) lo = mid + 1; else hi = mid;
-        }
-        offsets[k] = lo;
-    }
 }
 
 __global__ __launch_bounds__(MB) void k_mesh_vmap_out(const uint32_t* __restrict__ slots, int64_t n3, const int64_t* counts,
@@ -249,8 +233,7 @@ __global__ __launch_bounds__(MB) void k_mesh_roots(const int32_t* parent, int64_
     if (counts[2]) return;
     MESH_LOOP(f, nt + 1) {
         if (f == nt) { flags[f] = 0; continue; }
-        int32_t x = (int32_t)f;
-        for (;;) { const int32_t p = f3d_uf_load(parent + x); if (p == x) break; x = p; }
+        const int32_t x = f3d_uf_root(parent, (int32_t)f);
         root[f] = x;
         flags[f] = x == (int32_t)f && (!active || active[f]);
     }
@@ -271,56 +254,29 @@ __global__ __launch_bounds__(MB) void k_mesh_labels(const int32_t* __restrict__ 
     }
 }
 
-// wave_sum: lane l adds the items l, l + 64, l + 128, ... of [0, count) left to right, then the 64 lane sums meet in an xor butterfly
-template <typename At>
-__device__ __forceinline__ double wave_sum(int64_t count, int lane, At at) {
-    double acc = 0.0;
-    for (int64_t i = lane; i < count; i += 64) acc = acc + at(i);
-    for (int off = 32; off > 0; off >>= 1) acc = acc + __shfl_xor(acc, off);
-    return acc;
-}
-
-// partial[q] = wave_sum of the chunk of AREA_CHUNK consecutive members that starts at grouped position q.  A wave looks at 64
-// positions, finds the chunk starts among them (position - start of its cluster is a multiple of AREA_CHUNK) and sums each.
+// partial[q] = f3d_wave_sum of the chunk of AREA_CHUNK consecutive members that starts at grouped position q
 __global__ __launch_bounds__(MB) void k_mesh_chunk_sums(const double* __restrict__ tri_area, const uint32_t* __restrict__ order,
                                                         const uint32_t* __restrict__ skeys, const int64_t* __restrict__ starts,
                                                         const uint32_t* __restrict__ nclusters, int64_t nt, const int64_t* counts,
                                                         double* __restrict__ partial) {
     if (counts[2]) return;
-    const int64_t P = (int64_t)*nclusters;
     const int lane = threadIdx.x & 63;
-    for (int64_t w0 = (int64_t)blockIdx.x * MB + threadIdx.x - lane; w0 < nt; w0 += (int64_t)gridDim.x * MB) {
-        const int64_t p = w0 + lane;
-        bool head = false;
-        long long e = 0;
-        if (p < nt) {
-            const int64_t c = (int64_t)skeys[p];
-            if (c < P) { e = starts[c + 1]; head = ((p - starts[c]) % AREA_CHUNK) == 0; }
-        }
-        unsigned long long todo = __ballot(head);
-        while (todo) {
-            const int src = __ffsll((long long)todo) - 1;
-            todo &= todo - 1;
-            const int64_t q = w0 + src, ce = (int64_t)__shfl(e, src);
-            const int64_t len = ce - q < AREA_CHUNK ? ce - q : AREA_CHUNK;
-            const double sum = wave_sum(len, lane, [&](int64_t i) { return tri_area[order[q + i]]; });
-            if (lane == 0) partial[q] = sum;
-        }
-    }
+    f3d_chunk_heads<AREA_CHUNK, MB>(skeys, starts, nt, (int64_t)*nclusters, [&](int64_t q, int64_t len, int64_t) {
+        const double sum = f3d_wave_sum(len, lane, [&](int64_t i) { return tri_area[order[q + i]]; });
+        if (lane == 0) partial[q] = sum;
+    });
 }
 
-// one wave per cluster: the member count, and the area = wave_sum of the cluster's chunk sums
+// one wave per cluster: the member count, and the area = the sum of the cluster's chunk sums
 __global__ __launch_bounds__(MB) void k_mesh_cluster_sums(const double* __restrict__ partial, const int64_t* __restrict__ starts,
                                                           const uint32_t* __restrict__ nclusters, const int64_t* counts,
                                                           int64_t* __restrict__ cluster_n, double* __restrict__ cluster_area) {
     if (counts[2]) return;
-    const int64_t P = (int64_t)*nclusters;
     const int lane = threadIdx.x & 63;
-    for (int64_t c = ((int64_t)blockIdx.x * MB + threadIdx.x) >> 6; c < P; c += ((int64_t)gridDim.x * MB) >> 6) {
-        const int64_t b = starts[c], e = starts[c + 1];
-        const double sum = wave_sum((e - b + AREA_CHUNK - 1) / AREA_CHUNK, lane, [&](int64_t j) { return partial[b + j * AREA_CHUNK]; });
+    f3d_group_waves<MB>(starts, (int64_t)*nclusters, [&](int64_t c, int64_t b, int64_t e) {
+        const double sum = f3d_chunks_sum<AREA_CHUNK>(b, e, lane, [&](int64_t q) { return partial[q]; });
         if (lane == 0) { cluster_n[c] = e - b; cluster_area[c] = sum; }
-    }
+    });
 }
 
 // ---- clean_mesh -------------------------------------------------------------------------------------------------------
@@ -339,8 +295,6 @@ __global__ __launch_bounds__(MB) void k_mesh_clean_keep(const void* __restrict__
     }
 }
 
-int bits_for(int64_t v) { int b = 1; while (((int64_t)1 << b) < v) ++b; return b; }     // smallest b >= 1 with 2^b >= v
-
 struct mesh_layout {
     size_t keys_a, keys_b, vals_a, vals_b, flags, parent, root, first, fkeep, active, clusters, cluster_n, cluster_area, tri_area, partial, starts, temp,
         total;
@@ -352,9 +306,8 @@ mesh_layout mesh_layout_for(int64_t nv, int64_t nt) {
     if (nt < 1) nt = 1;
     mesh_layout L;
     const size_t n3 = (size_t)nt * 3, nflags = (size_t)(nv + nt > 4 * nt ? nv + nt : 4 * nt) + 1;
-    size_t a = 0, b = 0, c = 0;
+    size_t a = 0, b = f3d_group_temp_bytes((int64_t)n3), c = 0;
     (void)rocprim::radix_sort_pairs(nullptr, a, (uint64_t*)nullptr, (uint64_t*)nullptr, (uint32_t*)nullptr, (uint32_t*)nullptr, n3, 0u, 64u);
-    (void)rocprim::radix_sort_pairs(nullptr, b, (uint32_t*)nullptr, (uint32_t*)nullptr, (uint32_t*)nullptr, (uint32_t*)nullptr, n3, 0u, 32u);
     (void)rocprim::exclusive_scan(nullptr, c, (uint32_t*)nullptr, (uint32_t*)nullptr, (uint32_t)0, nflags, rocprim::plus<uint32_t>());
     L.temp_bytes = (a > b ? (a > c ? a : c) : (b > c ? b : c)) + 256;
     f3d_carve k;
@@ -369,15 +322,13 @@ mesh_layout mesh_layout_for(int64_t nv, int64_t nt) {
     return L;
 }
 
-#define MESH_TRY(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) return e_; } while (0)
-
 bool mesh_sizes_ok(int64_t nv, int64_t nt) { return nv >= 0 && nv <= 0x7fffffffLL && nt >= 0 && 3 * nt <= 0x7fffffffLL; }
 
 dim3 grid_of(int64_t n) { return dim3(f3d_grid_for(n, MB, MGRID)); }
 
 // counts = 0, then the index check
 hipError_t mesh_begin(const void* tris, int itype, int64_t nt, int64_t nv, int64_t* counts, int* err, hipStream_t s) {
-    MESH_TRY(hipMemsetAsync(counts, 0, 4 * sizeof(int64_t), s));
+    F3D_TRY(hipMemsetAsync(counts, 0, 4 * sizeof(int64_t), s));
     if (nt > 0) hipLaunchKernelGGL(k_mesh_check, grid_of(3 * nt), dim3(MB), 0, s, tris, itype, 3 * nt, nv, counts, err, F3D_DEVERR_MESH);
     return hipGetLastError();
 }
@@ -388,12 +339,13 @@ hipError_t mesh_scan(const mesh_layout& L, char* base, size_t n, hipStream_t s) 
     return rocprim::exclusive_scan(base + L.temp, tb, flags, flags, (uint32_t)0, n, rocprim::plus<uint32_t>(), s);
 }
 
-// stable sort of the n (key, value) pairs in keys_a / vals_a by the low `bits` of the key -> keys_b / vals_b
-hipError_t mesh_sort32(const mesh_layout& L, char* base, size_t n, int bits, hipStream_t s) {
-    size_t tb = L.temp_bytes;
-    return rocprim::radix_sort_pairs(base + L.temp, tb, reinterpret_cast<uint32_t*>(base + L.keys_a), reinterpret_cast<uint32_t*>(base + L.keys_b),
-                                     reinterpret_cast<uint32_t*>(base + L.vals_a), reinterpret_cast<uint32_t*>(base + L.vals_b), n, 0u,
-                                     (unsigned)bits, s);
+// the n (key, position) pairs in keys_a / vals_a grouped by the low `bits` of the key -> keys_b / vals_b and the rows' starts.
+// The early-out flag counts[2] is an int64 that holds 0 or 1: its low word is the 32-bit flag f3d_group_pairs reads.
+hipError_t mesh_group(const mesh_layout& L, char* base, int64_t n, int bits, int64_t nkeys, const uint32_t* nkeys_dev, const int64_t* counts,
+                      int64_t* starts, hipStream_t s) {
+    return f3d_group_pairs(reinterpret_cast<uint32_t*>(base + L.keys_a), reinterpret_cast<uint32_t*>(base + L.keys_b),
+                           reinterpret_cast<uint32_t*>(base + L.vals_a), reinterpret_cast<uint32_t*>(base + L.vals_b), n, bits, base + L.temp,
+                           L.temp_bytes, nkeys, nkeys_dev, reinterpret_cast<const int32_t*>(counts + 2), starts, s);
 }
 
 // the compaction: flags from vmask / fkeep, their scan, the outputs (k_mesh_compact)
@@ -402,8 +354,8 @@ hipError_t mesh_compact(const mesh_layout& L, char* base, const void* verts, int
                         int64_t* counts, hipStream_t s) {
     uint32_t* flags = reinterpret_cast<uint32_t*>(base + L.flags);
     hipLaunchKernelGGL(k_mesh_flags, grid_of(nv + nt + 1), dim3(MB), 0, s, nv, nt, vmask, invert, fkeep, counts, flags);
-    MESH_TRY(hipGetLastError());
-    MESH_TRY(mesh_scan(L, base, (size_t)(nv + nt + 1), s));
+    F3D_TRY(hipGetLastError());
+    F3D_TRY(mesh_scan(L, base, (size_t)(nv + nt + 1), s));
     hipLaunchKernelGGL(k_mesh_compact, grid_of(nv + nt), dim3(MB), 0, s, tris, itype, nt, nv, flags, verts, vdtype, out_tris, old2new, out_verts,
                        counts);
     return hipGetLastError();
@@ -419,20 +371,19 @@ hipError_t mesh_clusters(const mesh_layout& L, char* base, const void* verts, in
     int32_t *parent = reinterpret_cast<int32_t*>(base + L.parent), *root = reinterpret_cast<int32_t*>(base + L.root);
     int64_t* starts = reinterpret_cast<int64_t*>(base + L.starts);
     const dim3 g(grid_of(nt + 1)), g3(grid_of(3 * nt)), b(MB);
-    const int vb_bits = bits_for(nv);
+    const int vb_bits = f3d_bits_for(nv, 1);
     hipLaunchKernelGGL(k_mesh_area, g, b, 0, s, verts, vdtype, tris, itype, nt, counts, tri_area);
     hipLaunchKernelGGL(k_mesh_edge_keys, g, b, 0, s, tris, itype, nt, active, vb_bits, counts, ka, va, parent);
-    MESH_TRY(hipGetLastError());
+    F3D_TRY(hipGetLastError());
     size_t tb = L.temp_bytes;
-    MESH_TRY(rocprim::radix_sort_pairs(base + L.temp, tb, ka, kb, va, vb, (size_t)(3 * nt), 0u, (unsigned)(2 * vb_bits + (active ? 1 : 0)), s));
+    F3D_TRY(rocprim::radix_sort_pairs(base + L.temp, tb, ka, kb, va, vb, (size_t)(3 * nt), 0u, (unsigned)(2 * vb_bits + (active ? 1 : 0)), s));
     hipLaunchKernelGGL(k_mesh_union, g3, b, 0, s, kb, vb, 3 * nt, vb_bits, counts, parent);
     hipLaunchKernelGGL(k_mesh_roots, g, b, 0, s, parent, nt, active, counts, root, flags);
-    MESH_TRY(hipGetLastError());
-    MESH_TRY(mesh_scan(L, base, (size_t)(nt + 1), s));
+    F3D_TRY(hipGetLastError());
+    F3D_TRY(mesh_scan(L, base, (size_t)(nt + 1), s));
     hipLaunchKernelGGL(k_mesh_labels, g, b, 0, s, root, flags, nt, active, clusters, reinterpret_cast<uint32_t*>(ka), va, counts);
-    MESH_TRY(hipGetLastError());
-    MESH_TRY(mesh_sort32(L, base, (size_t)nt, bits_for(nt + 1), s));
-    hipLaunchKernelGGL(k_mesh_lower_bound, g, b, 0, s, reinterpret_cast<const uint32_t*>(kb), nt, nt, flags + nt, counts, starts);
+    F3D_TRY(hipGetLastError());
+    F3D_TRY(mesh_group(L, base, nt, f3d_bits_for(nt + 1, 1), nt, flags + nt, counts, starts, s));
     double* partial = reinterpret_cast<double*>(base + L.partial);
     hipLaunchKernelGGL(k_mesh_chunk_sums, g, b, 0, s, tri_area, vb, reinterpret_cast<const uint32_t*>(kb), starts, flags + nt, nt, counts, partial);
     hipLaunchKernelGGL(k_mesh_cluster_sums, dim3(f3d_grid_for(nt, MB / 64, MGRID)), b, 0, s, partial, starts, flags + nt, counts, cluster_n,
@@ -447,17 +398,15 @@ size_t f3d_mesh_scratch_bytes(int64_t nv, int64_t nt) { return mesh_layout_for(n
 hipError_t f3d_launch_mesh_vertex_map(const void* tris, int itype, int64_t nt, int64_t nv, int64_t* offsets, int32_t* tri, int8_t* pos,
                                       void* scratch, int64_t* counts, int* err, hipStream_t s) {
     if (!mesh_sizes_ok(nv, nt)) return hipErrorInvalidValue;
-    MESH_TRY(mesh_begin(tris, itype, nt, nv, counts, err, s));
+    F3D_TRY(mesh_begin(tris, itype, nt, nv, counts, err, s));
     if (nt == 0) return hipMemsetAsync(offsets, 0, (size_t)(nv + 1) * 8, s);
     const mesh_layout L = mesh_layout_for(nv, nt);
     char* base = reinterpret_cast<char*>(scratch);
     const int64_t n3 = 3 * nt;
     hipLaunchKernelGGL(k_mesh_corner_keys, grid_of(n3), dim3(MB), 0, s, tris, itype, n3, counts, reinterpret_cast<uint32_t*>(base + L.keys_a),
                        reinterpret_cast<uint32_t*>(base + L.vals_a));
-    MESH_TRY(hipGetLastError());
-    MESH_TRY(mesh_sort32(L, base, (size_t)n3, bits_for(nv), s));
-    hipLaunchKernelGGL(k_mesh_lower_bound, grid_of(nv + 1), dim3(MB), 0, s, reinterpret_cast<const uint32_t*>(base + L.keys_b), n3, nv,
-                       (const uint32_t*)nullptr, counts, offsets);
+    F3D_TRY(hipGetLastError());
+    F3D_TRY(mesh_group(L, base, n3, f3d_bits_for(nv, 1), nv, nullptr, counts, offsets, s));
     hipLaunchKernelGGL(k_mesh_vmap_out, grid_of(n3), dim3(MB), 0, s, reinterpret_cast<const uint32_t*>(base + L.vals_b), n3, counts, tri, pos);
     return hipGetLastError();
 }
@@ -465,28 +414,28 @@ hipError_t f3d_launch_mesh_vertex_map(const void* tris, int itype, int64_t nt, i
 hipError_t f3d_launch_mesh_remove_faces(const void* tris, int itype, int64_t nt, int64_t nv, const uint8_t* mask, uint8_t* not_removed,
                                         void* remaining, int64_t* old2new, void* scratch, int64_t* counts, int* err, hipStream_t s) {
     if (!mesh_sizes_ok(nv, nt)) return hipErrorInvalidValue;
-    MESH_TRY(mesh_begin(tris, itype, nt, nv, counts, err, s));
+    F3D_TRY(mesh_begin(tris, itype, nt, nv, counts, err, s));
     const mesh_layout L = mesh_layout_for(nv, nt);
     char* base = reinterpret_cast<char*>(scratch);
     if (nt > 0) hipLaunchKernelGGL(k_mesh_face_touch, grid_of(nt), dim3(MB), 0, s, tris, itype, nt, mask, 1, counts, not_removed);
-    MESH_TRY(hipGetLastError());
+    F3D_TRY(hipGetLastError());
     return mesh_compact(L, base, nullptr, F3D_F64, nv, tris, itype, nt, mask, 1, not_removed, remaining, old2new, nullptr, counts, s);
 }
 
 hipError_t f3d_launch_mesh_keep_faces(const void* verts, int vdtype, int64_t nv, const void* tris, int itype, int64_t nt, const uint8_t* mask,
                                       void* out_verts, void* out_tris, void* scratch, int64_t* counts, int* err, hipStream_t s) {
     if (!mesh_sizes_ok(nv, nt)) return hipErrorInvalidValue;
-    MESH_TRY(mesh_begin(tris, itype, nt, nv, counts, err, s));
+    F3D_TRY(mesh_begin(tris, itype, nt, nv, counts, err, s));
     if (nt == 0) return hipSuccess;
     const mesh_layout L = mesh_layout_for(nv, nt);
     char* base = reinterpret_cast<char*>(scratch);
     uint32_t *first = reinterpret_cast<uint32_t*>(base + L.first), *flags = reinterpret_cast<uint32_t*>(base + L.flags);
     uint8_t* fkeep = reinterpret_cast<uint8_t*>(base + L.fkeep);
-    MESH_TRY(hipMemsetAsync(first, 0xff, (size_t)nv * 4, s));
+    F3D_TRY(hipMemsetAsync(first, 0xff, (size_t)nv * 4, s));
     hipLaunchKernelGGL(k_mesh_keep_first, grid_of(nt), dim3(MB), 0, s, tris, itype, nt, mask, counts, first, fkeep);
     hipLaunchKernelGGL(k_mesh_keep_flags, grid_of(4 * nt + 1), dim3(MB), 0, s, tris, itype, nt, first, fkeep, counts, flags);
-    MESH_TRY(hipGetLastError());
-    MESH_TRY(mesh_scan(L, base, (size_t)(4 * nt + 1), s));
+    F3D_TRY(hipGetLastError());
+    F3D_TRY(mesh_scan(L, base, (size_t)(4 * nt + 1), s));
     hipLaunchKernelGGL(k_mesh_keep_out, grid_of(4 * nt), dim3(MB), 0, s, verts, vdtype, tris, itype, nt, first, flags, out_verts, out_tris, counts);
     return hipGetLastError();
 }
@@ -495,7 +444,7 @@ hipError_t f3d_launch_mesh_clusters(const void* verts, int vdtype, int64_t nv, c
                                     int64_t* cluster_n, double* cluster_area, double* tri_area, void* scratch, int64_t* counts, int* err,
                                     hipStream_t s) {
     if (!mesh_sizes_ok(nv, nt)) return hipErrorInvalidValue;
-    MESH_TRY(mesh_begin(tris, itype, nt, nv, counts, err, s));
+    F3D_TRY(mesh_begin(tris, itype, nt, nv, counts, err, s));
     if (nt == 0) return hipSuccess;
     const mesh_layout L = mesh_layout_for(nv, nt);
     char* base = reinterpret_cast<char*>(scratch);
@@ -507,8 +456,8 @@ hipError_t f3d_launch_mesh_clean(const void* verts, int vdtype, int64_t nv, cons
                                  int64_t min_triangles, double min_area, void* new_verts, void* new_tris, uint8_t* kept_v, uint8_t* kept_t,
                                  void* scratch, int64_t* counts, int* err, hipStream_t s) {
     if (!mesh_sizes_ok(nv, nt)) return hipErrorInvalidValue;
-    MESH_TRY(mesh_begin(tris, itype, nt, nv, counts, err, s));
-    if (nv > 0) MESH_TRY(hipMemsetAsync(kept_v, 0, (size_t)nv, s));
+    F3D_TRY(mesh_begin(tris, itype, nt, nv, counts, err, s));
+    if (nv > 0) F3D_TRY(hipMemsetAsync(kept_v, 0, (size_t)nv, s));
     if (nt == 0) return hipSuccess;
     const mesh_layout L = mesh_layout_for(nv, nt);
     char* base = reinterpret_cast<char*>(scratch);
@@ -516,15 +465,15 @@ hipError_t f3d_launch_mesh_clean(const void* verts, int vdtype, int64_t nv, cons
     if (remove_mask) {
         active = reinterpret_cast<uint8_t*>(base + L.active);
         hipLaunchKernelGGL(k_mesh_face_touch, grid_of(nt), dim3(MB), 0, s, tris, itype, nt, remove_mask, 1, counts, active);
-        MESH_TRY(hipGetLastError());
+        F3D_TRY(hipGetLastError());
     }
     int32_t* clusters = reinterpret_cast<int32_t*>(base + L.clusters);
     int64_t* cluster_n = reinterpret_cast<int64_t*>(base + L.cluster_n);
     double* cluster_area = reinterpret_cast<double*>(base + L.cluster_area);
-    MESH_TRY(mesh_clusters(L, base, verts, vdtype, nv, tris, itype, nt, active, clusters, cluster_n, cluster_area,
+    F3D_TRY(mesh_clusters(L, base, verts, vdtype, nv, tris, itype, nt, active, clusters, cluster_n, cluster_area,
                            reinterpret_cast<double*>(base + L.tri_area), counts, s));
     hipLaunchKernelGGL(k_mesh_clean_keep, grid_of(nt), dim3(MB), 0, s, tris, itype, nt, clusters, cluster_n, cluster_area, min_triangles, min_area,
                        counts, kept_t, kept_v);
-    MESH_TRY(hipGetLastError());
+    F3D_TRY(hipGetLastError());
     return mesh_compact(L, base, verts, vdtype, nv, tris, itype, nt, kept_v, 0, kept_t, new_tris, nullptr, new_verts, counts, s);
 }

@@ -3,7 +3,7 @@
 // The reference fits a box on `points[ids == id]` for every instance (Open3D: convex hull -> PCA of the hull vertices).  At
 // C5 scale (50M points, 4096 instances) 90 % of merge_bb's time was host work: grouping the points by instance id (a 50M
 // argsort) and 4096 convex hulls of ~12k points each.  Here
-//   f3d_group_by_id*     : the grouping -- key = id, stable radix sort of (key, index): `order` lists every instance's
+//   f3d_group_by_id*     : the grouping -- key = id, f3d_group_pairs (f3d_groups.h) of (key, index): `order` lists every instance's
 //                          members in ascending point index, exactly the array `np.nonzero(ids == id)[0]`;
 //   f3d_obb_extremes*    : per instance the members that are extreme along 26 fixed directions (+-x, +-y, +-z, the face and
 //                          body diagonals);
@@ -13,10 +13,10 @@
 // Streaming, HBM-bound passes over the cloud; no MFMA (nothing here is a dense contraction).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
-#include <rocprim/device/device_radix_sort.hpp>
 #include "f3d.h"
 #include "f3d_math.h"
 #include "f3d_kernels.h"
+#include "f3d_groups.h"
 
 namespace {
 
@@ -29,18 +29,6 @@ __global__ __launch_bounds__(OB) void k_id_keys(const int64_t* __restrict__ ids,
         keys[i] = (v >= 0 && v < nids) ? (uint32_t)v : (uint32_t)nids;     // ids outside [0, nids) share one bucket behind the others
         idx[i] = (uint32_t)i;
     }
-}
-
-// starts[k] = first position of key k in the sorted keys (lower bound), k = 0 .. nids + 1; starts[nids + 1] = n
-__global__ __launch_bounds__(OB) void k_seg_starts(const uint32_t* __restrict__ keys, int64_t n, int64_t nids, int64_t* __restrict__ starts) {
-    const int64_t k = (int64_t)blockIdx.x * OB + threadIdx.x;
-    if (k > nids + 1) return;
-    int64_t lo = 0, hi = n;
-    while (lo < hi) {
-        const int64_t mid = (lo + hi) >> 1;
-        if ((int64_t)keys[mid] < k) lo = mid + 1; else hi = mid;
-    }
-    starts[k] = lo;
 }
 
 // orderable bits of a float (larger float <-> larger unsigned)
@@ -173,21 +161,13 @@ __global__ __launch_bounds__(OB) void k_mask_scan_local(const unsigned long long
                                                          uint32_t* __restrict__ blocksum) {
     __shared__ uint32_t part[OB];
     const int64_t w0 = (int64_t)blockIdx.x * SCAN_WORDS + (int64_t)threadIdx.x * 16;
-    uint32_t c[16], sum = 0;
+    uint32_t c[16], sum = 0, run, tot;
 #pragma unroll
     for (int k = 0; k < 16; ++k) { c[k] = (w0 + k < nwords) ? (uint32_t)__popcll(maskw[w0 + k]) : 0u; sum += c[k]; }
-    part[threadIdx.x] = sum;
-    __syncthreads();
-    for (int off = 1; off < OB; off <<= 1) {
-        const uint32_t v = threadIdx.x >= off ? part[threadIdx.x - off] : 0u;
-        __syncthreads();
-        part[threadIdx.x] += v;
-        __syncthreads();
-    }
-    uint32_t run = part[threadIdx.x] - sum;
+    f3d_block_scan<OB>(sum, part, run, tot);
 #pragma unroll
     for (int k = 0; k < 16; ++k) { if (w0 + k < nwords) wordoff[w0 + k] = run; run += c[k]; }
-    if (threadIdx.x == OB - 1) blocksum[blockIdx.x] = part[OB - 1];
+    if (threadIdx.x == OB - 1) blocksum[blockIdx.x] = tot;
 }
 
 // one block: blocksum -> exclusive prefix in place; total[0] = the number of survivors
@@ -195,19 +175,11 @@ __global__ __launch_bounds__(OB) void k_mask_scan_blocks(uint32_t* __restrict__ 
     __shared__ uint32_t part[OB];
     const int per = (nblocks + OB - 1) / OB;
     const int lo = threadIdx.x * per, hi = min(nblocks, lo + per);
-    uint32_t sum = 0;
+    uint32_t sum = 0, run, tot;
     for (int k = lo; k < hi; ++k) sum += blocksum[k];
-    part[threadIdx.x] = sum;
-    __syncthreads();
-    for (int off = 1; off < OB; off <<= 1) {
-        const uint32_t v = threadIdx.x >= off ? part[threadIdx.x - off] : 0u;
-        __syncthreads();
-        part[threadIdx.x] += v;
-        __syncthreads();
-    }
-    uint32_t run = part[threadIdx.x] - sum;
+    f3d_block_scan<OB>(sum, part, run, tot);
     for (int k = lo; k < hi; ++k) { const uint32_t c = blocksum[k]; blocksum[k] = run; run += c; }
-    if (threadIdx.x == OB - 1) *total = (int64_t)part[OB - 1];
+    if (threadIdx.x == OB - 1) *total = (int64_t)tot;
 }
 
 __device__ __forceinline__ int64_t survivors_before(int64_t pos, int64_t n, const unsigned long long* __restrict__ maskw, const uint32_t* __restrict__ wordoff,
@@ -248,45 +220,30 @@ group_layout group_layout_for(int64_t n, unsigned bits) {
     f3d_carve c;
     L.keys_in = c.take((size_t)n * 4);
     L.idx_in = c.take((size_t)n * 4);
-    size_t tb = 0;
-    (void)rocprim::radix_sort_pairs(nullptr, tb, (uint32_t*)nullptr, (uint32_t*)nullptr, (uint32_t*)nullptr, (uint32_t*)nullptr, (size_t)n, 0u, bits,
-                                    (hipStream_t)0);
-    L.temp_bytes = tb;
-    L.temp = c.take(tb);
+    L.temp_bytes = f3d_group_temp_bytes(n, bits);
+    L.temp = c.take(L.temp_bytes);
     L.total = c.off;
     return L;
 }
 
-unsigned key_bits(int64_t nids) {
-    unsigned b = 1;
-    while (((int64_t)1 << b) <= nids) ++b;                               // keys 0 .. nids
-    return b;
-}
-
 }  // namespace
 
-size_t f3d_group_scratch_bytes(int64_t n, int64_t nids) { return group_layout_for(n < 1 ? 1 : n, key_bits(nids)).total; }
+size_t f3d_group_scratch_bytes(int64_t n, int64_t nids) { return group_layout_for(n < 1 ? 1 : n, (unsigned)f3d_bits_for(nids + 1, 1)).total; }
 
 hipError_t f3d_launch_group_by_id(const int64_t* ids, int64_t n, int64_t nids, int32_t* order, uint32_t* sorted_keys, int64_t* starts,
                                   void* scratch, hipStream_t s) {
-    if (n <= 0) {
-        hipLaunchKernelGGL(k_seg_starts, dim3(f3d_grid_for(nids + 2, OB, 65536)), dim3(OB), 0, s, sorted_keys, (int64_t)0, nids, starts);
-        return hipGetLastError();
-    }
+    // starts[k], k = 0 .. nids + 1: starts[nids] = first position of the out-of-range bucket, starts[nids + 1] = n
+    if (n <= 0) return f3d_launch_key_starts(sorted_keys, 0, nids + 1, nullptr, nullptr, starts, s);
     if (n > 0x7fffffffLL || nids < 0 || nids >= 0x7fffffffLL) return hipErrorInvalidValue;
-    const unsigned bits = key_bits(nids);
+    const unsigned bits = (unsigned)f3d_bits_for(nids + 1, 1);           // keys 0 .. nids
     const group_layout L = group_layout_for(n, bits);
     char* base = reinterpret_cast<char*>(scratch);
     uint32_t* keys_in = reinterpret_cast<uint32_t*>(base + L.keys_in);
     uint32_t* idx_in = reinterpret_cast<uint32_t*>(base + L.idx_in);
     hipLaunchKernelGGL(k_id_keys, dim3(f3d_grid_for(n, OB, 8192)), dim3(OB), 0, s, ids, n, nids, keys_in, idx_in);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return e;
-    size_t tb = L.temp_bytes;
-    e = rocprim::radix_sort_pairs(base + L.temp, tb, keys_in, sorted_keys, idx_in, reinterpret_cast<uint32_t*>(order), (size_t)n, 0u, bits, s);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(k_seg_starts, dim3(f3d_grid_for(nids + 2, OB, 65536)), dim3(OB), 0, s, sorted_keys, n, nids, starts);
-    return hipGetLastError();
+    F3D_TRY(hipGetLastError());
+    return f3d_group_pairs(keys_in, sorted_keys, idx_in, reinterpret_cast<uint32_t*>(order), n, (int)bits, base + L.temp, L.temp_bytes, nids + 1,
+                           nullptr, nullptr, starts, s);
 }
 
 hipError_t f3d_launch_obb_extremes(const void* xyz, int dtype, int64_t n, const int32_t* order, const uint32_t* sorted_keys, int64_t nseg,

@@ -6,9 +6,9 @@
 //                  moments added in row order by one thread, jacobi3);
 //   k_pl_union   : the smooth edges between core points, joined with f3d_uf_link (a root is its component's lowest index);
 //   k_pl_roots / k_pl_flags / scan / k_pl_labels : components of at least min_points members, numbered by ascending root;
-//   group        : a stable radix sort of (plane, point) pairs and a lower bound -> the members of every plane in ascending index;
-//   k_pl_chunk_sums / k_pl_fit : per plane the centroid, then the centred second moments, as fixed-shape sums (chunks of 4096 members,
-//                  lane-strided wave sums, xor butterfly: the scheme of f3d_mesh.hip), jacobi3 -> normal, in-plane axes;
+//   k_pl_group_keys + f3d_group_pairs : the members of every plane in ascending index;
+//   k_pl_chunk_sums / k_pl_fit : per plane the centroid, then the centred second moments, as the fixed-shape sums of f3d_groups.h
+//                  (chunks of 4096 members, lane-strided wave sums, xor butterfly), jacobi3 -> normal, in-plane axes;
 //   k_pl_inliers : members farther than dist from their plane become -1 (the plane is not refitted);
 //   k_pl_attach / k_pl_round_end : synchronous rounds over two label buffers; the changed flag stays on the device and the host reads
 //                  {done, rounds} back every ATTACH_CHUNK rounds;
@@ -19,10 +19,10 @@
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
-#include <rocprim/device/device_radix_sort.hpp>
 #include <rocprim/device/device_scan.hpp>
 #include "f3d.h"
 #include "f3d_kernels.h"
+#include "f3d_groups.h"
 #include "f3d_math.h"
 #include "f3d_eigen.h"
 
@@ -38,21 +38,11 @@ constexpr int WAVE_GROUPS = 8;             // distinct roots / planes of a wave 
 constexpr int ATTACH_CHUNK = 4;            // attach rounds enqueued between two readbacks of {done, rounds}
 
 #define PL_LOOP(i, n) for (int64_t i = (int64_t)blockIdx.x * PB + threadIdx.x; i < (n); i += (int64_t)gridDim.x * PB)
-#define PL_TRY(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) return e_; } while (0)
 
 struct pl_words { int32_t bad, done, rounds, changed; };
 
 __device__ __forceinline__ f3d_p3 ldp(const void* __restrict__ xyz, int dtype, int64_t i) {
     return dtype == F3D_F64 ? f3d_load_p3(reinterpret_cast<const double*>(xyz), i) : f3d_load_p3(reinterpret_cast<const float*>(xyz), i);
-}
-
-// doubles -> unsigned integers of the same order (min / max by integer atomics; exact in any order)
-__device__ __forceinline__ unsigned long long ord_enc(double x) {
-    const unsigned long long b = (unsigned long long)__double_as_longlong(x);
-    return (b >> 63) ? ~b : (b | 0x8000000000000000ull);
-}
-__device__ __forceinline__ double ord_dec(unsigned long long u) {
-    return __longlong_as_double((long long)((u >> 63) ? (u & 0x7fffffffffffffffull) : ~u));
 }
 
 // planes written: the qualifying components (scan[n]) cut at max_planes
@@ -177,10 +167,7 @@ __global__ __launch_bounds__(PB) void k_pl_roots(const int32_t* parent, int64_t 
         const int64_t i = w0 + lane;
         int32_t x = -1;
         if (i < n) {
-            if (core[i]) {
-                x = (int32_t)i;
-                for (;;) { const int32_t p = f3d_uf_load(parent + x); if (p == x) break; x = p; }
-            }
+            if (core[i]) x = f3d_uf_root(parent, (int32_t)i);
             root[i] = x;
         }
         // the lanes of the wave that share a root count themselves with one atomic (a room has a few large planes)
@@ -230,30 +217,6 @@ __global__ __launch_bounds__(PB) void k_pl_group_keys(const int32_t* __restrict_
     }
 }
 
-// starts[k] = first position of key k in the sorted keys, k = 0 .. P
-__global__ __launch_bounds__(PB) void k_pl_lower_bound(const uint32_t* __restrict__ keys, int64_t n, const uint32_t* __restrict__ scan,
-                                                       int64_t max_planes, const pl_words* w, int64_t* __restrict__ starts) {
-    if (w->bad) return;
-    const int64_t P = planes_written(scan, n, max_planes);
-    PL_LOOP(k, P + 1) {
-        int64_t lo = 0, hi = n;
-        while (lo < hi) {
-            const int64_t mid = (lo + hi) >> 1;
-            if ((int64_t)keys[mid] < k) lo = mid + 1; else hi = mid;
-        }
-        starts[k] = lo;
-    }
-}
-
-// wave_sum: lane l adds the items l, l + 64, l + 128, ... of [0, count) left to right, then the 64 lane sums meet in an xor butterfly
-template <typename At>
-__device__ __forceinline__ double wave_sum(int64_t count, int lane, At at) {
-    double acc = 0.0;
-    for (int64_t i = lane; i < count; i += 64) acc = acc + at(i);
-    for (int off = 32; off > 0; off >>= 1) acc = acc + __shfl_xor(acc, off);
-    return acc;
-}
-
 // what a member adds to its plane's sums
 //   SUM_MEAN: x, y, z;  SUM_MOMENTS: the 6 products of (p - c);  SUM_RESIDUAL: ((p - c) . n)^2
 enum { SUM_MEAN = 0, SUM_MOMENTS = 1, SUM_RESIDUAL = 2 };
@@ -270,40 +233,25 @@ __device__ __forceinline__ double sum_term(int mode, int k, const f3d_p3& p, con
 #define PL_FRAME 12
 
 // The chunk of SUM_CHUNK consecutive members of plane c that starts at grouped position q owns slot (q >> SUM_SHIFT) + c of `partial`
-// (6 doubles each): slots grow with the chunk inside a plane and from a plane to the next, so no two chunks share one.  A wave looks at
-// 64 positions, finds the chunk starts among them and sums each, term by term.
+// (6 doubles each): slots grow with the chunk inside a plane and from a plane to the next, so no two chunks share one.  Every chunk is
+// summed term by term.
 __global__ __launch_bounds__(PB) void k_pl_chunk_sums(const void* __restrict__ xyz, int dtype, int64_t n, int mode,
                                                       const uint32_t* __restrict__ order, const uint32_t* __restrict__ skeys,
                                                       const int64_t* __restrict__ starts, const uint32_t* __restrict__ scan, int64_t max_planes,
                                                       const double* __restrict__ frames, const pl_words* w, double* __restrict__ partial) {
     if (w->bad) return;
-    const int64_t P = planes_written(scan, n, max_planes);
     const int lane = threadIdx.x & 63;
     const int nterms = sum_terms(mode);
-    for (int64_t w0 = (int64_t)blockIdx.x * PB + threadIdx.x - lane; w0 < n; w0 += (int64_t)gridDim.x * PB) {
-        const int64_t p = w0 + lane;
-        bool head = false;
-        long long e = 0, c = 0;
-        if (p < n) {
-            c = (long long)skeys[p];
-            if (c < P) { e = starts[c + 1]; head = ((p - starts[c]) % SUM_CHUNK) == 0; }
+    f3d_chunk_heads<SUM_CHUNK, PB>(skeys, starts, n, planes_written(scan, n, max_planes), [&](int64_t q, int64_t len, int64_t c) {
+        const double* fr = frames + PL_FRAME * c;
+        for (int k = 0; k < nterms; ++k) {
+            const double sum = f3d_wave_sum(len, lane, [&](int64_t i) { return sum_term(mode, k, ldp(xyz, dtype, (int64_t)order[q + i]), fr); });
+            if (lane == 0) partial[6 * ((q >> SUM_SHIFT) + c) + k] = sum;
         }
-        unsigned long long todo = __ballot(head);
-        while (todo) {
-            const int src = __ffsll((long long)todo) - 1;
-            todo &= todo - 1;
-            const int64_t q = w0 + src, ce = (int64_t)__shfl(e, src), cc = (int64_t)__shfl(c, src);
-            const int64_t len = ce - q < SUM_CHUNK ? ce - q : SUM_CHUNK;
-            const double* fr = frames + PL_FRAME * cc;
-            for (int k = 0; k < nterms; ++k) {
-                const double sum = wave_sum(len, lane, [&](int64_t i) { return sum_term(mode, k, ldp(xyz, dtype, (int64_t)order[q + i]), fr); });
-                if (lane == 0) partial[6 * ((q >> SUM_SHIFT) + cc) + k] = sum;
-            }
-        }
-    }
+    });
 }
 
-// one wave per plane: wave_sum of the plane's chunk sums, term by term, then
+// one wave per plane: the sum of the plane's chunk sums, term by term, then
 //   SUM_MEAN    : frames[c].centroid = sums / members
 //   SUM_MOMENTS : jacobi3 of the moment sums -> normal (smallest eigenvalue), u (largest), v = normal x u, with their signs
 //   SUM_RESIDUAL: rms[c] = sqrt(sum / members) (NaN for a plane without members)
@@ -312,16 +260,13 @@ __global__ __launch_bounds__(PB) void k_pl_fit(int64_t n, int mode, const int64_
                                                int have_normals, const uint32_t* __restrict__ order, const pl_words* w,
                                                double* __restrict__ frames, double* __restrict__ rms) {
     if (w->bad) return;
-    const int64_t P = planes_written(scan, n, max_planes);
     const int lane = threadIdx.x & 63;
     const int nterms = sum_terms(mode);
-    for (int64_t c = ((int64_t)blockIdx.x * PB + threadIdx.x) >> 6; c < P; c += ((int64_t)gridDim.x * PB) >> 6) {
-        const int64_t b = starts[c], e = starts[c + 1];
-        const int64_t nchunks = (e - b + SUM_CHUNK - 1) / SUM_CHUNK;
+    f3d_group_waves<PB>(starts, planes_written(scan, n, max_planes), [&](int64_t c, int64_t b, int64_t e) {
         double s[6] = {0, 0, 0, 0, 0, 0};
         for (int k = 0; k < nterms; ++k)
-            s[k] = wave_sum(nchunks, lane, [&](int64_t j) { return partial[6 * (((b + j * SUM_CHUNK) >> SUM_SHIFT) + c) + k]; });
-        if (lane != 0) continue;
+            s[k] = f3d_chunks_sum<SUM_CHUNK>(b, e, lane, [&](int64_t q) { return partial[6 * ((q >> SUM_SHIFT) + c) + k]; });
+        if (lane != 0) return;
         double* fr = frames + PL_FRAME * c;
         const double m = (double)(e - b);
         if (mode == SUM_MEAN) {
@@ -345,7 +290,7 @@ __global__ __launch_bounds__(PB) void k_pl_fit(int64_t n, int mode, const int64_
             fr[6] = u[0]; fr[7] = u[1]; fr[8] = u[2];
             fr[9] = nv[1] * u[2] - nv[2] * u[1]; fr[10] = nv[2] * u[0] - nv[0] * u[2]; fr[11] = nv[0] * u[1] - nv[1] * u[0];
         }
-    }
+    });
 }
 
 // |(p - c) . n| of point p to the plane with frame fr
@@ -412,8 +357,8 @@ __global__ __launch_bounds__(PB) void k_pl_extents(const void* __restrict__ xyz,
             const double* fr = frames + PL_FRAME * (int64_t)l;
             const f3d_p3 p = ldp(xyz, dtype, i);
             const double dx = p.x - fr[0], dy = p.y - fr[1], dz = p.z - fr[2];
-            a = ord_enc(f3d_dot3(dx, dy, dz, fr[6], fr[7], fr[8]));
-            b = ord_enc(f3d_dot3(dx, dy, dz, fr[9], fr[10], fr[11]));
+            a = f3d_ord_enc(f3d_dot3(dx, dy, dz, fr[6], fr[7], fr[8]));
+            b = f3d_ord_enc(f3d_dot3(dx, dy, dz, fr[9], fr[10], fr[11]));
         }
         // the lanes of the wave that share a plane meet in a butterfly first: integer minima and maxima, the same bits in any order
         unsigned long long todo = __ballot(l >= 0);
@@ -468,8 +413,8 @@ __global__ __launch_bounds__(PB) void k_pl_finish(int64_t n, const uint32_t* __r
         pr[7] = rms[c];
         const bool any = starts[c + 1] > starts[c];
         const double nan = __longlong_as_double(0x7ff8000000000000ll);
-        const double a0 = any ? ord_dec(ext[4 * c]) : nan, a1 = any ? ord_dec(ext[4 * c + 1]) : nan;
-        const double b0 = any ? ord_dec(ext[4 * c + 2]) : nan, b1 = any ? ord_dec(ext[4 * c + 3]) : nan;
+        const double a0 = any ? f3d_ord_dec(ext[4 * c]) : nan, a1 = any ? f3d_ord_dec(ext[4 * c + 1]) : nan;
+        const double b0 = any ? f3d_ord_dec(ext[4 * c + 2]) : nan, b1 = any ? f3d_ord_dec(ext[4 * c + 3]) : nan;
         const double ca[4] = {a0, a1, a1, a0}, cb[4] = {b0, b0, b1, b1};
         for (int q = 0; q < 4; ++q)
             for (int k = 0; k < 3; ++k) cr[3 * q + k] = (fr[k] + ca[q] * fr[6 + k]) + cb[q] * fr[9 + k];
@@ -478,8 +423,6 @@ __global__ __launch_bounds__(PB) void k_pl_finish(int64_t n, const uint32_t* __r
         counts[0] = P; counts[1] = (int64_t)scan[n]; counts[2] = (int64_t)w->rounds; counts[3] = starts[P];
     }
 }
-
-int bits_for(int64_t v) { int b = 1; while (((int64_t)1 << b) < v) ++b; return b; }     // smallest b >= 1 with 2^b >= v
 
 struct planes_layout {
     size_t words, core, nrm, parent, root, cnt, flags, labels_b, keys_a, keys_b, vals_a, vals_b, starts, partial, frames, rms, ext, temp, total;
@@ -490,8 +433,7 @@ planes_layout planes_layout_for(int64_t n) {
     if (n < 1) n = 1;
     const size_t np = (size_t)(n / 3 + 1);                 // min_points >= 3: at most n / 3 planes
     planes_layout L;
-    size_t a = 0, b = 0;
-    (void)rocprim::radix_sort_pairs(nullptr, a, (uint32_t*)nullptr, (uint32_t*)nullptr, (uint32_t*)nullptr, (uint32_t*)nullptr, (size_t)n, 0u, 32u);
+    size_t a = f3d_group_temp_bytes(n), b = 0;
     (void)rocprim::exclusive_scan(nullptr, b, (uint32_t*)nullptr, (uint32_t*)nullptr, (uint32_t)0, (size_t)n + 1, rocprim::plus<uint32_t>());
     L.temp_bytes = (a > b ? a : b) + 256;
     f3d_carve k;
@@ -536,38 +478,35 @@ hipError_t f3d_launch_extract_planes(const void* xyz, int dtype, int64_t n, cons
     unsigned long long* ext = reinterpret_cast<unsigned long long*>(base + L.ext);
     const dim3 g(grid_of(n + 1)), b(PB), gw(f3d_grid_for(n / 3 + 1, PB / 64, PGRID));
     const int64_t mp = a.max_planes;
-    const int key_bits = bits_for(n / 3 + 2);
+    const int key_bits = f3d_bits_for(n / 3 + 2, 1);
 
-    PL_TRY(hipMemsetAsync(w, 0, sizeof(pl_words), s));
+    F3D_TRY(hipMemsetAsync(w, 0, sizeof(pl_words), s));
     hipLaunchKernelGGL(k_pl_check, g, b, 0, s, n, offs, nbrs, w, err);
     hipLaunchKernelGGL(k_pl_core, g, b, 0, s, xyz, dtype, n, offs, nbrs, normals, a.max_variation, w, core, nrm_w, parent, cnt);
     hipLaunchKernelGGL(k_pl_union, g, b, 0, s, xyz, dtype, n, offs, nbrs, core, nrm, a.cos_angle, a.offset, w, parent);
     hipLaunchKernelGGL(k_pl_roots, g, b, 0, s, parent, n, core, w, root, cnt);
     hipLaunchKernelGGL(k_pl_flags, g, b, 0, s, root, cnt, n, a.min_points, w, flags);
-    PL_TRY(hipGetLastError());
+    F3D_TRY(hipGetLastError());
     size_t tb = L.temp_bytes;
-    PL_TRY(rocprim::exclusive_scan(base + L.temp, tb, flags, flags, (uint32_t)0, (size_t)n + 1, rocprim::plus<uint32_t>(), s));
+    F3D_TRY(rocprim::exclusive_scan(base + L.temp, tb, flags, flags, (uint32_t)0, (size_t)n + 1, rocprim::plus<uint32_t>(), s));
     hipLaunchKernelGGL(k_pl_labels, g, b, 0, s, root, flags, n, mp, w, labels);
 
     // the members of every plane in ascending index, then centroid and moments
     auto group = [&](const int32_t* lab) -> hipError_t {
         hipLaunchKernelGGL(k_pl_group_keys, g, b, 0, s, lab, n, flags, mp, w, ka, va);
-        PL_TRY(hipGetLastError());
-        size_t t = L.temp_bytes;
-        PL_TRY(rocprim::radix_sort_pairs(base + L.temp, t, ka, kb, va, vb, (size_t)n, 0u, (unsigned)key_bits, s));
-        hipLaunchKernelGGL(k_pl_lower_bound, g, b, 0, s, kb, n, flags, mp, w, starts);
-        return hipGetLastError();
+        F3D_TRY(hipGetLastError());
+        return f3d_group_pairs(ka, kb, va, vb, n, key_bits, base + L.temp, L.temp_bytes, mp, flags + n, &w->bad, starts, s);
     };
     auto sums = [&](int mode) -> hipError_t {
         hipLaunchKernelGGL(k_pl_chunk_sums, g, b, 0, s, xyz, dtype, n, mode, vb, kb, starts, flags, mp, frames, w, partial);
         hipLaunchKernelGGL(k_pl_fit, gw, b, 0, s, n, mode, starts, flags, mp, partial, nrm, normals ? 1 : 0, vb, w, frames, rms);
         return hipGetLastError();
     };
-    PL_TRY(group(labels));
-    PL_TRY(sums(SUM_MEAN));
-    PL_TRY(sums(SUM_MOMENTS));
+    F3D_TRY(group(labels));
+    F3D_TRY(sums(SUM_MEAN));
+    F3D_TRY(sums(SUM_MOMENTS));
     hipLaunchKernelGGL(k_pl_inliers, g, b, 0, s, xyz, dtype, n, frames, a.dist, w, labels);
-    PL_TRY(hipGetLastError());
+    F3D_TRY(hipGetLastError());
 
     // attach: round t reads buf[t & 1] and writes buf[~t & 1]
     int32_t* buf[2] = {labels, labels_b};
@@ -577,17 +516,17 @@ hipError_t f3d_launch_extract_planes(const void* xyz, int dtype, int64_t n, cons
             hipLaunchKernelGGL(k_pl_attach, g, b, 0, s, xyz, dtype, n, offs, nbrs, frames, a.dist, buf[t & 1], buf[(t & 1) ^ 1], w);
             hipLaunchKernelGGL(k_pl_round_end, dim3(1), dim3(1), 0, s, w);
         }
-        PL_TRY(hipGetLastError());
-        PL_TRY(hipMemcpyAsync(&hw, w, sizeof(hw), hipMemcpyDeviceToHost, s));
-        PL_TRY(hipStreamSynchronize(s));
+        F3D_TRY(hipGetLastError());
+        F3D_TRY(hipMemcpyAsync(&hw, w, sizeof(hw), hipMemcpyDeviceToHost, s));
+        F3D_TRY(hipStreamSynchronize(s));
         if (hw.bad || hw.done) break;
     }
     const int32_t* fin = buf[hw.rounds & 1];
     if (fin != labels) hipLaunchKernelGGL(k_pl_copy_labels, g, b, 0, s, fin, n, w, labels);
 
     // final members: residuals, extents, the rows
-    PL_TRY(group(labels));
-    PL_TRY(sums(SUM_RESIDUAL));
+    F3D_TRY(group(labels));
+    F3D_TRY(sums(SUM_RESIDUAL));
     hipLaunchKernelGGL(k_pl_ext_init, g, b, 0, s, n, flags, mp, w, ext);
     hipLaunchKernelGGL(k_pl_extents, g, b, 0, s, xyz, dtype, n, labels, frames, w, ext);
     hipLaunchKernelGGL(k_pl_finish, grid_of(mp > 0 ? mp : 1), b, 0, s, n, flags, mp, frames, rms, ext, starts, w, planes, corners, counts);

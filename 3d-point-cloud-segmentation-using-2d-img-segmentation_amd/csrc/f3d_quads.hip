@@ -65,15 +65,6 @@ __device__ __forceinline__ bool inside_of(double px, double py, double pz, const
     return (u >= 0.0) & (v >= 0.0) & (u + v <= 1.0);
 }
 
-// doubles -> unsigned integers of the same order (min / max by integer atomics; exact in any order)
-__device__ __forceinline__ unsigned long long ord_enc(double x) {
-    const unsigned long long b = (unsigned long long)__double_as_longlong(x);
-    return (b >> 63) ? ~b : (b | 0x8000000000000000ull);
-}
-__device__ __forceinline__ double ord_dec(unsigned long long u) {
-    return __longlong_as_double((long long)((u >> 63) ? (u & 0x7fffffffffffffffull) : ~u));
-}
-
 __device__ __forceinline__ void load_pt(const double* __restrict__ pts, int64_t i, double& x, double& y, double& z) {
     x = pts[3 * i]; y = pts[3 * i + 1]; z = pts[3 * i + 2];
 }
@@ -305,8 +296,8 @@ __global__ __launch_bounds__(QB) void k_quad_extents(const double* __restrict__ 
             const double d2 = (pz - r.n[2] * perp) - o.origin[2];
             const double x = (d0 * o.i[0] + d2 * o.i[2]) + d1 * o.i[1];
             const double y = (d0 * o.j[0] + d2 * o.j[2]) + d1 * o.j[1];
-            xn = xx = ord_enc(x);
-            yn = yx = ord_enc(y);
+            xn = xx = f3d_ord_enc(x);
+            yn = yx = f3d_ord_enc(y);
         }
         const int s0 = __shfl(s, 0);
         if (__ballot(s != s0) == 0) {
@@ -333,8 +324,8 @@ __global__ __launch_bounds__(QB) void k_quad_build(const inst_rec* __restrict__ 
     status[s] = o.status;
     tri[s] = o.tri;
     const bool ok = o.status == F3D_QUAD_OK;
-    const double xmin = ord_dec(ext[4 * s]), xmax = ord_dec(ext[4 * s + 1]);
-    const double ymin = ord_dec(ext[4 * s + 2]), ymax = ord_dec(ext[4 * s + 3]);
+    const double xmin = f3d_ord_dec(ext[4 * s]), xmax = f3d_ord_dec(ext[4 * s + 1]);
+    const double ymin = f3d_ord_dec(ext[4 * s + 2]), ymax = f3d_ord_dec(ext[4 * s + 3]);
     const double cx[4] = {xmin, xmin, xmax, xmax}, cy[4] = {ymax, ymin, ymin, ymax};
     for (int q = 0; q < 4; ++q)
         for (int c = 0; c < 3; ++c)

@@ -124,28 +124,27 @@ __global__ __launch_bounds__(IB) void k_plane_distance(const double* __restrict_
     }
 }
 
+struct grow_layout { size_t inq, best, qa, qb, xq, total; };
+
+grow_layout grow_layout_for(int64_t n) {
+    const size_t n4 = (size_t)(n < 1 ? 1 : n) * 4;
+    f3d_carve c;                                                         // (a braced list is evaluated left to right)
+    return {c.take(n4), c.take(n4 * 2), c.take(n4), c.take(n4), c.take(n4), c.off};
+}
+
 }  // namespace
 
-size_t f3d_grow_scratch_bytes(int64_t n) {
-    f3d_carve c;
-    const size_t n4 = (size_t)(n < 1 ? 1 : n) * 4;
-    c.take(n4); c.take(n4 * 2); c.take(n4); c.take(n4); c.take(n4);
-    return c.off;
-}
+size_t f3d_grow_scratch_bytes(int64_t n) { return grow_layout_for(n).total; }
 
 hipError_t f3d_launch_region_grow(const void* values, int dtype, int nchan, int64_t n, const int64_t* offs, const int32_t* nbrs,
                                   const int64_t* seeds, int64_t nseeds, const f3d_grow_args& a, void* scratch, int64_t* cluster,
                                   int64_t* count_dev, int* err, hipStream_t s) {
     if (n <= 0 || n > F3D_GROW_MAX_POINTS || nseeds < 0 || nseeds > n || !(nchan == 3 || (nchan == 1 && dtype == F3D_F64)))
         return hipErrorInvalidValue;
-    f3d_carve c;
+    const grow_layout L = grow_layout_for(n);
     char* base = (char*)scratch;
-    const size_t n4 = (size_t)n * 4;
-    int32_t* inq = (int32_t*)(base + c.take(n4));
-    unsigned long long* best = (unsigned long long*)(base + c.take(n4 * 2));
-    int32_t* qa = (int32_t*)(base + c.take(n4));
-    int32_t* qb = (int32_t*)(base + c.take(n4));
-    int32_t* xq = (int32_t*)(base + c.take(n4));
+    int32_t *inq = (int32_t*)(base + L.inq), *qa = (int32_t*)(base + L.qa), *qb = (int32_t*)(base + L.qb), *xq = (int32_t*)(base + L.xq);
+    unsigned long long* best = (unsigned long long*)(base + L.best);
     hipLaunchKernelGGL(k_grow_init, dim3(f3d_grid_for(n, IB, 16384)), dim3(IB), 0, s, n, inq, best, count_dev);
     if (nseeds == 0) return hipGetLastError();
 #define F3D_GROW(T, C)                                                                                                                   \

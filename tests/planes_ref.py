@@ -271,6 +271,18 @@ def noisy(pts, nrm, rng, sigma_p=0.001, sigma_n=0.02, shuffle=True):
     return np.ascontiguousarray(pts[perm]), np.ascontiguousarray(nrm[perm]), perm
 
 
+# sheets whose single plane has a member count at the edge of a chunk of the plane sums (4096 members); the noise seed is one under
+# which `extract` reports a margin >= 1e-6 (tests/test_planes_cpu.py asserts it)
+EDGE_SHEETS = {'sheet4095': (5, 819, 4095), 'sheet4096': (64, 64, 4096), 'sheet4097': (17, 241, 4097)}
+
+
+def edge_sheet(name):
+    """-> (points, normals) of the named sheet of EDGE_SHEETS: nx x ny points 2 cm apart in z = 0, noisy and shuffled."""
+    nx, ny, seed = EDGE_SHEETS[name]
+    pts, nrm, _ = noisy(*sheet(nx, ny, 0.02, (0, 0, 0), (1, 0, 0), (0, 1, 0)), np.random.default_rng(seed))
+    return pts, nrm
+
+
 def room_corner(rng):
     """Three orthogonal 0.6 m faces that meet in a corner (floor z = 0, walls x = 0 and y = 0) and a slab 3 cm above the floor's level
     behind the x = 0 wall, 2 cm spacing: 4 x 900 points -> (points, normals, face id: floor 0, wall x 1, wall y 2, slab 3).  Floor and

@@ -8,6 +8,7 @@ import pytest
 
 import f3d
 import mesh_ref as R
+from planes_ref import shaped_sum
 
 pytestmark = pytest.mark.gpu
 
@@ -74,6 +75,14 @@ def _mesh(name):
     if name == 'strip':                                   # one cluster, a union chain across every block
         verts, tris = R.strip_mesh(70000, rng)
         return verts, tris, rng.random(len(verts)) < 0.001
+    if name.startswith('strip'):                          # one cluster of exactly M triangles: the chunks of its area sum end at M
+        verts, tris = R.strip_mesh(int(name[5:]), rng)
+        return verts, tris, rng.random(len(verts)) < 0.001
+    if name == 'two_strips':                              # clusters of 4096 and 4097 that share no vertex: the second one's first
+        va, ta = R.strip_mesh(4096, rng)                  # chunk starts right behind the first one's only, full chunk
+        vb, tb = R.strip_mesh(4097, rng)
+        verts = np.concatenate([va, vb + (0.0, 5.0, 0.0)])
+        return verts, np.concatenate([ta, tb + len(va)]), rng.random(len(verts)) < 0.001
     verts = rng.uniform(-1, 1, (12, 3))
     if name == 'fans':                                    # two fans that meet at vertex 0 only
         return verts, np.array(R.fan(0, [1, 2, 3, 4]) + R.fan(0, [5, 6, 7]), np.int64), np.arange(12) == 6
@@ -113,7 +122,8 @@ def _run_all(verts, tris, mask):
             mu.keep_faces_by_vertices(verts, tris, mask), mu.get_triangle_clusters((verts, tris), True))
 
 
-NAMES = ['m1', 'm2', 'm255', 'm256', 'm257', 'm1025', 'grid', 'grid32', 'strip', 'fans', 'edge3', 'dups']
+CHUNK_EDGES = ['strip4095', 'strip4096', 'strip4097', 'strip8193', 'two_strips']        # around the 4096 members of a chunk
+NAMES = ['m1', 'm2', 'm255', 'm256', 'm257', 'm1025', 'grid', 'grid32', 'strip', 'fans', 'edge3', 'dups'] + CHUNK_EDGES
 
 
 @pytest.mark.parametrize('name', NAMES)
@@ -132,6 +142,22 @@ def test_matches_restatement_and_repeats(name):
     for a, b in zip(first, second):
         for x, y in zip(a, b):
             assert x.tobytes() == y.tobytes()
+
+
+@pytest.mark.parametrize('on_device', [False, True], ids=['host', 'device'])
+@pytest.mark.parametrize('name', CHUNK_EDGES)
+def test_cluster_sums_at_chunk_edges(name, on_device):
+    """Clusters, sizes and triangle areas equal the restatement's bit for bit.  The restatement's cluster area is an fsum, which
+    the library's sum is only close to (_check_clusters); its bits are those of the contract's shaped sum (chunks of 4096 members in
+    ascending triangle index, planes_ref.shaped_sum) of the restatement's triangle areas."""
+    verts, tris, _ = _mesh(name)
+    wcl, wn, _, wta = _want(name)['clusters']
+    assert wn.tolist() == ([4096, 4097] if name == 'two_strips' else [int(name[5:])])
+    got = MU().get_triangle_clusters(_dev(verts, tris) if on_device else (verts, tris), True)
+    assert all(bool(getattr(a, 'is_cuda', False)) == on_device for a in got)
+    _check_clusters(got, _want(name)['clusters'])
+    shaped = np.array([shaped_sum(wta[wcl == c]) for c in range(len(wn))])
+    assert _np(got[2]).tobytes() == shaped.tobytes(), (_np(got[2]), shaped)
 
 
 def test_known_cluster_counts():

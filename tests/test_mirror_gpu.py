@@ -384,6 +384,40 @@ def test_group_by_id_extremes_and_hull_filter_kernels():
     assert dropped > 0.8 * (ids >= 0).sum() * 0.7                      # the filter really removes most members
 
 
+GROUPINGS = {'all_out': (np.array([7, -1, 9, 4, 4, -3, 1 << 40], np.int64), 4),           # every id outside [0, nids)
+             'none_out': (np.array([2, 0, 2, 1, 0, 2, 2], np.int64), 3),
+             'nids_1': (np.array([0, 5, 0, -1, 0], np.int64), 1),
+             'one_point': (np.array([3], np.int64), 6),
+             'descending_257': (np.arange(256, -1, -1, dtype=np.int64), 257)}             # more than one block of keys, reversed
+
+
+@pytest.mark.parametrize('on_device', [False, True], ids=['host', 'device'])
+@pytest.mark.parametrize('case', list(GROUPINGS))
+def test_group_by_id_equals_a_stable_argsort(case, on_device):
+    ids, nids = GROUPINGS[case]
+    n = len(ids)
+    keys = np.where((ids >= 0) & (ids < nids), ids, nids)
+    want_order = np.argsort(keys, kind='stable').astype(np.int32)
+    want_starts = np.searchsorted(keys[want_order], np.arange(nids + 2), side='left').astype(np.int64)
+    ctx = f3d.default_context()
+    if on_device:
+        import torch
+        st = torch.cuda.current_stream().cuda_stream
+        di = torch.from_numpy(ids).cuda()
+        order, skeys = torch.full((n,), -7, dtype=torch.int32, device='cuda'), torch.full((n,), -7, dtype=torch.int32, device='cuda')
+        starts = torch.full((nids + 2,), -7, dtype=torch.int64, device='cuda')
+        torch.cuda.synchronize()
+        ctx.group_by_id_dev(di.data_ptr(), n, nids, order.data_ptr(), skeys.data_ptr(), starts.data_ptr(), st)
+        torch.cuda.synchronize()
+        assert np.array_equal(skeys.cpu().numpy(), keys[want_order])
+        order, starts = order.cpu().numpy(), starts.cpu().numpy()
+    else:
+        order, starts = ctx.group_by_id(ids, nids)
+    assert order.dtype == np.int32 and starts.dtype == np.int64
+    assert np.array_equal(order, want_order), (order, want_order)
+    assert np.array_equal(starts, want_starts), (starts, want_starts)
+
+
 def _same_boxes(got_info, want_info, tol=1e-8):
     """'bbox' entries as corner SETS (the eigenvector signs, hence the corner order, are a convention: f3d.h)."""
     for g, w in zip(got_info, want_info):

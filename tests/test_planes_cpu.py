@@ -60,6 +60,18 @@ def test_room_corner_margin_condition(with_normals):
     assert _room_result(with_normals).margin >= 1e-6
 
 
+@pytest.mark.parametrize('name', list(R.EDGE_SHEETS))
+def test_chunk_edge_sheets_are_one_plane_of_that_many_members_with_margin(name):
+    """The scenes tests/test_planes_gpu.py compares exactly at the edges of a 4096-member chunk are fit for it under the restatement
+    alone: one plane that holds every point, fitted on exactly nx * ny core members, and the margin condition."""
+    nx, ny, _ = R.EDGE_SHEETS[name]
+    pts, nrm = R.edge_sheet(name)
+    assert len(pts) == nx * ny == int(name[5:])
+    r = R.extract(pts, *R.radius_csr(pts, 0.05), nrm)
+    assert r.counts.tolist()[:2] == [1, 1] and r.counts[3] == nx * ny and len(r.members[0]) == nx * ny
+    assert r.margin >= 1e-6, r.margin
+
+
 def test_restated_sums_have_the_contract_shape():
     x = np.random.default_rng(0).standard_normal(4900)
     lanes = [0.0] * 64

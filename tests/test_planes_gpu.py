@@ -53,6 +53,8 @@ def _scene(name):
         pts, nrm, radius, kw = pts[:m].copy(), nrm[:m].copy(), 0.1, dict(min_points=3)
     elif name == 'sheet70':                               # 4900 members: two chunks of the plane sums
         pts, nrm, _ = R.noisy(*R.sheet(70, 70, 0.02, (0, 0, 0), X, Y), rng)
+    elif name in R.EDGE_SHEETS:                           # 4095, 4096, 4097 members: a last chunk of 4095, none, 1
+        pts, nrm = R.edge_sheet(name)
     elif name == 'long':                                  # 3 : 1, so that the in-plane axes are well separated
         pts, nrm, _ = R.noisy(*R.sheet(60, 20, 0.02, (0, 0, 0), X, (0, 0.8, 0.6)), rng)
     elif name == 'min_exact':                             # components of exactly min_points and of min_points - 1 members
@@ -140,6 +142,7 @@ def test_the_scenes_are_what_they_are_meant_to_be():
     assert _want('sheets_half').counts[0] == 1 and _want('sheets_3').counts[0] == 2
     assert _want('fold5').counts[0] == 1 and _want('fold15').counts[0] == 2
     assert len(_want('sheet70').members[0]) == 4900
+    assert [len(_want(name).members[0]) for name in R.EDGE_SHEETS] == [4095, 4096, 4097]
     assert _want('many').counts.tolist()[:2] == [130, 130]
     assert _want('stripped').counts[2] >= 4 and (_want('stripped').labels >= 0).all()
 
@@ -204,7 +207,8 @@ def _angle(a, b):
 
 
 @MODES
-@pytest.mark.parametrize('name,with_normals', [('room', True), ('room', False), ('sheet70', True), ('long', True), ('long', False), ('fold15', True)])
+@pytest.mark.parametrize('name,with_normals', [('room', True), ('room', False), ('sheet70', True), ('long', True), ('long', False), ('fold15', True)] +
+                         [(name, True) for name in R.EDGE_SHEETS])
 def test_plane_parameters(name, with_normals, on_device):
     pts = _scene(name)[0].astype(np.float64)
     want = _want(name, with_normals)
