@@ -706,8 +706,12 @@ static int ensure_fuse_scratch(f3d_ctx* ctx, const f3d_fuse_todo& lay, int64_t n
 }
 
 // F3D_FUSE_SORT: the cloud's cell order into the context's permutation (FUSE_SORT scratch); the kernel then reads xyz[perm[i]]
-static int sort_into_perm(f3d_ctx* ctx, const void* xyz, f3d_dtype dtype, int64_t n, const fuse_scratch& sc, hipStream_t s, const int32_t** perm) {
-    F3D_HIP(ctx, f3d_launch_cell_sort(xyz, dtype, n, nullptr, (int32_t*)sc.perm, sc.sort, s));
+// ride (the one-shot call with coded masks, or NULL): presence, k_fuse_setup with the book, mask coding into sc.tm and the label fill run
+// inside the sort's launches; the caller then skips f3d_launch_code_masks_with_setup
+static int sort_into_perm(f3d_ctx* ctx, const void* xyz, f3d_dtype dtype, int64_t n, const fuse_scratch& sc, hipStream_t s, const int32_t** perm,
+                          f3d_fuse_job* ride = nullptr) {
+    if (ride) F3D_HIP(ctx, f3d_launch_cell_sort_with_riders(*ride, (uint8_t*)sc.tm, ctx->codebook, (int32_t*)sc.perm, sc.sort));
+    else F3D_HIP(ctx, f3d_launch_cell_sort(xyz, dtype, n, nullptr, (int32_t*)sc.perm, sc.sort, s));
     *perm = (const int32_t*)sc.perm;
     return F3D_OK;
 }
@@ -732,18 +736,21 @@ int f3d_project_vote_argmax_dev(f3d_ctx* ctx, const void* xyz, f3d_dtype dtype, 
     job.lay = f3d_fuse_todo_layout(n, nviews, nclasses);
     fuse_scratch sc;                                                                            // grows on first use only
     if ((rc = ensure_fuse_scratch(ctx, job.lay, n, nviews, h, w, nclasses, (coded ? FUSE_CODED : 0) | (sort ? FUSE_SORT : 0), 0, &sc))) return rc;
-    // (Measured and dropped: coding the masks on a second stream, forked from and joined into `stream` with events, while the cloud is
-    // sorted -- the two event dependencies cost more than the ~50 us of overlap they buy: 1.32 ms per C3 step instead of 1.26.)
+    // A call that sorts and codes hands presence, k_fuse_setup with the book, mask coding and the label fill to the sort as riders: extra
+    // blocks of three of its launches (f3d_sort_riders), no second stream, no event.  Measured at C3 (profiles/fuse_riders.md): 0.888 -> 0.865 ms
+    // per step, 0.299 -> 0.282 at 1.25M points; a step without that work at all would be 0.814 / 0.248.
+    // (Measured and dropped earlier: coding the masks on a second stream forked from and joined into `stream` with events while the
+    // cloud is sorted -- the two event dependencies cost more than the overlap they bought, 1.32 ms per C3 step instead of 1.26.)
     job.xyz = xyz; job.dtype = dtype; job.n = n; job.perm = perm; job.gather = (flags & F3D_FUSE_GATHER) && perm;
-    if (sort) {
-        if ((rc = sort_into_perm(ctx, xyz, dtype, n, sc, job.stream, &job.perm))) return rc;
-        job.gather = true;
-    }
     job.views_dev = views_dev; job.nviews = nviews; job.v0 = 0; job.v1 = nviews; job.masks = masks; job.h = h; job.w = w;
     job.nclasses = nclasses; job.threshold = threshold; job.classes = classes; job.votes = votes_u16; job.err = ctx->dev_err;
     job.todo = sc.todo; job.cb = ctx->codebook; job.tables = sc.tables;
+    if (sort) {
+        if ((rc = sort_into_perm(ctx, xyz, dtype, n, sc, job.stream, &job.perm, coded ? &job : nullptr))) return rc;
+        job.gather = true;
+    }
     if (coded) {                                                                                // coded, tiled copy for the fast kernel
-        F3D_HIP(ctx, f3d_launch_code_masks_with_setup(job, (uint8_t*)sc.tm, ctx->codebook));
+        if (!sort) F3D_HIP(ctx, f3d_launch_code_masks_with_setup(job, (uint8_t*)sc.tm, ctx->codebook));
         job.cmasks = (const uint8_t*)sc.tm;
     }
     F3D_HIP(ctx, f3d_launch_fuse(job));

@@ -21,6 +21,7 @@
 #include "f3d.h"
 #include "f3d_math.h"
 #include "f3d_kernels.h"
+#include "f3d_fuse_blocks.h"
 #include <cstdlib>
 
 #pragma clang fp contract(off)
@@ -112,22 +113,7 @@ __device__ __forceinline__ unsigned mask_offset(int iu, int iv, int W) {        
     return (unsigned)(iv * W + iu);
 }
 
-// ------------------------------------------------------------------------------------------
-// Vote-bin codes.  Code 0 = "no sample" (k_code_masks ends every view with 64 such bytes, and a lane without a pixel
-// gathers from there instead of carrying a validity flag through the vote), code 1 = a label the reference would
-// reject (> nclasses, IndexError at voting.py:98), then
-//   presence book (no filter, or votes requested): one code per label that occurs in the masks, the SMALLEST label
-//       getting the LARGEST code, so that the maximum of (count << 8 | code) is count desc, label asc = np.argmax's
-//       first-maximum rule;
-//   filter book: code 2 = any other valid label (it only counts towards the total, voting.py:120), codes 3.. = the
-//       distinct entries of filter_classes.
-// The book is built on the device (k_mask_presence + k_code_lut), so no host round trip decides the histogram size:
-// the launcher enqueues a SMALL-histogram and a FULL-histogram instance of k_fuse and each returns at once unless the
-// book's size is in its range.
-// ------------------------------------------------------------------------------------------
-#define F3D_CODE_NONE 0u
-#define F3D_CODE_BAD 1u
-#define F3D_CODE_OTHER 2u
+// (the vote-bin codes, the coded planes' shape and the bodies of the streaming helpers: f3d_fuse_blocks.h)
 #define F3D_PACKED_SMALL_WORDS 12             // packed 8-bit bins: alphabets up to 48 codes get the medium-LDS instance
 #ifndef F3D_PACKED_LARGE_WORDS
 #define F3D_PACKED_LARGE_WORDS 25            // ... up to 100 codes two points per lane with the view tables in global memory (3 blocks per CU)
@@ -135,60 +121,9 @@ __device__ __forceinline__ unsigned mask_offset(int iu, int iv, int W) {        
 #define F3D_BOOK_DWORDS 256                  // lut + inv + cmin of f3d_codebook, staged in LDS by k_fuse
 #define F3D_BIN32_MAX_CODES 12               // alphabets up to this many codes vote into dword bins (12 KiB of LDS per 256 points: 4 blocks per CU)
 
-// One view of the coded masks: (ceil(H/8) + 2) x (ceil(W/8) + 2) tiles of 8x8 pixels (64 B each): the image plus a one-tile border of
-// "no sample" all around, so that pixel (-1, -1) .. (W, H) are addressable -- tile (0, 0) of view 0, at offset 0, is such a border tile
-// and serves as the address a lane without a pixel gathers from.
-__host__ __device__ inline int f3d_coded_pitch(int W) { return ((W + 7) >> 3) + 2; }
-__host__ __device__ inline size_t f3d_coded_plane(int H, int W) { return (size_t)(((H + 7) >> 3) + 2) * (size_t)f3d_coded_pitch(W) * 64; }
-
-// which labels occur in the masks.  A thread keeps a 256-bit set in four 64-bit registers; masks are piecewise constant,
-// so an 8-byte word whose bytes all equal the previous label costs two instructions.
 template <bool VEC>
 __global__ __launch_bounds__(F3D_BLOCK) void k_mask_presence(const uint8_t* __restrict__ src, int64_t nbytes, f3d_codebook* __restrict__ cb) {
-    unsigned long long m0 = 0, m1 = 0, m2 = 0, m3 = 0;
-    auto mark = [&](unsigned l) {
-        const unsigned long long bit = 1ull << (l & 63u);
-        const unsigned q = l >> 6;
-        m0 |= q == 0u ? bit : 0ull; m1 |= q == 1u ? bit : 0ull; m2 |= q == 2u ? bit : 0ull; m3 |= q == 3u ? bit : 0ull;
-    };
-    if (VEC) {
-        const int64_t nw = nbytes >> 3;
-        const uint64_t* w = reinterpret_cast<const uint64_t*>(src);
-        uint64_t last = ~0ull;                                     // the previous word when all of its bytes were equal
-        for (int64_t k = (int64_t)blockIdx.x * F3D_BLOCK + threadIdx.x; k < nw; k += (int64_t)gridDim.x * F3D_BLOCK) {
-            const uint64_t x = w[k];
-            if (x == last) continue;
-            if (x == (x & 0xFFull) * 0x0101010101010101ull) { mark((unsigned)(x & 0xFFull)); last = x; continue; }
-#pragma unroll
-            for (int c = 0; c < 8; ++c) mark((unsigned)(x >> (8 * c)) & 0xFFu);
-        }
-        if (blockIdx.x == 0 && threadIdx.x < (nbytes & 7)) mark(src[(nw << 3) + threadIdx.x]);
-    } else {
-        for (int64_t k = (int64_t)blockIdx.x * F3D_BLOCK + threadIdx.x; k < nbytes; k += (int64_t)gridDim.x * F3D_BLOCK) mark(src[k]);
-    }
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) {
-        m0 |= __shfl_xor(m0, off, 64); m1 |= __shfl_xor(m1, off, 64); m2 |= __shfl_xor(m2, off, 64); m3 |= __shfl_xor(m3, off, 64);
-    }
-    // block-level OR in LDS, then one thread per dword adds only the bits the global set still lacks: thousands of waves
-    // hammering the same 8 dwords with atomics cost 0.38 ms; masks share their alphabet, so almost every block finds its bits set
-    __shared__ unsigned blk[8];
-    if (threadIdx.x < 8) blk[threadIdx.x] = 0u;
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) {
-        const unsigned long long m[4] = {m0, m1, m2, m3};
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            if ((unsigned)m[q]) atomicOr(&blk[2 * q], (unsigned)m[q]);
-            if ((unsigned)(m[q] >> 32)) atomicOr(&blk[2 * q + 1], (unsigned)(m[q] >> 32));
-        }
-    }
-    __syncthreads();
-    if (threadIdx.x < 8) {
-        const unsigned want = blk[threadIdx.x];
-        const unsigned have = __hip_atomic_load(&cb->presence[threadIdx.x], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        if (want & ~have) atomicOr(&cb->presence[threadIdx.x], want);
-    }
+    f3d_presence_block<VEC>(src, nbytes, cb, blockIdx.x, gridDim.x, F3D_BLOCK);
 }
 
 // the presence set as 256 bytes of 0 / 1 (to_bytes) or back (one block of 256 threads)
@@ -204,97 +139,14 @@ __global__ __launch_bounds__(F3D_BLOCK) void k_presence_bytes(f3d_codebook* __re
     if ((l & 63u) == 0u) { cb->presence[l >> 5] = (unsigned)m; cb->presence[(l >> 5) + 1] = (unsigned)(m >> 32); }
 }
 
-// cb->cmin for this call's threshold (see segment_point): thread t finds, by bisection with the reference's own float64 division,
-// how many c in 0..t give c / t < threshold.  One block of 256 threads.
-__device__ __forceinline__ void threshold_table(f3d_codebook* __restrict__ cb, double threshold) {
-    const int t = threadIdx.x;
-    int lo = 0, hi = t + 1;                                   // c in [lo, hi): the first c that is NOT below the threshold
-    while (lo < hi) {
-        const int mid = (lo + hi) >> 1;
-        if ((double)mid / (double)t < threshold) lo = mid + 1; else hi = mid;
-    }
-    cb->cmin[t] = (uint16_t)lo;                               // t = 0 is never looked up (no votes: voting.py:126)
-}
-
-// one block of 256 threads: thread l decides the code of label l.  book: 0 = every label 0..nclasses has a bin (no
-// presence pass ran), 1 = presence book, 2 = filter book.
-__device__ __forceinline__ void code_lut_block(f3d_codebook* __restrict__ cb, int nclasses, int book, const f3d_filter_args& flt) {
-    __shared__ unsigned pres[8];
-    __shared__ int first_of[256];                                  // filter book: position of label l's first occurrence, -1 = not listed
-    const unsigned l = threadIdx.x;
-    if (l < 8) { pres[l] = book == 1 ? cb->presence[l] : 0xFFFFFFFFu; cb->presence[l] = 0u; }   // consumed (see f3d_launch_mask_presence)
-    first_of[l] = -1;
-    cb->inv[l] = 0;
-    __syncthreads();
-    if (book == 2) {
-        if (l == 0)
-            for (int k = flt.nfilter - 1; k >= 0; --k) { const int f = f3d_filter_at(flt, k); if (f >= 0 && f < 256) first_of[f] = k; }
-        __syncthreads();
-        const bool listed = first_of[l] >= 0 && (int)l <= nclasses;
-        int rank = 0;                                              // distinct listed labels below l
-        for (unsigned j = 0; j < l; ++j) rank += (first_of[j] >= 0 && (int)j <= nclasses) ? 1 : 0;
-        int distinct = 0;
-        for (unsigned j = 0; j < 256; ++j) distinct += (first_of[j] >= 0 && (int)j <= nclasses) ? 1 : 0;
-        const unsigned code = (int)l > nclasses ? F3D_CODE_BAD : (listed ? 3u + (unsigned)rank : F3D_CODE_OTHER);
-        cb->lut[l] = (uint8_t)code;
-        if (listed) cb->inv[code] = (uint8_t)l;
-        if (l == 0) { cb->ncodes = 3 + distinct; cb->words = (3 + distinct + 3) >> 2; cb->book = 2; }
-        return;
-    }
-    const bool pv = (int)l <= nclasses && ((pres[l >> 5] >> (l & 31u)) & 1u);     // label l is valid and present
-    __shared__ unsigned long long wb[4];
-    const unsigned long long bal = __ballot(pv);
-    if ((l & 63u) == 0u) wb[l >> 6] = bal;
-    __syncthreads();
-    int K = 0, below = __popcll(bal & ((1ull << (l & 63u)) - 1ull));
-    for (unsigned w = 0; w < 4; ++w) { const int c = __popcll(wb[w]); K += c; below += (w < (l >> 6)) ? c : 0; }
-    unsigned code;
-    if ((int)l > nclasses) code = F3D_CODE_BAD;                    // only meaningful when such a byte really occurs
-    else if (pv) code = (unsigned)(K + 1 - below);                 // smallest present label -> K + 1, largest -> 2
-    else code = F3D_CODE_NONE;                                     // never gathered; its vote row reads the always-zero bin 0
-    cb->lut[l] = (uint8_t)code;
-    if (code >= 2u) cb->inv[code] = (uint8_t)l;
-    if (l == 0) { cb->ncodes = K + 2; cb->words = (K + 2 + 3) >> 2; cb->book = book; }
-}
-
 __global__ __launch_bounds__(F3D_BLOCK) void k_code_lut(f3d_codebook* __restrict__ cb, int nclasses, int book, f3d_filter_args flt) {
-    code_lut_block(cb, nclasses, book, flt);
+    f3d_code_lut_block(cb, nclasses, book, flt);
 }
 
-// [V,H,W] row-major labels -> [V][ceil(H/8) + 2][ceil(W/8) + 2][8][8] bin codes (border tiles = "no sample"); one thread moves one
-// tile row (8 bytes), a wave writes 512 contiguous bytes.  VEC: W % 8 == 0 and src 8-B aligned (one 8-B load per thread).
 template <bool VEC>
 __global__ __launch_bounds__(F3D_BLOCK) void k_code_masks(const uint8_t* __restrict__ src, uint8_t* __restrict__ dst, int V, int H, int W,
                                                            const f3d_codebook* __restrict__ cb) {
-    __shared__ uint32_t lut_w[64];
-    if (threadIdx.x < 64) lut_w[threadIdx.x] = reinterpret_cast<const uint32_t*>(cb->lut)[threadIdx.x];
-    __syncthreads();
-    const uint8_t* lut = reinterpret_cast<const uint8_t*>(lut_w);
-    const int tw = f3d_coded_pitch(W), th = ((H + 7) >> 3) + 2;    // border included
-    const int64_t per_view = (int64_t)th * tw * 8;                 // 8-byte pieces per view
-    const int64_t total = per_view * V;
-    const size_t tplane = f3d_coded_plane(H, W);
-    for (int64_t k = (int64_t)blockIdx.x * F3D_BLOCK + threadIdx.x; k < total; k += (int64_t)gridDim.x * F3D_BLOCK) {
-        const int64_t v = k / per_view; const int64_t r = k - v * per_view;      // r indexes (tile, row-in-tile) of the destination
-        uint64_t out = 0;                                                         // border and padding: F3D_CODE_NONE
-        const int tile = (int)(r >> 3), ry = (int)(r & 7);
-        const int ty = tile / tw, tx = tile - ty * tw;
-        const int y = (ty - 1) * 8 + ry, x0 = (tx - 1) * 8;
-        if (y >= 0 && y < H && x0 >= 0 && x0 < W) {
-            const uint8_t* row = src + (size_t)v * H * W + (size_t)y * W + x0;
-            if (VEC) {
-                const uint64_t x = *reinterpret_cast<const uint64_t*>(row);
-                if (x == (x & 0xFFull) * 0x0101010101010101ull) out = (uint64_t)lut[x & 0xFFull] * 0x0101010101010101ull;
-                else {
-#pragma unroll
-                    for (int c = 0; c < 8; ++c) out |= (uint64_t)lut[(x >> (8 * c)) & 0xFFull] << (8 * c);
-                }
-            } else {
-                for (int c = 0; c < 8; ++c) if (x0 + c < W) out |= (uint64_t)lut[row[c]] << (8 * c);
-            }
-        }
-        *reinterpret_cast<uint64_t*>(dst + (size_t)v * tplane + (size_t)r * 8) = out;
-    }
+    f3d_code_masks_block<VEC>(src, dst, V, H, W, cb, blockIdx.x, gridDim.x, F3D_BLOCK);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -334,7 +186,6 @@ __device__ __forceinline__ double rcp_newton(double x) {            // 1/x to ~1
 // vt: the view's first 15 doubles (M[9], t[3], mnorm[3] -- the head of f3d_view) with stride `vs` between them: straight from the
 // record (vs = 1) or from the block's LDS copy laid out [field][view] (vs = 64; lanes-over-views reads are then conflict-free
 // instead of 64 scattered cache lines per load)
-#define F3D_VHEAD 15
 #ifndef F3D_VT
 #define F3D_VT                           // (volatile was tried to stop the hoisting of these tile-invariant reads: more spills, not fewer)
 #endif
@@ -702,27 +553,9 @@ __device__ __forceinline__ void wave_box(float& lo0, float& hi0, float& lo1, flo
 #ifndef F3D_FUSE_WAVES
 #define F3D_FUSE_WAVES 3                 // waves per SIMD the register allocation of k_fuse must allow (4 spills: measured slower)
 #endif
-// [group][field][view] copies of the per-view constants the lanes-over-views prologue reads (24 floats: cull planes, margins, image
-// size; 15 doubles: M, t, mnorm), for the instance that cannot afford them in LDS: consecutive lanes read consecutive addresses
-__device__ __forceinline__ void threshold_table(f3d_codebook* __restrict__ cb, double threshold);
-__global__ __launch_bounds__(F3D_BLOCK) void k_fuse_setup(const f3d_view* __restrict__ views, int nviews, float* __restrict__ ctabT,
-                                                           double* __restrict__ vtabT, f3d_codebook* __restrict__ cb, double threshold,
-                                                           unsigned int* __restrict__ todo_count, int lut_nclasses, int lut_book, f3d_filter_args flt) {
-    // (the one-shot call builds the code book in the same launch: its last block is k_code_lut's block -- one launch less per step)
-    if (lut_book >= 0 && blockIdx.x == gridDim.x - 1) { code_lut_block(cb, lut_nclasses, lut_book, flt); return; }
-    if (blockIdx.x == 0) {
-        threshold_table(cb, threshold);                       // ... the call's threshold table (segment_point)
-        if (todo_count && threadIdx.x < 4) todo_count[threadIdx.x] = 0u;   // ... and empty deferred lists
-    }
-    const int ngroups = (nviews + 63) >> 6;
-    const int nsetup = lut_book >= 0 ? (int)gridDim.x - 1 : (int)gridDim.x;
-    for (int k = blockIdx.x * F3D_BLOCK + threadIdx.x; k < ngroups * 64 * 39; k += nsetup * F3D_BLOCK) {
-        const int v = k / 39, f = k - v * 39, g = v >> 6, l = v & 63;
-        const f3d_view& vw = views[v < nviews ? v : nviews - 1];
-        if (f < 24) ctabT[(g * 24 + f) * 64 + l] = reinterpret_cast<const float*>(&vw.cull_n32[0][0])[f];
-        else vtabT[(g * F3D_VHEAD + (f - 24)) * 64 + l] = reinterpret_cast<const double*>(&vw)[f - 24];
-    }
-}
+// the per-call tables of a k_fuse launch (f3d_fuse_setup_block, f3d_fuse_blocks.h).  (The one-shot call builds the code book in the same
+// launch: its last block is k_code_lut's block -- one launch less per step.)
+__global__ __launch_bounds__(F3D_BLOCK) void k_fuse_setup(f3d_setup_args a) { f3d_fuse_setup_block(a, blockIdx.x, gridDim.x, F3D_BLOCK); }
 
 // CARRY: the instance of the view-chunked call (f3d_fuse_chunk_dev): the views arrive in several launches; between two of them a
 // point's vote bins live in HBM as `carry` [tile][point slot][word][F3D_BLOCK], 8-bit bins packed four to a dword whatever the LDS
@@ -1671,8 +1504,7 @@ f3d_fuse_todo f3d_fuse_todo_layout(int64_t n, int nviews, int nclasses) {
 // profiles/r03_summary.md); the fill is 80 MB at streaming speed.  At the reference's threshold 0.5 most points of a real scene and
 // 99.9 % of the synthetic one stay unlabelled; at threshold 0 the fill is 15 us spent for nothing.
 __global__ __launch_bounds__(F3D_BLOCK) void k_fill_labels(int64_t* __restrict__ classes, int64_t n, int64_t value) {
-    for (int64_t i = (int64_t)blockIdx.x * F3D_BLOCK + threadIdx.x; i < n; i += (int64_t)gridDim.x * F3D_BLOCK)
-        __builtin_nontemporal_store(value, &classes[i]);
+    f3d_fill_labels_block(classes, n, value, blockIdx.x, gridDim.x, F3D_BLOCK);
 }
 
 static int64_t unlabelled_after_remap(int nclasses, const f3d_filter_args& flt) {   // segment_point's answer for a point without votes
@@ -1721,7 +1553,7 @@ static hipError_t launch_fuse_t(const f3d_fuse_job& j, int mode, int grid) {
     int64_t prefilled = F3D_NO_PREFILL;
     if (fast && !(chunk_flags & 2)) {                        // (a chunk that parks its bins writes no labels)
         prefilled = unlabelled_after_remap(nclasses, flt);
-        if (prefilled != F3D_NO_PREFILL)
+        if (prefilled != F3D_NO_PREFILL && !j.filled)           // (filled: a rider of the cell sort has done it)
             hipLaunchKernelGGL(k_fill_labels, dim3(f3d_grid_for(n, F3D_BLOCK, 2048)), dim3(F3D_BLOCK), 0, s, j.classes, n, prefilled);
     }
     if (fast) {
@@ -1777,16 +1609,45 @@ static hipError_t launch_fuse_t(const f3d_fuse_job& j, int mode, int grid) {
     return hipGetLastError();
 }
 
-hipError_t f3d_launch_fuse_setup(const f3d_fuse_job& j, f3d_codebook* cb, bool with_book) {
+// the arguments of the setup blocks for the job's views [v0, v1)
+static f3d_setup_args setup_args_for(const f3d_fuse_job& j, f3d_codebook* cb, bool with_book) {
     const int v0 = j.carry ? j.v0 : 0, cnv = (j.carry ? j.v1 : j.nviews) - v0;
-    if (cnv <= 0) return hipSuccess;
     const fuse_tables tab = fuse_tables_split(j.tables, cnv);
-    f3d_filter_args none; none.nfilter = 0; none.cls_dev = nullptr; none.cls_host = nullptr; for (int k = 0; k < 8; ++k) none.cls[k] = -1;
+    f3d_setup_args a;
+    a.views = j.views_dev + v0; a.nviews = cnv; a.ctabT = tab.ctabT; a.vtabT = tab.vtabT; a.cb = cb; a.threshold = j.threshold;
+    a.todo_count = v0 == 0 ? f3d_fuse_todo::counters(j.todo) : (unsigned int*)nullptr;
+    a.lut_nclasses = with_book ? j.nclasses : 0;
+    a.lut_book = with_book ? pick_book(j.flt, j.votes != nullptr) : -1;
+    a.flt = j.flt;
+    if (!with_book) { a.flt.nfilter = 0; a.flt.cls_dev = nullptr; a.flt.cls_host = nullptr; for (int k = 0; k < 8; ++k) a.flt.cls[k] = -1; }
+    return a;
+}
+
+hipError_t f3d_launch_fuse_setup(const f3d_fuse_job& j, f3d_codebook* cb, bool with_book) {
+    if ((j.carry ? j.v1 - j.v0 : j.nviews) <= 0) return hipSuccess;
     if (with_book && (j.nclasses < 0 || j.nclasses > F3D_CODE_MAX_NCLASSES)) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(k_fuse_setup, dim3(with_book ? 9 : 8), dim3(F3D_BLOCK), 0, j.stream, j.views_dev + v0, cnv, tab.ctabT, tab.vtabT, cb,
-                       j.threshold, v0 == 0 ? f3d_fuse_todo::counters(j.todo) : (unsigned int*)nullptr, with_book ? j.nclasses : 0,
-                       with_book ? pick_book(j.flt, j.votes != nullptr) : -1, with_book ? j.flt : none);
+    hipLaunchKernelGGL(k_fuse_setup, dim3(with_book ? 9 : 8), dim3(F3D_BLOCK), 0, j.stream, setup_args_for(j, cb, with_book));
     return hipGetLastError();
+}
+
+// The one-shot call that sorts: the cell sort with the work of f3d_launch_code_masks_with_setup and of the label fill riding in its
+// launches (f3d_sort_riders).  Sets job.filled (whether the labels were pre-filled); the caller sets job.cmasks = coded.
+hipError_t f3d_launch_cell_sort_with_riders(f3d_fuse_job& j, uint8_t* coded, f3d_codebook* cb, int32_t* perm, void* sort_scratch) {
+    if (j.nviews <= 0 || j.n <= 0) return hipErrorInvalidValue;
+    if (j.nclasses < 0 || j.nclasses > F3D_CODE_MAX_NCLASSES || ((uintptr_t)coded & 7)) return hipErrorInvalidValue;
+    f3d_sort_riders r;
+    r.masks = j.masks; r.mask_bytes = (int64_t)j.nviews * j.h * j.w; r.cb = cb;
+    r.presence = pick_book(j.flt, j.votes != nullptr) == 1;
+    const int64_t fill = unlabelled_after_remap(j.nclasses, j.flt);
+    j.filled = fill != F3D_NO_PREFILL;
+    r.classes = j.filled ? j.classes : nullptr; r.n = j.n; r.fill_value = fill;
+    const int pb = r.presence ? f3d_grid_for(r.mask_bytes >> 4, F3D_RIDER_THREADS * F3D_RIDER_UNROLL_1, F3D_RIDER_BLOCKS_1) : 0;
+    const int fb = j.filled ? f3d_grid_for(j.n, F3D_RIDER_THREADS * 8, F3D_RIDER_BLOCKS_1) : 0;
+    r.pass1_blocks = pb > fb ? pb : fb;
+    r.setup = setup_args_for(j, cb, true); r.setup_blocks = 9;
+    r.coded = coded; r.V = j.nviews; r.H = j.h; r.W = j.w;
+    r.code_blocks = f3d_grid_for((int64_t)j.nviews * (int64_t)(f3d_coded_plane(j.h, j.w) / 8), F3D_RIDER_THREADS * F3D_RIDER_UNROLL, F3D_RIDER_BLOCKS_2);
+    return f3d_launch_cell_sort(j.xyz, j.dtype, j.n, nullptr, perm, sort_scratch, j.stream, &r);
 }
 
 hipError_t f3d_launch_fuse(const f3d_fuse_job& j) {

@@ -349,6 +349,7 @@ struct f3d_fuse_job {
     void* todo; f3d_fuse_todo lay;                                                  // scratch: the todo block and its layout,
     const f3d_codebook* cb; void* tables; uint32_t* carry; void* xyz_keep;          //   the code book, f3d_fuse_tables_bytes(nviews), ...
     hipStream_t stream;
+    bool filled;                                                                    // the label fill has been done (a rider of the cell sort)
 };
 hipError_t f3d_launch_fuse(const f3d_fuse_job& job);
 // Before f3d_launch_fuse, on any stream that is joined into its stream: the threshold table of the code book (segment_point) and the
@@ -369,7 +370,27 @@ hipError_t f3d_launch_fastpath_audit(const void* xyz, int dtype, int64_t n, cons
                                      unsigned long long* stats_dev, hipStream_t s);
 // cell sort (f3d_sort.hip): perm (and sorted_xyz unless NULL) receive the cloud in grid-cell order; scratch >= f3d_sort_scratch_bytes(n)
 size_t f3d_sort_scratch_bytes(int64_t n);
-hipError_t f3d_launch_cell_sort(const void* xyz, int dtype, int64_t n, void* sorted_xyz, int32_t* perm, void* scratch, hipStream_t s);
+// riders (internal, f3d_fuse_blocks.h; NULL = none): streaming work of the fused call that depends on nothing the sort produces and runs
+// as extra blocks of three of the sort's launches -- label presence and the label fill beside pass 1, k_fuse_setup with the book inside
+// the second scan's launch, mask coding beside pass 2.  Ordering between them comes from the launches alone.
+struct f3d_sort_riders;
+hipError_t f3d_launch_cell_sort(const void* xyz, int dtype, int64_t n, void* sorted_xyz, int32_t* perm, void* scratch, hipStream_t s,
+                                const f3d_sort_riders* riders = nullptr);
+// Block b of a launch of `grid` blocks of which `extra` are riders, spread evenly through the grid (blocks are dispatched in index order:
+// riders at the end would start when the host kernel's own work is nearly over).  The riders before block b number floor(b * extra / grid);
+// b is a rider when that count steps at b + 1.  index: the rider's number 0..extra-1, or the host kernel's own block number 0..grid-extra-1.
+struct f3d_block_role { bool rider; int index; };
+__host__ __device__ inline f3d_block_role f3d_rider_role(unsigned b, unsigned grid, unsigned extra) {
+    const unsigned before = (unsigned)(((unsigned long long)b * extra) / grid);
+    const unsigned upto = (unsigned)(((unsigned long long)(b + 1) * extra) / grid);
+    f3d_block_role r;
+    r.rider = upto != before;
+    r.index = r.rider ? (int)before : (int)(b - before);
+    return r;
+}
+// the one-shot call that sorts and codes: the cell sort carrying the work of f3d_launch_code_masks_with_setup and the label fill as
+// riders (f3d_fuse.hip).  Sets job.filled; the caller sets job.cmasks = coded and must not call f3d_launch_code_masks_with_setup.
+hipError_t f3d_launch_cell_sort_with_riders(f3d_fuse_job& job, uint8_t* coded, f3d_codebook* cb, int32_t* perm, void* sort_scratch);
 // same-class connected components (f3d_cc.hip): root[i] = smallest index of i's component; parent = int32 [n] scratch
 hipError_t f3d_launch_components(const int64_t* classes, int64_t n, const int64_t* offs, const int32_t* nbrs, int32_t* parent,
                                  int64_t* root, int* err, hipStream_t s, int errbit = F3D_DEVERR_CC);

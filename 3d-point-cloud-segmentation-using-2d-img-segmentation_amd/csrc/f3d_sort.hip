@@ -18,6 +18,9 @@
 //   k_rs_scatter<2>: LSD pass 2 (high byte, stable): perm
 //   k_gather_xyz   : sorted[j] = xyz[perm[j]]     (only for the "prepared layout" entry point; the
 //                    in-step sort lets the fused kernel read xyz through perm instead)
+//   k_rs_scatter_ride<1|2>, k_rs_scan_setup : the same launches with RIDER blocks (f3d_sort_riders, f3d_fuse_blocks.h): streaming work of
+//                    the one-shot fused call -- label presence + label fill, k_fuse_setup with the code book, mask coding -- that depends
+//                    on nothing the sort produces and uses the HBM bandwidth the ranking rounds leave idle
 // A tile's ranks come from per-wave digit counts in LDS and, per round of 64 keys, one 64-bit lane mask per digit value in LDS (every lane
 // ORs its bit into its digit's mask, reads the mask back and counts the lanes below it: k_rs_scatter): no global atomic, no look-back
 // chain, the same perm in every run (equal keys keep their index order: both passes are stable).  (Until the lane masks a round matched
@@ -32,6 +35,7 @@
 #include <cstring>
 #include "f3d.h"
 #include "f3d_kernels.h"
+#include "f3d_fuse_blocks.h"
 
 namespace {
 
@@ -256,9 +260,9 @@ __global__ __launch_bounds__(RS_THREADS) void k_rs_hist2(const R* __restrict__ r
 }
 
 // block d: exclusive scan of row d of blkhist (the tiles' counts of digit value d) in place; tot[d] = the row's sum
-__global__ __launch_bounds__(256) void k_rs_scan(uint32_t* __restrict__ blkhist, int ntiles, uint32_t* __restrict__ tot) {
+__device__ __forceinline__ void rs_scan_row(uint32_t* __restrict__ blkhist, int ntiles, uint32_t* __restrict__ tot, int d) {
     __shared__ uint32_t part[256];
-    uint32_t* row = blkhist + (size_t)blockIdx.x * ntiles;
+    uint32_t* row = blkhist + (size_t)d * ntiles;
     const int per = (ntiles + 255) / 256;
     const int lo = threadIdx.x * per, hi = min(ntiles, lo + per);
     uint32_t sum = 0;
@@ -273,7 +277,18 @@ __global__ __launch_bounds__(256) void k_rs_scan(uint32_t* __restrict__ blkhist,
     }
     uint32_t run = part[threadIdx.x] - sum;                          // exclusive prefix of this thread's piece
     for (int k = lo; k < hi; ++k) { const uint32_t c = row[k]; row[k] = run; run += c; }
-    if (threadIdx.x == 255) tot[blockIdx.x] = part[255];
+    if (threadIdx.x == 255) tot[d] = part[255];
+}
+__global__ __launch_bounds__(256) void k_rs_scan(uint32_t* __restrict__ blkhist, int ntiles, uint32_t* __restrict__ tot) {
+    rs_scan_row(blkhist, ntiles, tot, blockIdx.x);
+}
+
+// The same scan with the k_fuse_setup blocks (tables, threshold table, empty todo lists, the code book) riding in its launch: the
+// book needs the label presence complete, which pass 1 (launched earlier on the stream) carried, and pass 2's coding rider needs the book.
+__global__ __launch_bounds__(256) void k_rs_scan_setup(uint32_t* __restrict__ blkhist, int ntiles, uint32_t* __restrict__ tot, f3d_setup_args setup, int extra) {
+    const f3d_block_role role = f3d_rider_role(blockIdx.x, gridDim.x, (unsigned)extra);
+    if (role.rider) { f3d_fuse_setup_block(setup, role.index, extra, 256); return; }
+    rs_scan_row(blkhist, ntiles, tot, role.index);
 }
 
 // exclusive prefix of `v` over threads 0..255 (threads >= 256 pass 0 and get garbage); every thread of the block must call it
@@ -318,9 +333,9 @@ __device__ __forceinline__ void rs_round_order() {
 // The mask tables lie on the first RS_WAVES x 2 KB of `srec` (a table of their own would cost a CU its third block), so the rounds
 // only compute positions -- kept with the digit in dig[r], no further register -- and the records are placed after a block barrier.
 template <int PASS, typename R>
-__global__ __launch_bounds__(RS_THREADS) void k_rs_scatter(const sort_key_t* __restrict__ keys, const R* __restrict__ recs_in, int64_t n,
-                                                            const uint32_t* __restrict__ offs, const uint32_t* __restrict__ tot, int ntiles,
-                                                            R* __restrict__ recs_out, uint32_t* __restrict__ perm_out) {
+__device__ __forceinline__ void rs_scatter_tile(const sort_key_t* __restrict__ keys, const R* __restrict__ recs_in, int64_t n,
+                                                const uint32_t* __restrict__ offs, const uint32_t* __restrict__ tot, int ntiles,
+                                                R* __restrict__ recs_out, uint32_t* __restrict__ perm_out, const int tile) {
     __shared__ uint32_t wcount[RS_WAVES][256];                       // per wave: count of each digit value, then its running position in the tile
     __shared__ uint32_t gdelta[256];                                 // global position of the tile's first key of a digit value - its position in the tile
     __shared__ uint32_t wsum[4];
@@ -335,14 +350,14 @@ __global__ __launch_bounds__(RS_THREADS) void k_rs_scatter(const sort_key_t* __r
     const int d_own = threadIdx.x & 255;
     const bool own = threadIdx.x < 256;
     const uint32_t t_d = own ? tot[d_own] : 0u;
-    const uint32_t o_d = own ? offs[(size_t)d_own * ntiles + blockIdx.x] : 0u;
+    const uint32_t o_d = own ? offs[(size_t)d_own * ntiles + tile] : 0u;
     for (int k = threadIdx.x; k < RS_WAVES * 256; k += RS_THREADS) { (&wcount[0][0])[k] = 0u; rs_dyn[k] = 0ull; }
     __syncthreads();
     uint32_t dig[RS_ROUNDS];                                         // the digit; after the ranking rounds (digit << 16) | tile position
     R val[RS_ROUNDS];                                                // the record that leaves (pass 1: built here; pass 2: the one that came in)
 #pragma unroll
     for (int r = 0; r < RS_ROUNDS; ++r) {
-        const int64_t i = rs_item(blockIdx.x, wave, r, lane);
+        const int64_t i = rs_item(tile, wave, r, lane);
         dig[r] = 0xFFFFFFFFu; val[r] = 0;
         if (i < n) {
             if (PASS == 1) { const uint32_t k = keys[i]; dig[r] = k & 0xFFu; val[r] = ((R)(k >> 8) << rs_rec<R>::shift) | (R)i; }
@@ -395,7 +410,7 @@ __global__ __launch_bounds__(RS_THREADS) void k_rs_scatter(const sort_key_t* __r
         }
     }
     __syncthreads();
-    const int64_t left = n - (int64_t)blockIdx.x * RS_TILE;
+    const int64_t left = n - (int64_t)tile * RS_TILE;
     const int count = (int)(left < RS_TILE ? left : RS_TILE);
 #pragma unroll 4
     for (int j = threadIdx.x; j < count; j += RS_THREADS) {
@@ -403,6 +418,42 @@ __global__ __launch_bounds__(RS_THREADS) void k_rs_scatter(const sort_key_t* __r
         if (PASS == 1) recs_out[(uint32_t)j + gdelta[sdig[j]]] = rec;
         else perm_out[(uint32_t)j + gdelta[(uint32_t)(rec >> rs_rec<R>::shift) & 0xFFu]] = (uint32_t)(rec & rs_rec<R>::imask);
     }
+}
+
+template <int PASS, typename R>
+__global__ __launch_bounds__(RS_THREADS) void k_rs_scatter(const sort_key_t* __restrict__ keys, const R* __restrict__ recs_in, int64_t n,
+                                                            const uint32_t* __restrict__ offs, const uint32_t* __restrict__ tot, int ntiles,
+                                                            R* __restrict__ recs_out, uint32_t* __restrict__ perm_out) {
+    rs_scatter_tile<PASS, R>(keys, recs_in, n, offs, tot, ntiles, recs_out, perm_out, blockIdx.x);
+}
+
+// The scatter passes with riders (f3d_sort_riders): `extra` blocks of the launch, spread evenly through the grid, do streaming work of the
+// fused call instead of a tile -- the ranking rounds are chains of LDS round trips that leave HBM idle, the riders are pure HBM traffic.
+// A rider block holds the kernel's LDS (a resident slot of the sort) while it lives; it waits for nobody and nobody waits for it.
+//   PASS 1: label presence over the mask bytes (masks == NULL: none), then the label fill (classes == NULL: none) -- pass 1 has bandwidth
+//   to spare, pass 2 + coding has not.   PASS 2: mask coding with the book the scan launch in front built.
+template <int PASS, typename R>
+__global__ __launch_bounds__(RS_THREADS) void k_rs_scatter_ride(const sort_key_t* __restrict__ keys, const R* __restrict__ recs_in, int64_t n,
+                                                                 const uint32_t* __restrict__ offs, const uint32_t* __restrict__ tot, int ntiles,
+                                                                 R* __restrict__ recs_out, uint32_t* __restrict__ perm_out,
+                                                                 const uint8_t* __restrict__ masks, int64_t mask_bytes, f3d_codebook* __restrict__ cb,
+                                                                 uint8_t* __restrict__ coded, int V, int H, int W,
+                                                                 int64_t* __restrict__ classes, int64_t nfill, int64_t fill_value, int extra) {
+    const f3d_block_role role = f3d_rider_role(blockIdx.x, gridDim.x, (unsigned)extra);
+    if (role.rider) {
+        if (PASS == 1) {
+            if (masks) {
+                if (!((uintptr_t)masks & 7)) f3d_presence_block_wide<F3D_RIDER_UNROLL_1>(masks, mask_bytes, cb, role.index, extra, RS_THREADS);
+                else f3d_presence_block<false>(masks, mask_bytes, cb, role.index, extra, RS_THREADS);
+            }
+            if (classes) f3d_fill_labels_block(classes, nfill, fill_value, role.index, extra, RS_THREADS);
+        } else {
+            if (!(W & 7) && !((uintptr_t)masks & 7)) f3d_code_masks_block_rows<F3D_RIDER_UNROLL>(masks, coded, V, H, W, cb, role.index, extra, RS_THREADS);
+            else f3d_code_masks_block<false>(masks, coded, V, H, W, cb, role.index, extra, RS_THREADS);
+        }
+        return;
+    }
+    rs_scatter_tile<PASS, R>(keys, recs_in, n, offs, tot, ntiles, recs_out, perm_out, role.index);
 }
 
 template <typename T>
@@ -435,7 +486,7 @@ sort_layout layout_for(int64_t n) {
 }
 
 template <typename R>
-hipError_t run_passes(const sort_layout& L, char* base, int64_t n, int32_t* perm, hipStream_t s) {
+hipError_t run_passes(const sort_layout& L, char* base, int64_t n, int32_t* perm, hipStream_t s, const f3d_sort_riders* rd) {
     const sort_key_t* keys = reinterpret_cast<const sort_key_t*>(base + L.keys);
     R* recs = reinterpret_cast<R*>(base + L.recs);
     uint32_t* hist = reinterpret_cast<uint32_t*>(base + L.hist);
@@ -446,6 +497,25 @@ hipError_t run_passes(const sort_layout& L, char* base, int64_t n, int32_t* perm
         hipError_t e = hipFuncSetAttribute((const void*)k_rs_scatter<1, R>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds1);
         if (e == hipSuccess) e = hipFuncSetAttribute((const void*)k_rs_scatter<2, R>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds2);
         if (e != hipSuccess) return e;
+    }
+    if (rd) {
+        if (lds1 > 48 * 1024) {
+            hipError_t e = hipFuncSetAttribute((const void*)k_rs_scatter_ride<1, R>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds1);
+            if (e == hipSuccess) e = hipFuncSetAttribute((const void*)k_rs_scatter_ride<2, R>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds2);
+            if (e != hipSuccess) return e;
+        }
+        hipLaunchKernelGGL(k_rs_scan, dim3(256), dim3(256), 0, s, hist, L.ntiles, tot);
+        if (rd->pass1_blocks > 0)
+            hipLaunchKernelGGL((k_rs_scatter_ride<1, R>), dim3(L.ntiles + rd->pass1_blocks), bt, lds1, s, keys, (const R*)nullptr, n, hist, tot, L.ntiles, recs,
+                               (uint32_t*)nullptr, rd->presence ? rd->masks : (const uint8_t*)nullptr, rd->mask_bytes, rd->cb, (uint8_t*)nullptr, 0, 0, 0,
+                               rd->classes, rd->n, rd->fill_value, rd->pass1_blocks);
+        else hipLaunchKernelGGL((k_rs_scatter<1, R>), gt, bt, lds1, s, keys, (const R*)nullptr, n, hist, tot, L.ntiles, recs, (uint32_t*)nullptr);
+        hipLaunchKernelGGL(k_rs_hist2<R>, gt, bt, 0, s, recs, n, hist, L.ntiles);
+        hipLaunchKernelGGL(k_rs_scan_setup, dim3(256 + rd->setup_blocks), dim3(256), 0, s, hist, L.ntiles, tot, rd->setup, rd->setup_blocks);
+        hipLaunchKernelGGL((k_rs_scatter_ride<2, R>), dim3(L.ntiles + rd->code_blocks), bt, lds2, s, (const sort_key_t*)nullptr, recs, n, hist, tot, L.ntiles,
+                           (R*)nullptr, reinterpret_cast<uint32_t*>(perm), rd->masks, rd->mask_bytes, rd->cb, rd->coded, rd->V, rd->H, rd->W,
+                           (int64_t*)nullptr, (int64_t)0, (int64_t)0, rd->code_blocks);
+        return hipGetLastError();
     }
     hipLaunchKernelGGL(k_rs_scan, dim3(256), dim3(256), 0, s, hist, L.ntiles, tot);
     hipLaunchKernelGGL((k_rs_scatter<1, R>), gt, bt, lds1, s, keys, (const R*)nullptr, n, hist, tot, L.ntiles, recs, (uint32_t*)nullptr);
@@ -459,7 +529,8 @@ hipError_t run_passes(const sort_layout& L, char* base, int64_t n, int32_t* perm
 
 size_t f3d_sort_scratch_bytes(int64_t n) { return layout_for(n < 1 ? 1 : n).total; }
 
-hipError_t f3d_launch_cell_sort(const void* xyz, int dtype, int64_t n, void* sorted_xyz, int32_t* perm, void* scratch, hipStream_t s) {
+hipError_t f3d_launch_cell_sort(const void* xyz, int dtype, int64_t n, void* sorted_xyz, int32_t* perm, void* scratch, hipStream_t s,
+                                const f3d_sort_riders* riders) {
     if (n <= 0) return hipSuccess;
     if (n > 0x7fffffffLL) return hipErrorInvalidValue;
     const sort_layout L = layout_for(n);
@@ -482,7 +553,7 @@ hipError_t f3d_launch_cell_sort(const void* xyz, int dtype, int64_t n, void* sor
         if (small) hipLaunchKernelGGL((k_rs_keys<float, RK_SMALL_THREADS>), gt, dim3(RK_SMALL_THREADS), 0, s, (const float*)xyz, n, partial, nparts, keys, hist, L.ntiles);
         else hipLaunchKernelGGL((k_rs_keys<float, F3D_RK_THREADS>), gt, dim3(F3D_RK_THREADS), 0, s, (const float*)xyz, n, partial, nparts, keys, hist, L.ntiles);
     }
-    hipError_t e = L.wide ? run_passes<uint64_t>(L, base, n, perm, s) : run_passes<uint32_t>(L, base, n, perm, s);
+    hipError_t e = L.wide ? run_passes<uint64_t>(L, base, n, perm, s, riders) : run_passes<uint32_t>(L, base, n, perm, s, riders);
     if (e != hipSuccess) return e;
     if (sorted_xyz) {
         if (dtype == F3D_F64) hipLaunchKernelGGL(k_gather_xyz<double>, dim3(gstream), dim3(SB), 0, s, (const double*)xyz, n, perm, (double*)sorted_xyz);
