@@ -1,4 +1,5 @@
-"""The mesh-topology part of the reference's Fusion3DSeg/segUtils/meshUtils.py on the GPU, plus ``clean_mesh``.
+"""The mesh-topology part of the reference's Fusion3DSeg/segUtils/meshUtils.py on the GPU, plus ``clean_mesh`` and the face graph
+(``face_normals``, ``face_adjacency``, ``segment_faces``: face votes smoothed over the faces' adjacency and split into instances).
 
 Same names and positional signatures as the reference (file:line in each docstring).  NumPy arrays in give NumPy arrays out
 (host-pointer entries of libf3d_hip); device tensors in give device tensors out, ordered with torch's current stream
@@ -10,13 +11,15 @@ and writes nothing -- a stated deviation: the reference's list and NumPy indexin
 The Open3D / cv2 converters and viewers of the reference file (to_pcd, to_mesh, to_lines, to_uvmesh, to_image, pick_points,
 get_roi, read_images, load_o3d_camera_data), generate_texture, uv2rgb and classwise_triangle_colors are not provided.
 """
+import math
+
 import numpy as np
 
 import f3d
 from f3d.tensors import dtype_code, index_code, on_device, work_stream
 
 __all__ = ['vertex_triangle_mapping', 'remove_faces_by_vertices', 'keep_faces_by_vertices', 'get_triangle_clusters', 'clean_mesh', 'label_faces',
-           'bbox_axes', 'one_to_all_angles', 'VertexTriangleMap']
+           'face_normals', 'face_adjacency', 'segment_faces_from_votes', 'segment_faces', 'bbox_axes', 'one_to_all_angles', 'VertexTriangleMap']
 
 
 # ------------------------------------------------------------------------------------------------ argument checks
@@ -342,7 +345,198 @@ def _label_faces(vertices, triangles, K, wxyzs, translations, masks, max_depth=1
     return (cls, votes) if return_votes else cls
 
 
-# ------------------------------------------------------------------------------------------------ 7. host helpers
+# ------------------------------------------------------------------------------------------------ 7. face graph
+def _is_mesh(x):
+    return (isinstance(x, tuple) and len(x) == 2) or (hasattr(x, 'vertices') and hasattr(x, 'triangles'))
+
+
+def _bad_index(ctx, work):
+    ctx.take_device_error(work.cuda_stream)
+    raise IndexError('mesh: a triangle vertex index is outside [0, nvertices)')
+
+
+def face_normals(vertices, *args, **kwargs):
+    """face_normals(vertices, triangles, return_centroids=False, return_areas=False), or with a mesh (``.vertices`` /
+    ``.triangles``, or a ``(vertices, triangles)`` pair) in place of the first two arguments.
+
+    Unit normals of the faces (f3d.h f3d_mesh_face_frames) -> float64 [M, 3]; with the flags a tuple (normals[, centroids float64
+    [M, 3]][, areas float64 [M]]).  normal = c / |c|, c = cross(p0 - p1, p0 - p2), and (0, 0, 0) where |c| is 0 or not finite;
+    areas equal get_triangle_clusters' triangle areas bit for bit."""
+    if _is_mesh(vertices):
+        return _face_normals(*_mesh_parts(vertices), *args, **kwargs)
+    return _face_normals(vertices, *args, **kwargs)
+
+
+def _face_normals(vertices, triangles, return_centroids=False, return_areas=False):
+    tris = _triangles(triangles)
+    verts = _vertices(vertices, tris)
+    nv, nt = verts.shape[0], tris.shape[0]
+    ctx = _ctx(tris)
+    if not on_device(tris):
+        nrm, cen, area = ctx.mesh_face_frames(verts, tris, return_centroids, return_areas)
+    else:
+        import torch
+        dev = tris.device
+        nrm = torch.empty((nt, 3), dtype=torch.float64, device=dev)
+        cen = torch.empty((nt, 3), dtype=torch.float64, device=dev) if return_centroids else None
+        area = torch.empty(nt, dtype=torch.float64, device=dev) if return_areas else None
+        counts = torch.empty(4, dtype=torch.int64, device=dev)
+        with work_stream(dev) as work:
+            ctx.mesh_face_frames_dev(verts.data_ptr(), dtype_code(verts), nv, tris.data_ptr(), index_code(tris), nt, nrm.data_ptr(),
+                                     None if cen is None else cen.data_ptr(), None if area is None else area.data_ptr(), counts.data_ptr(),
+                                     work.cuda_stream)
+            _counts(ctx, counts, work)
+    out = (nrm,) + ((cen,) if return_centroids else ()) + ((area,) if return_areas else ())
+    return out if len(out) > 1 else nrm
+
+
+def _crease(max_angle):
+    """cos of a crease angle given in degrees in [0, 180], or None."""
+    if max_angle is None:
+        return None
+    angle = float(max_angle)
+    if not 0.0 <= angle <= 180.0:
+        raise ValueError(f'max_angle must be in [0, 180] degrees, got {max_angle}')
+    return math.cos(math.radians(angle))
+
+
+def face_adjacency(triangles, nvertices=None, vertices=None, max_angle=None, return_stats=False):
+    """The faces' adjacency over shared edges as a CSR (f3d.h f3d_mesh_face_graph) -> (offsets int64 [M + 1], neighbours int32
+    [nnz]), the pair smooth_votes, smooth_segment, split_into_instances and extract_planes take.  ``triangles`` may be a mesh
+    (``.vertices`` / ``.triangles``, or a ``(vertices, triangles)`` pair).
+
+    Row f lists, ascending, every other face that shares an edge (min, max) of the corner pairs (0,1), (0,2), (1,2) with f:
+    get_triangle_clusters' edges, so the graph's connected components are its clusters; a non-manifold edge connects all its faces.
+    With ``max_angle`` (degrees in [0, 180]; it needs ``vertices``) two faces stay adjacent only through an edge over which their
+    dihedral angle is at most max_angle: s * dot(nf, ng) >= cos(max_angle), s = +1 for consistently wound neighbours and -1 for
+    inconsistently wound ones, so flipped faces do not cut a flat sheet and a sheet folded back on itself is cut.  Without a
+    max_angle ``nvertices`` alone is enough.  ``return_stats`` appends {'nonmanifold_edges', 'boundary_edges'}.
+
+    Room for 3 M entries is allocated; a non-manifold mesh that needs more is run once more with the size the first run found."""
+    if _is_mesh(triangles):
+        mesh_vertices, triangles = _mesh_parts(triangles)
+        vertices = mesh_vertices if vertices is None else vertices
+    tris = _triangles(triangles)
+    cos_crease = _crease(max_angle)
+    gate = cos_crease is not None
+    if gate and vertices is None:
+        raise ValueError('face_adjacency: a max_angle needs the vertices')
+    if vertices is None and nvertices is None:
+        raise ValueError('face_adjacency: nvertices or vertices must be given')
+    verts = None
+    if vertices is not None:
+        if gate:
+            verts = _vertices(vertices, tris)
+            shape = tuple(verts.shape)
+        else:
+            shape = tuple(vertices.shape) if hasattr(vertices, 'shape') else np.shape(vertices)
+            if len(shape) != 2 or shape[1] != 3:
+                raise ValueError(f'vertices must be [V, 3], got {shape}')
+        if nvertices is not None and int(nvertices) != shape[0]:
+            raise ValueError(f'nvertices is {nvertices}, vertices has {shape[0]} rows')
+        nvertices = shape[0]
+    nv, nt = _nvertices(nvertices), tris.shape[0]
+    ctx = _ctx(tris)
+    if not on_device(tris):
+        offsets, nbrs, counts = ctx.mesh_face_graph(tris, nv, verts, cos_crease)
+        if counts[0] > len(nbrs):
+            offsets, nbrs, counts = ctx.mesh_face_graph(tris, nv, verts, cos_crease, offsets, np.empty(int(counts[0]), np.int32))
+    else:
+        import torch
+        dev = tris.device
+        offsets = torch.empty(nt + 1, dtype=torch.int64, device=dev)
+        counts_dev = torch.empty(4, dtype=torch.int64, device=dev)
+        cap = 3 * nt
+        with work_stream(dev) as work:
+            while True:
+                nbrs = torch.empty(cap, dtype=torch.int32, device=dev)
+                ctx.mesh_face_graph_dev(verts.data_ptr() if gate else None, dtype_code(verts) if gate else f3d.F64, nv, tris.data_ptr(),
+                                        index_code(tris), nt, gate, cos_crease if gate else 0.0, offsets.data_ptr(), nbrs.data_ptr() if cap else None,
+                                        cap, counts_dev.data_ptr(), work.cuda_stream)
+                counts = counts_dev.cpu().numpy()                         # the one blocking readback (two for a non-manifold overflow)
+                if counts[2]:
+                    _bad_index(ctx, work)
+                if counts[0] <= cap:
+                    break
+                cap = int(counts[0])
+    adj = (offsets, nbrs[:int(counts[0])])
+    return adj + ({'nonmanifold_edges': int(counts[1]), 'boundary_edges': int(counts[3])},) if return_stats else adj
+
+
+def segment_faces_from_votes(votes, adj, nclasses=133, threshold=0.5, filter_classes=None, normals=None, angle=None, smooth_iterations=1,
+                             self_weight=1.0, instance_classes=None, minimum_faces=1):
+    """Face votes -> smoothed classes -> face instances: (classes int64 [M], ids [M], info).
+
+    votes [M, ncols] (label_faces' ``return_votes``), adj the faces' CSR pair (face_adjacency).  With ``smooth_iterations`` > 0 the
+    classes are ``voting.smooth_segment``'s over the graph (normals float64 [M, 3] with ``angle`` in degrees gate the sums, as there);
+    with 0 they are ``segment``'s of the votes as they are: label_faces' own classes.  ``cv.split_into_instances(classes, adj,
+    nclasses, instance_classes, minimum_faces)`` then numbers the connected same-class faces: its updated classes (instances smaller
+    than minimum_faces become ``nclasses``), per-face ids and info list ('area' counts faces) are returned.  Device votes and graph
+    stay on the device up to that split, which works on host arrays; its outputs are NumPy arrays."""
+    from Fusion3DSeg.segUtils import cv, voting
+    what = 'segment_faces_from_votes'
+    shape = tuple(votes.shape) if hasattr(votes, 'shape') else np.shape(votes)
+    if len(shape) != 2:
+        raise ValueError(f'{what}: votes must be [M, ncols], got {shape}')
+    m = shape[0]
+    if not (isinstance(adj, tuple) and len(adj) == 2):
+        raise TypeError(f'{what}: adj must be a CSR pair (offsets, neighbours)')
+    if len(adj[0]) != m + 1:
+        raise ValueError(f'{what}: votes has {m} rows, the adjacency offsets {len(adj[0])} entries ({m + 1} expected)')
+    iterations, minimum_faces = int(smooth_iterations), int(minimum_faces)
+    if iterations < 0:
+        raise ValueError(f'{what}: smooth_iterations must not be negative, got {smooth_iterations}')
+    if iterations > 0:
+        classes = voting.smooth_segment(votes, adj, nclasses, threshold, filter_classes, False, normals, angle, None, None, self_weight,
+                                        iterations)
+    elif on_device(votes):
+        import torch
+        if votes.dtype != torch.float64:
+            raise TypeError(f'{what}: device votes must be float64 without smoothing, got {votes.dtype}')
+        dev = votes.device
+        v = votes.contiguous()
+        classes = torch.empty(m, dtype=torch.int64, device=dev)
+        ctx = f3d.default_context(dev.index)
+        with work_stream(dev) as work:
+            ctx.segment_votes_dev(v.data_ptr(), m, shape[1], int(nclasses), float(threshold), filter_classes, classes.data_ptr(), work.cuda_stream)
+            ctx.take_device_error(work.cuda_stream)
+    else:
+        classes = f3d.default_context().segment_votes(np.asarray(votes), nclasses, threshold, filter_classes)
+    host = tuple(a.cpu().numpy() if on_device(a) else np.asarray(a) for a in adj)
+    classes = classes.cpu().numpy() if on_device(classes) else classes
+    _, ids, info, classes = cv.split_into_instances(classes, host, nclasses, instance_classes, minimum_faces)
+    return classes, ids, info
+
+
+def segment_faces(vertices, *args, **kwargs):
+    """segment_faces(vertices, triangles, K, wxyzs, translations, masks, max_depth=10, nclasses=133, threshold=0.5,
+    filter_classes=None, smooth_iterations=1, angle=None, max_angle=None, self_weight=1.0, instance_classes=None, minimum_faces=1,
+    return_votes=False), or with a mesh in place of the first two arguments.
+
+    The mesh route from masks to face instances: ``label_faces(..., return_votes=True)``, ``face_adjacency(..., max_angle=max_angle)``,
+    ``face_normals`` when ``angle`` gates the smoothing, then ``segment_faces_from_votes`` -> (classes, ids, info) (+ the votes)."""
+    if _is_mesh(vertices):
+        return _segment_faces(*_mesh_parts(vertices), *args, **kwargs)
+    return _segment_faces(vertices, *args, **kwargs)
+
+
+def _segment_faces(vertices, triangles, K, wxyzs, translations, masks, max_depth=10, nclasses=133, threshold=0.5, filter_classes=None,
+                   smooth_iterations=1, angle=None, max_angle=None, self_weight=1.0, instance_classes=None, minimum_faces=1, return_votes=False):
+    tris = _triangles(triangles)
+    _crease(max_angle)
+    if int(smooth_iterations) < 0:
+        raise ValueError(f'segment_faces: smooth_iterations must not be negative, got {smooth_iterations}')
+    verts = _vertices(vertices, tris)
+    _, votes = _label_faces(verts, tris, K, wxyzs, translations, masks, max_depth, nclasses, threshold, filter_classes, True)
+    adj = face_adjacency(tris, vertices=verts, max_angle=max_angle)
+    gated = angle is not None and int(smooth_iterations) > 0
+    normals = _face_normals(verts, tris) if gated else None
+    out = segment_faces_from_votes(votes, adj, nclasses, threshold, filter_classes, normals, angle if gated else None, smooth_iterations,
+                                   self_weight, instance_classes, minimum_faces)
+    return out + (votes,) if return_votes else out
+
+
+# ------------------------------------------------------------------------------------------------ 8. host helpers
 def bbox_axes(corners):
     """Origin, unit x and y axes and their lengths of an oriented box from its 8 corners in Open3D's order (reference :336-357):
     the x axis is the longest of the three edges at corner 0, the y axis the middle one; the origin is the midpoint of corners

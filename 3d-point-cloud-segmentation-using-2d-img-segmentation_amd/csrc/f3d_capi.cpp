@@ -36,7 +36,7 @@ enum scratch_slot { SLOT_OBB_BOXES = 0, SLOT_SORT_PERM, SLOT_SORT_SCRATCH, SLOT_
                     SLOT_PATCH, SLOT_GRP_SCRATCH, SLOT_OBB_TABLE, SLOT_OBB_FACETS, SLOT_OBB_CAND, SLOT_FUSE_TABLES, SLOT_FUSE_CARRY,
                     SLOT_FUSE_XYZ, SLOT_FUSION, SLOT_PATCH_STATUS, SLOT_NRM, SLOT_NRM_CAMS, SLOT_QRY, SLOT_FLOOD, SLOT_COLOR,
                     SLOT_CVS_INST, SLOT_CVS_STATS, SLOT_QUADS, SLOT_GROW, SLOT_PVOTE, SLOT_PVOTE_BITS, SLOT_MESH, SLOT_ZKEY,
-                    SLOT_ZCOUNTS, SLOT_KNN, SLOT_KNN_FLAG, SLOT_PLANES, SLOT_RASTER, SLOT_ZLUT, SLOT_SMOOTH, SLOT_COUNT };
+                    SLOT_ZCOUNTS, SLOT_KNN, SLOT_KNN_FLAG, SLOT_PLANES, SLOT_RASTER, SLOT_ZLUT, SLOT_SMOOTH, SLOT_FACE_GRAPH, SLOT_COUNT };
 enum kept_slot { KEPT_GRAPH_OFFS = 0,                                      // f3d_radius_graph_count -> _fill: the offsets
                  KEPT_QRY_IN, KEPT_QRY_OFFS,                               // f3d_radius_query_count -> _fill: the queries, the offsets
                  KEPT_GRP_ORDER, KEPT_GRP_KEYS, KEPT_GRP_STARTS,           // f3d_group_by_id -> f3d_obb_extremes -> f3d_obb_hull_filter
@@ -1772,7 +1772,7 @@ static size_t tri_bytes(int itype, int64_t nt) { return (size_t)nt * 3 * (itype 
 int f3d_ctx_reserve_mesh(f3d_ctx* ctx, int64_t nv, int64_t nt) {
     int rc = enter(ctx); if (rc) return rc;
     if (!mesh_args_ok(nv, nt, F3D_I64, F3D_F64)) return fail(ctx, F3D_ERR_INVALID, "ctx_reserve_mesh: " F3D_MESH_BAD);
-    return reserve(ctx, {{SLOT_MESH, f3d_mesh_scratch_bytes(nv, nt)}});
+    return reserve(ctx, {{SLOT_MESH, f3d_mesh_scratch_bytes(nv, nt)}, {SLOT_FACE_GRAPH, f3d_face_graph_scratch_bytes(nt)}});
 }
 
 static bool mesh_vertex_map_bad(int64_t nv, int64_t nt, int itype, const void* tris, const void* offsets, const void* tri, const void* pos, const void* counts) {
@@ -1976,6 +1976,85 @@ int f3d_mesh_clean(f3d_ctx* ctx, const void* verts, int vdtype, int64_t nv, cons
     if (!st.rc) st.rc = f3d_mesh_clean_dev(ctx, io + o_verts, vdtype, nv, io + o_tris, itype, nt, remove_mask ? (const uint8_t*)(io + o_mask) : nullptr,
                                            min_triangles, min_area, io + o_nv, io + o_nt, (uint8_t*)(io + o_kv), (uint8_t*)(io + o_kt),
                                            (int64_t*)(io + o_cnt), ctx->stream);
+    return st.finish(F3D_DEVERR_MESH);
+}
+
+static bool mesh_face_frames_bad(int64_t nv, int64_t nt, int itype, int vdtype, const void* verts, const void* tris, const void* normals, const void* counts) {
+    return !mesh_args_ok(nv, nt, itype, vdtype) || !counts || (nv > 0 && !verts) || (nt > 0 && (!tris || !normals));
+}
+
+int f3d_mesh_face_frames_dev(f3d_ctx* ctx, const void* verts, int vdtype, int64_t nv, const void* tris, int itype, int64_t nt,
+                             double* normals, double* centroids, double* areas, int64_t* counts, void* stream) {
+    int rc = enter(ctx); if (rc) return rc;
+    if (mesh_face_frames_bad(nv, nt, itype, vdtype, verts, tris, normals, counts))
+        return fail(ctx, F3D_ERR_INVALID, "mesh_face_frames: " F3D_MESH_BAD);
+    F3D_HIP(ctx, f3d_launch_mesh_face_frames(verts, vdtype, nv, tris, itype, nt, normals, centroids, areas, counts, ctx->dev_err,
+                                             pick(ctx, stream)));
+    return F3D_OK;
+}
+
+int f3d_mesh_face_frames(f3d_ctx* ctx, const void* verts, int vdtype, int64_t nv, const void* tris, int itype, int64_t nt,
+                         double* normals, double* centroids, double* areas, int64_t* counts) {
+    int rc = enter(ctx); if (rc) return rc;
+    if (mesh_face_frames_bad(nv, nt, itype, vdtype, verts, tris, normals, counts))
+        return fail(ctx, F3D_ERR_INVALID, "mesh_face_frames: " F3D_MESH_BAD);
+    f3d_carve c;
+    const size_t tb = tri_bytes(itype, nt), vb = xyz_bytes((f3d_dtype)vdtype, nv);
+    const size_t o_verts = c.take(vb), o_tris = c.take(tb), o_n = c.take((size_t)nt * 24), o_c = c.take((size_t)nt * 24), o_a = c.take((size_t)nt * 8),
+                 o_cnt = c.take(32);
+    staging st(ctx);
+    char* io = (char*)st.slot(c.off);
+    if (st.rc) return st.rc;
+    st.put(io + o_verts, verts, vb);
+    st.put(io + o_tris, tris, tb);
+    st.back(normals, io + o_n, (size_t)nt * 24);
+    st.back(centroids, io + o_c, (size_t)nt * 24);
+    st.back(areas, io + o_a, (size_t)nt * 8);
+    st.back(counts, io + o_cnt, 32);
+    if (!st.rc) st.rc = f3d_mesh_face_frames_dev(ctx, io + o_verts, vdtype, nv, io + o_tris, itype, nt, (double*)(io + o_n),
+                                                 centroids ? (double*)(io + o_c) : nullptr, areas ? (double*)(io + o_a) : nullptr,
+                                                 (int64_t*)(io + o_cnt), ctx->stream);
+    return st.finish(F3D_DEVERR_MESH);
+}
+
+static bool mesh_face_graph_bad(int64_t nv, int64_t nt, int itype, int vdtype, const void* verts, const void* tris, int gate, const void* offsets,
+                                const void* neighbours, int64_t cap, const void* counts) {
+    return !mesh_args_ok(nv, nt, itype, vdtype) || !counts || !offsets || cap < 0 || (cap > 0 && !neighbours) || (nt > 0 && !tris) ||
+           (gate && nv > 0 && !verts);
+}
+#define F3D_FACE_GRAPH_BAD F3D_MESH_BAD ", cap >= 0, vertices with a gate"
+
+int f3d_mesh_face_graph_dev(f3d_ctx* ctx, const void* verts, int vdtype, int64_t nv, const void* tris, int itype, int64_t nt, int gate,
+                            double cos_crease, int64_t* offsets, int32_t* neighbours, int64_t cap, int64_t* counts, void* stream) {
+    int rc = enter(ctx); if (rc) return rc;
+    if (mesh_face_graph_bad(nv, nt, itype, vdtype, verts, tris, gate, offsets, neighbours, cap, counts))
+        return fail(ctx, F3D_ERR_INVALID, "mesh_face_graph: " F3D_FACE_GRAPH_BAD);
+    void* scratch;
+    if ((rc = ensure(ctx, SLOT_FACE_GRAPH, f3d_face_graph_scratch_bytes(nt), &scratch))) return rc;
+    F3D_HIP(ctx, f3d_launch_mesh_face_graph(verts, vdtype, nv, tris, itype, nt, gate, cos_crease, offsets, cap > 0 ? neighbours : nullptr, cap,
+                                            scratch, counts, ctx->dev_err, pick(ctx, stream)));
+    return F3D_OK;
+}
+
+int f3d_mesh_face_graph(f3d_ctx* ctx, const void* verts, int vdtype, int64_t nv, const void* tris, int itype, int64_t nt, int gate,
+                        double cos_crease, int64_t* offsets, int32_t* neighbours, int64_t cap, int64_t* counts) {
+    int rc = enter(ctx); if (rc) return rc;
+    if (mesh_face_graph_bad(nv, nt, itype, vdtype, verts, tris, gate, offsets, neighbours, cap, counts))
+        return fail(ctx, F3D_ERR_INVALID, "mesh_face_graph: " F3D_FACE_GRAPH_BAD);
+    f3d_carve c;
+    const size_t tb = tri_bytes(itype, nt), vb = gate ? xyz_bytes((f3d_dtype)vdtype, nv) : 0;
+    const size_t o_verts = c.take(vb), o_tris = c.take(tb), o_offs = c.take((size_t)(nt + 1) * 8), o_nb = c.take((size_t)cap * 4), o_cnt = c.take(32);
+    staging st(ctx);
+    char* io = (char*)st.slot(c.off);
+    if (st.rc) return st.rc;
+    st.put(io + o_verts, verts, vb);
+    st.put(io + o_tris, tris, tb);
+    st.put(io + o_nb, neighbours, (size_t)cap * 4);           // what comes back when nnz > cap: the caller's own entries
+    st.back(offsets, io + o_offs, (size_t)(nt + 1) * 8);
+    st.back(neighbours, io + o_nb, (size_t)cap * 4);
+    st.back(counts, io + o_cnt, 32);
+    if (!st.rc) st.rc = f3d_mesh_face_graph_dev(ctx, gate ? io + o_verts : nullptr, vdtype, nv, io + o_tris, itype, nt, gate, cos_crease,
+                                                (int64_t*)(io + o_offs), (int32_t*)(io + o_nb), cap, (int64_t*)(io + o_cnt), ctx->stream);
     return st.finish(F3D_DEVERR_MESH);
 }
 

@@ -593,6 +593,16 @@ hipError_t f3d_launch_mesh_clusters(const void* verts, int vdtype, int64_t nv, c
 hipError_t f3d_launch_mesh_clean(const void* verts, int vdtype, int64_t nv, const void* tris, int itype, int64_t nt, const uint8_t* remove_mask,
                                  int64_t min_triangles, double min_area, void* new_verts, void* new_tris, uint8_t* kept_v, uint8_t* kept_t,
                                  void* scratch, int64_t* counts, int* err, hipStream_t s);
+// face frames and the face graph (f3d_mesh.hip, include/f3d.h f3d_mesh_face_frames / f3d_mesh_face_graph): normals / centroids float64
+// [nt, 3], areas float64 [nt] (the last two may be NULL; no scratch).  The graph: counts = {nnz, non-manifold edges, bad index, boundary
+// edges}; verts may be NULL without a gate; neighbours (room for cap entries, may be NULL) is written only when nnz <= cap.
+// scratch: f3d_face_graph_scratch_bytes(nt), whatever nv is
+size_t f3d_face_graph_scratch_bytes(int64_t nt);
+hipError_t f3d_launch_mesh_face_frames(const void* verts, int vdtype, int64_t nv, const void* tris, int itype, int64_t nt, double* normals,
+                                       double* centroids, double* areas, int64_t* counts, int* err, hipStream_t s);
+hipError_t f3d_launch_mesh_face_graph(const void* verts, int vdtype, int64_t nv, const void* tris, int itype, int64_t nt, int gate,
+                                      double cos_crease, int64_t* offsets, int32_t* neighbours, int64_t cap, void* scratch, int64_t* counts,
+                                      int* err, hipStream_t s);
 
 // point-splat z-buffer and the visibility-tested forward vote (f3d_render.hip).  zkey: uint64 [nv, h, w] depth keys of the nv views of
 // a pass (views_dev / masks point at the pass's first view); counts (device uint64 [3], may be NULL) += {samples, cells covered,

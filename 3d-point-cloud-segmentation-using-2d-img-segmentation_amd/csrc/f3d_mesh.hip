@@ -180,19 +180,25 @@ __global__ __launch_bounds__(MB) void k_mesh_keep_out(const void* __restrict__ v
 }
 
 // ---- cluster ----------------------------------------------------------------------------------------------------------
+// the corners of face f widened to float64 and c = cross(p0 - p1, p0 - p2), every product and difference rounded alone
+__device__ __forceinline__ void face_cross(const void* __restrict__ verts, int vdtype, const void* __restrict__ tris, int itype, int64_t f,
+                                           double p[3][3], double c[3]) {
+    for (int j = 0; j < 3; ++j) {
+        const int64_t v = tri_at(tris, itype, 3 * f + j);
+        for (int k = 0; k < 3; ++k) p[j][k] = coord(verts, vdtype, 3 * v + k);
+    }
+    const double a0 = p[0][0] - p[1][0], a1 = p[0][1] - p[1][1], a2 = p[0][2] - p[1][2];
+    const double b0 = p[0][0] - p[2][0], b1 = p[0][1] - p[2][1], b2 = p[0][2] - p[2][2];
+    c[0] = a1 * b2 - a2 * b1; c[1] = a2 * b0 - a0 * b2; c[2] = a0 * b1 - a1 * b0;
+}
+
 __global__ __launch_bounds__(MB) void k_mesh_area(const void* __restrict__ verts, int vdtype, const void* __restrict__ tris, int itype,
                                                   int64_t nt, const int64_t* counts, double* __restrict__ area) {
     if (counts[2]) return;
     MESH_LOOP(f, nt) {
-        double p[3][3];
-        for (int j = 0; j < 3; ++j) {
-            const int64_t v = tri_at(tris, itype, 3 * f + j);
-            for (int c = 0; c < 3; ++c) p[j][c] = coord(verts, vdtype, 3 * v + c);
-        }
-        const double a0 = p[0][0] - p[1][0], a1 = p[0][1] - p[1][1], a2 = p[0][2] - p[1][2];
-        const double b0 = p[0][0] - p[2][0], b1 = p[0][1] - p[2][1], b2 = p[0][2] - p[2][2];
-        const double cx = a1 * b2 - a2 * b1, cy = a2 * b0 - a0 * b2, cz = a0 * b1 - a1 * b0;
-        area[f] = 0.5 * sqrt((cx * cx + cy * cy) + cz * cz);
+        double p[3][3], c[3];
+        face_cross(verts, vdtype, tris, itype, f, p, c);
+        area[f] = 0.5 * sqrt((c[0] * c[0] + c[1] * c[1]) + c[2] * c[2]);
     }
 }
 
@@ -476,4 +482,197 @@ hipError_t f3d_launch_mesh_clean(const void* verts, int vdtype, int64_t nv, cons
                        counts, kept_t, kept_v);
     F3D_TRY(hipGetLastError());
     return mesh_compact(L, base, verts, vdtype, nv, tris, itype, nt, kept_v, 0, kept_t, new_tris, nullptr, new_verts, counts, s);
+}
+
+// ---- face graph -------------------------------------------------------------------------------------------------------
+// The cluster path's edge keys, sorted with the half-edge slot s = 3 f + j as the value (bit 31: the face runs through the edge
+// from its lower to its higher vertex).  The sort is stable and slots ascend with f, so a run of equal keys lists its faces in
+// ascending order and a face that holds the edge twice sits on adjacent entries.  Every sorted position scatters its run
+// [first, last) back to its slot (k_fg_runs); a face's row is then the three-way merge, duplicates skipped, of the runs of its
+// three slots (fg_row), once to count and once to fill.  A run of k faces costs O(k) per member: a fan of k faces on one edge is
+// quadratic in k, as is its output.
+namespace {
+
+constexpr uint32_t FG_SLOT = 0x7fffffffu;           // the slot of a sorted value; bit 31 is the direction
+constexpr uint32_t FG_END = 0xffffffffu;
+
+__global__ __launch_bounds__(MB) void k_face_frames(const void* __restrict__ verts, int vdtype, const void* __restrict__ tris, int itype,
+                                                    int64_t nt, const int64_t* counts, double* __restrict__ normals,
+                                                    double* __restrict__ centroids, double* __restrict__ areas) {
+    if (counts[2]) return;
+    MESH_LOOP(f, nt) {
+        double p[3][3], c[3];
+        face_cross(verts, vdtype, tris, itype, f, p, c);
+        const double len = sqrt((c[0] * c[0] + c[1] * c[1]) + c[2] * c[2]);
+        const bool ok = len > 0.0 && len < INFINITY;
+        for (int k = 0; k < 3; ++k) normals[3 * f + k] = ok ? c[k] / len : 0.0;
+        if (centroids) for (int k = 0; k < 3; ++k) centroids[3 * f + k] = ((p[0][k] + p[1][k]) + p[2][k]) / 3.0;
+        if (areas) areas[f] = 0.5 * len;
+    }
+}
+
+// winding v0 -> v1 -> v2 -> v0: edge (0,1) runs v0 -> v1, edge (0,2) runs v2 -> v0, edge (1,2) runs v1 -> v2
+__global__ __launch_bounds__(MB) void k_fg_keys(const void* __restrict__ tris, int itype, int64_t nt, int b, const int64_t* counts,
+                                                uint64_t* __restrict__ keys, uint32_t* __restrict__ vals) {
+    if (counts[2]) return;
+    MESH_LOOP(f, nt) {
+        const uint64_t v0 = (uint64_t)tri_at(tris, itype, 3 * f), v1 = (uint64_t)tri_at(tris, itype, 3 * f + 1),
+                       v2 = (uint64_t)tri_at(tris, itype, 3 * f + 2);
+        const uint32_t s = (uint32_t)(3 * f);
+        keys[3 * f] = edge_key(v0, v1, b);     vals[3 * f] = s | (uint32_t)(v0 < v1) << 31;
+        keys[3 * f + 1] = edge_key(v0, v2, b); vals[3 * f + 1] = (s + 1) | (uint32_t)(v2 < v0) << 31;
+        keys[3 * f + 2] = edge_key(v1, v2, b); vals[3 * f + 2] = (s + 2) | (uint32_t)(v1 < v2) << 31;
+    }
+}
+
+// bounds[slot] = first | last << 32 | direction << 63 of the slot's run in the sorted order; the head of a run counts it as a
+// boundary edge (one half-edge, counts[3]) or a non-manifold one (more than two, counts[1])
+__global__ __launch_bounds__(MB) void k_fg_runs(const uint64_t* __restrict__ keys, const uint32_t* __restrict__ vals, int64_t n3,
+                                                int64_t* counts, uint64_t* __restrict__ bounds) {
+    if (counts[2]) return;
+    unsigned long long boundary = 0, fans = 0;
+    MESH_LOOP(i, n3) {
+        const uint64_t k = keys[i];
+        int64_t lo = i, hi = i + 1;
+        while (lo > 0 && keys[lo - 1] == k) --lo;
+        while (hi < n3 && keys[hi] == k) ++hi;
+        const uint32_t v = vals[i];
+        bounds[v & FG_SLOT] = (uint64_t)lo | (uint64_t)hi << 32 | (uint64_t)(v >> 31) << 63;
+        if (lo == i) { boundary += hi - lo == 1; fans += hi - lo > 2; }
+    }
+    for (int o = 32; o; o >>= 1) { boundary += __shfl_xor(boundary, o); fans += __shfl_xor(fans, o); }
+    if ((threadIdx.x & 63) == 0) {
+        if (fans) atomicAdd(reinterpret_cast<unsigned long long*>(counts + 1), fans);
+        if (boundary) atomicAdd(reinterpret_cast<unsigned long long*>(counts + 3), boundary);
+    }
+}
+
+// Row f: every face g != f, ascending, that shares an edge with f through which the pair passes -> emit(g).  Through an edge the pair
+// passes when there is no gate, or when s * dot(nf, ng) >= cos_crease, s = +1 where the two faces run through the edge in opposite
+// directions (consistent orientation) and -1 where they run the same way; a face that holds the edge twice counts by its first entry.
+template <class Emit>
+__device__ __forceinline__ void fg_row(int64_t f, const uint32_t* __restrict__ vals, const uint64_t* __restrict__ bounds,
+                                       const double* __restrict__ normals, double cos_crease, Emit emit) {
+    uint32_t p[3], e[3], face[3], dir[3], own[3];
+#pragma unroll
+    for (int j = 0; j < 3; ++j) {
+        const uint64_t w = bounds[3 * f + j];
+        p[j] = (uint32_t)w; e[j] = (uint32_t)(w >> 32) & FG_SLOT; own[j] = (uint32_t)(w >> 63);
+        const uint32_t v = vals[p[j]];                                  // a slot's run holds the slot: never empty
+        face[j] = (v & FG_SLOT) / 3u; dir[j] = v >> 31;
+    }
+    double nf[3] = {0.0, 0.0, 0.0};
+    if (normals) for (int k = 0; k < 3; ++k) nf[k] = normals[3 * f + k];
+    for (;;) {
+        const uint32_t g = min(face[0], min(face[1], face[2]));
+        if (g == FG_END) break;
+        bool pass = !normals, have = false;
+        double dot = 0.0;
+#pragma unroll
+        for (int j = 0; j < 3; ++j) {
+            if (face[j] != g) continue;
+            if (normals && g != (uint32_t)f) {
+                if (!have) {
+                    const double* ng = normals + 3 * (int64_t)g;
+                    dot = (nf[0] * ng[0] + nf[1] * ng[1]) + nf[2] * ng[2];
+                    have = true;
+                }
+                pass |= (dir[j] != own[j] ? dot : -dot) >= cos_crease;
+            }
+            uint32_t next = FG_END, d = 0;
+            while (++p[j] < e[j]) {
+                const uint32_t v = vals[p[j]];
+                if ((v & FG_SLOT) / 3u != g) { next = (v & FG_SLOT) / 3u; d = v >> 31; break; }
+            }
+            face[j] = next; dir[j] = d;
+        }
+        if (pass && g != (uint32_t)f) emit((int32_t)g);
+    }
+}
+
+// FILL == false: rowoff[f] = the length of row f, rowoff[nt] = 0 (the scan turns them into the offsets).  FILL == true: the rows,
+// unless they need more than `cap` entries
+template <bool FILL>
+__global__ __launch_bounds__(MB) void k_fg_rows(const uint32_t* __restrict__ vals, const uint64_t* __restrict__ bounds,
+                                                const double* __restrict__ normals, double cos_crease, int64_t nt, const int64_t* counts,
+                                                int64_t* rowoff, int32_t* __restrict__ neighbours, int64_t cap) {
+    if (counts[2]) return;
+    if (FILL && rowoff[nt] > cap) return;
+    MESH_LOOP(f, nt + (FILL ? 0 : 1)) {
+        int64_t n = 0;
+        if (f < nt) {
+            int32_t* row = FILL ? neighbours + rowoff[f] : nullptr;
+            fg_row(f, vals, bounds, normals, cos_crease, [&](int32_t g) { if (FILL) row[n] = g; ++n; });
+        }
+        if (!FILL) rowoff[f] = n;
+    }
+}
+
+__global__ __launch_bounds__(MB) void k_fg_offsets(const int64_t* __restrict__ rowoff, int64_t nt, int64_t* counts, int64_t* __restrict__ offsets) {
+    if (counts[2]) return;
+    MESH_LOOP(i, nt + 1) {
+        offsets[i] = rowoff[i];
+        if (i == nt) counts[0] = rowoff[nt];
+    }
+}
+
+struct fg_layout { size_t keys_a, keys_b, vals_a, vals_b, normals, rowoff, temp, total, temp_bytes; };
+
+fg_layout fg_layout_for(int64_t nt) {
+    if (nt < 1) nt = 1;
+    fg_layout L;
+    const size_t n3 = (size_t)nt * 3;
+    size_t a = 0, b = 0;
+    (void)rocprim::radix_sort_pairs(nullptr, a, (uint64_t*)nullptr, (uint64_t*)nullptr, (uint32_t*)nullptr, (uint32_t*)nullptr, n3, 0u, 64u);
+    (void)rocprim::exclusive_scan(nullptr, b, (int64_t*)nullptr, (int64_t*)nullptr, (int64_t)0, (size_t)nt + 1, rocprim::plus<int64_t>());
+    L.temp_bytes = (a > b ? a : b) + 256;
+    f3d_carve k;
+    L.keys_a = k.take(n3 * 8); L.keys_b = k.take(n3 * 8); L.vals_a = k.take(n3 * 4); L.vals_b = k.take(n3 * 4);
+    L.normals = k.take((size_t)nt * 24); L.rowoff = k.take((size_t)(nt + 1) * 8);
+    L.temp = k.take(L.temp_bytes);
+    L.total = k.off;
+    return L;
+}
+
+}  // namespace
+
+size_t f3d_face_graph_scratch_bytes(int64_t nt) { return fg_layout_for(nt).total; }
+
+hipError_t f3d_launch_mesh_face_frames(const void* verts, int vdtype, int64_t nv, const void* tris, int itype, int64_t nt, double* normals,
+                                       double* centroids, double* areas, int64_t* counts, int* err, hipStream_t s) {
+    if (!mesh_sizes_ok(nv, nt)) return hipErrorInvalidValue;
+    F3D_TRY(mesh_begin(tris, itype, nt, nv, counts, err, s));
+    if (nt == 0) return hipSuccess;
+    hipLaunchKernelGGL(k_face_frames, grid_of(nt), dim3(MB), 0, s, verts, vdtype, tris, itype, nt, counts, normals, centroids, areas);
+    return hipGetLastError();
+}
+
+hipError_t f3d_launch_mesh_face_graph(const void* verts, int vdtype, int64_t nv, const void* tris, int itype, int64_t nt, int gate,
+                                      double cos_crease, int64_t* offsets, int32_t* neighbours, int64_t cap, void* scratch, int64_t* counts,
+                                      int* err, hipStream_t s) {
+    if (!mesh_sizes_ok(nv, nt) || cap < 0) return hipErrorInvalidValue;
+    F3D_TRY(mesh_begin(tris, itype, nt, nv, counts, err, s));
+    if (nt == 0) return hipMemsetAsync(offsets, 0, 8, s);
+    const fg_layout L = fg_layout_for(nt);
+    char* base = reinterpret_cast<char*>(scratch);
+    uint64_t *ka = reinterpret_cast<uint64_t*>(base + L.keys_a), *kb = reinterpret_cast<uint64_t*>(base + L.keys_b);
+    uint32_t *va = reinterpret_cast<uint32_t*>(base + L.vals_a), *vb = reinterpret_cast<uint32_t*>(base + L.vals_b);
+    double* normals = gate ? reinterpret_cast<double*>(base + L.normals) : nullptr;
+    int64_t* rowoff = reinterpret_cast<int64_t*>(base + L.rowoff);
+    const dim3 g(grid_of(nt + 1)), g3(grid_of(3 * nt)), b(MB);
+    const int bits = f3d_bits_for(nv, 1);
+    hipLaunchKernelGGL(k_fg_keys, g, b, 0, s, tris, itype, nt, bits, counts, ka, va);
+    if (gate) hipLaunchKernelGGL(k_face_frames, g, b, 0, s, verts, vdtype, tris, itype, nt, counts, normals, (double*)nullptr, (double*)nullptr);
+    F3D_TRY(hipGetLastError());
+    size_t tb = L.temp_bytes;
+    F3D_TRY(rocprim::radix_sort_pairs(base + L.temp, tb, ka, kb, va, vb, (size_t)(3 * nt), 0u, (unsigned)(2 * bits), s));
+    uint64_t* bounds = ka;                                                  // the unsorted keys are done with
+    hipLaunchKernelGGL(k_fg_runs, g3, b, 0, s, kb, vb, 3 * nt, counts, bounds);
+    hipLaunchKernelGGL(k_fg_rows<false>, g, b, 0, s, vb, bounds, normals, cos_crease, nt, counts, rowoff, (int32_t*)nullptr, cap);
+    F3D_TRY(hipGetLastError());
+    tb = L.temp_bytes;
+    F3D_TRY(rocprim::exclusive_scan(base + L.temp, tb, rowoff, rowoff, (int64_t)0, (size_t)(nt + 1), rocprim::plus<int64_t>(), s));
+    hipLaunchKernelGGL(k_fg_offsets, g, b, 0, s, rowoff, nt, counts, offsets);
+    if (neighbours) hipLaunchKernelGGL(k_fg_rows<true>, g, b, 0, s, vb, bounds, normals, cos_crease, nt, counts, rowoff, neighbours, cap);
+    return hipGetLastError();
 }

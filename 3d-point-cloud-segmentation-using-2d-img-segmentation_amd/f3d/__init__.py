@@ -180,6 +180,10 @@ def library():
         'f3d_mesh_triangle_clusters_dev': (i32, [vp, vp, i32, i64, vp, i32, i64, vp, vp, vp, vp, vp, vp]),
         'f3d_mesh_clean': (i32, [vp, vp, i32, i64, vp, i32, i64, vp, i64, dbl, vp, vp, vp, vp, vp]),
         'f3d_mesh_clean_dev': (i32, [vp, vp, i32, i64, vp, i32, i64, vp, i64, dbl, vp, vp, vp, vp, vp, vp]),
+        'f3d_mesh_face_frames': (i32, [vp, vp, i32, i64, vp, i32, i64, vp, vp, vp, vp]),
+        'f3d_mesh_face_frames_dev': (i32, [vp, vp, i32, i64, vp, i32, i64, vp, vp, vp, vp, vp]),
+        'f3d_mesh_face_graph': (i32, [vp, vp, i32, i64, vp, i32, i64, i32, dbl, vp, vp, i64, vp]),
+        'f3d_mesh_face_graph_dev': (i32, [vp, vp, i32, i64, vp, i32, i64, i32, dbl, vp, vp, i64, vp, vp]),
         'f3d_ctx_reserve_mesh': (i32, [vp, i64, i64]),
         'f3d_extract_planes': (i32, [vp, vp, i32, i64, vp, vp, vp, dbl, dbl, dbl, dbl, i64, i64, i64, vp, vp, vp, vp, vp]),
         'f3d_extract_planes_dev': (i32, [vp, vp, i32, i64, vp, vp, vp, dbl, dbl, dbl, dbl, i64, i64, i64, vp, vp, vp, vp, vp, vp]),
@@ -902,6 +906,33 @@ class Context:
                                              int(min_triangles), float(min_area), _ptr(nvs), _ptr(nts), _ptr(kv), _ptr(kt), _ptr(counts)))
         return nvs[:counts[1]].copy(), nts[:counts[0]].copy(), kv, kt
 
+    def mesh_face_frames(self, verts, tris, want_centroids=False, want_areas=False):
+        """-> (normals float64 [M, 3], centroids float64 [M, 3] or None, areas float64 [M] or None) (f3d.h f3d_mesh_face_frames)."""
+        nt, nv = len(tris), len(verts)
+        normals, counts = np.empty((nt, 3), np.float64), np.zeros(4, np.int64)
+        centroids = np.empty((nt, 3), np.float64) if want_centroids else None
+        areas = np.empty(nt, np.float64) if want_areas else None
+        self._check(self._lib.f3d_mesh_face_frames(self._h, _ptr(verts), dtype_code(verts), nv, _ptr(tris), index_code(tris), nt, _ptr(normals),
+                                                   _ptr(centroids), _ptr(areas), _ptr(counts)))
+        return normals, centroids, areas
+
+    def mesh_face_graph(self, tris, nvertices, verts=None, cos_crease=None, offsets=None, neighbours=None):
+        """The face graph (f3d.h f3d_mesh_face_graph), gated when cos_crease is given (it needs verts) -> (offsets int64 [M + 1],
+        neighbours int32 [cap], counts int64 [4]).  neighbours (default: 3 M entries) is filled only when counts[0] <= its length."""
+        nt = len(tris)
+        gate = cos_crease is not None
+        if gate and verts is None:
+            raise ValueError('mesh_face_graph: a gate needs the vertices')
+        if offsets is None:
+            offsets = np.empty(nt + 1, np.int64)
+        if neighbours is None:
+            neighbours = np.empty(3 * nt, np.int32)
+        counts = np.zeros(4, np.int64)
+        self._check(self._lib.f3d_mesh_face_graph(self._h, _ptr(verts) if gate else None, dtype_code(verts) if gate else F64, int(nvertices), _ptr(tris),
+                                                  index_code(tris), nt, int(gate), float(cos_crease) if gate else 0.0, _ptr(offsets),
+                                                  _ptr(neighbours) if len(neighbours) else None, len(neighbours), _ptr(counts)))
+        return offsets, neighbours, counts
+
     def extract_planes(self, points, offsets, neighbours, normals, cos_angle, offset, dist, max_variation, min_points, max_rounds,
                        max_planes, want_normals=False):
         """Plane table of a cloud over its adjacency (include/f3d.h f3d_extract_planes).  points float64 / float32 [n, 3]; offsets /
@@ -1235,6 +1266,17 @@ class Context:
                        kept_v_ptr, kept_t_ptr, counts_ptr, stream=None):
         self._check(self._lib.f3d_mesh_clean_dev(self._h, verts_ptr, vdtype, int(nv), tris_ptr, itype, int(nt), remove_mask_ptr, int(min_triangles),
                                                  float(min_area), new_verts_ptr, new_tris_ptr, kept_v_ptr, kept_t_ptr, counts_ptr, stream))
+
+    def mesh_face_frames_dev(self, verts_ptr, vdtype, nv, tris_ptr, itype, nt, normals_ptr, centroids_ptr, areas_ptr, counts_ptr, stream=None):
+        """f3d_mesh_face_frames_dev: centroids_ptr / areas_ptr may be None."""
+        self._check(self._lib.f3d_mesh_face_frames_dev(self._h, verts_ptr, vdtype, int(nv), tris_ptr, itype, int(nt), normals_ptr, centroids_ptr,
+                                                       areas_ptr, counts_ptr, stream))
+
+    def mesh_face_graph_dev(self, verts_ptr, vdtype, nv, tris_ptr, itype, nt, gate, cos_crease, offsets_ptr, neighbours_ptr, cap, counts_ptr,
+                            stream=None):
+        """f3d_mesh_face_graph_dev: verts_ptr may be None without a gate; neighbours (cap entries) is written only when counts[0] <= cap."""
+        self._check(self._lib.f3d_mesh_face_graph_dev(self._h, verts_ptr, vdtype, int(nv), tris_ptr, itype, int(nt), int(gate), float(cos_crease),
+                                                      offsets_ptr, neighbours_ptr, int(cap), counts_ptr, stream))
 
     def extract_planes_dev(self, xyz_ptr, dtype, n, offsets_ptr, neighbours_ptr, normals_ptr, cos_angle, offset, dist, max_variation,
                            min_points, max_rounds, max_planes, labels_ptr, planes_ptr, corners_ptr, counts_ptr, normals_out_ptr=None,

@@ -524,7 +524,7 @@ int f3d_door_window_quads_dev(f3d_ctx* ctx, const double* points, int64_t n, con
 int f3d_ctx_reserve_quads(f3d_ctx* ctx, int64_t n, int k, int64_t nt);
 
 /* ---- segUtils/meshUtils.py: face filtering, vertex maps, triangle clusters (reference :235-333, :360-375) ------------ */
-/* Common to the five entries below.  tris: [nt, 3] vertex indices, C-contiguous, int64 (F3D_I64) or int32 (F3D_I32); face
+/* Common to the mesh entries below. tris: [nt, 3] vertex indices, C-contiguous, int64 (F3D_I64) or int32 (F3D_I32); face
  * outputs have the same type.  verts: [nv, 3] of F3D_F64 or F3D_F32; vertex outputs have the same type.  Masks and flags are
  * bytes (0 / not 0 in, 0 / 1 out).  nv < 2^31 and 3 * nt < 2^31.  The slot of a triangle corner is s = 3 * f + j.
  * Outputs whose length depends on the data are sized by the caller for the largest case given below; counts (int64 [4])
@@ -587,6 +587,42 @@ int f3d_mesh_clean(f3d_ctx* ctx, const void* verts, int vdtype, int64_t nv, cons
 int f3d_mesh_clean_dev(f3d_ctx* ctx, const void* verts, int vdtype, int64_t nv, const void* tris, int itype, int64_t nt,
                        const uint8_t* remove_mask, int64_t min_triangles, double min_area, void* new_verts, void* new_tris,
                        uint8_t* kept_v, uint8_t* kept_t, int64_t* counts, void* stream);
+
+/* Face frames (no reference counterpart): normals float64 [nt, 3], centroids float64 [nt, 3] (may be NULL), areas float64 [nt]
+ * (may be NULL).  float32 vertices are widened exactly; every product, sum and difference is rounded alone:
+ *   c = cross(p0 - p1, p0 - p2), len = sqrt((cx*cx + cy*cy) + cz*cz), area = 0.5 * len (tri_area of f3d_mesh_triangle_clusters,
+ *   bit for bit), normal = c / len per component when len is finite and > 0 and (0, 0, 0) otherwise (a degenerate face, a
+ *   non-finite vertex, a cross product whose length underflows to 0 or overflows), centroid = ((p0 + p1) + p2) / 3.0.
+ * counts = {0, 0, bad-index flag, 0}.  No scratch. */
+int f3d_mesh_face_frames(f3d_ctx* ctx, const void* verts, int vdtype, int64_t nv, const void* tris, int itype, int64_t nt,
+                         double* normals, double* centroids, double* areas, int64_t* counts);
+int f3d_mesh_face_frames_dev(f3d_ctx* ctx, const void* verts, int vdtype, int64_t nv, const void* tris, int itype, int64_t nt,
+                             double* normals, double* centroids, double* areas, int64_t* counts, void* stream);
+
+/* The face graph (no reference counterpart): the adjacency of the faces over shared edges as a CSR, offsets int64 [nt + 1] and
+ * neighbours int32 [cap], the pair that f3d_smooth_votes, f3d_smooth_segment, f3d_components_same_class, f3d_extract_planes and
+ * split_into_instances take.  A face's edges are the unordered pairs (min, max) of its corners (0,1), (0,2), (1,2), the edges of
+ * f3d_mesh_triangle_clusters: (v, v) is an edge like any other, and an edge held by k faces connects all k.  Row f lists every
+ * face g != f that shares at least one edge with f through which the pair passes, in strictly ascending g: no duplicates, never
+ * f itself.  offsets is the exclusive scan of the row lengths, offsets[nt] = counts[0] = nnz.
+ *   gate == 0: every shared edge passes; verts may be NULL (nv still bounds the indices).
+ *   gate != 0: the pair passes through edge e iff s * ((nf0*ng0 + nf1*ng1) + nf2*ng2) >= cos_crease, n the normals of
+ *     f3d_mesh_face_frames, s = +1 when the two faces run through e in opposite directions of their windings v0 -> v1 -> v2 -> v0
+ *     (consistently oriented neighbours) and -1 when they run through it the same way; a face that holds e twice (degenerate,
+ *     normal 0) counts by its first occurrence.  So the test is the dihedral one whatever the winding of either face: a flat sheet
+ *     with randomly flipped faces stays connected, a sheet folded back on itself is cut.  A NaN makes the comparison false.
+ * The relation is symmetric by construction (the test reads the same from f and from g), which is what split_into_instances and
+ * f3d_components_same_class require of their adjacency.
+ * counts = {nnz, distinct edges held by more than two half-edges (non-manifold), bad-index flag, distinct edges held by exactly one
+ * half-edge (boundary)}.  When nnz > cap, offsets and counts are written, neighbours is left untouched (it may be NULL when cap
+ * is 0) and the call succeeds: call again with room.  cap = 3 nt suffices when no edge has more than two faces.
+ * Cost: one radix sort of the 3 nt edge keys, then per face a merge of the runs of its three keys; a run of k faces costs O(k) per
+ * member, so k faces fanned around one edge cost (and produce) O(k^2).
+ * Scratch grows with nt alone (f3d_ctx_reserve_mesh sizes it). */
+int f3d_mesh_face_graph(f3d_ctx* ctx, const void* verts, int vdtype, int64_t nv, const void* tris, int itype, int64_t nt, int gate,
+                        double cos_crease, int64_t* offsets, int32_t* neighbours, int64_t cap, int64_t* counts);
+int f3d_mesh_face_graph_dev(f3d_ctx* ctx, const void* verts, int vdtype, int64_t nv, const void* tris, int itype, int64_t nt, int gate,
+                            double cos_crease, int64_t* offsets, int32_t* neighbours, int64_t cap, int64_t* counts, void* stream);
 /* Sizes the scratch of the f3d_mesh_*_dev entries for meshes of up to nv vertices and nt triangles. */
 int f3d_ctx_reserve_mesh(f3d_ctx* ctx, int64_t nv, int64_t nt);
 
