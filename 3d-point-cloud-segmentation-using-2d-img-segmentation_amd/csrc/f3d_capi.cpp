@@ -70,6 +70,7 @@ struct f3d_ctx {
     int32_t filter_host[F3D_MAX_FILTER];  // its staging copy: must outlive the asynchronous upload
     unsigned long long* count_dev;
     f3d_codebook* codebook;             // vote-bin code book of the fused path (device)
+    f3d_fuse_occupancy fuse_occ;        // blocks per CU of the k_fuse instances launched so far (asked of the runtime once each)
     // radius graph: the search of the last count pass (the fill pass must follow it for the same cloud); graph_kept: that pass was
     // f3d_radius_graph_count, whose offsets KEPT_GRAPH_OFFS holds
     f3d_gridsearch graph;
@@ -744,7 +745,7 @@ int f3d_project_vote_argmax_dev(f3d_ctx* ctx, const void* xyz, f3d_dtype dtype, 
     job.xyz = xyz; job.dtype = dtype; job.n = n; job.perm = perm; job.gather = (flags & F3D_FUSE_GATHER) && perm;
     job.views_dev = views_dev; job.nviews = nviews; job.v0 = 0; job.v1 = nviews; job.masks = masks; job.h = h; job.w = w;
     job.nclasses = nclasses; job.threshold = threshold; job.classes = classes; job.votes = votes_u16; job.err = ctx->dev_err;
-    job.todo = sc.todo; job.cb = ctx->codebook; job.tables = sc.tables;
+    job.todo = sc.todo; job.cb = ctx->codebook; job.tables = sc.tables; job.occ = &ctx->fuse_occ;
     if (sort) {
         if ((rc = sort_into_perm(ctx, xyz, dtype, n, sc, job.stream, &job.perm, coded ? &job : nullptr))) return rc;
         job.gather = true;
@@ -836,6 +837,7 @@ static int fuse_chunk_impl(f3d_ctx* ctx, f3d_fuse_job& j, const uint8_t* coded, 
     j.cmasks = coded ? coded : (const uint8_t*)sc.tm;          // the exchange delivered coded planes: no coding, no raw masks, the exact tier reads codes
     if (!coded) F3D_HIP(ctx, f3d_launch_code_planes(j.masks + (size_t)v_begin * h * w, (uint8_t*)sc.tm + (size_t)v_begin * plane, v_end - v_begin, h, w, ctx->codebook, s));
     j.err = ctx->dev_err; j.todo = sc.todo; j.lay = ctx->chunk.lay; j.cb = ctx->codebook; j.tables = sc.tables; j.carry = (uint32_t*)sc.carry; j.xyz_keep = sc.keep;
+    j.occ = &ctx->fuse_occ;
     F3D_HIP(ctx, f3d_launch_fuse_setup(j, ctx->codebook, false));
     F3D_HIP(ctx, f3d_launch_fuse(j));
     if (sc.keep) { ctx->chunk.xyz = sc.keep; ctx->chunk.gather = 0; }

@@ -22,6 +22,7 @@
 #include "f3d_math.h"
 #include "f3d_kernels.h"
 #include "f3d_fuse_blocks.h"
+#include "f3d_fuse_deal.h"
 #include <cstdlib>
 
 #pragma clang fp contract(off)
@@ -40,10 +41,21 @@
 #define F3D_STORE_CLASS(p, v) (reinterpret_cast<uint8_t*>(classes)[(p) - classes] = (uint8_t)(v))
 #elif defined(F3D_EXP_STORE) && F3D_EXP_STORE == 4        // ... one byte, non-temporal
 #define F3D_STORE_CLASS(p, v) __builtin_nontemporal_store((uint8_t)(v), reinterpret_cast<uint8_t*>(classes) + ((p) - classes))
+#elif defined(F3D_EXP_STAMP)                              // ... the head of the label vector holds k_fuse's block stamps (below)
+#define F3D_STORE_CLASS(p, v) do { if ((p) - classes >= F3D_STAMP_WORDS) __builtin_nontemporal_store((int64_t)(v), (p)); } while (0)
 #elif F3D_NT_CLASSES
 #define F3D_STORE_CLASS(p, v) __builtin_nontemporal_store((int64_t)(v), (p))
 #else
 #define F3D_STORE_CLASS(p, v) (*(p) = (v))
+#endif
+// F3D_EXP_STAMP (timing experiment, results wrong; scripts/fuse_deal_stamps.py reads it back): every block of the k_fuse instance the
+// code book selects leaves four words at classes[4 * blockIdx.x]: its index, the 100 MHz wall clock at entry, at its first tile's turn
+// of the loop and at the exit of its last wave.  No label is stored below F3D_STAMP_WORDS, and a cloud shorter than that is not stamped.
+#define F3D_STAMP_WORDS (4 * 8192)
+#if defined(F3D_EXP_STAMP)
+#define F3D_STAMP_EXIT() do { if (n >= F3D_STAMP_WORDS && lane == 0) atomicMax(reinterpret_cast<unsigned long long*>(classes) + 4 * blockIdx.x + 3, (unsigned long long)wall_clock64()); } while (0)
+#else
+#define F3D_STAMP_EXIT() ((void)0)
 #endif
 
 namespace {
@@ -547,9 +559,6 @@ __device__ __forceinline__ void wave_box(float& lo0, float& hi0, float& lo1, flo
 #ifndef F3D_VTAB_GLOBAL
 #define F3D_VTAB_GLOBAL 0                // 1: M, t, mnorm of the views always from the transposed global table (7.7 KB less LDS per block)
 #endif
-#ifndef F3D_XCD_CHUNK_LOG2
-#define F3D_XCD_CHUNK_LOG2 6             // 64 tiles per chunk of the XCD-aware tile mapping (64 .. 256 measured alike)
-#endif
 #ifndef F3D_FUSE_WAVES
 #define F3D_FUSE_WAVES 3                 // waves per SIMD the register allocation of k_fuse must allow (4 spills: measured slower)
 #endif
@@ -574,7 +583,11 @@ __global__ __launch_bounds__(F3D_BLOCK, F3D_FUSE_WAVES) void k_fuse(const T* __r
                                                      const float* __restrict__ ctabT, const double* __restrict__ vtabT,
                                                      uint32_t* __restrict__ carry, int chunk_flags, T* __restrict__ xyz_keep,
                                                      unsigned long long* __restrict__ umask, uint32_t* __restrict__ park, int park_slots, int park_stride,
-                                                     int64_t prefilled) {
+                                                     int64_t prefilled, const f3d_deal deal) {
+#if defined(F3D_EXP_STAMP)
+    const long long stamp_entry = wall_clock64();
+    bool stamp_first = true;
+#endif
     const int ncodes = cb->ncodes;                                        // wave-uniform: scalar load
     if (ncodes > cmax || ncodes < cmin) return;                           // the other instance's book
     const int words = (ncodes + 3) >> 2;
@@ -632,14 +645,12 @@ __global__ __launch_bounds__(F3D_BLOCK, F3D_FUSE_WAVES) void k_fuse(const T* __r
     // regions (points seen by few / by many views) evenly.  r1/r2 gave every XCD ONE contiguous eighth of the cloud: the XCD
     // with the busiest region finished last while others idled -- 0.98 -> 0.85 ms for the fused call at C3, 1.46 -> 1.23 ms with
     // iid masks (profiles/r03_summary.md).  Placement affects speed only, never results.
-    int xlog = F3D_XCD_CHUNK_LOG2;                                        // chunk = 2^xlog tiles, smaller for small clouds: at least four chunks per XCD
-#ifndef F3D_XCD_MIN_ROWS
-#define F3D_XCD_MIN_ROWS 8               // chunk rows per XCD at least (small clouds: 1.25M points 0.349 -> 0.314 ms per step with 8 instead of 4)
-#endif
-    while (xlog > 0 && ntiles < ((8 * F3D_XCD_MIN_ROWS) << xlog)) --xlog;
-    const int chunk_rows = (ntiles + (8 << xlog) - 1) >> (xlog + 3);
-    const int tiles_per_xcd = chunk_rows << xlog;                         // positions j of one XCD's list (the last row may hold fewer tiles)
-    const int xcd = blockIdx.x & 7, bx = blockIdx.x >> 3, gx = gridDim.x >> 3;
+    const f3d_xcd_list xl = f3d_xcd_list_of(ntiles);                      // chunk = 2^xlog tiles, smaller for small clouds: at least F3D_XCD_MIN_ROWS chunks per XCD
+    const int xlog = xl.xlog;
+    const int tiles_per_xcd = xl.positions;                               // positions j of one XCD's list (the last row may hold fewer tiles)
+    const int xcd = blockIdx.x & 7, bx = blockIdx.x >> 3;
+    // The positions a block walks come from the deal (f3d_fuse_deal.h): one per layer, the low block indices through the most layers.
+    // The deal is a kernel argument by value: block-uniform, read with scalar loads.
     uint32_t* const hcol0 = hist + tid;
     uint32_t* const hcol1 = PPL == 2 ? hist + hdw * F3D_BLOCK + tid : hcol0;
     // The tile loop is ROTATED: a tile's points are REQUESTED one tile ahead (the coordinates as stored: loads, no arithmetic) and
@@ -649,7 +660,15 @@ __global__ __launch_bounds__(F3D_BLOCK, F3D_FUSE_WAVES) void k_fuse(const T* __r
     // of tile k+2 then travel while tile k scans its bins and stores its labels, and the turn of the loop is the only wait for either.
     // Only a position the block will consume is ever requested, and nothing beyond n.
     const auto tile_at = [&](int jj) { return ((jj >> xlog) << (xlog + 3)) + (xcd << xlog) + (jj & ((1 << xlog) - 1)); };
-    const auto next_pos = [&](int jj) { while (jj < tiles_per_xcd && tile_at(jj) >= ntiles) jj += gx; return jj; };   // >= tiles_per_xcd: none left
+    int layer = -1;                                                       // of the position asked for last
+    const auto next_pos = [&]() {                                         // the block's next position with a tile; >= tiles_per_xcd: none left
+        for (;;) {
+            const f3d_deal_pos p = f3d_deal_next(deal, tiles_per_xcd, bx, layer);
+            if (p.k < 0) return tiles_per_xcd;
+            layer = p.k;
+            if (tile_at(p.pos) < ntiles) return p.pos;
+        }
+    };
     const auto req_perm = [&](int t, int ln, int (&o)[2]) {               // caller-order indices of the lane's two points of tile t
 #pragma unroll
         for (int q = 0; q < 2; ++q) {
@@ -673,9 +692,9 @@ __global__ __launch_bounds__(F3D_BLOCK, F3D_FUSE_WAVES) void k_fuse(const T* __r
         for (int q = 0; q < 2; ++q) { const T* s = xyz + 3 * (int64_t)idx[q]; r[q][0] = s[0]; r[q][1] = s[1]; r[q][2] = s[2]; }
         if (pinned) __builtin_amdgcn_sched_barrier(0);
     };
-    int j = next_pos(bx);
-    if (j >= tiles_per_xcd) return;                                       // (no barrier follows)
-    int jn = next_pos(j + gx);                                            // the block's next valid position
+    int j = next_pos();
+    if (j >= tiles_per_xcd) { F3D_STAMP_EXIT(); return; }                 // (no barrier follows)
+    int jn = next_pos();                                                  // the block's next valid position
     int orig[2], orig_n[2], orig_nn[2] = {0, 0};
     T raw[2][3], raw_n[2][3];
     req_perm(tile_at(j), lane, orig_n);
@@ -688,12 +707,18 @@ __global__ __launch_bounds__(F3D_BLOCK, F3D_FUSE_WAVES) void k_fuse(const T* __r
     __syncthreads();
     for (;;) {
         // the loop turns: the requested tile becomes the current one (everything asked for so far is waited for here)
+#if defined(F3D_EXP_STAMP)
+        if (stamp_first && tid == 0 && n >= F3D_STAMP_WORDS) {
+            classes[4 * blockIdx.x] = blockIdx.x; classes[4 * blockIdx.x + 1] = stamp_entry; classes[4 * blockIdx.x + 2] = wall_clock64();
+        }
+        stamp_first = false;
+#endif
 #pragma unroll
         for (int q = 0; q < 2; ++q) {
             orig[q] = orig_n[q]; raw[q][0] = raw_n[q][0]; raw[q][1] = raw_n[q][1]; raw[q][2] = raw_n[q][2];
             orig_n[q] = orig_nn[q];
         }
-        const int jnn = jn < tiles_per_xcd ? next_pos(jn + gx) : tiles_per_xcd;   // ... and the one after it
+        const int jnn = jn < tiles_per_xcd ? next_pos() : tiles_per_xcd;   // ... and the one after it
         const int tile = tile_at(j);
         const int i0 = tile * TILE + (tid >> 6) * (64 * PPL) + lane;      // this lane's first point; its second is i0 + 64
         bool live[2], act[2], defer[2];
@@ -1046,6 +1071,7 @@ __global__ __launch_bounds__(F3D_BLOCK, F3D_FUSE_WAVES) void k_fuse(const T* __r
         if (jn >= tiles_per_xcd) break;
         j = jn; jn = jnn;
     }
+    F3D_STAMP_EXIT();
 }
 
 // ------------------------------------------------------------------------------------------
@@ -1385,8 +1411,8 @@ __global__ __launch_bounds__(F3D_BLOCK) void k_fastpath_audit(const T* __restric
 // launchers (called from f3d_capi.cpp)
 // =============================================================================================
 #ifndef F3D_FUSE_GRID
-#define F3D_FUSE_GRID (256 * 4 * 8)     // k_fuse: blocks per launch (multiple of 8; several rounds so that the tail stays short)
-#endif
+#define F3D_FUSE_GRID (256 * 4 * 8)     // k_fuse: blocks per launch at most (multiple of 8: an eighth of them per XCD); the deal of an instance
+#endif                                  // (f3d_fuse_deal.h) says how many it launches, and a cloud the deal cannot hold walks this many with a stride
 
 static size_t fuse_lds_bytes(int hist_dwords_per_point, int ppl, bool tables = true) {   // k_fuse: [tables +] code book + histograms of `ppl` points per lane
     return ((tables ? 64 * F3D_CULL_ROW + (F3D_VTAB_GLOBAL ? 0 : 2 * F3D_VHEAD * 64) : 0) + F3D_BOOK_DWORDS) * sizeof(uint32_t) + (size_t)hist_dwords_per_point * ppl * F3D_BLOCK * sizeof(uint32_t);
@@ -1514,6 +1540,32 @@ static int64_t unlabelled_after_remap(int nclasses, const f3d_filter_args& flt) 
     return r;
 }
 
+// Blocks of `kernel` with `lds` bytes of dynamic LDS that one XCD holds at a time: the slots its deal is made for.  The runtime is asked
+// once per (kernel, LDS size) and context; `assumed` blocks per CU stand in when it cannot say.
+static int fuse_slots_per_xcd(f3d_fuse_occupancy* occ, const void* kernel, size_t lds, int assumed) {
+    if (!occ) return assumed * 256 / 8;
+    for (int i = 0; i < occ->n; ++i)
+        if (occ->e[i].kernel == kernel && occ->e[i].lds == lds) return occ->e[i].blocks_per_cu * occ->cus / 8;
+    if (occ->cus <= 0) {
+        int dev = 0, cus = 0;
+        if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus < 8) {
+            (void)hipGetLastError();
+            cus = 256;
+        }
+        occ->cus = cus;
+    }
+    int per_cu = 0;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, F3D_BLOCK, lds) != hipSuccess || per_cu < 1) {
+        (void)hipGetLastError();
+        per_cu = assumed;
+    }
+    const int slots = (int)(sizeof occ->e / sizeof occ->e[0]);
+    if (occ->n >= slots) occ->n = 0;                         // (more instances than the table holds: start over)
+    occ->e[occ->n].kernel = kernel; occ->e[occ->n].lds = lds; occ->e[occ->n].blocks_per_cu = per_cu;
+    ++occ->n;
+    return per_cu * occ->cus / 8;
+}
+
 template <typename KernelT>
 static hipError_t raise_lds(KernelT kernel, size_t lds) {
     if (lds <= 48 * 1024) return hipSuccess;
@@ -1543,7 +1595,7 @@ static hipError_t launch_fuse_t(const f3d_fuse_job& j, int mode, int grid) {
     const int cnv = v1 - v0;
     if (fast && (n > 0x7ffff000LL || (flt.nfilter > 0 && !flt.cls_dev) || (uint64_t)nviews * f3d_coded_plane(h, w) >= (1ull << 32)))
         return hipErrorInvalidValue;                         // 32-bit point indices and mask offsets; filter list in device memory
-    const dim3 g(grid), b(F3D_BLOCK), ge(fast ? 512 : grid);
+    const dim3 b(F3D_BLOCK), ge(fast ? 512 : grid);         // (k_fuse: a grid per instance, below)
     const int words_max = j.lay.park_stride;                 // bin words of a point with every code in use
     const size_t lds_small = fuse_lds_bytes(F3D_BIN32_MAX_CODES, 2, cnv <= 64), lds_full = fuse_lds_bytes(words_max, 2, false);
     const fuse_tables tab = fuse_tables_split(j.tables, cnv);
@@ -1577,15 +1629,19 @@ static hipError_t launch_fuse_t(const f3d_fuse_job& j, int mode, int grid) {
         // of codes): LDS per block decides how many blocks a CU holds, and only the device
         // knows how many labels the masks contain -- the code book says which instance runs, the others return at once
         const size_t lds_mid = fuse_lds_bytes(F3D_PACKED_SMALL_WORDS, 2, one_group);
-        auto fuse = [&](decltype(ks) kernel, size_t lds, int cmin, int cmax) {   // the instance for the books of cmin..cmax codes
-            hipLaunchKernelGGL(kernel, g, b, lds, s, xyz, n, cviews, cnv, ccm, h, w, nclasses, flt.nfilter, flt.cls_dev, j.threshold,
+        // Every instance has its own deal of tiles to blocks (f3d_fuse_deal.h), made for the blocks an XCD holds of it, and its own grid:
+        // the deal's first layer on each of the 8 XCDs.  (An instance that returns at once is launched with that grid too.)
+        const int positions = f3d_xcd_list_of((int)((n + 2 * F3D_BLOCK - 1) / (2 * F3D_BLOCK))).positions;
+        auto fuse = [&](decltype(ks) kernel, size_t lds, int cmin, int cmax, int per_cu) {   // the instance for the books of cmin..cmax codes; per_cu: blocks per CU if the runtime cannot say
+            const f3d_deal deal = f3d_deal_make(positions, fuse_slots_per_xcd(j.occ, (const void*)kernel, lds, per_cu), F3D_FUSE_GRID / 8);
+            hipLaunchKernelGGL(kernel, dim3(8 * deal.width[0]), b, lds, s, xyz, n, cviews, cnv, ccm, h, w, nclasses, flt.nfilter, flt.cls_dev, j.threshold,
                                j.classes, j.votes, j.err, j.perm, gather, todo_count, todo, j.cb, cmin, cmax, tab.ctabT, tab.vtabT,
-                               j.carry, chunk_flags, (T*)j.xyz_keep, umask, park, j.lay.park_slots, j.lay.park_stride, prefilled);
+                               j.carry, chunk_flags, (T*)j.xyz_keep, umask, park, j.lay.park_slots, j.lay.park_stride, prefilled, deal);
         };
-        fuse(ks, lds_small, 0, F3D_BIN32_MAX_CODES);
-        if (nclasses + 3 > F3D_BIN32_MAX_CODES) fuse(km2, lds_mid, F3D_BIN32_MAX_CODES + 1, 4 * F3D_PACKED_SMALL_WORDS);
-        if (nclasses + 3 > 4 * F3D_PACKED_SMALL_WORDS) fuse(km3, lds_large, 4 * F3D_PACKED_SMALL_WORDS + 1, 4 * F3D_PACKED_LARGE_WORDS);
-        if (nclasses + 3 > 4 * F3D_PACKED_LARGE_WORDS) fuse(kf, lds_full, 4 * F3D_PACKED_LARGE_WORDS + 1, 256);
+        fuse(ks, lds_small, 0, F3D_BIN32_MAX_CODES, 4);
+        if (nclasses + 3 > F3D_BIN32_MAX_CODES) fuse(km2, lds_mid, F3D_BIN32_MAX_CODES + 1, 4 * F3D_PACKED_SMALL_WORDS, one_group ? 4 : 3);
+        if (nclasses + 3 > 4 * F3D_PACKED_SMALL_WORDS) fuse(km3, lds_large, 4 * F3D_PACKED_SMALL_WORDS + 1, 4 * F3D_PACKED_LARGE_WORDS, 3);
+        if (nclasses + 3 > 4 * F3D_PACKED_LARGE_WORDS) fuse(kf, lds_full, 4 * F3D_PACKED_LARGE_WORDS + 1, 256, 2);
         if (chunk_flags & 2) return hipGetLastError();       // more view chunks to come
         // float64 tier on the deferred points' open views, the reference's arithmetic for what it cannot prove either.  Beyond 255 views a
         // point whose 8-bit bin wrapped goes on to k_fuse_exact (16-bit bins, raw masks) through a list in the second list's storage.

@@ -340,6 +340,12 @@ size_t f3d_fuse_carry_bytes(int64_t n, int nclasses);
 // one launch over all views (v0, v1 ignored).  Otherwise the views [v0, v1) of a view-chunked call: `carry` holds f3d_fuse_carry_bytes
 // of scratch that survives from the chunk with v0 == 0 to the one with v1 == nviews; chunks ascending without gaps; no vote output.
 // xyz_keep (may be NULL; first chunk with gather only): receives the cloud in perm order -- the caller passes it as xyz from then on.
+// Blocks of a k_fuse instance a CU holds at a time, by (kernel, dynamic LDS bytes): asked of the runtime once and kept by the context
+// (the deal of tiles to blocks is sized by it, f3d_fuse_deal.h).  Zero-initialised = empty.
+struct f3d_fuse_occupancy {
+    struct entry { const void* kernel; size_t lds; int blocks_per_cu; } e[32];
+    int n, cus;
+};
 struct f3d_fuse_job {
     const void* xyz; int dtype; int64_t n; const int32_t* perm; bool gather;        // the cloud
     const f3d_view* views_dev; int nviews, v0, v1;                                  // the views
@@ -350,6 +356,7 @@ struct f3d_fuse_job {
     const f3d_codebook* cb; void* tables; uint32_t* carry; void* xyz_keep;          //   the code book, f3d_fuse_tables_bytes(nviews), ...
     hipStream_t stream;
     bool filled;                                                                    // the label fill has been done (a rider of the cell sort)
+    f3d_fuse_occupancy* occ;                                                        // the context's cache (NULL: the stated blocks per CU are assumed)
 };
 hipError_t f3d_launch_fuse(const f3d_fuse_job& job);
 // Before f3d_launch_fuse, on any stream that is joined into its stream: the threshold table of the code book (segment_point) and the
