@@ -36,7 +36,8 @@ enum scratch_slot { SLOT_OBB_BOXES = 0, SLOT_SORT_PERM, SLOT_SORT_SCRATCH, SLOT_
                     SLOT_PATCH, SLOT_GRP_SCRATCH, SLOT_OBB_TABLE, SLOT_OBB_FACETS, SLOT_OBB_CAND, SLOT_FUSE_TABLES, SLOT_FUSE_CARRY,
                     SLOT_FUSE_XYZ, SLOT_FUSION, SLOT_PATCH_STATUS, SLOT_NRM, SLOT_NRM_CAMS, SLOT_QRY, SLOT_FLOOD, SLOT_COLOR,
                     SLOT_CVS_INST, SLOT_CVS_STATS, SLOT_QUADS, SLOT_GROW, SLOT_PVOTE, SLOT_PVOTE_BITS, SLOT_MESH, SLOT_ZKEY,
-                    SLOT_ZCOUNTS, SLOT_KNN, SLOT_KNN_FLAG, SLOT_PLANES, SLOT_RASTER, SLOT_ZLUT, SLOT_SMOOTH, SLOT_FACE_GRAPH, SLOT_COUNT };
+                    SLOT_ZCOUNTS, SLOT_KNN, SLOT_KNN_FLAG, SLOT_PLANES, SLOT_RASTER, SLOT_ZLUT, SLOT_SMOOTH, SLOT_FACE_GRAPH, SLOT_LIFT, SLOT_LIFT_TABLE,
+                    SLOT_COUNT };
 enum kept_slot { KEPT_GRAPH_OFFS = 0,                                      // f3d_radius_graph_count -> _fill: the offsets
                  KEPT_QRY_IN, KEPT_QRY_OFFS,                               // f3d_radius_query_count -> _fill: the queries, the offsets
                  KEPT_GRP_ORDER, KEPT_GRP_KEYS, KEPT_GRP_STARTS,           // f3d_group_by_id -> f3d_obb_extremes -> f3d_obb_hull_filter
@@ -203,6 +204,8 @@ int take_error(f3d_ctx* ctx, hipStream_t s, int mask = F3D_DEVERR_ALL) {
             return fail(ctx, F3D_ERR_INDEX, "extract_planes: neighbour index outside [0, n)");
         if (e & F3D_DEVERR_SMOOTH)
             return fail(ctx, F3D_ERR_INDEX, "smooth_votes: neighbour index outside [0, n), or offsets that do not ascend");
+        if (e & F3D_DEVERR_LIFT)
+            return fail(ctx, F3D_ERR_INDEX, "lift: an instance id exceeds max_ids, or a lookup is not below npoints");
         if (e & F3D_DEVERR_RASTER)
             return fail(ctx, F3D_ERR_INDEX, "mesh render: a triangle's vertex index is outside [0, nv)");
         if (e & F3D_DEVERR_ZVOTE)
@@ -1758,6 +1761,152 @@ int f3d_smooth_segment(f3d_ctx* ctx, const void* votes, int vtype, int64_t n, in
                                                max_color_dist, self_weight, iterations, nclasses, threshold, filter, nfilter, lastcol, dcls,
                                                ctx->stream);
     return st.finish(F3D_DEVERR_SMOOTH);
+}
+
+// ---------------------------------------------------------------------------------------------
+// lift_overlaps / lift_instances: 3D instances from per-frame 2D instance ids
+// ---------------------------------------------------------------------------------------------
+namespace {
+
+#define F3D_LIFT_BAD "bad arguments (nframes, hw, npoints >= 1, 1 <= max_ids <= 65535, nframes * max_ids < 2^31, nframes * hw < 2^31)"
+
+bool lift_shape_ok(int nframes, int64_t hw, int64_t npoints, int max_ids) {
+    return nframes >= 1 && hw >= 1 && npoints >= 1 && npoints <= 0x7fffffffLL && max_ids >= 1 && max_ids <= 65535 &&
+           (int64_t)nframes * max_ids <= 0x7fffffffLL && hw <= 0x7fffffffLL && (int64_t)nframes * hw <= 0x7fffffffLL;
+}
+
+uint64_t lift_pow2(uint64_t v) { uint64_t s = 1024; while (s < v) s <<= 1; return s; }
+uint64_t lift_pair_bound(int64_t nseg) { return (uint64_t)nseg * (uint64_t)(nseg - 1) / 2; }
+uint64_t lift_min64(uint64_t a, uint64_t b) { return a < b ? a : b; }
+
+// slots of the pair table of a first run (include/f3d.h)
+uint64_t lift_first_slots(int64_t pixels, int64_t nseg) {
+    const uint64_t guess = (uint64_t)pixels / 4 > 32768 ? (uint64_t)pixels / 4 : 32768;
+    return lift_pow2(2 * lift_min64(lift_pair_bound(nseg), guess));
+}
+
+// incidence -> pair table, again with a larger one while it overflows -> stats as include/f3d.h states them
+int lift_run(f3d_ctx* ctx, f3d_lift_job& j, int64_t* stats, hipStream_t s) {
+    const int64_t pixels = (int64_t)j.nframes * j.hw, nseg = (int64_t)j.nframes * j.max_ids;
+    const int64_t cap = j.instances ? 0 : j.cap;
+    int rc;
+    if ((rc = ensure(ctx, SLOT_LIFT, f3d_lift_scratch_bytes(pixels, j.npoints, nseg), &j.scratch))) return rc;
+    uint64_t slots = lift_first_slots(pixels, nseg);
+    while (f3d_lift_table_bytes(slots * 2, cap) <= ctx->scratch[SLOT_LIFT_TABLE].cap) slots *= 2;       // room that is there already is used
+    j.err = ctx->dev_err; j.stream = s;
+    F3D_HIP(ctx, f3d_launch_lift_incidence(j));
+    int64_t st[F3D_LIFT_NSTATS];
+    int64_t rounds = 1;
+    for (;; ++rounds) {
+        if ((rc = ensure(ctx, SLOT_LIFT_TABLE, f3d_lift_table_bytes(slots, cap), &j.table))) return rc;
+        j.slots = slots;
+        F3D_HIP(ctx, f3d_launch_lift_merge(j, st));
+        if (st[6]) {
+            if ((rc = take_error(ctx, s, F3D_DEVERR_LIFT))) return rc;
+            return fail(ctx, F3D_ERR_INDEX, "lift: an instance id exceeds max_ids, or a lookup is not below npoints");
+        }
+        if (!st[5]) break;
+        const uint64_t need = lift_pow2(2 * lift_min64((uint64_t)st[4], lift_pair_bound(nseg)));
+        slots = need > slots * 2 ? need : slots * 2;
+        if (slots > ((uint64_t)1 << 36)) return fail(ctx, F3D_ERR_NOMEM, "lift: the pair table would need %llu slots", (unsigned long long)slots);
+    }
+    stats[0] = st[0]; stats[1] = st[1]; stats[2] = st[2]; stats[3] = st[3]; stats[4] = st[4]; stats[5] = rounds;
+    return F3D_OK;
+}
+
+f3d_lift_job lift_job(const int32_t* luts, const uint16_t* inst, int nframes, int64_t hw, int64_t npoints, int max_ids) {
+    f3d_lift_job j = {};
+    j.luts = luts; j.inst = inst; j.nframes = nframes; j.hw = hw; j.npoints = npoints; j.max_ids = max_ids;
+    return j;
+}
+
+}  // namespace
+
+int f3d_ctx_reserve_lift(f3d_ctx* ctx, int nframes, int64_t hw, int64_t npoints, int max_ids, int64_t max_pairs) {
+    int rc = enter(ctx); if (rc) return rc;
+    if (!lift_shape_ok(nframes, hw, npoints, max_ids) || max_pairs < 0 || max_pairs > 0x7fffffffLL)
+        return fail(ctx, F3D_ERR_INVALID, "ctx_reserve_lift: " F3D_LIFT_BAD ", 0 <= max_pairs < 2^31");
+    const int64_t pixels = (int64_t)nframes * hw, nseg = (int64_t)nframes * max_ids;
+    const uint64_t first = lift_first_slots(pixels, nseg), room = lift_pow2(2 * (uint64_t)max_pairs);
+    return reserve(ctx, {{SLOT_LIFT, f3d_lift_scratch_bytes(pixels, npoints, nseg)},
+                         {SLOT_LIFT_TABLE, f3d_lift_table_bytes(first > room ? first : room, max_pairs)}});
+}
+
+int f3d_lift_overlaps_dev(f3d_ctx* ctx, const int32_t* luts, const uint16_t* inst, int nframes, int64_t hw, int64_t npoints, int max_ids,
+                          int32_t* sizes, int32_t* pairs, int32_t* counts, int64_t cap, int64_t* stats, void* stream) {
+    int rc = enter(ctx); if (rc) return rc;
+    if (!lift_shape_ok(nframes, hw, npoints, max_ids) || !luts || !inst || !sizes || !stats || cap < 0 || cap > 0x7fffffffLL ||
+        (cap > 0 && (!pairs || !counts)))
+        return fail(ctx, F3D_ERR_INVALID, "lift_overlaps: " F3D_LIFT_BAD ", 0 <= cap < 2^31");
+    f3d_lift_job j = lift_job(luts, inst, nframes, hw, npoints, max_ids);
+    j.sizes = sizes; j.pairs = pairs; j.counts = counts; j.cap = cap;
+    return lift_run(ctx, j, stats, pick(ctx, stream));
+}
+
+int f3d_lift_overlaps(f3d_ctx* ctx, const int32_t* luts, const uint16_t* inst, int nframes, int64_t hw, int64_t npoints, int max_ids,
+                      int32_t* sizes, int32_t* pairs, int32_t* counts, int64_t cap, int64_t* stats) {
+    int rc = enter(ctx); if (rc) return rc;
+    if (!lift_shape_ok(nframes, hw, npoints, max_ids) || !luts || !inst || !sizes || !stats || cap < 0 || cap > 0x7fffffffLL ||
+        (cap > 0 && (!pairs || !counts)))
+        return fail(ctx, F3D_ERR_INVALID, "lift_overlaps: " F3D_LIFT_BAD ", 0 <= cap < 2^31");
+    const size_t pixels = (size_t)nframes * hw, nseg = (size_t)nframes * max_ids;
+    f3d_carve c;
+    const size_t o_luts = c.take(pixels * 4), o_inst = c.take(pixels * 2), o_sizes = c.take(nseg * 4), o_pairs = c.take((size_t)cap * 8),
+                 o_counts = c.take((size_t)cap * 4);
+    staging st(ctx);
+    char* io = (char*)st.slot(c.off);
+    if (st.rc) return st.rc;
+    st.put(io + o_luts, luts, pixels * 4);
+    st.put(io + o_inst, inst, pixels * 2);
+    st.put(io + o_pairs, pairs, (size_t)cap * 8);             // what comes back when P > cap: the caller's own entries
+    st.put(io + o_counts, counts, (size_t)cap * 4);
+    st.back(sizes, io + o_sizes, nseg * 4);
+    st.back(pairs, io + o_pairs, (size_t)cap * 8);
+    st.back(counts, io + o_counts, (size_t)cap * 4);
+    if (!st.rc) st.rc = f3d_lift_overlaps_dev(ctx, (const int32_t*)(io + o_luts), (const uint16_t*)(io + o_inst), nframes, hw, npoints, max_ids,
+                                              (int32_t*)(io + o_sizes), (int32_t*)(io + o_pairs), (int32_t*)(io + o_counts), cap, stats, ctx->stream);
+    return st.finish();
+}
+
+int f3d_lift_instances_dev(f3d_ctx* ctx, const int32_t* luts, const uint16_t* inst, int nframes, int64_t hw, int64_t npoints, int max_ids,
+                           double ratio, int64_t min_overlap, const int32_t* seg_classes, int64_t min_points, int32_t* ids,
+                           uint16_t* support, uint16_t* seen, int32_t* seg2inst, int64_t* inst_points, int64_t* stats, void* stream) {
+    int rc = enter(ctx); if (rc) return rc;
+    if (!lift_shape_ok(nframes, hw, npoints, max_ids) || !luts || !inst || !ids || !support || !seen || !seg2inst || !inst_points || !stats)
+        return fail(ctx, F3D_ERR_INVALID, "lift_instances: " F3D_LIFT_BAD);
+    f3d_lift_job j = lift_job(luts, inst, nframes, hw, npoints, max_ids);
+    j.instances = true; j.ratio = ratio; j.min_overlap = min_overlap; j.min_points = min_points; j.seg_classes = seg_classes;
+    j.ids = ids; j.support = support; j.seen = seen; j.seg2inst = seg2inst; j.inst_points = inst_points;
+    return lift_run(ctx, j, stats, pick(ctx, stream));
+}
+
+int f3d_lift_instances(f3d_ctx* ctx, const int32_t* luts, const uint16_t* inst, int nframes, int64_t hw, int64_t npoints, int max_ids,
+                       double ratio, int64_t min_overlap, const int32_t* seg_classes, int64_t min_points, int32_t* ids, uint16_t* support,
+                       uint16_t* seen, int32_t* seg2inst, int64_t* inst_points, int64_t* stats) {
+    int rc = enter(ctx); if (rc) return rc;
+    if (!lift_shape_ok(nframes, hw, npoints, max_ids) || !luts || !inst || !ids || !support || !seen || !seg2inst || !inst_points || !stats)
+        return fail(ctx, F3D_ERR_INVALID, "lift_instances: " F3D_LIFT_BAD);
+    const size_t pixels = (size_t)nframes * hw, nseg = (size_t)nframes * max_ids, np = (size_t)npoints;
+    f3d_carve c;
+    const size_t o_luts = c.take(pixels * 4), o_inst = c.take(pixels * 2), o_cls = c.take(seg_classes ? nseg * 4 : 0), o_ids = c.take(np * 4),
+                 o_sup = c.take(np * 2), o_seen = c.take(np * 2), o_s2i = c.take(nseg * 4), o_ip = c.take((nseg + 1) * 8);
+    staging st(ctx);
+    char* io = (char*)st.slot(c.off);
+    if (st.rc) return st.rc;
+    st.put(io + o_luts, luts, pixels * 4);
+    st.put(io + o_inst, inst, pixels * 2);
+    if (seg_classes) st.put(io + o_cls, seg_classes, nseg * 4);
+    st.put(io + o_ip, inst_points, (nseg + 1) * 8);           // the entries past I' come back as they were
+    st.back(ids, io + o_ids, np * 4);
+    st.back(support, io + o_sup, np * 2);
+    st.back(seen, io + o_seen, np * 2);
+    st.back(seg2inst, io + o_s2i, nseg * 4);
+    st.back(inst_points, io + o_ip, (nseg + 1) * 8);
+    if (!st.rc) st.rc = f3d_lift_instances_dev(ctx, (const int32_t*)(io + o_luts), (const uint16_t*)(io + o_inst), nframes, hw, npoints, max_ids, ratio,
+                                               min_overlap, seg_classes ? (const int32_t*)(io + o_cls) : nullptr, min_points, (int32_t*)(io + o_ids),
+                                               (uint16_t*)(io + o_sup), (uint16_t*)(io + o_seen), (int32_t*)(io + o_s2i), (int64_t*)(io + o_ip),
+                                               stats, ctx->stream);
+    return st.finish();
 }
 
 // ---------------------------------------------------------------------------------------------

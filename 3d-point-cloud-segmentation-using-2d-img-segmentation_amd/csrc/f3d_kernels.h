@@ -19,7 +19,8 @@
 #define F3D_DEVERR_PLANES 1024             // extract_planes: neighbour index outside [0, n)
 #define F3D_DEVERR_RASTER 2048             // mesh z-buffer: triangle vertex index outside [0, nv)
 #define F3D_DEVERR_SMOOTH 4096             // smooth_votes / smooth_segment: neighbour index outside [0, n), or offsets not ascending
-#define F3D_DEVERR_ALL 8191
+#define F3D_DEVERR_LIFT 8192               // lift_overlaps / lift_instances: an instance id > max_ids or a lookup >= npoints
+#define F3D_DEVERR_ALL 16383
 #define F3D_PLANES_PER_LAUNCH 16
 #define F3D_OBB_MAX_BOXES 4096
 #define F3D_SORT_MAX_CELLS 32767            // + 1 overflow cell = 2^15 keys -> 16 key bits sorted
@@ -668,3 +669,23 @@ hipError_t f3d_launch_smooth_check(int64_t n, const int64_t* offs, const int32_t
 hipError_t f3d_launch_smooth(const void* votes, int vtype, int64_t n, int ncols, const int64_t* offs, const int32_t* nbrs,
                              const f3d_smooth_gates& g, double self_weight, double* out, const f3d_smooth_seg* seg, int64_t* classes,
                              const int* err, hipStream_t s);
+
+// mask lifting (f3d_lift.hip; the contract is in include/f3d.h).  Device pointers.  f3d_launch_lift_incidence enqueues the incidence
+// (rows, sizes, seen); f3d_launch_lift_merge then runs the pair table of `slots` entries (a power of two) and, with `instances`, the merge,
+// the vote and the renumbering, or else the sorted pairs when at most `cap` of them exist.  It synchronises the stream for its one
+// readback: stats = {distinct pairs, instances kept, instances before min_points, incidences, pair occurrences, table overflowed, bad
+// input}.  After an overflow it is called again with a larger table (the incidence stays).  Bad input sets F3D_DEVERR_LIFT and nothing
+// is written.  scratch: f3d_lift_scratch_bytes(F * HW, N, F * K); table: f3d_lift_table_bytes(slots, cap) (cap 0 with `instances`)
+#define F3D_LIFT_NSTATS 7
+struct f3d_lift_job {
+    const int32_t* luts; const uint16_t* inst; int nframes; int64_t hw, npoints; int max_ids;               // the frames
+    bool instances; double ratio; int64_t min_overlap, min_points; const int32_t* seg_classes;            // the merge rule (seg_classes may be NULL)
+    uint16_t* seen; int32_t* sizes;                                                                         // incidence outputs (either may be NULL)
+    int32_t *pairs, *counts; int64_t cap;                                                                   // overlaps outputs
+    int32_t* ids; uint16_t* support; int32_t* seg2inst; int64_t* inst_points;                               // instances outputs
+    void *scratch, *table; uint64_t slots; int* err; hipStream_t stream;
+};
+size_t f3d_lift_scratch_bytes(int64_t pixels, int64_t npoints, int64_t nseg);
+size_t f3d_lift_table_bytes(uint64_t slots, int64_t cap);
+hipError_t f3d_launch_lift_incidence(const f3d_lift_job& j);
+hipError_t f3d_launch_lift_merge(const f3d_lift_job& j, int64_t stats[F3D_LIFT_NSTATS]);

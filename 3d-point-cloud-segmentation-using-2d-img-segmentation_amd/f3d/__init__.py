@@ -193,6 +193,11 @@ def library():
         'f3d_smooth_segment': (i32, [vp, vp, i32, i64, i32, vp, vp, vp, dbl, vp, i32, dbl, dbl, i32, i32, dbl, vp, i32, i32, vp]),
         'f3d_smooth_segment_dev': (i32, [vp, vp, i32, i64, i32, vp, vp, vp, dbl, vp, i32, dbl, dbl, i32, i32, dbl, vp, i32, i32, vp, vp]),
         'f3d_ctx_reserve_smooth': (i32, [vp, i64, i32, i32]),
+        'f3d_lift_overlaps': (i32, [vp, vp, vp, i32, i64, i64, i32, vp, vp, vp, i64, vp]),
+        'f3d_lift_overlaps_dev': (i32, [vp, vp, vp, i32, i64, i64, i32, vp, vp, vp, i64, vp, vp]),
+        'f3d_lift_instances': (i32, [vp, vp, vp, i32, i64, i64, i32, dbl, i64, vp, i64, vp, vp, vp, vp, vp, vp]),
+        'f3d_lift_instances_dev': (i32, [vp, vp, vp, i32, i64, i64, i32, dbl, i64, vp, i64, vp, vp, vp, vp, vp, vp, vp]),
+        'f3d_ctx_reserve_lift': (i32, [vp, i32, i64, i64, i32, i64]),
         'f3d_patch_owner': (i32, [vp, vp, i64, i32, i32, i32, dbl, dbl, vp, vp, vp, vp, vp, vp]),
         'f3d_patch_owner_dev': (i32, [vp, vp, i64, i32, i32, i32, dbl, dbl, vp, vp, vp, vp, vp, vp, vp]),
         'f3d_patch_match': (i32, [vp, vp, i64, i32, i32, i32, dbl, dbl, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
@@ -450,6 +455,11 @@ class Context:
         """Size the scratch of smooth_votes_dev / smooth_segment_dev for [n, ncols] vote matrices and that many iterations (one
         iteration needs none)."""
         self._check(self._lib.f3d_ctx_reserve_smooth(self._h, int(n), int(ncols), int(iterations)))
+
+    def reserve_lift(self, nframes, hw, npoints, max_ids, max_pairs=0):
+        """Size the scratch of lift_overlaps_dev / lift_instances_dev for nframes frames of hw pixels, npoints points, max_ids ids per
+        frame and a pair table (and pair output) of up to max_pairs distinct overlapping segment pairs."""
+        self._check(self._lib.f3d_ctx_reserve_lift(self._h, int(nframes), int(hw), int(npoints), int(max_ids), int(max_pairs)))
 
     def reserve_refine(self, n):
         """Size the scratch of region_grow_dev for clouds of up to n points."""
@@ -933,6 +943,29 @@ class Context:
                                                   _ptr(neighbours) if len(neighbours) else None, len(neighbours), _ptr(counts)))
         return offsets, neighbours, counts
 
+    def lift_overlaps(self, luts, inst, npoints, max_ids, cap):
+        """Segment sizes and overlaps (f3d.h f3d_lift_overlaps).  luts int32 [F, HW], inst uint16 [F, HW], C-contiguous -> (sizes int32
+        [F * max_ids], pairs int32 [cap, 2], counts int32 [cap], stats int64 [6]); pairs / counts are filled only when stats[0] <= cap."""
+        nf, hw = luts.shape
+        sizes, pairs, counts = np.zeros(nf * int(max_ids), np.int32), np.zeros((int(cap), 2), np.int32), np.zeros(int(cap), np.int32)
+        stats = np.zeros(6, np.int64)
+        self._check(self._lib.f3d_lift_overlaps(self._h, _ptr(luts), _ptr(inst), nf, hw, int(npoints), int(max_ids), _ptr(sizes),
+                                                _ptr(pairs) if cap else None, _ptr(counts) if cap else None, int(cap), _ptr(stats)))
+        return sizes, pairs, counts, stats
+
+    def lift_instances(self, luts, inst, npoints, max_ids, ratio, min_overlap, seg_classes, min_points):
+        """3D instances from per-frame ids (f3d.h f3d_lift_instances).  luts int32 [F, HW], inst uint16 [F, HW], seg_classes int32
+        [F * max_ids] or None -> (ids int32 [N], support uint16 [N], seen uint16 [N], seg2inst int32 [S], inst_points int64 [S + 1] of
+        which the first stats[1] + 1 entries are written, stats int64 [6])."""
+        nf, hw = luts.shape
+        n, nseg = int(npoints), nf * int(max_ids)
+        ids, support, seen = np.zeros(n, np.int32), np.zeros(n, np.uint16), np.zeros(n, np.uint16)
+        seg2inst, inst_points, stats = np.zeros(nseg, np.int32), np.zeros(nseg + 1, np.int64), np.zeros(6, np.int64)
+        self._check(self._lib.f3d_lift_instances(self._h, _ptr(luts), _ptr(inst), nf, hw, n, int(max_ids), float(ratio), int(min_overlap),
+                                                 _ptr(seg_classes), int(min_points), _ptr(ids), _ptr(support), _ptr(seen), _ptr(seg2inst),
+                                                 _ptr(inst_points), _ptr(stats)))
+        return ids, support, seen, seg2inst, inst_points, stats
+
     def extract_planes(self, points, offsets, neighbours, normals, cos_angle, offset, dist, max_variation, min_points, max_rounds,
                        max_planes, want_normals=False):
         """Plane table of a cloud over its adjacency (include/f3d.h f3d_extract_planes).  points float64 / float32 [n, 3]; offsets /
@@ -1305,6 +1338,24 @@ class Context:
                                                      normals_ptr, float(cos_angle), colors_ptr, int(cdtype), float(max_color_dist),
                                                      float(self_weight), int(iterations), int(nclasses), float(threshold), _ptr(f), nf,
                                                      int(bool(lastcol)), classes_ptr, stream))
+
+    def lift_overlaps_dev(self, luts_ptr, inst_ptr, nframes, hw, npoints, max_ids, sizes_ptr, pairs_ptr, counts_ptr, cap, stream=None):
+        """f3d_lift_overlaps_dev: device pointers; synchronises `stream` for its one readback -> stats int64 [6] (host).  pairs / counts
+        (cap entries) are written only when stats[0] <= cap.  Bad input raises IndexError and nothing is written."""
+        stats = np.zeros(6, np.int64)
+        self._check(self._lib.f3d_lift_overlaps_dev(self._h, luts_ptr, inst_ptr, int(nframes), int(hw), int(npoints), int(max_ids), sizes_ptr,
+                                                    pairs_ptr, counts_ptr, int(cap), _ptr(stats), stream))
+        return stats
+
+    def lift_instances_dev(self, luts_ptr, inst_ptr, nframes, hw, npoints, max_ids, ratio, min_overlap, seg_classes_ptr, min_points, ids_ptr,
+                           support_ptr, seen_ptr, seg2inst_ptr, inst_points_ptr, stream=None):
+        """f3d_lift_instances_dev: device pointers (seg_classes_ptr may be None; inst_points int64 [F * max_ids + 1]); synchronises
+        `stream` for its one readback -> stats int64 [6] (host).  Bad input raises IndexError and nothing is written."""
+        stats = np.zeros(6, np.int64)
+        self._check(self._lib.f3d_lift_instances_dev(self._h, luts_ptr, inst_ptr, int(nframes), int(hw), int(npoints), int(max_ids), float(ratio),
+                                                     int(min_overlap), seg_classes_ptr, int(min_points), ids_ptr, support_ptr, seen_ptr,
+                                                     seg2inst_ptr, inst_points_ptr, _ptr(stats), stream))
+        return stats
 
     def take_device_error(self, stream=None):
         self._check(self._lib.f3d_take_device_error(self._h, stream))

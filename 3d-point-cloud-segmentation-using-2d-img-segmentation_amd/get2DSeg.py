@@ -69,6 +69,24 @@ def _logits_of(outputs):
     return outputs
 
 
+def panoptic_to_instances(outputs):
+    """The instance map a predictor's panoptic answer holds, in the form segUtils.lifting takes.  outputs: the predictor's dict
+    with a detectron2-style ``panoptic_seg = (id map [H,W], segments_info)``, or that pair itself.  -> (uint16 [H,W] on the host:
+    the pixels of the ``isthing`` segments renumbered 1..k in their order in segments_info, 0 elsewhere; the list of their
+    category_id).  The reference unpacks ``sem, pan, inst`` and keeps ``sem`` alone (:109)."""
+    pan, info = outputs['panoptic_seg'] if isinstance(outputs, dict) else outputs
+    if hasattr(pan, 'detach'):
+        pan = pan.detach().cpu().numpy()
+    pan = np.asarray(pan)
+    things = [seg for seg in info if seg.get('isthing')]
+    if len(things) > 65535:
+        raise ValueError(f'panoptic_to_instances: {len(things)} instances do not fit uint16 ids')
+    inst = np.zeros(pan.shape, np.uint16)
+    for k, seg in enumerate(things):
+        inst[pan == seg['id']] = k + 1
+    return inst, [int(seg['category_id']) for seg in things]
+
+
 def sem_to_mask(sem, conf_threshold=0.017, low_label=133):
     """[C,H,W] float32 logits (torch CUDA tensor or array) -> uint8 [H,W] class mask on the HOST (reference :110-120)."""
     ctx = f3d.default_context()

@@ -196,13 +196,30 @@ def panoptic_viz(points, ids, idinfo, outdir, coco_data=None, colors=None, alpha
     return colors, pcd, palette, idinfo
 
 
+def refine_instances(ids, pan_info, instance_dir, uv2pt_dir, depth_hw, min_points=1):
+    """The instances of split_into_instances subdivided by the ids lifted from per-frame instance maps: an `isthing` instance is cut
+    where the lift tells two objects apart (lifting.split_by_lift); the others stay whole.  -> (ids, info list indexed by id)."""
+    from Fusion3DSeg.segUtils.lifting import lift_from_dirs, split_by_lift
+    ids = np.asarray(ids)
+    lifted = lift_from_dirs(instance_dir, uv2pt_dir, len(ids), depth_hw, min_points=min_points).ids
+    thing = np.array([bool(info['isthing']) for info in pan_info], bool)
+    new_ids, parent = split_by_lift(ids, np.where(thing[ids], lifted, 0), return_parent=True)
+    area = np.bincount(new_ids, minlength=len(parent))
+    info = [dict(pan_info[int(old)], id=int(new), area=int(area[new])) for new, old in enumerate(parent)]
+    return new_ids, info
+
+
 def segment(dirname, mask_dir, threshold=0.5, nclasses=133, filter_classes=[86, 114, 115], min_pts_per_inst=100, verbose=True,
-            smooth_iterations=0, smooth_angle=None):
+            smooth_iterations=0, smooth_angle=None, instance_dir=None):
     """Semantic + panoptic segmentation of a fused cloud from 2D masks (reference :18-116).
 
     smooth_iterations > 0 (not in the reference; needs the adjacency): the classes come from the votes summed over every point's
     neighbours that many times (voting.smooth_segment) instead of from each point's own row, which closes one-point islands and
-    unseen points before the instance split; smooth_angle (degrees) keeps the sums on one surface by the loaded normals."""
+    unseen points before the instance split; smooth_angle (degrees) keeps the sums on one surface by the loaded normals.
+
+    instance_dir (not in the reference; needs the adjacency): a directory of per-frame instance-id PNGs named like the lookups in
+    fusion/uv2pt (get2DSeg.panoptic_to_instances makes such maps).  The flood instances of the `isthing` classes are then
+    subdivided by the ids lifted from those maps (segUtils.lifting), so two objects of one class that touch come apart."""
     dirname = Path(dirname)
     points, norms, colors, nmerges, occurences, nframes, depth_hw, adj = Fusion.load_data(dirname)
     t0 = time.perf_counter()
@@ -222,6 +239,8 @@ def segment(dirname, mask_dir, threshold=0.5, nclasses=133, filter_classes=[86, 
     semantic_viz(points, classes, nclasses, votes=None, coco_data=_coco_meta(), outdir=dirname / 'segmentation')
     if adj is None:
         return votes, classes
+    if instance_dir is not None:
+        ids, pan_info = refine_instances(ids, pan_info, instance_dir, dirname / 'fusion' / 'uv2pt', depth_hw, min_pts_per_inst)
     panoptic_viz(points, ids, pan_info, dirname / 'panoptic_segmentation', _coco_meta(), colors=None, alpha=1.0)
     master_classes(dirname)
 

@@ -741,6 +741,55 @@ int f3d_smooth_segment_dev(f3d_ctx* ctx, const void* votes, int vtype, int64_t n
                            const int32_t* filter, int nfilter, int lastcol, int64_t* classes, void* stream);
 int f3d_ctx_reserve_smooth(f3d_ctx* ctx, int64_t n, int ncols, int iterations);
 
+/* ---- lift_overlaps / lift_instances: 3D instances from per-frame 2D instance ids (no reference counterpart) ---------------- */
+/* The 2D network separates two chairs that touch in every frame, but its instance ids are local to a frame, so they cannot be voted
+ * the way classes are.  These entries turn them into ids that are consistent over the cloud ("mask lifting"): integer set arithmetic
+ * over the pixel-to-point lookups (uv2pt of Fusion.fuse, f3d_render_lookups, f3d_render_mesh_lookups).  tests/lift_ref.py restates
+ * the contract in NumPy.
+ *
+ * Inputs.  luts int32 [F, HW]: pixel -> cloud point, negative = none.  inst uint16 [F, HW]: the pixel's instance id within its frame,
+ * 0 = none.  npoints N >= 1, max_ids K with 1 <= K <= 65535, F >= 1, HW >= 1, F * K < 2^31, F * HW < 2^31.  The segment of (frame f,
+ * id k) has index g = f * K + (k - 1); there are S = F * K segments.
+ * 1. Incidence.  The set of distinct pairs (point, g) over all pixels with lut >= 0 and inst > 0: several pixels of a frame that hit
+ *    one point with one id count once, and a point may lie in two segments of one frame.  row(p) = the segments of p in ascending g;
+ *    seen[p] = |row(p)| saturated at 65535 (uint16 [N]); sizes[g] = the number of distinct points of g (int32 [S]).
+ * 2. Overlaps.  overlap(a, b), a < b, = the number of points whose row holds both.  f3d_lift_overlaps lists the P pairs with
+ *    overlap > 0 in ascending (a, b): pairs int32 [cap, 2], counts int32 [cap].  They are written only when P <= cap (cap >= 0 entries
+ *    of room; stats[0] = P in any case: the caller repeats the call with room).
+ * 3. Merge.  a and b are linked iff overlap >= min_overlap, (double)overlap >= ratio * (double)min(sizes[a], sizes[b]) (one double
+ *    multiply, not contracted; a NaN ratio links nothing) and, when seg_classes (int32 [S], may be NULL) is given, seg_classes[a] ==
+ *    seg_classes[b].  Links are transitive.  A component's root is its smallest index; the non-empty segments' components are
+ *    numbered 1 .. I in ascending root.  seg2inst[g] (int32 [S]) = that number, 0 for an empty segment.
+ * 4. Vote.  count(i) = |{g in row(p) : seg2inst[g] = i}|; ids[p] (int32 [N]) = the instance with the largest count, a tie going to the
+ *    smaller id, 0 for an empty row; support[p] (uint16 [N]) = the winning count, saturated at 65535.
+ * 5. Small instances.  An instance that won fewer than min_points points is dropped: its points get ids 0 and support 0 (not the
+ *    runner-up).  The survivors are renumbered 1 .. I' in ascending old id and seg2inst follows.  inst_points int64 [S + 1]: entry i
+ *    <= I' = the points of i, entry 0 the unlabelled points; the entries past I' are not written.
+ * Everything but the comparison of step 3 is integer, so every output is bit-reproducible.
+ * stats (host int64 [6]) = {P, I', I, incidences, sum over the points of seen * (seen - 1) / 2, runs of the pair table}.
+ * Errors.  A pixel with inst > K or lut >= N (whatever the other array says) -> F3D_ERR_INDEX and no output is written: the first
+ * kernel raises a flag under which every later kernel returns at once.  Both the host entries and the _dev twins return it: they read
+ * the flag back with the counts.  Arguments outside the limits above -> F3D_ERR_INVALID.
+ * Cost and limits.  The pairs of a row are counted in an open-addressing table of 64-bit keys, so work grows with the sum of
+ * seen^2, not with S^2.  The table starts at 2 * min(S (S - 1) / 2, max(F * HW / 4, 32768)) slots, rounded up to a power of two >= 1024 (or
+ * at what f3d_ctx_reserve_lift set aside, when that is more); a probe sequence that finds no slot raises a flag, nothing is dropped,
+ * and the table stage runs again with 2 * min(sum of seen * (seen - 1) / 2, S (S - 1) / 2) slots, which holds every pair (a strict
+ * context returns F3D_ERR_NOMEM instead).  A row longer than 64 segments is handled by a whole wave.
+ * The host entries wrap the _dev twins, which take device pointers (stats stays on the host), enqueue on `stream` and synchronise it
+ * for ONE blocking readback of the counts.  Scratch: about 24 bytes per pixel + 20 per segment + 8 per point, and the table (12 bytes
+ * per slot, + 24 per entry of cap); f3d_ctx_reserve_lift(F, HW, N, K, max_pairs) sizes both for up to max_pairs distinct pairs. */
+int f3d_lift_overlaps(f3d_ctx* ctx, const int32_t* luts, const uint16_t* inst, int nframes, int64_t hw, int64_t npoints, int max_ids,
+                      int32_t* sizes, int32_t* pairs, int32_t* counts, int64_t cap, int64_t* stats);
+int f3d_lift_overlaps_dev(f3d_ctx* ctx, const int32_t* luts, const uint16_t* inst, int nframes, int64_t hw, int64_t npoints, int max_ids,
+                          int32_t* sizes, int32_t* pairs, int32_t* counts, int64_t cap, int64_t* stats, void* stream);
+int f3d_lift_instances(f3d_ctx* ctx, const int32_t* luts, const uint16_t* inst, int nframes, int64_t hw, int64_t npoints, int max_ids,
+                       double ratio, int64_t min_overlap, const int32_t* seg_classes, int64_t min_points, int32_t* ids, uint16_t* support,
+                       uint16_t* seen, int32_t* seg2inst, int64_t* inst_points, int64_t* stats);
+int f3d_lift_instances_dev(f3d_ctx* ctx, const int32_t* luts, const uint16_t* inst, int nframes, int64_t hw, int64_t npoints, int max_ids,
+                           double ratio, int64_t min_overlap, const int32_t* seg_classes, int64_t min_points, int32_t* ids,
+                           uint16_t* support, uint16_t* seen, int32_t* seg2inst, int64_t* inst_points, int64_t* stats, void* stream);
+int f3d_ctx_reserve_lift(f3d_ctx* ctx, int nframes, int64_t hw, int64_t npoints, int max_ids, int64_t max_pairs);
+
 /* ---- (f)#1: the adjacency itself, Fusion.save_data (Fusion3DSeg/fusion.py:374-375) -------- */
 /* tree = KDTree(points); adj = tree.query_radius(points, r=2*ds_radius): for every point the indices of all points
  * (itself included) whose float64 squared distance ((dx*dx + dy*dy) + dz*dz, sklearn's euclidean_rdist order) is
