@@ -505,6 +505,44 @@ class Fusion:
                     t.record_stream(df.caller)
         return out
 
+    def reconstruct_mesh(self, voxel, lo=None, dims=None, trunc=None, max_weight=64, max_depth=10, min_weight=1, skip=1, points=None):
+        """A triangle mesh of the capture by TSDF reconstruction (``segUtils.reconstruct``): the frames' world points go back to
+        camera-z depth images (``depth_images``, pixels that are not ``valid`` or not finite are holes), which are integrated into a
+        volume of ``voxel`` edge and extracted by surface nets -> (vertices float64 [V, 3], triangles int32 [M, 3]), ready for
+        ``render_mesh_lookups``, ``project_vote_argmax_occluded``, ``meshUtils.label_faces`` / ``face_adjacency`` and
+        ``write_triangle_mesh``.  Without ``lo`` and ``dims`` the volume is the box of the fused cloud ``points`` (as ``fuse``
+        returned it; without it, of the frames' valid points, which contains that box) grown by ``trunc`` (default 4 voxels) on
+        every side.  Frames of device tensors give device tensors.  ``fuse`` consumes the ``valid`` masks of NumPy frames, so call
+        this first, or on a copy of the frames."""
+        from Fusion3DSeg.segUtils.reconstruct import TSDFVolume, depth_images
+        ids = np.arange(0, self.nframes, skip)
+        frames = [self.frames[int(i)] for i in ids]
+        if not frames:
+            raise ValueError('reconstruct_mesh: no frames')
+        if on_device(frames[0][1]):
+            import torch
+            pts = torch.stack([fr[1].reshape(self.h, self.w, 3) for fr in frames])
+            valid = torch.stack([fr[4].reshape(self.h, self.w).to(torch.bool) for fr in frames])
+            good = valid & torch.isfinite(pts).all(dim=-1)
+            cloud = pts[good].cpu().numpy() if points is None and (lo is None or dims is None) else None
+        else:
+            pts = np.stack([np.asarray(fr[1], np.float64).reshape(self.h, self.w, 3) for fr in frames])
+            valid = np.stack([np.asarray(fr[4], bool).reshape(self.h, self.w) for fr in frames])
+            cloud = pts[valid & np.isfinite(pts).all(axis=-1)]
+        if not bool(valid.any()):
+            raise ValueError('reconstruct_mesh: no frame has a valid pixel (fuse consumes the valid masks of NumPy frames: call this first, or on a copy)')
+        voxel = float(voxel)
+        trunc = 4.0 * voxel if trunc is None else float(trunc)
+        if lo is None or dims is None:
+            cloud = cloud if points is None else np.asarray(points.cpu() if on_device(points) else points, np.float64).reshape(-1, 3)
+            if not len(cloud):
+                raise ValueError('reconstruct_mesh: no valid point to take the bounds from')
+            lo = cloud.min(axis=0) - trunc if lo is None else np.asarray(lo, np.float64)
+            dims = np.maximum(1, np.ceil((cloud.max(axis=0) + trunc - lo) / voxel)).astype(np.int64)
+        depths = depth_images(pts, self.xyzws[ids], self.translations[ids], valid)
+        vol = TSDFVolume(lo, dims, voxel, trunc, max_weight)
+        return vol.integrate(depths, self.K, self.xyzws[ids], self.translations[ids], 1.0, max_depth).extract_mesh(min_weight)
+
     @staticmethod
     def filter(values, threshold, data=None, less_than=False):
         mask = values <= threshold if less_than else values >= threshold

@@ -37,11 +37,12 @@ enum scratch_slot { SLOT_OBB_BOXES = 0, SLOT_SORT_PERM, SLOT_SORT_SCRATCH, SLOT_
                     SLOT_FUSE_XYZ, SLOT_FUSION, SLOT_PATCH_STATUS, SLOT_NRM, SLOT_NRM_CAMS, SLOT_QRY, SLOT_FLOOD, SLOT_COLOR,
                     SLOT_CVS_INST, SLOT_CVS_STATS, SLOT_QUADS, SLOT_GROW, SLOT_PVOTE, SLOT_PVOTE_BITS, SLOT_MESH, SLOT_ZKEY,
                     SLOT_ZCOUNTS, SLOT_KNN, SLOT_KNN_FLAG, SLOT_PLANES, SLOT_RASTER, SLOT_ZLUT, SLOT_SMOOTH, SLOT_FACE_GRAPH, SLOT_LIFT, SLOT_LIFT_TABLE,
-                    SLOT_COUNT };
+                    SLOT_TSDF, SLOT_COUNT };
 enum kept_slot { KEPT_GRAPH_OFFS = 0,                                      // f3d_radius_graph_count -> _fill: the offsets
                  KEPT_QRY_IN, KEPT_QRY_OFFS,                               // f3d_radius_query_count -> _fill: the queries, the offsets
                  KEPT_GRP_ORDER, KEPT_GRP_KEYS, KEPT_GRP_STARTS,           // f3d_group_by_id -> f3d_obb_extremes -> f3d_obb_hull_filter
                  KEPT_GRP_XYZ,                                             //   ... and, from the extremes call on, the cloud
+                 KEPT_TSDF,                                                // f3d_tsdf_extract_count -> _fill: the samples
                  KEPT_COUNT };
 enum { STAGE_MAX = 9,                                                      // staging buffers of one call: f3d_patch_match and f3d_door_window_quads take 9
        BACK_MAX = 5 };                                                     // outputs one call copies back: f3d_mesh_clean has 5
@@ -93,6 +94,13 @@ struct f3d_ctx {
     int64_t grp_n, grp_nids;
     int grp_dtype;
     bool grp_cloud;
+    // TSDF extract: dims and totals of the last count pass (tsdf_n = -1: none), its codes, ranks and offsets in SLOT_TSDF; tsdf_kept: that
+    // pass was f3d_tsdf_extract_count, whose samples KEPT_TSDF holds
+    int64_t tsdf_n, tsdf_nv, tsdf_nq;
+    int tsdf_dims[3];
+    bool tsdf_kept;
+    unsigned long long tsdf_counts[2];  // readback target of the count pass
+    int tsdf_grid_cap;                  // f3d_debug_tsdf_grid_cap (0 = the library's launch shapes)
     // view-chunked fused call in progress (f3d_fuse_chunked_begin_dev .. the chunk with v_end == nviews)
     struct { int active, next, nviews, h, w, nclasses, gather; int64_t n; const int32_t* perm; const void* xyz; f3d_fuse_todo lay; } chunk;
 };
@@ -376,7 +384,7 @@ f3d_ctx* f3d_ctx_create(int device) {
     }
     if (device < 0 || device >= count) { fail(nullptr, F3D_ERR_INVALID, "device %d out of range [0,%d)", device, count); return nullptr; }
     f3d_ctx* ctx = (f3d_ctx*)calloc(1, sizeof(f3d_ctx));
-    if (ctx) { ctx->graph_n = -1; ctx->grp_n = -1; ctx->qry_n = -1; }
+    if (ctx) { ctx->graph_n = -1; ctx->grp_n = -1; ctx->qry_n = -1; ctx->tsdf_n = -1; }
     if (!ctx) { fail(nullptr, F3D_ERR_NOMEM, "out of host memory"); return nullptr; }
     ctx->device = device;
     bool ok = hipSetDevice(device) == hipSuccess && hipStreamCreateWithFlags(&ctx->stream, hipStreamNonBlocking) == hipSuccess &&
@@ -3318,6 +3326,140 @@ int f3d_debug_raster_counts(f3d_ctx* ctx, const void* verts, f3d_dtype vdtype, i
     F3D_HIP(ctx, hipStreamSynchronize(s));
     if (ms) { ms[0] = fill_ms; ms[1] = raster_ms; }
     return F3D_OK;
+}
+
+// ---------------------------------------------------------------------------------------------
+// TSDF reconstruction: depth frames -> signed distance volume -> surface-nets mesh (include/f3d.h)
+// ---------------------------------------------------------------------------------------------
+static bool pos_finite(double x) { return x > 0.0 && x < INFINITY; }
+
+// voxels of a volume, or -1 for dims the entries refuse
+static int64_t tsdf_voxels(int nx, int ny, int nz) {
+    if (nx <= 0 || ny <= 0 || nz <= 0) return -1;
+    const int64_t xy = (int64_t)nx * ny;
+    if (xy >= ((int64_t)1 << 31) || xy * nz >= ((int64_t)1 << 31)) return -1;
+    return xy * nz;
+}
+
+static size_t depth_bytes(int depth_type, int nframes, int h, int w) {
+    return (size_t)nframes * h * w * (depth_type == F3D_DEPTH_U16 ? 2 : depth_type == F3D_DEPTH_F32 ? 4 : 8);
+}
+
+#define F3D_TSDF_BAD "bad arguments (dims >= 1 with a product < 2^31; vs, trunc, depth_scale, max_depth finite and > 0; max_weight in [1, 2^24]; a known depth type)"
+static bool tsdf_integrate_ok(const float* tsdf, const float* weight, int nx, int ny, int nz, const double* lo, double vs, double trunc,
+                              float max_weight, const void* depth, int depth_type, int nframes, int h, int w, double depth_scale,
+                              double max_depth, const f3d_view* views) {
+    return tsdf && weight && lo && tsdf_voxels(nx, ny, nz) > 0 && pos_finite(vs) && pos_finite(trunc) && pos_finite(depth_scale) &&
+           pos_finite(max_depth) && max_weight >= 1.0f && max_weight <= F3D_TSDF_MAX_WEIGHT &&
+           (depth_type == F3D_DEPTH_U16 || depth_type == F3D_DEPTH_F32 || depth_type == F3D_DEPTH_F64) && nframes >= 0 && h > 0 && w > 0 &&
+           (int64_t)h * w < ((int64_t)1 << 31) && (nframes == 0 || (depth && views));
+}
+
+int f3d_ctx_reserve_tsdf(f3d_ctx* ctx, int64_t nvoxels) {
+    int rc = enter(ctx); if (rc) return rc;
+    if (nvoxels < 0 || nvoxels >= ((int64_t)1 << 31)) return fail(ctx, F3D_ERR_INVALID, "ctx_reserve_tsdf: nvoxels must be in [0, 2^31)");
+    ctx->tsdf_n = -1;                                                          // the buffer may move: a counted sequence ends here
+    return reserve(ctx, {{SLOT_TSDF, f3d_tsdf_scratch_bytes(nvoxels)}});
+}
+
+int f3d_debug_tsdf_grid_cap(f3d_ctx* ctx, int blocks) {
+    int rc = enter(ctx); if (rc) return rc;
+    if (blocks < 0) return fail(ctx, F3D_ERR_INVALID, "debug_tsdf_grid_cap: blocks must not be negative");
+    ctx->tsdf_grid_cap = blocks;
+    return F3D_OK;
+}
+
+int f3d_tsdf_integrate_dev(f3d_ctx* ctx, float* tsdf, float* weight, int nx, int ny, int nz, const double lo[3], double vs, double trunc,
+                           float max_weight, const void* depth, int depth_type, int nframes, int h, int w, double depth_scale,
+                           double max_depth, const f3d_view* views_dev, void* stream) {
+    int rc = enter(ctx); if (rc) return rc;
+    if (!tsdf_integrate_ok(tsdf, weight, nx, ny, nz, lo, vs, trunc, max_weight, depth, depth_type, nframes, h, w, depth_scale, max_depth, views_dev))
+        return fail(ctx, F3D_ERR_INVALID, "tsdf_integrate: " F3D_TSDF_BAD);
+    if (nframes == 0) return F3D_OK;
+    F3D_HIP(ctx, f3d_launch_tsdf_integrate(tsdf, weight, nx, ny, nz, lo, vs, trunc, (double)max_weight, depth, depth_type, nframes, h, w, depth_scale,
+                                           max_depth, views_dev, ctx->tsdf_grid_cap, pick(ctx, stream)));
+    return F3D_OK;
+}
+
+int f3d_tsdf_integrate(f3d_ctx* ctx, float* tsdf, float* weight, int nx, int ny, int nz, const double lo[3], double vs, double trunc,
+                       float max_weight, const void* depth, int depth_type, int nframes, int h, int w, double depth_scale, double max_depth,
+                       const f3d_view* views) {
+    int rc = enter(ctx); if (rc) return rc;
+    if (!tsdf_integrate_ok(tsdf, weight, nx, ny, nz, lo, vs, trunc, max_weight, depth, depth_type, nframes, h, w, depth_scale, max_depth, views))
+        return fail(ctx, F3D_ERR_INVALID, "tsdf_integrate: " F3D_TSDF_BAD);
+    if (nframes == 0) return F3D_OK;
+    const size_t vol = (size_t)tsdf_voxels(nx, ny, nz) * 4;
+    staging st(ctx);
+    float* dt = st.inout(tsdf, vol);
+    float* dw = st.inout(weight, vol);
+    const void* dd = st.in((const char*)depth, depth_bytes(depth_type, nframes, h, w));
+    const f3d_view* dviews = st.in(views, sizeof(f3d_view) * (size_t)nframes);
+    if (!st.rc) st.rc = f3d_tsdf_integrate_dev(ctx, dt, dw, nx, ny, nz, lo, vs, trunc, max_weight, dd, depth_type, nframes, h, w, depth_scale, max_depth,
+                                               dviews, ctx->stream);
+    return st.finish();
+}
+
+int f3d_tsdf_extract_count_dev(f3d_ctx* ctx, const float* tsdf, const float* weight, int nx, int ny, int nz, float min_weight, int64_t* nv,
+                               int64_t* nt, void* stream) {
+    int rc = enter(ctx); if (rc) return rc;
+    const int64_t n = tsdf_voxels(nx, ny, nz);
+    if (!tsdf || !weight || !nv || !nt || n <= 0 || !(min_weight >= 1.0f))
+        return fail(ctx, F3D_ERR_INVALID, "tsdf_extract_count: bad arguments (dims >= 1 with a product < 2^31, min_weight >= 1)");
+    *nv = 0; *nt = 0; ctx->tsdf_n = -1; ctx->tsdf_kept = false;
+    hipStream_t s = pick(ctx, stream);
+    void* scratch;
+    if ((rc = ensure(ctx, SLOT_TSDF, f3d_tsdf_scratch_bytes(n), &scratch))) return rc;
+    F3D_HIP(ctx, f3d_launch_tsdf_count(tsdf, weight, nx, ny, nz, min_weight, scratch, ctx->tsdf_counts, ctx->tsdf_grid_cap, s));
+    F3D_HIP(ctx, hipStreamSynchronize(s));
+    if (ctx->tsdf_counts[1] >= ((unsigned long long)1 << 30))
+        return fail(ctx, F3D_ERR_INVALID, "tsdf_extract_count: %llu quads give 2^31 triangles or more", ctx->tsdf_counts[1]);
+    ctx->tsdf_n = n; ctx->tsdf_dims[0] = nx; ctx->tsdf_dims[1] = ny; ctx->tsdf_dims[2] = nz;
+    ctx->tsdf_nv = (int64_t)ctx->tsdf_counts[0]; ctx->tsdf_nq = (int64_t)ctx->tsdf_counts[1];
+    *nv = ctx->tsdf_nv; *nt = 2 * ctx->tsdf_nq;
+    return F3D_OK;
+}
+
+static bool tsdf_counted(const f3d_ctx* ctx, int nx, int ny, int nz) {
+    return ctx->tsdf_n > 0 && ctx->tsdf_dims[0] == nx && ctx->tsdf_dims[1] == ny && ctx->tsdf_dims[2] == nz;
+}
+
+int f3d_tsdf_extract_fill_dev(f3d_ctx* ctx, const float* tsdf, int nx, int ny, int nz, const double lo[3], double vs, double* verts,
+                              int32_t* tris, void* stream) {
+    int rc = enter(ctx); if (rc) return rc;
+    if (!tsdf_counted(ctx, nx, ny, nz)) return fail(ctx, F3D_ERR_INVALID, "tsdf_extract_fill: call f3d_tsdf_extract_count for this volume first");
+    if (!tsdf || !lo || !pos_finite(vs)) return fail(ctx, F3D_ERR_INVALID, "tsdf_extract_fill: bad arguments (vs finite and > 0)");
+    if (ctx->tsdf_nv == 0) return F3D_OK;
+    F3D_HIP(ctx, f3d_launch_tsdf_fill(tsdf, nx, ny, nz, lo, vs, ctx->scratch[SLOT_TSDF].p, verts, ctx->tsdf_nq ? tris : nullptr, ctx->tsdf_grid_cap,
+                                      pick(ctx, stream)));
+    return F3D_OK;
+}
+
+int f3d_tsdf_extract_count(f3d_ctx* ctx, const float* tsdf, const float* weight, int nx, int ny, int nz, float min_weight, int64_t* nv, int64_t* nt) {
+    int rc = enter(ctx); if (rc) return rc;
+    const int64_t n = tsdf_voxels(nx, ny, nz);
+    if (!tsdf || !weight || !nv || !nt || n <= 0 || !(min_weight >= 1.0f))
+        return fail(ctx, F3D_ERR_INVALID, "tsdf_extract_count: bad arguments (dims >= 1 with a product < 2^31, min_weight >= 1)");
+    staging st(ctx);
+    float* dt = (float*)st.keep(KEPT_TSDF, (size_t)n * 4);                     // f3d_tsdf_extract_fill reads the samples there
+    st.put(dt, tsdf, (size_t)n * 4);
+    const float* dw = st.in(weight, (size_t)n * 4);
+    if (!st.rc) st.rc = f3d_tsdf_extract_count_dev(ctx, dt, dw, nx, ny, nz, min_weight, nv, nt, ctx->stream);
+    if ((rc = st.finish())) { ctx->tsdf_n = -1; return rc; }
+    ctx->tsdf_kept = true;
+    return F3D_OK;
+}
+
+int f3d_tsdf_extract_fill(f3d_ctx* ctx, int nx, int ny, int nz, const double lo[3], double vs, double* verts, int32_t* tris) {
+    int rc = enter(ctx); if (rc) return rc;
+    if (!tsdf_counted(ctx, nx, ny, nz) || !ctx->tsdf_kept)
+        return fail(ctx, F3D_ERR_INVALID, "tsdf_extract_fill: call f3d_tsdf_extract_count for this volume first");
+    if (!lo || !pos_finite(vs)) return fail(ctx, F3D_ERR_INVALID, "tsdf_extract_fill: bad arguments (vs finite and > 0)");
+    if (ctx->tsdf_nv == 0) return F3D_OK;
+    staging st(ctx);
+    double* dv = st.out(verts, (size_t)ctx->tsdf_nv * 24);
+    int32_t* dtri = ctx->tsdf_nq ? st.out(tris, (size_t)ctx->tsdf_nq * 24) : nullptr;
+    if (!st.rc) st.rc = f3d_tsdf_extract_fill_dev(ctx, (const float*)ctx->kept[KEPT_TSDF].p, nx, ny, nz, lo, vs, dv, dtri, ctx->stream);
+    return st.finish();
 }
 
 }  // extern "C"

@@ -649,6 +649,19 @@ hipError_t f3d_launch_raster(const void* verts, int vdtype, const void* tris, in
                              int h, int w, double z_far, unsigned long long* zkey, long long* straddling, void* scratch, unsigned list_cap,
                              bool stats, hipStream_t s);
 
+// TSDF reconstruction (f3d_tsdf.hip; the contract is in include/f3d.h).  Device pointers, lo on the host.  Enqueue only.  The count
+// pass leaves the voxel codes, the cell ranks and the quad offsets in `scratch` (f3d_tsdf_scratch_bytes(nx * ny * nz)) for the fill pass
+// and enqueues the readback of counts_host = {active cells, quads} (the caller synchronises).  grid_cap > 0: at most that many blocks
+// per launch (a test forces the grid-stride passes at a small size; no result depends on it).
+size_t f3d_tsdf_scratch_bytes(int64_t nvoxels);
+hipError_t f3d_launch_tsdf_integrate(float* tsdf, float* weight, int nx, int ny, int nz, const double lo[3], double vs, double trunc, double max_weight,
+                                     const void* depth, int depth_type, int nframes, int h, int w, double depth_scale, double max_depth,
+                                     const f3d_view* views_dev, int grid_cap, hipStream_t s);
+hipError_t f3d_launch_tsdf_count(const float* tsdf, const float* weight, int nx, int ny, int nz, float min_weight, void* scratch,
+                                 unsigned long long* counts_host, int grid_cap, hipStream_t s);
+hipError_t f3d_launch_tsdf_fill(const float* tsdf, int nx, int ny, int nz, const double lo[3], double vs, const void* scratch, double* verts,
+                                int32_t* tris, int grid_cap, hipStream_t s);
+
 // plane table of a cloud over its adjacency (f3d_planes.hip).  Device pointers (counts int64 [4] too); normals (may be NULL: PCA of the
 // rows) and normals_out (may be NULL; written in PCA mode only) float64 [n, 3].  n >= 1.  Enqueues on `s` and synchronises it every few
 // attach rounds.  A neighbour outside [0, n) sets F3D_DEVERR_PLANES and nothing is written.  scratch: f3d_planes_scratch_bytes(n)

@@ -15,7 +15,7 @@ from pathlib import Path
 
 import numpy as np
 
-from f3d.tensors import dtype_code, host_csr, index_code
+from f3d.tensors import depth_code, dtype_code, host_csr, index_code
 
 __all__ = ['F3DError', 'F3DUnavailable', 'Context', 'default_context', 'library', 'library_path',
            'views_build', 'frustum_data', 'quat_inverse', 'VIEW_DOUBLES', 'F64', 'F32', 'FUSE_SORT', 'FUSE_GATHER']
@@ -35,6 +35,7 @@ I64, I32 = 0, 1              # f3d_itype: the index type of mesh triangles
 VOTES_F64, VOTES_U16 = 0, 1  # f3d_vtype: the element type of a vote matrix handed to smooth_votes / smooth_segment
 SMOOTH_MAX_COLS = 256        # the widest vote matrix smooth_votes / smooth_segment take
 KNN_MAX_K = 32               # F3D_KNN_MAX_K: the largest k of knn_query / transfer_labels
+TSDF_SCAN_TILE = 2048        # F3D_TSDF_SCAN_TILE: counts per tile of the extract scans (scanned by blocks of 256 threads)
 
 
 class F3DError(RuntimeError):
@@ -228,6 +229,14 @@ def library():
         'f3d_ctx_reserve_knn': (i32, [vp, i64]),
         'f3d_estimate_normals': (i32, [vp, vp, i64, vp, dbl, i32, i32, vp, vp, vp]),
         'f3d_estimate_normals_batch_dev': (i32, [vp, vp, i32, i64, vp, dbl, i32, i32, vp, vp, vp, vp]),
+        'f3d_tsdf_integrate': (i32, [vp, vp, vp, i32, i32, i32, vp, dbl, dbl, flt, vp, i32, i32, i32, i32, dbl, dbl, vp]),
+        'f3d_tsdf_integrate_dev': (i32, [vp, vp, vp, i32, i32, i32, vp, dbl, dbl, flt, vp, i32, i32, i32, i32, dbl, dbl, vp, vp]),
+        'f3d_tsdf_extract_count': (i32, [vp, vp, vp, i32, i32, i32, flt, vp, vp]),
+        'f3d_tsdf_extract_fill': (i32, [vp, i32, i32, i32, vp, dbl, vp, vp]),
+        'f3d_tsdf_extract_count_dev': (i32, [vp, vp, vp, i32, i32, i32, flt, vp, vp, vp]),
+        'f3d_tsdf_extract_fill_dev': (i32, [vp, vp, i32, i32, i32, vp, dbl, vp, vp, vp]),
+        'f3d_ctx_reserve_tsdf': (i32, [vp, i64]),
+        'f3d_debug_tsdf_grid_cap': (i32, [vp, i32]),
     }
     for name, (res, args) in protos.items():
         fn = getattr(lib, name)          # AttributeError here = header/library mismatch
@@ -342,6 +351,27 @@ def _xyz(points):
     if p.dtype == np.float32:
         return np.ascontiguousarray(p), F32
     return np.ascontiguousarray(p, dtype=np.float64), F64
+
+
+def _tsdf_state(tsdf, weight):
+    """(nz, ny, nx) of the two state arrays of a TSDF volume: C-contiguous float32 [nz, ny, nx] NumPy arrays, written in place."""
+    for a in (tsdf, weight):
+        if not isinstance(a, np.ndarray) or a.dtype != np.float32 or a.ndim != 3 or not a.flags.c_contiguous or not a.flags.writeable:
+            raise ValueError('tsdf and weight must be writeable C-contiguous float32 [nz, ny, nx] arrays')
+    if tsdf.shape != weight.shape:
+        raise ValueError(f'tsdf {tsdf.shape} and weight {weight.shape} differ in shape')
+    return tsdf.shape
+
+
+def _tsdf_frames(lo, depths, views):
+    """(lo float64 [3], depths [F, h, w] contiguous, its depth code, views [F, 88]) of a tsdf_integrate call."""
+    d = np.ascontiguousarray(depths)
+    if d.ndim != 3:
+        raise ValueError(f'depths must be [F, h, w], got {d.shape}')
+    views = _views(views)
+    if len(views) != len(d):
+        raise ValueError(f'{len(views)} views for {len(d)} depth frames')
+    return _f64(lo, (3,)), d, depth_code(d), views
 
 
 def _knn_k(k):
@@ -1091,6 +1121,32 @@ class Context:
         self._check(self._lib.f3d_unproject_depth(self._h, _ptr(d), code, d.shape[0], d.shape[1], _ptr(K), float(depth_scale), _ptr(q), _ptr(t), _ptr(out)))
         return out
 
+    def reserve_tsdf(self, nvoxels):
+        """Size the scratch of tsdf_extract_count_dev / tsdf_extract_fill_dev for volumes of up to nvoxels voxels."""
+        self._check(self._lib.f3d_ctx_reserve_tsdf(self._h, int(nvoxels)))
+
+    def debug_tsdf_grid_cap(self, blocks):
+        """Test hook: at most `blocks` blocks per grid-stride TSDF launch of this context (0 = the library's launch shapes)."""
+        self._check(self._lib.f3d_debug_tsdf_grid_cap(self._h, int(blocks)))
+
+    def tsdf_integrate(self, tsdf, weight, lo, voxel, trunc, max_weight, depths, views, depth_scale=1.0, max_depth=10.0):
+        """Integrate depth frames [F, h, w] (uint16, float32 or float64) into the volume IN PLACE (f3d.h f3d_tsdf_integrate): tsdf and
+        weight are C-contiguous float32 [nz, ny, nx] arrays, views the [F, 88] table of views_build."""
+        nz, ny, nx = _tsdf_state(tsdf, weight)
+        lo, d, code, views = _tsdf_frames(lo, depths, views)
+        self._check(self._lib.f3d_tsdf_integrate(self._h, _ptr(tsdf), _ptr(weight), nx, ny, nz, _ptr(lo), float(voxel), float(trunc), float(max_weight),
+                                                 _ptr(d), code, d.shape[0], d.shape[1], d.shape[2], float(depth_scale), float(max_depth), _ptr(views)))
+
+    def tsdf_extract(self, tsdf, weight, lo, voxel, min_weight=1.0):
+        """Surface-nets mesh of the volume (f3d.h f3d_tsdf_extract_count -> _fill) -> (vertices float64 [V, 3], triangles int32 [M, 3])."""
+        nz, ny, nx = _tsdf_state(tsdf, weight)
+        lo = _f64(lo, (3,))
+        nv, nt = C.c_int64(0), C.c_int64(0)
+        self._check(self._lib.f3d_tsdf_extract_count(self._h, _ptr(tsdf), _ptr(weight), nx, ny, nz, float(min_weight), C.byref(nv), C.byref(nt)))
+        verts, tris = np.empty((nv.value, 3), np.float64), np.empty((nt.value, 3), np.int32)
+        self._check(self._lib.f3d_tsdf_extract_fill(self._h, nx, ny, nz, _ptr(lo), float(voxel), _ptr(verts), _ptr(tris)))
+        return verts, tris
+
     def radius_graph(self, points, radius):
         """KDTree(points).query_radius(points, r=radius) (fusion.py:374-375) as CSR: (offsets int64 [n+1], neighbours int32)."""
         p, dt = _xyz(points)
@@ -1356,6 +1412,27 @@ class Context:
                                                      int(min_overlap), seg_classes_ptr, int(min_points), ids_ptr, support_ptr, seen_ptr,
                                                      seg2inst_ptr, inst_points_ptr, _ptr(stats), stream))
         return stats
+
+    def tsdf_integrate_dev(self, tsdf_ptr, weight_ptr, dims, lo, voxel, trunc, max_weight, depth_ptr, depth_type, nframes, h, w, depth_scale,
+                           max_depth, views_ptr, stream=None):
+        """dims = (nx, ny, nz); lo on the host; everything else device pointers (f3d.h f3d_tsdf_integrate_dev).  Enqueue only."""
+        lo = _f64(lo, (3,))
+        nx, ny, nz = (int(x) for x in dims)
+        self._check(self._lib.f3d_tsdf_integrate_dev(self._h, tsdf_ptr, weight_ptr, nx, ny, nz, _ptr(lo), float(voxel), float(trunc), float(max_weight),
+                                                     depth_ptr, int(depth_type), int(nframes), int(h), int(w), float(depth_scale), float(max_depth),
+                                                     views_ptr, stream))
+
+    def tsdf_extract_count_dev(self, tsdf_ptr, weight_ptr, dims, min_weight=1.0, stream=None):
+        """-> (nv, nt) of the volume's mesh; the ranks stay in the context for tsdf_extract_fill_dev.  Synchronises `stream` once."""
+        nx, ny, nz = (int(x) for x in dims)
+        nv, nt = C.c_int64(0), C.c_int64(0)
+        self._check(self._lib.f3d_tsdf_extract_count_dev(self._h, tsdf_ptr, weight_ptr, nx, ny, nz, float(min_weight), C.byref(nv), C.byref(nt), stream))
+        return nv.value, nt.value
+
+    def tsdf_extract_fill_dev(self, tsdf_ptr, dims, lo, voxel, verts_ptr, tris_ptr, stream=None):
+        lo = _f64(lo, (3,))
+        nx, ny, nz = (int(x) for x in dims)
+        self._check(self._lib.f3d_tsdf_extract_fill_dev(self._h, tsdf_ptr, nx, ny, nz, _ptr(lo), float(voxel), verts_ptr, tris_ptr, stream))
 
     def take_device_error(self, stream=None):
         self._check(self._lib.f3d_take_device_error(self._h, stream))

@@ -63,6 +63,14 @@ def index_code(a):
     return f3d.I32 if a.dtype.itemsize == 4 else f3d.I64
 
 
+def depth_code(depths):
+    """F3D_DEPTH_F64 / F32 / U16 (0 / 1 / 2) of a float64 / float32 / uint16 depth array or tensor, TypeError for anything else."""
+    name = str(depths.dtype).replace('torch.', '')
+    if name not in ('float64', 'float32', 'uint16'):
+        raise TypeError(f'depth frames must be uint16, float32 or float64, got {depths.dtype}')
+    return {'float64': 0, 'float32': 1, 'uint16': 2}[name]
+
+
 def host_csr(offsets, neighbours, n, message='offsets must have n+1 entries ending at len(neighbours)'):
     """(offsets int64 [n + 1], neighbours int32 [offsets[n]]) as contiguous NumPy arrays, checked: the kernels read every row
     the offsets name."""

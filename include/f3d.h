@@ -16,9 +16,9 @@
  *     through the context's staging buffers, the kernels run on the context's stream, outputs are
  *     copied back, and the call returns after the stream has drained (NumPy drop-in).  Staging is
  *     separate from the scratch of the _dev functions and holds nothing once a call has returned.
- *     Three host-pointer sequences keep data on the device between their calls, in buffers of their
- *     own: f3d_radius_graph_count -> _fill, f3d_radius_query_count -> _fill and f3d_group_by_id ->
- *     f3d_obb_extremes -> f3d_obb_hull_filter.  Any other call on the context may come in between;
+ *     Four host-pointer sequences keep data on the device between their calls, in buffers of their
+ *     own: f3d_radius_graph_count -> _fill, f3d_radius_query_count -> _fill, f3d_tsdf_extract_count -> _fill
+ *     and f3d_group_by_id -> f3d_obb_extremes -> f3d_obb_hull_filter.  Any other call on the context may come in between;
  *     a sequence ends where its first call is made again.  Staging and these buffers grow on first
  *     use like scratch (and a strict context refuses that); f3d_ctx_reserve*() does not size them.
  *   - "_dev" functions take DEVICE pointers and a hipStream_t (as void*; NULL = the context's
@@ -1146,6 +1146,75 @@ int f3d_estimate_normals(f3d_ctx* ctx, const double* xyz, int64_t n, const doubl
 int f3d_estimate_normals_batch_dev(f3d_ctx* ctx, const double* xyz, int nframes, int64_t n, const double* cam_centres,
                                    double radius, int max_nn, int orient, double* normals, int32_t* counts, int32_t* neighbours,
                                    void* stream);
+
+/* ---- TSDF reconstruction: a triangle mesh from posed depth frames (no reference counterpart) ------------------------------ */
+/* The reference takes its mesh from an external exporter; a capture of posed depth frames has none.  These entries integrate the
+ * frames into a truncated signed distance volume and extract a triangle mesh from it by surface nets (no lookup table).  All
+ * arithmetic is float64 without contraction, every product, sum and division as written; storage is float32.
+ *   volume     dims (nx, ny, nz), each >= 1, nx * ny * nz < 2^31; origin lo[3] (float64), voxel edge vs > 0.  Linear index
+ *              lin = (k * ny + j) * nx + i (x fastest); voxel centre c_a = lo[a] + ((double)idx_a + 0.5) * vs.  The state is two
+ *              caller-owned arrays, tsdf float32 [nz, ny, nx] and weight float32 [nz, ny, nx]; a fresh volume is all zeros.  The
+ *              library keeps no pointer to the state between calls.
+ *   integrate  nframes depth images [F, h, w] of type F3D_DEPTH_U16 / F32 / F64 with the depth_scale of f3d_unproject_depth; view f
+ *              is views[f] from f3d_views_build.  Per voxel the frames are applied in ascending f (the running average depends on
+ *              the order).  For each frame:
+ *                1. (h0, h1, h2) = f3d_project_h(K, qinv, t, c); skip unless h2 > 0.
+ *                2. x = h0 / h2, y = h1 / h2; skip unless x >= 0 && x < w && y >= 0 && y < h (NaN fails); u = (int)floor(x),
+ *                   v = (int)floor(y): the floor pixel of points2pixel, no interpolation.
+ *                3. d = (double)raw[v, u] / depth_scale; skip unless d > 0 && d <= max_depth (NaN and inf fail).
+ *                4. sdf = d - h2; skip if sdf < -trunc.  val = sdf / trunc, and val = 1.0 if val > 1.0.
+ *                5. T = (float)(((double)T_old * (double)w_old + val) / ((double)w_old + 1.0)).
+ *                6. w = (float)min((double)w_old + 1.0, (double)max_weight).
+ *              The five frustum planes of the view play no part in the result.  trunc > 0; max_weight in [1, 2^24].
+ *   extract    a voxel is observed iff weight >= min_weight (min_weight >= 1) and inside iff it is observed and tsdf < 0 (+0.0 and
+ *              -0.0 are outside).  Cell (i, j, k), 0 <= idx_a <= n_a - 2, has the 8 voxels idx + {0, 1}^3 as corners and is active
+ *              iff all 8 are observed and they are not all on one side.
+ *   vertex     of an active cell.  For an axis a let (b, c) be the next two axes cyclically (x -> (y, z), y -> (z, x), z -> (x, y)).
+ *              Cell edge e = 4 a + 2 oc + ob (ob, oc in {0, 1}) runs from the corner with local coordinates L[a] = 0, L[b] = ob,
+ *              L[c] = oc to the one with L[a] = 1; it crosses iff the insideness of its ends differs, at L with
+ *              L[a] = s0 / (s0 - s1), s0 and s1 the float32 samples at the two ends widened to double.  Each component is summed
+ *              over the crossing edges in ascending e, starting from 0.0; local = sum / (double)count;
+ *              vert_a = lo[a] + (((double)cell_a + 0.5) + local_a) * vs.  Vertex ids are the ranks of the active cells in ascending
+ *              linear cell index (the voxel formula).
+ *   faces      for every voxel p = (i, j, k) and axis a with p_a <= n_a - 2: both ends of the grid edge p -> p + e_a observed, their
+ *              insideness different, and the four cells around the edge in range and active: A = p - e_b - e_c, B = p - e_c, C = p,
+ *              D = p - e_b.  Each such edge gives one quad, (A, B, C, D) when p is inside (the normal points along +a, from inside to
+ *              outside), else (A, D, C, B); it splits into the triangles (q0, q1, q2) and (q0, q2, q3).  The quads come in
+ *              ascending 3 * lin(p) + a, the two triangles of a quad are consecutive.
+ * Outputs: verts float64 [nv, 3], tris int32 [nt, 3] of vertex ids; nv, nt < 2^31, otherwise F3D_ERR_INVALID.  The result depends on
+ * nothing but the state, min_weight, lo and vs: not on the launch shape, timing or the scan's tiling (tiles of F3D_TSDF_SCAN_TILE counts,
+ * scanned by blocks of 256).
+ * f3d_tsdf_extract_count -> f3d_tsdf_extract_fill is a sequence (see the preamble): the cell ranks and the quad offsets stay in
+ * context scratch, the host-pointer count also keeps its copy of tsdf; the sequence ends where count is called again.  The totals come
+ * back like those of f3d_radius_graph_count_dev: through host pointers, after one synchronisation of the stream.  The _dev fill takes
+ * the same tsdf and dims again.  Either output of fill may be NULL.
+ * F3D_ERR_INVALID, with nothing written (but for the one case named last): NULLs; non-positive dims or a product >= 2^31; vs, trunc, depth_scale or max_depth not finite
+ * and positive; max_weight outside [1, 2^24]; min_weight < 1 (or NaN); an unknown depth type; h, w <= 0 or nframes < 0; a fill without
+ * its count, or with other dims; a count that finds 2^30 quads or more (known only after the passes have run: *nv and *nt are then 0 and
+ * the sequence is ended).  Non-finite depths or poses are no error: they contribute nothing.  nframes == 0 is a no-op; a volume
+ * without an active cell gives nv = nt = 0.
+ * Scratch: 11 bytes per voxel + 4 per scan tile; f3d_ctx_reserve_tsdf(nvoxels) sizes it, and a strict context then allocates nothing in
+ * the three _dev entries.  Reserving may move the scratch, so it ends a counted sequence: count again before the fill.
+ * f3d_debug_tsdf_grid_cap (test hook): blocks > 0 caps the grid of every grid-stride TSDF launch of the context at that many blocks, so that
+ * a small volume takes many passes per block; 0 = the library's launch shapes.  No result depends on it. */
+#define F3D_TSDF_SCAN_TILE 2048
+#define F3D_TSDF_MAX_WEIGHT 16777216.0f
+int f3d_tsdf_integrate(f3d_ctx* ctx, float* tsdf, float* weight, int nx, int ny, int nz, const double lo[3], double vs, double trunc,
+                       float max_weight, const void* depth, int depth_type, int nframes, int h, int w, double depth_scale,
+                       double max_depth, const f3d_view* views);
+int f3d_tsdf_integrate_dev(f3d_ctx* ctx, float* tsdf, float* weight, int nx, int ny, int nz, const double lo[3] /*host*/, double vs,
+                           double trunc, float max_weight, const void* depth, int depth_type, int nframes, int h, int w,
+                           double depth_scale, double max_depth, const f3d_view* views_dev /*device [F]*/, void* stream);
+int f3d_tsdf_extract_count(f3d_ctx* ctx, const float* tsdf, const float* weight, int nx, int ny, int nz, float min_weight, int64_t* nv,
+                           int64_t* nt);
+int f3d_tsdf_extract_fill(f3d_ctx* ctx, int nx, int ny, int nz, const double lo[3], double vs, double* verts /*[nv,3]*/,
+                          int32_t* tris /*[nt,3]*/);
+int f3d_tsdf_extract_count_dev(f3d_ctx* ctx, const float* tsdf, const float* weight, int nx, int ny, int nz, float min_weight,
+                               int64_t* nv /*host*/, int64_t* nt /*host*/, void* stream);
+int f3d_tsdf_extract_fill_dev(f3d_ctx* ctx, const float* tsdf, int nx, int ny, int nz, const double lo[3] /*host*/, double vs,
+                              double* verts, int32_t* tris, void* stream);
+int f3d_ctx_reserve_tsdf(f3d_ctx* ctx, int64_t nvoxels);
+int f3d_debug_tsdf_grid_cap(f3d_ctx* ctx, int blocks);
 
 #ifdef __cplusplus
 }
