@@ -3462,4 +3462,86 @@ int f3d_tsdf_extract_fill(f3d_ctx* ctx, int nx, int ny, int nz, const double lo[
     return st.finish();
 }
 
+// ---------------------------------------------------------------------------------------------
+// feature fusion: per-point pooling of per-pixel feature maps over views (f3d_features.hip)
+// ---------------------------------------------------------------------------------------------
+#define F3D_FEAT_BAD F3D_RENDER_BAD ", hf, wf >= 1 with hf * wf < 2^31, d in [1, 4096], float16 / float32 features, depth_tol >= 0, views_per_pass >= 0"
+
+static bool features_args_ok(const void* xyz, f3d_dtype dtype, int64_t n, const void* views, int nviews, int h, int w, const void* feats,
+                             f3d_ftype ftype, int hf, int wf, int d, int splat, double depth_tol, const float* sums, const int32_t* counts,
+                             int views_per_pass) {
+    return render_args_ok(xyz, dtype, n, views, nviews, h, w, splat) && (ftype == F3D_FEAT_F16 || ftype == F3D_FEAT_F32) && hf >= 1 && wf >= 1 &&
+           (int64_t)hf * wf <= 0x7fffffffLL && d >= 1 && d <= 4096 && depth_tol >= 0.0 && views_per_pass >= 0 &&
+           (n == 0 || (sums && counts)) && (nviews == 0 || feats);
+}
+
+int f3d_fuse_features_dev(f3d_ctx* ctx, const void* xyz, f3d_dtype dtype, int64_t n, const f3d_view* views_dev, int nviews, int h, int w,
+                          const void* feats, f3d_ftype ftype, int hf, int wf, int d, int splat, double depth_tol, float* sums, int32_t* counts,
+                          int views_per_pass, void* stream) {
+    int rc = enter(ctx); if (rc) return rc;
+    if (!features_args_ok(xyz, dtype, n, views_dev, nviews, h, w, feats, ftype, hf, wf, d, splat, depth_tol, sums, counts, views_per_pass))
+        return fail(ctx, F3D_ERR_INVALID, "fuse_features: " F3D_FEAT_BAD);
+    if (n == 0 || nviews == 0) return F3D_OK;
+    hipStream_t s = pick(ctx, stream);
+    const size_t hw = (size_t)h * w, fbytes = (size_t)hf * wf * d * (ftype == F3D_FEAT_F16 ? 2 : 4);
+    const bool occl = depth_tol < INFINITY;                                  // +inf: every sample is visible, no keys
+    const int per = render_pass_views(nviews, h, w, views_per_pass);
+    unsigned long long* zkey = nullptr;
+    if (occl) {
+        void* zk;
+        if ((rc = ensure(ctx, SLOT_ZKEY, (size_t)per * hw * 8, &zk))) return rc;
+        zkey = (unsigned long long*)zk;
+    }
+    for (int v0 = 0; v0 < nviews; v0 += per) {                               // a pass: render, then gather (sums in ascending view order)
+        const int nv = nviews - v0 < per ? nviews - v0 : per;
+        if (occl) {
+            F3D_HIP(ctx, f3d_launch_zkey_fill(zkey, (size_t)nv * hw, s));
+            F3D_HIP(ctx, f3d_launch_zsplat(xyz, dtype, n, views_dev + v0, nv, h, w, splat, zkey, nullptr, s));
+        }
+        F3D_HIP(ctx, f3d_launch_fuse_features(xyz, dtype, n, views_dev + v0, nv, h, w, (const char*)feats + (size_t)v0 * fbytes, ftype, hf, wf, d,
+                                              zkey, depth_tol, sums, counts, s));
+    }
+    return F3D_OK;
+}
+
+int f3d_fuse_features(f3d_ctx* ctx, const void* xyz, f3d_dtype dtype, int64_t n, const f3d_view* views, int nviews, int h, int w,
+                      const void* feats, f3d_ftype ftype, int hf, int wf, int d, int splat, double depth_tol, float* sums, int32_t* counts,
+                      int views_per_pass) {
+    int rc = enter(ctx); if (rc) return rc;
+    if (!features_args_ok(xyz, dtype, n, views, nviews, h, w, feats, ftype, hf, wf, d, splat, depth_tol, sums, counts, views_per_pass))
+        return fail(ctx, F3D_ERR_INVALID, "fuse_features: " F3D_FEAT_BAD);
+    if (n == 0 || nviews == 0) return F3D_OK;
+    staging st(ctx);
+    const void* dxyz = st.in(xyz, xyz_bytes(dtype, n));
+    const f3d_view* dviews = st.in(views, sizeof(f3d_view) * (size_t)nviews);
+    const char* dfeats = st.in((const char*)feats, (size_t)nviews * hf * wf * d * (ftype == F3D_FEAT_F16 ? 2 : 4));
+    float* dsums = st.inout(sums, (size_t)n * d * 4);
+    int32_t* dcounts = st.inout(counts, (size_t)n * 4);
+    if (!st.rc) st.rc = f3d_fuse_features_dev(ctx, dxyz, dtype, n, dviews, nviews, h, w, dfeats, ftype, hf, wf, d, splat, depth_tol, dsums, dcounts,
+                                              views_per_pass, ctx->stream);
+    return st.finish();
+}
+
+int f3d_features_finalize_dev(f3d_ctx* ctx, const float* sums, const int32_t* counts, int64_t n, int d, int normalize, float* out, void* stream) {
+    int rc = enter(ctx); if (rc) return rc;
+    if (n < 0 || d < 1 || d > 4096 || (n > 0 && (!sums || !counts || !out)))
+        return fail(ctx, F3D_ERR_INVALID, "features_finalize: bad arguments (n >= 0, d in [1, 4096])");
+    if (n == 0) return F3D_OK;
+    F3D_HIP(ctx, f3d_launch_features_finalize(sums, counts, n, d, normalize, out, pick(ctx, stream)));
+    return F3D_OK;
+}
+
+int f3d_features_finalize(f3d_ctx* ctx, const float* sums, const int32_t* counts, int64_t n, int d, int normalize, float* out) {
+    int rc = enter(ctx); if (rc) return rc;
+    if (n < 0 || d < 1 || d > 4096 || (n > 0 && (!sums || !counts || !out)))
+        return fail(ctx, F3D_ERR_INVALID, "features_finalize: bad arguments (n >= 0, d in [1, 4096])");
+    if (n == 0) return F3D_OK;
+    staging st(ctx);
+    float* drows = st.in(sums, (size_t)n * d * 4);                           // finalised in place on the device copy
+    const int32_t* dcounts = st.in(counts, (size_t)n * 4);
+    st.back(out, drows, (size_t)n * d * 4);
+    if (!st.rc) st.rc = f3d_features_finalize_dev(ctx, drows, dcounts, n, d, normalize, drows, ctx->stream);
+    return st.finish();
+}
+
 }  // extern "C"

@@ -1,8 +1,10 @@
 // Internal interface between the C-ABI layer (f3d_capi.cpp) and the kernel sources (f3d_*.hip), and the launch helpers they share.
 #pragma once
 #include <hip/hip_runtime.h>
+#include <float.h>
 #include <stdint.h>
 #include "f3d.h"
+#include "f3d_math.h"
 
 // sticky device error word of a context: one bit per operation, so that an IndexError recorded by one operation is
 // neither blamed on nor silently skips another one that shares the context
@@ -612,6 +614,17 @@ hipError_t f3d_launch_mesh_face_graph(const void* verts, int vdtype, int64_t nv,
                                       double cos_crease, int64_t* offsets, int32_t* neighbours, int64_t cap, void* scratch, int64_t* counts,
                                       int* err, hipStream_t s);
 
+// the sample of point p in view vw, if it has one: pixel (u, v) inside the w x h image, float32 depth z32 in [FLT_MIN, inf)
+// (shared by f3d_render.hip and f3d_features.hip; f3d_math.h carries #pragma clang fp contract(off))
+__device__ __forceinline__ bool f3d_sample(const f3d_view& vw, f3d_p3 p, int h, int w, int& u, int& v, float& z32) {
+    if (!f3d_inside_view(vw, p)) return false;                             // a4 first: most pairs end here
+    const f3d_p3 hp = f3d_project_h(vw.K, vw.qinv, vw.t, p);
+    u = f3d_floor_to_i32(hp.x / hp.z);
+    v = f3d_floor_to_i32(hp.y / hp.z);
+    z32 = (float)hp.z;                                                     // round to nearest even
+    return u >= 0 && u < w && v >= 0 && v < h && z32 >= FLT_MIN && z32 < INFINITY;   // (NaN fails both depth tests)
+}
+
 // point-splat z-buffer and the visibility-tested forward vote (f3d_render.hip).  zkey: uint64 [nv, h, w] depth keys of the nv views of
 // a pass (views_dev / masks point at the pass's first view); counts (device uint64 [3], may be NULL) += {samples, cells covered,
 // atomics issued}.  Enqueue only.
@@ -702,3 +715,11 @@ size_t f3d_lift_scratch_bytes(int64_t pixels, int64_t npoints, int64_t nseg);
 size_t f3d_lift_table_bytes(uint64_t slots, int64_t cap);
 hipError_t f3d_launch_lift_incidence(const f3d_lift_job& j);
 hipError_t f3d_launch_lift_merge(const f3d_lift_job& j, int64_t stats[F3D_LIFT_NSTATS]);
+
+// feature fusion (f3d_features.hip; the contract is in include/f3d.h).  views_dev, feats and zkey point at the first view of a pass of
+// nv views; zkey: the splat keys of the same cloud for those views, or NULL when every sample is visible (depth_tol = +inf).  The
+// launcher picks the group shape from d and ftype.  Enqueue only, no scratch.
+hipError_t f3d_launch_fuse_features(const void* xyz, int dtype, int64_t n, const f3d_view* views_dev, int nv, int h, int w, const void* feats,
+                                    int ftype, int hf, int wf, int d, const unsigned long long* zkey, double depth_tol, float* sums,
+                                    int32_t* counts, hipStream_t s);
+hipError_t f3d_launch_features_finalize(const float* sums, const int32_t* counts, int64_t n, int d, int normalize, float* out, hipStream_t s);

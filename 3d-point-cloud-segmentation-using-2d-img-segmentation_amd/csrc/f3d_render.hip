@@ -22,16 +22,6 @@ __global__ __launch_bounds__(F3D_BLOCK) void k_zkey_fill(unsigned long long* __r
     for (size_t i = (size_t)blockIdx.x * F3D_BLOCK + threadIdx.x; i < cells; i += (size_t)gridDim.x * F3D_BLOCK) zkey[i] = F3D_ZKEY_EMPTY;
 }
 
-// the sample of point p in view vw, if it has one: pixel (u, v) inside the w x h image, float32 depth z32 in [FLT_MIN, inf)
-__device__ __forceinline__ bool f3d_sample(const f3d_view& vw, f3d_p3 p, int h, int w, int& u, int& v, float& z32) {
-    if (!f3d_inside_view(vw, p)) return false;                             // a4 first: most pairs end here
-    const f3d_p3 hp = f3d_project_h(vw.K, vw.qinv, vw.t, p);
-    u = f3d_floor_to_i32(hp.x / hp.z);
-    v = f3d_floor_to_i32(hp.y / hp.z);
-    z32 = (float)hp.z;                                                     // round to nearest even
-    return u >= 0 && u < w && v >= 0 && v < h && z32 >= FLT_MIN && z32 < INFINITY;   // (NaN fails both depth tests)
-}
-
 // One thread per point, blockIdx.y = view of the pass (the view record is wave-uniform: scalar loads).  A cell is read before the
 // atomic and the atomic skipped when the cell already holds a smaller key: under contention most samples lose, and min is
 // idempotent.  The read is an agent-scope atomic load (L2): a stale larger value would only cost a needless atomic, never a result.

@@ -32,6 +32,8 @@ NORMALS_MAX_NN = 64          # F3D_NORMALS_MAX_NN: the largest max_nn of estimat
 QUAD_OK, QUAD_HORIZONTAL, QUAD_NO_CANDIDATE = 0, 1, 2   # per-instance status of door_window_quads (f3d.h F3D_QUAD_*)
 QUADS_MAX_INST = 65535       # F3D_QUADS_MAX_INST
 I64, I32 = 0, 1              # f3d_itype: the index type of mesh triangles
+FEAT_F16, FEAT_F32 = 0, 1    # f3d_ftype: the element type of feature maps
+FEAT_MAX_D = 4096            # the most channels of a feature row (f3d.h f3d_fuse_features)
 VOTES_F64, VOTES_U16 = 0, 1  # f3d_vtype: the element type of a vote matrix handed to smooth_votes / smooth_segment
 SMOOTH_MAX_COLS = 256        # the widest vote matrix smooth_votes / smooth_segment take
 KNN_MAX_K = 32               # F3D_KNN_MAX_K: the largest k of knn_query / transfer_labels
@@ -237,6 +239,10 @@ def library():
         'f3d_tsdf_extract_fill_dev': (i32, [vp, vp, i32, i32, i32, vp, dbl, vp, vp, vp]),
         'f3d_ctx_reserve_tsdf': (i32, [vp, i64]),
         'f3d_debug_tsdf_grid_cap': (i32, [vp, i32]),
+        'f3d_fuse_features': (i32, [vp, vp, i32, i64, vp, i32, i32, i32, vp, i32, i32, i32, i32, i32, dbl, vp, vp, i32]),
+        'f3d_fuse_features_dev': (i32, [vp, vp, i32, i64, vp, i32, i32, i32, vp, i32, i32, i32, i32, i32, dbl, vp, vp, i32, vp]),
+        'f3d_features_finalize': (i32, [vp, vp, vp, i64, i32, i32, vp]),
+        'f3d_features_finalize_dev': (i32, [vp, vp, vp, i64, i32, i32, vp, vp]),
     }
     for name, (res, args) in protos.items():
         fn = getattr(lib, name)          # AttributeError here = header/library mismatch
@@ -331,6 +337,44 @@ def _views(views):
     if views.ndim != 2 or views.shape[1] != VIEW_DOUBLES:
         raise ValueError(f'views must be [V,{VIEW_DOUBLES}]')
     return views
+
+
+def features_check(sums, counts, feats=None, nviews=None, npoints=None):
+    """The array checks of fuse_features / features_finalize (f3d.h "feature fusion"), for NumPy arrays and torch tensors alike, with
+    no device call: sums C-contiguous float32 [N, d], 1 <= d <= 4096; counts C-contiguous int32 [N]; feats C-contiguous float16 /
+    float32 [V, hf, wf, d] with one map per view.  TypeError for a wrong dtype, ValueError for a wrong shape.  -> FEAT_F16 / FEAT_F32
+    (None without feats)."""
+    name = lambda a: str(a.dtype).replace('torch.', '')                      # noqa: E731
+    contiguous = lambda a: a.is_contiguous() if hasattr(a, 'is_contiguous') else a.flags.c_contiguous   # noqa: E731
+    for a, what in ((sums, 'sums'), (counts, 'counts'), (feats, 'feats')):
+        if a is not None and not (hasattr(a, 'dtype') and hasattr(a, 'shape')):
+            raise TypeError(f'{what} must be an array or a tensor, got {type(a).__name__}')
+    if name(sums) != 'float32':
+        raise TypeError(f'sums must be float32, got {sums.dtype}')
+    if name(counts) != 'int32':
+        raise TypeError(f'counts must be int32, got {counts.dtype}')
+    if len(sums.shape) != 2 or not contiguous(sums):
+        raise ValueError('sums must be a C-contiguous float32 [N, d] array')
+    n, d = (int(x) for x in sums.shape)
+    if not 1 <= d <= FEAT_MAX_D:
+        raise ValueError(f'd must be in [1, {FEAT_MAX_D}], got {d}')
+    if tuple(counts.shape) != (n,) or not contiguous(counts):
+        raise ValueError(f'counts must be a C-contiguous int32 [{n}] array, got {tuple(counts.shape)}')
+    if npoints is not None and n != int(npoints):
+        raise ValueError(f'sums has {n} rows, the cloud {int(npoints)} points')
+    if feats is None:
+        return None
+    if name(feats) not in ('float16', 'float32'):
+        raise TypeError(f'feats must be float16 or float32, got {feats.dtype}')
+    if len(feats.shape) != 4 or not contiguous(feats):
+        raise ValueError('feats must be a C-contiguous [V, hf, wf, d] array (channel-last)')
+    if int(feats.shape[3]) != d:
+        raise ValueError(f'feats has {int(feats.shape[3])} channels, sums {d}')
+    if int(feats.shape[1]) < 1 or int(feats.shape[2]) < 1:
+        raise ValueError(f'feature maps must have at least one pixel, got {tuple(feats.shape[1:3])}')
+    if nviews is not None and int(feats.shape[0]) != int(nviews):
+        raise ValueError(f'{int(nviews)} views for {int(feats.shape[0])} feature maps')
+    return FEAT_F16 if name(feats) == 'float16' else FEAT_F32
 
 
 def _mesh(vertices, triangles):
@@ -504,7 +548,8 @@ class Context:
         self._check(self._lib.f3d_ctx_reserve_knn(self._h, int(m)))
 
     def reserve_render(self, n, nviews, h, w):
-        """Size the depth keys of render_lookups_dev / vote_visible_dev (automatic pass size) for nviews views of h x w pixels."""
+        """Size the depth keys of render_lookups_dev / vote_visible_dev / fuse_features_dev (automatic pass size) for nviews views of
+        h x w pixels."""
         self._check(self._lib.f3d_ctx_reserve_render(self._h, int(n), int(nviews), int(h), int(w)))
 
     def set_strict(self, strict=True):
@@ -662,6 +707,31 @@ class Context:
         self._check(self._lib.f3d_vote_visible(self._h, _ptr(p), dt, len(p), _ptr(views), V, _ptr(masks), H, W, int(splat), float(depth_tol),
                                                _ptr(votes), votes.shape[1], int(views_per_pass)))
         return votes
+
+    def fuse_features(self, sums, counts, points, views, h, w, feats, splat=1, depth_tol=0.05, views_per_pass=0):
+        """Adds the feature rows of the visible samples to `sums` (float32 [N, d]) and their number to `counts` (int32 [N]), both in
+        place (f3d.h f3d_fuse_features): feats float16 / float32 [V, hf, wf, d], one map per view; h, w = the image size of the samples
+        and the z-buffer.  Callable repeatedly: the views of later calls add to the same sums."""
+        p, dt = _xyz(points)
+        views = _views(views)
+        feats = np.asarray(feats)
+        ft = features_check(sums, counts, feats, len(views), len(p))
+        V, hf, wf, d = feats.shape
+        self._check(self._lib.f3d_fuse_features(self._h, _ptr(p), dt, len(p), _ptr(views), V, int(h), int(w), _ptr(feats), ft, hf, wf, d,
+                                                int(splat), float(depth_tol), _ptr(sums), _ptr(counts), int(views_per_pass)))
+        return sums, counts
+
+    def features_finalize(self, sums, counts, normalize=True, out=None):
+        """Per-point mean rows, unit length with `normalize`, zeros where counts is 0 (f3d.h f3d_features_finalize) -> float32 [N, d];
+        out may be `sums` itself."""
+        features_check(sums, counts)
+        if out is None:
+            out = np.empty_like(sums)
+        elif out.dtype != np.float32 or out.shape != sums.shape or not out.flags.c_contiguous:
+            raise ValueError('out must be a C-contiguous float32 array of the shape of sums')
+        self._check(self._lib.f3d_features_finalize(self._h, _ptr(sums), _ptr(counts), sums.shape[0], sums.shape[1], int(bool(normalize)),
+                                                    _ptr(out)))
+        return out
 
     def render_mesh_lookups(self, vertices, triangles, views, h, w, z_far=np.inf, want_depth=True, want_uv2tri=True, want_straddling=True):
         """Triangle z-buffer of the mesh in every view (f3d.h f3d_render_mesh_lookups) -> depth float32 [V, h, w] (+inf = empty),
@@ -1468,6 +1538,18 @@ class Context:
         """Enqueue only; a label >= ncols on a visible sample is recorded for take_device_error."""
         self._check(self._lib.f3d_vote_visible_dev(self._h, xyz_ptr, int(dtype), int(n), views_ptr, int(nviews), masks_ptr, int(h), int(w),
                                                    int(splat), float(depth_tol), votes_ptr, int(ncols), int(views_per_pass), stream))
+
+    def fuse_features_dev(self, xyz_ptr, dtype, n, views_ptr, nviews, h, w, feats_ptr, ftype, hf, wf, d, splat, depth_tol, sums_ptr, counts_ptr,
+                          views_per_pass=0, stream=None):
+        """Enqueue only (f3d.h f3d_fuse_features_dev): feats [V, hf, wf, d] of FEAT_F16 / FEAT_F32, sums float32 [n, d] and counts int32 [n]
+        updated in place.  Scratch: reserve_render(n, nviews, h, w); none with depth_tol = inf."""
+        self._check(self._lib.f3d_fuse_features_dev(self._h, xyz_ptr, int(dtype), int(n), views_ptr, int(nviews), int(h), int(w), feats_ptr,
+                                                    int(ftype), int(hf), int(wf), int(d), int(splat), float(depth_tol), sums_ptr, counts_ptr,
+                                                    int(views_per_pass), stream))
+
+    def features_finalize_dev(self, sums_ptr, counts_ptr, n, d, normalize, out_ptr, stream=None):
+        """Enqueue only (f3d.h f3d_features_finalize_dev); out_ptr may be sums_ptr."""
+        self._check(self._lib.f3d_features_finalize_dev(self._h, sums_ptr, counts_ptr, int(n), int(d), int(bool(normalize)), out_ptr, stream))
 
     def render_counts_dev(self, xyz_ptr, dtype, n, views_ptr, nviews, h, w, splat, stream=None):
         """Diagnostic (synchronises): samples, covered cells and issued atomics of a render of these views, and the device-event times

@@ -1216,6 +1216,48 @@ int f3d_tsdf_extract_fill_dev(f3d_ctx* ctx, const float* tsdf, int nx, int ny, i
 int f3d_ctx_reserve_tsdf(f3d_ctx* ctx, int64_t nvoxels);
 int f3d_debug_tsdf_grid_cap(f3d_ctx* ctx, int blocks);
 
+/* ---- feature fusion: per-point pooling of per-pixel feature maps over views (no reference counterpart) -------------------- */
+/* Every other 2D -> 3D entry moves one byte per pixel (a class or an instance id).  These move a vector: the [C] logits or
+ * probabilities of the 2D network (soft votes), or a per-pixel embedding that is compared with text embeddings afterwards.  The
+ * geometry is that of the occlusion-aware forward vote above: the same samples, the same keys, the same visibility rule.
+ *   inputs     xyz [n, 3] F3D_F64 or F3D_F32, n < 2^31; views [V] from f3d_views_build; h, w > 0: the image size at which the samples
+ *              and the z-buffer are taken; feats [V, hf, wf, d], channel-last and C-contiguous, of type ftype (F3D_FEAT_F16: IEEE
+ *              binary16, F3D_FEAT_F32); hf, wf >= 1 are independent of h, w, hf * wf < 2^31; 1 <= d <= 4096; splat in [0, 8];
+ *              depth_tol >= 0, +inf allowed; sums float32 [n, d] and counts int32 [n], both updated IN PLACE (a fresh
+ *              accumulation starts from zeros: the caller zeroes them); views_per_pass >= 0 as in f3d_vote_visible.
+ *   sample     the sample (u, v, z32) of (point i, view j) is exactly that of f3d_vote_visible.  It is visible iff
+ *              (double)z32 <= (double)zmin32 + depth_tol, zmin32 = the depth of cell (j, v, u) of the splat z-buffer of this very
+ *              cloud.  With depth_tol = +inf every sample is visible and the z-buffer passes are skipped.
+ *   pixel      the feature pixel of a sample is uf = (int64)u * wf / w, vf = (int64)v * hf / h (the nearest rule of
+ *              segUtils/voting.py resize_nearest); it is in range by construction.
+ *   sum        for the views of the call in ascending j, for every visible sample (i, j):
+ *                sums[i, c] = (float)(sums[i, c] + (float)feats[j, vf, uf, c]) for every c (one float32 add; the binary16 -> float32
+ *                conversion is exact), counts[i] += 1.
+ *              No float atomics: a point's adds happen in ascending view order whatever the launch shape, so nothing in the result
+ *              depends on thread timing, on views_per_pass or on how the caller splits the views over calls: two calls over views
+ *              [0, a) and [a, V) equal one call over [0, V) bit for bit.  A point without a visible sample keeps its row.
+ *   finalize   f3d_features_finalize(sums, counts, n, d, normalize, out): m_c = sums[i, c] / (float)counts[i], the correctly rounded
+ *              float32 quotient; a row of zeros when counts[i] <= 0.  With normalize != 0: s = sum_c (double)m_c * (double)m_c in
+ *              float64 (in any order), out[i, c] = (float)((double)m_c / sqrt(s)), zeros when s == 0.  out float32 [n, d]; out == sums
+ *              is allowed.
+ * Scratch: only the depth keys of a pass, so f3d_ctx_reserve_render(n, nviews, h, w) sizes it and a strict context then allocates
+ * nothing in f3d_fuse_features_dev with views_per_pass = 0 (or any smaller pass); f3d_features_finalize_dev needs none.
+ * F3D_ERR_INVALID: the bad arguments of f3d_vote_visible, hf or wf < 1, hf * wf >= 2^31, d outside [1, 4096], an unknown ftype, a
+ * NULL array that is needed.  There is no device error: nothing is indexed by data.  n == 0 or V == 0 is a no-op. */
+typedef enum f3d_ftype {
+    F3D_FEAT_F16 = 0,             /* IEEE binary16 feature maps                                   */
+    F3D_FEAT_F32 = 1              /* float32 feature maps                                         */
+} f3d_ftype;
+int f3d_fuse_features(f3d_ctx* ctx, const void* xyz, f3d_dtype dtype, int64_t n, const f3d_view* views, int nviews, int h, int w,
+                      const void* feats /*[V,hf,wf,d]*/, f3d_ftype ftype, int hf, int wf, int d, int splat, double depth_tol,
+                      float* sums /*[n,d], in place*/, int32_t* counts /*[n], in place*/, int views_per_pass);
+int f3d_fuse_features_dev(f3d_ctx* ctx, const void* xyz, f3d_dtype dtype, int64_t n, const f3d_view* views_dev /*device [V]*/, int nviews,
+                          int h, int w, const void* feats, f3d_ftype ftype, int hf, int wf, int d, int splat, double depth_tol,
+                          float* sums, int32_t* counts, int views_per_pass, void* stream);
+int f3d_features_finalize(f3d_ctx* ctx, const float* sums, const int32_t* counts, int64_t n, int d, int normalize, float* out);
+int f3d_features_finalize_dev(f3d_ctx* ctx, const float* sums, const int32_t* counts, int64_t n, int d, int normalize, float* out,
+                              void* stream);
+
 #ifdef __cplusplus
 }
 #endif
