@@ -37,7 +37,7 @@ enum scratch_slot { SLOT_OBB_BOXES = 0, SLOT_SORT_PERM, SLOT_SORT_SCRATCH, SLOT_
                     SLOT_FUSE_XYZ, SLOT_FUSION, SLOT_PATCH_STATUS, SLOT_NRM, SLOT_NRM_CAMS, SLOT_QRY, SLOT_FLOOD, SLOT_COLOR,
                     SLOT_CVS_INST, SLOT_CVS_STATS, SLOT_QUADS, SLOT_GROW, SLOT_PVOTE, SLOT_PVOTE_BITS, SLOT_MESH, SLOT_ZKEY,
                     SLOT_ZCOUNTS, SLOT_KNN, SLOT_KNN_FLAG, SLOT_PLANES, SLOT_RASTER, SLOT_ZLUT, SLOT_SMOOTH, SLOT_FACE_GRAPH, SLOT_LIFT, SLOT_LIFT_TABLE,
-                    SLOT_TSDF, SLOT_COUNT };
+                    SLOT_TSDF, SLOT_ICP, SLOT_COUNT };
 enum kept_slot { KEPT_GRAPH_OFFS = 0,                                      // f3d_radius_graph_count -> _fill: the offsets
                  KEPT_QRY_IN, KEPT_QRY_OFFS,                               // f3d_radius_query_count -> _fill: the queries, the offsets
                  KEPT_GRP_ORDER, KEPT_GRP_KEYS, KEPT_GRP_STARTS,           // f3d_group_by_id -> f3d_obb_extremes -> f3d_obb_hull_filter
@@ -3459,6 +3459,152 @@ int f3d_tsdf_extract_fill(f3d_ctx* ctx, int nx, int ny, int nz, const double lo[
     double* dv = st.out(verts, (size_t)ctx->tsdf_nv * 24);
     int32_t* dtri = ctx->tsdf_nq ? st.out(tris, (size_t)ctx->tsdf_nq * 24) : nullptr;
     if (!st.rc) st.rc = f3d_tsdf_extract_fill_dev(ctx, (const float*)ctx->kept[KEPT_TSDF].p, nx, ny, nz, lo, vs, dv, dtri, ctx->stream);
+    return st.finish();
+}
+
+// ---------------------------------------------------------------------------------------------
+// registration: TSDF raycast and point-to-plane ICP (f3d_icp.hip; the contract is in include/f3d.h)
+// ---------------------------------------------------------------------------------------------
+static bool all_finite(const double* v, int n) {
+    for (int k = 0; k < n; ++k) if (!(fabs(v[k]) < INFINITY)) return false;
+    return true;
+}
+
+// qn = q / |q| by component division; false for a zero or non-finite quaternion
+static bool unit_quat(const double q[4], double qn[4]) {
+    if (!all_finite(q, 4)) return false;
+    const double len = sqrt(((q[0] * q[0] + q[1] * q[1]) + q[2] * q[2]) + q[3] * q[3]);
+    if (!(len > 0.0 && len < INFINITY)) return false;
+    for (int k = 0; k < 4; ++k) qn[k] = q[k] / len;
+    return true;
+}
+
+static bool image_ok(int h, int w) { return h > 0 && w > 0 && (int64_t)h * w < ((int64_t)1 << 31); }
+
+#define F3D_RAYCAST_BAD "bad arguments (dims >= 1 with a product < 2^31; vs and step finite and > 0; min_weight >= 1; znear >= 0; nsteps >= 1; h * w in [1, 2^31); finite lo, K and t; a finite non-zero quaternion)"
+static bool raycast_ok(const float* tsdf, const float* weight, int nx, int ny, int nz, const double* lo, double vs, float min_weight, const double* K,
+                       const double* q, const double* t, int h, int w, double znear, double step, int nsteps, double qn[4]) {
+    return tsdf && weight && lo && K && q && t && tsdf_voxels(nx, ny, nz) > 0 && pos_finite(vs) && min_weight >= 1.0f && image_ok(h, w) &&
+           znear >= 0.0 && znear < INFINITY && pos_finite(step) && nsteps >= 1 && all_finite(lo, 3) && all_finite(K, 9) && all_finite(t, 3) &&
+           unit_quat(q, qn);
+}
+
+int f3d_tsdf_raycast_dev(f3d_ctx* ctx, const float* tsdf, const float* weight, int nx, int ny, int nz, const double lo[3], double vs, float min_weight,
+                         const double K[9], const double q_wxyz[4], const double t[3], int h, int w, double znear, double step, int nsteps,
+                         double* vertex, double* normal, double* depth, void* stream) {
+    int rc = enter(ctx); if (rc) return rc;
+    double qn[4];
+    if (!raycast_ok(tsdf, weight, nx, ny, nz, lo, vs, min_weight, K, q_wxyz, t, h, w, znear, step, nsteps, qn))
+        return fail(ctx, F3D_ERR_INVALID, "tsdf_raycast: " F3D_RAYCAST_BAD);
+    if (!vertex && !normal && !depth) return F3D_OK;
+    F3D_HIP(ctx, f3d_launch_tsdf_raycast(tsdf, weight, nx, ny, nz, lo, vs, min_weight, K, qn, t, h, w, znear, step, nsteps, vertex, normal, depth,
+                                         ctx->tsdf_grid_cap, pick(ctx, stream)));
+    return F3D_OK;
+}
+
+int f3d_tsdf_raycast(f3d_ctx* ctx, const float* tsdf, const float* weight, int nx, int ny, int nz, const double lo[3], double vs, float min_weight,
+                     const double K[9], const double q_wxyz[4], const double t[3], int h, int w, double znear, double step, int nsteps,
+                     double* vertex, double* normal, double* depth) {
+    int rc = enter(ctx); if (rc) return rc;
+    double qn[4];
+    if (!raycast_ok(tsdf, weight, nx, ny, nz, lo, vs, min_weight, K, q_wxyz, t, h, w, znear, step, nsteps, qn))
+        return fail(ctx, F3D_ERR_INVALID, "tsdf_raycast: " F3D_RAYCAST_BAD);
+    const size_t vol = (size_t)tsdf_voxels(nx, ny, nz) * 4, px = (size_t)h * w * 8;
+    staging st(ctx);
+    const float* dt = st.in(tsdf, vol);
+    const float* dw = st.in(weight, vol);
+    double* dv = st.out(vertex, 3 * px);
+    double* dn = st.out(normal, 3 * px);
+    double* dd = st.out(depth, px);
+    if (!st.rc) st.rc = f3d_tsdf_raycast_dev(ctx, dt, dw, nx, ny, nz, lo, vs, min_weight, K, q_wxyz, t, h, w, znear, step, nsteps, dv, dn, dd, ctx->stream);
+    return st.finish();
+}
+
+#define F3D_ICP_BAD "bad arguments (h * w and hm * wm in [1, 2^31); depth_scale, max_depth and max_dist finite and > 0; a known depth type; finite K and t; a finite non-zero quaternion)"
+static bool icp_ok(const void* depth, int depth_type, int h, int w, const double* K, double depth_scale, double max_depth, const double* q,
+                   const double* t, const double* mv, const double* mn, int hm, int wm, const f3d_view* view, double max_dist) {
+    double qn[4];
+    return depth && K && q && t && mv && mn && view && image_ok(h, w) && image_ok(hm, wm) && pos_finite(depth_scale) && pos_finite(max_depth) &&
+           pos_finite(max_dist) && (depth_type == F3D_DEPTH_U16 || depth_type == F3D_DEPTH_F32 || depth_type == F3D_DEPTH_F64) &&
+           all_finite(K, 9) && all_finite(t, 3) && unit_quat(q, qn);
+}
+
+static f3d_icp_args icp_args(const void* depth, int depth_type, int h, int w, const double* K, double depth_scale, double max_depth, const double* mv,
+                             const double* mn, int hm, int wm, const f3d_view* view, double max_dist) {
+    f3d_icp_args a;
+    a.depth = depth; a.depth_type = depth_type; a.h = h; a.w = w; a.K = K; a.depth_scale = depth_scale; a.max_depth = max_depth;
+    a.model_vertex = mv; a.model_normal = mn; a.hm = hm; a.wm = wm; a.model_view = view; a.max_dist = max_dist;
+    return a;
+}
+
+int f3d_ctx_reserve_icp(f3d_ctx* ctx, int64_t npixels) {
+    int rc = enter(ctx); if (rc) return rc;
+    if (npixels < 0 || npixels >= ((int64_t)1 << 31)) return fail(ctx, F3D_ERR_INVALID, "ctx_reserve_icp: npixels must be in [0, 2^31)");
+    return reserve(ctx, {{SLOT_ICP, f3d_icp_scratch_bytes(npixels)}});
+}
+
+int f3d_icp_sums_dev(f3d_ctx* ctx, const void* depth, int depth_type, int h, int w, const double K[9], double depth_scale, double max_depth,
+                     const double q_wxyz[4], const double t[3], const double* model_vertex, const double* model_normal, int hm, int wm,
+                     const f3d_view* model_view, double max_dist, double* sums, void* stream) {
+    int rc = enter(ctx); if (rc) return rc;
+    if (!sums || !icp_ok(depth, depth_type, h, w, K, depth_scale, max_depth, q_wxyz, t, model_vertex, model_normal, hm, wm, model_view, max_dist))
+        return fail(ctx, F3D_ERR_INVALID, "icp_sums: " F3D_ICP_BAD);
+    void* scratch;
+    if ((rc = ensure(ctx, SLOT_ICP, f3d_icp_scratch_bytes((int64_t)h * w), &scratch))) return rc;
+    F3D_HIP(ctx, f3d_launch_icp_sums(icp_args(depth, depth_type, h, w, K, depth_scale, max_depth, model_vertex, model_normal, hm, wm, model_view, max_dist),
+                                     q_wxyz, t, scratch, sums, pick(ctx, stream)));
+    return F3D_OK;
+}
+
+int f3d_icp_sums(f3d_ctx* ctx, const void* depth, int depth_type, int h, int w, const double K[9], double depth_scale, double max_depth,
+                 const double q_wxyz[4], const double t[3], const double* model_vertex, const double* model_normal, int hm, int wm,
+                 const f3d_view* model_view, double max_dist, double* sums) {
+    int rc = enter(ctx); if (rc) return rc;
+    if (!sums || !icp_ok(depth, depth_type, h, w, K, depth_scale, max_depth, q_wxyz, t, model_vertex, model_normal, hm, wm, model_view, max_dist))
+        return fail(ctx, F3D_ERR_INVALID, "icp_sums: " F3D_ICP_BAD);
+    staging st(ctx);
+    const void* dd = st.in((const char*)depth, depth_bytes(depth_type, 1, h, w));
+    const double* dv = st.in(model_vertex, (size_t)hm * wm * 24);
+    const double* dn = st.in(model_normal, (size_t)hm * wm * 24);
+    const f3d_view* dview = st.in(model_view, sizeof(f3d_view));
+    double* ds = st.out(sums, F3D_ICP_NSUMS * sizeof(double));
+    if (!st.rc) st.rc = f3d_icp_sums_dev(ctx, dd, depth_type, h, w, K, depth_scale, max_depth, q_wxyz, t, dv, dn, hm, wm, dview, max_dist, ds, ctx->stream);
+    return st.finish();
+}
+
+int f3d_icp_dev(f3d_ctx* ctx, const void* depth, int depth_type, int h, int w, const double K[9], double depth_scale, double max_depth,
+                const double q_wxyz[4], const double t[3], const double* model_vertex, const double* model_normal, int hm, int wm,
+                const f3d_view* model_view, double max_dist, int iterations, int min_pairs, double* pose, double* stats, int32_t* status,
+                void* stream) {
+    int rc = enter(ctx); if (rc) return rc;
+    if (!pose || !stats || !icp_ok(depth, depth_type, h, w, K, depth_scale, max_depth, q_wxyz, t, model_vertex, model_normal, hm, wm, model_view, max_dist))
+        return fail(ctx, F3D_ERR_INVALID, "icp: " F3D_ICP_BAD);
+    if (iterations < 1 || min_pairs < 6) return fail(ctx, F3D_ERR_INVALID, "icp: iterations must be at least 1 and min_pairs at least 6");
+    void* scratch;
+    if ((rc = ensure(ctx, SLOT_ICP, f3d_icp_scratch_bytes((int64_t)h * w), &scratch))) return rc;
+    F3D_HIP(ctx, f3d_launch_icp(icp_args(depth, depth_type, h, w, K, depth_scale, max_depth, model_vertex, model_normal, hm, wm, model_view, max_dist),
+                                q_wxyz, t, iterations, min_pairs, scratch, pose, stats, status, pick(ctx, stream)));
+    return F3D_OK;
+}
+
+int f3d_icp(f3d_ctx* ctx, const void* depth, int depth_type, int h, int w, const double K[9], double depth_scale, double max_depth,
+            const double q_wxyz[4], const double t[3], const double* model_vertex, const double* model_normal, int hm, int wm,
+            const f3d_view* model_view, double max_dist, int iterations, int min_pairs, double* pose, double* stats, int32_t* status) {
+    int rc = enter(ctx); if (rc) return rc;
+    if (!pose || !stats || !status ||
+        !icp_ok(depth, depth_type, h, w, K, depth_scale, max_depth, q_wxyz, t, model_vertex, model_normal, hm, wm, model_view, max_dist))
+        return fail(ctx, F3D_ERR_INVALID, "icp: " F3D_ICP_BAD);
+    if (iterations < 1 || min_pairs < 6) return fail(ctx, F3D_ERR_INVALID, "icp: iterations must be at least 1 and min_pairs at least 6");
+    staging st(ctx);
+    const void* dd = st.in((const char*)depth, depth_bytes(depth_type, 1, h, w));
+    const double* dv = st.in(model_vertex, (size_t)hm * wm * 24);
+    const double* dn = st.in(model_normal, (size_t)hm * wm * 24);
+    const f3d_view* dview = st.in(model_view, sizeof(f3d_view));
+    double* dp = st.out(pose, 7 * sizeof(double));
+    double* ds = st.out(stats, (size_t)iterations * 3 * sizeof(double));
+    int32_t* dst = st.out(status, sizeof(int32_t));
+    if (!st.rc) st.rc = f3d_icp_dev(ctx, dd, depth_type, h, w, K, depth_scale, max_depth, q_wxyz, t, dv, dn, hm, wm, dview, max_dist, iterations, min_pairs,
+                                    dp, ds, dst, ctx->stream);
     return st.finish();
 }
 

@@ -1,0 +1,413 @@
+// Registration (include/f3d.h "registration"): model maps of a TSDF volume by ray casting, and projective point-to-plane ICP of a depth
+// frame against such maps.  The contract there is restated operation for operation in tests/icp_ref.py; everything that decides a
+// result is float64 without contraction, in the order written.
+//
+//   k_tsdf_raycast  one thread per pixel, a wavefront = one 8 x 8 pixel tile (neighbouring rays touch neighbouring voxels), no LDS.  The
+//                   per-ray constants (origin, direction, the sample range) are hoisted; the eight taps of a sample are loaded as four
+//                   pairs adjacent in x.  The march starts and ends where a slab test of the ray against the box of valid sample
+//                   positions, widened by a margin that dwarfs every rounding, says so: every sample it skips fails the index rule of
+//                   the contract, so no bit of the output depends on it.
+//   k_icp_terms     one wave per chunk of F3D_ICP_CHUNK source pixels: lane l takes the pixels l, l + 64, .. of the chunk in ascending
+//                   order with the 29 accumulators in registers (f3d_wave_sum's lane order), the xor butterfly follows, lane 0 stores
+//                   the chunk row.
+//   k_icp_solve     one block: its waves take the 29 totals in turn (f3d_wave_sum over the chunk sums); after the barrier thread 0 does
+//                   the 6 x 6 Cholesky solve and writes the pose and the stats row.  Two launches per round, no host round trip: the pose
+//                   and the lost flag live in device memory, both kernels read them.
+#include <hip/hip_runtime.h>
+#include <math.h>
+#include <stdint.h>
+#include "f3d.h"
+#include "f3d_math.h"
+#include "f3d_kernels.h"
+#include "f3d_groups.h"
+
+#pragma clang fp contract(off)
+
+namespace {
+
+constexpr int NS = F3D_ICP_NSUMS;
+constexpr int ICP_WAVES = F3D_BLOCK / 64;                  // chunks a block of k_icp_terms takes per pass: one per wave
+
+template <typename T> struct raw_depth;
+template <> struct raw_depth<double> { static __device__ __forceinline__ double at(const double* d, int64_t i) { return d[i]; } };
+template <> struct raw_depth<float> { static __device__ __forceinline__ double at(const float* d, int64_t i) { return (double)d[i]; } };
+template <> struct raw_depth<uint16_t> { static __device__ __forceinline__ double at(const uint16_t* d, int64_t i) { return (double)d[i]; } };
+
+struct ray_volume {
+    const float* tsdf; const float* weight;
+    int nx, ny, nz;
+    double lo[3], vs;
+    float min_weight;
+};
+
+// F(P) of the contract: false = the sample is invalid
+__device__ __forceinline__ bool sample(const ray_volume& g, double px, double py, double pz, double& F) {
+    const double gx = (px - g.lo[0]) / g.vs - 0.5, gy = (py - g.lo[1]) / g.vs - 0.5, gz = (pz - g.lo[2]) / g.vs - 0.5;
+    const double ix = floor(gx), iy = floor(gy), iz = floor(gz);
+    if (!(ix >= 0.0 && ix <= (double)(g.nx - 2) && iy >= 0.0 && iy <= (double)(g.ny - 2) && iz >= 0.0 && iz <= (double)(g.nz - 2))) return false;
+    const double fx = gx - ix, fy = gy - iy, fz = gz - iz;
+    const int64_t sy = g.nx, sz = (int64_t)g.nx * g.ny;
+    const int64_t at = ((int64_t)iz * g.ny + (int64_t)iy) * g.nx + (int64_t)ix;
+    const float* W = g.weight + at;
+    bool seen = true;
+#pragma unroll
+    for (int c = 0; c < 4; ++c) {
+        const int64_t o = (c & 1) * sy + (c >> 1) * sz;
+        seen = seen & (W[o] >= g.min_weight) & (W[o + 1] >= g.min_weight);
+    }
+    if (!seen) return false;
+    const float* S = g.tsdf + at;
+    double cjk[4];
+#pragma unroll
+    for (int c = 0; c < 4; ++c) {                           // c = j + 2 k: the pair (T0jk, T1jk), lerped along x
+        const int64_t o = (c & 1) * sy + (c >> 1) * sz;
+        const double t0 = (double)S[o], t1 = (double)S[o + 1];
+        cjk[c] = t0 + fx * (t1 - t0);
+    }
+    const double c0 = cjk[0] + fy * (cjk[1] - cjk[0]), c1 = cjk[2] + fy * (cjk[3] - cjk[2]);
+    F = c0 + fz * (c1 - c0);
+    return true;
+}
+
+// The samples k of [0, nsteps) that can be valid lie in [k0, k1): outside it P_a(s_k) misses the box of valid positions
+// [lo + 0.5 vs, lo + (n - 0.5) vs) on some axis by more than a voxel, a step and 1e-6 of the operand magnitudes, nine decimal orders
+// above the rounding of either evaluation.  Anything not finite leaves the whole range to the samples.
+__device__ __forceinline__ void sample_range(const ray_volume& g, const double t[3], const double dw[3], double near, double step, int nsteps,
+                                             int& k0, int& k1) {
+    k0 = 0; k1 = nsteps;
+    double s0 = -INFINITY, s1 = INFINITY;
+    const int n[3] = {g.nx, g.ny, g.nz};
+    const double far = near + (double)nsteps * step;
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+        const double bmin = g.lo[a], bmax = g.lo[a] + (double)n[a] * g.vs;
+        const double reach = fabs(dw[a]) * (fabs(near) + fabs(far));
+        const double m = g.vs + 1e-6 * (((fabs(bmin) + fabs(bmax)) + fabs(t[a])) + reach);
+        if (!(m < INFINITY)) return;
+        const double a0 = (bmin - m) - t[a], a1 = (bmax + m) - t[a];
+        if (reach < m * 1e-3) {                                                   // the ray moves far less than the margin along this axis
+            if (a0 > m || a1 < -m) { k1 = 0; return; }                            // and starts more than a margin outside the widened slab
+            continue;
+        }
+        const double u0 = a0 / dw[a], u1 = a1 / dw[a];
+        if (!(u0 == u0 && u1 == u1)) return;
+        s0 = fmax(s0, fmin(u0, u1)); s1 = fmin(s1, fmax(u0, u1));
+    }
+    if (!(s0 <= s1)) { k1 = 0; return; }
+    const double f0 = floor((s0 - near) / step) - 2.0, f1 = ceil((s1 - near) / step) + 3.0;
+    if (!(f0 == f0 && f1 == f1)) return;
+    if (f0 > 0.0) k0 = f0 < (double)nsteps ? (int)f0 : nsteps;
+    if (f1 < (double)nsteps) k1 = f1 > 0.0 ? (int)f1 : 0;
+}
+
+struct ray_camera { double fx, fy, cx, cy, qn[4], t[3]; };
+
+__global__ __launch_bounds__(F3D_BLOCK) void k_tsdf_raycast(ray_volume g, ray_camera cam, int h, int w, double near, double step, int nsteps,
+                                                             double* __restrict__ vertex, double* __restrict__ normal, double* __restrict__ depth) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int tx = (w + 7) >> 3, ty = (h + 7) >> 3;
+    const int64_t ntiles = (int64_t)tx * ty;
+    const double nan = __longlong_as_double(0x7ff8000000000000LL);
+    for (int64_t tile = (int64_t)blockIdx.x * (F3D_BLOCK / 64) + wave; tile < ntiles; tile += (int64_t)gridDim.x * (F3D_BLOCK / 64)) {
+        const int u = (int)(tile % tx) * 8 + (lane & 7), v = (int)(tile / tx) * 8 + (lane >> 3);
+        if (u >= w || v >= h) continue;
+        f3d_p3 dc;
+        dc.x = (((double)u + 0.5) - cam.cx) / cam.fx;
+        dc.y = (((double)v + 0.5) - cam.cy) / cam.fy;
+        dc.z = 1.0;
+        const f3d_p3 d = f3d_rotate(cam.qn, dc);
+        const double dw[3] = {d.x, d.y, d.z};
+        int k0, k1;
+        sample_range(g, cam.t, dw, near, step, nsteps, k0, k1);
+        bool hit = false, prev_ok = false;
+        double F_prev = 0.0, s_star = 0.0;
+        for (int k = k0; k < k1; ++k) {
+            const double s = near + (double)k * step;
+            double F = 0.0;
+            const bool valid = sample(g, cam.t[0] + s * dw[0], cam.t[1] + s * dw[1], cam.t[2] + s * dw[2], F);
+            if (valid && F < 0.0) {
+                if (prev_ok) {                                                  // then k >= 1: the sample before is the one that set prev_ok
+                    const double s_prev = near + (double)(k - 1) * step;
+                    s_star = s_prev + step * (F_prev / (F_prev - F));
+                    hit = true;
+                }
+                break;
+            }
+            prev_ok = valid && F >= 0.0;
+            F_prev = F;
+        }
+        double V[3] = {nan, nan, nan}, N[3] = {nan, nan, nan}, z = 0.0;
+        if (hit) {
+            const double P[3] = {cam.t[0] + s_star * dw[0], cam.t[1] + s_star * dw[1], cam.t[2] + s_star * dw[2]};
+            double G[3];
+            bool ok = true;
+#pragma unroll
+            for (int a = 0; a < 3; ++a) {
+                double Fp = 0.0, Fm = 0.0;
+                ok = ok && sample(g, P[0] + (a == 0 ? g.vs : 0.0), P[1] + (a == 1 ? g.vs : 0.0), P[2] + (a == 2 ? g.vs : 0.0), Fp);
+                ok = ok && sample(g, P[0] - (a == 0 ? g.vs : 0.0), P[1] - (a == 1 ? g.vs : 0.0), P[2] - (a == 2 ? g.vs : 0.0), Fm);
+                G[a] = Fp - Fm;
+            }
+            if (ok) {
+                const double len = sqrt((G[0] * G[0] + G[1] * G[1]) + G[2] * G[2]);
+                if (len > 0.0 && len < INFINITY) {
+#pragma unroll
+                    for (int a = 0; a < 3; ++a) { V[a] = P[a]; N[a] = G[a] / len; }
+                    z = s_star;
+                }
+            }
+        }
+        const int64_t i = (int64_t)v * w + u;
+        if (vertex) { vertex[3 * i] = V[0]; vertex[3 * i + 1] = V[1]; vertex[3 * i + 2] = V[2]; }
+        if (normal) { normal[3 * i] = N[0]; normal[3 * i + 1] = N[1]; normal[3 * i + 2] = N[2]; }
+        if (depth) depth[i] = z;
+    }
+}
+
+// ---- ICP -------------------------------------------------------------------------------------------------------------------
+struct icp_frame {
+    const void* depth;
+    int h, w;
+    double fx, fy, cx, cy, depth_scale, max_depth;
+    const double* model_vertex; const double* model_normal;
+    int hm, wm;
+    const f3d_view* model_view;
+    double max_dist2;
+};
+
+__device__ __forceinline__ void normalised(const double q[4], double qn[4]) {
+    const double len = sqrt(((q[0] * q[0] + q[1] * q[1]) + q[2] * q[2]) + q[3] * q[3]);
+    qn[0] = q[0] / len; qn[1] = q[1] / len; qn[2] = q[2] / len; qn[3] = q[3] / len;
+}
+
+// the pose of a call, from its kernel arguments into device memory, and the lost flag cleared
+__global__ void k_icp_init(double* __restrict__ pose, int* __restrict__ lost, double q0, double q1, double q2, double q3, double t0, double t1, double t2) {
+    if (threadIdx.x == 0 && blockIdx.x == 0) {
+        pose[0] = q0; pose[1] = q1; pose[2] = q2; pose[3] = q3; pose[4] = t0; pose[5] = t1; pose[6] = t2;
+        *lost = 0;
+    }
+}
+
+// the 29 terms of source pixel i at the pose (qn, t), added to acc; false = the pixel contributes 0.0 to every sum
+template <typename T>
+__device__ __forceinline__ bool icp_pixel(const icp_frame& f, const double qn[4], const double t[3], int64_t i, double J[6], double& r) {
+    const double d = raw_depth<T>::at((const T*)f.depth, i) / f.depth_scale;
+    if (!(d > 0.0 && d <= f.max_depth)) return false;
+    const int v = (int)(i / f.w), u = (int)(i - (int64_t)v * f.w);
+    f3d_p3 c;
+    c.x = (((double)u + 0.5) - f.cx) * (d / f.fx);
+    c.y = (((double)v + 0.5) - f.cy) * (d / f.fy);
+    c.z = d;
+    const f3d_p3 pr = f3d_rotate(qn, c);
+    f3d_p3 p;
+    p.x = pr.x + t[0]; p.y = pr.y + t[1]; p.z = pr.z + t[2];
+    const f3d_view& mv = *f.model_view;
+    const f3d_p3 hp = f3d_project_h(mv.K, mv.qinv, mv.t, p);
+    if (!(hp.z > 0.0)) return false;
+    const double x = hp.x / hp.z, y = hp.y / hp.z;
+    if (!(x >= 0.0 && x < (double)f.wm && y >= 0.0 && y < (double)f.hm)) return false;
+    const int um = (int)floor(x), vm = (int)floor(y);
+    const int64_t at = 3 * ((int64_t)vm * f.wm + um);
+    const double V0 = f.model_vertex[at], V1 = f.model_vertex[at + 1], V2 = f.model_vertex[at + 2];
+    const double N0 = f.model_normal[at], N1 = f.model_normal[at + 1], N2 = f.model_normal[at + 2];
+    if (!(fabs(V0) < INFINITY && fabs(V1) < INFINITY && fabs(V2) < INFINITY && fabs(N0) < INFINITY && fabs(N1) < INFINITY && fabs(N2) < INFINITY))
+        return false;
+    const double e0 = p.x - V0, e1 = p.y - V1, e2 = p.z - V2;
+    if (!((e0 * e0 + e1 * e1) + e2 * e2 <= f.max_dist2)) return false;
+    r = f3d_dot3(N0, N1, N2, e0, e1, e2);
+    J[0] = pr.y * N2 - pr.z * N1;
+    J[1] = pr.z * N0 - pr.x * N2;
+    J[2] = pr.x * N1 - pr.y * N0;
+    J[3] = N0; J[4] = N1; J[5] = N2;
+    return true;
+}
+
+template <typename T>
+__global__ __launch_bounds__(F3D_BLOCK) void k_icp_terms(icp_frame f, const double* __restrict__ pose, const int* __restrict__ lost,
+                                                          int64_t npix, int64_t nchunks, double* __restrict__ chunks) {
+    if (*lost) return;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    double qn[4];
+    normalised(pose, qn);
+    const double t[3] = {pose[4], pose[5], pose[6]};
+    for (int64_t chunk = (int64_t)blockIdx.x * ICP_WAVES + wave; chunk < nchunks; chunk += (int64_t)gridDim.x * ICP_WAVES) {
+        const int64_t first = chunk * F3D_ICP_CHUNK;
+        const int64_t count = npix - first < F3D_ICP_CHUNK ? npix - first : (int64_t)F3D_ICP_CHUNK;
+        double acc[NS];
+#pragma unroll
+        for (int j = 0; j < NS; ++j) acc[j] = 0.0;
+        for (int64_t i = lane; i < count; i += 64) {
+            double J[6], r;
+            if (!icp_pixel<T>(f, qn, t, first + i, J, r)) continue;            // + 0.0 leaves an accumulator as it is (none is ever -0.0)
+            int j = 0;
+#pragma unroll
+            for (int a = 0; a < 6; ++a)
+#pragma unroll
+                for (int b = a; b < 6; ++b) { acc[j] = acc[j] + J[a] * J[b]; ++j; }
+#pragma unroll
+            for (int a = 0; a < 6; ++a) acc[21 + a] = acc[21 + a] + J[a] * r;
+            acc[27] = acc[27] + r * r;
+            acc[28] = acc[28] + 1.0;
+        }
+#pragma unroll
+        for (int j = 0; j < NS; ++j)
+            for (int off = 32; off > 0; off >>= 1) acc[j] = acc[j] + __shfl_xor(acc[j], off);
+        if (lane == 0) {
+#pragma unroll
+            for (int j = 0; j < NS; ++j) chunks[chunk * NS + j] = acc[j];
+        }
+    }
+}
+
+// One block.  totals_out != NULL: the 29 totals go there and nothing else happens (f3d_icp_sums).  Otherwise one round of f3d_icp: the
+// solve, the update of `pose` and row `round` of stats.
+__global__ __launch_bounds__(F3D_BLOCK) void k_icp_solve(const double* __restrict__ chunks, int64_t nchunks, double* __restrict__ totals_out,
+                                                          double* __restrict__ pose, int* __restrict__ lost, double min_pairs,
+                                                          double* __restrict__ stats, int round) {
+    __shared__ double tot[NS];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const bool was_lost = totals_out ? false : *lost != 0;
+    if (!was_lost) {
+        for (int j = wave; j < NS; j += F3D_BLOCK / 64) {
+            const double s = f3d_wave_sum(nchunks, lane, [&](int64_t c) { return chunks[c * NS + j]; });
+            if (lane == 0) tot[j] = s;
+        }
+    }
+    __syncthreads();
+    if (threadIdx.x != 0) return;
+    if (totals_out) {
+        for (int j = 0; j < NS; ++j) totals_out[j] = tot[j];
+        return;
+    }
+    double* row = stats + 3 * (int64_t)round;
+    if (was_lost) { row[0] = 0.0; row[1] = 0.0; row[2] = (double)F3D_ICP_LOST; return; }
+    row[0] = tot[28]; row[1] = tot[27];
+    bool ok = !(tot[28] < min_pairs);
+    double A[6][6], L[6][6], b[6], y[6], x[6];
+    {
+        int j = 0;
+        for (int a = 0; a < 6; ++a)
+            for (int c = a; c < 6; ++c) { A[a][c] = tot[j]; A[c][a] = tot[j]; ++j; }
+        for (int a = 0; a < 6; ++a) b[a] = -tot[21 + a];
+    }
+    double maxd = A[0][0];
+    for (int a = 1; a < 6; ++a) if (A[a][a] > maxd) maxd = A[a][a];
+    const double floor_ = F3D_ICP_PIVOT_EPS * maxd;
+    for (int j = 0; j < 6 && ok; ++j) {
+        double s = A[j][j];
+        for (int k = 0; k < j; ++k) s = s - L[j][k] * L[j][k];
+        if (!(fabs(s) < INFINITY && s > floor_)) { ok = false; break; }
+        L[j][j] = sqrt(s);
+        for (int i = j + 1; i < 6; ++i) {
+            double e = A[i][j];
+            for (int k = 0; k < j; ++k) e = e - L[i][k] * L[j][k];
+            L[i][j] = e / L[j][j];
+        }
+    }
+    if (!ok) { row[2] = (double)F3D_ICP_LOST; *lost = 1; return; }
+    for (int i = 0; i < 6; ++i) {
+        double s = b[i];
+        for (int k = 0; k < i; ++k) s = s - L[i][k] * y[k];
+        y[i] = s / L[i][i];
+    }
+    for (int i = 5; i >= 0; --i) {
+        double s = y[i];
+        for (int k = i + 1; k < 6; ++k) s = s - L[k][i] * x[k];
+        x[i] = s / L[i][i];
+    }
+    double qn[4], qp[4];
+    normalised(pose, qn);
+    const double a0 = 1.0, a1 = x[0] / 2.0, a2 = x[1] / 2.0, a3 = x[2] / 2.0;
+    qp[0] = ((a0 * qn[0] - a1 * qn[1]) - a2 * qn[2]) - a3 * qn[3];
+    qp[1] = ((a0 * qn[1] + a1 * qn[0]) + a2 * qn[3]) - a3 * qn[2];
+    qp[2] = ((a0 * qn[2] - a1 * qn[3]) + a2 * qn[0]) + a3 * qn[1];
+    qp[3] = ((a0 * qn[3] + a1 * qn[2]) - a2 * qn[1]) + a3 * qn[0];
+    normalised(qp, qn);
+    pose[0] = qn[0]; pose[1] = qn[1]; pose[2] = qn[2]; pose[3] = qn[3];
+    pose[4] = pose[4] + x[3]; pose[5] = pose[5] + x[4]; pose[6] = pose[6] + x[5];
+    row[2] = (double)F3D_ICP_OK;
+}
+
+struct icp_scratch { size_t chunks, pose, lost, bytes; };
+
+icp_scratch icp_layout(int64_t npixels) {
+    f3d_carve c;
+    icp_scratch l;
+    l.chunks = c.take((size_t)((npixels + F3D_ICP_CHUNK - 1) / F3D_ICP_CHUNK) * NS * sizeof(double));
+    l.pose = c.take(7 * sizeof(double));
+    l.lost = c.take(sizeof(int));
+    l.bytes = c.off;
+    return l;
+}
+
+icp_frame frame_of(const f3d_icp_args& a) {
+    icp_frame f;
+    f.depth = a.depth; f.h = a.h; f.w = a.w;
+    f.fx = a.K[0]; f.cx = a.K[2]; f.fy = a.K[4]; f.cy = a.K[5];
+    f.depth_scale = a.depth_scale; f.max_depth = a.max_depth;
+    f.model_vertex = a.model_vertex; f.model_normal = a.model_normal; f.hm = a.hm; f.wm = a.wm;
+    f.model_view = a.model_view;
+    f.max_dist2 = a.max_dist * a.max_dist;
+    return f;
+}
+
+void launch_terms(const f3d_icp_args& a, const double* pose, const int* lost, double* chunks, hipStream_t s) {
+    const icp_frame f = frame_of(a);
+    const int64_t npix = (int64_t)a.h * a.w, nchunks = (npix + F3D_ICP_CHUNK - 1) / F3D_ICP_CHUNK;
+    const dim3 gr(f3d_grid_for(nchunks, ICP_WAVES, F3D_GRID_CAP)), b(F3D_BLOCK);
+    if (a.depth_type == F3D_DEPTH_U16) hipLaunchKernelGGL(k_icp_terms<uint16_t>, gr, b, 0, s, f, pose, lost, npix, nchunks, chunks);
+    else if (a.depth_type == F3D_DEPTH_F32) hipLaunchKernelGGL(k_icp_terms<float>, gr, b, 0, s, f, pose, lost, npix, nchunks, chunks);
+    else hipLaunchKernelGGL(k_icp_terms<double>, gr, b, 0, s, f, pose, lost, npix, nchunks, chunks);
+}
+
+}  // namespace
+
+size_t f3d_icp_scratch_bytes(int64_t npixels) { return icp_layout(npixels).bytes; }
+
+hipError_t f3d_launch_tsdf_raycast(const float* tsdf, const float* weight, int nx, int ny, int nz, const double lo[3], double vs, float min_weight,
+                                   const double K[9], const double qn[4], const double t[3], int h, int w, double near, double step, int nsteps,
+                                   double* vertex, double* normal, double* depth, int grid_cap, hipStream_t s) {
+    ray_volume g;
+    g.tsdf = tsdf; g.weight = weight; g.nx = nx; g.ny = ny; g.nz = nz; g.vs = vs; g.min_weight = min_weight;
+    ray_camera cam;
+    cam.fx = K[0]; cam.cx = K[2]; cam.fy = K[4]; cam.cy = K[5];
+    for (int c = 0; c < 3; ++c) { g.lo[c] = lo[c]; cam.t[c] = t[c]; }
+    for (int c = 0; c < 4; ++c) cam.qn[c] = qn[c];
+    const int64_t ntiles = (int64_t)((w + 7) / 8) * ((h + 7) / 8);
+    const int usual = F3D_GRID_CAP * 16;                                        // blocks of a launch: the usual cap, or the smaller one a test set
+    const dim3 gr(f3d_grid_for(ntiles, F3D_BLOCK / 64, grid_cap > 0 && grid_cap < usual ? grid_cap : usual)), b(F3D_BLOCK);
+    hipLaunchKernelGGL(k_tsdf_raycast, gr, b, 0, s, g, cam, h, w, near, step, nsteps, vertex, normal, depth);
+    return hipGetLastError();
+}
+
+hipError_t f3d_launch_icp_sums(const f3d_icp_args& a, const double q[4], const double t[3], void* scratch, double* sums, hipStream_t s) {
+    const int64_t npix = (int64_t)a.h * a.w;
+    const icp_scratch l = icp_layout(npix);
+    char* base = (char*)scratch;
+    double *chunks = (double*)(base + l.chunks), *pose = (double*)(base + l.pose);
+    int* lost = (int*)(base + l.lost);
+    hipLaunchKernelGGL(k_icp_init, dim3(1), dim3(64), 0, s, pose, lost, q[0], q[1], q[2], q[3], t[0], t[1], t[2]);
+    launch_terms(a, pose, lost, chunks, s);
+    hipLaunchKernelGGL(k_icp_solve, dim3(1), dim3(F3D_BLOCK), 0, s, chunks, (npix + F3D_ICP_CHUNK - 1) / F3D_ICP_CHUNK, sums, pose, lost, 0.0,
+                       (double*)nullptr, 0);
+    return hipGetLastError();
+}
+
+hipError_t f3d_launch_icp(const f3d_icp_args& a, const double q[4], const double t[3], int iterations, int min_pairs, void* scratch,
+                          double* pose_out, double* stats, int32_t* status, hipStream_t s) {
+    const int64_t npix = (int64_t)a.h * a.w;
+    const icp_scratch l = icp_layout(npix);
+    char* base = (char*)scratch;
+    double *chunks = (double*)(base + l.chunks), *pose = (double*)(base + l.pose);
+    int* lost = (int*)(base + l.lost);
+    hipLaunchKernelGGL(k_icp_init, dim3(1), dim3(64), 0, s, pose, lost, q[0], q[1], q[2], q[3], t[0], t[1], t[2]);
+    for (int round = 0; round < iterations; ++round) {
+        launch_terms(a, pose, lost, chunks, s);
+        hipLaunchKernelGGL(k_icp_solve, dim3(1), dim3(F3D_BLOCK), 0, s, chunks, (npix + F3D_ICP_CHUNK - 1) / F3D_ICP_CHUNK, (double*)nullptr, pose, lost,
+                           (double)min_pairs, stats, round);
+    }
+    F3D_TRY(hipGetLastError());
+    F3D_TRY(hipMemcpyAsync(pose_out, pose, 7 * sizeof(double), hipMemcpyDeviceToDevice, s));
+    if (status) F3D_TRY(hipMemcpyAsync(status, lost, sizeof(int32_t), hipMemcpyDeviceToDevice, s));
+    return hipSuccess;
+}

@@ -675,6 +675,28 @@ hipError_t f3d_launch_tsdf_count(const float* tsdf, const float* weight, int nx,
 hipError_t f3d_launch_tsdf_fill(const float* tsdf, int nx, int ny, int nz, const double lo[3], double vs, const void* scratch, double* verts,
                                 int32_t* tris, int grid_cap, hipStream_t s);
 
+// Registration (f3d_icp.hip; the contract is in include/f3d.h).  Device pointers; lo, K, qn / q and t on the host.  Enqueue only.
+// The raycast takes the quaternion already normalised (qn).  grid_cap as for the TSDF launches.
+hipError_t f3d_launch_tsdf_raycast(const float* tsdf, const float* weight, int nx, int ny, int nz, const double lo[3], double vs, float min_weight,
+                                   const double K[9], const double qn[4], const double t[3], int h, int w, double near, double step, int nsteps,
+                                   double* vertex, double* normal, double* depth, int grid_cap, hipStream_t s);
+// the source frame, the model maps and the model camera of an ICP call.  scratch: f3d_icp_scratch_bytes(h * w); it holds the chunk
+// sums, the pose between the rounds and the lost flag.  sums [29], pose_out [7], stats [iterations, 3] and status (may be NULL) are device
+// pointers.
+struct f3d_icp_args {
+    const void* depth; int depth_type, h, w;
+    const double* K;
+    double depth_scale, max_depth;
+    const double* model_vertex; const double* model_normal;
+    int hm, wm;
+    const f3d_view* model_view;
+    double max_dist;
+};
+size_t f3d_icp_scratch_bytes(int64_t npixels);
+hipError_t f3d_launch_icp_sums(const f3d_icp_args& a, const double q[4], const double t[3], void* scratch, double* sums, hipStream_t s);
+hipError_t f3d_launch_icp(const f3d_icp_args& a, const double q[4], const double t[3], int iterations, int min_pairs, void* scratch,
+                          double* pose_out, double* stats, int32_t* status, hipStream_t s);
+
 // plane table of a cloud over its adjacency (f3d_planes.hip).  Device pointers (counts int64 [4] too); normals (may be NULL: PCA of the
 // rows) and normals_out (may be NULL; written in PCA mode only) float64 [n, 3].  n >= 1.  Enqueues on `s` and synchronises it every few
 // attach rounds.  A neighbour outside [0, n) sets F3D_DEVERR_PLANES and nothing is written.  scratch: f3d_planes_scratch_bytes(n)

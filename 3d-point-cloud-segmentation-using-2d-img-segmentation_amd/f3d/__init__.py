@@ -38,6 +38,10 @@ VOTES_F64, VOTES_U16 = 0, 1  # f3d_vtype: the element type of a vote matrix hand
 SMOOTH_MAX_COLS = 256        # the widest vote matrix smooth_votes / smooth_segment take
 KNN_MAX_K = 32               # F3D_KNN_MAX_K: the largest k of knn_query / transfer_labels
 TSDF_SCAN_TILE = 2048        # F3D_TSDF_SCAN_TILE: counts per tile of the extract scans (scanned by blocks of 256 threads)
+ICP_CHUNK = 256              # F3D_ICP_CHUNK: source pixels per chunk of the ICP sums (one wave per chunk)
+ICP_NSUMS = 29               # F3D_ICP_NSUMS: 21 J J^T products, 6 J r, r r and the pair count
+ICP_PIVOT_EPS = 1e-10        # F3D_ICP_PIVOT_EPS: the smallest Cholesky pivot, as a fraction of the largest diagonal entry
+ICP_OK, ICP_LOST = 0, 1      # status of an icp round (f3d.h F3D_ICP_*)
 
 
 class F3DError(RuntimeError):
@@ -243,6 +247,13 @@ def library():
         'f3d_fuse_features_dev': (i32, [vp, vp, i32, i64, vp, i32, i32, i32, vp, i32, i32, i32, i32, i32, dbl, vp, vp, i32, vp]),
         'f3d_features_finalize': (i32, [vp, vp, vp, i64, i32, i32, vp]),
         'f3d_features_finalize_dev': (i32, [vp, vp, vp, i64, i32, i32, vp, vp]),
+        'f3d_tsdf_raycast': (i32, [vp, vp, vp, i32, i32, i32, vp, dbl, flt, vp, vp, vp, i32, i32, dbl, dbl, i32, vp, vp, vp]),
+        'f3d_tsdf_raycast_dev': (i32, [vp, vp, vp, i32, i32, i32, vp, dbl, flt, vp, vp, vp, i32, i32, dbl, dbl, i32, vp, vp, vp, vp]),
+        'f3d_icp_sums': (i32, [vp, vp, i32, i32, i32, vp, dbl, dbl, vp, vp, vp, vp, i32, i32, vp, dbl, vp]),
+        'f3d_icp_sums_dev': (i32, [vp, vp, i32, i32, i32, vp, dbl, dbl, vp, vp, vp, vp, i32, i32, vp, dbl, vp, vp]),
+        'f3d_icp': (i32, [vp, vp, i32, i32, i32, vp, dbl, dbl, vp, vp, vp, vp, i32, i32, vp, dbl, i32, i32, vp, vp, vp]),
+        'f3d_icp_dev': (i32, [vp, vp, i32, i32, i32, vp, dbl, dbl, vp, vp, vp, vp, i32, i32, vp, dbl, i32, i32, vp, vp, vp, vp]),
+        'f3d_ctx_reserve_icp': (i32, [vp, i64]),
     }
     for name, (res, args) in protos.items():
         fn = getattr(lib, name)          # AttributeError here = header/library mismatch
@@ -416,6 +427,21 @@ def _tsdf_frames(lo, depths, views):
     if len(views) != len(d):
         raise ValueError(f'{len(views)} views for {len(d)} depth frames')
     return _f64(lo, (3,)), d, depth_code(d), views
+
+
+def _icp_arrays(depth, K, q_wxyz, t, model_vertex, model_normal, hm, wm, model_view):
+    """The host arrays of icp_sums / icp as the C entry reads them: (depth [h, w], its depth code, K, q, t, the two model maps [hm*wm, 3],
+    the model view [88])."""
+    d = np.ascontiguousarray(depth)
+    if d.ndim != 2 or d.size == 0:
+        raise ValueError(f'depth must be one [h, w] frame with pixels, got {d.shape}')
+    hm, wm = int(hm), int(wm)
+    if hm < 1 or wm < 1:
+        raise ValueError('the model image must have pixels')
+    mv, mn = _f64(model_vertex), _f64(model_normal)
+    if mv.size != hm * wm * 3 or mn.size != hm * wm * 3:
+        raise ValueError(f'the model maps must be [{hm} * {wm}, 3], got {mv.shape} and {mn.shape}')
+    return d, depth_code(d), _f64(K, (3, 3)), _f64(q_wxyz, (4,)), _f64(t, (3,)), mv, mn, _f64(np.asarray(model_view).reshape(-1), (VIEW_DOUBLES,))
 
 
 def _knn_k(k):
@@ -1217,6 +1243,47 @@ class Context:
         self._check(self._lib.f3d_tsdf_extract_fill(self._h, nx, ny, nz, _ptr(lo), float(voxel), _ptr(verts), _ptr(tris)))
         return verts, tris
 
+    def reserve_icp(self, npixels):
+        """Size the scratch of icp_sums_dev / icp_dev for source frames of up to npixels pixels."""
+        self._check(self._lib.f3d_ctx_reserve_icp(self._h, int(npixels)))
+
+    def tsdf_raycast(self, tsdf, weight, lo, voxel, min_weight, K, q_wxyz, t, h, w, near, step, nsteps):
+        """Model maps of the volume from the camera->world pose (f3d.h f3d_tsdf_raycast) -> (vertex float64 [h*w, 3], normal float64
+        [h*w, 3], depth float64 [h*w]); a pixel without a hit has NaN rows and depth 0."""
+        nz, ny, nx = _tsdf_state(tsdf, weight)
+        lo, K, q, t = _f64(lo, (3,)), _f64(K, (3, 3)), _f64(q_wxyz, (4,)), _f64(t, (3,))
+        h, w = int(h), int(w)
+        if h < 1 or w < 1:
+            raise ValueError('the image must have pixels')
+        vertex, normal, depth = np.empty((h * w, 3)), np.empty((h * w, 3)), np.empty(h * w)
+        self._check(self._lib.f3d_tsdf_raycast(self._h, _ptr(tsdf), _ptr(weight), nx, ny, nz, _ptr(lo), float(voxel), float(min_weight), _ptr(K),
+                                               _ptr(q), _ptr(t), h, w, float(near), float(step), int(nsteps), _ptr(vertex), _ptr(normal),
+                                               _ptr(depth)))
+        return vertex, normal, depth
+
+    def icp_sums(self, depth, K, q_wxyz, t, model_vertex, model_normal, hm, wm, model_view, max_dist, depth_scale=1.0, max_depth=10.0):
+        """The 29 sums of one point-to-plane linearisation (f3d.h f3d_icp_sums): depth [h, w] (uint16, float32 or float64) at the
+        camera->world pose against the model maps float64 [hm*wm, 3] seen by model_view (one row of views_build) -> float64 [29]."""
+        d, code, K, q, t, mv, mn, view = _icp_arrays(depth, K, q_wxyz, t, model_vertex, model_normal, hm, wm, model_view)
+        sums = np.empty(ICP_NSUMS)
+        self._check(self._lib.f3d_icp_sums(self._h, _ptr(d), code, d.shape[0], d.shape[1], _ptr(K), float(depth_scale), float(max_depth), _ptr(q),
+                                           _ptr(t), _ptr(mv), _ptr(mn), int(hm), int(wm), _ptr(view), float(max_dist), _ptr(sums)))
+        return sums
+
+    def icp(self, depth, K, q_wxyz, t, model_vertex, model_normal, hm, wm, model_view, max_dist, depth_scale=1.0, max_depth=10.0, iterations=10,
+            min_pairs=100):
+        """`iterations` rounds of point-to-plane ICP on the device (f3d.h f3d_icp) -> (pose float64 [7] = wxyz, t; stats float64
+        [iterations, 3] = count, sum r^2, status per round; the final status ICP_OK / ICP_LOST)."""
+        d, code, K, q, t, mv, mn, view = _icp_arrays(depth, K, q_wxyz, t, model_vertex, model_normal, hm, wm, model_view)
+        iterations = int(iterations)
+        if iterations < 1:
+            raise ValueError(f'iterations must be at least 1, got {iterations}')
+        pose, stats, status = np.empty(7), np.empty((iterations, 3)), C.c_int32(0)
+        self._check(self._lib.f3d_icp(self._h, _ptr(d), code, d.shape[0], d.shape[1], _ptr(K), float(depth_scale), float(max_depth), _ptr(q), _ptr(t),
+                                      _ptr(mv), _ptr(mn), int(hm), int(wm), _ptr(view), float(max_dist), iterations, int(min_pairs), _ptr(pose),
+                                      _ptr(stats), C.byref(status)))
+        return pose, stats, status.value
+
     def radius_graph(self, points, radius):
         """KDTree(points).query_radius(points, r=radius) (fusion.py:374-375) as CSR: (offsets int64 [n+1], neighbours int32)."""
         p, dt = _xyz(points)
@@ -1503,6 +1570,32 @@ class Context:
         lo = _f64(lo, (3,))
         nx, ny, nz = (int(x) for x in dims)
         self._check(self._lib.f3d_tsdf_extract_fill_dev(self._h, tsdf_ptr, nx, ny, nz, _ptr(lo), float(voxel), verts_ptr, tris_ptr, stream))
+
+    def tsdf_raycast_dev(self, tsdf_ptr, weight_ptr, dims, lo, voxel, min_weight, K, q_wxyz, t, h, w, near, step, nsteps, vertex_ptr, normal_ptr,
+                         depth_ptr, stream=None):
+        """dims = (nx, ny, nz); lo, K and the pose on the host; the state and the three outputs (each may be None) device pointers
+        (f3d.h f3d_tsdf_raycast_dev).  Enqueue only."""
+        lo, K, q, t = _f64(lo, (3,)), _f64(K, (3, 3)), _f64(q_wxyz, (4,)), _f64(t, (3,))
+        nx, ny, nz = (int(x) for x in dims)
+        self._check(self._lib.f3d_tsdf_raycast_dev(self._h, tsdf_ptr, weight_ptr, nx, ny, nz, _ptr(lo), float(voxel), float(min_weight), _ptr(K),
+                                                   _ptr(q), _ptr(t), int(h), int(w), float(near), float(step), int(nsteps), vertex_ptr, normal_ptr,
+                                                   depth_ptr, stream))
+
+    def icp_sums_dev(self, depth_ptr, depth_type, h, w, K, q_wxyz, t, vertex_ptr, normal_ptr, hm, wm, view_ptr, max_dist, depth_scale, max_depth,
+                     sums_ptr, stream=None):
+        """K and the source pose on the host, everything else device pointers (view_ptr: one f3d_view); sums float64 [29].  Enqueue only."""
+        K, q, t = _f64(K, (3, 3)), _f64(q_wxyz, (4,)), _f64(t, (3,))
+        self._check(self._lib.f3d_icp_sums_dev(self._h, depth_ptr, int(depth_type), int(h), int(w), _ptr(K), float(depth_scale), float(max_depth),
+                                               _ptr(q), _ptr(t), vertex_ptr, normal_ptr, int(hm), int(wm), view_ptr, float(max_dist), sums_ptr, stream))
+
+    def icp_dev(self, depth_ptr, depth_type, h, w, K, q_wxyz, t, vertex_ptr, normal_ptr, hm, wm, view_ptr, max_dist, depth_scale, max_depth,
+                iterations, min_pairs, pose_ptr, stats_ptr, status_ptr=None, stream=None):
+        """As icp_sums_dev; pose float64 [7], stats float64 [iterations, 3] and status int32 [1] (may be None) on the device.  Enqueue
+        only: no host synchronisation between the rounds or after them."""
+        K, q, t = _f64(K, (3, 3)), _f64(q_wxyz, (4,)), _f64(t, (3,))
+        self._check(self._lib.f3d_icp_dev(self._h, depth_ptr, int(depth_type), int(h), int(w), _ptr(K), float(depth_scale), float(max_depth), _ptr(q),
+                                          _ptr(t), vertex_ptr, normal_ptr, int(hm), int(wm), view_ptr, float(max_dist), int(iterations),
+                                          int(min_pairs), pose_ptr, stats_ptr, status_ptr, stream))
 
     def take_device_error(self, stream=None):
         self._check(self._lib.f3d_take_device_error(self._h, stream))

@@ -1258,6 +1258,104 @@ int f3d_features_finalize(f3d_ctx* ctx, const float* sums, const int32_t* counts
 int f3d_features_finalize_dev(f3d_ctx* ctx, const float* sums, const int32_t* counts, int64_t n, int d, int normalize, float* out,
                               void* stream);
 
+/* ---- registration: TSDF raycast and point-to-plane ICP pose refinement (no reference counterpart) -------------------------- */
+/* Every other entry takes its camera poses as given.  These produce one: ray-cast the TSDF volume from a pose into a vertex map and a
+ * normal map (the model), align a depth frame to the maps by projective point-to-plane ICP, integrate the frame at the refined pose:
+ * frame-to-model tracking.  All arithmetic is float64 without contraction, every product, sum, division and sqrt as written; there is
+ * no sin, cos or atan in the contract.  dot(a, b) = (a0*b0 + a1*b1) + a2*b2; cross(a, b) = (a1*b2 - a2*b1, a2*b0 - a0*b2,
+ * a0*b1 - a1*b0); rotate is f3d_rotate_f64's q p conj(q), project_h the homogeneous pixel of f3d_tsdf_integrate's step 1.
+ *   pixels     the convention of the TSDF, not that of f3d_unproject_depth: f3d_tsdf_integrate gives the depth of pixel (u, v) to
+ *              everything that projects into [u, u+1) x [v, v+1), so a pixel stands for the ray through (u + 0.5, v + 0.5).  With
+ *              fx = K[0], cx = K[2], fy = K[4], cy = K[5] (the other entries of K are not read) the camera-frame ray of a pixel is
+ *              dc = (((double)u + 0.5 - cx) / fx, ((double)v + 0.5 - cy) / fy, 1.0).  f3d_unproject_depth keeps the reference's
+ *              integer grid (the ray through (u, v)).
+ *   quaternion a camera->world q (w, x, y, z) is normalised as qn = q / sqrt(((q0*q0 + q1*q1) + q2*q2) + q3*q3), by component
+ *              division; a zero or non-finite quaternion is F3D_ERR_INVALID.
+ * f3d_tsdf_raycast: model maps of the volume (tsdf, weight, dims, lo, vs, min_weight >= 1 as for extract) from the pose (q_wxyz, t)
+ * for an h x w image; znear >= 0, step > 0, nsteps >= 1.  Outputs, each may be NULL: vertex float64 [h*w, 3] (world), normal
+ * float64 [h*w, 3] (unit, world), depth float64 [h*w] (camera z).  A pixel without a hit gets NaN rows and depth 0.
+ *   ray        dw = rotate(qn, dc); the point at parameter s is P_a(s) = t[a] + s * dw_a; dc.z = 1, so s is the camera-z depth.
+ *   F(P)       g_a = (P_a - lo[a]) / vs - 0.5, i_a = floor(g_a).  The sample is valid iff 0 <= i_a <= n_a - 2 on all axes (NaN
+ *              fails) and all 8 corner weights are >= min_weight.  f_a = g_a - (double)i_a.  With the corner samples T_ijk
+ *              (offsets i, j, k in {0, 1} along x, y, z) widened to double: c_jk = T0jk + f_x * (T1jk - T0jk);
+ *              c_k = c_0k + f_y * (c_1k - c_0k); F = c_0 + f_z * (c_1 - c_0).
+ *   march      s_k = znear + (double)k * step, k = 0 .. nsteps-1 (no running sum).  The ray ends at the first valid sample with
+ *              F_k < 0 (+0.0 and -0.0 are outside, as in extract).  It is a hit iff k >= 1 and sample k-1 was valid with
+ *              F_{k-1} >= 0; then s* = s_{k-1} + step * (F_{k-1} / (F_{k-1} - F_k)).  Otherwise (the ray entered the surface from
+ *              behind or from unobserved space, or never ended) it is no hit.
+ *   normal     V = P(s*); G_a = F(V + vs e_a) - F(V - vs e_a), e_a the unit axis vector (the other two coordinates are V's own).  Any of
+ *              the six samples invalid: no hit.  len = sqrt((G0*G0 + G1*G1) + G2*G2); len == 0 or not finite: no hit.
+ *              normal = G / len: the stored TSDF is positive in front of the surface, so the normal points out of it, towards where
+ *              the cameras were.  vertex = V, depth = s*.
+ * The kernel skips samples that the index rule above calls invalid (a slab test of the ray against the volume with a wide margin);
+ * no bit of the output depends on that, on the launch shape or on f3d_debug_tsdf_grid_cap, which caps this launch too.
+ * f3d_icp_sums: one linearisation of the alignment of a source depth frame (depth, depth_type, h, w, K, depth_scale, max_depth as in
+ * f3d_tsdf_integrate, one frame) at the source pose (q_wxyz, t) to the model maps model_vertex, model_normal float64 [hm*wm, 3]
+ * (world frame, NaN = missing; usually from f3d_tsdf_raycast, or from another frame through f3d_unproject_depth and
+ * f3d_estimate_normals) seen by the model camera model_view (one record of f3d_views_build for an hm x wm image; its planes play no
+ * part).  max_dist > 0.  Per source pixel i = v*w + u; a pixel that fails a step contributes 0.0 to every sum:
+ *   1. d = (double)raw / depth_scale; d > 0 && d <= max_depth.
+ *   2. c = (((double)u + 0.5 - cx) * (d / fx), ((double)v + 0.5 - cy) * (d / fy), d); pr = rotate(qn, c); p = pr + t.
+ *   3. (h0, h1, h2) = project_h(Km, qinv_m, t_m, p); h2 > 0; x = h0 / h2, y = h1 / h2; 0 <= x < wm and 0 <= y < hm;
+ *      um = (int)floor(x), vm = (int)floor(y).
+ *   4. V, N = the model rows at vm*wm + um; all six values finite.
+ *   5. e = p - V; (e0*e0 + e1*e1) + e2*e2 <= max_dist * max_dist.
+ *   6. r = dot(N, e); J = (cross(pr, N), N): the increment rotates about the current camera centre, which keeps the system well
+ *      conditioned for clouds far from the origin.
+ *   7. the F3D_ICP_NSUMS = 29 terms: the 21 products J_a * J_b, a <= b, row-major; the 6 products J_a * r; r * r; 1.0.
+ * Each of the 29 sums runs over the pixel indices 0 .. h*w-1 in chunks of F3D_ICP_CHUNK pixels.  A chunk sum: lane l of 64 adds the
+ * chunk's items l, l + 64, .. left to right from 0.0, then the 64 lane sums meet in an xor butterfly 32, 16, .., 1
+ * (acc = acc + acc[lane ^ off]).  The total is the same sum of all the chunk sums.  Output: sums float64 [29].
+ * f3d_icp: iterations >= 1 rounds of that on the device, with no host synchronisation in the _dev entry; min_pairs >= 6.  Each round,
+ * at the current pose (q, t):
+ *   totals     as above; count = the last total.  count < min_pairs: the status becomes F3D_ICP_LOST.
+ *   solve      A = the symmetric 6 x 6 matrix of the 21 sums, b_a = -(sum J_a r), maxd = the largest A_aa.  Cholesky A = L L^T, column by
+ *              column: for j = 0 .. 5: s = A_jj; s = s - L_jk * L_jk for k = 0 .. j-1; the pivot s must be finite and
+ *              > F3D_ICP_PIVOT_EPS * maxd, otherwise the status becomes F3D_ICP_LOST; L_jj = sqrt(s); for i = j+1 .. 5: e = A_ij;
+ *              e = e - L_ik * L_jk for k = 0 .. j-1; L_ij = e / L_jj.  Forward: for i = 0 .. 5: s = b_i; s = s - L_ik * y_k for
+ *              k = 0 .. i-1; y_i = s / L_ii.  Back: for i = 5 .. 0: s = y_i; s = s - L_ki * x_k for k = i+1 .. 5; x_i = s / L_ii.
+ *              x = (omega, v).  F3D_ICP_PIVOT_EPS guards against a degenerate scene; it is not a tuning value.
+ *   update     dq = (1, omega0 / 2, omega1 / 2, omega2 / 2); q' = dq (x) qn, the Hamilton product, each component left to right:
+ *              w = ((a0*b0 - a1*b1) - a2*b2) - a3*b3, x = ((a0*b1 + a1*b0) + a2*b3) - a3*b2, y = ((a0*b2 - a1*b3) + a2*b0) + a3*b1,
+ *              z = ((a0*b3 + a1*b2) - a2*b1) + a3*b0 with a = dq, b = qn; q' is normalised as above; t' = t + v.
+ *   once lost  the pose stays as it was at the start of that round and the remaining rounds do nothing.
+ * Outputs: pose float64 [7] = q', t'; stats float64 [iterations, 3] = {count, sum r*r, status} per round, measured before that
+ * round's update; rows after a lost round are {0, 0, 1}; status = the final F3D_ICP_OK / F3D_ICP_LOST (int32; a device word in the _dev
+ * entry, may be NULL there).
+ * Scratch: the chunk sums [nchunks, 29], the pose and the lost flag (the 29 totals of a round stay in LDS);
+ * f3d_ctx_reserve_icp(npixels) sizes it, and a strict context then allocates nothing in the _dev entries.  The raycast needs none.
+ * F3D_ERR_INVALID, with nothing written: NULLs (but for the optional outputs); non-positive sizes; h*w or hm*wm >= 2^31; the bad volume
+ * arguments of extract; vs, step, depth_scale, max_depth or max_dist not finite and positive; znear negative or not finite;
+ * nsteps < 1; iterations < 1; min_pairs < 6; a non-finite K, t or lo; a zero or non-finite quaternion; an unknown depth type. */
+#define F3D_ICP_CHUNK 256
+#define F3D_ICP_NSUMS 29
+#define F3D_ICP_PIVOT_EPS 1e-10
+#define F3D_ICP_OK 0
+#define F3D_ICP_LOST 1
+int f3d_tsdf_raycast(f3d_ctx* ctx, const float* tsdf, const float* weight, int nx, int ny, int nz, const double lo[3], double vs,
+                     float min_weight, const double K[9], const double q_wxyz[4], const double t[3], int h, int w, double znear,
+                     double step, int nsteps, double* vertex /*[h*w,3]*/, double* normal /*[h*w,3]*/, double* depth /*[h*w]*/);
+int f3d_tsdf_raycast_dev(f3d_ctx* ctx, const float* tsdf, const float* weight, int nx, int ny, int nz, const double lo[3] /*host*/,
+                         double vs, float min_weight, const double K[9] /*host*/, const double q_wxyz[4] /*host*/,
+                         const double t[3] /*host*/, int h, int w, double znear, double step, int nsteps, double* vertex,
+                         double* normal, double* depth, void* stream);
+int f3d_icp_sums(f3d_ctx* ctx, const void* depth, int depth_type, int h, int w, const double K[9], double depth_scale, double max_depth,
+                 const double q_wxyz[4], const double t[3], const double* model_vertex, const double* model_normal, int hm, int wm,
+                 const f3d_view* model_view, double max_dist, double* sums /*[29]*/);
+int f3d_icp_sums_dev(f3d_ctx* ctx, const void* depth, int depth_type, int h, int w, const double K[9] /*host*/, double depth_scale,
+                     double max_depth, const double q_wxyz[4] /*host*/, const double t[3] /*host*/, const double* model_vertex,
+                     const double* model_normal, int hm, int wm, const f3d_view* model_view /*device*/, double max_dist,
+                     double* sums, void* stream);
+int f3d_icp(f3d_ctx* ctx, const void* depth, int depth_type, int h, int w, const double K[9], double depth_scale, double max_depth,
+            const double q_wxyz[4], const double t[3], const double* model_vertex, const double* model_normal, int hm, int wm,
+            const f3d_view* model_view, double max_dist, int iterations, int min_pairs, double* pose /*[7]*/,
+            double* stats /*[iterations,3]*/, int32_t* status);
+int f3d_icp_dev(f3d_ctx* ctx, const void* depth, int depth_type, int h, int w, const double K[9] /*host*/, double depth_scale,
+                double max_depth, const double q_wxyz[4] /*host*/, const double t[3] /*host*/, const double* model_vertex,
+                const double* model_normal, int hm, int wm, const f3d_view* model_view /*device*/, double max_dist, int iterations,
+                int min_pairs, double* pose, double* stats, int32_t* status /*device, may be NULL*/, void* stream);
+int f3d_ctx_reserve_icp(f3d_ctx* ctx, int64_t npixels);
+
 #ifdef __cplusplus
 }
 #endif
