@@ -1,290 +1,9 @@
-// C-ABI layer of libf3d_hip.so (see include/f3d.h): context, scratch arena, host-pointer
-// wrappers, and the tiny per-view host geometry.  No CPU fallback: every compute entry point
-// needs a HIP device.
-#include <hip/hip_runtime.h>
-#include <initializer_list>
-#include <vector>
-#include <cstddef>
-#include <math.h>
-#include <stdarg.h>
-#include <stdio.h>
-#include <stdlib.h>
-#include <string.h>
-
-#include "f3d.h"
-#include "f3d_kernels.h"
-#include "f3d_math.h"
-
-static_assert(sizeof(f3d_view) == 704, "f3d_view is 88 doubles");
-static_assert(offsetof(f3d_view, t) == 72 && offsetof(f3d_view, mnorm) == 96, "the kernels stage M, t, mnorm as the record's first 15 doubles");
-static_assert(offsetof(f3d_view, img_h) == offsetof(f3d_view, cull_n32) + 23 * 4, "cull planes, margins and image size: 24 consecutive floats");
-
-#pragma clang fp contract(off)
+// C-ABI layer of libf3d_hip.so (see include/f3d.h): the subsystems' entry points, their host-pointer
+// wrappers, and the tiny per-view host geometry; the context and its arenas are in f3d_ctx.h / f3d_ctx.cpp.
+// No CPU fallback: every compute entry point needs a HIP device.
+#include "f3d_ctx.h"
 
 namespace {
-
-// Device memory of a context, three kinds of buffer with a type each, so that a name of one kind does not compile where another
-// is expected.  All grow on first use of a larger problem (grow()) and are refused growth by a strict context.
-//   scratch_slot: the work area of a _dev entry (grids, sort buffers, coded masks, ...), one name per area; only _dev entries
-//                 ensure() them, and f3d_ctx_reserve* sizes them.  Some hold state between two _dev calls (the grid between a count
-//                 and its fill pass, the coded masks and the todo list of a view-chunked fused call).
-//   staging:      the device copies of a host-pointer entry's arguments.  They have no names: the k-th buffer a call asks for
-//                 is ctx->stage[k] (struct staging), and nothing in them outlives the call.
-//   kept_slot:    what a host-pointer SEQUENCE leaves on the device for its next call, owned by that sequence alone
-//                 (f3d_ctx::graph_kept, qry_kept, grp_cloud say whether they hold it).
-enum scratch_slot { SLOT_OBB_BOXES = 0, SLOT_SORT_PERM, SLOT_SORT_SCRATCH, SLOT_TILED_MASKS, SLOT_TODO, SLOT_GRAPH, SLOT_GRAPH_BBOX,
-                    SLOT_PATCH, SLOT_GRP_SCRATCH, SLOT_OBB_TABLE, SLOT_OBB_FACETS, SLOT_OBB_CAND, SLOT_FUSE_TABLES, SLOT_FUSE_CARRY,
-                    SLOT_FUSE_XYZ, SLOT_FUSION, SLOT_PATCH_STATUS, SLOT_NRM, SLOT_NRM_CAMS, SLOT_QRY, SLOT_FLOOD, SLOT_COLOR,
-                    SLOT_CVS_INST, SLOT_CVS_STATS, SLOT_QUADS, SLOT_GROW, SLOT_PVOTE, SLOT_PVOTE_BITS, SLOT_MESH, SLOT_ZKEY,
-                    SLOT_ZCOUNTS, SLOT_KNN, SLOT_KNN_FLAG, SLOT_PLANES, SLOT_RASTER, SLOT_ZLUT, SLOT_SMOOTH, SLOT_FACE_GRAPH, SLOT_LIFT, SLOT_LIFT_TABLE,
-                    SLOT_TSDF, SLOT_ICP, SLOT_COUNT };
-enum kept_slot { KEPT_GRAPH_OFFS = 0,                                      // f3d_radius_graph_count -> _fill: the offsets
-                 KEPT_QRY_IN, KEPT_QRY_OFFS,                               // f3d_radius_query_count -> _fill: the queries, the offsets
-                 KEPT_GRP_ORDER, KEPT_GRP_KEYS, KEPT_GRP_STARTS,           // f3d_group_by_id -> f3d_obb_extremes -> f3d_obb_hull_filter
-                 KEPT_GRP_XYZ,                                             //   ... and, from the extremes call on, the cloud
-                 KEPT_TSDF,                                                // f3d_tsdf_extract_count -> _fill: the samples
-                 KEPT_COUNT };
-enum { STAGE_MAX = 9,                                                      // staging buffers of one call: f3d_patch_match and f3d_door_window_quads take 9
-       BACK_MAX = 5 };                                                     // outputs one call copies back: f3d_mesh_clean has 5
-
-struct devbuf { void* p; size_t cap; };
-
-thread_local char g_create_err[512] = "";
-
-}  // namespace
-
-struct f3d_ctx {
-    int device;
-    hipStream_t stream;
-    char err[512];
-    devbuf scratch[SLOT_COUNT];
-    devbuf stage[STAGE_MAX];
-    devbuf kept[KEPT_COUNT];
-    int* dev_err;                       // sticky device error word: one bit per operation (F3D_DEVERR_*)
-    int strict;                         // 1: a scratch buffer that would have to grow is F3D_ERR_NOMEM (allocation-free _dev calls)
-    long long allocs;                   // device allocations made by this context so far (f3d_ctx_alloc_count)
-    unsigned long long* table;          // open-addressing set of the uv2pt vote
-    size_t table_slots;
-    unsigned vote_gen;                  // generation stamp of the batched vote's set entries (the set is cleared when it wraps)
-    bool table_stamped;                 // the table holds generation-stamped entries only (else: clear before a batched call)
-    int* first_bad;                     // device int: first frame of the current batched call with an out-of-range index
-    int* filter_dev;                    // filter_classes of the call being enqueued (device copy)
-    int32_t filter_host[F3D_MAX_FILTER];  // its staging copy: must outlive the asynchronous upload
-    unsigned long long* count_dev;
-    f3d_codebook* codebook;             // vote-bin code book of the fused path (device)
-    f3d_fuse_occupancy fuse_occ;        // blocks per CU of the k_fuse instances launched so far (asked of the runtime once each)
-    // radius graph: the search of the last count pass (the fill pass must follow it for the same cloud); graph_kept: that pass was
-    // f3d_radius_graph_count, whose offsets KEPT_GRAPH_OFFS holds
-    f3d_gridsearch graph;
-    int64_t graph_n;
-    bool graph_kept;
-    // radius query: the search of the last count pass, its grid in SLOT_QRY, for the fill pass of the same queries; qry_kept: that
-    // pass was f3d_radius_query_count, whose queries and offsets KEPT_QRY_IN / KEPT_QRY_OFFS hold
-    f3d_gridsearch qry;
-    int64_t qry_m, qry_n;
-    int qry_qdtype;
-    const void* qry_queries;
-    bool qry_kept;
-    // point vote: device int[4] of the call being enqueued (f3d_kernels.h); pv_partial: the last call stopped at a frame with
-    // non-finite queries after applying the frames before it (the host-pointer entry still copies the votes back)
-    int* pv_words;
-    int pv_partial;
-    // instance grouping of the last f3d_group_by_id call (host-pointer sequence group -> extremes -> hull filter), in KEPT_GRP_*;
-    // grp_cloud: f3d_obb_extremes has run for this grouping and left its cloud (of grp_dtype) in KEPT_GRP_XYZ
-    int64_t grp_n, grp_nids;
-    int grp_dtype;
-    bool grp_cloud;
-    // TSDF extract: dims and totals of the last count pass (tsdf_n = -1: none), its codes, ranks and offsets in SLOT_TSDF; tsdf_kept: that
-    // pass was f3d_tsdf_extract_count, whose samples KEPT_TSDF holds
-    int64_t tsdf_n, tsdf_nv, tsdf_nq;
-    int tsdf_dims[3];
-    bool tsdf_kept;
-    unsigned long long tsdf_counts[2];  // readback target of the count pass
-    int tsdf_grid_cap;                  // f3d_debug_tsdf_grid_cap (0 = the library's launch shapes)
-    // view-chunked fused call in progress (f3d_fuse_chunked_begin_dev .. the chunk with v_end == nviews)
-    struct { int active, next, nviews, h, w, nclasses, gather; int64_t n; const int32_t* perm; const void* xyz; f3d_fuse_todo lay; } chunk;
-};
-
-namespace {
-
-int fail(f3d_ctx* ctx, int code, const char* fmt, ...) {
-    char* dst = ctx ? ctx->err : g_create_err;
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(dst, 512, fmt, ap);
-    va_end(ap);
-    return code;
-}
-
-#define F3D_HIP(ctx, call)                                                                               \
-    do {                                                                                                 \
-        hipError_t e_ = (call);                                                                          \
-        if (e_ != hipSuccess) return fail(ctx, e_ == hipErrorOutOfMemory ? F3D_ERR_NOMEM : F3D_ERR_HIP,  \
-                                          "%s: %s", #call, hipGetErrorString(e_));                       \
-    } while (0)
-
-// One buffer of the context with room for `bytes`: it grows (with 1/8 of headroom) when it is too small, which a strict context refuses.
-int grow(f3d_ctx* ctx, devbuf* b, size_t bytes, const char* kind, int index, void** out) {
-    if (bytes == 0) bytes = 16;
-    if (b->cap < bytes) {
-        if (ctx->strict)
-            return fail(ctx, F3D_ERR_NOMEM, "strict context: %s buffer %d holds %zu bytes, %zu needed (f3d_ctx_reserve first)", kind, index, b->cap, bytes);
-        if (b->p) { F3D_HIP(ctx, hipFree(b->p)); b->p = nullptr; b->cap = 0; }
-        size_t want = bytes + bytes / 8;
-        F3D_HIP(ctx, hipMalloc(&b->p, want));
-        b->cap = want;
-        ++ctx->allocs;
-    }
-    *out = b->p;
-    return F3D_OK;
-}
-
-int ensure(f3d_ctx* ctx, scratch_slot s, size_t bytes, void** out) { return grow(ctx, &ctx->scratch[s], bytes, "scratch", s, out); }
-
-bool dtype_ok(int dt) { return dt == F3D_F64 || dt == F3D_F32; }
-
-hipStream_t pick(f3d_ctx* ctx, void* stream) { return stream ? (hipStream_t)stream : ctx->stream; }
-
-int enter(f3d_ctx* ctx) {
-    if (!ctx) return fail(nullptr, F3D_ERR_INVALID, "null context");
-    ctx->err[0] = 0;
-    F3D_HIP(ctx, hipSetDevice(ctx->device));
-    return F3D_OK;
-}
-
-size_t xyz_bytes(f3d_dtype dt, int64_t n) { return (size_t)n * 3 * (dt == F3D_F64 ? 8 : 4); }
-
-int make_filter(f3d_ctx* ctx, const int32_t* filter, int nfilter, int ncols, bool cols_must_exist, hipStream_t s,
-                f3d_filter_args* fa) {
-    fa->nfilter = 0; fa->cls_dev = nullptr; fa->cls_host = nullptr;
-    for (int k = 0; k < 8; ++k) fa->cls[k] = -1;
-    if (nfilter < 0 || nfilter > F3D_MAX_FILTER) return fail(ctx, F3D_ERR_INVALID, "nfilter %d out of range", nfilter);
-    if (nfilter == 0 || !filter) {
-        if (nfilter != 0) return fail(ctx, F3D_ERR_INVALID, "filter is NULL");
-        return F3D_OK;
-    }
-    for (int k = 0; k < nfilter; ++k) {
-        // votes[:, filter_classes] raises IndexError for a column that does not exist (voting.py:121)
-        if (cols_must_exist && (filter[k] >= ncols || filter[k] < -ncols))
-            return fail(ctx, F3D_ERR_INDEX, "filter class %d is out of bounds for %d vote columns", filter[k], ncols);
-    }
-    fa->nfilter = nfilter;
-    int32_t tmp[F3D_MAX_FILTER];
-    for (int k = 0; k < nfilter; ++k) tmp[k] = filter[k] < 0 ? filter[k] + ncols : filter[k];   // NumPy negative index
-    if (nfilter <= 8) for (int k = 0; k < nfilter; ++k) fa->cls[k] = tmp[k];
-    // the device copy always exists (the fused kernel reads the list from memory, whatever its length)
-    memcpy(ctx->filter_host, tmp, sizeof(int32_t) * nfilter);
-    F3D_HIP(ctx, hipMemcpyAsync(ctx->filter_dev, ctx->filter_host, sizeof(int32_t) * nfilter, hipMemcpyHostToDevice, s));
-    fa->cls_dev = ctx->filter_dev;
-    fa->cls_host = ctx->filter_host;
-    return F3D_OK;
-}
-
-// Reads the sticky device error word and consumes the bits in `mask` (each operation owns one bit, so that an error
-// recorded by one operation is never blamed on, or silently skips, another one that shares the context).
-int take_error(f3d_ctx* ctx, hipStream_t s, int mask = F3D_DEVERR_ALL) {
-    int e = 0;
-    F3D_HIP(ctx, hipMemcpyAsync(&e, ctx->dev_err, sizeof(int), hipMemcpyDeviceToHost, s));
-    F3D_HIP(ctx, hipStreamSynchronize(s));
-    e &= mask;
-    if (e) {
-        F3D_HIP(ctx, f3d_launch_clear_error_bits(ctx->dev_err, e, s));
-        F3D_HIP(ctx, hipStreamSynchronize(s));
-        if (e & F3D_DEVERR_FUSE)
-            return fail(ctx, F3D_ERR_INDEX, "project_vote_argmax: a sampled mask label exceeds nclasses (the reference raises IndexError at voting.py:98)");
-        if (e & F3D_DEVERR_VOTE)
-            return fail(ctx, F3D_ERR_INDEX, "vote_uv2pt: point index or mask label out of bounds (the reference raises IndexError at voting.py:98)");
-        if (e & F3D_DEVERR_CC)
-            return fail(ctx, F3D_ERR_INDEX, "components_same_class: neighbour index out of bounds");
-        if (e & F3D_DEVERR_FLOOD)
-            return fail(ctx, F3D_ERR_INDEX, "flood_order: neighbour index out of bounds");
-        if (e & F3D_DEVERR_COLOR)
-            return fail(ctx, F3D_ERR_INDEX, "color_segment: seed or neighbour index out of bounds");
-        if (e & F3D_DEVERR_GROW)
-            return fail(ctx, F3D_ERR_INDEX, "region_grow: seed or neighbour index out of bounds, or a seed listed twice");
-        if (e & F3D_DEVERR_QUADS)
-            return fail(ctx, F3D_ERR_INDEX, "door_window_quads: a triangle's vertex index is out of bounds");
-        if (e & F3D_DEVERR_PVOTE)
-            return fail(ctx, F3D_ERR_INDEX, "point_vote_frames: a mask label exceeds nclasses on a pixel that has a neighbour (the reference raises IndexError at voting.py:257)");
-        if (e & F3D_DEVERR_MESH)
-            return fail(ctx, F3D_ERR_INDEX, "mesh: a triangle's vertex index is outside [0, nv)");
-        if (e & F3D_DEVERR_PLANES)
-            return fail(ctx, F3D_ERR_INDEX, "extract_planes: neighbour index outside [0, n)");
-        if (e & F3D_DEVERR_SMOOTH)
-            return fail(ctx, F3D_ERR_INDEX, "smooth_votes: neighbour index outside [0, n), or offsets that do not ascend");
-        if (e & F3D_DEVERR_LIFT)
-            return fail(ctx, F3D_ERR_INDEX, "lift: an instance id exceeds max_ids, or a lookup is not below npoints");
-        if (e & F3D_DEVERR_RASTER)
-            return fail(ctx, F3D_ERR_INDEX, "mesh render: a triangle's vertex index is outside [0, nv)");
-        if (e & F3D_DEVERR_ZVOTE)
-            return fail(ctx, F3D_ERR_INDEX, "vote_visible: the mask label of a visible sample exceeds nclasses (the reference raises IndexError at voting.py:98)");
-    }
-    return F3D_OK;
-}
-
-// One call of an entry without "_dev" (include/f3d.h): inputs are copied into the context's staging buffers as they are staged, on
-// the context's stream; outputs are copied back by finish(), which returns after the stream has drained, so no two calls' staging
-// is alive at once and the k-th buffer a call asks for is simply ctx->stage[k].  The first failed allocation or copy stays in `rc`
-// and turns every later step into a no-op.  A NULL host pointer is not copied: a NULL output is not wanted (its buffer is passed
-// over, NULL device pointer), a NULL input (an optional one) leaves its buffer uninitialised.
-struct staging {
-    f3d_ctx* ctx;
-    int rc = F3D_OK;
-    struct { void* host; const void* dev; size_t bytes; } back_[BACK_MAX];
-    int nback = 0, next = 0;
-
-    explicit staging(f3d_ctx* c) : ctx(c) {}
-    void* slot(size_t bytes) {
-        void* p = nullptr;
-        if (!rc && next >= STAGE_MAX) rc = fail(ctx, F3D_ERR_INVALID, "staging: more than %d buffers", STAGE_MAX);
-        if (!rc) { rc = grow(ctx, &ctx->stage[next], bytes, "staging", next, &p); ++next; }
-        return p;
-    }
-    // what a host-pointer sequence leaves for its next call: a buffer of the sequence's own instead of a staging buffer
-    void* keep(kept_slot k, size_t bytes) {
-        void* p = nullptr;
-        if (!rc) rc = grow(ctx, &ctx->kept[k], bytes, "kept", k, &p);
-        return p;
-    }
-    void put(void* dev, const void* host, size_t bytes) { if (!rc && host && bytes) rc = h2d(dev, host, bytes); }
-    void back(void* host, const void* dev, size_t bytes) {
-        if (!host || !bytes || rc) return;
-        if (nback == BACK_MAX) { rc = fail(ctx, F3D_ERR_INVALID, "staging: more than %d outputs", BACK_MAX); return; }
-        back_[nback++] = {host, dev, bytes};
-    }
-    template <class T> T* in(const T* host, size_t bytes) {
-        void* p = slot(bytes);
-        put(p, host, bytes);
-        return (T*)p;
-    }
-    template <class T> T* out(T* host, size_t bytes) {
-        if (!host) { ++next; return nullptr; }                 // (a call's buffers keep their positions whatever it leaves out)
-        T* p = (T*)slot(bytes);
-        back(host, p, bytes);
-        return p;
-    }
-    template <class T> T* inout(T* host, size_t bytes) {
-        T* p = in(host, bytes);
-        back(host, p, bytes);
-        return p;
-    }
-    // Consumes the device-error bits in `mask` before the copies back (an IndexError writes nothing), or after them with
-    // `keep_partial` (what was applied before the error stays applied, as NumPy leaves it).
-    int finish(int mask = 0, bool keep_partial = false) {
-        if (rc) return rc;
-        hipStream_t s = ctx->stream;
-        if (mask && !keep_partial && (rc = take_error(ctx, s, mask))) return rc;
-        for (int k = 0; k < nback; ++k) F3D_HIP(ctx, hipMemcpyAsync(back_[k].host, back_[k].dev, back_[k].bytes, hipMemcpyDeviceToHost, s));
-        F3D_HIP(ctx, hipStreamSynchronize(s));
-        return mask && keep_partial ? take_error(ctx, s, mask) : F3D_OK;
-    }
-
-  private:
-    int h2d(void* dev, const void* host, size_t bytes) {
-        F3D_HIP(ctx, hipMemcpyAsync(dev, host, bytes, hipMemcpyHostToDevice, ctx->stream));
-        return F3D_OK;
-    }
-};
 
 // ---- host geometry, mirrored operation for operation by oracle/np_ref.py::frustum_data ------
 void inv3(const double K[9], double o[9]) {
@@ -338,119 +57,7 @@ int quat_inverse(const double q[4], double o[4]) {
     return F3D_OK;
 }
 
-// cell edge of a neighbour grid over a box of extent `ext`: a hair above the radius (two points within it are then provably in adjacent
-// cells whatever the rounding of the cell index), grown by 1.25 until fits(cells per axis) holds; dim receives the cells per axis
-template <typename Fits>
-double neighbour_cell(double radius, const double ext[3], int dim[3], Fits fits) {
-    for (double cell = radius * 1.000001 + 1e-300;; cell *= 1.25) {
-        double d[3];
-        for (int c = 0; c < 3; ++c) d[c] = floor(ext[c] / cell) + 1.0;
-        if (fits(d)) { for (int c = 0; c < 3; ++c) dim[c] = (int)d[c]; return cell; }
-    }
-}
-
 }  // namespace
-
-static int ensure_table(f3d_ctx* ctx, int64_t hw);
-
-// What every f3d_ctx_reserve* does after its argument check: sizes the listed scratch buffers (an entry with wanted == false is
-// passed over) and, with table_hw > 0, the vote table for frames of that many pixels.  Reserving is the one thing a strict context
-// may allocate for: strict is lifted here and back in place on every path.
-struct reservation { scratch_slot s; size_t bytes; bool wanted = true; };
-
-static int reserve(f3d_ctx* ctx, std::initializer_list<reservation> list, int64_t table_hw = 0) {
-    const int strict = ctx->strict;
-    ctx->strict = 0;
-    int rc = F3D_OK;
-    void* p;
-    for (const reservation& r : list) if (!rc && r.wanted) rc = ensure(ctx, r.s, r.bytes, &p);
-    if (!rc && table_hw > 0) rc = ensure_table(ctx, table_hw);
-    ctx->strict = strict;
-    return rc;
-}
-
-extern "C" {
-
-int f3d_version(void) { return F3D_VERSION; }
-
-f3d_ctx* f3d_ctx_create(int device) {
-    g_create_err[0] = 0;
-    int count = 0;
-    hipError_t e = hipGetDeviceCount(&count);
-    if (e != hipSuccess || count <= 0) {
-        fail(nullptr, F3D_ERR_HIP, "no HIP device available (%s); libf3d_hip has no CPU fallback",
-             e == hipSuccess ? "device count is 0" : hipGetErrorString(e));
-        return nullptr;
-    }
-    if (device < 0 || device >= count) { fail(nullptr, F3D_ERR_INVALID, "device %d out of range [0,%d)", device, count); return nullptr; }
-    f3d_ctx* ctx = (f3d_ctx*)calloc(1, sizeof(f3d_ctx));
-    if (ctx) { ctx->graph_n = -1; ctx->grp_n = -1; ctx->qry_n = -1; ctx->tsdf_n = -1; }
-    if (!ctx) { fail(nullptr, F3D_ERR_NOMEM, "out of host memory"); return nullptr; }
-    ctx->device = device;
-    bool ok = hipSetDevice(device) == hipSuccess && hipStreamCreateWithFlags(&ctx->stream, hipStreamNonBlocking) == hipSuccess &&
-              hipMalloc((void**)&ctx->dev_err, sizeof(int)) == hipSuccess &&
-              hipMalloc((void**)&ctx->filter_dev, sizeof(int32_t) * F3D_MAX_FILTER) == hipSuccess &&
-              hipMalloc((void**)&ctx->count_dev, sizeof(unsigned long long)) == hipSuccess &&
-              hipMalloc((void**)&ctx->codebook, sizeof(f3d_codebook)) == hipSuccess &&
-              hipMalloc((void**)&ctx->first_bad, sizeof(int)) == hipSuccess &&
-              hipMalloc((void**)&ctx->pv_words, 4 * sizeof(int)) == hipSuccess &&
-              hipMemset(ctx->dev_err, 0, sizeof(int)) == hipSuccess &&
-              hipMemset(ctx->codebook, 0, sizeof(f3d_codebook)) == hipSuccess;       // (the presence set is kept zero between calls)
-    if (!ok) {
-        fail(nullptr, F3D_ERR_HIP, "context setup failed: %s", hipGetErrorString(hipGetLastError()));
-        f3d_ctx_destroy(ctx);
-        return nullptr;
-    }
-    return ctx;
-}
-
-void f3d_ctx_destroy(f3d_ctx* ctx) {
-    if (!ctx) return;
-    (void)hipSetDevice(ctx->device);
-    if (ctx->stream) (void)hipStreamSynchronize(ctx->stream);
-    for (devbuf& b : ctx->scratch) if (b.p) (void)hipFree(b.p);
-    for (devbuf& b : ctx->stage) if (b.p) (void)hipFree(b.p);
-    for (devbuf& b : ctx->kept) if (b.p) (void)hipFree(b.p);
-    if (ctx->dev_err) (void)hipFree(ctx->dev_err);
-    if (ctx->table) (void)hipFree(ctx->table);
-    if (ctx->filter_dev) (void)hipFree(ctx->filter_dev);
-    if (ctx->count_dev) (void)hipFree(ctx->count_dev);
-    if (ctx->codebook) (void)hipFree(ctx->codebook);
-    if (ctx->first_bad) (void)hipFree(ctx->first_bad);
-    if (ctx->pv_words) (void)hipFree(ctx->pv_words);
-    if (ctx->stream) (void)hipStreamDestroy(ctx->stream);
-    free(ctx);
-}
-
-const char* f3d_last_error(const f3d_ctx* ctx) { return ctx ? ctx->err : g_create_err; }
-
-int f3d_ctx_synchronize(f3d_ctx* ctx) {
-    int rc = enter(ctx); if (rc) return rc;
-    F3D_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    return F3D_OK;
-}
-
-void* f3d_ctx_stream(f3d_ctx* ctx) { return ctx ? (void*)ctx->stream : nullptr; }
-
-int f3d_ctx_reserve(f3d_ctx* ctx, int64_t n, int nviews, int h, int w) {
-    int rc = enter(ctx); if (rc) return rc;
-    if (n < 0 || n > 0x7fffffffLL || nviews < 0 || h < 0 || w < 0) return fail(ctx, F3D_ERR_INVALID, "ctx_reserve: bad arguments");
-    const bool frames = h > 0 && w > 0;
-    return reserve(ctx, {{SLOT_TODO, f3d_fuse_todo_layout(n, nviews, F3D_CODE_MAX_NCLASSES).bytes},           // (any number of classes)
-                         {SLOT_SORT_PERM, (size_t)n * 4, n > 0},
-                         {SLOT_SORT_SCRATCH, f3d_sort_scratch_bytes(n), n > 0},
-                         {SLOT_TILED_MASKS, frames && nviews > 0 ? f3d_coded_masks_bytes(nviews, h, w) : 0, frames && nviews > 0},
-                         {SLOT_FUSE_TABLES, f3d_fuse_tables_bytes(nviews > 0 ? nviews : 1)}},
-                   frames ? (int64_t)h * w : 0);
-}
-
-int f3d_ctx_set_strict(f3d_ctx* ctx, int strict) {
-    if (!ctx) return F3D_ERR_INVALID;
-    ctx->strict = strict ? 1 : 0;
-    return F3D_OK;
-}
-
-long long f3d_ctx_alloc_count(const f3d_ctx* ctx) { return ctx ? ctx->allocs : -1; }
 
 // ---------------------------------------------------------------------------------------------
 // host geometry
@@ -908,11 +515,6 @@ int f3d_debug_fuse_deferred(f3d_ctx* ctx, void* stream, uint32_t counts[2]) {
     return F3D_OK;
 }
 
-int f3d_take_device_error(f3d_ctx* ctx, void* stream) {
-    int rc = enter(ctx); if (rc) return rc;
-    return take_error(ctx, pick(ctx, stream));
-}
-
 int f3d_project_vote_argmax(f3d_ctx* ctx, const void* xyz, f3d_dtype dtype, int64_t n, const f3d_view* views, int nviews,
                             const uint8_t* masks, int h, int w, int nclasses, const int32_t* filter, int nfilter,
                             double threshold, int64_t* classes, uint16_t* votes_u16) {
@@ -936,7 +538,7 @@ int f3d_project_vote_argmax(f3d_ctx* ctx, const void* xyz, f3d_dtype dtype, int6
 // ---------------------------------------------------------------------------------------------
 // a7 vote, a8 segment
 // ---------------------------------------------------------------------------------------------
-static int ensure_table(f3d_ctx* ctx, int64_t hw) {
+int ensure_table(f3d_ctx* ctx, int64_t hw) {
     size_t want = 1024;
     while (want < (size_t)hw * 2) want <<= 1;
     if (ctx->table_slots < want) {
@@ -1811,7 +1413,7 @@ int lift_run(f3d_ctx* ctx, f3d_lift_job& j, int64_t* stats, hipStream_t s) {
         F3D_HIP(ctx, f3d_launch_lift_merge(j, st));
         if (st[6]) {
             if ((rc = take_error(ctx, s, F3D_DEVERR_LIFT))) return rc;
-            return fail(ctx, F3D_ERR_INDEX, "lift: an instance id exceeds max_ids, or a lookup is not below npoints");
+            return fail(ctx, F3D_ERR_INDEX, "%s", device_error_message(F3D_DEVERR_LIFT));
         }
         if (!st[5]) break;
         const uint64_t need = lift_pow2(2 * lift_min64((uint64_t)st[4], lift_pair_bound(nseg)));
@@ -3689,5 +3291,3 @@ int f3d_features_finalize(f3d_ctx* ctx, const float* sums, const int32_t* counts
     if (!st.rc) st.rc = f3d_features_finalize_dev(ctx, drows, dcounts, n, d, normalize, drows, ctx->stream);
     return st.finish();
 }
-
-}  // extern "C"

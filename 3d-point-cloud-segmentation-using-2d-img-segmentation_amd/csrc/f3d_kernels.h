@@ -1,4 +1,4 @@
-// Internal interface between the C-ABI layer (f3d_capi.cpp) and the kernel sources (f3d_*.hip), and the launch helpers they share.
+// Internal interface between the C-ABI layer (f3d_ctx.cpp, f3d_capi.cpp) and the kernel sources (f3d_*.hip), and the launch helpers they share.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <float.h>

@@ -618,7 +618,7 @@ __global__ void k_vote_batch_flag(const int* __restrict__ first_bad, int* __rest
 }  // namespace
 
 // =============================================================================================
-// launchers (called from f3d_capi.cpp)
+// launchers (called from f3d_ctx.cpp and f3d_capi.cpp)
 // =============================================================================================
 
 hipError_t f3d_launch_clear_error_bits(int* err, int bits, hipStream_t s) {

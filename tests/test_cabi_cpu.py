@@ -1,6 +1,8 @@
 """CPU-side checks of the drop-in boundary: the C-ABI library loads and exports every symbol include/f3d.h
 declares, the host-side view geometry equals the oracle, error mapping, and the product never touches oracle/."""
 import re
+import shutil
+import subprocess
 
 import numpy as np
 import pytest
@@ -24,6 +26,30 @@ def test_library_exports_every_declared_symbol():
         assert hasattr(lib, name), f'{name} is declared in include/f3d.h but not exported by libf3d_hip.so'
     assert set(lib._f3d_symbols) == set(declared), set(lib._f3d_symbols) ^ set(declared)
     assert lib.f3d_version() == 100
+
+
+# helpers of the C-ABI layer that once sat in a namespace inside extern "C" and were exported with C linkage
+_ONCE_STRAY = ['lift_first_slots', 'lift_job', 'lift_min64', 'lift_pair_bound', 'lift_pow2', 'lift_run', 'lift_shape_ok',
+               'ranges_overlap',
+               'smooth_args_bad', 'smooth_enqueue', 'smooth_matrices', 'smooth_seg_make', 'smooth_stage', 'smooth_vote_bytes']
+
+
+def test_library_exports_no_stray_c_symbols():
+    """Next to torch, OpenCV and Open3D the library may define f3d_* names and nothing else of its own: every other defined
+    dynamic symbol is mangled C++ or the toolchain's (both start with an underscore)."""
+    lib = f3d.library()
+    nm = shutil.which('nm')
+    if nm:
+        out = subprocess.run([nm, '-D', '--defined-only', str(f3d.library_path())], check=True, capture_output=True, text=True).stdout
+        names = [line.split()[-1] for line in out.splitlines() if line.strip()]
+        assert set(_header_functions()) <= set(names)            # (the listing was read: it has every name of f3d.h)
+        stray = [n for n in names if not n.startswith('_') and not n.startswith('f3d_')]
+        assert not stray, stray
+    else:
+        resolved = [n for n in _ONCE_STRAY if hasattr(lib, n)]
+        assert not resolved, resolved
+    for name in _header_functions():
+        assert hasattr(lib, name), f'{name} is declared in include/f3d.h but not exported by libf3d_hip.so'
 
 
 def test_view_record_layout_matches_header():
