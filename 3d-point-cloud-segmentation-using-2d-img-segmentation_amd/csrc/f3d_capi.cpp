@@ -2971,6 +2971,21 @@ int f3d_debug_tsdf_grid_cap(f3d_ctx* ctx, int blocks) {
     return F3D_OK;
 }
 
+int f3d_debug_grid_cap(f3d_ctx* ctx, int blocks) {
+    int rc = enter(ctx); if (rc) return rc;
+    if (blocks < 0) return fail(ctx, F3D_ERR_INVALID, "debug_grid_cap: blocks must not be negative");
+    f3d_grid_debug_state.blocks.store(blocks, std::memory_order_relaxed);
+    return F3D_OK;
+}
+
+int f3d_debug_grid_cap_stats(f3d_ctx* ctx, int64_t out[2]) {
+    int rc = enter(ctx); if (rc) return rc;
+    if (!out) return fail(ctx, F3D_ERR_INVALID, "debug_grid_cap_stats: out must not be NULL");
+    out[0] = f3d_grid_debug_state.calls.exchange(0, std::memory_order_relaxed);
+    out[1] = f3d_grid_debug_state.lowered.exchange(0, std::memory_order_relaxed);
+    return F3D_OK;
+}
+
 int f3d_tsdf_integrate_dev(f3d_ctx* ctx, float* tsdf, float* weight, int nx, int ny, int nz, const double lo[3], double vs, double trunc,
                            float max_weight, const void* depth, int depth_type, int nframes, int h, int w, double depth_scale,
                            double max_depth, const f3d_view* views_dev, void* stream) {

@@ -46,8 +46,7 @@ hipError_t f3d_launch_components(const int64_t* classes, int64_t n, const int64_
                                  int64_t* root, int* err, hipStream_t s, int errbit) {
     if (n <= 0) return hipSuccess;
     if (n > 0x7fffffffLL) return hipErrorInvalidValue;
-    int64_t gb = (n + CB - 1) / CB;
-    const dim3 g((unsigned)(gb < 16384 ? gb : 16384)), b(CB);
+    const dim3 g((unsigned)f3d_grid_for(n, CB, 16384)), b(CB);
     hipLaunchKernelGGL(k_cc_init, g, b, 0, s, parent, n);
     hipLaunchKernelGGL(k_cc_hook, g, b, 0, s, classes, n, offs, nbrs, parent, err, errbit);
     hipLaunchKernelGGL(k_cc_compress, g, b, 0, s, parent, n, root);

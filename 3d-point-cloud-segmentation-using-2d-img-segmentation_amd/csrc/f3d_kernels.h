@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <float.h>
 #include <stdint.h>
+#include <atomic>
 #include "f3d.h"
 #include "f3d_math.h"
 
@@ -29,11 +30,24 @@
 #define F3D_BLOCK 256                       // threads per block of the f3d_kernels.hip / f3d_fuse.hip kernels
 #define F3D_GRID_CAP (256 * 8 * 4)          // their usual grid cap: 256 CUs x 8 blocks, x4 so that tails stay short
 
-// blocks of a grid-stride launch over n items, per_block items per block: ceil(n / per_block) clamped to [1, cap]
+// f3d_debug_grid_cap (test hook), one per process: blocks > 0 is a further upper bound of every f3d_grid_for, 0 = off.  calls counts the
+// f3d_grid_for calls made while it is on, lowered those whose grid it made smaller.  Relaxed atomics: launchers run on any host thread.
+struct f3d_grid_debug { std::atomic<int> blocks{0}; std::atomic<long long> calls{0}, lowered{0}; };
+inline f3d_grid_debug f3d_grid_debug_state;
+inline int f3d_grid_debug_cap() { return f3d_grid_debug_state.blocks.load(std::memory_order_relaxed); }
+
+// blocks of a grid-stride launch over n items, per_block items per block: ceil(n / per_block) clamped to [1, cap].  Every kernel launched
+// with this grid walks its items with a gridDim.x stride, so no result depends on the value: the debug cap may lower it further (never
+// below 1, never above what it would have been) to drive a small input through many passes per block.
 inline int f3d_grid_for(int64_t n, int per_block, int cap) {
     int64_t g = (n + per_block - 1) / per_block;
     if (g < 1) g = 1;
     if (g > cap) g = cap;
+    const int dbg = f3d_grid_debug_cap();
+    if (dbg > 0) {
+        f3d_grid_debug_state.calls.fetch_add(1, std::memory_order_relaxed);
+        if (g > dbg) { g = dbg; f3d_grid_debug_state.lowered.fetch_add(1, std::memory_order_relaxed); }
+    }
     return (int)g;
 }
 

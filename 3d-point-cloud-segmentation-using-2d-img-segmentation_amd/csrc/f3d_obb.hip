@@ -91,10 +91,10 @@ __global__ __launch_bounds__(OB) void k_obb_extremes(const T* __restrict__ xyz, 
 // extremes[seg][dir] = caller-order index of the extreme member, -1 for an empty segment
 __global__ __launch_bounds__(OB) void k_obb_extremes_out(const unsigned long long* __restrict__ table, const int32_t* __restrict__ order,
                                                           int64_t count, int32_t* __restrict__ extremes) {
-    const int64_t k = (int64_t)blockIdx.x * OB + threadIdx.x;
-    if (k >= count) return;
-    const unsigned long long t = table[k];
-    extremes[k] = t ? order[(uint32_t)t] : -1;
+    for (int64_t k = (int64_t)blockIdx.x * OB + threadIdx.x; k < count; k += (int64_t)gridDim.x * OB) {
+        const unsigned long long t = table[k];
+        extremes[k] = t ? order[(uint32_t)t] : -1;
+    }
 }
 
 // A member survives unless it lies strictly inside its segment's polytope: n_f . p + o_f < -margin[seg] for every facet f of
@@ -201,9 +201,8 @@ __global__ __launch_bounds__(OB) void k_obb_compact(int64_t n, const int32_t* __
 __global__ __launch_bounds__(OB) void k_obb_cand_starts(int64_t n, const int64_t* __restrict__ starts, int64_t nseg, const unsigned long long* __restrict__ maskw,
                                                          const uint32_t* __restrict__ wordoff, const uint32_t* __restrict__ blockoff,
                                                          const int64_t* __restrict__ total, int64_t* __restrict__ cand_start) {
-    const int64_t k = (int64_t)blockIdx.x * OB + threadIdx.x;
-    if (k > nseg) return;
-    cand_start[k] = survivors_before(starts[k], n, maskw, wordoff, blockoff, *total);     // starts[nseg] = first position of the out-of-range bucket
+    for (int64_t k = (int64_t)blockIdx.x * OB + threadIdx.x; k <= nseg; k += (int64_t)gridDim.x * OB)
+        cand_start[k] = survivors_before(starts[k], n, maskw, wordoff, blockoff, *total);     // starts[nseg] = first position of the out-of-range bucket
 }
 
 template <typename T>

@@ -110,16 +110,16 @@ __global__ __launch_bounds__(QB) void k_quad_tri_setup(const double* __restrict_
 // rank of every wanted id in (id, position) order: sorted_ids / sorted_slot for the binary search of k_quad_slot_keys
 __global__ __launch_bounds__(QB) void k_quad_rank_ids(const int64_t* __restrict__ inst, int k, int64_t* __restrict__ sorted_ids,
                                                       int32_t* __restrict__ sorted_slot) {
-    const int e = blockIdx.x * QB + threadIdx.x;
-    if (e >= k) return;
-    const int64_t id = inst[e];
-    int r = 0;
-    for (int f = 0; f < k; ++f) {
-        const int64_t g = inst[f];
-        r += (g < id) | ((g == id) & (f < e));
+    for (int64_t e = (int64_t)blockIdx.x * QB + threadIdx.x; e < k; e += (int64_t)gridDim.x * QB) {
+        const int64_t id = inst[e];
+        int r = 0;
+        for (int f = 0; f < k; ++f) {
+            const int64_t g = inst[f];
+            r += (g < id) | ((g == id) & (f < e));
+        }
+        sorted_ids[r] = id;
+        sorted_slot[r] = (int32_t)e;
     }
-    sorted_ids[r] = id;
-    sorted_slot[r] = e;
 }
 
 // keys[i] = slot of ids[i] among the wanted ids (the first slot of a repeated id), k if none
@@ -235,34 +235,34 @@ __global__ __launch_bounds__(QB) void k_quad_choose(const double* __restrict__ p
                                                     const int32_t* __restrict__ cand, const int32_t* __restrict__ ncand,
                                                     const int32_t* __restrict__ counts, inst_rec* __restrict__ irec,
                                                     unsigned long long* __restrict__ ext) {
-    const int s = blockIdx.x * QB + threadIdx.x;
-    if (s >= k) return;
-    ext[4 * s] = ~0ull; ext[4 * s + 1] = 0ull; ext[4 * s + 2] = ~0ull; ext[4 * s + 3] = 0ull;
-    inst_rec o;
-    for (int c = 0; c < 3; ++c) o.origin[c] = o.i[c] = o.j[c] = NAN;
-    const int nc = ncand[s];
-    if (nc == 0) { o.tri = -1; o.status = F3D_QUAD_NO_CANDIDATE; irec[s] = o; return; }
-    const int64_t row = (int64_t)s * nt;
-    int best = counts[row], bc = 0;
-    for (int c = 1; c < nc; ++c) if (counts[row + c] > best) { best = counts[row + c]; bc = c; }
-    o.tri = cand[row + bc];
-    const tri_rec r = rec[o.tri];
-    if (COS10 < r.n[2]) { o.status = F3D_QUAD_HORIZONTAL; irec[s] = o; return; }
-    const double len = sqrt(blas_dot(r.n[0], r.n[1], r.n[2], r.n[0], r.n[1], r.n[2]));
-    const double a0 = r.n[0] / len, a1 = r.n[1] / len, a2 = r.n[2] / len;
-    double b0 = 0.0, b1 = 0.0, b2 = 1.0;                                 // arbitrary = [0, 0, 1]
-    if (fabs(fabs(blas_dot(a0, a1, a2, b0, b1, b2)) - 1.0) <= ALLCLOSE_TOL) { b1 = 1.0; b2 = 0.0; }
-    const double c0 = a1 * b2 - a2 * b1, c1 = a2 * b0 - a0 * b2, c2 = a0 * b1 - a1 * b0;       // np.cross(normal, arbitrary)
-    const double e0 = a1 * c2 - a2 * c1, e1 = a2 * c0 - a0 * c2, e2 = a0 * c1 - a1 * c0;       // np.cross(normal, vector1)
-    const double l1 = sqrt(blas_dot(c0, c1, c2, c0, c1, c2)), l2 = sqrt(blas_dot(e0, e1, e2, e0, e1, e2));
-    o.i[0] = c0 / l1; o.i[1] = c1 / l1; o.i[2] = c2 / l1;
-    o.j[0] = e0 / l2; o.j[1] = e1 / l2; o.j[2] = e2 / l2;
-    double x, y, z;
-    load_pt(pts, order[starts[s]], x, y, z);                             // nc > 0: the instance has members
-    const double perp = perp_of(x, y, z, r);
-    o.origin[0] = x - r.n[0] * perp; o.origin[1] = y - r.n[1] * perp; o.origin[2] = z - r.n[2] * perp;
-    o.status = F3D_QUAD_OK;
-    irec[s] = o;
+    for (int64_t s = (int64_t)blockIdx.x * QB + threadIdx.x; s < k; s += (int64_t)gridDim.x * QB) {
+        ext[4 * s] = ~0ull; ext[4 * s + 1] = 0ull; ext[4 * s + 2] = ~0ull; ext[4 * s + 3] = 0ull;
+        inst_rec o;
+        for (int c = 0; c < 3; ++c) o.origin[c] = o.i[c] = o.j[c] = NAN;
+        const int nc = ncand[s];
+        if (nc == 0) { o.tri = -1; o.status = F3D_QUAD_NO_CANDIDATE; irec[s] = o; continue; }
+        const int64_t row = (int64_t)s * nt;
+        int best = counts[row], bc = 0;
+        for (int c = 1; c < nc; ++c) if (counts[row + c] > best) { best = counts[row + c]; bc = c; }
+        o.tri = cand[row + bc];
+        const tri_rec r = rec[o.tri];
+        if (COS10 < r.n[2]) { o.status = F3D_QUAD_HORIZONTAL; irec[s] = o; continue; }
+        const double len = sqrt(blas_dot(r.n[0], r.n[1], r.n[2], r.n[0], r.n[1], r.n[2]));
+        const double a0 = r.n[0] / len, a1 = r.n[1] / len, a2 = r.n[2] / len;
+        double b0 = 0.0, b1 = 0.0, b2 = 1.0;                                 // arbitrary = [0, 0, 1]
+        if (fabs(fabs(blas_dot(a0, a1, a2, b0, b1, b2)) - 1.0) <= ALLCLOSE_TOL) { b1 = 1.0; b2 = 0.0; }
+        const double c0 = a1 * b2 - a2 * b1, c1 = a2 * b0 - a0 * b2, c2 = a0 * b1 - a1 * b0;       // np.cross(normal, arbitrary)
+        const double e0 = a1 * c2 - a2 * c1, e1 = a2 * c0 - a0 * c2, e2 = a0 * c1 - a1 * c0;       // np.cross(normal, vector1)
+        const double l1 = sqrt(blas_dot(c0, c1, c2, c0, c1, c2)), l2 = sqrt(blas_dot(e0, e1, e2, e0, e1, e2));
+        o.i[0] = c0 / l1; o.i[1] = c1 / l1; o.i[2] = c2 / l1;
+        o.j[0] = e0 / l2; o.j[1] = e1 / l2; o.j[2] = e2 / l2;
+        double x, y, z;
+        load_pt(pts, order[starts[s]], x, y, z);                             // nc > 0: the instance has members
+        const double perp = perp_of(x, y, z, r);
+        o.origin[0] = x - r.n[0] * perp; o.origin[1] = y - r.n[1] * perp; o.origin[2] = z - r.n[2] * perp;
+        o.status = F3D_QUAD_OK;
+        irec[s] = o;
+    }
 }
 
 __device__ __forceinline__ void wave_minmax(unsigned long long& mn, unsigned long long& mx) {
@@ -318,18 +318,18 @@ __global__ __launch_bounds__(QB) void k_quad_extents(const double* __restrict__ 
 // bbox = [origin + xmin*i + ymax*j, origin + xmin*i + ymin*j, origin + xmax*i + ymin*j, origin + xmax*i + ymax*j] (:126-131)
 __global__ __launch_bounds__(QB) void k_quad_build(const inst_rec* __restrict__ irec, const unsigned long long* __restrict__ ext, int k,
                                                    double* __restrict__ quads, int32_t* __restrict__ status, int32_t* __restrict__ tri) {
-    const int s = blockIdx.x * QB + threadIdx.x;
-    if (s >= k) return;
-    const inst_rec o = irec[s];
-    status[s] = o.status;
-    tri[s] = o.tri;
-    const bool ok = o.status == F3D_QUAD_OK;
-    const double xmin = f3d_ord_dec(ext[4 * s]), xmax = f3d_ord_dec(ext[4 * s + 1]);
-    const double ymin = f3d_ord_dec(ext[4 * s + 2]), ymax = f3d_ord_dec(ext[4 * s + 3]);
-    const double cx[4] = {xmin, xmin, xmax, xmax}, cy[4] = {ymax, ymin, ymin, ymax};
-    for (int q = 0; q < 4; ++q)
-        for (int c = 0; c < 3; ++c)
-            quads[12 * (int64_t)s + 3 * q + c] = ok ? (o.origin[c] + cx[q] * o.i[c]) + cy[q] * o.j[c] : NAN;
+    for (int64_t s = (int64_t)blockIdx.x * QB + threadIdx.x; s < k; s += (int64_t)gridDim.x * QB) {
+        const inst_rec o = irec[s];
+        status[s] = o.status;
+        tri[s] = o.tri;
+        const bool ok = o.status == F3D_QUAD_OK;
+        const double xmin = f3d_ord_dec(ext[4 * s]), xmax = f3d_ord_dec(ext[4 * s + 1]);
+        const double ymin = f3d_ord_dec(ext[4 * s + 2]), ymax = f3d_ord_dec(ext[4 * s + 3]);
+        const double cx[4] = {xmin, xmin, xmax, xmax}, cy[4] = {ymax, ymin, ymin, ymax};
+        for (int q = 0; q < 4; ++q)
+            for (int c = 0; c < 3; ++c)
+                quads[12 * (int64_t)s + 3 * q + c] = ok ? (o.origin[c] + cx[q] * o.i[c]) + cy[q] * o.j[c] : NAN;
+    }
 }
 
 struct quad_layout { size_t keys, order, skeys, starts, group, rec, dist, cand, counts, ncand, sids, sslot, irec, ext, total; };

@@ -297,10 +297,11 @@ void scan_in_place(uint32_t* v, int64_t n, uint32_t* sums, hipStream_t s) {
     hipLaunchKernelGGL(k_tsdf_scan, dim3((unsigned)ntiles), dim3(F3D_BLOCK), 0, s, v, n, sums, 1);
 }
 
-// blocks of a launch: the usual cap, or the smaller one a test set (f3d_debug_tsdf_grid_cap; 0 = none)
+// blocks of a launch: the usual cap, or the smaller one a test set (f3d_debug_tsdf_grid_cap; 0 = none); f3d_grid_for then applies the
+// process-wide f3d_debug_grid_cap as well, so the smaller of the two holds
 int capped(int64_t blocks, int64_t usual, int grid_cap) {
     const int64_t cap = grid_cap > 0 && grid_cap < usual ? grid_cap : usual;
-    return (int)(blocks < 1 ? 1 : blocks < cap ? blocks : cap);
+    return f3d_grid_for(blocks, 1, (int)cap);
 }
 
 tsdf_grid grid_of(int nx, int ny, int nz, const double lo[3], double vs) {

@@ -243,6 +243,8 @@ def library():
         'f3d_tsdf_extract_fill_dev': (i32, [vp, vp, i32, i32, i32, vp, dbl, vp, vp, vp]),
         'f3d_ctx_reserve_tsdf': (i32, [vp, i64]),
         'f3d_debug_tsdf_grid_cap': (i32, [vp, i32]),
+        'f3d_debug_grid_cap': (i32, [vp, i32]),
+        'f3d_debug_grid_cap_stats': (i32, [vp, vp]),
         'f3d_fuse_features': (i32, [vp, vp, i32, i64, vp, i32, i32, i32, vp, i32, i32, i32, i32, i32, dbl, vp, vp, i32]),
         'f3d_fuse_features_dev': (i32, [vp, vp, i32, i64, vp, i32, i32, i32, vp, i32, i32, i32, i32, i32, dbl, vp, vp, i32, vp]),
         'f3d_features_finalize': (i32, [vp, vp, vp, i64, i32, i32, vp]),
@@ -1224,6 +1226,19 @@ class Context:
     def debug_tsdf_grid_cap(self, blocks):
         """Test hook: at most `blocks` blocks per grid-stride TSDF launch of this context (0 = the library's launch shapes)."""
         self._check(self._lib.f3d_debug_tsdf_grid_cap(self._h, int(blocks)))
+
+    def debug_grid_cap(self, blocks):
+        """Test hook: at most `blocks` blocks per grid-stride launch of the library (0 = the library's launch shapes), so that a small
+        input takes many passes per block.  The state is per PROCESS, not per context: it holds for every context until it is set
+        back to 0.  No result depends on it."""
+        self._check(self._lib.f3d_debug_grid_cap(self._h, int(blocks)))
+
+    def debug_grid_cap_stats(self):
+        """Test hook: (grids sized while debug_grid_cap was on, grids it made smaller) since the last call; reading resets both.  The
+        counters are per PROCESS, not per context.  No result depends on them."""
+        out = np.zeros(2, np.int64)
+        self._check(self._lib.f3d_debug_grid_cap_stats(self._h, _ptr(out)))
+        return int(out[0]), int(out[1])
 
     def tsdf_integrate(self, tsdf, weight, lo, voxel, trunc, max_weight, depths, views, depth_scale=1.0, max_depth=10.0):
         """Integrate depth frames [F, h, w] (uint16, float32 or float64) into the volume IN PLACE (f3d.h f3d_tsdf_integrate): tsdf and

@@ -1196,7 +1196,11 @@ int f3d_estimate_normals_batch_dev(f3d_ctx* ctx, const double* xyz, int nframes,
  * Scratch: 11 bytes per voxel + 4 per scan tile; f3d_ctx_reserve_tsdf(nvoxels) sizes it, and a strict context then allocates nothing in
  * the three _dev entries.  Reserving may move the scratch, so it ends a counted sequence: count again before the fill.
  * f3d_debug_tsdf_grid_cap (test hook): blocks > 0 caps the grid of every grid-stride TSDF launch of the context at that many blocks, so that
- * a small volume takes many passes per block; 0 = the library's launch shapes.  No result depends on it. */
+ * a small volume takes many passes per block; 0 = the library's launch shapes.  No result depends on it.
+ * f3d_debug_grid_cap (test hook): the same for every other grid-stride launch of the library, and for the TSDF and raycast launches as
+ * well (they take the smaller of the two caps).  The state belongs to the PROCESS, not to ctx: it holds for every context and every
+ * thread until it is set back to 0.  It only ever lowers a grid, never below one block.  f3d_debug_grid_cap_stats reads and resets two
+ * process-wide counters: out[0] = grids sized while the cap was on, out[1] = those the cap made smaller.  No result depends on either. */
 #define F3D_TSDF_SCAN_TILE 2048
 #define F3D_TSDF_MAX_WEIGHT 16777216.0f
 int f3d_tsdf_integrate(f3d_ctx* ctx, float* tsdf, float* weight, int nx, int ny, int nz, const double lo[3], double vs, double trunc,
@@ -1215,6 +1219,8 @@ int f3d_tsdf_extract_fill_dev(f3d_ctx* ctx, const float* tsdf, int nx, int ny, i
                               double* verts, int32_t* tris, void* stream);
 int f3d_ctx_reserve_tsdf(f3d_ctx* ctx, int64_t nvoxels);
 int f3d_debug_tsdf_grid_cap(f3d_ctx* ctx, int blocks);
+int f3d_debug_grid_cap(f3d_ctx* ctx, int blocks);
+int f3d_debug_grid_cap_stats(f3d_ctx* ctx, int64_t out[2]);
 
 /* ---- feature fusion: per-point pooling of per-pixel feature maps over views (no reference counterpart) -------------------- */
 /* Every other 2D -> 3D entry moves one byte per pixel (a class or an instance id).  These move a vector: the [C] logits or

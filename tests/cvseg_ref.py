@@ -185,3 +185,17 @@ def same_boundary(got, want):
     if want.dtype == object:
         return all((a is None and b is None) or (a is not None and b is not None and bool(a) == bool(b)) for a, b in zip(got, want))
     return got.dtype == want.dtype and np.array_equal(got, want)
+
+
+def same_instances(got, want):
+    """instance_seperate's result against (n, ids, info, clusters, boundaries) of the reference or the restatement: everything exactly, the
+    clusters in flood (pop) order, the boundaries as sets (same_boundary)."""
+    n, ids, info, clusters, bnds = want
+    assert len(got[0]) == n and np.array_equal(got[0], np.arange(n))
+    assert got[1].dtype == ids.dtype and np.array_equal(got[1], ids)
+    assert got[2] == info
+    assert len(got[3]) == len(clusters) and len(got[4]) == len(bnds)
+    for a, b in zip(got[3], clusters):
+        assert a.dtype == b.dtype and np.array_equal(a, b)          # flood (pop) order
+    for k in range(len(bnds)):
+        assert same_boundary(got[4][k], bnds[k]), k

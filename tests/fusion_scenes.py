@@ -4,7 +4,9 @@
 operations that round the same on every host are used (+, -, *, /, sqrt, and the uniform draws of ``np.random.default_rng``), so
 the frames regenerate bit for bit wherever the tests run: tests/golden/fuse_curved.npz stores a digest of them instead of the frames.
 """
+import contextlib
 import hashlib
+import warnings
 
 import numpy as np
 
@@ -155,3 +157,59 @@ def capture_digest(K, wxyz, translations, frames):
 
 def copy_frames(frames):
     return [(n, p.copy(), q.copy(), c.copy(), v.copy()) for n, p, q, c, v in frames]
+
+
+# ---- one sequence through the oracle or the library, and the comparison of two such runs (tests/test_fusion_device_gpu.py and others)
+def _bits(a):
+    a = np.ascontiguousarray(a)
+    return a.view(np.uint64) if a.dtype == np.float64 else a
+
+
+def same_bits(a, b):
+    return a.dtype == b.dtype and a.shape == b.shape and np.array_equal(_bits(a), _bits(b))
+
+
+@contextlib.contextmanager
+def _quiet():
+    with warnings.catch_warnings(), np.errstate(all='ignore'):
+        warnings.simplefilter('ignore', RuntimeWarning)              # means of empty sets (zero normal / NaN point), as the reference
+        yield
+
+
+def run_fuse(K, w, h, q, t, frames, params, seed, how, lookup_dir=None):
+    """`frames` through O.fuse ('oracle'), fuse ('host') or fuse_device ('device'), used as given (fuse and the oracle consume
+    their masks) -> (five outputs as NumPy, [(name, lookup)] in the order they were handed out, the generator's next draw, the
+    Fusion object)."""
+    from oracle import np_ref as O
+    lookups = []
+    if how == 'oracle':
+        np.random.seed(seed)
+        with _quiet():
+            *out, lookups = O.fuse(K, w, h, q, t, frames, *params)
+        return out, lookups, np.random.random(), None
+
+    def sink(name, lut):
+        if how == 'device':
+            assert lut.is_cuda and lut.dtype.is_signed and lut.element_size() == 4 and tuple(lut.shape) == (h * w,)
+        else:
+            assert isinstance(lut, np.ndarray) and lut.dtype == np.int32 and lut.shape == (h * w,)
+        lookups.append((name, lut.clone() if how == 'device' else lut.copy()))
+    from Fusion3DSeg.fusion import Fusion
+    fu = Fusion.from_frames(K, w, h, q, t, frames, lookup_dir=lookup_dir, lookup_sink=sink)
+    np.random.seed(seed)
+    out = fu.fuse_device(*params) if how == 'device' else fu.fuse(*params)
+    after = np.random.random()
+    if how == 'device':
+        out = [o.cpu().numpy() for o in out]
+        lookups = [(n, lut.cpu().numpy()) for n, lut in lookups]
+    return list(out), lookups, after, fu
+
+
+def assert_same_fuse(got, want):
+    (go, gl, ga, _), (wo, wl, wa, _) = got, want
+    for k, (a, b) in enumerate(zip(go, wo)):
+        assert same_bits(a, b), (k, a.dtype, b.dtype, a.shape, b.shape)
+    assert [n for n, _ in gl] == [n for n, _ in wl]
+    for (name, a), (_, b) in zip(gl, wl):
+        assert same_bits(a, b), name
+    assert ga == wa

@@ -156,3 +156,15 @@ def threshold_pair(overlap):
     b = list(range(8 - overlap, 20 - overlap))
     luts, inst = frames_from_sets(b[-1] + 1, [{1: a}, {1: b}])
     return b[-1] + 1, luts, inst
+
+
+def random_scene(seed, n, nf, hw, k, hit=0.6, skew=3.0, no_id=0.1):
+    """Lookups hit `hit` of the pixels; the hits crowd towards the low point indices (u^skew), so that points are seen many times,
+    also several times within a frame and with different ids; `no_id` of the pixels carry id 0."""
+    rng = np.random.default_rng(seed)
+    luts = np.floor(n * rng.random((nf, hw)) ** skew).astype(np.int32)
+    luts[rng.random((nf, hw)) >= hit] = -1
+    luts[rng.random((nf, hw)) < 0.01] = -7                          # any negative value means none
+    inst = rng.integers(1, k + 1, (nf, hw)).astype(np.uint16)
+    inst[rng.random((nf, hw)) < no_id] = 0
+    return luts, inst

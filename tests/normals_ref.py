@@ -85,3 +85,26 @@ def orient_dots(points, raw_normals, cam_centre):
 
 def surface_normal_estimation(points, cam_centre, radius=0.05, max_nn=30):
     return orient(points, normals(points, radius, max_nn)[0], cam_centre)
+
+
+def bits(a):
+    return np.ascontiguousarray(a).view(np.uint64)
+
+
+def angle(a, b):
+    return np.arctan2(np.linalg.norm(np.cross(a, b), axis=1), np.abs(np.einsum('ij,ij->i', a, b)))
+
+
+def check_against_oracle(pts, radius, max_nn, got):
+    """The check of estimate_normals' unoriented output `got` (tests/test_normals_gpu.py, tests/test_launch_shape_gpu.py): degenerate rows
+    are (0, 0, 1) bit for bit, rows with a clear eigen-gap lie within 1e-6 rad of the oracle's normal, every row has unit length.
+    -> (rows excluded for a small gap, rows compared, degenerate rows)."""
+    want, gap, degenerate, nb = normals(pts, radius, max_nn)
+    scale = np.array([np.mean(np.einsum('ij,ij->i', pts[k], pts[k])) if len(k) else 0.0 for k in nb])
+    ok = ~degenerate & (gap >= 1e-8 * scale)
+    excluded = int((~degenerate & ~ok).sum())
+    assert np.array_equal(bits(got[degenerate]), bits(np.tile([0.0, 0.0, 1.0], (int(degenerate.sum()), 1))))
+    ang = angle(got[ok], want[ok])
+    assert ang.max(initial=0.0) <= 1e-6, ang.max()
+    assert np.abs(np.linalg.norm(got, axis=1) - 1.0).max() <= 1e-14
+    return excluded, int(ok.sum()), int(degenerate.sum())

@@ -16,18 +16,6 @@ def _graph(g, gi):
     return g[f'g{gi}_classes'], [nb[offs[i]:offs[i + 1]] for i in range(len(offs) - 1)], (offs, nb)
 
 
-def _same_instances(got, want):
-    n, ids, info, clusters, bnds = want
-    assert len(got[0]) == n and np.array_equal(got[0], np.arange(n))
-    assert got[1].dtype == ids.dtype and np.array_equal(got[1], ids)
-    assert got[2] == info
-    assert len(got[3]) == len(clusters) and len(got[4]) == len(bnds)
-    for a, b in zip(got[3], clusters):
-        assert a.dtype == b.dtype and np.array_equal(a, b)          # flood (pop) order
-    for k in range(len(bnds)):
-        assert R.same_boundary(got[4][k], bnds[k]), k
-
-
 def test_instance_seperate_matches_reference_golden(golden):
     from Fusion3DSeg.segUtils.cv import CVSegmentation
     g = golden('cvseg')
@@ -38,7 +26,7 @@ def test_instance_seperate_matches_reference_golden(golden):
             mine = cls.copy()
             seg = CVSegmentation(mine, adj)
             got = seg.instance_seperate(ic, int(g[f'i{k}_minimum_points']))
-            _same_instances(got, R.decode_instances(g, f'i{k}_'))
+            R.same_instances(got, R.decode_instances(g, f'i{k}_'))
             assert np.array_equal(mine, g[f'i{k}_classes_after']), k         # the caller's classes, rewritten in place
             assert seg.floods and all(f.stats['levels'] >= 1 for f in seg.floods)
 
@@ -85,7 +73,7 @@ def test_large_scene_matches_restatement():
         seg = CVSegmentation(mine, (offs, nb))
         got = seg.instance_seperate(ic, mp)
         assert np.array_equal(mine, want_cls)
-        _same_instances(got, (len(want[0]), want[1], want[2], want[3], list(want[4])))
+        R.same_instances(got, (len(want[0]), want[1], want[2], want[3], list(want[4])))
         assert len(got[3]) > 10
         print(f'{len(cls)} points, {len(got[3])} clusters, floods {[f.stats for f in seg.floods]}')
     ids = got[1].copy()
@@ -184,7 +172,7 @@ def test_interleaved_with_components_and_split_into_instances(golden):
     for k in range(int(g['nicases'])):
         c2, rows2, _ = _graph(g, int(g[f'i{k}_graph']))
         ic = g[f'i{k}_instance_classes'].tolist() if g[f'i{k}_has_instance_classes'] else None
-        _same_instances(CVSegmentation(c2.copy(), rows2).instance_seperate(ic, int(g[f'i{k}_minimum_points'])),
+        R.same_instances(CVSegmentation(c2.copy(), rows2).instance_seperate(ic, int(g[f'i{k}_minimum_points'])),
                         R.decode_instances(g, f'i{k}_'))
         assert np.array_equal(ctx.components_same_class(cls, offs, nb), root0)
         s = split_into_instances(sp['classes'], sadj, 133, [86, 114, 115], 5)

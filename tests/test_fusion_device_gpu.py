@@ -2,9 +2,6 @@
 O.fuse bit for bit -- cloud, lookups in order, the state of the global NumPy generator and, for fuse, the consumed masks -- on the
 reference golden and on synthetic sequences that walk every quirk of the reference's loop.  The oracle is pinned to the reference's
 own runs by tests/test_fusion_oracle_cpu.py."""
-import contextlib
-import warnings
-
 import numpy as np
 import pytest
 
@@ -12,66 +9,9 @@ import f3d
 from f3d import synth
 from Fusion3DSeg import fusion
 from Fusion3DSeg.fusion import Fusion
-from oracle import np_ref as O
+from fusion_scenes import assert_same_fuse as _assert_same, copy_frames as _copy, run_fuse as _run
 
 pytestmark = pytest.mark.gpu
-
-
-def _bits(a):
-    a = np.ascontiguousarray(a)
-    return a.view(np.uint64) if a.dtype == np.float64 else a
-
-
-def _same(a, b):
-    return a.dtype == b.dtype and a.shape == b.shape and np.array_equal(_bits(a), _bits(b))
-
-
-def _copy(frames):
-    return [(n, p.copy(), q.copy(), c.copy(), v.copy()) for n, p, q, c, v in frames]
-
-
-@contextlib.contextmanager
-def _quiet():
-    with warnings.catch_warnings(), np.errstate(all='ignore'):
-        warnings.simplefilter('ignore', RuntimeWarning)              # means of empty sets (zero normal / NaN point), as the reference
-        yield
-
-
-def _run(K, w, h, q, t, frames, params, seed, how, lookup_dir=None):
-    """`frames` through O.fuse ('oracle'), fuse ('host') or fuse_device ('device'), used as given (fuse and the oracle consume
-    their masks) -> (five outputs as NumPy, [(name, lookup)] in the order they were handed out, the generator's next draw, the
-    Fusion object)."""
-    lookups = []
-    if how == 'oracle':
-        np.random.seed(seed)
-        with _quiet():
-            *out, lookups = O.fuse(K, w, h, q, t, frames, *params)
-        return out, lookups, np.random.random(), None
-
-    def sink(name, lut):
-        if how == 'device':
-            assert lut.is_cuda and lut.dtype.is_signed and lut.element_size() == 4 and tuple(lut.shape) == (h * w,)
-        else:
-            assert isinstance(lut, np.ndarray) and lut.dtype == np.int32 and lut.shape == (h * w,)
-        lookups.append((name, lut.clone() if how == 'device' else lut.copy()))
-    fu = Fusion.from_frames(K, w, h, q, t, frames, lookup_dir=lookup_dir, lookup_sink=sink)
-    np.random.seed(seed)
-    out = fu.fuse_device(*params) if how == 'device' else fu.fuse(*params)
-    after = np.random.random()
-    if how == 'device':
-        out = [o.cpu().numpy() for o in out]
-        lookups = [(n, lut.cpu().numpy()) for n, lut in lookups]
-    return list(out), lookups, after, fu
-
-
-def _assert_same(got, want):
-    (go, gl, ga, _), (wo, wl, wa, _) = got, want
-    for k, (a, b) in enumerate(zip(go, wo)):
-        assert _same(a, b), (k, a.dtype, b.dtype, a.shape, b.shape)
-    assert [n for n, _ in gl] == [n for n, _ in wl]
-    for (name, a), (_, b) in zip(gl, wl):
-        assert _same(a, b), name
-    assert ga == wa
 
 
 def _assert_masks(got, want):

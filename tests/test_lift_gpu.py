@@ -44,31 +44,19 @@ def _check(luts, inst, n, k, **kw):
     return want
 
 
-def random_scene(seed, n, nf, hw, k, hit=0.6, skew=3.0, no_id=0.1):
-    """Lookups hit `hit` of the pixels; the hits crowd towards the low point indices (u^skew), so that points are seen many times,
-    also several times within a frame and with different ids; `no_id` of the pixels carry id 0."""
-    rng = np.random.default_rng(seed)
-    luts = np.floor(n * rng.random((nf, hw)) ** skew).astype(np.int32)
-    luts[rng.random((nf, hw)) >= hit] = -1
-    luts[rng.random((nf, hw)) < 0.01] = -7                          # any negative value means none
-    inst = rng.integers(1, k + 1, (nf, hw)).astype(np.uint16)
-    inst[rng.random((nf, hw)) < no_id] = 0
-    return luts, inst
-
-
 @functools.lru_cache(maxsize=None)
 def scene(name):
     """-> (luts, inst, npoints, max_ids), read-only."""
     if name == 'A':
-        out = (*random_scene(1, 20000, 32, 48 * 64, 64, skew=2.0), 20000, 64)
+        out = (*R.random_scene(1, 20000, 32, 48 * 64, 64, skew=2.0), 20000, 64)
     elif name == 'B':                                               # one id per frame
-        out = (*random_scene(2, 3000, 24, 40 * 30, 1), 3000, 1)
+        out = (*R.random_scene(2, 3000, 24, 40 * 30, 1), 3000, 1)
     elif name == 'C':                                               # ids up to 300: past uint8
-        out = (*random_scene(3, 4000, 6, 64 * 48, 300, skew=2.0), 4000, 300)
+        out = (*R.random_scene(3, 4000, 6, 64 * 48, 300, skew=2.0), 4000, 300)
     elif name == 'D':                                               # 5 x 333 pixels: no multiple of a block, frame boundaries inside blocks
-        out = (*random_scene(4, 500, 5, 333, 7), 500, 7)
+        out = (*R.random_scene(4, 500, 5, 333, 7), 500, 7)
     elif name == 'E':                                               # 7 x 100: three frames share the first block
-        out = (*random_scene(5, 90, 7, 100, 3, skew=1.0), 90, 3)
+        out = (*R.random_scene(5, 90, 7, 100, 3, skew=1.0), 90, 3)
     for a in out[:2]:
         a.setflags(write=False)
     return out

@@ -16,14 +16,6 @@ H, W = 96, 128
 KD = np.array([[105.0, 0.0, 64.0], [0.0, 105.0, 48.0], [0.0, 0.0, 1.0]])     # 256x192 at f = 210, halved
 
 
-def _bits(a):
-    return np.ascontiguousarray(a).view(np.uint64)
-
-
-def _angle(a, b):
-    return np.arctan2(np.linalg.norm(np.cross(a, b), axis=1), np.abs(np.einsum('ij,ij->i', a, b)))
-
-
 def _depth(F, dropout=0.0, seed=0, floor_at=1.2):
     """uint16 millimetres: a wall at 2.5 m, a floor `floor_at` m below the camera (at 0.8 m it meets the wall in view, at row 82),
     a box in front; optional zero-depth pixels."""
@@ -78,19 +70,7 @@ def test_selection_is_exact(max_nn):
     assert (counts < 3).any() and (counts == max_nn).any()
     wn, gap, degenerate, _ = R.normals(pts, 0.5, max_nn)
     assert degenerate.any()
-    assert np.array_equal(_bits(nrm[degenerate]), _bits(np.tile([0.0, 0.0, 1.0], (int(degenerate.sum()), 1))))
-
-
-def _check_against_oracle(pts, radius, max_nn, got):
-    want, gap, degenerate, nb = R.normals(pts, radius, max_nn)
-    scale = np.array([np.mean(np.einsum('ij,ij->i', pts[k], pts[k])) if len(k) else 0.0 for k in nb])
-    ok = ~degenerate & (gap >= 1e-8 * scale)
-    excluded = int((~degenerate & ~ok).sum())
-    assert np.array_equal(_bits(got[degenerate]), _bits(np.tile([0.0, 0.0, 1.0], (int(degenerate.sum()), 1))))
-    ang = _angle(got[ok], want[ok])
-    assert ang.max(initial=0.0) <= 1e-6, ang.max()
-    assert np.abs(np.linalg.norm(got, axis=1) - 1.0).max() <= 1e-14
-    return excluded, int(ok.sum()), int(degenerate.sum())
+    assert np.array_equal(R.bits(nrm[degenerate]), R.bits(np.tile([0.0, 0.0, 1.0], (int(degenerate.sum()), 1))))
 
 
 @pytest.mark.parametrize('max_nn', [8, 30, 64])
@@ -99,7 +79,7 @@ def test_normals_agree_with_the_oracle_on_depth_scenes(max_nn):
     _, pts, _, t = _frames(2)
     for f in range(2):
         got = ctx.estimate_normals(pts[f], t[f], 0.05, max_nn, orient=False)
-        excluded, compared, degenerate = _check_against_oracle(pts[f], 0.05, max_nn, got)
+        excluded, compared, degenerate = R.check_against_oracle(pts[f], 0.05, max_nn, got)
         print(f'frame {f} max_nn {max_nn}: {compared} rows compared, {excluded} excluded (small eigen-gap), {degenerate} degenerate')
         assert excluded <= 0.001 * len(got)
         assert compared >= 0.99 * len(got)
@@ -114,7 +94,7 @@ def test_normals_agree_with_the_oracle_on_analytic_clouds():
     plane = np.stack([u.ravel(), v.ravel()], 1) @ np.array([[1.0, 0.2, -0.3], [0.1, 1.0, 0.4]]) + [0.3, -0.2, 2.0]
     for pts in (sphere, plane):
         got = ctx.estimate_normals(pts, np.zeros(3), 0.05, 30, orient=False)
-        excluded, compared, _ = _check_against_oracle(pts, 0.05, 30, got)
+        excluded, compared, _ = R.check_against_oracle(pts, 0.05, 30, got)
         assert excluded == 0 and compared == len(pts)
 
 
@@ -128,7 +108,7 @@ def test_orientation_is_the_reference_flip_of_the_unoriented_output():
         close = np.abs(dots) < 1e-12
         assert int(close.sum()) == 0
         want = R.orient(pts[f], raw, t[f])
-        assert np.array_equal(_bits(got), _bits(want))
+        assert np.array_equal(R.bits(got), R.bits(want))
         at_centre = (pts[f] == t[f]).all(axis=1)
         assert at_centre.sum() > 0 and (got[at_centre] == [0.0, 0.0, 1.0]).all()        # NaN direction: not flipped
 
@@ -157,21 +137,21 @@ def test_entry_points_agree_bit_for_bit():
     batch = out.cpu().numpy()
     bc, bn = cnt.cpu().numpy().reshape(F, n), nb.cpu().numpy().reshape(F, n, max_nn)
     for f in range(F):
-        assert np.array_equal(_bits(batch[f]), _bits(single[f][0]))                      # batch == single-frame calls
+        assert np.array_equal(R.bits(batch[f]), R.bits(single[f][0]))                      # batch == single-frame calls
         assert np.array_equal(bc[f], single[f][1]) and np.array_equal(bn[f], single[f][2])
     # device call of one frame == host-pointer call; the drop-in == the Context method; a repeat gives the same bits
     one = torch.empty((n, 3), dtype=torch.float64, device=dev)
     ctx.estimate_normals_batch_dev(x[1].data_ptr(), 1, n, t[1:2], one.data_ptr(), 0.05, max_nn, True, stream=s)
     torch.cuda.synchronize(dev)
-    assert np.array_equal(_bits(one.cpu().numpy()), _bits(single[1][0]))
+    assert np.array_equal(R.bits(one.cpu().numpy()), R.bits(single[1][0]))
     drop_in = ios_rtab.surface_normal_estimation(pts[2], t[2])
     assert drop_in.dtype == np.float64 and drop_in.shape == (n, 3)
-    assert np.array_equal(_bits(drop_in), _bits(ctx.estimate_normals(pts[2], t[2])))
-    assert np.array_equal(_bits(drop_in), _bits(single[2][0]))
-    assert np.array_equal(_bits(ios_rtab.surface_normal_estimation(pts[2], t[2])), _bits(drop_in))
+    assert np.array_equal(R.bits(drop_in), R.bits(ctx.estimate_normals(pts[2], t[2])))
+    assert np.array_equal(R.bits(drop_in), R.bits(single[2][0]))
+    assert np.array_equal(R.bits(ios_rtab.surface_normal_estimation(pts[2], t[2])), R.bits(drop_in))
     ctx.estimate_normals_batch_dev(x.data_ptr(), F, n, t, out.data_ptr(), 0.05, max_nn, True, cnt.data_ptr(), nb.data_ptr(), s)
     torch.cuda.synchronize(dev)
-    assert np.array_equal(_bits(out.cpu().numpy()), _bits(batch)) and np.array_equal(nb.cpu().numpy().reshape(F, n, max_nn), bn)
+    assert np.array_equal(R.bits(out.cpu().numpy()), R.bits(batch)) and np.array_equal(nb.cpu().numpy().reshape(F, n, max_nn), bn)
 
 
 def test_errors_write_nothing():
@@ -219,8 +199,8 @@ def test_depth_to_fused_cloud_end_to_end():
     assert pts.shape == (F, H * W, 3) and nrm.shape == (F, H * W, 3) and pts.is_cuda and nrm.dtype == torch.float64
     host_pts = pts.cpu().numpy()
     for j in range(F):                                                 # the same as the one-frame host paths
-        assert np.array_equal(_bits(host_pts[j]), _bits(ios_rtab.frame_points_world(depth[j], KD, odo_xyzw[j], odo_xyz[j])))
-    assert np.array_equal(_bits(nrm[2].cpu().numpy()), _bits(ios_rtab.surface_normal_estimation(host_pts[2], odo_xyz[2])))
+        assert np.array_equal(R.bits(host_pts[j]), R.bits(ios_rtab.frame_points_world(depth[j], KD, odo_xyzw[j], odo_xyz[j])))
+    assert np.array_equal(R.bits(nrm[2].cpu().numpy()), R.bits(ios_rtab.surface_normal_estimation(host_pts[2], odo_xyz[2])))
     rng = np.random.default_rng(4)
     clr = torch.from_numpy(rng.uniform(0, 1, (F, H * W, 3))).to(dev)
     valid = torch.from_numpy((depth > 0).reshape(F, -1).astype(np.uint8)).to(dev)
