@@ -193,6 +193,39 @@ int f3d_ctx_set_strict(f3d_ctx* ctx, int strict) {
 
 long long f3d_ctx_alloc_count(const f3d_ctx* ctx) { return ctx ? ctx->allocs : -1; }
 
+// Test hook (include/f3d.h): every byte a call may find in the arenas becomes `byte`.  What the code documents as holding nothing
+// between calls is filled; what carries an invariant across calls is left: dev_err (the sticky error word) and codebook (its
+// presence set is kept zero between calls).  The vote set is filled and marked unstamped, so the next batched vote clears it as it
+// does after a single-frame vote.  The sequences that keep state in the arenas are ended: their fill passes ask for the count pass.
+int f3d_debug_poison(f3d_ctx* ctx, int byte, int64_t out[2]) {
+    int rc = enter(ctx); if (rc) return rc;
+    if (!out || byte < 0 || byte > 255) return fail(ctx, F3D_ERR_INVALID, "debug_poison: byte must be in [0, 255] and out not NULL");
+    if (ctx->chunk.active) return fail(ctx, F3D_ERR_INVALID, "debug_poison: a view-chunked fused call is in progress (its coded masks and todo list live in the scratch)");
+    F3D_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    int64_t buffers = 0, bytes = 0;
+    auto fill = [&](void* p, size_t n) -> hipError_t {
+        if (!p || !n) return hipSuccess;
+        ++buffers; bytes += (int64_t)n;
+        return hipMemsetAsync(p, byte, n, ctx->stream);
+    };
+    for (devbuf& b : ctx->scratch) F3D_HIP(ctx, fill(b.p, b.cap));
+    for (devbuf& b : ctx->stage) F3D_HIP(ctx, fill(b.p, b.cap));
+    for (devbuf& b : ctx->kept) F3D_HIP(ctx, fill(b.p, b.cap));
+    F3D_HIP(ctx, fill(ctx->filter_dev, sizeof(int32_t) * F3D_MAX_FILTER));
+    F3D_HIP(ctx, fill(ctx->count_dev, sizeof(unsigned long long)));
+    F3D_HIP(ctx, fill(ctx->first_bad, sizeof(int)));
+    F3D_HIP(ctx, fill(ctx->pv_words, 4 * sizeof(int)));
+    F3D_HIP(ctx, fill(ctx->table, ctx->table_slots * sizeof(unsigned long long)));
+    ctx->table_stamped = false;
+    ctx->graph_n = -1; ctx->graph_kept = false;
+    ctx->qry_n = -1; ctx->qry_kept = false;
+    ctx->grp_n = -1; ctx->grp_cloud = false;
+    ctx->tsdf_n = -1; ctx->tsdf_kept = false;
+    F3D_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    out[0] = buffers; out[1] = bytes;
+    return F3D_OK;
+}
+
 int f3d_take_device_error(f3d_ctx* ctx, void* stream) {
     int rc = enter(ctx); if (rc) return rc;
     return take_error(ctx, pick(ctx, stream));

@@ -245,6 +245,7 @@ def library():
         'f3d_debug_tsdf_grid_cap': (i32, [vp, i32]),
         'f3d_debug_grid_cap': (i32, [vp, i32]),
         'f3d_debug_grid_cap_stats': (i32, [vp, vp]),
+        'f3d_debug_poison': (i32, [vp, i32, vp]),
         'f3d_fuse_features': (i32, [vp, vp, i32, i64, vp, i32, i32, i32, vp, i32, i32, i32, i32, i32, dbl, vp, vp, i32]),
         'f3d_fuse_features_dev': (i32, [vp, vp, i32, i64, vp, i32, i32, i32, vp, i32, i32, i32, i32, i32, dbl, vp, vp, i32, vp]),
         'f3d_features_finalize': (i32, [vp, vp, vp, i64, i32, i32, vp]),
@@ -1238,6 +1239,14 @@ class Context:
         counters are per PROCESS, not per context.  No result depends on them."""
         out = np.zeros(2, np.int64)
         self._check(self._lib.f3d_debug_grid_cap_stats(self._h, _ptr(out)))
+        return int(out[0]), int(out[1])
+
+    def debug_poison(self, byte):
+        """Test hook: fill every scratch, staging and kept buffer of this context, and the members that hold nothing between calls,
+        with `byte` (0..255) -> (buffers filled, bytes filled).  Counted sequences end: their fill passes ask for the count pass.
+        Refused while a view-chunked fused call is in progress.  No result of a later call depends on the byte."""
+        out = np.zeros(2, np.int64)
+        self._check(self._lib.f3d_debug_poison(self._h, int(byte), _ptr(out)))
         return int(out[0]), int(out[1])
 
     def tsdf_integrate(self, tsdf, weight, lo, voxel, trunc, max_weight, depths, views, depth_scale=1.0, max_depth=10.0):

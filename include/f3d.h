@@ -1200,7 +1200,15 @@ int f3d_estimate_normals_batch_dev(f3d_ctx* ctx, const double* xyz, int nframes,
  * f3d_debug_grid_cap (test hook): the same for every other grid-stride launch of the library, and for the TSDF and raycast launches as
  * well (they take the smaller of the two caps).  The state belongs to the PROCESS, not to ctx: it holds for every context and every
  * thread until it is set back to 0.  It only ever lowers a grid, never below one block.  f3d_debug_grid_cap_stats reads and resets two
- * process-wide counters: out[0] = grids sized while the cap was on, out[1] = those the cap made smaller.  No result depends on either. */
+ * process-wide counters: out[0] = grids sized while the cap was on, out[1] = those the cap made smaller.  No result depends on either.
+ * f3d_debug_poison (test hook): drains the context's stream, fills every allocated scratch, staging and kept buffer of ctx over its whole
+ * capacity with `byte` (0..255), and with them the members that hold nothing between calls (the filter list, the relabel counter, the
+ * batched vote's first-bad word, the point vote's words, the vote set, which the next batched vote then clears), and drains the stream
+ * again; out[0] = buffers filled, out[1] = bytes filled.  The sticky device error word and the code book keep their contents.  It ends
+ * every counted sequence of the context (radius graph, radius query, group -> extremes -> hull filter, TSDF extract): their fill passes
+ * then ask for the count pass, as after any other interruption.  F3D_ERR_INVALID: a byte outside [0, 255], out == NULL, or a
+ * view-chunked fused call in progress (nothing is filled).  It reads no environment variable and no entry looks at it: no result of a
+ * later call may depend on the byte. */
 #define F3D_TSDF_SCAN_TILE 2048
 #define F3D_TSDF_MAX_WEIGHT 16777216.0f
 int f3d_tsdf_integrate(f3d_ctx* ctx, float* tsdf, float* weight, int nx, int ny, int nz, const double lo[3], double vs, double trunc,
@@ -1221,6 +1229,7 @@ int f3d_ctx_reserve_tsdf(f3d_ctx* ctx, int64_t nvoxels);
 int f3d_debug_tsdf_grid_cap(f3d_ctx* ctx, int blocks);
 int f3d_debug_grid_cap(f3d_ctx* ctx, int blocks);
 int f3d_debug_grid_cap_stats(f3d_ctx* ctx, int64_t out[2]);
+int f3d_debug_poison(f3d_ctx* ctx, int byte, int64_t out[2]);
 
 /* ---- feature fusion: per-point pooling of per-pixel feature maps over views (no reference counterpart) -------------------- */
 /* Every other 2D -> 3D entry moves one byte per pixel (a class or an instance id).  These move a vector: the [C] logits or

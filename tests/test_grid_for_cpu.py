@@ -1,6 +1,6 @@
 """f3d_grid_for (csrc/f3d_kernels.h) without a GPU: its clamp and the process-wide debug cap, printed by a stand-alone host program
 and compared with the clamp restated here; and two readings of the kernel sources -- every file that sizes a grid with it has a case in
-tests/test_launch_shape_gpu.py, and every kernel launched with such a grid walks its items with a gridDim.x stride."""
+tests/family_cases.py (which tests/test_launch_shape_gpu.py runs under the cap), and every kernel launched with such a grid walks its items with a gridDim.x stride."""
 import ast
 import os
 import re
@@ -89,18 +89,19 @@ def sources_with_grid_for():
 
 
 def cases_keys():
-    """The keys of the CASES table of tests/test_launch_shape_gpu.py, read from its source: test modules do not import each other."""
-    tree = ast.parse((ROOT / 'tests' / 'test_launch_shape_gpu.py').read_text())
+    """The keys of the CASES table of tests/family_cases.py as its source lists them: a key written twice shows here, in the dict it would not."""
+    tree = ast.parse((ROOT / 'tests' / 'family_cases.py').read_text())
     for node in tree.body:
         if isinstance(node, ast.Assign) and any(isinstance(t, ast.Name) and t.id == 'CASES' for t in node.targets):
             assert isinstance(node.value, ast.Dict)
             return [ast.literal_eval(k) for k in node.value.keys]
-    raise AssertionError('test_launch_shape_gpu.py has no CASES table')
+    raise AssertionError('family_cases.py has no CASES table')
 
 
 def test_every_source_that_sizes_a_grid_has_a_launch_shape_case():
+    import family_cases
     keys = cases_keys()
-    assert len(keys) == len(set(keys))
+    assert len(keys) == len(set(keys)) and sorted(keys) == sorted(family_cases.CASES)     # the table the GPU tests import is the one read here
     assert sorted(keys) == sources_with_grid_for()                         # none uncovered, none stale
 
 
