@@ -316,3 +316,94 @@ def tracking_errors(pq, pt, q, t, q_true, t_true):
     centre, axis = E @ (T.SPHERE_C - t_true[0]) + pt[0], E @ AXIS_N
     errs = np.array([scene_error(q[f], t[f], q_true[f], t_true[f], centre, axis) for f in range(1, len(q))])
     return errs.mean(axis=0)
+
+
+# ------------------------------------------------------------------------------------------------ scenes of the sample-range tests
+# A sphere in a 23 x 19 x 17 volume, every weight 1, its radius (10.4 voxels) above the half extent on y (9.5) and z (8.5): the surface
+# leaves through four faces, so rays meet it right behind the first valid sample.  The image is 15 x 17 with the principal point on a
+# pixel centre: the centre column and the centre row have a camera-frame direction component of exactly 0.
+RAY_DIMS, RAY_LO, RAY_H, RAY_W = (23, 19, 17), np.array([-0.6, -0.5, 0.5]), 15, 17
+RAY_K = np.array([[16.0, 0.0, 8.5], [0.0, 16.0, 7.5], [0.0, 0.0, 1.0]])
+RAY_SHIFT = np.array([1000.0, -2000.0, 500.0])
+_R = np.sqrt(0.5)
+AXIS_CAMERAS = {'+z': ([1.0, 0.0, 0.0, 0.0], 2), '-z': ([0.0, 1.0, 0.0, 0.0], 2), '+x': ([_R, 0.0, _R, 0.0], 0), '-x': ([_R, 0.0, -_R, 0.0], 0),
+                '+y': ([_R, -_R, 0.0, 0.0], 1), '-y': ([_R, _R, 0.0, 0.0], 1)}      # looking along: (quaternion, axis)
+
+
+def ray_volume(vs=0.05):
+    """(tsdf, weight, lo, vs, centre): everything but lo scales with the voxel."""
+    centre = RAY_LO + np.array(RAY_DIMS) * vs / 2 + np.array([0.013, -0.021, 0.007]) * (vs / 0.05)
+    tsdf, weight = T.sphere_state(RAY_DIMS, RAY_LO, vs, centre, 10.4 * vs, 4 * vs)
+    return tsdf, weight, RAY_LO, vs, centre
+
+
+def ray_cases():
+    """name -> dict(vs, lo, K, q, t, near, step, nsteps): the cameras and marches of the sample-range tests.  Lengths are in voxels of
+    the case's volume: every camera but the distant ones stands 30 voxels from the sphere's centre and marches 80 voxels."""
+    cases = {}
+
+    def add(name, q, back, vs=0.05, K=RAY_K, near=0.0, step=1.0, nsteps=None, shift=None, sideways=(0.0, 0.0, 0.0)):
+        centre = ray_volume(vs)[4]
+        t = centre - np.asarray(back, np.float64) * vs + np.asarray(sideways, np.float64) * vs
+        lo = RAY_LO
+        if shift is not None:
+            lo, t = lo + shift, t + shift
+        nsteps = nsteps if nsteps is not None else int(np.floor(80.0 / step)) + 1
+        cases[name] = dict(vs=vs, lo=lo, K=K, q=np.array(q, np.float64), t=t, near=near * vs, step=step * vs, nsteps=nsteps)
+
+    def axis(name, distance=30.0):
+        q, a = AXIS_CAMERAS[name]
+        back = np.zeros(3)
+        back[a] = distance if name[0] == '+' else -distance
+        return q, back
+
+    for name in AXIS_CAMERAS:
+        add('axis' + name, *axis(name))
+    add('fine-voxels', *axis('+x'), vs=1.0 / 64)
+    # the centre column (dw_x == 0) runs beside the volume, three voxels outside it; the columns right of it still reach the sphere
+    add('beside', *axis('+z'), sideways=(-(RAY_DIMS[0] / 2 + 0.26) - 3.0, 0.0, 0.0))
+    # the centre row (dw_y == 0) runs inside the volume, a quarter voxel above the last valid sample position lo + (ny - 0.5) vs
+    add('just-outside', *axis('+z'), sideways=(0.0, (RAY_DIMS[1] / 2 + 0.42) - 0.5 + 0.25, 0.0))
+    # the same on the other side: three voxels beyond the +x face, and a quarter voxel below the first valid position lo + 0.5 vs
+    add('beside-high', *axis('+z'), sideways=((RAY_DIMS[0] / 2 - 0.26) + 3.0, 0.0, 0.0))
+    add('just-outside-low', *axis('+z'), sideways=(0.0, -(RAY_DIMS[1] / 2 - 0.42) + 0.5 - 0.25, 0.0))
+    for c in range(8):                                                  # from beyond the eight corners, looking at the centre
+        signs = np.array([1.0 if c >> a & 1 else -1.0 for a in range(3)])
+        q, _ = T.look_at(signs * 17.5, np.zeros(3))
+        add(f'corner{c}', q, -signs * 17.5)
+    add('coarse-steps', *axis('-y'), step=2.7)
+    add('fine-steps', cases['corner5']['q'], (-17.5, 17.5, -17.5), step=0.125)
+    add('near-inside', *axis('-x'), near=19.5)
+    add('near-beyond', *axis('+z'), near=45.0)
+    add('ends-before', *axis('+x'), nsteps=18)
+    add('ends-inside', *axis('+x'), nsteps=22)
+    tele = np.array([[640.0, 0.0, 8.5], [0.0, 640.0, 7.5], [0.0, 0.0, 1.0]])
+    add('distant', *axis('+z', 1200.0), K=tele, near=1160.0, nsteps=100)
+    add('distant-shifted', *axis('+z', 1200.0), K=tele, near=1160.0, nsteps=100, shift=RAY_SHIFT)
+    add('shifted', *axis('-x'), shift=RAY_SHIFT)
+    return cases
+
+
+def ray_rays(case, h=RAY_H, w=RAY_W):
+    """dw float64 [h*w, 3] of the header's rays."""
+    K = case['K']
+    vv, uu = np.meshgrid(np.arange(h, dtype=np.float64), np.arange(w, dtype=np.float64), indexing='ij')
+    dc = np.stack([((uu.reshape(-1) + 0.5) - K[0, 2]) / K[0, 0], ((vv.reshape(-1) + 0.5) - K[1, 2]) / K[1, 1], np.ones(h * w)], axis=1)
+    return O.rotate(normalise(case['q']), dc)
+
+
+def first_valid(case, state, h=RAY_H, w=RAY_W):
+    """int64 [h*w]: the first sample index of every ray that F(P) calls valid, -1 where none of the nsteps samples is; from `sample`
+    alone."""
+    tsdf, weight = state
+    dw, fv = ray_rays(case, h, w), np.full(h * w, -1)
+    for k in range(case['nsteps']):
+        s = case['near'] + np.float64(k) * case['step']
+        valid, _ = sample(tsdf, weight, case['lo'], case['vs'], 1.0, case['t'][None, :] + s * dw)
+        fv = np.where((fv < 0) & valid, k, fv)
+    return fv
+
+
+def ray_case_maps(case, state, h=RAY_H, w=RAY_W, nsteps=None):
+    return raycast(state[0], state[1], case['lo'], case['vs'], 1.0, case['K'], case['q'], case['t'], h, w, case['near'], case['step'],
+                   case['nsteps'] if nsteps is None else nsteps)

@@ -226,3 +226,109 @@ def test_argument_errors_need_no_device():
         track(depths=np.zeros((2, 4, 4), np.int64))
     q_out, t_out, status = track(depths=np.zeros((0, 4, 4)), wxyzs=np.zeros((0, 4)), translations=np.zeros((0, 3)))     # no frames: no device
     assert q_out.shape == (0, 4) and t_out.shape == (0, 3) and status.shape == (0,) and status.dtype == np.int32
+
+
+# ------------------------------------------------------------------------------------------------ the scenes of test_raycast_range_gpu.py
+# Each case of the sample-range tests must reach the path it is meant for.  That is shown here on the restatement alone: the rays of
+# the header (I.ray_rays), the validity of every sample (I.first_valid, from I.sample) and the restated maps.
+@pytest.fixture(scope='module')
+def ray_scene():
+    """(cases, name -> (first valid sample, hit mask, index of the sample before each hit))."""
+    cases, states, seen = I.ray_cases(), {}, {}
+
+    def look(name):
+        if name not in seen:
+            case = cases[name]
+            state = states.setdefault(case['vs'], I.ray_volume(case['vs'])[:2])
+            depth = I.ray_case_maps(case, state)[2]
+            hit = depth > 0
+            before = np.where(hit, np.floor((depth - case['near']) / case['step']), -1).astype(np.int64)
+            seen[name] = (I.first_valid(case, state), hit, before, state)
+        return seen[name]
+    return cases, look
+
+
+def near_first(fv, hit, before):
+    """hits whose last sample in front of the surface is the ray's first valid sample or the one after it"""
+    return int((hit & (before - fv <= 1)).sum())
+
+
+@pytest.mark.parametrize('name', ['axis' + a for a in I.AXIS_CAMERAS] + ['fine-voxels'])
+def test_axis_cameras_have_rays_along_the_faces(ray_scene, name):
+    cases, look = ray_scene
+    fv, hit, before, _ = look(name)
+    zeros = int((I.ray_rays(cases[name]) == 0).sum())
+    print(f'{name}: {zeros} direction components exactly 0, {int(hit.sum())} hits, {int((fv < 0).sum())} rays without a valid sample, '
+          f'{near_first(fv, hit, before)} hits within one step of the first valid sample')
+    assert zeros >= I.RAY_H + I.RAY_W
+    assert hit.sum() >= 5 and (fv < 0).sum() >= 5 and near_first(fv, hit, before) >= 5
+
+
+@pytest.mark.parametrize('c', range(8))
+def test_corner_cameras_enter_through_edges_and_corners(ray_scene, c):
+    """Among the first valid samples of the rays there are cells on an edge of the volume (two indices at an end of their range)."""
+    cases, look = ray_scene
+    case = cases[f'corner{c}']
+    fv, hit, before, _ = look(f'corner{c}')
+    P = case['t'][None, :] + (case['near'] + fv[fv >= 0].astype(np.float64) * case['step'])[:, None] * I.ray_rays(case)[fv >= 0]
+    cell = np.floor((P - case['lo'][None, :]) / case['vs'] - 0.5)
+    at_end = (cell == 0) | (cell == np.array(I.RAY_DIMS)[None, :] - 2)
+    print(f'corner{c}: {int(hit.sum())} hits, {int((fv < 0).sum())} rays without a valid sample, {near_first(fv, hit, before)} hits within one step '
+          f'of the first valid sample, {int((at_end.sum(axis=1) >= 2).sum())} rays enter through an edge cell')
+    assert hit.sum() >= 5 and (fv < 0).sum() >= 5 and (at_end.sum(axis=1) >= 2).sum() >= 3
+
+
+def test_rays_beside_the_volume(ray_scene):
+    """`beside`: the centre column has dw_x == 0 and starts three voxels outside the volume; it is NaN, columns right of it hit.
+    `just-outside`: the centre row has dw_y == 0 and starts inside the volume, a quarter voxel past the last valid position: only the
+    index rule of F(P) rejects its samples.  `beside-high` and `just-outside-low` are the same on the opposite faces."""
+    cases, look = ray_scene
+    shape = (I.RAY_H, I.RAY_W)
+    case = cases['beside']
+    fv, hit, _, _ = look('beside')
+    beside_hits = int(hit.sum())
+    dw = I.ray_rays(case).reshape(shape + (3,))
+    assert (dw[:, I.RAY_W // 2, 0] == 0).all() and case['t'][0] < I.RAY_LO[0] - 2.5 * case['vs']
+    assert (fv.reshape(shape)[:, :I.RAY_W // 2 + 1] < 0).all() and not hit.reshape(shape)[:, :I.RAY_W // 2 + 1].any()
+    assert hit.reshape(shape)[:, I.RAY_W // 2 + 1:].sum() >= 5
+    case = cases['just-outside']
+    fv, hit, _, _ = look('just-outside')
+    dw = I.ray_rays(case).reshape(shape + (3,))
+    top = I.RAY_LO[1] + (I.RAY_DIMS[1] - 0.5) * case['vs']
+    assert (dw[I.RAY_H // 2, :, 1] == 0).all() and top < case['t'][1] < top + 0.5 * case['vs']
+    assert (fv.reshape(shape)[I.RAY_H // 2:] < 0).all() and (fv.reshape(shape)[:I.RAY_H // 2] >= 0).any()
+    print(f'beside: {beside_hits} hits; just-outside: {int(hit.sum())} hits, {int((fv >= 0).sum())} rays with a valid sample')
+    assert hit.reshape(shape)[:I.RAY_H // 2].sum() >= 5
+    # the mirrored pair: beyond the +x face, and below the first valid position on y
+    case, mid = cases['beside-high'], I.RAY_W // 2
+    fv, hit, _, _ = look('beside-high')
+    high_hits = int(hit.sum())
+    assert (I.ray_rays(case).reshape(shape + (3,))[:, mid, 0] == 0).all()
+    assert case['t'][0] > I.RAY_LO[0] + (I.RAY_DIMS[0] + 2.5) * case['vs']
+    assert (fv.reshape(shape)[:, mid:] < 0).all() and not hit.reshape(shape)[:, mid:].any() and hit.reshape(shape)[:, :mid].sum() >= 5
+    case, mid = cases['just-outside-low'], I.RAY_H // 2
+    fv, hit, _, _ = look('just-outside-low')
+    bottom = I.RAY_LO[1] + 0.5 * case['vs']
+    assert (I.ray_rays(case).reshape(shape + (3,))[mid, :, 1] == 0).all() and bottom - 0.5 * case['vs'] < case['t'][1] < bottom
+    assert (fv.reshape(shape)[:mid + 1] < 0).all() and hit.reshape(shape)[mid + 1:].sum() >= 5
+    print(f'beside-high: {high_hits} hits; just-outside-low: {int(hit.sum())} hits, {int((fv >= 0).sum())} rays with a valid sample')
+
+
+def test_range_clips(ray_scene):
+    cases, look = ray_scene
+    for name in ('coarse-steps', 'fine-steps', 'near-inside', 'distant', 'distant-shifted', 'shifted'):
+        fv, hit, before, _ = look(name)
+        print(f'{name}: {int(hit.sum())} hits, {near_first(fv, hit, before)} within one step of the first valid sample')
+        assert hit.sum() >= 5
+    case = cases['near-inside']
+    start = case['t'] + case['near'] * I.ray_rays(case)[(I.RAY_H // 2) * I.RAY_W + I.RAY_W // 2]
+    assert np.all((start > I.RAY_LO) & (start < I.RAY_LO + np.array(I.RAY_DIMS) * case['vs']))
+    assert (look('near-inside')[0] == 0).sum() >= 5                     # first samples that are valid
+    for name in ('near-beyond', 'ends-before'):
+        fv, hit, _, _ = look(name)
+        assert (fv < 0).all() and not hit.any()
+    fv, hit, _, state = look('ends-inside')
+    later = I.ray_case_maps(cases['ends-inside'], state, nsteps=81)[2] > 0
+    print(f'ends-inside: {int(hit.sum())} hits, {int((later & ~hit).sum())} more on later samples')
+    assert hit.sum() >= 5 and (later & ~hit).sum() >= 5 and not (hit & ~later).any()
+    assert abs(np.linalg.norm(cases['distant']['t'] - I.ray_volume()[4]) - 60.0) < 1e-9 and cases['distant']['near'] == 58.0

@@ -172,6 +172,112 @@ def sphere_state(dims, lo, vs, centre, radius, trunc):
     return np.clip(sd, -1.0, 1.0).astype(np.float32).reshape(nz, ny, nx), np.ones((nz, ny, nx), np.float32)
 
 
+# ------------------------------------------------------------------------------------------------ scenes of the cull tests
+def frame_terms(K, wxyz, t, lo, dims, vs, depth, depth_scale=1.0):
+    """The per-voxel quantities of integrate's steps 1 - 4 for one frame, float64 [ny * nz, nx] each (a row is an x-run): h0, h1, h2,
+    px, py, d, sdf.  px and py are NaN where h2 > 0 fails, d and sdf where the voxel has no pixel."""
+    K, depth = np.asarray(K, np.float64), np.asarray(depth)
+    h, w = depth.shape
+    c = voxel_centres(lo, dims, vs)
+    cam = O.rotate(O.quat_inverse(wxyz), c - np.asarray(t, np.float64)[None, :])
+    x, y, z = cam[:, 0], cam[:, 1], cam[:, 2]
+    h0 = (K[0, 0] * x + K[0, 1] * y) + K[0, 2] * z
+    h1 = (K[1, 0] * x + K[1, 1] * y) + K[1, 2] * z
+    h2 = (K[2, 0] * x + K[2, 1] * y) + K[2, 2] * z
+    with np.errstate(all='ignore'):
+        px, py = np.where(h2 > 0, h0 / h2, np.nan), np.where(h2 > 0, h1 / h2, np.nan)
+        inside = (px >= 0) & (px < w) & (py >= 0) & (py < h)
+        u, v = np.where(inside, np.floor(px), 0).astype(np.int64), np.where(inside, np.floor(py), 0).astype(np.int64)
+        d = np.where(inside, depth[v, u].astype(np.float64) / np.float64(depth_scale), np.nan)
+    rows = lambda a: a.reshape(-1, dims[0])                            # noqa: E731
+    return dict(h0=rows(h0), h1=rows(h1), h2=rows(h2), px=rows(px), py=rows(py), d=rows(d), sdf=rows(d - h2))
+
+
+def failed_rules(terms, h, w, max_depth, trunc):
+    """Which of the contract's geometric rules each voxel fails, bool [ny * nz, nx] each.  `behind` is step 1 (h2 > 0 fails); `left`,
+    `right`, `up`, `down` are the four comparisons of step 2 (for h2 > 0); `far` is h2 > max_depth + trunc, where d <= max_depth
+    (step 3) and sdf >= -trunc (step 4) cannot both hold, whatever the depth."""
+    px, py, h2 = terms['px'], terms['py'], terms['h2']
+    with np.errstate(invalid='ignore'):
+        return dict(behind=~(h2 > 0), far=h2 > max_depth + trunc, left=px < 0, right=px >= w, up=py < 0, down=py >= h)
+
+
+def applied(terms, max_depth, trunc):
+    """bool [ny * nz, nx]: the frame changes the voxel (every step of the contract passes)."""
+    with np.errstate(invalid='ignore'):
+        return (terms['d'] > 0) & (terms['d'] <= max_depth) & ~(terms['sdf'] < -trunc)
+
+
+def run_counts(fails, rule):
+    """(x-runs whose every voxel fails `rule` and no other rule, x-runs that hold voxels that fail it and voxels that pass it)."""
+    others = np.zeros_like(fails[rule])
+    for name, f in fails.items():
+        if name != rule:
+            others |= f
+    only = fails[rule] & ~others
+    return int(only.all(axis=1).sum()), int((fails[rule].any(axis=1) & ~fails[rule].all(axis=1)).sum())
+
+
+def ring(F):
+    """F poses that wind three times around the sphere-and-wall scene, all in front of the wall -> (eyes, targets)."""
+    a = 2 * np.pi * np.arange(F) / F * 3.0
+    eyes = [(0.9 * np.cos(x), 0.6 * np.sin(x), 0.15 + 0.25 * np.sin(2.3 * x)) for x in a]
+    targets = [(0.05 + 0.3 * np.cos(1.7 * x), -0.02 + 0.2 * np.sin(x), 1.1) for x in a]
+    return eyes, targets
+
+
+# The ring's volume: 70 voxels along x are two x tiles of a wave, the second partial; it reaches from beside the sphere to beyond it.
+RING = dict(dims=(70, 9, 7), vs=0.05, lo=np.array([-1.7, -0.2, 0.9]), trunc=0.2, h=20, w=24, max_depth=4.0)
+
+
+def ring_scene(F):
+    """K, wxyzs, translations, depths float64 [F, 20, 24] of the ring."""
+    return scene(*ring(F), RING['h'], RING['w'])
+
+
+FAR_SHIFT = np.array([1000.0, -2000.0, 500.0])                         # moves a scene (lo and every translation) away from the origin
+# for the ring's 20 x 24 image: skew, unequal focal lengths, a principal point off the centre
+SKEW_K = np.array([[21.6, 1.5, 12.3], [0.0, 19.0, 9.6], [0.0, 0.0, 1.0]])
+
+
+# One camera per bound of the frame cull, over the volume of the base scene with a 20 x 24 image.  look_at's third argument is the
+# image's down direction: (1, 0, 0) rolls the camera by 90 degrees, so that the x-runs of the volume cross the upper and lower bounds.
+# The behind camera stands inside the volume, near its +x end, looking towards +x and tilted by 45 degrees, so that the runs of one
+# corner lie wholly behind its plane; its focal length is a third of the others', so that its frustum holds most of what is in front.
+BOUNDS = dict(dims=(37, 29, 21), vs=0.05, lo=np.array([-0.9, -0.7, 0.55]), trunc=0.2, h=20, w=24)
+BOUND_CAMERAS = {
+    'left': dict(eye=(2.46, -0.69, 0.55), target=(0.57, 0.69, 2.23), down=(0.0, 1.0, 0.0), max_depth=4.0),
+    'right': dict(eye=(-2.68, -0.08, 1.35), target=(-1.33, -0.04, 1.85), down=(0.0, 1.0, 0.0), max_depth=4.0),
+    'up': dict(eye=(-2.86, 0.58, 0.94), target=(-0.03, 1.14, 0.66), down=(-1.0, 0.0, 0.0), max_depth=4.0),
+    'down': dict(eye=(-2.86, 0.58, 0.94), target=(-0.03, 1.14, 0.66), down=(1.0, 0.0, 0.0), max_depth=4.0),
+    'far': dict(eye=(0.47, -0.57, -0.34), target=(0.16, 0.01, 1.38), down=(0.0, 1.0, 0.0), max_depth=1.5),
+    'behind': dict(eye=(0.76, 0.24, 0.75), target=(1.76, -0.35, 1.56), down=(0.0, 1.0, 0.0), max_depth=4.0, focal=0.3),
+}
+
+
+def bound_scene(rule):
+    """K, wxyz, translation, depth float64 [20, 24], max_depth of the camera that exercises `rule`.  The far camera's depths are cut
+    at max_depth where they exceed it in the right half of the image, so some equal max_depth exactly."""
+    cam, h, w = BOUND_CAMERAS[rule], BOUNDS['h'], BOUNDS['w']
+    K = intrinsics(h, w, cam.get('focal', 0.9))
+    q, t = look_at(cam['eye'], cam['target'], cam['down'])
+    depth = cast_depth(K, q, t, h, w)
+    if rule == 'far':
+        depth[:, w // 2:] = np.minimum(depth[:, w // 2:], cam['max_depth'])
+    return K, q, t, depth, cam['max_depth']
+
+
+# Ties on the bounds: an identity pose at the origin, a 16 x 16 image with focal length 8 and principal point (8, 8), voxels of 1 / 16
+# whose centres are odd multiples of 1 / 32, and a flat depth of 1.0 = max_depth.  Every product and sum of the projection is exact, so
+# px == 0 where x == -z, px == w where x == z, py == 0 where y == -z, and h2 == max_depth + trunc in the layer z = 1.21875.
+TIES = dict(vs=0.0625, trunc=0.21875, max_depth=1.0, h=16, w=16, K=np.array([[8.0, 0.0, 8.0], [0.0, 8.0, 8.0], [0.0, 0.0, 1.0]]),
+            wxyz=np.array([1.0, 0.0, 0.0, 0.0]), t=np.zeros(3))
+TIE_VOLUMES = {
+    'wide': dict(dims=(48, 12, 14), lo=np.array([-1.5, -0.875, 0.5])),   # the image's left and right bounds cross every x-run
+    'left-end': dict(dims=(6, 12, 14), lo=np.array([-0.875, -0.875, 0.5])),   # px == 0 at the last voxel of the runs of the first layer
+}
+
+
 # ------------------------------------------------------------------------------------------------ mesh checks
 def edge_stats(tris):
     """(max uses of an undirected edge, min uses, max uses of a directed edge, undirected edge count)."""
