@@ -505,7 +505,7 @@ class Fusion:
                     t.record_stream(df.caller)
         return out
 
-    def reconstruct_mesh(self, voxel, lo=None, dims=None, trunc=None, max_weight=64, max_depth=10, min_weight=1, skip=1, points=None):
+    def reconstruct_mesh(self, voxel, lo=None, dims=None, trunc=None, max_weight=64, max_depth=10, min_weight=1, skip=1, points=None, colors=False):
         """A triangle mesh of the capture by TSDF reconstruction (``segUtils.reconstruct``): the frames' world points go back to
         camera-z depth images (``depth_images``, pixels that are not ``valid`` or not finite are holes), which are integrated into a
         volume of ``voxel`` edge and extracted by surface nets -> (vertices float64 [V, 3], triangles int32 [M, 3]), ready for
@@ -513,7 +513,9 @@ class Fusion:
         ``write_triangle_mesh``.  Without ``lo`` and ``dims`` the volume is the box of the fused cloud ``points`` (as ``fuse``
         returned it; without it, of the frames' valid points, which contains that box) grown by ``trunc`` (default 4 voxels) on
         every side.  Frames of device tensors give device tensors.  ``fuse`` consumes the ``valid`` masks of NumPy frames, so call
-        this first, or on a copy of the frames."""
+        this first, or on a copy of the frames.  With ``colors`` the frames' colours (``fr[3]``, float [h*w, 3] in [0, 1], made uint8
+        by ``round(clip(c, 0, 1) * 255)`` with NaN as 0, the rule of ``write_triangle_mesh``) are integrated with the depths ->
+        (vertices, triangles, vertex_colors float64 [V, 3] in [0, 1]), ready for ``TriangleMesh``; a vertex without a colour is black."""
         from Fusion3DSeg.segUtils.reconstruct import TSDFVolume, depth_images
         ids = np.arange(0, self.nframes, skip)
         frames = [self.frames[int(i)] for i in ids]
@@ -540,8 +542,22 @@ class Fusion:
             lo = cloud.min(axis=0) - trunc if lo is None else np.asarray(lo, np.float64)
             dims = np.maximum(1, np.ceil((cloud.max(axis=0) + trunc - lo) / voxel)).astype(np.int64)
         depths = depth_images(pts, self.xyzws[ids], self.translations[ids], valid)
-        vol = TSDFVolume(lo, dims, voxel, trunc, max_weight)
-        return vol.integrate(depths, self.K, self.xyzws[ids], self.translations[ids], 1.0, max_depth).extract_mesh(min_weight)
+        vol = TSDFVolume(lo, dims, voxel, trunc, max_weight, color=bool(colors))
+        if not colors:
+            return vol.integrate(depths, self.K, self.xyzws[ids], self.translations[ids], 1.0, max_depth).extract_mesh(min_weight)
+        if on_device(frames[0][3]):
+            import torch
+            rgb = torch.stack([torch.round(torch.clip(torch.nan_to_num(fr[3].to(torch.float64)), 0.0, 1.0) * 255.0).to(torch.uint8).reshape(self.h, self.w, 3)
+                               for fr in frames])
+        else:
+            rgb = np.stack([np.round(np.clip(np.nan_to_num(np.asarray(fr[3], np.float64)), 0.0, 1.0) * 255.0).astype(np.uint8).reshape(self.h, self.w, 3)
+                            for fr in frames])
+        vol.integrate(depths, self.K, self.xyzws[ids], self.translations[ids], 1.0, max_depth, colors=rgb)
+        verts, tris, vrgb, _ = vol.extract_mesh(min_weight, colors=True)
+        if on_device(vrgb):                                             # a tensor divisor: torch multiplies by the reciprocal of a host scalar
+            import torch
+            return verts, tris, vrgb.to(torch.float64) / torch.full((), 255.0, dtype=torch.float64, device=vrgb.device)
+        return verts, tris, vrgb.astype(np.float64) / 255.0
 
     @staticmethod
     def filter(values, threshold, data=None, less_than=False):

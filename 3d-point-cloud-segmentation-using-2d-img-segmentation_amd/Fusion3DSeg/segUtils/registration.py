@@ -179,13 +179,14 @@ def icp(depth, K, wxyz, t, model_vertex, model_normal, model_K, model_wxyz, mode
 
 
 def track_frames(volume, depths, K, wxyzs, translations, depth_scale=1.0, max_depth=10, max_dist=0.1, iterations=10, min_pairs=100, min_weight=1,
-                 integrate=True):
+                 integrate=True, colors=None):
     """Frame-to-model tracking of the depth frames ``depths`` [F, h, w] into ``volume`` (a ``TSDFVolume``), in frame order.  A frame
     that meets a volume with no weight is integrated at its given pose.  Every later frame is ray-cast at its given pose, the prior
     (samples every voxel edge up to ``max_depth``), aligned to those maps by ``icp`` starting from the prior, takes the refined pose if
     the status is 0 and the prior otherwise, and is integrated at the pose taken (``integrate=False``: only frames that meet an empty
     volume are integrated).  -> (wxyzs [F, 4], translations [F, 3], status int32 [F]); NumPy arrays, or device tensors when the depths
-    or the volume are on the device.
+    or the volume are on the device.  ``colors``: the frames' colour images, uint8 [F, hc, wc, 3], for a volume built with
+    ``color=True``; each frame that is integrated hands its image to ``integrate``.
 
     One host synchronisation per frame: the readback of the 7 doubles of the pose and the status, because ``views_build``, which makes
     the record ``integrate`` projects with, needs the pose on the host.  While the volume is empty its weights are looked at, too."""
@@ -205,7 +206,9 @@ def track_frames(volume, depths, K, wxyzs, translations, depth_scale=1.0, max_de
     min_weight = _min_weight(min_weight)
     near, step, nsteps = _march(volume, 0.0, max_depth, None)
     out_q, out_t, status = qs.copy(), ts.copy(), np.zeros(F, np.int32)
-    device = on_device(depths) or volume.on_device
+    if colors is not None:
+        colors = volume._color_images(colors, F)
+    device = on_device(depths) or volume.on_device or (colors is not None and on_device(colors))
     if F == 0:
         return _tracked(device, out_q, out_t, status)
     ctx = f3d.default_context()
@@ -221,7 +224,8 @@ def track_frames(volume, depths, K, wxyzs, translations, depth_scale=1.0, max_de
                 if status[f] == 0:
                     out_q[f], out_t[f] = pose[:4], pose[4:]
             if empty or integrate:
-                volume.integrate(depths[f:f + 1], K, out_q[f:f + 1], out_t[f:f + 1], depth_scale, max_depth)
+                volume.integrate(depths[f:f + 1], K, out_q[f:f + 1], out_t[f:f + 1], depth_scale, max_depth,
+                                 colors=None if colors is None else colors[f:f + 1])
         return out_q, out_t, status
     torch, dev = torch_device(ctx, 'track_frames')
     volume._to_device()
@@ -246,7 +250,8 @@ def track_frames(volume, depths, K, wxyzs, translations, depth_scale=1.0, max_de
             if status[f] == 0:
                 out_q[f], out_t[f] = back[:4], back[4:7]
         if empty or integrate:
-            volume.integrate(d_all[f:f + 1], K, out_q[f:f + 1], out_t[f:f + 1], depth_scale, max_depth)
+            volume.integrate(d_all[f:f + 1], K, out_q[f:f + 1], out_t[f:f + 1], depth_scale, max_depth,
+                             colors=None if colors is None else colors[f:f + 1])
     return _tracked(True, out_q, out_t, status)
 
 

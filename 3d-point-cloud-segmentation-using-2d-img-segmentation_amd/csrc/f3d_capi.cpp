@@ -3079,6 +3079,72 @@ int f3d_tsdf_extract_fill(f3d_ctx* ctx, int nx, int ny, int nz, const double lo[
     return st.finish();
 }
 
+// colour: the integrate arguments plus the colour state and the colour images; the vertex colours of a counted volume
+#define F3D_TSDF_COLOR_BAD "bad arguments (those of tsdf_integrate; color and rgb not NULL, the device color 16-byte aligned; hc, wc_img > 0 with a product < 2^31)"
+static bool tsdf_color_ok(const float* color, const uint8_t* rgb, int nframes, int hc, int wc_img) {
+    return color && hc > 0 && wc_img > 0 && (int64_t)hc * wc_img < ((int64_t)1 << 31) && (nframes == 0 || rgb);
+}
+static bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }     // a host color needs none: its staging copy has it
+
+int f3d_tsdf_integrate_color_dev(f3d_ctx* ctx, float* tsdf, float* weight, float* color, int nx, int ny, int nz, const double lo[3], double vs,
+                                 double trunc, float max_weight, const void* depth, int depth_type, const uint8_t* rgb, int nframes, int h, int w,
+                                 int hc, int wc_img, double depth_scale, double max_depth, const f3d_view* views_dev, void* stream) {
+    int rc = enter(ctx); if (rc) return rc;
+    if (!tsdf_integrate_ok(tsdf, weight, nx, ny, nz, lo, vs, trunc, max_weight, depth, depth_type, nframes, h, w, depth_scale, max_depth, views_dev) ||
+        !tsdf_color_ok(color, rgb, nframes, hc, wc_img) || !aligned16(color))
+        return fail(ctx, F3D_ERR_INVALID, "tsdf_integrate_color: " F3D_TSDF_COLOR_BAD);
+    if (nframes == 0) return F3D_OK;
+    F3D_HIP(ctx, f3d_launch_tsdf_integrate_color(tsdf, weight, color, nx, ny, nz, lo, vs, trunc, (double)max_weight, depth, depth_type, rgb, nframes, h, w,
+                                                 hc, wc_img, depth_scale, max_depth, views_dev, ctx->tsdf_grid_cap, pick(ctx, stream)));
+    return F3D_OK;
+}
+
+int f3d_tsdf_integrate_color(f3d_ctx* ctx, float* tsdf, float* weight, float* color, int nx, int ny, int nz, const double lo[3], double vs,
+                             double trunc, float max_weight, const void* depth, int depth_type, const uint8_t* rgb, int nframes, int h, int w, int hc,
+                             int wc_img, double depth_scale, double max_depth, const f3d_view* views) {
+    int rc = enter(ctx); if (rc) return rc;
+    if (!tsdf_integrate_ok(tsdf, weight, nx, ny, nz, lo, vs, trunc, max_weight, depth, depth_type, nframes, h, w, depth_scale, max_depth, views) ||
+        !tsdf_color_ok(color, rgb, nframes, hc, wc_img))
+        return fail(ctx, F3D_ERR_INVALID, "tsdf_integrate_color: " F3D_TSDF_COLOR_BAD);
+    if (nframes == 0) return F3D_OK;
+    const size_t vol = (size_t)tsdf_voxels(nx, ny, nz) * 4;
+    staging st(ctx);
+    float* dt = st.inout(tsdf, vol);
+    float* dw = st.inout(weight, vol);
+    float* dc = st.inout(color, 4 * vol);
+    const void* dd = st.in((const char*)depth, depth_bytes(depth_type, nframes, h, w));
+    const uint8_t* drgb = st.in(rgb, (size_t)nframes * hc * wc_img * 3);
+    const f3d_view* dviews = st.in(views, sizeof(f3d_view) * (size_t)nframes);
+    if (!st.rc) st.rc = f3d_tsdf_integrate_color_dev(ctx, dt, dw, dc, nx, ny, nz, lo, vs, trunc, max_weight, dd, depth_type, drgb, nframes, h, w, hc, wc_img,
+                                                     depth_scale, max_depth, dviews, ctx->stream);
+    return st.finish();
+}
+
+int f3d_tsdf_extract_colors_dev(f3d_ctx* ctx, const float* tsdf, const float* color, int nx, int ny, int nz, uint8_t* rgb, uint8_t* colored,
+                                void* stream) {
+    int rc = enter(ctx); if (rc) return rc;
+    if (!tsdf_counted(ctx, nx, ny, nz)) return fail(ctx, F3D_ERR_INVALID, "tsdf_extract_colors: call f3d_tsdf_extract_count for this volume first");
+    if (!tsdf || !color || !aligned16(color) || !rgb)
+        return fail(ctx, F3D_ERR_INVALID, "tsdf_extract_colors: bad arguments (tsdf, color and rgb not NULL, color 16-byte aligned)");
+    if (ctx->tsdf_nv == 0) return F3D_OK;
+    F3D_HIP(ctx, f3d_launch_tsdf_vert_colors(tsdf, color, nx, ny, nz, ctx->scratch[SLOT_TSDF].p, rgb, colored, ctx->tsdf_grid_cap, pick(ctx, stream)));
+    return F3D_OK;
+}
+
+int f3d_tsdf_extract_colors(f3d_ctx* ctx, const float* color, int nx, int ny, int nz, uint8_t* rgb, uint8_t* colored) {
+    int rc = enter(ctx); if (rc) return rc;
+    if (!tsdf_counted(ctx, nx, ny, nz) || !ctx->tsdf_kept)
+        return fail(ctx, F3D_ERR_INVALID, "tsdf_extract_colors: call f3d_tsdf_extract_count for this volume first");
+    if (!color || !rgb) return fail(ctx, F3D_ERR_INVALID, "tsdf_extract_colors: bad arguments (color and rgb not NULL)");
+    if (ctx->tsdf_nv == 0) return F3D_OK;
+    staging st(ctx);
+    const float* dc = st.in(color, (size_t)ctx->tsdf_n * 16);
+    uint8_t* drgb = st.out(rgb, (size_t)ctx->tsdf_nv * 3);
+    uint8_t* dcol = st.out(colored, (size_t)ctx->tsdf_nv);
+    if (!st.rc) st.rc = f3d_tsdf_extract_colors_dev(ctx, (const float*)ctx->kept[KEPT_TSDF].p, dc, nx, ny, nz, drgb, dcol, ctx->stream);
+    return st.finish();
+}
+
 // ---------------------------------------------------------------------------------------------
 // registration: TSDF raycast and point-to-plane ICP (f3d_icp.hip; the contract is in include/f3d.h)
 // ---------------------------------------------------------------------------------------------

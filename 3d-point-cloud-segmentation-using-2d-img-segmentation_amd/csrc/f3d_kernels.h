@@ -688,6 +688,14 @@ hipError_t f3d_launch_tsdf_count(const float* tsdf, const float* weight, int nx,
                                  unsigned long long* counts_host, int grid_cap, hipStream_t s);
 hipError_t f3d_launch_tsdf_fill(const float* tsdf, int nx, int ny, int nz, const double lo[3], double vs, const void* scratch, double* verts,
                                 int32_t* tris, int grid_cap, hipStream_t s);
+// the same with colour: color float32 [nz, ny, nx, 4] (16-byte aligned), rgb uint8 [F, hc, wc, 3]; the vertex colours of a counted
+// volume read the codes, the active cells and the ranks of `scratch` (colored may be NULL)
+hipError_t f3d_launch_tsdf_integrate_color(float* tsdf, float* weight, float* color, int nx, int ny, int nz, const double lo[3], double vs, double trunc,
+                                           double max_weight, const void* depth, int depth_type, const uint8_t* rgb, int nframes, int h, int w,
+                                           int hc, int wc, double depth_scale, double max_depth, const f3d_view* views_dev, int grid_cap,
+                                           hipStream_t s);
+hipError_t f3d_launch_tsdf_vert_colors(const float* tsdf, const float* color, int nx, int ny, int nz, const void* scratch, uint8_t* rgb,
+                                       uint8_t* colored, int grid_cap, hipStream_t s);
 
 // Registration (f3d_icp.hip; the contract is in include/f3d.h).  Device pointers; lo, K, qn / q and t on the host.  Enqueue only.
 // The raycast takes the quaternion already normalised (qn).  grid_cap as for the TSDF launches.

@@ -11,7 +11,9 @@
 //                     and the wave skips the frame.  The bounds are evaluated on the homogeneous pixel (h2 <= 0, h0 < 0,
 //                     h0 >= w h2, h1 < 0, h1 >= h h2, h2 > max_depth + trunc), i.e. for the depth frames' own w, h and max_depth:
 //                     the planes stored in the view were built for the view's image size and far distance, which the per-voxel
-//                     rules do not read.
+//                     rules do not read.  COLOR = true (f3d_tsdf_integrate_color) adds step 7 to the same kernel: the voxel's
+//                     (r, g, b, wc) is read lazily, one 16-byte load at its first in-band sample, and stored only if it was read.
+//   vertex colours    k_tsdf_vert_colors, shaped like k_tsdf_verts, on the codes, active cells and ranks the count pass left.
 //   extract           k_tsdf_code (observed / inside per voxel) -> k_tsdf_cells (active cells) -> scan -> k_tsdf_quads (quad mask
 //                     per voxel) -> scan; then k_tsdf_verts and k_tsdf_tris.  The scan is the project's block scan over tiles of
 //                     F3D_TSDF_SCAN_TILE counts: tile sums, a one-block scan of the sums, and the tiles again.  Totals are integer
@@ -61,11 +63,16 @@ __device__ __forceinline__ bool run_outside(const f3d_view& vw, f3d_p3 a, f3d_p3
     return behind || far || (front && (left || up || right || down));
 }
 
-template <typename T>
+// the colour arguments of k_tsdf_integrate<T, true>: the state (r, g, b, wc) per voxel and the colour images [F, hc, wc, 3]; the
+// depth-only instantiations carry none
+template <bool COLOR> struct tsdf_color_io {};
+template <> struct tsdf_color_io<true> { float4* color; const uint8_t* rgb; int hc, wc; };
+
+template <typename T, bool COLOR>
 __global__ __launch_bounds__(F3D_BLOCK) void k_tsdf_integrate(float* __restrict__ tsdf, float* __restrict__ weight, tsdf_grid g, double trunc,
                                                                double max_weight, const T* __restrict__ depth, int nframes, int h, int w,
                                                                double depth_scale, double max_depth, const f3d_view* __restrict__ views,
-                                                               int64_t nrows, int xtiles) {
+                                                               int64_t nrows, int xtiles, tsdf_color_io<COLOR> cio) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const double fw = (double)w, fh = (double)h, zmax = max_depth + trunc;
     const int64_t hw = (int64_t)h * w;
@@ -89,6 +96,9 @@ __global__ __launch_bounds__(F3D_BLOCK) void k_tsdf_integrate(float* __restrict_
         float T_old = 0.f, w_old = 0.f;
         if (live) { T_old = tsdf[lin]; w_old = weight[lin]; }
         bool touched = false;
+        // colour (step 7): the voxel's 16 bytes are read at its first in-band sample and written back only if there was one
+        [[maybe_unused]] float4 C_old = make_float4(0.f, 0.f, 0.f, 0.f);
+        [[maybe_unused]] bool c_read = false;
         for (int f0 = 0; f0 < nframes; f0 += 64) {
           // the cull of 64 frames at once, one per lane (ca, cb are wave-uniform); the survivors in ascending order
           unsigned long long todo = __ballot(f0 + lane < nframes && !run_outside(views[min(f0 + lane, nframes - 1)], ca, cb, fw, fh, zmax));
@@ -106,6 +116,18 @@ __global__ __launch_bounds__(F3D_BLOCK) void k_tsdf_integrate(float* __restrict_
             const double sdf = d - hp.z;
             if (sdf < -trunc) continue;
             double val = sdf / trunc;
+            if constexpr (COLOR) {
+                if (!(val > 1.0)) {
+                    if (!c_read) { C_old = cio.color[lin]; c_read = true; }
+                    const int64_t uc = (int64_t)u * cio.wc / w, vc = (int64_t)v * cio.hc / h;
+                    const uint8_t* pix = cio.rgb + (((int64_t)f * cio.hc + vc) * cio.wc + uc) * 3;
+                    const double wc_old = (double)C_old.w;
+                    C_old.x = (float)(((double)C_old.x * wc_old + (double)pix[0]) / (wc_old + 1.0));
+                    C_old.y = (float)(((double)C_old.y * wc_old + (double)pix[1]) / (wc_old + 1.0));
+                    C_old.z = (float)(((double)C_old.z * wc_old + (double)pix[2]) / (wc_old + 1.0));
+                    C_old.w = (float)fmin(wc_old + 1.0, max_weight);
+                }
+            }
             if (val > 1.0) val = 1.0;
             const double wo = (double)w_old;
             T_old = (float)(((double)T_old * wo + val) / (wo + 1.0));
@@ -114,6 +136,7 @@ __global__ __launch_bounds__(F3D_BLOCK) void k_tsdf_integrate(float* __restrict_
           }
         }
         if (live && touched) { tsdf[lin] = T_old; weight[lin] = w_old; }
+        if constexpr (COLOR) { if (live && c_read) cio.color[lin] = C_old; }
     }
 }
 
@@ -255,6 +278,55 @@ __global__ __launch_bounds__(F3D_BLOCK) void k_tsdf_verts(const float* __restric
     }
 }
 
+// colour of every active cell's vertex: the mean over its crossing edges (ascending e, L[a] as in k_tsdf_verts) of the colour at the
+// crossing, taken from the ends that have one (wc > 0): both -> interpolated, one -> that end's, neither -> the edge adds nothing
+__global__ __launch_bounds__(F3D_BLOCK) void k_tsdf_vert_colors(const float* __restrict__ tsdf, const float4* __restrict__ color,
+                                                                 const uint8_t* __restrict__ code, const uint8_t* __restrict__ act,
+                                                                 const uint32_t* __restrict__ rank, int nx, int ny, int64_t n,
+                                                                 uint8_t* __restrict__ rgb, uint8_t* __restrict__ colored) {
+    const int64_t st[3] = {1, nx, (int64_t)nx * ny};
+    for (int64_t lin = (int64_t)blockIdx.x * F3D_BLOCK + threadIdx.x; lin < n; lin += (int64_t)gridDim.x * F3D_BLOCK) {
+        if (!act[lin]) continue;
+        double sum[3] = {0.0, 0.0, 0.0};
+        int count = 0;
+#pragma unroll
+        for (int a = 0; a < 3; ++a) {
+            const int b = (a + 1) % 3, c = (a + 2) % 3;
+#pragma unroll
+            for (int o = 0; o < 4; ++o) {
+                const int ob = o & 1, oc = o >> 1;
+                const int64_t at0 = lin + ob * st[b] + oc * st[c], at1 = at0 + st[a];
+                if (!((code[at0] ^ code[at1]) & CODE_INSIDE)) continue;
+                const float4 c0 = color[at0], c1 = color[at1];
+                const bool has0 = c0.w > 0.f, has1 = c1.w > 0.f;
+                if (!has0 && !has1) continue;
+                double col[3];
+                if (has0 && has1) {
+                    const double s0 = (double)tsdf[at0], s1 = (double)tsdf[at1];
+                    const double L = s0 / (s0 - s1);
+                    col[0] = (double)c0.x + L * ((double)c1.x - (double)c0.x);
+                    col[1] = (double)c0.y + L * ((double)c1.y - (double)c0.y);
+                    col[2] = (double)c0.z + L * ((double)c1.z - (double)c0.z);
+                } else {
+                    const float4 e = has0 ? c0 : c1;
+                    col[0] = (double)e.x; col[1] = (double)e.y; col[2] = (double)e.z;
+                }
+                sum[0] = sum[0] + col[0]; sum[1] = sum[1] + col[1]; sum[2] = sum[2] + col[2];
+                ++count;
+            }
+        }
+        const int64_t id = rank[lin];
+#pragma unroll
+        for (int ch = 0; ch < 3; ++ch) {
+            double m = count ? sum[ch] / (double)count : 0.0;
+            m = m > 0.0 ? m : 0.0;                                              // NaN -> 0
+            m = m < 255.0 ? m : 255.0;
+            rgb[3 * id + ch] = (uint8_t)floor(m + 0.5);
+        }
+        if (colored) colored[id] = count > 0;
+    }
+}
+
 __global__ __launch_bounds__(F3D_BLOCK) void k_tsdf_tris(const uint8_t* __restrict__ code, const uint8_t* __restrict__ qmask, const uint32_t* __restrict__ qoff,
                                                           const uint32_t* __restrict__ rank, int nx, int ny, int64_t n, int32_t* __restrict__ tris) {
     const int64_t st[3] = {1, nx, (int64_t)nx * ny};
@@ -311,6 +383,27 @@ tsdf_grid grid_of(int nx, int ny, int nz, const double lo[3], double vs) {
     return g;
 }
 
+template <bool COLOR>
+hipError_t launch_integrate(float* tsdf, float* weight, int nx, int ny, int nz, const double lo[3], double vs, double trunc, double max_weight,
+                            const void* depth, int depth_type, int nframes, int h, int w, double depth_scale, double max_depth,
+                            const f3d_view* views_dev, tsdf_color_io<COLOR> cio, int grid_cap, hipStream_t s) {
+    const tsdf_grid g = grid_of(nx, ny, nz, lo, vs);
+    const int64_t nrows = (int64_t)ny * nz;
+    const int xtiles = (nx + 63) / 64;
+    const int64_t ntiles = ((nrows + TSDF_ROWS - 1) / TSDF_ROWS) * xtiles;
+    const dim3 gr(capped(ntiles, (int64_t)F3D_GRID_CAP * 16, grid_cap)), b(F3D_BLOCK);
+    if (depth_type == F3D_DEPTH_U16)
+        hipLaunchKernelGGL((k_tsdf_integrate<uint16_t, COLOR>), gr, b, 0, s, tsdf, weight, g, trunc, max_weight, (const uint16_t*)depth, nframes, h, w,
+                           depth_scale, max_depth, views_dev, nrows, xtiles, cio);
+    else if (depth_type == F3D_DEPTH_F32)
+        hipLaunchKernelGGL((k_tsdf_integrate<float, COLOR>), gr, b, 0, s, tsdf, weight, g, trunc, max_weight, (const float*)depth, nframes, h, w,
+                           depth_scale, max_depth, views_dev, nrows, xtiles, cio);
+    else
+        hipLaunchKernelGGL((k_tsdf_integrate<double, COLOR>), gr, b, 0, s, tsdf, weight, g, trunc, max_weight, (const double*)depth, nframes, h, w,
+                           depth_scale, max_depth, views_dev, nrows, xtiles, cio);
+    return hipGetLastError();
+}
+
 }  // namespace
 
 size_t f3d_tsdf_scratch_bytes(int64_t nvoxels) { return tsdf_layout(nvoxels).bytes; }
@@ -318,21 +411,17 @@ size_t f3d_tsdf_scratch_bytes(int64_t nvoxels) { return tsdf_layout(nvoxels).byt
 hipError_t f3d_launch_tsdf_integrate(float* tsdf, float* weight, int nx, int ny, int nz, const double lo[3], double vs, double trunc, double max_weight,
                                      const void* depth, int depth_type, int nframes, int h, int w, double depth_scale, double max_depth,
                                      const f3d_view* views_dev, int grid_cap, hipStream_t s) {
-    const tsdf_grid g = grid_of(nx, ny, nz, lo, vs);
-    const int64_t nrows = (int64_t)ny * nz;
-    const int xtiles = (nx + 63) / 64;
-    const int64_t ntiles = ((nrows + TSDF_ROWS - 1) / TSDF_ROWS) * xtiles;
-    const dim3 gr(capped(ntiles, (int64_t)F3D_GRID_CAP * 16, grid_cap)), b(F3D_BLOCK);
-    if (depth_type == F3D_DEPTH_U16)
-        hipLaunchKernelGGL(k_tsdf_integrate<uint16_t>, gr, b, 0, s, tsdf, weight, g, trunc, max_weight, (const uint16_t*)depth, nframes, h, w, depth_scale,
-                           max_depth, views_dev, nrows, xtiles);
-    else if (depth_type == F3D_DEPTH_F32)
-        hipLaunchKernelGGL(k_tsdf_integrate<float>, gr, b, 0, s, tsdf, weight, g, trunc, max_weight, (const float*)depth, nframes, h, w, depth_scale,
-                           max_depth, views_dev, nrows, xtiles);
-    else
-        hipLaunchKernelGGL(k_tsdf_integrate<double>, gr, b, 0, s, tsdf, weight, g, trunc, max_weight, (const double*)depth, nframes, h, w, depth_scale,
-                           max_depth, views_dev, nrows, xtiles);
-    return hipGetLastError();
+    return launch_integrate<false>(tsdf, weight, nx, ny, nz, lo, vs, trunc, max_weight, depth, depth_type, nframes, h, w, depth_scale, max_depth,
+                                   views_dev, tsdf_color_io<false>{}, grid_cap, s);
+}
+
+hipError_t f3d_launch_tsdf_integrate_color(float* tsdf, float* weight, float* color, int nx, int ny, int nz, const double lo[3], double vs, double trunc,
+                                           double max_weight, const void* depth, int depth_type, const uint8_t* rgb, int nframes, int h, int w,
+                                           int hc, int wc, double depth_scale, double max_depth, const f3d_view* views_dev, int grid_cap,
+                                           hipStream_t s) {
+    const tsdf_color_io<true> cio = {(float4*)color, rgb, hc, wc};
+    return launch_integrate<true>(tsdf, weight, nx, ny, nz, lo, vs, trunc, max_weight, depth, depth_type, nframes, h, w, depth_scale, max_depth,
+                                  views_dev, cio, grid_cap, s);
 }
 
 hipError_t f3d_launch_tsdf_count(const float* tsdf, const float* weight, int nx, int ny, int nz, float min_weight, void* scratch,
@@ -364,5 +453,17 @@ hipError_t f3d_launch_tsdf_fill(const float* tsdf, int nx, int ny, int nz, const
     const dim3 gr(capped((n + F3D_BLOCK - 1) / F3D_BLOCK, F3D_GRID_CAP * 4, grid_cap)), b(F3D_BLOCK);
     if (verts) hipLaunchKernelGGL(k_tsdf_verts, gr, b, 0, s, tsdf, code, act, rank, grid_of(nx, ny, nz, lo, vs), n, verts);
     if (tris) hipLaunchKernelGGL(k_tsdf_tris, gr, b, 0, s, code, qmask, qoff, rank, nx, ny, n, tris);
+    return hipGetLastError();
+}
+
+hipError_t f3d_launch_tsdf_vert_colors(const float* tsdf, const float* color, int nx, int ny, int nz, const void* scratch, uint8_t* rgb,
+                                       uint8_t* colored, int grid_cap, hipStream_t s) {
+    const int64_t n = (int64_t)nx * ny * nz;
+    const tsdf_scratch l = tsdf_layout(n);
+    const char* base = (const char*)scratch;
+    const uint8_t *code = (const uint8_t*)(base + l.code), *act = (const uint8_t*)(base + l.act);
+    const uint32_t* rank = (const uint32_t*)(base + l.rank);
+    const dim3 gr(capped((n + F3D_BLOCK - 1) / F3D_BLOCK, F3D_GRID_CAP * 4, grid_cap)), b(F3D_BLOCK);
+    hipLaunchKernelGGL(k_tsdf_vert_colors, gr, b, 0, s, tsdf, (const float4*)color, code, act, rank, nx, ny, n, rgb, colored);
     return hipGetLastError();
 }

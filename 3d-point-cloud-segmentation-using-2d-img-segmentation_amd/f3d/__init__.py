@@ -241,6 +241,10 @@ def library():
         'f3d_tsdf_extract_fill': (i32, [vp, i32, i32, i32, vp, dbl, vp, vp]),
         'f3d_tsdf_extract_count_dev': (i32, [vp, vp, vp, i32, i32, i32, flt, vp, vp, vp]),
         'f3d_tsdf_extract_fill_dev': (i32, [vp, vp, i32, i32, i32, vp, dbl, vp, vp, vp]),
+        'f3d_tsdf_integrate_color': (i32, [vp, vp, vp, vp, i32, i32, i32, vp, dbl, dbl, flt, vp, i32, vp, i32, i32, i32, i32, i32, dbl, dbl, vp]),
+        'f3d_tsdf_integrate_color_dev': (i32, [vp, vp, vp, vp, i32, i32, i32, vp, dbl, dbl, flt, vp, i32, vp, i32, i32, i32, i32, i32, dbl, dbl, vp, vp]),
+        'f3d_tsdf_extract_colors': (i32, [vp, vp, i32, i32, i32, vp, vp]),
+        'f3d_tsdf_extract_colors_dev': (i32, [vp, vp, vp, i32, i32, i32, vp, vp, vp]),
         'f3d_ctx_reserve_tsdf': (i32, [vp, i64]),
         'f3d_debug_tsdf_grid_cap': (i32, [vp, i32]),
         'f3d_debug_grid_cap': (i32, [vp, i32]),
@@ -430,6 +434,27 @@ def _tsdf_frames(lo, depths, views):
     if len(views) != len(d):
         raise ValueError(f'{len(views)} views for {len(d)} depth frames')
     return _f64(lo, (3,)), d, depth_code(d), views
+
+
+def _tsdf_color(color, shape, writeable=True):
+    """The colour state of a TSDF volume whose tsdf has `shape`: a C-contiguous float32 [nz, ny, nx, 4] NumPy array."""
+    if not isinstance(color, np.ndarray) or color.dtype != np.float32:
+        raise TypeError('color must be a float32 NumPy array')
+    if color.shape != tuple(shape) + (4,) or not color.flags.c_contiguous or (writeable and not color.flags.writeable):
+        raise ValueError(f'color must be a writeable C-contiguous float32 {tuple(shape) + (4,)} array, got {color.shape}')
+    return color
+
+
+def _tsdf_rgb(rgb, nframes):
+    """The colour images of a tsdf_integrate_color call: uint8 [F, hc, wc, 3], C-contiguous, one per depth frame."""
+    rgb = np.asarray(rgb)
+    if rgb.dtype != np.uint8:
+        raise TypeError(f'colour images must be uint8, got {rgb.dtype}')
+    if rgb.ndim != 4 or rgb.shape[3] != 3 or rgb.shape[1] < 1 or rgb.shape[2] < 1:
+        raise ValueError(f'colour images must be [F, hc, wc, 3] with pixels, got {rgb.shape}')
+    if rgb.shape[0] != nframes:
+        raise ValueError(f'{rgb.shape[0]} colour images for {nframes} depth frames')
+    return np.ascontiguousarray(rgb)
 
 
 def _icp_arrays(depth, K, q_wxyz, t, model_vertex, model_normal, hm, wm, model_view):
@@ -1267,6 +1292,31 @@ class Context:
         self._check(self._lib.f3d_tsdf_extract_fill(self._h, nx, ny, nz, _ptr(lo), float(voxel), _ptr(verts), _ptr(tris)))
         return verts, tris
 
+    def tsdf_integrate_color(self, tsdf, weight, color, lo, voxel, trunc, max_weight, depths, rgb, views, depth_scale=1.0, max_depth=10.0):
+        """tsdf_integrate with colour (f3d.h f3d_tsdf_integrate_color): color is the C-contiguous float32 [nz, ny, nx, 4] state
+        (r, g, b, wc), updated IN PLACE; rgb the uint8 [F, hc, wc, 3] colour images, one per depth frame, of any size."""
+        nz, ny, nx = _tsdf_state(tsdf, weight)
+        _tsdf_color(color, (nz, ny, nx))
+        lo, d, code, views = _tsdf_frames(lo, depths, views)
+        rgb = _tsdf_rgb(rgb, d.shape[0])
+        self._check(self._lib.f3d_tsdf_integrate_color(self._h, _ptr(tsdf), _ptr(weight), _ptr(color), nx, ny, nz, _ptr(lo), float(voxel), float(trunc),
+                                                       float(max_weight), _ptr(d), code, _ptr(rgb), d.shape[0], d.shape[1], d.shape[2], rgb.shape[1],
+                                                       rgb.shape[2], float(depth_scale), float(max_depth), _ptr(views)))
+
+    def tsdf_extract_colors(self, tsdf, weight, color, lo, voxel, min_weight=1.0):
+        """tsdf_extract with vertex colours (f3d.h f3d_tsdf_extract_count -> _fill, _colors) -> (vertices float64 [V, 3], triangles
+        int32 [M, 3], rgb uint8 [V, 3], colored uint8 [V]: 0 where no end of a crossing edge of the vertex's cell has a colour)."""
+        nz, ny, nx = _tsdf_state(tsdf, weight)
+        _tsdf_color(color, (nz, ny, nx), writeable=False)
+        lo = _f64(lo, (3,))
+        nv, nt = C.c_int64(0), C.c_int64(0)
+        self._check(self._lib.f3d_tsdf_extract_count(self._h, _ptr(tsdf), _ptr(weight), nx, ny, nz, float(min_weight), C.byref(nv), C.byref(nt)))
+        verts, tris = np.empty((nv.value, 3), np.float64), np.empty((nt.value, 3), np.int32)
+        rgb, colored = np.empty((nv.value, 3), np.uint8), np.empty(nv.value, np.uint8)
+        self._check(self._lib.f3d_tsdf_extract_fill(self._h, nx, ny, nz, _ptr(lo), float(voxel), _ptr(verts), _ptr(tris)))
+        self._check(self._lib.f3d_tsdf_extract_colors(self._h, _ptr(color), nx, ny, nz, _ptr(rgb), _ptr(colored)))
+        return verts, tris, rgb, colored
+
     def reserve_icp(self, npixels):
         """Size the scratch of icp_sums_dev / icp_dev for source frames of up to npixels pixels."""
         self._check(self._lib.f3d_ctx_reserve_icp(self._h, int(npixels)))
@@ -1594,6 +1644,22 @@ class Context:
         lo = _f64(lo, (3,))
         nx, ny, nz = (int(x) for x in dims)
         self._check(self._lib.f3d_tsdf_extract_fill_dev(self._h, tsdf_ptr, nx, ny, nz, _ptr(lo), float(voxel), verts_ptr, tris_ptr, stream))
+
+    def tsdf_integrate_color_dev(self, tsdf_ptr, weight_ptr, color_ptr, dims, lo, voxel, trunc, max_weight, depth_ptr, depth_type, rgb_ptr, nframes,
+                                 h, w, hc, wc, depth_scale, max_depth, views_ptr, stream=None):
+        """tsdf_integrate_dev with the colour state [nz, ny, nx, 4] (16-byte aligned) and the colour images uint8 [F, hc, wc, 3], device
+        pointers both (f3d.h f3d_tsdf_integrate_color_dev).  Enqueue only."""
+        lo = _f64(lo, (3,))
+        nx, ny, nz = (int(x) for x in dims)
+        self._check(self._lib.f3d_tsdf_integrate_color_dev(self._h, tsdf_ptr, weight_ptr, color_ptr, nx, ny, nz, _ptr(lo), float(voxel), float(trunc),
+                                                           float(max_weight), depth_ptr, int(depth_type), rgb_ptr, int(nframes), int(h), int(w),
+                                                           int(hc), int(wc), float(depth_scale), float(max_depth), views_ptr, stream))
+
+    def tsdf_extract_colors_dev(self, tsdf_ptr, color_ptr, dims, rgb_ptr, colored_ptr=None, stream=None):
+        """Vertex colours of the volume counted last: rgb uint8 [nv, 3], colored uint8 [nv] or None (f3d.h f3d_tsdf_extract_colors_dev).
+        Enqueue only."""
+        nx, ny, nz = (int(x) for x in dims)
+        self._check(self._lib.f3d_tsdf_extract_colors_dev(self._h, tsdf_ptr, color_ptr, nx, ny, nz, rgb_ptr, colored_ptr, stream))
 
     def tsdf_raycast_dev(self, tsdf_ptr, weight_ptr, dims, lo, voxel, min_weight, K, q_wxyz, t, h, w, near, step, nsteps, vertex_ptr, normal_ptr,
                          depth_ptr, stream=None):

@@ -1166,7 +1166,20 @@ int f3d_estimate_normals_batch_dev(f3d_ctx* ctx, const double* xyz, int nframes,
  *                5. T = (float)(((double)T_old * (double)w_old + val) / ((double)w_old + 1.0)).
  *                6. w = (float)min((double)w_old + 1.0, (double)max_weight).
  *              The five frustum planes of the view play no part in the result.  trunc > 0; max_weight in [1, 2^24].
- *   extract    a voxel is observed iff weight >= min_weight (min_weight >= 1) and inside iff it is observed and tsdf < 0 (+0.0 and
+ *   colour     f3d_tsdf_integrate_color: the same with a third caller-owned state array, color float32 [nz, ny, nx, 4], channels
+ *              (r, g, b, wc) on a 0..255 scale, wc the colour's own weight; a fresh volume is all zeros; 16 bytes per voxel, 16-byte
+ *              aligned (the _dev form refuses another pointer).  Colour images rgb uint8 [F, hc, wc_img, 3], one per depth frame;
+ *              hc, wc_img > 0 are independent of h, w, hc * wc_img < 2^31.  The colour pixel of depth pixel (u, v) is
+ *              uc = (int64)u * wc_img / w, vc = (int64)v * hc / h (the integer rule of f3d_fuse_features).  Steps 1 - 6 are those above;
+ *              for a frame that has passed step 4, with val as computed there before the clamp:
+ *                7. the voxel is in band iff !(val > 1.0).  If it is, for each channel with pix = rgb[f, vc, uc, channel]:
+ *                   C = (float)(((double)C_old * (double)wc_old + (double)pix) / ((double)wc_old + 1.0)); then
+ *                   wc = (float)min((double)wc_old + 1.0, (double)max_weight).
+ *              Frames apply in ascending f.  tsdf and weight come out bit-identical to f3d_tsdf_integrate on the same inputs.  A voxel
+ *              that is never in band keeps its 16 bytes unread and unwritten.  The colour has a weight of its own because a voxel just
+ *              in front of a silhouette is updated, with the clamped 1.0, by every frame that sees the background far behind it
+ *              through the same pixel: those frames must not give it the background's colour.
+ *   extract   a voxel is observed iff weight >= min_weight (min_weight >= 1) and inside iff it is observed and tsdf < 0 (+0.0 and
  *              -0.0 are outside).  Cell (i, j, k), 0 <= idx_a <= n_a - 2, has the 8 voxels idx + {0, 1}^3 as corners and is active
  *              iff all 8 are observed and they are not all on one side.
  *   vertex     of an active cell.  For an axis a let (b, c) be the next two axes cyclically (x -> (y, z), y -> (z, x), z -> (x, y)).
@@ -1181,18 +1194,26 @@ int f3d_estimate_normals_batch_dev(f3d_ctx* ctx, const double* xyz, int nframes,
  *              D = p - e_b.  Each such edge gives one quad, (A, B, C, D) when p is inside (the normal points along +a, from inside to
  *              outside), else (A, D, C, B); it splits into the triangles (q0, q1, q2) and (q0, q2, q3).  The quads come in
  *              ascending 3 * lin(p) + a, the two triangles of a quad are consecutive.
+ *   vertex colours  f3d_tsdf_extract_colors, a third member of the count -> fill sequence (before, after or without the fill): for an
+ *              active cell, walk its crossing edges in ascending e with L[a] = s0 / (s0 - s1) exactly as the vertex rule does; c0, c1
+ *              the colour state at the edge's two ends.  Both ends with wc > 0: the edge adds col = c0 + L[a] * (c1 - c0) per channel
+ *              (float64, as written); one end: that end's colour; neither: nothing.  sum starts at 0.0 per channel,
+ *              m = sum / (double)count over the contributing edges, rgb uint8 [nv, 3] = (uint8)floor(min(max(m, 0), 255) + 0.5)
+ *              (a NaN m gives 0); the optional colored uint8 [nv] is 1 where count > 0, else 0 with rgb = 0.  Vertex ids are those of
+ *              the fill.  It needs no scratch beyond the count's.
  * Outputs: verts float64 [nv, 3], tris int32 [nt, 3] of vertex ids; nv, nt < 2^31, otherwise F3D_ERR_INVALID.  The result depends on
  * nothing but the state, min_weight, lo and vs: not on the launch shape, timing or the scan's tiling (tiles of F3D_TSDF_SCAN_TILE counts,
  * scanned by blocks of 256).
  * f3d_tsdf_extract_count -> f3d_tsdf_extract_fill is a sequence (see the preamble): the cell ranks and the quad offsets stay in
  * context scratch, the host-pointer count also keeps its copy of tsdf; the sequence ends where count is called again.  The totals come
  * back like those of f3d_radius_graph_count_dev: through host pointers, after one synchronisation of the stream.  The _dev fill takes
- * the same tsdf and dims again.  Either output of fill may be NULL.
+ * the same tsdf and dims again, and so does f3d_tsdf_extract_colors_dev.  Either output of fill may be NULL.
  * F3D_ERR_INVALID, with nothing written (but for the one case named last): NULLs; non-positive dims or a product >= 2^31; vs, trunc, depth_scale or max_depth not finite
  * and positive; max_weight outside [1, 2^24]; min_weight < 1 (or NaN); an unknown depth type; h, w <= 0 or nframes < 0; a fill without
  * its count, or with other dims; a count that finds 2^30 quads or more (known only after the passes have run: *nv and *nt are then 0 and
  * the sequence is ended).  Non-finite depths or poses are no error: they contribute nothing.  nframes == 0 is a no-op; a volume
- * without an active cell gives nv = nt = 0.
+ * without an active cell gives nv = nt = 0.  The colour entries add: a NULL color or rgb; hc or wc_img <= 0 or hc * wc_img >= 2^31; a
+ * device color that is not 16-byte aligned; f3d_tsdf_extract_colors without its count or with other dims.  nv == 0 is a no-op there.
  * Scratch: 11 bytes per voxel + 4 per scan tile; f3d_ctx_reserve_tsdf(nvoxels) sizes it, and a strict context then allocates nothing in
  * the three _dev entries.  Reserving may move the scratch, so it ends a counted sequence: count again before the fill.
  * f3d_debug_tsdf_grid_cap (test hook): blocks > 0 caps the grid of every grid-stride TSDF launch of the context at that many blocks, so that
@@ -1225,6 +1246,18 @@ int f3d_tsdf_extract_count_dev(f3d_ctx* ctx, const float* tsdf, const float* wei
                                int64_t* nv /*host*/, int64_t* nt /*host*/, void* stream);
 int f3d_tsdf_extract_fill_dev(f3d_ctx* ctx, const float* tsdf, int nx, int ny, int nz, const double lo[3] /*host*/, double vs,
                               double* verts, int32_t* tris, void* stream);
+int f3d_tsdf_integrate_color(f3d_ctx* ctx, float* tsdf, float* weight, float* color /*[nz,ny,nx,4]*/, int nx, int ny, int nz,
+                             const double lo[3], double vs, double trunc, float max_weight, const void* depth, int depth_type,
+                             const uint8_t* rgb /*[F,hc,wc_img,3]*/, int nframes, int h, int w, int hc, int wc_img, double depth_scale,
+                             double max_depth, const f3d_view* views);
+int f3d_tsdf_integrate_color_dev(f3d_ctx* ctx, float* tsdf, float* weight, float* color, int nx, int ny, int nz,
+                                 const double lo[3] /*host*/, double vs, double trunc, float max_weight, const void* depth, int depth_type,
+                                 const uint8_t* rgb, int nframes, int h, int w, int hc, int wc_img, double depth_scale, double max_depth,
+                                 const f3d_view* views_dev /*device [F]*/, void* stream);
+int f3d_tsdf_extract_colors(f3d_ctx* ctx, const float* color, int nx, int ny, int nz, uint8_t* rgb /*[nv,3]*/,
+                            uint8_t* colored /*[nv] or NULL*/);
+int f3d_tsdf_extract_colors_dev(f3d_ctx* ctx, const float* tsdf, const float* color, int nx, int ny, int nz, uint8_t* rgb,
+                                uint8_t* colored, void* stream);
 int f3d_ctx_reserve_tsdf(f3d_ctx* ctx, int64_t nvoxels);
 int f3d_debug_tsdf_grid_cap(f3d_ctx* ctx, int blocks);
 int f3d_debug_grid_cap(f3d_ctx* ctx, int blocks);
