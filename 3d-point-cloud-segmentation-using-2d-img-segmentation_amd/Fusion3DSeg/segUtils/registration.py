@@ -7,10 +7,16 @@ frame to such maps by projective point-to-plane ICP, ``track_frames`` does both 
 pose (frame-to-model tracking).  All of it runs on the GPU (f3d_tsdf_raycast, f3d_icp_sums, f3d_icp: include/f3d.h states the
 contract, tests/icp_ref.py restates it in NumPy).
 
+Depth cannot see a motion that maps the geometry onto itself: along a wall, about the axis of a round object.  The colour images can.
+``raycast(..., colors=True)`` renders the colour of a volume built with ``color=True`` along with its maps, ``icp_sums`` / ``icp`` take
+a photometric term (``color=``, ``model_intensity=``, ``color_weight=``: the intensity residual between the frame's colour image and
+the model's intensity map, weighted into the same 6 x 6 system), and ``track_frames(..., colors=..., color_weight=...)`` uses both
+(f3d_tsdf_raycast_color, f3d_icp_color_sums, f3d_icp_color; restated in tests/icp_color_ref.py).
+
 A pixel (u, v) stands for the ray through (u + 0.5, v + 0.5), the convention of ``TSDFVolume.integrate``.  NumPy arrays in, NumPy
 arrays back; device tensors in, or a volume that is on the device, keep everything on the GPU, ordered with torch's current stream.
-There is no CPU fallback.  Out of scope: image pyramids, colour or photometric terms, robust weights, loop closure, and
-re-unprojecting ``Fusion``'s stored frames at refined poses.
+There is no CPU fallback.  Out of scope: image pyramids, robust weights, an intensity-difference gate, exposure compensation, colour
+from anything but the volume, loop closure, and re-unprojecting ``Fusion``'s stored frames at refined poses.
 """
 import math
 
@@ -58,12 +64,16 @@ def _march(volume, near, far, step):
     return near, step, nsteps
 
 
-def raycast(volume, K, wxyz, t, hw, min_weight=1, near=0.0, far=10.0, step=None):
+def raycast(volume, K, wxyz, t, hw, min_weight=1, near=0.0, far=10.0, step=None, colors=False):
     """Model maps of ``volume`` (a ``TSDFVolume``) seen from the camera->world pose (``wxyz``, ``t``) with intrinsics ``K`` in an
     image of ``hw = (h, w)`` pixels -> (vertex float64 [h, w, 3] and unit normal float64 [h, w, 3] in the world frame, depth float64
     [h, w] along the camera z axis).  Rays are sampled every ``step`` (default: the voxel edge) from ``near`` to ``far``; only voxels seen at
-    least ``min_weight`` times count.  A pixel without a hit has NaN rows and depth 0.  Device tensors for a volume on the device."""
+    least ``min_weight`` times count.  A pixel without a hit has NaN rows and depth 0.  Device tensors for a volume on the device.
+    ``colors=True``, for a volume built with ``color=True``: two more maps after the three, rgb float64 [h, w, 3] on the 0..255 scale
+    and intensity float64 [h, w] = (0.299 R + 0.587 G + 0.114 B) / 255, NaN where a pixel has no hit or its hit no colour."""
     K, q, t = _pose(K, wxyz, t)
+    if colors and volume.color is None:
+        raise ValueError('colors=True needs a volume built with color=True')
     h, w = (int(x) for x in hw)
     if h < 1 or w < 1 or h * w >= 1 << 31:
         raise ValueError(f'hw must be two positive sizes with a product below 2^31, got {(h, w)}')
@@ -71,17 +81,27 @@ def raycast(volume, K, wxyz, t, hw, min_weight=1, near=0.0, far=10.0, step=None)
     near, step, nsteps = _march(volume, near, far, step)
     ctx = f3d.default_context()
     if not volume.on_device:
+        if colors:
+            vertex, normal, depth, rgb, intensity = ctx.tsdf_raycast_color(volume.tsdf, volume.weight, volume.color, volume.lo, volume.voxel, min_weight,
+                                                                           K, q, t, h, w, near, step, nsteps)
+            return vertex.reshape(h, w, 3), normal.reshape(h, w, 3), depth.reshape(h, w), rgb.reshape(h, w, 3), intensity.reshape(h, w)
         vertex, normal, depth = ctx.tsdf_raycast(volume.tsdf, volume.weight, volume.lo, volume.voxel, min_weight, K, q, t, h, w, near, step, nsteps)
         return vertex.reshape(h, w, 3), normal.reshape(h, w, 3), depth.reshape(h, w)
     torch, dev = torch_device(ctx, 'raycast')
     with torch.cuda.device(dev), work_stream(dev) as work:
         vertex, normal = (torch.empty((h, w, 3), dtype=torch.float64, device=dev) for _ in range(2))
         depth = torch.empty((h, w), dtype=torch.float64, device=dev)
-        ctx.tsdf_raycast_dev(volume.tsdf.data_ptr(), volume.weight.data_ptr(), volume.dims, volume.lo, volume.voxel, min_weight, K, q, t, h, w, near,
-                             step, nsteps, vertex.data_ptr(), normal.data_ptr(), depth.data_ptr(), work.cuda_stream)
-    for x in (vertex, normal, depth):
+        out = (vertex, normal, depth)
+        if colors:
+            out += (torch.empty((h, w, 3), dtype=torch.float64, device=dev), torch.empty((h, w), dtype=torch.float64, device=dev))
+            ctx.tsdf_raycast_color_dev(volume.tsdf.data_ptr(), volume.weight.data_ptr(), volume.color.data_ptr(), volume.dims, volume.lo, volume.voxel,
+                                       min_weight, K, q, t, h, w, near, step, nsteps, *(x.data_ptr() for x in out), work.cuda_stream)
+        else:
+            ctx.tsdf_raycast_dev(volume.tsdf.data_ptr(), volume.weight.data_ptr(), volume.dims, volume.lo, volume.voxel, min_weight, K, q, t, h, w,
+                                 near, step, nsteps, vertex.data_ptr(), normal.data_ptr(), depth.data_ptr(), work.cuda_stream)
+    for x in out:
         x.record_stream(torch.cuda.current_stream(dev))
-    return vertex, normal, depth
+    return out
 
 
 def _icp_args(depth, K, wxyz, t, model_vertex, model_normal, model_K, model_wxyz, model_t, max_dist, depth_scale, max_depth):
@@ -102,6 +122,26 @@ def _icp_args(depth, K, wxyz, t, model_vertex, model_normal, model_K, model_wxyz
     return depth, code, K, q, t, model_vertex, model_normal, shape[0], shape[1], view, max_dist, depth_scale, max_depth
 
 
+def _color_args(color, model_intensity, color_weight, hm, wm):
+    """The checked colour arguments of icp_sums / icp, before any device is touched: None when none of the three is given, else
+    (color uint8 [hc, wc, 3], model_intensity float64 [hm, wm], color_weight); some but not all of them is a ValueError."""
+    given = [x is not None for x in (color, model_intensity, color_weight)]
+    if not any(given):
+        return None
+    if not all(given):
+        raise ValueError('color, model_intensity and color_weight go together: pass all three or none')
+    color, model_intensity = (a if on_device(a) else np.asarray(a) for a in (color, model_intensity))
+    if len(model_intensity.shape) != 2:
+        raise ValueError(f'model_intensity must be [hm, wm], got {tuple(model_intensity.shape)}')
+    _, _, color_weight = f3d.icp_color_check(model_intensity, color, color_weight, hm, wm)
+    return color, model_intensity, color_weight
+
+
+def _color_to_device(torch, dev, color, model_intensity):
+    as_tensor = lambda a: a if on_device(a) else torch.from_numpy(np.ascontiguousarray(a))     # noqa: E731
+    return as_tensor(color).to(dev).contiguous(), as_tensor(model_intensity).to(dev).contiguous()
+
+
 def _rounds(iterations, min_pairs):
     iterations, min_pairs = int(iterations), int(min_pairs)
     if iterations < 1 or min_pairs < 6:
@@ -110,30 +150,51 @@ def _rounds(iterations, min_pairs):
 
 
 def _info(stats, status, xp=np):
-    """status, counts and rms per round from the stats rows {count, sum r^2, status}."""
-    counts = stats[:, 0]
-    return {'status': int(status), 'counts': counts, 'rms': xp.sqrt(stats[:, 1] / xp.where(counts > 0, counts, xp.ones_like(counts)))}
+    """status, counts and rms per round from the stats rows {count, sum r^2, status}; with the two colour columns {colour count, sum rc^2}
+    color_counts and color_rms as well."""
+    rms = lambda n, ss: xp.sqrt(ss / xp.where(n > 0, n, xp.ones_like(n)))                      # noqa: E731
+    info = {'status': int(status), 'counts': stats[:, 0], 'rms': rms(stats[:, 0], stats[:, 1])}
+    if stats.shape[1] == 5:
+        info.update(color_counts=stats[:, 3], color_rms=rms(stats[:, 3], stats[:, 4]))
+    return info
 
 
-def icp_sums(depth, K, wxyz, t, model_vertex, model_normal, model_K, model_wxyz, model_t, max_dist=0.1, depth_scale=1.0, max_depth=10):
+def icp_sums(depth, K, wxyz, t, model_vertex, model_normal, model_K, model_wxyz, model_t, max_dist=0.1, depth_scale=1.0, max_depth=10, *, color=None,
+             model_intensity=None, color_weight=None):
     """The 29 sums of one point-to-plane linearisation, for callers who bring their own solver: the 21 products J_a J_b (a <= b), the
     6 products J_a r, r r and the pair count, over the pixels of the depth frame ``depth`` [h, w] (uint16, float32 or float64) at the
     camera->world pose (``wxyz``, ``t``, intrinsics ``K``) that find a model point within ``max_dist``.  The model is a pair of maps
     ``model_vertex``, ``model_normal`` [hm, wm, 3] in the world frame (NaN = missing; what ``raycast`` returns) seen by the camera
-    (``model_K``, ``model_wxyz``, ``model_t``).  -> float64 [29]; a device tensor when any of the arrays is one."""
+    (``model_K``, ``model_wxyz``, ``model_t``).  -> float64 [29]; a device tensor when any of the arrays is one.
+
+    With the frame's colour image ``color`` (uint8 [hc, wc, 3] of any size), the model's intensity map ``model_intensity`` (float64
+    [hm, wm], NaN = missing; ``raycast(..., colors=True)``'s) and ``color_weight`` (all three or none; the weight is not read here)
+    -> float64 [58]: the 29 sums above, then the same 29 of the photometric pairs (Jc, rc)."""
     depth, code, K, q, t, model_vertex, model_normal, hm, wm, view, max_dist, depth_scale, max_depth = _icp_args(
         depth, K, wxyz, t, model_vertex, model_normal, model_K, model_wxyz, model_t, max_dist, depth_scale, max_depth)
+    col = _color_args(color, model_intensity, color_weight, hm, wm)
     ctx = f3d.default_context()
-    if not (on_device(depth) or on_device(model_vertex) or on_device(model_normal)):
+    if not (on_device(depth) or on_device(model_vertex) or on_device(model_normal) or (col is not None and (on_device(col[0]) or on_device(col[1])))):
+        if col is not None:
+            return ctx.icp_color_sums(depth, K, q, t, model_vertex, model_normal, hm, wm, view, max_dist, col[1], col[0], col[2], depth_scale, max_depth)
         return ctx.icp_sums(depth, K, q, t, model_vertex, model_normal, hm, wm, view, max_dist, depth_scale, max_depth)
     torch, dev = torch_device(ctx, 'icp_sums')
     h, w = (int(x) for x in depth.shape)
     with torch.cuda.device(dev), work_stream(dev) as work:
         d, mv, mn, dview = _to_device(torch, dev, depth, model_vertex, model_normal, view)
-        sums = torch.empty(f3d.ICP_NSUMS, dtype=torch.float64, device=dev)
-        ctx.icp_sums_dev(d.data_ptr(), code, h, w, K, q, t, mv.data_ptr(), mn.data_ptr(), hm, wm, dview.data_ptr(), max_dist, depth_scale, max_depth,
-                         sums.data_ptr(), work.cuda_stream)
-    for x in (d, mv, mn, dview, sums):
+        used = [d, mv, mn, dview]
+        if col is None:
+            sums = torch.empty(f3d.ICP_NSUMS, dtype=torch.float64, device=dev)
+            ctx.icp_sums_dev(d.data_ptr(), code, h, w, K, q, t, mv.data_ptr(), mn.data_ptr(), hm, wm, dview.data_ptr(), max_dist, depth_scale, max_depth,
+                             sums.data_ptr(), work.cuda_stream)
+        else:
+            rgb, mi = _color_to_device(torch, dev, col[0], col[1])
+            used += [rgb, mi]
+            sums = torch.empty(f3d.ICP_NSUMS_COLOR, dtype=torch.float64, device=dev)
+            ctx.icp_color_sums_dev(d.data_ptr(), code, h, w, K, q, t, mv.data_ptr(), mn.data_ptr(), hm, wm, dview.data_ptr(), max_dist, mi.data_ptr(),
+                                   rgb.data_ptr(), int(rgb.shape[0]), int(rgb.shape[1]), col[2], depth_scale, max_depth, sums.data_ptr(),
+                                   work.cuda_stream)
+    for x in used + [sums]:
         x.record_stream(torch.cuda.current_stream(dev))
     return sums
 
@@ -155,38 +216,72 @@ def _icp_device(ctx, torch, dev, work, d, code, K, q, t, mv, mn, hm, wm, dview, 
     return pose, stats, status
 
 
+def _icp_color_device(ctx, torch, dev, work, d, code, K, q, t, mv, mn, hm, wm, dview, max_dist, mi, rgb, color_weight, depth_scale, max_depth, iterations,
+                      min_pairs):
+    """_icp_device with the photometric term: mi the model's intensity map, rgb the frame's colour image [hc, wc, 3], both on the device
+    -> (pose [7], stats [iterations, 5], status [1])."""
+    pose = torch.empty(7, dtype=torch.float64, device=dev)
+    stats = torch.empty((iterations, 5), dtype=torch.float64, device=dev)
+    status = torch.empty(1, dtype=torch.int32, device=dev)
+    ctx.icp_color_dev(d.data_ptr(), code, int(d.shape[0]), int(d.shape[1]), K, q, t, mv.data_ptr(), mn.data_ptr(), hm, wm, dview.data_ptr(), max_dist,
+                      mi.data_ptr(), rgb.data_ptr(), int(rgb.shape[0]), int(rgb.shape[1]), color_weight, depth_scale, max_depth, iterations, min_pairs,
+                      pose.data_ptr(), stats.data_ptr(), status.data_ptr(), work.cuda_stream)
+    return pose, stats, status
+
+
 def icp(depth, K, wxyz, t, model_vertex, model_normal, model_K, model_wxyz, model_t, max_dist=0.1, depth_scale=1.0, max_depth=10, iterations=10,
-        min_pairs=100):
+        min_pairs=100, *, color=None, model_intensity=None, color_weight=None):
     """``iterations`` rounds of projective point-to-plane ICP of the depth frame against the model maps (the arguments of ``icp_sums``),
     starting from the pose (``wxyz``, ``t``), all on the device with no host round trip between the rounds -> (wxyz [4], t [3], info).
     ``info`` holds the final ``status`` (0 = converging, 1 = lost: fewer than ``min_pairs`` pairs or a degenerate system; the pose of a
-    lost call is the one its lost round started from) and ``counts`` and ``rms`` per round, measured before that round's update."""
+    lost call is the one its lost round started from) and ``counts`` and ``rms`` per round, measured before that round's update.
+
+    With ``color``, ``model_intensity`` and ``color_weight`` (the colour arguments of ``icp_sums``; all three or none) every round
+    solves ``A_g + color_weight A_c`` against ``-(b_g + color_weight b_c)``: the intensity residual holds what the geometry lets
+    slide.  Intensities are in [0, 1] and distances in metres, so the weight is a squared length: a residual of 1/255 counts as much as
+    one of sqrt(color_weight) / 255 metres.  ``info`` then also holds ``color_counts`` and ``color_rms`` per round; whether a round is
+    lost is decided by the geometric pairs alone."""
     depth, code, K, q, t, model_vertex, model_normal, hm, wm, view, max_dist, depth_scale, max_depth = _icp_args(
         depth, K, wxyz, t, model_vertex, model_normal, model_K, model_wxyz, model_t, max_dist, depth_scale, max_depth)
+    col = _color_args(color, model_intensity, color_weight, hm, wm)
     iterations, min_pairs = _rounds(iterations, min_pairs)
     ctx = f3d.default_context()
-    if not (on_device(depth) or on_device(model_vertex) or on_device(model_normal)):
-        pose, stats, status = ctx.icp(depth, K, q, t, model_vertex, model_normal, hm, wm, view, max_dist, depth_scale, max_depth, iterations, min_pairs)
+    if not (on_device(depth) or on_device(model_vertex) or on_device(model_normal) or (col is not None and (on_device(col[0]) or on_device(col[1])))):
+        if col is not None:
+            pose, stats, status = ctx.icp_color(depth, K, q, t, model_vertex, model_normal, hm, wm, view, max_dist, col[1], col[0], col[2], depth_scale,
+                                                max_depth, iterations, min_pairs)
+        else:
+            pose, stats, status = ctx.icp(depth, K, q, t, model_vertex, model_normal, hm, wm, view, max_dist, depth_scale, max_depth, iterations,
+                                          min_pairs)
         return pose[:4].copy(), pose[4:].copy(), _info(stats, status)
     torch, dev = torch_device(ctx, 'icp')
     with torch.cuda.device(dev), work_stream(dev) as work:
         d, mv, mn, dview = _to_device(torch, dev, depth, model_vertex, model_normal, view)
-        pose, stats, status = _icp_device(ctx, torch, dev, work, d, code, K, q, t, mv, mn, hm, wm, dview, max_dist, depth_scale, max_depth, iterations,
-                                          min_pairs)
-    for x in (d, mv, mn, dview, pose, stats, status):
+        used = [d, mv, mn, dview]
+        if col is None:
+            pose, stats, status = _icp_device(ctx, torch, dev, work, d, code, K, q, t, mv, mn, hm, wm, dview, max_dist, depth_scale, max_depth,
+                                              iterations, min_pairs)
+        else:
+            rgb, mi = _color_to_device(torch, dev, col[0], col[1])
+            used += [rgb, mi]
+            pose, stats, status = _icp_color_device(ctx, torch, dev, work, d, code, K, q, t, mv, mn, hm, wm, dview, max_dist, mi, rgb, col[2],
+                                                    depth_scale, max_depth, iterations, min_pairs)
+    for x in used + [pose, stats, status]:
         x.record_stream(torch.cuda.current_stream(dev))
     return pose[:4].clone(), pose[4:].clone(), _info(stats, status[0], torch)
 
 
 def track_frames(volume, depths, K, wxyzs, translations, depth_scale=1.0, max_depth=10, max_dist=0.1, iterations=10, min_pairs=100, min_weight=1,
-                 integrate=True, colors=None):
+                 integrate=True, colors=None, color_weight=None):
     """Frame-to-model tracking of the depth frames ``depths`` [F, h, w] into ``volume`` (a ``TSDFVolume``), in frame order.  A frame
     that meets a volume with no weight is integrated at its given pose.  Every later frame is ray-cast at its given pose, the prior
     (samples every voxel edge up to ``max_depth``), aligned to those maps by ``icp`` starting from the prior, takes the refined pose if
     the status is 0 and the prior otherwise, and is integrated at the pose taken (``integrate=False``: only frames that meet an empty
     volume are integrated).  -> (wxyzs [F, 4], translations [F, 3], status int32 [F]); NumPy arrays, or device tensors when the depths
     or the volume are on the device.  ``colors``: the frames' colour images, uint8 [F, hc, wc, 3], for a volume built with
-    ``color=True``; each frame that is integrated hands its image to ``integrate``.
+    ``color=True``; each frame that is integrated hands its image to ``integrate``.  ``color_weight`` (with ``colors``): every aligned
+    frame is ray-cast with the volume's colour and aligned by ``icp`` with the photometric term at that weight, against the intensity
+    of the model as built so far; ``None`` keeps the alignment depth-only.
 
     One host synchronisation per frame: the readback of the 7 doubles of the pose and the status, because ``views_build``, which makes
     the record ``integrate`` projects with, needs the pose on the host.  While the volume is empty its weights are looked at, too."""
@@ -208,6 +303,12 @@ def track_frames(volume, depths, K, wxyzs, translations, depth_scale=1.0, max_de
     out_q, out_t, status = qs.copy(), ts.copy(), np.zeros(F, np.int32)
     if colors is not None:
         colors = volume._color_images(colors, F)
+    if color_weight is not None:
+        if colors is None:
+            raise ValueError('color_weight needs the colour images (colors=...)')
+        color_weight = float(color_weight)
+        if not (color_weight >= 0.0 and color_weight < math.inf):
+            raise ValueError(f'color_weight must be finite and not negative, got {color_weight}')
     device = on_device(depths) or volume.on_device or (colors is not None and on_device(colors))
     if F == 0:
         return _tracked(device, out_q, out_t, status)
@@ -219,8 +320,15 @@ def track_frames(volume, depths, K, wxyzs, translations, depth_scale=1.0, max_de
             empty = empty and not volume.weight.any()
             if not empty:
                 view = f3d.views_build(K, w, h, q[None], t[None], max_depth)
-                vertex, normal, _ = ctx.tsdf_raycast(volume.tsdf, volume.weight, volume.lo, volume.voxel, min_weight, K, q, t, h, w, near, step, nsteps)
-                pose, _, status[f] = ctx.icp(depths[f], K, q, t, vertex, normal, h, w, view, max_dist, depth_scale, max_depth, iterations, min_pairs)
+                if color_weight is None:
+                    vertex, normal, _ = ctx.tsdf_raycast(volume.tsdf, volume.weight, volume.lo, volume.voxel, min_weight, K, q, t, h, w, near, step,
+                                                         nsteps)
+                    pose, _, status[f] = ctx.icp(depths[f], K, q, t, vertex, normal, h, w, view, max_dist, depth_scale, max_depth, iterations, min_pairs)
+                else:
+                    vertex, normal, _, _, intensity = ctx.tsdf_raycast_color(volume.tsdf, volume.weight, volume.color, volume.lo, volume.voxel,
+                                                                             min_weight, K, q, t, h, w, near, step, nsteps)
+                    pose, _, status[f] = ctx.icp_color(depths[f], K, q, t, vertex, normal, h, w, view, max_dist, intensity, colors[f], color_weight,
+                                                       depth_scale, max_depth, iterations, min_pairs)
                 if status[f] == 0:
                     out_q[f], out_t[f] = pose[:4], pose[4:]
             if empty or integrate:
@@ -230,6 +338,8 @@ def track_frames(volume, depths, K, wxyzs, translations, depth_scale=1.0, max_de
     torch, dev = torch_device(ctx, 'track_frames')
     volume._to_device()
     d_all = (depths if on_device(depths) else torch.from_numpy(np.ascontiguousarray(depths))).to(dev).contiguous()
+    if color_weight is not None:
+        rgb_all = (colors if on_device(colors) else torch.from_numpy(np.ascontiguousarray(colors))).to(dev).contiguous()
     for f in range(F):
         _, q, t = poses[f]
         empty = empty and not bool(volume.weight.any())
@@ -237,13 +347,24 @@ def track_frames(volume, depths, K, wxyzs, translations, depth_scale=1.0, max_de
             view = f3d.views_build(K, w, h, q[None], t[None], max_depth)
             with torch.cuda.device(dev), work_stream(dev) as work:
                 vertex, normal = (torch.empty((h * w, 3), dtype=torch.float64, device=dev) for _ in range(2))
-                ctx.tsdf_raycast_dev(volume.tsdf.data_ptr(), volume.weight.data_ptr(), volume.dims, volume.lo, volume.voxel, min_weight, K, q, t, h, w,
-                                     near, step, nsteps, vertex.data_ptr(), normal.data_ptr(), None, work.cuda_stream)
                 dview = torch.from_numpy(view).to(dev)
-                pose, stats, lost = _icp_device(ctx, torch, dev, work, d_all[f], code, K, q, t, vertex, normal, h, w, dview, max_dist, depth_scale,
-                                                max_depth, iterations, min_pairs)
-                back = torch.cat([pose, lost.to(torch.float64)])
-            for x in (vertex, normal, dview, pose, stats, lost):
+                used = [vertex, normal, dview]
+                if color_weight is None:
+                    ctx.tsdf_raycast_dev(volume.tsdf.data_ptr(), volume.weight.data_ptr(), volume.dims, volume.lo, volume.voxel, min_weight, K, q, t, h,
+                                         w, near, step, nsteps, vertex.data_ptr(), normal.data_ptr(), None, work.cuda_stream)
+                    pose, stats, lost = _icp_device(ctx, torch, dev, work, d_all[f], code, K, q, t, vertex, normal, h, w, dview, max_dist, depth_scale,
+                                                    max_depth, iterations, min_pairs)
+                    back = torch.cat([pose, lost.to(torch.float64)])
+                else:
+                    intensity = torch.empty(h * w, dtype=torch.float64, device=dev)
+                    used.append(intensity)
+                    ctx.tsdf_raycast_color_dev(volume.tsdf.data_ptr(), volume.weight.data_ptr(), volume.color.data_ptr(), volume.dims, volume.lo,
+                                               volume.voxel, min_weight, K, q, t, h, w, near, step, nsteps, vertex.data_ptr(), normal.data_ptr(), None,
+                                               None, intensity.data_ptr(), work.cuda_stream)
+                    pose, stats, lost = _icp_color_device(ctx, torch, dev, work, d_all[f], code, K, q, t, vertex, normal, h, w, dview, max_dist,
+                                                          intensity, rgb_all[f], color_weight, depth_scale, max_depth, iterations, min_pairs)
+                    back = torch.cat([pose, lost.to(torch.float64), stats[-1, 3:]])          # the two colour columns ride along
+            for x in used + [pose, stats, lost]:
                 x.record_stream(torch.cuda.current_stream(dev))
             back = back.cpu().numpy()                                  # the one synchronisation of the frame
             status[f] = int(back[7])

@@ -3291,6 +3291,140 @@ int f3d_icp(f3d_ctx* ctx, const void* depth, int depth_type, int h, int w, const
     return st.finish();
 }
 
+// colour: the raycast arguments plus the colour state and two more outputs; the ICP arguments plus the model's intensity map, the
+// source colour image and the weight of the photometric system
+#define F3D_RAYCAST_COLOR_BAD F3D_RAYCAST_BAD "; color not NULL, the device color 16-byte aligned"
+int f3d_tsdf_raycast_color_dev(f3d_ctx* ctx, const float* tsdf, const float* weight, const float* color, int nx, int ny, int nz, const double lo[3],
+                               double vs, float min_weight, const double K[9], const double q_wxyz[4], const double t[3], int h, int w, double znear,
+                               double step, int nsteps, double* vertex, double* normal, double* depth, double* rgb, double* intensity, void* stream) {
+    int rc = enter(ctx); if (rc) return rc;
+    double qn[4];
+    if (!raycast_ok(tsdf, weight, nx, ny, nz, lo, vs, min_weight, K, q_wxyz, t, h, w, znear, step, nsteps, qn) || !color || !aligned16(color))
+        return fail(ctx, F3D_ERR_INVALID, "tsdf_raycast_color: " F3D_RAYCAST_COLOR_BAD);
+    if (!vertex && !normal && !depth && !rgb && !intensity) return F3D_OK;
+    F3D_HIP(ctx, f3d_launch_tsdf_raycast_color(tsdf, weight, color, nx, ny, nz, lo, vs, min_weight, K, qn, t, h, w, znear, step, nsteps, vertex, normal,
+                                               depth, rgb, intensity, ctx->tsdf_grid_cap, pick(ctx, stream)));
+    return F3D_OK;
+}
+
+int f3d_tsdf_raycast_color(f3d_ctx* ctx, const float* tsdf, const float* weight, const float* color, int nx, int ny, int nz, const double lo[3],
+                           double vs, float min_weight, const double K[9], const double q_wxyz[4], const double t[3], int h, int w, double znear,
+                           double step, int nsteps, double* vertex, double* normal, double* depth, double* rgb, double* intensity) {
+    int rc = enter(ctx); if (rc) return rc;
+    double qn[4];
+    if (!raycast_ok(tsdf, weight, nx, ny, nz, lo, vs, min_weight, K, q_wxyz, t, h, w, znear, step, nsteps, qn) || !color)
+        return fail(ctx, F3D_ERR_INVALID, "tsdf_raycast_color: " F3D_RAYCAST_COLOR_BAD);
+    const size_t vol = (size_t)tsdf_voxels(nx, ny, nz) * 4, px = (size_t)h * w * 8;
+    staging st(ctx);
+    const float* dt = st.in(tsdf, vol);
+    const float* dw = st.in(weight, vol);
+    const float* dc = st.in(color, 4 * vol);
+    double* dv = st.out(vertex, 3 * px);
+    double* dn = st.out(normal, 3 * px);
+    double* dd = st.out(depth, px);
+    double* drgb = st.out(rgb, 3 * px);
+    double* di = st.out(intensity, px);
+    if (!st.rc) st.rc = f3d_tsdf_raycast_color_dev(ctx, dt, dw, dc, nx, ny, nz, lo, vs, min_weight, K, q_wxyz, t, h, w, znear, step, nsteps, dv, dn, dd,
+                                                   drgb, di, ctx->stream);
+    return st.finish();
+}
+
+#define F3D_ICP_COLOR_BAD F3D_ICP_BAD "; model_intensity and rgb not NULL; hc, wc_img > 0 with a product < 2^31; color_weight finite and >= 0"
+static bool icp_color_ok(const double* model_intensity, const uint8_t* rgb, int hc, int wc_img, double color_weight) {
+    return model_intensity && rgb && image_ok(hc, wc_img) && color_weight >= 0.0 && color_weight < INFINITY;
+}
+
+static f3d_icp_color_args icp_color_args(const double* model_intensity, const uint8_t* rgb, int hc, int wc_img, double color_weight) {
+    f3d_icp_color_args c;
+    c.model_intensity = model_intensity; c.rgb = rgb; c.hc = hc; c.wc_img = wc_img; c.color_weight = color_weight;
+    return c;
+}
+
+int f3d_ctx_reserve_icp_color(f3d_ctx* ctx, int64_t npixels) {
+    int rc = enter(ctx); if (rc) return rc;
+    if (npixels < 0 || npixels >= ((int64_t)1 << 31)) return fail(ctx, F3D_ERR_INVALID, "ctx_reserve_icp_color: npixels must be in [0, 2^31)");
+    return reserve(ctx, {{SLOT_ICP, f3d_icp_color_scratch_bytes(npixels)}});
+}
+
+int f3d_icp_color_sums_dev(f3d_ctx* ctx, const void* depth, int depth_type, int h, int w, const double K[9], double depth_scale, double max_depth,
+                           const double q_wxyz[4], const double t[3], const double* model_vertex, const double* model_normal, int hm, int wm,
+                           const f3d_view* model_view, double max_dist, const double* model_intensity, const uint8_t* rgb, int hc, int wc_img,
+                           double color_weight, double* sums, void* stream) {
+    int rc = enter(ctx); if (rc) return rc;
+    if (!sums || !icp_ok(depth, depth_type, h, w, K, depth_scale, max_depth, q_wxyz, t, model_vertex, model_normal, hm, wm, model_view, max_dist) ||
+        !icp_color_ok(model_intensity, rgb, hc, wc_img, color_weight))
+        return fail(ctx, F3D_ERR_INVALID, "icp_color_sums: " F3D_ICP_COLOR_BAD);
+    void* scratch;
+    if ((rc = ensure(ctx, SLOT_ICP, f3d_icp_color_scratch_bytes((int64_t)h * w), &scratch))) return rc;
+    F3D_HIP(ctx, f3d_launch_icp_color_sums(icp_args(depth, depth_type, h, w, K, depth_scale, max_depth, model_vertex, model_normal, hm, wm, model_view,
+                                                    max_dist),
+                                           icp_color_args(model_intensity, rgb, hc, wc_img, color_weight), q_wxyz, t, scratch, sums, pick(ctx, stream)));
+    return F3D_OK;
+}
+
+int f3d_icp_color_sums(f3d_ctx* ctx, const void* depth, int depth_type, int h, int w, const double K[9], double depth_scale, double max_depth,
+                       const double q_wxyz[4], const double t[3], const double* model_vertex, const double* model_normal, int hm, int wm,
+                       const f3d_view* model_view, double max_dist, const double* model_intensity, const uint8_t* rgb, int hc, int wc_img,
+                       double color_weight, double* sums) {
+    int rc = enter(ctx); if (rc) return rc;
+    if (!sums || !icp_ok(depth, depth_type, h, w, K, depth_scale, max_depth, q_wxyz, t, model_vertex, model_normal, hm, wm, model_view, max_dist) ||
+        !icp_color_ok(model_intensity, rgb, hc, wc_img, color_weight))
+        return fail(ctx, F3D_ERR_INVALID, "icp_color_sums: " F3D_ICP_COLOR_BAD);
+    staging st(ctx);
+    const void* dd = st.in((const char*)depth, depth_bytes(depth_type, 1, h, w));
+    const double* dv = st.in(model_vertex, (size_t)hm * wm * 24);
+    const double* dn = st.in(model_normal, (size_t)hm * wm * 24);
+    const f3d_view* dview = st.in(model_view, sizeof(f3d_view));
+    const double* di = st.in(model_intensity, (size_t)hm * wm * 8);
+    const uint8_t* drgb = st.in(rgb, (size_t)hc * wc_img * 3);
+    double* ds = st.out(sums, F3D_ICP_NSUMS_COLOR * sizeof(double));
+    if (!st.rc) st.rc = f3d_icp_color_sums_dev(ctx, dd, depth_type, h, w, K, depth_scale, max_depth, q_wxyz, t, dv, dn, hm, wm, dview, max_dist, di, drgb,
+                                               hc, wc_img, color_weight, ds, ctx->stream);
+    return st.finish();
+}
+
+int f3d_icp_color_dev(f3d_ctx* ctx, const void* depth, int depth_type, int h, int w, const double K[9], double depth_scale, double max_depth,
+                      const double q_wxyz[4], const double t[3], const double* model_vertex, const double* model_normal, int hm, int wm,
+                      const f3d_view* model_view, double max_dist, const double* model_intensity, const uint8_t* rgb, int hc, int wc_img,
+                      double color_weight, int iterations, int min_pairs, double* pose, double* stats, int32_t* status, void* stream) {
+    int rc = enter(ctx); if (rc) return rc;
+    if (!pose || !stats || !icp_ok(depth, depth_type, h, w, K, depth_scale, max_depth, q_wxyz, t, model_vertex, model_normal, hm, wm, model_view, max_dist) ||
+        !icp_color_ok(model_intensity, rgb, hc, wc_img, color_weight))
+        return fail(ctx, F3D_ERR_INVALID, "icp_color: " F3D_ICP_COLOR_BAD);
+    if (iterations < 1 || min_pairs < 6) return fail(ctx, F3D_ERR_INVALID, "icp_color: iterations must be at least 1 and min_pairs at least 6");
+    void* scratch;
+    if ((rc = ensure(ctx, SLOT_ICP, f3d_icp_color_scratch_bytes((int64_t)h * w), &scratch))) return rc;
+    F3D_HIP(ctx, f3d_launch_icp_color(icp_args(depth, depth_type, h, w, K, depth_scale, max_depth, model_vertex, model_normal, hm, wm, model_view, max_dist),
+                                      icp_color_args(model_intensity, rgb, hc, wc_img, color_weight), q_wxyz, t, iterations, min_pairs, scratch, pose,
+                                      stats, status, pick(ctx, stream)));
+    return F3D_OK;
+}
+
+int f3d_icp_color(f3d_ctx* ctx, const void* depth, int depth_type, int h, int w, const double K[9], double depth_scale, double max_depth,
+                  const double q_wxyz[4], const double t[3], const double* model_vertex, const double* model_normal, int hm, int wm,
+                  const f3d_view* model_view, double max_dist, const double* model_intensity, const uint8_t* rgb, int hc, int wc_img,
+                  double color_weight, int iterations, int min_pairs, double* pose, double* stats, int32_t* status) {
+    int rc = enter(ctx); if (rc) return rc;
+    if (!pose || !stats || !status ||
+        !icp_ok(depth, depth_type, h, w, K, depth_scale, max_depth, q_wxyz, t, model_vertex, model_normal, hm, wm, model_view, max_dist) ||
+        !icp_color_ok(model_intensity, rgb, hc, wc_img, color_weight))
+        return fail(ctx, F3D_ERR_INVALID, "icp_color: " F3D_ICP_COLOR_BAD);
+    if (iterations < 1 || min_pairs < 6) return fail(ctx, F3D_ERR_INVALID, "icp_color: iterations must be at least 1 and min_pairs at least 6");
+    staging st(ctx);
+    const void* dd = st.in((const char*)depth, depth_bytes(depth_type, 1, h, w));
+    const double* dv = st.in(model_vertex, (size_t)hm * wm * 24);
+    const double* dn = st.in(model_normal, (size_t)hm * wm * 24);
+    const f3d_view* dview = st.in(model_view, sizeof(f3d_view));
+    const double* di = st.in(model_intensity, (size_t)hm * wm * 8);
+    const uint8_t* drgb = st.in(rgb, (size_t)hc * wc_img * 3);
+    double* dp = st.out(pose, 7 * sizeof(double));
+    double* ds = st.out(stats, (size_t)iterations * 5 * sizeof(double));
+    int32_t* dst = st.out(status, sizeof(int32_t));
+    if (!st.rc) st.rc = f3d_icp_color_dev(ctx, dd, depth_type, h, w, K, depth_scale, max_depth, q_wxyz, t, dv, dn, hm, wm, dview, max_dist, di, drgb, hc,
+                                          wc_img, color_weight, iterations, min_pairs, dp, ds, dst, ctx->stream);
+    return st.finish();
+}
+
 // ---------------------------------------------------------------------------------------------
 // feature fusion: per-point pooling of per-pixel feature maps over views (f3d_features.hip)
 // ---------------------------------------------------------------------------------------------

@@ -13,6 +13,12 @@
 //   k_icp_solve     one block: its waves take the 29 totals in turn (f3d_wave_sum over the chunk sums); after the barrier thread 0 does
 //                   the 6 x 6 Cholesky solve and writes the pose and the stats row.  Two launches per round, no host round trip: the pose
 //                   and the lost flag live in device memory, both kernels read them.
+// Colour (f3d_tsdf_raycast_color, f3d_icp_color_sums, f3d_icp_color) is the COLOR = true instantiation of the three kernels; the
+// depth-only ones carry none of its arguments and none of its code:
+//   k_tsdf_raycast<true>  after the hit is settled, the colour state's eight corners around V, lerped like F.
+//   k_icp_terms<T, true>  a second sweep over the chunk recomputes each pixel and accumulates the 29 photometric terms, so that no more
+//                         than 29 accumulators are live at a time; a chunk row is 58 wide, the geometric sums first.
+//   k_icp_solve<true>     58 totals; A = A_g + color_weight * A_c; a stats row of 5.
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
@@ -26,6 +32,7 @@
 namespace {
 
 constexpr int NS = F3D_ICP_NSUMS;
+constexpr int NSC = F3D_ICP_NSUMS_COLOR;
 constexpr int ICP_WAVES = F3D_BLOCK / 64;                  // chunks a block of k_icp_terms takes per pass: one per wave
 
 template <typename T> struct raw_depth;
@@ -102,8 +109,45 @@ __device__ __forceinline__ void sample_range(const ray_volume& g, const double t
 
 struct ray_camera { double fx, fy, cx, cy, qn[4], t[3]; };
 
+// the colour arguments of k_tsdf_raycast<true>: the state (r, g, b, wc) per voxel and the two colour outputs (each may be NULL); the
+// depth-only instantiation carries none
+template <bool COLOR> struct ray_color_io {};
+template <> struct ray_color_io<true> { const float4* color; double* rgb; double* intensity; };
+
+__device__ __forceinline__ double intensity_of(double r, double g, double b) { return ((0.299 * r + 0.587 * g) + 0.114 * b) / 255.0; }
+
+// the colour sample of the contract at V: false = invalid (V outside the index rule, or a corner without colour)
+__device__ __forceinline__ bool sample_color(const ray_volume& g, const float4* __restrict__ color, const double V[3], double rgb[3]) {
+    const double gx = (V[0] - g.lo[0]) / g.vs - 0.5, gy = (V[1] - g.lo[1]) / g.vs - 0.5, gz = (V[2] - g.lo[2]) / g.vs - 0.5;
+    const double ix = floor(gx), iy = floor(gy), iz = floor(gz);
+    if (!(ix >= 0.0 && ix <= (double)(g.nx - 2) && iy >= 0.0 && iy <= (double)(g.ny - 2) && iz >= 0.0 && iz <= (double)(g.nz - 2))) return false;
+    const double fx = gx - ix, fy = gy - iy, fz = gz - iz;
+    const int64_t sy = g.nx, sz = (int64_t)g.nx * g.ny;
+    const float4* C = color + (((int64_t)iz * g.ny + (int64_t)iy) * g.nx + (int64_t)ix);
+    double cjk[4][3];
+    bool seen = true;
+#pragma unroll
+    for (int c = 0; c < 4; ++c) {                           // c = j + 2 k: the pair (C0jk, C1jk), lerped along x
+        const int64_t o = (c & 1) * sy + (c >> 1) * sz;
+        const float4 c0 = C[o], c1 = C[o + 1];
+        seen = seen & (c0.w > 0.f) & (c1.w > 0.f);
+        cjk[c][0] = (double)c0.x + fx * ((double)c1.x - (double)c0.x);
+        cjk[c][1] = (double)c0.y + fx * ((double)c1.y - (double)c0.y);
+        cjk[c][2] = (double)c0.z + fx * ((double)c1.z - (double)c0.z);
+    }
+    if (!seen) return false;
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+        const double c0 = cjk[0][a] + fy * (cjk[1][a] - cjk[0][a]), c1 = cjk[2][a] + fy * (cjk[3][a] - cjk[2][a]);
+        rgb[a] = c0 + fz * (c1 - c0);
+    }
+    return true;
+}
+
+template <bool COLOR>
 __global__ __launch_bounds__(F3D_BLOCK) void k_tsdf_raycast(ray_volume g, ray_camera cam, int h, int w, double near, double step, int nsteps,
-                                                             double* __restrict__ vertex, double* __restrict__ normal, double* __restrict__ depth) {
+                                                             double* __restrict__ vertex, double* __restrict__ normal, double* __restrict__ depth,
+                                                             ray_color_io<COLOR> cio) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int tx = (w + 7) >> 3, ty = (h + 7) >> 3;
     const int64_t ntiles = (int64_t)tx * ty;
@@ -161,6 +205,18 @@ __global__ __launch_bounds__(F3D_BLOCK) void k_tsdf_raycast(ray_volume g, ray_ca
         if (vertex) { vertex[3 * i] = V[0]; vertex[3 * i + 1] = V[1]; vertex[3 * i + 2] = V[2]; }
         if (normal) { normal[3 * i] = N[0]; normal[3 * i + 1] = N[1]; normal[3 * i + 2] = N[2]; }
         if (depth) depth[i] = z;
+        if constexpr (COLOR) {
+            double C[3] = {nan, nan, nan}, I = nan;
+            if (V[0] == V[0]) {                                                 // a hit: its vertex is finite
+                double S[3];
+                if (sample_color(g, cio.color, V, S)) {
+                    C[0] = S[0]; C[1] = S[1]; C[2] = S[2];
+                    I = intensity_of(S[0], S[1], S[2]);
+                }
+            }
+            if (cio.rgb) { cio.rgb[3 * i] = C[0]; cio.rgb[3 * i + 1] = C[1]; cio.rgb[3 * i + 2] = C[2]; }
+            if (cio.intensity) cio.intensity[i] = I;
+        }
     }
 }
 
@@ -174,6 +230,14 @@ struct icp_frame {
     const f3d_view* model_view;
     double max_dist2;
 };
+
+// the colour arguments of k_icp_terms<T, true>: the model's intensity map [hm*wm] (NaN = missing) and the source colour image
+// [hc, wc, 3]; the depth-only instantiations carry none
+template <bool COLOR> struct icp_color_io {};
+template <> struct icp_color_io<true> { const double* model_intensity; const uint8_t* rgb; int hc, wc; };
+
+// what the photometric pair of a pixel needs from its geometric steps
+struct icp_seen { f3d_p3 pr; double x, y, h2; int u, v; };
 
 __device__ __forceinline__ void normalised(const double q[4], double qn[4]) {
     const double len = sqrt(((q[0] * q[0] + q[1] * q[1]) + q[2] * q[2]) + q[3] * q[3]);
@@ -189,8 +253,8 @@ __global__ void k_icp_init(double* __restrict__ pose, int* __restrict__ lost, do
 }
 
 // the 29 terms of source pixel i at the pose (qn, t), added to acc; false = the pixel contributes 0.0 to every sum
-template <typename T>
-__device__ __forceinline__ bool icp_pixel(const icp_frame& f, const double qn[4], const double t[3], int64_t i, double J[6], double& r) {
+template <typename T, bool SEEN>
+__device__ __forceinline__ bool icp_pixel(const icp_frame& f, const double qn[4], const double t[3], int64_t i, double J[6], double& r, icp_seen& seen) {
     const double d = raw_depth<T>::at((const T*)f.depth, i) / f.depth_scale;
     if (!(d > 0.0 && d <= f.max_depth)) return false;
     const int v = (int)(i / f.w), u = (int)(i - (int64_t)v * f.w);
@@ -219,13 +283,46 @@ __device__ __forceinline__ bool icp_pixel(const icp_frame& f, const double qn[4]
     J[1] = pr.z * N0 - pr.x * N2;
     J[2] = pr.x * N1 - pr.y * N0;
     J[3] = N0; J[4] = N1; J[5] = N2;
+    if constexpr (SEEN) { seen.pr = pr; seen.x = x; seen.y = y; seen.h2 = hp.z; seen.u = u; seen.v = v; }
     return true;
 }
 
-template <typename T>
+// the photometric pair of a pixel that passed step 5: false = it has none
+__device__ __forceinline__ bool icp_color_pair(const icp_frame& f, const icp_color_io<true>& c, const icp_seen& p, double J[6], double& r) {
+    const double a = p.x - 0.5, b = p.y - 0.5;
+    const double i0 = floor(a), j0 = floor(b);
+    if (!(i0 >= 0.0 && i0 <= (double)(f.wm - 2) && j0 >= 0.0 && j0 <= (double)(f.hm - 2))) return false;
+    const double fa = a - i0, fb = b - j0;
+    const double* I = c.model_intensity + ((int64_t)j0 * f.wm + (int64_t)i0);
+    const double I00 = I[0], I10 = I[1], I01 = I[f.wm], I11 = I[f.wm + 1];
+    if (!(fabs(I00) < INFINITY && fabs(I10) < INFINITY && fabs(I01) < INFINITY && fabs(I11) < INFINITY)) return false;
+    const int64_t uc = (int64_t)p.u * c.wc / f.w, vc = (int64_t)p.v * c.hc / f.h;
+    const uint8_t* pix = c.rgb + (vc * c.wc + uc) * 3;
+    const double Is = intensity_of((double)pix[0], (double)pix[1], (double)pix[2]);
+    const double top = I00 + fa * (I10 - I00), bot = I01 + fa * (I11 - I01);
+    const double Im = top + fb * (bot - top);
+    const double dx0 = I10 - I00, dx1 = I11 - I01;
+    const double gx = dx0 + fb * (dx1 - dx0), gy = bot - top;
+    r = Im - Is;
+    const f3d_view& mv = *f.model_view;
+    f3d_p3 gc;
+    gc.x = (gx * (mv.K[0] - p.x * mv.K[6]) + gy * (mv.K[3] - p.y * mv.K[6])) / p.h2;
+    gc.y = (gx * (mv.K[1] - p.x * mv.K[7]) + gy * (mv.K[4] - p.y * mv.K[7])) / p.h2;
+    gc.z = (gx * (mv.K[2] - p.x * mv.K[8]) + gy * (mv.K[5] - p.y * mv.K[8])) / p.h2;
+    const double qc[4] = {mv.qinv[0], -mv.qinv[1], -mv.qinv[2], -mv.qinv[3]};
+    const f3d_p3 gw = f3d_rotate(qc, gc);
+    J[0] = p.pr.y * gw.z - p.pr.z * gw.y;
+    J[1] = p.pr.z * gw.x - p.pr.x * gw.z;
+    J[2] = p.pr.x * gw.y - p.pr.y * gw.x;
+    J[3] = gw.x; J[4] = gw.y; J[5] = gw.z;
+    return true;
+}
+
+template <typename T, bool COLOR>
 __global__ __launch_bounds__(F3D_BLOCK) void k_icp_terms(icp_frame f, const double* __restrict__ pose, const int* __restrict__ lost,
-                                                          int64_t npix, int64_t nchunks, double* __restrict__ chunks) {
+                                                          int64_t npix, int64_t nchunks, double* __restrict__ chunks, icp_color_io<COLOR> cio) {
     if (*lost) return;
+    constexpr int ROW = COLOR ? NSC : NS;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     double qn[4];
     normalised(pose, qn);
@@ -238,7 +335,8 @@ __global__ __launch_bounds__(F3D_BLOCK) void k_icp_terms(icp_frame f, const doub
         for (int j = 0; j < NS; ++j) acc[j] = 0.0;
         for (int64_t i = lane; i < count; i += 64) {
             double J[6], r;
-            if (!icp_pixel<T>(f, qn, t, first + i, J, r)) continue;            // + 0.0 leaves an accumulator as it is (none is ever -0.0)
+            icp_seen seen;
+            if (!icp_pixel<T, false>(f, qn, t, first + i, J, r, seen)) continue;   // + 0.0 leaves an accumulator as it is (none is ever -0.0)
             int j = 0;
 #pragma unroll
             for (int a = 0; a < 6; ++a)
@@ -254,16 +352,48 @@ __global__ __launch_bounds__(F3D_BLOCK) void k_icp_terms(icp_frame f, const doub
             for (int off = 32; off > 0; off >>= 1) acc[j] = acc[j] + __shfl_xor(acc[j], off);
         if (lane == 0) {
 #pragma unroll
-            for (int j = 0; j < NS; ++j) chunks[chunk * NS + j] = acc[j];
+            for (int j = 0; j < NS; ++j) chunks[chunk * ROW + j] = acc[j];
+        }
+        if constexpr (COLOR) {                                                  // the second sweep: the same pixels, their photometric pairs
+#pragma unroll
+            for (int j = 0; j < NS; ++j) acc[j] = 0.0;
+            for (int64_t i = lane; i < count; i += 64) {
+                double J[6], r;
+                icp_seen seen;
+                if (!icp_pixel<T, true>(f, qn, t, first + i, J, r, seen)) continue;
+                if (!icp_color_pair(f, cio, seen, J, r)) continue;
+                int j = 0;
+#pragma unroll
+                for (int a = 0; a < 6; ++a)
+#pragma unroll
+                    for (int b = a; b < 6; ++b) { acc[j] = acc[j] + J[a] * J[b]; ++j; }
+#pragma unroll
+                for (int a = 0; a < 6; ++a) acc[21 + a] = acc[21 + a] + J[a] * r;
+                acc[27] = acc[27] + r * r;
+                acc[28] = acc[28] + 1.0;
+            }
+#pragma unroll
+            for (int j = 0; j < NS; ++j)
+                for (int off = 32; off > 0; off >>= 1) acc[j] = acc[j] + __shfl_xor(acc[j], off);
+            if (lane == 0) {
+#pragma unroll
+                for (int j = 0; j < NS; ++j) chunks[chunk * ROW + NS + j] = acc[j];
+            }
         }
     }
 }
 
 // One block.  totals_out != NULL: the 29 totals go there and nothing else happens (f3d_icp_sums).  Otherwise one round of f3d_icp: the
-// solve, the update of `pose` and row `round` of stats.
+// solve, the update of `pose` and row `round` of stats.  COLOR: 58 totals, the photometric system weighted into the solve, a stats row of 5.
+template <bool COLOR> struct icp_solve_color {};
+template <> struct icp_solve_color<true> { double weight; };
+
+template <bool COLOR>
 __global__ __launch_bounds__(F3D_BLOCK) void k_icp_solve(const double* __restrict__ chunks, int64_t nchunks, double* __restrict__ totals_out,
                                                           double* __restrict__ pose, int* __restrict__ lost, double min_pairs,
-                                                          double* __restrict__ stats, int round) {
+                                                          double* __restrict__ stats, int round, icp_solve_color<COLOR> col) {
+    constexpr int NS = COLOR ? NSC : F3D_ICP_NSUMS;
+    constexpr int NSTAT = COLOR ? 5 : 3;
     __shared__ double tot[NS];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const bool was_lost = totals_out ? false : *lost != 0;
@@ -279,16 +409,28 @@ __global__ __launch_bounds__(F3D_BLOCK) void k_icp_solve(const double* __restric
         for (int j = 0; j < NS; ++j) totals_out[j] = tot[j];
         return;
     }
-    double* row = stats + 3 * (int64_t)round;
-    if (was_lost) { row[0] = 0.0; row[1] = 0.0; row[2] = (double)F3D_ICP_LOST; return; }
+    double* row = stats + NSTAT * (int64_t)round;
+    if (was_lost) {
+        row[0] = 0.0; row[1] = 0.0; row[2] = (double)F3D_ICP_LOST;
+        if constexpr (COLOR) { row[3] = 0.0; row[4] = 0.0; }
+        return;
+    }
     row[0] = tot[28]; row[1] = tot[27];
+    if constexpr (COLOR) { row[3] = tot[29 + 28]; row[4] = tot[29 + 27]; }
     bool ok = !(tot[28] < min_pairs);
     double A[6][6], L[6][6], b[6], y[6], x[6];
     {
         int j = 0;
         for (int a = 0; a < 6; ++a)
-            for (int c = a; c < 6; ++c) { A[a][c] = tot[j]; A[c][a] = tot[j]; ++j; }
-        for (int a = 0; a < 6; ++a) b[a] = -tot[21 + a];
+            for (int c = a; c < 6; ++c) {
+                double e = tot[j];
+                if constexpr (COLOR) e = e + col.weight * tot[29 + j];
+                A[a][c] = e; A[c][a] = e; ++j;
+            }
+        for (int a = 0; a < 6; ++a) {
+            if constexpr (COLOR) b[a] = -(tot[21 + a] + col.weight * tot[29 + 21 + a]);
+            else b[a] = -tot[21 + a];
+        }
     }
     double maxd = A[0][0];
     for (int a = 1; a < 6; ++a) if (A[a][a] > maxd) maxd = A[a][a];
@@ -330,10 +472,10 @@ __global__ __launch_bounds__(F3D_BLOCK) void k_icp_solve(const double* __restric
 
 struct icp_scratch { size_t chunks, pose, lost, bytes; };
 
-icp_scratch icp_layout(int64_t npixels) {
+icp_scratch icp_layout(int64_t npixels, int row = NS) {
     f3d_carve c;
     icp_scratch l;
-    l.chunks = c.take((size_t)((npixels + F3D_ICP_CHUNK - 1) / F3D_ICP_CHUNK) * NS * sizeof(double));
+    l.chunks = c.take((size_t)((npixels + F3D_ICP_CHUNK - 1) / F3D_ICP_CHUNK) * row * sizeof(double));
     l.pose = c.take(7 * sizeof(double));
     l.lost = c.take(sizeof(int));
     l.bytes = c.off;
@@ -351,32 +493,69 @@ icp_frame frame_of(const f3d_icp_args& a) {
     return f;
 }
 
-void launch_terms(const f3d_icp_args& a, const double* pose, const int* lost, double* chunks, hipStream_t s) {
+template <bool COLOR>
+void launch_terms(const f3d_icp_args& a, const double* pose, const int* lost, double* chunks, icp_color_io<COLOR> cio, hipStream_t s) {
     const icp_frame f = frame_of(a);
     const int64_t npix = (int64_t)a.h * a.w, nchunks = (npix + F3D_ICP_CHUNK - 1) / F3D_ICP_CHUNK;
     const dim3 gr(f3d_grid_for(nchunks, ICP_WAVES, F3D_GRID_CAP)), b(F3D_BLOCK);
-    if (a.depth_type == F3D_DEPTH_U16) hipLaunchKernelGGL(k_icp_terms<uint16_t>, gr, b, 0, s, f, pose, lost, npix, nchunks, chunks);
-    else if (a.depth_type == F3D_DEPTH_F32) hipLaunchKernelGGL(k_icp_terms<float>, gr, b, 0, s, f, pose, lost, npix, nchunks, chunks);
-    else hipLaunchKernelGGL(k_icp_terms<double>, gr, b, 0, s, f, pose, lost, npix, nchunks, chunks);
+    if (a.depth_type == F3D_DEPTH_U16) hipLaunchKernelGGL((k_icp_terms<uint16_t, COLOR>), gr, b, 0, s, f, pose, lost, npix, nchunks, chunks, cio);
+    else if (a.depth_type == F3D_DEPTH_F32) hipLaunchKernelGGL((k_icp_terms<float, COLOR>), gr, b, 0, s, f, pose, lost, npix, nchunks, chunks, cio);
+    else hipLaunchKernelGGL((k_icp_terms<double, COLOR>), gr, b, 0, s, f, pose, lost, npix, nchunks, chunks, cio);
+}
+
+icp_color_io<true> color_of(const f3d_icp_color_args& c) {
+    icp_color_io<true> cio;
+    cio.model_intensity = c.model_intensity; cio.rgb = c.rgb; cio.hc = c.hc; cio.wc = c.wc_img;
+    return cio;
+}
+
+ray_volume volume_of(const float* tsdf, const float* weight, int nx, int ny, int nz, const double lo[3], double vs, float min_weight) {
+    ray_volume g;
+    g.tsdf = tsdf; g.weight = weight; g.nx = nx; g.ny = ny; g.nz = nz; g.vs = vs; g.min_weight = min_weight;
+    for (int c = 0; c < 3; ++c) g.lo[c] = lo[c];
+    return g;
+}
+
+ray_camera camera_of(const double K[9], const double qn[4], const double t[3]) {
+    ray_camera cam;
+    cam.fx = K[0]; cam.cx = K[2]; cam.fy = K[4]; cam.cy = K[5];
+    for (int c = 0; c < 3; ++c) cam.t[c] = t[c];
+    for (int c = 0; c < 4; ++c) cam.qn[c] = qn[c];
+    return cam;
+}
+
+// blocks of a raycast launch: the usual cap, or the smaller one a test set
+int ray_blocks(int h, int w, int grid_cap) {
+    const int64_t ntiles = (int64_t)((w + 7) / 8) * ((h + 7) / 8);
+    const int usual = F3D_GRID_CAP * 16;
+    return f3d_grid_for(ntiles, F3D_BLOCK / 64, grid_cap > 0 && grid_cap < usual ? grid_cap : usual);
 }
 
 }  // namespace
 
 size_t f3d_icp_scratch_bytes(int64_t npixels) { return icp_layout(npixels).bytes; }
+size_t f3d_icp_color_scratch_bytes(int64_t npixels) { return icp_layout(npixels, NSC).bytes; }
 
 hipError_t f3d_launch_tsdf_raycast(const float* tsdf, const float* weight, int nx, int ny, int nz, const double lo[3], double vs, float min_weight,
                                    const double K[9], const double qn[4], const double t[3], int h, int w, double near, double step, int nsteps,
                                    double* vertex, double* normal, double* depth, int grid_cap, hipStream_t s) {
-    ray_volume g;
-    g.tsdf = tsdf; g.weight = weight; g.nx = nx; g.ny = ny; g.nz = nz; g.vs = vs; g.min_weight = min_weight;
-    ray_camera cam;
-    cam.fx = K[0]; cam.cx = K[2]; cam.fy = K[4]; cam.cy = K[5];
-    for (int c = 0; c < 3; ++c) { g.lo[c] = lo[c]; cam.t[c] = t[c]; }
-    for (int c = 0; c < 4; ++c) cam.qn[c] = qn[c];
-    const int64_t ntiles = (int64_t)((w + 7) / 8) * ((h + 7) / 8);
-    const int usual = F3D_GRID_CAP * 16;                                        // blocks of a launch: the usual cap, or the smaller one a test set
-    const dim3 gr(f3d_grid_for(ntiles, F3D_BLOCK / 64, grid_cap > 0 && grid_cap < usual ? grid_cap : usual)), b(F3D_BLOCK);
-    hipLaunchKernelGGL(k_tsdf_raycast, gr, b, 0, s, g, cam, h, w, near, step, nsteps, vertex, normal, depth);
+    const ray_volume g = volume_of(tsdf, weight, nx, ny, nz, lo, vs, min_weight);
+    const ray_camera cam = camera_of(K, qn, t);
+    const dim3 gr(ray_blocks(h, w, grid_cap)), b(F3D_BLOCK);
+    hipLaunchKernelGGL(k_tsdf_raycast<false>, gr, b, 0, s, g, cam, h, w, near, step, nsteps, vertex, normal, depth, ray_color_io<false>{});
+    return hipGetLastError();
+}
+
+hipError_t f3d_launch_tsdf_raycast_color(const float* tsdf, const float* weight, const float* color, int nx, int ny, int nz, const double lo[3],
+                                         double vs, float min_weight, const double K[9], const double qn[4], const double t[3], int h, int w,
+                                         double near, double step, int nsteps, double* vertex, double* normal, double* depth, double* rgb,
+                                         double* intensity, int grid_cap, hipStream_t s) {
+    const ray_volume g = volume_of(tsdf, weight, nx, ny, nz, lo, vs, min_weight);
+    const ray_camera cam = camera_of(K, qn, t);
+    ray_color_io<true> cio;
+    cio.color = (const float4*)color; cio.rgb = rgb; cio.intensity = intensity;
+    const dim3 gr(ray_blocks(h, w, grid_cap)), b(F3D_BLOCK);
+    hipLaunchKernelGGL(k_tsdf_raycast<true>, gr, b, 0, s, g, cam, h, w, near, step, nsteps, vertex, normal, depth, cio);
     return hipGetLastError();
 }
 
@@ -387,9 +566,9 @@ hipError_t f3d_launch_icp_sums(const f3d_icp_args& a, const double q[4], const d
     double *chunks = (double*)(base + l.chunks), *pose = (double*)(base + l.pose);
     int* lost = (int*)(base + l.lost);
     hipLaunchKernelGGL(k_icp_init, dim3(1), dim3(64), 0, s, pose, lost, q[0], q[1], q[2], q[3], t[0], t[1], t[2]);
-    launch_terms(a, pose, lost, chunks, s);
-    hipLaunchKernelGGL(k_icp_solve, dim3(1), dim3(F3D_BLOCK), 0, s, chunks, (npix + F3D_ICP_CHUNK - 1) / F3D_ICP_CHUNK, sums, pose, lost, 0.0,
-                       (double*)nullptr, 0);
+    launch_terms(a, pose, lost, chunks, icp_color_io<false>{}, s);
+    hipLaunchKernelGGL(k_icp_solve<false>, dim3(1), dim3(F3D_BLOCK), 0, s, chunks, (npix + F3D_ICP_CHUNK - 1) / F3D_ICP_CHUNK, sums, pose, lost, 0.0,
+                       (double*)nullptr, 0, icp_solve_color<false>{});
     return hipGetLastError();
 }
 
@@ -402,9 +581,46 @@ hipError_t f3d_launch_icp(const f3d_icp_args& a, const double q[4], const double
     int* lost = (int*)(base + l.lost);
     hipLaunchKernelGGL(k_icp_init, dim3(1), dim3(64), 0, s, pose, lost, q[0], q[1], q[2], q[3], t[0], t[1], t[2]);
     for (int round = 0; round < iterations; ++round) {
-        launch_terms(a, pose, lost, chunks, s);
-        hipLaunchKernelGGL(k_icp_solve, dim3(1), dim3(F3D_BLOCK), 0, s, chunks, (npix + F3D_ICP_CHUNK - 1) / F3D_ICP_CHUNK, (double*)nullptr, pose, lost,
-                           (double)min_pairs, stats, round);
+        launch_terms(a, pose, lost, chunks, icp_color_io<false>{}, s);
+        hipLaunchKernelGGL(k_icp_solve<false>, dim3(1), dim3(F3D_BLOCK), 0, s, chunks, (npix + F3D_ICP_CHUNK - 1) / F3D_ICP_CHUNK, (double*)nullptr, pose,
+                           lost, (double)min_pairs, stats, round, icp_solve_color<false>{});
+    }
+    F3D_TRY(hipGetLastError());
+    F3D_TRY(hipMemcpyAsync(pose_out, pose, 7 * sizeof(double), hipMemcpyDeviceToDevice, s));
+    if (status) F3D_TRY(hipMemcpyAsync(status, lost, sizeof(int32_t), hipMemcpyDeviceToDevice, s));
+    return hipSuccess;
+}
+
+hipError_t f3d_launch_icp_color_sums(const f3d_icp_args& a, const f3d_icp_color_args& c, const double q[4], const double t[3], void* scratch,
+                                     double* sums, hipStream_t s) {
+    const int64_t npix = (int64_t)a.h * a.w;
+    const icp_scratch l = icp_layout(npix, NSC);
+    char* base = (char*)scratch;
+    double *chunks = (double*)(base + l.chunks), *pose = (double*)(base + l.pose);
+    int* lost = (int*)(base + l.lost);
+    icp_solve_color<true> col;
+    col.weight = c.color_weight;
+    hipLaunchKernelGGL(k_icp_init, dim3(1), dim3(64), 0, s, pose, lost, q[0], q[1], q[2], q[3], t[0], t[1], t[2]);
+    launch_terms(a, pose, lost, chunks, color_of(c), s);
+    hipLaunchKernelGGL(k_icp_solve<true>, dim3(1), dim3(F3D_BLOCK), 0, s, chunks, (npix + F3D_ICP_CHUNK - 1) / F3D_ICP_CHUNK, sums, pose, lost, 0.0,
+                       (double*)nullptr, 0, col);
+    return hipGetLastError();
+}
+
+hipError_t f3d_launch_icp_color(const f3d_icp_args& a, const f3d_icp_color_args& c, const double q[4], const double t[3], int iterations,
+                                int min_pairs, void* scratch, double* pose_out, double* stats, int32_t* status, hipStream_t s) {
+    const int64_t npix = (int64_t)a.h * a.w;
+    const icp_scratch l = icp_layout(npix, NSC);
+    char* base = (char*)scratch;
+    double *chunks = (double*)(base + l.chunks), *pose = (double*)(base + l.pose);
+    int* lost = (int*)(base + l.lost);
+    icp_solve_color<true> col;
+    col.weight = c.color_weight;
+    hipLaunchKernelGGL(k_icp_init, dim3(1), dim3(64), 0, s, pose, lost, q[0], q[1], q[2], q[3], t[0], t[1], t[2]);
+    for (int round = 0; round < iterations; ++round) {
+        launch_terms(a, pose, lost, chunks, color_of(c), s);
+        hipLaunchKernelGGL(k_icp_solve<true>, dim3(1), dim3(F3D_BLOCK), 0, s, chunks, (npix + F3D_ICP_CHUNK - 1) / F3D_ICP_CHUNK, (double*)nullptr, pose,
+                           lost, (double)min_pairs, stats, round, col);
     }
     F3D_TRY(hipGetLastError());
     F3D_TRY(hipMemcpyAsync(pose_out, pose, 7 * sizeof(double), hipMemcpyDeviceToDevice, s));

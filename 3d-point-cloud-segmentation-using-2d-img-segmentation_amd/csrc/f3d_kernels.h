@@ -718,6 +718,23 @@ size_t f3d_icp_scratch_bytes(int64_t npixels);
 hipError_t f3d_launch_icp_sums(const f3d_icp_args& a, const double q[4], const double t[3], void* scratch, double* sums, hipStream_t s);
 hipError_t f3d_launch_icp(const f3d_icp_args& a, const double q[4], const double t[3], int iterations, int min_pairs, void* scratch,
                           double* pose_out, double* stats, int32_t* status, hipStream_t s);
+// The same with colour.  The raycast: color the state [nz, ny, nx, 4] (16-byte aligned), rgb [h*w, 3] and intensity [h*w] two more
+// optional outputs.  ICP: the model's intensity map [hm*wm], the source colour image [hc, wc_img, 3] and the weight of the photometric
+// system; scratch: f3d_icp_color_scratch_bytes(h * w), whose chunk rows are 58 wide; sums [58], stats [iterations, 5].
+hipError_t f3d_launch_tsdf_raycast_color(const float* tsdf, const float* weight, const float* color, int nx, int ny, int nz, const double lo[3],
+                                         double vs, float min_weight, const double K[9], const double qn[4], const double t[3], int h, int w,
+                                         double near, double step, int nsteps, double* vertex, double* normal, double* depth, double* rgb,
+                                         double* intensity, int grid_cap, hipStream_t s);
+struct f3d_icp_color_args {
+    const double* model_intensity;
+    const uint8_t* rgb; int hc, wc_img;
+    double color_weight;
+};
+size_t f3d_icp_color_scratch_bytes(int64_t npixels);
+hipError_t f3d_launch_icp_color_sums(const f3d_icp_args& a, const f3d_icp_color_args& c, const double q[4], const double t[3], void* scratch,
+                                     double* sums, hipStream_t s);
+hipError_t f3d_launch_icp_color(const f3d_icp_args& a, const f3d_icp_color_args& c, const double q[4], const double t[3], int iterations,
+                                int min_pairs, void* scratch, double* pose_out, double* stats, int32_t* status, hipStream_t s);
 
 // plane table of a cloud over its adjacency (f3d_planes.hip).  Device pointers (counts int64 [4] too); normals (may be NULL: PCA of the
 // rows) and normals_out (may be NULL; written in PCA mode only) float64 [n, 3].  n >= 1.  Enqueues on `s` and synchronises it every few

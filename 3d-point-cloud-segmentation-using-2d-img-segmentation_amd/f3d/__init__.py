@@ -40,6 +40,7 @@ KNN_MAX_K = 32               # F3D_KNN_MAX_K: the largest k of knn_query / trans
 TSDF_SCAN_TILE = 2048        # F3D_TSDF_SCAN_TILE: counts per tile of the extract scans (scanned by blocks of 256 threads)
 ICP_CHUNK = 256              # F3D_ICP_CHUNK: source pixels per chunk of the ICP sums (one wave per chunk)
 ICP_NSUMS = 29               # F3D_ICP_NSUMS: 21 J J^T products, 6 J r, r r and the pair count
+ICP_NSUMS_COLOR = 58         # F3D_ICP_NSUMS_COLOR: the 29 geometric sums, then the 29 of the photometric pairs
 ICP_PIVOT_EPS = 1e-10        # F3D_ICP_PIVOT_EPS: the smallest Cholesky pivot, as a fraction of the largest diagonal entry
 ICP_OK, ICP_LOST = 0, 1      # status of an icp round (f3d.h F3D_ICP_*)
 
@@ -261,6 +262,14 @@ def library():
         'f3d_icp': (i32, [vp, vp, i32, i32, i32, vp, dbl, dbl, vp, vp, vp, vp, i32, i32, vp, dbl, i32, i32, vp, vp, vp]),
         'f3d_icp_dev': (i32, [vp, vp, i32, i32, i32, vp, dbl, dbl, vp, vp, vp, vp, i32, i32, vp, dbl, i32, i32, vp, vp, vp, vp]),
         'f3d_ctx_reserve_icp': (i32, [vp, i64]),
+        'f3d_tsdf_raycast_color': (i32, [vp, vp, vp, vp, i32, i32, i32, vp, dbl, flt, vp, vp, vp, i32, i32, dbl, dbl, i32, vp, vp, vp, vp, vp]),
+        'f3d_tsdf_raycast_color_dev': (i32, [vp, vp, vp, vp, i32, i32, i32, vp, dbl, flt, vp, vp, vp, i32, i32, dbl, dbl, i32, vp, vp, vp, vp, vp, vp]),
+        'f3d_icp_color_sums': (i32, [vp, vp, i32, i32, i32, vp, dbl, dbl, vp, vp, vp, vp, i32, i32, vp, dbl, vp, vp, i32, i32, dbl, vp]),
+        'f3d_icp_color_sums_dev': (i32, [vp, vp, i32, i32, i32, vp, dbl, dbl, vp, vp, vp, vp, i32, i32, vp, dbl, vp, vp, i32, i32, dbl, vp, vp]),
+        'f3d_icp_color': (i32, [vp, vp, i32, i32, i32, vp, dbl, dbl, vp, vp, vp, vp, i32, i32, vp, dbl, vp, vp, i32, i32, dbl, i32, i32, vp, vp, vp]),
+        'f3d_icp_color_dev': (i32, [vp, vp, i32, i32, i32, vp, dbl, dbl, vp, vp, vp, vp, i32, i32, vp, dbl, vp, vp, i32, i32, dbl, i32, i32, vp, vp, vp,
+                                    vp]),
+        'f3d_ctx_reserve_icp_color': (i32, [vp, i64]),
     }
     for name, (res, args) in protos.items():
         fn = getattr(lib, name)          # AttributeError here = header/library mismatch
@@ -470,6 +479,36 @@ def _icp_arrays(depth, K, q_wxyz, t, model_vertex, model_normal, hm, wm, model_v
     if mv.size != hm * wm * 3 or mn.size != hm * wm * 3:
         raise ValueError(f'the model maps must be [{hm} * {wm}, 3], got {mv.shape} and {mn.shape}')
     return d, depth_code(d), _f64(K, (3, 3)), _f64(q_wxyz, (4,)), _f64(t, (3,)), mv, mn, _f64(np.asarray(model_view).reshape(-1), (VIEW_DOUBLES,))
+
+
+def icp_color_check(model_intensity, rgb, color_weight, hm, wm):
+    """The checks of the colour arguments of icp_color_sums / icp_color (f3d.h "colour in registration"), for NumPy arrays and torch
+    tensors alike, with no device call: model_intensity float64 with hm * wm values, rgb one uint8 [hc, wc, 3] image with pixels,
+    color_weight finite and >= 0.  TypeError for a wrong dtype, ValueError otherwise.  -> (hc, wc, color_weight)."""
+    name = lambda a: str(a.dtype).replace('torch.', '')                      # noqa: E731
+    if name(model_intensity) != 'float64':
+        raise TypeError(f'model_intensity must be float64, got {name(model_intensity)}')
+    if name(rgb) != 'uint8':
+        raise TypeError(f'the colour image must be uint8, got {name(rgb)}')
+    size = 1
+    for x in model_intensity.shape:
+        size *= int(x)
+    if size != int(hm) * int(wm):
+        raise ValueError(f'model_intensity must hold {hm} * {wm} values, got {tuple(model_intensity.shape)}')
+    shape = tuple(int(x) for x in rgb.shape)
+    if len(shape) != 3 or shape[2] != 3 or shape[0] < 1 or shape[1] < 1 or shape[0] * shape[1] >= 1 << 31:
+        raise ValueError(f'the colour image must be [hc, wc, 3] with pixels, fewer than 2^31, got {shape}')
+    color_weight = float(color_weight)
+    if not (color_weight >= 0.0 and color_weight < float('inf')):
+        raise ValueError(f'color_weight must be finite and not negative, got {color_weight}')
+    return shape[0], shape[1], color_weight
+
+
+def _icp_color_arrays(model_intensity, rgb, color_weight, hm, wm):
+    """The host arrays of the colour arguments as the C entry reads them -> (model_intensity [hm*wm], rgb [hc, wc, 3], color_weight)."""
+    mi, rgb = np.asarray(model_intensity), np.asarray(rgb)
+    _, _, color_weight = icp_color_check(mi, rgb, color_weight, hm, wm)
+    return np.ascontiguousarray(mi).reshape(-1), np.ascontiguousarray(rgb), color_weight
 
 
 def _knn_k(k):
@@ -1358,6 +1397,56 @@ class Context:
                                       _ptr(stats), C.byref(status)))
         return pose, stats, status.value
 
+    def reserve_icp_color(self, npixels):
+        """Size the scratch of icp_color_sums_dev / icp_color_dev (58-wide chunk rows; it covers icp_sums_dev / icp_dev too) for source
+        frames of up to npixels pixels."""
+        self._check(self._lib.f3d_ctx_reserve_icp_color(self._h, int(npixels)))
+
+    def tsdf_raycast_color(self, tsdf, weight, color, lo, voxel, min_weight, K, q_wxyz, t, h, w, near, step, nsteps):
+        """tsdf_raycast with the volume's colour state float32 [nz, ny, nx, 4] (f3d.h f3d_tsdf_raycast_color) -> (vertex, normal, depth
+        as tsdf_raycast gives them, rgb float64 [h*w, 3] on the 0..255 scale, intensity float64 [h*w]); NaN in the last two where a pixel
+        has no hit or its hit has no colour."""
+        nz, ny, nx = _tsdf_state(tsdf, weight)
+        _tsdf_color(color, (nz, ny, nx), writeable=False)
+        lo, K, q, t = _f64(lo, (3,)), _f64(K, (3, 3)), _f64(q_wxyz, (4,)), _f64(t, (3,))
+        h, w = int(h), int(w)
+        if h < 1 or w < 1:
+            raise ValueError('the image must have pixels')
+        vertex, normal, depth = np.empty((h * w, 3)), np.empty((h * w, 3)), np.empty(h * w)
+        rgb, intensity = np.empty((h * w, 3)), np.empty(h * w)
+        self._check(self._lib.f3d_tsdf_raycast_color(self._h, _ptr(tsdf), _ptr(weight), _ptr(color), nx, ny, nz, _ptr(lo), float(voxel),
+                                                     float(min_weight), _ptr(K), _ptr(q), _ptr(t), h, w, float(near), float(step), int(nsteps),
+                                                     _ptr(vertex), _ptr(normal), _ptr(depth), _ptr(rgb), _ptr(intensity)))
+        return vertex, normal, depth, rgb, intensity
+
+    def icp_color_sums(self, depth, K, q_wxyz, t, model_vertex, model_normal, hm, wm, model_view, max_dist, model_intensity, rgb, color_weight,
+                       depth_scale=1.0, max_depth=10.0):
+        """The 58 sums of one linearisation with colour (f3d.h f3d_icp_color_sums): the arguments of icp_sums plus the model's intensity
+        map float64 [hm*wm] (NaN = missing), the source colour image uint8 [hc, wc, 3] and color_weight -> float64 [58]."""
+        d, code, K, q, t, mv, mn, view = _icp_arrays(depth, K, q_wxyz, t, model_vertex, model_normal, hm, wm, model_view)
+        mi, rgb, color_weight = _icp_color_arrays(model_intensity, rgb, color_weight, hm, wm)
+        sums = np.empty(ICP_NSUMS_COLOR)
+        self._check(self._lib.f3d_icp_color_sums(self._h, _ptr(d), code, d.shape[0], d.shape[1], _ptr(K), float(depth_scale), float(max_depth), _ptr(q),
+                                                 _ptr(t), _ptr(mv), _ptr(mn), int(hm), int(wm), _ptr(view), float(max_dist), _ptr(mi), _ptr(rgb),
+                                                 rgb.shape[0], rgb.shape[1], color_weight, _ptr(sums)))
+        return sums
+
+    def icp_color(self, depth, K, q_wxyz, t, model_vertex, model_normal, hm, wm, model_view, max_dist, model_intensity, rgb, color_weight,
+                  depth_scale=1.0, max_depth=10.0, iterations=10, min_pairs=100):
+        """`iterations` rounds of ICP with the photometric term (f3d.h f3d_icp_color) -> (pose float64 [7] = wxyz, t; stats float64
+        [iterations, 5] = count, sum r^2, status, colour count, sum rc^2 per round; the final status ICP_OK / ICP_LOST)."""
+        d, code, K, q, t, mv, mn, view = _icp_arrays(depth, K, q_wxyz, t, model_vertex, model_normal, hm, wm, model_view)
+        mi, rgb, color_weight = _icp_color_arrays(model_intensity, rgb, color_weight, hm, wm)
+        iterations = int(iterations)
+        if iterations < 1:
+            raise ValueError(f'iterations must be at least 1, got {iterations}')
+        pose, stats, status = np.empty(7), np.empty((iterations, 5)), C.c_int32(0)
+        self._check(self._lib.f3d_icp_color(self._h, _ptr(d), code, d.shape[0], d.shape[1], _ptr(K), float(depth_scale), float(max_depth), _ptr(q),
+                                            _ptr(t), _ptr(mv), _ptr(mn), int(hm), int(wm), _ptr(view), float(max_dist), _ptr(mi), _ptr(rgb),
+                                            rgb.shape[0], rgb.shape[1], color_weight, iterations, int(min_pairs), _ptr(pose), _ptr(stats),
+                                            C.byref(status)))
+        return pose, stats, status.value
+
     def radius_graph(self, points, radius):
         """KDTree(points).query_radius(points, r=radius) (fusion.py:374-375) as CSR: (offsets int64 [n+1], neighbours int32)."""
         p, dt = _xyz(points)
@@ -1686,6 +1775,35 @@ class Context:
         self._check(self._lib.f3d_icp_dev(self._h, depth_ptr, int(depth_type), int(h), int(w), _ptr(K), float(depth_scale), float(max_depth), _ptr(q),
                                           _ptr(t), vertex_ptr, normal_ptr, int(hm), int(wm), view_ptr, float(max_dist), int(iterations),
                                           int(min_pairs), pose_ptr, stats_ptr, status_ptr, stream))
+
+    def tsdf_raycast_color_dev(self, tsdf_ptr, weight_ptr, color_ptr, dims, lo, voxel, min_weight, K, q_wxyz, t, h, w, near, step, nsteps, vertex_ptr,
+                               normal_ptr, depth_ptr, rgb_ptr, intensity_ptr, stream=None):
+        """tsdf_raycast_dev with the colour state [nz, ny, nx, 4] (16-byte aligned) and two more outputs, rgb float64 [h*w, 3] and intensity
+        float64 [h*w]; each of the five may be None (f3d.h f3d_tsdf_raycast_color_dev).  Enqueue only."""
+        lo, K, q, t = _f64(lo, (3,)), _f64(K, (3, 3)), _f64(q_wxyz, (4,)), _f64(t, (3,))
+        nx, ny, nz = (int(x) for x in dims)
+        self._check(self._lib.f3d_tsdf_raycast_color_dev(self._h, tsdf_ptr, weight_ptr, color_ptr, nx, ny, nz, _ptr(lo), float(voxel), float(min_weight),
+                                                         _ptr(K), _ptr(q), _ptr(t), int(h), int(w), float(near), float(step), int(nsteps), vertex_ptr,
+                                                         normal_ptr, depth_ptr, rgb_ptr, intensity_ptr, stream))
+
+    def icp_color_sums_dev(self, depth_ptr, depth_type, h, w, K, q_wxyz, t, vertex_ptr, normal_ptr, hm, wm, view_ptr, max_dist, intensity_ptr, rgb_ptr,
+                           hc, wc, color_weight, depth_scale, max_depth, sums_ptr, stream=None):
+        """As icp_sums_dev, plus the model's intensity map float64 [hm*wm] and the source colour image uint8 [hc, wc, 3] on the device;
+        sums float64 [58].  Enqueue only."""
+        K, q, t = _f64(K, (3, 3)), _f64(q_wxyz, (4,)), _f64(t, (3,))
+        self._check(self._lib.f3d_icp_color_sums_dev(self._h, depth_ptr, int(depth_type), int(h), int(w), _ptr(K), float(depth_scale), float(max_depth),
+                                                     _ptr(q), _ptr(t), vertex_ptr, normal_ptr, int(hm), int(wm), view_ptr, float(max_dist), intensity_ptr,
+                                                     rgb_ptr, int(hc), int(wc), float(color_weight), sums_ptr, stream))
+
+    def icp_color_dev(self, depth_ptr, depth_type, h, w, K, q_wxyz, t, vertex_ptr, normal_ptr, hm, wm, view_ptr, max_dist, intensity_ptr, rgb_ptr, hc, wc,
+                      color_weight, depth_scale, max_depth, iterations, min_pairs, pose_ptr, stats_ptr, status_ptr=None, stream=None):
+        """As icp_color_sums_dev; pose float64 [7], stats float64 [iterations, 5] and status int32 [1] (may be None) on the device.  Enqueue
+        only: no host synchronisation between the rounds or after them."""
+        K, q, t = _f64(K, (3, 3)), _f64(q_wxyz, (4,)), _f64(t, (3,))
+        self._check(self._lib.f3d_icp_color_dev(self._h, depth_ptr, int(depth_type), int(h), int(w), _ptr(K), float(depth_scale), float(max_depth),
+                                                _ptr(q), _ptr(t), vertex_ptr, normal_ptr, int(hm), int(wm), view_ptr, float(max_dist), intensity_ptr,
+                                                rgb_ptr, int(hc), int(wc), float(color_weight), int(iterations), int(min_pairs), pose_ptr, stats_ptr,
+                                                status_ptr, stream))
 
     def take_device_error(self, stream=None):
         self._check(self._lib.f3d_take_device_error(self._h, stream))

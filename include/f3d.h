@@ -1404,6 +1404,73 @@ int f3d_icp_dev(f3d_ctx* ctx, const void* depth, int depth_type, int h, int w, c
                 int min_pairs, double* pose, double* stats, int32_t* status /*device, may be NULL*/, void* stream);
 int f3d_ctx_reserve_icp(f3d_ctx* ctx, int64_t npixels);
 
+/* Colour in registration: the volume's colour rendered along with its maps, and a photometric term in the ICP.  Depth cannot see a
+ * motion that maps the geometry onto itself (along a wall, about the axis of a round object); the colour images can.  Everything
+ * above holds: float64 without contraction, every product, sum and division as written.
+ * f3d_tsdf_raycast_color: the arguments of f3d_tsdf_raycast plus color float32 [nz, ny, nx, 4], the state of
+ * f3d_tsdf_integrate_color (a device pointer must be 16-byte aligned), and two more optional outputs: rgb float64 [h*w, 3] on the
+ * 0..255 scale and intensity float64 [h*w].  vertex, normal and depth are f3d_tsdf_raycast's, bit for bit.
+ *   colour     for a hit at V: g, i, f as in F(P) at P = V.  The colour sample is valid iff the index rule of F(P) holds at V and all 8
+ *              corners have wc > 0 (their TSDF weights play no part).  Per channel, with the corner values C_ijk widened to double:
+ *              c_jk = C0jk + f_x * (C1jk - C0jk); c_k = c_0k + f_y * (c_1k - c_0k); value = c_0 + f_z * (c_1 - c_0).
+ *   intensity  ((0.299 * R + 0.587 * G) + 0.114 * B) / 255.0.
+ *   missing    a hit whose colour sample is invalid keeps its vertex, normal and depth and gets NaN in rgb and intensity; so does a
+ *              pixel without a hit.
+ * f3d_icp_color_sums: the arguments of f3d_icp_sums plus model_intensity float64 [hm*wm] (NaN = missing; f3d_tsdf_raycast_color's),
+ * the source colour image rgb uint8 [hc, wc_img, 3] (hc, wc_img > 0 with a product < 2^31, of any size) and color_weight, finite and
+ * >= 0 (read by f3d_icp_color only).  Steps 1 to 7 are unchanged and give the first 29 sums.  A pixel that passed step 5 contributes
+ * a photometric pair as well iff all of this holds:
+ *   source     uc = (int64)u * wc_img / w, vc = (int64)v * hc / h (the colour pixel of f3d_tsdf_integrate_color); Is = the intensity
+ *              of that pixel's three bytes.
+ *   model      a = x - 0.5, b = y - 0.5 with (x, y) of step 3; i0 = floor(a), j0 = floor(b); 0 <= i0 <= wm - 2 and 0 <= j0 <= hm - 2;
+ *              fa = a - i0, fb = b - j0; the taps I00 = I[j0, i0], I10 = I[j0, i0+1], I01 = I[j0+1, i0], I11 = I[j0+1, i0+1] all
+ *              finite.  top = I00 + fa * (I10 - I00); bot = I01 + fa * (I11 - I01); Im = top + fb * (bot - top); dx0 = I10 - I00,
+ *              dx1 = I11 - I01; gx = dx0 + fb * (dx1 - dx0); gy = bot - top.
+ *   residual   rc = Im - Is.
+ *   gradient   with the rows K0, K1, K2 of the model view's K and h2 of step 3, for k = 0, 1, 2:
+ *              gc_k = (gx * (K0k - x * K2k) + gy * (K1k - y * K2k)) / h2; gw = rotate(conj(qinv_m), gc), conj(q) = (q0, -q1, -q2, -q3).
+ *   Jc         (cross(pr, gw), gw): the shape of J with gw in place of N.
+ * The pair adds a second set of 29 terms after the first: the 21 products Jc_a * Jc_b, the 6 products Jc_a * rc, rc * rc, 1.0;
+ * F3D_ICP_NSUMS_COLOR = 58 sums, each of the shape above.  Output: sums float64 [58].
+ * f3d_icp_color: the rounds of f3d_icp with A = A_g + color_weight * A_c (entry by entry) and b_a = -(bg_a + color_weight * bc_a); the
+ * lost rule uses the geometric count; Cholesky, the pivot rule, the update and "once lost" are f3d_icp's.  stats float64
+ * [iterations, 5] = {count, sum r*r, status, colour count, sum rc*rc}; rows after a lost round are {0, 0, 1, 0, 0}.
+ * Scratch: the chunk sums [nchunks, 58], the pose and the lost flag; f3d_ctx_reserve_icp_color(npixels) sizes it (and covers the
+ * 29-sum entries), a strict context then allocates nothing in the _dev entries.  F3D_ERR_INVALID, with nothing written: the bad
+ * arguments of f3d_tsdf_raycast / f3d_icp_sums / f3d_icp; a NULL color, model_intensity or rgb; a device color that is not 16-byte
+ * aligned; hc or wc_img < 1 or hc * wc_img >= 2^31; a negative or non-finite color_weight.
+ * Out of scope: robust weights, an intensity-difference gate, image pyramids, exposure compensation, colour from anything but the
+ * volume. */
+#define F3D_ICP_NSUMS_COLOR 58
+int f3d_tsdf_raycast_color(f3d_ctx* ctx, const float* tsdf, const float* weight, const float* color /*[nz,ny,nx,4]*/, int nx, int ny, int nz,
+                           const double lo[3], double vs, float min_weight, const double K[9], const double q_wxyz[4], const double t[3],
+                           int h, int w, double znear, double step, int nsteps, double* vertex /*[h*w,3]*/, double* normal /*[h*w,3]*/,
+                           double* depth /*[h*w]*/, double* rgb /*[h*w,3]*/, double* intensity /*[h*w]*/);
+int f3d_tsdf_raycast_color_dev(f3d_ctx* ctx, const float* tsdf, const float* weight, const float* color, int nx, int ny, int nz,
+                               const double lo[3] /*host*/, double vs, float min_weight, const double K[9] /*host*/,
+                               const double q_wxyz[4] /*host*/, const double t[3] /*host*/, int h, int w, double znear, double step,
+                               int nsteps, double* vertex, double* normal, double* depth, double* rgb, double* intensity, void* stream);
+int f3d_icp_color_sums(f3d_ctx* ctx, const void* depth, int depth_type, int h, int w, const double K[9], double depth_scale,
+                       double max_depth, const double q_wxyz[4], const double t[3], const double* model_vertex, const double* model_normal,
+                       int hm, int wm, const f3d_view* model_view, double max_dist, const double* model_intensity /*[hm*wm]*/,
+                       const uint8_t* rgb /*[hc,wc_img,3]*/, int hc, int wc_img, double color_weight, double* sums /*[58]*/);
+int f3d_icp_color_sums_dev(f3d_ctx* ctx, const void* depth, int depth_type, int h, int w, const double K[9] /*host*/, double depth_scale,
+                           double max_depth, const double q_wxyz[4] /*host*/, const double t[3] /*host*/, const double* model_vertex,
+                           const double* model_normal, int hm, int wm, const f3d_view* model_view /*device*/, double max_dist,
+                           const double* model_intensity, const uint8_t* rgb, int hc, int wc_img, double color_weight, double* sums,
+                           void* stream);
+int f3d_icp_color(f3d_ctx* ctx, const void* depth, int depth_type, int h, int w, const double K[9], double depth_scale, double max_depth,
+                  const double q_wxyz[4], const double t[3], const double* model_vertex, const double* model_normal, int hm, int wm,
+                  const f3d_view* model_view, double max_dist, const double* model_intensity, const uint8_t* rgb, int hc, int wc_img,
+                  double color_weight, int iterations, int min_pairs, double* pose /*[7]*/, double* stats /*[iterations,5]*/,
+                  int32_t* status);
+int f3d_icp_color_dev(f3d_ctx* ctx, const void* depth, int depth_type, int h, int w, const double K[9] /*host*/, double depth_scale,
+                      double max_depth, const double q_wxyz[4] /*host*/, const double t[3] /*host*/, const double* model_vertex,
+                      const double* model_normal, int hm, int wm, const f3d_view* model_view /*device*/, double max_dist,
+                      const double* model_intensity, const uint8_t* rgb, int hc, int wc_img, double color_weight, int iterations,
+                      int min_pairs, double* pose, double* stats, int32_t* status /*device, may be NULL*/, void* stream);
+int f3d_ctx_reserve_icp_color(f3d_ctx* ctx, int64_t npixels);
+
 #ifdef __cplusplus
 }
 #endif
