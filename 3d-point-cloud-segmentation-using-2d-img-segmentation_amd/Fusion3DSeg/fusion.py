@@ -20,7 +20,7 @@ from pathlib import Path
 import numpy as np
 
 import f3d
-from f3d.tensors import dtype_code, index_code, on_device, torch_device, work_stream
+from f3d.tensors import dtype_code, index_code, on_device, torch_device, upload, work_stream
 
 
 def parse_rts(rts):
@@ -77,7 +77,7 @@ def render_lookups(points, K, wxyzs, translations, hw, max_depth=10, splat=0):
     torch, dev = torch_device(ctx, 'render_lookups')
     pts = _device_cloud(torch, dev, points)
     with torch.cuda.device(dev), work_stream(dev) as work:
-        dviews = torch.from_numpy(views).to(dev)
+        dviews = upload(views, dev)
         depth = torch.empty((len(views), H, W), dtype=torch.float32, device=dev)
         uv2pt = torch.empty((len(views), H * W), dtype=torch.int32, device=dev)
         ctx.render_lookups_dev(pts.data_ptr(), dtype_code(pts), len(pts), dviews.data_ptr(), len(views), H, W, splat, depth.data_ptr(),
@@ -122,7 +122,7 @@ def project_vote_argmax_visible(points, K, wxyzs, translations, masks, max_depth
         raise ValueError(f'masks must be uint8, got {dmasks.dtype}')
     dmasks = dmasks.contiguous()
     with torch.cuda.device(dev), work_stream(dev) as work:
-        dviews = torch.from_numpy(views).to(dev)
+        dviews = upload(views, dev)
         votes = torch.zeros((len(pts), nclasses + 1), dtype=torch.float64, device=dev)
         cls = torch.empty(len(pts), dtype=torch.int64, device=dev)
         ctx.vote_visible_dev(pts.data_ptr(), dtype_code(pts), len(pts), dviews.data_ptr(), V, dmasks.data_ptr(), H, W, splat, depth_tol,
@@ -165,7 +165,7 @@ def render_mesh_lookups(vertices, triangles, K, wxyzs, translations, hw, max_dep
     torch, dev = torch_device(ctx, 'render_mesh_lookups')
     verts, tris = _device_mesh(torch, dev, vertices, triangles)
     with torch.cuda.device(dev), work_stream(dev) as work:
-        dviews = torch.from_numpy(views).to(dev)
+        dviews = upload(views, dev)
         depth = torch.empty((len(views), H, W), dtype=torch.float32, device=dev)
         uv2tri = torch.empty((len(views), H * W), dtype=torch.int32, device=dev)
         straddling = torch.empty(len(views), dtype=torch.int64, device=dev)
@@ -212,7 +212,7 @@ def project_vote_argmax_occluded(points, vertices, triangles, K, wxyzs, translat
         raise ValueError(f'masks must be uint8, got {dmasks.dtype}')
     dmasks = dmasks.contiguous()
     with torch.cuda.device(dev), work_stream(dev) as work:
-        dviews = torch.from_numpy(views).to(dev)
+        dviews = upload(views, dev)
         votes = torch.zeros((len(pts), nclasses + 1), dtype=torch.float64, device=dev)
         cls = torch.empty(len(pts), dtype=torch.int64, device=dev)
         ctx.vote_visible_mesh_dev(pts.data_ptr(), dtype_code(pts), len(pts), verts.data_ptr(), dtype_code(verts), len(verts), tris.data_ptr(),

@@ -146,8 +146,10 @@ class HipCloud:
         if self.torch is None:
             return self.ctx.group_by_id(ids, nids)
         torch = self.torch
+        resident = torch.is_tensor(ids)
+        if resident:
+            self._resident_ids(ids)
         with torch.cuda.stream(self.stream):
-            resident = torch.is_tensor(ids)
             dids = ids if resident else torch.from_numpy(np.ascontiguousarray(ids, dtype=np.int64)).to(self.device)
             self.d_order = torch.empty(self.n, dtype=torch.int32, device=self.device)
             self.d_keys = torch.empty(self.n, dtype=torch.int32, device=self.device)
@@ -159,8 +161,14 @@ class HipCloud:
             # resident ids: the member lists stay on the device (nobody relabels a host array); only the segment bounds come back
             return (None if resident else self.d_order.cpu().numpy()), self.d_starts.cpu().numpy()
 
+    def _resident_ids(self, ids):
+        """Resident ids are read, and relabelled, where they lie: through their data pointer."""
+        if not (self.torch.is_tensor(ids) and ids.is_cuda and ids.dtype == self.torch.int64 and ids.dim() == 1 and len(ids) == self.n and ids.is_contiguous()):
+            raise ValueError(f'resident ids must be a contiguous int64 CUDA tensor [{self.n}]')
+
     def relabel(self, ids, src, dst):
         """ids[ids == src] = dst on the device tensor `ids` (update_id_info, merge_intersecting_bb.py:59-61)."""
+        self._resident_ids(ids)
         with self.torch.cuda.stream(self.stream):
             self.ctx.relabel_dev(ids.data_ptr(), self.n, int(src), int(dst), None, self.stream.cuda_stream)
 

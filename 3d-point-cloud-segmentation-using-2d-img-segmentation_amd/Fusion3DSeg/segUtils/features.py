@@ -16,7 +16,7 @@ NumPy arrays in, NumPy arrays back; device tensors for ``points`` or ``features`
 import numpy as np
 
 import f3d
-from f3d.tensors import device_points, dtype_code, on_device, torch_device, work_stream
+from f3d.tensors import device_points, dtype_code, on_device, torch_device, upload, work_stream
 
 __all__ = ['fuse_features', 'FeatureFusion', 'soft_votes', 'classify_features']
 
@@ -71,7 +71,7 @@ def _fuse(points, K, wxyzs, translations, features, H, W, max_depth, splat, dept
             sums = torch.zeros((npts, d), dtype=torch.float32, device=dev)
             counts = torch.zeros(npts, dtype=torch.int32, device=dev)
         ft = f3d.features_check(sums, counts, feats, len(views), len(pts))
-        dviews = torch.from_numpy(views).to(dev)
+        dviews = upload(views, dev)
         ctx.fuse_features_dev(pts.data_ptr(), dtype_code(pts), len(pts), dviews.data_ptr(), V, H, W, feats.data_ptr(), ft,
                               int(feats.shape[1]), int(feats.shape[2]), d, splat, depth_tol, sums.data_ptr(), counts.data_ptr(), 0,
                               work.cuda_stream)

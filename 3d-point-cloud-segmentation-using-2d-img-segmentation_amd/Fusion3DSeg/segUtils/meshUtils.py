@@ -16,7 +16,7 @@ import math
 import numpy as np
 
 import f3d
-from f3d.tensors import dtype_code, index_code, on_device, work_stream
+from f3d.tensors import dtype_code, index_code, on_device, upload, work_stream
 
 __all__ = ['vertex_triangle_mapping', 'remove_faces_by_vertices', 'keep_faces_by_vertices', 'get_triangle_clusters', 'clean_mesh', 'label_faces',
            'face_normals', 'face_adjacency', 'segment_faces_from_votes', 'segment_faces', 'bbox_axes', 'one_to_all_angles', 'VertexTriangleMap']
@@ -333,7 +333,7 @@ def _label_faces(vertices, triangles, K, wxyzs, translations, masks, max_depth=1
         raise ValueError(f'masks must be uint8, got {dmasks.dtype}')
     dmasks = dmasks.contiguous()
     with torch.cuda.device(dev), work_stream(dev) as work:
-        dviews = torch.from_numpy(views).to(dev)
+        dviews = upload(views, dev)
         votes = torch.zeros((nt, ncols), dtype=torch.float64, device=dev)
         cls = torch.empty(nt, dtype=torch.int64, device=dev)
         ctx.vote_faces_dev(verts.data_ptr(), dtype_code(verts), verts.shape[0], tris.data_ptr(), index_code(tris), nt, dviews.data_ptr(), V,

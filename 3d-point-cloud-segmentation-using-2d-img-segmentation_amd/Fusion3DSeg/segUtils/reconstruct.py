@@ -19,7 +19,7 @@ import math
 import numpy as np
 
 import f3d
-from f3d.tensors import depth_code, on_device, torch_device, work_stream
+from f3d.tensors import depth_code, on_device, torch_device, upload, work_stream
 
 __all__ = ['TSDFVolume', 'reconstruct_mesh', 'depth_images']
 
@@ -66,9 +66,9 @@ class TSDFVolume:
         if not self.on_device:
             ctx = f3d.default_context()
             torch, dev = torch_device(ctx, 'TSDFVolume(device=True)')
-            self.tsdf, self.weight = torch.from_numpy(self.tsdf).to(dev), torch.from_numpy(self.weight).to(dev)
+            self.tsdf, self.weight = upload(self.tsdf, dev), upload(self.weight, dev)
             if self.color is not None:
-                self.color = torch.from_numpy(self.color).to(dev)
+                self.color = upload(self.color, dev)
 
     def integrate(self, depths, K, wxyzs, translations, depth_scale=1.0, max_depth=10, colors=None):
         """Integrates the depth frames ``depths`` [F, h, w] (uint16, float32 or float64; raw / depth_scale = metres along the camera
@@ -108,7 +108,7 @@ class TSDFVolume:
             rgb = (colors if on_device(colors) else torch.from_numpy(np.ascontiguousarray(colors))).to(dev).contiguous()
             used.append(rgb)
         with torch.cuda.device(dev), work_stream(dev) as work:
-            dviews = torch.from_numpy(views).to(dev)
+            dviews = upload(views, dev)
             if colors is None:
                 ctx.tsdf_integrate_dev(self.tsdf.data_ptr(), self.weight.data_ptr(), self.dims, self.lo, self.voxel, self.trunc, self.max_weight,
                                        d.data_ptr(), code, F, h, w, depth_scale, max_depth, dviews.data_ptr(), work.cuda_stream)
@@ -210,7 +210,7 @@ def depth_images(frame_points, wxyzs, translations, valid=None):
     out = torch.zeros((F, h, w), dtype=torch.float64, device=dev)
     with torch.cuda.device(dev), work_stream(dev) as work:
         for f in range(F):
-            rel = (pts[f] - torch.from_numpy(t[f]).to(dev)).reshape(-1, 3).contiguous()
+            rel = (pts[f] - upload(t[f], dev)).reshape(-1, 3).contiguous()
             cam = torch.empty_like(rel)
             ctx.rotate_dev(rel.data_ptr(), len(rel), qinv[f], cam.data_ptr(), work.cuda_stream)
             ok = torch.isfinite(pts[f]).all(dim=-1)

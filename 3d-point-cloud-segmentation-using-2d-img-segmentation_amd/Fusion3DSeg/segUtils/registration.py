@@ -23,7 +23,7 @@ import math
 import numpy as np
 
 import f3d
-from f3d.tensors import depth_code, on_device, torch_device, work_stream
+from f3d.tensors import depth_code, on_device, torch_device, upload, work_stream
 
 __all__ = ['raycast', 'icp_sums', 'icp', 'track_frames']
 
@@ -203,7 +203,7 @@ def _to_device(torch, dev, depth, model_vertex, model_normal, view):
     as_tensor = lambda a: a if on_device(a) else torch.from_numpy(np.ascontiguousarray(a))     # noqa: E731
     d = as_tensor(depth).to(dev).contiguous()
     mv, mn = (as_tensor(a).to(dev, torch.float64).contiguous() for a in (model_vertex, model_normal))
-    return d, mv, mn, torch.from_numpy(view).to(dev)
+    return d, mv, mn, upload(view, dev)
 
 
 def _icp_device(ctx, torch, dev, work, d, code, K, q, t, mv, mn, hm, wm, dview, max_dist, depth_scale, max_depth, iterations, min_pairs):
@@ -347,7 +347,7 @@ def track_frames(volume, depths, K, wxyzs, translations, depth_scale=1.0, max_de
             view = f3d.views_build(K, w, h, q[None], t[None], max_depth)
             with torch.cuda.device(dev), work_stream(dev) as work:
                 vertex, normal = (torch.empty((h * w, 3), dtype=torch.float64, device=dev) for _ in range(2))
-                dview = torch.from_numpy(view).to(dev)
+                dview = upload(view, dev)
                 used = [vertex, normal, dview]
                 if color_weight is None:
                     ctx.tsdf_raycast_dev(volume.tsdf.data_ptr(), volume.weight.data_ptr(), volume.dims, volume.lo, volume.voxel, min_weight, K, q, t, h,

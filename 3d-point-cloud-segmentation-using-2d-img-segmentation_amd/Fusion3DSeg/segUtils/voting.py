@@ -149,17 +149,21 @@ class _DeviceVotes:
 
     def add_frames(self, luts, masks, h, w):
         """Frames of h*w lookups each, in order, as ONE batched call.  The lookups may be device tensors (the int32 [h*w] ones
-        Fusion.fuse_device hands its lookup_sink): they are stacked on the device, after the work of the caller's current stream."""
+        Fusion.fuse_device hands its lookup_sink): they are stacked on the caller's current stream, so the caller may free or rewrite
+        them as soon as this returns; the vote of the stacked copies follows on the session's stream."""
         if not luts:
             return
         if self.torch is not None and isinstance(luts[0], self.torch.Tensor):
             torch = self.torch
-            self.stream.wait_stream(torch.cuda.current_stream(self.dev))
+            caller = torch.cuda.current_stream(self.dev)
+            dl = torch.stack([t.reshape(-1).to(self.dev, torch.int32) for t in luts])
+            dm = torch.stack([torch.as_tensor(mk).reshape(-1).to(self.dev, torch.uint8) for mk in masks])
+            self.stream.wait_stream(caller)
             with torch.cuda.stream(self.stream):
-                dl = torch.stack([t.reshape(-1).to(self.dev, torch.int32) for t in luts])
-                dm = torch.stack([torch.as_tensor(mk).reshape(-1).to(self.dev, torch.uint8) for mk in masks])
                 self.ctx.vote_uv2pt_batch_dev(dl.data_ptr(), dm.data_ptr(), len(luts), h, w, self.t.data_ptr(), self.t.shape[0], self.t.shape[1],
                                               self.stream.cuda_stream)
+            for t in (dl, dm):                                          # memory of the caller's stream, read on the session's
+                t.record_stream(self.stream)
             return
         lut = np.ascontiguousarray(np.stack(luts), dtype=np.int32)
         m = np.ascontiguousarray(np.stack(masks), dtype=np.uint8)

@@ -51,6 +51,15 @@ def work_stream(device):
             caller.wait_stream(work)
 
 
+def upload(a, dev):
+    """A host array (a view table, a pose, a volume's zeros) as a tensor on `dev`, enqueued on the current stream with no host stall:
+    it goes through pinned memory.  ``torch.from_numpy(a).to(dev)`` of a pageable array returns only when the copy is done, and the copy
+    is ordered behind the stream's earlier work, so the host would wait for all of it.  torch's host allocator keeps the pinned block
+    until the copy has run."""
+    import torch
+    return torch.from_numpy(np.ascontiguousarray(a)).pin_memory().to(dev, non_blocking=True)
+
+
 def dtype_code(a):
     """f3d.F32 / f3d.F64 of a float32 / float64 array or tensor."""
     import f3d
