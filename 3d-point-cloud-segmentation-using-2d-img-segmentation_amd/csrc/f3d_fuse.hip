@@ -1697,8 +1697,11 @@ hipError_t f3d_launch_cell_sort_with_riders(f3d_fuse_job& j, uint8_t* coded, f3d
     const int64_t fill = unlabelled_after_remap(j.nclasses, j.flt);
     j.filled = fill != F3D_NO_PREFILL;
     r.classes = j.filled ? j.classes : nullptr; r.n = j.n; r.fill_value = fill;
-    const int pb = r.presence ? f3d_grid_for(r.mask_bytes >> 4, F3D_RIDER_THREADS * F3D_RIDER_UNROLL_1, F3D_RIDER_BLOCKS_1) : 0;
-    const int fb = j.filled ? f3d_grid_for(j.n, F3D_RIDER_THREADS * 8, F3D_RIDER_BLOCKS_1) : 0;
+    const bool small = j.n < F3D_RIDER_SMALL_POINTS;
+    const int cap1 = small ? F3D_RIDER_BLOCKS_1_SMALL : F3D_RIDER_BLOCKS_1;
+    const int pb = r.presence ? f3d_grid_for(r.mask_bytes >> 4, F3D_RIDER_THREADS * F3D_RIDER_UNROLL_1, cap1) : 0;
+    r.fill_blocks = (j.filled && !small && F3D_RIDER_BLOCKS_FILL > 0) ? f3d_grid_for(j.n, F3D_RIDER_THREADS * 8, F3D_RIDER_BLOCKS_FILL) : 0;
+    const int fb = (j.filled && r.fill_blocks == 0) ? f3d_grid_for(j.n, F3D_RIDER_THREADS * 8, cap1) : 0;
     r.pass1_blocks = pb > fb ? pb : fb;
     r.setup = setup_args_for(j, cb, true); r.setup_blocks = 9;
     r.coded = coded; r.V = j.nviews; r.H = j.h; r.W = j.w;

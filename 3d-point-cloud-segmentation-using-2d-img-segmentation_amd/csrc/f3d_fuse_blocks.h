@@ -26,16 +26,27 @@
 // ------------------------------------------------------------------------------------------
 #define F3D_RIDER_THREADS 512                // threads of a rider block = those of the sort's scatter passes
 #ifndef F3D_RIDER_UNROLL
-#define F3D_RIDER_UNROLL 6                   // loads a rider thread keeps in flight (coding; 8 takes 82 VGPRs: pass 2 must stay at 80 or below)
+#define F3D_RIDER_UNROLL 6                   // loads a rider thread keeps in flight (coding; 8 took 82 VGPRs: pass 2 must stay at 64 or below for its 4 blocks per CU)
 #endif
 #ifndef F3D_RIDER_UNROLL_1
-#define F3D_RIDER_UNROLL_1 8                 // ... presence, 16-byte loads (pass 1 must stay at 80 VGPRs or below for its 3 blocks per CU)
+#define F3D_RIDER_UNROLL_1 8                 // ... presence, 16-byte loads (pass 1 must stay at 64 VGPRs or below for its 4 blocks per CU)
 #endif
 #ifndef F3D_RIDER_BLOCKS_1
 #define F3D_RIDER_BLOCKS_1 256               // rider blocks beside pass 1 (presence, fill), at most
 #endif
 #ifndef F3D_RIDER_BLOCKS_2
 #define F3D_RIDER_BLOCKS_2 1024              // ... beside pass 2 (coding)
+#endif
+#ifndef F3D_RIDER_BLOCKS_FILL
+#define F3D_RIDER_BLOCKS_FILL 512            // ... beside k_rs_hist2 (the label fill of a large cloud; 0: the fill always rides beside pass 1)
+#endif
+// A small cloud (fewer sort tiles than two per CU, as in f3d_launch_cell_sort) does not fill the chip: its riders run on idle CUs beside
+// pass 1, where fewer of them disturb the tiles less, and k_rs_hist2 is too short to carry the fill (profiles/sort_occupancy.md).
+#ifndef F3D_RIDER_SMALL_POINTS
+#define F3D_RIDER_SMALL_POINTS (512 * 8192)
+#endif
+#ifndef F3D_RIDER_BLOCKS_1_SMALL
+#define F3D_RIDER_BLOCKS_1_SMALL 128         // rider blocks beside pass 1 of a small cloud (presence and the fill)
 #endif
 #define F3D_CODE_NONE 0u
 #define F3D_CODE_BAD 1u
@@ -108,7 +119,7 @@ __device__ __forceinline__ void f3d_presence_block(const uint8_t* __restrict__ s
 // The same for a rider block (src 8-byte aligned, at least 256 threads).  A rider holds one of the host kernel's few resident slots,
 // so what it keeps in flight per thread decides what the riders cost the host: 16-byte loads, UNROLL of them requested before the first
 // is looked at, and the set kept as 256 flag bytes in LDS (stores without a return value) instead of eight registers and twelve
-// instructions per mark -- the register form of this loop does not fit the 80 VGPRs pass 1 of the sort may use.  A block takes
+// instructions per mark -- the register form of this loop does not fit the 64 VGPRs pass 1 of the sort may use.  A block takes
 // nthr * UNROLL consecutive 16-byte pairs per step (one uniform base, 32-bit lane offsets); a word in front of the first 16-byte
 // boundary, one behind the last pair and the last nbytes & 7 bytes are block 0's.
 template <int UNROLL>
@@ -339,9 +350,10 @@ __device__ __forceinline__ void f3d_fuse_setup_block(const f3d_setup_args& a, in
 // The riders of one cell sort (f3d_launch_cell_sort, f3d_kernels.h), as the launcher hands them to the sort
 struct f3d_sort_riders {
     // beside k_rs_scatter<1> (pass1_blocks rider blocks): label presence over all mask bytes (presence == false: the filter book needs
-    // none), then the label fill (classes == NULL: no fill)
+    // none), then the label fill (classes == NULL: no fill; fill_blocks > 0: not here)
     const uint8_t* masks; int64_t mask_bytes; f3d_codebook* cb; bool presence;
     int64_t* classes; int64_t n; int64_t fill_value; int pass1_blocks;
+    int fill_blocks;                         // > 0: the label fill rides beside k_rs_hist2 instead (that many rider blocks; large clouds)
     // inside the second k_rs_scan's launch: k_fuse_setup with the book (setup_blocks, the last of them the book's)
     f3d_setup_args setup; int setup_blocks;
     // beside k_rs_scatter<2>: mask coding

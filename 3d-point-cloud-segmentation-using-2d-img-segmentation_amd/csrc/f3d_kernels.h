@@ -395,8 +395,9 @@ hipError_t f3d_launch_fastpath_audit(const void* xyz, int dtype, int64_t n, cons
 // cell sort (f3d_sort.hip): perm (and sorted_xyz unless NULL) receive the cloud in grid-cell order; scratch >= f3d_sort_scratch_bytes(n)
 size_t f3d_sort_scratch_bytes(int64_t n);
 // riders (internal, f3d_fuse_blocks.h; NULL = none): streaming work of the fused call that depends on nothing the sort produces and runs
-// as extra blocks of three of the sort's launches -- label presence and the label fill beside pass 1, k_fuse_setup with the book inside
-// the second scan's launch, mask coding beside pass 2.  Ordering between them comes from the launches alone.
+// as extra blocks of the sort's launches -- label presence beside pass 1, the label fill beside the high-byte histogram (a small cloud:
+// beside pass 1), k_fuse_setup with the book inside the second scan's launch, mask coding beside pass 2.  Ordering between them comes
+// from the launches alone.
 struct f3d_sort_riders;
 hipError_t f3d_launch_cell_sort(const void* xyz, int dtype, int64_t n, void* sorted_xyz, int32_t* perm, void* scratch, hipStream_t s,
                                 const f3d_sort_riders* riders = nullptr);
@@ -411,6 +412,26 @@ __host__ __device__ inline f3d_block_role f3d_rider_role(unsigned b, unsigned gr
     r.rider = upto != before;
     r.index = r.rider ? (int)before : (int)(b - before);
     return r;
+}
+// Which run of a sorted tile a position lies in, without a byte per position (pass 1 of the cell sort, f3d_sort.hip: its record carries
+// the OTHER byte of the key).  The tile's keys stand in runs of equal digit value; a run is known by its rank among the non-empty runs.
+//   starts[w]  64-bit word w of a bitmap over the tile's positions: bit p & 63 of word p >> 6 is set when a run starts at position p
+//   before[w]  the runs that start in front of word w's first position (before[0] = 0)
+// The owner of a non-empty run (start, count, rank) sets the run's bit and writes rank + 1 to before[w] of every word w whose first
+// position comes after the run's start and no later than one past the run's end: the run that holds position 64 w - 1 is the last one
+// that starts in front of word w.  f3d_run_span_of gives the bit and that range of words (first > last: none; nwords = words of the tile,
+// no entry beyond it is ever read); f3d_run_at turns a position's word, its `before` entry and its bit number into the rank of its run.
+struct f3d_run_span { unsigned word, bit, first, last; };
+__host__ __device__ inline f3d_run_span f3d_run_span_of(unsigned start, unsigned count, unsigned nwords) {
+    f3d_run_span s;
+    s.word = start >> 6; s.bit = start & 63u;
+    s.first = (start >> 6) + 1u;
+    s.last = (start + count) >> 6;
+    if (s.last > nwords - 1u) s.last = nwords - 1u;
+    return s;
+}
+__host__ __device__ inline unsigned f3d_run_at(unsigned long long word, unsigned before, unsigned bit) {
+    return before + (unsigned)__builtin_popcountll(word & ((2ull << bit) - 1ull)) - 1u;      // (bit 63: 2 << 63 wraps to 0, - 1 = all ones)
 }
 // the one-shot call that sorts and codes: the cell sort carrying the work of f3d_launch_code_masks_with_setup and the label fill as
 // riders (f3d_fuse.hip).  Sets job.filled; the caller sets job.cmasks = coded and must not call f3d_launch_code_masks_with_setup.

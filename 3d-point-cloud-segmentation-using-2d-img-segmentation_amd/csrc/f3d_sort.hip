@@ -18,9 +18,10 @@
 //   k_rs_scatter<2>: LSD pass 2 (high byte, stable): perm
 //   k_gather_xyz   : sorted[j] = xyz[perm[j]]     (only for the "prepared layout" entry point; the
 //                    in-step sort lets the fused kernel read xyz through perm instead)
-//   k_rs_scatter_ride<1|2>, k_rs_scan_setup : the same launches with RIDER blocks (f3d_sort_riders, f3d_fuse_blocks.h): streaming work of
-//                    the one-shot fused call -- label presence + label fill, k_fuse_setup with the code book, mask coding -- that depends
-//                    on nothing the sort produces and uses the HBM bandwidth the ranking rounds leave idle
+//   k_rs_scatter_ride<1|2>, k_rs_scan_setup, k_rs_hist2 with `extra` : the same launches with RIDER blocks (f3d_sort_riders,
+//                    f3d_fuse_blocks.h): streaming work of the one-shot fused call -- label presence, the label fill (beside pass 1 for a
+//                    small cloud, beside k_rs_hist2 otherwise), k_fuse_setup with the code book, mask coding -- that depends on nothing
+//                    the sort produces and uses the HBM bandwidth the ranking rounds leave idle
 // A tile's ranks come from per-wave digit counts in LDS and, per round of 64 keys, one 64-bit lane mask per digit value in LDS (every lane
 // ORs its bit into its digit's mask, reads the mask back and counts the lanes below it: k_rs_scatter): no global atomic, no look-back
 // chain, the same perm in every run (equal keys keep their index order: both passes are stable).  (Until the lane masks a round matched
@@ -243,20 +244,44 @@ template <typename R> struct rs_rec;
 template <> struct rs_rec<uint32_t> { static constexpr int shift = 24; static constexpr uint32_t imask = 0xFFFFFFu; };
 template <> struct rs_rec<uint64_t> { static constexpr int shift = 32; static constexpr uint64_t imask = 0xFFFFFFFFull; };
 
-// histogram of the high bytes per tile of the pass-1 order
+// histogram of the high bytes per tile of the pass-1 order.  F3D_RH_THREADS threads walk the tile's 8192 records with 16-byte loads, all
+// of a thread's loads requested before the first is counted (with one 4-byte load per key and round the kernel took 15 us for 40 MB).
+// The block shape is the kernel's own, as in k_rs_keys, but here 512 threads win: 256 (every block resident at once) measured 5 us
+// slower per step at 10M points and 3 us at 1.25M (profiles/sort_occupancy.md).
+// `extra` rider blocks (f3d_sort_riders::fill_blocks, f3d_rider_role) do the label fill instead of a tile: the kernel holds 1 KB of LDS and
+// reads 4 B/point, so a rider takes no slot from it, and it runs in front of k_fuse, which is all the fill needs.
+#ifndef F3D_RH_THREADS
+#define F3D_RH_THREADS 512
+#endif
+constexpr int RH_THREADS = F3D_RH_THREADS;
 template <typename R>
-__global__ __launch_bounds__(RS_THREADS) void k_rs_hist2(const R* __restrict__ recs, int64_t n, uint32_t* __restrict__ blkhist, int ntiles) {
+__global__ __launch_bounds__(RH_THREADS) void k_rs_hist2(const R* __restrict__ recs, int64_t n, uint32_t* __restrict__ blkhist, int ntiles,
+                                                          int64_t* __restrict__ classes, int64_t nfill, int64_t fill_value, int extra) {
+    const f3d_block_role role = f3d_rider_role(blockIdx.x, gridDim.x, (unsigned)extra);
+    if (role.rider) { f3d_fill_labels_block(classes, nfill, fill_value, role.index, extra, RH_THREADS); return; }
     __shared__ uint32_t hist[256];
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    constexpr int PER = 16 / sizeof(R);                              // records of a 16-byte load
+    constexpr int LOADS = RS_TILE / (RH_THREADS * PER);
+    static_assert(RH_THREADS >= 256 && LOADS * RH_THREADS * PER == RS_TILE, "the histogram kernel's block must cover a tile");
+    typedef R vec_t __attribute__((ext_vector_type(PER)));
     if (threadIdx.x < 256) hist[threadIdx.x] = 0u;
     __syncthreads();
-#pragma unroll 4
-    for (int r = 0; r < RS_ROUNDS; ++r) {
-        const int64_t i = rs_item(blockIdx.x, wave, r, lane);
-        if (i < n) atomicAdd(&hist[(uint32_t)(recs[i] >> rs_rec<R>::shift) & 0xFFu], 1u);
+    const int64_t base = (int64_t)role.index * RS_TILE;
+    if (base + RS_TILE <= n && !((uintptr_t)recs & 15)) {
+        const vec_t* __restrict__ src = reinterpret_cast<const vec_t*>(recs + base);
+        vec_t v[LOADS];
+#pragma unroll
+        for (int r = 0; r < LOADS; ++r) v[r] = src[r * RH_THREADS + threadIdx.x];
+#pragma unroll
+        for (int r = 0; r < LOADS; ++r)
+#pragma unroll
+            for (int c = 0; c < PER; ++c) atomicAdd(&hist[(uint32_t)(v[r][c] >> rs_rec<R>::shift) & 0xFFu], 1u);
+    } else {                                                         // the last tile, or records that are not 16-byte aligned
+        const int64_t end = base + RS_TILE < n ? base + RS_TILE : n;
+        for (int64_t i = base + threadIdx.x; i < end; i += RH_THREADS) atomicAdd(&hist[(uint32_t)(recs[i] >> rs_rec<R>::shift) & 0xFFu], 1u);
     }
     __syncthreads();
-    if (threadIdx.x < 256) blkhist[(size_t)threadIdx.x * ntiles + blockIdx.x] = hist[threadIdx.x];
+    if (threadIdx.x < 256) blkhist[(size_t)threadIdx.x * ntiles + role.index] = hist[threadIdx.x];
 }
 
 // block d: exclusive scan of row d of blkhist (the tiles' counts of digit value d) in place; tot[d] = the row's sum
@@ -321,29 +346,49 @@ __device__ __forceinline__ void rs_round_order() {
 // instead of 64 scattered stores per instruction (measured at 10M keys: pass 1 144 -> 95 us with the run-wise output).
 //
 // Ranking a round (64 consecutive keys of a wave).  The wave owns wmask[wave][256], one 64-bit lane mask per digit value, all zero
-// between rounds, and wcount[wave][256], the tile position of the wave's next key of each digit value.
+// between rounds, and wcount[wave][256], the tile position of the wave's next key of each digit value, 16 bits each (a position is below
+// RS_TILE = 8192; two digit values share a 32-bit word, and every access below is to one 16-bit half).
 //   (1) every live lane ORs its lane bit into wmask[wave][digit]                     (ds_or_b64, no return; an OR has no order)
-//   (2) every live lane reads wmask[wave][digit] and wcount[wave][digit]             (ds_read_b64, ds_read_b32)
+//   (2) every live lane reads wmask[wave][digit] and wcount[wave][digit]             (ds_read_b64, ds_read_u16)
 //       rank = popc(mask & lanes below me): equal digits keep lane = index order; position = count + rank
-//   (3) the lane of rank 0 stores count + popc(mask) and a zero mask                  (ds_write_b32, ds_write_b64)
+//   (3) the lane of rank 0 stores count + popc(mask) and a zero mask                  (ds_write_b16, ds_write_b64)
 // rs_round_order() stands between (1) and (2), between (2) and (3), and between (3) and the next round's (1): each time the wave
 // waits until its own LDS instructions have completed (lgkmcnt(0)) before it issues the next group, and the compiler keeps the groups
 // apart.  No other wave touches these words, so nothing else needs an order; the OR, the loads and the stores are relaxed atomics so that the
 // compiler neither keeps a word in a register across a fence nor drops the store of the zero.  A lane without a key takes no part.
-// The mask tables lie on the first RS_WAVES x 2 KB of `srec` (a table of their own would cost a CU its third block), so the rounds
+// (The 16-bit store of (3) writes its own half only: the leaders of digit values d and d + 1 may store into one 32-bit word in the same
+// instruction, each its half.  Before the rounds the halves are COUNTS, at most 1024 per wave, added with one 32-bit LDS atomic on the
+// pair -- 1 << 16 for the odd digit value; a half cannot carry into its neighbour.)
+// The mask tables lie on the first RS_WAVES x 2 KB of `srec` (a table of their own would cost a CU a resident block), so the rounds
 // only compute positions -- kept with the digit in dig[r], no further register -- and the records are placed after a block barrier.
+//
+// The output loop needs gdelta of the run position j lies in.  Pass 2 reads the digit out of the record.  Pass 1's record carries the
+// HIGH byte while the run goes by the low one; a byte per position for it would be 8 KB of LDS (the fourth block of a CU) and one
+// conflicted byte store per key.  Instead the 256 owners leave a bitmap of run starts with a running count per 64-bit word and gdelta
+// compacted by the rank of the non-empty run (f3d_run_span_of, f3d_run_at: f3d_kernels.h); a wave of the output loop covers one word,
+// so the word and its count are one broadcast read each.
+//
+// LDS of a block, uint32 records: records 32,768 + wcount 4,096 + gdelta 1,024 + wsum 16, pass 1 + 1,024 + 256 (bitmap, counts): with
+// the riders' own tables 39,504 / 38,416 B for pass 1 / pass 2 -- four blocks in a CU's 160 KiB, which also takes 64 VGPRs or fewer.
+constexpr int RS_WORDS = RS_TILE / 64;                               // 64-bit words of the run-start bitmap
+template <int PASS, typename R> constexpr size_t rs_dyn_lds() { return (size_t)RS_TILE * sizeof(R) + (PASS == 1 ? RS_WORDS * (sizeof(unsigned long long) + sizeof(uint16_t)) : 0); }
+// waves per SIMD the scatter kernels are compiled for: 8 (four 512-thread blocks per CU, 64 VGPRs) with 32-bit records; the 64-bit
+// records take 64 KB and more of LDS per block, two blocks per CU at most
+template <typename R> constexpr int rs_min_waves() { return sizeof(R) == 4 ? 8 : 2; }
+
 template <int PASS, typename R>
 __device__ __forceinline__ void rs_scatter_tile(const sort_key_t* __restrict__ keys, const R* __restrict__ recs_in, int64_t n,
                                                 const uint32_t* __restrict__ offs, const uint32_t* __restrict__ tot, int ntiles,
                                                 R* __restrict__ recs_out, uint32_t* __restrict__ perm_out, const int tile) {
-    __shared__ uint32_t wcount[RS_WAVES][256];                       // per wave: count of each digit value, then its running position in the tile
+    __shared__ uint16_t wcount[RS_WAVES][256];                       // per wave: count of each digit value, then its running position in the tile
     __shared__ uint32_t gdelta[256];                                 // global position of the tile's first key of a digit value - its position in the tile
-    __shared__ uint32_t wsum[4];
-    extern __shared__ unsigned long long rs_dyn[];                   // the tile in digit order: RS_TILE records (+ pass 1: their low bytes)
+    __shared__ uint32_t wsum[4];                                     //   (pass 1: of the r-th non-empty digit value)
+    extern __shared__ unsigned long long rs_dyn[];                   // the tile in digit order: RS_TILE records (+ pass 1: the run-start bitmap and its counts)
     R* srec = reinterpret_cast<R*>(rs_dyn);
-    uint8_t* sdig = reinterpret_cast<uint8_t*>(srec + RS_TILE);      // pass 1 only: the record carries the HIGH byte, the run is found by the low one
+    unsigned long long* starts = reinterpret_cast<unsigned long long*>(srec + RS_TILE);      // pass 1 only
+    uint16_t* before = reinterpret_cast<uint16_t*>(starts + RS_WORDS);
     static_assert((size_t)RS_WAVES * 256 * sizeof(unsigned long long) <= (size_t)RS_TILE * sizeof(uint32_t), "the lane masks must fit under the records");
-    static_assert(RS_TILE <= (1 << 16), "a tile position is packed into 16 bits of dig[r]");
+    static_assert(RS_TILE <= (1 << 16) - 1 && RS_ROUNDS * 64 < (1 << 16), "a tile position and a wave's count fit 16 bits");
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     unsigned long long* const wmask = rs_dyn + wave * 256;           // this wave's lane masks (until the records are placed)
     // requested first: the two table entries of this thread's digit value (latency hidden behind the key loads and the counting)
@@ -351,7 +396,10 @@ __device__ __forceinline__ void rs_scatter_tile(const sort_key_t* __restrict__ k
     const bool own = threadIdx.x < 256;
     const uint32_t t_d = own ? tot[d_own] : 0u;
     const uint32_t o_d = own ? offs[(size_t)d_own * ntiles + tile] : 0u;
-    for (int k = threadIdx.x; k < RS_WAVES * 256; k += RS_THREADS) { (&wcount[0][0])[k] = 0u; rs_dyn[k] = 0ull; }
+    typedef uint32_t __attribute__((may_alias)) pair_t;
+    pair_t* const wpair = reinterpret_cast<pair_t*>(&wcount[0][0]);  // the counts as pairs (digit values 2k, 2k + 1)
+    for (int k = threadIdx.x; k < RS_WAVES * 256; k += RS_THREADS) { if (k < RS_WAVES * 128) wpair[k] = 0u; rs_dyn[k] = 0ull; }
+    if (PASS == 1 && threadIdx.x < RS_WORDS) { starts[threadIdx.x] = 0ull; if (threadIdx.x == 0) before[0] = 0; }
     __syncthreads();
     uint32_t dig[RS_ROUNDS];                                         // the digit; after the ranking rounds (digit << 16) | tile position
     R val[RS_ROUNDS];                                                // the record that leaves (pass 1: built here; pass 2: the one that came in)
@@ -362,7 +410,7 @@ __device__ __forceinline__ void rs_scatter_tile(const sort_key_t* __restrict__ k
         if (i < n) {
             if (PASS == 1) { const uint32_t k = keys[i]; dig[r] = k & 0xFFu; val[r] = ((R)(k >> 8) << rs_rec<R>::shift) | (R)i; }
             else { val[r] = recs_in[i]; dig[r] = (uint32_t)(val[r] >> rs_rec<R>::shift) & 0xFFu; }
-            atomicAdd(&wcount[wave][dig[r]], 1u);
+            atomicAdd(&wpair[wave * 128 + (dig[r] >> 1)], 1u << (16 * (dig[r] & 1u)));
         }
     }
     __syncthreads();
@@ -370,11 +418,22 @@ __device__ __forceinline__ void rs_scatter_tile(const sort_key_t* __restrict__ k
         uint32_t c_d = 0u;
         if (own) for (int w = 0; w < RS_WAVES; ++w) c_d += wcount[w][d_own];
         const uint32_t gstart = rs_excl_scan256(t_d, wsum);          // keys of smaller digit values in the whole array
-        const uint32_t lstart = rs_excl_scan256(c_d, wsum);          // ... in this tile
+        // ... in this tile (at most RS_TILE: 16 bits) and, pass 1, above them the NON-EMPTY smaller digit values: one scan for both
+        const uint32_t both = rs_excl_scan256(PASS == 1 ? (c_d | (c_d ? 1u << 16 : 0u)) : c_d, wsum);
+        const uint32_t lstart = both & 0xFFFFu;
         if (own) {
-            gdelta[d_own] = gstart + o_d - lstart;
+            const uint32_t gd = gstart + o_d - lstart;
+            if (PASS == 1) {
+                if (c_d) {
+                    const uint32_t rank = both >> 16;
+                    const f3d_run_span sp = f3d_run_span_of(lstart, c_d, RS_WORDS);
+                    __hip_atomic_fetch_or(&starts[sp.word], 1ull << sp.bit, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+                    gdelta[rank] = gd;
+                    for (uint32_t w = sp.first; w <= sp.last; ++w) before[w] = (uint16_t)(rank + 1u);
+                }
+            } else gdelta[d_own] = gd;
             uint32_t run = lstart;
-            for (int w = 0; w < RS_WAVES; ++w) { const uint32_t c = wcount[w][d_own]; wcount[w][d_own] = run; run += c; }
+            for (int w = 0; w < RS_WAVES; ++w) { const uint32_t c = wcount[w][d_own]; wcount[w][d_own] = (uint16_t)run; run += c; }
         }
     }
     __syncthreads();
@@ -394,7 +453,7 @@ __device__ __forceinline__ void rs_scatter_tile(const sort_key_t* __restrict__ k
         rs_round_order();                                            // (2) -> (3): every lane has its mask and count
         const uint32_t rank = (uint32_t)__popcll(m & below);
         if (live && rank == 0u) {
-            __hip_atomic_store(&wcount[wave][d], base + (uint32_t)__popcll(m), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+            __hip_atomic_store(&wcount[wave][d], (uint16_t)(base + (uint32_t)__popcll(m)), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
             __hip_atomic_store(&wmask[d], 0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
         }
         rs_round_order();                                            // (3) -> the next round's (1): count advanced, mask zero again
@@ -402,26 +461,21 @@ __device__ __forceinline__ void rs_scatter_tile(const sort_key_t* __restrict__ k
     }
     __syncthreads();                                                 // every wave is done with its masks: the records may overwrite them
 #pragma unroll
-    for (int r = 0; r < RS_ROUNDS; ++r) {
-        if (dig[r] != 0xFFFFFFFFu) {
-            const uint32_t pos = dig[r] & 0xFFFFu;
-            srec[pos] = val[r];
-            if (PASS == 1) sdig[pos] = (uint8_t)(dig[r] >> 16);
-        }
-    }
+    for (int r = 0; r < RS_ROUNDS; ++r)
+        if (dig[r] != 0xFFFFFFFFu) srec[dig[r] & 0xFFFFu] = val[r];
     __syncthreads();
     const int64_t left = n - (int64_t)tile * RS_TILE;
     const int count = (int)(left < RS_TILE ? left : RS_TILE);
 #pragma unroll 4
-    for (int j = threadIdx.x; j < count; j += RS_THREADS) {
+    for (int j = threadIdx.x; j < count; j += RS_THREADS) {          // (a wave's 64 positions are one word of the bitmap)
         const R rec = srec[j];
-        if (PASS == 1) recs_out[(uint32_t)j + gdelta[sdig[j]]] = rec;
+        if (PASS == 1) recs_out[(uint32_t)j + gdelta[f3d_run_at(starts[j >> 6], before[j >> 6], (unsigned)j & 63u)]] = rec;
         else perm_out[(uint32_t)j + gdelta[(uint32_t)(rec >> rs_rec<R>::shift) & 0xFFu]] = (uint32_t)(rec & rs_rec<R>::imask);
     }
 }
 
 template <int PASS, typename R>
-__global__ __launch_bounds__(RS_THREADS) void k_rs_scatter(const sort_key_t* __restrict__ keys, const R* __restrict__ recs_in, int64_t n,
+__global__ __launch_bounds__(RS_THREADS, rs_min_waves<R>()) void k_rs_scatter(const sort_key_t* __restrict__ keys, const R* __restrict__ recs_in, int64_t n,
                                                             const uint32_t* __restrict__ offs, const uint32_t* __restrict__ tot, int ntiles,
                                                             R* __restrict__ recs_out, uint32_t* __restrict__ perm_out) {
     rs_scatter_tile<PASS, R>(keys, recs_in, n, offs, tot, ntiles, recs_out, perm_out, blockIdx.x);
@@ -429,11 +483,11 @@ __global__ __launch_bounds__(RS_THREADS) void k_rs_scatter(const sort_key_t* __r
 
 // The scatter passes with riders (f3d_sort_riders): `extra` blocks of the launch, spread evenly through the grid, do streaming work of the
 // fused call instead of a tile -- the ranking rounds are chains of LDS round trips that leave HBM idle, the riders are pure HBM traffic.
-// A rider block holds the kernel's LDS (a resident slot of the sort) while it lives; it waits for nobody and nobody waits for it.
-//   PASS 1: label presence over the mask bytes (masks == NULL: none), then the label fill (classes == NULL: none) -- pass 1 has bandwidth
-//   to spare, pass 2 + coding has not.   PASS 2: mask coding with the book the scan launch in front built.
+// A rider block holds the kernel's LDS (one of the four resident slots of a CU) while it lives; it waits for nobody and nobody waits for it.
+//   PASS 1: label presence over the mask bytes (masks == NULL: none), then the label fill (classes == NULL: none, or it rides beside
+//   k_rs_hist2) -- pass 1 has bandwidth to spare, pass 2 + coding has not.   PASS 2: mask coding with the book the scan launch in front built.
 template <int PASS, typename R>
-__global__ __launch_bounds__(RS_THREADS) void k_rs_scatter_ride(const sort_key_t* __restrict__ keys, const R* __restrict__ recs_in, int64_t n,
+__global__ __launch_bounds__(RS_THREADS, rs_min_waves<R>()) void k_rs_scatter_ride(const sort_key_t* __restrict__ keys, const R* __restrict__ recs_in, int64_t n,
                                                                  const uint32_t* __restrict__ offs, const uint32_t* __restrict__ tot, int ntiles,
                                                                  R* __restrict__ recs_out, uint32_t* __restrict__ perm_out,
                                                                  const uint8_t* __restrict__ masks, int64_t mask_bytes, f3d_codebook* __restrict__ cb,
@@ -492,7 +546,7 @@ hipError_t run_passes(const sort_layout& L, char* base, int64_t n, int32_t* perm
     uint32_t* hist = reinterpret_cast<uint32_t*>(base + L.hist);
     uint32_t* tot = reinterpret_cast<uint32_t*>(base + L.tot);
     const dim3 gt(L.ntiles), bt(RS_THREADS);
-    const size_t lds1 = (size_t)RS_TILE * sizeof(R) + RS_TILE, lds2 = (size_t)RS_TILE * sizeof(R);
+    const size_t lds1 = rs_dyn_lds<1, R>(), lds2 = rs_dyn_lds<2, R>();
     if (lds1 > 48 * 1024) {
         hipError_t e = hipFuncSetAttribute((const void*)k_rs_scatter<1, R>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds1);
         if (e == hipSuccess) e = hipFuncSetAttribute((const void*)k_rs_scatter<2, R>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds2);
@@ -505,12 +559,14 @@ hipError_t run_passes(const sort_layout& L, char* base, int64_t n, int32_t* perm
             if (e != hipSuccess) return e;
         }
         hipLaunchKernelGGL(k_rs_scan, dim3(256), dim3(256), 0, s, hist, L.ntiles, tot);
+        const bool fill2 = rd->classes && rd->fill_blocks > 0;       // the fill rides beside the second histogram, not beside pass 1
         if (rd->pass1_blocks > 0)
             hipLaunchKernelGGL((k_rs_scatter_ride<1, R>), dim3(L.ntiles + rd->pass1_blocks), bt, lds1, s, keys, (const R*)nullptr, n, hist, tot, L.ntiles, recs,
                                (uint32_t*)nullptr, rd->presence ? rd->masks : (const uint8_t*)nullptr, rd->mask_bytes, rd->cb, (uint8_t*)nullptr, 0, 0, 0,
-                               rd->classes, rd->n, rd->fill_value, rd->pass1_blocks);
+                               fill2 ? (int64_t*)nullptr : rd->classes, rd->n, rd->fill_value, rd->pass1_blocks);
         else hipLaunchKernelGGL((k_rs_scatter<1, R>), gt, bt, lds1, s, keys, (const R*)nullptr, n, hist, tot, L.ntiles, recs, (uint32_t*)nullptr);
-        hipLaunchKernelGGL(k_rs_hist2<R>, gt, bt, 0, s, recs, n, hist, L.ntiles);
+        const int fb = fill2 ? rd->fill_blocks : 0;
+        hipLaunchKernelGGL(k_rs_hist2<R>, dim3(L.ntiles + fb), dim3(RH_THREADS), 0, s, recs, n, hist, L.ntiles, fill2 ? rd->classes : (int64_t*)nullptr, rd->n, rd->fill_value, fb);
         hipLaunchKernelGGL(k_rs_scan_setup, dim3(256 + rd->setup_blocks), dim3(256), 0, s, hist, L.ntiles, tot, rd->setup, rd->setup_blocks);
         hipLaunchKernelGGL((k_rs_scatter_ride<2, R>), dim3(L.ntiles + rd->code_blocks), bt, lds2, s, (const sort_key_t*)nullptr, recs, n, hist, tot, L.ntiles,
                            (R*)nullptr, reinterpret_cast<uint32_t*>(perm), rd->masks, rd->mask_bytes, rd->cb, rd->coded, rd->V, rd->H, rd->W,
@@ -519,7 +575,7 @@ hipError_t run_passes(const sort_layout& L, char* base, int64_t n, int32_t* perm
     }
     hipLaunchKernelGGL(k_rs_scan, dim3(256), dim3(256), 0, s, hist, L.ntiles, tot);
     hipLaunchKernelGGL((k_rs_scatter<1, R>), gt, bt, lds1, s, keys, (const R*)nullptr, n, hist, tot, L.ntiles, recs, (uint32_t*)nullptr);
-    hipLaunchKernelGGL(k_rs_hist2<R>, gt, bt, 0, s, recs, n, hist, L.ntiles);
+    hipLaunchKernelGGL(k_rs_hist2<R>, gt, dim3(RH_THREADS), 0, s, recs, n, hist, L.ntiles, (int64_t*)nullptr, (int64_t)0, (int64_t)0, 0);
     hipLaunchKernelGGL(k_rs_scan, dim3(256), dim3(256), 0, s, hist, L.ntiles, tot);
     hipLaunchKernelGGL((k_rs_scatter<2, R>), gt, bt, lds2, s, (const sort_key_t*)nullptr, recs, n, hist, tot, L.ntiles, (R*)nullptr, reinterpret_cast<uint32_t*>(perm));
     return hipGetLastError();
