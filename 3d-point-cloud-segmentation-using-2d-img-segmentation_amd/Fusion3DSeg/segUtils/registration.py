@@ -15,8 +15,14 @@ the model's intensity map, weighted into the same 6 x 6 system), and ``track_fra
 
 A pixel (u, v) stands for the ray through (u + 0.5, v + 0.5), the convention of ``TSDFVolume.integrate``.  NumPy arrays in, NumPy
 arrays back; device tensors in, or a volume that is on the device, keep everything on the GPU, ordered with torch's current stream.
-There is no CPU fallback.  Out of scope: image pyramids, robust weights, an intensity-difference gate, exposure compensation, colour
-from anything but the volume, loop closure, and re-unprojecting ``Fusion``'s stored frames at refined poses.
+There is no CPU fallback.
+
+A start pose a few centimetres off on a surface with structure near the pixel scale needs ``icp(..., levels=3)``: pyramids of the
+depth frame and of the model maps by gated 2 x 2 averages, the rounds chained coarse to fine on the device (f3d_depth_half,
+f3d_maps_half, f3d_icp_levels; restated in tests/levels_ref.py).  ``track_frames`` takes the same three arguments.
+
+Out of scope: pyramids of the colour image, robust weights, an intensity-difference gate, exposure compensation, colour from
+anything but the volume, loop closure, and re-unprojecting ``Fusion``'s stored frames at refined poses.
 """
 import math
 
@@ -199,11 +205,15 @@ def icp_sums(depth, K, wxyz, t, model_vertex, model_normal, model_K, model_wxyz,
     return sums
 
 
-def _to_device(torch, dev, depth, model_vertex, model_normal, view):
+def _maps_to_device(torch, dev, depth, model_vertex, model_normal):
     as_tensor = lambda a: a if on_device(a) else torch.from_numpy(np.ascontiguousarray(a))     # noqa: E731
     d = as_tensor(depth).to(dev).contiguous()
     mv, mn = (as_tensor(a).to(dev, torch.float64).contiguous() for a in (model_vertex, model_normal))
-    return d, mv, mn, upload(view, dev)
+    return d, mv, mn
+
+
+def _to_device(torch, dev, depth, model_vertex, model_normal, view):
+    return _maps_to_device(torch, dev, depth, model_vertex, model_normal) + (upload(view, dev),)
 
 
 def _icp_device(ctx, torch, dev, work, d, code, K, q, t, mv, mn, hm, wm, dview, max_dist, depth_scale, max_depth, iterations, min_pairs):
@@ -229,8 +239,92 @@ def _icp_color_device(ctx, torch, dev, work, d, code, K, q, t, mv, mn, hm, wm, d
     return pose, stats, status
 
 
+def _levels_plan(levels, level_iterations, gate, iterations, min_pairs, max_dist, shapes):
+    """The coarse-to-fine arguments of icp / track_frames, checked before any device call.  None for the single call of today
+    (``levels=1`` with the other two ``None``); else (levels, rounds per level finest first, gate, min_pairs per level finest first).
+    ``shapes``: (rows, columns) of the frame and of the model image, each of which must survive ``levels - 1`` halvings."""
+    levels = int(levels)
+    if not 1 <= levels <= f3d.ICP_MAX_LEVELS:
+        raise ValueError(f'levels must be in [1, {f3d.ICP_MAX_LEVELS}], got {levels}')
+    if levels == 1 and level_iterations is None and gate is None:
+        return None
+    if level_iterations is None:
+        rounds = (iterations,) + (max(1, iterations // 2),) * (levels - 1)
+    else:
+        rounds = tuple(int(x) for x in level_iterations)
+        if len(rounds) != levels or min(rounds) < 1:
+            raise ValueError(f'level_iterations must hold {levels} counts of at least 1, finest level first, got {tuple(level_iterations)}')
+    gate = _positive('gate', max_dist if gate is None else gate)
+    for rows, cols in shapes:
+        if min(int(rows), int(cols)) < 1 << (levels - 1):
+            raise ValueError(f'{levels} levels need at least {1 << (levels - 1)} rows and columns, got {(int(rows), int(cols))}')
+    return levels, rounds, gate, tuple(max(6, min_pairs >> (2 * l)) for l in range(levels))
+
+
+def _half_K(K):
+    """The intrinsics of a half-sampled image: input coordinate x is output coordinate x / 2 (f3d.h), so the first two rows halve."""
+    K = np.array(K, np.float64)
+    K[:2] /= 2.0
+    return K
+
+
+def _level_cameras(plan, K, hw, mK, mhw, mq, mt, max_depth):
+    """Per level, finest first: (K, (h, w), model K, (hm, wm), the model's views_build record)."""
+    out = []
+    for _ in range(plan[0]):
+        out.append((K, hw, mK, mhw, f3d.views_build(mK, mhw[1], mhw[0], mq[None], mt[None], max_depth)))
+        K, mK, hw, mhw = _half_K(K), _half_K(mK), (hw[0] // 2, hw[1] // 2), (mhw[0] // 2, mhw[1] // 2)
+    return out
+
+
+def _icp_levels_host(ctx, plan, depth, K, q, t, mv, mn, mi, hm, wm, mK, mq, mt, max_dist, depth_scale, max_depth, rgb, color_weight):
+    """The half-samplings and the levelled rounds through the host bindings -> (pose, stats, status) of ``Context.icp_levels``."""
+    _, rounds, gate, pairs = plan
+    recs = []
+    for l, (K_l, _, _, (hm_l, wm_l), view) in enumerate(_level_cameras(plan, K, depth.shape, mK, (hm, wm), mq, mt, max_depth)):
+        if l:
+            p = recs[-1]
+            depth, depth_scale = ctx.depth_half(p['depth'], p['depth_scale'], max_depth, gate), 1.0
+            maps = ctx.maps_half(p['model_vertex'], p['model_normal'], p['hm'], p['wm'], p['model_view'], gate, p['model_intensity'])
+            mv, mn, mi = maps if mi is not None else maps + (None,)
+        recs.append(dict(depth=depth, K=K_l, depth_scale=depth_scale, model_vertex=mv, model_normal=mn, model_intensity=mi, hm=hm_l, wm=wm_l,
+                         model_view=view, max_dist=max_dist, iterations=rounds[l], min_pairs=pairs[l]))
+    return ctx.icp_levels(recs[::-1], q, t, max_depth, rgb, color_weight)
+
+
+def _icp_levels_device(ctx, torch, dev, work, plan, d, code, K, q, t, mv, mn, mi, hm, wm, mK, mq, mt, max_dist, depth_scale, max_depth, rgb,
+                       color_weight):
+    """Enqueues the half-samplings and the levelled rounds on `work`, all inputs on the device -> (pose [7], stats [rounds, 3 or 5],
+    status [1], the tensors the launches read).  One upload (every level's view record), no host synchronisation."""
+    from f3d import levels as LV
+    _, rounds, gate, pairs = plan
+    cams = _level_cameras(plan, K, tuple(int(x) for x in d.shape), mK, (hm, wm), mq, mt, max_depth)
+    dviews = upload(np.stack([np.asarray(c[4]).reshape(-1) for c in cams]), dev)
+    f64 = lambda *shape: torch.empty(shape, dtype=torch.float64, device=dev)                    # noqa: E731
+    ptr = lambda x: None if x is None else x.data_ptr()                                       # noqa: E731
+    keep, recs = [dviews], []
+    for l, (K_l, (h_l, w_l), _, (hm_l, wm_l), _) in enumerate(cams):
+        if l:
+            p = recs[-1]
+            d, code, depth_scale = f64(h_l * w_l), 0, 1.0
+            LV.depth_half_dev(ctx, p['depth'], p['depth_type'], p['h'], p['w'], p['depth_scale'], max_depth, gate, d.data_ptr(), work.cuda_stream)
+            mv, mn, mi = f64(hm_l * wm_l, 3), f64(hm_l * wm_l, 3), None if mi is None else f64(hm_l * wm_l)
+            LV.maps_half_dev(ctx, p['model_vertex'], p['model_normal'], p['model_intensity'], p['hm'], p['wm'], p['model_view'], gate, mv.data_ptr(),
+                             mn.data_ptr(), ptr(mi), work.cuda_stream)
+            keep += [x for x in (d, mv, mn, mi) if x is not None]
+        recs.append(dict(depth=d.data_ptr(), depth_type=code, h=h_l, w=w_l, K=K_l, depth_scale=depth_scale, model_vertex=mv.data_ptr(),
+                         model_normal=mn.data_ptr(), model_intensity=ptr(mi), hm=hm_l, wm=wm_l, model_view=dviews[l].data_ptr(), max_dist=max_dist,
+                         iterations=rounds[l], min_pairs=pairs[l]))
+    pose, stats = f64(7), f64(sum(rounds), 3 if rgb is None else 5)
+    status = torch.empty(1, dtype=torch.int32, device=dev)
+    hc, wc = (0, 0) if rgb is None else (int(rgb.shape[0]), int(rgb.shape[1]))
+    LV.icp_levels_dev(ctx, recs[::-1], q, t, max_depth, pose.data_ptr(), stats.data_ptr(), status.data_ptr(), ptr(rgb), hc, wc, color_weight,
+                      work.cuda_stream)
+    return pose, stats, status, keep
+
+
 def icp(depth, K, wxyz, t, model_vertex, model_normal, model_K, model_wxyz, model_t, max_dist=0.1, depth_scale=1.0, max_depth=10, iterations=10,
-        min_pairs=100, *, color=None, model_intensity=None, color_weight=None):
+        min_pairs=100, *, color=None, model_intensity=None, color_weight=None, levels=1, level_iterations=None, gate=None):
     """``iterations`` rounds of projective point-to-plane ICP of the depth frame against the model maps (the arguments of ``icp_sums``),
     starting from the pose (``wxyz``, ``t``), all on the device with no host round trip between the rounds -> (wxyz [4], t [3], info).
     ``info`` holds the final ``status`` (0 = converging, 1 = lost: fewer than ``min_pairs`` pairs or a degenerate system; the pose of a
@@ -240,13 +334,43 @@ def icp(depth, K, wxyz, t, model_vertex, model_normal, model_K, model_wxyz, mode
     solves ``A_g + color_weight A_c`` against ``-(b_g + color_weight b_c)``: the intensity residual holds what the geometry lets
     slide.  Intensities are in [0, 1] and distances in metres, so the weight is a squared length: a residual of 1/255 counts as much as
     one of sqrt(color_weight) / 255 metres.  ``info`` then also holds ``color_counts`` and ``color_rms`` per round; whether a round is
-    lost is decided by the geometric pairs alone."""
+    lost is decided by the geometric pairs alone.
+
+    ``levels`` > 1 runs coarse to fine: the frame and the model maps (with the intensity map) are half-sampled ``levels - 1`` times by
+    2 x 2 averages that keep to the nearest surface within ``gate`` metres (default ``max_dist``), and the rounds run from the coarsest
+    level to the full resolution in one chain on the device.  A surface with structure near the pixel scale (bricks, slats, shelves)
+    otherwise pulls a start a few centimetres off into the neighbouring period of that structure, with status 0.
+    ``level_iterations``: the rounds per level, finest first (default ``iterations`` at full resolution and half of it, at least 1, on
+    every coarser level); level l runs with ``max(6, min_pairs >> 2 l)``.  ``info``'s per-round arrays then hold every level's rounds in
+    running order, coarsest first, and ``level_rounds`` the rounds per level in that order.  The colour image is not half-sampled: a
+    coarse pixel reads the full image by the pixel rule."""
     depth, code, K, q, t, model_vertex, model_normal, hm, wm, view, max_dist, depth_scale, max_depth = _icp_args(
         depth, K, wxyz, t, model_vertex, model_normal, model_K, model_wxyz, model_t, max_dist, depth_scale, max_depth)
     col = _color_args(color, model_intensity, color_weight, hm, wm)
     iterations, min_pairs = _rounds(iterations, min_pairs)
+    plan = _levels_plan(levels, level_iterations, gate, iterations, min_pairs, max_dist, (depth.shape, (hm, wm)))
     ctx = f3d.default_context()
-    if not (on_device(depth) or on_device(model_vertex) or on_device(model_normal) or (col is not None and (on_device(col[0]) or on_device(col[1])))):
+    device = on_device(depth) or on_device(model_vertex) or on_device(model_normal) or (col is not None and (on_device(col[0]) or on_device(col[1])))
+    if plan is not None:
+        mK, mq, mt = _pose(model_K, model_wxyz, model_t, 'model_')
+        rgb, mi, weight = (None, None, None) if col is None else col
+        if not device:
+            pose, stats, status = _icp_levels_host(ctx, plan, depth, K, q, t, model_vertex, model_normal, mi, hm, wm, mK, mq, mt, max_dist, depth_scale,
+                                                   max_depth, rgb, weight)
+            return pose[:4].copy(), pose[4:].copy(), dict(_info(stats, status), level_rounds=plan[1][::-1])
+        torch, dev = torch_device(ctx, 'icp')
+        with torch.cuda.device(dev), work_stream(dev) as work:
+            d, mv, mn = _maps_to_device(torch, dev, depth, model_vertex, model_normal)
+            used = [d, mv, mn]
+            if col is not None:
+                rgb, mi = _color_to_device(torch, dev, rgb, mi)
+                used += [rgb, mi]
+            pose, stats, status, keep = _icp_levels_device(ctx, torch, dev, work, plan, d, code, K, q, t, mv, mn, mi, hm, wm, mK, mq, mt, max_dist,
+                                                           depth_scale, max_depth, rgb, weight)
+        for x in used + keep + [pose, stats, status]:
+            x.record_stream(torch.cuda.current_stream(dev))
+        return pose[:4].clone(), pose[4:].clone(), dict(_info(stats, status[0], torch), level_rounds=plan[1][::-1])
+    if not device:
         if col is not None:
             pose, stats, status = ctx.icp_color(depth, K, q, t, model_vertex, model_normal, hm, wm, view, max_dist, col[1], col[0], col[2], depth_scale,
                                                 max_depth, iterations, min_pairs)
@@ -272,7 +396,7 @@ def icp(depth, K, wxyz, t, model_vertex, model_normal, model_K, model_wxyz, mode
 
 
 def track_frames(volume, depths, K, wxyzs, translations, depth_scale=1.0, max_depth=10, max_dist=0.1, iterations=10, min_pairs=100, min_weight=1,
-                 integrate=True, colors=None, color_weight=None):
+                 integrate=True, colors=None, color_weight=None, levels=1, level_iterations=None, gate=None):
     """Frame-to-model tracking of the depth frames ``depths`` [F, h, w] into ``volume`` (a ``TSDFVolume``), in frame order.  A frame
     that meets a volume with no weight is integrated at its given pose.  Every later frame is ray-cast at its given pose, the prior
     (samples every voxel edge up to ``max_depth``), aligned to those maps by ``icp`` starting from the prior, takes the refined pose if
@@ -281,7 +405,8 @@ def track_frames(volume, depths, K, wxyzs, translations, depth_scale=1.0, max_de
     or the volume are on the device.  ``colors``: the frames' colour images, uint8 [F, hc, wc, 3], for a volume built with
     ``color=True``; each frame that is integrated hands its image to ``integrate``.  ``color_weight`` (with ``colors``): every aligned
     frame is ray-cast with the volume's colour and aligned by ``icp`` with the photometric term at that weight, against the intensity
-    of the model as built so far; ``None`` keeps the alignment depth-only.
+    of the model as built so far; ``None`` keeps the alignment depth-only.  ``levels``, ``level_iterations``, ``gate``: every aligned
+    frame runs ``icp``'s coarse-to-fine rounds, its pyramids built from the frame and from the maps ray-cast at full resolution.
 
     One host synchronisation per frame: the readback of the 7 doubles of the pose and the status, because ``views_build``, which makes
     the record ``integrate`` projects with, needs the pose on the host.  While the volume is empty its weights are looked at, too."""
@@ -298,6 +423,7 @@ def track_frames(volume, depths, K, wxyzs, translations, depth_scale=1.0, max_de
     K = np.ascontiguousarray(np.asarray(K, np.float64))
     depth_scale, max_depth, max_dist = _positive('depth_scale', depth_scale), _positive('max_depth', max_depth), _positive('max_dist', max_dist)
     iterations, min_pairs = _rounds(iterations, min_pairs)
+    plan = _levels_plan(levels, level_iterations, gate, iterations, min_pairs, max_dist, ((h, w),))
     min_weight = _min_weight(min_weight)
     near, step, nsteps = _march(volume, 0.0, max_depth, None)
     out_q, out_t, status = qs.copy(), ts.copy(), np.zeros(F, np.int32)
@@ -323,10 +449,16 @@ def track_frames(volume, depths, K, wxyzs, translations, depth_scale=1.0, max_de
                 if color_weight is None:
                     vertex, normal, _ = ctx.tsdf_raycast(volume.tsdf, volume.weight, volume.lo, volume.voxel, min_weight, K, q, t, h, w, near, step,
                                                          nsteps)
-                    pose, _, status[f] = ctx.icp(depths[f], K, q, t, vertex, normal, h, w, view, max_dist, depth_scale, max_depth, iterations, min_pairs)
+                    intensity = None
                 else:
                     vertex, normal, _, _, intensity = ctx.tsdf_raycast_color(volume.tsdf, volume.weight, volume.color, volume.lo, volume.voxel,
                                                                              min_weight, K, q, t, h, w, near, step, nsteps)
+                if plan is not None:
+                    pose, _, status[f] = _icp_levels_host(ctx, plan, depths[f], K, q, t, vertex, normal, intensity, h, w, K, q, t, max_dist, depth_scale,
+                                                          max_depth, None if color_weight is None else colors[f], color_weight)
+                elif color_weight is None:
+                    pose, _, status[f] = ctx.icp(depths[f], K, q, t, vertex, normal, h, w, view, max_dist, depth_scale, max_depth, iterations, min_pairs)
+                else:
                     pose, _, status[f] = ctx.icp_color(depths[f], K, q, t, vertex, normal, h, w, view, max_dist, intensity, colors[f], color_weight,
                                                        depth_scale, max_depth, iterations, min_pairs)
                 if status[f] == 0:
@@ -347,13 +479,20 @@ def track_frames(volume, depths, K, wxyzs, translations, depth_scale=1.0, max_de
             view = f3d.views_build(K, w, h, q[None], t[None], max_depth)
             with torch.cuda.device(dev), work_stream(dev) as work:
                 vertex, normal = (torch.empty((h * w, 3), dtype=torch.float64, device=dev) for _ in range(2))
-                dview = upload(view, dev)
-                used = [vertex, normal, dview]
+                used = [vertex, normal]
+                if plan is None:
+                    dview = upload(view, dev)
+                    used.append(dview)
                 if color_weight is None:
                     ctx.tsdf_raycast_dev(volume.tsdf.data_ptr(), volume.weight.data_ptr(), volume.dims, volume.lo, volume.voxel, min_weight, K, q, t, h,
                                          w, near, step, nsteps, vertex.data_ptr(), normal.data_ptr(), None, work.cuda_stream)
-                    pose, stats, lost = _icp_device(ctx, torch, dev, work, d_all[f], code, K, q, t, vertex, normal, h, w, dview, max_dist, depth_scale,
-                                                    max_depth, iterations, min_pairs)
+                    if plan is None:
+                        pose, stats, lost = _icp_device(ctx, torch, dev, work, d_all[f], code, K, q, t, vertex, normal, h, w, dview, max_dist,
+                                                        depth_scale, max_depth, iterations, min_pairs)
+                    else:
+                        pose, stats, lost, keep = _icp_levels_device(ctx, torch, dev, work, plan, d_all[f], code, K, q, t, vertex, normal, None, h, w,
+                                                                     K, q, t, max_dist, depth_scale, max_depth, None, None)
+                        used += keep
                     back = torch.cat([pose, lost.to(torch.float64)])
                 else:
                     intensity = torch.empty(h * w, dtype=torch.float64, device=dev)
@@ -361,8 +500,13 @@ def track_frames(volume, depths, K, wxyzs, translations, depth_scale=1.0, max_de
                     ctx.tsdf_raycast_color_dev(volume.tsdf.data_ptr(), volume.weight.data_ptr(), volume.color.data_ptr(), volume.dims, volume.lo,
                                                volume.voxel, min_weight, K, q, t, h, w, near, step, nsteps, vertex.data_ptr(), normal.data_ptr(), None,
                                                None, intensity.data_ptr(), work.cuda_stream)
-                    pose, stats, lost = _icp_color_device(ctx, torch, dev, work, d_all[f], code, K, q, t, vertex, normal, h, w, dview, max_dist,
-                                                          intensity, rgb_all[f], color_weight, depth_scale, max_depth, iterations, min_pairs)
+                    if plan is None:
+                        pose, stats, lost = _icp_color_device(ctx, torch, dev, work, d_all[f], code, K, q, t, vertex, normal, h, w, dview, max_dist,
+                                                              intensity, rgb_all[f], color_weight, depth_scale, max_depth, iterations, min_pairs)
+                    else:
+                        pose, stats, lost, keep = _icp_levels_device(ctx, torch, dev, work, plan, d_all[f], code, K, q, t, vertex, normal, intensity, h,
+                                                                     w, K, q, t, max_dist, depth_scale, max_depth, rgb_all[f], color_weight)
+                        used += keep
                     back = torch.cat([pose, lost.to(torch.float64), stats[-1, 3:]])          # the two colour columns ride along
             for x in used + [pose, stats, lost]:
                 x.record_stream(torch.cuda.current_stream(dev))

@@ -3425,6 +3425,150 @@ int f3d_icp_color(f3d_ctx* ctx, const void* depth, int depth_type, int h, int w,
     return st.finish();
 }
 
+// coarse-to-fine: one pyramid step of a depth frame and of model maps, and the rounds over a list of levels
+#define F3D_DEPTH_HALF_BAD "bad arguments (h, w >= 2 with h * w < 2^31; depth_scale, max_depth and gate finite and > 0; a known depth type)"
+static bool depth_half_ok(const void* depth, int depth_type, int h, int w, double depth_scale, double max_depth, double gate, const double* out) {
+    return depth && out && h >= 2 && w >= 2 && image_ok(h, w) && pos_finite(depth_scale) && pos_finite(max_depth) && pos_finite(gate) &&
+           (depth_type == F3D_DEPTH_U16 || depth_type == F3D_DEPTH_F32 || depth_type == F3D_DEPTH_F64);
+}
+
+int f3d_depth_half_dev(f3d_ctx* ctx, const void* depth, int depth_type, int h, int w, double depth_scale, double max_depth, double gate, double* out,
+                       void* stream) {
+    int rc = enter(ctx); if (rc) return rc;
+    if (!depth_half_ok(depth, depth_type, h, w, depth_scale, max_depth, gate, out)) return fail(ctx, F3D_ERR_INVALID, "depth_half: " F3D_DEPTH_HALF_BAD);
+    F3D_HIP(ctx, f3d_launch_depth_half(depth, depth_type, h, w, depth_scale, max_depth, gate, out, pick(ctx, stream)));
+    return F3D_OK;
+}
+
+int f3d_depth_half(f3d_ctx* ctx, const void* depth, int depth_type, int h, int w, double depth_scale, double max_depth, double gate, double* out) {
+    int rc = enter(ctx); if (rc) return rc;
+    if (!depth_half_ok(depth, depth_type, h, w, depth_scale, max_depth, gate, out)) return fail(ctx, F3D_ERR_INVALID, "depth_half: " F3D_DEPTH_HALF_BAD);
+    staging st(ctx);
+    const void* dd = st.in((const char*)depth, depth_bytes(depth_type, 1, h, w));
+    double* dout = st.out(out, (size_t)(h / 2) * (w / 2) * sizeof(double));
+    if (!st.rc) st.rc = f3d_depth_half_dev(ctx, dd, depth_type, h, w, depth_scale, max_depth, gate, dout, ctx->stream);
+    return st.finish();
+}
+
+#define F3D_MAPS_HALF_BAD "bad arguments (hm, wm >= 2 with hm * wm < 2^31; gate finite and > 0; intensity_out given iff model_intensity is)"
+static bool maps_half_ok(const double* mv, const double* mn, const double* mi, int hm, int wm, const f3d_view* view, double gate, const double* vo,
+                         const double* no, const double* io) {
+    return mv && mn && view && vo && no && !mi == !io && hm >= 2 && wm >= 2 && image_ok(hm, wm) && pos_finite(gate);
+}
+
+int f3d_maps_half_dev(f3d_ctx* ctx, const double* model_vertex, const double* model_normal, const double* model_intensity, int hm, int wm,
+                      const f3d_view* model_view, double gate, double* vertex_out, double* normal_out, double* intensity_out, void* stream) {
+    int rc = enter(ctx); if (rc) return rc;
+    if (!maps_half_ok(model_vertex, model_normal, model_intensity, hm, wm, model_view, gate, vertex_out, normal_out, intensity_out))
+        return fail(ctx, F3D_ERR_INVALID, "maps_half: " F3D_MAPS_HALF_BAD);
+    F3D_HIP(ctx, f3d_launch_maps_half(model_vertex, model_normal, model_intensity, hm, wm, model_view, gate, vertex_out, normal_out, intensity_out,
+                                      pick(ctx, stream)));
+    return F3D_OK;
+}
+
+int f3d_maps_half(f3d_ctx* ctx, const double* model_vertex, const double* model_normal, const double* model_intensity, int hm, int wm,
+                  const f3d_view* model_view, double gate, double* vertex_out, double* normal_out, double* intensity_out) {
+    int rc = enter(ctx); if (rc) return rc;
+    if (!maps_half_ok(model_vertex, model_normal, model_intensity, hm, wm, model_view, gate, vertex_out, normal_out, intensity_out))
+        return fail(ctx, F3D_ERR_INVALID, "maps_half: " F3D_MAPS_HALF_BAD);
+    const size_t px = (size_t)hm * wm * 8, px2 = (size_t)(hm / 2) * (wm / 2) * 8;
+    staging st(ctx);
+    const double* dv = st.in(model_vertex, 3 * px);
+    const double* dn = st.in(model_normal, 3 * px);
+    const double* di = model_intensity ? st.in(model_intensity, px) : nullptr;
+    const f3d_view* dview = st.in(model_view, sizeof(f3d_view));
+    double* dvo = st.out(vertex_out, 3 * px2);
+    double* dno = st.out(normal_out, 3 * px2);
+    double* dio = st.out(intensity_out, px2);
+    if (!st.rc) st.rc = f3d_maps_half_dev(ctx, dv, dn, di, hm, wm, dview, gate, dvo, dno, dio, ctx->stream);
+    return st.finish();
+}
+
+#define F3D_ICP_LEVELS_BAD "bad arguments (nlevels in [1, 6]; per level: " F3D_ICP_BAD ", iterations >= 1, min_pairs >= 6; model_intensity on every level and rgb, or on none and no rgb; with rgb: hc, wc_img > 0 with a product < 2^31, color_weight finite and >= 0)"
+// the total of the levels' rounds, or -1 for a call the contract refuses
+static int64_t icp_levels_rounds(const f3d_icp_level* lv, int nlevels, double max_depth, const double* q, const double* t, const uint8_t* rgb, int hc,
+                                 int wc_img, double color_weight) {
+    if (!lv || nlevels < 1 || nlevels > F3D_ICP_MAX_LEVELS) return -1;
+    int64_t rounds = 0;
+    for (int l = 0; l < nlevels; ++l) {
+        if (!icp_ok(lv[l].depth, lv[l].depth_type, lv[l].h, lv[l].w, lv[l].K, lv[l].depth_scale, max_depth, q, t, lv[l].model_vertex, lv[l].model_normal,
+                    lv[l].hm, lv[l].wm, lv[l].model_view, lv[l].max_dist) ||
+            lv[l].iterations < 1 || lv[l].min_pairs < 6 || !lv[l].model_intensity != !rgb)
+            return -1;
+        rounds += lv[l].iterations;
+    }
+    if (rgb && !icp_color_ok(lv[0].model_intensity, rgb, hc, wc_img, color_weight)) return -1;
+    return rounds;
+}
+
+static int64_t icp_levels_pixels(const f3d_icp_level* lv, int nlevels) {
+    int64_t most = 0;
+    for (int l = 0; l < nlevels; ++l) {
+        const int64_t npix = (int64_t)lv[l].h * lv[l].w;
+        if (npix > most) most = npix;
+    }
+    return most;
+}
+
+int f3d_icp_levels_dev(f3d_ctx* ctx, const f3d_icp_level* levels, int nlevels, double max_depth, const double q_wxyz[4], const double t[3],
+                       const uint8_t* rgb, int hc, int wc_img, double color_weight, double* pose, double* stats, int32_t* status, void* stream) {
+    int rc = enter(ctx); if (rc) return rc;
+    if (!pose || !stats || icp_levels_rounds(levels, nlevels, max_depth, q_wxyz, t, rgb, hc, wc_img, color_weight) < 0)
+        return fail(ctx, F3D_ERR_INVALID, "icp_levels: " F3D_ICP_LEVELS_BAD);
+    const int64_t most = icp_levels_pixels(levels, nlevels);
+    void* scratch;
+    if ((rc = ensure(ctx, SLOT_ICP, rgb ? f3d_icp_color_scratch_bytes(most) : f3d_icp_scratch_bytes(most), &scratch))) return rc;
+    F3D_HIP(ctx, f3d_launch_icp_levels(levels, nlevels, max_depth, q_wxyz, t, rgb, hc, wc_img, color_weight, scratch, pose, stats, status,
+                                       pick(ctx, stream)));
+    return F3D_OK;
+}
+
+// The host entry stages every input of every level in one buffer (a call may hold 6 levels of five arrays each, more than the
+// staging buffers a call has): each piece starts on a 256-byte boundary of it.
+int f3d_icp_levels(f3d_ctx* ctx, const f3d_icp_level* levels, int nlevels, double max_depth, const double q_wxyz[4], const double t[3],
+                   const uint8_t* rgb, int hc, int wc_img, double color_weight, double* pose, double* stats, int32_t* status) {
+    int rc = enter(ctx); if (rc) return rc;
+    const int64_t rounds = icp_levels_rounds(levels, nlevels, max_depth, q_wxyz, t, rgb, hc, wc_img, color_weight);
+    if (!pose || !stats || !status || rounds < 0) return fail(ctx, F3D_ERR_INVALID, "icp_levels: " F3D_ICP_LEVELS_BAD);
+    struct piece { size_t depth, vertex, normal, intensity, view; } at[F3D_ICP_MAX_LEVELS];
+    f3d_carve c;
+    for (int l = 0; l < nlevels; ++l) {
+        const f3d_icp_level& lv = levels[l];
+        const size_t px = (size_t)lv.hm * lv.wm * 8;
+        at[l].depth = c.take(depth_bytes(lv.depth_type, 1, lv.h, lv.w));
+        at[l].vertex = c.take(3 * px);
+        at[l].normal = c.take(3 * px);
+        at[l].intensity = c.take(rgb ? px : 0);
+        at[l].view = c.take(sizeof(f3d_view));
+    }
+    const size_t rgb_at = c.take(rgb ? (size_t)hc * wc_img * 3 : 0);
+    staging st(ctx);
+    char* in = (char*)st.slot(c.off);
+    f3d_icp_level dev[F3D_ICP_MAX_LEVELS];
+    for (int l = 0; l < nlevels && !st.rc; ++l) {
+        const f3d_icp_level& lv = levels[l];
+        const size_t px = (size_t)lv.hm * lv.wm * 8;
+        dev[l] = lv;
+        st.put(in + at[l].depth, lv.depth, depth_bytes(lv.depth_type, 1, lv.h, lv.w));
+        st.put(in + at[l].vertex, lv.model_vertex, 3 * px);
+        st.put(in + at[l].normal, lv.model_normal, 3 * px);
+        if (rgb) st.put(in + at[l].intensity, lv.model_intensity, px);
+        st.put(in + at[l].view, lv.model_view, sizeof(f3d_view));
+        dev[l].depth = in + at[l].depth;
+        dev[l].model_vertex = (const double*)(in + at[l].vertex);
+        dev[l].model_normal = (const double*)(in + at[l].normal);
+        dev[l].model_intensity = rgb ? (const double*)(in + at[l].intensity) : nullptr;
+        dev[l].model_view = (const f3d_view*)(in + at[l].view);
+    }
+    if (rgb) st.put(in + rgb_at, rgb, (size_t)hc * wc_img * 3);
+    double* dp = st.out(pose, 7 * sizeof(double));
+    double* ds = st.out(stats, (size_t)rounds * (rgb ? 5 : 3) * sizeof(double));
+    int32_t* dst = st.out(status, sizeof(int32_t));
+    if (!st.rc) st.rc = f3d_icp_levels_dev(ctx, dev, nlevels, max_depth, q_wxyz, t, rgb ? (const uint8_t*)(in + rgb_at) : nullptr, hc, wc_img, color_weight,
+                                           dp, ds, dst, ctx->stream);
+    return st.finish();
+}
+
 // ---------------------------------------------------------------------------------------------
 // feature fusion: per-point pooling of per-pixel feature maps over views (f3d_features.hip)
 // ---------------------------------------------------------------------------------------------

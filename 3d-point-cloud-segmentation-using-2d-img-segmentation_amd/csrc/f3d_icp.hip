@@ -19,6 +19,12 @@
 //   k_icp_terms<T, true>  a second sweep over the chunk recomputes each pixel and accumulates the 29 photometric terms, so that no more
 //                         than 29 accumulators are live at a time; a chunk row is 58 wide, the geometric sums first.
 //   k_icp_solve<true>     58 totals; A = A_g + color_weight * A_c; a stats row of 5.
+// Coarse-to-fine (f3d_depth_half, f3d_maps_half, f3d_icp_levels): two kernels that halve a depth frame and a set of model maps, and a
+// launcher that runs the rounds above over a list of levels.  It adds no arithmetic to a round: k_icp_terms and k_icp_solve are used
+// as they are.
+//   k_depth_half<T>       one thread per output pixel, grid-stride; the 2 x 2 block's four samples in registers; no LDS, no atomics.
+//   k_maps_half<INTENSITY> the same over the model maps: a block row's two map rows are 48 contiguous bytes, which the compiler
+//                         fetches with three 16-byte loads (global memory needs no 16-byte alignment for them).
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
@@ -470,6 +476,98 @@ __global__ __launch_bounds__(F3D_BLOCK) void k_icp_solve(const double* __restric
     row[2] = (double)F3D_ICP_OK;
 }
 
+// ---- coarse-to-fine: one pyramid step of a depth frame and of model maps ------------------------------------------------------
+// Output pixel (u, v) reads the input pixels (2v, 2u), (2v, 2u+1), (2v+1, 2u), (2v+1, 2u+1), in that order; an odd last row or column
+// of the input is never read.
+template <typename T>
+__global__ __launch_bounds__(F3D_BLOCK) void k_depth_half(const T* __restrict__ depth, int w, int w2, int64_t n2, double depth_scale, double max_depth,
+                                                           double gate, double* __restrict__ out) {
+    for (int64_t i = (int64_t)blockIdx.x * F3D_BLOCK + threadIdx.x; i < n2; i += (int64_t)gridDim.x * F3D_BLOCK) {
+        const int64_t v = i / w2, u = i - v * w2;
+        const int64_t top = 2 * v * w + 2 * u;
+        const int64_t at[4] = {top, top + 1, top + w, top + w + 1};
+        double d[4], dmin = 0.0;
+        bool ok[4], any = false;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            d[k] = raw_depth<T>::at(depth, at[k]) / depth_scale;
+            ok[k] = d[k] > 0.0 && d[k] <= max_depth;
+            if (ok[k] && (!any || d[k] < dmin)) dmin = d[k];
+            any = any || ok[k];
+        }
+        double sum = 0.0;
+        int count = 0;
+#pragma unroll
+        for (int k = 0; k < 4; ++k)
+            if (ok[k] && d[k] - dmin <= gate) { sum = sum + d[k]; ++count; }
+        out[i] = count ? sum / (double)count : 0.0;
+    }
+}
+
+// the intensity arguments of k_maps_half<true>; the instantiation without carries none
+template <bool INTENSITY> struct maps_half_io {};
+template <> struct maps_half_io<true> { const double* intensity; double* out; };
+
+// two neighbouring map rows: 6 doubles, 48 contiguous bytes at p (the compiler fetches them with three 16-byte loads)
+__device__ __forceinline__ void load_row_pair(const double* __restrict__ p, double a[3], double b[3]) {
+    a[0] = p[0]; a[1] = p[1]; a[2] = p[2]; b[0] = p[3]; b[1] = p[4]; b[2] = p[5];
+}
+
+template <bool INTENSITY>
+__global__ __launch_bounds__(F3D_BLOCK) void k_maps_half(const double* __restrict__ vertex, const double* __restrict__ normal, int wm, int w2, int64_t n2,
+                                                          const f3d_view* __restrict__ view, double gate,
+                                                          double* __restrict__ vertex_out, double* __restrict__ normal_out, maps_half_io<INTENSITY> io) {
+    const double nan = __longlong_as_double(0x7ff8000000000000LL);
+    const f3d_view& mv = *view;
+    for (int64_t i = (int64_t)blockIdx.x * F3D_BLOCK + threadIdx.x; i < n2; i += (int64_t)gridDim.x * F3D_BLOCK) {
+        const int64_t v = i / w2, u = i - v * w2;
+        const int64_t top = 2 * v * wm + 2 * u, bot = top + wm;
+        const int64_t at[4] = {top, top + 1, bot, bot + 1};
+        double V[4][3], N[4][3];
+        load_row_pair(vertex + 3 * top, V[0], V[1]);
+        load_row_pair(vertex + 3 * bot, V[2], V[3]);
+        load_row_pair(normal + 3 * top, N[0], N[1]);
+        load_row_pair(normal + 3 * bot, N[2], N[3]);
+        double z[4], zmin = 0.0;
+        bool ok[4], any = false;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const bool finite = fabs(V[k][0]) < INFINITY && fabs(V[k][1]) < INFINITY && fabs(V[k][2]) < INFINITY && fabs(N[k][0]) < INFINITY &&
+                                fabs(N[k][1]) < INFINITY && fabs(N[k][2]) < INFINITY;
+            f3d_p3 p;
+            p.x = V[k][0]; p.y = V[k][1]; p.z = V[k][2];
+            z[k] = f3d_project_h(mv.K, mv.qinv, mv.t, p).z;
+            ok[k] = finite && z[k] > 0.0;
+            if (ok[k] && (!any || z[k] < zmin)) zmin = z[k];
+            any = any || ok[k];
+        }
+        double S[3] = {0.0, 0.0, 0.0}, G[3] = {0.0, 0.0, 0.0}, si = 0.0;
+        int count = 0, ci = 0;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            if (!(ok[k] && z[k] - zmin <= gate)) continue;
+#pragma unroll
+            for (int a = 0; a < 3; ++a) { S[a] = S[a] + V[k][a]; G[a] = G[a] + N[k][a]; }
+            ++count;
+            if constexpr (INTENSITY) {
+                const double I = io.intensity[at[k]];
+                if (fabs(I) < INFINITY) { si = si + I; ++ci; }
+            }
+        }
+        double Vo[3] = {nan, nan, nan}, No[3] = {nan, nan, nan};
+        if (count) {
+            const double len = sqrt((G[0] * G[0] + G[1] * G[1]) + G[2] * G[2]);
+            if (len > 0.0 && len < INFINITY) {
+#pragma unroll
+                for (int a = 0; a < 3; ++a) { Vo[a] = S[a] / (double)count; No[a] = G[a] / len; }
+            }
+        }
+        vertex_out[3 * i] = Vo[0]; vertex_out[3 * i + 1] = Vo[1]; vertex_out[3 * i + 2] = Vo[2];
+        normal_out[3 * i] = No[0]; normal_out[3 * i + 1] = No[1]; normal_out[3 * i + 2] = No[2];
+        if constexpr (INTENSITY) io.out[i] = ci ? si / (double)ci : nan;
+    }
+}
+
 struct icp_scratch { size_t chunks, pose, lost, bytes; };
 
 icp_scratch icp_layout(int64_t npixels, int row = NS) {
@@ -626,4 +724,89 @@ hipError_t f3d_launch_icp_color(const f3d_icp_args& a, const f3d_icp_color_args&
     F3D_TRY(hipMemcpyAsync(pose_out, pose, 7 * sizeof(double), hipMemcpyDeviceToDevice, s));
     if (status) F3D_TRY(hipMemcpyAsync(status, lost, sizeof(int32_t), hipMemcpyDeviceToDevice, s));
     return hipSuccess;
+}
+
+hipError_t f3d_launch_depth_half(const void* depth, int depth_type, int h, int w, double depth_scale, double max_depth, double gate, double* out,
+                                 hipStream_t s) {
+    const int w2 = w / 2;
+    const int64_t n2 = (int64_t)(h / 2) * w2;
+    const dim3 gr(f3d_grid_for(n2, F3D_BLOCK, F3D_GRID_CAP)), b(F3D_BLOCK);
+    if (depth_type == F3D_DEPTH_U16)
+        hipLaunchKernelGGL(k_depth_half<uint16_t>, gr, b, 0, s, (const uint16_t*)depth, w, w2, n2, depth_scale, max_depth, gate, out);
+    else if (depth_type == F3D_DEPTH_F32)
+        hipLaunchKernelGGL(k_depth_half<float>, gr, b, 0, s, (const float*)depth, w, w2, n2, depth_scale, max_depth, gate, out);
+    else
+        hipLaunchKernelGGL(k_depth_half<double>, gr, b, 0, s, (const double*)depth, w, w2, n2, depth_scale, max_depth, gate, out);
+    return hipGetLastError();
+}
+
+hipError_t f3d_launch_maps_half(const double* vertex, const double* normal, const double* intensity, int hm, int wm, const f3d_view* view, double gate,
+                                double* vertex_out, double* normal_out, double* intensity_out, hipStream_t s) {
+    const int w2 = wm / 2;
+    const int64_t n2 = (int64_t)(hm / 2) * w2;
+    const dim3 gr(f3d_grid_for(n2, F3D_BLOCK, F3D_GRID_CAP)), b(F3D_BLOCK);
+    if (intensity) {
+        maps_half_io<true> io;
+        io.intensity = intensity; io.out = intensity_out;
+        hipLaunchKernelGGL(k_maps_half<true>, gr, b, 0, s, vertex, normal, wm, w2, n2, view, gate, vertex_out, normal_out, io);
+    } else {
+        hipLaunchKernelGGL(k_maps_half<false>, gr, b, 0, s, vertex, normal, wm, w2, n2, view, gate, vertex_out, normal_out,
+                           maps_half_io<false>{});
+    }
+    return hipGetLastError();
+}
+
+namespace {
+
+// the scratch of a levelled call is that of its level with the most source pixels
+int64_t most_pixels(const f3d_icp_level* levels, int nlevels) {
+    int64_t most = 0;
+    for (int k = 0; k < nlevels; ++k) {
+        const int64_t npix = (int64_t)levels[k].h * levels[k].w;
+        if (npix > most) most = npix;
+    }
+    return most;
+}
+
+// The rounds of f3d_launch_icp / f3d_launch_icp_color, level after level: one k_icp_init, then per round of every level the same two
+// launches, the running round index as the stats row.  The pose and the lost flag stay where they are between the levels.
+template <bool COLOR>
+hipError_t launch_levels(const f3d_icp_level* levels, int nlevels, double max_depth, const double q[4], const double t[3], const uint8_t* rgb, int hc,
+                         int wc_img, double color_weight, void* scratch, double* pose_out, double* stats, int32_t* status, hipStream_t s) {
+    const icp_scratch lay = icp_layout(most_pixels(levels, nlevels), COLOR ? NSC : NS);
+    char* base = (char*)scratch;
+    double *chunks = (double*)(base + lay.chunks), *pose = (double*)(base + lay.pose);
+    int* lost = (int*)(base + lay.lost);
+    icp_solve_color<COLOR> col;
+    if constexpr (COLOR) col.weight = color_weight;
+    hipLaunchKernelGGL(k_icp_init, dim3(1), dim3(64), 0, s, pose, lost, q[0], q[1], q[2], q[3], t[0], t[1], t[2]);
+    int round = 0;
+    for (int k = 0; k < nlevels; ++k) {
+        const f3d_icp_level& lv = levels[k];
+        f3d_icp_args a;
+        a.depth = lv.depth; a.depth_type = lv.depth_type; a.h = lv.h; a.w = lv.w; a.K = lv.K; a.depth_scale = lv.depth_scale; a.max_depth = max_depth;
+        a.model_vertex = lv.model_vertex; a.model_normal = lv.model_normal; a.hm = lv.hm; a.wm = lv.wm; a.model_view = lv.model_view;
+        a.max_dist = lv.max_dist;
+        icp_color_io<COLOR> cio;
+        if constexpr (COLOR) { cio.model_intensity = lv.model_intensity; cio.rgb = rgb; cio.hc = hc; cio.wc = wc_img; }
+        const int64_t npix = (int64_t)lv.h * lv.w;
+        for (int it = 0; it < lv.iterations; ++it, ++round) {
+            launch_terms(a, pose, lost, chunks, cio, s);
+            hipLaunchKernelGGL(k_icp_solve<COLOR>, dim3(1), dim3(F3D_BLOCK), 0, s, chunks, (npix + F3D_ICP_CHUNK - 1) / F3D_ICP_CHUNK, (double*)nullptr,
+                               pose, lost, (double)lv.min_pairs, stats, round, col);
+        }
+    }
+    F3D_TRY(hipGetLastError());
+    F3D_TRY(hipMemcpyAsync(pose_out, pose, 7 * sizeof(double), hipMemcpyDeviceToDevice, s));
+    if (status) F3D_TRY(hipMemcpyAsync(status, lost, sizeof(int32_t), hipMemcpyDeviceToDevice, s));
+    return hipSuccess;
+}
+
+}  // namespace
+
+hipError_t f3d_launch_icp_levels(const f3d_icp_level* levels, int nlevels, double max_depth, const double q[4], const double t[3], const uint8_t* rgb,
+                                 int hc, int wc_img, double color_weight, void* scratch, double* pose_out, double* stats, int32_t* status,
+                                 hipStream_t s) {
+    if (rgb) return launch_levels<true>(levels, nlevels, max_depth, q, t, rgb, hc, wc_img, color_weight, scratch, pose_out, stats, status, s);
+    return launch_levels<false>(levels, nlevels, max_depth, q, t, nullptr, 0, 0, 0.0, scratch, pose_out, stats, status, s);
 }

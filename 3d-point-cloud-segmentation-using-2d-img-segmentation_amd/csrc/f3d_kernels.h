@@ -756,6 +756,17 @@ hipError_t f3d_launch_icp_color_sums(const f3d_icp_args& a, const f3d_icp_color_
                                      double* sums, hipStream_t s);
 hipError_t f3d_launch_icp_color(const f3d_icp_args& a, const f3d_icp_color_args& c, const double q[4], const double t[3], int iterations,
                                 int min_pairs, void* scratch, double* pose_out, double* stats, int32_t* status, hipStream_t s);
+// Coarse-to-fine.  One pyramid step of a depth frame (out [h/2 * w/2], metres) and of model maps (the outputs [hm/2 * wm/2, 3] and
+// [hm/2 * wm/2]; intensity and intensity_out both NULL = no intensity map); no scratch.  The rounds of f3d_launch_icp /
+// f3d_launch_icp_color over nlevels host records whose pointers are device pointers (rgb NULL = depth only); scratch: that of the
+// level with the most source pixels, f3d_icp_scratch_bytes / f3d_icp_color_scratch_bytes of that count; stats [sum of iterations, 3 or 5].
+hipError_t f3d_launch_depth_half(const void* depth, int depth_type, int h, int w, double depth_scale, double max_depth, double gate, double* out,
+                                 hipStream_t s);
+hipError_t f3d_launch_maps_half(const double* vertex, const double* normal, const double* intensity, int hm, int wm, const f3d_view* view, double gate,
+                                double* vertex_out, double* normal_out, double* intensity_out, hipStream_t s);
+hipError_t f3d_launch_icp_levels(const f3d_icp_level* levels, int nlevels, double max_depth, const double q[4], const double t[3], const uint8_t* rgb,
+                                 int hc, int wc_img, double color_weight, void* scratch, double* pose_out, double* stats, int32_t* status,
+                                 hipStream_t s);
 
 // plane table of a cloud over its adjacency (f3d_planes.hip).  Device pointers (counts int64 [4] too); normals (may be NULL: PCA of the
 // rows) and normals_out (may be NULL; written in PCA mode only) float64 [n, 3].  n >= 1.  Enqueues on `s` and synchronises it every few

@@ -43,6 +43,14 @@ ICP_NSUMS = 29               # F3D_ICP_NSUMS: 21 J J^T products, 6 J r, r r and 
 ICP_NSUMS_COLOR = 58         # F3D_ICP_NSUMS_COLOR: the 29 geometric sums, then the 29 of the photometric pairs
 ICP_PIVOT_EPS = 1e-10        # F3D_ICP_PIVOT_EPS: the smallest Cholesky pivot, as a fraction of the largest diagonal entry
 ICP_OK, ICP_LOST = 0, 1      # status of an icp round (f3d.h F3D_ICP_*)
+ICP_MAX_LEVELS = 6           # F3D_ICP_MAX_LEVELS: the most levels of one icp_levels call
+
+
+class IcpLevel(C.Structure):
+    """f3d_icp_level (f3d.h): the source frame, the model and the rounds of one level of icp_levels."""
+    _fields_ = [('depth', C.c_void_p), ('depth_type', C.c_int), ('h', C.c_int), ('w', C.c_int), ('K', C.c_double * 9), ('depth_scale', C.c_double),
+                ('model_vertex', C.c_void_p), ('model_normal', C.c_void_p), ('model_intensity', C.c_void_p), ('hm', C.c_int), ('wm', C.c_int),
+                ('model_view', C.c_void_p), ('max_dist', C.c_double), ('iterations', C.c_int), ('min_pairs', C.c_int)]
 
 
 class F3DError(RuntimeError):
@@ -270,6 +278,12 @@ def library():
         'f3d_icp_color_dev': (i32, [vp, vp, i32, i32, i32, vp, dbl, dbl, vp, vp, vp, vp, i32, i32, vp, dbl, vp, vp, i32, i32, dbl, i32, i32, vp, vp, vp,
                                     vp]),
         'f3d_ctx_reserve_icp_color': (i32, [vp, i64]),
+        'f3d_depth_half': (i32, [vp, vp, i32, i32, i32, dbl, dbl, dbl, vp]),
+        'f3d_depth_half_dev': (i32, [vp, vp, i32, i32, i32, dbl, dbl, dbl, vp, vp]),
+        'f3d_maps_half': (i32, [vp, vp, vp, vp, i32, i32, vp, dbl, vp, vp, vp]),
+        'f3d_maps_half_dev': (i32, [vp, vp, vp, vp, i32, i32, vp, dbl, vp, vp, vp, vp]),
+        'f3d_icp_levels': (i32, [vp, vp, i32, dbl, vp, vp, vp, i32, i32, dbl, vp, vp, vp]),
+        'f3d_icp_levels_dev': (i32, [vp, vp, i32, dbl, vp, vp, vp, i32, i32, dbl, vp, vp, vp, vp]),
     }
     for name, (res, args) in protos.items():
         fn = getattr(lib, name)          # AttributeError here = header/library mismatch
@@ -509,6 +523,60 @@ def _icp_color_arrays(model_intensity, rgb, color_weight, hm, wm):
     mi, rgb = np.asarray(model_intensity), np.asarray(rgb)
     _, _, color_weight = icp_color_check(mi, rgb, color_weight, hm, wm)
     return np.ascontiguousarray(mi).reshape(-1), np.ascontiguousarray(rgb), color_weight
+
+
+def _half_check(what, shape, gate):
+    """The checks depth_half / maps_half make before any device call: a 2D image of at least 2 x 2 pixels and a finite positive
+    gate -> gate as a float."""
+    shape = tuple(int(x) for x in shape)
+    if len(shape) != 2 or shape[0] < 2 or shape[1] < 2:
+        raise ValueError(f'{what} must be [h, w] with at least 2 rows and 2 columns, got {shape}')
+    gate = float(gate)
+    if not (gate > 0.0 and gate < float('inf')):
+        raise ValueError(f'gate must be finite and positive, got {gate}')
+    return gate
+
+
+def _half_intensity(model_intensity, hm, wm):
+    mi = np.asarray(model_intensity)
+    if mi.dtype != np.float64:
+        raise TypeError(f'model_intensity must be float64, got {mi.dtype}')
+    if mi.size != hm * wm:
+        raise ValueError(f'model_intensity must hold {hm} * {wm} values, got {mi.shape}')
+    return np.ascontiguousarray(mi).reshape(-1)
+
+
+ICP_LEVEL_KEYS = ('depth', 'K', 'model_vertex', 'model_normal', 'hm', 'wm', 'model_view', 'max_dist', 'iterations', 'min_pairs')
+
+
+def _icp_levels_check(levels, rgb, color_weight):
+    """The checks of an icp_levels call that need no array: 1 .. ICP_MAX_LEVELS levels with every key, iterations >= 1 and
+    min_pairs >= 6 on each, and colour on every level with rgb and color_weight, or on none without -> the levels as a list."""
+    levels = list(levels)
+    if not 1 <= len(levels) <= ICP_MAX_LEVELS:
+        raise ValueError(f'icp_levels takes 1 to {ICP_MAX_LEVELS} levels, got {len(levels)}')
+    if (rgb is None) != (color_weight is None):
+        raise ValueError('rgb and color_weight go together: pass both or none')
+    for lv in levels:
+        missing = [k for k in ICP_LEVEL_KEYS if k not in lv]
+        if missing:
+            raise ValueError(f'a level lacks {missing}')
+        if int(lv['iterations']) < 1 or int(lv['min_pairs']) < 6:
+            raise ValueError(f'a level needs iterations >= 1 and min_pairs >= 6, got {lv["iterations"]} and {lv["min_pairs"]}')
+        if (lv.get('model_intensity') is None) != (rgb is None):
+            raise ValueError('either every level has a model_intensity and rgb is given, or none has and rgb is None')
+    return levels
+
+
+def _fill_level(rec, depth_ptr, depth_type, h, w, K, depth_scale, vertex_ptr, normal_ptr, intensity_ptr, hm, wm, view_ptr, max_dist, iterations,
+                min_pairs):
+    """One IcpLevel record from raw pointers (host or device) and the level's numbers."""
+    rec.depth, rec.depth_type, rec.h, rec.w = depth_ptr, int(depth_type), int(h), int(w)
+    rec.K[:] = [float(x) for x in np.asarray(K, np.float64).reshape(9)]
+    rec.depth_scale = float(depth_scale)
+    rec.model_vertex, rec.model_normal, rec.model_intensity = vertex_ptr, normal_ptr, intensity_ptr
+    rec.hm, rec.wm, rec.model_view = int(hm), int(wm), view_ptr
+    rec.max_dist, rec.iterations, rec.min_pairs = float(max_dist), int(iterations), int(min_pairs)
 
 
 def _knn_k(k):
@@ -1445,6 +1513,56 @@ class Context:
                                             _ptr(t), _ptr(mv), _ptr(mn), int(hm), int(wm), _ptr(view), float(max_dist), _ptr(mi), _ptr(rgb),
                                             rgb.shape[0], rgb.shape[1], color_weight, iterations, int(min_pairs), _ptr(pose), _ptr(stats),
                                             C.byref(status)))
+        return pose, stats, status.value
+
+    def depth_half(self, depth, depth_scale=1.0, max_depth=10.0, gate=0.1):
+        """One pyramid step of a depth frame [h, w] (f3d.h f3d_depth_half) -> float64 [h // 2, w // 2] in metres: the mean of each
+        2 x 2 block's valid samples within `gate` of its nearest one, 0 where it has none."""
+        d = np.ascontiguousarray(depth)
+        gate = _half_check('depth', d.shape, gate)
+        code = depth_code(d)
+        out = np.empty((d.shape[0] // 2, d.shape[1] // 2))
+        self._check(self._lib.f3d_depth_half(self._h, _ptr(d), code, d.shape[0], d.shape[1], float(depth_scale), float(max_depth), gate, _ptr(out)))
+        return out
+
+    def maps_half(self, model_vertex, model_normal, hm, wm, model_view, gate, model_intensity=None):
+        """One pyramid step of model maps float64 [hm*wm, 3] seen by model_view (f3d.h f3d_maps_half) -> (vertex, normal float64
+        [(hm // 2) * (wm // 2), 3]), and with model_intensity float64 [hm*wm] a third array, the intensity [(hm // 2) * (wm // 2)]."""
+        hm, wm = int(hm), int(wm)
+        gate = _half_check('the model image', (hm, wm), gate)
+        mv, mn = _f64(model_vertex), _f64(model_normal)
+        if mv.size != hm * wm * 3 or mn.size != hm * wm * 3:
+            raise ValueError(f'the model maps must be [{hm} * {wm}, 3], got {mv.shape} and {mn.shape}')
+        mi = None if model_intensity is None else _half_intensity(model_intensity, hm, wm)
+        view = _f64(np.asarray(model_view).reshape(-1), (VIEW_DOUBLES,))
+        n2 = (hm // 2) * (wm // 2)
+        vertex, normal, intensity = np.empty((n2, 3)), np.empty((n2, 3)), None if mi is None else np.empty(n2)
+        self._check(self._lib.f3d_maps_half(self._h, _ptr(mv), _ptr(mn), _ptr(mi), hm, wm, _ptr(view), gate, _ptr(vertex), _ptr(normal),
+                                            _ptr(intensity)))
+        return (vertex, normal) if mi is None else (vertex, normal, intensity)
+
+    def icp_levels(self, levels, q_wxyz, t, max_depth=10.0, rgb=None, color_weight=None):
+        """The rounds of icp / icp_color over `levels`, coarsest first, chained on the device (f3d.h f3d_icp_levels).  A level is a dict:
+        depth [h, w], K, depth_scale (default 1), model_vertex, model_normal [hm*wm, 3], hm, wm, model_view, max_dist, iterations,
+        min_pairs, and with colour model_intensity [hm*wm]; rgb uint8 [hc, wc, 3] and color_weight go with the intensity maps, all or
+        none -> (pose float64 [7], stats float64 [sum of iterations, 3 or 5], the final status)."""
+        levels = _icp_levels_check(levels, rgb, color_weight)
+        q, t = _f64(q_wxyz, (4,)), _f64(t, (3,))
+        keep, recs = [], (IcpLevel * len(levels))()
+        for rec, lv in zip(recs, levels):
+            d, code, K, _, _, mv, mn, view = _icp_arrays(lv['depth'], lv['K'], q, t, lv['model_vertex'], lv['model_normal'], lv['hm'], lv['wm'],
+                                                         lv['model_view'])
+            mi = None
+            if rgb is not None:
+                mi, rgb, color_weight = _icp_color_arrays(lv['model_intensity'], rgb, color_weight, lv['hm'], lv['wm'])
+            keep += [d, mv, mn, view, mi]
+            _fill_level(rec, d.ctypes.data, code, d.shape[0], d.shape[1], K, lv.get('depth_scale', 1.0), mv.ctypes.data, mn.ctypes.data,
+                        None if mi is None else mi.ctypes.data, lv['hm'], lv['wm'], view.ctypes.data, lv['max_dist'], lv['iterations'], lv['min_pairs'])
+        rounds = sum(int(lv['iterations']) for lv in levels)
+        pose, stats, status = np.empty(7), np.empty((rounds, 3 if rgb is None else 5)), C.c_int32(0)
+        hc, wc = (0, 0) if rgb is None else rgb.shape[:2]
+        self._check(self._lib.f3d_icp_levels(self._h, C.byref(recs), len(levels), float(max_depth), _ptr(q), _ptr(t), _ptr(rgb), hc, wc,
+                                             0.0 if rgb is None else color_weight, _ptr(pose), _ptr(stats), C.byref(status)))
         return pose, stats, status.value
 
     def radius_graph(self, points, radius):

@@ -1439,8 +1439,8 @@ int f3d_ctx_reserve_icp(f3d_ctx* ctx, int64_t npixels);
  * 29-sum entries), a strict context then allocates nothing in the _dev entries.  F3D_ERR_INVALID, with nothing written: the bad
  * arguments of f3d_tsdf_raycast / f3d_icp_sums / f3d_icp; a NULL color, model_intensity or rgb; a device color that is not 16-byte
  * aligned; hc or wc_img < 1 or hc * wc_img >= 2^31; a negative or non-finite color_weight.
- * Out of scope: robust weights, an intensity-difference gate, image pyramids, exposure compensation, colour from anything but the
- * volume. */
+ * Out of scope: robust weights, an intensity-difference gate, pyramids of the colour image, exposure compensation, colour from
+ * anything but the volume. */
 #define F3D_ICP_NSUMS_COLOR 58
 int f3d_tsdf_raycast_color(f3d_ctx* ctx, const float* tsdf, const float* weight, const float* color /*[nz,ny,nx,4]*/, int nx, int ny, int nz,
                            const double lo[3], double vs, float min_weight, const double K[9], const double q_wxyz[4], const double t[3],
@@ -1470,6 +1470,87 @@ int f3d_icp_color_dev(f3d_ctx* ctx, const void* depth, int depth_type, int h, in
                       const double* model_intensity, const uint8_t* rgb, int hc, int wc_img, double color_weight, int iterations,
                       int min_pairs, double* pose, double* stats, int32_t* status /*device, may be NULL*/, void* stream);
 int f3d_ctx_reserve_icp_color(f3d_ctx* ctx, int64_t npixels);
+
+/* Coarse-to-fine registration: pyramids of the depth frame and of the model maps, and the rounds above run level after level.  At
+ * full resolution, projective ICP on a surface with structure near the pixel scale (bricks, slats, shelves) slides into the
+ * neighbouring period of that structure and still reports F3D_ICP_OK; a few rounds on half- and quarter-size averages put the pose
+ * within the basin of the right one first.  Everything above holds: float64 without contraction, every sum, division and sqrt as written.
+ * Both half-samplings give output pixel (u, v) of an h2 x w2 = (h / 2) x (w / 2) image (integer division: an odd last row or column is
+ * dropped) from the four input pixels (2v, 2u), (2v, 2u+1), (2v+1, 2u), (2v+1, 2u+1), "the four" below, always in that order.
+ *   intrinsics a pixel stands for the ray through (u + 0.5, v + 0.5), and the block of output pixel u covers [2u, 2u + 2) with its
+ *              centre at 2(u + 0.5): input coordinate x is output coordinate x / 2, exactly, with no half-pixel term.  So the output's
+ *              intrinsics are K' = (fx / 2, fy / 2, cx / 2, cy / 2): the first two rows of K divided by 2 (a division by 2 is exact),
+ *              and ((u + 0.5) - cx') / fx' is the mean of the two input columns' ((u_in + 0.5) - cx) / fx up to rounding.
+ * f3d_depth_half: depth, depth_type, h, w, depth_scale, max_depth as in f3d_icp_sums; gate > 0; h, w >= 2.  out float64 [h2*w2], metres.
+ *   1. d = (double)raw / depth_scale for each of the four; a sample is valid iff d > 0 && d <= max_depth.
+ *   2. dmin = the smallest valid d.
+ *   3. a sample is used iff it is valid and d - dmin <= gate: at a silhouette the foreground wins and no depth is invented between
+ *      two surfaces.
+ *   4. out = sum / (double)count, the sum left to right from 0.0 over the used samples; no valid sample: out = 0.0.
+ * The output is a depth frame of type F3D_DEPTH_F64 with depth_scale 1, for the next step and for the ICP.
+ * f3d_maps_half: model_vertex, model_normal float64 [hm*wm, 3], model_intensity float64 [hm*wm] or NULL, model_view (one f3d_view for
+ * the hm x wm image, as f3d_icp_sums takes it), gate > 0; hm, wm >= 2.  Outputs vertex_out, normal_out float64 [hm2*wm2, 3] and, iff
+ * model_intensity is given, intensity_out float64 [hm2*wm2].
+ *   1. a row of the four is usable iff its six values are finite and z = project_h(Km, qinv_m, t_m, V).h2 > 0.
+ *   2. zmin = the smallest z of the usable rows.
+ *   3. a row is used iff it is usable and z - zmin <= gate.
+ *   4. vertex = S / (double)count per component, S the sum of the used vertices, left to right from 0.0.
+ *   5. G = the sum of the used normals, likewise; len = sqrt((G0*G0 + G1*G1) + G2*G2); len == 0 or not finite: the vertex and normal rows
+ *      are NaN; otherwise normal = G / len.
+ *   6. intensity = the sum of the finite intensities of the used rows, left to right from 0.0, over their count; none: NaN (also where
+ *      step 5 gave NaN rows).
+ *   7. no usable row: every output is NaN.
+ * The averages are why this is a step of its own: ray-casting the volume again at the coarse size point-samples the surface, which
+ * aliases the very structure a coarse level is meant to smooth.  The output's model view is f3d_views_build of K' for hm2 x wm2.
+ * f3d_icp_levels: the rounds of f3d_icp (rgb NULL) or f3d_icp_color (rgb given) over nlevels in [1, F3D_ICP_MAX_LEVELS] records, in
+ * array order; the caller lists the coarsest first.  A record holds the source frame (depth, depth_type, h, w, K, depth_scale), the
+ * model (model_vertex, model_normal, model_intensity or NULL, hm, wm, model_view) and max_dist, iterations >= 1, min_pairs >= 6 of
+ * its level; max_depth, the start pose, the colour image (rgb, hc, wc_img: every level samples the full image by the pixel rule of
+ * f3d_icp_color_sums) and color_weight belong to the call.  Either every level has a model_intensity and rgb is given, or none has
+ * and rgb is NULL.  The records live on the host; in the _dev entry their pointers are device pointers.
+ *   rounds     each round is exactly a round of f3d_icp / f3d_icp_color on its level's frame at the pose the round before left, across a
+ *              level boundary too: there is no new arithmetic.
+ *   once lost  covers the whole call: the pose stays as it was at the start of the lost round, every later round of every level writes
+ *              {0, 0, 1} (five columns with colour: {0, 0, 1, 0, 0}).
+ * Hence: nlevels = 1 equals f3d_icp / f3d_icp_color bit for bit; nlevels = n equals n calls of f3d_icp, each started from the pose the
+ * call before returned, their stats rows concatenated, for as long as no call is lost.
+ * Outputs: pose float64 [7]; stats float64 [sum of iterations, 3 or 5]; status as f3d_icp's.  Scratch: that of the level with the
+ * most source pixels; f3d_ctx_reserve_icp(that count), or f3d_ctx_reserve_icp_color with colour, covers it and a strict context then
+ * allocates nothing in the _dev entry.  The half-samplings need none.
+ * F3D_ERR_INVALID, with nothing written: NULLs (but for model_intensity, intensity_out, rgb and the _dev status); h, w, hm or wm < 2 in
+ * a half-sampling; gate not finite and positive; nlevels outside [1, F3D_ICP_MAX_LEVELS]; a level that f3d_icp would refuse; levels
+ * with and without model_intensity in one call, or a mismatch between them and rgb; with rgb, the bad colour arguments of f3d_icp_color.
+ * Out of scope: filters with more than the four taps, pyramids of the colour image, robust weights, damping. */
+#define F3D_ICP_MAX_LEVELS 6
+typedef struct f3d_icp_level {
+    const void* depth;              /* the source frame of this level */
+    int depth_type, h, w;
+    double K[9];
+    double depth_scale;
+    const double* model_vertex;     /* [hm*wm, 3] */
+    const double* model_normal;     /* [hm*wm, 3] */
+    const double* model_intensity;  /* [hm*wm], or NULL in a call without colour */
+    int hm, wm;
+    const f3d_view* model_view;
+    double max_dist;
+    int iterations, min_pairs;
+} f3d_icp_level;
+int f3d_depth_half(f3d_ctx* ctx, const void* depth, int depth_type, int h, int w, double depth_scale, double max_depth, double gate,
+                   double* out /*[(h/2)*(w/2)]*/);
+int f3d_depth_half_dev(f3d_ctx* ctx, const void* depth, int depth_type, int h, int w, double depth_scale, double max_depth, double gate,
+                       double* out, void* stream);
+int f3d_maps_half(f3d_ctx* ctx, const double* model_vertex, const double* model_normal, const double* model_intensity /*may be NULL*/,
+                  int hm, int wm, const f3d_view* model_view, double gate, double* vertex_out /*[(hm/2)*(wm/2),3]*/,
+                  double* normal_out /*[(hm/2)*(wm/2),3]*/, double* intensity_out /*[(hm/2)*(wm/2)], NULL iff model_intensity is*/);
+int f3d_maps_half_dev(f3d_ctx* ctx, const double* model_vertex, const double* model_normal, const double* model_intensity, int hm, int wm,
+                      const f3d_view* model_view /*device*/, double gate, double* vertex_out, double* normal_out, double* intensity_out,
+                      void* stream);
+int f3d_icp_levels(f3d_ctx* ctx, const f3d_icp_level* levels /*host pointers inside*/, int nlevels, double max_depth,
+                   const double q_wxyz[4], const double t[3], const uint8_t* rgb /*[hc,wc_img,3] or NULL*/, int hc, int wc_img,
+                   double color_weight, double* pose /*[7]*/, double* stats /*[sum of iterations, 3 or 5]*/, int32_t* status);
+int f3d_icp_levels_dev(f3d_ctx* ctx, const f3d_icp_level* levels /*host records, device pointers inside*/, int nlevels, double max_depth,
+                       const double q_wxyz[4] /*host*/, const double t[3] /*host*/, const uint8_t* rgb, int hc, int wc_img,
+                       double color_weight, double* pose, double* stats, int32_t* status /*device, may be NULL*/, void* stream);
 
 #ifdef __cplusplus
 }
