@@ -515,6 +515,15 @@ int f3d_debug_fuse_deferred(f3d_ctx* ctx, void* stream, uint32_t counts[2]) {
     return F3D_OK;
 }
 
+int f3d_debug_fuse_decided(f3d_ctx* ctx, void* stream, uint32_t* count) {
+    int rc = enter(ctx); if (rc) return rc;
+    if (!count || !ctx->scratch[SLOT_TODO].p) return fail(ctx, F3D_ERR_INVALID, "fuse_decided: no fused call has run in this context");
+    hipStream_t s = pick(ctx, stream);
+    F3D_HIP(ctx, hipMemcpyAsync(count, f3d_fuse_todo::counters(ctx->scratch[SLOT_TODO].p) + 3, 4, hipMemcpyDeviceToHost, s));
+    F3D_HIP(ctx, hipStreamSynchronize(s));
+    return F3D_OK;
+}
+
 int f3d_project_vote_argmax(f3d_ctx* ctx, const void* xyz, f3d_dtype dtype, int64_t n, const f3d_view* views, int nviews,
                             const uint8_t* masks, int h, int w, int nclasses, const int32_t* filter, int nfilter,
                             double threshold, int64_t* classes, uint16_t* votes_u16) {

@@ -23,11 +23,20 @@
 #include "f3d_kernels.h"
 #include "f3d_fuse_blocks.h"
 #include "f3d_fuse_deal.h"
+#include "f3d_fuse_decide.h"
 #include <cstdlib>
 
 #pragma clang fp contract(off)
 
 #define F3D_NO_PREFILL ((int64_t)0x7fffffffffffffffLL)   // "the label vector was not pre-filled": every label is stored
+#ifndef F3D_DECIDE_FIRST
+#define F3D_DECIDE_FIRST 2               // early decisions: a wave checks its points with FIRST / 8 and SECOND / 8 of the group's whole-wave views left
+#define F3D_DECIDE_SECOND 1              //   (75 % and 87.5 % of them done: profiles/fuse_decided.md)
+#endif
+#ifndef F3D_DECIDE_MIN_MIXED
+#define F3D_DECIDE_MIN_MIXED 2            // ... and in front of the mixed views only when there are at least this many of them
+#endif
+#define F3D_DECIDE_MIN_VIEWS 8            // ... and not at all with fewer whole-wave views than this
 #define F3D_PART_MAX_GROUPS 16            // view groups whose open-view masks a parked point carries (more: the point is redone from nothing)
 #ifndef F3D_MID_DENSE
 #define F3D_MID_DENSE 8                  // k_fuse_mid: more open views per point than this on a block's average -> the views run in the outer loop
@@ -583,7 +592,7 @@ __global__ __launch_bounds__(F3D_BLOCK, F3D_FUSE_WAVES) void k_fuse(const T* __r
                                                      const float* __restrict__ ctabT, const double* __restrict__ vtabT,
                                                      uint32_t* __restrict__ carry, int chunk_flags, T* __restrict__ xyz_keep,
                                                      unsigned long long* __restrict__ umask, uint32_t* __restrict__ park, int park_slots, int park_stride,
-                                                     int64_t prefilled, const f3d_deal deal) {
+                                                     int64_t prefilled, int decide, const f3d_deal deal) {
 #if defined(F3D_EXP_STAMP)
     const long long stamp_entry = wall_clock64();
     bool stamp_first = true;
@@ -602,6 +611,15 @@ __global__ __launch_bounds__(F3D_BLOCK, F3D_FUSE_WAVES) void k_fuse(const T* __r
     const uint16_t* vmin = (WRAP || nviews > 255) ? nullptr : reinterpret_cast<const uint16_t*>(lutw + 128);   // totals beyond 255: the division itself
     const uint8_t* lut = reinterpret_cast<const uint8_t*>(lutw);
     const uint8_t* inv = lut + 256;
+    // Early decisions (f3d_fuse_decide.h): a point is "unlabelled" as soon as the views still out cannot lift it over the
+    // threshold, and a wave whose points are all decided leaves its view loops.  Off unless every view's vote is in this launch and no
+    // vote rows are asked for (template), the launcher saw a threshold above 0 and no filter list (`decide`), the threshold table
+    // exists, and the code book states that no label above nclasses occurs in the masks -- a view left out could otherwise hide the
+    // reference's IndexError.  All of it is launch-uniform.  Only the instances of a one-group call (TLDS: at most 64 views) have it,
+    // and of those the ones where a scan of two points' bins costs less than a view.
+    const bool dec_wave = TLDS && !WRITE_VOTES && !CARRY && !WRAP && decide != 0 && vmin != nullptr && cb->pad != 0 &&
+                          (BIN32 || words <= F3D_PACKED_SMALL_WORDS);
+    unsigned n_early = 0u;                                                // wave-tiles of this wave that left early
     const int tid = threadIdx.x, lane = threadIdx.x & 63;
     constexpr int TILE = F3D_BLOCK * PPL;                                 // PPL = points per lane: every instance in use has 2 (a one-point
                                                                           // instance for huge histograms was measured slower than two points at 2 blocks per CU)
@@ -802,6 +820,25 @@ __global__ __launch_bounds__(F3D_BLOCK, F3D_FUSE_WAVES) void k_fuse(const T* __r
 #else
 #define F3D_OLDEST ccode
 #endif
+        // the leader's count among the bins that can win (codes >= 2) and the votes counted so far (codes >= 1) of one point
+        auto scan_bins = [&](const uint32_t* hc, unsigned& lead, unsigned& cast) {
+            if (BIN32) {
+                lead = 0u; cast = hc[F3D_BLOCK];
+                for (int c = 2; c < ncodes; ++c) { const unsigned nc = hc[c * F3D_BLOCK]; cast += nc; lead = lead > nc ? lead : nc; }
+            } else {
+                const unsigned x0 = hc[0];
+                const unsigned c2 = (x0 >> 16) & 0xFFu, c3 = x0 >> 24;
+                cast = ((x0 >> 8) & 0xFFu) + c2 + c3; lead = c2 > c3 ? c2 : c3;
+                for (int wd = 1; wd < words; ++wd) {
+                    const unsigned x = hc[wd * F3D_BLOCK];
+                    cast = __builtin_amdgcn_sad_u8(x, 0u, cast);
+                    const unsigned m01 = (x & 0xFFu) > ((x >> 8) & 0xFFu) ? (x & 0xFFu) : ((x >> 8) & 0xFFu);
+                    const unsigned m23 = ((x >> 16) & 0xFFu) > (x >> 24) ? ((x >> 16) & 0xFFu) : (x >> 24);
+                    lead = lead > m01 ? lead : m01; lead = lead > m23 ? lead : m23;
+                }
+            }
+        };
+        bool left_early = false;                             // wave-uniform: every point of the tile is decided, the remaining views are skipped
         auto vote = [&](int q, unsigned b) {
             if (q >= PPL) return;
             if (BIN32) vote_bin32(q ? hcol1 : hcol0, b);
@@ -856,7 +893,34 @@ __global__ __launch_bounds__(F3D_BLOCK, F3D_FUSE_WAVES) void k_fuse(const T* __r
 #if defined(F3D_EXP_SKIP) && (F3D_EXP_SKIP == 1 || F3D_EXP_SKIP == 3)   // timing experiment: no whole-wave views
             todo_v = 0ull;
 #endif
+            // The last group, a few times per tile: is every point of the wave unlabelled whatever is still out?  Out for a point are the
+            // whole-wave views not yet projected, the gathers in flight (counted, not drained), the mixed views, the pending gather of an
+            // earlier group and the point's own unproven views.  A lane without a point is decided; a point without usable coordinates, or
+            // one that already has a place in the deferred list, never is.  (A decided point with unproven views is still deferred at the end
+            // of the group, with the bins it has: the float64 tier adds some of the votes the rule allowed for, and finds it unlabelled.)
+            const bool chk_on = dec_wave && g == ngroups - 1;
+            const int nwhole = chk_on ? __builtin_popcountll(todo_v) : 0;
+            const unsigned nmixed = (unsigned)__builtin_popcountll(valid_m & ~out_m & ~(in_m & row_m));
+            const unsigned nlater = nmixed + (unsigned)(F3D_CHUNK * F3D_GATHER_DEPTH) + (g > 0 ? 1u : 0u);
+            // every point of the wave is decided with `rout` views out besides its own unproven ones (all lanes active)
+            auto wave_decided = [&](unsigned rout) {
+                bool ok = true;
+#pragma unroll
+                for (int q = 0; q < PPL; ++q) {
+                    unsigned lead, cast;
+                    scan_bins(q ? hcol1 : hcol0, lead, cast);
+                    const bool dq = act[q] & (slot[q] < 0) & (unsure[q] == 0u) &
+                                    f3d_decided_unlabelled(lead, cast, rout + (unsigned)__builtin_popcountll(um[q]), vmin);
+                    ok = ok & (dq | !live[q]);
+                }
+                return (bool)__all(ok);
+            };
+            int chk_at = nwhole >= F3D_DECIDE_MIN_VIEWS ? (nwhole * F3D_DECIDE_FIRST) >> 3 : -1;   // the next check: with this many whole-wave views left
             while (todo_v) {
+                if (chk_on && __builtin_popcountll(todo_v) <= chk_at) {
+                    chk_at = chk_at > ((nwhole * F3D_DECIDE_SECOND) >> 3) ? (nwhole * F3D_DECIDE_SECOND) >> 3 : -1;
+                    if (wave_decided((unsigned)__builtin_popcountll(todo_v) + nlater)) { left_early = true; break; }
+                }
                 int cbit[F3D_CHUNK]; unsigned coff[2][F3D_CHUNK];
                 bool use[F3D_CHUNK];
                 unsigned long long unsm[2][F3D_CHUNK];                         // PART: the lanes a view left unproven, as a (scalar) lane mask
@@ -921,7 +985,9 @@ __global__ __launch_bounds__(F3D_BLOCK, F3D_FUSE_WAVES) void k_fuse(const T* __r
             }
             // every other visible view: per-point cull in offset form, image-range test; a lane inside the rounding margin of a
             // plane, or a view without a usable centre row, sends the point to the next tier
-            todo_v = valid_m & ~out_m & ~(in_m & row_m);
+            // ... and once more in front of the mixed views, the whole-wave votes drained: only the mixed views are still out
+            if (chk_on && !left_early && nmixed >= F3D_DECIDE_MIN_MIXED && wave_decided(nmixed + (g > 0 ? 1u : 0u))) left_early = true;
+            todo_v = left_early ? 0ull : valid_m & ~out_m & ~(in_m & row_m);
 #if defined(F3D_EXP_SKIP) && F3D_EXP_SKIP == 2         // timing experiment: no mixed views
             todo_v = 0ull;
 #elif defined(F3D_EXP_SKIP) && F3D_EXP_SKIP == 3       // neither: the per-tile prologue and epilogue alone
@@ -1068,8 +1134,18 @@ __global__ __launch_bounds__(F3D_BLOCK, F3D_FUSE_WAVES) void k_fuse(const T* __r
             }
             if (bad & !d) atomicOr(err, F3D_DEVERR_FUSE);
         }
+        n_early += left_early ? 1u : 0u;
         if (jn >= tiles_per_xcd) break;
         j = jn; jn = jnn;
+    }
+    static_assert(F3D_BLOCK == 256, "the counter is summed over four waves");
+    if (dec_wave) {                                          // block-uniform, as is every way here: one atomic per block for the counter
+        if (lane == 0) hcol0[0] = n_early;                   // (the wave's own column: nobody else's tile is touched)
+        __syncthreads();
+        if (tid == 0) {
+            const unsigned total = (hist[0] + hist[64]) + (hist[128] + hist[192]);
+            if (total) atomicAdd(todo_count + 3, total);
+        }
     }
     F3D_STAMP_EXIT();
 }
@@ -1612,6 +1688,8 @@ static hipError_t launch_fuse_t(const f3d_fuse_job& j, int mode, int grid) {
         // the guarded vote: an 8-bit bin of a real code can wrap (more than 255 views), or the "no sample" byte could (a point casts up to
         // nviews + 3 ngroups + 2 votes, placeholders included: from ~240 views on)
         const bool wrap = nviews + 3 * ((nviews + 63) / 64) + 2 > 255;
+        // early decisions (k_fuse): the launch-uniform half of their gates.  A NaN threshold compares false.
+        const int decide = (!V && !CARRY && !wrap && cnv <= 64 && flt.nfilter == 0 && j.threshold > 0.0) ? 1 : 0;
         // the view tables of ONE 64-view group are staged in LDS; with more views every instance reads the transposed global copies (the
         // tile loop then has no block-wide barrier, and the register allocation does not have to serve a path C3 never takes)
         const bool one_group = cnv <= 64;
@@ -1636,7 +1714,7 @@ static hipError_t launch_fuse_t(const f3d_fuse_job& j, int mode, int grid) {
             const f3d_deal deal = f3d_deal_make(positions, fuse_slots_per_xcd(j.occ, (const void*)kernel, lds, per_cu), F3D_FUSE_GRID / 8);
             hipLaunchKernelGGL(kernel, dim3(8 * deal.width[0]), b, lds, s, xyz, n, cviews, cnv, ccm, h, w, nclasses, flt.nfilter, flt.cls_dev, j.threshold,
                                j.classes, j.votes, j.err, j.perm, gather, todo_count, todo, j.cb, cmin, cmax, tab.ctabT, tab.vtabT,
-                               j.carry, chunk_flags, (T*)j.xyz_keep, umask, park, j.lay.park_slots, j.lay.park_stride, prefilled, deal);
+                               j.carry, chunk_flags, (T*)j.xyz_keep, umask, park, j.lay.park_slots, j.lay.park_stride, prefilled, decide, deal);
         };
         fuse(ks, lds_small, 0, F3D_BIN32_MAX_CODES, 4);
         if (nclasses + 3 > F3D_BIN32_MAX_CODES) fuse(km2, lds_mid, F3D_BIN32_MAX_CODES + 1, 4 * F3D_PACKED_SMALL_WORDS, one_group ? 4 : 3);

@@ -187,7 +187,7 @@ __device__ __forceinline__ void f3d_threshold_table(f3d_codebook* __restrict__ c
 __device__ __forceinline__ void f3d_code_lut_block(f3d_codebook* __restrict__ cb, int nclasses, int book, const f3d_filter_args& flt) {
     __shared__ unsigned pres[8];
     __shared__ int first_of[256];                                  // filter book: position of label l's first occurrence, -1 = not listed
-    __shared__ unsigned long long wb[4];
+    __shared__ unsigned long long wb[4], wr[4];
     const unsigned l = threadIdx.x;
     const bool act = l < 256u;
     if (l < 8) { pres[l] = book == 1 ? cb->presence[l] : 0xFFFFFFFFu; cb->presence[l] = 0u; }   // consumed (see f3d_launch_mask_presence)
@@ -206,12 +206,13 @@ __device__ __forceinline__ void f3d_code_lut_block(f3d_codebook* __restrict__ cb
         const unsigned code = (int)l > nclasses ? F3D_CODE_BAD : (listed ? 3u + (unsigned)rank : F3D_CODE_OTHER);
         cb->lut[l] = (uint8_t)code;
         if (listed) cb->inv[code] = (uint8_t)l;
-        if (l == 0) { cb->ncodes = 3 + distinct; cb->words = (3 + distinct + 3) >> 2; cb->book = 2; }
+        if (l == 0) { cb->ncodes = 3 + distinct; cb->words = (3 + distinct + 3) >> 2; cb->book = 2; cb->pad = 0; }   // (pad: this book cannot tell)
         return;
     }
     const bool pv = act && (int)l <= nclasses && ((pres[(l >> 5) & 7u] >> (l & 31u)) & 1u);     // label l is valid and present
-    const unsigned long long bal = __ballot(pv);
-    if (act && (l & 63u) == 0u) wb[l >> 6] = bal;
+    const bool pr = act && (int)l > nclasses && ((pres[(l >> 5) & 7u] >> (l & 31u)) & 1u);      // label l is rejected and present
+    const unsigned long long bal = __ballot(pv), balr = __ballot(pr);
+    if (act && (l & 63u) == 0u) { wb[l >> 6] = bal; wr[l >> 6] = balr; }
     __syncthreads();
     if (!act) return;
     int K = 0, below = __popcll(bal & ((1ull << (l & 63u)) - 1ull));
@@ -222,7 +223,9 @@ __device__ __forceinline__ void f3d_code_lut_block(f3d_codebook* __restrict__ cb
     else code = F3D_CODE_NONE;                                     // never gathered; its vote row reads the always-zero bin 0
     cb->lut[l] = (uint8_t)code;
     if (code >= 2u) cb->inv[code] = (uint8_t)l;
-    if (l == 0) { cb->ncodes = K + 2; cb->words = (K + 2 + 3) >> 2; cb->book = book; }
+    // pad = "no label above nclasses occurs in the masks": only the presence book knows.  k_fuse may then leave views out of a point's
+    // vote without hiding the reference's IndexError (f3d_fuse_decide.h)
+    if (l == 0) { cb->ncodes = K + 2; cb->words = (K + 2 + 3) >> 2; cb->book = book; cb->pad = (book == 1 && !(wr[0] | wr[1] | wr[2] | wr[3])) ? 1 : 0; }
 }
 
 // [V,H,W] row-major labels -> [V][ceil(H/8) + 2][ceil(W/8) + 2][8][8] bin codes (border tiles = "no sample"); one thread moves one

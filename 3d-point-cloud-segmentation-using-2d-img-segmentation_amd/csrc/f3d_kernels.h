@@ -323,7 +323,8 @@ struct f3d_codebook {
     uint8_t lut[256];                      // label -> bin code (0 = no sample / absent label, 1 = rejected label, ...)
     uint8_t inv[256];                      // bin code -> label (must follow lut directly: the kernels stage both with one copy)
     uint16_t cmin[256];                    // (must follow inv directly) cmin[t]: votes below which max / t < threshold (k_threshold_table)
-    int ncodes, words, book, pad;          // bins in use, histogram dwords per thread = (ncodes + 3) / 4, 1 presence / 2 filter book
+    int ncodes, words, book, pad;          // bins in use, histogram dwords per thread = (ncodes + 3) / 4, 1 presence / 2 filter book,
+                                           // pad = 1: the book states that no label above nclasses occurs in the masks (presence book only)
     unsigned presence[8];                  // bit l: label l occurs in the masks
 };
 
@@ -337,7 +338,7 @@ hipError_t f3d_launch_inside_polyhedra(const void* xyz, int dtype, int64_t n, co
                                        hipStream_t s);
 #define F3D_CODE_MAX_NCLASSES 253            // labels 0..nclasses + "rejected" + "no sample" must fit the 256 byte codes
 // The SLOT_TODO scratch of a fused call: 4 counters (first list, second list, the exact kernel's list of a call
-// with more than 255 views, 1 spare); two index lists of n entries (fast kernel -> float64 tier -> exact kernel); then per parked slot of
+// with more than 255 views, the wave-tiles k_fuse took out of their view loops early); two index lists of n entries (fast kernel -> float64 tier -> exact kernel); then per parked slot of
 // the first list the open-view masks (ngroups words of 64 views) and, behind all of those, the parked bins (park_stride dwords each).
 struct f3d_fuse_todo {
     size_t bytes, list2_off, umask_off, park_off;      // of the whole block; byte offsets (the counters and the first list have fixed ones)

@@ -121,6 +121,7 @@ def library():
         'f3d_fuse_chunk_coded_dev': (i32, [vp, vp, i32, i64, vp, i32, i32, i32, vp, i32, i32, i32, vp, i32, dbl, vp, C.c_uint, vp, vp]),
         'f3d_debug_fastpath_audit': (i32, [vp, vp, i32, i64, vp, i32, i32, i32, vp]),
         'f3d_debug_fuse_deferred': (i32, [vp, vp, vp]),
+        'f3d_debug_fuse_decided': (i32, [vp, vp, vp]),
         'f3d_cloud_sort_cells_dev': (i32, [vp, vp, i32, i64, vp, vp, vp]),
         'f3d_take_device_error': (i32, [vp, vp]),
         'f3d_vote_uv2pt': (i32, [vp, vp, vp, i64, vp, i64, i32]),
@@ -1710,6 +1711,12 @@ class Context:
         c = np.zeros(2, np.uint32)
         self._check(self._lib.f3d_debug_fuse_deferred(self._h, stream, _ptr(c)))
         return int(c[0]), int(c[1])
+
+    def fuse_decided(self, stream=None):
+        """Wave-tiles (128 points) of the last fused call that left their view loops early: every point already decided "unlabelled"."""
+        c = np.zeros(1, np.uint32)
+        self._check(self._lib.f3d_debug_fuse_decided(self._h, stream, _ptr(c)))
+        return int(c[0])
 
     def flood_order_dev(self, classes_ptr, n, offsets_ptr, neighbours_ptr, instance_classes, root_ptr, order_ptr, coffs_ptr, flags_ptr,
                         stream=None):

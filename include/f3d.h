@@ -255,6 +255,9 @@ int f3d_debug_fastpath_audit(f3d_ctx* ctx, const void* xyz, f3d_dtype dtype, int
  * tier (counts[0]) and how many of those needed the reference's own arithmetic for at least one view (counts[1]).
  * Synchronises `stream`. */
 int f3d_debug_fuse_deferred(f3d_ctx* ctx, void* stream, uint32_t counts[2]);
+/* Diagnostic: how many wave-tiles (128 points) of the last fused call of this context left their view loops early because
+ * every point of the tile was already decided "unlabelled".  Synchronises `stream`. */
+int f3d_debug_fuse_decided(f3d_ctx* ctx, void* stream, uint32_t* count);
 /* Sort of the cloud by coarse grid cell: perm (int32 [n], caller-order index of sorted point i)
  * and, unless NULL, sorted_xyz (same dtype/size as xyz); device buffers owned by the caller. */
 int f3d_cloud_sort_cells_dev(f3d_ctx* ctx, const void* xyz, f3d_dtype dtype, int64_t n,
