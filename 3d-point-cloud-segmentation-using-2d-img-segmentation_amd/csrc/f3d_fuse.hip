@@ -24,6 +24,7 @@
 #include "f3d_fuse_blocks.h"
 #include "f3d_fuse_deal.h"
 #include "f3d_fuse_decide.h"
+#include "f3d_fuse_todo.h"               // F3D_PART_MAX_GROUPS and f3d_fuse_todo_layout: host code that tests compile on its own
 #include <cstdlib>
 
 #pragma clang fp contract(off)
@@ -37,7 +38,6 @@
 #define F3D_DECIDE_MIN_MIXED 2            // ... and in front of the mixed views only when there are at least this many of them
 #endif
 #define F3D_DECIDE_MIN_VIEWS 8            // ... and not at all with fewer whole-wave views than this
-#define F3D_PART_MAX_GROUPS 16            // view groups whose open-view masks a parked point carries (more: the point is redone from nothing)
 #ifndef F3D_MID_DENSE
 #define F3D_MID_DENSE 8                  // k_fuse_mid: more open views per point than this on a block's average -> the views run in the outer loop
 #endif
@@ -1580,25 +1580,7 @@ static size_t mid_lds_bytes(int words_max) {
     return (size_t)(128 + (F3D_BLOCK + 4) + 2 * F3D_BLOCK) * 4 + (size_t)F3D_BLOCK * 8 + (size_t)3 * F3D_BLOCK * 8 + (size_t)words_max * F3D_BLOCK * 4;
 }
 
-// The layout of the todo block (f3d_fuse_todo, f3d_kernels.h).  The slots of the first list whose points can be parked (bins + view
-// masks) are n / 16 + 4096; deferred points beyond them are redone from nothing.
-f3d_fuse_todo f3d_fuse_todo_layout(int64_t n, int nviews, int nclasses) {
-    int64_t k = 0;
-    if (nviews > 0 && nviews <= 64 * F3D_PART_MAX_GROUPS) {
-        k = n / 16 + 4096;
-        if (const char* e = getenv("F3D_DEBUG_PARK_SLOTS")) k = atoll(e);   // tests: force the overflow path (deferred points beyond the parked slots)
-        k = k < n ? (k < 0 ? 0 : k) : n;
-    }
-    f3d_fuse_todo t;
-    t.park_slots = (int)k;
-    t.park_stride = (nclasses + 1 + 2 + 3) >> 2;              // every label 0..nclasses present, plus the codes "no sample" and "rejected"
-    t.ngroups = (nviews + 63) / 64;
-    t.list2_off = 4 * sizeof(unsigned int) + (size_t)n * sizeof(int32_t);
-    t.umask_off = t.list2_off + (size_t)n * sizeof(int32_t);
-    t.park_off = t.umask_off + (size_t)k * t.ngroups * sizeof(unsigned long long);
-    t.bytes = t.park_off + (size_t)k * t.park_stride * sizeof(uint32_t);
-    return t;
-}
+// (The layout of the todo block, f3d_fuse_todo_layout, is defined in f3d_fuse_todo.h.)
 
 // The label vector is filled with the label of a point nobody votes for ("unlabelled": nclasses, through the filter remap) by
 // streaming stores, and k_fuse scatters only the labels that differ.  A scattered 8-byte store is one write transaction on the fabric

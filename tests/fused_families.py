@@ -92,22 +92,21 @@ def _ulp_steps(x, steps):
     return x
 
 
-@functools.lru_cache(maxsize=None)
-def on_plane_points(name, per=300):
-    """The adversarial cloud of a family, [V * 5 * per, 3] float64 in (view, plane, draw) order: per view, `per` points on each
+def on_plane_points_of(K, q, t, max_depth, w, h, per, owners=None, seed=29):
+    """The adversarial cloud of a scene, [len(owners) * 5 * per, 3] float64 in (owner, plane, draw) order (owners: view indices in
+    the order given; None = every view in turn): per owner view, `per` points on each
     of the 4 side planes (eye + r (s a + (1 - s) b): a, b the unit rays through two adjacent image corners, built the way
     O.frustum_data builds them) and `per` on the far plane (eye + max_depth d / (d . lookat), d through pixels of the image
     grown by 20 % on every side).  The oracle's unit normal of a telephoto side plane -- the cross product of two nearly parallel
     rays -- is itself ~1e-15 rad off the plane those rays span: 30 ulp at the far end.  So every point takes one step onto the
     plane AS THE ORACLE EVALUATES IT (it ends within an ulp or two of n . (p - pp) = 0), and then every coordinate is moved by
     -3..3 ulp: each point straddles one plane of its own view."""
-    _, K, q, t, max_depth, w, h, _ = family(name)
-    rng = np.random.default_rng(29)
+    rng = np.random.default_rng(seed)
     Kinv = O.inv3(K)
     eyes, lookats, _, _ = O.frustum_data(K, w, h, q, t)
     ppts, pnrm = O.frustum_planes(K, w, h, q, t, max_depth)
     out = []
-    for j in range(len(t)):
+    for j in (range(len(t)) if owners is None else owners):
         def rays(pix):                                                   # unit rays through pixels, as O.frustum_data builds them
             cam = np.stack([(Kinv[r, 0] * pix[:, 0] + Kinv[r, 1] * pix[:, 1]) + Kinv[r, 2] * pix[:, 2] for r in range(3)], axis=1)
             vec = (O.rotate(q[j], cam) + t[j][None, :]) - eyes[j][None, :]
@@ -128,6 +127,13 @@ def on_plane_points(name, per=300):
     pts = _ulp_steps(pts, rng.integers(-3, 4, pts.shape))
     pts.setflags(write=False)
     return pts
+
+
+@functools.lru_cache(maxsize=None)
+def on_plane_points(name, per=300):
+    """on_plane_points_of the family's scene, every view an owner: [V * 5 * per, 3] in (view, plane, draw) order."""
+    _, K, q, t, max_depth, w, h, _ = family(name)
+    return on_plane_points_of(K, q, t, max_depth, w, h, per)
 
 
 def on_plane_owner(name, per=300):

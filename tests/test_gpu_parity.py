@@ -368,7 +368,8 @@ def test_device_api_sort_flags_and_prepared_layout(ctx):
 @pytest.mark.parametrize('mask_kind', ['block64', 'iid'])
 def test_partially_deferred_points_parked_bins_and_their_overflow(ctx, mask_kind, monkeypatch):
     """A point the float32 kernel cannot finish keeps the votes of its proven views: bins parked in HBM, one mask of open views, the
-    float64 tier visits those views only (calls with at most 64 views).  Deferred points beyond the parked slots (n/16 + 4096 of them) are
+    float64 tier visits those views only (one mask per 64-view group, up to 16 groups; this scene has 64 views, one group -- several
+    groups: tests/test_fuse_view_groups_gpu.py).  Deferred points beyond the parked slots (n/16 + 4096 of them) are
     redone from nothing -- forced here through F3D_DEBUG_PARK_SLOTS; an unsorted cloud (whole-scene wave boxes, wide float32 bounds)
     makes the deferred list long.  Labels and vote rows must not depend on which way a point went."""
     sc = synth.scene('C3', n=120_000, mask_kind=mask_kind)
