@@ -3579,6 +3579,113 @@ int f3d_icp_levels(f3d_ctx* ctx, const f3d_icp_level* levels, int nlevels, doubl
 }
 
 // ---------------------------------------------------------------------------------------------
+// cloud-to-cloud ICP: nearest-point search in the target's grid fused with the sums (f3d_icp.hip; contract in f3d.h)
+// ---------------------------------------------------------------------------------------------
+#define F3D_CLOUD_ICP_BAD "bad arguments (n, m < 2^31; float32 / float64 clouds; a known mode, normals in plane mode; max_dist finite, > 0 and < 1e300; a finite t; a finite non-zero quaternion)"
+static bool cloud_icp_ok(const void* source, int sdtype, int64_t n, const void* target, int tdtype, int64_t m, const double* normals, int mode,
+                         const double* q, const double* t, double max_dist) {
+    double qn[4];
+    return n >= 0 && n <= 0x7fffffffLL && m >= 0 && m <= 0x7fffffffLL && (n == 0 || source) && (m == 0 || target) && dtype_ok(sdtype) &&
+           dtype_ok(tdtype) && (mode == F3D_CLOUD_ICP_POINT || (mode == F3D_CLOUD_ICP_PLANE && (normals || m == 0))) && q && t &&
+           pos_finite(max_dist) && max_dist < 1e300 && all_finite(t, 3) && unit_quat(q, qn);
+}
+
+int f3d_ctx_reserve_cloud_icp(f3d_ctx* ctx, int64_t m, int64_t n) {
+    int rc = enter(ctx); if (rc) return rc;
+    if (m < 0 || m > 0x7fffffffLL || n < 0 || n > 0x7fffffffLL) return fail(ctx, F3D_ERR_INVALID, "ctx_reserve_cloud_icp: m and n must be in [0, 2^31)");
+    return reserve(ctx, {{SLOT_GRAPH_BBOX, f3d_graph_bbox_bytes()}, {SLOT_KNN_FLAG, 64},
+                         {SLOT_KNN, f3d_graph_scratch_bytes(m, GRID_MAX_CELLS)},                       // (any grid the radius allows)
+                         {SLOT_ICP, f3d_icp_scratch_bytes(n)}});
+}
+
+// What the two _dev entries share after their argument checks: the one readback (the target's box and the source's non-finite flag
+// together), the target's grid, built once in SLOT_KNN, and the round scratch in SLOT_ICP.
+static int cloud_icp_prepare(f3d_ctx* ctx, const char* op, const void* source, f3d_dtype sdtype, int64_t n, const void* target, f3d_dtype tdtype,
+                             int64_t m, const double* normals, int mode, double max_dist, hipStream_t s, f3d_cloud_icp_args* a, void** scratch) {
+    if (m == 0) return fail(ctx, F3D_ERR_INVALID, "%s: the target is empty", op);
+    void *dbox, *dflag, *grid;
+    int rc = ensure(ctx, SLOT_GRAPH_BBOX, f3d_graph_bbox_bytes(), &dbox); if (rc) return rc;
+    if ((rc = ensure(ctx, SLOT_KNN_FLAG, 64, &dflag))) return rc;
+    unsigned flag = 0;
+    F3D_HIP(ctx, hipMemsetAsync(dflag, 0, 4, s));
+    if (n > 0) F3D_HIP(ctx, f3d_launch_knn_flag(source, sdtype, n, (unsigned*)dflag, s));
+    F3D_HIP(ctx, hipMemcpyAsync(&flag, dflag, 4, hipMemcpyDeviceToHost, s));
+    if ((rc = cloud_search(ctx, target, tdtype, m, max_dist, s, op, &a->gs))) return rc;               // (synchronises)
+    if (flag) return fail(ctx, F3D_ERR_INVALID, "%s: the source contains NaN or infinity", op);
+    if ((rc = ensure(ctx, SLOT_KNN, f3d_graph_scratch_bytes(m, f3d_ncells(a->gs.g)), &grid))) return rc;
+    if ((rc = ensure(ctx, SLOT_ICP, f3d_icp_scratch_bytes(n), scratch))) return rc;
+    F3D_HIP(ctx, f3d_launch_graph_grid(target, tdtype, m, a->gs.g, grid, &a->gv, s));
+    a->source = source; a->source_dtype = sdtype; a->n = n; a->normals = normals; a->mode = mode;
+    return F3D_OK;
+}
+
+int f3d_cloud_icp_sums_dev(f3d_ctx* ctx, const void* source, f3d_dtype source_dtype, int64_t n, const void* target, f3d_dtype target_dtype, int64_t m,
+                           const double* target_normals, int mode, const double q_wxyz[4], const double t[3], double max_dist, double* sums,
+                           int32_t* pairs, void* stream) {
+    int rc = enter(ctx); if (rc) return rc;
+    if (!sums || !cloud_icp_ok(source, source_dtype, n, target, target_dtype, m, target_normals, mode, q_wxyz, t, max_dist))
+        return fail(ctx, F3D_ERR_INVALID, "cloud_icp_sums: " F3D_CLOUD_ICP_BAD);
+    hipStream_t s = pick(ctx, stream);
+    f3d_cloud_icp_args a;
+    void* scratch;
+    if ((rc = cloud_icp_prepare(ctx, "cloud_icp_sums", source, source_dtype, n, target, target_dtype, m, target_normals, mode, max_dist, s, &a, &scratch)))
+        return rc;
+    F3D_HIP(ctx, f3d_launch_cloud_icp_sums(a, q_wxyz, t, scratch, sums, pairs, s));
+    return F3D_OK;
+}
+
+int f3d_cloud_icp_dev(f3d_ctx* ctx, const void* source, f3d_dtype source_dtype, int64_t n, const void* target, f3d_dtype target_dtype, int64_t m,
+                      const double* target_normals, int mode, const double q_wxyz[4], const double t[3], double max_dist, int iterations,
+                      int min_pairs, double* pose, double* stats, int32_t* status, void* stream) {
+    int rc = enter(ctx); if (rc) return rc;
+    if (!pose || !stats || !cloud_icp_ok(source, source_dtype, n, target, target_dtype, m, target_normals, mode, q_wxyz, t, max_dist))
+        return fail(ctx, F3D_ERR_INVALID, "cloud_icp: " F3D_CLOUD_ICP_BAD);
+    if (iterations < 1 || min_pairs < 6) return fail(ctx, F3D_ERR_INVALID, "cloud_icp: iterations must be at least 1 and min_pairs at least 6");
+    hipStream_t s = pick(ctx, stream);
+    f3d_cloud_icp_args a;
+    void* scratch;
+    if ((rc = cloud_icp_prepare(ctx, "cloud_icp", source, source_dtype, n, target, target_dtype, m, target_normals, mode, max_dist, s, &a, &scratch)))
+        return rc;
+    F3D_HIP(ctx, f3d_launch_cloud_icp(a, q_wxyz, t, iterations, min_pairs, scratch, pose, stats, status, s));
+    return F3D_OK;
+}
+
+int f3d_cloud_icp_sums(f3d_ctx* ctx, const void* source, f3d_dtype source_dtype, int64_t n, const void* target, f3d_dtype target_dtype, int64_t m,
+                       const double* target_normals, int mode, const double q_wxyz[4], const double t[3], double max_dist, double* sums,
+                       int32_t* pairs) {
+    int rc = enter(ctx); if (rc) return rc;
+    if (!sums || !cloud_icp_ok(source, source_dtype, n, target, target_dtype, m, target_normals, mode, q_wxyz, t, max_dist))
+        return fail(ctx, F3D_ERR_INVALID, "cloud_icp_sums: " F3D_CLOUD_ICP_BAD);
+    staging st(ctx);
+    const void* dsrc = st.in(source, xyz_bytes(source_dtype, n));
+    const void* dtgt = st.in(target, xyz_bytes(target_dtype, m));
+    const double* dnrm = mode == F3D_CLOUD_ICP_PLANE ? st.in(target_normals, (size_t)m * 24) : nullptr;
+    double* ds = st.out(sums, F3D_ICP_NSUMS * sizeof(double));
+    int32_t* dpr = st.out(pairs, (size_t)n * 4);
+    if (!st.rc) st.rc = f3d_cloud_icp_sums_dev(ctx, dsrc, source_dtype, n, dtgt, target_dtype, m, dnrm, mode, q_wxyz, t, max_dist, ds, dpr, ctx->stream);
+    return st.finish();
+}
+
+int f3d_cloud_icp(f3d_ctx* ctx, const void* source, f3d_dtype source_dtype, int64_t n, const void* target, f3d_dtype target_dtype, int64_t m,
+                  const double* target_normals, int mode, const double q_wxyz[4], const double t[3], double max_dist, int iterations, int min_pairs,
+                  double* pose, double* stats, int32_t* status) {
+    int rc = enter(ctx); if (rc) return rc;
+    if (!pose || !stats || !status || !cloud_icp_ok(source, source_dtype, n, target, target_dtype, m, target_normals, mode, q_wxyz, t, max_dist))
+        return fail(ctx, F3D_ERR_INVALID, "cloud_icp: " F3D_CLOUD_ICP_BAD);
+    if (iterations < 1 || min_pairs < 6) return fail(ctx, F3D_ERR_INVALID, "cloud_icp: iterations must be at least 1 and min_pairs at least 6");
+    staging st(ctx);
+    const void* dsrc = st.in(source, xyz_bytes(source_dtype, n));
+    const void* dtgt = st.in(target, xyz_bytes(target_dtype, m));
+    const double* dnrm = mode == F3D_CLOUD_ICP_PLANE ? st.in(target_normals, (size_t)m * 24) : nullptr;
+    double* dp = st.out(pose, 7 * sizeof(double));
+    double* ds = st.out(stats, (size_t)iterations * 3 * sizeof(double));
+    int32_t* dst = st.out(status, sizeof(int32_t));
+    if (!st.rc) st.rc = f3d_cloud_icp_dev(ctx, dsrc, source_dtype, n, dtgt, target_dtype, m, dnrm, mode, q_wxyz, t, max_dist, iterations, min_pairs, dp, ds,
+                                          dst, ctx->stream);
+    return st.finish();
+}
+
+// ---------------------------------------------------------------------------------------------
 // feature fusion: per-point pooling of per-pixel feature maps over views (f3d_features.hip)
 // ---------------------------------------------------------------------------------------------
 #define F3D_FEAT_BAD F3D_RENDER_BAD ", hf, wf >= 1 with hf * wf < 2^31, d in [1, 4096], float16 / float32 features, depth_tol >= 0, views_per_pass >= 0"

@@ -25,6 +25,12 @@
 //   k_depth_half<T>       one thread per output pixel, grid-stride; the 2 x 2 block's four samples in registers; no LDS, no atomics.
 //   k_maps_half<INTENSITY> the same over the model maps: a block row's two map rows are 48 contiguous bytes, which the compiler
 //                         fetches with three 16-byte loads (global memory needs no 16-byte alignment for them).
+// Cloud to cloud (f3d_cloud_icp_sums, f3d_cloud_icp): the source is an unordered cloud and its partner the nearest target point, found
+// in the target's radius grid (f3d_launch_graph_grid, built once per call by the C-ABI layer) with f3d_grid_walk_d2.
+//   k_cloud_icp_terms<T, MODE>  k_icp_terms' wave per chunk, lane order, butterfly and chunk row.  A lane transforms its point, walks the
+//                         <= 27 cells around it keeping the running (d2, index) minimum, and forms the terms of the pair: no pair list is
+//                         kept in memory.  MODE is point-to-plane (the target's normals) or point-to-point (three unit-axis rows per pair,
+//                         their zero products left out).  k_icp_solve follows unchanged.
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
@@ -476,6 +482,95 @@ __global__ __launch_bounds__(F3D_BLOCK) void k_icp_solve(const double* __restric
     row[2] = (double)F3D_ICP_OK;
 }
 
+// ---- cloud to cloud: the nearest target of every source point and its terms, one kernel ---------------------------------------------
+// the nearest target of p within the radius under (d2, caller-order index): j = that index or -1, at = its place in the sorted copy
+__device__ __forceinline__ void cloud_nearest(const f3d_gridview& gv, const f3d_gridsearch& gs, double px, double py, double pz, int& j, int& at) {
+    double best = INFINITY;
+    int jb = 0x7fffffff, kb = 0;
+    if (f3d_in_box(gs.reach, px, py, pz))
+        f3d_grid_walk_d2(gv, gs.g, px, py, pz, gs.r2, [&](int k, double d) {
+            if (d <= best) {                                                       // (a candidate farther than the minimum needs no index)
+                const int jn = (int)gv.perm[k];
+                if (d < best || jn < jb) { best = d; jb = jn; kb = k; }
+            }
+            return false;
+        });
+    j = jb == 0x7fffffff ? -1 : jb;
+    at = kb;
+}
+
+// One wave per chunk of F3D_ICP_CHUNK source points, the lane order, butterfly and chunk row of k_icp_terms.  pairs (NULL = not wanted)
+// receives the nearest target of every source point, also where the pair is then rejected for its normal.
+template <typename T, int MODE>
+__global__ __launch_bounds__(F3D_BLOCK) void k_cloud_icp_terms(const T* __restrict__ source, int64_t n, int64_t nchunks, const double* __restrict__ sorted,
+                                                                const uint32_t* __restrict__ perm, const int2* __restrict__ cells, f3d_gridsearch gs,
+                                                                const double* __restrict__ normals, const double* __restrict__ pose,
+                                                                const int* __restrict__ lost, double* __restrict__ chunks, int32_t* __restrict__ pairs) {
+    if (*lost) return;
+    const f3d_gridview gv = {sorted, perm, cells};
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    double qn[4];
+    normalised(pose, qn);
+    const double t[3] = {pose[4], pose[5], pose[6]};
+    for (int64_t chunk = (int64_t)blockIdx.x * ICP_WAVES + wave; chunk < nchunks; chunk += (int64_t)gridDim.x * ICP_WAVES) {
+        const int64_t first = chunk * F3D_ICP_CHUNK;
+        const int64_t count = n - first < F3D_ICP_CHUNK ? n - first : (int64_t)F3D_ICP_CHUNK;
+        double acc[NS];
+#pragma unroll
+        for (int j = 0; j < NS; ++j) acc[j] = 0.0;
+        for (int64_t i = lane; i < count; i += 64) {
+            const f3d_p3 pr = f3d_rotate(qn, f3d_load_p3(source, first + i));
+            const double px = pr.x + t[0], py = pr.y + t[1], pz = pr.z + t[2];
+            int j, at;
+            cloud_nearest(gv, gs, px, py, pz, j, at);
+            if (pairs) pairs[first + i] = j;
+            if (j < 0) continue;                                                  // + 0.0 leaves an accumulator as it is (none is ever -0.0)
+            const double e0 = px - sorted[3 * (int64_t)at], e1 = py - sorted[3 * (int64_t)at + 1], e2 = pz - sorted[3 * (int64_t)at + 2];
+            if constexpr (MODE == F3D_CLOUD_ICP_PLANE) {
+                const double N0 = normals[3 * (int64_t)j], N1 = normals[3 * (int64_t)j + 1], N2 = normals[3 * (int64_t)j + 2];
+                if (!(fabs(N0) < INFINITY && fabs(N1) < INFINITY && fabs(N2) < INFINITY)) continue;
+                const double r = f3d_dot3(N0, N1, N2, e0, e1, e2);
+                const double J[6] = {pr.y * N2 - pr.z * N1, pr.z * N0 - pr.x * N2, pr.x * N1 - pr.y * N0, N0, N1, N2};
+                int s = 0;
+#pragma unroll
+                for (int a = 0; a < 6; ++a)
+#pragma unroll
+                    for (int b = a; b < 6; ++b) { acc[s] = acc[s] + J[a] * J[b]; ++s; }
+#pragma unroll
+                for (int a = 0; a < 6; ++a) acc[21 + a] = acc[21 + a] + J[a] * r;
+                acc[27] = acc[27] + r * r;
+            } else {
+                // N = the unit axis a, a = 0, 1, 2 in turn: J = (cross(pr, e_a), e_a) has the entries written here and zeros, r = e[a].
+                // The products with a zero entry are +-0.0 and leave their accumulator as it is, so they are not formed.
+                const double nx = -pr.x, ny = -pr.y, nz = -pr.z;
+                // a = 0: J = (0, pr.z, -pr.y, 1, 0, 0)
+                acc[6] = acc[6] + pr.z * pr.z; acc[7] = acc[7] + pr.z * ny; acc[8] = acc[8] + pr.z;
+                acc[11] = acc[11] + ny * ny; acc[12] = acc[12] + ny; acc[15] = acc[15] + 1.0;
+                acc[22] = acc[22] + pr.z * e0; acc[23] = acc[23] + ny * e0; acc[24] = acc[24] + e0;
+                acc[27] = acc[27] + e0 * e0;
+                // a = 1: J = (-pr.z, 0, pr.x, 0, 1, 0)
+                acc[0] = acc[0] + nz * nz; acc[2] = acc[2] + nz * pr.x; acc[4] = acc[4] + nz;
+                acc[11] = acc[11] + pr.x * pr.x; acc[13] = acc[13] + pr.x; acc[18] = acc[18] + 1.0;
+                acc[21] = acc[21] + nz * e1; acc[23] = acc[23] + pr.x * e1; acc[25] = acc[25] + e1;
+                acc[27] = acc[27] + e1 * e1;
+                // a = 2: J = (pr.y, -pr.x, 0, 0, 0, 1)
+                acc[0] = acc[0] + pr.y * pr.y; acc[1] = acc[1] + pr.y * nx; acc[5] = acc[5] + pr.y;
+                acc[6] = acc[6] + nx * nx; acc[10] = acc[10] + nx; acc[20] = acc[20] + 1.0;
+                acc[21] = acc[21] + pr.y * e2; acc[22] = acc[22] + nx * e2; acc[26] = acc[26] + e2;
+                acc[27] = acc[27] + e2 * e2;
+            }
+            acc[28] = acc[28] + 1.0;
+        }
+#pragma unroll
+        for (int j = 0; j < NS; ++j)
+            for (int off = 32; off > 0; off >>= 1) acc[j] = acc[j] + __shfl_xor(acc[j], off);
+        if (lane == 0) {
+#pragma unroll
+            for (int j = 0; j < NS; ++j) chunks[chunk * NS + j] = acc[j];
+        }
+    }
+}
+
 // ---- coarse-to-fine: one pyramid step of a depth frame and of model maps ------------------------------------------------------
 // Output pixel (u, v) reads the input pixels (2v, 2u), (2v, 2u+1), (2v+1, 2u), (2v+1, 2u+1), in that order; an odd last row or column
 // of the input is never read.
@@ -809,4 +904,56 @@ hipError_t f3d_launch_icp_levels(const f3d_icp_level* levels, int nlevels, doubl
                                  hipStream_t s) {
     if (rgb) return launch_levels<true>(levels, nlevels, max_depth, q, t, rgb, hc, wc_img, color_weight, scratch, pose_out, stats, status, s);
     return launch_levels<false>(levels, nlevels, max_depth, q, t, nullptr, 0, 0, 0.0, scratch, pose_out, stats, status, s);
+}
+
+namespace {
+
+template <typename T>
+void launch_cloud_terms_of(const f3d_cloud_icp_args& a, const double* pose, const int* lost, double* chunks, int32_t* pairs, hipStream_t s) {
+    const int64_t nchunks = (a.n + F3D_ICP_CHUNK - 1) / F3D_ICP_CHUNK;
+    const dim3 gr(f3d_grid_for(nchunks, ICP_WAVES, F3D_GRID_CAP)), b(F3D_BLOCK);
+    if (a.mode == F3D_CLOUD_ICP_PLANE)
+        hipLaunchKernelGGL((k_cloud_icp_terms<T, F3D_CLOUD_ICP_PLANE>), gr, b, 0, s, (const T*)a.source, a.n, nchunks, a.gv.sorted, a.gv.perm, a.gv.cells,
+                           a.gs, a.normals, pose, lost, chunks, pairs);
+    else
+        hipLaunchKernelGGL((k_cloud_icp_terms<T, F3D_CLOUD_ICP_POINT>), gr, b, 0, s, (const T*)a.source, a.n, nchunks, a.gv.sorted, a.gv.perm, a.gv.cells,
+                           a.gs, a.normals, pose, lost, chunks, pairs);
+}
+
+void launch_cloud_terms(const f3d_cloud_icp_args& a, const double* pose, const int* lost, double* chunks, int32_t* pairs, hipStream_t s) {
+    if (a.source_dtype == F3D_F64) launch_cloud_terms_of<double>(a, pose, lost, chunks, pairs, s);
+    else launch_cloud_terms_of<float>(a, pose, lost, chunks, pairs, s);
+}
+
+}  // namespace
+
+hipError_t f3d_launch_cloud_icp_sums(const f3d_cloud_icp_args& a, const double q[4], const double t[3], void* scratch, double* sums, int32_t* pairs,
+                                     hipStream_t s) {
+    const icp_scratch l = icp_layout(a.n);
+    char* base = (char*)scratch;
+    double *chunks = (double*)(base + l.chunks), *pose = (double*)(base + l.pose);
+    int* lost = (int*)(base + l.lost);
+    hipLaunchKernelGGL(k_icp_init, dim3(1), dim3(64), 0, s, pose, lost, q[0], q[1], q[2], q[3], t[0], t[1], t[2]);
+    launch_cloud_terms(a, pose, lost, chunks, pairs, s);
+    hipLaunchKernelGGL(k_icp_solve<false>, dim3(1), dim3(F3D_BLOCK), 0, s, chunks, (a.n + F3D_ICP_CHUNK - 1) / F3D_ICP_CHUNK, sums, pose, lost, 0.0,
+                       (double*)nullptr, 0, icp_solve_color<false>{});
+    return hipGetLastError();
+}
+
+hipError_t f3d_launch_cloud_icp(const f3d_cloud_icp_args& a, const double q[4], const double t[3], int iterations, int min_pairs, void* scratch,
+                                double* pose_out, double* stats, int32_t* status, hipStream_t s) {
+    const icp_scratch l = icp_layout(a.n);
+    char* base = (char*)scratch;
+    double *chunks = (double*)(base + l.chunks), *pose = (double*)(base + l.pose);
+    int* lost = (int*)(base + l.lost);
+    hipLaunchKernelGGL(k_icp_init, dim3(1), dim3(64), 0, s, pose, lost, q[0], q[1], q[2], q[3], t[0], t[1], t[2]);
+    for (int round = 0; round < iterations; ++round) {
+        launch_cloud_terms(a, pose, lost, chunks, nullptr, s);
+        hipLaunchKernelGGL(k_icp_solve<false>, dim3(1), dim3(F3D_BLOCK), 0, s, chunks, (a.n + F3D_ICP_CHUNK - 1) / F3D_ICP_CHUNK, (double*)nullptr, pose,
+                           lost, (double)min_pairs, stats, round, icp_solve_color<false>{});
+    }
+    F3D_TRY(hipGetLastError());
+    F3D_TRY(hipMemcpyAsync(pose_out, pose, 7 * sizeof(double), hipMemcpyDeviceToDevice, s));
+    if (status) F3D_TRY(hipMemcpyAsync(status, lost, sizeof(int32_t), hipMemcpyDeviceToDevice, s));
+    return hipSuccess;
 }

@@ -768,6 +768,19 @@ hipError_t f3d_launch_maps_half(const double* vertex, const double* normal, cons
 hipError_t f3d_launch_icp_levels(const f3d_icp_level* levels, int nlevels, double max_depth, const double q[4], const double t[3], const uint8_t* rgb,
                                  int hc, int wc_img, double color_weight, void* scratch, double* pose_out, double* stats, int32_t* status,
                                  hipStream_t s);
+// Cloud to cloud.  The source cloud [n, 3] of source_dtype, the target's built grid (f3d_launch_graph_grid) with its search, the target's
+// normals float64 [m, 3] in the caller's order (read in F3D_CLOUD_ICP_PLANE mode only) and the mode.  scratch: f3d_icp_scratch_bytes(n);
+// sums [29], pairs int32 [n] (may be NULL), pose_out, stats and status as for f3d_launch_icp.  n = 0 is fine: zero sums.
+struct f3d_cloud_icp_args {
+    const void* source; int source_dtype; int64_t n;
+    f3d_gridview gv; f3d_gridsearch gs;
+    const double* normals;
+    int mode;
+};
+hipError_t f3d_launch_cloud_icp_sums(const f3d_cloud_icp_args& a, const double q[4], const double t[3], void* scratch, double* sums, int32_t* pairs,
+                                     hipStream_t s);
+hipError_t f3d_launch_cloud_icp(const f3d_cloud_icp_args& a, const double q[4], const double t[3], int iterations, int min_pairs, void* scratch,
+                                double* pose_out, double* stats, int32_t* status, hipStream_t s);
 
 // plane table of a cloud over its adjacency (f3d_planes.hip).  Device pointers (counts int64 [4] too); normals (may be NULL: PCA of the
 // rows) and normals_out (may be NULL; written in PCA mode only) float64 [n, 3].  n >= 1.  Enqueues on `s` and synchronises it every few

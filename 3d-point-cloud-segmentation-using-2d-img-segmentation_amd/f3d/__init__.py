@@ -44,6 +44,7 @@ ICP_NSUMS_COLOR = 58         # F3D_ICP_NSUMS_COLOR: the 29 geometric sums, then 
 ICP_PIVOT_EPS = 1e-10        # F3D_ICP_PIVOT_EPS: the smallest Cholesky pivot, as a fraction of the largest diagonal entry
 ICP_OK, ICP_LOST = 0, 1      # status of an icp round (f3d.h F3D_ICP_*)
 ICP_MAX_LEVELS = 6           # F3D_ICP_MAX_LEVELS: the most levels of one icp_levels call
+CLOUD_ICP_PLANE, CLOUD_ICP_POINT = 0, 1   # mode of cloud_icp_sums / cloud_icp (f3d.h F3D_CLOUD_ICP_*)
 
 
 class IcpLevel(C.Structure):
@@ -285,6 +286,11 @@ def library():
         'f3d_maps_half_dev': (i32, [vp, vp, vp, vp, i32, i32, vp, dbl, vp, vp, vp, vp]),
         'f3d_icp_levels': (i32, [vp, vp, i32, dbl, vp, vp, vp, i32, i32, dbl, vp, vp, vp]),
         'f3d_icp_levels_dev': (i32, [vp, vp, i32, dbl, vp, vp, vp, i32, i32, dbl, vp, vp, vp, vp]),
+        'f3d_cloud_icp_sums': (i32, [vp, vp, i32, i64, vp, i32, i64, vp, i32, vp, vp, dbl, vp, vp]),
+        'f3d_cloud_icp_sums_dev': (i32, [vp, vp, i32, i64, vp, i32, i64, vp, i32, vp, vp, dbl, vp, vp, vp]),
+        'f3d_cloud_icp': (i32, [vp, vp, i32, i64, vp, i32, i64, vp, i32, vp, vp, dbl, i32, i32, vp, vp, vp]),
+        'f3d_cloud_icp_dev': (i32, [vp, vp, i32, i64, vp, i32, i64, vp, i32, vp, vp, dbl, i32, i32, vp, vp, vp, vp]),
+        'f3d_ctx_reserve_cloud_icp': (i32, [vp, i64, i64]),
     }
     for name, (res, args) in protos.items():
         fn = getattr(lib, name)          # AttributeError here = header/library mismatch
@@ -578,6 +584,54 @@ def _fill_level(rec, depth_ptr, depth_type, h, w, K, depth_scale, vertex_ptr, no
     rec.model_vertex, rec.model_normal, rec.model_intensity = vertex_ptr, normal_ptr, intensity_ptr
     rec.hm, rec.wm, rec.model_view = int(hm), int(wm), view_ptr
     rec.max_dist, rec.iterations, rec.min_pairs = float(max_dist), int(iterations), int(min_pairs)
+
+
+def _quat_matrix(q_wxyz):
+    """The rotation matrix float64 [3, 3] of a (not necessarily unit) quaternion; ValueError for a zero or non-finite one.  Host
+    bookkeeping of the cloud ICP callers (the centre folded into and out of t), no part of the contract's arithmetic."""
+    q = np.asarray(q_wxyz, np.float64).reshape(4)
+    norm = np.sqrt((q * q).sum())
+    if not (0.0 < norm < np.inf):
+        raise ValueError('the quaternion must be finite and not zero')
+    w, x, y, z = q / norm
+    return np.array([[1 - 2 * (y * y + z * z), 2 * (x * y - w * z), 2 * (x * z + w * y)],
+                     [2 * (x * y + w * z), 1 - 2 * (x * x + z * z), 2 * (y * z - w * x)],
+                     [2 * (x * z - w * y), 2 * (y * z + w * x), 1 - 2 * (x * x + y * y)]])
+
+
+def _cloud_icp_check(mode, has_normals, q_wxyz, t, max_dist, iterations=None, min_pairs=None):
+    """The numbers of a cloud_icp_sums / cloud_icp call as the C entry reads them -> (mode, q float64 [4], t float64 [3], max_dist), or
+    ValueError for what f3d.h refuses: an unknown mode, plane mode without normals, a max_dist that is not finite, positive and below
+    1e300, a zero or non-finite quaternion, a non-finite t, iterations < 1, min_pairs < 6."""
+    if mode not in (CLOUD_ICP_PLANE, CLOUD_ICP_POINT):
+        raise ValueError(f'mode must be CLOUD_ICP_PLANE or CLOUD_ICP_POINT, got {mode!r}')
+    if mode == CLOUD_ICP_PLANE and not has_normals:
+        raise ValueError('CLOUD_ICP_PLANE needs the normals of the target')
+    q, t, max_dist = _f64(q_wxyz, (4,)), _f64(t, (3,)), float(max_dist)
+    if not (0.0 < max_dist < 1e300):
+        raise ValueError(f'max_dist must be finite, positive and below 1e300, got {max_dist}')
+    if not (np.isfinite(q).all() and np.isfinite(t).all() and 0.0 < float(np.sqrt((q * q).sum())) < np.inf):
+        raise ValueError('the pose must be a finite non-zero quaternion and a finite translation')
+    if iterations is not None and int(iterations) < 1:
+        raise ValueError(f'iterations must be at least 1, got {iterations}')
+    if min_pairs is not None and int(min_pairs) < 6:
+        raise ValueError(f'min_pairs must be at least 6, got {min_pairs}')
+    return int(mode), q, t, max_dist
+
+
+def _cloud_icp_arrays(source, target, target_normals, mode):
+    """The host arrays of cloud_icp_sums / cloud_icp: (source [n, 3], its dtype code, target [m, 3], its dtype code, the normals float64
+    [m, 3] or None in point mode)."""
+    s, sdt = _xyz(source)
+    g, gdt = _xyz(target)
+    if len(g) == 0:
+        raise ValueError('the target is empty')
+    nrm = None
+    if mode == CLOUD_ICP_PLANE:
+        nrm = _f64(target_normals)
+        if nrm.shape != g.shape:
+            raise ValueError(f'the normals must be {g.shape} like the target, got {nrm.shape}')
+    return s, sdt, g, gdt, nrm
 
 
 def _knn_k(k):
@@ -1464,6 +1518,38 @@ class Context:
         self._check(self._lib.f3d_icp(self._h, _ptr(d), code, d.shape[0], d.shape[1], _ptr(K), float(depth_scale), float(max_depth), _ptr(q), _ptr(t),
                                       _ptr(mv), _ptr(mn), int(hm), int(wm), _ptr(view), float(max_dist), iterations, int(min_pairs), _ptr(pose),
                                       _ptr(stats), C.byref(status)))
+        return pose, stats, status.value
+
+    def reserve_cloud_icp(self, m, n):
+        """Size the scratch of the cloud_icp_sums_dev / cloud_icp_dev entries (f3d.clouds) for targets of up to m points and sources of
+        up to n points, at any max_dist."""
+        m, n = int(m), int(n)
+        if not (0 <= m < 2 ** 31 and 0 <= n < 2 ** 31):
+            raise ValueError(f'm and n must be in [0, 2^31), got {m} and {n}')
+        self._check(self._lib.f3d_ctx_reserve_cloud_icp(self._h, m, n))
+
+    def cloud_icp_sums(self, source, target, target_normals, mode, q_wxyz, t, max_dist, pairs=False):
+        """The 29 sums of one linearisation of cloud-to-cloud ICP (f3d.h f3d_cloud_icp_sums): source [n, 3] at the pose (q_wxyz, t), which
+        maps it into the frame of target [m, 3], each paired with its nearest target within max_dist; mode CLOUD_ICP_PLANE (against
+        target_normals float64 [m, 3]) or CLOUD_ICP_POINT (target_normals is not read) -> float64 [29], and with pairs=True
+        (sums, int32 [n]: the nearest target of every source point or -1)."""
+        mode, q, t, max_dist = _cloud_icp_check(mode, target_normals is not None, q_wxyz, t, max_dist)
+        s, sdt, g, gdt, nrm = _cloud_icp_arrays(source, target, target_normals, mode)
+        sums = np.empty(ICP_NSUMS)
+        out = np.empty(len(s), np.int32) if pairs else None
+        self._check(self._lib.f3d_cloud_icp_sums(self._h, _ptr(s), sdt, len(s), _ptr(g), gdt, len(g), _ptr(nrm), mode, _ptr(q), _ptr(t), max_dist,
+                                                 _ptr(sums), _ptr(out)))
+        return (sums, out) if pairs else sums
+
+    def cloud_icp(self, source, target, target_normals, mode, q_wxyz, t, max_dist, iterations=30, min_pairs=100):
+        """`iterations` rounds of cloud-to-cloud ICP on the device (f3d.h f3d_cloud_icp), the target's grid built once -> (pose float64
+        [7] = wxyz, t; stats float64 [iterations, 3] = count, sum r^2, status per round; the final status ICP_OK / ICP_LOST)."""
+        mode, q, t, max_dist = _cloud_icp_check(mode, target_normals is not None, q_wxyz, t, max_dist, iterations, min_pairs)
+        s, sdt, g, gdt, nrm = _cloud_icp_arrays(source, target, target_normals, mode)
+        iterations = int(iterations)
+        pose, stats, status = np.empty(7), np.empty((iterations, 3)), C.c_int32(0)
+        self._check(self._lib.f3d_cloud_icp(self._h, _ptr(s), sdt, len(s), _ptr(g), gdt, len(g), _ptr(nrm), mode, _ptr(q), _ptr(t), max_dist,
+                                            iterations, int(min_pairs), _ptr(pose), _ptr(stats), C.byref(status)))
         return pose, stats, status.value
 
     def reserve_icp_color(self, npixels):

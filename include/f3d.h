@@ -1555,6 +1555,54 @@ int f3d_icp_levels_dev(f3d_ctx* ctx, const f3d_icp_level* levels /*host records,
                        const double q_wxyz[4] /*host*/, const double t[3] /*host*/, const uint8_t* rgb, int hc, int wc_img,
                        double color_weight, double* pose, double* stats, int32_t* status /*device, may be NULL*/, void* stream);
 
+/* Cloud-to-cloud ICP: the alignment of an unordered source cloud to an unordered target cloud in another frame.  f3d_icp pairs a
+ * depth frame with model maps through a camera projection; here the partner of a source point is its nearest target point, found in
+ * the target's radius grid (the grid and the exact walk of f3d_knn_query).  The pose (q_wxyz, t) maps source coordinates into the
+ * target's frame.  All arithmetic is float64 without contraction, every operation rounded alone; dot, cross, rotate and the
+ * quaternion normalisation are those of f3d_icp; float32 inputs are widened exactly.
+ * f3d_cloud_icp_sums: one linearisation.  source [n, 3] of source_dtype, target [m, 3] of target_dtype, target_normals float64 [m, 3]
+ * (F3D_CLOUD_ICP_PLANE; not read and may be NULL in F3D_CLOUD_ICP_POINT), max_dist > 0.  Per source point i; a point that fails a step
+ * contributes 0.0 to every sum:
+ *   1. pr = rotate(qn, s_i); p = pr + t.
+ *   2. j = the target index that minimises (d2, j) lexicographically over the targets with d2 <= max_dist * max_dist, where
+ *      e = p - T_j and d2 = (e0*e0 + e1*e1) + e2*e2: the predicate, the bits and the tie rule (the lower index wins) of f3d_knn_query
+ *      with k = 1.  No such target: no pair.  pairs[i] = j or -1; it is written whenever a neighbour exists, also when step 3 then
+ *      rejects the pair.
+ *   3. F3D_CLOUD_ICP_PLANE: N = target_normals[j]; its three components must be finite, else no pair (the second nearest target is
+ *      not tried).  r = dot(N, e); J = (cross(pr, N), N); the 29 terms of f3d_icp step 7.
+ *   4. F3D_CLOUD_ICP_POINT: for a = 0, 1, 2 in that order N = the unit axis e_a, r = e[a], J = (cross(pr, e_a), e_a), and the 27
+ *      products of each a are added to the accumulators in that order; 1.0 is added to the count once per pair.  (The terms that are
+ *      +-0.0 by construction may be left out: no accumulator is ever -0.0.)
+ * The sums run over the source indices 0 .. n-1 in chunks of F3D_ICP_CHUNK with the lane, butterfly and chunk layout of f3d_icp_sums;
+ * no result depends on the launch shape, the cell order or thread timing.  Outputs: sums float64 [29]; pairs int32 [n] (may be NULL).
+ * f3d_cloud_icp: iterations >= 1 rounds of that with the solve, the update, the lost rule, the stats rows and the status of f3d_icp,
+ * unchanged; min_pairs >= 6 in both modes.  The increment rotates about t: a caller whose source lies far from its origin subtracts
+ * the source's mean first and folds it back into t.  The target's grid (cell edge a hair above max_dist) is built once per call, and
+ * there is one blocking readback per call (the target's box with the non-finite flag of the source); everything after it is
+ * enqueued, in the _dev entries with no further host synchronisation.  n == 0: zero sums, and every round of f3d_cloud_icp is lost.
+ * Scratch: the target's grid (as for f3d_knn_query), the chunk sums [ceil(n / 256), 29], the pose and the lost flag;
+ * f3d_ctx_reserve_cloud_icp(m, n) sizes it for any radius, and a strict context then allocates nothing in the _dev entries.
+ * F3D_ERR_INVALID, with nothing written: NULLs other than the optional outputs (source may be NULL when n == 0); PLANE mode without
+ * normals; an unknown mode or dtype; m == 0; n or m >= 2^31; NaN or infinity in the source or the target; max_dist not finite and
+ * positive, or >= 1e300; iterations < 1; min_pairs < 6; a zero or non-finite quaternion; a non-finite t. */
+#define F3D_CLOUD_ICP_PLANE 0
+#define F3D_CLOUD_ICP_POINT 1
+int f3d_cloud_icp_sums(f3d_ctx* ctx, const void* source, f3d_dtype source_dtype, int64_t n, const void* target, f3d_dtype target_dtype,
+                       int64_t m, const double* target_normals /*[m,3] or NULL*/, int mode, const double q_wxyz[4], const double t[3],
+                       double max_dist, double* sums /*[29]*/, int32_t* pairs /*[n] or NULL*/);
+int f3d_cloud_icp_sums_dev(f3d_ctx* ctx, const void* source, f3d_dtype source_dtype, int64_t n, const void* target,
+                           f3d_dtype target_dtype, int64_t m, const double* target_normals, int mode, const double q_wxyz[4] /*host*/,
+                           const double t[3] /*host*/, double max_dist, double* sums, int32_t* pairs, void* stream);
+int f3d_cloud_icp(f3d_ctx* ctx, const void* source, f3d_dtype source_dtype, int64_t n, const void* target, f3d_dtype target_dtype,
+                  int64_t m, const double* target_normals /*[m,3] or NULL*/, int mode, const double q_wxyz[4], const double t[3],
+                  double max_dist, int iterations, int min_pairs, double* pose /*[7]*/, double* stats /*[iterations,3]*/,
+                  int32_t* status);
+int f3d_cloud_icp_dev(f3d_ctx* ctx, const void* source, f3d_dtype source_dtype, int64_t n, const void* target, f3d_dtype target_dtype,
+                      int64_t m, const double* target_normals, int mode, const double q_wxyz[4] /*host*/, const double t[3] /*host*/,
+                      double max_dist, int iterations, int min_pairs, double* pose, double* stats,
+                      int32_t* status /*device, may be NULL*/, void* stream);
+int f3d_ctx_reserve_cloud_icp(f3d_ctx* ctx, int64_t m, int64_t n);
+
 #ifdef __cplusplus
 }
 #endif
